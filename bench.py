@@ -91,6 +91,8 @@ def _worker_cmd(args, extra=()):
         cmd.append("--no-cpu-baseline")
     if args.dry_run:
         cmd.append("--dry-run")
+    if args.dump_outputs:
+        cmd += ["--dump-outputs", args.dump_outputs]
     return cmd + list(extra)
 
 
@@ -298,6 +300,26 @@ def cpu_baseline(host, threads, budget_s=12.0, frame=None, gpu_cam=None, dev=Non
     }, st
 
 
+DUMP_BYTES = 64_000_000      # --dump-outputs: cap on what one run writes
+
+
+def dump_outputs(directory, frame):
+    """--dump-outputs: the frame the last timed step computed, as DIR/frame.npy (float32, rows x columns x RGB).  A frame larger
+    than DUMP_BYTES (the c5 workload) is written as DIR/frame_sample.npy instead: the pixels at a fixed, seeded set of positions,
+    in row-major order, so that two builds given the same arguments can be compared output for output."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    frame = np.ascontiguousarray(frame, dtype=np.float32)
+    if frame.nbytes <= DUMP_BYTES:
+        np.save(os.path.join(directory, "frame.npy"), frame)
+        return ["frame.npy"]
+    pixels = frame.reshape(-1, frame.shape[-1])
+    keep = (DUMP_BYTES - 4096) // pixels[0].nbytes                  # (room for the .npy header)
+    idx = np.sort(np.random.default_rng(20261015).choice(pixels.shape[0], keep, replace=False))
+    np.save(os.path.join(directory, "frame_sample.npy"), pixels[idx])
+    return ["frame_sample.npy"]
+
+
 def dry_run_worker(args, world, rank):
     """No GPU: the N-rank control flow only (rendezvous, band arithmetic, one gather, world-size check).
     Every rank fills its rows with a function of (row, column) and rank 0 checks the assembled frame.
@@ -424,6 +446,8 @@ def worker(args):
         t = torch.tensor([elapsed], dtype=torch.float64, device=f"cuda:{local_rank}" if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    # the last timed step's frame, copied out before anything below renders into the same buffer again
+    dumped = dump_outputs(args.dump_outputs, frame.detach().cpu().numpy()) if args.dump_outputs and rank == 0 and frame is not None else None
 
     # ---- second clock: what the reference's own timer brackets besides the kernel — the copy of the float
     # frame to the host (src/camera.cu:333-343 times render_kernel + cudaMemcpy D2H + the saver loop); never `value`
@@ -462,6 +486,8 @@ def worker(args):
                        "wide_nodes": bool(last_t[0] is not None and last_t[0].wide_nodes),
                        "view_lists_reused_between_steps": False},
         }
+        if args.dump_outputs:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "files": dumped}
         base, st = (None, None)
         if world > 1 and os.environ.get("RTP_BENCH_CHECK"):
             import oracle_bindings as ob       # rehearsal only: the assembled frame against the checker
@@ -539,12 +565,19 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pmc", action="store_true", help="launcher, N = 1: skip the rocprofv3 counter passes")
     ap.add_argument("--pmc-timeout", type=int, default=240)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the frame of the last one as DIR/frame.npy (float32; a seeded sample of "
+                         "its pixels as DIR/frame_sample.npy where the frame exceeds 64 MB)")
     ap.add_argument("--dry-run", action="store_true",
                     help="no GPU: rehearse the N-rank launch + gather over gloo; prints a line without a measurement")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 and not args.dry_run:
+        raise SystemExit("--steps must be >= 1: ms_per_step is the time of one timed step")
     set_workload(args.workload)
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
     if args.spp <= 0:
         args.spp = SPP
     if "WORLD_SIZE" in os.environ:

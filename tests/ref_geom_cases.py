@@ -6,6 +6,7 @@ bvh, bvh_builder) compiled from where they lie, build container only — and `Or
 comparison is `same_bits(ref[k], orc[k])` key by key.
 """
 import ctypes as C
+import hashlib
 import os
 
 import numpy as np
@@ -118,6 +119,47 @@ def scene_cases(rng, n_spheres, n_planes, n_rays, spread=6.0):
     target = rng.uniform(-spread, spread, (n_rays, 3)).astype(np.float32)
     d = (target - o).astype(np.float32)
     return f32(sph), f32(pl), types, f32(o), f32(d)
+
+
+# The comparisons tests/test_ref_geom.py makes (and tests/golden/make_ref_geom_golden.py records the reference's side of).
+CHEAP = ("aabb_hit", "div", "unit", "reflect", "refract", "near_zero", "dot", "cross", "len", "contains", "ray_at", "face_normal", "front")
+SCENES = ((1, 0), (0, 1), (2, 0), (37, 0), (500, 0), (0, 40), (120, 60), (1500, 200), (5000, 0))
+
+
+def primitive_runs():
+    """(name, cases, keys compared): a quarter of a million cases with every output, then the cheap operators on three more
+    batches — a million items in all.  keys None: every output."""
+    yield "primitives", primitive_cases(np.random.default_rng(20260), 250_000), None
+    for seed in (1, 2, 3):
+        yield f"batch {seed}", primitive_cases(np.random.default_rng(seed), 250_000), CHEAP
+
+
+def scene_runs():
+    """(name, (spheres, planes), scene_cases(...)) with 60 000 rays per scene."""
+    rng = np.random.default_rng(4711)
+    for ns, npl in SCENES:
+        yield f"{ns} spheres, {npl} planes", (ns, npl), scene_cases(rng, ns, npl, 60_000)
+
+
+def hit_key(key):
+    """The hit flags that say which items of output `key` are records (records exist for hits only), or None."""
+    if key.startswith("rec_") or key == "rec" or key.startswith("code"):
+        return "hit" + key[key.index("_"):] if "_" in key else "hit"
+    return None
+
+
+def digests(out, keys=None):
+    """sha256 per output, in the terms of `differing`: records only where there is a hit, every NaN alike."""
+    d = {}
+    for key in (out if keys is None else keys):
+        a = np.ascontiguousarray(out[key])
+        if hit_key(key):
+            a = np.ascontiguousarray(a[out[hit_key(key)] != 0])
+        if a.dtype == np.float32:
+            a = a.copy()
+            a[np.isnan(a)] = np.float32(np.nan)
+        d[key] = hashlib.sha256(f"{a.dtype.str}{a.shape}".encode() + a.tobytes()).hexdigest()
+    return d
 
 
 def _p(a):
