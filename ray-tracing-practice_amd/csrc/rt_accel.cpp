@@ -898,4 +898,61 @@ std::string pack_scene(const rt_scene_desc &d, TreeMode mode, Packed &out, const
     return pk.primitive_tables();
 }
 
+bool make_magic(uint32_t d, uint64_t n_max, Magic &g) {
+    if (d == 0) return false;
+    if (d == 1) { g.m = 0; g.s = 0; return true; }
+    uint32_t lg = 0;
+    while (((uint64_t)2 << lg) <= d) ++lg;           // floor(log2 d) (64-bit: d may be 2^31 or more)
+    g.s = 31 + lg;
+    const uint64_t mm = ((uint64_t)1 << g.s) / d + 1;
+    if (mm >> 32) return false;
+    g.m = (uint32_t)mm;
+    // n*m/2^s - n/d = n * (m*d - 2^s) / (d * 2^s) <= n * d / (d * 2^s): the floor is exact while n * d < 2^s
+    return n_max * (uint64_t)d < ((uint64_t)1 << g.s);
+}
+
+int32_t PassPlan::first(int32_t p) const { return p * pass_size - (p > long_passes ? p - long_passes : 0); }
+
+int32_t PassPlan::count(int32_t p) const {
+    const int32_t c = pass_size - (p >= long_passes ? 1 : 0), left = spp - first(p);
+    return c < left ? c : left;
+}
+
+PassPlan PassPlan::uniform(int32_t spp, int32_t pass_size) {
+    PassPlan pl;
+    pl.spp = spp;
+    pl.pass_size = pass_size;
+    pl.passes = pl.long_passes = (spp + pass_size - 1) / pass_size;
+    return pl;
+}
+
+PassPlan plan_passes(uint64_t num_pixels, int32_t spp, uint64_t workspace_bytes, uint64_t device_bytes, int32_t forced_pass_spp) {
+    // the hard bound: num_pixels * pass + 64 <= 2^30 (every work index of the pass, and the margin behind it)
+    const uint64_t index_fit = num_pixels ? (kWorkIndexLimit - kWorkIndexMargin) / num_pixels : 0;
+    if (index_fit < 1 || spp < 1) return PassPlan{};
+    if (forced_pass_spp > 0) {
+        uint64_t size = (uint64_t)(forced_pass_spp < spp ? forced_pass_spp : spp);
+        if (size > index_fit) size = index_fit;
+        return PassPlan::uniform(spp, (int32_t)size);
+    }
+    // as many samples as the workspace budget admits, in whole 128-byte slab lines, at least 64 (a speed preference that
+    // gives way to the bound: at 2^24 pixels a pass holds 63 samples)
+    const uint64_t budget = workspace_bytes ? workspace_bytes : device_bytes / kWorkspaceShareOfDevice;
+    uint64_t fit = budget / (num_pixels * kSampleBytes);
+    fit &= ~(uint64_t)31;
+    if (fit < 64) fit = 64;
+    if (fit > index_fit) fit = index_fit;
+    if ((uint64_t)spp <= fit) return PassPlan::uniform(spp, spp);
+    // the fewest passes of at most `fit`, then the samples spread over them: pass lengths differ by at most one
+    int32_t passes = (int32_t)((spp + fit - 1) / fit);
+    const int32_t size = (spp + passes - 1) / passes;
+    passes = (spp + size - 1) / size;                 // (never more passes than that size needs)
+    PassPlan pl;
+    pl.spp = spp;
+    pl.passes = passes;
+    pl.pass_size = (spp + passes - 1) / passes;
+    pl.long_passes = spp - passes * (pl.pass_size - 1);
+    return pl;
+}
+
 }  // namespace rtaccel

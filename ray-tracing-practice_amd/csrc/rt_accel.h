@@ -128,4 +128,39 @@ uint16_t float_to_half_dir(float f, bool toward_minus_inf);
 std::string pack_scene(const rt_scene_desc &desc, TreeMode mode, Packed &out, const PackOptions &opt = PackOptions(),
                        const float *camera_hint = nullptr);
 
+// ---- pass sizing of rt_render (pure host arithmetic, checked over a grid by tests/cpu_native/test_accel.cpp) ----
+
+// n / d as (n * m) >> s with m = floor(2^s / d) + 1, s = 31 + floor(log2 d); m == 0 encodes d == 1 (the kernel's div_magic)
+struct Magic { uint32_t m, s; };
+// The reciprocal of d, exact for every n <= n_max (checked, not assumed); false when no (m, s) of this form is.  Every
+// n_max <= 2^30 is accepted (n_max * d < 2^30 * 2^(floor(log2 d) + 1) = 2^s).
+bool make_magic(uint32_t d, uint64_t n_max, Magic &g);
+
+// The work index of a pass, pixel * pass_count + slot, and the 64 indices behind the last one stay below 2^30: the kernel's
+// div_magic, the flagged-list hole marker kFlagHole and the dry counter of an abandoned pass (kAbandonedCounter = 2^30)
+// rely on it (rt_kernel.hip.inc).  A pass has at least one sample, so a call with more than kWorkIndexLimit - 64 pixels
+// cannot meet the bound; rt_render takes at most kMaxCallPixels (2^24) pixels per call and never asks.
+constexpr uint64_t kWorkIndexLimit = (uint64_t)1 << 30;
+constexpr uint64_t kWorkIndexMargin = 64;
+constexpr uint64_t kMaxCallPixels = (uint64_t)1 << 24;
+constexpr int kMaxPasses = 1024;            // counter words per pass in a scene handle (rt_capi.hip, kQueue*)
+constexpr uint64_t kSampleBytes = 12;       // one radiance record of the slab
+constexpr uint64_t kWorkspaceShareOfDevice = 16;    // rt_config.workspace_bytes == 0: a sixteenth of the device's memory
+
+// Samples [first(p), first(p) + count(p)) of every pixel are traced by pass p.  Automatic plans are balanced: the first
+// `long_passes` passes have pass_size samples and the others pass_size - 1.  A forced pass size (rt_config.pass_spp) or
+// the out-of-memory fallback of rt_render gives passes of pass_size with a short last one (long_passes == passes).
+struct PassPlan {
+    int32_t spp = 0, pass_size = 0, passes = 0, long_passes = 0;
+    int32_t first(int32_t p) const;
+    int32_t count(int32_t p) const;
+    static PassPlan uniform(int32_t spp, int32_t pass_size);
+};
+
+// The passes of a call of num_pixels local pixels at spp samples: as long as the workspace budget admits (workspace_bytes,
+// or a sixteenth of device_bytes when 0; at least 64 samples where the bound allows it), never past the work-index bound,
+// then made equally long.  forced_pass_spp > 0 asks for that size, clamped to spp and to the bound.  passes == 0 when
+// num_pixels is 0 or above kWorkIndexLimit - 64, or spp < 1; the caller checks passes <= kMaxPasses.
+PassPlan plan_passes(uint64_t num_pixels, int32_t spp, uint64_t workspace_bytes, uint64_t device_bytes, int32_t forced_pass_spp);
+
 }  // namespace rtaccel

@@ -58,11 +58,11 @@ int env_int(const char *name, int fallback) {
 #ifndef RTP_BY_PIXEL_MIN
 #define RTP_BY_PIXEL_MIN 96         /* samples per pixel and pass from which the primary-visibility pass takes a wave per PIXEL (configs[4], passes of 125: 10.6 instead of 11.9 ms; S-rtiow at 100 spp: 1.84 vs 1.91) */
 #endif
-constexpr uint64_t kWorkspaceShareOfDevice = 16;
-constexpr uint64_t kSampleBytes = 12;        // one radiance record of the slab
+using rtaccel::kWorkspaceShareOfDevice;
+using rtaccel::kSampleBytes;
 
 constexpr uint32_t kLdsLimit = 160 * 1024;
-constexpr int kMaxPasses = 1024;        // >= 64 samples per pass
+using rtaccel::kMaxPasses;               // (rt_accel.h: plan_passes)
 constexpr int kTimedPasses = 64;        // trace launches individually timed per call
 
 // Counter block of a scene handle (uint32 words): work counters of the trace launches, of the exact
@@ -273,19 +273,7 @@ rt_status upload(const std::vector<T> &host, void **dev) {
     return RT_OK;
 }
 
-// Reciprocal for div_magic(): exact quotients for every n <= n_max (checked, not assumed).
-bool make_magic(uint32_t d, uint64_t n_max, rtk::Magic &g) {
-    if (d == 0) return false;
-    if (d == 1) { g.m = 0; g.s = 0; return true; }
-    uint32_t lg = 0;
-    while ((2u << lg) <= d) ++lg;                     // floor(log2 d)
-    g.s = 31 + lg;
-    const uint64_t mm = ((uint64_t)1 << g.s) / d + 1;
-    if (mm >> 32) return false;
-    g.m = (uint32_t)mm;
-    // n*m/2^s - n/d = n * (m*d - 2^s) / (d * 2^s) <= n * d / (d * 2^s): the floor is exact while n * d < 2^s
-    return n_max * (uint64_t)d < ((uint64_t)1 << g.s);
-}
+using rtaccel::make_magic;
 
 void normalise_shard(const rt_shard *in, int32_t height, rt_shard &out) {
     if (!in || in->num_parts <= 1 || in->band_rows <= 0) {
@@ -982,31 +970,19 @@ rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *s
 #endif
     if (use_queue) guarded = false;
 
-    // Samples per pass: as many as the workspace budget admits (rt_config.workspace_bytes, default just under 4 GiB;
-    // 12 bytes per sample), at least 64, and few enough for the 32-bit work index and its reciprocal-multiply
-    // division; the passes of a frame are made equally long.
+    // Samples per pass (rt_accel.h, plan_passes): as many as the workspace budget admits (rt_config.workspace_bytes, default a
+    // sixteenth of the device; 12 bytes per sample), at least 64 where the work-index bound allows, and never more than the
+    // bound num_pixels * pass + 64 <= 2^30 of the kernel's 32-bit work index (div_magic, kFlagHole, kAbandonedCounter) —
+    // a forced rt_config.pass_spp included; the passes of a frame are made equally long.
     // Fewer, larger launches amortise the end-of-launch tail — on a row shard of an N-GPU frame
     // the pass grows N-fold, so a launch keeps the size it has on one GPU.
     const uint32_t num_pixels = (uint32_t)P.local_rows * (uint32_t)P.row_w;
-    int pass_size = P.spp;
     // rows of the slab start on 128-byte lines (32 slots x 12 B = 3 lines) — except for passes shorter than that, whose rows are
     // only padded to the 16 bytes the accumulate kernel's row reads need (a 4K frame at 1 spp: 0.4 GB instead of 3.2 GB)
     auto pitch_of = [](int pass) { return pass < 32 ? (uint32_t)((pass + 3) & ~3) : (uint32_t)((pass + 31) & ~31); };
-    {
-        const uint64_t budget = cfg.workspace_bytes ? cfg.workspace_bytes : sc->device_bytes / kWorkspaceShareOfDevice;
-        uint64_t fit = budget / ((uint64_t)num_pixels * kSampleBytes);
-        fit &= ~(uint64_t)31;
-        const uint64_t index_fit = (((uint64_t)1 << 30) - 64) / num_pixels;     // total_work + 64 <= 2^30
-        if (fit > index_fit) fit = index_fit;
-        if (fit < 64) fit = 64;
-        if ((uint64_t)pass_size > fit) {
-            const int passes_wanted = (int)((P.spp + fit - 1) / fit);
-            pass_size = (P.spp + passes_wanted - 1) / passes_wanted;
-        }
-        if (const int forced = cfg.pass_spp) pass_size = forced < P.spp ? forced : P.spp;
-        rtk::Magic probe;
-        while (pass_size > 64 && !make_magic((uint32_t)pass_size, (uint64_t)num_pixels * pass_size + 64, probe)) --pass_size;
-    }
+    rtaccel::PassPlan plan = rtaccel::plan_passes(num_pixels, P.spp, cfg.workspace_bytes, sc->device_bytes, cfg.pass_spp);
+    if (plan.passes < 1) return fail(RT_ERR_UNSUPPORTED, "image too large for the work index arithmetic");
+    int pass_size = plan.pass_size;
     // workspace: three floats per (local pixel, slot)
     size_t need = (size_t)num_pixels * (size_t)pitch_of(pass_size) * 3;
     if (sc->slab_floats < need) {
@@ -1020,14 +996,15 @@ rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *s
             (void)hipGetLastError();
             if (e != hipErrorOutOfMemory || pass_size <= 64) HIP_TRY(e);
             pass_size = pass_size / 2 < 64 ? 64 : pass_size / 2;
+            plan = rtaccel::PassPlan::uniform(P.spp, pass_size);      // (shorter than before: within the bound too)
             need = (size_t)num_pixels * (size_t)pitch_of(pass_size) * 3;
         }
         sc->slab_floats = need;
     }
     P.slab = sc->slab;
     P.num_pixels = num_pixels;
-    const int passes = (P.spp + pass_size - 1) / pass_size;
-    if (passes > kMaxPasses) return fail(RT_ERR_UNSUPPORTED, "samples_per_pixel above 65536");
+    const int passes = plan.passes;
+    if (passes > kMaxPasses) return fail(RT_ERR_UNSUPPORTED, "more than 1024 passes (samples_per_pixel above 65536, or above 64512 at 2^24 pixels)");
     if (guarded) {
         // flagged-sample list: a quarter of a pass's samples (a fuller list means "re-walk everything")
         const size_t cap = (size_t)num_pixels * (size_t)pass_size / 4 + 65536;
@@ -1251,8 +1228,8 @@ rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *s
         // samples [pass_first, pass_first + pass_count) of every pixel, traced in any order into the slab …
         const bool timed_pass = pass < kTimedPasses;
         if (timed_pass) HIP_TRY(hipEventRecord(sc->pass_events[4 * pass], stream));
-        P.pass_first = pass * pass_size;
-        P.pass_count = P.spp - P.pass_first < pass_size ? P.spp - P.pass_first : pass_size;
+        P.pass_first = plan.first(pass);
+        P.pass_count = plan.count(pass);
         P.total_work = num_pixels * (uint32_t)P.pass_count;      // work index = pixel * pass_count + slot
         P.slab_pitch = pitch_of(pass_size);
         if ((uint64_t)num_pixels * (uint64_t)P.pass_count >= (1ull << 31) - 4096 || !make_magic((uint32_t)P.pass_count, (uint64_t)P.total_work + 64, P.magic_count))

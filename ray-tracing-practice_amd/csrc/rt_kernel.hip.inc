@@ -108,7 +108,7 @@ constexpr int kBlock = RTP_BLOCK;            // threads per workgroup; RTP_MIN_W
 constexpr int kSimpleBlock = 1024;
 constexpr int kSimpleWaves = 8;
 
-struct Magic { uint32_t m, s; };
+using Magic = rtaccel::Magic;         // (rt_accel.h: make_magic)
 
 struct KParams {
     // CameraData (include/camera.cuh:86-95)
@@ -1284,7 +1284,8 @@ __device__ __forceinline__ void start_sample(Lane &L, const KParams &P, int32_t 
 }
 
 // n / d with a host-made reciprocal: m = floor(2^s / d) + 1, s = 31 + floor(log2 d), packed as
-// (m, s).  Exact for n < 2^30 (n * d < 2^s, checked on the host in make_magic); two multiplies
+// (m, s).  Exact for n < 2^30 (n * d < 2^s, checked on the host in make_magic; rt_accel.h, plan_passes keeps every work
+// index of a pass and the 64 behind it below 2^30); two multiplies
 // instead of the ~25-instruction integer division.  m == 0 encodes d == 1.
 __device__ __forceinline__ uint32_t div_magic(uint32_t n, Magic g) {
     return g.m ? (uint32_t)(((uint64_t)n * (uint64_t)g.m) >> g.s) : n;

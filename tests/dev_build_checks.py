@@ -35,6 +35,25 @@ def test_this_is_the_developer_library():
     assert b"dev=1" in v and b"parity=1" in v
 
 
+def test_wide_nodes_keep_the_pinned_default_config_frame():
+    """The default-config frame 7 (polyhedra, 1080x720x2500, two passes) through a fresh default handle with the 4-wide node
+    walk: every band of 8 rows is the oracle-made pin of tests/golden/frame_pins.json."""
+    import sys
+    sys.path.insert(0, os.path.join(HERE, "golden"))
+    import json
+    import make_frame_pins as mfp
+    pins = json.load(open(os.path.join(HERE, "golden", "frame_pins.json")))
+    pin = pins["frames"]["default7"]
+    host, cam = mfp.scene_and_camera(pin["scene"], pin["camera"])
+    dev = rb.DeviceScene(host, device=0, honour_env=False, traversal=rb.TRAVERSAL_AUTO, guard_keep=0, wide_nodes=1)
+    fb, t = dev.render_to_host(cam)
+    dev.close()
+    assert t.guarded == 1 and t.wide_nodes == 1, (t.guarded, t.wide_nodes)
+    band = pins["band_rows"]
+    bad = [r for r in range(0, pin["height"], band) if mfp.band_digest(fb[r:r + band]) != pin["band_sha256_16"][r // band]]
+    assert not bad, f"wide nodes: {len(bad)} bands of {band} rows differ from the pin, first rows {bad[:12]}"
+
+
 def test_wavefront_kernel_gives_the_same_frames():
     """rt_config.kernel = RT_KERNEL_WAVEFRONT (rt_kernel_wf.hip.inc: a wave owns a pool of paths in wave-private L2-resident
     stacks and alternates dense SHADE / GENERATE / EXCHANGE / TRACE steps) — same bits as the oracle: S-rtiow at several

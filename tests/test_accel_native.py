@@ -21,6 +21,22 @@ def test_accel_tables_under_sanitizers(tmp_path):
     assert "all ok" in out.stdout
 
 
+def test_pass_sizing_keeps_the_work_index_bound(tmp_path):
+    """rt_render's pass sizing (csrc/rt_accel.cpp: plan_passes, make_magic) under AddressSanitizer + UBSan: make_magic against
+    integer division for every divisor up to 65536 (at 0, d - 1, d, k*d +- 1 near the top and at the largest accepted n) and
+    1e6 random pairs, through both of the kernel's division forms; and over a grid of frames and row shards (1 pixel to
+    2^24), spp, forced pass sizes and workspace budgets, every pass keeps pixels * pass + 64 <= 2^30 — the bound the kernel's
+    div_magic, kFlagHole and kAbandonedCounter rely on, which 2^24 pixels at 64 spp and a forced pass_spp of 300 at 3840x2160
+    used to break — and the passes cover the samples in order, automatic ones equally long."""
+    exe = str(tmp_path / "test_pass_plan")
+    srcs = [os.path.join(ROOT, "tests", "cpu_native", "test_pass_plan.cpp"), os.path.join(PKG, "csrc", "rt_accel.cpp")]
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                    "-ffp-contract=off", "-o", exe] + srcs, check=True)
+    out = subprocess.run([exe], capture_output=True, text=True, env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "all ok" in out.stdout and "plan_passes: 5712 cases" in out.stdout, out.stdout
+
+
 def test_margin_budget_against_adversarial_rays(tmp_path):
     """The error budget behind the guarded walk's margins (gamma = 24 ulp of |oc|^2 |d|^2 in hit_sphere's discriminant,
     docs/LOG.md §3b): 400 k rays aimed at and around the silhouettes of tiny spheres from up to 2 000 units away — where

@@ -118,93 +118,6 @@ def test_rtiow_c2_rows_at_full_width(rtiow):
         assert_same_frame(fb[row0:row0 + 20], want, f"rows {row0}..")
 
 
-def test_rtiow_probe_at_headline_config(rtiow):
-    host, dev = rtiow
-    g = np.load(os.path.join(HERE, "golden", "rtiow_probe.npz"))
-    cam = rb.rtiow_camera(1920, 1080, 500, 50)
-    rad, rays, seeds = dev.trace_samples(cam, g["ijs"])
-    assert np.array_equal(bits(rad), g["rad_bits"])
-    assert np.array_equal(rays, g["rays"]) and np.array_equal(seeds, g["seeds"])
-    assert rays.max() > 20        # deep paths are exercised
-
-
-def test_rtiow_small_frame_matches_golden(rtiow):
-    host, dev = rtiow
-    g = np.load(os.path.join(HERE, "golden", "rtiow_probe.npz"))
-    fb, t = dev.render_to_host(rb.rtiow_camera(96, 64, 4, 50))
-    assert np.array_equal(bits(fb), g["fb_bits"])
-    assert t.scene_in_lds == 1 and t.kernel_ms > 0
-
-
-def test_rtiow_c2_rows_at_full_width(rtiow):
-    """BASELINE configs[1] geometry (1200x800, depth 50) at 6 spp: every pixel of the GPU frame
-    equals the oracle's, checked on three row bands the oracle finishes in seconds."""
-    host, dev = rtiow
-    cam = rb.rtiow_camera(1200, 800, 6, 50)
-    fb, _ = dev.render_to_host(cam)
-    for row0 in (0, 396, 780):
-        want = ob.render(host, cam, row0=row0, row1=row0 + 20, threads=8)
-        assert_same_frame(fb[row0:row0 + 20], want, f"rows {row0}..")
-
-
-def test_rtiow_probe_at_headline_config(rtiow):
-    host, dev = rtiow
-    g = np.load(os.path.join(HERE, "golden", "rtiow_probe.npz"))
-    cam = rb.rtiow_camera(1920, 1080, 500, 50)
-    rad, rays, seeds = dev.trace_samples(cam, g["ijs"])
-    assert np.array_equal(bits(rad), g["rad_bits"])
-    assert np.array_equal(rays, g["rays"]) and np.array_equal(seeds, g["seeds"])
-    assert rays.max() > 20        # deep paths are exercised
-
-
-def test_rtiow_small_frame_matches_golden(rtiow):
-    host, dev = rtiow
-    g = np.load(os.path.join(HERE, "golden", "rtiow_probe.npz"))
-    fb, t = dev.render_to_host(rb.rtiow_camera(96, 64, 4, 50))
-    assert np.array_equal(bits(fb), g["fb_bits"])
-    assert t.scene_in_lds == 1 and t.kernel_ms > 0
-
-
-def test_rtiow_c2_rows_at_full_width(rtiow):
-    """BASELINE configs[1] geometry (1200x800, depth 50) at 6 spp: every pixel of the GPU frame
-    equals the oracle's, checked on three row bands the oracle finishes in seconds."""
-    host, dev = rtiow
-    cam = rb.rtiow_camera(1200, 800, 6, 50)
-    fb, _ = dev.render_to_host(cam)
-    for row0 in (0, 396, 780):
-        want = ob.render(host, cam, row0=row0, row1=row0 + 20, threads=8)
-        assert_same_frame(fb[row0:row0 + 20], want, f"rows {row0}..")
-
-
-def test_rtiow_probe_at_headline_config(rtiow):
-    host, dev = rtiow
-    g = np.load(os.path.join(HERE, "golden", "rtiow_probe.npz"))
-    cam = rb.rtiow_camera(1920, 1080, 500, 50)
-    rad, rays, seeds = dev.trace_samples(cam, g["ijs"])
-    assert np.array_equal(bits(rad), g["rad_bits"])
-    assert np.array_equal(rays, g["rays"]) and np.array_equal(seeds, g["seeds"])
-    assert rays.max() > 20        # deep paths are exercised
-
-
-def test_rtiow_small_frame_matches_golden(rtiow):
-    host, dev = rtiow
-    g = np.load(os.path.join(HERE, "golden", "rtiow_probe.npz"))
-    fb, t = dev.render_to_host(rb.rtiow_camera(96, 64, 4, 50))
-    assert np.array_equal(bits(fb), g["fb_bits"])
-    assert t.scene_in_lds == 1 and t.kernel_ms > 0
-
-
-def test_rtiow_c2_rows_at_full_width(rtiow):
-    """BASELINE configs[1] geometry (1200x800, depth 50) at 6 spp: every pixel of the GPU frame
-    equals the oracle's, checked on three row bands the oracle finishes in seconds."""
-    host, dev = rtiow
-    cam = rb.rtiow_camera(1200, 800, 6, 50)
-    fb, _ = dev.render_to_host(cam)
-    for row0 in (0, 396, 780):
-        want = ob.render(host, cam, row0=row0, row1=row0 + 20, threads=8)
-        assert_same_frame(fb[row0:row0 + 20], want, f"rows {row0}..")
-
-
 def test_production_kernel_at_the_headline_config():
     """BASELINE configs[2] — 1920x1080, 500 spp, 50 bounces — through the DEFAULT path of a fresh handle: ONE launch of the
     sphere-only trace kernel fed by the primary-visibility pass (render_kernel, src/camera.cu:17-34), three rows of the frame
