@@ -202,7 +202,8 @@ std::string build_lbvh(const float *leaf_boxes, const int32_t *leaf_codes, int32
         std::vector<int32_t> big;
         for (int32_t i = 0; i < n; ++i)
             if (extent_of(i) > 0.25f * scene_extent) big.push_back(i);
-        std::sort(big.begin(), big.end(), [&](int32_t a, int32_t b) { return extent_of(a) > extent_of(b); });
+        // stable: equal extents keep their leaf order, so the tree is a function of the leaves alone (tests/lbvh_reference.py)
+        std::stable_sort(big.begin(), big.end(), [&](int32_t a, int32_t b) { return extent_of(a) > extent_of(b); });
         if ((int)big.size() > kMaxLarge) big.resize(kMaxLarge);
         if ((int32_t)big.size() < n) {
             std::vector<char> is_big((size_t)n, 0);

@@ -1599,6 +1599,51 @@ rt_status rt_debug_check_fast_math(uint64_t out[3]) {
     return RT_OK;
 }
 
+// Developer hooks (not part of the ABI header): the device LBVH builder (rt_build.hip) on its own, for the node-by-node check
+// against a host reference (tests/dev_tree_checks.py, tests/lbvh_reference.py).
+// rt_debug_guard_leaves: the inflated leaf boxes (6 floats each) and leaf codes a handle with tree_build = RT_BUILD_DEVICE_LBVH
+// hands to build_lbvh for this scene and config.  *n_inout: capacity of the buffers in leaves (ignored when both are null), on
+// return the number of leaves.  Fails when the scene is not eligible for the guarded walk (nothing would be built).
+rt_status rt_debug_guard_leaves(const rt_scene_desc *d, const rt_config *cfg, float *boxes, int32_t *codes, int32_t *n_inout) {
+    if (!d || !n_inout) return fail(RT_ERR_INVALID_ARG, "null argument");
+    const rt_config c = config_from_caller(cfg);
+    rtaccel::Packed pk;
+    const std::string err = rtaccel::pack_scene(*d, rtaccel::TreeMode::GuardedLeaves, pk, pack_options(c, d));
+    if (!err.empty()) return fail(RT_ERR_INVALID_ARG, err);
+    if (!pk.guard.ok) return fail(RT_ERR_INVALID_ARG, "not eligible for the guarded walk: " + pk.guard.reason);
+    const int32_t n = (int32_t)pk.guard_leaf_codes.size();
+    if (boxes || codes) {
+        if (!boxes || !codes || *n_inout < n) return fail(RT_ERR_INVALID_ARG, "leaf buffers missing or too small");
+        std::memcpy(boxes, pk.guard_leaf_boxes.data(), sizeof(float) * 6 * (size_t)n);
+        std::memcpy(codes, pk.guard_leaf_codes.data(), sizeof(int32_t) * (size_t)n);
+    }
+    *n_inout = n;
+    return RT_OK;
+}
+
+// rt_debug_build_lbvh: build_lbvh on the caller's n leaves; copies the num_internal fp32 pair records (16 floats each) to
+// nodes_out and the binary16 ones (8 floats each) to hnodes_out — both with room for n - 1 records — and sets
+// info = {root, num_internal, depth, 0}.  The device tree is freed; nothing is rendered.
+rt_status rt_debug_build_lbvh(const float *boxes, const int32_t *codes, int32_t n, float *nodes_out, float *hnodes_out, int32_t info[4]) {
+    if (!boxes || !codes || !info || n <= 0 || (n > 1 && (!nodes_out || !hnodes_out))) return fail(RT_ERR_INVALID_ARG, "null argument or n <= 0");
+    rtbuild::DeviceTree tree;
+    const std::string err = rtbuild::build_lbvh(boxes, codes, n, tree);
+    if (!err.empty()) return fail(RT_ERR_HIP, "device BVH build: " + err);
+    info[0] = tree.root; info[1] = tree.num_internal; info[2] = tree.depth; info[3] = 0;
+    hipError_t e = hipSuccess;
+    if (tree.num_internal < 0 || tree.num_internal > n - 1) {
+        (void)hipFree(tree.nodes); (void)hipFree(tree.hnodes);
+        return fail(RT_ERR_HIP, "device BVH build: " + std::to_string(tree.num_internal) + " records for " + std::to_string(n) + " leaves");
+    }
+    if (tree.num_internal > 0) {
+        e = hipMemcpy(nodes_out, tree.nodes, 64 * (size_t)tree.num_internal, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(hnodes_out, tree.hnodes, 32 * (size_t)tree.num_internal, hipMemcpyDeviceToHost);
+    }
+    (void)hipFree(tree.nodes); (void)hipFree(tree.hnodes);
+    HIP_TRY(e);
+    return RT_OK;
+}
+
 // Developer hook (not part of the ABI header): the next render calls of this scene inject the fault the tripwire exists for
 // (rt_kernel.hip.inc, RTP_TRIPWIRE) — rt_last_timing must then fail with RT_ERR_HIP and the tripwire's code instead of the
 // launch hanging.  0 switches it off again.

@@ -1352,6 +1352,7 @@ def test_developer_build_checks():
     lib = rb.amd_lib()
     assert b"dev=0" in lib.rt_version_string() and b"parity=1" in lib.rt_version_string()
     assert not hasattr(lib, "rt_debug_check_fast_math") and not hasattr(lib, "rt_debug_check_sphere_roots")
+    assert not hasattr(lib, "rt_debug_build_lbvh") and not hasattr(lib, "rt_debug_guard_leaves")
     host = rb.HostScene.rtiow()
     with pytest.raises(RuntimeError, match="developer build"):
         rb.DeviceScene(host, device=0, honour_env=False, kernel=rb.KERNEL_WAVEFRONT).render_to_host(rb.rtiow_camera(32, 20, 2, 8))
