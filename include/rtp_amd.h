@@ -319,6 +319,50 @@ rt_status rt_render(rt_scene *scene, const rt_camera_data *cam, const rt_shard *
 rt_status rt_render_tile(rt_scene *scene, const rt_camera_data *cam, int32_t tile_x0, int32_t tile_y0, int32_t tile_w, int32_t tile_h,
                          float *d_fb_sum, void *hip_stream, int32_t sync, rt_timing *timing);
 
+/* ---- first-hit AOVs: the per-pixel buffers a denoiser and a compositor want, from the beauty frame's own camera samples -----
+ * For pixel (i, j) and sample s = 0 … samples_per_pixel-1, in sample order: the reference's camera ray (get_ray with the seed of
+ * the beauty pass) and its first hit, hit_scene over Interval(0.001, 1e30) as in ray_color.  A hit adds
+ *     albedo_sum += m.albedo (times the texel tex2D_cpu gives at the hit, for a textured material) for LAMBERTIAN and METAL,
+ *                   (1, 1, 1) for DIELECTRIC and DIFFUSE_LIGHT;
+ *     normal_sum += rec.normal, the face-forwarded normal set_face_normal leaves;
+ *     depth_sum  += rec.t, the RAY PARAMETER — camera directions are not unit length, so this is not a distance;
+ *     hit_count  += 1;
+ * a miss adds the camera's background to albedo_sum and nothing else.  first_prim is the code 2 * index + type (type 0 sphere /
+ * 1 plane) of sample 0's hit, -1 if sample 0 misses.  Sums are float32, start at 0 and are added one sample at a time in sample
+ * order.  max_depth plays no part.  Buffers are compacted like d_fb_sum (rt_shard_rows() x image_width pixels, or tile_h x tile_w),
+ * so rows, shards and tiles assemble to the bits of the whole frame.
+ * An IN structure that grows with the library: the caller sets struct_bytes to the sizeof(rt_aov_buffers) it was compiled with
+ * (rt_aov_buffers_init does) and the library reads at most that many bytes; fields past them count as NULL.  All pointers are
+ * DEVICE memory and each may be NULL (that buffer is not written); all of them NULL, or struct_bytes below 16, is
+ * RT_ERR_INVALID_ARG. */
+typedef struct rt_aov_buffers {
+    uint32_t struct_bytes;    /* in: sizeof(rt_aov_buffers) as the caller compiled it */
+    uint32_t reserved;        /* 0 */
+    float    *albedo_sum;     /* 3 floats per pixel */
+    float    *normal_sum;     /* 3 floats per pixel */
+    float    *depth_sum;      /* 1 float per pixel */
+    uint32_t *hit_count;      /* 1 per pixel */
+    int32_t  *first_prim;     /* 1 per pixel */
+} rt_aov_buffers;
+/* *b = all NULL with struct_bytes = sizeof(rt_aov_buffers). */
+void rt_aov_buffers_init(rt_aov_buffers *b);
+
+/* The AOVs of a frame, a shard of its rows or a tile: the argument checks, limits, stream contract and pass planning of rt_render
+ * and rt_render_tile.  Where the handle takes camera rays from per-pixel candidate lists (rt_config.primary_visibility) those
+ * lists and the primary pass resolve the samples, sharing the handle's lists with its beauty frames (rt_config.reuse_view_lists);
+ * the samples they cannot vouch for, and every sample elsewhere, get the reference-order walk.  The call leaves the handle's own
+ * decisions — its choice of walk, a pause of the guarded walk, the re-pack of its tree for a far camera — as a sequence of
+ * rt_render calls alone would leave them, and rt_last_timing keeps describing the last rt_render.
+ * timing (may be NULL) with sync != 0: kernel_ms, primary_visibility, primary_ms (candidate lists and primary passes),
+ * traced_samples (the samples of pixels some leaf can be hit through, or all of them), flagged_samples (the samples the
+ * reference-order walk resolved) and rework_ms (the launches that walk whole pixels, or every sample: the few single samples the
+ * candidate lists leave undecided are walked inside the accumulation); every other field 0.  With sync == 0 only
+ * primary_visibility is filled. */
+rt_status rt_render_aov(rt_scene *scene, const rt_camera_data *cam, const rt_shard *shard, const rt_aov_buffers *buffers,
+                        void *hip_stream, int32_t sync, rt_timing *timing);
+rt_status rt_render_aov_tile(rt_scene *scene, const rt_camera_data *cam, int32_t tile_x0, int32_t tile_y0, int32_t tile_w, int32_t tile_h,
+                             const rt_aov_buffers *buffers, void *hip_stream, int32_t sync, rt_timing *timing);
+
 /* Milliseconds of the most recent rt_render kernel of this scene (waits for it). */
 rt_status rt_last_kernel_ms(rt_scene *scene, float *ms);
 /* The whole rt_timing of the most recent rt_render of this scene (waits for it). */

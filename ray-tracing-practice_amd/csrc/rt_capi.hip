@@ -15,6 +15,7 @@
 #include "rt_device_math.h"
 #include "rt_kernel.hip.inc"
 #include "rt_primary.hip.inc"
+#include "rt_aov.hip.inc"
 // Developer build only (make dev → librtp_amd_dev.so, -DRTP_DEV_BUILD): the two experimental kernels that lost to render_kernel
 // (rt_kernel_wf.hip.inc: wave-owned path pools in L2, −37 %; rt_kernel_queue.hip.inc: T-wave/S-wave LDS queues, −30 %; docs/LOG.md) and
 // the rt_debug_* entry points (exhaustive on-device checks of recip / sqrt_cr / sphere_root, the RTP_STATS counters).  The shipped
@@ -260,6 +261,11 @@ struct rt_scene {
     uint64_t device_bytes = 0;      // total memory of the device (workspace default: a sixteenth of it)
     float build_ms = 0.0f;          // device BVH build time (RTP_BUILD=device), else 0
     bool absorbing_glass = false;   // some DIELECTRIC material has a non-zero absorption (Beer-Lambert code needed)
+    // rt_render_aov: its own counter word (records the reference-order walk resolved) and events, so that rt_last_timing and the
+    // handle's judgement of its guarded walk keep reading what the last rt_render left
+    uint32_t *aov_walked = nullptr;
+    hipEvent_t aov_start = nullptr, aov_stop = nullptr;
+    std::vector<hipEvent_t> aov_events;    // per timed pass: before the primary pass, before the resolve launch, after it
 };
 
 namespace {
@@ -442,7 +448,7 @@ const char *rt_get_last_error_string(void) { return g_last_error.c_str(); }
 #else
 #define RTP_VERSION_DEV "0"
 #endif
-const char *rt_version_string(void) { return "rtp_amd 0.4 gfx950 parity=" RTP_VERSION_PARITY " dev=" RTP_VERSION_DEV; }
+const char *rt_version_string(void) { return "rtp_amd 0.5 gfx950 parity=" RTP_VERSION_PARITY " dev=" RTP_VERSION_DEV; }
 
 rt_status rt_set_device(int32_t device_ordinal) {
     int n = 0;
@@ -634,6 +640,10 @@ rt_status rt_scene_destroy(rt_scene *sc) {
     for (hipEvent_t e : sc->pass_events) (void)hipEventDestroy(e);
     if (sc->ev_start) (void)hipEventDestroy(sc->ev_start);
     if (sc->ev_stop) (void)hipEventDestroy(sc->ev_stop);
+    (void)hipFree(sc->aov_walked);
+    for (hipEvent_t e : sc->aov_events) (void)hipEventDestroy(e);
+    if (sc->aov_start) (void)hipEventDestroy(sc->aov_start);
+    if (sc->aov_stop) (void)hipEventDestroy(sc->aov_stop);
     for (rt_scene::Feedback &f : sc->feedback) {
         if (f.done) { if (f.pending) (void)hipEventSynchronize(f.done); (void)hipEventDestroy(f.done); }
         if (f.start) (void)hipEventDestroy(f.start);
@@ -748,6 +758,93 @@ rt_status acquire_feedback(rt_scene *sc, rt_scene::Feedback **out) {
     }
     *out = &f;
     return RT_OK;
+}
+// Rows of the sample slab start on 128-byte lines (32 slots x 12 B = 3 lines) — except for passes shorter than that, whose rows are
+// only padded to the 16 bytes the accumulate kernels' row reads need (a 4K frame at 1 spp: 0.4 GB instead of 3.2 GB)
+uint32_t slab_pitch_of(int pass) { return pass < 32 ? (uint32_t)((pass + 3) & ~3) : (uint32_t)((pass + 31) & ~31); }
+// The passes of a call (rt_accel.h, plan_passes) and a slab that holds one of them: three floats per (local pixel, slot)
+rt_status reserve_slab(rt_scene *sc, uint32_t num_pixels, int32_t spp, hipStream_t stream, rtaccel::PassPlan &plan) {
+    const rt_config &cfg = sc->cfg;
+    plan = rtaccel::plan_passes(num_pixels, spp, cfg.workspace_bytes, sc->device_bytes, cfg.pass_spp);
+    if (plan.passes < 1) return fail(RT_ERR_UNSUPPORTED, "image too large for the work index arithmetic");
+    int pass_size = plan.pass_size;
+    size_t need = (size_t)num_pixels * (size_t)slab_pitch_of(pass_size) * 3;
+    if (sc->slab_floats < need) {
+        HIP_TRY(hipStreamSynchronize(stream));
+        (void)hipFree(sc->slab);
+        sc->slab = nullptr;
+        sc->slab_floats = 0;
+        for (;;) {      // a device short of memory gets shorter passes, not an error
+            const hipError_t e = hipMalloc((void **)&sc->slab, need * sizeof(float));
+            if (e == hipSuccess) break;
+            (void)hipGetLastError();
+            if (e != hipErrorOutOfMemory || pass_size <= 64) HIP_TRY(e);
+            pass_size = pass_size / 2 < 64 ? 64 : pass_size / 2;
+            plan = rtaccel::PassPlan::uniform(spp, pass_size);      // (shorter than before: within the bound too)
+            need = (size_t)num_pixels * (size_t)slab_pitch_of(pass_size) * 3;
+        }
+        sc->slab_floats = need;
+    }
+    return RT_OK;
+}
+// Room for the per-pixel candidate lists of the primary-visibility pass (64 bytes per pixel) + 4 bytes per pixel for the fetch
+// order and 12 per 256 pixels for its counting sort (order_* kernels).  A device short of memory renders without the pass
+// rather than not at all: prim = false.
+rt_status reserve_view_lists(rt_scene *sc, uint32_t num_pixels, hipStream_t stream, bool &prim) {
+    if (!prim || sc->cand_pixels >= (size_t)num_pixels) return RT_OK;
+    HIP_TRY(hipStreamSynchronize(stream));
+    (void)hipFree(sc->cand);
+    sc->cand = nullptr;
+    sc->cand_pixels = 0;
+    sc->cand_key.valid = false;
+    const size_t cand_words = (size_t)num_pixels * (rtk::kCandWords + 1) + 3 * (((size_t)num_pixels + rtk::kOrderBlock - 1) / rtk::kOrderBlock);
+    if (hipMalloc((void **)&sc->cand, cand_words * sizeof(uint32_t)) == hipSuccess) {
+        sc->cand_pixels = (size_t)num_pixels;
+    } else {
+        (void)hipGetLastError();
+        sc->cand = nullptr;
+        prim = false;
+    }
+    return RT_OK;
+}
+// The candidate lists and the fetch order made from them, for this view on this stream — unless the handle holds them already
+// (rt_config.reuse_view_lists): the same camera, image, shard and tree on the same stream
+rt_status make_view_lists(rt_scene *sc, const rt_camera_data *cam, const rtk::KParams &P, uint32_t num_pixels, hipStream_t stream) {
+    rt_scene::CandKey key{};
+    std::memcpy(key.view + 0, cam->origin.e, 12); std::memcpy(key.view + 3, cam->pixel00_loc.e, 12);
+    std::memcpy(key.view + 6, cam->pixel_delta_u.e, 12); std::memcpy(key.view + 9, cam->pixel_delta_v.e, 12);
+    const int32_t dims[9] = {P.width, P.height, P.local_rows, P.band_rows, P.num_parts, P.part, P.row_w, P.tile_x0, P.tile_y0};
+    std::memcpy(key.dims, dims, sizeof(dims));
+    key.repacks = sc->repacks; key.stream = stream; key.valid = true;
+    const bool cand_cached = sc->cfg.reuse_view_lists >= 0 && sc->cand_key.valid && std::memcmp(key.view, sc->cand_key.view, sizeof(key.view)) == 0 &&
+                             std::memcmp(key.dims, sc->cand_key.dims, sizeof(key.dims)) == 0 && key.repacks == sc->cand_key.repacks && key.stream == sc->cand_key.stream;
+    if (cand_cached) return RT_OK;
+    sc->cand_key.valid = false;          // (valid again once the launches below are queued)
+    const double coord_max = rtbeam::coord_bound(cam->origin.e, cam->pixel00_loc.e, cam->pixel_delta_u.e, cam->pixel_delta_v.e, cam->image_width, cam->image_height);
+    hipLaunchKernelGGL(rtk::cand_kernel, dim3((num_pixels + 255u) / 256u), dim3(256), 0, stream, P, sc->cand, coord_max);
+    HIP_TRY(hipGetLastError());
+    // the order the trace kernel fetches the pixels in: expensive ones first (rt_primary.hip.inc)
+    uint32_t *order = sc->cand + sc->cand_pixels * rtk::kCandWords, *counts = order + sc->cand_pixels;
+    const uint32_t order_blocks = (num_pixels + (uint32_t)rtk::kOrderBlock - 1u) / (uint32_t)rtk::kOrderBlock;
+    hipLaunchKernelGGL(rtk::order_count_kernel, dim3(order_blocks), dim3(rtk::kOrderBlock), 0, stream, (const uint32_t *)sc->cand, num_pixels, order_blocks, counts);
+    hipLaunchKernelGGL(rtk::order_scan_kernel, dim3(1), dim3(1024), 0, stream, counts, 3u * order_blocks);
+    hipLaunchKernelGGL(rtk::order_scatter_kernel, dim3(order_blocks), dim3(rtk::kOrderBlock), 0, stream, (const uint32_t *)sc->cand, num_pixels, order_blocks,
+                       (const uint32_t *)counts, order);
+    HIP_TRY(hipGetLastError());
+    sc->cand_key = key;
+    return RT_OK;
+}
+// the primary-visibility pass of one pass of samples: (hit distance, primitive, seed) into each sample's slot of the slab
+void launch_primary(const rt_scene *sc, const rtk::KParams &P, uint32_t num_pixels, hipStream_t stream) {
+    int pgrid = sc->num_cus * 8;                            // 256-thread workgroups: 8 waves per SIMD
+    const bool by_pixel = P.pass_count >= RTP_BY_PIXEL_MIN;  // a wave per pixel once a pixel (nearly) fills it twice
+    const uint32_t units = by_pixel ? (num_pixels + 3u) / 4u : (P.total_work + 255u) / 256u;
+    if ((uint32_t)pgrid > units) pgrid = (int)units;
+    if (by_pixel) {
+        if (P.num_planes > 0) hipLaunchKernelGGL(rtk::primary_pixel_kernel<true>, dim3(pgrid), dim3(256), 0, stream, P);
+        else hipLaunchKernelGGL(rtk::primary_pixel_kernel<false>, dim3(pgrid), dim3(256), 0, stream, P);
+    } else if (P.num_planes > 0) hipLaunchKernelGGL(rtk::primary_kernel<true>, dim3(pgrid), dim3(256), 0, stream, P);
+    else hipLaunchKernelGGL(rtk::primary_kernel<false>, dim3(pgrid), dim3(256), 0, stream, P);
 }
 // rt_render and rt_render_tile: whole rows of a shard, or a rectangle
 rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shard, const Tile *tile, float *d_fb_sum, void *hip_stream,
@@ -977,30 +1074,9 @@ rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *s
     // Fewer, larger launches amortise the end-of-launch tail — on a row shard of an N-GPU frame
     // the pass grows N-fold, so a launch keeps the size it has on one GPU.
     const uint32_t num_pixels = (uint32_t)P.local_rows * (uint32_t)P.row_w;
-    // rows of the slab start on 128-byte lines (32 slots x 12 B = 3 lines) — except for passes shorter than that, whose rows are
-    // only padded to the 16 bytes the accumulate kernel's row reads need (a 4K frame at 1 spp: 0.4 GB instead of 3.2 GB)
-    auto pitch_of = [](int pass) { return pass < 32 ? (uint32_t)((pass + 3) & ~3) : (uint32_t)((pass + 31) & ~31); };
-    rtaccel::PassPlan plan = rtaccel::plan_passes(num_pixels, P.spp, cfg.workspace_bytes, sc->device_bytes, cfg.pass_spp);
-    if (plan.passes < 1) return fail(RT_ERR_UNSUPPORTED, "image too large for the work index arithmetic");
-    int pass_size = plan.pass_size;
-    // workspace: three floats per (local pixel, slot)
-    size_t need = (size_t)num_pixels * (size_t)pitch_of(pass_size) * 3;
-    if (sc->slab_floats < need) {
-        HIP_TRY(hipStreamSynchronize(stream));
-        (void)hipFree(sc->slab);
-        sc->slab = nullptr;
-        sc->slab_floats = 0;
-        for (;;) {      // a device short of memory gets shorter passes, not an error
-            const hipError_t e = hipMalloc((void **)&sc->slab, need * sizeof(float));
-            if (e == hipSuccess) break;
-            (void)hipGetLastError();
-            if (e != hipErrorOutOfMemory || pass_size <= 64) HIP_TRY(e);
-            pass_size = pass_size / 2 < 64 ? 64 : pass_size / 2;
-            plan = rtaccel::PassPlan::uniform(P.spp, pass_size);      // (shorter than before: within the bound too)
-            need = (size_t)num_pixels * (size_t)pitch_of(pass_size) * 3;
-        }
-        sc->slab_floats = need;
-    }
+    rtaccel::PassPlan plan;
+    if ((st = reserve_slab(sc, num_pixels, P.spp, stream, plan)) != RT_OK) return st;
+    const int pass_size = plan.pass_size;
     P.slab = sc->slab;
     P.num_pixels = num_pixels;
     const int passes = plan.passes;
@@ -1086,23 +1162,7 @@ rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *s
         const double dx = (double)cam->origin.e[0] - sc->guard.center[0], dy = (double)cam->origin.e[1] - sc->guard.center[1], dz = (double)cam->origin.e[2] - sc->guard.center[2];
         if (!(dx * dx + dy * dy + dz * dz <= (double)sc->guard.d0_sq * (1.0 - 1e-5))) prim = false;
     }
-    if (prim && sc->cand_pixels < (size_t)num_pixels) {
-        HIP_TRY(hipStreamSynchronize(stream));
-        (void)hipFree(sc->cand);
-        sc->cand = nullptr;
-        sc->cand_pixels = 0;
-        sc->cand_key.valid = false;
-        // (64 bytes per pixel; a device short of memory renders without the pass rather than not at all)
-        // + 4 bytes per pixel for the fetch order and 12 per 256 pixels for its counting sort (order_* kernels)
-        const size_t cand_words = (size_t)num_pixels * (rtk::kCandWords + 1) + 3 * (((size_t)num_pixels + rtk::kOrderBlock - 1) / rtk::kOrderBlock);
-        if (hipMalloc((void **)&sc->cand, cand_words * sizeof(uint32_t)) == hipSuccess) {
-            sc->cand_pixels = (size_t)num_pixels;
-        } else {
-            (void)hipGetLastError();
-            sc->cand = nullptr;
-            prim = false;
-        }
-    }
+    if ((st = reserve_view_lists(sc, num_pixels, stream, prim)) != RT_OK) return st;
     P.cand = prim ? sc->cand : nullptr;
     P.order = prim ? sc->cand + sc->cand_pixels * rtk::kCandWords : nullptr;
     P.traced_pixels = prim ? P.order + sc->cand_pixels + 2 * (((size_t)num_pixels + rtk::kOrderBlock - 1) / rtk::kOrderBlock) : nullptr;      // counts[2 * blocks] after the scan
@@ -1110,30 +1170,10 @@ rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *s
     if ((st = acquire_feedback(sc, &feedback)) != RT_OK) return st;
     HIP_TRY(hipEventRecord(feedback->start, stream));
     HIP_TRY(hipEventRecord(sc->ev_start, stream));
-    rt_scene::CandKey key{};
     if (prim) {
-        std::memcpy(key.view + 0, cam->origin.e, 12); std::memcpy(key.view + 3, cam->pixel00_loc.e, 12);
-        std::memcpy(key.view + 6, cam->pixel_delta_u.e, 12); std::memcpy(key.view + 9, cam->pixel_delta_v.e, 12);
-        const int32_t dims[9] = {P.width, P.height, P.local_rows, P.band_rows, P.num_parts, P.part, P.row_w, P.tile_x0, P.tile_y0};
-        std::memcpy(key.dims, dims, sizeof(dims));
-        key.repacks = sc->repacks; key.stream = stream; key.valid = true;
-    }
-    const bool cand_cached = prim && cfg.reuse_view_lists >= 0 && sc->cand_key.valid && std::memcmp(key.view, sc->cand_key.view, sizeof(key.view)) == 0 &&
-                             std::memcmp(key.dims, sc->cand_key.dims, sizeof(key.dims)) == 0 && key.repacks == sc->cand_key.repacks && key.stream == sc->cand_key.stream;
-    if (!cand_cached) sc->cand_key.valid = false;          // (valid again once the launches below are queued)
-    if (prim && !cand_cached) {
-        const double coord_max = rtbeam::coord_bound(cam->origin.e, cam->pixel00_loc.e, cam->pixel_delta_u.e, cam->pixel_delta_v.e, cam->image_width, cam->image_height);
-        hipLaunchKernelGGL(rtk::cand_kernel, dim3((num_pixels + 255u) / 256u), dim3(256), 0, stream, P, sc->cand, coord_max);
-        HIP_TRY(hipGetLastError());
-        // the order the trace kernel fetches the pixels in: expensive ones first (rt_primary.hip.inc)
-        uint32_t *order = sc->cand + sc->cand_pixels * rtk::kCandWords, *counts = order + sc->cand_pixels;
-        const uint32_t order_blocks = (num_pixels + (uint32_t)rtk::kOrderBlock - 1u) / (uint32_t)rtk::kOrderBlock;
-        hipLaunchKernelGGL(rtk::order_count_kernel, dim3(order_blocks), dim3(rtk::kOrderBlock), 0, stream, (const uint32_t *)sc->cand, num_pixels, order_blocks, counts);
-        hipLaunchKernelGGL(rtk::order_scan_kernel, dim3(1), dim3(1024), 0, stream, counts, 3u * order_blocks);
-        hipLaunchKernelGGL(rtk::order_scatter_kernel, dim3(order_blocks), dim3(rtk::kOrderBlock), 0, stream, (const uint32_t *)sc->cand, num_pixels, order_blocks,
-                           (const uint32_t *)counts, order);
-        HIP_TRY(hipGetLastError());
-        sc->cand_key = key;
+        if ((st = make_view_lists(sc, cam, P, num_pixels, stream)) != RT_OK) return st;
+    } else {
+        sc->cand_key.valid = false;
     }
     hipStream_t launch_stream = stream;       // the exact re-walk may go to the handle's second stream (overlap_rework)
     // registers and scratch of the dominant (trace) kernel as the loaded code object reports them → rt_timing
@@ -1231,7 +1271,7 @@ rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *s
         P.pass_first = plan.first(pass);
         P.pass_count = plan.count(pass);
         P.total_work = num_pixels * (uint32_t)P.pass_count;      // work index = pixel * pass_count + slot
-        P.slab_pitch = pitch_of(pass_size);
+        P.slab_pitch = slab_pitch_of(pass_size);
         if ((uint64_t)num_pixels * (uint64_t)P.pass_count >= (1ull << 31) - 4096 || !make_magic((uint32_t)P.pass_count, (uint64_t)P.total_work + 64, P.magic_count))
             return fail(RT_ERR_UNSUPPORTED, "image too large for the work index arithmetic");
         P.queue = sc->queue + kQueueWork + pass;
@@ -1251,15 +1291,7 @@ rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *s
         }
         if (prim) {
             // primary visibility of this pass's samples: (hit distance, primitive) into each sample's slot of the slab
-            int pgrid = sc->num_cus * 8;                            // 256-thread workgroups: 8 waves per SIMD
-            const bool by_pixel = P.pass_count >= RTP_BY_PIXEL_MIN;  // a wave per pixel once a pixel (nearly) fills it twice
-            const uint32_t units = by_pixel ? (num_pixels + 3u) / 4u : (P.total_work + 255u) / 256u;
-            if ((uint32_t)pgrid > units) pgrid = (int)units;
-            if (by_pixel) {
-                if (P.num_planes > 0) hipLaunchKernelGGL(rtk::primary_pixel_kernel<true>, dim3(pgrid), dim3(256), 0, stream, P);
-                else hipLaunchKernelGGL(rtk::primary_pixel_kernel<false>, dim3(pgrid), dim3(256), 0, stream, P);
-            } else if (P.num_planes > 0) hipLaunchKernelGGL(rtk::primary_kernel<true>, dim3(pgrid), dim3(256), 0, stream, P);
-            else hipLaunchKernelGGL(rtk::primary_kernel<false>, dim3(pgrid), dim3(256), 0, stream, P);
+            launch_primary(sc, P, num_pixels, stream);
             HIP_TRY(hipGetLastError());
         }
         if (timed_pass) HIP_TRY(hipEventRecord(sc->pass_events[4 * pass + 1], stream));
@@ -1464,6 +1496,139 @@ rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *s
     timing_out(sc->last, timing);
     return RT_OK;
 }
+
+// rt_render_aov and rt_render_aov_tile (rt_aov.hip.inc).  The handle's state it may change is only what any call shares: the slab, the
+// candidate lists (and their key, so that a beauty frame of the same view reuses them).  No feedback slot, no re-pack, no counter
+// block, no per-pass events of rt_render: what the handle decides next, and what rt_last_timing reports, stay those of its
+// rt_render calls.
+rt_status aov_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shard, const Tile *tile, const rt_aov_buffers *buffers, void *hip_stream,
+                   int32_t sync, rt_timing *timing) {
+    // (the buffers first: a caller's mistake there is reported as such whatever else is wrong)
+    if (!buffers || buffers->struct_bytes < 16u) return fail(RT_ERR_INVALID_ARG, "null AOV buffers (or struct_bytes below 16)");
+    rt_aov_buffers b{};
+    std::memcpy(&b, buffers, buffers->struct_bytes < sizeof(b) ? buffers->struct_bytes : sizeof(b));
+    if (!b.albedo_sum && !b.normal_sum && !b.depth_sum && !b.hit_count && !b.first_prim) return fail(RT_ERR_INVALID_ARG, "every AOV buffer is NULL");
+    rtk::KParams P;
+    rt_status st = fill_params(sc, cam, shard, P, tile);
+    if (st != RT_OK) return st;
+    if ((st = check_device(sc)) != RT_OK) return st;
+    if ((st = timing_check(timing)) != RT_OK) return st;
+    const rt_config &cfg = sc->cfg;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    timing_out(rt_timing{}, timing);
+    if (P.local_rows == 0) return RT_OK;
+    const uint32_t num_pixels = (uint32_t)P.local_rows * (uint32_t)P.row_w;
+    const rtk::AovOut out{b.albedo_sum, b.normal_sum, b.depth_sum, b.hit_count, b.first_prim};
+    if (P.spp <= 0) {       // no samples: zero sums, no hit
+        if (out.albedo) HIP_TRY(hipMemsetAsync(out.albedo, 0, (size_t)num_pixels * 12, stream));
+        if (out.normal) HIP_TRY(hipMemsetAsync(out.normal, 0, (size_t)num_pixels * 12, stream));
+        if (out.depth) HIP_TRY(hipMemsetAsync(out.depth, 0, (size_t)num_pixels * 4, stream));
+        if (out.hits) HIP_TRY(hipMemsetAsync(out.hits, 0, (size_t)num_pixels * 4, stream));
+        if (out.prim) HIP_TRY(hipMemsetAsync(out.prim, 0xff, (size_t)num_pixels * 4, stream));
+        if (sync) HIP_TRY(hipStreamSynchronize(stream));
+        return RT_OK;
+    }
+    // Candidate lists where the handle's next beauty frame of this view would take its camera rays from them: the guarded walk is
+    // its choice (not paused, not an exact frame forced by rt_config), and its tree's margins already cover this camera — rt_render
+    // would re-pack the tree for a camera outside them; this call does not, and walks the reference's order instead.
+    bool prim = sc->guard.ok && cfg.traversal != RT_TRAVERSAL_EXACT && P.root >= 0 && guarded_wanted(cfg, (int64_t)P.num_spheres + P.num_planes) &&
+                !(sc->guard_paused && !cfg.guard_keep) && cfg.kernel != RT_KERNEL_WAVEFRONT && cfg.primary_visibility >= 0 && sc->nodes != nullptr &&
+                (sc->guard.dyn_k > 0.0f || cfg.scene_in_lds != 0);
+    if (prim) {
+        auto dist_sq = [&](const float *c) {
+            const double dx = (double)cam->origin.e[0] - c[0], dy = (double)cam->origin.e[1] - c[1], dz = (double)cam->origin.e[2] - c[2];
+            return dx * dx + dy * dy + dz * dz;
+        };
+        if (!(dist_sq(sc->guard.origin_center) <= (double)sc->guard.origin_radius * sc->guard.origin_radius)) prim = false;
+        if (sc->guard.num_small > 0 && !(dist_sq(sc->guard.center) <= (double)sc->guard.d0_sq * (1.0 - 1e-5))) prim = false;
+    }
+    rtaccel::PassPlan plan;
+    if ((st = reserve_slab(sc, num_pixels, P.spp, stream, plan)) != RT_OK) return st;
+    const int passes = plan.passes;
+    if (passes > kMaxPasses) return fail(RT_ERR_UNSUPPORTED, "more than 1024 passes (samples_per_pixel above 65536, or above 64512 at 2^24 pixels)");
+    P.slab = sc->slab;
+    P.num_pixels = num_pixels;
+    P.slab_pitch = slab_pitch_of(plan.pass_size);
+    if ((st = reserve_view_lists(sc, num_pixels, stream, prim)) != RT_OK) return st;
+    P.cand = prim ? sc->cand : nullptr;
+    P.order = prim ? sc->cand + sc->cand_pixels * rtk::kCandWords : nullptr;
+    P.traced_pixels = prim ? P.order + sc->cand_pixels + 2 * (((size_t)num_pixels + rtk::kOrderBlock - 1) / rtk::kOrderBlock) : nullptr;
+    if (!sc->aov_walked) HIP_TRY(hipMalloc((void **)&sc->aov_walked, sizeof(uint32_t)));
+    if (!sc->aov_start) {
+        HIP_TRY(hipEventCreate(&sc->aov_start));
+        HIP_TRY(hipEventCreate(&sc->aov_stop));
+    }
+    const int timed = passes < kTimedPasses ? passes : kTimedPasses;
+    while ((int)sc->aov_events.size() < 3 * timed) {
+        hipEvent_t e;
+        HIP_TRY(hipEventCreate(&e));
+        sc->aov_events.push_back(e);
+    }
+    HIP_TRY(hipEventRecord(sc->aov_start, stream));
+    HIP_TRY(hipMemsetAsync(sc->aov_walked, 0, sizeof(uint32_t), stream));
+    if (prim) {
+        if ((st = make_view_lists(sc, cam, P, num_pixels, stream)) != RT_OK) return st;
+    } else {
+        sc->cand_key.valid = false;         // (as rt_render does: the next call with lists makes them anew)
+    }
+    for (int pass = 0; pass < passes; ++pass) {
+        const bool timed_pass = pass < timed;
+        P.pass_first = plan.first(pass);
+        P.pass_count = plan.count(pass);
+        P.total_work = num_pixels * (uint32_t)P.pass_count;
+        if ((uint64_t)num_pixels * (uint64_t)P.pass_count >= (1ull << 31) - 4096 || !make_magic((uint32_t)P.pass_count, (uint64_t)P.total_work + 64, P.magic_count))
+            return fail(RT_ERR_UNSUPPORTED, "image too large for the work index arithmetic");
+        if (timed_pass) HIP_TRY(hipEventRecord(sc->aov_events[3 * pass], stream));
+        if (prim) {
+            launch_primary(sc, P, num_pixels, stream);
+            HIP_TRY(hipGetLastError());
+        }
+        if (timed_pass) HIP_TRY(hipEventRecord(sc->aov_events[3 * pass + 1], stream));
+        // (1) the records of pixels without a list (every record, without lists) through the reference-order walk
+        const uint32_t units = prim ? (num_pixels + 3u) / 4u : (P.total_work + 255u) / 256u;
+        const uint32_t rgrid = std::min<uint32_t>(units, (uint32_t)sc->num_cus * 8u);
+        if (prim) hipLaunchKernelGGL(rtk::aov_resolve_kernel<false>, dim3(rgrid), dim3(256), 0, stream, P, sc->aov_walked);
+        else hipLaunchKernelGGL(rtk::aov_resolve_kernel<true>, dim3(rgrid), dim3(256), 0, stream, P, sc->aov_walked);
+        HIP_TRY(hipGetLastError());
+        if (timed_pass) HIP_TRY(hipEventRecord(sc->aov_events[3 * pass + 2], stream));
+        // (2) … added to the pixel's sums in sample order
+        const dim3 acc_grid((num_pixels + 64 * rtk::kAccWaves - 1) / (64 * rtk::kAccWaves)), acc_block(64 * rtk::kAccWaves);
+        hipLaunchKernelGGL(rtk::aov_accumulate_kernel, acc_grid, acc_block, 0, stream, P, out, pass == 0 ? 1 : 0, sc->aov_walked);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(sc->aov_stop, stream));
+    rt_timing t{};
+    t.primary_visibility = prim ? 1u : 0u;
+    if (sync) {
+        HIP_TRY(hipEventSynchronize(sc->aov_stop));
+        HIP_TRY(hipEventElapsedTime(&t.kernel_ms, sc->aov_start, sc->aov_stop));
+        float primary = 0.0f, rework = 0.0f, ms = 0.0f;
+        for (int p = 0; p < timed; ++p) {
+            HIP_TRY(hipEventElapsedTime(&ms, sc->aov_events[3 * p], sc->aov_events[3 * p + 1]));
+            primary += ms;
+            HIP_TRY(hipEventElapsedTime(&ms, sc->aov_events[3 * p + 1], sc->aov_events[3 * p + 2]));
+            rework += ms;
+        }
+        // passes beyond the individually timed ones are priced at the mean of the timed ones; + the lists, made before the first pass
+        primary *= (float)passes / (float)timed;
+        rework *= (float)passes / (float)timed;
+        HIP_TRY(hipEventElapsedTime(&ms, sc->aov_start, sc->aov_events[0]));
+        t.primary_ms = prim ? primary + ms : 0.0f;
+        t.rework_ms = rework;
+        const uint64_t samples = (uint64_t)num_pixels * (uint64_t)P.spp;
+        t.traced_samples = samples;
+        t.flagged_samples = samples;
+        if (prim) {
+            uint32_t traced = 0, walked = 0;
+            HIP_TRY(hipMemcpy(&traced, P.traced_pixels, 4, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(&walked, sc->aov_walked, 4, hipMemcpyDeviceToHost));
+            t.traced_samples = (uint64_t)traced * (uint64_t)P.spp;
+            t.flagged_samples = walked;
+        }
+    }
+    timing_out(t, timing);
+    return RT_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1477,6 +1642,23 @@ rt_status rt_render_tile(rt_scene *sc, const rt_camera_data *cam, int32_t tile_x
                          float *d_fb_sum, void *hip_stream, int32_t sync, rt_timing *timing) {
     const Tile tile{tile_x0, tile_y0, tile_w, tile_h};
     return render_impl(sc, cam, nullptr, &tile, d_fb_sum, hip_stream, sync, timing);
+}
+
+void rt_aov_buffers_init(rt_aov_buffers *b) {
+    if (!b) return;
+    std::memset(b, 0, sizeof(*b));
+    b->struct_bytes = (uint32_t)sizeof(*b);
+}
+
+rt_status rt_render_aov(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shard, const rt_aov_buffers *buffers, void *hip_stream,
+                        int32_t sync, rt_timing *timing) {
+    return aov_impl(sc, cam, shard, nullptr, buffers, hip_stream, sync, timing);
+}
+
+rt_status rt_render_aov_tile(rt_scene *sc, const rt_camera_data *cam, int32_t tile_x0, int32_t tile_y0, int32_t tile_w, int32_t tile_h,
+                             const rt_aov_buffers *buffers, void *hip_stream, int32_t sync, rt_timing *timing) {
+    const Tile tile{tile_x0, tile_y0, tile_w, tile_h};
+    return aov_impl(sc, cam, nullptr, &tile, buffers, hip_stream, sync, timing);
 }
 
 void rt_timing_init(rt_timing *t) {

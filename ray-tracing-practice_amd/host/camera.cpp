@@ -3,12 +3,37 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <fstream>
 #include <iostream>
+#include <vector>
 
 #include "png_writer.h"
 #include "scene_params.h"
 
 namespace rtp {
+
+// ---- first-hit AOV file (rtp_main --gpu --aov) ------------------------------------------------------
+bool write_aov_file(const std::string &path, int32_t width, int32_t height, int32_t spp, const float *albedo_sum, const float *normal_sum,
+                    const float *depth_sum, const uint32_t *hit_count) {
+    std::ofstream out(path, std::ios::binary);
+    if (!out) return false;
+    const int32_t hdr[3] = {width, height, spp};
+    out.write(reinterpret_cast<const char *>(hdr), sizeof(hdr));
+    const size_t pixels = static_cast<size_t>(width) * static_cast<size_t>(height);
+    const float n = static_cast<float>(spp);
+    std::vector<float> rec(pixels * 8);
+    for (size_t p = 0; p < pixels; ++p) {
+        float *r = &rec[8 * p];
+        for (int c = 0; c < 3; ++c) {
+            r[c] = albedo_sum[3 * p + c] / n;
+            r[3 + c] = normal_sum[3 * p + c] / n;
+        }
+        r[6] = hit_count[p] != 0u ? depth_sum[p] / static_cast<float>(hit_count[p]) : 0.0f;
+        r[7] = static_cast<float>(hit_count[p]) / n;
+    }
+    out.write(reinterpret_cast<const char *>(rec.data()), static_cast<std::streamsize>(rec.size() * sizeof(float)));
+    return static_cast<bool>(out);
+}
 
 // ---- savers ---------------------------------------------------------------------------------
 

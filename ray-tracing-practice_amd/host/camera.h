@@ -117,8 +117,15 @@ struct SceneParams;
 void orbit_pose(const SceneParams &p, int frame, Vec3 &eye, Vec3 &target);
 
 // gpu_render (src/camera.cu:290-349): per frame BinarySaver + orbit camera + render, printing
-// "n \t ms \t W*H*sqrt_spp^2".  The scene must already be bound.
-void gpu_render(const SceneParams &params);
+// "n \t ms \t W*H*sqrt_spp^2".  The scene must already be bound.  aov (rtp_main --gpu --aov): each frame's first-hit AOVs
+// (rt_render_aov) go to "<frame file>.aov" as well (write_aov_file).
+void gpu_render(const SceneParams &params, bool aov = false);
+
+// The .aov file of a frame: int32 width, height, spp, then per pixel in row order 8 float32 — albedo_sum / spp (3),
+// normal_sum / spp (3), depth_sum / hit_count (0 where no sample hit) and hit_count / spp, each one float32 division.
+// Inputs as rt_aov_buffers holds them (width * height pixels).  Returns false when the file cannot be written.
+bool write_aov_file(const std::string &path, int32_t width, int32_t height, int32_t spp, const float *albedo_sum, const float *normal_sum,
+                    const float *depth_sum, const uint32_t *hit_count);
 
 // Animation driver beyond the reference: frames dealt round-robin to num_devices GPUs, saver
 // arithmetic on the device, file output overlapped with the next frame.  Same files, byte for byte.

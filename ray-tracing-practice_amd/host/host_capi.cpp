@@ -105,6 +105,11 @@ int32_t rtp_host_write_binary_image(const char *path, const float *fb_sum, int32
     return 0;
 }
 
+int32_t rtp_host_write_aov(const char *path, int32_t width, int32_t height, int32_t spp, const float *albedo_sum, const float *normal_sum,
+                           const float *depth_sum, const uint32_t *hit_count) {
+    return rtp::write_aov_file(path, width, height, spp, albedo_sum, normal_sum, depth_sum, hit_count) ? 0 : 1;
+}
+
 int32_t rtp_host_write_png(const char *path, const float *fb_sum, int32_t width, int32_t height, int32_t divisor) {
     rtp::PngSaver saver(divisor, path);
     saver.set_format(width, height);

@@ -75,10 +75,25 @@ std::string frame_filename(const std::string &pattern, int n) {
     return out;
 }
 
-void gpu_render(const SceneParams &params) {
+void gpu_render(const SceneParams &params, bool aov) {
     float *d_fb = nullptr;
     const size_t num_pixels = static_cast<size_t>(params.width) * params.height;
     RTP_CHECK(rt_device_alloc(num_pixels * 3 * sizeof(float), reinterpret_cast<void **>(&d_fb)));
+    // --aov: the first-hit AOVs of every frame (albedo, normal, depth, hit count; rt_render_aov)
+    rt_aov_buffers aov_bufs;
+    rt_aov_buffers_init(&aov_bufs);
+    std::vector<float> h_albedo, h_normal, h_depth;
+    std::vector<uint32_t> h_hits;
+    if (aov) {
+        RTP_CHECK(rt_device_alloc(num_pixels * 12, reinterpret_cast<void **>(&aov_bufs.albedo_sum)));
+        RTP_CHECK(rt_device_alloc(num_pixels * 12, reinterpret_cast<void **>(&aov_bufs.normal_sum)));
+        RTP_CHECK(rt_device_alloc(num_pixels * 4, reinterpret_cast<void **>(&aov_bufs.depth_sum)));
+        RTP_CHECK(rt_device_alloc(num_pixels * 4, reinterpret_cast<void **>(&aov_bufs.hit_count)));
+        h_albedo.resize(num_pixels * 3);
+        h_normal.resize(num_pixels * 3);
+        h_depth.resize(num_pixels);
+        h_hits.resize(num_pixels);
+    }
 
     for (int n = 0; n < params.num_frames; ++n) {
         const std::string filename = frame_filename(params.output_pattern, n);
@@ -99,8 +114,25 @@ void gpu_render(const SceneParams &params) {
         const float ms = std::chrono::duration<float, std::milli>(t1 - t0).count();
         const long long total_rays = static_cast<long long>(params.width) * params.height * params.sqrt_spp * params.sqrt_spp;
         std::cout << n << "\t" << ms << "\t" << total_rays << "\n";
+        if (aov) {          // (outside the frame's timed span: the reference has no such output)
+            const rt_camera_data cam = camera.build_camera_data();
+            RTP_CHECK(rt_render_aov(bound_scene(), &cam, nullptr, &aov_bufs, nullptr, 1, nullptr));
+            RTP_CHECK(rt_copy_to_host(h_albedo.data(), aov_bufs.albedo_sum, num_pixels * 12));
+            RTP_CHECK(rt_copy_to_host(h_normal.data(), aov_bufs.normal_sum, num_pixels * 12));
+            RTP_CHECK(rt_copy_to_host(h_depth.data(), aov_bufs.depth_sum, num_pixels * 4));
+            RTP_CHECK(rt_copy_to_host(h_hits.data(), aov_bufs.hit_count, num_pixels * 4));
+            if (!write_aov_file(filename + ".aov", params.width, params.height, cam.samples_per_pixel, h_albedo.data(), h_normal.data(), h_depth.data(),
+                                h_hits.data())) {
+                std::cerr << "cannot write " << filename << ".aov\n";
+                std::exit(99);
+            }
+        }
     }
     rt_device_free(d_fb);  // unchecked in the reference too (src/camera.cu:348)
+    rt_device_free(aov_bufs.albedo_sum);
+    rt_device_free(aov_bufs.normal_sum);
+    rt_device_free(aov_bufs.depth_sum);
+    rt_device_free(aov_bufs.hit_count);
 }
 
 // ---- animation driver ("next" rows f1 + f2 of SURVEY.md §8) ---------------------------------------

@@ -48,6 +48,9 @@ void rtp_host_make_camera(int32_t width, int32_t height, float vfov_degrees, con
 void rtp_host_quantize(const float *fb_sum, int64_t num_pixels, int32_t divisor, uint8_t *rgb8);
 /* BinarySaver file image: 8-byte header + RGB8.  Returns 0 on success. */
 int32_t rtp_host_write_binary_image(const char *path, const float *fb_sum, int32_t width, int32_t height, int32_t divisor);
+/* The .aov file of rtp_main --gpu --aov (rtp::write_aov_file): header width, height, spp, then 8 float32 per pixel.  0 on success. */
+int32_t rtp_host_write_aov(const char *path, int32_t width, int32_t height, int32_t spp, const float *albedo_sum, const float *normal_sum,
+                           const float *depth_sum, const uint32_t *hit_count);
 int32_t rtp_host_write_png(const char *path, const float *fb_sum, int32_t width, int32_t height, int32_t divisor);
 /* Host texture loader (JPEG / PPM / PFM → float RGBA, stbi_loadf rule).  Returns 0 on success and
  * fills width/height; rgba (may be NULL to query the size) receives width*height*4 floats. */

@@ -73,6 +73,21 @@ class Timing(C.Structure):
         self.struct_bytes = C.sizeof(Timing)
 
 
+class AovBuffers(C.Structure):
+    """rt_aov_buffers (include/rtp_amd.h): DEVICE addresses of the first-hit AOV sums, each may be NULL."""
+    _fields_ = [("struct_bytes", C.c_uint32), ("reserved", C.c_uint32), ("albedo_sum", C.c_void_p), ("normal_sum", C.c_void_p),
+                ("depth_sum", C.c_void_p), ("hit_count", C.c_void_p), ("first_prim", C.c_void_p)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_bytes = C.sizeof(AovBuffers)
+
+
+# rt_aov_buffers field of each AOV, its numpy type and its values per pixel (render_aov_to_host)
+AOV_CHANNELS = (("albedo", "albedo_sum", np.float32, 3), ("normal", "normal_sum", np.float32, 3), ("depth", "depth_sum", np.float32, 1),
+                ("hits", "hit_count", np.uint32, 1), ("prim", "first_prim", np.int32, 1))
+
+
 TRAVERSAL_AUTO, TRAVERSAL_EXACT, TRAVERSAL_GUARDED = 0, 1, 2
 BUILD_HOST_SAH, BUILD_DEVICE_LBVH = 0, 1
 KERNEL_AUTO, KERNEL_MEGA, KERNEL_WAVEFRONT = 0, 1, 2
@@ -120,7 +135,7 @@ RTP_AMD_SYMBOLS = [
     "rt_render_to_host", "rt_trace_samples", "rt_closest_hits", "rt_device_alloc", "rt_device_free", "rt_copy_to_host", "rt_tonemap",
     "rt_get_last_error_string", "rt_version_string",
     "rt_context_create", "rt_context_destroy", "rt_context_num_devices", "rt_context_transport", "rt_context_scene_create",
-    "rt_render_sharded", "rt_gather",
+    "rt_render_sharded", "rt_gather", "rt_aov_buffers_init", "rt_render_aov", "rt_render_aov_tile",
 ]
 
 _host = None
@@ -185,6 +200,13 @@ def amd_lib():
                                   C.c_int32, C.POINTER(Timing)]
         lib.rt_render_tile.argtypes = [C.c_void_p, C.POINTER(CameraData), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                        C.c_int32, C.POINTER(Timing)]
+        if hasattr(lib, "rt_render_aov"):        # (an older build loaded through RTP_AMD_LIB for an A/B run has no AOV calls)
+            lib.rt_aov_buffers_init.argtypes = [C.POINTER(AovBuffers)]
+            lib.rt_aov_buffers_init.restype = None
+            lib.rt_render_aov.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(Shard), C.POINTER(AovBuffers), C.c_void_p, C.c_int32,
+                                          C.POINTER(Timing)]
+            lib.rt_render_aov_tile.argtypes = [C.c_void_p, C.POINTER(CameraData), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                               C.POINTER(AovBuffers), C.c_void_p, C.c_int32, C.POINTER(Timing)]
         lib.rt_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         lib.rt_last_timing.argtypes = [C.c_void_p, C.POINTER(Timing)]
         lib.rt_timing_init.argtypes = [C.POINTER(Timing)]
@@ -380,6 +402,53 @@ class DeviceScene:
         finally:
             lib.rt_device_free(d)
         return fb, t
+
+    def render_aov(self, cam, ptrs, shard=None, stream=None, sync=True):
+        """rt_render_aov.  ptrs: {"albedo", "normal", "depth", "hits", "prim"} → integer device address (missing / None: not
+        written).  Returns the rt_timing."""
+        b = AovBuffers()
+        for key, field, _, _ in AOV_CHANNELS:
+            if ptrs.get(key):
+                setattr(b, field, ptrs[key])
+        t = Timing()
+        self._apply_config()
+        _check(amd_lib().rt_render_aov(self._h, C.byref(cam), C.byref(shard) if shard else None, C.byref(b), C.c_void_p(stream or 0),
+                                       1 if sync else 0, C.byref(t)), "rt_render_aov")
+        return t
+
+    def render_aov_to_host(self, cam, shard=None, tile=None):
+        """The AOVs of the frame, a shard of its rows or a tile (x0, y0, w, h) through fresh device buffers: ({"albedo": (rows, w, 3),
+        "normal": (rows, w, 3), "depth": (rows, w), "hits": (rows, w) uint32, "prim": (rows, w) int32}, rt_timing)."""
+        lib = amd_lib()
+        if tile is not None:
+            x0, y0, w, rows = tile
+        else:
+            w, rows = cam.image_width, lib.rt_shard_rows(cam.image_height, C.byref(shard) if shard else None)
+        pixels = max(w, 0) * max(rows, 0)
+        b = AovBuffers()
+        dev = {}
+        t = Timing()
+        try:
+            for key, field, dtype, per in AOV_CHANNELS:
+                d = C.c_void_p()
+                _check(lib.rt_device_alloc(pixels * per * 4 or 4, C.byref(d)), "rt_device_alloc")
+                dev[key] = d
+                setattr(b, field, d.value)
+            self._apply_config()
+            if tile is not None:
+                _check(lib.rt_render_aov_tile(self._h, C.byref(cam), x0, y0, w, rows, C.byref(b), C.c_void_p(0), 1, C.byref(t)), "rt_render_aov_tile")
+            else:
+                _check(lib.rt_render_aov(self._h, C.byref(cam), C.byref(shard) if shard else None, C.byref(b), C.c_void_p(0), 1, C.byref(t)),
+                       "rt_render_aov")
+            out = {}
+            for key, field, dtype, per in AOV_CHANNELS:
+                a = np.empty((rows, w, per) if per > 1 else (rows, w), dtype=dtype)
+                _check(lib.rt_copy_to_host(a.ctypes.data, dev[key], a.nbytes), "rt_copy_to_host")
+                out[key] = a
+        finally:
+            for d in dev.values():
+                lib.rt_device_free(d)
+        return out, t
 
     def last_kernel_ms(self):
         ms = C.c_float()
