@@ -178,7 +178,7 @@ typedef struct rt_scene rt_scene;   /* opaque: device-resident repacked scene */
  * otherwise. */
 enum { RT_TRAVERSAL_AUTO = 0, RT_TRAVERSAL_EXACT = 1, RT_TRAVERSAL_GUARDED = 2 };
 enum { RT_BUILD_HOST_SAH = 0, RT_BUILD_DEVICE_LBVH = 1 };
-enum { RT_KERNEL_AUTO = 0, RT_KERNEL_MEGA = 1, RT_KERNEL_WAVEFRONT = 2 };
+enum { RT_KERNEL_AUTO = 0, RT_KERNEL_MEGA = 1, RT_KERNEL_WAVEFRONT = 2 /* retired experiment: rendering answers RT_ERR_UNSUPPORTED */ };
 typedef struct rt_config {
     uint32_t struct_bytes;        /* sizeof(rt_config) as the caller compiled it */
     /* --- fixed at rt_scene_create_ex ------------------------------------------------------------ */
@@ -212,13 +212,13 @@ typedef struct rt_config {
     int32_t  k_inner, k_shade;    /* wave scheduling thresholds in lanes (0 = defaults: 24 / 48; 32 / 52 for the LDS-resident guarded walk, 48 / 52 for big scenes with distance-aware margins) */
     int32_t  reserve_chunk;       /* work indices per queue reservation in units of 64 (0 = auto) */
     int32_t  reserve_taper;       /* 1 (default): reservations shrink towards the end of a pass */
-    int32_t  wavefront_paths;     /* RT_KERNEL_WAVEFRONT: paths in flight per wave, >= 128 (0 = auto) */
-    int32_t  wavefront_exchange;  /* … lanes that must be free before a wave exchanges results for new rays (0 = auto) */
+    int32_t  wavefront_paths;     /* (RT_KERNEL_WAVEFRONT, retired: ignored) */
+    int32_t  wavefront_exchange;  /* (RT_KERNEL_WAVEFRONT, retired: ignored) */
     int32_t  wide_nodes;          /* 0 (default): scenes with distance-aware margins (guard_dynamic_margins) walk the 4-wide form of their tree —
                                      half the dependent record loads per ray, and with the growth of the boxes in parametric form fewer
                                      instructions as well (BASELINE configs[4] +1.7 %) —, every other scene child-pair nodes; -1: pair nodes
-                                     always; 1: 4-wide nodes for every guarded walk — developer build only (RT_ERR_UNSUPPORTED in the
-                                     shipped library): 6 % slower than the octant pair walk on S-rtiow */
+                                     always; 1: 4-wide nodes for every guarded walk — a retired experiment, 6 % slower than the octant
+                                     pair walk on S-rtiow: rendering answers RT_ERR_UNSUPPORTED */
     int32_t  guard_dynamic_margins; /* (fixed at create) margins of the guarded walk's small spheres: 0 = auto (distance-aware
                                      where one margin per sphere would exceed a quarter of the smallest radius), 1 = always one
                                      margin per sphere, 2 = always distance-aware */

@@ -16,18 +16,9 @@
 #include "rt_kernel.hip.inc"
 #include "rt_primary.hip.inc"
 #include "rt_aov.hip.inc"
-// Developer build only (make dev → librtp_amd_dev.so, -DRTP_DEV_BUILD): the two experimental kernels that lost to render_kernel
-// (rt_kernel_wf.hip.inc: wave-owned path pools in L2, −37 %; rt_kernel_queue.hip.inc: T-wave/S-wave LDS queues, −30 %; docs/LOG.md) and
-// the rt_debug_* entry points (exhaustive on-device checks of recip / sqrt_cr / sphere_root, the RTP_STATS counters).  The shipped
-// library contains none of them.
-#ifdef RTP_DEV_BUILD
-#define RTP_DEV_QUEUE_KERNEL 1
-#include "rt_kernel_wf.hip.inc"
-#include "rt_kernel_queue.hip.inc"
-#else
-namespace rtk { constexpr int kWfBlock = 256, kWfRayRows = 0, kWfHitRows = 0; }
-#define RTP_WF_MIN_WAVES 4
-#endif
+// Developer build only (make dev → librtp_amd_dev.so, -DRTP_DEV_BUILD): the rt_debug_* entry points (exhaustive on-device checks of
+// recip / sqrt_cr / sphere_root, the device LBVH builder on its own, the tripwire, the RTP_STATS counters) at the end of this file.
+// The shipped library contains none of them.
 
 namespace {
 
@@ -65,6 +56,7 @@ using rtaccel::kSampleBytes;
 constexpr uint32_t kLdsLimit = 160 * 1024;
 using rtaccel::kMaxPasses;               // (rt_accel.h: plan_passes)
 constexpr int kTimedPasses = 64;        // trace launches individually timed per call
+constexpr uint32_t kResumeBits = 18;    // resume table: 2^18 entries
 
 // Counter block of a scene handle (uint32 words): work counters of the trace launches, of the exact
 // re-walk launches, the flagged-sample counts (one each per pass), then 16 developer words.
@@ -155,8 +147,7 @@ rtaccel::PackOptions pack_options(const rt_config &cfg, const rt_scene_desc *d =
     o.dynamic = cfg.guard_dynamic_margins;
     if (cfg.guard_gamma_ulps > 0.0f) o.gamma = (double)cfg.guard_gamma_ulps * 5.9604644775390625e-8;
     o.leaf_table = cfg.guard_exact_leaf_table != 0;
-    // (the developer build's wavefront kernel arms its rays itself: everything stays in the tree)
-    o.front_max = (cfg.guard_front_primitives < 0 || cfg.kernel == RT_KERNEL_WAVEFRONT) ? 0 : rtaccel::kMaxFront;
+    o.front_max = cfg.guard_front_primitives < 0 ? 0 : rtaccel::kMaxFront;
     return o;
 }
 uint32_t bail_share_of(const rt_config &cfg) {      // in 1/256ths; 0 = never
@@ -196,8 +187,8 @@ struct rt_scene {
     float4 *tnodes = nullptr, *xnodes = nullptr;
     int32_t num_tnodes = 0, num_top = 0, num_top_pairs = 0;
     float4 *hnodes = nullptr;       // pair records with binary16 planes (guarded walk from global memory)
-    float4 *wnodes = nullptr, *whnodes = nullptr;     // the same tree as 4-wide nodes (fp32 / binary16 boxes); null: pair nodes only
-    int32_t num_wide = 0, num_top_wide = 0, wroot = rtk::kDone, wide_depth = 0;
+    float4 *whnodes = nullptr;      // the same tree as 4-wide nodes (binary16 boxes: step_wide_par); null: pair nodes only
+    int32_t num_wide = 0, wroot = rtk::kDone, wide_depth = 0;
     float4 *nodes = nullptr, *spheres = nullptr, *planes = nullptr, *materials = nullptr, *tex_data = nullptr;
     int32_t *sphere_mat = nullptr;
     int4 *tex_info = nullptr;
@@ -247,8 +238,6 @@ struct rt_scene {
     // what the lists in `cand` (and the fetch order behind them) were made for: a call with the same view of the same tree on the
     // same stream — the next sample batch of a progressive render, the next frame of a still — reuses them (0.4 ms at 1080p)
     struct CandKey { float view[12]; int32_t dims[9]; int repacks; hipStream_t stream; bool valid = false; } cand_key;
-    float4 *wf_pool = nullptr;      // render_kernel_wf: ray/hit stacks of every resident wave, grown on demand
-    size_t wf_pool_float4s = 0;
     int32_t num_internal = 0, num_spheres = 0, num_planes = 0, num_materials = 0, root = rtk::kDone, tree_depth = 0;
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;
     std::vector<hipEvent_t> pass_events;   // per pass: before the trace launch, after it, after the exact re-walk (first kTimedPasses passes)
@@ -338,7 +327,7 @@ rt_status fill_params(const rt_scene *sc, const rt_camera_data *cam, const rt_sh
         P.tile_y0 = tile->y0;
     }
     P.nodes = sc->nodes; P.hnodes = sc->hnodes; P.num_internal = sc->num_internal; P.root = sc->root;
-    P.wnodes = sc->wnodes; P.whnodes = sc->whnodes; P.num_wide = sc->num_wide; P.wroot = sc->wroot;
+    P.whnodes = sc->whnodes; P.wroot = sc->wroot;
     P.tnodes = sc->tnodes; P.num_tnodes = sc->num_tnodes;
     P.xnodes = sc->xnodes; P.num_top = sc->num_top;
     P.spheres = sc->spheres; P.num_spheres = sc->num_spheres;
@@ -406,18 +395,18 @@ rt_status repack_for_camera(rt_scene *sc, const float cam[3], hipStream_t stream
         return RT_OK;
     }
     HIP_TRY(hipStreamSynchronize(stream));          // the old tables may still be in use on this stream
-    float4 *nodes = nullptr, *hnodes = nullptr, *wnodes = nullptr, *whnodes = nullptr, *leaf_boxes = nullptr, *plane_leaf_boxes = nullptr;
+    float4 *nodes = nullptr, *hnodes = nullptr, *whnodes = nullptr, *leaf_boxes = nullptr, *plane_leaf_boxes = nullptr;
     rt_status st = RT_OK;
     if ((st = upload(pk.nodes, (void **)&nodes)) != RT_OK || (st = upload(pk.hnodes, (void **)&hnodes)) != RT_OK ||
-        (st = upload(pk.wnodes, (void **)&wnodes)) != RT_OK || (st = upload(pk.whnodes, (void **)&whnodes)) != RT_OK ||
+        (st = upload(pk.whnodes, (void **)&whnodes)) != RT_OK ||
         (st = upload(pk.leaf_boxes, (void **)&leaf_boxes)) != RT_OK || (st = upload(pk.plane_leaf_boxes, (void **)&plane_leaf_boxes)) != RT_OK) {
-        (void)hipFree(nodes); (void)hipFree(hnodes); (void)hipFree(wnodes); (void)hipFree(whnodes); (void)hipFree(leaf_boxes); (void)hipFree(plane_leaf_boxes);
+        (void)hipFree(nodes); (void)hipFree(hnodes); (void)hipFree(whnodes); (void)hipFree(leaf_boxes); (void)hipFree(plane_leaf_boxes);
         return st;
     }
-    (void)hipFree(sc->nodes); (void)hipFree(sc->hnodes); (void)hipFree(sc->wnodes); (void)hipFree(sc->whnodes);
+    (void)hipFree(sc->nodes); (void)hipFree(sc->hnodes); (void)hipFree(sc->whnodes);
     (void)hipFree(sc->leaf_boxes); (void)hipFree(sc->plane_leaf_boxes);
-    sc->nodes = nodes; sc->hnodes = hnodes; sc->wnodes = wnodes; sc->whnodes = whnodes; sc->leaf_boxes = leaf_boxes; sc->plane_leaf_boxes = plane_leaf_boxes;
-    sc->num_wide = pk.num_wide; sc->num_top_wide = pk.num_top_wide; sc->wroot = pk.wroot; sc->wide_depth = pk.wide_depth;
+    sc->nodes = nodes; sc->hnodes = hnodes; sc->whnodes = whnodes; sc->leaf_boxes = leaf_boxes; sc->plane_leaf_boxes = plane_leaf_boxes;
+    sc->num_wide = pk.num_wide; sc->wroot = pk.wroot; sc->wide_depth = pk.wide_depth;
     sc->num_internal = pk.num_internal;
     sc->num_top_pairs = pk.num_top_pairs;
     sc->root = pk.root;
@@ -581,9 +570,8 @@ rt_status rt_scene_create_ex(const rt_scene_desc *desc, const rt_config *user_cf
     } else {
         if ((st = upload(pk.nodes, (void **)&sc->nodes)) != RT_OK) return bail(st);
         if ((st = upload(pk.hnodes, (void **)&sc->hnodes)) != RT_OK) return bail(st);
-        if ((st = upload(pk.wnodes, (void **)&sc->wnodes)) != RT_OK) return bail(st);
         if ((st = upload(pk.whnodes, (void **)&sc->whnodes)) != RT_OK) return bail(st);
-        sc->num_wide = pk.num_wide; sc->num_top_wide = pk.num_top_wide; sc->wroot = pk.wroot; sc->wide_depth = pk.wide_depth;
+        sc->num_wide = pk.num_wide; sc->wroot = pk.wroot; sc->wide_depth = pk.wide_depth;
     }
     if ((st = upload(pk.tnodes, (void **)&sc->tnodes)) != RT_OK) return bail(st);
     sc->num_tnodes = pk.num_tnodes;
@@ -626,10 +614,10 @@ rt_status rt_scene_destroy(rt_scene *sc) {
     if (!sc) return RT_OK;
     (void)hipFree(sc->tnodes);
     (void)hipFree(sc->xnodes);
-    (void)hipFree(sc->nodes); (void)hipFree(sc->hnodes); (void)hipFree(sc->wnodes); (void)hipFree(sc->whnodes);
+    (void)hipFree(sc->nodes); (void)hipFree(sc->hnodes); (void)hipFree(sc->whnodes);
     (void)hipFree(sc->spheres); (void)hipFree(sc->planes); (void)hipFree(sc->materials);
     (void)hipFree(sc->sphere_mat); (void)hipFree(sc->tex_data); (void)hipFree(sc->tex_info); (void)hipFree(sc->queue); (void)hipFree(sc->slab);
-    (void)hipFree(sc->leaf_boxes); (void)hipFree(sc->plane_leaf_boxes); (void)hipFree(sc->flag_list); (void)hipFree(sc->wf_pool);
+    (void)hipFree(sc->leaf_boxes); (void)hipFree(sc->plane_leaf_boxes); (void)hipFree(sc->flag_list);
     (void)hipFree(sc->dirty); (void)hipFree(sc->dirty_list); (void)hipFree(sc->cand);
     (void)hipFree(sc->resume_tag); (void)hipFree(sc->resume_state);
     if (sc->aux_stream) (void)hipStreamDestroy(sc->aux_stream);
@@ -678,6 +666,8 @@ namespace {
 // and event times): a pass that gave up, or more flagged samples overall than the bail share, and the following frames go to the
 // exact walk; a frame that flagged more than kExploreShare makes the next AUTO frame an exact one, and the faster of the two per
 // sample stays (rt_config.guard_keep: the guarded walk stays whatever happens).
+// passes beyond the individually timed ones are priced at the mean of the timed ones
+float untimed_scale(int passes, int timed) { return (float)passes / (float)timed; }
 // trace / re-walk / primary-pass time of the handle's most recent frame, from its per-pass events (the frame must be done)
 rt_status frame_parts(rt_scene *sc, float &trace, float &rework, float &primary) {
     trace = rework = primary = 0.0f;
@@ -690,9 +680,8 @@ rt_status frame_parts(rt_scene *sc, float &trace, float &rework, float &primary)
         HIP_TRY(hipEventElapsedTime(&ms, sc->pass_events[4 * p + 2], sc->pass_events[4 * p + 3]));
         rework += ms;
     }
-    // passes beyond the individually timed ones are priced at the mean of the timed ones
     if (sc->timed_passes > 0) {
-        const float scale = (float)sc->last.trace_launches / (float)sc->timed_passes;
+        const float scale = untimed_scale((int)sc->last.trace_launches, sc->timed_passes);
         trace *= scale; rework *= scale; primary *= scale;
         float ms = 0.0f;          // + the per-pixel candidate lists, made once per call before the first pass
         HIP_TRY(hipEventElapsedTime(&ms, sc->ev_start, sc->pass_events[0]));
@@ -767,6 +756,7 @@ rt_status reserve_slab(rt_scene *sc, uint32_t num_pixels, int32_t spp, hipStream
     const rt_config &cfg = sc->cfg;
     plan = rtaccel::plan_passes(num_pixels, spp, cfg.workspace_bytes, sc->device_bytes, cfg.pass_spp);
     if (plan.passes < 1) return fail(RT_ERR_UNSUPPORTED, "image too large for the work index arithmetic");
+    if (plan.passes > kMaxPasses) return fail(RT_ERR_UNSUPPORTED, "more than 1024 passes (samples_per_pixel above 65536, or above 64512 at 2^24 pixels)");
     int pass_size = plan.pass_size;
     size_t need = (size_t)num_pixels * (size_t)slab_pitch_of(pass_size) * 3;
     if (sc->slab_floats < need) {
@@ -807,6 +797,12 @@ rt_status reserve_view_lists(rt_scene *sc, uint32_t num_pixels, hipStream_t stre
     }
     return RT_OK;
 }
+// P's view of them: the lists, the fetch order behind them and the count of pixels with a list (counts[2 * blocks] after the scan)
+void bind_view_lists(const rt_scene *sc, rtk::KParams &P, uint32_t num_pixels, bool prim) {
+    P.cand = prim ? sc->cand : nullptr;
+    P.order = prim ? sc->cand + sc->cand_pixels * rtk::kCandWords : nullptr;
+    P.traced_pixels = prim ? P.order + sc->cand_pixels + 2 * (((size_t)num_pixels + rtk::kOrderBlock - 1) / rtk::kOrderBlock) : nullptr;
+}
 // The candidate lists and the fetch order made from them, for this view on this stream — unless the handle holds them already
 // (rt_config.reuse_view_lists): the same camera, image, shard and tree on the same stream
 rt_status make_view_lists(rt_scene *sc, const rt_camera_data *cam, const rtk::KParams &P, uint32_t num_pixels, hipStream_t stream) {
@@ -846,38 +842,86 @@ void launch_primary(const rt_scene *sc, const rtk::KParams &P, uint32_t num_pixe
     } else if (P.num_planes > 0) hipLaunchKernelGGL(rtk::primary_kernel<true>, dim3(pgrid), dim3(256), 0, stream, P);
     else hipLaunchKernelGGL(rtk::primary_kernel<false>, dim3(pgrid), dim3(256), 0, stream, P);
 }
-// rt_render and rt_render_tile: whole rows of a shard, or a rectangle
-rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shard, const Tile *tile, float *d_fb_sum, void *hip_stream,
-                      int32_t sync, rt_timing *timing) {
-    rtk::KParams P;
-    rt_status st = fill_params(sc, cam, shard, P, tile);
-    if (st != RT_OK) return st;
-    if ((st = check_device(sc)) != RT_OK) return st;
-    if (!d_fb_sum) return fail(RT_ERR_INVALID_ARG, "null framebuffer");
-    if ((st = timing_check(timing)) != RT_OK) return st;
-    const rt_config &cfg = sc->cfg;
-    hipStream_t stream = (hipStream_t)hip_stream;
-    P.fb = d_fb_sum;
-    timing_out(rt_timing{}, timing);
-    // what earlier frames of this handle reported about their guarded walk (no wait: whatever has landed by now)
-    if ((st = poll_feedback(sc, false)) != RT_OK) return st;
-    const size_t fb_bytes = (size_t)P.local_rows * P.row_w * 3 * sizeof(float);
-    if (P.local_rows == 0) return RT_OK;
-    if (P.spp <= 0 || P.max_depth <= 0) {     // the reference's loops add nothing: all-zero sums
-        HIP_TRY(hipMemsetAsync(d_fb_sum, 0, fb_bytes, stream));
-        if (sync) HIP_TRY(hipStreamSynchronize(stream));
-        sc->timed = false;
-        return RT_OK;
-    }
+// ---- rt_render's steps: the walk and its launch shapes (plan_launch), the buffers they need, the passes, the record of the frame
 
+// The margins were sized for ray origins within origin_radius of origin_center, and those of the small spheres for origins within
+// sqrt(d0_sq) of their cluster (NaN coordinates are within nothing)
+bool camera_within(const rt_camera_data *cam, const float c[3], double radius_sq) {
+    const double dx = (double)cam->origin.e[0] - c[0], dy = (double)cam->origin.e[1] - c[1], dz = (double)cam->origin.e[2] - c[2];
+    return dx * dx + dy * dy + dz * dz <= radius_sq;
+}
+// … and both with room to spare where the small spheres' margins matter, as the primary-visibility pass needs them: it takes
+// camera rays from the guarded walk's tree, so the far-origin test must never fire for one (the device compares in float: a hair of
+// slack)
+bool camera_inside_margins(const rt_scene *sc, const rt_camera_data *cam) {
+    return camera_within(cam, sc->guard.origin_center, (double)sc->guard.origin_radius * sc->guard.origin_radius) &&
+           !(sc->guard.num_small > 0 && !camera_within(cam, sc->guard.center, (double)sc->guard.d0_sq * (1.0 - 1e-5)));
+}
+
+// Step 2 of rt_render: the exact or the guarded walk, and the guarded walk's tree re-packed for a camera beyond its margins (which
+// changes the handle's tables: P is filled again)
+rt_status choose_traversal(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shard, const Tile *tile, hipStream_t stream, rtk::KParams &P,
+                           bool &guarded, bool &exploring) {
+    const rt_config &cfg = sc->cfg;
+    // (RT_KERNEL_WAVEFRONT and rt_config.wide_nodes = 1 were experiments, retired: −37 % and −6 % on S-rtiow; docs/LOG.md)
+    if (cfg.kernel == RT_KERNEL_WAVEFRONT) return fail(RT_ERR_UNSUPPORTED, "RT_KERNEL_WAVEFRONT was an experiment and has been retired: not in this library");
+    if (cfg.wide_nodes > 0) return fail(RT_ERR_UNSUPPORTED, "rt_config.wide_nodes = 1 was an experiment and has been retired: not in this library");
+    // only for eligible scenes (and, below, for cameras within the margins and tables that leave room for a useful stack)
+    guarded = sc->guard.ok && cfg.traversal != RT_TRAVERSAL_EXACT && P.root >= 0 && guarded_wanted(cfg, (int64_t)P.num_spheres + P.num_planes) &&
+              !(sc->guard_paused && !cfg.guard_keep);
+    // (AUTO only: one exact frame to time the guarded walk against — judge_frame)
+    exploring = guarded && sc->explore_exact && cfg.traversal == RT_TRAVERSAL_AUTO && !cfg.guard_keep;
+    if (exploring) guarded = false;
+    if (!guarded) return RT_OK;
+    // A camera outside the margins gets the tree re-packed with margins for where it is (once per growth of the reach; the exact
+    // walk's tables do not change).
+    const bool far_cam = !camera_within(cam, sc->guard.origin_center, (double)sc->guard.origin_radius * sc->guard.origin_radius) ||
+                         (sc->guard.num_small > 0 && !camera_within(cam, sc->guard.center, (double)sc->guard.d0_sq));
+    if (far_cam && !sc->repack_refused && std::isfinite(cam->origin.e[0]) && std::isfinite(cam->origin.e[1]) && std::isfinite(cam->origin.e[2]) &&
+        cfg.guard_repack) {
+        rt_status st = repack_for_camera(sc, cam->origin.e, stream);
+        if (st != RT_OK) return st;
+        float *fb = P.fb;
+        if ((st = fill_params(sc, cam, shard, P, tile)) != RT_OK) return st;       // table pointers and guard parameters changed
+        P.fb = fb;
+    }
+    if (!camera_within(cam, sc->guard.origin_center, (double)sc->guard.origin_radius * sc->guard.origin_radius)) guarded = false;
+    if (sc->repack_refused && sc->guard.num_small > 0 && !camera_within(cam, sc->guard.center, (double)sc->guard.d0_sq)) guarded = false;
+    return RT_OK;
+}
+
+// Launch shape of one walk: tables in LDS or not, LDS bytes per workgroup, workgroups per CU, stack rows per lane, treelet records
+struct Shape { bool in_lds; uint32_t lds_bytes; int wgs_per_cu; int32_t stack_levels; int32_t num_top; };
+enum class Walk { Exact, ExactSimple, Guarded };
+struct LaunchPlan {
+    Walk walk = Walk::Exact;
+    Shape exact{}, exact_s{}, fast{};       // the exact walk, its sphere-only build, the guarded walk
+    bool wide = false;                      // guarded walk on the 4-wide nodes (step_wide_par)
+    bool dyn = false;                       // guarded walk with distance-aware margins
+    bool simple = false;                    // guarded walk, sphere-only build
+    bool prim = false;                      // primary-visibility pass before the trace launch
+    bool overlap = false;                   // exact re-walk on the handle's second stream
+    bool resume = false;                    // resume table for flagged samples
+    uint32_t flag_chunk_words = 0;          // LDS words per wave for its chunk of the flagged-sample list (rt_kernel.hip.inc, flag_collect): 2, or 0
+    int32_t k_inner = 0, k_shade = 0;       // vote thresholds of the trace launch
+    bool guarded() const { return walk == Walk::Guarded; }
+    bool sphere_only() const { return walk == Walk::ExactSimple || (walk == Walk::Guarded && simple); }
+    uint32_t block() const { return sphere_only() ? (uint32_t)rtk::kSimpleBlock : (uint32_t)rtk::kBlock; }      // threads per workgroup of the trace launch
+    const Shape &trace_shape() const { return walk == Walk::Guarded ? fast : (walk == Walk::ExactSimple ? exact_s : exact); }
+};
+
+// Step 3 of rt_render: the launch shapes of the walks, from the handle's tables, its config and P alone (no HIP call, nothing
+// of the handle changes).  `guarded`: what choose_traversal decided; the plan may still fall back to the exact walk.
+LaunchPlan plan_launch(const rt_scene *sc, const rt_camera_data *cam, const rtk::KParams &P, bool guarded) {
+    const rt_config &cfg = sc->cfg;
+    LaunchPlan L;
     const uint32_t waves = rtk::kBlock / rtk::kWave;
     const uint32_t pool_bytes = waves * 8u;                  // per-wave reserved work range
     const uint64_t prim_f4 = (uint64_t)P.num_spheres + (uint64_t)P.num_planes * 5 + (uint64_t)P.num_materials * RTP_LDS_MAT_ROWS +      // LDS keeps the first RTP_LDS_MAT_ROWS of the 3 material rows
                              ((uint64_t)P.num_spheres + 3) / 4;
 
-    // ---- exact (threaded) walk: launch shape
-    struct Shape { bool in_lds; uint32_t lds_bytes; int wgs_per_cu; int32_t stack_levels; int32_t num_top; };
-    Shape exact{};
+    // ---- exact (threaded) walk
+    Shape &exact = L.exact;
     {
         const uint64_t scene_bytes = (((uint64_t)P.num_tnodes + 1) * 2 + prim_f4) * 16;
         exact.in_lds = cfg.scene_in_lds && scene_bytes + pool_bytes <= kLdsLimit;
@@ -899,110 +943,59 @@ rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *s
     // workgroups, 8 waves per SIMD) for WHOLE passes of scenes that have none of those: S-rtiow 5 210 against 4 855 Msamples/s.
     // The re-walk of a list keeps the general build: it is a few long paths, and those run slower in the tighter kernel
     // (headline frame: re-walk 3.1 ms instead of 1.7).
-    Shape exact_s{};
     bool exact_simple = exact.in_lds && cfg.sphere_only_kernel >= 0 && P.num_planes == 0 && sc->tex_data == nullptr && !sc->absorbing_glass &&
                         cfg.workgroups_per_cu == 0 && P.num_spheres > 0;
     if (exact_simple) {
         const uint64_t simple_bytes = (((uint64_t)P.num_tnodes + 1) * 4 + (uint64_t)P.num_spheres + ((uint64_t)P.num_spheres + 3) / 4) * 16;
         const uint64_t simple_pool = (uint64_t)(rtk::kSimpleBlock / rtk::kWave) * 8u + 16u * rtk::kConstRows;      // work ranges + the constants block
-        exact_s.in_lds = true;
-        exact_s.wgs_per_cu = rtk::kSimpleWaves * 256 / rtk::kSimpleBlock;
-        exact_s.lds_bytes = (uint32_t)(simple_bytes + simple_pool);
-        if ((uint64_t)exact_s.wgs_per_cu * exact_s.lds_bytes > kLdsLimit) exact_simple = false;
+        L.exact_s.in_lds = true;
+        L.exact_s.wgs_per_cu = rtk::kSimpleWaves * 256 / rtk::kSimpleBlock;
+        L.exact_s.lds_bytes = (uint32_t)(simple_bytes + simple_pool);
+        if ((uint64_t)L.exact_s.wgs_per_cu * L.exact_s.lds_bytes > kLdsLimit) exact_simple = false;
     }
 
-    // ---- guarded near-first walk: only for eligible scenes that fit LDS with a useful stack
-    bool guarded = sc->guard.ok && cfg.traversal != RT_TRAVERSAL_EXACT && P.root >= 0 && guarded_wanted(cfg, (int64_t)P.num_spheres + P.num_planes) &&
-                   !(sc->guard_paused && !cfg.guard_keep);
-    // (AUTO only: one exact frame to time the guarded walk against — judge_frame)
-    const bool exploring = guarded && sc->explore_exact && cfg.traversal == RT_TRAVERSAL_AUTO && !cfg.guard_keep;
-    if (exploring) guarded = false;
-    Shape fast{};
-    // kernel form of the guarded pass: render_kernel (a lane owns a path) or render_kernel_wf (a wave owns a pool of paths)
-    const bool want_wavefront = cfg.kernel == RT_KERNEL_WAVEFRONT;
-#ifndef RTP_DEV_BUILD
-    if (want_wavefront) return fail(RT_ERR_UNSUPPORTED, "RT_KERNEL_WAVEFRONT is an experiment of the developer build (make dev): not in this library");
-#endif
-    // 4-wide nodes (where the scene has them: a host-built tree with at least one inner node).  Scenes with distance-aware margins
-    // walk them by default (step_wide_par: half the dependent record loads of the pair walk and, with the growth in parametric
-    // form, fewer instructions per ray — configs[4] +1.7 %).  For every other walk they stay an experiment of the developer build
-    // (rt_config.wide_nodes = 1: measured 6 % slower on S-rtiow; docs/LOG.md); the wavefront kernel walks pairs
-#ifndef RTP_DEV_BUILD
-    if (cfg.wide_nodes > 0) return fail(RT_ERR_UNSUPPORTED, "rt_config.wide_nodes = 1 is an experiment of the developer build (make dev): not in this library");
-#endif
-    // (it arms its rays itself: a tree without its front primitives — rt_accel.h — is not its to walk)
-    if (want_wavefront && sc->guard.num_front > 0)
-        return fail(RT_ERR_UNSUPPORTED, "the wavefront kernel needs a scene handle created with it selected (its tree must hold every primitive)");
-    // (a function of the handle's tables: evaluated again after a re-pack for a far camera — which may turn distance-aware margins
-    // on or off — below)
-    auto wide_nodes_wanted = [&]() {
-        // (step_wide_par tells an empty child slot by its box — the finite inverted (65504, -65504) of the binary16 table — which holds
-        // while the growth stays below 65504: it never exceeds dyn_k x (twice the radius every ray origin lies within)^2)
-        const double growth_max = (double)sc->guard.dyn_k * 4.0 * (double)sc->guard.origin_radius * (double)sc->guard.origin_radius;
-        const bool wide_par_scene = sc->guard.dyn_k > 0.0f && growth_max < 16384.0;
-        return sc->whnodes != nullptr && sc->num_wide > 0 && !want_wavefront && (cfg.wide_nodes > 0 || (cfg.wide_nodes == 0 && wide_par_scene));
-    };
-    bool wide = wide_nodes_wanted();
-    uint32_t gblock = want_wavefront ? (uint32_t)rtk::kWfBlock : (uint32_t)rtk::kBlock;     // threads per workgroup of the guarded pass
-    int gwgs_per_cu = (want_wavefront ? RTP_WF_MIN_WAVES : RTP_MIN_WAVES) * 256 / (int)gblock;
-    // the sphere-only build of the octant walk (render_kernel<…, kSimple>): 1024-thread workgroups, 8 waves per SIMD
+    // ---- guarded near-first walk: only where its tables leave room for a useful stack
+    // 4-wide nodes (where the scene has them: a host-built tree with at least one inner node) for scenes with distance-aware
+    // margins (step_wide_par: half the dependent record loads of the pair walk and, with the growth in parametric form, fewer
+    // instructions per ray — configs[4] +1.7 %).  (step_wide_par tells an empty child slot by its box — the finite inverted
+    // (65504, -65504) of the binary16 table — which holds while the growth stays below 65504: it never exceeds dyn_k x (twice the
+    // radius every ray origin lies within)^2)
+    const bool dyn_scene = sc->guard.dyn_k > 0.0f;          // distance-aware margins (big or widely spread scenes)
+    const double growth_max = (double)sc->guard.dyn_k * 4.0 * (double)sc->guard.origin_radius * (double)sc->guard.origin_radius;
+    bool wide = sc->whnodes != nullptr && sc->num_wide > 0 && cfg.wide_nodes == 0 && dyn_scene && growth_max < 16384.0;
     bool simple = false;
-    uint32_t flag_chunk_words = 0;       // LDS words per wave for its chunk of the flagged-sample list (rt_kernel.hip.inc, flag_collect): 2, or 0
+    Shape &fast = L.fast;
     if (guarded) {
-        // The margins were sized for ray origins within origin_radius of origin_center, and those of the small
-        // spheres for origins within sqrt(d0_sq) of their cluster: a camera outside either gets the tree re-packed
-        // with margins for where it is (once per growth of the reach; the exact walk's tables do not change).
-        auto outside = [&](const float *c, double radius_sq) {
-            const double dx = (double)cam->origin.e[0] - c[0], dy = (double)cam->origin.e[1] - c[1], dz = (double)cam->origin.e[2] - c[2];
-            return !(dx * dx + dy * dy + dz * dz <= radius_sq);
-        };
-        const bool far_cam = outside(sc->guard.origin_center, (double)sc->guard.origin_radius * sc->guard.origin_radius) ||
-                             (sc->guard.num_small > 0 && outside(sc->guard.center, (double)sc->guard.d0_sq));
-        if (far_cam && !sc->repack_refused && std::isfinite(cam->origin.e[0]) && std::isfinite(cam->origin.e[1]) &&
-            std::isfinite(cam->origin.e[2]) && cfg.guard_repack) {
-            st = repack_for_camera(sc, cam->origin.e, stream);
-            if (st != RT_OK) return st;
-            st = fill_params(sc, cam, shard, P, tile);       // table pointers and guard parameters changed
-            if (st != RT_OK) return st;
-            P.fb = d_fb_sum;
-            wide = wide_nodes_wanted();
-        }
-        if (outside(sc->guard.origin_center, (double)sc->guard.origin_radius * sc->guard.origin_radius)) guarded = false;
-        if (sc->repack_refused && sc->guard.num_small > 0 && outside(sc->guard.center, (double)sc->guard.d0_sq)) guarded = false;
-    }
-    if (guarded) {
-        // fp32 records when LDS-resident: 7 float4 per wide node, 4 per pair node — 5 in the octant layout the kernel stages
-        // for the pair walk with static margins (rt_kernel.hip.inc, step_octant)
-        const bool octant = (RTP_OCTANT != 0) && !wide && !want_wavefront && !(sc->guard.dyn_k > 0.0f);
-        uint64_t table_bytes = ((wide ? (uint64_t)P.num_wide * 7 : (uint64_t)P.num_internal * (octant ? 5 : 4)) + prim_f4) * 16 +
-                               (!want_wavefront ? kGuardBlockBytes : 0u);      // + the guarded kernels' constants block
+        uint32_t gblock = (uint32_t)rtk::kBlock;           // threads per workgroup of the guarded pass
+        int gwgs_per_cu = RTP_MIN_WAVES * 256 / (int)gblock;
+        // fp32 records when LDS-resident: 5 float4 per pair node in the octant layout the kernel stages (rt_kernel.hip.inc, step_octant)
+        // + the guarded kernels' constants block
+        uint64_t table_bytes = ((uint64_t)P.num_internal * 5 + prim_f4) * 16 + kGuardBlockBytes;
         const int32_t deepest = wide ? 3 * sc->wide_depth : sc->tree_depth;          // a wide node leaves up to three children waiting
         const int32_t want = deepest + 1 > 2 ? deepest + 1 : 2;       // never overflows
         uint32_t per_level = gblock * 4u;
         uint32_t pool_extra = 0;       // (the sphere-only builds have four more waves' work ranges than pool_bytes counts)
-        // sphere-only build: no planes, no textures, leaf boxes recomputed from the spheres; its LDS holds no material rows
-        // (all three come from global memory), which pays for the wider stack rows of 1024 lanes
-        simple = octant && cfg.scene_in_lds != 0 && cfg.sphere_only_kernel >= 0 && P.num_planes == 0 && sc->tex_data == nullptr &&
-                 P.leaf_boxes == nullptr && cfg.workgroups_per_cu == 0 && !sc->absorbing_glass;
-        if (simple) {
+        // the sphere-only build of the octant walk (render_kernel<…, kSimple>: 1024-thread workgroups, 8 waves per SIMD): no planes,
+        // no textures, leaf boxes recomputed from the spheres; its LDS holds no material rows (all three come from global memory),
+        // which pays for the wider stack rows of 1024 lanes
+        const bool plain = cfg.sphere_only_kernel >= 0 && P.num_planes == 0 && sc->tex_data == nullptr && P.leaf_boxes == nullptr &&
+                           cfg.workgroups_per_cu == 0 && !sc->absorbing_glass;
+        if (plain && !dyn_scene && cfg.scene_in_lds != 0) {
             const uint64_t simple_bytes = ((uint64_t)P.num_internal * 5 + (uint64_t)P.num_spheres + ((uint64_t)P.num_spheres + 3) / 4) * 16;
             const uint64_t budget = kLdsLimit / 2;
             const int64_t fit = simple_bytes + pool_bytes + 256 < budget ? (int64_t)((budget - simple_bytes - pool_bytes - 256) / ((uint64_t)rtk::kSimpleBlock * 4u)) : 0;
             if (fit >= 6 || fit >= want) {          // at least the sentinel + 5 levels: below that the re-walk launch eats the gain
+                simple = true;
                 gblock = (uint32_t)rtk::kSimpleBlock;
                 gwgs_per_cu = rtk::kSimpleWaves * 256 / rtk::kSimpleBlock;
                 table_bytes = simple_bytes + ((uint64_t)(rtk::kSimpleBlock / rtk::kWave) * 8u - pool_bytes) + kGuardBlockBytes;      // + the four extra waves' work ranges + the constants block
                 per_level = gblock * 4u;
-            } else {
-                simple = false;
             }
         }
         // … and of the walk through L1 / L2 for scenes with distance-aware margins (step_pair_par on pair nodes: the 4-wide step does
         // not fit 64 registers): sphere-only scenes beyond what LDS holds — S-rtiow x 785 … 99 857 spheres: +7 … +10 % over the general
         // build on 4-wide nodes (8.1 / 7.7 / 6.7 / 3.9 against 7.5 / 7.2 / 6.2 / 3.6 Gsamples/s; tools/size_sweep.py)
-        const bool dyn_global_scene = sc->guard.dyn_k > 0.0f && !want_wavefront && cfg.wide_nodes <= 0;
-        if (!simple && dyn_global_scene && cfg.sphere_only_kernel >= 0 && P.num_planes == 0 && sc->tex_data == nullptr && P.leaf_boxes == nullptr &&
-            cfg.workgroups_per_cu == 0 && !sc->absorbing_glass) {
+        if (plain && dyn_scene) {
             simple = true;
             wide = false;
             gblock = (uint32_t)rtk::kSimpleBlock;
@@ -1024,8 +1017,7 @@ rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *s
         // full stack, two workgroups per CU whatever the size of the tree).  The LDS-resident form of that walk lost on every
         // random scene it was tried on — tables of a thousand nodes leave room for one workgroup per CU or for a stack of four,
         // and the rays a short stack hands to the exact walk cost more than L1 does: tools/dyn_probe.py, docs/LOG.md round 4.
-        const bool dyn_global = sc->guard.dyn_k > 0.0f && !want_wavefront;
-        fast.in_lds = cfg.scene_in_lds != 0 && !dyn_global;
+        fast.in_lds = cfg.scene_in_lds != 0 && !dyn_scene;
         if (fast.in_lds) {
             fast.stack_levels = levels_for(table_bytes, fast.wgs_per_cu);
             while (fast.wgs_per_cu > 1 && fast.stack_levels < min_levels) fast.stack_levels = levels_for(table_bytes, --fast.wgs_per_cu);
@@ -1033,8 +1025,7 @@ rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *s
         }
         // (step_pair_par / step_wide_par, the walks of scenes with distance-aware margins, keep a sentinel in level 0 — one level
         // more for the same twelve entries — and two rows of per-ray values behind the stack)
-        const bool dyn_pair = !fast.in_lds && dyn_global;       // (pair nodes, or their 4-wide form)
-        const int32_t extra_rows = dyn_pair ? 2 : 0;
+        const int32_t extra_rows = dyn_scene ? 2 : 0;
         if (!fast.in_lds) {
             // tables through L1/L2: a 12-entry stack per lane (deeper ones are rare enough to flag), the rest of
             // the workgroup's LDS share holds the top of the tree
@@ -1042,48 +1033,55 @@ rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *s
             const uint64_t budget = kLdsLimit / (uint64_t)fast.wgs_per_cu;
             const int64_t fit = budget > pool_bytes + pool_extra + kGuardBlockBytes ? (int64_t)((budget - pool_bytes - pool_extra - kGuardBlockBytes) / per_level) : 0;
             // (the 4-wide walk leaves up to three children of a node waiting, and LDS holds nothing but the stacks: twenty entries)
-            const int32_t cap = (dyn_pair ? (wide ? 21 : 13) : 12) + extra_rows;
+            const int32_t cap = (dyn_scene ? (wide ? 21 : 13) : 12) + extra_rows;
             fast.stack_levels = (int32_t)std::min<int64_t>(std::min<int64_t>(fit, want + extra_rows), cap);
         }
         if (const int forced = cfg.stack_levels) fast.stack_levels = forced + extra_rows < fast.stack_levels ? forced + extra_rows : fast.stack_levels;
         if (fast.stack_levels - extra_rows < (want < 2 ? want : 2)) guarded = false;
         // (the walks of scenes with distance-aware margins read every record through L1 / L2: no treelet)
-        if (!fast.in_lds && cfg.lds_treelet && !dyn_pair) {
+        if (!fast.in_lds && cfg.lds_treelet && !dyn_scene) {
             const uint64_t budget = kLdsLimit / (uint64_t)fast.wgs_per_cu;
-            const uint64_t used = pool_bytes + (uint64_t)fast.stack_levels * per_level + (!want_wavefront ? kGuardBlockBytes : 0u);
-            const int64_t fit = budget > used ? (int64_t)((budget - used) / (wide ? 64 : 32)) : 0;
-            const int32_t top_have = wide ? sc->num_top_wide : sc->num_top_pairs;
-            fast.num_top = (int32_t)(fit < top_have ? fit : top_have);
+            const uint64_t used = pool_bytes + (uint64_t)fast.stack_levels * per_level + kGuardBlockBytes;
+            const int64_t fit = budget > used ? (int64_t)((budget - used) / 32) : 0;
+            fast.num_top = (int32_t)(fit < sc->num_top_pairs ? fit : sc->num_top_pairs);
         }
-        if ((!fast.in_lds && !dyn_global_scene) || fast.wgs_per_cu != gwgs_per_cu) simple = false;      // (cannot happen after the fit test above; the general kernel is always right)
-        fast.lds_bytes = (uint32_t)((fast.in_lds ? table_bytes : (uint64_t)fast.num_top * (wide ? 64 : 32) + pool_extra + (!want_wavefront ? kGuardBlockBytes : 0u)) + pool_bytes +
+        if ((!fast.in_lds && !dyn_scene) || fast.wgs_per_cu != gwgs_per_cu) simple = false;      // (cannot happen after the fit test above; the general kernel is always right)
+        fast.lds_bytes = (uint32_t)((fast.in_lds ? table_bytes : (uint64_t)fast.num_top * 32 + pool_extra + kGuardBlockBytes) + pool_bytes +
                                     (uint64_t)fast.stack_levels * per_level);
         if (const int w = cfg.workgroups_per_cu) { if ((uint64_t)w * fast.lds_bytes <= kLdsLimit) fast.wgs_per_cu = w; }
-        if (!want_wavefront) flag_chunk_words = 2u;          // (the wave's chunk of the flagged-sample list: inside kGuardBlockBytes)
+        L.flag_chunk_words = 2u;          // (the wave's chunk of the flagged-sample list: inside kGuardBlockBytes)
     }
-    bool use_queue = false;
-#ifdef RTP_DEV_QUEUE_KERNEL
-    if (const char *kq = getenv("RTP_KERNEL")) use_queue = std::string(kq) == "queue";      // developer build only
-#endif
-    if (use_queue) guarded = false;
+    L.walk = guarded ? Walk::Guarded : (exact_simple ? Walk::ExactSimple : Walk::Exact);
+    L.wide = guarded && wide;
+    L.simple = simple;
+    L.dyn = guarded && dyn_scene;
+    // (not with a capped flag list or an unproven margin: a list that overflowed makes the re-walk rewrite EVERY slab entry
+    // while the other stream sums the rows of unflagged pixels — harmless only where both walks give the same bits)
+    L.overlap = guarded && cfg.overlap_rework >= 0 && cfg.flag_capacity == 0 && !gamma_unproven(cfg);
+    // Primary visibility without a walk (rt_primary.hip.inc): the pair-node walks of render_kernel — the LDS-resident octant walk
+    // with static margins, and the walk with distance-aware margins (through L1/L2) — and a camera inside the margins
+    L.prim = guarded && (L.dyn || fast.in_lds) && cfg.primary_visibility >= 0 && sc->nodes != nullptr && P.max_depth < rtk::kMaxPrimDepth &&
+             camera_inside_margins(sc, cam);
+    // resume table: not for paths longer than the depth field
+    L.resume = guarded && cfg.resume_flagged >= 0 && P.max_depth < rtk::kMaxPrimDepth;
+    // vote thresholds: the octant walk's (its pair steps are cheaper, so a block of them is worth starting for fewer idle lanes
+    // and a shade step is worth waiting for a few more): re-swept after step_octant, +1.0 %.  Scenes with distance-aware margins
+    // (records through L1/L2, step_pair_par / step_wide_par): a block of steps costs memory round trips on top of its
+    // instructions — worth starting only for a nearly full wave (S-100k, swept 16-52 x 44-56: +4 %)
+    const int32_t k_inner = guarded && fast.in_lds ? 32 : (L.dyn ? 48 : 24), k_shade = guarded && (fast.in_lds || L.dyn) ? 52 : 48;
+    L.k_inner = cfg.k_inner > 0 ? cfg.k_inner : k_inner;
+    L.k_shade = cfg.k_shade > 0 ? cfg.k_shade : k_shade;
+    return L;
+}
 
-    // Samples per pass (rt_accel.h, plan_passes): as many as the workspace budget admits (rt_config.workspace_bytes, default a
-    // sixteenth of the device; 12 bytes per sample), at least 64 where the work-index bound allows, and never more than the
-    // bound num_pixels * pass + 64 <= 2^30 of the kernel's 32-bit work index (div_magic, kFlagHole, kAbandonedCounter) —
-    // a forced rt_config.pass_spp included; the passes of a frame are made equally long.
-    // Fewer, larger launches amortise the end-of-launch tail — on a row shard of an N-GPU frame
-    // the pass grows N-fold, so a launch keeps the size it has on one GPU.
-    const uint32_t num_pixels = (uint32_t)P.local_rows * (uint32_t)P.row_w;
-    rtaccel::PassPlan plan;
-    if ((st = reserve_slab(sc, num_pixels, P.spp, stream, plan)) != RT_OK) return st;
-    const int pass_size = plan.pass_size;
-    P.slab = sc->slab;
-    P.num_pixels = num_pixels;
-    const int passes = plan.passes;
-    if (passes > kMaxPasses) return fail(RT_ERR_UNSUPPORTED, "more than 1024 passes (samples_per_pixel above 65536, or above 64512 at 2^24 pixels)");
-    if (guarded) {
+// Step 4 of rt_render: the handle's buffers for this call, grown where they are short.  A device short of memory for the view lists
+// renders without the primary-visibility pass (plan.prim = false).
+rt_status reserve_buffers(rt_scene *sc, const rtk::KParams &P, uint32_t num_pixels, hipStream_t stream, LaunchPlan &plan, rtaccel::PassPlan &passes) {
+    const rt_config &cfg = sc->cfg;
+    if (const rt_status st = reserve_slab(sc, num_pixels, P.spp, stream, passes)) return st;
+    if (plan.guarded()) {
         // flagged-sample list: a quarter of a pass's samples (a fuller list means "re-walk everything")
-        const size_t cap = (size_t)num_pixels * (size_t)pass_size / 4 + 65536;
+        const size_t cap = (size_t)num_pixels * (size_t)passes.pass_size / 4 + 65536;
         if (sc->flag_cap < cap) {
             HIP_TRY(hipStreamSynchronize(stream));
             (void)hipFree(sc->flag_list);
@@ -1109,41 +1107,138 @@ rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *s
             HIP_TRY(hipEventCreateWithFlags(&sc->ev_join, hipEventDisableTiming));
         }
     }
-
-    // kernel form of the guarded pass: render_kernel (a lane owns a path) or render_kernel_wf (a wave owns a pool of paths)
-    const bool dyn = guarded && sc->guard.dyn_k > 0.0f;                     // distance-aware margins (big or widely spread scenes)
-    const bool wavefront = guarded && want_wavefront && !use_queue && !dyn;
-    uint32_t wf_target = 0;
-    if (wavefront) {
-        wf_target = (uint32_t)(cfg.wavefront_paths > 0 ? cfg.wavefront_paths : 192);
-        if (wf_target < 128u) wf_target = 128u;              // below that a wave can run dry (rt_kernel_wf.hip.inc)
-        if (wf_target > 4096u) wf_target = 4096u;
-        wf_target = (wf_target + 63u) & ~63u;
-        const size_t waves_total = (size_t)sc->num_cus * fast.wgs_per_cu * (rtk::kWfBlock / rtk::kWave);
-        const size_t need_pool = waves_total * (size_t)(rtk::kWfRayRows + rtk::kWfHitRows) * wf_target;
-        if (sc->wf_pool_float4s < need_pool) {
-            HIP_TRY(hipStreamSynchronize(stream));
-            (void)hipFree(sc->wf_pool);
-            sc->wf_pool = nullptr;
-            sc->wf_pool_float4s = 0;
-            HIP_TRY(hipMalloc((void **)&sc->wf_pool, need_pool * sizeof(float4)));
-            sc->wf_pool_float4s = need_pool;
+    // resume table (made with the first guarded frame that uses it; a device short of memory renders without it)
+    if (plan.resume && sc->resume_tag == nullptr) {
+        if (hipMalloc((void **)&sc->resume_tag, sizeof(uint32_t) << kResumeBits) != hipSuccess ||
+            hipMalloc((void **)&sc->resume_state, (size_t)64 << kResumeBits) != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipFree(sc->resume_tag); (void)hipFree(sc->resume_state);
+            sc->resume_tag = nullptr; sc->resume_state = nullptr;
         }
     }
-    const Shape &main_shape = guarded ? fast : (exact_simple ? exact_s : exact);
+    return reserve_view_lists(sc, num_pixels, stream, plan.prim);
+}
+
+// The trace kernel of a plan (render_kernel<kLds, kThreaded, kDyn, kWide, kSimple, kPrim>)
+const void *trace_kernel(const LaunchPlan &L) {
+    using rtk::render_kernel;
+    if (L.walk == Walk::ExactSimple) return (const void *)render_kernel<true, true, false, false, true>;
+    if (L.walk == Walk::Exact) return L.exact.in_lds ? (const void *)render_kernel<true, true> : (const void *)render_kernel<false, true>;
+    if (L.wide)          // distance-aware margins on 4-wide nodes (step_wide_par)
+        return L.prim ? (const void *)render_kernel<false, false, true, true, false, true> : (const void *)render_kernel<false, false, true, true>;
+    if (L.dyn && L.simple)          // sphere-only scenes beyond what LDS holds: step_pair_par at 64 registers, 8 waves per SIMD
+        return L.prim ? (const void *)render_kernel<false, false, true, false, true, true> : (const void *)render_kernel<false, false, true, false, true>;
+    if (L.dyn) return L.prim ? (const void *)render_kernel<false, false, true, false, false, true> : (const void *)render_kernel<false, false, true>;
+    if (L.fast.in_lds && L.simple)
+        return L.prim ? (const void *)render_kernel<true, false, false, false, true, true> : (const void *)render_kernel<true, false, false, false, true>;
+    if (L.fast.in_lds) return L.prim ? (const void *)render_kernel<true, false, false, false, false, true> : (const void *)render_kernel<true, false>;
+    return (const void *)render_kernel<false, false>;
+}
+
+hipError_t launch(const void *kernel, uint32_t block, int grid, uint32_t lds, hipStream_t stream, const rtk::KParams &KP) {
+    hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    void *args[] = {(void *)&KP};
+    e = hipLaunchKernel(kernel, dim3(grid), dim3(block), args, lds, stream);
+    const hipError_t last = hipGetLastError();
+    return e != hipSuccess ? e : last;
+}
+
+// Work indices a wave reserves per atomicAdd on the pass's counter.  6144 waves hammering ONE address with an atomic per 64 samples
+// was the bottleneck of the whole kernel (5.05 -> 6.25 Gsamples/s with 512 per atomic); small frames keep at least 16 reservations
+// per wave so the tail stays balanced.  Near the end of the pass reservations shrink to remaining / (RTP_TAPER_FACTOR x waves),
+// rounded to a power of two: taper_shift.
+void reservation(uint32_t total_work, uint64_t waves_total, uint32_t &chunk, uint32_t &taper_shift) {
+    uint64_t per = (uint64_t)total_work / (waves_total * 16u * 64u);
+    per = per < 1 ? 1 : (per > 16 ? 16 : per);      // 1024 per atomic with 8192 waves: +1 % over 512 (32: the same, 64: the tail shows)
+    chunk = (uint32_t)(64u * per);
+    taper_shift = 1;
+    while (((uint64_t)1 << taper_shift) < RTP_TAPER_FACTOR * waves_total) ++taper_shift;
+}
+
+// samples [pass_first, pass_first + pass_count) of every pixel: work index = pixel * pass_count + slot, below the bound of the
+// kernels' 32-bit arithmetic
+rt_status set_pass(rtk::KParams &P, const rtaccel::PassPlan &passes, int pass, uint32_t num_pixels) {
+    P.pass_first = passes.first(pass);
+    P.pass_count = passes.count(pass);
+    P.total_work = num_pixels * (uint32_t)P.pass_count;
+    if ((uint64_t)num_pixels * (uint64_t)P.pass_count >= (1ull << 31) - 4096 || !make_magic((uint32_t)P.pass_count, (uint64_t)P.total_work + 64, P.magic_count))
+        return fail(RT_ERR_UNSUPPORTED, "image too large for the work index arithmetic");
+    return RT_OK;
+}
+
+
+// rt_render and rt_render_tile: whole rows of a shard, or a rectangle
+rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shard, const Tile *tile, float *d_fb_sum, void *hip_stream,
+                      int32_t sync, rt_timing *timing) {
+    // ---- 1. validate, fill P
+    rtk::KParams P;
+    rt_status st = fill_params(sc, cam, shard, P, tile);
+    if (st != RT_OK) return st;
+    if ((st = check_device(sc)) != RT_OK) return st;
+    if (!d_fb_sum) return fail(RT_ERR_INVALID_ARG, "null framebuffer");
+    if ((st = timing_check(timing)) != RT_OK) return st;
+    const rt_config &cfg = sc->cfg;
+    hipStream_t stream = (hipStream_t)hip_stream;
+    P.fb = d_fb_sum;
+    timing_out(rt_timing{}, timing);
+    // what earlier frames of this handle reported about their guarded walk (no wait: whatever has landed by now)
+    if ((st = poll_feedback(sc, false)) != RT_OK) return st;
+    const size_t fb_bytes = (size_t)P.local_rows * P.row_w * 3 * sizeof(float);
+    if (P.local_rows == 0) return RT_OK;
+    if (P.spp <= 0 || P.max_depth <= 0) {     // the reference's loops add nothing: all-zero sums
+        HIP_TRY(hipMemsetAsync(d_fb_sum, 0, fb_bytes, stream));
+        if (sync) HIP_TRY(hipStreamSynchronize(stream));
+        sc->timed = false;
+        return RT_OK;
+    }
+
+    // ---- 2. the walk, the tree re-packed for a far camera
+    bool guarded = false, exploring = false;
+    if ((st = choose_traversal(sc, cam, shard, tile, stream, P, guarded, exploring)) != RT_OK) return st;
+    // ---- 3. launch shapes
+    LaunchPlan plan = plan_launch(sc, cam, P, guarded);
+    guarded = plan.guarded();
+    // ---- 4. buffers.  Samples per pass (rt_accel.h, plan_passes): as many as the workspace budget admits (rt_config.workspace_bytes,
+    // default a sixteenth of the device; 12 bytes per sample), at least 64 where the work-index bound allows, and never more than the
+    // bound num_pixels * pass + 64 <= 2^30 of the kernel's 32-bit work index (div_magic, kFlagHole, kAbandonedCounter) —
+    // a forced rt_config.pass_spp included; the passes of a frame are made equally long.
+    // Fewer, larger launches amortise the end-of-launch tail — on a row shard of an N-GPU frame
+    // the pass grows N-fold, so a launch keeps the size it has on one GPU.
+    const uint32_t num_pixels = (uint32_t)P.local_rows * (uint32_t)P.row_w;
+    rtaccel::PassPlan passes;
+    if ((st = reserve_buffers(sc, P, num_pixels, stream, plan, passes)) != RT_OK) return st;
+    const bool prim = plan.prim;
+    P.slab = sc->slab;
+    P.num_pixels = num_pixels;
+    P.slab_pitch = slab_pitch_of(passes.pass_size);
+    bind_view_lists(sc, P, num_pixels, prim);
+    P.k_inner = plan.k_inner;
+    P.k_shade = plan.k_shade;
+
+    // ---- 5. the passes
+    const Shape &trace_shape = plan.trace_shape();
     const uint32_t max_wgs = (uint32_t)(((uint64_t)num_pixels * (P.spp < 64 ? P.spp : 64) + rtk::kBlock - 1) / rtk::kBlock);
     auto grid_for = [&](const Shape &sh) {
         int wgs = sc->num_cus * sh.wgs_per_cu;
         if ((uint32_t)wgs > max_wgs) wgs = (int)max_wgs;
         return wgs < 1 ? 1 : wgs;
     };
-    int wgs = grid_for(main_shape);
+    const int wgs = grid_for(trace_shape), rework_wgs = grid_for(plan.exact);
+    const void *trace = trace_kernel(plan);
+    const void *rework = plan.exact.in_lds ? (const void *)rtk::render_kernel<true, true> : (const void *)rtk::render_kernel<false, true>;
+    // registers and scratch of the dominant (trace) kernel as the loaded code object reports them → rt_timing
+    uint32_t trace_vgprs = 0, trace_scratch = 0;
+    {
+        hipFuncAttributes attr;
+        if (hipFuncGetAttributes(&attr, trace) == hipSuccess) {
+            trace_vgprs = (uint32_t)attr.numRegs;
+            trace_scratch = (uint32_t)attr.localSizeBytes;
+        }
+    }
 
     HIP_TRY(hipMemsetAsync(sc->queue, 0, kQueueWords * 4, stream));
-    // (not with a capped flag list or an unproven margin: a list that overflowed makes the re-walk rewrite EVERY slab entry
-    // while the other stream sums the rows of unflagged pixels — harmless only where both walks give the same bits)
-    const bool overlap = guarded && !wavefront && !use_queue && cfg.overlap_rework >= 0 && sc->aux_stream != nullptr && sc->dirty != nullptr &&
-                         cfg.flag_capacity == 0 && !gamma_unproven(cfg);
+    const bool overlap = plan.overlap;
     // an early return between the fork to the second stream and the join must not leave that stream running unobserved
     struct JoinOnExit {
         rt_scene *sc; hipStream_t stream; bool forked = false, listing = false;
@@ -1152,20 +1247,6 @@ rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *s
             if (listing) (void)hipStreamWaitEvent(stream, sc->ev_listed, 0);
         }
     } join_guard{sc, stream};
-    // Primary visibility without a walk (rt_primary.hip.inc): the pair-node walks of render_kernel — the LDS-resident octant walk
-    // with static margins, and the walk with distance-aware margins (LDS-resident or through L1/L2) — and a camera inside the
-    // distance static margins were sized for (so that the far-origin test can never fire for a camera ray; the device compares
-    // in float: a hair of slack)
-    bool prim = guarded && !wavefront && !use_queue && (!wide || (dyn && !fast.in_lds)) && (dyn || ((RTP_OCTANT != 0) && fast.in_lds)) && cfg.primary_visibility >= 0 &&
-                sc->nodes != nullptr && P.max_depth < rtk::kMaxPrimDepth;
-    if (prim && sc->guard.num_small > 0) {
-        const double dx = (double)cam->origin.e[0] - sc->guard.center[0], dy = (double)cam->origin.e[1] - sc->guard.center[1], dz = (double)cam->origin.e[2] - sc->guard.center[2];
-        if (!(dx * dx + dy * dy + dz * dz <= (double)sc->guard.d0_sq * (1.0 - 1e-5))) prim = false;
-    }
-    if ((st = reserve_view_lists(sc, num_pixels, stream, prim)) != RT_OK) return st;
-    P.cand = prim ? sc->cand : nullptr;
-    P.order = prim ? sc->cand + sc->cand_pixels * rtk::kCandWords : nullptr;
-    P.traced_pixels = prim ? P.order + sc->cand_pixels + 2 * (((size_t)num_pixels + rtk::kOrderBlock - 1) / rtk::kOrderBlock) : nullptr;      // counts[2 * blocks] after the scan
     rt_scene::Feedback *feedback = nullptr;
     if ((st = acquire_feedback(sc, &feedback)) != RT_OK) return st;
     HIP_TRY(hipEventRecord(feedback->start, stream));
@@ -1175,234 +1256,86 @@ rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *s
     } else {
         sc->cand_key.valid = false;
     }
-    hipStream_t launch_stream = stream;       // the exact re-walk may go to the handle's second stream (overlap_rework)
-    // registers and scratch of the dominant (trace) kernel as the loaded code object reports them → rt_timing
-    uint32_t trace_vgprs = 0, trace_scratch = 0;
-    auto note_resources = [&](auto kernel) {
-        hipFuncAttributes attr;
-        if (trace_vgprs == 0 && hipFuncGetAttributes(&attr, (const void *)kernel) == hipSuccess) {
-            trace_vgprs = (uint32_t)attr.numRegs;
-            trace_scratch = (uint32_t)attr.localSizeBytes;
-        }
-    };
-    auto launch = [&](auto kernel, const rtk::KParams &KP, int grid, uint32_t lds) -> hipError_t {
-        hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        note_resources(kernel);
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(rtk::kBlock), lds, launch_stream, KP);
-        return hipGetLastError();
-    };
-    auto launch_simple = [&](auto kernel, const rtk::KParams &KP, int grid, uint32_t lds) -> hipError_t {
-        hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        note_resources(kernel);
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(rtk::kSimpleBlock), lds, stream, KP);
-        return hipGetLastError();
-    };
-    auto launch_simple_on = [&](auto kernel, const rtk::KParams &KP, int grid, uint32_t lds) -> hipError_t {      // (on launch_stream: the re-walk may run on the second stream)
-        hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        note_resources(kernel);
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(rtk::kSimpleBlock), lds, launch_stream, KP);
-        return hipGetLastError();
-    };
-    auto launch_wf = [&](auto kernel, const rtk::KParams &KP, int grid, uint32_t lds) -> hipError_t {
-        hipError_t e = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-        note_resources(kernel);
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(rtk::kWfBlock), lds, stream, KP);
-        return hipGetLastError();
-    };
-    auto launch_exact = [&](rtk::KParams &KP, int grid, bool whole_pass) -> hipError_t {
-        KP.stack_levels = 0;
-        KP.num_top = exact.num_top;
-        if (whole_pass && exact_simple) {
-            KP.flag_chunk_words = 0;
-            KP.bail_share = 0;
-            rtk::fill_consts(KP);          // (its launch constants come from the LDS block, like the guarded sphere-only build's)
-            return launch_simple_on(rtk::render_kernel<true, true, false, false, true>, KP, grid, exact_s.lds_bytes);
-        }
-        if (exact.in_lds) return launch(rtk::render_kernel<true, true>, KP, grid, exact.lds_bytes);
-        return launch(rtk::render_kernel<false, true>, KP, grid, exact.lds_bytes);
-    };
-    while ((int)sc->pass_events.size() < 4 * (passes < kTimedPasses ? passes : kTimedPasses)) {
+    while ((int)sc->pass_events.size() < 4 * (passes.passes < kTimedPasses ? passes.passes : kTimedPasses)) {
         hipEvent_t e;
         HIP_TRY(hipEventCreate(&e));
         sc->pass_events.push_back(e);
     }
     sc->timed_passes = 0;
-    uint32_t q_lds = 0;
-#ifdef RTP_DEV_QUEUE_KERNEL
-    // RTP_KERNEL=queue: T-waves/S-waves with LDS queues (rt_kernel_queue.hip.inc), exact walk + LDS-resident scenes only
-    if (use_queue && exact.in_lds) {
-        P.q_s_waves = env_int("RTP_Q_SWAVES", 4);
-        P.q_k_refill = env_int("RTP_Q_KREFILL", 16);
-        P.q_k_busy = env_int("RTP_Q_KBUSY", 0);
-        P.q_k_leaf = env_int("RTP_Q_KLEAF", 24);
-        const uint64_t base_f4 = ((uint64_t)P.num_tnodes + 1) * 2 + (uint64_t)P.num_spheres + (uint64_t)P.num_planes * 5 + ((uint64_t)P.num_spheres + 3) / 4;
-        const uint64_t mat_bytes = (uint64_t)P.num_materials * 48;
-        uint32_t slots = (uint32_t)env_int("RTP_Q_SLOTS", 1152);
-        auto lds_for = [&](uint32_t n, bool mats) {
-            uint32_t cap = 64;
-            while (cap < n) cap <<= 1;
-            return base_f4 * 16 + (mats ? mat_bytes : 0) + (uint64_t)n * rtk::kSlotDwords * 4 + 2ull * cap * 4 + (rtk::QC_WORDS + 2 * (rtk::kQBlock / rtk::kWave)) * 4 + 16;
-        };
-        P.q_mats_in_lds = env_int("RTP_Q_MATS_LDS", 1);
-        if (P.q_mats_in_lds && lds_for(slots, true) > kLdsLimit) P.q_mats_in_lds = 0;
-        while (slots > 128 && lds_for(slots, P.q_mats_in_lds != 0) > kLdsLimit) slots -= 64;
-        if (lds_for(slots, P.q_mats_in_lds != 0) > kLdsLimit) use_queue = false;
-        P.q_slots = slots;
-        P.q_ring_cap = 64;
-        while (P.q_ring_cap < slots) P.q_ring_cap <<= 1;
-        q_lds = (uint32_t)lds_for(slots, P.q_mats_in_lds != 0);
+    if (guarded) {
+        // near-first walk; samples it cannot vouch for go to the list …
+        P.stack_levels = plan.fast.stack_levels;
+        P.num_top = plan.fast.num_top;
+        P.flag_list = sc->flag_list;
+        P.resume_tag = plan.resume ? sc->resume_tag : nullptr;
+        P.resume_state = plan.resume ? sc->resume_state : nullptr;
+        P.resume_shift = plan.resume ? 32u - kResumeBits : 0u;
+        P.dirty = overlap ? sc->dirty : nullptr;
+        P.dirty_list = overlap ? sc->dirty_list : nullptr;
+        P.flag_cap = (uint32_t)(sc->flag_cap < 0xffffffffu ? sc->flag_cap : 0xffffffffu);
+        if (const uint32_t tiny = cfg.flag_capacity) P.flag_cap = tiny < P.flag_cap ? tiny : P.flag_cap;   // test hook: overflow path
+        P.flag_chunk_words = plan.flag_chunk_words;
+        // in-launch bail-out (not for a caller who insists on the guarded walk)
+        P.bail_share = cfg.guard_keep ? 0u : bail_share_of(cfg);
+        P.bail_floor = bail_floor();
+        P.bail_latest = bail_latest();
     } else {
-        use_queue = false;
+        P.stack_levels = 0;
+        P.num_top = plan.exact.num_top;
+        if (plan.walk == Walk::ExactSimple) {
+            P.flag_chunk_words = 0;
+            P.bail_share = 0;
+        }
     }
-    if (use_queue) {
-        wgs = sc->num_cus;
-        if ((uint32_t)wgs > max_wgs) wgs = (int)max_wgs;
-        if (wgs < 1) wgs = 1;
-    }
-#endif
-    for (int pass = 0; pass < passes; ++pass) {
+    const uint64_t waves_total = (uint64_t)wgs * (plan.block() / rtk::kWave);
+    for (int pass = 0; pass < passes.passes; ++pass) {
         // samples [pass_first, pass_first + pass_count) of every pixel, traced in any order into the slab …
         const bool timed_pass = pass < kTimedPasses;
         if (timed_pass) HIP_TRY(hipEventRecord(sc->pass_events[4 * pass], stream));
-        P.pass_first = plan.first(pass);
-        P.pass_count = plan.count(pass);
-        P.total_work = num_pixels * (uint32_t)P.pass_count;      // work index = pixel * pass_count + slot
-        P.slab_pitch = slab_pitch_of(pass_size);
-        if ((uint64_t)num_pixels * (uint64_t)P.pass_count >= (1ull << 31) - 4096 || !make_magic((uint32_t)P.pass_count, (uint64_t)P.total_work + 64, P.magic_count))
-            return fail(RT_ERR_UNSUPPORTED, "image too large for the work index arithmetic");
+        if ((st = set_pass(P, passes, pass, num_pixels)) != RT_OK) return st;
         P.queue = sc->queue + kQueueWork + pass;
         P.work_list = nullptr;
-        // Work indices a wave reserves per atomicAdd on the pass's counter.  6144 waves hammering ONE address
-        // with an atomic per 64 samples was the bottleneck of the whole kernel (5.05 -> 6.25 Gsamples/s with
-        // 512 per atomic); small frames keep at least 16 reservations per wave so the tail stays balanced.
-        {
-            const uint64_t waves_total = (uint64_t)wgs * ((wavefront ? rtk::kWfBlock : ((guarded ? simple : exact_simple) ? rtk::kSimpleBlock : rtk::kBlock)) / rtk::kWave);
-            uint64_t per = (uint64_t)P.total_work / (waves_total * 16u * 64u);
-            per = per < 1 ? 1 : (per > 16 ? 16 : per);      // 1024 per atomic with 8192 waves: +1 % over 512 (32: the same, 64: the tail shows)
-            if (const int forced = cfg.reserve_chunk) per = (uint64_t)(forced > 0 ? forced : 1);
-            P.chunk = (uint32_t)(64u * per);
-            P.taper_shift = 1;                      // remaining / (2 x waves), rounded to a power of two
-            while (((uint64_t)1 << P.taper_shift) < RTP_TAPER_FACTOR * waves_total) ++P.taper_shift;
-            if (!cfg.reserve_taper) P.taper_shift = 0;
-        }
+        reservation(P.total_work, waves_total, P.chunk, P.taper_shift);
+        if (const int forced = cfg.reserve_chunk) P.chunk = (uint32_t)(64u * (uint64_t)(forced > 0 ? forced : 1));
+        if (!cfg.reserve_taper) P.taper_shift = 0;
         if (prim) {
             // primary visibility of this pass's samples: (hit distance, primitive) into each sample's slot of the slab
             launch_primary(sc, P, num_pixels, stream);
             HIP_TRY(hipGetLastError());
         }
         if (timed_pass) HIP_TRY(hipEventRecord(sc->pass_events[4 * pass + 1], stream));
-#ifdef RTP_DEV_QUEUE_KERNEL
-        if (use_queue) {
-            P.stack_levels = 0;
-            HIP_TRY(hipFuncSetAttribute((const void *)rtk::render_kernel_q<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)q_lds));
-            hipLaunchKernelGGL(rtk::render_kernel_q<true>, dim3(wgs), dim3(rtk::kQBlock), q_lds, stream, P);
-            HIP_TRY(hipGetLastError());
-        } else
-#endif
         if (guarded) {
-            // near-first walk; samples it cannot vouch for go to the list …
-            P.stack_levels = fast.stack_levels;
-            P.num_top = fast.num_top;
-            // vote thresholds of the octant walk (its pair steps are cheaper, so a block of them is worth starting for fewer
-            // idle lanes and a shade step is worth waiting for a few more): re-swept after step_octant, +1.0 %
-            const bool octant_launch = (RTP_OCTANT != 0) && fast.in_lds && !wide && !wavefront && !dyn;
-            if (octant_launch && sc->cfg.k_inner <= 0) P.k_inner = 32;
-            if (octant_launch && sc->cfg.k_shade <= 0) P.k_shade = 52;
-            // scene with distance-aware margins (records through L1/L2, step_pair_par / step_wide_par): a block of steps costs memory round
-            // trips on top of its instructions — worth starting only for a nearly full wave (S-100k, swept 16-52 x 44-56: +4 %)
-            const bool big_dyn_launch = dyn && !fast.in_lds && !wavefront;
-            if (big_dyn_launch && sc->cfg.k_inner <= 0) P.k_inner = 48;
-            if (big_dyn_launch && sc->cfg.k_shade <= 0) P.k_shade = 52;
-            P.flag_list = sc->flag_list;
-            // resume table: cleared per pass (1 MB of tags); not for the experimental kernels, nor for paths longer than the depth field
-            constexpr uint32_t kResumeBits = 18;
-            if (!wavefront && cfg.resume_flagged >= 0 && P.max_depth < rtk::kMaxPrimDepth) {
-                if (sc->resume_tag == nullptr) {
-                    if (hipMalloc((void **)&sc->resume_tag, sizeof(uint32_t) << kResumeBits) != hipSuccess ||
-                        hipMalloc((void **)&sc->resume_state, (size_t)64 << kResumeBits) != hipSuccess) {
-                        (void)hipGetLastError();
-                        (void)hipFree(sc->resume_tag); (void)hipFree(sc->resume_state);
-                        sc->resume_tag = nullptr; sc->resume_state = nullptr;
-                    }
-                }
-                if (sc->resume_tag != nullptr) HIP_TRY(hipMemsetAsync(sc->resume_tag, 0, sizeof(uint32_t) << kResumeBits, stream));
-                P.resume_tag = sc->resume_tag; P.resume_state = sc->resume_state; P.resume_shift = 32u - kResumeBits;
-            } else {
-                P.resume_tag = nullptr; P.resume_state = nullptr;
-            }
+            // resume table: cleared per pass (1 MB of tags)
+            if (P.resume_tag != nullptr) HIP_TRY(hipMemsetAsync(sc->resume_tag, 0, sizeof(uint32_t) << kResumeBits, stream));
             P.flag_count = sc->queue + kQueueFlag + pass;
-            P.dirty = overlap ? sc->dirty : nullptr;
             if (overlap) HIP_TRY(hipMemsetAsync(sc->dirty, 0, (size_t)num_pixels * sizeof(uint32_t), stream));      // this pass's marks (8 MB at 1080p: microseconds)
-            P.dirty_list = overlap ? sc->dirty_list : nullptr;
             P.dirty_count = sc->queue + kQueueDirty + pass;
-            P.flag_cap = (uint32_t)(sc->flag_cap < 0xffffffffu ? sc->flag_cap : 0xffffffffu);
-            if (const uint32_t tiny = cfg.flag_capacity) P.flag_cap = tiny < P.flag_cap ? tiny : P.flag_cap;   // test hook: overflow path
-            P.flag_chunk_words = flag_chunk_words;
-            // in-launch bail-out (not for a caller who insists on the guarded walk, nor for the experimental kernels)
-            P.bail_share = (cfg.guard_keep || wavefront) ? 0u : bail_share_of(cfg);
-            P.bail_floor = bail_floor();
-            P.bail_latest = bail_latest();
             P.abandon = P.bail_share != 0u ? sc->queue + kQueueAbandon + pass : nullptr;
             rtk::fill_consts(P);          // (everything the constants block copies is final now)
-            if (wavefront) {
-                P.wf_pool = sc->wf_pool;
-                P.wf_cap = P.wf_target = wf_target;
-                P.wf_k_exchange = cfg.wavefront_exchange > 0 ? (cfg.wavefront_exchange > 64 ? 64 : cfg.wavefront_exchange) : 16;
-#ifdef RTP_DEV_BUILD
-                if (fast.in_lds) HIP_TRY(launch_wf(rtk::render_kernel_wf<true>, P, wgs, fast.lds_bytes));
-                else HIP_TRY(launch_wf(rtk::render_kernel_wf<false>, P, wgs, fast.lds_bytes));
-#else
-                (void)launch_wf;
-#endif
-            } else if (wide && dyn && !fast.in_lds) {      // distance-aware margins on 4-wide nodes (step_wide_par)
-                if (prim) HIP_TRY(launch(rtk::render_kernel<false, false, true, true, false, true>, P, wgs, fast.lds_bytes));
-                else HIP_TRY(launch(rtk::render_kernel<false, false, true, true>, P, wgs, fast.lds_bytes));
-#ifdef RTP_DEV_BUILD
-            } else if (wide) {
-                if (fast.in_lds) HIP_TRY(launch(rtk::render_kernel<true, false, false, true>, P, wgs, fast.lds_bytes));
-                else HIP_TRY(launch(rtk::render_kernel<false, false, false, true>, P, wgs, fast.lds_bytes));
-#endif
-            } else if (dyn && simple) {      // sphere-only scenes beyond what LDS holds: step_pair_par at 64 registers, 8 waves per SIMD
-                if (prim) HIP_TRY(launch_simple(rtk::render_kernel<false, false, true, false, true, true>, P, wgs, fast.lds_bytes));
-                else HIP_TRY(launch_simple(rtk::render_kernel<false, false, true, false, true>, P, wgs, fast.lds_bytes));
-            } else if (dyn) {
-                if (prim) HIP_TRY(launch(rtk::render_kernel<false, false, true, false, false, true>, P, wgs, fast.lds_bytes));
-                else HIP_TRY(launch(rtk::render_kernel<false, false, true>, P, wgs, fast.lds_bytes));
-            } else if (fast.in_lds && simple && prim) HIP_TRY(launch_simple(rtk::render_kernel<true, false, false, false, true, true>, P, wgs, fast.lds_bytes));
-            else if (fast.in_lds && simple) HIP_TRY(launch_simple(rtk::render_kernel<true, false, false, false, true>, P, wgs, fast.lds_bytes));
-            else if (fast.in_lds && prim) HIP_TRY(launch(rtk::render_kernel<true, false, false, false, false, true>, P, wgs, fast.lds_bytes));
-            else if (fast.in_lds) HIP_TRY(launch(rtk::render_kernel<true, false>, P, wgs, fast.lds_bytes));
-            else HIP_TRY(launch(rtk::render_kernel<false, false>, P, wgs, fast.lds_bytes));
+            HIP_TRY(launch(trace, plan.block(), wgs, trace_shape.lds_bytes, stream, P));
             if (timed_pass) HIP_TRY(hipEventRecord(sc->pass_events[4 * pass + 2], stream));
             // … and are walked again in the reference's order, overwriting their slab entries
             rtk::KParams R = P;
-            R.k_inner = sc->cfg.k_inner > 0 ? sc->cfg.k_inner : 24;
-            R.k_shade = sc->cfg.k_shade > 0 ? sc->cfg.k_shade : 48;
+            R.k_inner = cfg.k_inner > 0 ? cfg.k_inner : 24;
+            R.k_shade = cfg.k_shade > 0 ? cfg.k_shade : 48;
+            R.stack_levels = 0;
+            R.num_top = plan.exact.num_top;
             R.queue = sc->queue + kQueueRework + pass;
             R.work_list = sc->flag_list;
             R.work_count = sc->queue + kQueueFlag + pass;
             R.work_cap = P.flag_cap;
             R.chunk = 64u;                     // a short list: finest granularity
             R.taper_shift = 0;
-            {       // … unless it turns out to be the whole pass (overflow, abandoned guarded pass): a trace launch's reservations
-                const uint64_t waves_total = (uint64_t)grid_for(exact) * (rtk::kBlock / rtk::kWave);
-                uint64_t per = (uint64_t)P.total_work / (waves_total * 16u * 64u);
-                per = per < 1 ? 1 : (per > 16 ? 16 : per);
-                R.full_chunk = (uint32_t)(64u * per);
-                R.full_taper = 1;
-                while (((uint64_t)1 << R.full_taper) < RTP_TAPER_FACTOR * waves_total) ++R.full_taper;
-            }
+            // … unless it turns out to be the whole pass (overflow, abandoned guarded pass): a trace launch's reservations
+            reservation(P.total_work, (uint64_t)rework_wgs * (rtk::kBlock / rtk::kWave), R.full_chunk, R.full_taper);
             R.dirty = nullptr;
+            hipStream_t rework_stream = stream;       // the exact re-walk may go to the handle's second stream (overlap_rework)
             if (overlap) {
                 // the re-walk and the accumulation of the pixels it touches on the second stream …
                 HIP_TRY(hipEventRecord(sc->ev_fork, stream));
                 HIP_TRY(hipStreamWaitEvent(sc->aux_stream, sc->ev_fork, 0));
                 join_guard.forked = true;
-                launch_stream = sc->aux_stream;
+                rework_stream = sc->aux_stream;
                 // the pixels the trace launch marked, as a list for the second accumulate launch — made on a third stream beside the
                 // re-walk (0.2 ms at 1080p that would otherwise lengthen the re-walk's chain past the other pixels' accumulation)
                 HIP_TRY(hipStreamWaitEvent(sc->list_stream, sc->ev_fork, 0));
@@ -1412,20 +1345,19 @@ rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *s
                 HIP_TRY(hipEventRecord(sc->ev_listed, sc->list_stream));
                 join_guard.listing = true;
             }
-            HIP_TRY(launch_exact(R, grid_for(exact), false));
-            launch_stream = stream;
+            HIP_TRY(launch(rework, (uint32_t)rtk::kBlock, rework_wgs, plan.exact.lds_bytes, rework_stream, R));
         } else {
-            HIP_TRY(launch_exact(P, wgs, true));
+            if (plan.walk == Walk::ExactSimple) rtk::fill_consts(P);          // (its launch constants come from the LDS block, like the guarded sphere-only build's)
+            HIP_TRY(launch(trace, plan.block(), wgs, trace_shape.lds_bytes, stream, P));
         }
-        const bool overlapped = overlap && guarded && !wavefront;
         if (timed_pass) {
             if (!guarded) HIP_TRY(hipEventRecord(sc->pass_events[4 * pass + 2], stream));
-            HIP_TRY(hipEventRecord(sc->pass_events[4 * pass + 3], overlapped ? sc->aux_stream : stream));
+            HIP_TRY(hipEventRecord(sc->pass_events[4 * pass + 3], overlap ? sc->aux_stream : stream));
             sc->timed_passes = pass + 1;
         }
         // … then added to the pixel sums strictly in sample order
         const dim3 acc_grid((num_pixels + 64 * rtk::kAccWaves - 1) / (64 * rtk::kAccWaves)), acc_block(64 * rtk::kAccWaves);
-        if (overlapped) {
+        if (overlap) {
             // (a pass the guarded launch gave up has rows nobody traced yet: both launches stand down — P.abandon — and a third one,
             // after the re-walk of everything, sums every pixel)
             HIP_TRY(hipStreamWaitEvent(sc->aux_stream, sc->ev_listed, 0));
@@ -1451,44 +1383,42 @@ rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *s
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(sc->ev_stop, stream));
+
+    // ---- 6. what the frame leaves for later calls
     {
         // flagged counts and abandon words of this call → pinned host memory, and the frame's end, for a later call's poll_feedback
         rt_scene::Feedback &f = *feedback;
         if (guarded) {
-            HIP_TRY(hipMemcpyAsync(f.host, sc->queue + kQueueFlag, (size_t)passes * 4, hipMemcpyDeviceToHost, stream));
-            HIP_TRY(hipMemcpyAsync(f.host + kMaxPasses, sc->queue + kQueueAbandon, (size_t)passes * 4, hipMemcpyDeviceToHost, stream));
-            HIP_TRY(hipMemcpyAsync(f.host + 2 * kMaxPasses, sc->queue + kQueueHoles, (size_t)passes * 4, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipMemcpyAsync(f.host, sc->queue + kQueueFlag, (size_t)passes.passes * 4, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipMemcpyAsync(f.host + kMaxPasses, sc->queue + kQueueAbandon, (size_t)passes.passes * 4, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(hipMemcpyAsync(f.host + 2 * kMaxPasses, sc->queue + kQueueHoles, (size_t)passes.passes * 4, hipMemcpyDeviceToHost, stream));
         }
         HIP_TRY(hipEventRecord(f.done, stream));
         f.pending = true;
         f.guarded = guarded;
         f.exploring = exploring;
-        f.passes = passes;
+        f.passes = passes.passes;
         f.samples = (uint64_t)num_pixels * (uint64_t)P.spp;
         f.serial = ++sc->frame_serial;
     }
     sc->timed = true;
     sc->last = rt_timing{};
     sc->last.num_workgroups = (uint32_t)wgs;
-    sc->last.workgroup_size = wavefront ? (uint32_t)rtk::kWfBlock : ((guarded ? simple : exact_simple) ? (uint32_t)rtk::kSimpleBlock : (uint32_t)rtk::kBlock);
-    sc->last.lds_bytes = main_shape.lds_bytes;
-#ifdef RTP_DEV_QUEUE_KERNEL
-    if (use_queue) { sc->last.workgroup_size = rtk::kQBlock; sc->last.lds_bytes = q_lds; }
-#endif
-    (void)q_lds;
-    sc->last.scene_in_lds = main_shape.in_lds ? 1u : 0u;
-    sc->last.trace_launches = (uint32_t)passes;
+    sc->last.workgroup_size = plan.block();
+    sc->last.lds_bytes = trace_shape.lds_bytes;
+    sc->last.scene_in_lds = trace_shape.in_lds ? 1u : 0u;
+    sc->last.trace_launches = (uint32_t)passes.passes;
     sc->last.guarded = guarded ? 1u : 0u;
     sc->last.guard_unproven = (guarded && gamma_unproven(cfg)) ? 1u : 0u;
-    sc->last.kernel = wavefront ? RT_KERNEL_WAVEFRONT : RT_KERNEL_MEGA;
-    sc->last.guard_dynamic = dyn ? 1u : 0u;
+    sc->last.kernel = RT_KERNEL_MEGA;
+    sc->last.guard_dynamic = plan.dyn ? 1u : 0u;
     sc->last.front_primitives = guarded ? (uint32_t)sc->guard.num_front : 0u;
-    sc->last.wide_nodes = (guarded && wide) ? 1u : 0u;
-    sc->last.sphere_only = ((guarded && simple && !wavefront && !wide) || (!guarded && exact_simple)) ? 1u : 0u;
+    sc->last.wide_nodes = plan.wide ? 1u : 0u;
+    sc->last.sphere_only = plan.sphere_only() ? 1u : 0u;
     sc->last.primary_visibility = prim ? 1u : 0u;
     sc->last.trace_vgprs = trace_vgprs;
     sc->last.trace_scratch_bytes = trace_scratch;
-    sc->last_passes = passes;
+    sc->last_passes = passes.passes;
     sc->last_samples = (uint64_t)num_pixels * (uint64_t)P.spp;
     sc->last_traced_pixels = prim ? P.traced_pixels : nullptr;
     sc->last_spp = P.spp;
@@ -1534,25 +1464,15 @@ rt_status aov_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shar
     bool prim = sc->guard.ok && cfg.traversal != RT_TRAVERSAL_EXACT && P.root >= 0 && guarded_wanted(cfg, (int64_t)P.num_spheres + P.num_planes) &&
                 !(sc->guard_paused && !cfg.guard_keep) && cfg.kernel != RT_KERNEL_WAVEFRONT && cfg.primary_visibility >= 0 && sc->nodes != nullptr &&
                 (sc->guard.dyn_k > 0.0f || cfg.scene_in_lds != 0);
-    if (prim) {
-        auto dist_sq = [&](const float *c) {
-            const double dx = (double)cam->origin.e[0] - c[0], dy = (double)cam->origin.e[1] - c[1], dz = (double)cam->origin.e[2] - c[2];
-            return dx * dx + dy * dy + dz * dz;
-        };
-        if (!(dist_sq(sc->guard.origin_center) <= (double)sc->guard.origin_radius * sc->guard.origin_radius)) prim = false;
-        if (sc->guard.num_small > 0 && !(dist_sq(sc->guard.center) <= (double)sc->guard.d0_sq * (1.0 - 1e-5))) prim = false;
-    }
+    if (prim && !camera_inside_margins(sc, cam)) prim = false;
     rtaccel::PassPlan plan;
     if ((st = reserve_slab(sc, num_pixels, P.spp, stream, plan)) != RT_OK) return st;
     const int passes = plan.passes;
-    if (passes > kMaxPasses) return fail(RT_ERR_UNSUPPORTED, "more than 1024 passes (samples_per_pixel above 65536, or above 64512 at 2^24 pixels)");
     P.slab = sc->slab;
     P.num_pixels = num_pixels;
     P.slab_pitch = slab_pitch_of(plan.pass_size);
     if ((st = reserve_view_lists(sc, num_pixels, stream, prim)) != RT_OK) return st;
-    P.cand = prim ? sc->cand : nullptr;
-    P.order = prim ? sc->cand + sc->cand_pixels * rtk::kCandWords : nullptr;
-    P.traced_pixels = prim ? P.order + sc->cand_pixels + 2 * (((size_t)num_pixels + rtk::kOrderBlock - 1) / rtk::kOrderBlock) : nullptr;
+    bind_view_lists(sc, P, num_pixels, prim);
     if (!sc->aov_walked) HIP_TRY(hipMalloc((void **)&sc->aov_walked, sizeof(uint32_t)));
     if (!sc->aov_start) {
         HIP_TRY(hipEventCreate(&sc->aov_start));
@@ -1573,11 +1493,7 @@ rt_status aov_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shar
     }
     for (int pass = 0; pass < passes; ++pass) {
         const bool timed_pass = pass < timed;
-        P.pass_first = plan.first(pass);
-        P.pass_count = plan.count(pass);
-        P.total_work = num_pixels * (uint32_t)P.pass_count;
-        if ((uint64_t)num_pixels * (uint64_t)P.pass_count >= (1ull << 31) - 4096 || !make_magic((uint32_t)P.pass_count, (uint64_t)P.total_work + 64, P.magic_count))
-            return fail(RT_ERR_UNSUPPORTED, "image too large for the work index arithmetic");
+        if ((st = set_pass(P, plan, pass, num_pixels)) != RT_OK) return st;
         if (timed_pass) HIP_TRY(hipEventRecord(sc->aov_events[3 * pass], stream));
         if (prim) {
             launch_primary(sc, P, num_pixels, stream);
@@ -1609,9 +1525,9 @@ rt_status aov_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shar
             HIP_TRY(hipEventElapsedTime(&ms, sc->aov_events[3 * p + 1], sc->aov_events[3 * p + 2]));
             rework += ms;
         }
-        // passes beyond the individually timed ones are priced at the mean of the timed ones; + the lists, made before the first pass
-        primary *= (float)passes / (float)timed;
-        rework *= (float)passes / (float)timed;
+        // (+ the lists, made before the first pass)
+        primary *= untimed_scale(passes, timed);
+        rework *= untimed_scale(passes, timed);
         HIP_TRY(hipEventElapsedTime(&ms, sc->aov_start, sc->aov_events[0]));
         t.primary_ms = prim ? primary + ms : 0.0f;
         t.rework_ms = rework;

@@ -54,23 +54,8 @@ constexpr int32_t kDone = INT32_MIN;     // traversal finished / no hit
 #ifndef RTP_UNROLL
 #define RTP_UNROLL 4
 #endif
-#ifndef RTP_DEFER
-#define RTP_DEFER 1             /* parked primitive tests in the guarded walk (park_leaf) */
-#endif
-#ifndef RTP_OCTANT
-#define RTP_OCTANT 1              /* LDS pair nodes laid out so that the ray's octant picks near/far planes by ADDRESS (step_octant) */
-#endif
 #ifndef RTP_LDS_MAT_ROWS
 #define RTP_LDS_MAT_ROWS 1        /* material rows kept in LDS (row 0: albedo + type; row 1, emission + fuzz, and row 2 come from global memory) */
-#endif
-#ifndef RTP_SPHERE_SHARED_RCP
-#define RTP_SPHERE_SHARED_RCP 1    /* test_sphere: both roots from one fp64 reciprocal, no exec-mask regions */
-#endif
-#ifndef RTP_ACC_PIPELINED
-#define RTP_ACC_PIPELINED 1       /* accumulate_kernel: next tile's loads in flight while the current one is summed */
-#endif
-#ifndef RTP_FINAL_IN_SHADE
-#define RTP_FINAL_IN_SHADE 1    /* 1: the last parked primitive test of a ray runs at the head of the shade step */
 #endif
 #ifndef RTP_UNROLL_WIDE
 #define RTP_UNROLL_WIDE 3       /* steps on 4-wide nodes per vote (each does the work of two pair steps; 1: -0.6 %, 3 as good as any on configs[4]) */
@@ -121,8 +106,7 @@ struct KParams {
     // scene tables (global memory)
     const float4 *nodes;     int32_t num_internal; int32_t root;     // guarded walk, fp32 pair records (LDS-resident scenes)
     const float4 *hnodes;                                            // the same records with binary16 planes (global-memory scenes)
-    const float4 *wnodes;    int32_t num_wide; int32_t wroot;        // guarded walk, 4-wide nodes: 7 x float4 (fp32) …
-    const float4 *whnodes;                                           // … or 4 x float4 (binary16 boxes)
+    const float4 *whnodes;   int32_t wroot;                          // guarded walk with distance-aware margins, 4-wide nodes (binary16 boxes)
     const float4 *tnodes;    int32_t num_tnodes;          // reference-order (threaded) node table
     const float4 *xnodes;    int32_t num_top;             // explicit-link copy, records [0,num_top) = LDS treelet
     const float4 *spheres;   int32_t num_spheres;
@@ -146,12 +130,6 @@ struct KParams {
     uint32_t total_work;     // work indices of this pass: local pixels * pass_count
     int32_t stack_levels;    // LDS stack rows per lane
     int32_t k_inner, k_shade; // scheduling thresholds (lanes)
-    // render_kernel_q (rt_kernel_queue.hip.inc)
-    uint32_t q_slots, q_ring_cap;        // path slots per workgroup; ring entries (power of two >= slots)
-    int32_t q_s_waves, q_mats_in_lds;    // shading waves per workgroup; materials staged in LDS?
-    int32_t q_k_refill, q_k_busy, q_k_leaf;
-    // render_kernel_wf (rt_kernel_wf.hip.inc): per-wave ray/hit stacks
-    float4 *wf_pool; uint32_t wf_cap, wf_target; int32_t wf_k_exchange;
     // guarded near-first walk (docs/LOG.md §3b): exact leaf boxes for the final check, the far-origin test,
     // and the list of samples handed to the exact walk
     const float4 *leaf_boxes;          // per sphere, or null: boxes are fl(c -/+ r)
@@ -596,78 +574,6 @@ __device__ __forceinline__ void step_octant(Lane &L, uint32_t *stack, int32_t le
     else pop<true>(L, stack);
 }
 
-// One step of the guarded near-first walk on 4-WIDE nodes (rt_accel.cpp: the SAH tree collapsed): all four child
-// boxes in one step, the nearest hit child next, the other hit children pushed.  Half as many steps per ray as
-// step_inner for about the same number of box tests, i.e. half the dependent LDS / L1 round trips and half the
-// per-step bookkeeping.  Unused child slots carry the code kDone.
-template <bool kTop, bool kHalf, class NodeTab>
-__device__ __forceinline__ void step_wide(Lane &L, NodeTab nodes, const float4 *top, int32_t num_top, uint32_t *stack, int32_t levels) {
-    const float t_far = L.closest * kGuardSlack;
-    const f3 inv = mk(__builtin_amdgcn_fmed3f(L.inv.x, -1e18f, 1e18f), __builtin_amdgcn_fmed3f(L.inv.y, -1e18f, 1e18f),
-                      __builtin_amdgcn_fmed3f(L.inv.z, -1e18f, 1e18f));
-    const f3 noi = mk(-(L.o.x * inv.x), -(L.o.y * inv.y), -(L.o.z * inv.z));
-    float lox[4], hix[4], loy[4], hiy[4], loz[4], hiz[4];
-    int32_t code[4];
-    if (kHalf) {
-        float4 A, B, C, D;
-        if (kTop && L.node < num_top) {
-            A = top[4 * L.node + 0]; B = top[4 * L.node + 1]; C = top[4 * L.node + 2]; D = top[4 * L.node + 3];
-        } else {
-            A = nodes[4 * L.node + 0]; B = nodes[4 * L.node + 1]; C = nodes[4 * L.node + 2]; D = nodes[4 * L.node + 3];
-        }
-        typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-        const half8 ha = __builtin_bit_cast(half8, A), hb = __builtin_bit_cast(half8, B), hc = __builtin_bit_cast(half8, C);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {       // (each dword: the (lo, hi) pair of one axis of one child — rt_accel.cpp)
-            lox[k] = (float)ha[2 * k]; hix[k] = (float)ha[2 * k + 1];
-            loy[k] = (float)hb[2 * k]; hiy[k] = (float)hb[2 * k + 1];
-            loz[k] = (float)hc[2 * k]; hiz[k] = (float)hc[2 * k + 1];
-        }
-        code[0] = as_int(D.x); code[1] = as_int(D.y); code[2] = as_int(D.z); code[3] = as_int(D.w);
-    } else {
-        const float4 X0 = nodes[7 * L.node + 0], X1 = nodes[7 * L.node + 1], Y0 = nodes[7 * L.node + 2], Y1 = nodes[7 * L.node + 3],
-                     Z0 = nodes[7 * L.node + 4], Z1 = nodes[7 * L.node + 5], Cd = nodes[7 * L.node + 6];
-        lox[0] = X0.x; lox[1] = X0.y; lox[2] = X0.z; lox[3] = X0.w;  hix[0] = X1.x; hix[1] = X1.y; hix[2] = X1.z; hix[3] = X1.w;
-        loy[0] = Y0.x; loy[1] = Y0.y; loy[2] = Y0.z; loy[3] = Y0.w;  hiy[0] = Y1.x; hiy[1] = Y1.y; hiy[2] = Y1.z; hiy[3] = Y1.w;
-        loz[0] = Z0.x; loz[1] = Z0.y; loz[2] = Z0.z; loz[3] = Z0.w;  hiz[0] = Z1.x; hiz[1] = Z1.y; hiz[2] = Z1.z; hiz[3] = Z1.w;
-        code[0] = as_int(Cd.x); code[1] = as_int(Cd.y); code[2] = as_int(Cd.z); code[3] = as_int(Cd.w);
-    }
-    bool h[4];
-    float e[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        // (an unused slot is told by its code: slab_fused takes min/max of the two plane distances, so no box is "inverted")
-        h[k] = slab_fused(inv, noi, lox[k], loy[k], loz[k], hix[k], hiy[k], hiz[k], t_far, e[k]) && code[k] != kDone;
-        e[k] = h[k] ? e[k] : 3.0e38f;
-    }
-    // nearest hit child (ties: the lower slot)
-    const bool s01 = e[1] < e[0], s23 = e[3] < e[2];
-    const float e01 = s01 ? e[1] : e[0], e23 = s23 ? e[3] : e[2];
-    const int32_t c01 = s01 ? code[1] : code[0], c23 = s23 ? code[3] : code[2];
-    const int32_t k01 = s01 ? 1 : 0, k23 = s23 ? 3 : 2;
-    const bool sb = e23 < e01;
-    const int32_t near_c = sb ? c23 : c01;
-    const int32_t near_k = sb ? k23 : k01;
-    const bool any = h[0] || h[1] || h[2] || h[3];
-    // the other hit children wait on the stack (slot 3 first, so slot 0 comes off first)
-    const bool p0 = h[0] && near_k != 0, p1 = h[1] && near_k != 1, p2 = h[2] && near_k != 2, p3 = h[3] && near_k != 3;
-    const int32_t n_push = (int32_t)p0 + (int32_t)p1 + (int32_t)p2 + (int32_t)p3;
-    if (n_push > 0) {
-        if (L.sp + n_push <= levels) {
-            int32_t at = L.sp;
-            if (p3) { stack[at * kWave] = (uint32_t)code[3]; ++at; }
-            if (p2) { stack[at * kWave] = (uint32_t)code[2]; ++at; }
-            if (p1) { stack[at * kWave] = (uint32_t)code[1]; ++at; }
-            if (p0) { stack[at * kWave] = (uint32_t)code[0]; ++at; }
-            L.sp = at;
-        } else {
-            L.depth |= kFlagBit | RTP_WHY(0);        // full stack: the exact walk redoes the sample
-        }
-    }
-    if (any) L.node = near_c;
-    else pop(L, stack);
-}
-
 // Root selection of hit_sphere (include/sphere.h:35-45): root = (-half_b - sqrtD) / a in double; if its float value is not in
 // [0.001, closest], (-half_b + sqrtD) / a; returns whether a root was accepted and which.  nb = -half_b, sq = sqrtf(D), da = a.
 // sphere_root_plain is the reference's form with the compiler's division (kept for rt_debug_check_sphere_roots and as the
@@ -695,7 +601,7 @@ __device__ __forceinline__ double sphere_root_rcp(double da);
 template <bool kLazyFar = false>
 __device__ __forceinline__ bool sphere_root_with(double nb, double sq, double da, double y, float closest, float &t);
 __device__ __forceinline__ bool sphere_root(double nb, double sq, double da, float closest, float &t) {
-#if RTP_SPHERE_SHARED_RCP && defined(__HIP_DEVICE_COMPILE__)
+#ifdef __HIP_DEVICE_COMPILE__
     // Both roots from ONE reciprocal.  The compiler's correctly rounded n / d is: v_div_scale (n, d), y = v_rcp_f64(d), two
     // Newton steps on y, q0 = n*y, r = fma(-d, q0, n), q = v_div_fmas(r, y, q0), v_div_fixup.  With operands that began as
     // binary32 (|exponent| <= 149 of the 1022 a double has) the scaling never engages — v_div_scale returns its operand,
@@ -712,7 +618,7 @@ __device__ __forceinline__ bool sphere_root(double nb, double sq, double da, flo
     return sphere_root_plain(nb, sq, da, closest, t);
 #endif
 }
-#if RTP_SPHERE_SHARED_RCP && defined(__HIP_DEVICE_COMPILE__)
+#ifdef __HIP_DEVICE_COMPILE__
 // (the two halves of sphere_root: the reciprocal of a = |d|^2 belongs to the RAY — a caller that tests several spheres
 // against one ray, the primary-visibility pass, makes it once)
 __device__ __forceinline__ double sphere_root_rcp(double da) {
@@ -1303,9 +1209,6 @@ __device__ __forceinline__ void store_sample(const KParams &P, uint32_t w, f3 co
         const uint32_t sq = div_magic_v(w, mg.x, mg.y);
         const uint32_t sk = w - sq * wd.w;
         float *rec = P.slab + (size_t)(sq * wd.y + sk) * 3;        // pixels x pitch < 2^32 (the pass fits the 32-bit work index): one 64-bit multiply-add
-#ifdef RTP_EXP_NO_STORE      /* timing experiment (docs/LOG.md round 4, slab traffic): the address is made, nothing is written */
-        if (color.x != 123456.78125f) return;
-#endif
         rec[0] = color.x; rec[1] = color.y; rec[2] = color.z;
         return;
     }
@@ -1572,14 +1475,16 @@ __device__ __forceinline__ bool resume_load(const KParams &P, uint32_t w, Lane &
 // kLds: traversal tables staged in LDS (else read through L1/L2).
 // kThreaded: reference-order traversal of the caller's tree (bit-exact with the reference also
 // where its result depends on visit order); else near-first traversal of the SAH child-pair tree.
-// kDyn: guarded walk with distance-aware margins (step_inner / step_wide).  kWide: guarded walk on the 4-wide nodes.
+// kDyn: guarded walk with distance-aware margins (step_pair_par), kWide: on the 4-wide nodes (step_wide_par).  Without them the
+// LDS-resident guarded walk is the octant walk (step_octant).
 // kSimple: the sphere-only specialisation of the octant walk (above, kSimpleBlock).
 constexpr uint32_t kShortListLanes = 8;      // exact re-walk: up to this many paths per wave count as a short list (below)
 template <bool kLds, bool kThreaded, bool kDyn = false, bool kWide = false, bool kSimple = false, bool kPrim = false>
 __global__ void __launch_bounds__(kSimple ? kSimpleBlock : RTP_BLOCK, kSimple ? kSimpleWaves : RTP_MIN_WAVES) render_kernel(const KParams P) {
     static_assert(!kPrim || !kThreaded, "primary visibility feeds the guarded walk");
     constexpr int kBlock = kSimple ? kSimpleBlock : rtk::kBlock;      // (shadows the namespace constant inside this kernel)
-    static_assert(!kSimple || (kLds && !kDyn && !kWide && RTP_OCTANT != 0) || (!kLds && !kThreaded && kDyn && !kWide),
+    static_assert(!kWide || kDyn, "the 4-wide nodes are walked only with distance-aware margins (step_wide_par)");
+    static_assert(!kSimple || (kLds && !kDyn && !kWide) || (!kLds && !kThreaded && kDyn && !kWide),
                   "kSimple is a variant of the LDS-resident walks — the octant walk, and the exact walk — and of the pair walk through L1 / L2 (step_pair_par)");
     extern __shared__ float4 smem[];
     const int tid = threadIdx.x;
@@ -1602,7 +1507,7 @@ __global__ void __launch_bounds__(kSimple ? kSimpleBlock : RTP_BLOCK, kSimple ? 
 
     const bool kTreelet = !kLds && kThreaded;          // big scene, exact walk: only the top of the tree lives in LDS
     const bool kTopPairs = !kLds && !kThreaded;        // big scene, guarded walk: likewise
-    constexpr bool kOct = (RTP_OCTANT != 0) && kLds && !kThreaded && !kWide && !kDyn;      // octant-addressed pair records (step_octant)
+    constexpr bool kOct = kLds && !kThreaded;               // every LDS-resident guarded walk is the octant walk (step_octant)
     constexpr bool kOctT = kThreaded && kLds && kSimple;          // exact walk, sphere-only build: octant-addressed node records (step_threaded_oct)
     static_assert(!kDyn || (!kLds && !kThreaded), "scenes with distance-aware margins walk through L1 / L2 (step_pair_par, step_wide_par)");
     constexpr bool kDynPair = kDyn && !kWide;              // distance-aware margins on pair nodes: step_pair_par
@@ -1612,8 +1517,8 @@ __global__ void __launch_bounds__(kSimple ? kSimpleBlock : RTP_BLOCK, kSimple ? 
     // step_pair_par: the last two rows of the lane's stack column hold the ray's own growth bound and sqrt(k) |d|
     const int32_t walk_levels = kDynPar ? P.stack_levels - 2 : P.stack_levels;
     const DynPar dyn_par = {P.g_dyn_b, P.g_dyn_c3, walk_levels * kLevelBytes, walk_levels * kLevelBytes + kLevelBytes};
-    const int n_node4 = kLds ? (kThreaded ? (P.num_tnodes + 1) * (kOctT ? 4 : 2) : (kWide ? P.num_wide * 7 : P.num_internal * (kOct ? 5 : 4)))     // + the end sentinel
-                             : P.num_top * (kWide && !kThreaded ? 4 : 2);
+    const int n_node4 = kLds ? (kThreaded ? (P.num_tnodes + 1) * (kOctT ? 4 : 2) : P.num_internal * (kOct ? 5 : 4))     // + the end sentinel
+                             : P.num_top * 2;
     const int n_sph4 = kLds ? P.num_spheres : 0;
     const int n_pl4 = kLds ? P.num_planes * 5 : 0;
     const int n_mat4 = (kLds && !kSimple) ? P.num_materials * RTP_LDS_MAT_ROWS : 0;      // kSimple: every material row from global memory
@@ -1649,9 +1554,9 @@ __global__ void __launch_bounds__(kSimple ? kSimpleBlock : RTP_BLOCK, kSimple ? 
     constexpr bool kConsts = !kThreaded || kSimple;      // every guarded build keeps the constants block, and the 64-register build of the exact walk
     if (kConsts) write_consts(P, consts_lds, tid);
     if (kSent) l_stack[0] = (uint32_t)kDone;              // level 0 of every lane's stack: the sentinel of pop<true>
-    const float4 *g_nodes = kThreaded ? P.tnodes : (kWide ? (kLds ? P.wnodes : P.whnodes) : (kLds ? P.nodes : P.hnodes));
+    const float4 *g_nodes = kThreaded ? P.tnodes : (kWide ? P.whnodes : (kLds ? P.nodes : P.hnodes));
     if (kTreelet || kTopPairs) {
-        const float4 *src = kTreelet ? P.xnodes : (kWide ? P.whnodes : P.hnodes);
+        const float4 *src = kTreelet ? P.xnodes : P.hnodes;
         for (int k = tid; k < n_node4; k += kBlock) l_nodes[k] = src[k];
         __syncthreads();
     }
@@ -1700,15 +1605,10 @@ __global__ void __launch_bounds__(kSimple ? kSimpleBlock : RTP_BLOCK, kSimple ? 
     Lane L;
     L.node = end_node; L.hit = -1; L.sp = 0; L.pend = 0; L.depth = 0; L.closest = 0; L.seed = 0; L.e = 0;
     L.o = L.d = L.inv = L.beta = L.color = mk(0, 0, 0);
-    constexpr bool kDefer = !kThreaded && (RTP_DEFER != 0);        // parked primitive tests (guarded walk)
-#if RTP_FINAL_IN_SHADE
+    constexpr bool kDefer = !kThreaded;        // parked primitive tests (guarded walk)
     // a lane with nothing left to walk goes to the shade step with its parked test still open: the step tests it first
     auto finished = [&]() { return kDefer ? (L.node == kDone) : traversal_finished<kThreaded>(L, end_node); };
     auto stuck_at_leaf = [&]() { return kDefer ? (L.pend != 0 && L.node < 0 && L.node != kDone) : wants_leaf<kThreaded>(L, end_node); };
-#else
-    auto finished = [&]() { return kDefer ? (L.node == kDone && L.pend == 0) : traversal_finished<kThreaded>(L, end_node); };
-    auto stuck_at_leaf = [&]() { return kDefer ? (L.pend != 0 && L.node < 0) : wants_leaf<kThreaded>(L, end_node); };
-#endif
 #ifdef RTP_EXIT_HIST
     const uint64_t exit_hist_t0 = __builtin_amdgcn_s_memrealtime();
     uint32_t exit_hist_fetch = (uint32_t)exit_hist_t0, exit_hist_dead = (uint32_t)exit_hist_t0;       // when the lane took its last sample / found the pass dry
@@ -1929,9 +1829,7 @@ __global__ void __launch_bounds__(kSimple ? kSimpleBlock : RTP_BLOCK, kSimple ? 
             // A lane that misses therefore goes from the end of one path to the second ray of the next path within one
             // step, and the walk only ever sees rays that left a surface.
             if (alive && finished()) {
-#if RTP_FINAL_IN_SHADE
                 if (kDefer && L.pend != 0) step_leaf_parked<kSent, kSimple>(L, spheres, planes, l_stack);
-#endif
                 auto over = [&]() { return alive && L.node == kDone && (!path_open || (L.hit < 0 && !(L.depth & kArmBit)) || (L.depth & (kFlagBit | kEndBit)) != 0); };
                 bool go = over();
                 for (int it = 0;; ++it) {
@@ -1984,9 +1882,7 @@ __global__ void __launch_bounds__(kSimple ? kSimpleBlock : RTP_BLOCK, kSimple ? 
             }
         } else
         if (alive && finished()) {
-#if RTP_FINAL_IN_SHADE
             if (kDefer && L.pend != 0) step_leaf_parked<kSent, kSimple>(L, spheres, planes, l_stack);
-#endif
             bool cont = false;
             f3 ray_o = mk(0, 0, 0), ray_d = mk(0, 0, 0);
             RTP_COUNT(3, path_open);
@@ -2034,7 +1930,6 @@ __global__ void __launch_bounds__(kSimple ? kSimpleBlock : RTP_BLOCK, kSimple ? 
                     else if (kOctT) step_threaded_oct(L, (uint32_t)oct_base);
                     else if (kThreaded) step_threaded(L, nodes, P.num_tnodes);
                     else if (kWidePar) step_wide_par(L, nodes, l_stack, walk_levels, dyn_par);
-                    else if (kWide) step_wide<!kLds, !kLds>(L, nodes, l_nodes, P.num_top, l_stack, P.stack_levels);
                     else if (kOct) step_octant(L, l_stack, P.stack_levels);
                     else if (kDynPair) step_pair_par(L, nodes, l_stack, walk_levels, dyn_par);
                     else step_inner<!kLds, !kLds>(L, nodes, l_nodes, P.num_top, l_stack, P.stack_levels);
@@ -2048,7 +1943,6 @@ __global__ void __launch_bounds__(kSimple ? kSimpleBlock : RTP_BLOCK, kSimple ? 
                         else if (kOctT) step_threaded_oct(L, (uint32_t)oct_base);
                     else if (kThreaded) step_threaded(L, nodes, P.num_tnodes);
                         else if (kWidePar) step_wide_par(L, nodes, l_stack, walk_levels, dyn_par);
-                    else if (kWide) step_wide<!kLds, !kLds>(L, nodes, l_nodes, P.num_top, l_stack, P.stack_levels);
                         else if (kOct) step_octant(L, l_stack, P.stack_levels);
                         else if (kDynPair) step_pair_par(L, nodes, l_stack, walk_levels, dyn_par);
                         else step_inner<!kLds, !kLds>(L, nodes, l_nodes, P.num_top, l_stack, P.stack_levels);
@@ -2263,7 +2157,6 @@ __global__ void __launch_bounds__(kAccWaves * 64) accumulate_kernel(float *fb, c
         if (valid) { const f3 t = sky_sum(); fb[3 * (size_t)q] = t.x; fb[3 * (size_t)q + 1] = t.y; fb[3 * (size_t)q + 2] = t.z; }
         return;
     }
-#if RTP_ACC_PIPELINED
     if (npix == 64u && (pitch % kAccSlots) == 0u) {
         // Full wave, whole tiles: the loads of tile t+1 are in flight (in registers) while tile t is summed out of LDS.
         // One load instruction covers 5 pixels x 12 float4 (lanes 0..59: 192 contiguous bytes per pixel); 13 of them cover
@@ -2313,7 +2206,6 @@ __global__ void __launch_bounds__(kAccWaves * 64) accumulate_kernel(float *fb, c
         if (valid) { fb[3 * (size_t)q] = sum.x; fb[3 * (size_t)q + 1] = sum.y; fb[3 * (size_t)q + 2] = sum.z; }      // (not valid: a pixel left to the list launch)
         return;
     }
-#endif
     for (uint32_t s0 = 0; s0 < (uint32_t)count; s0 += kAccSlots) {
         const uint32_t ns = pitch - s0 < (uint32_t)kAccSlots ? pitch - s0 : (uint32_t)kAccSlots;      // slots of this tile (padding included: multiple of 4)
         const uint32_t seg4 = ns * 3u / 4u;                                                           // float4s per pixel segment

@@ -465,8 +465,6 @@ class DeviceScene:
         """Name (as rocprofv3 prints it) of the dominant kernel of the most recent rt_render."""
         t = self.last_timing()
         lds = "true" if t.scene_in_lds else "false"
-        if t.kernel == KERNEL_WAVEFRONT:
-            return f"void rtk::render_kernel_wf<{lds}>(rtk::KParams)"
         return (f"void rtk::render_kernel<{lds}, {'false' if t.guarded else 'true'}, {'true' if t.guard_dynamic else 'false'}, "
                 f"{'true' if t.wide_nodes else 'false'}, {'true' if t.sphere_only else 'false'}, "
                 f"{'true' if t.primary_visibility else 'false'}>(rtk::KParams)")

@@ -601,6 +601,22 @@ def test_distance_aware_margins():
     assert_same_frame(fb, ob.render(host, cam, threads=8), "scattered tiny spheres, distance-aware margins")
 
 
+def test_wide_nodes_with_distance_aware_margins_and_a_short_stack():
+    """The walk with distance-aware margins on 4-wide nodes (step_wide_par: S-rtiow with the margins forced and the general build),
+    with its own stack and with a 3-entry one that overflows (more flagged samples): the oracle's frames."""
+    host = rb.HostScene.rtiow()
+    cam = rb.rtiow_camera(240, 135, 8, 50)
+    want = ob.render(host, cam, threads=8)
+    dev = rb.DeviceScene(host, device=0, honour_env=False, guard_dynamic_margins=2, sphere_only_kernel=-1, traversal=rb.TRAVERSAL_GUARDED, guard_keep=1)
+    fb, t = dev.render_to_host(cam)
+    assert t.guarded == 1 and t.wide_nodes == 1 and t.guard_dynamic == 1 and t.scene_in_lds == 0
+    assert_same_frame(fb, want, "S-rtiow, wide nodes + distance-aware margins")
+    dev.configure(stack_levels=3, guard_keep=1)
+    fb, t3 = dev.render_to_host(cam)
+    assert t3.wide_nodes == 1 and t3.flagged_samples > t.flagged_samples
+    assert_same_frame(fb, want, "S-rtiow, wide nodes + distance-aware margins, 3-entry stack")
+
+
 def test_distance_aware_margins_with_the_by_pixel_primary_pass():
     """the combination a big scene rendered in few big passes takes by default — distance-aware margins (kDyn
     kernels) x the primary-visibility pass in its by-pixel form (primary_pixel_kernel: passes of 96 samples per pixel or more),
@@ -1341,12 +1357,12 @@ def test_hit_scene_on_crafted_rays():
     assert np.array_equal(t[h].view(np.uint32), ot[h].view(np.uint32)) and np.array_equal(prim[h], oprim[h])
 
 
-def test_developer_build_checks():
-    """The developer build (make dev → librtp_amd_dev.so: the shipped library plus the experimental wavefront kernel and the
-    rt_debug_* entry points) through tests/dev_build_checks.py, in ONE child process that loads that library instead of the
-    shipped one: recip() / sqrt_cr() against the compiler's correctly rounded forms on all 2^32 floats ON THIS DEVICE, the
-    shared-reciprocal sphere roots on 2^32 sampled operand sets, the wavefront kernel's frames against the oracle.  The
-    shipped library must not carry any of it."""
+def test_developer_build_checks_and_retired_experiments():
+    """The developer build (make dev → librtp_amd_dev.so: the shipped library plus the rt_debug_* entry points and the tripwire)
+    through tests/dev_build_checks.py, in ONE child process that loads that library instead of the shipped one: recip() /
+    sqrt_cr() against the compiler's correctly rounded forms on all 2^32 floats ON THIS DEVICE, the shared-reciprocal sphere roots
+    on 2^32 sampled operand sets, the tripwire.  The shipped library must not carry any of it, and refuses the retired experiments
+    (RT_KERNEL_WAVEFRONT, rt_config.wide_nodes = 1)."""
     import subprocess
     import sys
     lib = rb.amd_lib()
@@ -1354,9 +1370,9 @@ def test_developer_build_checks():
     assert not hasattr(lib, "rt_debug_check_fast_math") and not hasattr(lib, "rt_debug_check_sphere_roots")
     assert not hasattr(lib, "rt_debug_build_lbvh") and not hasattr(lib, "rt_debug_guard_leaves")
     host = rb.HostScene.rtiow()
-    with pytest.raises(RuntimeError, match="developer build"):
+    with pytest.raises(RuntimeError, match="retired"):
         rb.DeviceScene(host, device=0, honour_env=False, kernel=rb.KERNEL_WAVEFRONT).render_to_host(rb.rtiow_camera(32, 20, 2, 8))
-    with pytest.raises(RuntimeError, match="developer build"):
+    with pytest.raises(RuntimeError, match="retired"):
         rb.DeviceScene(host, device=0, honour_env=False, wide_nodes=1).render_to_host(rb.rtiow_camera(32, 20, 2, 8))
     dev_lib = os.path.join(os.path.dirname(HERE), "ray-tracing-practice_amd", "librtp_amd_dev.so")
     assert os.path.exists(dev_lib), "run __graft_entry__.build() (make -C ray-tracing-practice_amd dev)"

@@ -1,5 +1,6 @@
-"""Dev tool (GPU): 4-wide nodes vs child-pair nodes — S-rtiow 1920x1080 (SPP, default 100) and S-100k 4K (C5SPP, default 16);
-frames compared with each other, times from rt_timing."""
+"""Dev tool (GPU): rt_config.wide_nodes = 0 (4-wide nodes for scenes with distance-aware margins: step_wide_par) vs -1 (child-pair
+nodes only) — S-rtiow 1920x1080 (SPP, default 100) and S-100k 4K (C5SPP, default 16); frames compared with each other, times from
+rt_timing."""
 import os, sys
 sys.path.insert(0, 'tests'); sys.path.insert(0, 'ray-tracing-practice_amd')
 import numpy as np
@@ -9,7 +10,7 @@ SPP = int(os.environ.get('SPP', 100)); C5SPP = int(os.environ.get('C5SPP', 16))
 for label, host, cam in (('S-rtiow 1080p', rb.HostScene.rtiow(), rb.rtiow_camera(1920, 1080, SPP, 50)),
                          ('S-100k 4K', rb.HostScene.rtiow(half_extent=158, textured_quad=True, texture_size=1024), rb.rtiow_camera(3840, 2160, C5SPP, 50))):
     ref = None
-    for wide in (1, 0):
+    for wide in (0, -1):
         dev = rb.DeviceScene(host, device=0, wide_nodes=wide)
         best = 1e9
         for _ in range(3):
