@@ -363,6 +363,57 @@ rt_status rt_render_aov(rt_scene *scene, const rt_camera_data *cam, const rt_sha
 rt_status rt_render_aov_tile(rt_scene *scene, const rt_camera_data *cam, int32_t tile_x0, int32_t tile_y0, int32_t tile_w, int32_t tile_h,
                              const rt_aov_buffers *buffers, void *hip_stream, int32_t sync, rt_timing *timing);
 
+/* ---- denoising: an edge-avoiding à-trous wavelet filter guided by the first-hit AOVs ----------------------------------------
+ * The spatial filter of SVGF (Dammertz et al. 2010, Schied et al. 2017; no temporal part) over a whole image: a beauty frame as
+ * rt_render writes it (the sum over samples) and the AOV sums rt_render_aov wrote for the same camera.  W x H buffers of a frame
+ * rendered without a shard, or of one tile treated as an image of its own.
+ *
+ * The arithmetic is part of the contract: float32, evaluated in the order written, nothing fused, divisions and sqrtf correctly
+ * rounded, exp = the host libm's expf (the library's exp_libm restates it bit for bit for x <= 0).  S = samples_per_pixel,
+ * inv = (float)(1.0 / (double)S) as rt_tonemap computes it.  A pixel is a HIT pixel when hit_count > 0.
+ *   Sky pixels (hit_count == 0): out = fb_sum bit for bit; a sky pixel is never a tap of another pixel.
+ *   Prepass, per hit pixel:  c_k = fb_sum_k * inv,  a_k = albedo_sum_k * inv,  d_k = fmaxf(a_k, 1e-3f),  L_k = c_k / d_k;
+ *     len2 = (N.x*N.x + N.y*N.y) + N.z*N.z with N = normal_sum,  n_k = N_k / sqrtf(len2)  (n = 0 when len2 == 0);
+ *     z = depth_sum / (float)hit_count;   lum(L) = (0.2126f*L0 + 0.7152f*L1) + 0.0722f*L2.
+ *   Second prepass, per hit pixel p:
+ *     var_p: over the 3x3 window (dy = -1..1 outer, dx = -1..1 inner), hit pixels inside the image only, l = lum(L):
+ *       m1 += l, m2 += l*l, k += 1 (float, from 0);  var = fmaxf(0, m2/k - (m1/k)*(m1/k)).
+ *     gz_p = gx + gy,  gx = fminf(|z(x+1) - z_p|, |z_p - z(x-1)|) where a neighbour outside the image or not a hit pixel gives
+ *       +inf for its term; gx = 0 when both are missing.  gy the same along y.
+ *   Iteration i = 0 … iterations-1, step s = 2^i, per hit pixel p:
+ *     rl = 1 / (sigma_luminance * sqrtf(var_p) + 1e-4f);   rz[m] = 1 / ((sigma_depth * gz_p) * (float)(s*m) + 1e-4f), m = 0…4;
+ *     taps q = p + s*(dx, dy), dy = -2..2 outer, dx = -2..2 inner, skipping taps outside the image or not hit pixels; W, ΣL_k,
+ *     ΣV start at 0;  per tap:
+ *       h  = kern[|dx|] * kern[|dy|],  kern = {3/8, 1/4, 1/16};
+ *       wn = fmaxf(0, (n_p.x*n_q.x + n_p.y*n_q.y) + n_p.z*n_q.z), then wn = wn*wn, normal_squarings times;
+ *       e  = |z_p - z_q| * rz[|dx|+|dy|] + |l_p - l_q| * rl;       w = (h * wn) * exp(-e);
+ *       W += w;  ΣL_k += w * L_q,k;  ΣV += (w*w) * var_q;
+ *     L'_p = ΣL / W, var'_p = ΣV / (W*W); W == 0 keeps L and var.  The next iteration reads L' and var' (and l = lum(L')).
+ *   Remodulation, per hit pixel: out_k = (L_k * d_k) * (float)S  (with iterations = 0: the prepass's L).
+ * d_out has d_fb_sum's convention (the sum over samples), so rt_tonemap with the caller's divisor and the savers take it as they
+ * take a beauty frame. */
+typedef struct rt_denoise_params {   /* IN, grows like rt_aov_buffers: the library reads at most struct_bytes; later fields keep
+                                        their defaults.  struct_bytes below 8 is RT_ERR_INVALID_ARG */
+    uint32_t struct_bytes;           /* sizeof(rt_denoise_params) as the caller compiled it */
+    int32_t  iterations;             /* 5; 0 … 8 (the last step is 2^7 = 128 pixels) */
+    float    sigma_depth;            /* 1.0 (> 0, finite) */
+    float    sigma_luminance;        /* 4.0 (> 0, finite) */
+    int32_t  normal_squarings;       /* 7: the normal weight is max(0, n_p·n_q)^(2^7); 0 … 10 */
+} rt_denoise_params;
+/* Defaults into *p, struct_bytes = sizeof(rt_denoise_params). */
+void rt_denoise_params_init(rt_denoise_params *p);
+/* Bytes of device workspace rt_denoise needs for a width x height image (64 per pixel and 256 for alignment; 0 when width or
+ * height is below 1).  Any alignment of d_workspace is accepted. */
+uint64_t rt_denoise_workspace_bytes(int32_t width, int32_t height);
+/* Enqueues the filter on hip_stream (NULL = default stream): no allocation, no synchronisation.  All pointers are DEVICE memory;
+ * aov->albedo_sum, normal_sum, depth_sum and hit_count are required (first_prim is not used).  params NULL = defaults.
+ * RT_ERR_INVALID_ARG: a required pointer NULL, width or height below 1, samples_per_pixel outside 1 … 65536, a parameter outside
+ * its range, workspace_bytes below rt_denoise_workspace_bytes, d_out overlapping an input or the workspace, or the workspace
+ * overlapping an input.  RT_ERR_UNSUPPORTED: width x height above 2^24 (rt_render's limit).  Every check comes before any HIP
+ * call. */
+rt_status rt_denoise(const float *d_fb_sum, const rt_aov_buffers *aov, int32_t width, int32_t height, int32_t samples_per_pixel,
+                     const rt_denoise_params *params, void *d_workspace, uint64_t workspace_bytes, float *d_out, void *hip_stream);
+
 /* Milliseconds of the most recent rt_render kernel of this scene (waits for it). */
 rt_status rt_last_kernel_ms(rt_scene *scene, float *ms);
 /* The whole rt_timing of the most recent rt_render of this scene (waits for it). */

@@ -28,21 +28,25 @@ int main(int argc, char *argv[]) {
     rtp::build_config_scene(params, "", host);
 
     const rt_scene_desc desc = host.desc();
-    // extension: `--gpu --aov` also writes each frame's first-hit AOVs to "<frame file>.aov" (frame-after-frame driver only)
-    bool aov = false;
-    for (int a = 2; a < argc; ++a)
+    // extension: `--gpu --aov` also writes each frame's first-hit AOVs to "<frame file>.aov", and `--gpu --denoise` the frame filtered
+    // by rt_denoise to "<frame file>.denoised" (frame-after-frame driver only)
+    bool aov = false, denoise = false;
+    for (int a = 2; a < argc; ++a) {
         if (std::string(argv[a]) == "--aov") aov = true;
+        if (std::string(argv[a]) == "--denoise") denoise = true;
+    }
     // extension: `--gpu --devices N` (or RTP_DEVICES=N) renders the animation with the pipelined
     // multi-GPU driver; the default is the reference's frame-after-frame loop.
     int devices = 0;
     if (const char *env = getenv("RTP_DEVICES")) devices = atoi(env);
     for (int a = 2; a + 1 < argc; ++a)
         if (std::string(argv[a]) == "--devices") devices = atoi(argv[a + 1]);
-    if (aov) {
+    if (aov || denoise) {
         for (int a = 2; a < argc; ++a)
             if (std::string(argv[a]) == "--devices" || std::string(argv[a]) == "--shard") devices = 1;
         if (devices > 0) {
-            std::cerr << "rtp_main: --aov renders frame after frame on one GPU: it cannot be combined with --devices, --shard or RTP_DEVICES\n";
+            std::cerr << "rtp_main: " << (aov ? "--aov" : "--denoise")
+                      << " renders frame after frame on one GPU: it cannot be combined with --devices, --shard or RTP_DEVICES\n";
             return 2;
         }
     }
@@ -59,7 +63,7 @@ int main(int argc, char *argv[]) {
     rt_scene *scene = nullptr;
     RTP_CHECK(rt_scene_create(&desc, &scene));
     rtp::bind_scene(scene);
-    rtp::gpu_render(params, aov);
+    rtp::gpu_render(params, aov, denoise);
     RTP_CHECK(rt_scene_destroy(scene));
     return 0;
 }

@@ -75,7 +75,7 @@ std::string frame_filename(const std::string &pattern, int n) {
     return out;
 }
 
-void gpu_render(const SceneParams &params, bool aov) {
+void gpu_render(const SceneParams &params, bool aov, bool denoise) {
     float *d_fb = nullptr;
     const size_t num_pixels = static_cast<size_t>(params.width) * params.height;
     RTP_CHECK(rt_device_alloc(num_pixels * 3 * sizeof(float), reinterpret_cast<void **>(&d_fb)));
@@ -84,7 +84,7 @@ void gpu_render(const SceneParams &params, bool aov) {
     rt_aov_buffers_init(&aov_bufs);
     std::vector<float> h_albedo, h_normal, h_depth;
     std::vector<uint32_t> h_hits;
-    if (aov) {
+    if (aov || denoise) {
         RTP_CHECK(rt_device_alloc(num_pixels * 12, reinterpret_cast<void **>(&aov_bufs.albedo_sum)));
         RTP_CHECK(rt_device_alloc(num_pixels * 12, reinterpret_cast<void **>(&aov_bufs.normal_sum)));
         RTP_CHECK(rt_device_alloc(num_pixels * 4, reinterpret_cast<void **>(&aov_bufs.depth_sum)));
@@ -93,6 +93,16 @@ void gpu_render(const SceneParams &params, bool aov) {
         h_normal.resize(num_pixels * 3);
         h_depth.resize(num_pixels);
         h_hits.resize(num_pixels);
+    }
+    // --denoise: rt_denoise's workspace and output (the sum over samples, like d_fb)
+    void *d_workspace = nullptr;
+    float *d_denoised = nullptr;
+    const uint64_t workspace_bytes = denoise ? rt_denoise_workspace_bytes(params.width, params.height) : 0;
+    std::vector<float> h_denoised;
+    if (denoise) {
+        RTP_CHECK(rt_device_alloc(workspace_bytes, &d_workspace));
+        RTP_CHECK(rt_device_alloc(num_pixels * 3 * sizeof(float), reinterpret_cast<void **>(&d_denoised)));
+        h_denoised.resize(num_pixels * 3);
     }
 
     for (int n = 0; n < params.num_frames; ++n) {
@@ -114,17 +124,27 @@ void gpu_render(const SceneParams &params, bool aov) {
         const float ms = std::chrono::duration<float, std::milli>(t1 - t0).count();
         const long long total_rays = static_cast<long long>(params.width) * params.height * params.sqrt_spp * params.sqrt_spp;
         std::cout << n << "\t" << ms << "\t" << total_rays << "\n";
-        if (aov) {          // (outside the frame's timed span: the reference has no such output)
+        if (aov || denoise) {          // (outside the frame's timed span: the reference has no such output)
             const rt_camera_data cam = camera.build_camera_data();
             RTP_CHECK(rt_render_aov(bound_scene(), &cam, nullptr, &aov_bufs, nullptr, 1, nullptr));
-            RTP_CHECK(rt_copy_to_host(h_albedo.data(), aov_bufs.albedo_sum, num_pixels * 12));
-            RTP_CHECK(rt_copy_to_host(h_normal.data(), aov_bufs.normal_sum, num_pixels * 12));
-            RTP_CHECK(rt_copy_to_host(h_depth.data(), aov_bufs.depth_sum, num_pixels * 4));
-            RTP_CHECK(rt_copy_to_host(h_hits.data(), aov_bufs.hit_count, num_pixels * 4));
-            if (!write_aov_file(filename + ".aov", params.width, params.height, cam.samples_per_pixel, h_albedo.data(), h_normal.data(), h_depth.data(),
-                                h_hits.data())) {
-                std::cerr << "cannot write " << filename << ".aov\n";
-                std::exit(99);
+            if (aov) {
+                RTP_CHECK(rt_copy_to_host(h_albedo.data(), aov_bufs.albedo_sum, num_pixels * 12));
+                RTP_CHECK(rt_copy_to_host(h_normal.data(), aov_bufs.normal_sum, num_pixels * 12));
+                RTP_CHECK(rt_copy_to_host(h_depth.data(), aov_bufs.depth_sum, num_pixels * 4));
+                RTP_CHECK(rt_copy_to_host(h_hits.data(), aov_bufs.hit_count, num_pixels * 4));
+                if (!write_aov_file(filename + ".aov", params.width, params.height, cam.samples_per_pixel, h_albedo.data(), h_normal.data(),
+                                    h_depth.data(), h_hits.data())) {
+                    std::cerr << "cannot write " << filename << ".aov\n";
+                    std::exit(99);
+                }
+            }
+            if (denoise) {       // the frame's own saver code and divisor, into "<frame file>.denoised"
+                RTP_CHECK(rt_denoise(d_fb, &aov_bufs, params.width, params.height, cam.samples_per_pixel, nullptr, d_workspace, workspace_bytes,
+                                     d_denoised, nullptr));
+                RTP_CHECK(rt_copy_to_host(h_denoised.data(), d_denoised, num_pixels * 3 * sizeof(float)));
+                BinarySaver out(params.sqrt_spp, filename + ".denoised");
+                out.set_format(params.width, params.height);
+                for (size_t p = 0; p < num_pixels; ++p) out.write_color(Vec3(h_denoised[3 * p], h_denoised[3 * p + 1], h_denoised[3 * p + 2]));
             }
         }
     }
@@ -133,6 +153,8 @@ void gpu_render(const SceneParams &params, bool aov) {
     rt_device_free(aov_bufs.normal_sum);
     rt_device_free(aov_bufs.depth_sum);
     rt_device_free(aov_bufs.hit_count);
+    rt_device_free(d_workspace);
+    rt_device_free(d_denoised);
 }
 
 // ---- animation driver ("next" rows f1 + f2 of SURVEY.md §8) ---------------------------------------

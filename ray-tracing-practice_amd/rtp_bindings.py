@@ -88,6 +88,17 @@ AOV_CHANNELS = (("albedo", "albedo_sum", np.float32, 3), ("normal", "normal_sum"
                 ("hits", "hit_count", np.uint32, 1), ("prim", "first_prim", np.int32, 1))
 
 
+class DenoiseParams(C.Structure):
+    """rt_denoise_params (include/rtp_amd.h): an IN structure of the caller's size — struct_bytes is set on construction; the
+    other fields are 0 until rt_denoise_params_init (denoise_params()) fills the defaults."""
+    _fields_ = [("struct_bytes", C.c_uint32), ("iterations", C.c_int32), ("sigma_depth", C.c_float), ("sigma_luminance", C.c_float),
+                ("normal_squarings", C.c_int32)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_bytes = C.sizeof(DenoiseParams)
+
+
 TRAVERSAL_AUTO, TRAVERSAL_EXACT, TRAVERSAL_GUARDED = 0, 1, 2
 BUILD_HOST_SAH, BUILD_DEVICE_LBVH = 0, 1
 KERNEL_AUTO, KERNEL_MEGA, KERNEL_WAVEFRONT = 0, 1, 2
@@ -136,6 +147,7 @@ RTP_AMD_SYMBOLS = [
     "rt_get_last_error_string", "rt_version_string",
     "rt_context_create", "rt_context_destroy", "rt_context_num_devices", "rt_context_transport", "rt_context_scene_create",
     "rt_render_sharded", "rt_gather", "rt_aov_buffers_init", "rt_render_aov", "rt_render_aov_tile",
+    "rt_denoise_params_init", "rt_denoise_workspace_bytes", "rt_denoise",
 ]
 
 _host = None
@@ -207,6 +219,13 @@ def amd_lib():
                                           C.POINTER(Timing)]
             lib.rt_render_aov_tile.argtypes = [C.c_void_p, C.POINTER(CameraData), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                                C.POINTER(AovBuffers), C.c_void_p, C.c_int32, C.POINTER(Timing)]
+        if hasattr(lib, "rt_denoise"):
+            lib.rt_denoise_params_init.argtypes = [C.POINTER(DenoiseParams)]
+            lib.rt_denoise_params_init.restype = None
+            lib.rt_denoise_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
+            lib.rt_denoise_workspace_bytes.restype = C.c_uint64
+            lib.rt_denoise.argtypes = [C.c_void_p, C.POINTER(AovBuffers), C.c_int32, C.c_int32, C.c_int32, C.POINTER(DenoiseParams),
+                                       C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         lib.rt_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         lib.rt_last_timing.argtypes = [C.c_void_p, C.POINTER(Timing)]
         lib.rt_timing_init.argtypes = [C.POINTER(Timing)]
@@ -325,6 +344,96 @@ def binary_image_bytes(fb_sum, width, height, divisor):
 HONOUR_ENV = False
 # rt_config fields every DeviceScene made without them starts from (a test fixture's way to say "guarded walk throughout")
 DEFAULTS = {}
+
+
+def denoise_params(**params):
+    """rt_denoise_params with the library's defaults (rt_denoise_params_init), then the given fields (iterations, sigma_depth,
+    sigma_luminance, normal_squarings)."""
+    p = DenoiseParams()
+    amd_lib().rt_denoise_params_init(C.byref(p))
+    for k, v in params.items():
+        if k not in ("iterations", "sigma_depth", "sigma_luminance", "normal_squarings"):
+            raise TypeError(f"rt_denoise_params has no field {k!r}")
+        setattr(p, k, v)
+    return p
+
+
+# rt_denoise workspaces, one per size: allocated on the device current at their first use (a caller that switches devices
+# passes workspace=(address, bytes) of its own)
+_denoise_workspaces = {}
+
+
+def denoise(d_fb, aov_ptrs, width, height, spp, d_out, stream=None, workspace=None, **params):
+    """rt_denoise on device addresses: d_fb (the beauty sums), aov_ptrs {"albedo", "normal", "depth", "hits"} → device address (as
+    DeviceScene.render_aov takes them), d_out (width * height * 3 floats).  Only enqueues on `stream` (None = default stream).
+    params: rt_denoise_params fields."""
+    lib = amd_lib()
+    b = AovBuffers()
+    for key, field, _, _ in AOV_CHANNELS:
+        if aov_ptrs.get(key):
+            setattr(b, field, aov_ptrs[key])
+    if workspace is None:
+        need = lib.rt_denoise_workspace_bytes(width, height)
+        workspace = _denoise_workspaces.get(need)
+        if workspace is None and need > 0:
+            d = C.c_void_p()
+            _check(lib.rt_device_alloc(need, C.byref(d)), "rt_device_alloc")
+            workspace = _denoise_workspaces[need] = (d.value, need)
+    ws_ptr, ws_bytes = workspace or (None, 0)
+    p = denoise_params(**params)
+    _check(lib.rt_denoise(C.c_void_p(d_fb), C.byref(b), width, height, spp, C.byref(p), C.c_void_p(ws_ptr), ws_bytes, C.c_void_p(d_out),
+                          C.c_void_p(stream or 0)), "rt_denoise")
+
+
+_hip_rt = None
+
+
+def _hip():
+    """The HIP runtime librtp_amd.so itself runs on (already loaded with it: found by soname, never loaded a second time), for the
+    host-to-device copies of denoise_to_host — the C ABI has no upload call of its own."""
+    global _hip_rt
+    if _hip_rt is None:
+        amd_lib()
+        for name in ("libamdhip64.so.7", "libamdhip64.so.6", "libamdhip64.so"):
+            try:
+                _hip_rt = C.CDLL(name, mode=os.RTLD_NOLOAD | os.RTLD_LAZY)
+                break
+            except OSError:
+                continue
+        if _hip_rt is None:
+            raise RuntimeError("the HIP runtime of librtp_amd.so is not loaded")
+        _hip_rt.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    return _hip_rt
+
+
+def denoise_to_host(fb_sum, aov, spp, **params):
+    """rt_denoise of host arrays: fb_sum (H, W, 3) float32 as DeviceScene.render_to_host returns it, aov the dict of
+    DeviceScene.render_aov_to_host (albedo, normal, depth, hits; prim is not used).  Returns the (H, W, 3) float32 output, the sum
+    over samples like fb_sum.  Synchronous (default stream)."""
+    lib = amd_lib()
+    fb = np.ascontiguousarray(fb_sum, dtype=np.float32)
+    height, width = fb.shape[:2]
+    arrays = {"fb": fb}
+    for key, _, dtype, _ in AOV_CHANNELS[:4]:
+        arrays[key] = np.ascontiguousarray(aov[key], dtype=dtype)
+    dev = {}
+    try:
+        for key, a in arrays.items():
+            d = C.c_void_p()
+            _check(lib.rt_device_alloc(a.nbytes or 4, C.byref(d)), "rt_device_alloc")
+            dev[key] = d
+            if _hip().hipMemcpy(d, a.ctypes.data, a.nbytes, 1) != 0:       # hipMemcpyHostToDevice
+                raise RtError("hipMemcpy host to device failed")
+        d_out = C.c_void_p()
+        _check(lib.rt_device_alloc(fb.nbytes or 4, C.byref(d_out)), "rt_device_alloc")
+        dev["out"] = d_out
+        denoise(dev["fb"].value, {k: dev[k].value for k in ("albedo", "normal", "depth", "hits")}, width, height, spp, d_out.value, **params)
+        out = np.empty_like(fb)
+        _check(lib.rt_copy_to_host(out.ctypes.data, d_out, out.nbytes), "rt_copy_to_host")
+    finally:
+        for d in dev.values():
+            lib.rt_device_free(d)
+    return out
 
 
 class DeviceScene:
