@@ -369,7 +369,7 @@ rt_status rt_render_aov_tile(rt_scene *scene, const rt_camera_data *cam, int32_t
  * rendered without a shard, or of one tile treated as an image of its own.
  *
  * The arithmetic is part of the contract: float32, evaluated in the order written, nothing fused, divisions and sqrtf correctly
- * rounded, exp = the host libm's expf (the library's exp_libm restates it bit for bit for x <= 0).  S = samples_per_pixel,
+ * rounded, exp = the host libm's expf (the library's exp_libm restates it bit for bit for every float).  S = samples_per_pixel,
  * inv = (float)(1.0 / (double)S) as rt_tonemap computes it.  A pixel is a HIT pixel when hit_count > 0.
  *   Sky pixels (hit_count == 0): out = fb_sum bit for bit; a sky pixel is never a tap of another pixel.
  *   Prepass, per hit pixel:  c_k = fb_sum_k * inv,  a_k = albedo_sum_k * inv,  d_k = fmaxf(a_k, 1e-3f),  L_k = c_k / d_k;

@@ -159,10 +159,12 @@ RT_HD uint64_t exp2_tab_entry(uint32_t i) {
 #endif
 }
 
-// exp(x) for x <= 0 (the only range Beer-Lambert produces) and moderate positive x.
+// exp(x) for every float, NaN bits included.  Positive arguments are reachable: Beer-Lambert evaluates exp(-absorption * dist)
+// and rt_material.absorption may be negative (a colour component above 1 in scene_builder.cpp), so the overflow threshold is the
+// libm's own — the largest float whose exp is finite is 0x1.62e42ep6 — and a NaN comes back quiet, as x + x, as the libm's does.
 RT_HD float exp_libm(float x) {
-    if (!(x >= -104.0f)) return x != x ? x : 0.0f;      // underflow to 0 (and NaN passthrough)
-    if (x > 88.0f) return x * 3.0e38f;                  // overflow → +inf (unused by the renderer)
+    if (!(x >= -104.0f)) return x != x ? x + x : 0.0f;  // underflow to 0 (a NaN comes back quietened, payload kept)
+    if (x > 0x1.62e42ep6f) return x * 3.0e38f;          // overflow → +inf
     const double N = 32.0;
     const double inv_ln2_n = 0x1.71547652b82fep+0 * N;
     const double shift = 0x1.8p+52;
@@ -177,7 +179,8 @@ RT_HD float exp_libm(float x) {
     kd -= shift;
     // The build of this routine that x86-64 hosts with FMA run (glibc's ifunc picks __expf_fma) has `z - kd` and the
     // polynomial contracted to fused multiply-adds; with exactly these four fusions the values below are that libm's
-    // for EVERY float in [-128, 0] and [0, 88] (2.24e9 values, tests/test_device_math.py; the unfused form differs on 2).
+    // for EVERY float, NaNs included (tests/test_device_math.py on the host, tests/dev_math_checks.py on the device; the unfused
+    // form differs on 2).
     const double r = __builtin_fma(inv_ln2_n, xd, -kd);
     uint64_t t = exp2_tab_entry((uint32_t)(ki % 32u));
     t += ki << (52 - 5);
@@ -290,7 +293,8 @@ RT_HD float acos_libm(float x) {
     memcpy(&ux, &x, 4);
     const int32_t hx = (int32_t)ux, ix = hx & 0x7fffffff;
     if (ix == 0x3f800000) return hx > 0 ? 0.0f : pi + 2.0f * pio2_lo;        // |x| == 1
-    if (ix > 0x3f800000) return (x - x) / (x - x);                               // |x| > 1: NaN
+    // |x| > 1: the libm's +qNaN.  The source's (x - x) / (x - x) gives the FPU's default NaN there, -qNaN on x86-64.
+    if (ix > 0x3f800000) return ix > 0x7f800000 ? x + x : __builtin_nanf("");
     if (ix < 0x3f000000) {                                                       // |x| < 0.5
         if (ix <= 0x32800000) return pio2_hi + pio2_lo;
         const float z = x * x;
@@ -365,7 +369,9 @@ RT_HD float atan2_libm(float y, float x) {
     memcpy(&ux, &x, 4);
     memcpy(&uy, &y, 4);
     const int32_t hx = (int32_t)ux, hy = (int32_t)uy, ix = hx & 0x7fffffff, iy = hy & 0x7fffffff;
-    if (ix > 0x7f800000 || iy > 0x7f800000) return x + y;                        // NaN
+    // NaN: the libm's x + y, which on x86-64 gives the first operand's NaN, quietened, when both are NaN.  Written out, since
+    // a compiler may commute the sum (the host build did, and returned y's NaN).
+    if (ix > 0x7f800000 || iy > 0x7f800000) return ix > 0x7f800000 ? x + x : y + y;
     if (hx == 0x3f800000) return atan_libm(y);                                   // x == 1
     const int32_t m = ((hy >> 31) & 1) | ((hx >> 30) & 2);                       // 2 sign(x) + sign(y)
     if (iy == 0) return m < 2 ? y : (m == 2 ? pi + tiny : -pi - tiny);           // y == +-0
@@ -406,7 +412,7 @@ constexpr uint32_t kPow5Window = 6;
 // evaluating it: r0 + (1 - r0) * p is a non-decreasing function of p in float arithmetic (1 - r0 > 0, rounding is monotonic),
 // and the libm's p lies within kPow5Window steps of pow5_float(x).  If even the lower end of that window gives a value above
 // rnd the answer is yes, if not even the upper end does it is no; only when rnd falls inside the window (~1e-6 of the
-// draws) is powf itself restated (pow5) — by the exact walk: the guarded trace kernel hands such a sample to the re-walk launch
+// draws; 3.3e-7 of random draws over every cos of [-1, 1], tests/dev_math_checks.py) is powf itself restated (pow5) — by the exact walk: the guarded trace kernel hands such a sample to the re-walk launch
 // like any other it cannot vouch for, so its hot shade step carries neither the table-driven code nor its registers, nor any
 // double-precision temporaries (the glass branch runs in nine shade steps of ten; evaluating pow5 there cost 8 % of the
 // headline frame).
