@@ -319,6 +319,15 @@ rt_status rt_render(rt_scene *scene, const rt_camera_data *cam, const rt_shard *
 rt_status rt_render_tile(rt_scene *scene, const rt_camera_data *cam, int32_t tile_x0, int32_t tile_y0, int32_t tile_w, int32_t tile_h,
                          float *d_fb_sum, void *hip_stream, int32_t sync, rt_timing *timing);
 
+/* rt_render for samples sample_first … sample_first + samples_per_pixel - 1 of every pixel instead of 0 … samples_per_pixel - 1: the
+ * seeds of those samples (pixel (i, j), sample s: wang_hash(wang_hash(base(i, j) + s)), as always), added in sample order into sums
+ * that start from 0 — d_fb_sum is overwritten, not added onto.  Successive calls with sample_first = 0, S, 2S, … are fresh samples
+ * of the same image (what a temporal filter needs from a still camera).  rt_render is this call with sample_first = 0.
+ * RT_ERR_INVALID_ARG: sample_first < 0.  RT_ERR_UNSUPPORTED: sample_first + samples_per_pixel above 2^30 (the kernels carry sample
+ * indices as int32).  Both before anything is enqueued.  Rows of a shard only: tiles and rt_context have no such call. */
+rt_status rt_render_samples(rt_scene *scene, const rt_camera_data *cam, const rt_shard *shard, int32_t sample_first,
+                            float *d_fb_sum, void *hip_stream, int32_t sync, rt_timing *timing);
+
 /* ---- first-hit AOVs: the per-pixel buffers a denoiser and a compositor want, from the beauty frame's own camera samples -----
  * For pixel (i, j) and sample s = 0 … samples_per_pixel-1, in sample order: the reference's camera ray (get_ray with the seed of
  * the beauty pass) and its first hit, hit_scene over Interval(0.001, 1e30) as in ray_color.  A hit adds
@@ -362,6 +371,10 @@ rt_status rt_render_aov(rt_scene *scene, const rt_camera_data *cam, const rt_sha
                         void *hip_stream, int32_t sync, rt_timing *timing);
 rt_status rt_render_aov_tile(rt_scene *scene, const rt_camera_data *cam, int32_t tile_x0, int32_t tile_y0, int32_t tile_w, int32_t tile_h,
                              const rt_aov_buffers *buffers, void *hip_stream, int32_t sync, rt_timing *timing);
+/* rt_render_aov for samples sample_first … sample_first + samples_per_pixel - 1, with the checks of rt_render_samples: the sums start
+ * from 0 and first_prim is the hit of sample sample_first.  rt_render_aov is this call with sample_first = 0. */
+rt_status rt_render_aov_samples(rt_scene *scene, const rt_camera_data *cam, const rt_shard *shard, int32_t sample_first,
+                                const rt_aov_buffers *buffers, void *hip_stream, int32_t sync, rt_timing *timing);
 
 /* ---- denoising: an edge-avoiding à-trous wavelet filter guided by the first-hit AOVs ----------------------------------------
  * The spatial filter of SVGF (Dammertz et al. 2010, Schied et al. 2017; no temporal part) over a whole image: a beauty frame as
@@ -413,6 +426,57 @@ uint64_t rt_denoise_workspace_bytes(int32_t width, int32_t height);
  * call. */
 rt_status rt_denoise(const float *d_fb_sum, const rt_aov_buffers *aov, int32_t width, int32_t height, int32_t samples_per_pixel,
                      const rt_denoise_params *params, void *d_workspace, uint64_t workspace_bytes, float *d_out, void *hip_stream);
+
+/* ---- temporal denoising: SVGF's reprojected history across the frames of an animation ----------------------------------------
+ * rt_denoise's filter fed with colour and luminance moments accumulated over earlier frames (Schied et al. 2017, §4.1-4.2): each hit
+ * pixel is reprojected into the history the previous call wrote, blended with it, and the variance that steers the à-trous weights
+ * comes from the accumulated moments once the history is long enough.  The image size and S come from cam (HOST memory); the
+ * other inputs are rt_denoise's plus first_prim (all five AOV buffers required).
+ *
+ * The arithmetic extends rt_denoise's contract (same rules: float32 in the order written, nothing fused, correctly rounded division
+ * and sqrtf, exp = expf).  Fixed constants: tau2 = 0.0025f (a tap's hit point within 0.05 of the pixel's distance from the camera),
+ * min_weight = 0.01f, max_len = 32.0f, min_alpha = 0.2f, moments_len = 4.0f, min_normal_dot = 0.9f.  dot(a, b) = (a0*b0 + a1*b1) + a2*b2.
+ *   Prepass and second prepass: rt_denoise's, giving per hit pixel L_cur, d, n, z, gz and the 3x3 spatial variance var_sp.
+ *   Temporal pass, per hit pixel p = (x, y), with prim = first_prim_p and m1 = lum(L_cur):
+ *     pc_k = (P00_k + (float)x * du_k) + (float)y * dv_k,  X_k = O_k + z * (pc_k - O_k)  (the camera cam: O origin, P00 pixel00_loc,
+ *       du, dv pixel_delta_u / v);  OX = X - O,  reach2 = tau2 * dot(OX, OX).
+ *     The history is EMPTY when history_prev is NULL or its header is not one this call writes for this width and height (an
+ *       all-zero buffer is empty).  Otherwise, with the history's camera (O', P00', du', dv'):
+ *       N = cross(du', dv') = (du'1*dv'2 - du'2*dv'1, du'2*dv'0 - du'0*dv'2, du'0*dv'1 - du'1*dv'0);  E = P00' - O',  D = X - O';
+ *       t = dot(E, N) / dot(D, N); the pixel reprojects only when 0 < t < +inf (in front of the old camera, not on its plane);
+ *       R_k = t * D_k - E_k,  u = dot(R, du') / dot(du', du'),  v = dot(R, dv') / dot(dv', dv');  and only when -1 < u < W, -1 < v < H.
+ *       x0 = floorf(u), y0 = floorf(v), fx = u - x0, fy = v - y0.  Taps q = (x0, y0), (x0+1, y0), (x0, y0+1), (x0+1, y0+1) in that
+ *       order, bilinear weights w = (fx or 1 - fx) * (fy or 1 - fy); a tap counts when it lies inside the image, its history length
+ *       len_q > 0 (it was a hit pixel), first_prim_q == prim, dot(n_p, n_q) >= min_normal_dot and dot(X_q - X, X_q - X) <= reach2
+ *       (X_q - X per component).  Over the taps that count, from 0: W += w, S_k += w * Lh_q,k, SM1 += w * M1_q, SM2 += w * M2_q,
+ *       SN += w * len_q.
+ *     With W >= min_weight: len = fminf(SN / W + 1, max_len), a = fmaxf(min_alpha, 1 / len), b = 1 - a;
+ *       L_k = b * (S_k / W) + a * L_cur,k,  M1 = b * (SM1 / W) + a * m1,  M2 = b * (SM2 / W) + a * (m1 * m1).
+ *     Otherwise (empty history, no reprojection, W < min_weight) the pixel is disoccluded: L = L_cur, M1 = m1, M2 = m1 * m1, len = 1.
+ *     var = len >= moments_len ? fmaxf(0, M2 - M1 * M1) : var_sp.
+ *   Iterations: rt_denoise's, on (L, var).  Remodulation: rt_denoise's (with iterations = 0: of L).  Sky pixels: out = fb_sum bit for bit.
+ * With an empty history d_out is rt_denoise's output bit for bit.
+ *
+ * History buffer (rt_denoise_history_bytes, 16-byte aligned): a 256-byte header — uint32 magic 0x31485452, int32 width, int32 height,
+ * uint32 0, the 76-byte rt_camera_data the history was made with, zeros — then four planes of W x H records of four floats:
+ *   colour  (L'_0, L'_1, L'_2, var')  iteration 0's output, the colour the next frame reprojects (with 0 iterations: (L, var))
+ *   moments (M1, M2, len, prim)       prim as its int32 bits
+ *   position (X_0, X_1, X_2, 0)   normal (n_0, n_1, n_2, 0)
+ * A sky pixel's four records are all zero (len = 0).  The call's kernels write the whole of history_next; the caller swaps prev and
+ * next between frames and may hipMemset a fresh buffer to 0 (or pass NULL) for a first frame or a cut.  Because the two buffers are
+ * distinct, a call can be replayed. */
+/* Bytes of one history buffer for a width x height image (64 per pixel and the 256-byte header; 0 when width or height is below 1). */
+uint64_t rt_denoise_history_bytes(int32_t width, int32_t height);
+/* Enqueues the temporal filter on hip_stream (NULL = default stream): no allocation, no synchronisation.  The workspace is rt_denoise's
+ * (rt_denoise_workspace_bytes).  params NULL = defaults.
+ * RT_ERR_INVALID_ARG: a required pointer NULL, the image width or height below 1, samples_per_pixel outside 1 … 65536, a parameter
+ * outside its range, workspace_bytes or history_bytes below their size functions, a history buffer not 16-byte aligned,
+ * history_next overlapping history_prev, an input, the workspace or d_out, d_out overlapping an input, the workspace or
+ * history_prev, or the workspace overlapping an input or history_prev.  RT_ERR_UNSUPPORTED: more than 2^24 pixels.  Every check
+ * comes before any HIP call. */
+rt_status rt_denoise_temporal(const float *d_fb_sum, const rt_aov_buffers *aov, const rt_camera_data *cam, const rt_denoise_params *params,
+                              const void *d_history_prev, void *d_history_next, uint64_t history_bytes,
+                              void *d_workspace, uint64_t workspace_bytes, float *d_out, void *hip_stream);
 
 /* Milliseconds of the most recent rt_render kernel of this scene (waits for it). */
 rt_status rt_last_kernel_ms(rt_scene *scene, float *ms);

@@ -1157,9 +1157,10 @@ void reservation(uint32_t total_work, uint64_t waves_total, uint32_t &chunk, uin
 }
 
 // samples [pass_first, pass_first + pass_count) of every pixel: work index = pixel * pass_count + slot, below the bound of the
-// kernels' 32-bit arithmetic
-rt_status set_pass(rtk::KParams &P, const rtaccel::PassPlan &passes, int pass, uint32_t num_pixels) {
-    P.pass_first = passes.first(pass);
+// kernels' 32-bit arithmetic.  A call for samples [sample_first, sample_first + spp) shifts every pass by sample_first (checked by
+// check_sample_range: below 2^30).
+rt_status set_pass(rtk::KParams &P, const rtaccel::PassPlan &passes, int pass, uint32_t num_pixels, int32_t sample_first) {
+    P.pass_first = sample_first + passes.first(pass);
     P.pass_count = passes.count(pass);
     P.total_work = num_pixels * (uint32_t)P.pass_count;
     if ((uint64_t)num_pixels * (uint64_t)P.pass_count >= (1ull << 31) - 4096 || !make_magic((uint32_t)P.pass_count, (uint64_t)P.total_work + 64, P.magic_count))
@@ -1167,14 +1168,22 @@ rt_status set_pass(rtk::KParams &P, const rtaccel::PassPlan &passes, int pass, u
     return RT_OK;
 }
 
+// rt_render_samples / rt_render_aov_samples: samples [sample_first, sample_first + spp) — the kernels carry sample indices as int32
+rt_status check_sample_range(const char *what, int32_t sample_first, int32_t spp) {
+    if (sample_first < 0) return fail(RT_ERR_INVALID_ARG, std::string(what) + ": sample_first is negative");
+    if ((int64_t)sample_first + (int64_t)spp > (int64_t)1 << 30)
+        return fail(RT_ERR_UNSUPPORTED, std::string(what) + ": sample_first + samples_per_pixel above 2^30");
+    return RT_OK;
+}
 
-// rt_render and rt_render_tile: whole rows of a shard, or a rectangle
+// rt_render, rt_render_tile and rt_render_samples: whole rows of a shard, or a rectangle; samples [sample_first, sample_first + spp)
 rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shard, const Tile *tile, float *d_fb_sum, void *hip_stream,
-                      int32_t sync, rt_timing *timing) {
+                      int32_t sync, rt_timing *timing, int32_t sample_first = 0) {
     // ---- 1. validate, fill P
     rtk::KParams P;
     rt_status st = fill_params(sc, cam, shard, P, tile);
     if (st != RT_OK) return st;
+    if ((st = check_sample_range("rt_render_samples", sample_first, P.spp)) != RT_OK) return st;
     if ((st = check_device(sc)) != RT_OK) return st;
     if (!d_fb_sum) return fail(RT_ERR_INVALID_ARG, "null framebuffer");
     if ((st = timing_check(timing)) != RT_OK) return st;
@@ -1292,7 +1301,7 @@ rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *s
         // samples [pass_first, pass_first + pass_count) of every pixel, traced in any order into the slab …
         const bool timed_pass = pass < kTimedPasses;
         if (timed_pass) HIP_TRY(hipEventRecord(sc->pass_events[4 * pass], stream));
-        if ((st = set_pass(P, passes, pass, num_pixels)) != RT_OK) return st;
+        if ((st = set_pass(P, passes, pass, num_pixels, sample_first)) != RT_OK) return st;
         P.queue = sc->queue + kQueueWork + pass;
         P.work_list = nullptr;
         reservation(P.total_work, waves_total, P.chunk, P.taper_shift);
@@ -1432,7 +1441,7 @@ rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *s
 // block, no per-pass events of rt_render: what the handle decides next, and what rt_last_timing reports, stay those of its
 // rt_render calls.
 rt_status aov_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shard, const Tile *tile, const rt_aov_buffers *buffers, void *hip_stream,
-                   int32_t sync, rt_timing *timing) {
+                   int32_t sync, rt_timing *timing, int32_t sample_first = 0) {
     // (the buffers first: a caller's mistake there is reported as such whatever else is wrong)
     if (!buffers || buffers->struct_bytes < 16u) return fail(RT_ERR_INVALID_ARG, "null AOV buffers (or struct_bytes below 16)");
     rt_aov_buffers b{};
@@ -1441,6 +1450,7 @@ rt_status aov_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shar
     rtk::KParams P;
     rt_status st = fill_params(sc, cam, shard, P, tile);
     if (st != RT_OK) return st;
+    if ((st = check_sample_range("rt_render_aov_samples", sample_first, P.spp)) != RT_OK) return st;
     if ((st = check_device(sc)) != RT_OK) return st;
     if ((st = timing_check(timing)) != RT_OK) return st;
     const rt_config &cfg = sc->cfg;
@@ -1493,7 +1503,7 @@ rt_status aov_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shar
     }
     for (int pass = 0; pass < passes; ++pass) {
         const bool timed_pass = pass < timed;
-        if ((st = set_pass(P, plan, pass, num_pixels)) != RT_OK) return st;
+        if ((st = set_pass(P, plan, pass, num_pixels, sample_first)) != RT_OK) return st;
         if (timed_pass) HIP_TRY(hipEventRecord(sc->aov_events[3 * pass], stream));
         if (prim) {
             launch_primary(sc, P, num_pixels, stream);
@@ -1551,7 +1561,12 @@ extern "C" {
 
 rt_status rt_render(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shard, float *d_fb_sum, void *hip_stream,
                     int32_t sync, rt_timing *timing) {
-    return render_impl(sc, cam, shard, nullptr, d_fb_sum, hip_stream, sync, timing);
+    return render_impl(sc, cam, shard, nullptr, d_fb_sum, hip_stream, sync, timing, 0);
+}
+
+rt_status rt_render_samples(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shard, int32_t sample_first, float *d_fb_sum,
+                            void *hip_stream, int32_t sync, rt_timing *timing) {
+    return render_impl(sc, cam, shard, nullptr, d_fb_sum, hip_stream, sync, timing, sample_first);
 }
 
 rt_status rt_render_tile(rt_scene *sc, const rt_camera_data *cam, int32_t tile_x0, int32_t tile_y0, int32_t tile_w, int32_t tile_h,
@@ -1568,7 +1583,12 @@ void rt_aov_buffers_init(rt_aov_buffers *b) {
 
 rt_status rt_render_aov(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shard, const rt_aov_buffers *buffers, void *hip_stream,
                         int32_t sync, rt_timing *timing) {
-    return aov_impl(sc, cam, shard, nullptr, buffers, hip_stream, sync, timing);
+    return aov_impl(sc, cam, shard, nullptr, buffers, hip_stream, sync, timing, 0);
+}
+
+rt_status rt_render_aov_samples(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shard, int32_t sample_first, const rt_aov_buffers *buffers,
+                                void *hip_stream, int32_t sync, rt_timing *timing) {
+    return aov_impl(sc, cam, shard, nullptr, buffers, hip_stream, sync, timing, sample_first);
 }
 
 rt_status rt_render_aov_tile(rt_scene *sc, const rt_camera_data *cam, int32_t tile_x0, int32_t tile_y0, int32_t tile_w, int32_t tile_h,

@@ -11,6 +11,17 @@
 //     dg            (d0, d1, d2, gz)    demodulation divisor and depth gradient: read by the pixel itself only
 // Launches: prepass (→ lv[0], nz, dg) · moments (lv[0] → lv[1] with var, gz into dg) · one step per iteration, the last of which
 // remodulates into d_out.  With iterations = 0 the prepass writes d_out itself.
+//
+// rt_denoise_temporal (SVGF's temporal half) runs the same kernels with one more between moments and the first step: denoise_temporal
+// reprojects each hit pixel into the history of the previous frame and replaces lv[1] in place with the accumulated colour and the
+// variance of the accumulated moments (or keeps the spatial one while the history is short).  The first step also writes its output
+// into the history (kFeedback), the colour the next frame reprojects.  The history buffer is a 256-byte header, then four planes of
+// one 16-byte record per pixel:
+//     colour   (L0, L1, L2, var)     iteration 0's output (the accumulated colour itself with 0 iterations)
+//     moments  (M1, M2, len, prim)   accumulated luminance moments, history length (0: sky), first_prim as its int32 bits
+//     position (X, 0)                mean first-hit point
+//     normal   (n, 0)                unit normal of the prepass
+// With an empty history every pixel is disoccluded, denoise_temporal writes back what moments wrote, and d_out is rt_denoise's.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -143,9 +154,10 @@ struct Sigmas {
 };
 
 // One à-trous pass at step s: 25 taps p + s*(dx, dy).  kFinal: remodulate into out (sky pixels copy fb) instead of writing lv_out.
-template <bool kFinal>
+// kFeedback: also write the result into the colour plane of the temporal history (rt_denoise_temporal's first iteration).
+template <bool kFinal, bool kFeedback = false>
 __global__ __launch_bounds__(256) void denoise_step(Image im, int32_t s, Sigmas sg, const float4 *lv_in, const float4 *nz, const float4 *dg,
-                                                    float4 *lv_out, const float *fb, float spp, float *out) {
+                                                    float4 *lv_out, const float *fb, float spp, float *out, float4 *feedback = nullptr) {
     int32_t x, y;
     if (!pixel_of(im, x, y)) return;
     const int64_t p = (int64_t)y * im.width + x;
@@ -190,6 +202,7 @@ __global__ __launch_bounds__(256) void denoise_step(Image im, int32_t s, Sigmas 
     }
     float4 r = vp;
     if (W != 0.0f) r = make_float4(S0 / W, S1 / W, S2 / W, SV / (W * W));
+    if (kFeedback) feedback[p] = r;
     if (kFinal) {
         const float4 d = dg[p];
         out[3 * p] = (r.x * d.x) * spp;
@@ -197,6 +210,146 @@ __global__ __launch_bounds__(256) void denoise_step(Image im, int32_t s, Sigmas 
         out[3 * p + 2] = (r.z * d.z) * spp;
     } else {
         lv_out[p] = r;
+    }
+}
+
+// ---- the temporal half (rt_denoise_temporal) ------------------------------------------------------------------------------------
+
+constexpr uint32_t kHistMagic = 0x31485452u;          // "RTH1"
+constexpr uint64_t kHistHeader = 256, kHistPlanes = 4;
+constexpr float kTau2 = 0.0025f, kMinWeight = 0.01f, kMaxLen = 32.0f, kMinAlpha = 0.2f, kMomentsLen = 4.0f, kMinNormalDot = 0.9f;
+
+struct History {            // the header: written by denoise_temporal's first lane, read by all of them
+    uint32_t magic;
+    int32_t width, height;
+    uint32_t zero;
+    rt_camera_data cam;     // the camera the history was made with
+    uint32_t zeros[(kHistHeader - 16 - sizeof(rt_camera_data)) / 4];
+};
+static_assert(sizeof(History) == kHistHeader, "history header");
+
+// plane k of a history buffer (16-byte aligned: checked by the caller)
+__host__ __device__ __forceinline__ float4 *plane(void *h, uint64_t pixels, int k) {
+    return (float4 *)((char *)h + kHistHeader) + (uint64_t)k * pixels;
+}
+
+__device__ __forceinline__ float dot3(const float a[3], const float b[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+
+// Per pixel, after moments: reproject into the history of `prev`, accumulate (L, M1, M2) and write (L, var) back into lv in place;
+// write the pixel's history records into `next`.  out != nullptr (iterations = 0): remodulate straight into it, and the colour plane
+// of the history gets (L, var) here instead of from the first step.
+__global__ __launch_bounds__(256) void denoise_temporal(Image im, rt_camera_data cam, const int32_t *first_prim, const History *prev, History *next,
+                                                        float4 *lv, const float4 *nz, const float4 *dg, const float *fb, float spp, float *out) {
+    const uint64_t pixels = (uint64_t)im.width * (uint64_t)im.height;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        History h;
+        memset(&h, 0, sizeof(h));
+        h.magic = kHistMagic;
+        h.width = im.width;
+        h.height = im.height;
+        h.cam = cam;
+        *next = h;
+    }
+    int32_t x, y;
+    if (!pixel_of(im, x, y)) return;
+    const int64_t p = (int64_t)y * im.width + x;
+    float4 *const colour = plane(next, pixels, 0);
+    const float4 np = nz[p];
+    if (is_sky(np)) {
+        const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        colour[p] = zero;
+        plane(next, pixels, 1)[p] = zero;
+        plane(next, pixels, 2)[p] = zero;
+        plane(next, pixels, 3)[p] = zero;
+        if (out) copy3(out, fb, p);
+        return;
+    }
+    const float4 cur = lv[p];
+    const int32_t prim = first_prim[p];
+    const float Lc[3] = {cur.x, cur.y, cur.z};
+    const float m1 = lum(cur.x, cur.y, cur.z);
+    // the mean first-hit point along the pixel-centre ray
+    const float O[3] = {cam.origin.e[0], cam.origin.e[1], cam.origin.e[2]};
+    float X[3], OX[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float pc = (cam.pixel00_loc.e[k] + (float)x * cam.pixel_delta_u.e[k]) + (float)y * cam.pixel_delta_v.e[k];
+        X[k] = O[k] + np.w * (pc - O[k]);
+        OX[k] = X[k] - O[k];
+    }
+    const float reach2 = kTau2 * dot3(OX, OX);
+    float L[3] = {Lc[0], Lc[1], Lc[2]}, M1 = m1, M2 = m1 * m1, len = 1.0f;
+    if (prev && prev->magic == kHistMagic && prev->width == im.width && prev->height == im.height) {
+        // projection through the old viewport plane (normal du' x dv'), pixel units with integers at pixel centres
+        const rt_camera_data &c = prev->cam;
+        const float du[3] = {c.pixel_delta_u.e[0], c.pixel_delta_u.e[1], c.pixel_delta_u.e[2]};
+        const float dv[3] = {c.pixel_delta_v.e[0], c.pixel_delta_v.e[1], c.pixel_delta_v.e[2]};
+        const float N[3] = {du[1] * dv[2] - du[2] * dv[1], du[2] * dv[0] - du[0] * dv[2], du[0] * dv[1] - du[1] * dv[0]};
+        float E[3], D[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            E[k] = c.pixel00_loc.e[k] - c.origin.e[k];
+            D[k] = X[k] - c.origin.e[k];
+        }
+        const float t = dot3(E, N) / dot3(D, N);
+        if (t > 0.0f && t < __builtin_inff()) {
+            float R[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) R[k] = t * D[k] - E[k];
+            const float u = dot3(R, du) / dot3(du, du), v = dot3(R, dv) / dot3(dv, dv);
+            if (u > -1.0f && u < (float)im.width && v > -1.0f && v < (float)im.height) {
+                const float fu = floorf(u), fv = floorf(v);
+                const int32_t x0 = (int32_t)fu, y0 = (int32_t)fv;
+                const float fx = u - fu, fy = v - fv;
+                const float4 *h_colour = plane((void *)prev, pixels, 0), *h_moments = plane((void *)prev, pixels, 1);
+                const float4 *h_pos = plane((void *)prev, pixels, 2), *h_normal = plane((void *)prev, pixels, 3);
+                float W = 0.0f, S0 = 0.0f, S1 = 0.0f, S2 = 0.0f, SM1 = 0.0f, SM2 = 0.0f, SN = 0.0f;
+#pragma unroll
+                for (int tap = 0; tap < 4; ++tap) {
+                    const int32_t qx = x0 + (tap & 1), qy = y0 + (tap >> 1);
+                    if (qx < 0 || qx >= im.width || qy < 0 || qy >= im.height) continue;
+                    const int64_t q = (int64_t)qy * im.width + qx;
+                    const float4 mq = h_moments[q];
+                    if (!(mq.z > 0.0f) || __float_as_int(mq.w) != prim) continue;
+                    const float4 nq = h_normal[q];
+                    if (!((np.x * nq.x + np.y * nq.y) + np.z * nq.z >= kMinNormalDot)) continue;
+                    const float4 xq = h_pos[q];
+                    const float e[3] = {xq.x - X[0], xq.y - X[1], xq.z - X[2]};
+                    if (!(dot3(e, e) <= reach2)) continue;
+                    const float w = ((tap & 1) ? fx : 1.0f - fx) * ((tap >> 1) ? fy : 1.0f - fy);
+                    const float4 cq = h_colour[q];
+                    W += w;
+                    S0 += w * cq.x;
+                    S1 += w * cq.y;
+                    S2 += w * cq.z;
+                    SM1 += w * mq.x;
+                    SM2 += w * mq.y;
+                    SN += w * mq.z;
+                }
+                if (W >= kMinWeight) {
+                    len = fminf(SN / W + 1.0f, kMaxLen);
+                    const float a = fmaxf(kMinAlpha, 1.0f / len), b = 1.0f - a;
+                    L[0] = b * (S0 / W) + a * Lc[0];
+                    L[1] = b * (S1 / W) + a * Lc[1];
+                    L[2] = b * (S2 / W) + a * Lc[2];
+                    M1 = b * (SM1 / W) + a * m1;
+                    M2 = b * (SM2 / W) + a * (m1 * m1);
+                }
+            }
+        }
+    }
+    const float var = len >= kMomentsLen ? fmaxf(0.0f, M2 - M1 * M1) : cur.w;
+    const float4 r = make_float4(L[0], L[1], L[2], var);
+    lv[p] = r;
+    plane(next, pixels, 1)[p] = make_float4(M1, M2, len, __int_as_float(prim));
+    plane(next, pixels, 2)[p] = make_float4(X[0], X[1], X[2], 0.0f);
+    plane(next, pixels, 3)[p] = make_float4(np.x, np.y, np.z, 0.0f);
+    if (out) {
+        colour[p] = r;
+        const float4 d = dg[p];
+        out[3 * p] = (L[0] * d.x) * spp;
+        out[3 * p + 1] = (L[1] * d.y) * spp;
+        out[3 * p + 2] = (L[2] * d.z) * spp;
     }
 }
 
@@ -209,6 +362,69 @@ bool overlap(const void *a, uint64_t na, const void *b, uint64_t nb) {
 rt_status fail(rt_status st, const std::string &msg) {
     rt_internal_set_error(msg);
     return st;
+}
+
+// params (NULL = defaults) into prm, checked; errors start with `who`
+rt_status read_params(const char *who, const rt_denoise_params *params, rt_denoise_params &prm) {
+    const std::string w(who);
+    rt_denoise_params_init(&prm);
+    if (params) {
+        if (params->struct_bytes < 8) return fail(RT_ERR_INVALID_ARG, w + ": rt_denoise_params.struct_bytes is not set (rt_denoise_params_init)");
+        memcpy(&prm, params, params->struct_bytes < sizeof(prm) ? params->struct_bytes : sizeof(prm));
+    }
+    if (prm.iterations < 0 || prm.iterations > 8) return fail(RT_ERR_INVALID_ARG, w + ": iterations outside 0 … 8");
+    if (!(prm.sigma_depth > 0.0f) || !isfinite(prm.sigma_depth)) return fail(RT_ERR_INVALID_ARG, w + ": sigma_depth must be positive and finite");
+    if (!(prm.sigma_luminance > 0.0f) || !isfinite(prm.sigma_luminance))
+        return fail(RT_ERR_INVALID_ARG, w + ": sigma_luminance must be positive and finite");
+    if (prm.normal_squarings < 0 || prm.normal_squarings > 10) return fail(RT_ERR_INVALID_ARG, w + ": normal_squarings outside 0 … 10");
+    return RT_OK;
+}
+
+// The launch shape of a width x height image (one lane per pixel, kTileW x kTileH pixels per workgroup) and the workspace planes
+struct Launch {
+    Image im;
+    dim3 grid, block;
+    float4 *lv[2], *nz, *dg;
+    Launch(int32_t width, int32_t height, void *workspace) {
+        const uint64_t pixels = (uint64_t)width * (uint64_t)height;
+        float4 *base = (float4 *)(((uintptr_t)workspace + kAlign - 1) & ~(uintptr_t)(kAlign - 1));
+        lv[0] = base;
+        lv[1] = base + pixels;
+        nz = base + 2 * pixels;
+        dg = base + 3 * pixels;
+        im.width = width;
+        im.height = height;
+        im.tiles_x = (width + kTileW - 1) / kTileW;
+        grid = dim3((uint32_t)im.tiles_x * (uint32_t)((height + kTileH - 1) / kTileH));
+        block = dim3(kTileW * kTileH);
+    }
+};
+
+rt_status launched(const char *what) {
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(RT_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
+    return RT_OK;
+}
+
+// The iterations: lv[1] → lv[0] → lv[1] …, the last one remodulating into out; feedback != nullptr: iteration 0 also writes it
+rt_status enqueue_steps(const Launch &l, const rt_denoise_params &prm, const float *fb, float spp, float *out, float4 *feedback, hipStream_t stream) {
+    const Sigmas sg = {prm.sigma_depth, prm.sigma_luminance, prm.normal_squarings};
+    for (int32_t i = 0; i < prm.iterations; ++i) {
+        const float4 *src = l.lv[(i + 1) & 1];
+        float4 *dst = l.lv[i & 1];
+        const bool last = i + 1 == prm.iterations;
+        if (i == 0 && feedback) {
+            if (!last) hipLaunchKernelGGL((denoise_step<false, true>), l.grid, l.block, 0, stream, l.im, 1 << i, sg, src, l.nz, l.dg, dst, fb, spp, out, feedback);
+            else hipLaunchKernelGGL((denoise_step<true, true>), l.grid, l.block, 0, stream, l.im, 1 << i, sg, src, l.nz, l.dg, dst, fb, spp, out, feedback);
+        } else if (!last) {
+            hipLaunchKernelGGL(denoise_step<false>, l.grid, l.block, 0, stream, l.im, 1 << i, sg, src, l.nz, l.dg, dst, fb, spp, out, nullptr);
+        } else {
+            hipLaunchKernelGGL(denoise_step<true>, l.grid, l.block, 0, stream, l.im, 1 << i, sg, src, l.nz, l.dg, dst, fb, spp, out, nullptr);
+        }
+        rt_status st;
+        if ((st = launched("denoise_step")) != RT_OK) return st;
+    }
+    return RT_OK;
 }
 
 }  // namespace rtdn
@@ -244,16 +460,8 @@ rt_status rt_denoise(const float *d_fb_sum, const rt_aov_buffers *aov, int32_t w
     if (samples_per_pixel < 1 || samples_per_pixel > 65536)
         return fail(RT_ERR_INVALID_ARG, "rt_denoise: samples_per_pixel outside 1 … 65536");
     rt_denoise_params prm;
-    rt_denoise_params_init(&prm);
-    if (params) {
-        if (params->struct_bytes < 8) return fail(RT_ERR_INVALID_ARG, "rt_denoise: rt_denoise_params.struct_bytes is not set (rt_denoise_params_init)");
-        memcpy(&prm, params, params->struct_bytes < sizeof(prm) ? params->struct_bytes : sizeof(prm));
-    }
-    if (prm.iterations < 0 || prm.iterations > 8) return fail(RT_ERR_INVALID_ARG, "rt_denoise: iterations outside 0 … 8");
-    if (!(prm.sigma_depth > 0.0f) || !isfinite(prm.sigma_depth)) return fail(RT_ERR_INVALID_ARG, "rt_denoise: sigma_depth must be positive and finite");
-    if (!(prm.sigma_luminance > 0.0f) || !isfinite(prm.sigma_luminance))
-        return fail(RT_ERR_INVALID_ARG, "rt_denoise: sigma_luminance must be positive and finite");
-    if (prm.normal_squarings < 0 || prm.normal_squarings > 10) return fail(RT_ERR_INVALID_ARG, "rt_denoise: normal_squarings outside 0 … 10");
+    rt_status st = rtdn::read_params("rt_denoise", params, prm);
+    if (st != RT_OK) return st;
     const uint64_t pixels = (uint64_t)width * (uint64_t)height;
     if (pixels > (1ull << 24)) return fail(RT_ERR_UNSUPPORTED, "rt_denoise: more than 2^24 pixels");
     const uint64_t need = rt_denoise_workspace_bytes(width, height);
@@ -269,37 +477,82 @@ rt_status rt_denoise(const float *d_fb_sum, const rt_aov_buffers *aov, int32_t w
 
     // ---- enqueue -------------------------------------------------------------------------------------------------------------
     const hipStream_t stream = (hipStream_t)hip_stream;
-    float4 *base = (float4 *)(((uintptr_t)d_workspace + rtdn::kAlign - 1) & ~(uintptr_t)(rtdn::kAlign - 1));
-    float4 *lv[2] = {base, base + pixels};
-    float4 *nz = base + 2 * pixels, *dg = base + 3 * pixels;
-    rtdn::Image im;
-    im.width = width;
-    im.height = height;
-    im.tiles_x = (width + rtdn::kTileW - 1) / rtdn::kTileW;
-    const uint32_t blocks = (uint32_t)im.tiles_x * (uint32_t)((height + rtdn::kTileH - 1) / rtdn::kTileH);
+    const rtdn::Launch l(width, height, d_workspace);
     const rtdn::Inputs in = {d_fb_sum, b.albedo_sum, b.normal_sum, b.depth_sum, b.hit_count};
     const float inv = (float)(1.0 / (double)samples_per_pixel);
     const float spp = (float)samples_per_pixel;
-    const dim3 grid(blocks), block(rtdn::kTileW * rtdn::kTileH);
-    auto launched = [](const char *what) -> rt_status {
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(RT_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e));
-        return RT_OK;
-    };
-    rt_status st;
-    hipLaunchKernelGGL(rtdn::denoise_prepass, grid, block, 0, stream, im, in, inv, spp, lv[0], nz, dg, prm.iterations == 0 ? d_out : nullptr);
+    using rtdn::launched;
+    hipLaunchKernelGGL(rtdn::denoise_prepass, l.grid, l.block, 0, stream, l.im, in, inv, spp, l.lv[0], l.nz, l.dg, prm.iterations == 0 ? d_out : nullptr);
     if ((st = launched("denoise_prepass")) != RT_OK || prm.iterations == 0) return st;
-    hipLaunchKernelGGL(rtdn::denoise_moments, grid, block, 0, stream, im, lv[0], nz, dg, lv[1]);
+    hipLaunchKernelGGL(rtdn::denoise_moments, l.grid, l.block, 0, stream, l.im, l.lv[0], l.nz, l.dg, l.lv[1]);
     if ((st = launched("denoise_moments")) != RT_OK) return st;
-    const rtdn::Sigmas sg = {prm.sigma_depth, prm.sigma_luminance, prm.normal_squarings};
-    for (int32_t i = 0; i < prm.iterations; ++i) {
-        const float4 *src = lv[(i + 1) & 1];
-        float4 *dst = lv[i & 1];
-        if (i + 1 < prm.iterations) hipLaunchKernelGGL(rtdn::denoise_step<false>, grid, block, 0, stream, im, 1 << i, sg, src, nz, dg, dst, d_fb_sum, spp, d_out);
-        else hipLaunchKernelGGL(rtdn::denoise_step<true>, grid, block, 0, stream, im, 1 << i, sg, src, nz, dg, dst, d_fb_sum, spp, d_out);
-        if ((st = launched("denoise_step")) != RT_OK) return st;
+    return rtdn::enqueue_steps(l, prm, d_fb_sum, spp, d_out, nullptr, stream);
+}
+
+uint64_t rt_denoise_history_bytes(int32_t width, int32_t height) {
+    if (width < 1 || height < 1) return 0;
+    return (uint64_t)width * (uint64_t)height * rtdn::kHistPlanes * 16 + rtdn::kHistHeader;
+}
+
+rt_status rt_denoise_temporal(const float *d_fb_sum, const rt_aov_buffers *aov, const rt_camera_data *cam, const rt_denoise_params *params,
+                              const void *d_history_prev, void *d_history_next, uint64_t history_bytes, void *d_workspace, uint64_t workspace_bytes,
+                              float *d_out, void *hip_stream) {
+    using rtdn::fail;
+    using rtdn::overlap;
+    if (!d_fb_sum || !aov || !cam || !d_history_next || !d_workspace || !d_out) return fail(RT_ERR_INVALID_ARG, "rt_denoise_temporal: null argument");
+    rt_aov_buffers b;
+    rt_aov_buffers_init(&b);
+    const uint32_t ab = aov->struct_bytes < sizeof(b) ? aov->struct_bytes : (uint32_t)sizeof(b);
+    memcpy(&b, aov, ab);
+    if (ab < offsetof(rt_aov_buffers, first_prim) + sizeof(b.first_prim) || !b.albedo_sum || !b.normal_sum || !b.depth_sum || !b.hit_count ||
+        !b.first_prim)
+        return fail(RT_ERR_INVALID_ARG, "rt_denoise_temporal: albedo_sum, normal_sum, depth_sum, hit_count and first_prim are required");
+    const int32_t width = cam->image_width, height = cam->image_height, samples_per_pixel = cam->samples_per_pixel;
+    if (width < 1 || height < 1) return fail(RT_ERR_INVALID_ARG, "rt_denoise_temporal: image width and height must be at least 1");
+    if (samples_per_pixel < 1 || samples_per_pixel > 65536)
+        return fail(RT_ERR_INVALID_ARG, "rt_denoise_temporal: samples_per_pixel outside 1 … 65536");
+    rt_denoise_params prm;
+    rt_status st = rtdn::read_params("rt_denoise_temporal", params, prm);
+    if (st != RT_OK) return st;
+    const uint64_t pixels = (uint64_t)width * (uint64_t)height;
+    if (pixels > (1ull << 24)) return fail(RT_ERR_UNSUPPORTED, "rt_denoise_temporal: more than 2^24 pixels");
+    const uint64_t need = rt_denoise_workspace_bytes(width, height), hist = rt_denoise_history_bytes(width, height);
+    if (workspace_bytes < need)
+        return fail(RT_ERR_INVALID_ARG, "rt_denoise_temporal: workspace_bytes below rt_denoise_workspace_bytes (" + std::to_string(need) + ")");
+    if (history_bytes < hist)
+        return fail(RT_ERR_INVALID_ARG, "rt_denoise_temporal: history_bytes below rt_denoise_history_bytes (" + std::to_string(hist) + ")");
+    if (((uintptr_t)d_history_prev | (uintptr_t)d_history_next) & 15u)
+        return fail(RT_ERR_INVALID_ARG, "rt_denoise_temporal: a history buffer is not 16-byte aligned");
+    const struct { const void *ptr; uint64_t bytes; } inputs[] = {{d_fb_sum, 12 * pixels}, {b.albedo_sum, 12 * pixels}, {b.normal_sum, 12 * pixels},
+                                                                   {b.depth_sum, 4 * pixels}, {b.hit_count, 4 * pixels}, {b.first_prim, 4 * pixels}};
+    const uint64_t prev_bytes = d_history_prev ? hist : 0;
+    for (const auto &in : inputs) {
+        if (overlap(d_history_next, hist, in.ptr, in.bytes)) return fail(RT_ERR_INVALID_ARG, "rt_denoise_temporal: history_next overlaps an input");
+        if (overlap(d_out, 12 * pixels, in.ptr, in.bytes)) return fail(RT_ERR_INVALID_ARG, "rt_denoise_temporal: d_out overlaps an input");
+        if (overlap(d_workspace, need, in.ptr, in.bytes)) return fail(RT_ERR_INVALID_ARG, "rt_denoise_temporal: the workspace overlaps an input");
     }
-    return RT_OK;
+    if (overlap(d_history_next, hist, d_history_prev, prev_bytes)) return fail(RT_ERR_INVALID_ARG, "rt_denoise_temporal: history_next overlaps history_prev");
+    if (overlap(d_history_next, hist, d_workspace, need)) return fail(RT_ERR_INVALID_ARG, "rt_denoise_temporal: history_next overlaps the workspace");
+    if (overlap(d_history_next, hist, d_out, 12 * pixels)) return fail(RT_ERR_INVALID_ARG, "rt_denoise_temporal: history_next overlaps d_out");
+    if (overlap(d_out, 12 * pixels, d_workspace, need)) return fail(RT_ERR_INVALID_ARG, "rt_denoise_temporal: d_out overlaps the workspace");
+    if (overlap(d_out, 12 * pixels, d_history_prev, prev_bytes)) return fail(RT_ERR_INVALID_ARG, "rt_denoise_temporal: d_out overlaps history_prev");
+    if (overlap(d_workspace, need, d_history_prev, prev_bytes)) return fail(RT_ERR_INVALID_ARG, "rt_denoise_temporal: the workspace overlaps history_prev");
+
+    // ---- enqueue: prepass · moments · temporal · the iterations, the first of which feeds the history ----------------------------
+    const hipStream_t stream = (hipStream_t)hip_stream;
+    const rtdn::Launch l(width, height, d_workspace);
+    const rtdn::Inputs in = {d_fb_sum, b.albedo_sum, b.normal_sum, b.depth_sum, b.hit_count};
+    const float inv = (float)(1.0 / (double)samples_per_pixel);
+    const float spp = (float)samples_per_pixel;
+    using rtdn::launched;
+    hipLaunchKernelGGL(rtdn::denoise_prepass, l.grid, l.block, 0, stream, l.im, in, inv, spp, l.lv[0], l.nz, l.dg, nullptr);
+    if ((st = launched("denoise_prepass")) != RT_OK) return st;
+    hipLaunchKernelGGL(rtdn::denoise_moments, l.grid, l.block, 0, stream, l.im, l.lv[0], l.nz, l.dg, l.lv[1]);
+    if ((st = launched("denoise_moments")) != RT_OK) return st;
+    hipLaunchKernelGGL(rtdn::denoise_temporal, l.grid, l.block, 0, stream, l.im, *cam, (const int32_t *)b.first_prim, (const rtdn::History *)d_history_prev,
+                       (rtdn::History *)d_history_next, l.lv[1], l.nz, l.dg, d_fb_sum, spp, prm.iterations == 0 ? d_out : nullptr);
+    if ((st = launched("denoise_temporal")) != RT_OK || prm.iterations == 0) return st;
+    return rtdn::enqueue_steps(l, prm, d_fb_sum, spp, d_out, rtdn::plane(d_history_next, pixels, 0), stream);
 }
 
 }  // extern "C"

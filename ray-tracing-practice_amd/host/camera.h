@@ -120,8 +120,9 @@ void orbit_pose(const SceneParams &p, int frame, Vec3 &eye, Vec3 &target);
 // "n \t ms \t W*H*sqrt_spp^2".  The scene must already be bound.  aov (rtp_main --gpu --aov): each frame's first-hit AOVs
 // (rt_render_aov) go to "<frame file>.aov" as well (write_aov_file).  denoise (rtp_main --gpu --denoise): each frame is also
 // filtered by rt_denoise, guided by its AOVs, and written through a BinarySaver with the frame's own divisor to
-// "<frame file>.denoised".  Both extras run outside the frame's timed span.
-void gpu_render(const SceneParams &params, bool aov = false, bool denoise = false);
+// "<frame file>.denoised".  temporal (rtp_main --gpu --denoise-temporal): that file comes from rt_denoise_temporal instead, with the
+// history carried from frame to frame (frame 0 starts without one).  The extras run outside the frame's timed span.
+void gpu_render(const SceneParams &params, bool aov = false, bool denoise = false, bool temporal = false);
 
 // The .aov file of a frame: int32 width, height, spp, then per pixel in row order 8 float32 — albedo_sum / spp (3),
 // normal_sum / spp (3), depth_sum / hit_count (0 where no sample hit) and hit_count / spp, each one float32 division.

@@ -29,11 +29,17 @@ int main(int argc, char *argv[]) {
 
     const rt_scene_desc desc = host.desc();
     // extension: `--gpu --aov` also writes each frame's first-hit AOVs to "<frame file>.aov", and `--gpu --denoise` the frame filtered
-    // by rt_denoise to "<frame file>.denoised" (frame-after-frame driver only)
-    bool aov = false, denoise = false;
+    // by rt_denoise to "<frame file>.denoised"; `--gpu --denoise-temporal` writes that file through rt_denoise_temporal instead, the
+    // history carried from frame to frame (frame-after-frame driver only)
+    bool aov = false, denoise = false, temporal = false;
     for (int a = 2; a < argc; ++a) {
         if (std::string(argv[a]) == "--aov") aov = true;
         if (std::string(argv[a]) == "--denoise") denoise = true;
+        if (std::string(argv[a]) == "--denoise-temporal") temporal = true;
+    }
+    if (denoise && temporal) {
+        std::cerr << "rtp_main: --denoise and --denoise-temporal both write <frame>.denoised: choose one\n";
+        return 2;
     }
     // extension: `--gpu --devices N` (or RTP_DEVICES=N) renders the animation with the pipelined
     // multi-GPU driver; the default is the reference's frame-after-frame loop.
@@ -41,11 +47,11 @@ int main(int argc, char *argv[]) {
     if (const char *env = getenv("RTP_DEVICES")) devices = atoi(env);
     for (int a = 2; a + 1 < argc; ++a)
         if (std::string(argv[a]) == "--devices") devices = atoi(argv[a + 1]);
-    if (aov || denoise) {
+    if (aov || denoise || temporal) {
         for (int a = 2; a < argc; ++a)
             if (std::string(argv[a]) == "--devices" || std::string(argv[a]) == "--shard") devices = 1;
         if (devices > 0) {
-            std::cerr << "rtp_main: " << (aov ? "--aov" : "--denoise")
+            std::cerr << "rtp_main: " << (aov ? "--aov" : denoise ? "--denoise" : "--denoise-temporal")
                       << " renders frame after frame on one GPU: it cannot be combined with --devices, --shard or RTP_DEVICES\n";
             return 2;
         }
@@ -63,7 +69,7 @@ int main(int argc, char *argv[]) {
     rt_scene *scene = nullptr;
     RTP_CHECK(rt_scene_create(&desc, &scene));
     rtp::bind_scene(scene);
-    rtp::gpu_render(params, aov, denoise);
+    rtp::gpu_render(params, aov, denoise, temporal);
     RTP_CHECK(rt_scene_destroy(scene));
     return 0;
 }

@@ -75,7 +75,7 @@ std::string frame_filename(const std::string &pattern, int n) {
     return out;
 }
 
-void gpu_render(const SceneParams &params, bool aov, bool denoise) {
+void gpu_render(const SceneParams &params, bool aov, bool denoise, bool temporal) {
     float *d_fb = nullptr;
     const size_t num_pixels = static_cast<size_t>(params.width) * params.height;
     RTP_CHECK(rt_device_alloc(num_pixels * 3 * sizeof(float), reinterpret_cast<void **>(&d_fb)));
@@ -84,7 +84,7 @@ void gpu_render(const SceneParams &params, bool aov, bool denoise) {
     rt_aov_buffers_init(&aov_bufs);
     std::vector<float> h_albedo, h_normal, h_depth;
     std::vector<uint32_t> h_hits;
-    if (aov || denoise) {
+    if (aov || denoise || temporal) {
         RTP_CHECK(rt_device_alloc(num_pixels * 12, reinterpret_cast<void **>(&aov_bufs.albedo_sum)));
         RTP_CHECK(rt_device_alloc(num_pixels * 12, reinterpret_cast<void **>(&aov_bufs.normal_sum)));
         RTP_CHECK(rt_device_alloc(num_pixels * 4, reinterpret_cast<void **>(&aov_bufs.depth_sum)));
@@ -94,12 +94,20 @@ void gpu_render(const SceneParams &params, bool aov, bool denoise) {
         h_depth.resize(num_pixels);
         h_hits.resize(num_pixels);
     }
-    // --denoise: rt_denoise's workspace and output (the sum over samples, like d_fb)
+    // --denoise-temporal: first_prim as well, and two history buffers swapped after every frame
+    void *d_history[2] = {nullptr, nullptr};
+    const uint64_t history_bytes = temporal ? rt_denoise_history_bytes(params.width, params.height) : 0;
+    if (temporal) {
+        RTP_CHECK(rt_device_alloc(num_pixels * 4, reinterpret_cast<void **>(&aov_bufs.first_prim)));
+        RTP_CHECK(rt_device_alloc(history_bytes, &d_history[0]));
+        RTP_CHECK(rt_device_alloc(history_bytes, &d_history[1]));
+    }
+    // --denoise / --denoise-temporal: the filter's workspace and output (the sum over samples, like d_fb)
     void *d_workspace = nullptr;
     float *d_denoised = nullptr;
-    const uint64_t workspace_bytes = denoise ? rt_denoise_workspace_bytes(params.width, params.height) : 0;
+    const uint64_t workspace_bytes = denoise || temporal ? rt_denoise_workspace_bytes(params.width, params.height) : 0;
     std::vector<float> h_denoised;
-    if (denoise) {
+    if (denoise || temporal) {
         RTP_CHECK(rt_device_alloc(workspace_bytes, &d_workspace));
         RTP_CHECK(rt_device_alloc(num_pixels * 3 * sizeof(float), reinterpret_cast<void **>(&d_denoised)));
         h_denoised.resize(num_pixels * 3);
@@ -124,7 +132,7 @@ void gpu_render(const SceneParams &params, bool aov, bool denoise) {
         const float ms = std::chrono::duration<float, std::milli>(t1 - t0).count();
         const long long total_rays = static_cast<long long>(params.width) * params.height * params.sqrt_spp * params.sqrt_spp;
         std::cout << n << "\t" << ms << "\t" << total_rays << "\n";
-        if (aov || denoise) {          // (outside the frame's timed span: the reference has no such output)
+        if (aov || denoise || temporal) {          // (outside the frame's timed span: the reference has no such output)
             const rt_camera_data cam = camera.build_camera_data();
             RTP_CHECK(rt_render_aov(bound_scene(), &cam, nullptr, &aov_bufs, nullptr, 1, nullptr));
             if (aov) {
@@ -138,9 +146,13 @@ void gpu_render(const SceneParams &params, bool aov, bool denoise) {
                     std::exit(99);
                 }
             }
-            if (denoise) {       // the frame's own saver code and divisor, into "<frame file>.denoised"
-                RTP_CHECK(rt_denoise(d_fb, &aov_bufs, params.width, params.height, cam.samples_per_pixel, nullptr, d_workspace, workspace_bytes,
-                                     d_denoised, nullptr));
+            if (denoise || temporal) {       // the frame's own saver code and divisor, into "<frame file>.denoised"
+                if (denoise)
+                    RTP_CHECK(rt_denoise(d_fb, &aov_bufs, params.width, params.height, cam.samples_per_pixel, nullptr, d_workspace, workspace_bytes,
+                                         d_denoised, nullptr));
+                else       // frame n reads the history frame n - 1 wrote (frame 0: none)
+                    RTP_CHECK(rt_denoise_temporal(d_fb, &aov_bufs, &cam, nullptr, n == 0 ? nullptr : d_history[(n + 1) & 1], d_history[n & 1],
+                                                  history_bytes, d_workspace, workspace_bytes, d_denoised, nullptr));
                 RTP_CHECK(rt_copy_to_host(h_denoised.data(), d_denoised, num_pixels * 3 * sizeof(float)));
                 BinarySaver out(params.sqrt_spp, filename + ".denoised");
                 out.set_format(params.width, params.height);
@@ -153,6 +165,9 @@ void gpu_render(const SceneParams &params, bool aov, bool denoise) {
     rt_device_free(aov_bufs.normal_sum);
     rt_device_free(aov_bufs.depth_sum);
     rt_device_free(aov_bufs.hit_count);
+    rt_device_free(aov_bufs.first_prim);
+    rt_device_free(d_history[0]);
+    rt_device_free(d_history[1]);
     rt_device_free(d_workspace);
     rt_device_free(d_denoised);
 }

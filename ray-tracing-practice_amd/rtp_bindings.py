@@ -148,6 +148,7 @@ RTP_AMD_SYMBOLS = [
     "rt_context_create", "rt_context_destroy", "rt_context_num_devices", "rt_context_transport", "rt_context_scene_create",
     "rt_render_sharded", "rt_gather", "rt_aov_buffers_init", "rt_render_aov", "rt_render_aov_tile",
     "rt_denoise_params_init", "rt_denoise_workspace_bytes", "rt_denoise",
+    "rt_render_samples", "rt_render_aov_samples", "rt_denoise_history_bytes", "rt_denoise_temporal",
 ]
 
 _host = None
@@ -226,6 +227,15 @@ def amd_lib():
             lib.rt_denoise_workspace_bytes.restype = C.c_uint64
             lib.rt_denoise.argtypes = [C.c_void_p, C.POINTER(AovBuffers), C.c_int32, C.c_int32, C.c_int32, C.POINTER(DenoiseParams),
                                        C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        if hasattr(lib, "rt_denoise_temporal"):
+            lib.rt_render_samples.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(Shard), C.c_int32, C.c_void_p, C.c_void_p,
+                                              C.c_int32, C.POINTER(Timing)]
+            lib.rt_render_aov_samples.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(Shard), C.c_int32, C.POINTER(AovBuffers),
+                                                  C.c_void_p, C.c_int32, C.POINTER(Timing)]
+            lib.rt_denoise_history_bytes.argtypes = [C.c_int32, C.c_int32]
+            lib.rt_denoise_history_bytes.restype = C.c_uint64
+            lib.rt_denoise_temporal.argtypes = [C.c_void_p, C.POINTER(AovBuffers), C.POINTER(CameraData), C.POINTER(DenoiseParams),
+                                                C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         lib.rt_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         lib.rt_last_timing.argtypes = [C.c_void_p, C.POINTER(Timing)]
         lib.rt_timing_init.argtypes = [C.POINTER(Timing)]
@@ -385,6 +395,27 @@ def denoise(d_fb, aov_ptrs, width, height, spp, d_out, stream=None, workspace=No
                           C.c_void_p(stream or 0)), "rt_denoise")
 
 
+def _aov_struct(aov_ptrs):
+    b = AovBuffers()
+    for key, field, _, _ in AOV_CHANNELS:
+        if aov_ptrs.get(key):
+            setattr(b, field, aov_ptrs[key])
+    return b
+
+
+def denoise_temporal(d_fb, aov_ptrs, cam, d_history_prev, d_history_next, history_bytes, d_out, workspace, stream=None, **params):
+    """rt_denoise_temporal on device addresses: d_fb (the beauty sums of cam), aov_ptrs {"albedo", "normal", "depth", "hits",
+    "prim"} → device address, d_history_prev (None: no history) and d_history_next (history_bytes each), d_out (3 floats per
+    pixel), workspace = (address, bytes) of at least rt_denoise_workspace_bytes.  Only enqueues on `stream` (None = default
+    stream).  params: rt_denoise_params fields."""
+    b = _aov_struct(aov_ptrs)
+    p = denoise_params(**params)
+    ws_ptr, ws_bytes = workspace
+    _check(amd_lib().rt_denoise_temporal(C.c_void_p(d_fb), C.byref(b), C.byref(cam), C.byref(p), C.c_void_p(d_history_prev or 0),
+                                         C.c_void_p(d_history_next), history_bytes, C.c_void_p(ws_ptr), ws_bytes, C.c_void_p(d_out),
+                                         C.c_void_p(stream or 0)), "rt_denoise_temporal")
+
+
 _hip_rt = None
 
 
@@ -436,6 +467,96 @@ def denoise_to_host(fb_sum, aov, spp, **params):
     return out
 
 
+def _upload(a):
+    """A fresh device buffer holding the host array a (rt_device_alloc: the caller frees it)."""
+    d = C.c_void_p()
+    _check(amd_lib().rt_device_alloc(a.nbytes or 4, C.byref(d)), "rt_device_alloc")
+    if a.nbytes and _hip().hipMemcpy(d, a.ctypes.data, a.nbytes, 1) != 0:       # hipMemcpyHostToDevice
+        amd_lib().rt_device_free(d)
+        raise RtError("hipMemcpy host to device failed")
+    return d
+
+
+class TemporalDenoiser:
+    """rt_denoise_temporal over the frames of an animation: owns the two history buffers and the workspace of a width x height
+    image on the device current at construction.  step_to_host() denoises one frame and keeps its history for the next one;
+    reset() forgets the history (a cut).  params: rt_denoise_params fields, the same for every frame."""
+
+    def __init__(self, width, height, **params):
+        lib = amd_lib()
+        self.width, self.height, self.params = width, height, dict(params)
+        denoise_params(**params)                              # (unknown fields fail here, not at the first frame)
+        self.history_bytes = lib.rt_denoise_history_bytes(width, height)
+        self.workspace_bytes = lib.rt_denoise_workspace_bytes(width, height)
+        if self.history_bytes == 0:
+            raise RtError(f"TemporalDenoiser: no image of {width} x {height}")
+        self._dev = []
+        try:
+            for n in (self.history_bytes, self.history_bytes, self.workspace_bytes):
+                d = C.c_void_p()
+                _check(lib.rt_device_alloc(n, C.byref(d)), "rt_device_alloc")
+                self._dev.append(d)
+        except Exception:
+            self.close()
+            raise
+        self._prev, self._next = self._dev[0].value, self._dev[1].value
+        self._have = False
+
+    def reset(self):
+        """The next frame starts without history."""
+        self._have = False
+
+    def step(self, d_fb, aov_ptrs, cam, d_out, stream=None):
+        """One frame on device addresses (denoise_temporal); only enqueues on `stream`."""
+        if (cam.image_width, cam.image_height) != (self.width, self.height):
+            raise RtError(f"TemporalDenoiser: a {cam.image_width} x {cam.image_height} frame for a {self.width} x {self.height} history")
+        denoise_temporal(d_fb, aov_ptrs, cam, self._prev if self._have else None, self._next, self.history_bytes, d_out,
+                         (self._dev[2].value, self.workspace_bytes), stream=stream, **self.params)
+        self._prev, self._next = self._next, self._prev
+        self._have = True
+
+    def step_to_host(self, fb_sum, aov, cam):
+        """One frame of host arrays: fb_sum (H, W, 3) float32 as DeviceScene.render_to_host returns it, aov the dict of
+        DeviceScene.render_aov_to_host (prim included), cam its camera.  Returns the (H, W, 3) float32 output, the sum over samples
+        like fb_sum.  Synchronous (default stream)."""
+        lib = amd_lib()
+        fb = np.ascontiguousarray(fb_sum, dtype=np.float32)
+        arrays = {"fb": fb}
+        for key, _, dtype, _ in AOV_CHANNELS:
+            arrays[key] = np.ascontiguousarray(aov[key], dtype=dtype)
+        dev = {}
+        try:
+            for key, a in arrays.items():
+                dev[key] = _upload(a)
+            d_out = C.c_void_p()
+            _check(lib.rt_device_alloc(fb.nbytes or 4, C.byref(d_out)), "rt_device_alloc")
+            dev["out"] = d_out
+            self.step(dev["fb"].value, {k: dev[k].value for k, _, _, _ in AOV_CHANNELS}, cam, d_out.value)
+            out = np.empty_like(fb)
+            _check(lib.rt_copy_to_host(out.ctypes.data, d_out, out.nbytes), "rt_copy_to_host")
+        finally:
+            for d in dev.values():
+                lib.rt_device_free(d)
+        return out
+
+    def history_to_host(self):
+        """The history the last step wrote (uint8 array of rt_denoise_history_bytes; the header's layout)."""
+        h = np.empty(self.history_bytes, np.uint8)
+        _check(amd_lib().rt_copy_to_host(h.ctypes.data, C.c_void_p(self._prev), h.nbytes), "rt_copy_to_host")
+        return h
+
+    def close(self):
+        for d in self._dev:
+            amd_lib().rt_device_free(d)
+        self._dev = []
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class DeviceScene:
     """rt_scene handle (device-resident repacked scene).
 
@@ -479,20 +600,35 @@ class DeviceScene:
         _check(amd_lib().rt_scene_get_config(self._h, C.byref(cfg)), "rt_scene_get_config")
         return cfg
 
-    def render_to_host(self, cam, shard=None):
+    def render_to_host(self, cam, shard=None, sample_first=0):
+        """The frame's sums as a (rows, width, 3) float32 array and the rt_timing; sample_first != 0: samples sample_first … of
+        every pixel (rt_render_samples through a fresh device buffer)."""
         lib = amd_lib()
         rows = lib.rt_shard_rows(cam.image_height, C.byref(shard) if shard else None)
         fb = np.empty((rows, cam.image_width, 3), dtype=np.float32)
         t = Timing()
+        if sample_first:
+            d = C.c_void_p()
+            _check(lib.rt_device_alloc(fb.nbytes or 12, C.byref(d)), "rt_device_alloc")
+            try:
+                t = self.render(cam, d.value, shard=shard, sample_first=sample_first)
+                _check(lib.rt_copy_to_host(fb.ctypes.data, d, fb.nbytes), "rt_copy_to_host")
+            finally:
+                lib.rt_device_free(d)
+            return fb, t
         self._apply_config()
         _check(lib.rt_render_to_host(self._h, C.byref(cam), C.byref(shard) if shard else None, fb.ctypes.data,
                                      C.byref(t)), "rt_render_to_host")
         return fb, t
 
-    def render(self, cam, d_fb_ptr, shard=None, stream=None, sync=True):
-        """d_fb_ptr: integer device address (e.g. torch tensor.data_ptr())."""
+    def render(self, cam, d_fb_ptr, shard=None, stream=None, sync=True, sample_first=0):
+        """d_fb_ptr: integer device address (e.g. torch tensor.data_ptr()).  sample_first != 0: rt_render_samples."""
         t = Timing()
         self._apply_config()
+        if sample_first:
+            _check(amd_lib().rt_render_samples(self._h, C.byref(cam), C.byref(shard) if shard else None, sample_first, C.c_void_p(d_fb_ptr),
+                                               C.c_void_p(stream or 0), 1 if sync else 0, C.byref(t)), "rt_render_samples")
+            return t
         _check(amd_lib().rt_render(self._h, C.byref(cam), C.byref(shard) if shard else None, C.c_void_p(d_fb_ptr),
                                    C.c_void_p(stream or 0), 1 if sync else 0, C.byref(t)), "rt_render")
         return t
@@ -512,23 +648,27 @@ class DeviceScene:
             lib.rt_device_free(d)
         return fb, t
 
-    def render_aov(self, cam, ptrs, shard=None, stream=None, sync=True):
-        """rt_render_aov.  ptrs: {"albedo", "normal", "depth", "hits", "prim"} → integer device address (missing / None: not
-        written).  Returns the rt_timing."""
-        b = AovBuffers()
-        for key, field, _, _ in AOV_CHANNELS:
-            if ptrs.get(key):
-                setattr(b, field, ptrs[key])
+    def render_aov(self, cam, ptrs, shard=None, stream=None, sync=True, sample_first=0):
+        """rt_render_aov (rt_render_aov_samples for sample_first != 0).  ptrs: {"albedo", "normal", "depth", "hits", "prim"} →
+        integer device address (missing / None: not written).  Returns the rt_timing."""
+        b = _aov_struct(ptrs)
         t = Timing()
         self._apply_config()
+        if sample_first:
+            _check(amd_lib().rt_render_aov_samples(self._h, C.byref(cam), C.byref(shard) if shard else None, sample_first, C.byref(b),
+                                                   C.c_void_p(stream or 0), 1 if sync else 0, C.byref(t)), "rt_render_aov_samples")
+            return t
         _check(amd_lib().rt_render_aov(self._h, C.byref(cam), C.byref(shard) if shard else None, C.byref(b), C.c_void_p(stream or 0),
                                        1 if sync else 0, C.byref(t)), "rt_render_aov")
         return t
 
-    def render_aov_to_host(self, cam, shard=None, tile=None):
+    def render_aov_to_host(self, cam, shard=None, tile=None, sample_first=0):
         """The AOVs of the frame, a shard of its rows or a tile (x0, y0, w, h) through fresh device buffers: ({"albedo": (rows, w, 3),
-        "normal": (rows, w, 3), "depth": (rows, w), "hits": (rows, w) uint32, "prim": (rows, w) int32}, rt_timing)."""
+        "normal": (rows, w, 3), "depth": (rows, w), "hits": (rows, w) uint32, "prim": (rows, w) int32}, rt_timing).  sample_first
+        != 0: samples sample_first … (rt_render_aov_samples; not for a tile)."""
         lib = amd_lib()
+        if tile is not None and sample_first:
+            raise RtError("render_aov_to_host: a tile has no sample_first (rt_render_aov_samples renders rows)")
         if tile is not None:
             x0, y0, w, rows = tile
         else:
@@ -546,6 +686,9 @@ class DeviceScene:
             self._apply_config()
             if tile is not None:
                 _check(lib.rt_render_aov_tile(self._h, C.byref(cam), x0, y0, w, rows, C.byref(b), C.c_void_p(0), 1, C.byref(t)), "rt_render_aov_tile")
+            elif sample_first:
+                _check(lib.rt_render_aov_samples(self._h, C.byref(cam), C.byref(shard) if shard else None, sample_first, C.byref(b), C.c_void_p(0),
+                                                 1, C.byref(t)), "rt_render_aov_samples")
             else:
                 _check(lib.rt_render_aov(self._h, C.byref(cam), C.byref(shard) if shard else None, C.byref(b), C.c_void_p(0), 1, C.byref(t)),
                        "rt_render_aov")
