@@ -478,6 +478,63 @@ rt_status rt_denoise_temporal(const float *d_fb_sum, const rt_aov_buffers *aov, 
                               const void *d_history_prev, void *d_history_next, uint64_t history_bytes,
                               void *d_workspace, uint64_t workspace_bytes, float *d_out, void *hip_stream);
 
+/* ---- adaptive sampling: per pixel, samples until a noise target or a cap -----------------------------------------------------
+ * Instead of samples_per_pixel for every pixel, each pixel gets samples in rounds until the standard error of its mean luminance is
+ * small enough or max_spp is reached.
+ *
+ * Per-pixel parity (the central promise).  Pixel p receives n_p samples, namely samples 0 … n_p - 1, and d_fb_sum[p] equals, bit for
+ * bit, pixel p of rt_render with samples_per_pixel = n_p: the sum added in sample order, starting from 0.  d_spp[p] = n_p, and n_p is
+ * min_spp + k * batch_spp for some k >= 0 with n_p <= max_spp.  cam->samples_per_pixel is ignored.
+ *
+ * Statistics.  Per sample, with (r, g, b) the radiance rt_render adds for it: y = (0.2126f*r + 0.7152f*g) + 0.0722f*b (rt_denoise's lum);
+ * S1 += y and S2 += y*y, float32, from 0, in sample order, nothing fused.  When d_moments is not NULL it receives (S1, S2) per pixel
+ * (2 floats per pixel, compacted like d_fb_sum).  A pixel no leaf can be hit through (primary visibility) adds the background's y once
+ * per sample, like every other pixel's miss.
+ *
+ * Rule.  With R = (max_spp - min_spp) / batch_spp (integer division) rounds after the min_spp samples, the rule is evaluated after the
+ * min_spp samples and after every round but the last.  For a pixel with n samples (float32, in this order, nothing fused, division
+ * correctly rounded; t = threshold):
+ *     mean = S1 / (float)n;   var = fmaxf(0, (S2 - S1 * mean) / (float)(n - 1));
+ *     goes_on = n + batch_spp <= max_spp && (t == 0 || var / (float)n > (t * t) * (mean * mean + 1e-4f))
+ * A pixel goes on to the next round iff it went on in every earlier judgement and goes_on holds now; a pixel that stops never
+ * resumes.  So every pixel of round r (1 … R) has min_spp + (r - 1) * batch_spp samples as it starts and gets the next batch_spp.
+ * In C:
+ *     int n = min_spp; for (int r = 1; r <= R; ++r) { if (!goes_on(S1, S2, n)) break; add samples n … n + batch_spp - 1; n += batch_spp; }
+ *     n_p = n;
+ * threshold = 0 never stops early: n_p = min_spp + R * batch_spp everywhere.  A NaN radiance makes var NaN and stops the pixel.
+ *
+ * Limits and checks: rt_render's (at most 2^24 pixels, its stream contract, a shard's rows or the whole frame; no tiles, no
+ * rt_context).  Before anything is enqueued: RT_ERR_INVALID_ARG for params NULL or struct_bytes below 8, min_spp < 2, batch_spp < 1,
+ * max_spp < min_spp, a threshold that is negative, NaN or infinite, d_fb_sum or d_spp NULL (and rt_render's own checks);
+ * RT_ERR_UNSUPPORTED for max_spp above 65536, or pixels x batch_spp at or above 2^31 - 4096 when there is a round.
+ *
+ * Work.  All R rounds are enqueued up front; which pixels go on, and how many, lives on the device only, and a round whose list is
+ * empty costs a few empty launches.  With sync == 0 the call only enqueues (it may wait for the stream once, when it grows the
+ * handle's buffers, as rt_render does for its slab).  The rounds walk the scene in the reference's order (the exact walk) with
+ * every sample traced from the camera.
+ * Handle state: the min_spp samples are an ordinary rt_render frame — its walk, its feedback and RT_TRAVERSAL_AUTO's decisions count
+ * like an rt_render's, and rt_last_timing then describes that frame alone.  The rounds leave the handle's decisions alone, as
+ * rt_render_aov does.  timing (may be NULL) with sync != 0: what rt_last_timing reports for the min_spp frame, except kernel_ms (from
+ * the first to the last kernel of the whole call) and trace_launches (+ R). */
+typedef struct rt_adaptive_params {   /* IN, grows like rt_denoise_params: the library reads at most struct_bytes; later fields keep
+                                         their defaults.  struct_bytes below 8 is RT_ERR_INVALID_ARG */
+    uint32_t struct_bytes;            /* sizeof(rt_adaptive_params) as the caller compiled it */
+    int32_t  min_spp;                 /* 16: samples every pixel gets first (>= 2) */
+    int32_t  batch_spp;               /* 16: samples added per round to each pixel still going on (>= 1) */
+    int32_t  max_spp;                 /* 256: cap (>= min_spp, <= 65536); n_p <= min_spp + R * batch_spp <= max_spp */
+    float    threshold;               /* 0.02: relative standard error of the mean luminance to stop at (>= 0, finite; 0 = never stop early) */
+} rt_adaptive_params;
+/* Defaults into *p, struct_bytes = sizeof(rt_adaptive_params). */
+void rt_adaptive_params_init(rt_adaptive_params *p);
+/* d_fb_sum: 3 floats per pixel, d_spp: 1 int32 per pixel, d_moments: NULL or 2 floats per pixel — DEVICE memory, compacted like
+ * rt_render's buffer (rt_shard_rows() x image_width pixels). */
+rt_status rt_render_adaptive(rt_scene *scene, const rt_camera_data *cam, const rt_shard *shard, const rt_adaptive_params *params,
+                             float *d_fb_sum, int32_t *d_spp, float *d_moments, void *hip_stream, int32_t sync, rt_timing *timing);
+/* rt_tonemap of an adaptive frame: d_rgb8[3p + c] = u8(256*clamp(sqrt(d_fb_sum[3p + c] * inv_p), 0, 0.999)) with
+ * inv_p = (float)(1.0 / (double)d_spp[p]) — rt_tonemap's arithmetic at divisor n_p, so each pixel's bytes equal rt_tonemap's of the
+ * uniform frame at n_p.  num_pixels pixels; device pointers; enqueued on hip_stream. */
+rt_status rt_tonemap_spp(const float *d_fb_sum, const int32_t *d_spp, uint8_t *d_rgb8, int64_t num_pixels, void *hip_stream);
+
 /* Milliseconds of the most recent rt_render kernel of this scene (waits for it). */
 rt_status rt_last_kernel_ms(rt_scene *scene, float *ms);
 /* The whole rt_timing of the most recent rt_render of this scene (waits for it). */

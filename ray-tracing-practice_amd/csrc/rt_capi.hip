@@ -16,6 +16,7 @@
 #include "rt_kernel.hip.inc"
 #include "rt_primary.hip.inc"
 #include "rt_aov.hip.inc"
+#include "rt_adaptive.hip.inc"
 // Developer build only (make dev → librtp_amd_dev.so, -DRTP_DEV_BUILD): the rt_debug_* entry points (exhaustive on-device checks of
 // recip / sqrt_cr / sphere_root, the device LBVH builder on its own, the tripwire, the RTP_STATS counters) at the end of this file.
 // The shipped library contains none of them.
@@ -255,6 +256,13 @@ struct rt_scene {
     uint32_t *aov_walked = nullptr;
     hipEvent_t aov_start = nullptr, aov_stop = nullptr;
     std::vector<hipEvent_t> aov_events;    // per timed pass: before the primary pass, before the resolve launch, after it
+    // rt_render_adaptive (rt_adaptive.hip.inc): the moments of a caller who passes none (2 floats per local pixel), two lists of pixels
+    // (2 x adapt_pixels words: one round reads the previous round's list while it writes its own), the work indices of a round
+    // (adapt_work_cap words) and three counter words per round (list length, work indices, trace queue); grown on demand
+    float *adapt_mom = nullptr;
+    uint32_t *adapt_list = nullptr, *adapt_work = nullptr, *adapt_counters = nullptr;
+    size_t adapt_mom_pixels = 0, adapt_pixels = 0, adapt_work_cap = 0, adapt_counter_words = 0;
+    hipEvent_t adapt_start = nullptr, adapt_stop = nullptr;
 };
 
 namespace {
@@ -632,6 +640,9 @@ rt_status rt_scene_destroy(rt_scene *sc) {
     for (hipEvent_t e : sc->aov_events) (void)hipEventDestroy(e);
     if (sc->aov_start) (void)hipEventDestroy(sc->aov_start);
     if (sc->aov_stop) (void)hipEventDestroy(sc->aov_stop);
+    (void)hipFree(sc->adapt_mom); (void)hipFree(sc->adapt_list); (void)hipFree(sc->adapt_work); (void)hipFree(sc->adapt_counters);
+    if (sc->adapt_start) (void)hipEventDestroy(sc->adapt_start);
+    if (sc->adapt_stop) (void)hipEventDestroy(sc->adapt_stop);
     for (rt_scene::Feedback &f : sc->feedback) {
         if (f.done) { if (f.pending) (void)hipEventSynchronize(f.done); (void)hipEventDestroy(f.done); }
         if (f.start) (void)hipEventDestroy(f.start);
@@ -1176,9 +1187,10 @@ rt_status check_sample_range(const char *what, int32_t sample_first, int32_t spp
     return RT_OK;
 }
 
-// rt_render, rt_render_tile and rt_render_samples: whole rows of a shard, or a rectangle; samples [sample_first, sample_first + spp)
+// rt_render, rt_render_tile and rt_render_samples: whole rows of a shard, or a rectangle; samples [sample_first, sample_first + spp).
+// moments (rt_render_adaptive's min_spp round; null for every other call): each pass's luminance moments are added there as well.
 rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shard, const Tile *tile, float *d_fb_sum, void *hip_stream,
-                      int32_t sync, rt_timing *timing, int32_t sample_first = 0) {
+                      int32_t sync, rt_timing *timing, int32_t sample_first = 0, float *moments = nullptr) {
     // ---- 1. validate, fill P
     rtk::KParams P;
     rt_status st = fill_params(sc, cam, shard, P, tile);
@@ -1389,6 +1401,13 @@ rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *s
             hipLaunchKernelGGL(rtk::accumulate_kernel<false>, acc_grid, acc_block, 0, stream, d_fb_sum, (const float *)sc->slab, num_pixels, P.slab_pitch,
                                P.pass_count, pass == 0 ? 1 : 0, (uint32_t *)nullptr, (const uint32_t *)nullptr, (const uint32_t *)nullptr, P.cand, (uint32_t)rtk::kCandWords, P.bg[0], P.bg[1], P.bg[2]);
         }
+        if (moments) {
+            // rt_render_adaptive: the pass's luminance moments, once every row of it is final — on this stream after the join with the
+            // overlapped re-walk, and after the third accumulate launch of an abandoned pass
+            hipLaunchKernelGGL(rtk::moments_kernel<false>, dim3((num_pixels + rtk::kAdaptBlock - 1) / rtk::kAdaptBlock), dim3(rtk::kAdaptBlock), 0, stream, moments,
+                               (const float *)sc->slab, num_pixels, P.slab_pitch, P.pass_count, pass == 0 ? 1 : 0, (const uint32_t *)nullptr, (const uint32_t *)nullptr,
+                               P.cand, (uint32_t)rtk::kCandWords, P.bg[0], P.bg[1], P.bg[2]);
+        }
     }
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(sc->ev_stop, stream));
@@ -1555,6 +1574,164 @@ rt_status aov_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shar
     timing_out(t, timing);
     return RT_OK;
 }
+
+// rt_render_adaptive (rtp_amd.h).  The min_spp round is an ordinary rt_render frame (render_impl: its walk, its feedback,
+// its decisions) that also keeps the luminance moments; every later round traces the samples [n, n + batch) of the pixels still going
+// on with the reference-order walk on a list of work indices, adds them onto the running sums (accumulate_kernel<true>) and the
+// moments, and judges them again.  Every round is enqueued up front: the lists and their lengths live on the device only.
+void adaptive_defaults(rt_adaptive_params &p) {
+    std::memset(&p, 0, sizeof(p));
+    p.struct_bytes = (uint32_t)sizeof(p);
+    p.min_spp = 16;
+    p.batch_spp = 16;
+    p.max_spp = 256;
+    p.threshold = 0.02f;
+}
+// a handle buffer of at least `need` elements (its contents are not kept)
+template <class T>
+rt_status grow(T *&buf, size_t &have, size_t need, hipStream_t stream) {
+    if (have >= need) return RT_OK;
+    HIP_TRY(hipStreamSynchronize(stream));          // (the old one may still be in use on this stream)
+    (void)hipFree(buf);
+    buf = nullptr;
+    have = 0;
+    HIP_TRY(hipMalloc((void **)&buf, need * sizeof(T)));
+    have = need;
+    return RT_OK;
+}
+rt_status adaptive_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shard, const rt_adaptive_params *params, float *d_fb_sum,
+                        int32_t *d_spp, float *d_moments, void *hip_stream, int32_t sync, rt_timing *timing) {
+    // ---- 1. every check before anything is enqueued
+    if (!params || params->struct_bytes < 8) return fail(RT_ERR_INVALID_ARG, "rt_render_adaptive: null params (or struct_bytes below 8)");
+    rt_adaptive_params a;
+    adaptive_defaults(a);
+    std::memcpy(&a, params, params->struct_bytes < sizeof(a) ? params->struct_bytes : sizeof(a));
+    if (a.min_spp < 2) return fail(RT_ERR_INVALID_ARG, "rt_render_adaptive: min_spp below 2");
+    if (a.batch_spp < 1) return fail(RT_ERR_INVALID_ARG, "rt_render_adaptive: batch_spp below 1");
+    if (a.max_spp < a.min_spp) return fail(RT_ERR_INVALID_ARG, "rt_render_adaptive: max_spp below min_spp");
+    if (!(a.threshold >= 0.0f) || !std::isfinite(a.threshold)) return fail(RT_ERR_INVALID_ARG, "rt_render_adaptive: threshold negative, NaN or infinite");
+    if (a.max_spp > 65536) return fail(RT_ERR_UNSUPPORTED, "rt_render_adaptive: max_spp above 65536");
+    if (!cam) return fail(RT_ERR_INVALID_ARG, "null scene or camera");
+    rt_camera_data base = *cam;
+    base.samples_per_pixel = a.min_spp;
+    rtk::KParams P;
+    rt_status st = fill_params(sc, &base, shard, P);
+    if (st != RT_OK) return st;
+    if ((st = check_device(sc)) != RT_OK) return st;
+    if (!d_fb_sum || !d_spp) return fail(RT_ERR_INVALID_ARG, "rt_render_adaptive: null framebuffer or sample counts");
+    if ((st = timing_check(timing)) != RT_OK) return st;
+    const uint32_t num_pixels = (uint32_t)P.local_rows * (uint32_t)P.row_w;
+    const int32_t batch = a.batch_spp, rounds = (a.max_spp - a.min_spp) / a.batch_spp;
+    if (rounds > 0 && (uint64_t)num_pixels * (uint64_t)batch >= (1ull << 31) - 4096)
+        return fail(RT_ERR_UNSUPPORTED, "rt_render_adaptive: pixels x batch_spp beyond the work index arithmetic");
+    hipStream_t stream = (hipStream_t)hip_stream;
+    timing_out(rt_timing{}, timing);
+    if (num_pixels == 0) return RT_OK;
+
+    // ---- 2. the handle's buffers: moments, lists, work indices, counters, and a slab with rows of a round's batch
+    float *mom = d_moments;
+    if (!mom && (st = grow(sc->adapt_mom, sc->adapt_mom_pixels, (size_t)num_pixels * 2, stream)) != RT_OK) return st;
+    if (!mom) mom = sc->adapt_mom;
+    if ((st = grow(sc->adapt_list, sc->adapt_pixels, (size_t)num_pixels * 2, stream)) != RT_OK) return st;
+    if ((st = grow(sc->adapt_counters, sc->adapt_counter_words, (size_t)3 * (size_t)(rounds + 1), stream)) != RT_OK) return st;
+    const uint32_t pitch = slab_pitch_of(batch);
+    const size_t slab_need = rounds > 0 ? (size_t)num_pixels * pitch * 3 : 0;
+    if (rounds > 0) {
+        if ((st = grow(sc->adapt_work, sc->adapt_work_cap, (size_t)num_pixels * (size_t)batch, stream)) != RT_OK) return st;
+        if ((st = grow(sc->slab, sc->slab_floats, slab_need, stream)) != RT_OK) return st;
+    }
+    if (!sc->adapt_start) {
+        HIP_TRY(hipEventCreate(&sc->adapt_start));
+        HIP_TRY(hipEventCreate(&sc->adapt_stop));
+    }
+    HIP_TRY(hipEventRecord(sc->adapt_start, stream));
+
+    // ---- 3. the min_spp round: rt_render's frame, with the moments
+    if ((st = render_impl(sc, &base, shard, nullptr, d_fb_sum, hip_stream, 0, nullptr, 0, mom)) != RT_OK) return st;
+    if (P.max_depth <= 0) {
+        // (render_impl wrote all-zero sums without a pass: every sample is 0, so is every moment — and the rule stops every pixel at
+        // min_spp unless the threshold is 0)
+        HIP_TRY(hipMemsetAsync(mom, 0, (size_t)num_pixels * 8, stream));
+        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)d_spp, a.threshold == 0.0f ? a.min_spp + rounds * batch : a.min_spp, num_pixels, stream));
+        HIP_TRY(hipEventRecord(sc->adapt_stop, stream));
+        if (sync) HIP_TRY(hipStreamSynchronize(stream));
+        return RT_OK;
+    }
+    if (sc->slab_floats < slab_need) return fail(RT_ERR_OUT_OF_MEMORY, "rt_render_adaptive: the sample slab shrank below a round's batch");
+
+    // ---- 4. the rounds: the exact walk's launch shape for this view (the tables may have been re-packed by the frame: P anew)
+    if ((st = fill_params(sc, &base, shard, P)) != RT_OK) return st;
+    const LaunchPlan plan = plan_launch(sc, &base, P, false);
+    const rt_config &cfg = sc->cfg;
+    P.fb = d_fb_sum;
+    P.slab = sc->slab;
+    P.num_pixels = num_pixels;
+    P.slab_pitch = pitch;
+    P.stack_levels = 0;
+    P.num_top = plan.exact.num_top;
+    P.k_inner = cfg.k_inner > 0 ? cfg.k_inner : 24;
+    P.k_shade = cfg.k_shade > 0 ? cfg.k_shade : 48;
+    P.chunk = 64u;                      // (lists: finest granularity, as the exact re-walk of flagged samples)
+    P.taper_shift = 0;
+    P.cand = nullptr; P.order = nullptr; P.traced_pixels = nullptr;       // every sample starts from the camera …
+    P.resume_tag = nullptr; P.resume_state = nullptr; P.abandon = nullptr; P.dirty = nullptr; P.dirty_list = nullptr;
+    P.work_list = sc->adapt_work;
+    P.work_cap = num_pixels * (uint32_t)batch;                            // … and the list never stands for "every sample"
+    const void *exact = plan.exact.in_lds ? (const void *)rtk::render_kernel<true, true> : (const void *)rtk::render_kernel<false, true>;
+    int wgs = sc->num_cus * plan.exact.wgs_per_cu;
+    const uint32_t max_wgs = (uint32_t)(((uint64_t)num_pixels * (batch < 64 ? batch : 64) + rtk::kBlock - 1) / rtk::kBlock);
+    if ((uint32_t)wgs > max_wgs) wgs = (int)max_wgs;
+    if (wgs < 1) wgs = 1;
+    const dim3 pix_grid((num_pixels + rtk::kAdaptBlock - 1) / rtk::kAdaptBlock), pix_block(rtk::kAdaptBlock);
+    const dim3 acc_grid((num_pixels + 64 * rtk::kAccWaves - 1) / (64 * rtk::kAccWaves)), acc_block(64 * rtk::kAccWaves);
+    const uint64_t expand_items = (uint64_t)num_pixels * (uint64_t)batch;
+    const uint32_t expand_grid = (uint32_t)std::min<uint64_t>((expand_items + rtk::kAdaptBlock - 1) / rtk::kAdaptBlock, (uint64_t)sc->num_cus * 8u);
+    uint32_t *lists[2] = {sc->adapt_list, sc->adapt_list + num_pixels};
+    uint32_t *const counters = sc->adapt_counters;          // round r (1 …): [3(r-1)] its list's length, [3(r-1) + 1] its work indices, [3(r-1) + 2] its queue
+    HIP_TRY(hipMemsetAsync(counters, 0, (size_t)3 * (size_t)(rounds + 1) * sizeof(uint32_t), stream));
+    int32_t n = a.min_spp;
+    // after the min_spp round: every pixel is judged (and its count written)
+    hipLaunchKernelGGL(rtk::adaptive_select_kernel<true>, pix_grid, pix_block, 0, stream, (const float *)mom, d_spp, num_pixels, (const uint32_t *)nullptr,
+                       (const uint32_t *)nullptr, lists[0], counters, n, batch, a.max_spp, a.threshold);
+    HIP_TRY(hipGetLastError());
+    for (int32_t r = 1; r <= rounds; ++r) {
+        const uint32_t *list = lists[(r - 1) & 1];
+        const uint32_t *listed = counters + 3 * (r - 1);
+        hipLaunchKernelGGL(rtk::adaptive_expand_kernel, dim3(expand_grid), pix_block, 0, stream, list, listed, (uint32_t)batch, sc->adapt_work,
+                           counters + 3 * (r - 1) + 1);
+        // samples [n, n + batch) of the listed pixels: work index = local pixel * batch + slot, in the pixel's own slab row
+        P.pass_first = n;
+        P.pass_count = batch;
+        P.total_work = num_pixels * (uint32_t)batch;
+        if (!make_magic((uint32_t)batch, (uint64_t)P.total_work + 64, P.magic_count)) return fail(RT_ERR_UNSUPPORTED, "image too large for the work index arithmetic");
+        P.work_count = counters + 3 * (r - 1) + 1;
+        P.queue = counters + 3 * (r - 1) + 2;
+        reservation(P.total_work, (uint64_t)wgs * (rtk::kBlock / rtk::kWave), P.full_chunk, P.full_taper);
+        HIP_TRY(launch(exact, (uint32_t)rtk::kBlock, wgs, plan.exact.lds_bytes, stream, P));
+        // … added onto the running sums in slot order, and onto the moments
+        hipLaunchKernelGGL(rtk::accumulate_kernel<true>, acc_grid, acc_block, 0, stream, d_fb_sum, (const float *)sc->slab, num_pixels, pitch, batch, 0,
+                           (uint32_t *)nullptr, list, listed);
+        hipLaunchKernelGGL(rtk::moments_kernel<true>, pix_grid, pix_block, 0, stream, mom, (const float *)sc->slab, num_pixels, pitch, batch, 0, list, listed,
+                           (const uint32_t *)nullptr, 0u, 0.0f, 0.0f, 0.0f);
+        n += batch;
+        if (r < rounds)
+            hipLaunchKernelGGL(rtk::adaptive_select_kernel<false>, pix_grid, pix_block, 0, stream, (const float *)mom, d_spp, num_pixels, list, listed,
+                               lists[r & 1], counters + 3 * r, n, batch, a.max_spp, a.threshold);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(sc->adapt_stop, stream));
+    if (!sync) return RT_OK;
+    // what rt_last_timing reports for the min_spp round, with the whole call's kernel_ms and every trace launch of it
+    rt_timing t;
+    std::memset(&t, 0, sizeof(t));
+    t.struct_bytes = (uint32_t)sizeof(t);
+    if ((st = rt_last_timing(sc, &t)) != RT_OK) return st;
+    HIP_TRY(hipEventSynchronize(sc->adapt_stop));
+    HIP_TRY(hipEventElapsedTime(&t.kernel_ms, sc->adapt_start, sc->adapt_stop));
+    t.trace_launches += (uint32_t)rounds;
+    timing_out(t, timing);
+    return RT_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -1595,6 +1772,15 @@ rt_status rt_render_aov_tile(rt_scene *sc, const rt_camera_data *cam, int32_t ti
                              const rt_aov_buffers *buffers, void *hip_stream, int32_t sync, rt_timing *timing) {
     const Tile tile{tile_x0, tile_y0, tile_w, tile_h};
     return aov_impl(sc, cam, nullptr, &tile, buffers, hip_stream, sync, timing);
+}
+
+void rt_adaptive_params_init(rt_adaptive_params *p) {
+    if (p) adaptive_defaults(*p);
+}
+
+rt_status rt_render_adaptive(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shard, const rt_adaptive_params *params, float *d_fb_sum,
+                             int32_t *d_spp, float *d_moments, void *hip_stream, int32_t sync, rt_timing *timing) {
+    return adaptive_impl(sc, cam, shard, params, d_fb_sum, d_spp, d_moments, hip_stream, sync, timing);
 }
 
 void rt_timing_init(rt_timing *t) {
@@ -1899,6 +2085,18 @@ rt_status rt_tonemap(const float *d_fb_sum, uint8_t *d_rgb8, int64_t num_floats,
     int64_t blocks = (num_floats + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(rtk::tonemap_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)hip_stream, d_fb_sum, d_rgb8, num_floats, inv);
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
+
+rt_status rt_tonemap_spp(const float *d_fb_sum, const int32_t *d_spp, uint8_t *d_rgb8, int64_t num_pixels, void *hip_stream) {
+    if (num_pixels <= 0) return RT_OK;
+    if (!d_fb_sum || !d_spp || !d_rgb8) return fail(RT_ERR_INVALID_ARG, "null argument");
+    if (num_pixels > ((int64_t)1 << 40)) return fail(RT_ERR_UNSUPPORTED, "rt_tonemap_spp: more than 2^40 pixels");
+    const int64_t n = 3 * num_pixels;
+    int64_t blocks = (n + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(rtk::tonemap_spp_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)hip_stream, d_fb_sum, d_spp, d_rgb8, n);
     HIP_TRY(hipGetLastError());
     return RT_OK;
 }

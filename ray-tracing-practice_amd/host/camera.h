@@ -133,6 +133,8 @@ bool write_aov_file(const std::string &path, int32_t width, int32_t height, int3
 // Animation driver beyond the reference: frames dealt round-robin to num_devices GPUs, saver
 // arithmetic on the device, file output overlapped with the next frame.  Same files, byte for byte.
 void gpu_render_pipelined(const SceneParams &params, const rt_scene_desc &desc, int num_devices);
+// rtp_main --gpu --adaptive: the orbit frame after frame on one GPU, each frame through rt_render_adaptive and rt_tonemap_spp
+void gpu_render_adaptive(const SceneParams &params, const rt_scene_desc &desc, const rt_adaptive_params &ap);
 
 // … and the other split: every frame sharded in row bands over num_devices GPUs (<= 0: all) with one RCCL gather per
 // frame (rt_context, rt_render_sharded).  Same files, byte for byte.

@@ -3,6 +3,7 @@
 // description.  --cpu is the reference's single-threaded CPU loop: this build ships no CPU
 // render path (its CPU restatement lives under oracle/ as a test checker only), so --cpu fails
 // loudly instead of silently rendering on the host.
+#include <cstdio>
 #include <cstdlib>
 #include <iostream>
 #include <string>
@@ -56,6 +57,32 @@ int main(int argc, char *argv[]) {
             return 2;
         }
     }
+    // extension: `--gpu --adaptive <threshold> [--adaptive-spp min:batch:max]` renders every frame with per-pixel adaptive sampling
+    // (rt_render_adaptive; default 16:16:256) and saves it through rt_tonemap_spp — one GPU, frame after frame
+    for (int a = 2; a + 1 < argc; ++a)
+        if (std::string(argv[a]) == "--adaptive") {
+            rt_adaptive_params ap;
+            rt_adaptive_params_init(&ap);
+            ap.threshold = strtof(argv[a + 1], nullptr);
+            for (int b = 2; b + 1 < argc; ++b)
+                if (std::string(argv[b]) == "--adaptive-spp" &&
+                    sscanf(argv[b + 1], "%d:%d:%d", &ap.min_spp, &ap.batch_spp, &ap.max_spp) != 3) {
+                    std::cerr << "rtp_main: --adaptive-spp takes min:batch:max\n";
+                    return 2;
+                }
+            if (aov || denoise || temporal || devices > 0) {
+                std::cerr << "rtp_main: --adaptive renders frame after frame on one GPU: it cannot be combined with --aov, --denoise, "
+                             "--denoise-temporal, --devices, --shard or RTP_DEVICES\n";
+                return 2;
+            }
+            for (int b = 2; b < argc; ++b)
+                if (std::string(argv[b]) == "--shard") {
+                    std::cerr << "rtp_main: --adaptive cannot be combined with --shard\n";
+                    return 2;
+                }
+            rtp::gpu_render_adaptive(params, desc, ap);
+            return 0;
+        }
     // extension: `--gpu --shard N` splits EVERY frame over N GPUs (0 = all of the node) with one RCCL gather per frame
     for (int a = 2; a + 1 < argc; ++a)
         if (std::string(argv[a]) == "--shard") {

@@ -252,6 +252,52 @@ void gpu_render_pipelined(const SceneParams &params, const rt_scene_desc &desc, 
     for (std::thread &t : threads) t.join();
 }
 
+// ---- adaptive sampling (rtp_main --gpu --adaptive) ----------------------------------------------------------
+// The orbit of gpu_render, each frame rendered by rt_render_adaptive and saved through rt_tonemap_spp: every pixel's bytes are the
+// saver arithmetic with its own sample count as the divisor (the mean of its samples).  Prints frame, milliseconds and the samples
+// the frame took.
+void gpu_render_adaptive(const SceneParams &params, const rt_scene_desc &desc, const rt_adaptive_params &ap) {
+    rt_scene *scene = nullptr;
+    RTP_CHECK(rt_scene_create(&desc, &scene));
+    const size_t num_pixels = static_cast<size_t>(params.width) * params.height;
+    float *d_fb = nullptr;
+    int32_t *d_spp = nullptr;
+    uint8_t *d_rgb = nullptr;
+    RTP_CHECK(rt_device_alloc(num_pixels * 3 * sizeof(float), reinterpret_cast<void **>(&d_fb)));
+    RTP_CHECK(rt_device_alloc(num_pixels * sizeof(int32_t), reinterpret_cast<void **>(&d_spp)));
+    RTP_CHECK(rt_device_alloc(num_pixels * 3, reinterpret_cast<void **>(&d_rgb)));
+    std::vector<int32_t> spp(num_pixels);
+    for (int n = 0; n < params.num_frames; ++n) {
+        Vec3 eye, target;
+        orbit_pose(params, n, eye, target);
+        Camera camera(params.height, params.width, nullptr, eye, target);
+        camera.vfov = params.fov_degrees;
+        camera.samples_per_pixel = ap.min_spp;
+        camera.max_depth = params.max_depth;
+        camera.background_color = Vec3(0, 0, 0);
+        const rt_camera_data cam = camera.build_camera_data();
+        const auto t0 = std::chrono::steady_clock::now();
+        RTP_CHECK(rt_render_adaptive(scene, &cam, nullptr, &ap, d_fb, d_spp, nullptr, nullptr, 1, nullptr));
+        RTP_CHECK(rt_tonemap_spp(d_fb, d_spp, d_rgb, static_cast<int64_t>(num_pixels), nullptr));
+        PendingFile file;
+        file.path = frame_filename(params.output_pattern, n);
+        file.width = params.width;
+        file.height = params.height;
+        file.rgb.resize(num_pixels * 3);
+        RTP_CHECK(rt_copy_to_host(file.rgb.data(), d_rgb, num_pixels * 3));
+        RTP_CHECK(rt_copy_to_host(spp.data(), d_spp, num_pixels * sizeof(int32_t)));
+        write_binary_frame(file);
+        const float ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        long long samples = 0;
+        for (int32_t k : spp) samples += k;
+        std::cout << n << "\t" << ms << "\t" << samples << "\n";
+    }
+    rt_device_free(d_fb);
+    rt_device_free(d_spp);
+    rt_device_free(d_rgb);
+    RTP_CHECK(rt_scene_destroy(scene));
+}
+
 // ---- one frame over all GPUs (BASELINE configs[3]) ------------------------------------------
 // The other way to use a node: every frame is split into interleaved 8-row bands over `num_devices` GPUs
 // (rt_context / rt_render_sharded: scene replicated, one RCCL gather per frame to the root GPU), then the root runs

@@ -99,6 +99,27 @@ class DenoiseParams(C.Structure):
         self.struct_bytes = C.sizeof(DenoiseParams)
 
 
+class AdaptiveParams(C.Structure):
+    """rt_adaptive_params (include/rtp_amd.h): an IN structure of the caller's size — struct_bytes is set on construction; the other
+    fields are 0 until rt_adaptive_params_init (adaptive_params()) fills the defaults."""
+    _fields_ = [("struct_bytes", C.c_uint32), ("min_spp", C.c_int32), ("batch_spp", C.c_int32), ("max_spp", C.c_int32), ("threshold", C.c_float)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_bytes = C.sizeof(AdaptiveParams)
+
+
+def adaptive_params(**params):
+    """rt_adaptive_params with the library's defaults, then the given fields (min_spp, batch_spp, max_spp, threshold)."""
+    p = AdaptiveParams()
+    amd_lib().rt_adaptive_params_init(C.byref(p))
+    for k, v in params.items():
+        if k not in dict(AdaptiveParams._fields_):
+            raise RtError(f"rt_adaptive_params has no field {k}")
+        setattr(p, k, v)
+    return p
+
+
 TRAVERSAL_AUTO, TRAVERSAL_EXACT, TRAVERSAL_GUARDED = 0, 1, 2
 BUILD_HOST_SAH, BUILD_DEVICE_LBVH = 0, 1
 KERNEL_AUTO, KERNEL_MEGA, KERNEL_WAVEFRONT = 0, 1, 2
@@ -149,6 +170,7 @@ RTP_AMD_SYMBOLS = [
     "rt_render_sharded", "rt_gather", "rt_aov_buffers_init", "rt_render_aov", "rt_render_aov_tile",
     "rt_denoise_params_init", "rt_denoise_workspace_bytes", "rt_denoise",
     "rt_render_samples", "rt_render_aov_samples", "rt_denoise_history_bytes", "rt_denoise_temporal",
+    "rt_adaptive_params_init", "rt_render_adaptive", "rt_tonemap_spp",
 ]
 
 _host = None
@@ -227,6 +249,12 @@ def amd_lib():
             lib.rt_denoise_workspace_bytes.restype = C.c_uint64
             lib.rt_denoise.argtypes = [C.c_void_p, C.POINTER(AovBuffers), C.c_int32, C.c_int32, C.c_int32, C.POINTER(DenoiseParams),
                                        C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        if hasattr(lib, "rt_render_adaptive"):
+            lib.rt_adaptive_params_init.argtypes = [C.POINTER(AdaptiveParams)]
+            lib.rt_adaptive_params_init.restype = None
+            lib.rt_render_adaptive.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(Shard), C.POINTER(AdaptiveParams), C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(Timing)]
+            lib.rt_tonemap_spp.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
         if hasattr(lib, "rt_denoise_temporal"):
             lib.rt_render_samples.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(Shard), C.c_int32, C.c_void_p, C.c_void_p,
                                               C.c_int32, C.POINTER(Timing)]
@@ -701,6 +729,41 @@ class DeviceScene:
             for d in dev.values():
                 lib.rt_device_free(d)
         return out, t
+
+    def render_adaptive(self, cam, d_fb_ptr, d_spp_ptr, d_moments_ptr=None, shard=None, stream=None, sync=True, **params):
+        """rt_render_adaptive: d_fb_ptr (3 floats per pixel), d_spp_ptr (1 int32 per pixel), d_moments_ptr (None, or 2 floats per pixel)
+        are integer device addresses; params are rt_adaptive_params fields (min_spp, batch_spp, max_spp, threshold).  Returns the
+        rt_timing."""
+        p = adaptive_params(**params)
+        t = Timing()
+        self._apply_config()
+        _check(amd_lib().rt_render_adaptive(self._h, C.byref(cam), C.byref(shard) if shard else None, C.byref(p), C.c_void_p(d_fb_ptr),
+                                            C.c_void_p(d_spp_ptr), C.c_void_p(d_moments_ptr or 0), C.c_void_p(stream or 0), 1 if sync else 0,
+                                            C.byref(t)), "rt_render_adaptive")
+        return t
+
+    def render_adaptive_to_host(self, cam, shard=None, **params):
+        """rt_render_adaptive through fresh device buffers: (fb (rows, w, 3) float32 sums, spp (rows, w) int32, moments (rows, w, 2)
+        float32 (S1, S2)) and the rt_timing."""
+        lib = amd_lib()
+        rows = lib.rt_shard_rows(cam.image_height, C.byref(shard) if shard else None)
+        w = cam.image_width
+        fb = np.empty((rows, w, 3), dtype=np.float32)
+        spp = np.empty((rows, w), dtype=np.int32)
+        mom = np.empty((rows, w, 2), dtype=np.float32)
+        dev = []
+        try:
+            for a in (fb, spp, mom):
+                d = C.c_void_p()
+                _check(lib.rt_device_alloc(a.nbytes or 12, C.byref(d)), "rt_device_alloc")
+                dev.append(d)
+            t = self.render_adaptive(cam, dev[0].value, dev[1].value, dev[2].value, shard=shard, **params)
+            for a, d in zip((fb, spp, mom), dev):
+                _check(lib.rt_copy_to_host(a.ctypes.data, d, a.nbytes), "rt_copy_to_host")
+        finally:
+            for d in dev:
+                lib.rt_device_free(d)
+        return fb, spp, mom, t
 
     def last_kernel_ms(self):
         ms = C.c_float()
