@@ -535,6 +535,50 @@ rt_status rt_render_adaptive(rt_scene *scene, const rt_camera_data *cam, const r
  * uniform frame at n_p.  num_pixels pixels; device pointers; enqueued on hip_stream. */
 rt_status rt_tonemap_spp(const float *d_fb_sum, const int32_t *d_spp, uint8_t *d_rgb8, int64_t num_pixels, void *hip_stream);
 
+/* ---- thin-lens depth of field and shutter motion blur ---------------------------------------------------------
+ * rt_render_samples / rt_render_aov_samples with a camera that has a lens and / or an open shutter.  Pixel (i, j), sample s; the
+ * draws come from the same RNG as the pinhole's, and the path goes on from the state they leave:
+ *   1. the seed is as always; ox, oy are drawn exactly as the pinhole camera draws them;
+ *   2. time, only when cam_close != NULL: tau = random_float; each of origin, pixel00_loc, pixel_delta_u and pixel_delta_v becomes
+ *      X = X0 + tau * (X1 - X0) per component (0: cam_open, 1: cam_close);
+ *   3. lens, only when lens_radius > 0: (lx, ly) by rejection, as random_in_unit_sphere does it — repeat
+ *      lx = random_range(-1, 1); ly = random_range(-1, 1) (x first) while lx*lx + ly*ly >= 1;
+ *   4. pinhole ray: S = (((P00 + i*du) + j*dv) + ox*du) + oy*dv (i, j as floats), D = S - O.  With lens_radius == 0 the ray is (O, D);
+ *   5. thin lens, otherwise: n = cross(du, dv) = (du1*dv2 - du2*dv1, du2*dv0 - du0*dv2, du0*dv1 - du1*dv0);
+ *      dimg = fabsf(dot(P00 - O, n)) / sqrtf(dot(n, n)); k = focus_distance / dimg; focus point F = O + k*D;
+ *      uh = du / sqrtf(dot(du, du)), vh = dv / sqrtf(dot(dv, dv)); lens point L = (O + (R*lx)*uh) + (R*ly)*vh; the ray is (L, F - L).
+ * Float32 throughout, in the order written, nothing fused, division and sqrtf correctly rounded.  With cam_close == NULL and
+ * lens_radius == 0 the call is rt_render_samples / rt_render_aov_samples bit for bit.  Sums run over samples sample_first … in sample
+ * order, starting from 0.
+ * Checks and limits: rt_render_samples's (rows of a shard only: no tiles, no rt_context).  Before anything is enqueued,
+ * RT_ERR_INVALID_ARG for: cam_close differing from cam_open in width, height, spp, max_depth or background; a negative, NaN or
+ * infinite lens_radius; with the lens on, a focus_distance that is not positive and finite, or a camera (either end) with
+ * dot(P00 - O, n) == 0.  A pose between the ends can still degenerate; then the arithmetic above defines the result.
+ * Handle state: the calls leave the handle's own decisions alone, as rt_render_aov does — its walk choice, a pause of the guarded walk,
+ * the re-pack of its tree, its cached view lists and what rt_last_timing reports.  The guarded walk serves a lens frame only where every
+ * ray origin it can make lies within the reach its margins were sized for; otherwise the exact walk runs (timing->guarded says which).
+ * Results are the same bits on every walk.  timing (may be NULL): this call's record (kernel_ms and flagged_samples with sync != 0). */
+typedef struct rt_lens_params {   /* IN, grows like rt_adaptive_params: the library reads at most struct_bytes; < 8 = RT_ERR_INVALID_ARG */
+    uint32_t struct_bytes;        /* sizeof(rt_lens_params) as the caller compiled it */
+    float    lens_radius;         /* 0 (default): pinhole, no lens draws.  >= 0, finite, world units */
+    float    focus_distance;      /* 10: distance of the plane in focus from the camera origin along the image plane's normal
+                                     (> 0, finite; read only when lens_radius > 0) */
+} rt_lens_params;
+/* Defaults into *p, struct_bytes = sizeof(rt_lens_params). */
+void rt_lens_params_init(rt_lens_params *p);
+/* rt_render_samples with a camera that has a lens and / or an open shutter (cam_close NULL: no motion; lens NULL: defaults). */
+rt_status rt_render_lens(rt_scene *scene, const rt_camera_data *cam_open, const rt_camera_data *cam_close, const rt_lens_params *lens,
+                         const rt_shard *shard, int32_t sample_first, float *d_fb_sum, void *hip_stream, int32_t sync, rt_timing *timing);
+/* rt_render_aov_samples with the same camera rays (first hit of the lens / motion ray). */
+rt_status rt_render_aov_lens(rt_scene *scene, const rt_camera_data *cam_open, const rt_camera_data *cam_close, const rt_lens_params *lens,
+                             const rt_shard *shard, int32_t sample_first, const rt_aov_buffers *buffers, void *hip_stream, int32_t sync,
+                             rt_timing *timing);
+/* Probe for tests, HOST memory: the camera ray of n (i, j, s) samples (ijs: 3 int32 each; origins, directions: 3 floats each), made by
+ * the device code the kernels inline, and the RNG state after the camera's draws (final_seed: 1 word each).  Runs on the current
+ * device. */
+rt_status rt_lens_camera_rays(const rt_camera_data *cam_open, const rt_camera_data *cam_close, const rt_lens_params *lens,
+                              int32_t n, const int32_t *ijs, float *origins, float *directions, uint32_t *final_seed);
+
 /* Milliseconds of the most recent rt_render kernel of this scene (waits for it). */
 rt_status rt_last_kernel_ms(rt_scene *scene, float *ms);
 /* The whole rt_timing of the most recent rt_render of this scene (waits for it). */

@@ -28,11 +28,19 @@ struct AovOut {
 constexpr int kAovSlots = 8;            // accumulate: slots per LDS tile — 28 KB per workgroup, five workgroups per CU: its loop waits on gathers (16, accumulate_kernel's: 2.3 ms slower at 1080p x 500)
 constexpr int kAovRow = kAovSlots * 3 + 4;
 
+// a sample's camera ray: the pinhole's (camera_ray), or kLens: the lens / moving camera's (lens_camera_ray, rt_render_aov_lens)
+template <bool kLens>
+__device__ __forceinline__ void aov_camera_ray(Lane &L, const KParams &P, const LensCam &C, int32_t pi, int32_t pj, uint32_t seed1, f3 &ray_o, f3 &ray_d) {
+    if constexpr (kLens) lens_camera_ray(L, C, pi, pj, seed1, ray_o, ray_d);
+    else camera_ray<false>(L, P, pi, pj, seed1, ray_o, ray_d);
+}
+
 // hit_scene for a sample's camera ray: the reference-order walk, closest_hit_kernel's loop → (t, code or kPrimMiss)
-__device__ __forceinline__ int32_t aov_walk(const KParams &P, int32_t pi, int32_t pj, uint32_t seed1, float &t) {
+template <bool kLens = false>
+__device__ __forceinline__ int32_t aov_walk(const KParams &P, int32_t pi, int32_t pj, uint32_t seed1, float &t, const LensCam &C = LensCam{}) {
     Lane L;
     f3 ray_o, ray_d;
-    camera_ray<false>(L, P, pi, pj, seed1, ray_o, ray_d);
+    aov_camera_ray<kLens>(L, P, C, pi, pj, seed1, ray_o, ray_d);
     begin_ray(L, ray_o, ray_d, 0);
     while (!traversal_finished<true>(L, kBlocked)) {
         if (L.sp != 0) leaf_threaded(L, P.spheres, P.planes);
@@ -51,6 +59,28 @@ __device__ __forceinline__ void aov_pixel(const KParams &P, uint32_t q, int32_t 
     } else {
         const uint32_t band = div_magic(pjl, P.magic_band);
         pj = (int32_t)((band * (uint32_t)P.num_parts + (uint32_t)P.part) * (uint32_t)P.band_rows + (pjl - band * (uint32_t)P.band_rows));
+    }
+}
+
+// every sample of the pass, a lane per sample, 64 consecutive samples per wave → its (t, code, seed) record, from the lens camera's ray
+// (aov_resolve_lens_kernel).  The kAll branch of aov_resolve_kernel below is the same loop for the pinhole, kept as its own text: called
+// through this helper, that kernel's code changed (one instruction), and the pinhole kernels stay what they were.
+template <bool kLens>
+__device__ __forceinline__ void aov_resolve_all(const KParams &P, const LensCam &C, uint32_t lane, uint32_t wave, uint32_t num_waves) {
+    const uint32_t batches = (P.total_work + 63u) >> 6;
+    for (uint32_t b = wave; b < batches; b += num_waves) {
+        const uint32_t w = b * 64u + lane;
+        if (w >= P.total_work) continue;
+        int32_t pi, pj;
+        uint32_t k, record;
+        map_work<false>(P, w, pi, pj, k, 0u, nullptr, nullptr, &record);
+        const uint32_t seed1 = sample_seed1(wang_hash((uint32_t)pi * (uint32_t)P.width + (uint32_t)pj), P.pass_first + (int32_t)k);
+        float t;
+        const int32_t code = aov_walk<kLens>(P, pi, pj, seed1, t, C);
+        float *rec = P.slab + (size_t)record * 3;
+        rec[0] = t;
+        rec[1] = __int_as_float(code);
+        rec[2] = __uint_as_float(seed1);
     }
 }
 
@@ -99,10 +129,12 @@ __global__ void __launch_bounds__(256) aov_resolve_kernel(const KParams P, uint3
 
 // What one hit adds: shade()'s surface arithmetic (rt_kernel.hip.inc) on the sample's camera ray — the hit point, the outward
 // normal, set_face_normal, the material row and, for a textured LAMBERTIAN or METAL material, its texel.
-__device__ __forceinline__ void aov_hit(const KParams &P, int32_t pi, int32_t pj, uint32_t seed1, float t, int32_t code, f3 &albedo, f3 &normal) {
+template <bool kLens = false>
+__device__ __forceinline__ void aov_hit(const KParams &P, int32_t pi, int32_t pj, uint32_t seed1, float t, int32_t code, f3 &albedo, f3 &normal,
+                                        const LensCam &C = LensCam{}) {
     Lane L;
     f3 ray_o, ray_d;
-    camera_ray<false>(L, P, pi, pj, seed1, ray_o, ray_d);
+    aov_camera_ray<kLens>(L, P, C, pi, pj, seed1, ray_o, ray_d);
     const f3 point = add(ray_o, scale(t, ray_d));        // r.at(rec.t)
     const int32_t idx = code >> 1;
     const bool is_plane = (code & 1) != 0;
@@ -150,84 +182,26 @@ __device__ __forceinline__ void aov_hit(const KParams &P, int32_t pi, int32_t pj
 // reads its own pixel's samples.  A kPrimFlag record is walked here (*walked counts them).  A miss adds the background to the albedo and nothing else; a sky pixel (no candidate leaf) is all
 // misses and has no row, and a wave of nothing but sky reads no slab at all.
 __global__ void __launch_bounds__(kAccWaves * 64) aov_accumulate_kernel(const KParams P, const AovOut out, int32_t first_pass, uint32_t *walked) {
-    __shared__ float4 tile4[kAccWaves][64 * kAovRow / 4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t num_pixels = P.num_pixels, pitch = P.slab_pitch;
-    const int32_t count = P.pass_count;
-    const uint32_t pg = (blockIdx.x * (uint32_t)kAccWaves + (uint32_t)wave) * 64u;
-    if (pg >= num_pixels) return;
-    const uint32_t q = pg + (uint32_t)lane;
-    const bool in = q < num_pixels;
-    f3 alb = mk(0.0f, 0.0f, 0.0f), nrm = mk(0.0f, 0.0f, 0.0f);
-    float dep = 0.0f;
-    uint32_t hits = 0u;
-    int32_t prim = -1;
-    if (in && !first_pass) {
-        if (out.albedo) alb = mk(out.albedo[3 * (size_t)q], out.albedo[3 * (size_t)q + 1], out.albedo[3 * (size_t)q + 2]);
-        if (out.normal) nrm = mk(out.normal[3 * (size_t)q], out.normal[3 * (size_t)q + 1], out.normal[3 * (size_t)q + 2]);
-        if (out.depth) dep = out.depth[q];
-        if (out.hits) hits = out.hits[q];
-    }
-    const f3 bg = mk(P.bg[0], P.bg[1], P.bg[2]);
-    const bool sky = P.cand != nullptr && in && P.cand[(size_t)q * kCandWords] == 0u;
-    auto store = [&]() {
-        if (out.albedo) { out.albedo[3 * (size_t)q] = alb.x; out.albedo[3 * (size_t)q + 1] = alb.y; out.albedo[3 * (size_t)q + 2] = alb.z; }
-        if (out.normal) { out.normal[3 * (size_t)q] = nrm.x; out.normal[3 * (size_t)q + 1] = nrm.y; out.normal[3 * (size_t)q + 2] = nrm.z; }
-        if (out.depth) out.depth[q] = dep;
-        if (out.hits) out.hits[q] = hits;
-        if (out.prim && first_pass) out.prim[q] = prim;
-    };
-    if (P.cand != nullptr && __ballot(sky) == __ballot(in)) {        // a wave of nothing but sky
-        if (in) {
-            for (int32_t s = 0; s < count; ++s) alb = add(alb, bg);
-            store();
-        }
-        return;
-    }
-    int32_t pi = 0, pj = 0;
-    if (in) aov_pixel(P, q, pi, pj);
-    uint32_t rewalked = 0;
-    float *tile = reinterpret_cast<float *>(tile4[wave]);
-    const uint32_t npix = num_pixels - pg < 64u ? num_pixels - pg : 64u;
-    for (uint32_t s0 = 0; s0 < (uint32_t)count; s0 += kAovSlots) {
-        const uint32_t ns = pitch - s0 < (uint32_t)kAovSlots ? pitch - s0 : (uint32_t)kAovSlots;      // slots of this tile (padding included: multiple of 4)
-        const uint32_t seg4 = ns * 3u / 4u;
-        const uint32_t total4 = npix * seg4;
-        for (uint32_t k = (uint32_t)lane; k < total4; k += 64u) {
-            const uint32_t pl = k / seg4, f4 = k - pl * seg4;
-            const float4 v = *reinterpret_cast<const float4 *>(P.slab + ((size_t)(pg + pl) * pitch + s0) * 3 + f4 * 4u);
-            *reinterpret_cast<float4 *>(tile + pl * kAovRow + f4 * 4u) = v;
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-        const uint32_t nv = (uint32_t)count - s0 < (uint32_t)kAovSlots ? (uint32_t)count - s0 : (uint32_t)kAovSlots;
-        if (in && !sky) {
-            const float *row = tile + lane * kAovRow;
-            for (uint32_t s = 0; s < nv; ++s) {
-                float t = row[3 * s];
-                int32_t code = __float_as_int(row[3 * s + 1]);
-                if (code == kPrimFlag || code == kPrimWalk) {       // (kPrimWalk: its pixel was resolved by aov_resolve_kernel — not met here)
-                    code = aov_walk(P, pi, pj, __float_as_uint(row[3 * s + 2]), t);
-                    ++rewalked;
-                }
-                if (s0 + s == 0u) prim = code >= 0 ? code : -1;
-                if (code >= 0) {
-                    f3 a, n;
-                    aov_hit(P, pi, pj, __float_as_uint(row[3 * s + 2]), t, code, a, n);
-                    alb = add(alb, a);
-                    nrm = add(nrm, n);
-                    dep = dep + t;
-                    ++hits;
-                } else {
-                    alb = add(alb, bg);
-                }
-            }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    }
-    if (sky)
-        for (int32_t s = 0; s < count; ++s) alb = add(alb, bg);
-    if (in) store();
-    if (rewalked != 0u) atomicAdd(walked, rewalked);
+#define RTP_AOV_WALK(...) aov_walk(__VA_ARGS__)
+#define RTP_AOV_HIT(...) aov_hit(__VA_ARGS__)
+#include "rt_aov_accumulate_body.inc"
+#undef RTP_AOV_WALK
+#undef RTP_AOV_HIT
+}
+
+// rt_render_aov_lens: the same two steps with the lens / moving camera's rays and no candidate lists — (1) every sample's first hit …
+__global__ void __launch_bounds__(256) aov_resolve_lens_kernel(const KParams P, const LensCam C) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane((blockIdx.x * 256u + threadIdx.x) >> 6), num_waves = gridDim.x * 4u;
+    aov_resolve_all<true>(P, C, lane, wave, num_waves);
+}
+// … (2) added to the sums in sample order, each hit rebuilt from the sample's lens ray
+__global__ void __launch_bounds__(kAccWaves * 64) aov_accumulate_lens_kernel(const KParams P, const LensCam C, const AovOut out, int32_t first_pass, uint32_t *walked) {
+#define RTP_AOV_WALK(...) aov_walk<true>(__VA_ARGS__, C)
+#define RTP_AOV_HIT(...) aov_hit<true>(__VA_ARGS__, C)
+#include "rt_aov_accumulate_body.inc"
+#undef RTP_AOV_WALK
+#undef RTP_AOV_HIT
 }
 
 }  // namespace rtk

@@ -263,6 +263,9 @@ struct rt_scene {
     uint32_t *adapt_list = nullptr, *adapt_work = nullptr, *adapt_counters = nullptr;
     size_t adapt_mom_pixels = 0, adapt_pixels = 0, adapt_work_cap = 0, adapt_counter_words = 0;
     hipEvent_t adapt_start = nullptr, adapt_stop = nullptr;
+    // rt_render_lens: events of its own (rt_last_timing keeps reporting the last rt_render)
+    hipEvent_t lens_start = nullptr, lens_stop = nullptr;
+    uint32_t *lens_queue = nullptr;         // … and a counter block of its own (kQueueWords)
 };
 
 namespace {
@@ -643,6 +646,9 @@ rt_status rt_scene_destroy(rt_scene *sc) {
     (void)hipFree(sc->adapt_mom); (void)hipFree(sc->adapt_list); (void)hipFree(sc->adapt_work); (void)hipFree(sc->adapt_counters);
     if (sc->adapt_start) (void)hipEventDestroy(sc->adapt_start);
     if (sc->adapt_stop) (void)hipEventDestroy(sc->adapt_stop);
+    (void)hipFree(sc->lens_queue);
+    if (sc->lens_start) (void)hipEventDestroy(sc->lens_start);
+    if (sc->lens_stop) (void)hipEventDestroy(sc->lens_stop);
     for (rt_scene::Feedback &f : sc->feedback) {
         if (f.done) { if (f.pending) (void)hipEventSynchronize(f.done); (void)hipEventDestroy(f.done); }
         if (f.start) (void)hipEventDestroy(f.start);
@@ -901,6 +907,30 @@ rt_status choose_traversal(rt_scene *sc, const rt_camera_data *cam, const rt_sha
     return RT_OK;
 }
 
+// Step 2 of a lens frame (rt_render_lens): the handle's walk as it stands — no re-pack, no exploring frame, nothing of the handle
+// changes — and the guarded walk only where EVERY ray origin the camera can make lies within the reach its margins were sized for.
+// A lens point is O + R (lx uh + ly vh) with unit uh, vh and lx^2 + ly^2 < 1: its distance from the pose's origin is below
+// R (|lx| + |ly|) < sqrt(2) R whatever the angle between du and dv (a caller's skewed camera, or an interpolated pose).  The pose's
+// origin lies on the segment between the two ends' origins, and the reach is a ball: both ends checked with the radius reduced by
+// sqrt(2) R cover every pose between them (a hair of slack for the rounding of the interpolated pose and of the lens point).
+bool lens_guarded(const rt_scene *sc, const rtk::KParams &P, const rtk::LensCam &C) {
+    const rt_config &cfg = sc->cfg;
+    if (!(sc->guard.ok && cfg.traversal != RT_TRAVERSAL_EXACT && P.root >= 0 && guarded_wanted(cfg, (int64_t)P.num_spheres + P.num_planes) &&
+          !(sc->guard_paused && !cfg.guard_keep)))
+        return false;
+    auto within = [&](int end, const float c[3], double reach) {
+        reach -= std::sqrt(2.0) * (double)C.radius;
+        if (!(reach > 0.0)) return false;
+        const double dx = (double)C.o[end][0] - c[0], dy = (double)C.o[end][1] - c[1], dz = (double)C.o[end][2] - c[2];
+        return dx * dx + dy * dy + dz * dz <= reach * reach * (1.0 - 1e-5);
+    };
+    for (int end = 0; end <= C.motion; ++end) {
+        if (!within(end, sc->guard.origin_center, (double)sc->guard.origin_radius)) return false;
+        if (sc->guard.num_small > 0 && !within(end, sc->guard.center, std::sqrt((double)sc->guard.d0_sq))) return false;
+    }
+    return true;
+}
+
 // Launch shape of one walk: tables in LDS or not, LDS bytes per workgroup, workgroups per CU, stack rows per lane, treelet records
 struct Shape { bool in_lds; uint32_t lds_bytes; int wgs_per_cu; int32_t stack_levels; int32_t num_top; };
 enum class Walk { Exact, ExactSimple, Guarded };
@@ -923,7 +953,9 @@ struct LaunchPlan {
 
 // Step 3 of rt_render: the launch shapes of the walks, from the handle's tables, its config and P alone (no HIP call, nothing
 // of the handle changes).  `guarded`: what choose_traversal decided; the plan may still fall back to the exact walk.
-LaunchPlan plan_launch(const rt_scene *sc, const rt_camera_data *cam, const rtk::KParams &P, bool guarded) {
+// pinhole = false (lens frames): neither sphere-only build (no lens instantiation of them: the general builds of the same walks) nor
+// the primary-visibility pass.
+LaunchPlan plan_launch(const rt_scene *sc, const rt_camera_data *cam, const rtk::KParams &P, bool guarded, bool pinhole = true) {
     const rt_config &cfg = sc->cfg;
     LaunchPlan L;
     const uint32_t waves = rtk::kBlock / rtk::kWave;
@@ -955,7 +987,7 @@ LaunchPlan plan_launch(const rt_scene *sc, const rt_camera_data *cam, const rtk:
     // The re-walk of a list keeps the general build: it is a few long paths, and those run slower in the tighter kernel
     // (headline frame: re-walk 3.1 ms instead of 1.7).
     bool exact_simple = exact.in_lds && cfg.sphere_only_kernel >= 0 && P.num_planes == 0 && sc->tex_data == nullptr && !sc->absorbing_glass &&
-                        cfg.workgroups_per_cu == 0 && P.num_spheres > 0;
+                        cfg.workgroups_per_cu == 0 && P.num_spheres > 0 && pinhole;
     if (exact_simple) {
         const uint64_t simple_bytes = (((uint64_t)P.num_tnodes + 1) * 4 + (uint64_t)P.num_spheres + ((uint64_t)P.num_spheres + 3) / 4) * 16;
         const uint64_t simple_pool = (uint64_t)(rtk::kSimpleBlock / rtk::kWave) * 8u + 16u * rtk::kConstRows;      // work ranges + the constants block
@@ -990,7 +1022,7 @@ LaunchPlan plan_launch(const rt_scene *sc, const rt_camera_data *cam, const rtk:
         // no textures, leaf boxes recomputed from the spheres; its LDS holds no material rows (all three come from global memory),
         // which pays for the wider stack rows of 1024 lanes
         const bool plain = cfg.sphere_only_kernel >= 0 && P.num_planes == 0 && sc->tex_data == nullptr && P.leaf_boxes == nullptr &&
-                           cfg.workgroups_per_cu == 0 && !sc->absorbing_glass;
+                           cfg.workgroups_per_cu == 0 && !sc->absorbing_glass && pinhole;
         if (plain && !dyn_scene && cfg.scene_in_lds != 0) {
             const uint64_t simple_bytes = ((uint64_t)P.num_internal * 5 + (uint64_t)P.num_spheres + ((uint64_t)P.num_spheres + 3) / 4) * 16;
             const uint64_t budget = kLdsLimit / 2;
@@ -1071,7 +1103,7 @@ LaunchPlan plan_launch(const rt_scene *sc, const rt_camera_data *cam, const rtk:
     L.overlap = guarded && cfg.overlap_rework >= 0 && cfg.flag_capacity == 0 && !gamma_unproven(cfg);
     // Primary visibility without a walk (rt_primary.hip.inc): the pair-node walks of render_kernel — the LDS-resident octant walk
     // with static margins, and the walk with distance-aware margins (through L1/L2) — and a camera inside the margins
-    L.prim = guarded && (L.dyn || fast.in_lds) && cfg.primary_visibility >= 0 && sc->nodes != nullptr && P.max_depth < rtk::kMaxPrimDepth &&
+    L.prim = pinhole && guarded && (L.dyn || fast.in_lds) && cfg.primary_visibility >= 0 && sc->nodes != nullptr && P.max_depth < rtk::kMaxPrimDepth &&
              camera_inside_margins(sc, cam);
     // resume table: not for paths longer than the depth field
     L.resume = guarded && cfg.resume_flagged >= 0 && P.max_depth < rtk::kMaxPrimDepth;
@@ -1146,11 +1178,23 @@ const void *trace_kernel(const LaunchPlan &L) {
     return (const void *)render_kernel<false, false>;
 }
 
-hipError_t launch(const void *kernel, uint32_t block, int grid, uint32_t lds, hipStream_t stream, const rtk::KParams &KP) {
+// … and of a lens frame (render_lens_kernel<kLds, kThreaded, kDyn, kWide>: the general builds only, plan_launch with pinhole = false)
+const void *lens_trace_kernel(const LaunchPlan &L) {
+    using rtk::render_lens_kernel;
+    if (L.walk != Walk::Guarded) return L.exact.in_lds ? (const void *)render_lens_kernel<true, true> : (const void *)render_lens_kernel<false, true>;
+    if (L.wide) return (const void *)render_lens_kernel<false, false, true, true>;
+    if (L.dyn) return (const void *)render_lens_kernel<false, false, true>;
+    if (L.fast.in_lds) return (const void *)render_lens_kernel<true, false>;
+    return (const void *)render_lens_kernel<false, false>;
+}
+
+// (lens: the second kernel argument of render_lens_kernel; null for render_kernel)
+hipError_t launch(const void *kernel, uint32_t block, int grid, uint32_t lds, hipStream_t stream, const rtk::KParams &KP, const rtk::LensCam *lens = nullptr) {
     hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     void *args[] = {(void *)&KP};
-    e = hipLaunchKernel(kernel, dim3(grid), dim3(block), args, lds, stream);
+    void *lens_args[] = {(void *)&KP, (void *)lens};
+    e = hipLaunchKernel(kernel, dim3(grid), dim3(block), lens ? lens_args : args, lds, stream);
     const hipError_t last = hipGetLastError();
     return e != hipSuccess ? e : last;
 }
@@ -1189,8 +1233,11 @@ rt_status check_sample_range(const char *what, int32_t sample_first, int32_t spp
 
 // rt_render, rt_render_tile and rt_render_samples: whole rows of a shard, or a rectangle; samples [sample_first, sample_first + spp).
 // moments (rt_render_adaptive's min_spp round; null for every other call): each pass's luminance moments are added there as well.
+// lens (rt_render_lens; null for every other call): every sample starts from the lens / moving camera (render_lens_kernel), without
+// candidate lists; the handle's own state — its walk choice and judgement, the re-pack, the view lists, what rt_last_timing reports —
+// is left as it was, and *timing gets this call's record.
 rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shard, const Tile *tile, float *d_fb_sum, void *hip_stream,
-                      int32_t sync, rt_timing *timing, int32_t sample_first = 0, float *moments = nullptr) {
+                      int32_t sync, rt_timing *timing, int32_t sample_first = 0, float *moments = nullptr, const rtk::LensCam *lens = nullptr) {
     // ---- 1. validate, fill P
     rtk::KParams P;
     rt_status st = fill_params(sc, cam, shard, P, tile);
@@ -1204,21 +1251,27 @@ rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *s
     P.fb = d_fb_sum;
     timing_out(rt_timing{}, timing);
     // what earlier frames of this handle reported about their guarded walk (no wait: whatever has landed by now)
-    if ((st = poll_feedback(sc, false)) != RT_OK) return st;
+    if (!lens && (st = poll_feedback(sc, false)) != RT_OK) return st;
     const size_t fb_bytes = (size_t)P.local_rows * P.row_w * 3 * sizeof(float);
     if (P.local_rows == 0) return RT_OK;
     if (P.spp <= 0 || P.max_depth <= 0) {     // the reference's loops add nothing: all-zero sums
         HIP_TRY(hipMemsetAsync(d_fb_sum, 0, fb_bytes, stream));
         if (sync) HIP_TRY(hipStreamSynchronize(stream));
-        sc->timed = false;
+        if (!lens) sc->timed = false;
         return RT_OK;
     }
 
     // ---- 2. the walk, the tree re-packed for a far camera
     bool guarded = false, exploring = false;
-    if ((st = choose_traversal(sc, cam, shard, tile, stream, P, guarded, exploring)) != RT_OK) return st;
+    if (lens) {
+        // (rt_render_samples's refusals, which choose_traversal makes for it)
+        if (cfg.kernel == RT_KERNEL_WAVEFRONT) return fail(RT_ERR_UNSUPPORTED, "RT_KERNEL_WAVEFRONT was an experiment and has been retired: not in this library");
+        if (cfg.wide_nodes > 0) return fail(RT_ERR_UNSUPPORTED, "rt_config.wide_nodes = 1 was an experiment and has been retired: not in this library");
+        guarded = lens_guarded(sc, P, *lens);
+    }
+    else if ((st = choose_traversal(sc, cam, shard, tile, stream, P, guarded, exploring)) != RT_OK) return st;
     // ---- 3. launch shapes
-    LaunchPlan plan = plan_launch(sc, cam, P, guarded);
+    LaunchPlan plan = plan_launch(sc, cam, P, guarded, lens == nullptr);
     guarded = plan.guarded();
     // ---- 4. buffers.  Samples per pass (rt_accel.h, plan_passes): as many as the workspace budget admits (rt_config.workspace_bytes,
     // default a sixteenth of the device; 12 bytes per sample), at least 64 where the work-index bound allows, and never more than the
@@ -1246,8 +1299,9 @@ rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *s
         return wgs < 1 ? 1 : wgs;
     };
     const int wgs = grid_for(trace_shape), rework_wgs = grid_for(plan.exact);
-    const void *trace = trace_kernel(plan);
-    const void *rework = plan.exact.in_lds ? (const void *)rtk::render_kernel<true, true> : (const void *)rtk::render_kernel<false, true>;
+    const void *trace = lens ? lens_trace_kernel(plan) : trace_kernel(plan);
+    const void *rework = lens ? (plan.exact.in_lds ? (const void *)rtk::render_lens_kernel<true, true> : (const void *)rtk::render_lens_kernel<false, true>)
+                              : (plan.exact.in_lds ? (const void *)rtk::render_kernel<true, true> : (const void *)rtk::render_kernel<false, true>);
     // registers and scratch of the dominant (trace) kernel as the loaded code object reports them → rt_timing
     uint32_t trace_vgprs = 0, trace_scratch = 0;
     {
@@ -1258,7 +1312,14 @@ rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *s
         }
     }
 
-    HIP_TRY(hipMemsetAsync(sc->queue, 0, kQueueWords * 4, stream));
+    // (a lens frame counts in a counter block of its own: rt_last_timing reads the last rt_render's from the handle's block)
+    uint32_t *queue = sc->queue;
+    if (lens) {
+        if (!sc->lens_queue) HIP_TRY(hipMalloc((void **)&sc->lens_queue, kQueueWords * 4));
+        queue = sc->lens_queue;
+        P.stats = queue + kQueueStats;
+    }
+    HIP_TRY(hipMemsetAsync(queue, 0, kQueueWords * 4, stream));
     const bool overlap = plan.overlap;
     // an early return between the fork to the second stream and the join must not leave that stream running unobserved
     struct JoinOnExit {
@@ -1269,20 +1330,28 @@ rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *s
         }
     } join_guard{sc, stream};
     rt_scene::Feedback *feedback = nullptr;
-    if ((st = acquire_feedback(sc, &feedback)) != RT_OK) return st;
-    HIP_TRY(hipEventRecord(feedback->start, stream));
-    HIP_TRY(hipEventRecord(sc->ev_start, stream));
+    if (lens) {
+        if (!sc->lens_start) {
+            HIP_TRY(hipEventCreate(&sc->lens_start));
+            HIP_TRY(hipEventCreate(&sc->lens_stop));
+        }
+        HIP_TRY(hipEventRecord(sc->lens_start, stream));
+    } else {
+        if ((st = acquire_feedback(sc, &feedback)) != RT_OK) return st;
+        HIP_TRY(hipEventRecord(feedback->start, stream));
+        HIP_TRY(hipEventRecord(sc->ev_start, stream));
+    }
     if (prim) {
         if ((st = make_view_lists(sc, cam, P, num_pixels, stream)) != RT_OK) return st;
-    } else {
+    } else if (!lens) {
         sc->cand_key.valid = false;
     }
-    while ((int)sc->pass_events.size() < 4 * (passes.passes < kTimedPasses ? passes.passes : kTimedPasses)) {
+    while (!lens && (int)sc->pass_events.size() < 4 * (passes.passes < kTimedPasses ? passes.passes : kTimedPasses)) {
         hipEvent_t e;
         HIP_TRY(hipEventCreate(&e));
         sc->pass_events.push_back(e);
     }
-    sc->timed_passes = 0;
+    if (!lens) sc->timed_passes = 0;
     if (guarded) {
         // near-first walk; samples it cannot vouch for go to the list …
         P.stack_levels = plan.fast.stack_levels;
@@ -1311,10 +1380,10 @@ rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *s
     const uint64_t waves_total = (uint64_t)wgs * (plan.block() / rtk::kWave);
     for (int pass = 0; pass < passes.passes; ++pass) {
         // samples [pass_first, pass_first + pass_count) of every pixel, traced in any order into the slab …
-        const bool timed_pass = pass < kTimedPasses;
+        const bool timed_pass = !lens && pass < kTimedPasses;
         if (timed_pass) HIP_TRY(hipEventRecord(sc->pass_events[4 * pass], stream));
         if ((st = set_pass(P, passes, pass, num_pixels, sample_first)) != RT_OK) return st;
-        P.queue = sc->queue + kQueueWork + pass;
+        P.queue = queue + kQueueWork + pass;
         P.work_list = nullptr;
         reservation(P.total_work, waves_total, P.chunk, P.taper_shift);
         if (const int forced = cfg.reserve_chunk) P.chunk = (uint32_t)(64u * (uint64_t)(forced > 0 ? forced : 1));
@@ -1328,12 +1397,12 @@ rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *s
         if (guarded) {
             // resume table: cleared per pass (1 MB of tags)
             if (P.resume_tag != nullptr) HIP_TRY(hipMemsetAsync(sc->resume_tag, 0, sizeof(uint32_t) << kResumeBits, stream));
-            P.flag_count = sc->queue + kQueueFlag + pass;
+            P.flag_count = queue + kQueueFlag + pass;
             if (overlap) HIP_TRY(hipMemsetAsync(sc->dirty, 0, (size_t)num_pixels * sizeof(uint32_t), stream));      // this pass's marks (8 MB at 1080p: microseconds)
-            P.dirty_count = sc->queue + kQueueDirty + pass;
-            P.abandon = P.bail_share != 0u ? sc->queue + kQueueAbandon + pass : nullptr;
+            P.dirty_count = queue + kQueueDirty + pass;
+            P.abandon = P.bail_share != 0u ? queue + kQueueAbandon + pass : nullptr;
             rtk::fill_consts(P);          // (everything the constants block copies is final now)
-            HIP_TRY(launch(trace, plan.block(), wgs, trace_shape.lds_bytes, stream, P));
+            HIP_TRY(launch(trace, plan.block(), wgs, trace_shape.lds_bytes, stream, P, lens));
             if (timed_pass) HIP_TRY(hipEventRecord(sc->pass_events[4 * pass + 2], stream));
             // … and are walked again in the reference's order, overwriting their slab entries
             rtk::KParams R = P;
@@ -1341,9 +1410,9 @@ rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *s
             R.k_shade = cfg.k_shade > 0 ? cfg.k_shade : 48;
             R.stack_levels = 0;
             R.num_top = plan.exact.num_top;
-            R.queue = sc->queue + kQueueRework + pass;
+            R.queue = queue + kQueueRework + pass;
             R.work_list = sc->flag_list;
-            R.work_count = sc->queue + kQueueFlag + pass;
+            R.work_count = queue + kQueueFlag + pass;
             R.work_cap = P.flag_cap;
             R.chunk = 64u;                     // a short list: finest granularity
             R.taper_shift = 0;
@@ -1361,15 +1430,15 @@ rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *s
                 // re-walk (0.2 ms at 1080p that would otherwise lengthen the re-walk's chain past the other pixels' accumulation)
                 HIP_TRY(hipStreamWaitEvent(sc->list_stream, sc->ev_fork, 0));
                 hipLaunchKernelGGL(rtk::dirty_compact_kernel, dim3((num_pixels + rtk::kDirtyPixels - 1) / rtk::kDirtyPixels), dim3(rtk::kDirtyBlock), 0, sc->list_stream,
-                                   (const uint32_t *)sc->dirty, num_pixels, sc->dirty_list, sc->queue + kQueueDirty + pass);
+                                   (const uint32_t *)sc->dirty, num_pixels, sc->dirty_list, queue + kQueueDirty + pass);
                 HIP_TRY(hipGetLastError());
                 HIP_TRY(hipEventRecord(sc->ev_listed, sc->list_stream));
                 join_guard.listing = true;
             }
-            HIP_TRY(launch(rework, (uint32_t)rtk::kBlock, rework_wgs, plan.exact.lds_bytes, rework_stream, R));
+            HIP_TRY(launch(rework, (uint32_t)rtk::kBlock, rework_wgs, plan.exact.lds_bytes, rework_stream, R, lens));
         } else {
             if (plan.walk == Walk::ExactSimple) rtk::fill_consts(P);          // (its launch constants come from the LDS block, like the guarded sphere-only build's)
-            HIP_TRY(launch(trace, plan.block(), wgs, trace_shape.lds_bytes, stream, P));
+            HIP_TRY(launch(trace, plan.block(), wgs, trace_shape.lds_bytes, stream, P, lens));
         }
         if (timed_pass) {
             if (!guarded) HIP_TRY(hipEventRecord(sc->pass_events[4 * pass + 2], stream));
@@ -1384,7 +1453,7 @@ rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *s
             HIP_TRY(hipStreamWaitEvent(sc->aux_stream, sc->ev_listed, 0));
             join_guard.listing = false;
             hipLaunchKernelGGL(rtk::accumulate_kernel<true>, acc_grid, acc_block, 0, sc->aux_stream, d_fb_sum, (const float *)sc->slab, num_pixels, P.slab_pitch,
-                               P.pass_count, pass == 0 ? 1 : 0, sc->dirty, (const uint32_t *)sc->dirty_list, (const uint32_t *)(sc->queue + kQueueDirty + pass),
+                               P.pass_count, pass == 0 ? 1 : 0, sc->dirty, (const uint32_t *)sc->dirty_list, (const uint32_t *)(queue + kQueueDirty + pass),
                                (const uint32_t *)nullptr, 0u, 0.0f, 0.0f, 0.0f, (const uint32_t *)P.abandon, 0u);
             HIP_TRY(hipEventRecord(sc->ev_join, sc->aux_stream));
             // … while every other pixel is accumulated here
@@ -1410,6 +1479,45 @@ rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *s
         }
     }
     HIP_TRY(hipGetLastError());
+    if (lens) {
+        // a lens frame leaves nothing for later calls: its record goes to the caller alone
+        HIP_TRY(hipEventRecord(sc->lens_stop, stream));
+        rt_timing t{};
+        t.num_workgroups = (uint32_t)wgs;
+        t.workgroup_size = plan.block();
+        t.lds_bytes = trace_shape.lds_bytes;
+        t.scene_in_lds = trace_shape.in_lds ? 1u : 0u;
+        t.trace_launches = (uint32_t)passes.passes;
+        t.guarded = guarded ? 1u : 0u;
+        t.guard_unproven = (guarded && gamma_unproven(cfg)) ? 1u : 0u;
+        t.kernel = RT_KERNEL_MEGA;
+        t.guard_dynamic = plan.dyn ? 1u : 0u;
+        t.front_primitives = guarded ? (uint32_t)sc->guard.num_front : 0u;
+        t.wide_nodes = plan.wide ? 1u : 0u;
+        t.trace_vgprs = trace_vgprs;
+        t.trace_scratch_bytes = trace_scratch;
+        t.traced_samples = (uint64_t)num_pixels * (uint64_t)P.spp;
+        t.guard_paused = sc->guard_paused ? 1u : 0u;
+        if (sync) {
+            HIP_TRY(hipEventSynchronize(sc->lens_stop));
+            HIP_TRY(hipEventElapsedTime(&t.kernel_ms, sc->lens_start, sc->lens_stop));
+            if (guarded) {
+                std::vector<uint32_t> counts((size_t)passes.passes), gave_up((size_t)passes.passes), holes((size_t)passes.passes);
+                HIP_TRY(hipMemcpy(counts.data(), queue + kQueueFlag, counts.size() * 4, hipMemcpyDeviceToHost));
+                HIP_TRY(hipMemcpy(holes.data(), queue + kQueueHoles, holes.size() * 4, hipMemcpyDeviceToHost));
+                HIP_TRY(hipMemcpy(gave_up.data(), queue + kQueueAbandon, gave_up.size() * 4, hipMemcpyDeviceToHost));
+                for (size_t p = 0; p < counts.size(); ++p) {
+                    t.flagged_samples += counts[p] - holes[p];
+                    t.abandoned_passes += gave_up[p] != 0u ? 1u : 0u;
+                }
+            }
+            uint32_t abort_code = 0;        // (the tripwire's abort word of a developer build: in this call's own counter block)
+            HIP_TRY(hipMemcpy(&abort_code, queue + kQueueStats + 15, 4, hipMemcpyDeviceToHost));
+            if (abort_code != 0) return fail(RT_ERR_HIP, "render kernel aborted (protocol timeout, code " + std::to_string(abort_code) + ")");
+        }
+        timing_out(t, timing);
+        return RT_OK;
+    }
     HIP_TRY(hipEventRecord(sc->ev_stop, stream));
 
     // ---- 6. what the frame leaves for later calls
@@ -1459,8 +1567,10 @@ rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *s
 // candidate lists (and their key, so that a beauty frame of the same view reuses them).  No feedback slot, no re-pack, no counter
 // block, no per-pass events of rt_render: what the handle decides next, and what rt_last_timing reports, stay those of its
 // rt_render calls.
+// lens (rt_render_aov_lens): every sample's first hit from the lens / moving camera's ray, without candidate lists (those of the
+// handle stay as they are).
 rt_status aov_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shard, const Tile *tile, const rt_aov_buffers *buffers, void *hip_stream,
-                   int32_t sync, rt_timing *timing, int32_t sample_first = 0) {
+                   int32_t sync, rt_timing *timing, int32_t sample_first = 0, const rtk::LensCam *lens = nullptr) {
     // (the buffers first: a caller's mistake there is reported as such whatever else is wrong)
     if (!buffers || buffers->struct_bytes < 16u) return fail(RT_ERR_INVALID_ARG, "null AOV buffers (or struct_bytes below 16)");
     rt_aov_buffers b{};
@@ -1493,7 +1603,7 @@ rt_status aov_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shar
     bool prim = sc->guard.ok && cfg.traversal != RT_TRAVERSAL_EXACT && P.root >= 0 && guarded_wanted(cfg, (int64_t)P.num_spheres + P.num_planes) &&
                 !(sc->guard_paused && !cfg.guard_keep) && cfg.kernel != RT_KERNEL_WAVEFRONT && cfg.primary_visibility >= 0 && sc->nodes != nullptr &&
                 (sc->guard.dyn_k > 0.0f || cfg.scene_in_lds != 0);
-    if (prim && !camera_inside_margins(sc, cam)) prim = false;
+    if (prim && (lens || !camera_inside_margins(sc, cam))) prim = false;
     rtaccel::PassPlan plan;
     if ((st = reserve_slab(sc, num_pixels, P.spp, stream, plan)) != RT_OK) return st;
     const int passes = plan.passes;
@@ -1517,7 +1627,7 @@ rt_status aov_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shar
     HIP_TRY(hipMemsetAsync(sc->aov_walked, 0, sizeof(uint32_t), stream));
     if (prim) {
         if ((st = make_view_lists(sc, cam, P, num_pixels, stream)) != RT_OK) return st;
-    } else {
+    } else if (!lens) {
         sc->cand_key.valid = false;         // (as rt_render does: the next call with lists makes them anew)
     }
     for (int pass = 0; pass < passes; ++pass) {
@@ -1532,13 +1642,15 @@ rt_status aov_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shar
         // (1) the records of pixels without a list (every record, without lists) through the reference-order walk
         const uint32_t units = prim ? (num_pixels + 3u) / 4u : (P.total_work + 255u) / 256u;
         const uint32_t rgrid = std::min<uint32_t>(units, (uint32_t)sc->num_cus * 8u);
-        if (prim) hipLaunchKernelGGL(rtk::aov_resolve_kernel<false>, dim3(rgrid), dim3(256), 0, stream, P, sc->aov_walked);
+        if (lens) hipLaunchKernelGGL(rtk::aov_resolve_lens_kernel, dim3(rgrid), dim3(256), 0, stream, P, *lens);
+        else if (prim) hipLaunchKernelGGL(rtk::aov_resolve_kernel<false>, dim3(rgrid), dim3(256), 0, stream, P, sc->aov_walked);
         else hipLaunchKernelGGL(rtk::aov_resolve_kernel<true>, dim3(rgrid), dim3(256), 0, stream, P, sc->aov_walked);
         HIP_TRY(hipGetLastError());
         if (timed_pass) HIP_TRY(hipEventRecord(sc->aov_events[3 * pass + 2], stream));
         // (2) … added to the pixel's sums in sample order
         const dim3 acc_grid((num_pixels + 64 * rtk::kAccWaves - 1) / (64 * rtk::kAccWaves)), acc_block(64 * rtk::kAccWaves);
-        hipLaunchKernelGGL(rtk::aov_accumulate_kernel, acc_grid, acc_block, 0, stream, P, out, pass == 0 ? 1 : 0, sc->aov_walked);
+        if (lens) hipLaunchKernelGGL(rtk::aov_accumulate_lens_kernel, acc_grid, acc_block, 0, stream, P, *lens, out, pass == 0 ? 1 : 0, sc->aov_walked);
+        else hipLaunchKernelGGL(rtk::aov_accumulate_kernel, acc_grid, acc_block, 0, stream, P, out, pass == 0 ? 1 : 0, sc->aov_walked);
         HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipEventRecord(sc->aov_stop, stream));
@@ -1781,6 +1893,102 @@ void rt_adaptive_params_init(rt_adaptive_params *p) {
 rt_status rt_render_adaptive(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shard, const rt_adaptive_params *params, float *d_fb_sum,
                              int32_t *d_spp, float *d_moments, void *hip_stream, int32_t sync, rt_timing *timing) {
     return adaptive_impl(sc, cam, shard, params, d_fb_sum, d_spp, d_moments, hip_stream, sync, timing);
+}
+
+// ---- rt_render_lens / rt_render_aov_lens / rt_lens_camera_rays (rtp_amd.h) -------------------------------------
+void rt_lens_params_init(rt_lens_params *p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->struct_bytes = (uint32_t)sizeof(*p);
+    p->lens_radius = 0.0f;
+    p->focus_distance = 10.0f;
+}
+
+namespace {
+// dot(P00 - O, cross(du, dv)) in the header's float order: 0 leaves the plane in focus undefined
+float lens_plane_dot(const rt_camera_data *c) {
+    const float *o = c->origin.e, *p = c->pixel00_loc.e, *u = c->pixel_delta_u.e, *v = c->pixel_delta_v.e;
+    const float n0 = u[1] * v[2] - u[2] * v[1], n1 = u[2] * v[0] - u[0] * v[2], n2 = u[0] * v[1] - u[1] * v[0];
+    const float e0 = p[0] - o[0], e1 = p[1] - o[1], e2 = p[2] - o[2];
+    return e0 * n0 + e1 * n1 + e2 * n2;
+}
+// the checks every lens call makes before anything is enqueued → the kernels' camera pair
+rt_status lens_setup(const char *what, const rt_camera_data *open, const rt_camera_data *close, const rt_lens_params *params, rtk::LensCam &C) {
+    const std::string w(what);
+    if (!open) return fail(RT_ERR_INVALID_ARG, w + ": null camera");
+    rt_lens_params lp;
+    rt_lens_params_init(&lp);
+    if (params) {
+        if (params->struct_bytes < 8u) return fail(RT_ERR_INVALID_ARG, w + ": rt_lens_params.struct_bytes below 8");
+        std::memcpy(&lp, params, params->struct_bytes < sizeof(lp) ? params->struct_bytes : sizeof(lp));
+    }
+    if (close && (close->image_width != open->image_width || close->image_height != open->image_height ||
+                  close->samples_per_pixel != open->samples_per_pixel || close->max_depth != open->max_depth ||
+                  std::memcmp(close->background.e, open->background.e, sizeof(open->background.e)) != 0))
+        return fail(RT_ERR_INVALID_ARG, w + ": cam_close differs from cam_open in width, height, spp, max_depth or background");
+    if (!(std::isfinite(lp.lens_radius) && lp.lens_radius >= 0.0f)) return fail(RT_ERR_INVALID_ARG, w + ": lens_radius must be finite and >= 0");
+    if (lp.lens_radius > 0.0f) {
+        if (!(std::isfinite(lp.focus_distance) && lp.focus_distance > 0.0f))
+            return fail(RT_ERR_INVALID_ARG, w + ": focus_distance must be positive and finite");
+        if (lens_plane_dot(open) == 0.0f || (close && lens_plane_dot(close) == 0.0f))
+            return fail(RT_ERR_INVALID_ARG, w + ": the camera origin lies in its image plane (dot(P00 - O, n) == 0)");
+    }
+    C = rtk::LensCam{};
+    const rt_camera_data *ends[2] = {open, close ? close : open};
+    for (int e = 0; e < 2; ++e)
+        for (int k = 0; k < 3; ++k) {
+            C.o[e][k] = ends[e]->origin.e[k];
+            C.p00[e][k] = ends[e]->pixel00_loc.e[k];
+            C.du[e][k] = ends[e]->pixel_delta_u.e[k];
+            C.dv[e][k] = ends[e]->pixel_delta_v.e[k];
+        }
+    C.radius = lp.lens_radius;
+    C.focus = lp.focus_distance;
+    C.motion = close ? 1 : 0;
+    C.width = open->image_width;
+    return RT_OK;
+}
+}  // namespace
+
+rt_status rt_render_lens(rt_scene *sc, const rt_camera_data *cam_open, const rt_camera_data *cam_close, const rt_lens_params *lens,
+                         const rt_shard *shard, int32_t sample_first, float *d_fb_sum, void *hip_stream, int32_t sync, rt_timing *timing) {
+    rtk::LensCam C;
+    if (const rt_status st = lens_setup("rt_render_lens", cam_open, cam_close, lens, C)) return st;
+    if (!sc) return fail(RT_ERR_INVALID_ARG, "rt_render_lens: null scene");
+    return render_impl(sc, cam_open, shard, nullptr, d_fb_sum, hip_stream, sync, timing, sample_first, nullptr, &C);
+}
+
+rt_status rt_render_aov_lens(rt_scene *sc, const rt_camera_data *cam_open, const rt_camera_data *cam_close, const rt_lens_params *lens,
+                             const rt_shard *shard, int32_t sample_first, const rt_aov_buffers *buffers, void *hip_stream, int32_t sync,
+                             rt_timing *timing) {
+    rtk::LensCam C;
+    if (const rt_status st = lens_setup("rt_render_aov_lens", cam_open, cam_close, lens, C)) return st;
+    if (!sc) return fail(RT_ERR_INVALID_ARG, "rt_render_aov_lens: null scene");
+    return aov_impl(sc, cam_open, shard, nullptr, buffers, hip_stream, sync, timing, sample_first, &C);
+}
+
+rt_status rt_lens_camera_rays(const rt_camera_data *cam_open, const rt_camera_data *cam_close, const rt_lens_params *lens, int32_t n,
+                              const int32_t *ijs, float *origins, float *directions, uint32_t *final_seed) {
+    rtk::LensCam C;
+    if (const rt_status st = lens_setup("rt_lens_camera_rays", cam_open, cam_close, lens, C)) return st;
+    if (n < 0) return fail(RT_ERR_INVALID_ARG, "rt_lens_camera_rays: negative count");
+    if (n == 0) return RT_OK;
+    if (!ijs || !origins || !directions || !final_seed) return fail(RT_ERR_INVALID_ARG, "rt_lens_camera_rays: null argument");
+    int32_t *d_ijs = nullptr;
+    float *d_o = nullptr, *d_d = nullptr;
+    uint32_t *d_s = nullptr;
+    struct Free { int32_t *&a; float *&b, *&c; uint32_t *&d; ~Free() { (void)hipFree(a); (void)hipFree(b); (void)hipFree(c); (void)hipFree(d); } } freer{d_ijs, d_o, d_d, d_s};
+    HIP_TRY(hipMalloc((void **)&d_ijs, (size_t)n * 12));
+    HIP_TRY(hipMalloc((void **)&d_o, (size_t)n * 12));
+    HIP_TRY(hipMalloc((void **)&d_d, (size_t)n * 12));
+    HIP_TRY(hipMalloc((void **)&d_s, (size_t)n * 4));
+    HIP_TRY(hipMemcpy(d_ijs, ijs, (size_t)n * 12, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(rtk::lens_ray_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, C, (const int32_t *)d_ijs, n, d_o, d_d, d_s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(origins, d_o, (size_t)n * 12, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(directions, d_d, (size_t)n * 12, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(final_seed, d_s, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return RT_OK;
 }
 
 void rt_timing_init(rt_timing *t) {

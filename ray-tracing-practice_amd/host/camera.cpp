@@ -135,8 +135,10 @@ rt_camera_data Camera::build_camera_data() const {
 
 // ---- frame driver ------------------------------------------------------------------------------
 
-void orbit_pose(const SceneParams &p, int frame, Vec3 &eye, Vec3 &target) {
-    const float t = static_cast<float>((static_cast<float>(frame) / p.num_frames) * 2.0f * M_PI);
+void orbit_pose(const SceneParams &p, int frame, Vec3 &eye, Vec3 &target) { orbit_pose_at(p, static_cast<float>(frame), eye, target); }
+
+void orbit_pose_at(const SceneParams &p, float frame_time, Vec3 &eye, Vec3 &target) {
+    const float t = static_cast<float>((frame_time / p.num_frames) * 2.0f * M_PI);
     auto pose = [t](const OrbitParams &o) {
         const float r = o.r0 + o.amp_r * sinf(o.w_r * t + o.phase_r);
         const float z = o.z0 + o.amp_z * sinf(o.w_z * t + o.phase_z);

@@ -115,6 +115,8 @@ private:
 struct SceneParams;
 // Eye / look-at for frame n of num_frames (src/camera.cu:301-315).
 void orbit_pose(const SceneParams &p, int frame, Vec3 &eye, Vec3 &target);
+// … the same orbit at a fractional frame (the shutter of rtp_main --motion-blur); orbit_pose(n) is orbit_pose_at((float)n)
+void orbit_pose_at(const SceneParams &p, float frame_time, Vec3 &eye, Vec3 &target);
 
 // gpu_render (src/camera.cu:290-349): per frame BinarySaver + orbit camera + render, printing
 // "n \t ms \t W*H*sqrt_spp^2".  The scene must already be bound.  aov (rtp_main --gpu --aov): each frame's first-hit AOVs
@@ -133,6 +135,9 @@ bool write_aov_file(const std::string &path, int32_t width, int32_t height, int3
 // Animation driver beyond the reference: frames dealt round-robin to num_devices GPUs, saver
 // arithmetic on the device, file output overlapped with the next frame.  Same files, byte for byte.
 void gpu_render_pipelined(const SceneParams &params, const rt_scene_desc &desc, int num_devices);
+// rtp_main --gpu --lens R:F / --motion-blur S: the orbit frame after frame on one GPU through rt_render_lens (shutter S: open at frame
+// n, closed at n + S; 0: no motion), saved with rt_tonemap; aov / denoise from rt_render_aov_lens
+void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const rt_lens_params &lens, float shutter, bool aov, bool denoise);
 // rtp_main --gpu --adaptive: the orbit frame after frame on one GPU, each frame through rt_render_adaptive and rt_tonemap_spp
 void gpu_render_adaptive(const SceneParams &params, const rt_scene_desc &desc, const rt_adaptive_params &ap);
 

@@ -72,8 +72,12 @@ void rtp_host_scene_config(const rtp_host_scene *s, rtp_config_info *out) {
 }
 
 void rtp_host_frame_camera(const rtp_host_scene *s, int32_t frame, rt_camera_data *out) {
+    rtp_host_frame_camera_at(s, static_cast<float>(frame), out);      // (orbit_pose(n) is orbit_pose_at((float)n))
+}
+
+void rtp_host_frame_camera_at(const rtp_host_scene *s, float frame_time, rt_camera_data *out) {
     rtp::Vec3 eye, target;
-    rtp::orbit_pose(s->params, frame, eye, target);
+    rtp::orbit_pose_at(s->params, frame_time, eye, target);
     rtp::Camera cam(s->params.height, s->params.width, nullptr, eye, target);
     cam.vfov = s->params.fov_degrees;
     cam.samples_per_pixel = s->params.sqrt_spp * s->params.sqrt_spp;

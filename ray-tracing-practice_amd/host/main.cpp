@@ -3,6 +3,7 @@
 // description.  --cpu is the reference's single-threaded CPU loop: this build ships no CPU
 // render path (its CPU restatement lives under oracle/ as a test checker only), so --cpu fails
 // loudly instead of silently rendering on the host.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <iostream>
@@ -37,6 +38,49 @@ int main(int argc, char *argv[]) {
         if (std::string(argv[a]) == "--aov") aov = true;
         if (std::string(argv[a]) == "--denoise") denoise = true;
         if (std::string(argv[a]) == "--denoise-temporal") temporal = true;
+    }
+    // extension: `--gpu --lens R:F` (thin lens of radius R focused at distance F) and / or `--gpu --motion-blur S` (shutter open from
+    // frame n to n + S, 0 < S <= 1): every frame through rt_render_lens on one GPU, the same saver bytes (--aov / --denoise from
+    // rt_render_aov_lens).  The temporal filter's reprojection assumes a pinhole: not with --denoise-temporal; nor with --adaptive,
+    // --devices, --shard or RTP_DEVICES.
+    {
+        bool lens_on = false, motion_on = false, lens_bad = false;
+        rt_lens_params lens;
+        rt_lens_params_init(&lens);
+        float shutter = 0.0f;
+        bool others = getenv("RTP_DEVICES") != nullptr;
+        for (int a = 2; a < argc; ++a) {
+            const std::string arg = argv[a];
+            if (arg == "--denoise-temporal" || arg == "--adaptive" || arg == "--devices" || arg == "--shard") others = true;
+            if (arg == "--lens") {
+                lens_on = true;
+                float r = 0, f = 0;
+                char tail = 0;
+                if (a + 1 >= argc || sscanf(argv[a + 1], "%f:%f%c", &r, &f, &tail) != 2 || !(r >= 0.0f) || !(f > 0.0f) || !std::isfinite(r) ||
+                    !std::isfinite(f))
+                    lens_bad = true;
+                lens.lens_radius = r;
+                lens.focus_distance = f;
+            }
+            if (arg == "--motion-blur") {
+                motion_on = true;
+                char tail = 0;
+                if (a + 1 >= argc || sscanf(argv[a + 1], "%f%c", &shutter, &tail) != 1 || !(shutter > 0.0f && shutter <= 1.0f)) lens_bad = true;
+            }
+        }
+        if (lens_on || motion_on) {
+            if (lens_bad) {
+                std::cerr << "rtp_main: --lens takes R:F (R >= 0, F > 0, finite) and --motion-blur takes S (0 < S <= 1)\n";
+                return 99;
+            }
+            if (others) {
+                std::cerr << "rtp_main: --lens / --motion-blur render frame after frame on one GPU: they cannot be combined with "
+                             "--denoise-temporal, --adaptive, --devices, --shard or RTP_DEVICES\n";
+                return 99;
+            }
+            rtp::gpu_render_lens(params, desc, lens, shutter, aov, denoise);
+            return 0;
+        }
     }
     if (denoise && temporal) {
         std::cerr << "rtp_main: --denoise and --denoise-temporal both write <frame>.denoised: choose one\n";

@@ -252,6 +252,99 @@ void gpu_render_pipelined(const SceneParams &params, const rt_scene_desc &desc, 
     for (std::thread &t : threads) t.join();
 }
 
+// ---- thin lens and open shutter (rtp_main --gpu --lens R:F --motion-blur S) ---------------------------------------
+// The orbit of gpu_render, each frame through rt_render_lens: the shutter opens at frame n and closes at n + shutter (0: no motion),
+// the lens has radius lens.lens_radius.  Saved through rt_tonemap with the frame's divisor — the bytes gpu_render's saver writes for
+// these sums.  aov / denoise as in gpu_render, from rt_render_aov_lens.
+void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const rt_lens_params &lens, float shutter, bool aov, bool denoise) {
+    rt_scene *scene = nullptr;
+    RTP_CHECK(rt_scene_create(&desc, &scene));
+    const size_t num_pixels = static_cast<size_t>(params.width) * params.height;
+    float *d_fb = nullptr, *d_denoised = nullptr;
+    uint8_t *d_rgb = nullptr;
+    void *d_workspace = nullptr;
+    const uint64_t workspace_bytes = denoise ? rt_denoise_workspace_bytes(params.width, params.height) : 0;
+    RTP_CHECK(rt_device_alloc(num_pixels * 3 * sizeof(float), reinterpret_cast<void **>(&d_fb)));
+    RTP_CHECK(rt_device_alloc(num_pixels * 3, reinterpret_cast<void **>(&d_rgb)));
+    rt_aov_buffers aov_bufs;
+    rt_aov_buffers_init(&aov_bufs);
+    std::vector<float> h_albedo, h_normal, h_depth, h_denoised;
+    std::vector<uint32_t> h_hits;
+    if (aov || denoise) {
+        RTP_CHECK(rt_device_alloc(num_pixels * 12, reinterpret_cast<void **>(&aov_bufs.albedo_sum)));
+        RTP_CHECK(rt_device_alloc(num_pixels * 12, reinterpret_cast<void **>(&aov_bufs.normal_sum)));
+        RTP_CHECK(rt_device_alloc(num_pixels * 4, reinterpret_cast<void **>(&aov_bufs.depth_sum)));
+        RTP_CHECK(rt_device_alloc(num_pixels * 4, reinterpret_cast<void **>(&aov_bufs.hit_count)));
+    }
+    if (denoise) {
+        RTP_CHECK(rt_device_alloc(workspace_bytes, &d_workspace));
+        RTP_CHECK(rt_device_alloc(num_pixels * 3 * sizeof(float), reinterpret_cast<void **>(&d_denoised)));
+        h_denoised.resize(num_pixels * 3);
+    }
+    auto camera_at = [&](float t) {
+        Vec3 eye, target;
+        orbit_pose_at(params, t, eye, target);
+        Camera camera(params.height, params.width, nullptr, eye, target);
+        camera.vfov = params.fov_degrees;
+        camera.samples_per_pixel = params.sqrt_spp * params.sqrt_spp;
+        camera.max_depth = params.max_depth;
+        camera.background_color = Vec3(0, 0, 0);
+        return camera.build_camera_data();
+    };
+    PendingFile file;
+    file.width = params.width;
+    file.height = params.height;
+    file.rgb.resize(num_pixels * 3);
+    for (int n = 0; n < params.num_frames; ++n) {
+        const std::string filename = frame_filename(params.output_pattern, n);
+        const rt_camera_data cam = camera_at(static_cast<float>(n));
+        const rt_camera_data close = camera_at(static_cast<float>(n) + shutter);
+        const rt_camera_data *cam_close = shutter > 0.0f ? &close : nullptr;
+        const auto t0 = std::chrono::steady_clock::now();
+        RTP_CHECK(rt_render_lens(scene, &cam, cam_close, &lens, nullptr, 0, d_fb, nullptr, 1, nullptr));
+        RTP_CHECK(rt_tonemap(d_fb, d_rgb, static_cast<int64_t>(num_pixels) * 3, params.sqrt_spp, nullptr));
+        RTP_CHECK(rt_copy_to_host(file.rgb.data(), d_rgb, num_pixels * 3));
+        file.path = filename;
+        write_binary_frame(file);
+        const auto t1 = std::chrono::steady_clock::now();
+        const float ms = std::chrono::duration<float, std::milli>(t1 - t0).count();
+        const long long total_rays = static_cast<long long>(params.width) * params.height * params.sqrt_spp * params.sqrt_spp;
+        std::cout << n << "\t" << ms << "\t" << total_rays << "\n";
+        if (aov || denoise) {          // (outside the frame's timed span, as in gpu_render)
+            RTP_CHECK(rt_render_aov_lens(scene, &cam, cam_close, &lens, nullptr, 0, &aov_bufs, nullptr, 1, nullptr));
+            if (aov) {
+                h_albedo.resize(num_pixels * 3); h_normal.resize(num_pixels * 3); h_depth.resize(num_pixels); h_hits.resize(num_pixels);
+                RTP_CHECK(rt_copy_to_host(h_albedo.data(), aov_bufs.albedo_sum, num_pixels * 12));
+                RTP_CHECK(rt_copy_to_host(h_normal.data(), aov_bufs.normal_sum, num_pixels * 12));
+                RTP_CHECK(rt_copy_to_host(h_depth.data(), aov_bufs.depth_sum, num_pixels * 4));
+                RTP_CHECK(rt_copy_to_host(h_hits.data(), aov_bufs.hit_count, num_pixels * 4));
+                if (!write_aov_file(filename + ".aov", params.width, params.height, cam.samples_per_pixel, h_albedo.data(), h_normal.data(),
+                                    h_depth.data(), h_hits.data())) {
+                    std::cerr << "cannot write " << filename << ".aov\n";
+                    std::exit(99);
+                }
+            }
+            if (denoise) {
+                RTP_CHECK(rt_denoise(d_fb, &aov_bufs, params.width, params.height, cam.samples_per_pixel, nullptr, d_workspace, workspace_bytes,
+                                     d_denoised, nullptr));
+                RTP_CHECK(rt_copy_to_host(h_denoised.data(), d_denoised, num_pixels * 3 * sizeof(float)));
+                BinarySaver out(params.sqrt_spp, filename + ".denoised");
+                out.set_format(params.width, params.height);
+                for (size_t p = 0; p < num_pixels; ++p) out.write_color(Vec3(h_denoised[3 * p], h_denoised[3 * p + 1], h_denoised[3 * p + 2]));
+            }
+        }
+    }
+    rt_device_free(d_fb);
+    rt_device_free(d_rgb);
+    rt_device_free(aov_bufs.albedo_sum);
+    rt_device_free(aov_bufs.normal_sum);
+    rt_device_free(aov_bufs.depth_sum);
+    rt_device_free(aov_bufs.hit_count);
+    rt_device_free(d_workspace);
+    rt_device_free(d_denoised);
+    RTP_CHECK(rt_scene_destroy(scene));
+}
+
 // ---- adaptive sampling (rtp_main --gpu --adaptive) ----------------------------------------------------------
 // The orbit of gpu_render, each frame rendered by rt_render_adaptive and saved through rt_tonemap_spp: every pixel's bytes are the
 // saver arithmetic with its own sample count as the divisor (the mean of its samples).  Prints frame, milliseconds and the samples

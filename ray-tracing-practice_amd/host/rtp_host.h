@@ -41,6 +41,8 @@ void rtp_host_scene_config(const rtp_host_scene *s, rtp_config_info *out);
 /* CameraData of frame n as gpu_render/cpu_render set it up (orbit pose, spp = sqrt_spp^2,
  * black background). */
 void rtp_host_frame_camera(const rtp_host_scene *s, int32_t frame, rt_camera_data *out);
+/* The same at a fractional frame of the orbit (rt_render_lens's shutter); frame_time = n gives rtp_host_frame_camera's camera. */
+void rtp_host_frame_camera_at(const rtp_host_scene *s, float frame_time, rt_camera_data *out);
 /* Camera::build_camera_data for an explicit pose (z-up). */
 void rtp_host_make_camera(int32_t width, int32_t height, float vfov_degrees, const float eye[3], const float target[3],
                           const float background[3], int32_t samples_per_pixel, int32_t max_depth, rt_camera_data *out);

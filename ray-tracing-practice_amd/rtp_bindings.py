@@ -120,6 +120,46 @@ def adaptive_params(**params):
     return p
 
 
+class LensParams(C.Structure):
+    """rt_lens_params (include/rtp_amd.h): an IN structure of the caller's size — struct_bytes is set on construction; the other
+    fields are 0 until rt_lens_params_init (lens_params()) fills the defaults."""
+    _fields_ = [("struct_bytes", C.c_uint32), ("lens_radius", C.c_float), ("focus_distance", C.c_float)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_bytes = C.sizeof(LensParams)
+
+
+def lens_params(**params):
+    """rt_lens_params with the library's defaults, then the given fields (lens_radius, focus_distance)."""
+    p = LensParams()
+    amd_lib().rt_lens_params_init(C.byref(p))
+    for k, v in params.items():
+        if k not in dict(LensParams._fields_):
+            raise RtError(f"rt_lens_params has no field {k}")
+        setattr(p, k, v)
+    return p
+
+
+def _lens_struct(lens):
+    """None → NULL (the defaults); a LensParams as it is; a dict → lens_params(**dict)."""
+    if lens is None:
+        return None
+    return C.byref(lens if isinstance(lens, LensParams) else lens_params(**lens))
+
+
+def lens_camera_rays(cam_open, cam_close, lens, ijs):
+    """rt_lens_camera_rays: ijs (n, 3) int32 (i, j, s) → (origins (n, 3) float32, directions (n, 3) float32, final seeds (n,) uint32)."""
+    ijs = np.ascontiguousarray(ijs, dtype=np.int32).reshape(-1, 3)
+    n = ijs.shape[0]
+    org = np.empty((n, 3), dtype=np.float32)
+    dirs = np.empty((n, 3), dtype=np.float32)
+    seeds = np.empty(n, dtype=np.uint32)
+    _check(amd_lib().rt_lens_camera_rays(C.byref(cam_open), C.byref(cam_close) if cam_close is not None else None, _lens_struct(lens), n,
+                                         ijs.ctypes.data, org.ctypes.data, dirs.ctypes.data, seeds.ctypes.data), "rt_lens_camera_rays")
+    return org, dirs, seeds
+
+
 TRAVERSAL_AUTO, TRAVERSAL_EXACT, TRAVERSAL_GUARDED = 0, 1, 2
 BUILD_HOST_SAH, BUILD_DEVICE_LBVH = 0, 1
 KERNEL_AUTO, KERNEL_MEGA, KERNEL_WAVEFRONT = 0, 1, 2
@@ -171,6 +211,7 @@ RTP_AMD_SYMBOLS = [
     "rt_denoise_params_init", "rt_denoise_workspace_bytes", "rt_denoise",
     "rt_render_samples", "rt_render_aov_samples", "rt_denoise_history_bytes", "rt_denoise_temporal",
     "rt_adaptive_params_init", "rt_render_adaptive", "rt_tonemap_spp",
+    "rt_lens_params_init", "rt_render_lens", "rt_render_aov_lens", "rt_lens_camera_rays",
 ]
 
 _host = None
@@ -195,6 +236,7 @@ def host_lib():
         lib.rtp_host_scene_desc.argtypes = [C.c_void_p, C.POINTER(SceneDesc)]
         lib.rtp_host_scene_config.argtypes = [C.c_void_p, C.POINTER(ConfigInfo)]
         lib.rtp_host_frame_camera.argtypes = [C.c_void_p, C.c_int32, C.POINTER(CameraData)]
+        lib.rtp_host_frame_camera_at.argtypes = [C.c_void_p, C.c_float, C.POINTER(CameraData)]
         lib.rtp_host_make_camera.argtypes = [C.c_int32, C.c_int32, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float),
                                              C.POINTER(C.c_float), C.c_int32, C.c_int32, C.POINTER(CameraData)]
         lib.rtp_host_quantize.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
@@ -264,6 +306,15 @@ def amd_lib():
             lib.rt_denoise_history_bytes.restype = C.c_uint64
             lib.rt_denoise_temporal.argtypes = [C.c_void_p, C.POINTER(AovBuffers), C.POINTER(CameraData), C.POINTER(DenoiseParams),
                                                 C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        if hasattr(lib, "rt_render_lens"):
+            lib.rt_lens_params_init.argtypes = [C.POINTER(LensParams)]
+            lib.rt_lens_params_init.restype = None
+            lib.rt_render_lens.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(CameraData), C.POINTER(LensParams), C.POINTER(Shard),
+                                           C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(Timing)]
+            lib.rt_render_aov_lens.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(CameraData), C.POINTER(LensParams),
+                                               C.POINTER(Shard), C.c_int32, C.POINTER(AovBuffers), C.c_void_p, C.c_int32, C.POINTER(Timing)]
+            lib.rt_lens_camera_rays.argtypes = [C.POINTER(CameraData), C.POINTER(CameraData), C.POINTER(LensParams), C.c_int32, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p]
         lib.rt_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         lib.rt_last_timing.argtypes = [C.c_void_p, C.POINTER(Timing)]
         lib.rt_timing_init.argtypes = [C.POINTER(Timing)]
@@ -334,6 +385,12 @@ class HostScene:
     def frame_camera(self, frame=0):
         cam = CameraData()
         host_lib().rtp_host_frame_camera(self._h, frame, C.byref(cam))
+        return cam
+
+    def frame_camera_at(self, frame_time):
+        """The orbit's camera at a fractional frame (rtp_host_frame_camera_at)."""
+        cam = CameraData()
+        host_lib().rtp_host_frame_camera_at(self._h, frame_time, C.byref(cam))
         return cam
 
     def nodes_array(self):
@@ -764,6 +821,67 @@ class DeviceScene:
             for d in dev:
                 lib.rt_device_free(d)
         return fb, spp, mom, t
+
+    def render_lens(self, cam_open, d_fb_ptr, cam_close=None, lens=None, shard=None, stream=None, sync=True, sample_first=0):
+        """rt_render_lens: cam_close None = no motion; lens None (defaults), a LensParams or a dict of its fields.  Returns the
+        rt_timing of this call."""
+        t = Timing()
+        self._apply_config()
+        _check(amd_lib().rt_render_lens(self._h, C.byref(cam_open), C.byref(cam_close) if cam_close is not None else None, _lens_struct(lens),
+                                        C.byref(shard) if shard else None, sample_first, C.c_void_p(d_fb_ptr), C.c_void_p(stream or 0),
+                                        1 if sync else 0, C.byref(t)), "rt_render_lens")
+        return t
+
+    def render_lens_to_host(self, cam_open, cam_close=None, lens=None, shard=None, sample_first=0):
+        """rt_render_lens through a fresh device buffer: (rows, width, 3) float32 sums and the rt_timing."""
+        lib = amd_lib()
+        rows = lib.rt_shard_rows(cam_open.image_height, C.byref(shard) if shard else None)
+        fb = np.empty((rows, cam_open.image_width, 3), dtype=np.float32)
+        d = C.c_void_p()
+        _check(lib.rt_device_alloc(fb.nbytes or 12, C.byref(d)), "rt_device_alloc")
+        try:
+            t = self.render_lens(cam_open, d.value, cam_close=cam_close, lens=lens, shard=shard, sample_first=sample_first)
+            _check(lib.rt_copy_to_host(fb.ctypes.data, d, fb.nbytes), "rt_copy_to_host")
+        finally:
+            lib.rt_device_free(d)
+        return fb, t
+
+    def render_aov_lens(self, cam_open, ptrs, cam_close=None, lens=None, shard=None, stream=None, sync=True, sample_first=0):
+        """rt_render_aov_lens.  ptrs as render_aov takes them.  Returns the rt_timing."""
+        b = _aov_struct(ptrs)
+        t = Timing()
+        self._apply_config()
+        _check(amd_lib().rt_render_aov_lens(self._h, C.byref(cam_open), C.byref(cam_close) if cam_close is not None else None,
+                                            _lens_struct(lens), C.byref(shard) if shard else None, sample_first, C.byref(b),
+                                            C.c_void_p(stream or 0), 1 if sync else 0, C.byref(t)), "rt_render_aov_lens")
+        return t
+
+    def render_aov_lens_to_host(self, cam_open, cam_close=None, lens=None, shard=None, sample_first=0):
+        """rt_render_aov_lens through fresh device buffers: (the dict render_aov_to_host returns, rt_timing)."""
+        lib = amd_lib()
+        w, rows = cam_open.image_width, lib.rt_shard_rows(cam_open.image_height, C.byref(shard) if shard else None)
+        pixels = max(w, 0) * max(rows, 0)
+        dev = {}
+        try:
+            for key, field, dtype, per in AOV_CHANNELS:
+                d = C.c_void_p()
+                _check(lib.rt_device_alloc(pixels * per * 4 or 4, C.byref(d)), "rt_device_alloc")
+                dev[key] = d
+            t = self.render_aov_lens(cam_open, {k: d.value for k, d in dev.items()}, cam_close=cam_close, lens=lens, shard=shard,
+                                     sample_first=sample_first)
+            out = {}
+            for key, field, dtype, per in AOV_CHANNELS:
+                a = np.empty((rows, w, per) if per > 1 else (rows, w), dtype=dtype)
+                _check(lib.rt_copy_to_host(a.ctypes.data, dev[key], a.nbytes), "rt_copy_to_host")
+                out[key] = a
+        finally:
+            for d in dev.values():
+                lib.rt_device_free(d)
+        return out, t
+
+    def lens_camera_rays(self, cam_open, cam_close, lens, ijs):
+        """rt_lens_camera_rays (the module function lens_camera_rays: no scene involved, the current device)."""
+        return lens_camera_rays(cam_open, cam_close, lens, ijs)
 
     def last_kernel_ms(self):
         ms = C.c_float()
