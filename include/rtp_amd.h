@@ -579,6 +579,65 @@ rt_status rt_render_aov_lens(rt_scene *scene, const rt_camera_data *cam_open, co
 rt_status rt_lens_camera_rays(const rt_camera_data *cam_open, const rt_camera_data *cam_close, const rt_lens_params *lens,
                               int32_t n, const int32_t *ijs, float *origins, float *directions, uint32_t *final_seed);
 
+/* ---- next-event estimation: direct light sampling of emissive spheres with MIS ---------------------------------
+ * rt_render_samples with one light sample at every diffuse event, combined with the path's own (BSDF) sample by multiple importance
+ * sampling.  The estimator has rt_render's expectation; float32 throughout, in the order written, nothing fused, division and sqrtf
+ * correctly rounded.  dot(a, b) = (a0*b0 + a1*b1) + a2*b2; random_float(s): s = wang_hash(s), (float)s / 2^32.
+ *   Emitter table (built on a handle's first rt_render_nee and kept): the spheres, in sphere order, with radius > 0 whose material's
+ *     emit components are all finite and >= 0 and not all 0.  w_i = (e0 + e1 + e2) * r^2, summed in double; cdf_i = (float)(prefix
+ *     sum through i / total), the last one 1; pmf_i = cdf_i - cdf_{i-1} in float (cdf_{-1} = 0): the probability the pick below
+ *     gives.  Emissive planes and other emitters are found by the path alone (weight 1).
+ *   Streams: the path draws exactly what rt_render_samples draws, from the same seed.  The light samples draw from their own state,
+ *     nee = wang_hash(wang_hash(base + s) ^ RT_NEE_STREAM_KEY), base = wang_hash(i * W + j), with random_float.
+ *   Diffuse event: a LAMBERTIAN hit, or a METAL hit whose branch draw chose the hemisphere branch, at the point x of closest-hit query
+ *     k (the camera ray is query 0), with face-forwarded normal n, albedo a (texture-modulated) and throughput beta before it is
+ *     multiplied by the attenuation.  When k + 1 < max_depth and the table is not empty, one light sample; its draws stop at the
+ *     first step that gives no contribution:
+ *     1. u = random_float(nee); e = the smallest entry with u < cdf_e; none (u == 1): no contribution.
+ *     2. (c, r) = sphere e; w = c - x; d2 = dot(w, w); rr = r * r; !(d2 > rr): none; cos_max = sqrtf(1 - rr / d2); om = 1 - cos_max;
+ *        om <= 0: none; pdf_cone = 1 / (RT_NEE_TWO_PI * om).
+ *     3. u1 = random_float(nee); cos_t = 1 - u1 * om; sin_t = sqrtf(fmaxf(0, 1 - cos_t * cos_t)); then (px, py) by rejection: repeat
+ *        px = -1 + 2 * random_float(nee), py = -1 + 2 * random_float(nee) (x first) while q2 = px*px + py*py is >= 1 or == 0;
+ *        q = sqrtf(q2), cx = px / q, cy = py / q.  len = sqrtf(d2), wn = (w0 / len, w1 / len, w2 / len); the basis of Duff et al.
+ *        2017: sg = copysignf(1, wn2), ba = -1 / (sg + wn2), bb = (wn0 * wn1) * ba,
+ *        t1 = (1 + ((sg * wn0) * wn0) * ba, sg * bb, -sg * wn0), t2 = (bb, sg + (wn1 * wn1) * ba, -wn1);
+ *        sx = sin_t * cx, sy = sin_t * cy; wl_k = (t1_k * sx + t2_k * sy) + wn_k * cos_t.
+ *     4. !(dot(wl, n) > 0): none.  Otherwise the shadow ray (x, wl): its closest hit over (0.001, 1e30) in the reference's visit order
+ *        contributes only if it is sphere e.  pb = RT_NEE_PB, pl = pmf_e * pdf_cone,
+ *        f = mis ? (pb * pl) / (pl * pl + pb * pb) : pb / pl;  contribution_k = ((beta_k * a_k) * emit_e,k) * f.
+ *   BSDF hits: the hit of the query k + 1 ray that leaves a diffuse event at x, on a sphere e of the table, adds
+ *     (beta_k * emit_k) * w_b instead of beta_k * emit_k: w_b = mis ? (pb * pb) / (pb * pb + pl * pl) : (pl > 0 ? 0 : 1), with
+ *     pl = pmf_e * pdf_cone by step 2 from x (0 where step 2 gives none).  Every other emission term — camera rays, hits after
+ *     DIELECTRIC or specular METAL events, planes, spheres outside the table — and the background keep weight 1.
+ *   Order: at each vertex the emission term first, then the vertex's light sample; sums over samples sample_first … in sample order
+ *     from 0.  Where no diffuse event takes a light sample (an empty table, a scene without diffuse surfaces) the call is
+ *     rt_render_samples bit for bit.
+ * Checks and limits: rt_render_samples's (rows of a shard only: no tiles, no rt_context); every refusal comes before anything is
+ * enqueued; RT_ERR_INVALID_ARG for params with struct_bytes below 8 or mis outside {0, 1}.  The light samples run on the
+ * reference-order walk only.  Handle state: the call leaves the handle's own decisions alone, as rt_render_lens does — its walk choice,
+ * a pause of the guarded walk, the re-pack of its tree, its cached view lists and what rt_last_timing reports; timing (may be NULL)
+ * is this call's record (kernel_ms with sync != 0). */
+#define RT_NEE_STREAM_KEY 0x4E454531u
+#define RT_NEE_TWO_PI 6.28318548f          /* (float)(2 pi) */
+#define RT_NEE_PB 0.159154937f             /* (float)(1 / (2 pi)): the density of the uniform-hemisphere direction */
+typedef struct rt_nee_params {   /* IN, grows like rt_lens_params: the library reads at most struct_bytes; < 8 = RT_ERR_INVALID_ARG */
+    uint32_t struct_bytes;       /* sizeof(rt_nee_params) as the caller compiled it */
+    int32_t  mis;                /* 1 (default): power heuristic; 0: light sampling alone (the BSDF hit of a table sphere counts 0) */
+    int32_t  reserved[2];        /* 0: room to grow */
+} rt_nee_params;
+/* Defaults into *p, struct_bytes = sizeof(rt_nee_params). */
+void rt_nee_params_init(rt_nee_params *p);
+/* rt_render_samples with next-event estimation (params NULL: defaults). */
+rt_status rt_render_nee(rt_scene *scene, const rt_camera_data *cam, const rt_nee_params *params, const rt_shard *shard, int32_t sample_first,
+                        float *d_fb_sum, void *hip_stream, int32_t sync, rt_timing *timing);
+/* Probe for tests, HOST memory: the emitter table (built if the handle has none yet).  *count = its length; the first min(cap, count)
+ * entries go to sphere_index, cdf and pmf (each may be NULL when cap is 0). */
+rt_status rt_nee_light_table(rt_scene *scene, int32_t cap, int32_t *sphere_index, float *cdf, float *pmf, int32_t *count);
+/* Probe for tests, HOST memory: rt_trace_samples for the estimator of rt_render_nee — radiance, rays (closest-hit queries, shadow rays
+ * included), the path's final RNG state and the light samples' final state per (i, j, s). */
+rt_status rt_trace_samples_nee(rt_scene *scene, const rt_camera_data *cam, const rt_nee_params *params, int32_t n, const int32_t *ijs,
+                               float *radiance, int32_t *rays, uint32_t *final_seed, uint32_t *final_nee_seed);
+
 /* Milliseconds of the most recent rt_render kernel of this scene (waits for it). */
 rt_status rt_last_kernel_ms(rt_scene *scene, float *ms);
 /* The whole rt_timing of the most recent rt_render of this scene (waits for it). */

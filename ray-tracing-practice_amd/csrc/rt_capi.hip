@@ -17,6 +17,7 @@
 #include "rt_primary.hip.inc"
 #include "rt_aov.hip.inc"
 #include "rt_adaptive.hip.inc"
+#include "rt_nee.hip.inc"
 // Developer build only (make dev → librtp_amd_dev.so, -DRTP_DEV_BUILD): the rt_debug_* entry points (exhaustive on-device checks of
 // recip / sqrt_cr / sphere_root, the device LBVH builder on its own, the tripwire, the RTP_STATS counters) at the end of this file.
 // The shipped library contains none of them.
@@ -266,6 +267,15 @@ struct rt_scene {
     // rt_render_lens: events of its own (rt_last_timing keeps reporting the last rt_render)
     hipEvent_t lens_start = nullptr, lens_stop = nullptr;
     uint32_t *lens_queue = nullptr;         // … and a counter block of its own (kQueueWords)
+    // rt_render_nee (rt_nee.hip.inc): the emitter table, made by the handle's first call (host copy + device columns), its events and
+    // its work counters (one per pass)
+    bool nee_built = false;
+    std::vector<int32_t> nee_index;
+    std::vector<float> nee_cdf, nee_pmf;
+    int32_t *nee_index_dev = nullptr;
+    float *nee_cdf_dev = nullptr, *nee_pmf_dev = nullptr;
+    uint32_t *nee_queue = nullptr;
+    hipEvent_t nee_start = nullptr, nee_stop = nullptr;
 };
 
 namespace {
@@ -647,6 +657,9 @@ rt_status rt_scene_destroy(rt_scene *sc) {
     if (sc->adapt_start) (void)hipEventDestroy(sc->adapt_start);
     if (sc->adapt_stop) (void)hipEventDestroy(sc->adapt_stop);
     (void)hipFree(sc->lens_queue);
+    (void)hipFree(sc->nee_index_dev); (void)hipFree(sc->nee_cdf_dev); (void)hipFree(sc->nee_pmf_dev); (void)hipFree(sc->nee_queue);
+    if (sc->nee_start) (void)hipEventDestroy(sc->nee_start);
+    if (sc->nee_stop) (void)hipEventDestroy(sc->nee_stop);
     if (sc->lens_start) (void)hipEventDestroy(sc->lens_start);
     if (sc->lens_stop) (void)hipEventDestroy(sc->lens_stop);
     for (rt_scene::Feedback &f : sc->feedback) {
@@ -1988,6 +2001,240 @@ rt_status rt_lens_camera_rays(const rt_camera_data *cam_open, const rt_camera_da
     HIP_TRY(hipMemcpy(origins, d_o, (size_t)n * 12, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(directions, d_d, (size_t)n * 12, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(final_seed, d_s, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+// ---- rt_render_nee / rt_nee_light_table / rt_trace_samples_nee (rtp_amd.h) ---------------------------------------
+void rt_nee_params_init(rt_nee_params *p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->struct_bytes = (uint32_t)sizeof(*p);
+    p->mis = 1;
+}
+
+namespace {
+rt_status nee_setup(const char *what, const rt_nee_params *params, int32_t &mis) {
+    const std::string w(what);
+    rt_nee_params np;
+    rt_nee_params_init(&np);
+    if (params) {
+        if (params->struct_bytes < 8u) return fail(RT_ERR_INVALID_ARG, w + ": rt_nee_params.struct_bytes below 8");
+        std::memcpy(&np, params, params->struct_bytes < sizeof(np) ? params->struct_bytes : sizeof(np));
+    }
+    if (np.mis != 0 && np.mis != 1) return fail(RT_ERR_INVALID_ARG, w + ": mis must be 0 or 1");
+    mis = np.mis;
+    return RT_OK;
+}
+
+// The emitter table of the header, from the handle's own device tables (read back once: rt_scene_create keeps no host copy of them)
+rt_status nee_table_ensure(rt_scene *sc) {
+    if (sc->nee_built) return RT_OK;
+    const int32_t ns = sc->num_spheres, nm = sc->num_materials;
+    std::vector<float4> spheres((size_t)ns), materials((size_t)nm * 3);
+    std::vector<int32_t> smat((size_t)ns);
+    if (ns > 0) {
+        HIP_TRY(hipMemcpy(spheres.data(), sc->spheres, (size_t)ns * sizeof(float4), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(smat.data(), sc->sphere_mat, (size_t)ns * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    if (nm > 0) HIP_TRY(hipMemcpy(materials.data(), sc->materials, materials.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    std::vector<int32_t> index;
+    std::vector<double> weight;
+    for (int32_t i = 0; i < ns; ++i) {
+        const float r = spheres[(size_t)i].w;
+        const int32_t m = smat[(size_t)i];
+        if (!(r > 0.0f) || m < 0 || m >= nm) continue;
+        const float4 e = materials[(size_t)m * 3 + 1];
+        const float ev[3] = {e.x, e.y, e.z};
+        bool ok = true, lit = false;
+        for (float c : ev) {
+            if (!(std::isfinite(c) && c >= 0.0f)) ok = false;
+            if (c > 0.0f) lit = true;
+        }
+        if (!ok || !lit) continue;
+        index.push_back(i);
+        weight.push_back(((double)e.x + (double)e.y + (double)e.z) * ((double)r * (double)r));
+    }
+    const size_t n = index.size();
+    std::vector<float> cdf(n), pmf(n);
+    double total = 0.0;
+    for (double x : weight) total += x;
+    double run = 0.0;
+    for (size_t k = 0; k < n; ++k) {
+        run += weight[k];
+        cdf[k] = k + 1 == n ? 1.0f : (float)(run / total);
+        pmf[k] = cdf[k] - (k == 0 ? 0.0f : cdf[k - 1]);
+    }
+    if (n > 0) {
+        if (const rt_status st = upload(index, (void **)&sc->nee_index_dev)) return st;
+        if (const rt_status st = upload(cdf, (void **)&sc->nee_cdf_dev)) return st;
+        if (const rt_status st = upload(pmf, (void **)&sc->nee_pmf_dev)) return st;
+    }
+    sc->nee_index = std::move(index);
+    sc->nee_cdf = std::move(cdf);
+    sc->nee_pmf = std::move(pmf);
+    sc->nee_built = true;
+    return RT_OK;
+}
+
+rtk::NeeTable nee_table_of(const rt_scene *sc, int32_t mis) {
+    rtk::NeeTable T;
+    T.index = sc->nee_index_dev;
+    T.cdf = sc->nee_cdf_dev;
+    T.pmf = sc->nee_pmf_dev;
+    T.count = (int32_t)sc->nee_index.size();
+    T.mis = mis;
+    return T;
+}
+
+// rt_render_nee: the passes of render_impl (plan_passes, the slab, accumulate_kernel in sample order) with nee_render_kernel as the
+// trace launch; nothing of the handle's walk machinery is touched
+rt_status render_nee_impl(rt_scene *sc, const rt_camera_data *cam, int32_t mis, const rt_shard *shard, int32_t sample_first, float *d_fb_sum,
+                          void *hip_stream, int32_t sync, rt_timing *timing) {
+    rtk::KParams P;
+    rt_status st = fill_params(sc, cam, shard, P);
+    if (st != RT_OK) return st;
+    if ((st = check_sample_range("rt_render_nee", sample_first, P.spp)) != RT_OK) return st;
+    if ((st = check_device(sc)) != RT_OK) return st;
+    if (!d_fb_sum) return fail(RT_ERR_INVALID_ARG, "null framebuffer");
+    if ((st = timing_check(timing)) != RT_OK) return st;
+    if (sc->cfg.kernel == RT_KERNEL_WAVEFRONT) return fail(RT_ERR_UNSUPPORTED, "RT_KERNEL_WAVEFRONT was an experiment and has been retired: not in this library");
+    if (sc->cfg.wide_nodes > 0) return fail(RT_ERR_UNSUPPORTED, "rt_config.wide_nodes = 1 was an experiment and has been retired: not in this library");
+    hipStream_t stream = (hipStream_t)hip_stream;
+    timing_out(rt_timing{}, timing);
+    const size_t fb_bytes = (size_t)P.local_rows * P.row_w * 3 * sizeof(float);
+    if (P.local_rows == 0) return RT_OK;
+    if (P.spp <= 0 || P.max_depth <= 0) {
+        HIP_TRY(hipMemsetAsync(d_fb_sum, 0, fb_bytes, stream));
+        if (sync) HIP_TRY(hipStreamSynchronize(stream));
+        return RT_OK;
+    }
+    if ((st = nee_table_ensure(sc)) != RT_OK) return st;
+    const rtk::NeeTable T = nee_table_of(sc, mis);
+    P.fb = d_fb_sum;
+    const uint32_t num_pixels = (uint32_t)P.local_rows * (uint32_t)P.row_w;
+    rtaccel::PassPlan passes;
+    if ((st = reserve_slab(sc, num_pixels, P.spp, stream, passes)) != RT_OK) return st;
+    P.slab = sc->slab;
+    P.num_pixels = num_pixels;
+    P.slab_pitch = slab_pitch_of(passes.pass_size);
+    P.cand = nullptr;
+    P.order = nullptr;
+    const void *kernel = (const void *)rtk::nee_render_kernel;
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, rtk::kNeeBlock, 0) != hipSuccess || per_cu < 1) {
+        (void)hipGetLastError();
+        per_cu = 1;
+    }
+    hipFuncAttributes attr;
+    uint32_t vgprs = 0, scratch = 0;
+    if (hipFuncGetAttributes(&attr, kernel) == hipSuccess) {
+        vgprs = (uint32_t)attr.numRegs;
+        scratch = (uint32_t)attr.localSizeBytes;
+    }
+    if (!sc->nee_queue) HIP_TRY(hipMalloc((void **)&sc->nee_queue, kMaxPasses * 4));
+    if (!sc->nee_start) {
+        HIP_TRY(hipEventCreate(&sc->nee_start));
+        HIP_TRY(hipEventCreate(&sc->nee_stop));
+    }
+    HIP_TRY(hipMemsetAsync(sc->nee_queue, 0, kMaxPasses * 4, stream));
+    HIP_TRY(hipEventRecord(sc->nee_start, stream));
+    const int wgs = sc->num_cus * per_cu;
+    int first_grid = 0;
+    const uint32_t acc_blocks = (num_pixels + 64 * rtk::kAccWaves - 1) / (64 * rtk::kAccWaves);
+    for (int pass = 0; pass < passes.passes; ++pass) {
+        if ((st = set_pass(P, passes, pass, num_pixels, sample_first)) != RT_OK) return st;
+        P.queue = sc->nee_queue + pass;
+        const uint32_t need = (P.total_work + rtk::kNeeChunk - 1) / rtk::kNeeChunk;          // waves that can get work at all
+        int grid = wgs;
+        if ((uint64_t)grid * (rtk::kNeeBlock / rtk::kWave) > need) grid = (int)((need + rtk::kNeeBlock / rtk::kWave - 1) / (rtk::kNeeBlock / rtk::kWave));
+        if (grid < 1) grid = 1;
+        hipLaunchKernelGGL(rtk::nee_render_kernel, dim3(grid), dim3(rtk::kNeeBlock), 0, stream, P, T);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(rtk::accumulate_kernel<false>, dim3(acc_blocks), dim3(64 * rtk::kAccWaves), 0, stream, d_fb_sum, (const float *)sc->slab, num_pixels,
+                           P.slab_pitch, P.pass_count, pass == 0 ? 1 : 0, (uint32_t *)nullptr, (const uint32_t *)nullptr, (const uint32_t *)nullptr,
+                           (const uint32_t *)nullptr, (uint32_t)rtk::kCandWords, P.bg[0], P.bg[1], P.bg[2]);
+        HIP_TRY(hipGetLastError());
+        if (pass == 0) first_grid = grid;
+    }
+    HIP_TRY(hipEventRecord(sc->nee_stop, stream));
+    rt_timing t{};
+    t.num_workgroups = (uint32_t)first_grid;
+    t.workgroup_size = (uint32_t)rtk::kNeeBlock;
+    t.trace_launches = (uint32_t)passes.passes;
+    t.kernel = RT_KERNEL_MEGA;
+    t.trace_vgprs = vgprs;
+    t.trace_scratch_bytes = scratch;
+    t.traced_samples = (uint64_t)num_pixels * (uint64_t)P.spp;
+    t.guard_paused = sc->guard_paused ? 1u : 0u;
+    if (sync) {
+        HIP_TRY(hipEventSynchronize(sc->nee_stop));
+        HIP_TRY(hipEventElapsedTime(&t.kernel_ms, sc->nee_start, sc->nee_stop));
+        HIP_TRY(hipEventElapsedTime(&t.trace_ms, sc->nee_start, sc->nee_stop));
+    }
+    timing_out(t, timing);
+    return RT_OK;
+}
+}  // namespace
+
+rt_status rt_render_nee(rt_scene *sc, const rt_camera_data *cam, const rt_nee_params *params, const rt_shard *shard, int32_t sample_first,
+                        float *d_fb_sum, void *hip_stream, int32_t sync, rt_timing *timing) {
+    int32_t mis = 1;
+    if (const rt_status st = nee_setup("rt_render_nee", params, mis)) return st;
+    if (!sc) return fail(RT_ERR_INVALID_ARG, "rt_render_nee: null scene");
+    return render_nee_impl(sc, cam, mis, shard, sample_first, d_fb_sum, hip_stream, sync, timing);
+}
+
+rt_status rt_nee_light_table(rt_scene *sc, int32_t cap, int32_t *sphere_index, float *cdf, float *pmf, int32_t *count) {
+    if (!sc || !count || cap < 0 || (cap > 0 && (!sphere_index || !cdf || !pmf))) return fail(RT_ERR_INVALID_ARG, "rt_nee_light_table: null argument or negative cap");
+    if (const rt_status st = check_device(sc)) return st;
+    if (const rt_status st = nee_table_ensure(sc)) return st;
+    const int32_t n = (int32_t)sc->nee_index.size();
+    *count = n;
+    const int32_t m = cap < n ? cap : n;
+    for (int32_t k = 0; k < m; ++k) {
+        sphere_index[k] = sc->nee_index[(size_t)k];
+        cdf[k] = sc->nee_cdf[(size_t)k];
+        pmf[k] = sc->nee_pmf[(size_t)k];
+    }
+    return RT_OK;
+}
+
+rt_status rt_trace_samples_nee(rt_scene *sc, const rt_camera_data *cam, const rt_nee_params *params, int32_t n, const int32_t *ijs,
+                               float *radiance, int32_t *rays, uint32_t *final_seed, uint32_t *final_nee_seed) {
+    int32_t mis = 1;
+    if (const rt_status st = nee_setup("rt_trace_samples_nee", params, mis)) return st;
+    if (n < 0 || (n > 0 && (!ijs || !radiance || !rays || !final_seed || !final_nee_seed))) return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_nee: null argument");
+    rtk::KParams P;
+    rt_status st = fill_params(sc, cam, nullptr, P);
+    if (st != RT_OK) return st;
+    if ((st = check_device(sc)) != RT_OK) return st;
+    if (n == 0) return RT_OK;
+    for (int32_t k = 0; k < n; ++k)
+        if (ijs[3 * k] < 0 || ijs[3 * k] >= cam->image_width || ijs[3 * k + 1] < 0 || ijs[3 * k + 1] >= cam->image_height || ijs[3 * k + 2] < 0)
+            return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_nee: sample coordinate out of range");
+    if ((st = nee_table_ensure(sc)) != RT_OK) return st;
+    const rtk::NeeTable T = nee_table_of(sc, mis);
+    int32_t *d_ijs = nullptr, *d_rays = nullptr;
+    float *d_rad = nullptr;
+    uint32_t *d_seed = nullptr, *d_nee = nullptr;
+    struct Free {
+        int32_t *&a, *&b; float *&c; uint32_t *&d, *&e;
+        ~Free() { (void)hipFree(a); (void)hipFree(b); (void)hipFree(c); (void)hipFree(d); (void)hipFree(e); }
+    } freer{d_ijs, d_rays, d_rad, d_seed, d_nee};
+    HIP_TRY(hipMalloc((void **)&d_ijs, (size_t)n * 12));
+    HIP_TRY(hipMalloc((void **)&d_rad, (size_t)n * 12));
+    HIP_TRY(hipMalloc((void **)&d_rays, (size_t)n * 4));
+    HIP_TRY(hipMalloc((void **)&d_seed, (size_t)n * 4));
+    HIP_TRY(hipMalloc((void **)&d_nee, (size_t)n * 4));
+    HIP_TRY(hipMemcpy(d_ijs, ijs, (size_t)n * 12, hipMemcpyHostToDevice));
+    P.probe_ijs = d_ijs; P.probe_rad = d_rad; P.probe_rays = d_rays; P.probe_seed = d_seed; P.probe_n = n;
+    hipLaunchKernelGGL(rtk::nee_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, P, T, d_nee);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(radiance, d_rad, (size_t)n * 12, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(rays, d_rays, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(final_seed, d_seed, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(final_nee_seed, d_nee, (size_t)n * 4, hipMemcpyDeviceToHost));
     return RT_OK;
 }
 

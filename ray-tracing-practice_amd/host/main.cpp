@@ -39,6 +39,45 @@ int main(int argc, char *argv[]) {
         if (std::string(argv[a]) == "--denoise") denoise = true;
         if (std::string(argv[a]) == "--denoise-temporal") temporal = true;
     }
+    // extension: `--gpu --nee [mis|light]`: every frame through rt_render_nee on one GPU (direct light sampling of the emissive spheres,
+    // combined with the path's own sample by the power heuristic, or alone), the same saver bytes; --aov / --denoise as without it
+    // (first-hit AOVs do not depend on the estimator).  Not with --lens, --motion-blur, --adaptive, --denoise-temporal, --devices,
+    // --shard or RTP_DEVICES.
+    {
+        bool nee_on = false, nee_bad = false, nee_others = getenv("RTP_DEVICES") != nullptr;
+        rt_nee_params nee;
+        rt_nee_params_init(&nee);
+        for (int a = 2; a < argc; ++a) {
+            const std::string arg = argv[a];
+            if (arg == "--lens" || arg == "--motion-blur" || arg == "--adaptive" || arg == "--denoise-temporal" || arg == "--devices" ||
+                arg == "--shard")
+                nee_others = true;
+            if (arg == "--nee") {
+                nee_on = true;
+                if (a + 1 < argc && argv[a + 1][0] != '-') {
+                    const std::string mode = argv[a + 1];
+                    if (mode == "mis") nee.mis = 1;
+                    else if (mode == "light") nee.mis = 0;
+                    else nee_bad = true;
+                }
+            }
+        }
+        if (nee_on) {
+            if (nee_bad) {
+                std::cerr << "rtp_main: --nee takes mis (default) or light\n";
+                return 99;
+            }
+            if (nee_others) {
+                std::cerr << "rtp_main: --nee renders frame after frame on one GPU: it cannot be combined with --lens, --motion-blur, "
+                             "--adaptive, --denoise-temporal, --devices, --shard or RTP_DEVICES\n";
+                return 99;
+            }
+            rt_lens_params pinhole;
+            rt_lens_params_init(&pinhole);
+            rtp::gpu_render_lens(params, desc, pinhole, 0.0f, aov, denoise, &nee);
+            return 0;
+        }
+    }
     // extension: `--gpu --lens R:F` (thin lens of radius R focused at distance F) and / or `--gpu --motion-blur S` (shutter open from
     // frame n to n + S, 0 < S <= 1): every frame through rt_render_lens on one GPU, the same saver bytes (--aov / --denoise from
     // rt_render_aov_lens).  The temporal filter's reprojection assumes a pinhole: not with --denoise-temporal; nor with --adaptive,

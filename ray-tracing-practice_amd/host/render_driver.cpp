@@ -256,7 +256,9 @@ void gpu_render_pipelined(const SceneParams &params, const rt_scene_desc &desc, 
 // The orbit of gpu_render, each frame through rt_render_lens: the shutter opens at frame n and closes at n + shutter (0: no motion),
 // the lens has radius lens.lens_radius.  Saved through rt_tonemap with the frame's divisor — the bytes gpu_render's saver writes for
 // these sums.  aov / denoise as in gpu_render, from rt_render_aov_lens.
-void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const rt_lens_params &lens, float shutter, bool aov, bool denoise) {
+// nee: the frames through rt_render_nee (rtp_main --nee), the AOVs through rt_render_aov_samples — the same first hits
+void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const rt_lens_params &lens, float shutter, bool aov, bool denoise,
+                     const rt_nee_params *nee) {
     rt_scene *scene = nullptr;
     RTP_CHECK(rt_scene_create(&desc, &scene));
     const size_t num_pixels = static_cast<size_t>(params.width) * params.height;
@@ -301,7 +303,8 @@ void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const
         const rt_camera_data close = camera_at(static_cast<float>(n) + shutter);
         const rt_camera_data *cam_close = shutter > 0.0f ? &close : nullptr;
         const auto t0 = std::chrono::steady_clock::now();
-        RTP_CHECK(rt_render_lens(scene, &cam, cam_close, &lens, nullptr, 0, d_fb, nullptr, 1, nullptr));
+        if (nee) RTP_CHECK(rt_render_nee(scene, &cam, nee, nullptr, 0, d_fb, nullptr, 1, nullptr));
+        else RTP_CHECK(rt_render_lens(scene, &cam, cam_close, &lens, nullptr, 0, d_fb, nullptr, 1, nullptr));
         RTP_CHECK(rt_tonemap(d_fb, d_rgb, static_cast<int64_t>(num_pixels) * 3, params.sqrt_spp, nullptr));
         RTP_CHECK(rt_copy_to_host(file.rgb.data(), d_rgb, num_pixels * 3));
         file.path = filename;
@@ -311,7 +314,8 @@ void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const
         const long long total_rays = static_cast<long long>(params.width) * params.height * params.sqrt_spp * params.sqrt_spp;
         std::cout << n << "\t" << ms << "\t" << total_rays << "\n";
         if (aov || denoise) {          // (outside the frame's timed span, as in gpu_render)
-            RTP_CHECK(rt_render_aov_lens(scene, &cam, cam_close, &lens, nullptr, 0, &aov_bufs, nullptr, 1, nullptr));
+            if (nee) RTP_CHECK(rt_render_aov_samples(scene, &cam, nullptr, 0, &aov_bufs, nullptr, 1, nullptr));
+            else RTP_CHECK(rt_render_aov_lens(scene, &cam, cam_close, &lens, nullptr, 0, &aov_bufs, nullptr, 1, nullptr));
             if (aov) {
                 h_albedo.resize(num_pixels * 3); h_normal.resize(num_pixels * 3); h_depth.resize(num_pixels); h_hits.resize(num_pixels);
                 RTP_CHECK(rt_copy_to_host(h_albedo.data(), aov_bufs.albedo_sum, num_pixels * 12));

@@ -160,6 +160,34 @@ def lens_camera_rays(cam_open, cam_close, lens, ijs):
     return org, dirs, seeds
 
 
+class NeeParams(C.Structure):
+    """rt_nee_params (include/rtp_amd.h): an IN structure of the caller's size — struct_bytes is set on construction; the other
+    fields are 0 until rt_nee_params_init (nee_params()) fills the defaults."""
+    _fields_ = [("struct_bytes", C.c_uint32), ("mis", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_bytes = C.sizeof(NeeParams)
+
+
+def nee_params(**params):
+    """rt_nee_params with the library's defaults (mis = 1), then the given fields."""
+    p = NeeParams()
+    amd_lib().rt_nee_params_init(C.byref(p))
+    for k, v in params.items():
+        if k not in dict(NeeParams._fields_) or k == "reserved":
+            raise RtError(f"rt_nee_params has no field {k}")
+        setattr(p, k, v)
+    return p
+
+
+def _nee_struct(params):
+    """None → NULL (the defaults); a NeeParams as it is; a dict → nee_params(**dict)."""
+    if params is None:
+        return None
+    return C.byref(params if isinstance(params, NeeParams) else nee_params(**params))
+
+
 TRAVERSAL_AUTO, TRAVERSAL_EXACT, TRAVERSAL_GUARDED = 0, 1, 2
 BUILD_HOST_SAH, BUILD_DEVICE_LBVH = 0, 1
 KERNEL_AUTO, KERNEL_MEGA, KERNEL_WAVEFRONT = 0, 1, 2
@@ -212,6 +240,7 @@ RTP_AMD_SYMBOLS = [
     "rt_render_samples", "rt_render_aov_samples", "rt_denoise_history_bytes", "rt_denoise_temporal",
     "rt_adaptive_params_init", "rt_render_adaptive", "rt_tonemap_spp",
     "rt_lens_params_init", "rt_render_lens", "rt_render_aov_lens", "rt_lens_camera_rays",
+    "rt_nee_params_init", "rt_render_nee", "rt_nee_light_table", "rt_trace_samples_nee",
 ]
 
 _host = None
@@ -315,6 +344,14 @@ def amd_lib():
                                                C.POINTER(Shard), C.c_int32, C.POINTER(AovBuffers), C.c_void_p, C.c_int32, C.POINTER(Timing)]
             lib.rt_lens_camera_rays.argtypes = [C.POINTER(CameraData), C.POINTER(CameraData), C.POINTER(LensParams), C.c_int32, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(lib, "rt_render_nee"):
+            lib.rt_nee_params_init.argtypes = [C.POINTER(NeeParams)]
+            lib.rt_nee_params_init.restype = None
+            lib.rt_render_nee.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(NeeParams), C.POINTER(Shard), C.c_int32, C.c_void_p,
+                                          C.c_void_p, C.c_int32, C.POINTER(Timing)]
+            lib.rt_nee_light_table.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
+            lib.rt_trace_samples_nee.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(NeeParams), C.c_int32, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p]
         lib.rt_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         lib.rt_last_timing.argtypes = [C.c_void_p, C.POINTER(Timing)]
         lib.rt_timing_init.argtypes = [C.POINTER(Timing)]
@@ -882,6 +919,53 @@ class DeviceScene:
     def lens_camera_rays(self, cam_open, cam_close, lens, ijs):
         """rt_lens_camera_rays (the module function lens_camera_rays: no scene involved, the current device)."""
         return lens_camera_rays(cam_open, cam_close, lens, ijs)
+
+    def render_nee(self, cam, d_fb_ptr, params=None, shard=None, stream=None, sync=True, sample_first=0):
+        """rt_render_nee: params None (defaults: mis = 1), a NeeParams or a dict of its fields.  Returns the rt_timing of this call."""
+        t = Timing()
+        self._apply_config()
+        _check(amd_lib().rt_render_nee(self._h, C.byref(cam), _nee_struct(params), C.byref(shard) if shard else None, sample_first,
+                                       C.c_void_p(d_fb_ptr), C.c_void_p(stream or 0), 1 if sync else 0, C.byref(t)), "rt_render_nee")
+        return t
+
+    def render_nee_to_host(self, cam, params=None, shard=None, sample_first=0):
+        """rt_render_nee through a fresh device buffer: (rows, width, 3) float32 sums and the rt_timing."""
+        lib = amd_lib()
+        rows = lib.rt_shard_rows(cam.image_height, C.byref(shard) if shard else None)
+        fb = np.empty((rows, cam.image_width, 3), dtype=np.float32)
+        d = C.c_void_p()
+        _check(lib.rt_device_alloc(fb.nbytes or 12, C.byref(d)), "rt_device_alloc")
+        try:
+            t = self.render_nee(cam, d.value, params=params, shard=shard, sample_first=sample_first)
+            _check(lib.rt_copy_to_host(fb.ctypes.data, d, fb.nbytes), "rt_copy_to_host")
+        finally:
+            lib.rt_device_free(d)
+        return fb, t
+
+    def nee_light_table(self):
+        """rt_nee_light_table: (sphere indices int32, cdf float32, pmf float32) of the handle's emitter table."""
+        lib = amd_lib()
+        n = C.c_int32()
+        _check(lib.rt_nee_light_table(self._h, 0, None, None, None, C.byref(n)), "rt_nee_light_table")
+        idx = np.zeros(n.value, dtype=np.int32)
+        cdf = np.zeros(n.value, dtype=np.float32)
+        pmf = np.zeros(n.value, dtype=np.float32)
+        if n.value:
+            _check(lib.rt_nee_light_table(self._h, n.value, idx.ctypes.data, cdf.ctypes.data, pmf.ctypes.data, C.byref(n)),
+                   "rt_nee_light_table")
+        return idx, cdf, pmf
+
+    def trace_samples_nee(self, cam, ijs, params=None):
+        """rt_trace_samples_nee: ijs (n, 3) → (radiance (n, 3), rays (n,), final seeds (n,), final light-sample seeds (n,))."""
+        ijs = np.ascontiguousarray(ijs, dtype=np.int32).reshape(-1, 3)
+        n = ijs.shape[0]
+        rad = np.empty((n, 3), dtype=np.float32)
+        rays = np.empty(n, dtype=np.int32)
+        seeds = np.empty(n, dtype=np.uint32)
+        nee = np.empty(n, dtype=np.uint32)
+        _check(amd_lib().rt_trace_samples_nee(self._h, C.byref(cam), _nee_struct(params), n, ijs.ctypes.data, rad.ctypes.data,
+                                              rays.ctypes.data, seeds.ctypes.data, nee.ctypes.data), "rt_trace_samples_nee")
+        return rad, rays, seeds, nee
 
     def last_kernel_ms(self):
         ms = C.c_float()
