@@ -638,6 +638,88 @@ rt_status rt_nee_light_table(rt_scene *scene, int32_t cap, int32_t *sphere_index
 rt_status rt_trace_samples_nee(rt_scene *scene, const rt_camera_data *cam, const rt_nee_params *params, int32_t n, const int32_t *ijs,
                                float *radiance, int32_t *rays, uint32_t *final_seed, uint32_t *final_nee_seed);
 
+/* ---- image-based lighting: an environment map with importance sampling -----------------------------------------
+ * rt_render_samples whose miss is a lookup in an environment map instead of cam->background, with one light sample of the map at
+ * every diffuse event, combined with the path's own (BSDF) sample by multiple importance sampling.  float32 throughout, in the
+ * order written, nothing fused, division and sqrtf correctly rounded; dot(a, b) = (a0*b0 + a1*b1) + a2*b2; random_float(s) as above;
+ * sg(x) = x >= 0 ? 1 : -1 (so sg(-0) = 1).
+ *   The map: n x n texels, OCTAHEDRAL, pole axis +y (get_sphere_uv's).  Texel (ix, iy) — rgb[(iy * n + ix) * 3 …] — covers
+ *     u in [-1 + 2 ix / n, -1 + 2 (ix + 1) / n), v likewise from iy.  decode(u, v): y = (1 - |u|) - |v|; y >= 0: (x, z) = (u, v); else
+ *     x = (1 - |v|) * sg(u), z = (1 - |u|) * sg(v); the octahedron point p = (x, y, z), the direction p normalised.
+ *     texel(d): s = (|d0| + |d1|) + |d2|; p = (d0 / s, d1 / s, d2 / s); p1 >= 0: (u, v) = (p0, p2); else u = (1 - |p2|) * sg(p0),
+ *     v = (1 - |p0|) * sg(p2); t = ((u + 1) * 0.5f) * (float)n; ix = t >= 0 ? (t < (float)n ? (int)t : n - 1) : 0 (NaN: 0); iy from v.
+ *     Lookup is the nearest texel: E(d) = rgb of texel(d).  No trigonometry on the device.
+ *   The sampling table (built by rt_env_create on the host, kept on the device): texel centre uc = -1 + (2 ix + 1) / n, vc likewise,
+ *     pc = decode(uc, vc), l2 = (pc0*pc0 + pc1*pc1) + pc2*pc2, all in double; weight w = ((r + g) + b) * (((2 / n) * (2 / n)) /
+ *     (l2 * sqrt(l2))) in double — radiance times the texel's solid angle.  Row iy's weight is the sum of its texels' in ix order, the
+ *     total the sum of the rows' in iy order.  Marginal: row_cdf_iy = (float)(prefix through iy / total), the last one 1;
+ *     row_pmf_iy = row_cdf_iy - row_cdf_{iy-1} in float (cdf_{-1} = 0).  Conditional of row iy, the same rule over its texels with the
+ *     row's weight as total; a row of weight 0 has all zeros.  total == 0 (an all-black map): the table is EMPTY.
+ *     pj(ix, iy) = row_pmf_iy * col_pmf_iy,ix (float).
+ *   Density with respect to solid angle of a direction whose octahedron point is p (|p0| + |p1| + |p2| = 1) in texel (ix, iy):
+ *     q2 = dot(p, p); q = sqrtf(q2); pl = (pj(ix, iy) * (((float)n * (float)n) * 0.25f)) * (q2 * q); 0 where the table is empty.
+ *   Parameters (rt_env_params): mode, scale, rot (rows R0, R1, R2 of the world → environment rotation: de = (dot(R0, d), dot(R1, d),
+ *     dot(R2, d))), camera_visible.  sE(d) = (scale * E0, scale * E1, scale * E2) of texel(de).
+ *   The path draws exactly what rt_render_samples draws, from the same seed.  A closest-hit query k (the camera ray is query 0) with
+ *     direction d that hits nothing adds term = beta_k * sE(d); when the ray left a diffuse event (below), mode != 0 and the table is
+ *     not empty, term * w_b instead (w_b * term_c per component): p = de / s as texel(de) computes it, pl as above,
+ *     w_b = mode == 1 ? (pb * pb) / (pb * pb + pl * pl) : (pl > 0 ? 0 : 1), pb = RT_NEE_PB.  camera_visible == 0: a query 0 miss adds
+ *     beta_0 * cam->background instead.  Emission of spheres and planes keeps weight 1.
+ *   Diffuse event: rt_render_nee's definition (LAMBERTIAN, or METAL's hemisphere branch), at the hit point x of query k with
+ *     face-forwarded normal n, albedo a and throughput beta_k before the attenuation.  When k + 1 < max_depth, mode != 0 and the
+ *     table is not empty, one light sample from its own state env = wang_hash(wang_hash(base + s) ^ RT_ENV_STREAM_KEY),
+ *     base = wang_hash(i * W + j); its draws stop at the first step that gives no contribution:
+ *     1. ua = random_float(env); iy = the smallest row with ua < row_cdf_iy; none: no contribution.
+ *     2. ub = random_float(env); ix = the smallest texel of row iy with ub < col_cdf_iy,ix; none: no contribution.
+ *     3. uc = random_float(env), ud = random_float(env); h = 2.0f / (float)n; u = ((float)ix + uc) * h - 1; v = ((float)iy + ud) * h - 1;
+ *        p = decode(u, v); q2 = dot(p, p); q = sqrtf(q2); we = (p0 / q, p1 / q, p2 / q);
+ *        wl_c = (R0_c * we0 + R1_c * we1) + R2_c * we2 (the transpose: environment → world).
+ *     4. !(dot(wl, n) > 0): none.  Otherwise the shadow ray (x, wl) over (0.001, 1e30), an occlusion query: it contributes only if it
+ *        hits NOTHING.  pl = (pj(ix, iy) * (((float)n * (float)n) * 0.25f)) * (q2 * q);
+ *        f = mode == 1 ? (pb * pl) / (pl * pl + pb * pb) : pb / pl;  contribution_c = ((beta_k,c * a_c) * (scale * E_c(ix, iy))) * f.
+ *   Order: at each vertex the emission / miss term first, then the vertex's light sample; sums over samples in sample order.
+ *   Identities, bit for bit: mode 0 with every texel equal to c and scale 1, any rot = rt_render_samples with background c; an all-black
+ *     map, any mode = rt_render_samples with background 0.
+ * Checks and limits: rt_render_nee's (rows of a shard only: no tiles, no rt_context; every refusal before anything is enqueued; the
+ * handle's walk decisions, view lists and rt_last_timing left alone).  RT_ERR_INVALID_ARG: params with struct_bytes below 8, mode
+ * outside {0, 1, 2}, scale negative or not finite, camera_visible outside {0, 1}, rot with |dot(Ra, Rb) - (a == b)| above 1e-4 for
+ * some pair of rows, a null env, an env created on another device than the scene's. */
+#define RT_ENV_STREAM_KEY 0x454E5631u
+#define RT_ENV_MAX_N 4096
+typedef struct rt_env rt_env;
+/* rgb: HOST memory, n x n x 3 floats (copied).  RT_ERR_INVALID_ARG: null pointers, n < 1, n > RT_ENV_MAX_N, a texel that is negative,
+ * NaN or infinite.  The object lives on the calling thread's current device; it is read-only afterwards and may be shared by any
+ * number of scenes of that device and destroyed before or after them (not while a render that uses it is in flight). */
+rt_status rt_env_create(const float *rgb, int32_t n, rt_env **out_env);
+rt_status rt_env_destroy(rt_env *env);
+typedef struct rt_env_params {   /* IN, grows like rt_nee_params: the library reads at most struct_bytes; < 8 = RT_ERR_INVALID_ARG */
+    uint32_t struct_bytes;       /* sizeof(rt_env_params) as the caller compiled it */
+    int32_t  mode;               /* 0: the path alone; 1 (default): MIS by the power heuristic; 2: light sampling alone */
+    float    scale;              /* 1 (default): multiplies the map's radiance; finite, >= 0 */
+    float    rot[9];             /* identity (default): rows of the world → environment rotation */
+    int32_t  camera_visible;     /* 1 (default); 0: camera rays that miss add cam->background instead (compositing) */
+    int32_t  reserved[3];        /* 0: room to grow */
+} rt_env_params;
+/* Defaults into *p, struct_bytes = sizeof(rt_env_params). */
+void rt_env_params_init(rt_env_params *p);
+/* rt_render_samples lit by the environment (params NULL: defaults). */
+rt_status rt_render_env(rt_scene *scene, const rt_camera_data *cam, const rt_env *env, const rt_env_params *params, const rt_shard *shard,
+                        int32_t sample_first, float *d_fb_sum, void *hip_stream, int32_t sync, rt_timing *timing);
+/* Probe for tests, HOST memory: the sampling table as the device holds it (read back).  *count = n, or 0 for an empty table; row_cdf and
+ * row_pmf get n floats; col_cdf and col_pmf the n floats of row `row`'s conditional (0 <= row < n).  Any output may be NULL. */
+rt_status rt_env_table(const rt_env *env, int32_t row, float *row_cdf, float *row_pmf, float *col_cdf, float *col_pmf, int32_t *count);
+/* Probe for tests, HOST memory: n directions (3 n floats) through the DEVICE's lookup (no rotation): texel = iy * n + ix, radiance
+ * (3 n floats, unscaled) and pl per direction. */
+rt_status rt_env_lookup(const rt_env *env, int32_t n, const float *directions, int32_t *texel, float *radiance, float *pl);
+/* Probe for tests, HOST memory: rt_trace_samples for the estimator of rt_render_env — radiance, rays (closest-hit queries plus shadow
+ * rays, one each), the path's final RNG state and the light samples' final state per (i, j, s). */
+rt_status rt_trace_samples_env(rt_scene *scene, const rt_camera_data *cam, const rt_env *env, const rt_env_params *params, int32_t n,
+                               const int32_t *ijs, float *radiance, int32_t *rays, uint32_t *final_seed, uint32_t *final_env_seed);
+/* Host helper (no device, host libm; not part of the bit-exact contract): a lat-long image (w x h x 3 floats, row 0 at the +y pole,
+ * column by get_sphere_uv's u: phi = atan2(-z, x) + pi, u = phi / 2 pi; v = acos(y) / pi from the top) resampled into out (n x n x 3):
+ * each texel the mean of the nearest lat-long pixels at a 4 x 4 grid of points inside it. */
+rt_status rt_env_from_equirect(const float *rgb, int32_t w, int32_t h, int32_t n, float *out);
+
 /* Milliseconds of the most recent rt_render kernel of this scene (waits for it). */
 rt_status rt_last_kernel_ms(rt_scene *scene, float *ms);
 /* The whole rt_timing of the most recent rt_render of this scene (waits for it). */

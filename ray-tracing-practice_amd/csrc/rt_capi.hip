@@ -18,6 +18,7 @@
 #include "rt_aov.hip.inc"
 #include "rt_adaptive.hip.inc"
 #include "rt_nee.hip.inc"
+#include "rt_env.hip.inc"
 // Developer build only (make dev → librtp_amd_dev.so, -DRTP_DEV_BUILD): the rt_debug_* entry points (exhaustive on-device checks of
 // recip / sqrt_cr / sphere_root, the device LBVH builder on its own, the tripwire, the RTP_STATS counters) at the end of this file.
 // The shipped library contains none of them.
@@ -276,6 +277,9 @@ struct rt_scene {
     float *nee_cdf_dev = nullptr, *nee_pmf_dev = nullptr;
     uint32_t *nee_queue = nullptr;
     hipEvent_t nee_start = nullptr, nee_stop = nullptr;
+    // rt_render_env (rt_env.hip.inc): its events and its work counters (one per pass); the environment is an object of its own
+    uint32_t *env_queue = nullptr;
+    hipEvent_t env_start = nullptr, env_stop = nullptr;
 };
 
 namespace {
@@ -660,6 +664,9 @@ rt_status rt_scene_destroy(rt_scene *sc) {
     (void)hipFree(sc->nee_index_dev); (void)hipFree(sc->nee_cdf_dev); (void)hipFree(sc->nee_pmf_dev); (void)hipFree(sc->nee_queue);
     if (sc->nee_start) (void)hipEventDestroy(sc->nee_start);
     if (sc->nee_stop) (void)hipEventDestroy(sc->nee_stop);
+    (void)hipFree(sc->env_queue);
+    if (sc->env_start) (void)hipEventDestroy(sc->env_start);
+    if (sc->env_stop) (void)hipEventDestroy(sc->env_stop);
     if (sc->lens_start) (void)hipEventDestroy(sc->lens_start);
     if (sc->lens_stop) (void)hipEventDestroy(sc->lens_stop);
     for (rt_scene::Feedback &f : sc->feedback) {
@@ -2235,6 +2242,375 @@ rt_status rt_trace_samples_nee(rt_scene *sc, const rt_camera_data *cam, const rt
     HIP_TRY(hipMemcpy(rays, d_rays, (size_t)n * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(final_seed, d_seed, (size_t)n * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(final_nee_seed, d_nee, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+// ---- rt_env / rt_render_env / rt_env_table / rt_env_lookup / rt_trace_samples_env (rtp_amd.h) ---------------------
+// An environment: the texels (r, g, b, pj) and both cdf tables on the device it was created on.  The table is built here, on the
+// host, in double (the header's sums, in its order) — once per environment.
+struct rt_env {
+    int device = 0;
+    int32_t n = 0;
+    bool empty = true;                 // an all-black map: no light samples
+    float4 *texels = nullptr;          // n * n
+    float *row_cdf = nullptr;          // n
+    float *col_cdf = nullptr;          // n * n
+};
+
+void rt_env_params_init(rt_env_params *p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->struct_bytes = (uint32_t)sizeof(*p);
+    p->mode = 1;
+    p->scale = 1.0f;
+    p->rot[0] = p->rot[4] = p->rot[8] = 1.0f;
+    p->camera_visible = 1;
+}
+
+namespace {
+// (u, v) → the octahedron point, in double: the header's decode
+void env_decode_d(double u, double v, double p[3]) {
+    const double y = (1.0 - std::fabs(u)) - std::fabs(v);
+    p[1] = y;
+    if (y >= 0.0) {
+        p[0] = u;
+        p[2] = v;
+    } else {
+        p[0] = (1.0 - std::fabs(v)) * (u >= 0.0 ? 1.0 : -1.0);
+        p[2] = (1.0 - std::fabs(u)) * (v >= 0.0 ? 1.0 : -1.0);
+    }
+}
+
+// cdf_i = (float)(prefix / total), the last one 1, over n weights; a total of 0 gives zeros
+void env_cdf(const double *w, int32_t n, double total, float *cdf) {
+    double run = 0.0;
+    for (int32_t k = 0; k < n; ++k) {
+        run += w[k];
+        cdf[k] = total > 0.0 ? (k + 1 == n ? 1.0f : (float)(run / total)) : 0.0f;
+    }
+}
+
+rt_status env_setup(const char *what, const rt_env_params *params, rt_env_params &np) {
+    const std::string w(what);
+    rt_env_params_init(&np);
+    if (params) {
+        if (params->struct_bytes < 8u) return fail(RT_ERR_INVALID_ARG, w + ": rt_env_params.struct_bytes below 8");
+        std::memcpy(&np, params, params->struct_bytes < sizeof(np) ? params->struct_bytes : sizeof(np));
+    }
+    if (np.mode < 0 || np.mode > 2) return fail(RT_ERR_INVALID_ARG, w + ": mode must be 0, 1 or 2");
+    if (!(std::isfinite(np.scale) && np.scale >= 0.0f)) return fail(RT_ERR_INVALID_ARG, w + ": scale must be finite and not negative");
+    if (np.camera_visible != 0 && np.camera_visible != 1) return fail(RT_ERR_INVALID_ARG, w + ": camera_visible must be 0 or 1");
+    for (int a = 0; a < 3; ++a)
+        for (int b = a; b < 3; ++b) {
+            double d = 0.0;
+            for (int k = 0; k < 3; ++k) d += (double)np.rot[3 * a + k] * (double)np.rot[3 * b + k];
+            if (!(std::fabs(d - (a == b ? 1.0 : 0.0)) <= 1e-4)) return fail(RT_ERR_INVALID_ARG, w + ": the rows of rot are not orthonormal");
+        }
+    return RT_OK;
+}
+
+rt_status env_check(const char *what, const rt_env *env) {
+    if (!env) return fail(RT_ERR_INVALID_ARG, std::string(what) + ": null environment");
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess) return fail(RT_ERR_HIP, "hipGetDevice failed");
+    if (cur != env->device) return fail(RT_ERR_INVALID_ARG, std::string(what) + ": the environment was created on another device than the calling thread's current one");
+    return RT_OK;
+}
+
+rtk::EnvDev env_dev_of(const rt_env *env, const rt_env_params &np) {
+    rtk::EnvDev E;
+    E.texels = env->texels;
+    E.row_cdf = env->row_cdf;
+    E.col_cdf = env->col_cdf;
+    E.n = env->n;
+    E.sampled = (np.mode != 0 && !env->empty) ? 1 : 0;
+    E.mis = np.mode == 1 ? 1 : 0;
+    E.camera_visible = np.camera_visible;
+    E.scale = np.scale;
+    for (int k = 0; k < 9; ++k) E.rot[k] = np.rot[k];
+    E.dens = ((float)env->n * (float)env->n) * 0.25f;
+    E.h = 2.0f / (float)env->n;
+    return E;
+}
+}  // namespace
+
+rt_status rt_env_create(const float *rgb, int32_t n, rt_env **out_env) {
+    if (!rgb || !out_env) return fail(RT_ERR_INVALID_ARG, "rt_env_create: null argument");
+    *out_env = nullptr;
+    if (n < 1 || n > RT_ENV_MAX_N) return fail(RT_ERR_INVALID_ARG, "rt_env_create: n must be 1 … " + std::to_string(RT_ENV_MAX_N));
+    const size_t nn = (size_t)n * (size_t)n;
+    for (size_t k = 0; k < nn * 3; ++k)
+        if (!(std::isfinite(rgb[k]) && rgb[k] >= 0.0f)) return fail(RT_ERR_INVALID_ARG, "rt_env_create: a texel is negative, NaN or infinite");
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(RT_ERR_NO_DEVICE, "rt_env_create: no current HIP device");
+    }
+    // texel weights (radiance x solid angle) and the rows' sums, in double
+    std::vector<double> w(nn), row_w((size_t)n);
+    const double cell = (2.0 / (double)n) * (2.0 / (double)n);
+    double total = 0.0;
+    for (int32_t iy = 0; iy < n; ++iy) {
+        const double vc = -1.0 + (double)(2 * iy + 1) / (double)n;
+        double row = 0.0;
+        for (int32_t ix = 0; ix < n; ++ix) {
+            const double uc = -1.0 + (double)(2 * ix + 1) / (double)n;
+            double p[3];
+            env_decode_d(uc, vc, p);
+            const double l2 = (p[0] * p[0] + p[1] * p[1]) + p[2] * p[2];
+            const float *t = rgb + ((size_t)iy * n + ix) * 3;
+            const double wt = (((double)t[0] + (double)t[1]) + (double)t[2]) * (cell / (l2 * std::sqrt(l2)));
+            w[(size_t)iy * n + ix] = wt;
+            row += wt;
+        }
+        row_w[(size_t)iy] = row;
+        total += row;
+    }
+    std::vector<float> row_cdf((size_t)n), col_cdf(nn);
+    env_cdf(row_w.data(), n, total, row_cdf.data());
+    for (int32_t iy = 0; iy < n; ++iy) env_cdf(w.data() + (size_t)iy * n, n, total > 0.0 ? row_w[(size_t)iy] : 0.0, col_cdf.data() + (size_t)iy * n);
+    std::vector<float4> texels(nn);
+    for (int32_t iy = 0; iy < n; ++iy) {
+        const float rp = row_cdf[(size_t)iy] - (iy == 0 ? 0.0f : row_cdf[(size_t)iy - 1]);
+        for (int32_t ix = 0; ix < n; ++ix) {
+            const size_t k = (size_t)iy * n + ix;
+            const float cp = col_cdf[k] - (ix == 0 ? 0.0f : col_cdf[k - 1]);
+            texels[k] = make_float4(rgb[3 * k], rgb[3 * k + 1], rgb[3 * k + 2], rp * cp);
+        }
+    }
+    rt_env *env = new (std::nothrow) rt_env();
+    if (!env) return fail(RT_ERR_OUT_OF_MEMORY, "rt_env_create: out of host memory");
+    env->device = dev;
+    env->n = n;
+    env->empty = !(total > 0.0);
+    rt_status st = upload(texels, (void **)&env->texels);
+    if (st == RT_OK) st = upload(row_cdf, (void **)&env->row_cdf);
+    if (st == RT_OK) st = upload(col_cdf, (void **)&env->col_cdf);
+    if (st != RT_OK) {
+        (void)rt_env_destroy(env);
+        return st;
+    }
+    *out_env = env;
+    return RT_OK;
+}
+
+rt_status rt_env_destroy(rt_env *env) {
+    if (!env) return RT_OK;
+    (void)hipFree(env->texels);
+    (void)hipFree(env->row_cdf);
+    (void)hipFree(env->col_cdf);
+    delete env;
+    return RT_OK;
+}
+
+rt_status rt_env_table(const rt_env *env, int32_t row, float *row_cdf, float *row_pmf, float *col_cdf, float *col_pmf, int32_t *count) {
+    if (const rt_status st = env_check("rt_env_table", env)) return st;
+    const int32_t n = env->n;
+    if (row < 0 || row >= n) return fail(RT_ERR_INVALID_ARG, "rt_env_table: row out of range");
+    std::vector<float> r((size_t)n), c((size_t)n);
+    HIP_TRY(hipMemcpy(r.data(), env->row_cdf, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(c.data(), env->col_cdf + (size_t)row * n, (size_t)n * 4, hipMemcpyDeviceToHost));
+    for (int32_t k = 0; k < n; ++k) {
+        if (row_cdf) row_cdf[k] = r[(size_t)k];
+        if (row_pmf) row_pmf[k] = r[(size_t)k] - (k == 0 ? 0.0f : r[(size_t)k - 1]);
+        if (col_cdf) col_cdf[k] = c[(size_t)k];
+        if (col_pmf) col_pmf[k] = c[(size_t)k] - (k == 0 ? 0.0f : c[(size_t)k - 1]);
+    }
+    if (count) *count = env->empty ? 0 : n;
+    return RT_OK;
+}
+
+rt_status rt_env_lookup(const rt_env *env, int32_t n, const float *directions, int32_t *texel, float *radiance, float *pl) {
+    if (n < 0 || (n > 0 && (!directions || !texel || !radiance || !pl))) return fail(RT_ERR_INVALID_ARG, "rt_env_lookup: null argument or negative count");
+    if (const rt_status st = env_check("rt_env_lookup", env)) return st;
+    if (n == 0) return RT_OK;
+    float *d_dir = nullptr, *d_rad = nullptr, *d_pl = nullptr;
+    int32_t *d_tex = nullptr;
+    struct Free {
+        float *&a, *&b, *&c; int32_t *&d;
+        ~Free() { (void)hipFree(a); (void)hipFree(b); (void)hipFree(c); (void)hipFree(d); }
+    } freer{d_dir, d_rad, d_pl, d_tex};
+    HIP_TRY(hipMalloc((void **)&d_dir, (size_t)n * 12));
+    HIP_TRY(hipMalloc((void **)&d_rad, (size_t)n * 12));
+    HIP_TRY(hipMalloc((void **)&d_pl, (size_t)n * 4));
+    HIP_TRY(hipMalloc((void **)&d_tex, (size_t)n * 4));
+    HIP_TRY(hipMemcpy(d_dir, directions, (size_t)n * 12, hipMemcpyHostToDevice));
+    rt_env_params np;
+    rt_env_params_init(&np);
+    const rtk::EnvDev E = env_dev_of(env, np);
+    hipLaunchKernelGGL(rtk::env_lookup_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, E, n, (const float *)d_dir, d_tex, d_rad, d_pl);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(texel, d_tex, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(radiance, d_rad, (size_t)n * 12, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(pl, d_pl, (size_t)n * 4, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
+rt_status rt_env_from_equirect(const float *rgb, int32_t w, int32_t h, int32_t n, float *out) {
+    if (!rgb || !out || w < 1 || h < 1 || n < 1 || n > RT_ENV_MAX_N) return fail(RT_ERR_INVALID_ARG, "rt_env_from_equirect: null argument or size out of range");
+    const int sub = 4;
+    const double pi = 3.14159265358979323846;
+    for (int32_t iy = 0; iy < n; ++iy)
+        for (int32_t ix = 0; ix < n; ++ix) {
+            double acc[3] = {0.0, 0.0, 0.0};
+            for (int b = 0; b < sub; ++b)
+                for (int a = 0; a < sub; ++a) {
+                    const double u = -1.0 + 2.0 * ((double)ix + ((double)a + 0.5) / sub) / (double)n;
+                    const double v = -1.0 + 2.0 * ((double)iy + ((double)b + 0.5) / sub) / (double)n;
+                    double p[3];
+                    env_decode_d(u, v, p);
+                    const double len = std::sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]);
+                    const double theta = std::acos(std::fmin(1.0, std::fmax(-1.0, p[1] / len)));
+                    const double phi = std::atan2(-p[2], p[0]) + pi;
+                    int32_t px = (int32_t)(phi / (2.0 * pi) * (double)w), py = (int32_t)(theta / pi * (double)h);
+                    px = px < 0 ? 0 : (px >= w ? w - 1 : px);
+                    py = py < 0 ? 0 : (py >= h ? h - 1 : py);
+                    const float *t = rgb + ((size_t)py * w + px) * 3;
+                    for (int c = 0; c < 3; ++c) acc[c] += (double)t[c];
+                }
+            for (int c = 0; c < 3; ++c) out[((size_t)iy * n + ix) * 3 + c] = (float)(acc[c] / (double)(sub * sub));
+        }
+    return RT_OK;
+}
+
+namespace {
+// rt_render_env: the passes of render_impl (plan_passes, the slab, accumulate_kernel in sample order) with env_render_kernel as the
+// trace launch; nothing of the handle's walk machinery is touched
+rt_status render_env_impl(rt_scene *sc, const rt_camera_data *cam, const rt_env *env, const rt_env_params &np, const rt_shard *shard,
+                          int32_t sample_first, float *d_fb_sum, void *hip_stream, int32_t sync, rt_timing *timing) {
+    rtk::KParams P;
+    rt_status st = fill_params(sc, cam, shard, P);
+    if (st != RT_OK) return st;
+    if ((st = check_sample_range("rt_render_env", sample_first, P.spp)) != RT_OK) return st;
+    if ((st = check_device(sc)) != RT_OK) return st;
+    if (env->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_render_env: the environment was created on another device than the scene");
+    if (!d_fb_sum) return fail(RT_ERR_INVALID_ARG, "null framebuffer");
+    if ((st = timing_check(timing)) != RT_OK) return st;
+    if (sc->cfg.kernel == RT_KERNEL_WAVEFRONT) return fail(RT_ERR_UNSUPPORTED, "RT_KERNEL_WAVEFRONT was an experiment and has been retired: not in this library");
+    if (sc->cfg.wide_nodes > 0) return fail(RT_ERR_UNSUPPORTED, "rt_config.wide_nodes = 1 was an experiment and has been retired: not in this library");
+    hipStream_t stream = (hipStream_t)hip_stream;
+    timing_out(rt_timing{}, timing);
+    const size_t fb_bytes = (size_t)P.local_rows * P.row_w * 3 * sizeof(float);
+    if (P.local_rows == 0) return RT_OK;
+    if (P.spp <= 0 || P.max_depth <= 0) {
+        HIP_TRY(hipMemsetAsync(d_fb_sum, 0, fb_bytes, stream));
+        if (sync) HIP_TRY(hipStreamSynchronize(stream));
+        return RT_OK;
+    }
+    const rtk::EnvDev E = env_dev_of(env, np);
+    P.fb = d_fb_sum;
+    const uint32_t num_pixels = (uint32_t)P.local_rows * (uint32_t)P.row_w;
+    rtaccel::PassPlan passes;
+    if ((st = reserve_slab(sc, num_pixels, P.spp, stream, passes)) != RT_OK) return st;
+    P.slab = sc->slab;
+    P.num_pixels = num_pixels;
+    P.slab_pitch = slab_pitch_of(passes.pass_size);
+    P.cand = nullptr;
+    P.order = nullptr;
+    const void *kernel = (const void *)rtk::env_render_kernel;
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, rtk::kEnvBlock, 0) != hipSuccess || per_cu < 1) {
+        (void)hipGetLastError();
+        per_cu = 1;
+    }
+    hipFuncAttributes attr;
+    uint32_t vgprs = 0, scratch = 0;
+    if (hipFuncGetAttributes(&attr, kernel) == hipSuccess) {
+        vgprs = (uint32_t)attr.numRegs;
+        scratch = (uint32_t)attr.localSizeBytes;
+    }
+    if (!sc->env_queue) HIP_TRY(hipMalloc((void **)&sc->env_queue, kMaxPasses * 4));
+    if (!sc->env_start) {
+        HIP_TRY(hipEventCreate(&sc->env_start));
+        HIP_TRY(hipEventCreate(&sc->env_stop));
+    }
+    HIP_TRY(hipMemsetAsync(sc->env_queue, 0, kMaxPasses * 4, stream));
+    HIP_TRY(hipEventRecord(sc->env_start, stream));
+    const int wgs = sc->num_cus * per_cu;
+    int first_grid = 0;
+    const uint32_t acc_blocks = (num_pixels + 64 * rtk::kAccWaves - 1) / (64 * rtk::kAccWaves);
+    for (int pass = 0; pass < passes.passes; ++pass) {
+        if ((st = set_pass(P, passes, pass, num_pixels, sample_first)) != RT_OK) return st;
+        P.queue = sc->env_queue + pass;
+        const uint32_t need = (P.total_work + rtk::kEnvChunk - 1) / rtk::kEnvChunk;          // waves that can get work at all
+        int grid = wgs;
+        if ((uint64_t)grid * (rtk::kEnvBlock / rtk::kWave) > need) grid = (int)((need + rtk::kEnvBlock / rtk::kWave - 1) / (rtk::kEnvBlock / rtk::kWave));
+        if (grid < 1) grid = 1;
+        hipLaunchKernelGGL(rtk::env_render_kernel, dim3(grid), dim3(rtk::kEnvBlock), 0, stream, P, E);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(rtk::accumulate_kernel<false>, dim3(acc_blocks), dim3(64 * rtk::kAccWaves), 0, stream, d_fb_sum, (const float *)sc->slab, num_pixels,
+                           P.slab_pitch, P.pass_count, pass == 0 ? 1 : 0, (uint32_t *)nullptr, (const uint32_t *)nullptr, (const uint32_t *)nullptr,
+                           (const uint32_t *)nullptr, (uint32_t)rtk::kCandWords, P.bg[0], P.bg[1], P.bg[2]);
+        HIP_TRY(hipGetLastError());
+        if (pass == 0) first_grid = grid;
+    }
+    HIP_TRY(hipEventRecord(sc->env_stop, stream));
+    rt_timing t{};
+    t.num_workgroups = (uint32_t)first_grid;
+    t.workgroup_size = (uint32_t)rtk::kEnvBlock;
+    t.trace_launches = (uint32_t)passes.passes;
+    t.kernel = RT_KERNEL_MEGA;
+    t.trace_vgprs = vgprs;
+    t.trace_scratch_bytes = scratch;
+    t.traced_samples = (uint64_t)num_pixels * (uint64_t)P.spp;
+    t.guard_paused = sc->guard_paused ? 1u : 0u;
+    if (sync) {
+        HIP_TRY(hipEventSynchronize(sc->env_stop));
+        HIP_TRY(hipEventElapsedTime(&t.kernel_ms, sc->env_start, sc->env_stop));
+        HIP_TRY(hipEventElapsedTime(&t.trace_ms, sc->env_start, sc->env_stop));
+    }
+    timing_out(t, timing);
+    return RT_OK;
+}
+}  // namespace
+
+rt_status rt_render_env(rt_scene *sc, const rt_camera_data *cam, const rt_env *env, const rt_env_params *params, const rt_shard *shard,
+                        int32_t sample_first, float *d_fb_sum, void *hip_stream, int32_t sync, rt_timing *timing) {
+    rt_env_params np;
+    if (const rt_status st = env_setup("rt_render_env", params, np)) return st;
+    if (!env) return fail(RT_ERR_INVALID_ARG, "rt_render_env: null environment");
+    if (!sc) return fail(RT_ERR_INVALID_ARG, "rt_render_env: null scene");
+    return render_env_impl(sc, cam, env, np, shard, sample_first, d_fb_sum, hip_stream, sync, timing);
+}
+
+rt_status rt_trace_samples_env(rt_scene *sc, const rt_camera_data *cam, const rt_env *env, const rt_env_params *params, int32_t n,
+                               const int32_t *ijs, float *radiance, int32_t *rays, uint32_t *final_seed, uint32_t *final_env_seed) {
+    rt_env_params np;
+    if (const rt_status st = env_setup("rt_trace_samples_env", params, np)) return st;
+    if (!env) return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_env: null environment");
+    if (n < 0 || (n > 0 && (!ijs || !radiance || !rays || !final_seed || !final_env_seed))) return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_env: null argument");
+    rtk::KParams P;
+    rt_status st = fill_params(sc, cam, nullptr, P);
+    if (st != RT_OK) return st;
+    if ((st = check_device(sc)) != RT_OK) return st;
+    if (env->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_env: the environment was created on another device than the scene");
+    if (n == 0) return RT_OK;
+    for (int32_t k = 0; k < n; ++k)
+        if (ijs[3 * k] < 0 || ijs[3 * k] >= cam->image_width || ijs[3 * k + 1] < 0 || ijs[3 * k + 1] >= cam->image_height || ijs[3 * k + 2] < 0)
+            return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_env: sample coordinate out of range");
+    const rtk::EnvDev E = env_dev_of(env, np);
+    int32_t *d_ijs = nullptr, *d_rays = nullptr;
+    float *d_rad = nullptr;
+    uint32_t *d_seed = nullptr, *d_env = nullptr;
+    struct Free {
+        int32_t *&a, *&b; float *&c; uint32_t *&d, *&e;
+        ~Free() { (void)hipFree(a); (void)hipFree(b); (void)hipFree(c); (void)hipFree(d); (void)hipFree(e); }
+    } freer{d_ijs, d_rays, d_rad, d_seed, d_env};
+    HIP_TRY(hipMalloc((void **)&d_ijs, (size_t)n * 12));
+    HIP_TRY(hipMalloc((void **)&d_rad, (size_t)n * 12));
+    HIP_TRY(hipMalloc((void **)&d_rays, (size_t)n * 4));
+    HIP_TRY(hipMalloc((void **)&d_seed, (size_t)n * 4));
+    HIP_TRY(hipMalloc((void **)&d_env, (size_t)n * 4));
+    HIP_TRY(hipMemcpy(d_ijs, ijs, (size_t)n * 12, hipMemcpyHostToDevice));
+    P.probe_ijs = d_ijs; P.probe_rad = d_rad; P.probe_rays = d_rays; P.probe_seed = d_seed; P.probe_n = n;
+    hipLaunchKernelGGL(rtk::env_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, P, E, d_env);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(radiance, d_rad, (size_t)n * 12, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(rays, d_rays, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(final_seed, d_seed, (size_t)n * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(final_env_seed, d_env, (size_t)n * 4, hipMemcpyDeviceToHost));
     return RT_OK;
 }
 

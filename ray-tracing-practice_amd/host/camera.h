@@ -137,9 +137,10 @@ bool write_aov_file(const std::string &path, int32_t width, int32_t height, int3
 void gpu_render_pipelined(const SceneParams &params, const rt_scene_desc &desc, int num_devices);
 // rtp_main --gpu --lens R:F / --motion-blur S: the orbit frame after frame on one GPU through rt_render_lens (shutter S: open at frame
 // n, closed at n + S; 0: no motion), saved with rt_tonemap; aov / denoise from rt_render_aov_lens
-// nee (rtp_main --nee): frames through rt_render_nee with these parameters instead (the lens and shutter then unused: a pinhole at frame n)
+// nee (rtp_main --nee): frames through rt_render_nee with these parameters instead (the lens and shutter then unused: a pinhole at frame n);
+// env (rtp_main --env): through rt_render_env with env_params, likewise
 void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const rt_lens_params &lens, float shutter, bool aov, bool denoise,
-                     const rt_nee_params *nee = nullptr);
+                     const rt_nee_params *nee = nullptr, const rt_env *env = nullptr, const rt_env_params *env_params = nullptr);
 // rtp_main --gpu --adaptive: the orbit frame after frame on one GPU, each frame through rt_render_adaptive and rt_tonemap_spp
 void gpu_render_adaptive(const SceneParams &params, const rt_scene_desc &desc, const rt_adaptive_params &ap);
 

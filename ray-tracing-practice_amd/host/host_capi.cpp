@@ -138,6 +138,27 @@ int32_t rtp_host_load_texture(const char *path, int32_t *width, int32_t *height,
     return 0;
 }
 
+// rtp_main --env's image loader (texture_io.h, load_hdr_image): the size first (rgb NULL), then the w x h x 3 floats, top row first
+int32_t rtp_host_load_hdr(const char *path, int32_t *width, int32_t *height, float *rgb) {
+    static thread_local std::string cached_path;
+    static thread_local rtp::HdrImage cached;
+    if (!path || !width || !height) return 1;
+    if (cached_path != path) {
+        rtp::HdrImage img;
+        std::string error;
+        if (!rtp::load_hdr_image(path, img, error)) return 1;
+        cached = std::move(img);
+        cached_path = path;
+    }
+    *width = cached.width;
+    *height = cached.height;
+    if (rgb) {
+        std::copy(cached.rgb.begin(), cached.rgb.end(), rgb);
+        cached_path.clear();
+    }
+    return 0;
+}
+
 const char *rtp_host_default_config(void) {
     static const std::string text = rtp::default_config_text();
     return text.c_str();

@@ -8,10 +8,12 @@
 #include <cstdlib>
 #include <iostream>
 #include <string>
+#include <vector>
 
 #include "camera.h"
 #include "scene_builder.h"
 #include "scene_params.h"
+#include "texture_io.h"
 
 int main(int argc, char *argv[]) {
     const std::string mode = argc < 2 ? "--gpu" : argv[1];
@@ -38,6 +40,83 @@ int main(int argc, char *argv[]) {
         if (std::string(argv[a]) == "--aov") aov = true;
         if (std::string(argv[a]) == "--denoise") denoise = true;
         if (std::string(argv[a]) == "--denoise-temporal") temporal = true;
+    }
+    // extension: `--gpu --env FILE[:N] [--env-mode path|mis|light] [--env-scale S] [--env-up y|z]`: every frame through rt_render_env on one
+    // GPU, lit by the lat-long image FILE (PFM or Radiance .hdr) resampled into an N x N octahedral map (N defaults to 1024); mis is the
+    // default mode, --env-up z turns the map for a z-up scene such as the default configuration; the same saver bytes, --aov /
+    // --denoise as with --nee.  Not with --nee, --lens, --motion-blur, --adaptive, --denoise-temporal, --devices, --shard or RTP_DEVICES.
+    {
+        bool env_on = false, env_others = getenv("RTP_DEVICES") != nullptr;
+        std::string env_bad, env_file;
+        int env_n = 1024;
+        rt_env_params ep;
+        rt_env_params_init(&ep);
+        for (int a = 2; a < argc; ++a) {
+            const std::string arg = argv[a];
+            const std::string value = a + 1 < argc ? argv[a + 1] : "";
+            if (arg == "--nee" || arg == "--lens" || arg == "--motion-blur" || arg == "--adaptive" || arg == "--denoise-temporal" || arg == "--devices" ||
+                arg == "--shard")
+                env_others = true;
+            if (arg == "--env") {
+                env_on = true;
+                env_file = value;
+                const size_t colon = env_file.rfind(':');
+                if (colon != std::string::npos && colon + 1 < env_file.size() && env_file.find_first_not_of("0123456789", colon + 1) == std::string::npos) {
+                    env_n = env_file.size() - colon - 1 > 5 ? 0 : atoi(env_file.c_str() + colon + 1);
+                    env_file.erase(colon);
+                }
+                if (env_file.empty()) env_bad = "--env takes FILE[:N]";
+                else if (env_n < 1 || env_n > RT_ENV_MAX_N) env_bad = "--env FILE:N takes N from 1 to " + std::to_string(RT_ENV_MAX_N);
+            } else if (arg == "--env-mode") {
+                if (value == "path") ep.mode = 0;
+                else if (value == "mis") ep.mode = 1;
+                else if (value == "light") ep.mode = 2;
+                else env_bad = "--env-mode takes path, mis (default) or light";
+            } else if (arg == "--env-scale") {
+                char *end = nullptr;
+                ep.scale = strtof(value.c_str(), &end);
+                if (value.empty() || *end != 0 || !(std::isfinite(ep.scale) && ep.scale >= 0.0f)) env_bad = "--env-scale takes a finite number that is not negative";
+            } else if (arg == "--env-up") {
+                if (value == "z") {
+                    const float z_up[9] = {1, 0, 0, 0, 0, 1, 0, -1, 0};        // environment y = world z
+                    for (int k = 0; k < 9; ++k) ep.rot[k] = z_up[k];
+                } else if (value != "y") {
+                    env_bad = "--env-up takes y (default) or z";
+                }
+            }
+        }
+        if (!env_on)
+            for (int a = 2; a < argc; ++a)
+                if (std::string(argv[a]).compare(0, 6, "--env-") == 0) env_bad = std::string(argv[a]) + " needs --env FILE";
+        if (env_on || !env_bad.empty()) {
+            if (!env_bad.empty()) {
+                std::cerr << "rtp_main: " << env_bad << "\n";
+                return 99;
+            }
+            if (env_others) {
+                std::cerr << "rtp_main: --env renders frame after frame on one GPU: it cannot be combined with --nee, --lens, --motion-blur, "
+                             "--adaptive, --denoise-temporal, --devices, --shard or RTP_DEVICES\n";
+                return 99;
+            }
+            rtp::HdrImage image;
+            std::string error;
+            if (!rtp::load_hdr_image(env_file, image, error)) {
+                std::cerr << "rtp_main: --env: " << error << "\n";
+                return 99;
+            }
+            std::vector<float> map(static_cast<size_t>(env_n) * env_n * 3);
+            rt_env *env = nullptr;
+            if (rt_env_from_equirect(image.rgb.data(), image.width, image.height, env_n, map.data()) != RT_OK ||
+                rt_env_create(map.data(), env_n, &env) != RT_OK) {
+                std::cerr << "rtp_main: --env: " << env_file << ": " << rt_get_last_error_string() << "\n";
+                return 99;
+            }
+            rt_lens_params pinhole;
+            rt_lens_params_init(&pinhole);
+            rtp::gpu_render_lens(params, desc, pinhole, 0.0f, aov, denoise, nullptr, env, &ep);
+            rt_env_destroy(env);
+            return 0;
+        }
     }
     // extension: `--gpu --nee [mis|light]`: every frame through rt_render_nee on one GPU (direct light sampling of the emissive spheres,
     // combined with the path's own sample by the power heuristic, or alone), the same saver bytes; --aov / --denoise as without it

@@ -24,6 +24,16 @@ bool load_texture(const std::string &path, TextureImage &out);
 // 8-bit sRGB-ish → linear float RGBA, the stbi_loadf rule (gamma 2.2, scale 1).
 void ldr_to_linear_rgba(const unsigned char *rgb, int width, int height, int channels, TextureImage &out);
 
+// A high-dynamic-range image for rtp_main --env: float RGB, row-major, top row first.
+struct HdrImage {
+    std::vector<float> rgb;
+    int width = 0, height = 0;
+};
+// PFM ("PF": three floats per pixel, either endianness by the sign of the scale token, bottom row first) and Radiance RGBE
+// ("#?RADIANCE", "-Y h +X w", flat and new-style run-length-encoded scanlines).  Own readers, nothing vendored.  false (and a
+// message in `error`): unreadable, truncated, or not one of these.
+bool load_hdr_image(const std::string &path, HdrImage &out, std::string &error);
+
 // Deterministic procedural texture for tests/benchmarks (two-tone checker with a gradient).
 void make_checker_texture(int size, TextureImage &out);
 

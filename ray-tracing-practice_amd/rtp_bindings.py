@@ -188,6 +188,107 @@ def _nee_struct(params):
     return C.byref(params if isinstance(params, NeeParams) else nee_params(**params))
 
 
+class EnvParams(C.Structure):
+    """rt_env_params (include/rtp_amd.h): an IN structure of the caller's size — struct_bytes is set on construction; the other
+    fields are 0 until rt_env_params_init (env_params()) fills the defaults."""
+    _fields_ = [("struct_bytes", C.c_uint32), ("mode", C.c_int32), ("scale", C.c_float), ("rot", C.c_float * 9),
+                ("camera_visible", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_bytes = C.sizeof(EnvParams)
+
+
+ENV_PATH, ENV_MIS, ENV_LIGHT = 0, 1, 2
+
+
+def env_params(**params):
+    """rt_env_params with the library's defaults (mode = 1, scale = 1, rot = identity, camera_visible = 1), then the given fields
+    (rot: nine numbers, the rows of the world → environment rotation)."""
+    p = EnvParams()
+    amd_lib().rt_env_params_init(C.byref(p))
+    for k, v in params.items():
+        if k not in dict(EnvParams._fields_) or k == "reserved":
+            raise RtError(f"rt_env_params has no field {k}")
+        if k == "rot":
+            v = np.asarray(v, dtype=np.float32).ravel()
+            if v.size != 9:
+                raise RtError("rt_env_params.rot takes nine numbers")
+            for i in range(9):
+                p.rot[i] = float(v[i])
+        else:
+            setattr(p, k, v)
+    return p
+
+
+def _env_struct(params):
+    """None → NULL (the defaults); an EnvParams as it is; a dict → env_params(**dict)."""
+    if params is None:
+        return None
+    return C.byref(params if isinstance(params, EnvParams) else env_params(**params))
+
+
+class Env:
+    """rt_env: an octahedral environment map with its sampling table on the current device.  Env(rgb) takes an (n, n, 3) array;
+    Env.from_equirect(image, n) resamples a lat-long image first.  A context manager; close() destroys the object."""
+
+    def __init__(self, rgb):
+        rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+        if rgb.ndim != 3 or rgb.shape[0] != rgb.shape[1] or rgb.shape[2] != 3:
+            raise RtError(f"Env takes an (n, n, 3) array, not {rgb.shape}")
+        self.n = int(rgb.shape[0])
+        h = C.c_void_p()
+        _check(amd_lib().rt_env_create(rgb.ctypes.data, self.n, C.byref(h)), "rt_env_create")
+        self._h = h
+
+    @staticmethod
+    def equirect_to_octahedral(image, n=1024):
+        """rt_env_from_equirect: (h, w, 3) lat-long → (n, n, 3) octahedral (host only)."""
+        image = np.ascontiguousarray(image, dtype=np.float32)
+        if image.ndim != 3 or image.shape[2] != 3:
+            raise RtError(f"a lat-long image is (h, w, 3), not {image.shape}")
+        out = np.empty((n, n, 3), dtype=np.float32)
+        _check(amd_lib().rt_env_from_equirect(image.ctypes.data, image.shape[1], image.shape[0], n, out.ctypes.data), "rt_env_from_equirect")
+        return out
+
+    @classmethod
+    def from_equirect(cls, image, n=1024):
+        return cls(cls.equirect_to_octahedral(image, n))
+
+    def table(self, row=0):
+        """rt_env_table: (count, row cdf, row pmf, row `row`'s conditional cdf, its pmf); count = n, or 0 for an empty table."""
+        n = self.n
+        out = [np.zeros(n, dtype=np.float32) for _ in range(4)]
+        count = C.c_int32()
+        _check(amd_lib().rt_env_table(self._h, row, *(a.ctypes.data for a in out), C.byref(count)), "rt_env_table")
+        return (count.value, *out)
+
+    def lookup(self, dirs):
+        """rt_env_lookup: dirs (m, 3) → (texel = iy * n + ix (m,), radiance (m, 3), pl (m,)), computed on the device."""
+        dirs = np.ascontiguousarray(dirs, dtype=np.float32).reshape(-1, 3)
+        m = dirs.shape[0]
+        tex, rad, pl = np.empty(m, np.int32), np.empty((m, 3), np.float32), np.empty(m, np.float32)
+        _check(amd_lib().rt_env_lookup(self._h, m, dirs.ctypes.data, tex.ctypes.data, rad.ctypes.data, pl.ctypes.data), "rt_env_lookup")
+        return tex, rad, pl
+
+    def close(self):
+        if self._h is not None:
+            amd_lib().rt_env_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 TRAVERSAL_AUTO, TRAVERSAL_EXACT, TRAVERSAL_GUARDED = 0, 1, 2
 BUILD_HOST_SAH, BUILD_DEVICE_LBVH = 0, 1
 KERNEL_AUTO, KERNEL_MEGA, KERNEL_WAVEFRONT = 0, 1, 2
@@ -241,6 +342,8 @@ RTP_AMD_SYMBOLS = [
     "rt_adaptive_params_init", "rt_render_adaptive", "rt_tonemap_spp",
     "rt_lens_params_init", "rt_render_lens", "rt_render_aov_lens", "rt_lens_camera_rays",
     "rt_nee_params_init", "rt_render_nee", "rt_nee_light_table", "rt_trace_samples_nee",
+    "rt_env_params_init", "rt_env_create", "rt_env_destroy", "rt_env_table", "rt_env_lookup", "rt_env_from_equirect", "rt_render_env",
+    "rt_trace_samples_env",
 ]
 
 _host = None
@@ -352,6 +455,18 @@ def amd_lib():
             lib.rt_nee_light_table.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
             lib.rt_trace_samples_nee.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(NeeParams), C.c_int32, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(lib, "rt_render_env"):
+            lib.rt_env_params_init.argtypes = [C.POINTER(EnvParams)]
+            lib.rt_env_params_init.restype = None
+            lib.rt_env_create.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
+            lib.rt_env_destroy.argtypes = [C.c_void_p]
+            lib.rt_env_table.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
+            lib.rt_env_lookup.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+            lib.rt_env_from_equirect.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
+            lib.rt_render_env.argtypes = [C.c_void_p, C.POINTER(CameraData), C.c_void_p, C.POINTER(EnvParams), C.POINTER(Shard), C.c_int32,
+                                          C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(Timing)]
+            lib.rt_trace_samples_env.argtypes = [C.c_void_p, C.POINTER(CameraData), C.c_void_p, C.POINTER(EnvParams), C.c_int32, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.rt_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         lib.rt_last_timing.argtypes = [C.c_void_p, C.POINTER(Timing)]
         lib.rt_timing_init.argtypes = [C.POINTER(Timing)]
@@ -444,6 +559,19 @@ class HostScene:
             self.close()
         except Exception:
             pass
+
+
+def load_hdr_image(path):
+    """rtp_main --env's loader (host/texture_io.cpp): a PFM or Radiance .hdr file → (h, w, 3) float32, top row first."""
+    lib = host_lib()
+    lib.rtp_host_load_hdr.argtypes = [C.c_char_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]
+    w, h = C.c_int32(), C.c_int32()
+    if lib.rtp_host_load_hdr(os.fsencode(path), C.byref(w), C.byref(h), None) != 0:
+        raise RtError(f"cannot load {path} as a PFM or Radiance image")
+    out = np.empty((h.value, w.value, 3), dtype=np.float32)
+    if lib.rtp_host_load_hdr(os.fsencode(path), C.byref(w), C.byref(h), out.ctypes.data) != 0:
+        raise RtError(f"cannot load {path} as a PFM or Radiance image")
+    return out
 
 
 def make_camera(width, height, vfov, eye, target, background=(0, 0, 0), spp=1, max_depth=50):
@@ -966,6 +1094,41 @@ class DeviceScene:
         _check(amd_lib().rt_trace_samples_nee(self._h, C.byref(cam), _nee_struct(params), n, ijs.ctypes.data, rad.ctypes.data,
                                               rays.ctypes.data, seeds.ctypes.data, nee.ctypes.data), "rt_trace_samples_nee")
         return rad, rays, seeds, nee
+
+    def render_env(self, cam, env, d_fb_ptr, params=None, shard=None, stream=None, sync=True, sample_first=0):
+        """rt_render_env: env an Env; params None (defaults: MIS, scale 1, no rotation), an EnvParams or a dict of its fields.  Returns the
+        rt_timing of this call."""
+        t = Timing()
+        self._apply_config()
+        _check(amd_lib().rt_render_env(self._h, C.byref(cam), env._h, _env_struct(params), C.byref(shard) if shard else None, sample_first,
+                                       C.c_void_p(d_fb_ptr), C.c_void_p(stream or 0), 1 if sync else 0, C.byref(t)), "rt_render_env")
+        return t
+
+    def render_env_to_host(self, cam, env, params=None, shard=None, sample_first=0):
+        """rt_render_env through a fresh device buffer: (rows, width, 3) float32 sums and the rt_timing."""
+        lib = amd_lib()
+        rows = lib.rt_shard_rows(cam.image_height, C.byref(shard) if shard else None)
+        fb = np.empty((rows, cam.image_width, 3), dtype=np.float32)
+        d = C.c_void_p()
+        _check(lib.rt_device_alloc(fb.nbytes or 12, C.byref(d)), "rt_device_alloc")
+        try:
+            t = self.render_env(cam, env, d.value, params=params, shard=shard, sample_first=sample_first)
+            _check(lib.rt_copy_to_host(fb.ctypes.data, d, fb.nbytes), "rt_copy_to_host")
+        finally:
+            lib.rt_device_free(d)
+        return fb, t
+
+    def trace_samples_env(self, cam, env, ijs, params=None):
+        """rt_trace_samples_env: ijs (n, 3) → (radiance (n, 3), rays (n,), final seeds (n,), final light-sample seeds (n,))."""
+        ijs = np.ascontiguousarray(ijs, dtype=np.int32).reshape(-1, 3)
+        n = ijs.shape[0]
+        rad = np.empty((n, 3), dtype=np.float32)
+        rays = np.empty(n, dtype=np.int32)
+        seeds = np.empty(n, dtype=np.uint32)
+        es = np.empty(n, dtype=np.uint32)
+        _check(amd_lib().rt_trace_samples_env(self._h, C.byref(cam), env._h, _env_struct(params), n, ijs.ctypes.data, rad.ctypes.data,
+                                              rays.ctypes.data, seeds.ctypes.data, es.ctypes.data), "rt_trace_samples_env")
+        return rad, rays, seeds, es
 
     def last_kernel_ms(self):
         ms = C.c_float()
