@@ -19,6 +19,7 @@
 #include "rt_adaptive.hip.inc"
 #include "rt_nee.hip.inc"
 #include "rt_env.hip.inc"
+#include "rt_light.hip.inc"
 // Developer build only (make dev → librtp_amd_dev.so, -DRTP_DEV_BUILD): the rt_debug_* entry points (exhaustive on-device checks of
 // recip / sqrt_cr / sphere_root, the device LBVH builder on its own, the tripwire, the RTP_STATS counters) at the end of this file.
 // The shipped library contains none of them.
@@ -268,18 +269,16 @@ struct rt_scene {
     // rt_render_lens: events of its own (rt_last_timing keeps reporting the last rt_render)
     hipEvent_t lens_start = nullptr, lens_stop = nullptr;
     uint32_t *lens_queue = nullptr;         // … and a counter block of its own (kQueueWords)
-    // rt_render_nee (rt_nee.hip.inc): the emitter table, made by the handle's first call (host copy + device columns), its events and
-    // its work counters (one per pass)
+    // rt_render_nee (rt_nee.hip.inc): the emitter table, made by the handle's first call (host copy + device columns)
     bool nee_built = false;
     std::vector<int32_t> nee_index;
     std::vector<float> nee_cdf, nee_pmf;
     int32_t *nee_index_dev = nullptr;
     float *nee_cdf_dev = nullptr, *nee_pmf_dev = nullptr;
-    uint32_t *nee_queue = nullptr;
-    hipEvent_t nee_start = nullptr, nee_stop = nullptr;
-    // rt_render_env (rt_env.hip.inc): its events and its work counters (one per pass); the environment is an object of its own
-    uint32_t *env_queue = nullptr;
-    hipEvent_t env_start = nullptr, env_stop = nullptr;
+    // rt_render_nee and rt_render_env (rt_light.hip.inc): their events and work counters (one per pass) — one set, a handle renders one
+    // frame at a time; the environment is an object of its own
+    uint32_t *light_queue = nullptr;
+    hipEvent_t light_start = nullptr, light_stop = nullptr;
 };
 
 namespace {
@@ -661,12 +660,9 @@ rt_status rt_scene_destroy(rt_scene *sc) {
     if (sc->adapt_start) (void)hipEventDestroy(sc->adapt_start);
     if (sc->adapt_stop) (void)hipEventDestroy(sc->adapt_stop);
     (void)hipFree(sc->lens_queue);
-    (void)hipFree(sc->nee_index_dev); (void)hipFree(sc->nee_cdf_dev); (void)hipFree(sc->nee_pmf_dev); (void)hipFree(sc->nee_queue);
-    if (sc->nee_start) (void)hipEventDestroy(sc->nee_start);
-    if (sc->nee_stop) (void)hipEventDestroy(sc->nee_stop);
-    (void)hipFree(sc->env_queue);
-    if (sc->env_start) (void)hipEventDestroy(sc->env_start);
-    if (sc->env_stop) (void)hipEventDestroy(sc->env_stop);
+    (void)hipFree(sc->nee_index_dev); (void)hipFree(sc->nee_cdf_dev); (void)hipFree(sc->nee_pmf_dev); (void)hipFree(sc->light_queue);
+    if (sc->light_start) (void)hipEventDestroy(sc->light_start);
+    if (sc->light_stop) (void)hipEventDestroy(sc->light_stop);
     if (sc->lens_start) (void)hipEventDestroy(sc->lens_start);
     if (sc->lens_stop) (void)hipEventDestroy(sc->lens_stop);
     for (rt_scene::Feedback &f : sc->feedback) {
@@ -1208,13 +1204,13 @@ const void *lens_trace_kernel(const LaunchPlan &L) {
     return (const void *)render_lens_kernel<false, false>;
 }
 
-// (lens: the second kernel argument of render_lens_kernel; null for render_kernel)
-hipError_t launch(const void *kernel, uint32_t block, int grid, uint32_t lds, hipStream_t stream, const rtk::KParams &KP, const rtk::LensCam *lens = nullptr) {
+// (second: the second kernel argument — render_lens_kernel's LensCam, a lit trace kernel's light table; null for render_kernel)
+hipError_t launch(const void *kernel, uint32_t block, int grid, uint32_t lds, hipStream_t stream, const rtk::KParams &KP, const void *second = nullptr) {
     hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     void *args[] = {(void *)&KP};
-    void *lens_args[] = {(void *)&KP, (void *)lens};
-    e = hipLaunchKernel(kernel, dim3(grid), dim3(block), lens ? lens_args : args, lds, stream);
+    void *both_args[] = {(void *)&KP, (void *)second};
+    e = hipLaunchKernel(kernel, dim3(grid), dim3(block), second ? both_args : args, lds, stream);
     const hipError_t last = hipGetLastError();
     return e != hipSuccess ? e : last;
 }
@@ -1864,6 +1860,133 @@ rt_status adaptive_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard 
     timing_out(t, timing);
     return RT_OK;
 }
+
+// ---- what the lit calls share: the frame driver of rt_render_nee / rt_render_env, the probe of rt_trace_samples and its lit kin ---------
+// rt_render_nee / rt_render_env: the passes of render_impl (plan_passes, the slab, accumulate_kernel in sample order) with a trace kernel
+// of rt_light.hip.inc as the trace launch; nothing of the handle's walk machinery is touched.
+//   light_device: the device of a light that is an object of its own (null: the light is the handle's);
+//   make_light: fills the kernel's second argument, once the call is known to trace
+template <class Light, class MakeLight>
+rt_status render_light_impl(const char *what, void (*trace)(rtk::KParams, Light), const int *light_device, MakeLight make_light, rt_scene *sc,
+                            const rt_camera_data *cam, const rt_shard *shard, int32_t sample_first, float *d_fb_sum, void *hip_stream, int32_t sync,
+                            rt_timing *timing) {
+    rtk::KParams P;
+    rt_status st = fill_params(sc, cam, shard, P);
+    if (st != RT_OK) return st;
+    if ((st = check_sample_range(what, sample_first, P.spp)) != RT_OK) return st;
+    if ((st = check_device(sc)) != RT_OK) return st;
+    if (light_device && *light_device != sc->device) return fail(RT_ERR_INVALID_ARG, std::string(what) + ": the environment was created on another device than the scene");
+    if (!d_fb_sum) return fail(RT_ERR_INVALID_ARG, "null framebuffer");
+    if ((st = timing_check(timing)) != RT_OK) return st;
+    if (sc->cfg.kernel == RT_KERNEL_WAVEFRONT) return fail(RT_ERR_UNSUPPORTED, "RT_KERNEL_WAVEFRONT was an experiment and has been retired: not in this library");
+    if (sc->cfg.wide_nodes > 0) return fail(RT_ERR_UNSUPPORTED, "rt_config.wide_nodes = 1 was an experiment and has been retired: not in this library");
+    hipStream_t stream = (hipStream_t)hip_stream;
+    timing_out(rt_timing{}, timing);
+    const size_t fb_bytes = (size_t)P.local_rows * P.row_w * 3 * sizeof(float);
+    if (P.local_rows == 0) return RT_OK;
+    if (P.spp <= 0 || P.max_depth <= 0) {
+        HIP_TRY(hipMemsetAsync(d_fb_sum, 0, fb_bytes, stream));
+        if (sync) HIP_TRY(hipStreamSynchronize(stream));
+        return RT_OK;
+    }
+    Light T;
+    if ((st = make_light(T)) != RT_OK) return st;
+    P.fb = d_fb_sum;
+    const uint32_t num_pixels = (uint32_t)P.local_rows * (uint32_t)P.row_w;
+    rtaccel::PassPlan passes;
+    if ((st = reserve_slab(sc, num_pixels, P.spp, stream, passes)) != RT_OK) return st;
+    P.slab = sc->slab;
+    P.num_pixels = num_pixels;
+    P.slab_pitch = slab_pitch_of(passes.pass_size);
+    P.cand = nullptr;
+    P.order = nullptr;
+    const void *kernel = (const void *)trace;
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, rtk::kLightBlock, 0) != hipSuccess || per_cu < 1) {
+        (void)hipGetLastError();
+        per_cu = 1;
+    }
+    hipFuncAttributes attr;
+    uint32_t vgprs = 0, scratch = 0;
+    if (hipFuncGetAttributes(&attr, kernel) == hipSuccess) {
+        vgprs = (uint32_t)attr.numRegs;
+        scratch = (uint32_t)attr.localSizeBytes;
+    }
+    if (!sc->light_queue) HIP_TRY(hipMalloc((void **)&sc->light_queue, kMaxPasses * 4));
+    if (!sc->light_start) HIP_TRY(hipEventCreate(&sc->light_start));
+    if (!sc->light_stop) HIP_TRY(hipEventCreate(&sc->light_stop));
+    HIP_TRY(hipMemsetAsync(sc->light_queue, 0, kMaxPasses * 4, stream));
+    HIP_TRY(hipEventRecord(sc->light_start, stream));
+    const int wgs = sc->num_cus * per_cu;
+    const int waves_per_wg = rtk::kLightBlock / rtk::kWave;
+    int first_grid = 0;
+    const uint32_t acc_blocks = (num_pixels + 64 * rtk::kAccWaves - 1) / (64 * rtk::kAccWaves);
+    for (int pass = 0; pass < passes.passes; ++pass) {
+        if ((st = set_pass(P, passes, pass, num_pixels, sample_first)) != RT_OK) return st;
+        P.queue = sc->light_queue + pass;
+        const uint32_t need = (P.total_work + rtk::kLightChunk - 1) / rtk::kLightChunk;          // waves that can get work at all
+        int grid = wgs;
+        if ((uint64_t)grid * waves_per_wg > need) grid = (int)((need + waves_per_wg - 1) / waves_per_wg);
+        if (grid < 1) grid = 1;
+        HIP_TRY(launch(kernel, (uint32_t)rtk::kLightBlock, grid, 0, stream, P, &T));
+        hipLaunchKernelGGL(rtk::accumulate_kernel<false>, dim3(acc_blocks), dim3(64 * rtk::kAccWaves), 0, stream, d_fb_sum, (const float *)sc->slab, num_pixels,
+                           P.slab_pitch, P.pass_count, pass == 0 ? 1 : 0, (uint32_t *)nullptr, (const uint32_t *)nullptr, (const uint32_t *)nullptr,
+                           (const uint32_t *)nullptr, (uint32_t)rtk::kCandWords, P.bg[0], P.bg[1], P.bg[2]);
+        HIP_TRY(hipGetLastError());
+        if (pass == 0) first_grid = grid;
+    }
+    HIP_TRY(hipEventRecord(sc->light_stop, stream));
+    rt_timing t{};
+    t.num_workgroups = (uint32_t)first_grid;
+    t.workgroup_size = (uint32_t)rtk::kLightBlock;
+    t.trace_launches = (uint32_t)passes.passes;
+    t.kernel = RT_KERNEL_MEGA;
+    t.trace_vgprs = vgprs;
+    t.trace_scratch_bytes = scratch;
+    t.traced_samples = (uint64_t)num_pixels * (uint64_t)P.spp;
+    t.guard_paused = sc->guard_paused ? 1u : 0u;
+    if (sync) {
+        HIP_TRY(hipEventSynchronize(sc->light_stop));
+        HIP_TRY(hipEventElapsedTime(&t.kernel_ms, sc->light_start, sc->light_stop));
+        HIP_TRY(hipEventElapsedTime(&t.trace_ms, sc->light_start, sc->light_stop));
+    }
+    timing_out(t, timing);
+    return RT_OK;
+}
+
+// rt_trace_samples, rt_trace_samples_nee, rt_trace_samples_env: the (i, j, s) triples checked against cam and uploaded, launch_probe(P,
+// d_light_seed) run on P with the probe columns set, the columns downloaded; device memory is freed on every path.
+//   what: the prefix of the call's messages; final_light_seed: the lit probes' second RNG state (null: no such column)
+template <class LaunchProbe>
+rt_status run_probe(const std::string &what, rtk::KParams &P, const rt_camera_data *cam, int32_t n, const int32_t *ijs, float *radiance, int32_t *rays,
+                    uint32_t *final_seed, uint32_t *final_light_seed, LaunchProbe launch_probe) {
+    if (n == 0) return RT_OK;
+    for (int32_t k = 0; k < n; ++k)
+        if (ijs[3 * k] < 0 || ijs[3 * k] >= cam->image_width || ijs[3 * k + 1] < 0 || ijs[3 * k + 1] >= cam->image_height || ijs[3 * k + 2] < 0)
+            return fail(RT_ERR_INVALID_ARG, what + "sample coordinate out of range");
+    int32_t *d_ijs = nullptr, *d_rays = nullptr;
+    float *d_rad = nullptr;
+    uint32_t *d_seed = nullptr, *d_light = nullptr;
+    struct Free {
+        int32_t *&a, *&b; float *&c; uint32_t *&d, *&e;
+        ~Free() { (void)hipFree(a); (void)hipFree(b); (void)hipFree(c); (void)hipFree(d); (void)hipFree(e); }
+    } freer{d_ijs, d_rays, d_rad, d_seed, d_light};
+    if (hipMalloc((void **)&d_ijs, (size_t)n * 12) != hipSuccess || hipMalloc((void **)&d_rad, (size_t)n * 12) != hipSuccess ||
+        hipMalloc((void **)&d_rays, (size_t)n * 4) != hipSuccess || hipMalloc((void **)&d_seed, (size_t)n * 4) != hipSuccess ||
+        (final_light_seed && hipMalloc((void **)&d_light, (size_t)n * 4) != hipSuccess))
+        return fail(RT_ERR_OUT_OF_MEMORY, what + "hipMalloc failed");
+    if (hipMemcpy(d_ijs, ijs, (size_t)n * 12, hipMemcpyHostToDevice) != hipSuccess) return fail(RT_ERR_HIP, what + "hipMemcpy H2D failed");
+    P.probe_ijs = d_ijs; P.probe_rad = d_rad; P.probe_rays = d_rays; P.probe_seed = d_seed; P.probe_n = n;
+    if (const rt_status st = launch_probe(P, d_light)) return st;
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpy(radiance, d_rad, (size_t)n * 12, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(rays, d_rays, (size_t)n * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(final_seed, d_seed, (size_t)n * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && final_light_seed) e = hipMemcpy(final_light_seed, d_light, (size_t)n * 4, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(RT_ERR_HIP, what + "probe kernel: " + hipGetErrorString(e));
+    return RT_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -2093,94 +2216,6 @@ rtk::NeeTable nee_table_of(const rt_scene *sc, int32_t mis) {
     return T;
 }
 
-// rt_render_nee: the passes of render_impl (plan_passes, the slab, accumulate_kernel in sample order) with nee_render_kernel as the
-// trace launch; nothing of the handle's walk machinery is touched
-rt_status render_nee_impl(rt_scene *sc, const rt_camera_data *cam, int32_t mis, const rt_shard *shard, int32_t sample_first, float *d_fb_sum,
-                          void *hip_stream, int32_t sync, rt_timing *timing) {
-    rtk::KParams P;
-    rt_status st = fill_params(sc, cam, shard, P);
-    if (st != RT_OK) return st;
-    if ((st = check_sample_range("rt_render_nee", sample_first, P.spp)) != RT_OK) return st;
-    if ((st = check_device(sc)) != RT_OK) return st;
-    if (!d_fb_sum) return fail(RT_ERR_INVALID_ARG, "null framebuffer");
-    if ((st = timing_check(timing)) != RT_OK) return st;
-    if (sc->cfg.kernel == RT_KERNEL_WAVEFRONT) return fail(RT_ERR_UNSUPPORTED, "RT_KERNEL_WAVEFRONT was an experiment and has been retired: not in this library");
-    if (sc->cfg.wide_nodes > 0) return fail(RT_ERR_UNSUPPORTED, "rt_config.wide_nodes = 1 was an experiment and has been retired: not in this library");
-    hipStream_t stream = (hipStream_t)hip_stream;
-    timing_out(rt_timing{}, timing);
-    const size_t fb_bytes = (size_t)P.local_rows * P.row_w * 3 * sizeof(float);
-    if (P.local_rows == 0) return RT_OK;
-    if (P.spp <= 0 || P.max_depth <= 0) {
-        HIP_TRY(hipMemsetAsync(d_fb_sum, 0, fb_bytes, stream));
-        if (sync) HIP_TRY(hipStreamSynchronize(stream));
-        return RT_OK;
-    }
-    if ((st = nee_table_ensure(sc)) != RT_OK) return st;
-    const rtk::NeeTable T = nee_table_of(sc, mis);
-    P.fb = d_fb_sum;
-    const uint32_t num_pixels = (uint32_t)P.local_rows * (uint32_t)P.row_w;
-    rtaccel::PassPlan passes;
-    if ((st = reserve_slab(sc, num_pixels, P.spp, stream, passes)) != RT_OK) return st;
-    P.slab = sc->slab;
-    P.num_pixels = num_pixels;
-    P.slab_pitch = slab_pitch_of(passes.pass_size);
-    P.cand = nullptr;
-    P.order = nullptr;
-    const void *kernel = (const void *)rtk::nee_render_kernel;
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, rtk::kNeeBlock, 0) != hipSuccess || per_cu < 1) {
-        (void)hipGetLastError();
-        per_cu = 1;
-    }
-    hipFuncAttributes attr;
-    uint32_t vgprs = 0, scratch = 0;
-    if (hipFuncGetAttributes(&attr, kernel) == hipSuccess) {
-        vgprs = (uint32_t)attr.numRegs;
-        scratch = (uint32_t)attr.localSizeBytes;
-    }
-    if (!sc->nee_queue) HIP_TRY(hipMalloc((void **)&sc->nee_queue, kMaxPasses * 4));
-    if (!sc->nee_start) {
-        HIP_TRY(hipEventCreate(&sc->nee_start));
-        HIP_TRY(hipEventCreate(&sc->nee_stop));
-    }
-    HIP_TRY(hipMemsetAsync(sc->nee_queue, 0, kMaxPasses * 4, stream));
-    HIP_TRY(hipEventRecord(sc->nee_start, stream));
-    const int wgs = sc->num_cus * per_cu;
-    int first_grid = 0;
-    const uint32_t acc_blocks = (num_pixels + 64 * rtk::kAccWaves - 1) / (64 * rtk::kAccWaves);
-    for (int pass = 0; pass < passes.passes; ++pass) {
-        if ((st = set_pass(P, passes, pass, num_pixels, sample_first)) != RT_OK) return st;
-        P.queue = sc->nee_queue + pass;
-        const uint32_t need = (P.total_work + rtk::kNeeChunk - 1) / rtk::kNeeChunk;          // waves that can get work at all
-        int grid = wgs;
-        if ((uint64_t)grid * (rtk::kNeeBlock / rtk::kWave) > need) grid = (int)((need + rtk::kNeeBlock / rtk::kWave - 1) / (rtk::kNeeBlock / rtk::kWave));
-        if (grid < 1) grid = 1;
-        hipLaunchKernelGGL(rtk::nee_render_kernel, dim3(grid), dim3(rtk::kNeeBlock), 0, stream, P, T);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(rtk::accumulate_kernel<false>, dim3(acc_blocks), dim3(64 * rtk::kAccWaves), 0, stream, d_fb_sum, (const float *)sc->slab, num_pixels,
-                           P.slab_pitch, P.pass_count, pass == 0 ? 1 : 0, (uint32_t *)nullptr, (const uint32_t *)nullptr, (const uint32_t *)nullptr,
-                           (const uint32_t *)nullptr, (uint32_t)rtk::kCandWords, P.bg[0], P.bg[1], P.bg[2]);
-        HIP_TRY(hipGetLastError());
-        if (pass == 0) first_grid = grid;
-    }
-    HIP_TRY(hipEventRecord(sc->nee_stop, stream));
-    rt_timing t{};
-    t.num_workgroups = (uint32_t)first_grid;
-    t.workgroup_size = (uint32_t)rtk::kNeeBlock;
-    t.trace_launches = (uint32_t)passes.passes;
-    t.kernel = RT_KERNEL_MEGA;
-    t.trace_vgprs = vgprs;
-    t.trace_scratch_bytes = scratch;
-    t.traced_samples = (uint64_t)num_pixels * (uint64_t)P.spp;
-    t.guard_paused = sc->guard_paused ? 1u : 0u;
-    if (sync) {
-        HIP_TRY(hipEventSynchronize(sc->nee_stop));
-        HIP_TRY(hipEventElapsedTime(&t.kernel_ms, sc->nee_start, sc->nee_stop));
-        HIP_TRY(hipEventElapsedTime(&t.trace_ms, sc->nee_start, sc->nee_stop));
-    }
-    timing_out(t, timing);
-    return RT_OK;
-}
 }  // namespace
 
 rt_status rt_render_nee(rt_scene *sc, const rt_camera_data *cam, const rt_nee_params *params, const rt_shard *shard, int32_t sample_first,
@@ -2188,7 +2223,12 @@ rt_status rt_render_nee(rt_scene *sc, const rt_camera_data *cam, const rt_nee_pa
     int32_t mis = 1;
     if (const rt_status st = nee_setup("rt_render_nee", params, mis)) return st;
     if (!sc) return fail(RT_ERR_INVALID_ARG, "rt_render_nee: null scene");
-    return render_nee_impl(sc, cam, mis, shard, sample_first, d_fb_sum, hip_stream, sync, timing);
+    auto make_table = [&](rtk::NeeTable &T) {
+        if (const rt_status st = nee_table_ensure(sc)) return st;
+        T = nee_table_of(sc, mis);
+        return RT_OK;
+    };
+    return render_light_impl("rt_render_nee", rtk::nee_render_kernel, nullptr, make_table, sc, cam, shard, sample_first, d_fb_sum, hip_stream, sync, timing);
 }
 
 rt_status rt_nee_light_table(rt_scene *sc, int32_t cap, int32_t *sphere_index, float *cdf, float *pmf, int32_t *count) {
@@ -2215,34 +2255,11 @@ rt_status rt_trace_samples_nee(rt_scene *sc, const rt_camera_data *cam, const rt
     rt_status st = fill_params(sc, cam, nullptr, P);
     if (st != RT_OK) return st;
     if ((st = check_device(sc)) != RT_OK) return st;
-    if (n == 0) return RT_OK;
-    for (int32_t k = 0; k < n; ++k)
-        if (ijs[3 * k] < 0 || ijs[3 * k] >= cam->image_width || ijs[3 * k + 1] < 0 || ijs[3 * k + 1] >= cam->image_height || ijs[3 * k + 2] < 0)
-            return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_nee: sample coordinate out of range");
-    if ((st = nee_table_ensure(sc)) != RT_OK) return st;
-    const rtk::NeeTable T = nee_table_of(sc, mis);
-    int32_t *d_ijs = nullptr, *d_rays = nullptr;
-    float *d_rad = nullptr;
-    uint32_t *d_seed = nullptr, *d_nee = nullptr;
-    struct Free {
-        int32_t *&a, *&b; float *&c; uint32_t *&d, *&e;
-        ~Free() { (void)hipFree(a); (void)hipFree(b); (void)hipFree(c); (void)hipFree(d); (void)hipFree(e); }
-    } freer{d_ijs, d_rays, d_rad, d_seed, d_nee};
-    HIP_TRY(hipMalloc((void **)&d_ijs, (size_t)n * 12));
-    HIP_TRY(hipMalloc((void **)&d_rad, (size_t)n * 12));
-    HIP_TRY(hipMalloc((void **)&d_rays, (size_t)n * 4));
-    HIP_TRY(hipMalloc((void **)&d_seed, (size_t)n * 4));
-    HIP_TRY(hipMalloc((void **)&d_nee, (size_t)n * 4));
-    HIP_TRY(hipMemcpy(d_ijs, ijs, (size_t)n * 12, hipMemcpyHostToDevice));
-    P.probe_ijs = d_ijs; P.probe_rad = d_rad; P.probe_rays = d_rays; P.probe_seed = d_seed; P.probe_n = n;
-    hipLaunchKernelGGL(rtk::nee_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, P, T, d_nee);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(radiance, d_rad, (size_t)n * 12, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(rays, d_rays, (size_t)n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(final_seed, d_seed, (size_t)n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(final_nee_seed, d_nee, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return RT_OK;
+    return run_probe("rt_trace_samples_nee: ", P, cam, n, ijs, radiance, rays, final_seed, final_nee_seed, [&](const rtk::KParams &KP, uint32_t *d_nee) {
+        if (const rt_status ts = nee_table_ensure(sc)) return ts;
+        hipLaunchKernelGGL(rtk::nee_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, KP, nee_table_of(sc, mis), d_nee);
+        return RT_OK;
+    });
 }
 
 // ---- rt_env / rt_render_env / rt_env_table / rt_env_lookup / rt_trace_samples_env (rtp_amd.h) ---------------------
@@ -2474,104 +2491,17 @@ rt_status rt_env_from_equirect(const float *rgb, int32_t w, int32_t h, int32_t n
     return RT_OK;
 }
 
-namespace {
-// rt_render_env: the passes of render_impl (plan_passes, the slab, accumulate_kernel in sample order) with env_render_kernel as the
-// trace launch; nothing of the handle's walk machinery is touched
-rt_status render_env_impl(rt_scene *sc, const rt_camera_data *cam, const rt_env *env, const rt_env_params &np, const rt_shard *shard,
-                          int32_t sample_first, float *d_fb_sum, void *hip_stream, int32_t sync, rt_timing *timing) {
-    rtk::KParams P;
-    rt_status st = fill_params(sc, cam, shard, P);
-    if (st != RT_OK) return st;
-    if ((st = check_sample_range("rt_render_env", sample_first, P.spp)) != RT_OK) return st;
-    if ((st = check_device(sc)) != RT_OK) return st;
-    if (env->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_render_env: the environment was created on another device than the scene");
-    if (!d_fb_sum) return fail(RT_ERR_INVALID_ARG, "null framebuffer");
-    if ((st = timing_check(timing)) != RT_OK) return st;
-    if (sc->cfg.kernel == RT_KERNEL_WAVEFRONT) return fail(RT_ERR_UNSUPPORTED, "RT_KERNEL_WAVEFRONT was an experiment and has been retired: not in this library");
-    if (sc->cfg.wide_nodes > 0) return fail(RT_ERR_UNSUPPORTED, "rt_config.wide_nodes = 1 was an experiment and has been retired: not in this library");
-    hipStream_t stream = (hipStream_t)hip_stream;
-    timing_out(rt_timing{}, timing);
-    const size_t fb_bytes = (size_t)P.local_rows * P.row_w * 3 * sizeof(float);
-    if (P.local_rows == 0) return RT_OK;
-    if (P.spp <= 0 || P.max_depth <= 0) {
-        HIP_TRY(hipMemsetAsync(d_fb_sum, 0, fb_bytes, stream));
-        if (sync) HIP_TRY(hipStreamSynchronize(stream));
-        return RT_OK;
-    }
-    const rtk::EnvDev E = env_dev_of(env, np);
-    P.fb = d_fb_sum;
-    const uint32_t num_pixels = (uint32_t)P.local_rows * (uint32_t)P.row_w;
-    rtaccel::PassPlan passes;
-    if ((st = reserve_slab(sc, num_pixels, P.spp, stream, passes)) != RT_OK) return st;
-    P.slab = sc->slab;
-    P.num_pixels = num_pixels;
-    P.slab_pitch = slab_pitch_of(passes.pass_size);
-    P.cand = nullptr;
-    P.order = nullptr;
-    const void *kernel = (const void *)rtk::env_render_kernel;
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, rtk::kEnvBlock, 0) != hipSuccess || per_cu < 1) {
-        (void)hipGetLastError();
-        per_cu = 1;
-    }
-    hipFuncAttributes attr;
-    uint32_t vgprs = 0, scratch = 0;
-    if (hipFuncGetAttributes(&attr, kernel) == hipSuccess) {
-        vgprs = (uint32_t)attr.numRegs;
-        scratch = (uint32_t)attr.localSizeBytes;
-    }
-    if (!sc->env_queue) HIP_TRY(hipMalloc((void **)&sc->env_queue, kMaxPasses * 4));
-    if (!sc->env_start) {
-        HIP_TRY(hipEventCreate(&sc->env_start));
-        HIP_TRY(hipEventCreate(&sc->env_stop));
-    }
-    HIP_TRY(hipMemsetAsync(sc->env_queue, 0, kMaxPasses * 4, stream));
-    HIP_TRY(hipEventRecord(sc->env_start, stream));
-    const int wgs = sc->num_cus * per_cu;
-    int first_grid = 0;
-    const uint32_t acc_blocks = (num_pixels + 64 * rtk::kAccWaves - 1) / (64 * rtk::kAccWaves);
-    for (int pass = 0; pass < passes.passes; ++pass) {
-        if ((st = set_pass(P, passes, pass, num_pixels, sample_first)) != RT_OK) return st;
-        P.queue = sc->env_queue + pass;
-        const uint32_t need = (P.total_work + rtk::kEnvChunk - 1) / rtk::kEnvChunk;          // waves that can get work at all
-        int grid = wgs;
-        if ((uint64_t)grid * (rtk::kEnvBlock / rtk::kWave) > need) grid = (int)((need + rtk::kEnvBlock / rtk::kWave - 1) / (rtk::kEnvBlock / rtk::kWave));
-        if (grid < 1) grid = 1;
-        hipLaunchKernelGGL(rtk::env_render_kernel, dim3(grid), dim3(rtk::kEnvBlock), 0, stream, P, E);
-        HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(rtk::accumulate_kernel<false>, dim3(acc_blocks), dim3(64 * rtk::kAccWaves), 0, stream, d_fb_sum, (const float *)sc->slab, num_pixels,
-                           P.slab_pitch, P.pass_count, pass == 0 ? 1 : 0, (uint32_t *)nullptr, (const uint32_t *)nullptr, (const uint32_t *)nullptr,
-                           (const uint32_t *)nullptr, (uint32_t)rtk::kCandWords, P.bg[0], P.bg[1], P.bg[2]);
-        HIP_TRY(hipGetLastError());
-        if (pass == 0) first_grid = grid;
-    }
-    HIP_TRY(hipEventRecord(sc->env_stop, stream));
-    rt_timing t{};
-    t.num_workgroups = (uint32_t)first_grid;
-    t.workgroup_size = (uint32_t)rtk::kEnvBlock;
-    t.trace_launches = (uint32_t)passes.passes;
-    t.kernel = RT_KERNEL_MEGA;
-    t.trace_vgprs = vgprs;
-    t.trace_scratch_bytes = scratch;
-    t.traced_samples = (uint64_t)num_pixels * (uint64_t)P.spp;
-    t.guard_paused = sc->guard_paused ? 1u : 0u;
-    if (sync) {
-        HIP_TRY(hipEventSynchronize(sc->env_stop));
-        HIP_TRY(hipEventElapsedTime(&t.kernel_ms, sc->env_start, sc->env_stop));
-        HIP_TRY(hipEventElapsedTime(&t.trace_ms, sc->env_start, sc->env_stop));
-    }
-    timing_out(t, timing);
-    return RT_OK;
-}
-}  // namespace
-
 rt_status rt_render_env(rt_scene *sc, const rt_camera_data *cam, const rt_env *env, const rt_env_params *params, const rt_shard *shard,
                         int32_t sample_first, float *d_fb_sum, void *hip_stream, int32_t sync, rt_timing *timing) {
     rt_env_params np;
     if (const rt_status st = env_setup("rt_render_env", params, np)) return st;
     if (!env) return fail(RT_ERR_INVALID_ARG, "rt_render_env: null environment");
     if (!sc) return fail(RT_ERR_INVALID_ARG, "rt_render_env: null scene");
-    return render_env_impl(sc, cam, env, np, shard, sample_first, d_fb_sum, hip_stream, sync, timing);
+    auto make_env = [&](rtk::EnvDev &E) {
+        E = env_dev_of(env, np);
+        return RT_OK;
+    };
+    return render_light_impl("rt_render_env", rtk::env_render_kernel, &env->device, make_env, sc, cam, shard, sample_first, d_fb_sum, hip_stream, sync, timing);
 }
 
 rt_status rt_trace_samples_env(rt_scene *sc, const rt_camera_data *cam, const rt_env *env, const rt_env_params *params, int32_t n,
@@ -2585,33 +2515,10 @@ rt_status rt_trace_samples_env(rt_scene *sc, const rt_camera_data *cam, const rt
     if (st != RT_OK) return st;
     if ((st = check_device(sc)) != RT_OK) return st;
     if (env->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_env: the environment was created on another device than the scene");
-    if (n == 0) return RT_OK;
-    for (int32_t k = 0; k < n; ++k)
-        if (ijs[3 * k] < 0 || ijs[3 * k] >= cam->image_width || ijs[3 * k + 1] < 0 || ijs[3 * k + 1] >= cam->image_height || ijs[3 * k + 2] < 0)
-            return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_env: sample coordinate out of range");
-    const rtk::EnvDev E = env_dev_of(env, np);
-    int32_t *d_ijs = nullptr, *d_rays = nullptr;
-    float *d_rad = nullptr;
-    uint32_t *d_seed = nullptr, *d_env = nullptr;
-    struct Free {
-        int32_t *&a, *&b; float *&c; uint32_t *&d, *&e;
-        ~Free() { (void)hipFree(a); (void)hipFree(b); (void)hipFree(c); (void)hipFree(d); (void)hipFree(e); }
-    } freer{d_ijs, d_rays, d_rad, d_seed, d_env};
-    HIP_TRY(hipMalloc((void **)&d_ijs, (size_t)n * 12));
-    HIP_TRY(hipMalloc((void **)&d_rad, (size_t)n * 12));
-    HIP_TRY(hipMalloc((void **)&d_rays, (size_t)n * 4));
-    HIP_TRY(hipMalloc((void **)&d_seed, (size_t)n * 4));
-    HIP_TRY(hipMalloc((void **)&d_env, (size_t)n * 4));
-    HIP_TRY(hipMemcpy(d_ijs, ijs, (size_t)n * 12, hipMemcpyHostToDevice));
-    P.probe_ijs = d_ijs; P.probe_rad = d_rad; P.probe_rays = d_rays; P.probe_seed = d_seed; P.probe_n = n;
-    hipLaunchKernelGGL(rtk::env_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, P, E, d_env);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(radiance, d_rad, (size_t)n * 12, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(rays, d_rays, (size_t)n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(final_seed, d_seed, (size_t)n * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(final_env_seed, d_env, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return RT_OK;
+    return run_probe("rt_trace_samples_env: ", P, cam, n, ijs, radiance, rays, final_seed, final_env_seed, [&](const rtk::KParams &KP, uint32_t *d_env) {
+        hipLaunchKernelGGL(rtk::env_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, KP, env_dev_of(env, np), d_env);
+        return RT_OK;
+    });
 }
 
 void rt_timing_init(rt_timing *t) {
@@ -2827,30 +2734,10 @@ rt_status rt_trace_samples(rt_scene *sc, const rt_camera_data *cam, int32_t n, c
     rt_status st = fill_params(sc, cam, nullptr, P);
     if (st != RT_OK) return st;
     if ((st = check_device(sc)) != RT_OK) return st;
-    if (n == 0) return RT_OK;
-    for (int32_t k = 0; k < n; ++k)
-        if (ijs[3 * k] < 0 || ijs[3 * k] >= cam->image_width || ijs[3 * k + 1] < 0 || ijs[3 * k + 1] >= cam->image_height || ijs[3 * k + 2] < 0)
-            return fail(RT_ERR_INVALID_ARG, "sample coordinate out of range");
-    int32_t *d_ijs = nullptr, *d_rays = nullptr;
-    float *d_rad = nullptr;
-    uint32_t *d_seed = nullptr;
-    auto cleanup = [&]() { (void)hipFree(d_ijs); (void)hipFree(d_rays); (void)hipFree(d_rad); (void)hipFree(d_seed); };
-    if (hipMalloc((void **)&d_ijs, (size_t)n * 12) != hipSuccess || hipMalloc((void **)&d_rad, (size_t)n * 12) != hipSuccess ||
-        hipMalloc((void **)&d_rays, (size_t)n * 4) != hipSuccess || hipMalloc((void **)&d_seed, (size_t)n * 4) != hipSuccess) {
-        cleanup();
-        return fail(RT_ERR_OUT_OF_MEMORY, "hipMalloc failed");
-    }
-    if (hipMemcpy(d_ijs, ijs, (size_t)n * 12, hipMemcpyHostToDevice) != hipSuccess) { cleanup(); return fail(RT_ERR_HIP, "hipMemcpy H2D failed"); }
-    P.probe_ijs = d_ijs; P.probe_rad = d_rad; P.probe_rays = d_rays; P.probe_seed = d_seed; P.probe_n = n;
-    hipLaunchKernelGGL(rtk::probe_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, P);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(radiance, d_rad, (size_t)n * 12, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(rays, d_rays, (size_t)n * 4, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(final_seed, d_seed, (size_t)n * 4, hipMemcpyDeviceToHost);
-    cleanup();
-    if (e != hipSuccess) return fail(RT_ERR_HIP, std::string("probe kernel: ") + hipGetErrorString(e));
-    return RT_OK;
+    return run_probe("", P, cam, n, ijs, radiance, rays, final_seed, nullptr, [&](const rtk::KParams &KP, uint32_t *) {
+        hipLaunchKernelGGL(rtk::probe_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, KP);
+        return RT_OK;
+    });
 }
 
 rt_status rt_closest_hits(rt_scene *sc, int32_t n, const float *origins, const float *directions, int32_t *hit, float *t, int32_t *prim) {

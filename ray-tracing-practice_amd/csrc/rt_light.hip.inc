@@ -1,0 +1,351 @@
+// rt_light.hip.inc — the path that takes light samples, written once for both kinds of light: the emissive spheres of rt_render_nee
+// (NeeTable, rt_nee.hip.inc; DESIGN.md §13) and the environment of rt_render_env (EnvDev, rt_env.hip.inc; §14).  Included by rt_capi.hip
+// after both.  A light is its table type; what the two do differently is the overloads below, everything else — the lit vertex, the
+// walk step, the probe and the trace kernel — is one text.
+#pragma once
+
+namespace rtk {
+
+constexpr int kLightBlock = 256;
+constexpr uint32_t kLightChunk = 128u;                       // work indices a wave reserves per atomic
+constexpr int kLightShadeLanes = 32;                         // a wave shades once this many lanes are ready (or none is walking)
+
+// ---- what a light is ---------------------------------------------------------------------------------------------------------------
+// the key of its RNG stream: light = wang_hash(sample_seed ^ key)
+__device__ __forceinline__ uint32_t light_key(const NeeTable &) { return kNeeStreamKey; }
+__device__ __forceinline__ uint32_t light_key(const EnvDev &) { return kEnvStreamKey; }
+// are light samples drawn at all?
+__device__ __forceinline__ bool light_on(const NeeTable &T) { return T.count > 0; }
+__device__ __forceinline__ bool light_on(const EnvDev &E) { return E.sampled != 0; }
+// Is its shadow ray an occlusion query?  The environment's is: it contributes when it hits nothing, an answer that does not depend on
+// the visit order, and up to the first accepted hit the walk is the closest-hit search's own (closest is still 1e30) — so the walk ends
+// there.  An emitter's shadow ray has to find that sphere as its closest hit: a full walk.
+template <class Light> constexpr bool kLightOcclusion = false;
+template <> constexpr bool kLightOcclusion<EnvDev> = true;
+
+// miss: what the lane's ray adds when it hits nothing
+__device__ __forceinline__ f3 light_miss(const KParams &P, const NeeTable &, const Lane &L, bool) { return mul(L.beta, mk(P.bg[0], P.bg[1], P.bg[2])); }
+__device__ __forceinline__ f3 light_miss(const KParams &P, const EnvDev &E, const Lane &L, bool prev_diffuse) {
+    if (L.depth == 0 && !E.camera_visible) return mul(L.beta, mk(P.bg[0], P.bg[1], P.bg[2]));
+    return env_miss(E, L.d, L.beta, prev_diffuse);
+}
+// emitted: beta * emitted of the hit (sphere or plane idx) — weighted when a BSDF ray from a diffuse event found a table sphere; the
+// environment leaves it to the path alone
+__device__ __forceinline__ f3 light_emitted(const KParams &P, const NeeTable &T, const Lane &L, int32_t idx, bool is_plane, bool prev_diffuse, f3 emitted) {
+    if (prev_diffuse && !is_plane) {
+        const int32_t e = nee_find(T, idx);
+        if (e >= 0) {
+            f3 w;
+            float d2, om, pl = 0.0f;
+            if (nee_cone(L.o, P.spheres[idx], w, d2, om)) pl = T.pmf[e] * nee_pdf_cone(om);
+            const float wb = T.mis ? (kNeePb * kNeePb) / (kNeePb * kNeePb + pl * pl) : (pl > 0.0f ? 0.0f : 1.0f);
+            emitted = scale(wb, emitted);
+        }
+    }
+    return emitted;
+}
+__device__ __forceinline__ f3 light_emitted(const KParams &, const EnvDev &, const Lane &, int32_t, bool, bool, f3 emitted) { return emitted; }
+// sample: the light sample of a diffuse vertex at x (face-forwarded normal n, albedo a, throughput beta before the attenuation).  false:
+// none; else the shadow ray's direction, what it adds when it reaches the light, and (emitters) the code of the sphere to reach
+__device__ __forceinline__ bool light_sample(const KParams &P, const NeeTable &T, uint32_t &ls, f3 x, f3 n, f3 a, f3 beta, f3 &dir, f3 &c, int32_t &code) {
+    return nee_sample(P, T, ls, x, n, a, beta, dir, c, code);
+}
+__device__ __forceinline__ bool light_sample(const KParams &, const EnvDev &E, uint32_t &ls, f3, f3 n, f3 a, f3 beta, f3 &dir, f3 &c, int32_t &) {
+    return env_sample(E, ls, n, a, beta, dir, c);
+}
+// reached: the verdict of a finished shadow walk
+__device__ __forceinline__ bool light_reached(const NeeTable &, const Lane &L, int32_t code) { return L.hit == code; }
+__device__ __forceinline__ bool light_reached(const EnvDev &, const Lane &L, int32_t) { return L.hit < 0; }
+
+// the light samples' RNG state of a sample (the path's own is start_sample's)
+template <class Light>
+__device__ __forceinline__ uint32_t light_seed_of(const Light &T, uint32_t base_seed, int32_t s) {
+    return wang_hash(wang_hash(base_seed + (uint32_t)s) ^ light_key(T));
+}
+
+// ---- the lit vertex ----------------------------------------------------------------------------------------------------------------
+// shade() of the exact walk (kGuard = false, the global material table, the general build) with light samples:
+//   prev_diffuse: the ray that found this hit (or nothing) left a diffuse event at its origin L.o; diffuse_out: this vertex is one (the
+//   next ray's prev_diffuse); sample: it takes a light sample — the shadow ray (out_o, sdir), which adds c when it reaches the light
+//   (code).  Only a diffuse event whose next query is inside max_depth samples, so a vertex that samples always has a next ray, and
+//   out_o — the hit point — is both rays' origin.
+// The main stream's draws, the branches, the roulette and the next ray are shade()'s.
+template <class Light>
+__device__ __forceinline__ bool shade_lit(Lane &L, const KParams &P, const Light &T, bool prev_diffuse, uint32_t &ls, f3 &out_o, f3 &out_d,
+                                          f3 &sdir, f3 &c, int32_t &code, bool &sample, bool &diffuse_out) {
+    sample = false;
+    diffuse_out = false;
+    if (L.hit < 0) {
+        L.color = add(L.color, light_miss(P, T, L, prev_diffuse));
+        return false;
+    }
+    const int32_t hit = L.hit;
+    const int32_t idx = hit >> 1;
+    const float t = L.closest;
+    const f3 point = add(L.o, scale(t, L.d));        // r.at(rec.t)
+    f3 normal;
+    bool front;
+    int32_t mat_idx;
+    float tu = 0.0f, tv = 0.0f;
+    const bool is_plane = (hit & 1) != 0;
+    f3 outward = mk(0, 0, 0);
+    if (is_plane) {
+        const float4 P0 = P.planes[5 * idx + 0];
+        const float4 P2 = P.planes[5 * idx + 2];
+        outward = mk(P0.x, P0.y, P0.z);
+        mat_idx = as_int(P2.w);
+    } else {
+        const float4 s = P.spheres[idx];
+        outward = divs(sub(point, mk(s.x, s.y, s.z)), s.w);
+        mat_idx = P.sphere_mat[idx];
+    }
+    front = dot(L.d, outward) < 0;
+    normal = front ? outward : neg(outward);
+
+    const float4 MA = P.materials[3 * mat_idx + 0];
+    const float4 ME = P.materials[3 * mat_idx + 1];
+    const int32_t type = as_int(MA.w) & 3;
+    const int32_t tex_id = as_int(MA.w) >> 2;
+    f3 albedo = mk(MA.x, MA.y, MA.z);
+    if (tex_id != 0) {
+        if (is_plane) {
+            const float4 P1 = P.planes[5 * idx + 1];
+            const float4 P2 = P.planes[5 * idx + 2];
+            const float4 P3 = P.planes[5 * idx + 3];
+            const float4 P4 = P.planes[5 * idx + 4];
+            const f3 ph = sub(point, mk(P4.x, P4.y, P4.z));
+            const f3 w = mk(P1.x, P1.y, P1.z);
+            tu = dot(w, cross(ph, mk(P3.x, P3.y, P3.z)));
+            tv = dot(w, cross(mk(P2.x, P2.y, P2.z), ph));
+        } else {
+            const float theta = acos_libm(outward.y);
+            const float phi = (float)((double)atan2_libm(-outward.z, outward.x) + 3.14159265358979323846);
+            tu = (float)((double)phi / (2 * 3.14159265358979323846));
+            tv = (float)((double)theta / 3.14159265358979323846);
+        }
+        albedo = mul(albedo, sample_texture(P, tex_id - 1, tu, tv));
+    }
+    const f3 beta_in = L.beta;
+    const f3 emitted = light_emitted(P, T, L, idx, is_plane, prev_diffuse, mul(beta_in, mk(ME.x, ME.y, ME.z)));        // final_color += beta * emitted
+
+    f3 new_o = point, new_d = normal, att = albedo;
+    const bool is_lamb = type == RT_MAT_LAMBERTIAN;
+    const bool is_metal = type == RT_MAT_METAL;
+    const bool is_glass = type == RT_MAT_DIELECTRIC;
+    if (!(is_lamb || is_metal || is_glass)) {                        // DIFFUSE_LIGHT
+        L.color = add(L.color, emitted);
+        return false;
+    }
+    float4 MB = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
+    if (is_glass) MB = P.materials[3 * mat_idx + 2];
+    bool metal_reflect = false;
+    if (is_metal) metal_reflect = random_float(L.seed) < 0.8f;
+    f3 in_sphere = mk(0, 0, 0);
+    if (is_lamb || is_metal) in_sphere = random_in_unit_sphere(L.seed);
+    L.color = add(L.color, emitted);
+    f3 ud = mk(0, 0, 0);
+    if (metal_reflect || is_glass) ud = unit(L.d);
+    if (is_glass) {
+        const float ir = MB.w;
+        const float ratio = front ? ME.w : ir;
+        const float cos_theta = fminf(dot(neg(ud), normal), 1.0f);
+        const float sin_theta = sqrt_cr(1.0f - cos_theta * cos_theta);
+        const bool cannot_refract = ratio * sin_theta > 1.0f;
+        bool do_reflect = cannot_refract;
+        if (!cannot_refract) {
+            const float rnd = random_float(L.seed);
+            do_reflect = schlick_exceeds(cos_theta, front ? MA.x : MA.y, rnd);
+        }
+        new_d = do_reflect ? reflect(ud, normal) : refract(ud, normal, ratio);
+        att = mk(1.0f, 1.0f, 1.0f);
+        if (!front) {
+            const float dist = sqrt_cr(lensq(sub(point, L.o)));
+            const f3 tr = mk(MB.x == 0.0f ? 1.0f : exp_libm(-MB.x * dist), MB.y == 0.0f ? 1.0f : exp_libm(-MB.y * dist),
+                             MB.z == 0.0f ? 1.0f : exp_libm(-MB.z * dist));
+            att = mul(att, tr);
+        }
+        const float p = fmaxf(att.x, fmaxf(att.y, att.z));
+        if (random_float(L.seed) > p) return false;                  // Russian roulette
+        if (p != 1.0f) att = scale(recip(p), att);
+        const float side = dot(new_d, normal) > 0 ? 1.0f : -1.0f;
+        new_o = add(point, scale(side, scale(1e-4f, normal)));
+    } else if (metal_reflect) {
+        new_d = add(reflect(ud, normal), scale(ME.w, in_sphere));
+        if (!(dot(new_d, normal) > 0)) return false;
+    } else {                                                         // LAMBERTIAN and METAL's 20 % branch: a diffuse event
+        new_d = scatter_diffuse_dir(in_sphere, normal);
+        diffuse_out = true;
+        if (L.depth + 1 < P.max_depth && light_on(T)) sample = light_sample(P, T, ls, point, normal, albedo, beta_in, sdir, c, code);
+    }
+    L.beta = mul(L.beta, att);
+    L.depth++;
+    if (L.depth >= P.max_depth) return false;
+    out_o = new_o;
+    out_d = new_d;
+    return true;
+}
+
+// one step of the lane's armed ray: reference order, through L1 / L2 (shadow: the ray is a shadow ray)
+template <class Light>
+__device__ __forceinline__ void light_step(Lane &L, const KParams &P, bool shadow) {
+    if (L.sp != 0) {
+        leaf_threaded(L, P.spheres, P.planes);
+        if (kLightOcclusion<Light> && shadow && L.hit >= 0) L.node = kBlocked;
+    } else {
+        step_threaded(L, P.tnodes, P.num_tnodes);
+    }
+}
+
+// ---- probe (rt_trace_samples_nee / _env): one lane traces one (i, j, s) sample -------------------------------------------------------
+template <class Light>
+__device__ __forceinline__ void light_probe_body(const KParams &P, const Light &T, uint32_t *light_seed_out) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= P.probe_n) return;
+    const int32_t i = P.probe_ijs[3 * g], j = P.probe_ijs[3 * g + 1], s = P.probe_ijs[3 * g + 2];
+    Lane L;
+    const uint32_t base_seed = wang_hash((uint32_t)i * (uint32_t)P.width + (uint32_t)j);
+    uint32_t ls = light_seed_of(T, base_seed, s);
+    f3 ray_o, ray_d;
+    start_sample(L, P, i, j, base_seed, s, ray_o, ray_d);
+    begin_ray(L, ray_o, ray_d, 0);
+    int32_t rays = 0;
+    bool prev_diffuse = false;
+    if (P.max_depth > 0) {
+        for (;;) {
+            rays++;
+            while (!traversal_finished<true>(L, kBlocked)) light_step<Light>(L, P, false);
+            f3 sdir, c;
+            int32_t code = -1;
+            bool sample, diffuse;
+            const bool more = shade_lit(L, P, T, prev_diffuse, ls, ray_o, ray_d, sdir, c, code, sample, diffuse);
+            if (sample) {
+                rays++;
+                begin_ray(L, ray_o, sdir, 0);
+                while (!traversal_finished<true>(L, kBlocked)) light_step<Light>(L, P, true);
+                if (light_reached(T, L, code)) L.color = add(L.color, c);
+            }
+            if (!more) break;
+            prev_diffuse = diffuse;
+            begin_ray(L, ray_o, ray_d, 0);
+        }
+    }
+    P.probe_rad[3 * g] = L.color.x; P.probe_rad[3 * g + 1] = L.color.y; P.probe_rad[3 * g + 2] = L.color.z;
+    P.probe_rays[g] = rays;
+    P.probe_seed[g] = L.seed;
+    light_seed_out[g] = ls;
+}
+
+// ---- the trace kernel of rt_render_nee / rt_render_env: one pass of samples into the slab -------------------------------------------
+// Persistent waves fetch work indices kLightChunk at a time (one atomic per wave) and hand them to lanes as they free up.  Each lane
+// is a small state machine — walking its path ray, walking a shadow ray, or idle — and the wave either takes up to four walk steps for
+// the lanes that walk or, once kLightShadeLanes lanes (or all that are busy) have finished their walk, one shade step for those: the
+// path's shade (shade_lit), or the shadow ray's verdict.
+// Across a shadow walk a lane holds the next ray's direction, the pending contribution and the code to reach (seven registers; the
+// code is dead for the environment): the next ray's origin is the shadow ray's own (L.o), and a vertex that samples always has a next
+// ray, so no flag for it either.
+constexpr int32_t kLightIdle = 0, kLightPath = 1, kLightShadow = 2;
+template <class Light>
+__device__ __forceinline__ void light_render_body(const KParams &P, const Light &T) {
+    const int lane = (int)(threadIdx.x & (kWave - 1));
+    Lane L;
+    L.node = kBlocked;
+    L.sp = 0;
+    L.hit = -1;
+    L.closest = 1e30f;
+    L.color = mk(0.0f, 0.0f, 0.0f);
+    L.beta = mk(1.0f, 1.0f, 1.0f);
+    L.depth = 0;
+    L.seed = 0;
+    int32_t phase = kLightIdle;
+    uint32_t w = 0, ls = 0;
+    bool prev_diffuse = false;
+    f3 next_d = mk(0, 0, 0), contrib = mk(0, 0, 0);
+    int32_t target = -1;
+    uint32_t pool_next = 0, pool_end = 0;        // (wave-uniform)
+    bool exhausted = false;
+    for (;;) {
+        // ---- lanes without a sample take the next work indices of the wave's pool (refilled with one atomic)
+        const uint64_t idle = __ballot(phase == kLightIdle);
+        if (idle != 0 && !exhausted) {
+            const uint32_t cnt = (uint32_t)__popcll(idle);
+            const uint32_t rank = (uint32_t)lane_rank(idle);
+            const uint32_t avail = pool_end - pool_next;
+            uint32_t mine;
+            if (avail < cnt) {
+                uint32_t base = 0;
+                if (lane == 0) base = atomicAdd(P.queue, kLightChunk);
+                base = __builtin_amdgcn_readfirstlane(base);
+                mine = rank < avail ? pool_next + rank : base + (rank - avail);
+                pool_next = base + (cnt - avail);
+                pool_end = base + kLightChunk;
+                if (base >= P.total_work) exhausted = true;
+            } else {
+                mine = pool_next + rank;
+                pool_next += cnt;
+            }
+            if (phase == kLightIdle && mine < P.total_work) {
+                w = mine;
+                int32_t pi, pj;
+                uint32_t k;
+                map_work(P, w, pi, pj, k);
+                const int32_t s = P.pass_first + (int32_t)k;
+                const uint32_t base_seed = wang_hash((uint32_t)pi * (uint32_t)P.width + (uint32_t)pj);
+                ls = light_seed_of(T, base_seed, s);
+                f3 o, d;
+                start_sample(L, P, pi, pj, base_seed, s, o, d);
+                begin_ray(L, o, d, 0);
+                prev_diffuse = false;
+                phase = kLightPath;
+            }
+        }
+        const bool busy = phase != kLightIdle;
+        if (!__any(busy)) {
+            if (exhausted) break;
+            continue;
+        }
+        const bool walking = busy && !traversal_finished<true>(L, kBlocked);
+        const bool ready = busy && !walking;
+        const int n_walk = __popcll(__ballot(walking));
+        const int n_ready = __popcll(__ballot(ready));
+        if (n_walk == 0 || n_ready >= kLightShadeLanes) {
+            if (ready) {
+                if (phase == kLightPath) {
+                    f3 next_o, sdir;
+                    bool sample, diffuse;
+                    const bool more = shade_lit(L, P, T, prev_diffuse, ls, next_o, next_d, sdir, contrib, target, sample, diffuse);
+                    prev_diffuse = diffuse;
+                    if (sample) {
+                        begin_ray(L, next_o, sdir, 0);
+                        phase = kLightShadow;
+                    } else if (more) {
+                        begin_ray(L, next_o, next_d, 0);
+                    } else {
+                        store_sample(P, w, L.color);
+                        phase = kLightIdle;
+                    }
+                } else {
+                    if (light_reached(T, L, target)) L.color = add(L.color, contrib);
+                    begin_ray(L, L.o, next_d, 0);
+                    phase = kLightPath;
+                }
+                if (phase == kLightIdle) {
+                    L.node = kBlocked;
+                    L.sp = 0;
+                }
+            }
+        } else {
+            const bool shadow = phase == kLightShadow;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if (!traversal_finished<true>(L, kBlocked)) light_step<Light>(L, P, shadow);
+            }
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) nee_probe_kernel(const KParams P, const NeeTable T, uint32_t *nee_seed_out) { light_probe_body(P, T, nee_seed_out); }
+__global__ void __launch_bounds__(256) env_probe_kernel(const KParams P, const EnvDev E, uint32_t *env_seed_out) { light_probe_body(P, E, env_seed_out); }
+__global__ void __launch_bounds__(kLightBlock) nee_render_kernel(const KParams P, const NeeTable T) { light_render_body(P, T); }
+__global__ void __launch_bounds__(kLightBlock) env_render_kernel(const KParams P, const EnvDev E) { light_render_body(P, E); }
+
+}  // namespace rtk
