@@ -168,20 +168,56 @@ uint32_t bail_latest() {          // … and until when, in eighths of the pass 
     static const uint32_t f = [] { const int v = env_int("RTP_BAIL_LATEST", (int)kDefaultBailLatest); return (uint32_t)(v < 1 ? 1 : v > 8 ? 8 : v); }();
     return f;
 }
-// rt_timing is an out-structure of the caller's size (include/rtp_amd.h)
+// Out-structures (rt_timing, rt_config; include/rtp_amd.h) are written at the size the caller was compiled with and not a byte beyond
+template <class T>
+void copy_out(const T &src, T *dst, uint32_t caller_bytes) {
+    const uint32_t n = caller_bytes < sizeof(T) ? caller_bytes : (uint32_t)sizeof(T);
+    std::memcpy(dst, &src, n);
+    dst->struct_bytes = n;
+}
 rt_status timing_check(const rt_timing *t) {
     if (t && t->struct_bytes < 8) { g_last_error = "rt_timing.struct_bytes is not set (rt_timing_init)"; return RT_ERR_INVALID_ARG; }
     return RT_OK;
 }
 void timing_out(const rt_timing &src, rt_timing *dst) {
-    if (!dst) return;
-    const uint32_t n = dst->struct_bytes < sizeof(rt_timing) ? dst->struct_bytes : (uint32_t)sizeof(rt_timing);
-    std::memcpy(dst, &src, n);
-    dst->struct_bytes = n;
+    if (dst) copy_out(src, dst, dst->struct_bytes);
 }
 bool gamma_unproven(const rt_config &cfg) {
     return cfg.guard_gamma_ulps > 0.0f && (double)cfg.guard_gamma_ulps * 5.9604644775390625e-8 < (double)rtaccel::kGuardGammaBound;
 }
+// (RT_KERNEL_WAVEFRONT and rt_config.wide_nodes = 1 were experiments, retired: −37 % and −6 % on S-rtiow; docs/LOG.md)
+rt_status refuse_retired(const rt_config &cfg) {
+    if (cfg.kernel == RT_KERNEL_WAVEFRONT) return fail(RT_ERR_UNSUPPORTED, "RT_KERNEL_WAVEFRONT was an experiment and has been retired: not in this library");
+    if (cfg.wide_nodes > 0) return fail(RT_ERR_UNSUPPORTED, "rt_config.wide_nodes = 1 was an experiment and has been retired: not in this library");
+    return RT_OK;
+}
+
+// The clock of one family of calls (rt_scene::clock): a start and a stop event around everything a call enqueues and, where the family
+// counts on the device, counter words of its own.  One per family, so that rt_last_timing goes on reporting the last rt_render after an
+// AOV, lens or lit call.
+enum { kClockRender, kClockAov, kClockAdaptive, kClockLens, kClockLight, kNumClocks };
+struct CallClock {
+    hipEvent_t first = nullptr, last = nullptr;
+    uint32_t *words = nullptr;
+    rt_status make(size_t num_words = 0) {          // by the family's first call
+        if (num_words && !words) HIP_TRY(hipMalloc((void **)&words, num_words * sizeof(uint32_t)));
+        if (!first) HIP_TRY(hipEventCreate(&first));
+        if (!last) HIP_TRY(hipEventCreate(&last));
+        return RT_OK;
+    }
+    rt_status start(hipStream_t stream) { HIP_TRY(hipEventRecord(first, stream)); return RT_OK; }
+    rt_status stop(hipStream_t stream) { HIP_TRY(hipEventRecord(last, stream)); return RT_OK; }
+    rt_status elapsed(float &ms) {                  // waits for the call to finish
+        HIP_TRY(hipEventSynchronize(last));
+        HIP_TRY(hipEventElapsedTime(&ms, first, last));
+        return RT_OK;
+    }
+    void destroy() {
+        if (first) (void)hipEventDestroy(first);
+        if (last) (void)hipEventDestroy(last);
+        (void)hipFree(words);
+    }
+};
 
 }  // namespace
 
@@ -243,8 +279,11 @@ struct rt_scene {
     // same stream — the next sample batch of a progressive render, the next frame of a still — reuses them (0.4 ms at 1080p)
     struct CandKey { float view[12]; int32_t dims[9]; int repacks; hipStream_t stream; bool valid = false; } cand_key;
     int32_t num_internal = 0, num_spheres = 0, num_planes = 0, num_materials = 0, root = rtk::kDone, tree_depth = 0;
-    hipEvent_t ev_start = nullptr, ev_stop = nullptr;
-    std::vector<hipEvent_t> pass_events;   // per pass: before the trace launch, after it, after the exact re-walk (first kTimedPasses passes)
+    // one clock per family of calls: kClockRender (rt_render*, rt_render_adaptive's min_spp round) is made with the handle and counts in
+    // `queue`; rt_render_aov has a counter word of its own, rt_render_lens a counter block, the lit calls a work counter per pass — so
+    // that rt_last_timing and the handle's judgement of its guarded walk keep reading what the last rt_render left
+    CallClock clock[kNumClocks];
+    std::vector<hipEvent_t> pass_events;   // per pass: before the primary pass, before the trace launch, after it, after the exact re-walk (first kTimedPasses passes)
     int timed_passes = 0;
     rt_timing last{};
     int last_passes = 0;
@@ -254,31 +293,19 @@ struct rt_scene {
     uint64_t device_bytes = 0;      // total memory of the device (workspace default: a sixteenth of it)
     float build_ms = 0.0f;          // device BVH build time (RTP_BUILD=device), else 0
     bool absorbing_glass = false;   // some DIELECTRIC material has a non-zero absorption (Beer-Lambert code needed)
-    // rt_render_aov: its own counter word (records the reference-order walk resolved) and events, so that rt_last_timing and the
-    // handle's judgement of its guarded walk keep reading what the last rt_render left
-    uint32_t *aov_walked = nullptr;
-    hipEvent_t aov_start = nullptr, aov_stop = nullptr;
-    std::vector<hipEvent_t> aov_events;    // per timed pass: before the primary pass, before the resolve launch, after it
+    std::vector<hipEvent_t> aov_events;    // rt_render_aov, per timed pass: before the primary pass, before the resolve launch, after it
     // rt_render_adaptive (rt_adaptive.hip.inc): the moments of a caller who passes none (2 floats per local pixel), two lists of pixels
     // (2 x adapt_pixels words: one round reads the previous round's list while it writes its own), the work indices of a round
     // (adapt_work_cap words) and three counter words per round (list length, work indices, trace queue); grown on demand
     float *adapt_mom = nullptr;
     uint32_t *adapt_list = nullptr, *adapt_work = nullptr, *adapt_counters = nullptr;
     size_t adapt_mom_pixels = 0, adapt_pixels = 0, adapt_work_cap = 0, adapt_counter_words = 0;
-    hipEvent_t adapt_start = nullptr, adapt_stop = nullptr;
-    // rt_render_lens: events of its own (rt_last_timing keeps reporting the last rt_render)
-    hipEvent_t lens_start = nullptr, lens_stop = nullptr;
-    uint32_t *lens_queue = nullptr;         // … and a counter block of its own (kQueueWords)
     // rt_render_nee (rt_nee.hip.inc): the emitter table, made by the handle's first call (host copy + device columns)
     bool nee_built = false;
     std::vector<int32_t> nee_index;
     std::vector<float> nee_cdf, nee_pmf;
     int32_t *nee_index_dev = nullptr;
     float *nee_cdf_dev = nullptr, *nee_pmf_dev = nullptr;
-    // rt_render_nee and rt_render_env (rt_light.hip.inc): their events and work counters (one per pass) — one set, a handle renders one
-    // frame at a time; the environment is an object of its own
-    uint32_t *light_queue = nullptr;
-    hipEvent_t light_start = nullptr, light_stop = nullptr;
 };
 
 namespace {
@@ -479,9 +506,7 @@ void rt_config_init_sized(rt_config *cfg, uint32_t struct_bytes) {
     if (!cfg || struct_bytes < 8) return;
     rt_config c;
     config_defaults(c);
-    const uint32_t n = struct_bytes < sizeof(rt_config) ? struct_bytes : (uint32_t)sizeof(rt_config);
-    std::memcpy(cfg, &c, n);
-    cfg->struct_bytes = n;
+    copy_out(c, cfg, struct_bytes);
 }
 
 void rt_config_from_env(rt_config *user) {
@@ -522,9 +547,7 @@ void rt_config_from_env(rt_config *user) {
     if (env_int("RTP_NO_FRONT", 0)) cfg->guard_front_primitives = -1;
     if (env_int("RTP_NO_VIEW_CACHE", 0)) cfg->reuse_view_lists = -1;
     if (env_int("RTP_NO_RESUME", 0)) cfg->resume_flagged = -1;
-    const uint32_t n = user->struct_bytes < sizeof(rt_config) ? user->struct_bytes : (uint32_t)sizeof(rt_config);
-    std::memcpy(user, &full, n);
-    user->struct_bytes = n;
+    copy_out(full, user, user->struct_bytes);
 }
 
 rt_status rt_scene_create(const rt_scene_desc *desc, rt_scene **out_scene) { return rt_scene_create_ex(desc, nullptr, out_scene); }
@@ -545,9 +568,7 @@ rt_status rt_scene_set_config(rt_scene *sc, const rt_config *cfg) {
 rt_status rt_scene_get_config(const rt_scene *sc, rt_config *cfg) {
     if (!sc || !cfg) return fail(RT_ERR_INVALID_ARG, "null argument");
     if (cfg->struct_bytes < 8) return fail(RT_ERR_INVALID_ARG, "rt_config.struct_bytes is not set (rt_config_init)");
-    const uint32_t n = cfg->struct_bytes < sizeof(rt_config) ? cfg->struct_bytes : (uint32_t)sizeof(rt_config);
-    std::memcpy(cfg, &sc->cfg, n);
-    cfg->struct_bytes = n;
+    copy_out(sc->cfg, cfg, cfg->struct_bytes);
     return RT_OK;
 }
 
@@ -621,8 +642,7 @@ rt_status rt_scene_create_ex(const rt_scene_desc *desc, const rt_config *user_cf
         sc->device_built = device_build;
     }
     if (hipMalloc((void **)&sc->queue, kQueueWords * 4) != hipSuccess) return bail(fail(RT_ERR_OUT_OF_MEMORY, "hipMalloc(queue) failed"));
-    if (hipEventCreate(&sc->ev_start) != hipSuccess || hipEventCreate(&sc->ev_stop) != hipSuccess)
-        return bail(fail(RT_ERR_HIP, "hipEventCreate failed"));
+    if (sc->clock[kClockRender].make() != RT_OK) return bail(fail(RT_ERR_HIP, "hipEventCreate failed"));
     sc->num_internal = pk.num_internal;
     sc->num_top_pairs = pk.num_top_pairs;
     sc->num_spheres = (int32_t)pk.sphere_mat.size();
@@ -650,21 +670,10 @@ rt_status rt_scene_destroy(rt_scene *sc) {
     if (sc->ev_fork) (void)hipEventDestroy(sc->ev_fork);
     if (sc->ev_join) (void)hipEventDestroy(sc->ev_join);
     for (hipEvent_t e : sc->pass_events) (void)hipEventDestroy(e);
-    if (sc->ev_start) (void)hipEventDestroy(sc->ev_start);
-    if (sc->ev_stop) (void)hipEventDestroy(sc->ev_stop);
-    (void)hipFree(sc->aov_walked);
     for (hipEvent_t e : sc->aov_events) (void)hipEventDestroy(e);
-    if (sc->aov_start) (void)hipEventDestroy(sc->aov_start);
-    if (sc->aov_stop) (void)hipEventDestroy(sc->aov_stop);
+    for (CallClock &c : sc->clock) c.destroy();         // (every family's events and counter words)
     (void)hipFree(sc->adapt_mom); (void)hipFree(sc->adapt_list); (void)hipFree(sc->adapt_work); (void)hipFree(sc->adapt_counters);
-    if (sc->adapt_start) (void)hipEventDestroy(sc->adapt_start);
-    if (sc->adapt_stop) (void)hipEventDestroy(sc->adapt_stop);
-    (void)hipFree(sc->lens_queue);
-    (void)hipFree(sc->nee_index_dev); (void)hipFree(sc->nee_cdf_dev); (void)hipFree(sc->nee_pmf_dev); (void)hipFree(sc->light_queue);
-    if (sc->light_start) (void)hipEventDestroy(sc->light_start);
-    if (sc->light_stop) (void)hipEventDestroy(sc->light_stop);
-    if (sc->lens_start) (void)hipEventDestroy(sc->lens_start);
-    if (sc->lens_stop) (void)hipEventDestroy(sc->lens_stop);
+    (void)hipFree(sc->nee_index_dev); (void)hipFree(sc->nee_cdf_dev); (void)hipFree(sc->nee_pmf_dev);
     for (rt_scene::Feedback &f : sc->feedback) {
         if (f.done) { if (f.pending) (void)hipEventSynchronize(f.done); (void)hipEventDestroy(f.done); }
         if (f.start) (void)hipEventDestroy(f.start);
@@ -717,7 +726,7 @@ rt_status frame_parts(rt_scene *sc, float &trace, float &rework, float &primary)
         const float scale = untimed_scale((int)sc->last.trace_launches, sc->timed_passes);
         trace *= scale; rework *= scale; primary *= scale;
         float ms = 0.0f;          // + the per-pixel candidate lists, made once per call before the first pass
-        HIP_TRY(hipEventElapsedTime(&ms, sc->ev_start, sc->pass_events[0]));
+        HIP_TRY(hipEventElapsedTime(&ms, sc->clock[kClockRender].first, sc->pass_events[0]));
         primary += ms;
     }
     return RT_OK;
@@ -890,18 +899,20 @@ bool camera_inside_margins(const rt_scene *sc, const rt_camera_data *cam) {
     return camera_within(cam, sc->guard.origin_center, (double)sc->guard.origin_radius * sc->guard.origin_radius) &&
            !(sc->guard.num_small > 0 && !camera_within(cam, sc->guard.center, (double)sc->guard.d0_sq * (1.0 - 1e-5)));
 }
+// The guarded walk is the handle's choice for this scene: eligible, not ruled out by rt_config, wanted at this size, not paused
+bool guarded_chosen(const rt_scene *sc, const rtk::KParams &P) {
+    const rt_config &cfg = sc->cfg;
+    return sc->guard.ok && cfg.traversal != RT_TRAVERSAL_EXACT && P.root >= 0 && guarded_wanted(cfg, (int64_t)P.num_spheres + P.num_planes) &&
+           !(sc->guard_paused && !cfg.guard_keep);
+}
 
 // Step 2 of rt_render: the exact or the guarded walk, and the guarded walk's tree re-packed for a camera beyond its margins (which
 // changes the handle's tables: P is filled again)
 rt_status choose_traversal(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shard, const Tile *tile, hipStream_t stream, rtk::KParams &P,
                            bool &guarded, bool &exploring) {
     const rt_config &cfg = sc->cfg;
-    // (RT_KERNEL_WAVEFRONT and rt_config.wide_nodes = 1 were experiments, retired: −37 % and −6 % on S-rtiow; docs/LOG.md)
-    if (cfg.kernel == RT_KERNEL_WAVEFRONT) return fail(RT_ERR_UNSUPPORTED, "RT_KERNEL_WAVEFRONT was an experiment and has been retired: not in this library");
-    if (cfg.wide_nodes > 0) return fail(RT_ERR_UNSUPPORTED, "rt_config.wide_nodes = 1 was an experiment and has been retired: not in this library");
     // only for eligible scenes (and, below, for cameras within the margins and tables that leave room for a useful stack)
-    guarded = sc->guard.ok && cfg.traversal != RT_TRAVERSAL_EXACT && P.root >= 0 && guarded_wanted(cfg, (int64_t)P.num_spheres + P.num_planes) &&
-              !(sc->guard_paused && !cfg.guard_keep);
+    guarded = guarded_chosen(sc, P);
     // (AUTO only: one exact frame to time the guarded walk against — judge_frame)
     exploring = guarded && sc->explore_exact && cfg.traversal == RT_TRAVERSAL_AUTO && !cfg.guard_keep;
     if (exploring) guarded = false;
@@ -930,10 +941,7 @@ rt_status choose_traversal(rt_scene *sc, const rt_camera_data *cam, const rt_sha
 // origin lies on the segment between the two ends' origins, and the reach is a ball: both ends checked with the radius reduced by
 // sqrt(2) R cover every pose between them (a hair of slack for the rounding of the interpolated pose and of the lens point).
 bool lens_guarded(const rt_scene *sc, const rtk::KParams &P, const rtk::LensCam &C) {
-    const rt_config &cfg = sc->cfg;
-    if (!(sc->guard.ok && cfg.traversal != RT_TRAVERSAL_EXACT && P.root >= 0 && guarded_wanted(cfg, (int64_t)P.num_spheres + P.num_planes) &&
-          !(sc->guard_paused && !cfg.guard_keep)))
-        return false;
+    if (!guarded_chosen(sc, P)) return false;
     auto within = [&](int end, const float c[3], double reach) {
         reach -= std::sqrt(2.0) * (double)C.radius;
         if (!(reach > 0.0)) return false;
@@ -1133,6 +1141,18 @@ LaunchPlan plan_launch(const rt_scene *sc, const rt_camera_data *cam, const rtk:
     return L;
 }
 
+// a handle buffer of at least `need` elements (its contents are not kept)
+template <class T>
+rt_status grow(T *&buf, size_t &have, size_t need, hipStream_t stream) {
+    if (have >= need) return RT_OK;
+    HIP_TRY(hipStreamSynchronize(stream));          // (the old one may still be in use on this stream)
+    (void)hipFree(buf);
+    buf = nullptr;
+    have = 0;
+    HIP_TRY(hipMalloc((void **)&buf, need * sizeof(T)));
+    have = need;
+    return RT_OK;
+}
 // Step 4 of rt_render: the handle's buffers for this call, grown where they are short.  A device short of memory for the view lists
 // renders without the primary-visibility pass (plan.prim = false).
 rt_status reserve_buffers(rt_scene *sc, const rtk::KParams &P, uint32_t num_pixels, hipStream_t stream, LaunchPlan &plan, rtaccel::PassPlan &passes) {
@@ -1141,14 +1161,7 @@ rt_status reserve_buffers(rt_scene *sc, const rtk::KParams &P, uint32_t num_pixe
     if (plan.guarded()) {
         // flagged-sample list: a quarter of a pass's samples (a fuller list means "re-walk everything")
         const size_t cap = (size_t)num_pixels * (size_t)passes.pass_size / 4 + 65536;
-        if (sc->flag_cap < cap) {
-            HIP_TRY(hipStreamSynchronize(stream));
-            (void)hipFree(sc->flag_list);
-            sc->flag_list = nullptr;
-            sc->flag_cap = 0;
-            HIP_TRY(hipMalloc((void **)&sc->flag_list, cap * sizeof(uint32_t)));
-            sc->flag_cap = cap;
-        }
+        if (const rt_status st = grow(sc->flag_list, sc->flag_cap, cap, stream)) return st;
         if (cfg.overlap_rework >= 0 && sc->dirty_cap < (size_t)num_pixels) {
             HIP_TRY(hipStreamSynchronize(stream));
             (void)hipFree(sc->dirty); (void)hipFree(sc->dirty_list);
@@ -1247,44 +1260,260 @@ rt_status check_sample_range(const char *what, int32_t sample_first, int32_t spp
     return RT_OK;
 }
 
+// ---- what the frame drivers share (render_impl, aov_impl, adaptive_impl, render_light_impl) -----------------------------------------
+// What every render-type call checks before it enqueues anything, in the order its errors are reported, and what it sets up: P, the
+// stream, the pixel count, *timing zeroed.  missing: the message for a required buffer that is NULL (null: none is); light_device: the
+// device of a light that is an object of its own (null: none); late(): the call's own last refusal, after the shared ones and before
+// *timing is written.  nothing_to_do(): a shard without rows — the caller returns RT_OK.
+struct Frame {
+    rtk::KParams P;
+    hipStream_t stream = nullptr;
+    uint32_t num_pixels = 0;
+    bool nothing_to_do() const { return P.local_rows == 0; }
+};
+template <class Late>
+rt_status frame_prologue(const char *what, const rt_scene *sc, const rt_camera_data *cam, const rt_shard *shard, const Tile *tile, int32_t sample_first,
+                         const int *light_device, const char *missing, void *hip_stream, rt_timing *timing, Frame &F, Late late) {
+    rt_status st = fill_params(sc, cam, shard, F.P, tile);
+    if (st != RT_OK) return st;
+    if ((st = check_sample_range(what, sample_first, F.P.spp)) != RT_OK) return st;
+    if ((st = check_device(sc)) != RT_OK) return st;
+    if (light_device && *light_device != sc->device) return fail(RT_ERR_INVALID_ARG, std::string(what) + ": the environment was created on another device than the scene");
+    if (missing) return fail(RT_ERR_INVALID_ARG, missing);
+    if ((st = timing_check(timing)) != RT_OK) return st;
+    F.num_pixels = (uint32_t)F.P.local_rows * (uint32_t)F.P.row_w;
+    if ((st = late()) != RT_OK) return st;
+    F.stream = (hipStream_t)hip_stream;
+    timing_out(rt_timing{}, timing);
+    return RT_OK;
+}
+rt_status nothing_late() { return RT_OK; }
+// no samples, or no depth: the reference's loops add nothing — all-zero sums
+rt_status blank_frame(float *d_fb_sum, const Frame &F, int32_t sync) {
+    HIP_TRY(hipMemsetAsync(d_fb_sum, 0, (size_t)F.num_pixels * 3 * sizeof(float), F.stream));
+    if (sync) HIP_TRY(hipStreamSynchronize(F.stream));
+    return RT_OK;
+}
+
+// P's view of the sample slab (after reserve_slab / reserve_buffers), with rows for passes of pass_size samples
+void bind_slab(const rt_scene *sc, rtk::KParams &P, uint32_t num_pixels, int pass_size) {
+    P.slab = sc->slab;
+    P.num_pixels = num_pixels;
+    P.slab_pitch = slab_pitch_of(pass_size);
+}
+// Workgroups of a trace launch: what fills the device at the shape's occupancy, fewer where spp samples of every pixel do not need them
+int grid_for(const rt_scene *sc, const Shape &sh, uint32_t num_pixels, int32_t spp) {
+    const uint32_t max_wgs = (uint32_t)(((uint64_t)num_pixels * (spp < 64 ? spp : 64) + rtk::kBlock - 1) / rtk::kBlock);
+    int wgs = sc->num_cus * sh.wgs_per_cu;
+    if ((uint32_t)wgs > max_wgs) wgs = (int)max_wgs;
+    return wgs < 1 ? 1 : wgs;
+}
+// registers and scratch of a kernel as the loaded code object reports them → rt_timing
+void kernel_resources(const void *kernel, uint32_t &vgprs, uint32_t &scratch) {
+    hipFuncAttributes attr;
+    const bool known = hipFuncGetAttributes(&attr, kernel) == hipSuccess;
+    vgprs = known ? (uint32_t)attr.numRegs : 0u;
+    scratch = known ? (uint32_t)attr.localSizeBytes : 0u;
+}
+// … and of the exact re-walk of a list (flagged samples, the rounds of rt_render_adaptive): the exact walk's general build
+const void *rewalk_kernel(LaunchPlan L, bool lens = false) {
+    L.walk = Walk::Exact;
+    return lens ? lens_trace_kernel(L) : trace_kernel(L);
+}
+// Its parameters: the exact walk's own vote thresholds and treelet, no stack, and a list at the finest granularity, without taper
+void set_exact_rewalk(rtk::KParams &R, const rt_config &cfg, const LaunchPlan &plan) {
+    R.k_inner = cfg.k_inner > 0 ? cfg.k_inner : 24;
+    R.k_shade = cfg.k_shade > 0 ? cfg.k_shade : 48;
+    R.stack_levels = 0;
+    R.num_top = plan.exact.num_top;
+    R.chunk = 64u;
+    R.taper_shift = 0;
+}
+// accumulate_kernel: a pass's slab rows (P.slab, P.pass_count of them per pixel) added to P.fb strictly in sample order.  Which pixels:
+struct Acc {
+    int32_t first_pass = 0;                                     // the sums start from zero
+    uint32_t *dirty = nullptr;                                  // the overlapped re-walk's marks
+    const uint32_t *list = nullptr, *list_count = nullptr;      // only these pixels (accumulate_kernel<true>)
+    const uint32_t *abandon = nullptr;                          // the pass's abandon word: set, the launch stands down — or,
+    uint32_t run_if_abandoned = 0u;                             // … with this, runs only then
+    static Acc every_pixel(int pass) { Acc a; a.first_pass = pass == 0 ? 1 : 0; return a; }
+    static Acc unmarked(int pass, uint32_t *dirty, const uint32_t *abandon) { Acc a = every_pixel(pass); a.dirty = dirty; a.abandon = abandon; return a; }
+    static Acc onto_sums(const uint32_t *list, const uint32_t *count) { Acc a; a.list = list; a.list_count = count; return a; }      // (rt_render_adaptive's rounds)
+    static Acc marked(int pass, uint32_t *dirty, const uint32_t *list, const uint32_t *count, const uint32_t *abandon) {
+        Acc a = onto_sums(list, count); a.first_pass = pass == 0 ? 1 : 0; a.dirty = dirty; a.abandon = abandon; return a;
+    }
+    // the third launch of a pass the guarded launch gave up: every pixel, once the re-walk of everything is done
+    static Acc abandoned_pass(int pass, const uint32_t *abandon) { Acc a = every_pixel(pass); a.abandon = abandon; a.run_if_abandoned = 1u; return a; }
+};
+// the accumulate launches' shape: a wave per 64 pixels
+dim3 acc_grid(uint32_t num_pixels) { return dim3((num_pixels + 64 * rtk::kAccWaves - 1) / (64 * rtk::kAccWaves)); }
+// (a listed launch's pixels have rows: no sky pixel among them — no candidate lists, no background)
+void launch_accumulate(hipStream_t stream, const rtk::KParams &P, const Acc &a) {
+    if (a.list)
+        hipLaunchKernelGGL(rtk::accumulate_kernel<true>, acc_grid(P.num_pixels), dim3(64 * rtk::kAccWaves), 0, stream, P.fb, (const float *)P.slab, P.num_pixels, P.slab_pitch,
+                           P.pass_count, a.first_pass, a.dirty, a.list, a.list_count, (const uint32_t *)nullptr, 0u, 0.0f, 0.0f, 0.0f, a.abandon, a.run_if_abandoned);
+    else
+        hipLaunchKernelGGL(rtk::accumulate_kernel<false>, acc_grid(P.num_pixels), dim3(64 * rtk::kAccWaves), 0, stream, P.fb, (const float *)P.slab, P.num_pixels, P.slab_pitch,
+                           P.pass_count, a.first_pass, a.dirty, a.list, a.list_count, (const uint32_t *)P.cand, (uint32_t)rtk::kCandWords, P.bg[0], P.bg[1], P.bg[2],
+                           a.abandon, a.run_if_abandoned);
+}
+// moments_kernel<false> (rt_render_adaptive's min_spp round): the pass's luminance moments of every pixel added to mom (first_pass: from zero)
+void launch_moments(hipStream_t stream, float *mom, const rtk::KParams &P, int32_t first_pass) {
+    hipLaunchKernelGGL(rtk::moments_kernel<false>, dim3((P.num_pixels + rtk::kAdaptBlock - 1) / rtk::kAdaptBlock), dim3(rtk::kAdaptBlock), 0, stream, mom,
+                       (const float *)P.slab, P.num_pixels, P.slab_pitch, P.pass_count, first_pass, (const uint32_t *)nullptr, (const uint32_t *)nullptr,
+                       (const uint32_t *)P.cand, (uint32_t)rtk::kCandWords, P.bg[0], P.bg[1], P.bg[2]);
+}
+// per-pass timing events of a family, made on demand
+rt_status grow_events(std::vector<hipEvent_t> &events, size_t n) {
+    while (events.size() < n) {
+        hipEvent_t e;
+        HIP_TRY(hipEventCreate(&e));
+        events.push_back(e);
+    }
+    return RT_OK;
+}
+// What the launch plan of a frame says in an rt_timing
+rt_timing plan_timing(const rt_scene *sc, const LaunchPlan &plan, int wgs, int passes, const void *trace) {
+    const Shape &shape = plan.trace_shape();
+    rt_timing t{};
+    t.num_workgroups = (uint32_t)wgs;
+    t.workgroup_size = plan.block();
+    t.lds_bytes = shape.lds_bytes;
+    t.scene_in_lds = shape.in_lds ? 1u : 0u;
+    t.trace_launches = (uint32_t)passes;
+    t.guarded = plan.guarded() ? 1u : 0u;
+    t.guard_unproven = (plan.guarded() && gamma_unproven(sc->cfg)) ? 1u : 0u;
+    t.kernel = RT_KERNEL_MEGA;
+    t.guard_dynamic = plan.dyn ? 1u : 0u;
+    t.front_primitives = plan.guarded() ? (uint32_t)sc->guard.num_front : 0u;
+    t.wide_nodes = plan.wide ? 1u : 0u;
+    t.sphere_only = plan.sphere_only() ? 1u : 0u;
+    t.primary_visibility = plan.prim ? 1u : 0u;
+    kernel_resources(trace, t.trace_vgprs, t.trace_scratch_bytes);
+    return t;
+}
+// What a finished frame left in its counter block: the flagged samples (list slots handed out less the ones nobody filled) and the
+// passes the guarded launch gave up → t; the abort word of a developer build's tripwire → an error
+rt_status read_counters(const uint32_t *queue, int passes, rt_timing &t) {
+    if (t.guarded) {
+        std::vector<uint32_t> counts((size_t)passes), gave_up((size_t)passes), holes((size_t)passes);
+        HIP_TRY(hipMemcpy(counts.data(), queue + kQueueFlag, counts.size() * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(holes.data(), queue + kQueueHoles, holes.size() * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(gave_up.data(), queue + kQueueAbandon, gave_up.size() * 4, hipMemcpyDeviceToHost));
+        t.flagged_samples = 0;
+        t.abandoned_passes = 0;
+        for (size_t p = 0; p < counts.size(); ++p) {
+            t.flagged_samples += counts[p] - holes[p];
+            t.abandoned_passes += gave_up[p] != 0u ? 1u : 0u;
+        }
+    }
+    uint32_t abort_code = 0;
+    HIP_TRY(hipMemcpy(&abort_code, queue + kQueueStats + 15, 4, hipMemcpyDeviceToHost));
+    if (abort_code != 0) return fail(RT_ERR_HIP, "render kernel aborted (protocol timeout, code " + std::to_string(abort_code) + ")");
+    return RT_OK;
+}
+
+// What a frame of render_impl's is to the handle.  A frame of its history (rt_render*, the min_spp round of rt_render_adaptive) counts in
+// the handle's counter block, is timed by the handle's clock and per-pass events, reports to a feedback slot for the handle's judgement
+// of its guarded walk, owns the key of the view lists and is what rt_last_timing describes (sc->last*).  A frame outside it
+// (rt_render_lens) has the handle's walk machinery and none of its memory of past frames: a clock and a counter block of its own, no
+// per-pass events, no feedback, and its record goes to the caller alone.
+struct FrameBook {
+    bool history = true;
+    CallClock *clock = nullptr;
+    uint32_t *queue = nullptr;                  // the counter block the frame counts in (kQueue*)
+    int timed_passes = 0;                       // passes with events of their own
+    rt_scene::Feedback *feedback = nullptr;     // the slot the frame reports to
+};
+// before the first launch: the counter block cleared, the feedback slot taken, the clock started
+rt_status open_book(rt_scene *sc, bool history, int passes, hipStream_t stream, FrameBook &B) {
+    rt_status st = RT_OK;
+    B.history = history;
+    B.clock = &sc->clock[history ? kClockRender : kClockLens];
+    if (!history && (st = B.clock->make(kQueueWords)) != RT_OK) return st;
+    B.queue = history ? sc->queue : B.clock->words;
+    HIP_TRY(hipMemsetAsync(B.queue, 0, kQueueWords * 4, stream));
+    if (history) {
+        if ((st = acquire_feedback(sc, &B.feedback)) != RT_OK) return st;
+        HIP_TRY(hipEventRecord(B.feedback->start, stream));
+        B.timed_passes = passes < kTimedPasses ? passes : kTimedPasses;
+        if ((st = grow_events(sc->pass_events, 4 * (size_t)B.timed_passes)) != RT_OK) return st;
+        sc->timed_passes = 0;
+    }
+    return B.clock->start(stream);
+}
+// after the last launch: the clock stopped, and the frame's record — to the caller alone, or left with the handle for later calls
+rt_status close_book(rt_scene *sc, const FrameBook &B, const rt_timing &record, const rtk::KParams &P, int passes, bool exploring, hipStream_t stream,
+                     int32_t sync, rt_timing *timing) {
+    rt_status st = B.clock->stop(stream);
+    if (st != RT_OK) return st;
+    const uint64_t samples = (uint64_t)P.num_pixels * (uint64_t)P.spp;
+    if (!B.history) {
+        rt_timing t = record;
+        t.traced_samples = samples;
+        t.guard_paused = sc->guard_paused ? 1u : 0u;
+        if (sync) {
+            if ((st = B.clock->elapsed(t.kernel_ms)) != RT_OK) return st;
+            if ((st = read_counters(B.queue, passes, t)) != RT_OK) return st;
+        }
+        timing_out(t, timing);
+        return RT_OK;
+    }
+    // flagged counts and abandon words of this call → pinned host memory, and the frame's end, for a later call's poll_feedback
+    rt_scene::Feedback &f = *B.feedback;
+    if (record.guarded) {
+        HIP_TRY(hipMemcpyAsync(f.host, B.queue + kQueueFlag, (size_t)passes * 4, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(f.host + kMaxPasses, B.queue + kQueueAbandon, (size_t)passes * 4, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(f.host + 2 * kMaxPasses, B.queue + kQueueHoles, (size_t)passes * 4, hipMemcpyDeviceToHost, stream));
+    }
+    HIP_TRY(hipEventRecord(f.done, stream));
+    f.pending = true;
+    f.guarded = record.guarded != 0u;
+    f.exploring = exploring;
+    f.passes = passes;
+    f.samples = samples;
+    f.serial = ++sc->frame_serial;
+    sc->timed = true;
+    sc->last = record;
+    sc->last_passes = passes;
+    sc->last_samples = samples;
+    sc->last_traced_pixels = record.primary_visibility ? P.traced_pixels : nullptr;
+    sc->last_spp = P.spp;
+    if (sync) return rt_last_timing(sc, timing);
+    timing_out(sc->last, timing);
+    return RT_OK;
+}
+
 // rt_render, rt_render_tile and rt_render_samples: whole rows of a shard, or a rectangle; samples [sample_first, sample_first + spp).
 // moments (rt_render_adaptive's min_spp round; null for every other call): each pass's luminance moments are added there as well.
 // lens (rt_render_lens; null for every other call): every sample starts from the lens / moving camera (render_lens_kernel), without
-// candidate lists; the handle's own state — its walk choice and judgement, the re-pack, the view lists, what rt_last_timing reports —
-// is left as it was, and *timing gets this call's record.
+// candidate lists or a re-pack, and the frame is none of the handle's history (FrameBook): *timing gets this call's record.
 rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shard, const Tile *tile, float *d_fb_sum, void *hip_stream,
                       int32_t sync, rt_timing *timing, int32_t sample_first = 0, float *moments = nullptr, const rtk::LensCam *lens = nullptr) {
     // ---- 1. validate, fill P
-    rtk::KParams P;
-    rt_status st = fill_params(sc, cam, shard, P, tile);
+    Frame F;
+    rt_status st = frame_prologue("rt_render_samples", sc, cam, shard, tile, sample_first, nullptr, d_fb_sum ? nullptr : "null framebuffer", hip_stream, timing, F,
+                                  nothing_late);
     if (st != RT_OK) return st;
-    if ((st = check_sample_range("rt_render_samples", sample_first, P.spp)) != RT_OK) return st;
-    if ((st = check_device(sc)) != RT_OK) return st;
-    if (!d_fb_sum) return fail(RT_ERR_INVALID_ARG, "null framebuffer");
-    if ((st = timing_check(timing)) != RT_OK) return st;
+    rtk::KParams &P = F.P;
     const rt_config &cfg = sc->cfg;
-    hipStream_t stream = (hipStream_t)hip_stream;
+    const hipStream_t stream = F.stream;
+    const uint32_t num_pixels = F.num_pixels;
+    const bool history = lens == nullptr;
     P.fb = d_fb_sum;
-    timing_out(rt_timing{}, timing);
     // what earlier frames of this handle reported about their guarded walk (no wait: whatever has landed by now)
-    if (!lens && (st = poll_feedback(sc, false)) != RT_OK) return st;
-    const size_t fb_bytes = (size_t)P.local_rows * P.row_w * 3 * sizeof(float);
-    if (P.local_rows == 0) return RT_OK;
-    if (P.spp <= 0 || P.max_depth <= 0) {     // the reference's loops add nothing: all-zero sums
-        HIP_TRY(hipMemsetAsync(d_fb_sum, 0, fb_bytes, stream));
-        if (sync) HIP_TRY(hipStreamSynchronize(stream));
-        if (!lens) sc->timed = false;
+    if (history && (st = poll_feedback(sc, false)) != RT_OK) return st;
+    if (F.nothing_to_do()) return RT_OK;
+    if (P.spp <= 0 || P.max_depth <= 0) {
+        if ((st = blank_frame(d_fb_sum, F, sync)) != RT_OK) return st;
+        if (history) sc->timed = false;
         return RT_OK;
     }
 
     // ---- 2. the walk, the tree re-packed for a far camera
     bool guarded = false, exploring = false;
-    if (lens) {
-        // (rt_render_samples's refusals, which choose_traversal makes for it)
-        if (cfg.kernel == RT_KERNEL_WAVEFRONT) return fail(RT_ERR_UNSUPPORTED, "RT_KERNEL_WAVEFRONT was an experiment and has been retired: not in this library");
-        if (cfg.wide_nodes > 0) return fail(RT_ERR_UNSUPPORTED, "rt_config.wide_nodes = 1 was an experiment and has been retired: not in this library");
-        guarded = lens_guarded(sc, P, *lens);
-    }
+    if ((st = refuse_retired(cfg)) != RT_OK) return st;
+    if (lens) guarded = lens_guarded(sc, P, *lens);
     else if ((st = choose_traversal(sc, cam, shard, tile, stream, P, guarded, exploring)) != RT_OK) return st;
     // ---- 3. launch shapes
     LaunchPlan plan = plan_launch(sc, cam, P, guarded, lens == nullptr);
@@ -1295,47 +1524,20 @@ rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *s
     // a forced rt_config.pass_spp included; the passes of a frame are made equally long.
     // Fewer, larger launches amortise the end-of-launch tail — on a row shard of an N-GPU frame
     // the pass grows N-fold, so a launch keeps the size it has on one GPU.
-    const uint32_t num_pixels = (uint32_t)P.local_rows * (uint32_t)P.row_w;
     rtaccel::PassPlan passes;
     if ((st = reserve_buffers(sc, P, num_pixels, stream, plan, passes)) != RT_OK) return st;
     const bool prim = plan.prim;
-    P.slab = sc->slab;
-    P.num_pixels = num_pixels;
-    P.slab_pitch = slab_pitch_of(passes.pass_size);
+    bind_slab(sc, P, num_pixels, passes.pass_size);
     bind_view_lists(sc, P, num_pixels, prim);
     P.k_inner = plan.k_inner;
     P.k_shade = plan.k_shade;
 
     // ---- 5. the passes
     const Shape &trace_shape = plan.trace_shape();
-    const uint32_t max_wgs = (uint32_t)(((uint64_t)num_pixels * (P.spp < 64 ? P.spp : 64) + rtk::kBlock - 1) / rtk::kBlock);
-    auto grid_for = [&](const Shape &sh) {
-        int wgs = sc->num_cus * sh.wgs_per_cu;
-        if ((uint32_t)wgs > max_wgs) wgs = (int)max_wgs;
-        return wgs < 1 ? 1 : wgs;
-    };
-    const int wgs = grid_for(trace_shape), rework_wgs = grid_for(plan.exact);
+    const int wgs = grid_for(sc, trace_shape, num_pixels, P.spp), rework_wgs = grid_for(sc, plan.exact, num_pixels, P.spp);
     const void *trace = lens ? lens_trace_kernel(plan) : trace_kernel(plan);
-    const void *rework = lens ? (plan.exact.in_lds ? (const void *)rtk::render_lens_kernel<true, true> : (const void *)rtk::render_lens_kernel<false, true>)
-                              : (plan.exact.in_lds ? (const void *)rtk::render_kernel<true, true> : (const void *)rtk::render_kernel<false, true>);
-    // registers and scratch of the dominant (trace) kernel as the loaded code object reports them → rt_timing
-    uint32_t trace_vgprs = 0, trace_scratch = 0;
-    {
-        hipFuncAttributes attr;
-        if (hipFuncGetAttributes(&attr, trace) == hipSuccess) {
-            trace_vgprs = (uint32_t)attr.numRegs;
-            trace_scratch = (uint32_t)attr.localSizeBytes;
-        }
-    }
-
-    // (a lens frame counts in a counter block of its own: rt_last_timing reads the last rt_render's from the handle's block)
-    uint32_t *queue = sc->queue;
-    if (lens) {
-        if (!sc->lens_queue) HIP_TRY(hipMalloc((void **)&sc->lens_queue, kQueueWords * 4));
-        queue = sc->lens_queue;
-        P.stats = queue + kQueueStats;
-    }
-    HIP_TRY(hipMemsetAsync(queue, 0, kQueueWords * 4, stream));
+    const void *rework = rewalk_kernel(plan, lens != nullptr);
+    const rt_timing record = plan_timing(sc, plan, wgs, passes.passes, trace);
     const bool overlap = plan.overlap;
     // an early return between the fork to the second stream and the join must not leave that stream running unobserved
     struct JoinOnExit {
@@ -1345,29 +1547,15 @@ rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *s
             if (listing) (void)hipStreamWaitEvent(stream, sc->ev_listed, 0);
         }
     } join_guard{sc, stream};
-    rt_scene::Feedback *feedback = nullptr;
-    if (lens) {
-        if (!sc->lens_start) {
-            HIP_TRY(hipEventCreate(&sc->lens_start));
-            HIP_TRY(hipEventCreate(&sc->lens_stop));
-        }
-        HIP_TRY(hipEventRecord(sc->lens_start, stream));
-    } else {
-        if ((st = acquire_feedback(sc, &feedback)) != RT_OK) return st;
-        HIP_TRY(hipEventRecord(feedback->start, stream));
-        HIP_TRY(hipEventRecord(sc->ev_start, stream));
-    }
+    FrameBook book;
+    if ((st = open_book(sc, history, passes.passes, stream, book)) != RT_OK) return st;
+    uint32_t *const queue = book.queue;
+    P.stats = queue + kQueueStats;
     if (prim) {
         if ((st = make_view_lists(sc, cam, P, num_pixels, stream)) != RT_OK) return st;
-    } else if (!lens) {
+    } else if (history) {
         sc->cand_key.valid = false;
     }
-    while (!lens && (int)sc->pass_events.size() < 4 * (passes.passes < kTimedPasses ? passes.passes : kTimedPasses)) {
-        hipEvent_t e;
-        HIP_TRY(hipEventCreate(&e));
-        sc->pass_events.push_back(e);
-    }
-    if (!lens) sc->timed_passes = 0;
     if (guarded) {
         // near-first walk; samples it cannot vouch for go to the list …
         P.stack_levels = plan.fast.stack_levels;
@@ -1396,7 +1584,7 @@ rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *s
     const uint64_t waves_total = (uint64_t)wgs * (plan.block() / rtk::kWave);
     for (int pass = 0; pass < passes.passes; ++pass) {
         // samples [pass_first, pass_first + pass_count) of every pixel, traced in any order into the slab …
-        const bool timed_pass = !lens && pass < kTimedPasses;
+        const bool timed_pass = pass < book.timed_passes;
         if (timed_pass) HIP_TRY(hipEventRecord(sc->pass_events[4 * pass], stream));
         if ((st = set_pass(P, passes, pass, num_pixels, sample_first)) != RT_OK) return st;
         P.queue = queue + kQueueWork + pass;
@@ -1422,17 +1610,12 @@ rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *s
             if (timed_pass) HIP_TRY(hipEventRecord(sc->pass_events[4 * pass + 2], stream));
             // … and are walked again in the reference's order, overwriting their slab entries
             rtk::KParams R = P;
-            R.k_inner = cfg.k_inner > 0 ? cfg.k_inner : 24;
-            R.k_shade = cfg.k_shade > 0 ? cfg.k_shade : 48;
-            R.stack_levels = 0;
-            R.num_top = plan.exact.num_top;
+            set_exact_rewalk(R, cfg, plan);
             R.queue = queue + kQueueRework + pass;
             R.work_list = sc->flag_list;
             R.work_count = queue + kQueueFlag + pass;
             R.work_cap = P.flag_cap;
-            R.chunk = 64u;                     // a short list: finest granularity
-            R.taper_shift = 0;
-            // … unless it turns out to be the whole pass (overflow, abandoned guarded pass): a trace launch's reservations
+            // … unless the list turns out to be the whole pass (overflow, abandoned guarded pass): a trace launch's reservations
             reservation(P.total_work, (uint64_t)rework_wgs * (rtk::kBlock / rtk::kWave), R.full_chunk, R.full_taper);
             R.dirty = nullptr;
             hipStream_t rework_stream = stream;       // the exact re-walk may go to the handle's second stream (overlap_rework)
@@ -1462,121 +1645,29 @@ rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *s
             sc->timed_passes = pass + 1;
         }
         // … then added to the pixel sums strictly in sample order
-        const dim3 acc_grid((num_pixels + 64 * rtk::kAccWaves - 1) / (64 * rtk::kAccWaves)), acc_block(64 * rtk::kAccWaves);
         if (overlap) {
+            // the pixels the re-walk may touch on the second stream, once they are listed …
             // (a pass the guarded launch gave up has rows nobody traced yet: both launches stand down — P.abandon — and a third one,
             // after the re-walk of everything, sums every pixel)
             HIP_TRY(hipStreamWaitEvent(sc->aux_stream, sc->ev_listed, 0));
             join_guard.listing = false;
-            hipLaunchKernelGGL(rtk::accumulate_kernel<true>, acc_grid, acc_block, 0, sc->aux_stream, d_fb_sum, (const float *)sc->slab, num_pixels, P.slab_pitch,
-                               P.pass_count, pass == 0 ? 1 : 0, sc->dirty, (const uint32_t *)sc->dirty_list, (const uint32_t *)(queue + kQueueDirty + pass),
-                               (const uint32_t *)nullptr, 0u, 0.0f, 0.0f, 0.0f, (const uint32_t *)P.abandon, 0u);
+            launch_accumulate(sc->aux_stream, P, Acc::marked(pass, sc->dirty, sc->dirty_list, queue + kQueueDirty + pass, P.abandon));
             HIP_TRY(hipEventRecord(sc->ev_join, sc->aux_stream));
             // … while every other pixel is accumulated here
-            hipLaunchKernelGGL(rtk::accumulate_kernel<false>, acc_grid, acc_block, 0, stream, d_fb_sum, (const float *)sc->slab, num_pixels, P.slab_pitch,
-                               P.pass_count, pass == 0 ? 1 : 0, sc->dirty, (const uint32_t *)nullptr, (const uint32_t *)nullptr, P.cand, (uint32_t)rtk::kCandWords, P.bg[0], P.bg[1], P.bg[2],
-                               (const uint32_t *)P.abandon, 0u);
+            launch_accumulate(stream, P, Acc::unmarked(pass, sc->dirty, P.abandon));
             HIP_TRY(hipStreamWaitEvent(stream, sc->ev_join, 0));
             join_guard.forked = false;
-            if (P.abandon)
-                hipLaunchKernelGGL(rtk::accumulate_kernel<false>, acc_grid, acc_block, 0, stream, d_fb_sum, (const float *)sc->slab, num_pixels, P.slab_pitch,
-                                   P.pass_count, pass == 0 ? 1 : 0, (uint32_t *)nullptr, (const uint32_t *)nullptr, (const uint32_t *)nullptr, P.cand, (uint32_t)rtk::kCandWords,
-                                   P.bg[0], P.bg[1], P.bg[2], (const uint32_t *)P.abandon, 1u);
+            if (P.abandon) launch_accumulate(stream, P, Acc::abandoned_pass(pass, P.abandon));
         } else {
-            hipLaunchKernelGGL(rtk::accumulate_kernel<false>, acc_grid, acc_block, 0, stream, d_fb_sum, (const float *)sc->slab, num_pixels, P.slab_pitch,
-                               P.pass_count, pass == 0 ? 1 : 0, (uint32_t *)nullptr, (const uint32_t *)nullptr, (const uint32_t *)nullptr, P.cand, (uint32_t)rtk::kCandWords, P.bg[0], P.bg[1], P.bg[2]);
+            launch_accumulate(stream, P, Acc::every_pixel(pass));
         }
-        if (moments) {
-            // rt_render_adaptive: the pass's luminance moments, once every row of it is final — on this stream after the join with the
-            // overlapped re-walk, and after the third accumulate launch of an abandoned pass
-            hipLaunchKernelGGL(rtk::moments_kernel<false>, dim3((num_pixels + rtk::kAdaptBlock - 1) / rtk::kAdaptBlock), dim3(rtk::kAdaptBlock), 0, stream, moments,
-                               (const float *)sc->slab, num_pixels, P.slab_pitch, P.pass_count, pass == 0 ? 1 : 0, (const uint32_t *)nullptr, (const uint32_t *)nullptr,
-                               P.cand, (uint32_t)rtk::kCandWords, P.bg[0], P.bg[1], P.bg[2]);
-        }
+        // rt_render_adaptive: the pass's luminance moments, once every row of it is final — on this stream after the join with the
+        // overlapped re-walk, and after the third accumulate launch of an abandoned pass
+        if (moments) launch_moments(stream, moments, P, pass == 0 ? 1 : 0);
     }
     HIP_TRY(hipGetLastError());
-    if (lens) {
-        // a lens frame leaves nothing for later calls: its record goes to the caller alone
-        HIP_TRY(hipEventRecord(sc->lens_stop, stream));
-        rt_timing t{};
-        t.num_workgroups = (uint32_t)wgs;
-        t.workgroup_size = plan.block();
-        t.lds_bytes = trace_shape.lds_bytes;
-        t.scene_in_lds = trace_shape.in_lds ? 1u : 0u;
-        t.trace_launches = (uint32_t)passes.passes;
-        t.guarded = guarded ? 1u : 0u;
-        t.guard_unproven = (guarded && gamma_unproven(cfg)) ? 1u : 0u;
-        t.kernel = RT_KERNEL_MEGA;
-        t.guard_dynamic = plan.dyn ? 1u : 0u;
-        t.front_primitives = guarded ? (uint32_t)sc->guard.num_front : 0u;
-        t.wide_nodes = plan.wide ? 1u : 0u;
-        t.trace_vgprs = trace_vgprs;
-        t.trace_scratch_bytes = trace_scratch;
-        t.traced_samples = (uint64_t)num_pixels * (uint64_t)P.spp;
-        t.guard_paused = sc->guard_paused ? 1u : 0u;
-        if (sync) {
-            HIP_TRY(hipEventSynchronize(sc->lens_stop));
-            HIP_TRY(hipEventElapsedTime(&t.kernel_ms, sc->lens_start, sc->lens_stop));
-            if (guarded) {
-                std::vector<uint32_t> counts((size_t)passes.passes), gave_up((size_t)passes.passes), holes((size_t)passes.passes);
-                HIP_TRY(hipMemcpy(counts.data(), queue + kQueueFlag, counts.size() * 4, hipMemcpyDeviceToHost));
-                HIP_TRY(hipMemcpy(holes.data(), queue + kQueueHoles, holes.size() * 4, hipMemcpyDeviceToHost));
-                HIP_TRY(hipMemcpy(gave_up.data(), queue + kQueueAbandon, gave_up.size() * 4, hipMemcpyDeviceToHost));
-                for (size_t p = 0; p < counts.size(); ++p) {
-                    t.flagged_samples += counts[p] - holes[p];
-                    t.abandoned_passes += gave_up[p] != 0u ? 1u : 0u;
-                }
-            }
-            uint32_t abort_code = 0;        // (the tripwire's abort word of a developer build: in this call's own counter block)
-            HIP_TRY(hipMemcpy(&abort_code, queue + kQueueStats + 15, 4, hipMemcpyDeviceToHost));
-            if (abort_code != 0) return fail(RT_ERR_HIP, "render kernel aborted (protocol timeout, code " + std::to_string(abort_code) + ")");
-        }
-        timing_out(t, timing);
-        return RT_OK;
-    }
-    HIP_TRY(hipEventRecord(sc->ev_stop, stream));
-
-    // ---- 6. what the frame leaves for later calls
-    {
-        // flagged counts and abandon words of this call → pinned host memory, and the frame's end, for a later call's poll_feedback
-        rt_scene::Feedback &f = *feedback;
-        if (guarded) {
-            HIP_TRY(hipMemcpyAsync(f.host, sc->queue + kQueueFlag, (size_t)passes.passes * 4, hipMemcpyDeviceToHost, stream));
-            HIP_TRY(hipMemcpyAsync(f.host + kMaxPasses, sc->queue + kQueueAbandon, (size_t)passes.passes * 4, hipMemcpyDeviceToHost, stream));
-            HIP_TRY(hipMemcpyAsync(f.host + 2 * kMaxPasses, sc->queue + kQueueHoles, (size_t)passes.passes * 4, hipMemcpyDeviceToHost, stream));
-        }
-        HIP_TRY(hipEventRecord(f.done, stream));
-        f.pending = true;
-        f.guarded = guarded;
-        f.exploring = exploring;
-        f.passes = passes.passes;
-        f.samples = (uint64_t)num_pixels * (uint64_t)P.spp;
-        f.serial = ++sc->frame_serial;
-    }
-    sc->timed = true;
-    sc->last = rt_timing{};
-    sc->last.num_workgroups = (uint32_t)wgs;
-    sc->last.workgroup_size = plan.block();
-    sc->last.lds_bytes = trace_shape.lds_bytes;
-    sc->last.scene_in_lds = trace_shape.in_lds ? 1u : 0u;
-    sc->last.trace_launches = (uint32_t)passes.passes;
-    sc->last.guarded = guarded ? 1u : 0u;
-    sc->last.guard_unproven = (guarded && gamma_unproven(cfg)) ? 1u : 0u;
-    sc->last.kernel = RT_KERNEL_MEGA;
-    sc->last.guard_dynamic = plan.dyn ? 1u : 0u;
-    sc->last.front_primitives = guarded ? (uint32_t)sc->guard.num_front : 0u;
-    sc->last.wide_nodes = plan.wide ? 1u : 0u;
-    sc->last.sphere_only = plan.sphere_only() ? 1u : 0u;
-    sc->last.primary_visibility = prim ? 1u : 0u;
-    sc->last.trace_vgprs = trace_vgprs;
-    sc->last.trace_scratch_bytes = trace_scratch;
-    sc->last_passes = passes.passes;
-    sc->last_samples = (uint64_t)num_pixels * (uint64_t)P.spp;
-    sc->last_traced_pixels = prim ? P.traced_pixels : nullptr;
-    sc->last_spp = P.spp;
-    if (sync) return rt_last_timing(sc, timing);
-    timing_out(sc->last, timing);
-    return RT_OK;
+    // ---- 6. what the frame leaves: for the caller, and (a frame of the handle's history) for later calls
+    return close_book(sc, book, record, P, passes.passes, exploring, stream, sync, timing);
 }
 
 // rt_render_aov and rt_render_aov_tile (rt_aov.hip.inc).  The handle's state it may change is only what any call shares: the slab, the
@@ -1592,17 +1683,14 @@ rt_status aov_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shar
     rt_aov_buffers b{};
     std::memcpy(&b, buffers, buffers->struct_bytes < sizeof(b) ? buffers->struct_bytes : sizeof(b));
     if (!b.albedo_sum && !b.normal_sum && !b.depth_sum && !b.hit_count && !b.first_prim) return fail(RT_ERR_INVALID_ARG, "every AOV buffer is NULL");
-    rtk::KParams P;
-    rt_status st = fill_params(sc, cam, shard, P, tile);
+    Frame F;
+    rt_status st = frame_prologue("rt_render_aov_samples", sc, cam, shard, tile, sample_first, nullptr, nullptr, hip_stream, timing, F, nothing_late);
     if (st != RT_OK) return st;
-    if ((st = check_sample_range("rt_render_aov_samples", sample_first, P.spp)) != RT_OK) return st;
-    if ((st = check_device(sc)) != RT_OK) return st;
-    if ((st = timing_check(timing)) != RT_OK) return st;
+    if (F.nothing_to_do()) return RT_OK;
+    rtk::KParams &P = F.P;
     const rt_config &cfg = sc->cfg;
-    hipStream_t stream = (hipStream_t)hip_stream;
-    timing_out(rt_timing{}, timing);
-    if (P.local_rows == 0) return RT_OK;
-    const uint32_t num_pixels = (uint32_t)P.local_rows * (uint32_t)P.row_w;
+    const hipStream_t stream = F.stream;
+    const uint32_t num_pixels = F.num_pixels;
     const rtk::AovOut out{b.albedo_sum, b.normal_sum, b.depth_sum, b.hit_count, b.first_prim};
     if (P.spp <= 0) {       // no samples: zero sums, no hit
         if (out.albedo) HIP_TRY(hipMemsetAsync(out.albedo, 0, (size_t)num_pixels * 12, stream));
@@ -1616,31 +1704,23 @@ rt_status aov_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shar
     // Candidate lists where the handle's next beauty frame of this view would take its camera rays from them: the guarded walk is
     // its choice (not paused, not an exact frame forced by rt_config), and its tree's margins already cover this camera — rt_render
     // would re-pack the tree for a camera outside them; this call does not, and walks the reference's order instead.
-    bool prim = sc->guard.ok && cfg.traversal != RT_TRAVERSAL_EXACT && P.root >= 0 && guarded_wanted(cfg, (int64_t)P.num_spheres + P.num_planes) &&
-                !(sc->guard_paused && !cfg.guard_keep) && cfg.kernel != RT_KERNEL_WAVEFRONT && cfg.primary_visibility >= 0 && sc->nodes != nullptr &&
+    bool prim = guarded_chosen(sc, P) && cfg.kernel != RT_KERNEL_WAVEFRONT && cfg.primary_visibility >= 0 && sc->nodes != nullptr &&
                 (sc->guard.dyn_k > 0.0f || cfg.scene_in_lds != 0);
     if (prim && (lens || !camera_inside_margins(sc, cam))) prim = false;
     rtaccel::PassPlan plan;
     if ((st = reserve_slab(sc, num_pixels, P.spp, stream, plan)) != RT_OK) return st;
     const int passes = plan.passes;
-    P.slab = sc->slab;
-    P.num_pixels = num_pixels;
-    P.slab_pitch = slab_pitch_of(plan.pass_size);
+    bind_slab(sc, P, num_pixels, plan.pass_size);
     if ((st = reserve_view_lists(sc, num_pixels, stream, prim)) != RT_OK) return st;
     bind_view_lists(sc, P, num_pixels, prim);
-    if (!sc->aov_walked) HIP_TRY(hipMalloc((void **)&sc->aov_walked, sizeof(uint32_t)));
-    if (!sc->aov_start) {
-        HIP_TRY(hipEventCreate(&sc->aov_start));
-        HIP_TRY(hipEventCreate(&sc->aov_stop));
-    }
+    // (the call's own clock and counter word — records the reference-order walk resolved — and per-pass events)
+    CallClock &clock = sc->clock[kClockAov];
+    if ((st = clock.make(1)) != RT_OK) return st;
+    uint32_t *const walked = clock.words;
     const int timed = passes < kTimedPasses ? passes : kTimedPasses;
-    while ((int)sc->aov_events.size() < 3 * timed) {
-        hipEvent_t e;
-        HIP_TRY(hipEventCreate(&e));
-        sc->aov_events.push_back(e);
-    }
-    HIP_TRY(hipEventRecord(sc->aov_start, stream));
-    HIP_TRY(hipMemsetAsync(sc->aov_walked, 0, sizeof(uint32_t), stream));
+    if ((st = grow_events(sc->aov_events, 3 * (size_t)timed)) != RT_OK) return st;
+    if ((st = clock.start(stream)) != RT_OK) return st;
+    HIP_TRY(hipMemsetAsync(walked, 0, sizeof(uint32_t), stream));
     if (prim) {
         if ((st = make_view_lists(sc, cam, P, num_pixels, stream)) != RT_OK) return st;
     } else if (!lens) {
@@ -1659,22 +1739,20 @@ rt_status aov_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shar
         const uint32_t units = prim ? (num_pixels + 3u) / 4u : (P.total_work + 255u) / 256u;
         const uint32_t rgrid = std::min<uint32_t>(units, (uint32_t)sc->num_cus * 8u);
         if (lens) hipLaunchKernelGGL(rtk::aov_resolve_lens_kernel, dim3(rgrid), dim3(256), 0, stream, P, *lens);
-        else if (prim) hipLaunchKernelGGL(rtk::aov_resolve_kernel<false>, dim3(rgrid), dim3(256), 0, stream, P, sc->aov_walked);
-        else hipLaunchKernelGGL(rtk::aov_resolve_kernel<true>, dim3(rgrid), dim3(256), 0, stream, P, sc->aov_walked);
+        else if (prim) hipLaunchKernelGGL(rtk::aov_resolve_kernel<false>, dim3(rgrid), dim3(256), 0, stream, P, walked);
+        else hipLaunchKernelGGL(rtk::aov_resolve_kernel<true>, dim3(rgrid), dim3(256), 0, stream, P, walked);
         HIP_TRY(hipGetLastError());
         if (timed_pass) HIP_TRY(hipEventRecord(sc->aov_events[3 * pass + 2], stream));
         // (2) … added to the pixel's sums in sample order
-        const dim3 acc_grid((num_pixels + 64 * rtk::kAccWaves - 1) / (64 * rtk::kAccWaves)), acc_block(64 * rtk::kAccWaves);
-        if (lens) hipLaunchKernelGGL(rtk::aov_accumulate_lens_kernel, acc_grid, acc_block, 0, stream, P, *lens, out, pass == 0 ? 1 : 0, sc->aov_walked);
-        else hipLaunchKernelGGL(rtk::aov_accumulate_kernel, acc_grid, acc_block, 0, stream, P, out, pass == 0 ? 1 : 0, sc->aov_walked);
+        if (lens) hipLaunchKernelGGL(rtk::aov_accumulate_lens_kernel, acc_grid(num_pixels), dim3(64 * rtk::kAccWaves), 0, stream, P, *lens, out, pass == 0 ? 1 : 0, walked);
+        else hipLaunchKernelGGL(rtk::aov_accumulate_kernel, acc_grid(num_pixels), dim3(64 * rtk::kAccWaves), 0, stream, P, out, pass == 0 ? 1 : 0, walked);
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipEventRecord(sc->aov_stop, stream));
+    if ((st = clock.stop(stream)) != RT_OK) return st;
     rt_timing t{};
     t.primary_visibility = prim ? 1u : 0u;
     if (sync) {
-        HIP_TRY(hipEventSynchronize(sc->aov_stop));
-        HIP_TRY(hipEventElapsedTime(&t.kernel_ms, sc->aov_start, sc->aov_stop));
+        if ((st = clock.elapsed(t.kernel_ms)) != RT_OK) return st;
         float primary = 0.0f, rework = 0.0f, ms = 0.0f;
         for (int p = 0; p < timed; ++p) {
             HIP_TRY(hipEventElapsedTime(&ms, sc->aov_events[3 * p], sc->aov_events[3 * p + 1]));
@@ -1685,18 +1763,18 @@ rt_status aov_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shar
         // (+ the lists, made before the first pass)
         primary *= untimed_scale(passes, timed);
         rework *= untimed_scale(passes, timed);
-        HIP_TRY(hipEventElapsedTime(&ms, sc->aov_start, sc->aov_events[0]));
+        HIP_TRY(hipEventElapsedTime(&ms, clock.first, sc->aov_events[0]));
         t.primary_ms = prim ? primary + ms : 0.0f;
         t.rework_ms = rework;
         const uint64_t samples = (uint64_t)num_pixels * (uint64_t)P.spp;
         t.traced_samples = samples;
         t.flagged_samples = samples;
         if (prim) {
-            uint32_t traced = 0, walked = 0;
+            uint32_t traced = 0, resolved = 0;
             HIP_TRY(hipMemcpy(&traced, P.traced_pixels, 4, hipMemcpyDeviceToHost));
-            HIP_TRY(hipMemcpy(&walked, sc->aov_walked, 4, hipMemcpyDeviceToHost));
+            HIP_TRY(hipMemcpy(&resolved, walked, 4, hipMemcpyDeviceToHost));
             t.traced_samples = (uint64_t)traced * (uint64_t)P.spp;
-            t.flagged_samples = walked;
+            t.flagged_samples = resolved;
         }
     }
     timing_out(t, timing);
@@ -1715,18 +1793,6 @@ void adaptive_defaults(rt_adaptive_params &p) {
     p.max_spp = 256;
     p.threshold = 0.02f;
 }
-// a handle buffer of at least `need` elements (its contents are not kept)
-template <class T>
-rt_status grow(T *&buf, size_t &have, size_t need, hipStream_t stream) {
-    if (have >= need) return RT_OK;
-    HIP_TRY(hipStreamSynchronize(stream));          // (the old one may still be in use on this stream)
-    (void)hipFree(buf);
-    buf = nullptr;
-    have = 0;
-    HIP_TRY(hipMalloc((void **)&buf, need * sizeof(T)));
-    have = need;
-    return RT_OK;
-}
 rt_status adaptive_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shard, const rt_adaptive_params *params, float *d_fb_sum,
                         int32_t *d_spp, float *d_moments, void *hip_stream, int32_t sync, rt_timing *timing) {
     // ---- 1. every check before anything is enqueued
@@ -1742,19 +1808,19 @@ rt_status adaptive_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard 
     if (!cam) return fail(RT_ERR_INVALID_ARG, "null scene or camera");
     rt_camera_data base = *cam;
     base.samples_per_pixel = a.min_spp;
-    rtk::KParams P;
-    rt_status st = fill_params(sc, &base, shard, P);
-    if (st != RT_OK) return st;
-    if ((st = check_device(sc)) != RT_OK) return st;
-    if (!d_fb_sum || !d_spp) return fail(RT_ERR_INVALID_ARG, "rt_render_adaptive: null framebuffer or sample counts");
-    if ((st = timing_check(timing)) != RT_OK) return st;
-    const uint32_t num_pixels = (uint32_t)P.local_rows * (uint32_t)P.row_w;
     const int32_t batch = a.batch_spp, rounds = (a.max_spp - a.min_spp) / a.batch_spp;
-    if (rounds > 0 && (uint64_t)num_pixels * (uint64_t)batch >= (1ull << 31) - 4096)
-        return fail(RT_ERR_UNSUPPORTED, "rt_render_adaptive: pixels x batch_spp beyond the work index arithmetic");
-    hipStream_t stream = (hipStream_t)hip_stream;
-    timing_out(rt_timing{}, timing);
-    if (num_pixels == 0) return RT_OK;
+    Frame F;
+    rt_status st = frame_prologue("rt_render_adaptive", sc, &base, shard, nullptr, 0, nullptr,
+                                  d_fb_sum && d_spp ? nullptr : "rt_render_adaptive: null framebuffer or sample counts", hip_stream, timing, F, [&] {
+        if (rounds > 0 && (uint64_t)F.num_pixels * (uint64_t)batch >= (1ull << 31) - 4096)
+            return fail(RT_ERR_UNSUPPORTED, "rt_render_adaptive: pixels x batch_spp beyond the work index arithmetic");
+        return RT_OK;
+    });
+    if (st != RT_OK) return st;
+    if (F.nothing_to_do()) return RT_OK;
+    rtk::KParams &P = F.P;
+    const hipStream_t stream = F.stream;
+    const uint32_t num_pixels = F.num_pixels;
 
     // ---- 2. the handle's buffers: moments, lists, work indices, counters, and a slab with rows of a round's batch
     float *mom = d_moments;
@@ -1762,17 +1828,14 @@ rt_status adaptive_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard 
     if (!mom) mom = sc->adapt_mom;
     if ((st = grow(sc->adapt_list, sc->adapt_pixels, (size_t)num_pixels * 2, stream)) != RT_OK) return st;
     if ((st = grow(sc->adapt_counters, sc->adapt_counter_words, (size_t)3 * (size_t)(rounds + 1), stream)) != RT_OK) return st;
-    const uint32_t pitch = slab_pitch_of(batch);
-    const size_t slab_need = rounds > 0 ? (size_t)num_pixels * pitch * 3 : 0;
+    const size_t slab_need = rounds > 0 ? (size_t)num_pixels * slab_pitch_of(batch) * 3 : 0;
     if (rounds > 0) {
         if ((st = grow(sc->adapt_work, sc->adapt_work_cap, (size_t)num_pixels * (size_t)batch, stream)) != RT_OK) return st;
         if ((st = grow(sc->slab, sc->slab_floats, slab_need, stream)) != RT_OK) return st;
     }
-    if (!sc->adapt_start) {
-        HIP_TRY(hipEventCreate(&sc->adapt_start));
-        HIP_TRY(hipEventCreate(&sc->adapt_stop));
-    }
-    HIP_TRY(hipEventRecord(sc->adapt_start, stream));
+    CallClock &clock = sc->clock[kClockAdaptive];
+    if ((st = clock.make()) != RT_OK) return st;
+    if ((st = clock.start(stream)) != RT_OK) return st;
 
     // ---- 3. the min_spp round: rt_render's frame, with the moments
     if ((st = render_impl(sc, &base, shard, nullptr, d_fb_sum, hip_stream, 0, nullptr, 0, mom)) != RT_OK) return st;
@@ -1781,7 +1844,7 @@ rt_status adaptive_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard 
         // min_spp unless the threshold is 0)
         HIP_TRY(hipMemsetAsync(mom, 0, (size_t)num_pixels * 8, stream));
         HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)d_spp, a.threshold == 0.0f ? a.min_spp + rounds * batch : a.min_spp, num_pixels, stream));
-        HIP_TRY(hipEventRecord(sc->adapt_stop, stream));
+        if ((st = clock.stop(stream)) != RT_OK) return st;
         if (sync) HIP_TRY(hipStreamSynchronize(stream));
         return RT_OK;
     }
@@ -1790,28 +1853,16 @@ rt_status adaptive_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard 
     // ---- 4. the rounds: the exact walk's launch shape for this view (the tables may have been re-packed by the frame: P anew)
     if ((st = fill_params(sc, &base, shard, P)) != RT_OK) return st;
     const LaunchPlan plan = plan_launch(sc, &base, P, false);
-    const rt_config &cfg = sc->cfg;
     P.fb = d_fb_sum;
-    P.slab = sc->slab;
-    P.num_pixels = num_pixels;
-    P.slab_pitch = pitch;
-    P.stack_levels = 0;
-    P.num_top = plan.exact.num_top;
-    P.k_inner = cfg.k_inner > 0 ? cfg.k_inner : 24;
-    P.k_shade = cfg.k_shade > 0 ? cfg.k_shade : 48;
-    P.chunk = 64u;                      // (lists: finest granularity, as the exact re-walk of flagged samples)
-    P.taper_shift = 0;
+    bind_slab(sc, P, num_pixels, batch);
+    set_exact_rewalk(P, sc->cfg, plan);          // (lists: finest granularity, as the exact re-walk of flagged samples)
     P.cand = nullptr; P.order = nullptr; P.traced_pixels = nullptr;       // every sample starts from the camera …
     P.resume_tag = nullptr; P.resume_state = nullptr; P.abandon = nullptr; P.dirty = nullptr; P.dirty_list = nullptr;
     P.work_list = sc->adapt_work;
     P.work_cap = num_pixels * (uint32_t)batch;                            // … and the list never stands for "every sample"
-    const void *exact = plan.exact.in_lds ? (const void *)rtk::render_kernel<true, true> : (const void *)rtk::render_kernel<false, true>;
-    int wgs = sc->num_cus * plan.exact.wgs_per_cu;
-    const uint32_t max_wgs = (uint32_t)(((uint64_t)num_pixels * (batch < 64 ? batch : 64) + rtk::kBlock - 1) / rtk::kBlock);
-    if ((uint32_t)wgs > max_wgs) wgs = (int)max_wgs;
-    if (wgs < 1) wgs = 1;
+    const void *exact = rewalk_kernel(plan);
+    const int wgs = grid_for(sc, plan.exact, num_pixels, batch);
     const dim3 pix_grid((num_pixels + rtk::kAdaptBlock - 1) / rtk::kAdaptBlock), pix_block(rtk::kAdaptBlock);
-    const dim3 acc_grid((num_pixels + 64 * rtk::kAccWaves - 1) / (64 * rtk::kAccWaves)), acc_block(64 * rtk::kAccWaves);
     const uint64_t expand_items = (uint64_t)num_pixels * (uint64_t)batch;
     const uint32_t expand_grid = (uint32_t)std::min<uint64_t>((expand_items + rtk::kAdaptBlock - 1) / rtk::kAdaptBlock, (uint64_t)sc->num_cus * 8u);
     uint32_t *lists[2] = {sc->adapt_list, sc->adapt_list + num_pixels};
@@ -1837,9 +1888,8 @@ rt_status adaptive_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard 
         reservation(P.total_work, (uint64_t)wgs * (rtk::kBlock / rtk::kWave), P.full_chunk, P.full_taper);
         HIP_TRY(launch(exact, (uint32_t)rtk::kBlock, wgs, plan.exact.lds_bytes, stream, P));
         // … added onto the running sums in slot order, and onto the moments
-        hipLaunchKernelGGL(rtk::accumulate_kernel<true>, acc_grid, acc_block, 0, stream, d_fb_sum, (const float *)sc->slab, num_pixels, pitch, batch, 0,
-                           (uint32_t *)nullptr, list, listed);
-        hipLaunchKernelGGL(rtk::moments_kernel<true>, pix_grid, pix_block, 0, stream, mom, (const float *)sc->slab, num_pixels, pitch, batch, 0, list, listed,
+        launch_accumulate(stream, P, Acc::onto_sums(list, listed));
+        hipLaunchKernelGGL(rtk::moments_kernel<true>, pix_grid, pix_block, 0, stream, mom, (const float *)P.slab, num_pixels, P.slab_pitch, batch, 0, list, listed,
                            (const uint32_t *)nullptr, 0u, 0.0f, 0.0f, 0.0f);
         n += batch;
         if (r < rounds)
@@ -1847,15 +1897,13 @@ rt_status adaptive_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard 
                                lists[r & 1], counters + 3 * r, n, batch, a.max_spp, a.threshold);
         HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipEventRecord(sc->adapt_stop, stream));
+    if ((st = clock.stop(stream)) != RT_OK) return st;
     if (!sync) return RT_OK;
     // what rt_last_timing reports for the min_spp round, with the whole call's kernel_ms and every trace launch of it
     rt_timing t;
-    std::memset(&t, 0, sizeof(t));
-    t.struct_bytes = (uint32_t)sizeof(t);
+    rt_timing_init(&t);
     if ((st = rt_last_timing(sc, &t)) != RT_OK) return st;
-    HIP_TRY(hipEventSynchronize(sc->adapt_stop));
-    HIP_TRY(hipEventElapsedTime(&t.kernel_ms, sc->adapt_start, sc->adapt_stop));
+    if ((st = clock.elapsed(t.kernel_ms)) != RT_OK) return st;
     t.trace_launches += (uint32_t)rounds;
     timing_out(t, timing);
     return RT_OK;
@@ -1870,92 +1918,82 @@ template <class Light, class MakeLight>
 rt_status render_light_impl(const char *what, void (*trace)(rtk::KParams, Light), const int *light_device, MakeLight make_light, rt_scene *sc,
                             const rt_camera_data *cam, const rt_shard *shard, int32_t sample_first, float *d_fb_sum, void *hip_stream, int32_t sync,
                             rt_timing *timing) {
-    rtk::KParams P;
-    rt_status st = fill_params(sc, cam, shard, P);
+    Frame F;
+    rt_status st = frame_prologue(what, sc, cam, shard, nullptr, sample_first, light_device, d_fb_sum ? nullptr : "null framebuffer", hip_stream, timing, F,
+                                  [&] { return refuse_retired(sc->cfg); });
     if (st != RT_OK) return st;
-    if ((st = check_sample_range(what, sample_first, P.spp)) != RT_OK) return st;
-    if ((st = check_device(sc)) != RT_OK) return st;
-    if (light_device && *light_device != sc->device) return fail(RT_ERR_INVALID_ARG, std::string(what) + ": the environment was created on another device than the scene");
-    if (!d_fb_sum) return fail(RT_ERR_INVALID_ARG, "null framebuffer");
-    if ((st = timing_check(timing)) != RT_OK) return st;
-    if (sc->cfg.kernel == RT_KERNEL_WAVEFRONT) return fail(RT_ERR_UNSUPPORTED, "RT_KERNEL_WAVEFRONT was an experiment and has been retired: not in this library");
-    if (sc->cfg.wide_nodes > 0) return fail(RT_ERR_UNSUPPORTED, "rt_config.wide_nodes = 1 was an experiment and has been retired: not in this library");
-    hipStream_t stream = (hipStream_t)hip_stream;
-    timing_out(rt_timing{}, timing);
-    const size_t fb_bytes = (size_t)P.local_rows * P.row_w * 3 * sizeof(float);
-    if (P.local_rows == 0) return RT_OK;
-    if (P.spp <= 0 || P.max_depth <= 0) {
-        HIP_TRY(hipMemsetAsync(d_fb_sum, 0, fb_bytes, stream));
-        if (sync) HIP_TRY(hipStreamSynchronize(stream));
-        return RT_OK;
-    }
+    if (F.nothing_to_do()) return RT_OK;
+    rtk::KParams &P = F.P;
+    const hipStream_t stream = F.stream;
+    const uint32_t num_pixels = F.num_pixels;
+    if (P.spp <= 0 || P.max_depth <= 0) return blank_frame(d_fb_sum, F, sync);
     Light T;
     if ((st = make_light(T)) != RT_OK) return st;
     P.fb = d_fb_sum;
-    const uint32_t num_pixels = (uint32_t)P.local_rows * (uint32_t)P.row_w;
     rtaccel::PassPlan passes;
     if ((st = reserve_slab(sc, num_pixels, P.spp, stream, passes)) != RT_OK) return st;
-    P.slab = sc->slab;
-    P.num_pixels = num_pixels;
-    P.slab_pitch = slab_pitch_of(passes.pass_size);
-    P.cand = nullptr;
-    P.order = nullptr;
+    bind_slab(sc, P, num_pixels, passes.pass_size);          // (no candidate lists: fill_params left P.cand and P.order null)
     const void *kernel = (const void *)trace;
     int per_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, rtk::kLightBlock, 0) != hipSuccess || per_cu < 1) {
         (void)hipGetLastError();
         per_cu = 1;
     }
-    hipFuncAttributes attr;
-    uint32_t vgprs = 0, scratch = 0;
-    if (hipFuncGetAttributes(&attr, kernel) == hipSuccess) {
-        vgprs = (uint32_t)attr.numRegs;
-        scratch = (uint32_t)attr.localSizeBytes;
-    }
-    if (!sc->light_queue) HIP_TRY(hipMalloc((void **)&sc->light_queue, kMaxPasses * 4));
-    if (!sc->light_start) HIP_TRY(hipEventCreate(&sc->light_start));
-    if (!sc->light_stop) HIP_TRY(hipEventCreate(&sc->light_stop));
-    HIP_TRY(hipMemsetAsync(sc->light_queue, 0, kMaxPasses * 4, stream));
-    HIP_TRY(hipEventRecord(sc->light_start, stream));
+    rt_timing t{};
+    kernel_resources(kernel, t.trace_vgprs, t.trace_scratch_bytes);
+    // (a clock and work counters of the lit calls' own, one per pass — one set: a handle renders one frame at a time)
+    CallClock &clock = sc->clock[kClockLight];
+    if ((st = clock.make(kMaxPasses)) != RT_OK) return st;
+    HIP_TRY(hipMemsetAsync(clock.words, 0, kMaxPasses * 4, stream));
+    if ((st = clock.start(stream)) != RT_OK) return st;
     const int wgs = sc->num_cus * per_cu;
     const int waves_per_wg = rtk::kLightBlock / rtk::kWave;
-    int first_grid = 0;
-    const uint32_t acc_blocks = (num_pixels + 64 * rtk::kAccWaves - 1) / (64 * rtk::kAccWaves);
     for (int pass = 0; pass < passes.passes; ++pass) {
         if ((st = set_pass(P, passes, pass, num_pixels, sample_first)) != RT_OK) return st;
-        P.queue = sc->light_queue + pass;
+        P.queue = clock.words + pass;
         const uint32_t need = (P.total_work + rtk::kLightChunk - 1) / rtk::kLightChunk;          // waves that can get work at all
         int grid = wgs;
         if ((uint64_t)grid * waves_per_wg > need) grid = (int)((need + waves_per_wg - 1) / waves_per_wg);
         if (grid < 1) grid = 1;
         HIP_TRY(launch(kernel, (uint32_t)rtk::kLightBlock, grid, 0, stream, P, &T));
-        hipLaunchKernelGGL(rtk::accumulate_kernel<false>, dim3(acc_blocks), dim3(64 * rtk::kAccWaves), 0, stream, d_fb_sum, (const float *)sc->slab, num_pixels,
-                           P.slab_pitch, P.pass_count, pass == 0 ? 1 : 0, (uint32_t *)nullptr, (const uint32_t *)nullptr, (const uint32_t *)nullptr,
-                           (const uint32_t *)nullptr, (uint32_t)rtk::kCandWords, P.bg[0], P.bg[1], P.bg[2]);
+        launch_accumulate(stream, P, Acc::every_pixel(pass));
         HIP_TRY(hipGetLastError());
-        if (pass == 0) first_grid = grid;
+        if (pass == 0) t.num_workgroups = (uint32_t)grid;
     }
-    HIP_TRY(hipEventRecord(sc->light_stop, stream));
-    rt_timing t{};
-    t.num_workgroups = (uint32_t)first_grid;
+    if ((st = clock.stop(stream)) != RT_OK) return st;
     t.workgroup_size = (uint32_t)rtk::kLightBlock;
     t.trace_launches = (uint32_t)passes.passes;
     t.kernel = RT_KERNEL_MEGA;
-    t.trace_vgprs = vgprs;
-    t.trace_scratch_bytes = scratch;
     t.traced_samples = (uint64_t)num_pixels * (uint64_t)P.spp;
     t.guard_paused = sc->guard_paused ? 1u : 0u;
     if (sync) {
-        HIP_TRY(hipEventSynchronize(sc->light_stop));
-        HIP_TRY(hipEventElapsedTime(&t.kernel_ms, sc->light_start, sc->light_stop));
-        HIP_TRY(hipEventElapsedTime(&t.trace_ms, sc->light_start, sc->light_stop));
+        if ((st = clock.elapsed(t.kernel_ms)) != RT_OK) return st;
+        t.trace_ms = t.kernel_ms;
     }
     timing_out(t, timing);
     return RT_OK;
 }
 
+// a caller's params struct over the defaults already in `into` (compiled against an older, shorter struct: the fields it has)
+template <class T>
+rt_status take_params(const std::string &what, const char *name, const T *params, T &into) {
+    if (params && params->struct_bytes < 8u) return fail(RT_ERR_INVALID_ARG, what + ": " + name + ".struct_bytes below 8");
+    if (params) std::memcpy(&into, params, params->struct_bytes < sizeof(T) ? params->struct_bytes : sizeof(T));
+    return RT_OK;
+}
+// Device buffers of one probe-style call, freed on every path out of it
+struct Scratch {
+    std::vector<void *> owned;
+    template <class T> hipError_t alloc(T *&p, size_t bytes) {
+        const hipError_t e = hipMalloc((void **)&p, bytes);
+        if (e == hipSuccess) owned.push_back((void *)p);
+        return e;
+    }
+    ~Scratch() { for (void *p : owned) (void)hipFree(p); }
+};
+
 // rt_trace_samples, rt_trace_samples_nee, rt_trace_samples_env: the (i, j, s) triples checked against cam and uploaded, launch_probe(P,
-// d_light_seed) run on P with the probe columns set, the columns downloaded; device memory is freed on every path.
+// d_light_seed) run on P with the probe columns set, the columns downloaded.
 //   what: the prefix of the call's messages; final_light_seed: the lit probes' second RNG state (null: no such column)
 template <class LaunchProbe>
 rt_status run_probe(const std::string &what, rtk::KParams &P, const rt_camera_data *cam, int32_t n, const int32_t *ijs, float *radiance, int32_t *rays,
@@ -1967,13 +2005,9 @@ rt_status run_probe(const std::string &what, rtk::KParams &P, const rt_camera_da
     int32_t *d_ijs = nullptr, *d_rays = nullptr;
     float *d_rad = nullptr;
     uint32_t *d_seed = nullptr, *d_light = nullptr;
-    struct Free {
-        int32_t *&a, *&b; float *&c; uint32_t *&d, *&e;
-        ~Free() { (void)hipFree(a); (void)hipFree(b); (void)hipFree(c); (void)hipFree(d); (void)hipFree(e); }
-    } freer{d_ijs, d_rays, d_rad, d_seed, d_light};
-    if (hipMalloc((void **)&d_ijs, (size_t)n * 12) != hipSuccess || hipMalloc((void **)&d_rad, (size_t)n * 12) != hipSuccess ||
-        hipMalloc((void **)&d_rays, (size_t)n * 4) != hipSuccess || hipMalloc((void **)&d_seed, (size_t)n * 4) != hipSuccess ||
-        (final_light_seed && hipMalloc((void **)&d_light, (size_t)n * 4) != hipSuccess))
+    Scratch mem;
+    if (mem.alloc(d_ijs, (size_t)n * 12) != hipSuccess || mem.alloc(d_rad, (size_t)n * 12) != hipSuccess || mem.alloc(d_rays, (size_t)n * 4) != hipSuccess ||
+        mem.alloc(d_seed, (size_t)n * 4) != hipSuccess || (final_light_seed && mem.alloc(d_light, (size_t)n * 4) != hipSuccess))
         return fail(RT_ERR_OUT_OF_MEMORY, what + "hipMalloc failed");
     if (hipMemcpy(d_ijs, ijs, (size_t)n * 12, hipMemcpyHostToDevice) != hipSuccess) return fail(RT_ERR_HIP, what + "hipMemcpy H2D failed");
     P.probe_ijs = d_ijs; P.probe_rad = d_rad; P.probe_rays = d_rays; P.probe_seed = d_seed; P.probe_n = n;
@@ -2061,10 +2095,7 @@ rt_status lens_setup(const char *what, const rt_camera_data *open, const rt_came
     if (!open) return fail(RT_ERR_INVALID_ARG, w + ": null camera");
     rt_lens_params lp;
     rt_lens_params_init(&lp);
-    if (params) {
-        if (params->struct_bytes < 8u) return fail(RT_ERR_INVALID_ARG, w + ": rt_lens_params.struct_bytes below 8");
-        std::memcpy(&lp, params, params->struct_bytes < sizeof(lp) ? params->struct_bytes : sizeof(lp));
-    }
+    if (const rt_status st = take_params(w, "rt_lens_params", params, lp)) return st;
     if (close && (close->image_width != open->image_width || close->image_height != open->image_height ||
                   close->samples_per_pixel != open->samples_per_pixel || close->max_depth != open->max_depth ||
                   std::memcmp(close->background.e, open->background.e, sizeof(open->background.e)) != 0))
@@ -2120,11 +2151,11 @@ rt_status rt_lens_camera_rays(const rt_camera_data *cam_open, const rt_camera_da
     int32_t *d_ijs = nullptr;
     float *d_o = nullptr, *d_d = nullptr;
     uint32_t *d_s = nullptr;
-    struct Free { int32_t *&a; float *&b, *&c; uint32_t *&d; ~Free() { (void)hipFree(a); (void)hipFree(b); (void)hipFree(c); (void)hipFree(d); } } freer{d_ijs, d_o, d_d, d_s};
-    HIP_TRY(hipMalloc((void **)&d_ijs, (size_t)n * 12));
-    HIP_TRY(hipMalloc((void **)&d_o, (size_t)n * 12));
-    HIP_TRY(hipMalloc((void **)&d_d, (size_t)n * 12));
-    HIP_TRY(hipMalloc((void **)&d_s, (size_t)n * 4));
+    Scratch mem;
+    HIP_TRY(mem.alloc(d_ijs, (size_t)n * 12));
+    HIP_TRY(mem.alloc(d_o, (size_t)n * 12));
+    HIP_TRY(mem.alloc(d_d, (size_t)n * 12));
+    HIP_TRY(mem.alloc(d_s, (size_t)n * 4));
     HIP_TRY(hipMemcpy(d_ijs, ijs, (size_t)n * 12, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(rtk::lens_ray_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, C, (const int32_t *)d_ijs, n, d_o, d_d, d_s);
     HIP_TRY(hipGetLastError());
@@ -2147,10 +2178,7 @@ rt_status nee_setup(const char *what, const rt_nee_params *params, int32_t &mis)
     const std::string w(what);
     rt_nee_params np;
     rt_nee_params_init(&np);
-    if (params) {
-        if (params->struct_bytes < 8u) return fail(RT_ERR_INVALID_ARG, w + ": rt_nee_params.struct_bytes below 8");
-        std::memcpy(&np, params, params->struct_bytes < sizeof(np) ? params->struct_bytes : sizeof(np));
-    }
+    if (const rt_status st = take_params(w, "rt_nee_params", params, np)) return st;
     if (np.mis != 0 && np.mis != 1) return fail(RT_ERR_INVALID_ARG, w + ": mis must be 0 or 1");
     mis = np.mis;
     return RT_OK;
@@ -2310,10 +2338,7 @@ void env_cdf(const double *w, int32_t n, double total, float *cdf) {
 rt_status env_setup(const char *what, const rt_env_params *params, rt_env_params &np) {
     const std::string w(what);
     rt_env_params_init(&np);
-    if (params) {
-        if (params->struct_bytes < 8u) return fail(RT_ERR_INVALID_ARG, w + ": rt_env_params.struct_bytes below 8");
-        std::memcpy(&np, params, params->struct_bytes < sizeof(np) ? params->struct_bytes : sizeof(np));
-    }
+    if (const rt_status st = take_params(w, "rt_env_params", params, np)) return st;
     if (np.mode < 0 || np.mode > 2) return fail(RT_ERR_INVALID_ARG, w + ": mode must be 0, 1 or 2");
     if (!(std::isfinite(np.scale) && np.scale >= 0.0f)) return fail(RT_ERR_INVALID_ARG, w + ": scale must be finite and not negative");
     if (np.camera_visible != 0 && np.camera_visible != 1) return fail(RT_ERR_INVALID_ARG, w + ": camera_visible must be 0 or 1");
@@ -2443,14 +2468,11 @@ rt_status rt_env_lookup(const rt_env *env, int32_t n, const float *directions, i
     if (n == 0) return RT_OK;
     float *d_dir = nullptr, *d_rad = nullptr, *d_pl = nullptr;
     int32_t *d_tex = nullptr;
-    struct Free {
-        float *&a, *&b, *&c; int32_t *&d;
-        ~Free() { (void)hipFree(a); (void)hipFree(b); (void)hipFree(c); (void)hipFree(d); }
-    } freer{d_dir, d_rad, d_pl, d_tex};
-    HIP_TRY(hipMalloc((void **)&d_dir, (size_t)n * 12));
-    HIP_TRY(hipMalloc((void **)&d_rad, (size_t)n * 12));
-    HIP_TRY(hipMalloc((void **)&d_pl, (size_t)n * 4));
-    HIP_TRY(hipMalloc((void **)&d_tex, (size_t)n * 4));
+    Scratch mem;
+    HIP_TRY(mem.alloc(d_dir, (size_t)n * 12));
+    HIP_TRY(mem.alloc(d_rad, (size_t)n * 12));
+    HIP_TRY(mem.alloc(d_pl, (size_t)n * 4));
+    HIP_TRY(mem.alloc(d_tex, (size_t)n * 4));
     HIP_TRY(hipMemcpy(d_dir, directions, (size_t)n * 12, hipMemcpyHostToDevice));
     rt_env_params np;
     rt_env_params_init(&np);
@@ -2531,24 +2553,12 @@ rt_status rt_last_timing(rt_scene *sc, rt_timing *timing) {
     if (!sc) return fail(RT_ERR_INVALID_ARG, "null argument");
     if (const rt_status ts = timing_check(timing)) return ts;
     if (sc->timed) {
-        HIP_TRY(hipEventSynchronize(sc->ev_stop));
-        HIP_TRY(hipEventElapsedTime(&sc->last.kernel_ms, sc->ev_start, sc->ev_stop));
+        if (const rt_status ps = sc->clock[kClockRender].elapsed(sc->last.kernel_ms)) return ps;
         float sum = 0.0f, rework = 0.0f, primary = 0.0f;
         if (const rt_status ps = frame_parts(sc, sum, rework, primary)) return ps;
         sc->last.trace_ms = sum;
         sc->last.rework_ms = rework;
         sc->last.primary_ms = sc->last.primary_visibility ? primary : 0.0f;
-        if (sc->last.guarded) {
-            std::vector<uint32_t> counts((size_t)sc->last_passes), gave_up((size_t)sc->last_passes), holes((size_t)sc->last_passes);
-            HIP_TRY(hipMemcpy(counts.data(), sc->queue + kQueueFlag, counts.size() * 4, hipMemcpyDeviceToHost));
-            HIP_TRY(hipMemcpy(holes.data(), sc->queue + kQueueHoles, holes.size() * 4, hipMemcpyDeviceToHost));
-            HIP_TRY(hipMemcpy(gave_up.data(), sc->queue + kQueueAbandon, gave_up.size() * 4, hipMemcpyDeviceToHost));
-            uint64_t total = 0;
-            uint32_t abandoned = 0;
-            for (size_t p = 0; p < counts.size(); ++p) { total += counts[p] - holes[p]; abandoned += gave_up[p] != 0u ? 1u : 0u; }
-            sc->last.flagged_samples = total;
-            sc->last.abandoned_passes = abandoned;
-        }
         // (the frame is done, so what it left for the handle's judgement has landed as well: a scene the guarded walk keeps handing
         // back — dense overlaps, a camera inside a sphere, … — is cheaper on the exact walk alone; later frames of this handle use it)
         if (const rt_status ps = poll_feedback(sc, true)) return ps;
@@ -2559,9 +2569,7 @@ rt_status rt_last_timing(rt_scene *sc, rt_timing *timing) {
             HIP_TRY(hipMemcpy(&traced, sc->last_traced_pixels, 4, hipMemcpyDeviceToHost));
             sc->last.traced_samples = (uint64_t)traced * (uint64_t)sc->last_spp;
         }
-        uint32_t abort_code = 0;
-        HIP_TRY(hipMemcpy(&abort_code, sc->queue + kQueueStats + 15, 4, hipMemcpyDeviceToHost));
-        if (abort_code != 0) return fail(RT_ERR_HIP, "render kernel aborted (protocol timeout, code " + std::to_string(abort_code) + ")");
+        if (const rt_status ps = read_counters(sc->queue, sc->last_passes, sc->last)) return ps;
     }
     timing_out(sc->last, timing);
     return RT_OK;
@@ -2617,29 +2625,21 @@ __global__ void __launch_bounds__(256) sphere_root_check_kernel(unsigned long lo
     atomicAdd(&out[0], bad); atomicAdd(&out[1], hits); atomicAdd(&out[2], seen);
 }
 }  // namespace rtk
-rt_status rt_debug_check_sphere_roots(uint64_t n, uint64_t out[3]) {
+// (both: a result block of three counters, zeroed, the check kernel run on it, copied to out)
+static rt_status run_math_check(bool roots, uint64_t n, uint64_t out[3]) {
     if (!out) return fail(RT_ERR_INVALID_ARG, "null argument");
     unsigned long long *d = nullptr;
-    HIP_TRY(hipMalloc(&d, 24));
-    hipError_t e = hipMemset(d, 0, 24);
-    if (e == hipSuccess) { hipLaunchKernelGGL(rtk::sphere_root_check_kernel, dim3(4096), dim3(256), 0, 0, d, (unsigned long long)n); e = hipGetLastError(); }
-    if (e == hipSuccess) e = hipMemcpy(out, d, 24, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    HIP_TRY(e);
+    Scratch mem;
+    HIP_TRY(mem.alloc(d, 24));
+    HIP_TRY(hipMemset(d, 0, 24));
+    if (roots) hipLaunchKernelGGL(rtk::sphere_root_check_kernel, dim3(4096), dim3(256), 0, 0, d, (unsigned long long)n);
+    else hipLaunchKernelGGL(rtk::fast_math_check_kernel, dim3(4096), dim3(256), 0, 0, d);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(out, d, 24, hipMemcpyDeviceToHost));
     return RT_OK;
 }
-
-rt_status rt_debug_check_fast_math(uint64_t out[3]) {
-    if (!out) return fail(RT_ERR_INVALID_ARG, "null argument");
-    unsigned long long *d = nullptr;
-    HIP_TRY(hipMalloc(&d, 24));
-    hipError_t e = hipMemset(d, 0, 24);
-    if (e == hipSuccess) { hipLaunchKernelGGL(rtk::fast_math_check_kernel, dim3(4096), dim3(256), 0, 0, d); e = hipGetLastError(); }
-    if (e == hipSuccess) e = hipMemcpy(out, d, 24, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    HIP_TRY(e);
-    return RT_OK;
-}
+rt_status rt_debug_check_sphere_roots(uint64_t n, uint64_t out[3]) { return run_math_check(true, n, out); }
+rt_status rt_debug_check_fast_math(uint64_t out[3]) { return run_math_check(false, 0, out); }
 
 // Developer hooks (not part of the ABI header): the device LBVH builder (rt_build.hip) on its own, for the node-by-node check
 // against a host reference (tests/dev_tree_checks.py, tests/lbvh_reference.py).
@@ -2709,9 +2709,7 @@ rt_status rt_last_kernel_ms(rt_scene *sc, float *ms) {
     if (!sc || !ms) return fail(RT_ERR_INVALID_ARG, "null argument");
     *ms = 0.0f;
     if (!sc->timed) return RT_OK;
-    HIP_TRY(hipEventSynchronize(sc->ev_stop));
-    HIP_TRY(hipEventElapsedTime(ms, sc->ev_start, sc->ev_stop));
-    return RT_OK;
+    return sc->clock[kClockRender].elapsed(*ms);
 }
 
 rt_status rt_render_to_host(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shard, float *h_fb_sum, rt_timing *timing) {
@@ -2720,10 +2718,10 @@ rt_status rt_render_to_host(rt_scene *sc, const rt_camera_data *cam, const rt_sh
     const size_t bytes = (size_t)rows * (size_t)(cam->image_width > 0 ? cam->image_width : 0) * 3 * sizeof(float);
     if (bytes == 0) return RT_OK;
     float *d_fb = nullptr;
-    HIP_TRY(hipMalloc((void **)&d_fb, bytes));
+    Scratch mem;
+    HIP_TRY(mem.alloc(d_fb, bytes));
     rt_status st = rt_render(sc, cam, shard, d_fb, nullptr, 1, timing);
     if (st == RT_OK && hipMemcpy(h_fb_sum, d_fb, bytes, hipMemcpyDeviceToHost) != hipSuccess) st = fail(RT_ERR_HIP, "hipMemcpy D2H failed");
-    (void)hipFree(d_fb);
     return st;
 }
 
@@ -2752,13 +2750,11 @@ rt_status rt_closest_hits(rt_scene *sc, int32_t n, const float *origins, const f
     if ((st = check_device(sc)) != RT_OK) return st;
     float *d_o = nullptr, *d_d = nullptr, *d_t = nullptr;
     int32_t *d_hit = nullptr, *d_prim = nullptr;
-    auto cleanup = [&]() { (void)hipFree(d_o); (void)hipFree(d_d); (void)hipFree(d_t); (void)hipFree(d_hit); (void)hipFree(d_prim); };
+    Scratch mem;
     const size_t n3 = (size_t)n * 12, n1 = (size_t)n * 4;
-    if (hipMalloc((void **)&d_o, n3) != hipSuccess || hipMalloc((void **)&d_d, n3) != hipSuccess || hipMalloc((void **)&d_t, n1) != hipSuccess ||
-        hipMalloc((void **)&d_hit, n1) != hipSuccess || hipMalloc((void **)&d_prim, n1) != hipSuccess) {
-        cleanup();
+    if (mem.alloc(d_o, n3) != hipSuccess || mem.alloc(d_d, n3) != hipSuccess || mem.alloc(d_t, n1) != hipSuccess || mem.alloc(d_hit, n1) != hipSuccess ||
+        mem.alloc(d_prim, n1) != hipSuccess)
         return fail(RT_ERR_OUT_OF_MEMORY, "hipMalloc failed");
-    }
     hipError_t e = hipMemcpy(d_o, origins, n3, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d_d, directions, n3, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemset(d_t, 0, n1);
@@ -2771,7 +2767,6 @@ rt_status rt_closest_hits(rt_scene *sc, int32_t n, const float *origins, const f
     if (e == hipSuccess) e = hipMemcpy(hit, d_hit, n1, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(t, d_t, n1, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(prim, d_prim, n1, hipMemcpyDeviceToHost);
-    cleanup();
     if (e != hipSuccess) return fail(RT_ERR_HIP, std::string("closest-hit probe: ") + hipGetErrorString(e));
     return RT_OK;
 }

@@ -225,9 +225,17 @@ def test_config_defaults_and_env_overlay():
         os.environ.pop("RTP_NO_FRONT")
     assert all(b == 0xAB for b in bytes(buf)[short:]), "rt_config_from_env wrote past the caller's struct"
     assert full.guard_front_primitives == -1 and full.struct_bytes == C.sizeof(rb.Config)
+    # The whole host side of the C ABI — every frame driver, the helpers they share, the lens / light / environment / probe entry
+    # points — less the functions that are there to read the environment: env_int itself, rt_config_from_env, and (still, for
+    # measurements) bail_floor / bail_latest.
     src = open(os.path.join(ROOT, "ray-tracing-practice_amd", "csrc", "rt_capi.hip")).read()
-    render = src[src.index("rt_status render_impl(rt_scene *sc"):src.index("rt_status rt_last_timing(")]
-    shipped = re_strip_dev(render)
+    for head in ("int env_int(", "uint32_t bail_floor() {", "uint32_t bail_latest() {", "void rt_config_from_env("):
+        start = src.index(head)
+        src = src[:start] + src[src.index("\n}\n", start):]
+    for driver in ("rt_status render_impl(rt_scene *sc", "rt_status aov_impl(", "rt_status adaptive_impl(", "rt_status render_light_impl(",
+                   "rt_status frame_prologue(", "rt_status rt_render_lens(", "rt_status rt_render_env(", "rt_status run_probe(", "rt_status rt_last_timing("):
+        assert driver in src, driver
+    shipped = re_strip_dev(src)
     assert "getenv" not in shipped and "env_int" not in shipped
 
 
