@@ -720,6 +720,56 @@ rt_status rt_trace_samples_env(rt_scene *scene, const rt_camera_data *cam, const
  * each texel the mean of the nearest lat-long pixels at a 4 x 4 grid of points inside it. */
 rt_status rt_env_from_equirect(const float *rgb, int32_t w, int32_t h, int32_t n, float *out);
 
+/* ---- emitters, environment and lens in one frame -----------------------------------------------------------------
+ * rt_render_lens's camera in front of a path that takes rt_render_nee's light sample of the emitter table AND rt_render_env's light
+ * sample of an environment at every diffuse event.  No new arithmetic: every expression is one of the three sections above, float32
+ * in the order written there, nothing fused, division and sqrtf correctly rounded; this section fixes composition and order only.
+ *   Camera: steps 1 … 5 of rt_render_lens — ox, oy, then tau when cam_close != NULL, then (lx, ly) when lens_radius > 0.  The path goes
+ *     on from the RNG state those draws leave.
+ *   Streams: nee = wang_hash(wang_hash(base + s) ^ RT_NEE_STREAM_KEY), env = wang_hash(wang_hash(base + s) ^ RT_ENV_STREAM_KEY),
+ *     base = wang_hash(i * W + j), as in the single calls: the camera's extra draws do not move them.  A light that is off (the
+ *     emitters: sample_emitters == 0 or an empty table; the environment: env == NULL, mode 0 or an empty table) never advances its
+ *     state; rt_trace_samples_lit reports it as initialised.
+ *   At the vertex of closest-hit query k, in this order:
+ *     1. the emission or miss term.  A hit on a sphere of the emitter table by a ray that left a diffuse event adds
+ *        (beta_k * emit_k) * w_b with rt_render_nee's w_b when sample_emitters != 0 (nothing to weight where the table is empty);
+ *     2. a miss adds rt_render_env's miss term when env != NULL — with its w_b after a diffuse event when mode != 0 and the map's
+ *        table is not empty, and with its camera_visible rule for query 0 — and beta_k * cam->background otherwise;
+ *     3. every other emission keeps weight 1;
+ *     4. at a diffuse event with k + 1 < max_depth: the emitter sample, rt_render_nee's steps 1 … 4 from the nee state; its shadow
+ *        ray's closest hit must be sphere e; its contribution is added to the sample's radiance as soon as it is known to count;
+ *     5. at the same event: the environment sample, rt_render_env's steps 1 … 4 from the env state; its shadow ray is an occlusion
+ *        query from the same point x; its contribution is added after the emitter's.
+ *   Spheres are hits and the map is misses: the two estimators never weight the same radiance, each keeps its own two-strategy MIS
+ *   against the BSDF ray, and the sum has rt_render's expectation under that map.
+ *   Identities, bit for bit: env == NULL, no lens, no motion, sample_emitters = 1 = rt_render_nee with the same nee parameters;
+ *     sample_emitters = 0 (or an empty emitter table) with env != NULL, no lens, no motion = rt_render_env; sample_emitters = 0 and
+ *     env == NULL = rt_render_lens, and so rt_render_samples without lens and motion.
+ * Checks and limits: the union of rt_render_lens's, rt_render_nee's and rt_render_env's, in that order, every refusal before anything
+ * is enqueued (nee is read only when sample_emitters != 0, env_params only when env != NULL); lit == NULL means the defaults;
+ * RT_ERR_INVALID_ARG for a struct_bytes below 8 and for sample_emitters outside {0, 1}.  Rows of a shard only: no tiles, no rt_context.
+ * Handle state: as rt_render_nee — the handle's walk choice, a pause of the guarded walk, the re-pack, the view lists and rt_last_timing
+ * are left alone; the emitter table is the handle's one table, built by whichever of rt_render_nee / rt_render_lit comes first.  The
+ * light samples run on the reference-order walk only (timing->guarded is 0); timing (may be NULL) is this call's record. */
+typedef struct rt_lit_params {          /* IN, grows like rt_env_params: the library reads at most struct_bytes; < 8 = RT_ERR_INVALID_ARG */
+    uint32_t struct_bytes;              /* sizeof(rt_lit_params) as the caller compiled it */
+    int32_t  sample_emitters;           /* 1 (default): light samples of the handle's emitter table; 0: none */
+    const rt_camera_data *cam_close;    /* NULL (default): no motion */
+    const rt_lens_params *lens;         /* NULL: rt_lens_params_init's defaults (pinhole) */
+    const rt_nee_params  *nee;          /* NULL: defaults; read only when sample_emitters != 0 */
+    const rt_env         *env;          /* NULL: no environment — a miss adds cam->background */
+    const rt_env_params  *env_params;   /* NULL: defaults; read only when env != NULL */
+} rt_lit_params;
+/* Defaults into *p, struct_bytes = sizeof(rt_lit_params). */
+void rt_lit_params_init(rt_lit_params *p);
+/* rt_render_samples from the lens camera with both light samples (lit NULL: defaults — emitter sampling, pinhole, no environment). */
+rt_status rt_render_lit(rt_scene *scene, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_shard *shard,
+                        int32_t sample_first, float *d_fb_sum, void *hip_stream, int32_t sync, rt_timing *timing);
+/* Probe for tests, HOST memory: rt_trace_samples for the estimator of rt_render_lit — radiance, rays (closest-hit queries plus every
+ * shadow ray of either kind), the path's final RNG state and both light streams' final states per (i, j, s). */
+rt_status rt_trace_samples_lit(rt_scene *scene, const rt_camera_data *cam_open, const rt_lit_params *lit, int32_t n, const int32_t *ijs,
+                               float *radiance, int32_t *rays, uint32_t *final_seed, uint32_t *final_nee_seed, uint32_t *final_env_seed);
+
 /* Milliseconds of the most recent rt_render kernel of this scene (waits for it). */
 rt_status rt_last_kernel_ms(rt_scene *scene, float *ms);
 /* The whole rt_timing of the most recent rt_render of this scene (waits for it). */

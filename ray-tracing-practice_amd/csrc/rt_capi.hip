@@ -1217,13 +1217,15 @@ const void *lens_trace_kernel(const LaunchPlan &L) {
     return (const void *)render_lens_kernel<false, false>;
 }
 
-// (second: the second kernel argument — render_lens_kernel's LensCam, a lit trace kernel's light table; null for render_kernel)
-hipError_t launch(const void *kernel, uint32_t block, int grid, uint32_t lds, hipStream_t stream, const rtk::KParams &KP, const void *second = nullptr) {
+// (second: the second kernel argument — render_lens_kernel's LensCam, a lit trace kernel's light table; null for render_kernel.
+// third: lit_render_kernel's LensCam behind its light; null for every other kernel)
+hipError_t launch(const void *kernel, uint32_t block, int grid, uint32_t lds, hipStream_t stream, const rtk::KParams &KP, const void *second = nullptr,
+                  const void *third = nullptr) {
     hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     void *args[] = {(void *)&KP};
-    void *both_args[] = {(void *)&KP, (void *)second};
-    e = hipLaunchKernel(kernel, dim3(grid), dim3(block), second ? both_args : args, lds, stream);
+    void *more_args[] = {(void *)&KP, (void *)second, (void *)third};
+    e = hipLaunchKernel(kernel, dim3(grid), dim3(block), second ? more_args : args, lds, stream);
     const hipError_t last = hipGetLastError();
     return e != hipSuccess ? e : last;
 }
@@ -1909,15 +1911,16 @@ rt_status adaptive_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard 
     return RT_OK;
 }
 
-// ---- what the lit calls share: the frame driver of rt_render_nee / rt_render_env, the probe of rt_trace_samples and its lit kin ---------
-// rt_render_nee / rt_render_env: the passes of render_impl (plan_passes, the slab, accumulate_kernel in sample order) with a trace kernel
-// of rt_light.hip.inc as the trace launch; nothing of the handle's walk machinery is touched.
+// ---- what the lit calls share: the frame driver of rt_render_nee / rt_render_env / rt_render_lit, the probe of rt_trace_samples and its
+// lit kin.  The passes of render_impl (plan_passes, the slab, accumulate_kernel in sample order) with a trace kernel of rt_light.hip.inc as
+// the trace launch; nothing of the handle's walk machinery is touched.
+//   trace: a kernel (KParams, Light) — or, with lens, (KParams, Light, LensCam): rt_render_lit's;
 //   light_device: the device of a light that is an object of its own (null: the light is the handle's);
 //   make_light: fills the kernel's second argument, once the call is known to trace
 template <class Light, class MakeLight>
-rt_status render_light_impl(const char *what, void (*trace)(rtk::KParams, Light), const int *light_device, MakeLight make_light, rt_scene *sc,
+rt_status render_light_impl(const char *what, const void *trace, const int *light_device, MakeLight make_light, rt_scene *sc,
                             const rt_camera_data *cam, const rt_shard *shard, int32_t sample_first, float *d_fb_sum, void *hip_stream, int32_t sync,
-                            rt_timing *timing) {
+                            rt_timing *timing, const rtk::LensCam *lens = nullptr) {
     Frame F;
     rt_status st = frame_prologue(what, sc, cam, shard, nullptr, sample_first, light_device, d_fb_sum ? nullptr : "null framebuffer", hip_stream, timing, F,
                                   [&] { return refuse_retired(sc->cfg); });
@@ -1933,7 +1936,7 @@ rt_status render_light_impl(const char *what, void (*trace)(rtk::KParams, Light)
     rtaccel::PassPlan passes;
     if ((st = reserve_slab(sc, num_pixels, P.spp, stream, passes)) != RT_OK) return st;
     bind_slab(sc, P, num_pixels, passes.pass_size);          // (no candidate lists: fill_params left P.cand and P.order null)
-    const void *kernel = (const void *)trace;
+    const void *kernel = trace;
     int per_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, rtk::kLightBlock, 0) != hipSuccess || per_cu < 1) {
         (void)hipGetLastError();
@@ -1955,7 +1958,7 @@ rt_status render_light_impl(const char *what, void (*trace)(rtk::KParams, Light)
         int grid = wgs;
         if ((uint64_t)grid * waves_per_wg > need) grid = (int)((need + waves_per_wg - 1) / waves_per_wg);
         if (grid < 1) grid = 1;
-        HIP_TRY(launch(kernel, (uint32_t)rtk::kLightBlock, grid, 0, stream, P, &T));
+        HIP_TRY(launch(kernel, (uint32_t)rtk::kLightBlock, grid, 0, stream, P, &T, lens));
         launch_accumulate(stream, P, Acc::every_pixel(pass));
         HIP_TRY(hipGetLastError());
         if (pass == 0) t.num_workgroups = (uint32_t)grid;
@@ -1992,32 +1995,35 @@ struct Scratch {
     ~Scratch() { for (void *p : owned) (void)hipFree(p); }
 };
 
-// rt_trace_samples, rt_trace_samples_nee, rt_trace_samples_env: the (i, j, s) triples checked against cam and uploaded, launch_probe(P,
-// d_light_seed) run on P with the probe columns set, the columns downloaded.
-//   what: the prefix of the call's messages; final_light_seed: the lit probes' second RNG state (null: no such column)
+// rt_trace_samples, rt_trace_samples_nee, rt_trace_samples_env, rt_trace_samples_lit: the (i, j, s) triples checked against cam and
+// uploaded, launch_probe(P, d_light_seed, d_light_seed2) run on P with the probe columns set, the columns downloaded.
+//   what: the prefix of the call's messages; final_light_seed, final_light_seed2: the lit probes' light-sample RNG states (null: no
+//   such column)
 template <class LaunchProbe>
 rt_status run_probe(const std::string &what, rtk::KParams &P, const rt_camera_data *cam, int32_t n, const int32_t *ijs, float *radiance, int32_t *rays,
-                    uint32_t *final_seed, uint32_t *final_light_seed, LaunchProbe launch_probe) {
+                    uint32_t *final_seed, uint32_t *final_light_seed, uint32_t *final_light_seed2, LaunchProbe launch_probe) {
     if (n == 0) return RT_OK;
     for (int32_t k = 0; k < n; ++k)
         if (ijs[3 * k] < 0 || ijs[3 * k] >= cam->image_width || ijs[3 * k + 1] < 0 || ijs[3 * k + 1] >= cam->image_height || ijs[3 * k + 2] < 0)
             return fail(RT_ERR_INVALID_ARG, what + "sample coordinate out of range");
     int32_t *d_ijs = nullptr, *d_rays = nullptr;
     float *d_rad = nullptr;
-    uint32_t *d_seed = nullptr, *d_light = nullptr;
+    uint32_t *d_seed = nullptr, *d_light = nullptr, *d_light2 = nullptr;
     Scratch mem;
     if (mem.alloc(d_ijs, (size_t)n * 12) != hipSuccess || mem.alloc(d_rad, (size_t)n * 12) != hipSuccess || mem.alloc(d_rays, (size_t)n * 4) != hipSuccess ||
-        mem.alloc(d_seed, (size_t)n * 4) != hipSuccess || (final_light_seed && mem.alloc(d_light, (size_t)n * 4) != hipSuccess))
+        mem.alloc(d_seed, (size_t)n * 4) != hipSuccess || (final_light_seed && mem.alloc(d_light, (size_t)n * 4) != hipSuccess) ||
+        (final_light_seed2 && mem.alloc(d_light2, (size_t)n * 4) != hipSuccess))
         return fail(RT_ERR_OUT_OF_MEMORY, what + "hipMalloc failed");
     if (hipMemcpy(d_ijs, ijs, (size_t)n * 12, hipMemcpyHostToDevice) != hipSuccess) return fail(RT_ERR_HIP, what + "hipMemcpy H2D failed");
     P.probe_ijs = d_ijs; P.probe_rad = d_rad; P.probe_rays = d_rays; P.probe_seed = d_seed; P.probe_n = n;
-    if (const rt_status st = launch_probe(P, d_light)) return st;
+    if (const rt_status st = launch_probe(P, d_light, d_light2)) return st;
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e == hipSuccess) e = hipMemcpy(radiance, d_rad, (size_t)n * 12, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(rays, d_rays, (size_t)n * 4, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(final_seed, d_seed, (size_t)n * 4, hipMemcpyDeviceToHost);
     if (e == hipSuccess && final_light_seed) e = hipMemcpy(final_light_seed, d_light, (size_t)n * 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && final_light_seed2) e = hipMemcpy(final_light_seed2, d_light2, (size_t)n * 4, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(RT_ERR_HIP, what + "probe kernel: " + hipGetErrorString(e));
     return RT_OK;
 }
@@ -2256,7 +2262,7 @@ rt_status rt_render_nee(rt_scene *sc, const rt_camera_data *cam, const rt_nee_pa
         T = nee_table_of(sc, mis);
         return RT_OK;
     };
-    return render_light_impl("rt_render_nee", rtk::nee_render_kernel, nullptr, make_table, sc, cam, shard, sample_first, d_fb_sum, hip_stream, sync, timing);
+    return render_light_impl<rtk::NeeTable>("rt_render_nee", (const void *)rtk::nee_render_kernel, nullptr, make_table, sc, cam, shard, sample_first, d_fb_sum, hip_stream, sync, timing);
 }
 
 rt_status rt_nee_light_table(rt_scene *sc, int32_t cap, int32_t *sphere_index, float *cdf, float *pmf, int32_t *count) {
@@ -2283,7 +2289,7 @@ rt_status rt_trace_samples_nee(rt_scene *sc, const rt_camera_data *cam, const rt
     rt_status st = fill_params(sc, cam, nullptr, P);
     if (st != RT_OK) return st;
     if ((st = check_device(sc)) != RT_OK) return st;
-    return run_probe("rt_trace_samples_nee: ", P, cam, n, ijs, radiance, rays, final_seed, final_nee_seed, [&](const rtk::KParams &KP, uint32_t *d_nee) {
+    return run_probe("rt_trace_samples_nee: ", P, cam, n, ijs, radiance, rays, final_seed, final_nee_seed, nullptr, [&](const rtk::KParams &KP, uint32_t *d_nee, uint32_t *) {
         if (const rt_status ts = nee_table_ensure(sc)) return ts;
         hipLaunchKernelGGL(rtk::nee_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, KP, nee_table_of(sc, mis), d_nee);
         return RT_OK;
@@ -2523,7 +2529,7 @@ rt_status rt_render_env(rt_scene *sc, const rt_camera_data *cam, const rt_env *e
         E = env_dev_of(env, np);
         return RT_OK;
     };
-    return render_light_impl("rt_render_env", rtk::env_render_kernel, &env->device, make_env, sc, cam, shard, sample_first, d_fb_sum, hip_stream, sync, timing);
+    return render_light_impl<rtk::EnvDev>("rt_render_env", (const void *)rtk::env_render_kernel, &env->device, make_env, sc, cam, shard, sample_first, d_fb_sum, hip_stream, sync, timing);
 }
 
 rt_status rt_trace_samples_env(rt_scene *sc, const rt_camera_data *cam, const rt_env *env, const rt_env_params *params, int32_t n,
@@ -2537,8 +2543,87 @@ rt_status rt_trace_samples_env(rt_scene *sc, const rt_camera_data *cam, const rt
     if (st != RT_OK) return st;
     if ((st = check_device(sc)) != RT_OK) return st;
     if (env->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_env: the environment was created on another device than the scene");
-    return run_probe("rt_trace_samples_env: ", P, cam, n, ijs, radiance, rays, final_seed, final_env_seed, [&](const rtk::KParams &KP, uint32_t *d_env) {
+    return run_probe("rt_trace_samples_env: ", P, cam, n, ijs, radiance, rays, final_seed, final_env_seed, nullptr, [&](const rtk::KParams &KP, uint32_t *d_env, uint32_t *) {
         hipLaunchKernelGGL(rtk::env_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, KP, env_dev_of(env, np), d_env);
+        return RT_OK;
+    });
+}
+
+// ---- rt_render_lit / rt_trace_samples_lit (rtp_amd.h): emitters, environment and lens in one frame -------------------
+void rt_lit_params_init(rt_lit_params *p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->struct_bytes = (uint32_t)sizeof(*p);
+    p->sample_emitters = 1;
+}
+
+namespace {
+// What a lit call is made of, after the checks of its three components in their order (lens, emitters, environment)
+struct LitSetup {
+    rtk::LensCam C;
+    bool lens = false;            // the camera draws more than the pinhole's: the kLens kernels
+    bool emitters = true;
+    int32_t mis = 1;
+    const rt_env *env = nullptr;
+    rt_env_params ep;
+};
+rt_status lit_setup(const char *what, const rt_camera_data *cam_open, const rt_lit_params *lit, LitSetup &S) {
+    rt_lit_params lp;
+    rt_lit_params_init(&lp);
+    if (const rt_status st = take_params(what, "rt_lit_params", lit, lp)) return st;
+    if (lp.sample_emitters != 0 && lp.sample_emitters != 1) return fail(RT_ERR_INVALID_ARG, std::string(what) + ": sample_emitters must be 0 or 1");
+    if (const rt_status st = lens_setup(what, cam_open, lp.cam_close, lp.lens, S.C)) return st;
+    S.lens = S.C.motion != 0 || S.C.radius > 0.0f;
+    S.emitters = lp.sample_emitters != 0;
+    if (S.emitters)
+        if (const rt_status st = nee_setup(what, lp.nee, S.mis)) return st;
+    S.env = lp.env;
+    if (S.env)
+        if (const rt_status st = env_setup(what, lp.env_params, S.ep)) return st;
+    return RT_OK;
+}
+// the kernels' light: the handle's emitter table (emitters off: an empty one) and the environment (none: off)
+rt_status lit_light_of(rt_scene *sc, const LitSetup &S, rtk::LitLight &T) {
+    T = rtk::LitLight{};
+    if (S.emitters) {
+        if (const rt_status st = nee_table_ensure(sc)) return st;
+        T.N = nee_table_of(sc, S.mis);
+    }
+    if (S.env) {
+        T.E = env_dev_of(S.env, S.ep);
+        T.env_on = 1;
+    }
+    return RT_OK;
+}
+}  // namespace
+
+rt_status rt_render_lit(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_shard *shard, int32_t sample_first,
+                        float *d_fb_sum, void *hip_stream, int32_t sync, rt_timing *timing) {
+    LitSetup S;
+    if (const rt_status st = lit_setup("rt_render_lit", cam_open, lit, S)) return st;
+    if (!sc) return fail(RT_ERR_INVALID_ARG, "rt_render_lit: null scene");
+    const void *kernel = S.lens ? (const void *)rtk::lit_render_kernel<true> : (const void *)rtk::lit_render_kernel<false>;
+    return render_light_impl<rtk::LitLight>("rt_render_lit", kernel, S.env ? &S.env->device : nullptr, [&](rtk::LitLight &T) { return lit_light_of(sc, S, T); },
+                                            sc, cam_open, shard, sample_first, d_fb_sum, hip_stream, sync, timing, &S.C);
+}
+
+rt_status rt_trace_samples_lit(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, int32_t n, const int32_t *ijs, float *radiance,
+                               int32_t *rays, uint32_t *final_seed, uint32_t *final_nee_seed, uint32_t *final_env_seed) {
+    LitSetup S;
+    if (const rt_status st = lit_setup("rt_trace_samples_lit", cam_open, lit, S)) return st;
+    if (n < 0 || (n > 0 && (!ijs || !radiance || !rays || !final_seed || !final_nee_seed || !final_env_seed)))
+        return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_lit: null argument");
+    rtk::KParams P;
+    rt_status st = fill_params(sc, cam_open, nullptr, P);
+    if (st != RT_OK) return st;
+    if ((st = check_device(sc)) != RT_OK) return st;
+    if (S.env && S.env->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_lit: the environment was created on another device than the scene");
+    return run_probe("rt_trace_samples_lit: ", P, cam_open, n, ijs, radiance, rays, final_seed, final_nee_seed, final_env_seed,
+                     [&](const rtk::KParams &KP, uint32_t *d_nee, uint32_t *d_env) {
+        rtk::LitLight T;
+        if (const rt_status ts = lit_light_of(sc, S, T)) return ts;
+        if (S.lens) hipLaunchKernelGGL(rtk::lit_probe_kernel<true>, dim3((n + 255) / 256), dim3(256), 0, 0, KP, T, S.C, d_nee, d_env);
+        else hipLaunchKernelGGL(rtk::lit_probe_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, 0, KP, T, S.C, d_nee, d_env);
         return RT_OK;
     });
 }
@@ -2732,7 +2817,7 @@ rt_status rt_trace_samples(rt_scene *sc, const rt_camera_data *cam, int32_t n, c
     rt_status st = fill_params(sc, cam, nullptr, P);
     if (st != RT_OK) return st;
     if ((st = check_device(sc)) != RT_OK) return st;
-    return run_probe("", P, cam, n, ijs, radiance, rays, final_seed, nullptr, [&](const rtk::KParams &KP, uint32_t *) {
+    return run_probe("", P, cam, n, ijs, radiance, rays, final_seed, nullptr, nullptr, [&](const rtk::KParams &KP, uint32_t *, uint32_t *) {
         hipLaunchKernelGGL(rtk::probe_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, KP);
         return RT_OK;
     });

@@ -1,6 +1,6 @@
 // rt_light.hip.inc — the path that takes light samples, written once for both kinds of light: the emissive spheres of rt_render_nee
-// (NeeTable, rt_nee.hip.inc; DESIGN.md §13) and the environment of rt_render_env (EnvDev, rt_env.hip.inc; §14).  Included by rt_capi.hip
-// after both.  A light is its table type; what the two do differently is the overloads below, everything else — the lit vertex, the
+// (NeeTable, rt_nee.hip.inc; DESIGN.md §13) and the environment of rt_render_env (EnvDev, rt_env.hip.inc; §14) — and, at the end, for
+// both at once from the lens camera (rt_render_lit, LitLight; §16).  Included by rt_capi.hip after both.  A light is its table type; what the two do differently is the overloads below, everything else — the lit vertex, the
 // walk step, the probe and the trace kernel — is one text.
 #pragma once
 
@@ -70,119 +70,125 @@ __device__ __forceinline__ uint32_t light_seed_of(const Light &T, uint32_t base_
 //   (code).  Only a diffuse event whose next query is inside max_depth samples, so a vertex that samples always has a next ray, and
 //   out_o — the hit point — is both rays' origin.
 // The main stream's draws, the branches, the roulette and the next ray are shade()'s.
+// The vertex is one text for both of its forms — shade_lit (one light sample) and, at the end of this file, shade_lit2 (the emitter's
+// and the environment's): RTP_LIT_VERTEX, the body of a function with L, P, T, prev_diffuse, out_o, out_d and diffuse_out (set to false)
+// in scope.  TAKE_SAMPLES is the statement a diffuse event runs for its light samples, with point, normal, albedo and beta_in (the
+// throughput before the attenuation) at hand.
+#define RTP_LIT_VERTEX(TAKE_SAMPLES)                                                                                                                 \
+    if (L.hit < 0) {                                                                                                                                 \
+        L.color = add(L.color, light_miss(P, T, L, prev_diffuse));                                                                                   \
+        return false;                                                                                                                                \
+    }                                                                                                                                                \
+    const int32_t hit = L.hit;                                                                                                                       \
+    const int32_t idx = hit >> 1;                                                                                                                    \
+    const float t = L.closest;                                                                                                                       \
+    const f3 point = add(L.o, scale(t, L.d));  /* r.at(rec.t) */                                                                                     \
+    f3 normal;                                                                                                                                       \
+    bool front;                                                                                                                                      \
+    int32_t mat_idx;                                                                                                                                 \
+    float tu = 0.0f, tv = 0.0f;                                                                                                                      \
+    const bool is_plane = (hit & 1) != 0;                                                                                                            \
+    f3 outward = mk(0, 0, 0);                                                                                                                        \
+    if (is_plane) {                                                                                                                                  \
+        const float4 P0 = P.planes[5 * idx + 0];                                                                                                     \
+        const float4 P2 = P.planes[5 * idx + 2];                                                                                                     \
+        outward = mk(P0.x, P0.y, P0.z);                                                                                                              \
+        mat_idx = as_int(P2.w);                                                                                                                      \
+    } else {                                                                                                                                         \
+        const float4 s = P.spheres[idx];                                                                                                             \
+        outward = divs(sub(point, mk(s.x, s.y, s.z)), s.w);                                                                                          \
+        mat_idx = P.sphere_mat[idx];                                                                                                                 \
+    }                                                                                                                                                \
+    front = dot(L.d, outward) < 0;                                                                                                                   \
+    normal = front ? outward : neg(outward);                                                                                                         \
+                                                                                                                                                     \
+    const float4 MA = P.materials[3 * mat_idx + 0];                                                                                                  \
+    const float4 ME = P.materials[3 * mat_idx + 1];                                                                                                  \
+    const int32_t type = as_int(MA.w) & 3;                                                                                                           \
+    const int32_t tex_id = as_int(MA.w) >> 2;                                                                                                        \
+    f3 albedo = mk(MA.x, MA.y, MA.z);                                                                                                                \
+    if (tex_id != 0) {                                                                                                                               \
+        if (is_plane) {                                                                                                                              \
+            const float4 P1 = P.planes[5 * idx + 1];                                                                                                 \
+            const float4 P2 = P.planes[5 * idx + 2];                                                                                                 \
+            const float4 P3 = P.planes[5 * idx + 3];                                                                                                 \
+            const float4 P4 = P.planes[5 * idx + 4];                                                                                                 \
+            const f3 ph = sub(point, mk(P4.x, P4.y, P4.z));                                                                                          \
+            const f3 w = mk(P1.x, P1.y, P1.z);                                                                                                       \
+            tu = dot(w, cross(ph, mk(P3.x, P3.y, P3.z)));                                                                                            \
+            tv = dot(w, cross(mk(P2.x, P2.y, P2.z), ph));                                                                                            \
+        } else {                                                                                                                                     \
+            const float theta = acos_libm(outward.y);                                                                                                \
+            const float phi = (float)((double)atan2_libm(-outward.z, outward.x) + 3.14159265358979323846);                                           \
+            tu = (float)((double)phi / (2 * 3.14159265358979323846));                                                                                \
+            tv = (float)((double)theta / 3.14159265358979323846);                                                                                    \
+        }                                                                                                                                            \
+        albedo = mul(albedo, sample_texture(P, tex_id - 1, tu, tv));                                                                                 \
+    }                                                                                                                                                \
+    const f3 beta_in = L.beta;                                                                                                                       \
+    const f3 emitted = light_emitted(P, T, L, idx, is_plane, prev_diffuse, mul(beta_in, mk(ME.x, ME.y, ME.z)));  /* final_color += beta * emitted */ \
+                                                                                                                                                     \
+    f3 new_o = point, new_d = normal, att = albedo;                                                                                                  \
+    const bool is_lamb = type == RT_MAT_LAMBERTIAN;                                                                                                  \
+    const bool is_metal = type == RT_MAT_METAL;                                                                                                      \
+    const bool is_glass = type == RT_MAT_DIELECTRIC;                                                                                                 \
+    if (!(is_lamb || is_metal || is_glass)) {  /* DIFFUSE_LIGHT */                                                                                   \
+        L.color = add(L.color, emitted);                                                                                                             \
+        return false;                                                                                                                                \
+    }                                                                                                                                                \
+    float4 MB = make_float4(0.0f, 0.0f, 0.0f, 1.0f);                                                                                                 \
+    if (is_glass) MB = P.materials[3 * mat_idx + 2];                                                                                                 \
+    bool metal_reflect = false;                                                                                                                      \
+    if (is_metal) metal_reflect = random_float(L.seed) < 0.8f;                                                                                       \
+    f3 in_sphere = mk(0, 0, 0);                                                                                                                      \
+    if (is_lamb || is_metal) in_sphere = random_in_unit_sphere(L.seed);                                                                              \
+    L.color = add(L.color, emitted);                                                                                                                 \
+    f3 ud = mk(0, 0, 0);                                                                                                                             \
+    if (metal_reflect || is_glass) ud = unit(L.d);                                                                                                   \
+    if (is_glass) {                                                                                                                                  \
+        const float ir = MB.w;                                                                                                                       \
+        const float ratio = front ? ME.w : ir;                                                                                                       \
+        const float cos_theta = fminf(dot(neg(ud), normal), 1.0f);                                                                                   \
+        const float sin_theta = sqrt_cr(1.0f - cos_theta * cos_theta);                                                                               \
+        const bool cannot_refract = ratio * sin_theta > 1.0f;                                                                                        \
+        bool do_reflect = cannot_refract;                                                                                                            \
+        if (!cannot_refract) {                                                                                                                       \
+            const float rnd = random_float(L.seed);                                                                                                  \
+            do_reflect = schlick_exceeds(cos_theta, front ? MA.x : MA.y, rnd);                                                                       \
+        }                                                                                                                                            \
+        new_d = do_reflect ? reflect(ud, normal) : refract(ud, normal, ratio);                                                                       \
+        att = mk(1.0f, 1.0f, 1.0f);                                                                                                                  \
+        if (!front) {                                                                                                                                \
+            const float dist = sqrt_cr(lensq(sub(point, L.o)));                                                                                      \
+            const f3 tr = mk(MB.x == 0.0f ? 1.0f : exp_libm(-MB.x * dist), MB.y == 0.0f ? 1.0f : exp_libm(-MB.y * dist),                             \
+                             MB.z == 0.0f ? 1.0f : exp_libm(-MB.z * dist));                                                                          \
+            att = mul(att, tr);                                                                                                                      \
+        }                                                                                                                                            \
+        const float p = fmaxf(att.x, fmaxf(att.y, att.z));                                                                                           \
+        if (random_float(L.seed) > p) return false;  /* Russian roulette */                                                                          \
+        if (p != 1.0f) att = scale(recip(p), att);                                                                                                   \
+        const float side = dot(new_d, normal) > 0 ? 1.0f : -1.0f;                                                                                    \
+        new_o = add(point, scale(side, scale(1e-4f, normal)));                                                                                       \
+    } else if (metal_reflect) {                                                                                                                      \
+        new_d = add(reflect(ud, normal), scale(ME.w, in_sphere));                                                                                    \
+        if (!(dot(new_d, normal) > 0)) return false;                                                                                                 \
+    } else {  /* LAMBERTIAN and METAL's 20 % branch: a diffuse event */                                                                              \
+        new_d = scatter_diffuse_dir(in_sphere, normal);                                                                                              \
+        diffuse_out = true;                                                                                                                          \
+        TAKE_SAMPLES                                                                                                                                 \
+    }                                                                                                                                                \
+    L.beta = mul(L.beta, att);                                                                                                                       \
+    L.depth++;                                                                                                                                       \
+    if (L.depth >= P.max_depth) return false;                                                                                                        \
+    out_o = new_o;                                                                                                                                   \
+    out_d = new_d;                                                                                                                                   \
+    return true;
 template <class Light>
 __device__ __forceinline__ bool shade_lit(Lane &L, const KParams &P, const Light &T, bool prev_diffuse, uint32_t &ls, f3 &out_o, f3 &out_d,
                                           f3 &sdir, f3 &c, int32_t &code, bool &sample, bool &diffuse_out) {
     sample = false;
     diffuse_out = false;
-    if (L.hit < 0) {
-        L.color = add(L.color, light_miss(P, T, L, prev_diffuse));
-        return false;
-    }
-    const int32_t hit = L.hit;
-    const int32_t idx = hit >> 1;
-    const float t = L.closest;
-    const f3 point = add(L.o, scale(t, L.d));        // r.at(rec.t)
-    f3 normal;
-    bool front;
-    int32_t mat_idx;
-    float tu = 0.0f, tv = 0.0f;
-    const bool is_plane = (hit & 1) != 0;
-    f3 outward = mk(0, 0, 0);
-    if (is_plane) {
-        const float4 P0 = P.planes[5 * idx + 0];
-        const float4 P2 = P.planes[5 * idx + 2];
-        outward = mk(P0.x, P0.y, P0.z);
-        mat_idx = as_int(P2.w);
-    } else {
-        const float4 s = P.spheres[idx];
-        outward = divs(sub(point, mk(s.x, s.y, s.z)), s.w);
-        mat_idx = P.sphere_mat[idx];
-    }
-    front = dot(L.d, outward) < 0;
-    normal = front ? outward : neg(outward);
-
-    const float4 MA = P.materials[3 * mat_idx + 0];
-    const float4 ME = P.materials[3 * mat_idx + 1];
-    const int32_t type = as_int(MA.w) & 3;
-    const int32_t tex_id = as_int(MA.w) >> 2;
-    f3 albedo = mk(MA.x, MA.y, MA.z);
-    if (tex_id != 0) {
-        if (is_plane) {
-            const float4 P1 = P.planes[5 * idx + 1];
-            const float4 P2 = P.planes[5 * idx + 2];
-            const float4 P3 = P.planes[5 * idx + 3];
-            const float4 P4 = P.planes[5 * idx + 4];
-            const f3 ph = sub(point, mk(P4.x, P4.y, P4.z));
-            const f3 w = mk(P1.x, P1.y, P1.z);
-            tu = dot(w, cross(ph, mk(P3.x, P3.y, P3.z)));
-            tv = dot(w, cross(mk(P2.x, P2.y, P2.z), ph));
-        } else {
-            const float theta = acos_libm(outward.y);
-            const float phi = (float)((double)atan2_libm(-outward.z, outward.x) + 3.14159265358979323846);
-            tu = (float)((double)phi / (2 * 3.14159265358979323846));
-            tv = (float)((double)theta / 3.14159265358979323846);
-        }
-        albedo = mul(albedo, sample_texture(P, tex_id - 1, tu, tv));
-    }
-    const f3 beta_in = L.beta;
-    const f3 emitted = light_emitted(P, T, L, idx, is_plane, prev_diffuse, mul(beta_in, mk(ME.x, ME.y, ME.z)));        // final_color += beta * emitted
-
-    f3 new_o = point, new_d = normal, att = albedo;
-    const bool is_lamb = type == RT_MAT_LAMBERTIAN;
-    const bool is_metal = type == RT_MAT_METAL;
-    const bool is_glass = type == RT_MAT_DIELECTRIC;
-    if (!(is_lamb || is_metal || is_glass)) {                        // DIFFUSE_LIGHT
-        L.color = add(L.color, emitted);
-        return false;
-    }
-    float4 MB = make_float4(0.0f, 0.0f, 0.0f, 1.0f);
-    if (is_glass) MB = P.materials[3 * mat_idx + 2];
-    bool metal_reflect = false;
-    if (is_metal) metal_reflect = random_float(L.seed) < 0.8f;
-    f3 in_sphere = mk(0, 0, 0);
-    if (is_lamb || is_metal) in_sphere = random_in_unit_sphere(L.seed);
-    L.color = add(L.color, emitted);
-    f3 ud = mk(0, 0, 0);
-    if (metal_reflect || is_glass) ud = unit(L.d);
-    if (is_glass) {
-        const float ir = MB.w;
-        const float ratio = front ? ME.w : ir;
-        const float cos_theta = fminf(dot(neg(ud), normal), 1.0f);
-        const float sin_theta = sqrt_cr(1.0f - cos_theta * cos_theta);
-        const bool cannot_refract = ratio * sin_theta > 1.0f;
-        bool do_reflect = cannot_refract;
-        if (!cannot_refract) {
-            const float rnd = random_float(L.seed);
-            do_reflect = schlick_exceeds(cos_theta, front ? MA.x : MA.y, rnd);
-        }
-        new_d = do_reflect ? reflect(ud, normal) : refract(ud, normal, ratio);
-        att = mk(1.0f, 1.0f, 1.0f);
-        if (!front) {
-            const float dist = sqrt_cr(lensq(sub(point, L.o)));
-            const f3 tr = mk(MB.x == 0.0f ? 1.0f : exp_libm(-MB.x * dist), MB.y == 0.0f ? 1.0f : exp_libm(-MB.y * dist),
-                             MB.z == 0.0f ? 1.0f : exp_libm(-MB.z * dist));
-            att = mul(att, tr);
-        }
-        const float p = fmaxf(att.x, fmaxf(att.y, att.z));
-        if (random_float(L.seed) > p) return false;                  // Russian roulette
-        if (p != 1.0f) att = scale(recip(p), att);
-        const float side = dot(new_d, normal) > 0 ? 1.0f : -1.0f;
-        new_o = add(point, scale(side, scale(1e-4f, normal)));
-    } else if (metal_reflect) {
-        new_d = add(reflect(ud, normal), scale(ME.w, in_sphere));
-        if (!(dot(new_d, normal) > 0)) return false;
-    } else {                                                         // LAMBERTIAN and METAL's 20 % branch: a diffuse event
-        new_d = scatter_diffuse_dir(in_sphere, normal);
-        diffuse_out = true;
-        if (L.depth + 1 < P.max_depth && light_on(T)) sample = light_sample(P, T, ls, point, normal, albedo, beta_in, sdir, c, code);
-    }
-    L.beta = mul(L.beta, att);
-    L.depth++;
-    if (L.depth >= P.max_depth) return false;
-    out_o = new_o;
-    out_d = new_d;
-    return true;
+    RTP_LIT_VERTEX(if (L.depth + 1 < P.max_depth && light_on(T)) sample = light_sample(P, T, ls, point, normal, albedo, beta_in, sdir, c, code);)
 }
 
 // one step of the lane's armed ray: reference order, through L1 / L2 (shadow: the ray is a shadow ray)
@@ -347,5 +353,227 @@ __global__ void __launch_bounds__(256) nee_probe_kernel(const KParams P, const N
 __global__ void __launch_bounds__(256) env_probe_kernel(const KParams P, const EnvDev E, uint32_t *env_seed_out) { light_probe_body(P, E, env_seed_out); }
 __global__ void __launch_bounds__(kLightBlock) nee_render_kernel(const KParams P, const NeeTable T) { light_render_body(P, T); }
 __global__ void __launch_bounds__(kLightBlock) env_render_kernel(const KParams P, const EnvDev E) { light_render_body(P, E); }
+
+// ---- rt_render_lit: the emitter table and an environment at once, from the lens camera (DESIGN.md §16) -------------------------------
+// The third light: both tables, either of which may be off (an emitter table with count 0 — sample_emitters = 0 or no emitter; env_on = 0
+// — no environment: a miss adds the background).  Spheres are hits and the map is misses, so the two never weight the same radiance:
+// miss and emitted are the single lights' own, and a vertex takes one sample of each light that is on, from that light's own stream.
+struct LitLight {
+    NeeTable N;
+    EnvDev E;
+    int32_t env_on;
+};
+__device__ __forceinline__ f3 light_miss(const KParams &P, const LitLight &T, const Lane &L, bool prev_diffuse) {
+    if (T.env_on) return light_miss(P, T.E, L, prev_diffuse);
+    return light_miss(P, T.N, L, prev_diffuse);
+}
+__device__ __forceinline__ f3 light_emitted(const KParams &P, const LitLight &T, const Lane &L, int32_t idx, bool is_plane, bool prev_diffuse, f3 emitted) {
+    return light_emitted(P, T.N, L, idx, is_plane, prev_diffuse, emitted);
+}
+__device__ __forceinline__ bool env_sampled(const LitLight &T) { return T.env_on && light_on(T.E); }
+
+// The two light samples of a lit vertex: the emitter's (a: the shadow ray has to reach sphere `code`) and the environment's (b: it has
+// to reach nothing).  Both are drawn at shade time — the streams are independent, and the order of the adds is the caller's.
+struct LitSamples {
+    f3 adir, ac, bdir, bc;
+    int32_t code;
+    bool a, b;
+};
+__device__ __forceinline__ bool shade_lit2(Lane &L, const KParams &P, const LitLight &T, bool prev_diffuse, uint32_t &nee, uint32_t &env, f3 &out_o,
+                                           f3 &out_d, LitSamples &S, bool &diffuse_out) {
+    S.a = false;
+    S.b = false;
+    diffuse_out = false;
+    RTP_LIT_VERTEX(if (L.depth + 1 < P.max_depth) {
+        if (light_on(T.N)) S.a = light_sample(P, T.N, nee, point, normal, albedo, beta_in, S.adir, S.ac, S.code);
+        if (env_sampled(T)) S.b = light_sample(P, T.E, env, point, normal, albedo, beta_in, S.bdir, S.bc, S.code);
+    })
+}
+#undef RTP_LIT_VERTEX
+// a sample's camera ray: the pinhole's (start_sample), or kLens: the lens / moving camera's
+template <bool kLens>
+__device__ __forceinline__ void lit_start(Lane &L, const KParams &P, const LensCam &C, int32_t i, int32_t j, uint32_t base_seed, int32_t s, f3 &o, f3 &d) {
+    if constexpr (kLens) lens_camera_ray(L, C, i, j, sample_seed1(base_seed, s), o, d);
+    else start_sample(L, P, i, j, base_seed, s, o, d);
+}
+// one step of the lane's armed ray (occlusion: the environment's shadow ray, which ends at its first accepted hit)
+__device__ __forceinline__ void lit_step(Lane &L, const KParams &P, bool occlusion) {
+    if (L.sp != 0) {
+        leaf_threaded(L, P.spheres, P.planes);
+        if (occlusion && L.hit >= 0) L.node = kBlocked;
+    } else {
+        step_threaded(L, P.tnodes, P.num_tnodes);
+    }
+}
+
+// ---- probe (rt_trace_samples_lit) ----------------------------------------------------------------------------------------------------
+template <bool kLens>
+__device__ __forceinline__ void lit_probe_body(const KParams &P, const LitLight &T, const LensCam &C, uint32_t *nee_seed_out, uint32_t *env_seed_out) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= P.probe_n) return;
+    const int32_t i = P.probe_ijs[3 * g], j = P.probe_ijs[3 * g + 1], s = P.probe_ijs[3 * g + 2];
+    Lane L;
+    const uint32_t base_seed = wang_hash((uint32_t)i * (uint32_t)P.width + (uint32_t)j);
+    uint32_t nee = light_seed_of(T.N, base_seed, s), env = light_seed_of(T.E, base_seed, s);
+    f3 ray_o, ray_d;
+    lit_start<kLens>(L, P, C, i, j, base_seed, s, ray_o, ray_d);
+    begin_ray(L, ray_o, ray_d, 0);
+    int32_t rays = 0;
+    bool prev_diffuse = false;
+    if (P.max_depth > 0) {
+        for (;;) {
+            rays++;
+            while (!traversal_finished<true>(L, kBlocked)) lit_step(L, P, false);
+            LitSamples S;
+            S.code = -1;
+            bool diffuse;
+            const bool more = shade_lit2(L, P, T, prev_diffuse, nee, env, ray_o, ray_d, S, diffuse);
+            if (S.a) {
+                rays++;
+                begin_ray(L, ray_o, S.adir, 0);
+                while (!traversal_finished<true>(L, kBlocked)) lit_step(L, P, false);
+                if (L.hit == S.code) L.color = add(L.color, S.ac);
+            }
+            if (S.b) {
+                rays++;
+                begin_ray(L, ray_o, S.bdir, 0);
+                while (!traversal_finished<true>(L, kBlocked)) lit_step(L, P, true);
+                if (L.hit < 0) L.color = add(L.color, S.bc);
+            }
+            if (!more) break;
+            prev_diffuse = diffuse;
+            begin_ray(L, ray_o, ray_d, 0);
+        }
+    }
+    P.probe_rad[3 * g] = L.color.x; P.probe_rad[3 * g + 1] = L.color.y; P.probe_rad[3 * g + 2] = L.color.z;
+    P.probe_rays[g] = rays;
+    P.probe_seed[g] = L.seed;
+    nee_seed_out[g] = nee;
+    env_seed_out[g] = env;
+}
+
+// ---- the trace kernel of rt_render_lit -----------------------------------------------------------------------------------------------
+// light_render_body's wave loop with a second shadow phase: path → emitter shadow (a full closest-hit walk) → environment shadow (ends at
+// its first hit) → path; a phase is skipped when its light gave no sample.  kLitShadowAB is the emitter's walk of a vertex whose
+// environment sample still waits.  Across the emitter's walk a lane holds the next direction, both pending contributions, the
+// environment's direction and the target (thirteen registers); across the environment's, the next direction and its contribution.
+constexpr int32_t kLitShadowA = 2, kLitShadowAB = 3, kLitShadowB = 4;
+template <bool kLens>
+__device__ __forceinline__ void lit_render_body(const KParams &P, const LitLight &T, const LensCam &C) {
+    const int lane = (int)(threadIdx.x & (kWave - 1));
+    Lane L;
+    L.node = kBlocked;
+    L.sp = 0;
+    L.hit = -1;
+    L.closest = 1e30f;
+    L.color = mk(0.0f, 0.0f, 0.0f);
+    L.beta = mk(1.0f, 1.0f, 1.0f);
+    L.depth = 0;
+    L.seed = 0;
+    int32_t phase = kLightIdle;
+    uint32_t w = 0, nee = 0, env = 0;
+    bool prev_diffuse = false;
+    f3 next_d = mk(0, 0, 0);
+    LitSamples S;
+    S.adir = S.ac = S.bdir = S.bc = mk(0, 0, 0);
+    S.code = -1;
+    S.a = S.b = false;
+    uint32_t pool_next = 0, pool_end = 0;        // (wave-uniform)
+    bool exhausted = false;
+    for (;;) {
+        // ---- lanes without a sample take the next work indices of the wave's pool (refilled with one atomic)
+        const uint64_t idle = __ballot(phase == kLightIdle);
+        if (idle != 0 && !exhausted) {
+            const uint32_t cnt = (uint32_t)__popcll(idle);
+            const uint32_t rank = (uint32_t)lane_rank(idle);
+            const uint32_t avail = pool_end - pool_next;
+            uint32_t mine;
+            if (avail < cnt) {
+                uint32_t base = 0;
+                if (lane == 0) base = atomicAdd(P.queue, kLightChunk);
+                base = __builtin_amdgcn_readfirstlane(base);
+                mine = rank < avail ? pool_next + rank : base + (rank - avail);
+                pool_next = base + (cnt - avail);
+                pool_end = base + kLightChunk;
+                if (base >= P.total_work) exhausted = true;
+            } else {
+                mine = pool_next + rank;
+                pool_next += cnt;
+            }
+            if (phase == kLightIdle && mine < P.total_work) {
+                w = mine;
+                int32_t pi, pj;
+                uint32_t k;
+                map_work(P, w, pi, pj, k);
+                const int32_t s = P.pass_first + (int32_t)k;
+                const uint32_t base_seed = wang_hash((uint32_t)pi * (uint32_t)P.width + (uint32_t)pj);
+                nee = light_seed_of(T.N, base_seed, s);
+                env = light_seed_of(T.E, base_seed, s);
+                f3 o, d;
+                lit_start<kLens>(L, P, C, pi, pj, base_seed, s, o, d);
+                begin_ray(L, o, d, 0);
+                prev_diffuse = false;
+                phase = kLightPath;
+            }
+        }
+        const bool busy = phase != kLightIdle;
+        if (!__any(busy)) {
+            if (exhausted) break;
+            continue;
+        }
+        const bool walking = busy && !traversal_finished<true>(L, kBlocked);
+        const bool ready = busy && !walking;
+        const int n_walk = __popcll(__ballot(walking));
+        const int n_ready = __popcll(__ballot(ready));
+        if (n_walk == 0 || n_ready >= kLightShadeLanes) {
+            if (ready) {
+                if (phase == kLightPath) {
+                    f3 next_o;
+                    bool diffuse;
+                    const bool more = shade_lit2(L, P, T, prev_diffuse, nee, env, next_o, next_d, S, diffuse);
+                    prev_diffuse = diffuse;
+                    if (S.a) {
+                        begin_ray(L, next_o, S.adir, 0);
+                        phase = S.b ? kLitShadowAB : kLitShadowA;
+                    } else if (S.b) {
+                        begin_ray(L, next_o, S.bdir, 0);
+                        phase = kLitShadowB;
+                    } else if (more) {
+                        begin_ray(L, next_o, next_d, 0);
+                    } else {
+                        store_sample(P, w, L.color);
+                        phase = kLightIdle;
+                    }
+                } else if (phase == kLitShadowB) {
+                    if (L.hit < 0) L.color = add(L.color, S.bc);
+                    begin_ray(L, L.o, next_d, 0);
+                    phase = kLightPath;
+                } else {
+                    if (L.hit == S.code) L.color = add(L.color, S.ac);
+                    const bool then_env = phase == kLitShadowAB;
+                    begin_ray(L, L.o, then_env ? S.bdir : next_d, 0);
+                    phase = then_env ? kLitShadowB : kLightPath;
+                }
+                if (phase == kLightIdle) {
+                    L.node = kBlocked;
+                    L.sp = 0;
+                }
+            }
+        } else {
+            const bool occlusion = phase == kLitShadowB;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if (!traversal_finished<true>(L, kBlocked)) lit_step(L, P, occlusion);
+            }
+        }
+    }
+}
+
+template <bool kLens>
+__global__ void __launch_bounds__(256) lit_probe_kernel(const KParams P, const LitLight T, const LensCam C, uint32_t *nee_seed_out, uint32_t *env_seed_out) {
+    lit_probe_body<kLens>(P, T, C, nee_seed_out, env_seed_out);
+}
+template <bool kLens>
+__global__ void __launch_bounds__(kLightBlock, 4) lit_render_kernel(const KParams P, const LitLight T, const LensCam C) { lit_render_body<kLens>(P, T, C); }
 
 }  // namespace rtk

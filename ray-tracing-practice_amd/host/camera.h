@@ -138,9 +138,12 @@ void gpu_render_pipelined(const SceneParams &params, const rt_scene_desc &desc, 
 // rtp_main --gpu --lens R:F / --motion-blur S: the orbit frame after frame on one GPU through rt_render_lens (shutter S: open at frame
 // n, closed at n + S; 0: no motion), saved with rt_tonemap; aov / denoise from rt_render_aov_lens
 // nee (rtp_main --nee): frames through rt_render_nee with these parameters instead (the lens and shutter then unused: a pinhole at frame n);
-// env (rtp_main --env): through rt_render_env with env_params, likewise
+// env (rtp_main --env): through rt_render_env with env_params, likewise;
+// lit (rtp_main --lit): through rt_render_lit with lit's emitters and environment, this lens and this shutter (lit->lens and
+// lit->cam_close are set per frame here), aov / denoise from rt_render_aov_lens
 void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const rt_lens_params &lens, float shutter, bool aov, bool denoise,
-                     const rt_nee_params *nee = nullptr, const rt_env *env = nullptr, const rt_env_params *env_params = nullptr);
+                     const rt_nee_params *nee = nullptr, const rt_env *env = nullptr, const rt_env_params *env_params = nullptr,
+                     const rt_lit_params *lit = nullptr);
 // rtp_main --gpu --adaptive: the orbit frame after frame on one GPU, each frame through rt_render_adaptive and rt_tonemap_spp
 void gpu_render_adaptive(const SceneParams &params, const rt_scene_desc &desc, const rt_adaptive_params &ap);
 

@@ -41,6 +41,30 @@ int main(int argc, char *argv[]) {
         if (std::string(argv[a]) == "--denoise") denoise = true;
         if (std::string(argv[a]) == "--denoise-temporal") temporal = true;
     }
+    // extension: `--gpu --lit`: every frame through rt_render_lit on one GPU — light samples of the emissive spheres (`--nee [mis|light]`
+    // picks their weighting), and with it, and only with it, `--env FILE[:N]` (with --env-mode, --env-scale, --env-up), `--lens R:F` and
+    // `--motion-blur S` in any combination; --aov / --denoise as with --lens (first hits do not depend on the estimator).  Each of those
+    // flags is parsed by its own block below, which hands its value on instead of rendering.  Not with --adaptive, --denoise-temporal,
+    // --devices, --shard or RTP_DEVICES.
+    bool lit_on = false;
+    rt_env *lit_env = nullptr;
+    rt_env_params lit_ep;
+    rt_env_params_init(&lit_ep);
+    rt_nee_params lit_nee;
+    rt_nee_params_init(&lit_nee);
+    {
+        bool lit_others = getenv("RTP_DEVICES") != nullptr;
+        for (int a = 2; a < argc; ++a) {
+            const std::string arg = argv[a];
+            if (arg == "--lit") lit_on = true;
+            if (arg == "--adaptive" || arg == "--denoise-temporal" || arg == "--devices" || arg == "--shard") lit_others = true;
+        }
+        if (lit_on && lit_others) {
+            std::cerr << "rtp_main: --lit renders frame after frame on one GPU: it cannot be combined with --adaptive, --denoise-temporal, "
+                         "--devices, --shard or RTP_DEVICES\n";
+            return 99;
+        }
+    }
     // extension: `--gpu --env FILE[:N] [--env-mode path|mis|light] [--env-scale S] [--env-up y|z]`: every frame through rt_render_env on one
     // GPU, lit by the lat-long image FILE (PFM or Radiance .hdr) resampled into an N x N octahedral map (N defaults to 1024); mis is the
     // default mode, --env-up z turns the map for a z-up scene such as the default configuration; the same saver bytes, --aov /
@@ -54,8 +78,8 @@ int main(int argc, char *argv[]) {
         for (int a = 2; a < argc; ++a) {
             const std::string arg = argv[a];
             const std::string value = a + 1 < argc ? argv[a + 1] : "";
-            if (arg == "--nee" || arg == "--lens" || arg == "--motion-blur" || arg == "--adaptive" || arg == "--denoise-temporal" || arg == "--devices" ||
-                arg == "--shard")
+            if (!lit_on && (arg == "--nee" || arg == "--lens" || arg == "--motion-blur" || arg == "--adaptive" || arg == "--denoise-temporal" ||
+                            arg == "--devices" || arg == "--shard"))
                 env_others = true;
             if (arg == "--env") {
                 env_on = true;
@@ -111,11 +135,16 @@ int main(int argc, char *argv[]) {
                 std::cerr << "rtp_main: --env: " << env_file << ": " << rt_get_last_error_string() << "\n";
                 return 99;
             }
-            rt_lens_params pinhole;
-            rt_lens_params_init(&pinhole);
-            rtp::gpu_render_lens(params, desc, pinhole, 0.0f, aov, denoise, nullptr, env, &ep);
-            rt_env_destroy(env);
-            return 0;
+            if (lit_on) {
+                lit_env = env;
+                lit_ep = ep;
+            } else {
+                rt_lens_params pinhole;
+                rt_lens_params_init(&pinhole);
+                rtp::gpu_render_lens(params, desc, pinhole, 0.0f, aov, denoise, nullptr, env, &ep);
+                rt_env_destroy(env);
+                return 0;
+            }
         }
     }
     // extension: `--gpu --nee [mis|light]`: every frame through rt_render_nee on one GPU (direct light sampling of the emissive spheres,
@@ -146,15 +175,19 @@ int main(int argc, char *argv[]) {
                 std::cerr << "rtp_main: --nee takes mis (default) or light\n";
                 return 99;
             }
-            if (nee_others) {
+            if (lit_on) {
+                lit_nee = nee;
+            } else if (nee_others) {
                 std::cerr << "rtp_main: --nee renders frame after frame on one GPU: it cannot be combined with --lens, --motion-blur, "
                              "--adaptive, --denoise-temporal, --devices, --shard or RTP_DEVICES\n";
                 return 99;
             }
-            rt_lens_params pinhole;
-            rt_lens_params_init(&pinhole);
-            rtp::gpu_render_lens(params, desc, pinhole, 0.0f, aov, denoise, &nee);
-            return 0;
+            if (!lit_on) {
+                rt_lens_params pinhole;
+                rt_lens_params_init(&pinhole);
+                rtp::gpu_render_lens(params, desc, pinhole, 0.0f, aov, denoise, &nee);
+                return 0;
+            }
         }
     }
     // extension: `--gpu --lens R:F` (thin lens of radius R focused at distance F) and / or `--gpu --motion-blur S` (shutter open from
@@ -186,7 +219,7 @@ int main(int argc, char *argv[]) {
                 if (a + 1 >= argc || sscanf(argv[a + 1], "%f%c", &shutter, &tail) != 1 || !(shutter > 0.0f && shutter <= 1.0f)) lens_bad = true;
             }
         }
-        if (lens_on || motion_on) {
+        if (lens_on || motion_on || lit_on) {
             if (lens_bad) {
                 std::cerr << "rtp_main: --lens takes R:F (R >= 0, F > 0, finite) and --motion-blur takes S (0 < S <= 1)\n";
                 return 99;
@@ -195,6 +228,16 @@ int main(int argc, char *argv[]) {
                 std::cerr << "rtp_main: --lens / --motion-blur render frame after frame on one GPU: they cannot be combined with "
                              "--denoise-temporal, --adaptive, --devices, --shard or RTP_DEVICES\n";
                 return 99;
+            }
+            if (lit_on) {
+                rt_lit_params lit;
+                rt_lit_params_init(&lit);
+                lit.nee = &lit_nee;
+                lit.env = lit_env;
+                lit.env_params = &lit_ep;
+                rtp::gpu_render_lens(params, desc, lens, shutter, aov, denoise, nullptr, nullptr, nullptr, &lit);
+                rt_env_destroy(lit_env);
+                return 0;
             }
             rtp::gpu_render_lens(params, desc, lens, shutter, aov, denoise);
             return 0;

@@ -257,9 +257,10 @@ void gpu_render_pipelined(const SceneParams &params, const rt_scene_desc &desc, 
 // the lens has radius lens.lens_radius.  Saved through rt_tonemap with the frame's divisor — the bytes gpu_render's saver writes for
 // these sums.  aov / denoise as in gpu_render, from rt_render_aov_lens.
 // nee: the frames through rt_render_nee (rtp_main --nee), the AOVs through rt_render_aov_samples — the same first hits; env: through
-// rt_render_env with env_params (rtp_main --env), the AOVs likewise
+// rt_render_env with env_params (rtp_main --env), the AOVs likewise; lit: through rt_render_lit (rtp_main --lit) with this lens and
+// shutter, the AOVs through rt_render_aov_lens
 void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const rt_lens_params &lens, float shutter, bool aov, bool denoise,
-                     const rt_nee_params *nee, const rt_env *env, const rt_env_params *env_params) {
+                     const rt_nee_params *nee, const rt_env *env, const rt_env_params *env_params, const rt_lit_params *lit) {
     rt_scene *scene = nullptr;
     RTP_CHECK(rt_scene_create(&desc, &scene));
     const size_t num_pixels = static_cast<size_t>(params.width) * params.height;
@@ -304,7 +305,12 @@ void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const
         const rt_camera_data close = camera_at(static_cast<float>(n) + shutter);
         const rt_camera_data *cam_close = shutter > 0.0f ? &close : nullptr;
         const auto t0 = std::chrono::steady_clock::now();
-        if (env) RTP_CHECK(rt_render_env(scene, &cam, env, env_params, nullptr, 0, d_fb, nullptr, 1, nullptr));
+        if (lit) {
+            rt_lit_params frame_lit = *lit;
+            frame_lit.cam_close = cam_close;
+            frame_lit.lens = &lens;
+            RTP_CHECK(rt_render_lit(scene, &cam, &frame_lit, nullptr, 0, d_fb, nullptr, 1, nullptr));
+        } else if (env) RTP_CHECK(rt_render_env(scene, &cam, env, env_params, nullptr, 0, d_fb, nullptr, 1, nullptr));
         else if (nee) RTP_CHECK(rt_render_nee(scene, &cam, nee, nullptr, 0, d_fb, nullptr, 1, nullptr));
         else RTP_CHECK(rt_render_lens(scene, &cam, cam_close, &lens, nullptr, 0, d_fb, nullptr, 1, nullptr));
         RTP_CHECK(rt_tonemap(d_fb, d_rgb, static_cast<int64_t>(num_pixels) * 3, params.sqrt_spp, nullptr));
@@ -316,7 +322,7 @@ void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const
         const long long total_rays = static_cast<long long>(params.width) * params.height * params.sqrt_spp * params.sqrt_spp;
         std::cout << n << "\t" << ms << "\t" << total_rays << "\n";
         if (aov || denoise) {          // (outside the frame's timed span, as in gpu_render)
-            if (nee || env) RTP_CHECK(rt_render_aov_samples(scene, &cam, nullptr, 0, &aov_bufs, nullptr, 1, nullptr));
+            if (!lit && (nee || env)) RTP_CHECK(rt_render_aov_samples(scene, &cam, nullptr, 0, &aov_bufs, nullptr, 1, nullptr));
             else RTP_CHECK(rt_render_aov_lens(scene, &cam, cam_close, &lens, nullptr, 0, &aov_bufs, nullptr, 1, nullptr));
             if (aov) {
                 h_albedo.resize(num_pixels * 3); h_normal.resize(num_pixels * 3); h_depth.resize(num_pixels); h_hits.resize(num_pixels);

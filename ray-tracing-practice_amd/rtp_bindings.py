@@ -221,11 +221,48 @@ def env_params(**params):
     return p
 
 
+env_params_of = env_params      # (lit_params has an argument of that name)
+
+
 def _env_struct(params):
     """None → NULL (the defaults); an EnvParams as it is; a dict → env_params(**dict)."""
     if params is None:
         return None
     return C.byref(params if isinstance(params, EnvParams) else env_params(**params))
+
+
+class LitParams(C.Structure):
+    """rt_lit_params (include/rtp_amd.h): an IN structure of the caller's size — struct_bytes is set on construction; the other fields
+    are 0 until rt_lit_params_init (lit_params()) fills the defaults.  The pointers are borrowed: lit_params() keeps what it points
+    into alive in `_keep`."""
+    _fields_ = [("struct_bytes", C.c_uint32), ("sample_emitters", C.c_int32), ("cam_close", C.POINTER(CameraData)),
+                ("lens", C.POINTER(LensParams)), ("nee", C.POINTER(NeeParams)), ("env", C.c_void_p), ("env_params", C.POINTER(EnvParams))]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_bytes = C.sizeof(LitParams)
+
+
+def lit_params(cam_close=None, lens=None, emitters=True, nee=None, env=None, env_params=None):
+    """rt_lit_params with the library's defaults, then: cam_close a CameraData (None: no motion); lens, nee, env_params None (the
+    defaults), the params structure or a dict of its fields; emitters False: no light samples of the emitter table; env an Env."""
+    p = LitParams()
+    amd_lib().rt_lit_params_init(C.byref(p))
+    p.sample_emitters = int(emitters) if not isinstance(emitters, bool) else (1 if emitters else 0)
+    keep = []
+    if cam_close is not None:
+        p.cam_close = C.pointer(cam_close)
+    for field, value, kind, make in (("lens", lens, LensParams, lens_params), ("nee", nee, NeeParams, nee_params),
+                                     ("env_params", env_params, EnvParams, env_params_of)):
+        if value is not None:
+            value = value if isinstance(value, kind) else make(**value)
+            keep.append(value)
+            setattr(p, field, C.pointer(value))
+    if env is not None:
+        p.env = env._h
+        keep.append(env)
+    p._keep = keep
+    return p
 
 
 class Env:
@@ -344,6 +381,7 @@ RTP_AMD_SYMBOLS = [
     "rt_nee_params_init", "rt_render_nee", "rt_nee_light_table", "rt_trace_samples_nee",
     "rt_env_params_init", "rt_env_create", "rt_env_destroy", "rt_env_table", "rt_env_lookup", "rt_env_from_equirect", "rt_render_env",
     "rt_trace_samples_env",
+    "rt_lit_params_init", "rt_render_lit", "rt_trace_samples_lit",
 ]
 
 _host = None
@@ -466,6 +504,13 @@ def amd_lib():
             lib.rt_render_env.argtypes = [C.c_void_p, C.POINTER(CameraData), C.c_void_p, C.POINTER(EnvParams), C.POINTER(Shard), C.c_int32,
                                           C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(Timing)]
             lib.rt_trace_samples_env.argtypes = [C.c_void_p, C.POINTER(CameraData), C.c_void_p, C.POINTER(EnvParams), C.c_int32, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(lib, "rt_render_lit"):
+            lib.rt_lit_params_init.argtypes = [C.POINTER(LitParams)]
+            lib.rt_lit_params_init.restype = None
+            lib.rt_render_lit.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(LitParams), C.POINTER(Shard), C.c_int32, C.c_void_p,
+                                          C.c_void_p, C.c_int32, C.POINTER(Timing)]
+            lib.rt_trace_samples_lit.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(LitParams), C.c_int32, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.rt_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         lib.rt_last_timing.argtypes = [C.c_void_p, C.POINTER(Timing)]
@@ -1129,6 +1174,45 @@ class DeviceScene:
         _check(amd_lib().rt_trace_samples_env(self._h, C.byref(cam), env._h, _env_struct(params), n, ijs.ctypes.data, rad.ctypes.data,
                                               rays.ctypes.data, seeds.ctypes.data, es.ctypes.data), "rt_trace_samples_env")
         return rad, rays, seeds, es
+
+    def render_lit(self, cam, d_fb_ptr, *, cam_close=None, lens=None, emitters=True, nee=None, env=None, env_params=None, shard=None,
+                   stream=None, sync=True, sample_first=0):
+        """rt_render_lit: emitters, environment and lens in one frame (lit_params()'s arguments).  Returns the rt_timing of this call."""
+        t = Timing()
+        self._apply_config()
+        lit = lit_params(cam_close=cam_close, lens=lens, emitters=emitters, nee=nee, env=env, env_params=env_params)
+        _check(amd_lib().rt_render_lit(self._h, C.byref(cam), C.byref(lit), C.byref(shard) if shard else None, sample_first,
+                                       C.c_void_p(d_fb_ptr), C.c_void_p(stream or 0), 1 if sync else 0, C.byref(t)), "rt_render_lit")
+        return t
+
+    def render_lit_to_host(self, cam, *, cam_close=None, lens=None, emitters=True, nee=None, env=None, env_params=None, shard=None,
+                           sample_first=0):
+        """rt_render_lit through a fresh device buffer: (rows, width, 3) float32 sums and the rt_timing."""
+        lib = amd_lib()
+        rows = lib.rt_shard_rows(cam.image_height, C.byref(shard) if shard else None)
+        fb = np.empty((rows, cam.image_width, 3), dtype=np.float32)
+        d = C.c_void_p()
+        _check(lib.rt_device_alloc(fb.nbytes or 12, C.byref(d)), "rt_device_alloc")
+        try:
+            t = self.render_lit(cam, d.value, cam_close=cam_close, lens=lens, emitters=emitters, nee=nee, env=env, env_params=env_params,
+                                shard=shard, sample_first=sample_first)
+            _check(lib.rt_copy_to_host(fb.ctypes.data, d, fb.nbytes), "rt_copy_to_host")
+        finally:
+            lib.rt_device_free(d)
+        return fb, t
+
+    def trace_samples_lit(self, cam, ijs, *, cam_close=None, lens=None, emitters=True, nee=None, env=None, env_params=None):
+        """rt_trace_samples_lit: ijs (n, 3) → (radiance (n, 3), rays (n,), final seeds (n,), final emitter-stream seeds (n,), final
+        environment-stream seeds (n,))."""
+        ijs = np.ascontiguousarray(ijs, dtype=np.int32).reshape(-1, 3)
+        n = ijs.shape[0]
+        rad = np.empty((n, 3), dtype=np.float32)
+        rays = np.empty(n, dtype=np.int32)
+        seeds, ns, es = np.empty(n, dtype=np.uint32), np.empty(n, dtype=np.uint32), np.empty(n, dtype=np.uint32)
+        lit = lit_params(cam_close=cam_close, lens=lens, emitters=emitters, nee=nee, env=env, env_params=env_params)
+        _check(amd_lib().rt_trace_samples_lit(self._h, C.byref(cam), C.byref(lit), n, ijs.ctypes.data, rad.ctypes.data, rays.ctypes.data,
+                                              seeds.ctypes.data, ns.ctypes.data, es.ctypes.data), "rt_trace_samples_lit")
+        return rad, rays, seeds, ns, es
 
     def last_kernel_ms(self):
         ms = C.c_float()
