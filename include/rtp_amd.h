@@ -586,7 +586,7 @@ rt_status rt_lens_camera_rays(const rt_camera_data *cam_open, const rt_camera_da
  *   Emitter table (built on a handle's first rt_render_nee and kept): the spheres, in sphere order, with radius > 0 whose material's
  *     emit components are all finite and >= 0 and not all 0.  w_i = (e0 + e1 + e2) * r^2, summed in double; cdf_i = (float)(prefix
  *     sum through i / total), the last one 1; pmf_i = cdf_i - cdf_{i-1} in float (cdf_{-1} = 0): the probability the pick below
- *     gives.  Emissive planes and other emitters are found by the path alone (weight 1).
+ *     gives.  Emissive planes are found by the path alone (weight 1) unless sample_planes = 1 (below); other emitters always are.
  *   Streams: the path draws exactly what rt_render_samples draws, from the same seed.  The light samples draw from their own state,
  *     nee = wang_hash(wang_hash(base + s) ^ RT_NEE_STREAM_KEY), base = wang_hash(i * W + j), with random_float.
  *   Diffuse event: a LAMBERTIAN hit, or a METAL hit whose branch draw chose the hemisphere branch, at the point x of closest-hit query
@@ -612,8 +612,26 @@ rt_status rt_lens_camera_rays(const rt_camera_data *cam_open, const rt_camera_da
  *   Order: at each vertex the emission term first, then the vertex's light sample; sums over samples sample_first … in sample order
  *     from 0.  Where no diffuse event takes a light sample (an empty table, a scene without diffuse surfaces) the call is
  *     rt_render_samples bit for bit.
+ *   sample_planes = 1 (read only when struct_bytes >= 12, an older 8-byte caller gets 0): the emitter table also holds the
+ *     emissive QUAD, ELLIPSE and TRIANGLE planes.  Its entries are the spheres of the table above, in sphere order, then the planes, in
+ *     plane order, whose type is one of the three, whose material's (any type) emit components are all finite and >= 0 and not all 0,
+ *     and whose area A is finite and > 0: A = (float)(k * sqrt(dot(n, n))) in double, n = cross(u, v) in double from the float u, v,
+ *     k = 1 (QUAD), pi / 4 (ELLIPSE), 1 / 2 (TRIANGLE).  Weights in double: a sphere's (e0 + e1 + e2) * r^2 as above, a plane's
+ *     (e0 + e1 + e2) * A / pi (both: emission x largest projected area / pi); cdf and pmf as above.  A scene without such a plane has
+ *     the same table under both settings, and every call is then sample_planes = 0 bit for bit.  A handle keeps both tables.
+ *     The light sample is step 1, then by the kind of entry e: a sphere takes steps 2 to 4; plane e (rt_plane base, u, v, normal) takes
+ *     2p. QUAD: a = random_float(nee), b = random_float(nee).  TRIANGLE: the same two draws, then if a + b > 1: a = 1 - a, b = 1 - b.
+ *         ELLIPSE: step 3's rejection loop (px first) repeated while q2 >= 1; a = 0.5f + 0.5f * px, b = 0.5f + 0.5f * py.
+ *         y_k = (base_k + a * u_k) + b * v_k.
+ *     3p. w = y - x; d2 = dot(w, w); !(d2 > 0): none; len = sqrtf(d2); wl_k = w_k / len; cos_l = fabsf(dot(normal, wl));
+ *         !(cos_l >= 1e-8f): none; pa = d2 / (cos_l * A); pl = pmf_e * pa.
+ *     4p. !(dot(wl, n) > 0): none.  Otherwise the shadow ray (x, wl): its closest hit over (0.001, 1e30) in the reference's visit order
+ *         contributes only if it is plane e (a sample whose ray misses its own plane by rounding at the rim counts nothing); f and the
+ *         contribution are step 4's with this pl and the plane's material's emit.  Emission is two-sided: no facing test on the light.
+ *     BSDF hits: the hit of the query k + 1 ray that leaves a diffuse event at x, on a plane e of the table at the point p, is weighted
+ *     by w_b with pl from step 3p for w = p - x (0 where 3p gives none).  Planes outside the table keep weight 1.
  * Checks and limits: rt_render_samples's (rows of a shard only: no tiles, no rt_context); every refusal comes before anything is
- * enqueued; RT_ERR_INVALID_ARG for params with struct_bytes below 8 or mis outside {0, 1}.  The light samples run on the
+ * enqueued; RT_ERR_INVALID_ARG for params with struct_bytes below 8, mis outside {0, 1} or sample_planes outside {0, 1}.  The light samples run on the
  * reference-order walk only.  Handle state: the call leaves the handle's own decisions alone, as rt_render_lens does — its walk choice,
  * a pause of the guarded walk, the re-pack of its tree, its cached view lists and what rt_last_timing reports; timing (may be NULL)
  * is this call's record (kernel_ms with sync != 0). */
@@ -623,16 +641,22 @@ rt_status rt_lens_camera_rays(const rt_camera_data *cam_open, const rt_camera_da
 typedef struct rt_nee_params {   /* IN, grows like rt_lens_params: the library reads at most struct_bytes; < 8 = RT_ERR_INVALID_ARG */
     uint32_t struct_bytes;       /* sizeof(rt_nee_params) as the caller compiled it */
     int32_t  mis;                /* 1 (default): power heuristic; 0: light sampling alone (the BSDF hit of a table sphere counts 0) */
-    int32_t  reserved[2];        /* 0: room to grow */
+    int32_t  sample_planes;      /* 0 (default): spheres only; 1: emissive QUAD / ELLIPSE / TRIANGLE planes are sampled too (struct_bytes >= 12) */
+    int32_t  reserved[1];        /* 0: room to grow */
 } rt_nee_params;
 /* Defaults into *p, struct_bytes = sizeof(rt_nee_params). */
 void rt_nee_params_init(rt_nee_params *p);
 /* rt_render_samples with next-event estimation (params NULL: defaults). */
 rt_status rt_render_nee(rt_scene *scene, const rt_camera_data *cam, const rt_nee_params *params, const rt_shard *shard, int32_t sample_first,
                         float *d_fb_sum, void *hip_stream, int32_t sync, rt_timing *timing);
-/* Probe for tests, HOST memory: the emitter table (built if the handle has none yet).  *count = its length; the first min(cap, count)
- * entries go to sphere_index, cdf and pmf (each may be NULL when cap is 0). */
+/* Probe for tests, HOST memory: the sphere-only emitter table (built if the handle has none yet).  *count = its length; the first
+ * min(cap, count) entries go to sphere_index, cdf and pmf (each may be NULL when cap is 0). */
 rt_status rt_nee_light_table(rt_scene *scene, int32_t cap, int32_t *sphere_index, float *cdf, float *pmf, int32_t *count);
+/* Probe for tests, HOST memory: the emitter table that params select (NULL: the defaults), built if the handle has none yet.  kind: 0 a
+ * sphere, 1 a plane; index: the sphere or plane index; area: A of a plane, 0 for a sphere.  count and cap as above; the parameter checks
+ * are rt_render_nee's and come first. */
+rt_status rt_nee_emitter_table(rt_scene *scene, const rt_nee_params *params, int32_t cap, int32_t *kind, int32_t *index, float *cdf, float *pmf,
+                               float *area, int32_t *count);
 /* Probe for tests, HOST memory: rt_trace_samples for the estimator of rt_render_nee — radiance, rays (closest-hit queries, shadow rays
  * included), the path's final RNG state and the light samples' final state per (i, j, s). */
 rt_status rt_trace_samples_nee(rt_scene *scene, const rt_camera_data *cam, const rt_nee_params *params, int32_t n, const int32_t *ijs,
@@ -731,13 +755,13 @@ rt_status rt_env_from_equirect(const float *rgb, int32_t w, int32_t h, int32_t n
  *     emitters: sample_emitters == 0 or an empty table; the environment: env == NULL, mode 0 or an empty table) never advances its
  *     state; rt_trace_samples_lit reports it as initialised.
  *   At the vertex of closest-hit query k, in this order:
- *     1. the emission or miss term.  A hit on a sphere of the emitter table by a ray that left a diffuse event adds
+ *     1. the emission or miss term.  A hit on a sphere (nee->sample_planes = 1: an entry) of the emitter table by a ray that left a diffuse event adds
  *        (beta_k * emit_k) * w_b with rt_render_nee's w_b when sample_emitters != 0 (nothing to weight where the table is empty);
  *     2. a miss adds rt_render_env's miss term when env != NULL — with its w_b after a diffuse event when mode != 0 and the map's
  *        table is not empty, and with its camera_visible rule for query 0 — and beta_k * cam->background otherwise;
  *     3. every other emission keeps weight 1;
  *     4. at a diffuse event with k + 1 < max_depth: the emitter sample, rt_render_nee's steps 1 … 4 from the nee state; its shadow
- *        ray's closest hit must be sphere e; its contribution is added to the sample's radiance as soon as it is known to count;
+ *        ray's closest hit must be sphere e (nee->sample_planes = 1: steps 2p … 4p for a plane entry, and the hit must be entry e); its contribution is added to the sample's radiance as soon as it is known to count;
  *     5. at the same event: the environment sample, rt_render_env's steps 1 … 4 from the env state; its shadow ray is an occlusion
  *        query from the same point x; its contribution is added after the emitter's.
  *   Spheres are hits and the map is misses: the two estimators never weight the same radiance, each keeps its own two-strategy MIS
@@ -749,7 +773,8 @@ rt_status rt_env_from_equirect(const float *rgb, int32_t w, int32_t h, int32_t n
  * is enqueued (nee is read only when sample_emitters != 0, env_params only when env != NULL); lit == NULL means the defaults;
  * RT_ERR_INVALID_ARG for a struct_bytes below 8 and for sample_emitters outside {0, 1}.  Rows of a shard only: no tiles, no rt_context.
  * Handle state: as rt_render_nee — the handle's walk choice, a pause of the guarded walk, the re-pack, the view lists and rt_last_timing
- * are left alone; the emitter table is the handle's one table, built by whichever of rt_render_nee / rt_render_lit comes first.  The
+ * are left alone; the emitter tables (the sphere-only one and sample_planes = 1's) are the handle's two tables, built together by whichever
+ * of rt_render_nee / rt_render_lit comes first.  The
  * light samples run on the reference-order walk only (timing->guarded is 0); timing (may be NULL) is this call's record. */
 typedef struct rt_lit_params {          /* IN, grows like rt_env_params: the library reads at most struct_bytes; < 8 = RT_ERR_INVALID_ARG */
     uint32_t struct_bytes;              /* sizeof(rt_lit_params) as the caller compiled it */

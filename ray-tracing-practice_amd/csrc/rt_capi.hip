@@ -306,6 +306,13 @@ struct rt_scene {
     std::vector<float> nee_cdf, nee_pmf;
     int32_t *nee_index_dev = nullptr;
     float *nee_cdf_dev = nullptr, *nee_pmf_dev = nullptr;
+    // … and the table of sample_planes = 1 (spheres, then planes: code = 2 * index + kind), made by the same call.  Without a qualifying
+    // plane it is the first table again and is never handed to a kernel (emit_planes == 0: no device columns)
+    std::vector<int32_t> emit_code;
+    std::vector<float> emit_cdf, emit_pmf, emit_area;
+    int32_t emit_spheres = 0, emit_planes = 0;
+    int32_t *emit_code_dev = nullptr;
+    float *emit_cdf_dev = nullptr, *emit_pmf_dev = nullptr, *emit_area_dev = nullptr;
 };
 
 namespace {
@@ -674,6 +681,7 @@ rt_status rt_scene_destroy(rt_scene *sc) {
     for (CallClock &c : sc->clock) c.destroy();         // (every family's events and counter words)
     (void)hipFree(sc->adapt_mom); (void)hipFree(sc->adapt_list); (void)hipFree(sc->adapt_work); (void)hipFree(sc->adapt_counters);
     (void)hipFree(sc->nee_index_dev); (void)hipFree(sc->nee_cdf_dev); (void)hipFree(sc->nee_pmf_dev);
+    (void)hipFree(sc->emit_code_dev); (void)hipFree(sc->emit_cdf_dev); (void)hipFree(sc->emit_pmf_dev); (void)hipFree(sc->emit_area_dev);
     for (rt_scene::Feedback &f : sc->feedback) {
         if (f.done) { if (f.pending) (void)hipEventSynchronize(f.done); (void)hipEventDestroy(f.done); }
         if (f.start) (void)hipEventDestroy(f.start);
@@ -1916,7 +1924,8 @@ rt_status adaptive_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard 
 // the trace launch; nothing of the handle's walk machinery is touched.
 //   trace: a kernel (KParams, Light) — or, with lens, (KParams, Light, LensCam): rt_render_lit's;
 //   light_device: the device of a light that is an object of its own (null: the light is the handle's);
-//   make_light: fills the kernel's second argument, once the call is known to trace
+//   make_light(T, kernel): fills the kernel's second argument, once the call is known to trace — and may name another kernel for it (a
+//   Light that is a union of two table types: which one the handle's emitter table needs is known only then)
 template <class Light, class MakeLight>
 rt_status render_light_impl(const char *what, const void *trace, const int *light_device, MakeLight make_light, rt_scene *sc,
                             const rt_camera_data *cam, const rt_shard *shard, int32_t sample_first, float *d_fb_sum, void *hip_stream, int32_t sync,
@@ -1931,12 +1940,12 @@ rt_status render_light_impl(const char *what, const void *trace, const int *ligh
     const uint32_t num_pixels = F.num_pixels;
     if (P.spp <= 0 || P.max_depth <= 0) return blank_frame(d_fb_sum, F, sync);
     Light T;
-    if ((st = make_light(T)) != RT_OK) return st;
+    const void *kernel = trace;
+    if ((st = make_light(T, kernel)) != RT_OK) return st;
     P.fb = d_fb_sum;
     rtaccel::PassPlan passes;
     if ((st = reserve_slab(sc, num_pixels, P.spp, stream, passes)) != RT_OK) return st;
     bind_slab(sc, P, num_pixels, passes.pass_size);          // (no candidate lists: fill_params left P.cand and P.order null)
-    const void *kernel = trace;
     int per_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, rtk::kLightBlock, 0) != hipSuccess || per_cu < 1) {
         (void)hipGetLastError();
@@ -2180,46 +2189,29 @@ void rt_nee_params_init(rt_nee_params *p) {
 }
 
 namespace {
-rt_status nee_setup(const char *what, const rt_nee_params *params, int32_t &mis) {
+// what a call's rt_nee_params say, after their checks
+struct NeeSetup {
+    int32_t mis = 1;
+    int32_t planes = 0;           // sample_planes
+};
+rt_status nee_setup(const char *what, const rt_nee_params *params, NeeSetup &N) {
     const std::string w(what);
     rt_nee_params np;
     rt_nee_params_init(&np);
     if (const rt_status st = take_params(w, "rt_nee_params", params, np)) return st;
+    if (params && params->struct_bytes < 12u) np.sample_planes = 0;          // (an older caller's struct ends before the field)
     if (np.mis != 0 && np.mis != 1) return fail(RT_ERR_INVALID_ARG, w + ": mis must be 0 or 1");
-    mis = np.mis;
+    if (np.sample_planes != 0 && np.sample_planes != 1) return fail(RT_ERR_INVALID_ARG, w + ": sample_planes must be 0 or 1");
+    N.mis = np.mis;
+    N.planes = np.sample_planes;
     return RT_OK;
 }
 
-// The emitter table of the header, from the handle's own device tables (read back once: rt_scene_create keeps no host copy of them)
-rt_status nee_table_ensure(rt_scene *sc) {
-    if (sc->nee_built) return RT_OK;
-    const int32_t ns = sc->num_spheres, nm = sc->num_materials;
-    std::vector<float4> spheres((size_t)ns), materials((size_t)nm * 3);
-    std::vector<int32_t> smat((size_t)ns);
-    if (ns > 0) {
-        HIP_TRY(hipMemcpy(spheres.data(), sc->spheres, (size_t)ns * sizeof(float4), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(smat.data(), sc->sphere_mat, (size_t)ns * sizeof(int32_t), hipMemcpyDeviceToHost));
-    }
-    if (nm > 0) HIP_TRY(hipMemcpy(materials.data(), sc->materials, materials.size() * sizeof(float4), hipMemcpyDeviceToHost));
-    std::vector<int32_t> index;
-    std::vector<double> weight;
-    for (int32_t i = 0; i < ns; ++i) {
-        const float r = spheres[(size_t)i].w;
-        const int32_t m = smat[(size_t)i];
-        if (!(r > 0.0f) || m < 0 || m >= nm) continue;
-        const float4 e = materials[(size_t)m * 3 + 1];
-        const float ev[3] = {e.x, e.y, e.z};
-        bool ok = true, lit = false;
-        for (float c : ev) {
-            if (!(std::isfinite(c) && c >= 0.0f)) ok = false;
-            if (c > 0.0f) lit = true;
-        }
-        if (!ok || !lit) continue;
-        index.push_back(i);
-        weight.push_back(((double)e.x + (double)e.y + (double)e.z) * ((double)r * (double)r));
-    }
-    const size_t n = index.size();
-    std::vector<float> cdf(n), pmf(n);
+// cdf and pmf of the header from an emitter table's weights: double prefix sums, the last cdf entry 1, pmf the float difference
+void nee_cdf_of(const std::vector<double> &weight, std::vector<float> &cdf, std::vector<float> &pmf) {
+    const size_t n = weight.size();
+    cdf.assign(n, 0.0f);
+    pmf.assign(n, 0.0f);
     double total = 0.0;
     for (double x : weight) total += x;
     double run = 0.0;
@@ -2228,11 +2220,86 @@ rt_status nee_table_ensure(rt_scene *sc) {
         cdf[k] = k + 1 == n ? 1.0f : (float)(run / total);
         pmf[k] = cdf[k] - (k == 0 ? 0.0f : cdf[k - 1]);
     }
+}
+
+// The emitter tables of the header — the sphere-only one and the one of sample_planes = 1 — from the handle's own device tables (read
+// back once: rt_scene_create keeps no host copy of them)
+rt_status nee_table_ensure(rt_scene *sc) {
+    if (sc->nee_built) return RT_OK;
+    const int32_t ns = sc->num_spheres, nm = sc->num_materials, npl = sc->num_planes;
+    std::vector<float4> spheres((size_t)ns), materials((size_t)nm * 3), planes((size_t)npl * 5);
+    if (npl > 0) HIP_TRY(hipMemcpy(planes.data(), sc->planes, planes.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    std::vector<int32_t> smat((size_t)ns);
+    if (ns > 0) {
+        HIP_TRY(hipMemcpy(spheres.data(), sc->spheres, (size_t)ns * sizeof(float4), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(smat.data(), sc->sphere_mat, (size_t)ns * sizeof(int32_t), hipMemcpyDeviceToHost));
+    }
+    if (nm > 0) HIP_TRY(hipMemcpy(materials.data(), sc->materials, materials.size() * sizeof(float4), hipMemcpyDeviceToHost));
+    // emit of material m as a light's: its sum in double, or a negative number when m does not qualify
+    auto emit_sum = [&](int32_t m) {
+        if (m < 0 || m >= nm) return -1.0;
+        const float4 e = materials[(size_t)m * 3 + 1];
+        const float ev[3] = {e.x, e.y, e.z};
+        bool ok = true, lit = false;
+        for (float c : ev) {
+            if (!(std::isfinite(c) && c >= 0.0f)) ok = false;
+            if (c > 0.0f) lit = true;
+        }
+        return ok && lit ? (double)e.x + (double)e.y + (double)e.z : -1.0;
+    };
+    std::vector<int32_t> index;
+    std::vector<double> weight;
+    for (int32_t i = 0; i < ns; ++i) {
+        const float r = spheres[(size_t)i].w;
+        const double e = emit_sum(smat[(size_t)i]);
+        if (!(r > 0.0f) || e < 0.0) continue;
+        index.push_back(i);
+        weight.push_back(e * ((double)r * (double)r));
+    }
+    const size_t n = index.size();
+    std::vector<float> cdf, pmf;
+    nee_cdf_of(weight, cdf, pmf);
+    // the second table: the first one's spheres, then the planes that qualify
+    std::vector<int32_t> code;
+    std::vector<float> area(n, 0.0f);
+    for (int32_t i : index) code.push_back(2 * i);
+    for (int32_t i = 0; i < npl; ++i) {
+        const float4 P1 = planes[(size_t)i * 5 + 1], U = planes[(size_t)i * 5 + 2], V = planes[(size_t)i * 5 + 3];
+        int32_t type, m;
+        std::memcpy(&type, &P1.w, 4);
+        std::memcpy(&m, &U.w, 4);
+        if (type != RT_PLANE_QUAD && type != RT_PLANE_ELLIPSE && type != RT_PLANE_TRIANGLE) continue;
+        const double e = emit_sum(m);
+        if (e < 0.0) continue;
+        const double ux = U.x, uy = U.y, uz = U.z, vx = V.x, vy = V.y, vz = V.z;
+        const double nx = uy * vz - uz * vy, ny = uz * vx - ux * vz, nz = ux * vy - uy * vx;
+        const double k = type == RT_PLANE_QUAD ? 1.0 : (type == RT_PLANE_ELLIPSE ? 3.14159265358979323846 / 4.0 : 0.5);
+        const float A = (float)(k * std::sqrt((nx * nx + ny * ny) + nz * nz));
+        if (!(std::isfinite(A) && A > 0.0f)) continue;
+        code.push_back(2 * i + 1);
+        area.push_back(A);
+        weight.push_back(e * (double)A / 3.14159265358979323846);
+    }
+    const int32_t emit_planes = (int32_t)(code.size() - n);
+    std::vector<float> ecdf, epmf;
+    nee_cdf_of(weight, ecdf, epmf);
     if (n > 0) {
         if (const rt_status st = upload(index, (void **)&sc->nee_index_dev)) return st;
         if (const rt_status st = upload(cdf, (void **)&sc->nee_cdf_dev)) return st;
         if (const rt_status st = upload(pmf, (void **)&sc->nee_pmf_dev)) return st;
     }
+    if (emit_planes > 0) {
+        if (const rt_status st = upload(code, (void **)&sc->emit_code_dev)) return st;
+        if (const rt_status st = upload(ecdf, (void **)&sc->emit_cdf_dev)) return st;
+        if (const rt_status st = upload(epmf, (void **)&sc->emit_pmf_dev)) return st;
+        if (const rt_status st = upload(area, (void **)&sc->emit_area_dev)) return st;
+    }
+    sc->emit_code = std::move(code);
+    sc->emit_cdf = std::move(ecdf);
+    sc->emit_pmf = std::move(epmf);
+    sc->emit_area = std::move(area);
+    sc->emit_spheres = (int32_t)n;
+    sc->emit_planes = emit_planes;
     sc->nee_index = std::move(index);
     sc->nee_cdf = std::move(cdf);
     sc->nee_pmf = std::move(pmf);
@@ -2249,20 +2316,44 @@ rtk::NeeTable nee_table_of(const rt_scene *sc, int32_t mis) {
     T.mis = mis;
     return T;
 }
+// does a call with these parameters run the two-kind kernels?  Only where the table holds a plane: without one both tables are the same
+// and the sphere-only kernels give sample_planes = 0 bit for bit (the tables must have been made: nee_table_ensure)
+// a trace kernel's table argument: either table type, at the same address
+union NeeEither {
+    rtk::NeeTable nee;
+    rtk::EmitTable emit;
+};
+bool emit_planes_on(const rt_scene *sc, const NeeSetup &N) { return N.planes != 0 && sc->emit_planes > 0; }
+rtk::EmitTable emit_table_of(const rt_scene *sc, int32_t mis) {
+    rtk::EmitTable T;
+    T.code = sc->emit_code_dev;
+    T.cdf = sc->emit_cdf_dev;
+    T.pmf = sc->emit_pmf_dev;
+    T.area = sc->emit_area_dev;
+    T.count = (int32_t)sc->emit_code.size();
+    T.spheres = sc->emit_spheres;
+    T.mis = mis;
+    return T;
+}
 
 }  // namespace
 
 rt_status rt_render_nee(rt_scene *sc, const rt_camera_data *cam, const rt_nee_params *params, const rt_shard *shard, int32_t sample_first,
                         float *d_fb_sum, void *hip_stream, int32_t sync, rt_timing *timing) {
-    int32_t mis = 1;
-    if (const rt_status st = nee_setup("rt_render_nee", params, mis)) return st;
+    NeeSetup N;
+    if (const rt_status st = nee_setup("rt_render_nee", params, N)) return st;
     if (!sc) return fail(RT_ERR_INVALID_ARG, "rt_render_nee: null scene");
-    auto make_table = [&](rtk::NeeTable &T) {
+    auto make_table = [&](NeeEither &T, const void *&kernel) {
         if (const rt_status st = nee_table_ensure(sc)) return st;
-        T = nee_table_of(sc, mis);
+        if (emit_planes_on(sc, N)) {
+            T.emit = emit_table_of(sc, N.mis);
+            kernel = (const void *)rtk::emit_render_kernel;
+        } else {
+            T.nee = nee_table_of(sc, N.mis);
+        }
         return RT_OK;
     };
-    return render_light_impl<rtk::NeeTable>("rt_render_nee", (const void *)rtk::nee_render_kernel, nullptr, make_table, sc, cam, shard, sample_first, d_fb_sum, hip_stream, sync, timing);
+    return render_light_impl<NeeEither>("rt_render_nee", (const void *)rtk::nee_render_kernel, nullptr, make_table, sc, cam, shard, sample_first, d_fb_sum, hip_stream, sync, timing);
 }
 
 rt_status rt_nee_light_table(rt_scene *sc, int32_t cap, int32_t *sphere_index, float *cdf, float *pmf, int32_t *count) {
@@ -2280,10 +2371,32 @@ rt_status rt_nee_light_table(rt_scene *sc, int32_t cap, int32_t *sphere_index, f
     return RT_OK;
 }
 
+rt_status rt_nee_emitter_table(rt_scene *sc, const rt_nee_params *params, int32_t cap, int32_t *kind, int32_t *index, float *cdf, float *pmf,
+                               float *area, int32_t *count) {
+    NeeSetup N;
+    if (const rt_status st = nee_setup("rt_nee_emitter_table", params, N)) return st;
+    if (!sc || !count || cap < 0 || (cap > 0 && (!kind || !index || !cdf || !pmf || !area)))
+        return fail(RT_ERR_INVALID_ARG, "rt_nee_emitter_table: null argument or negative cap");
+    if (const rt_status st = check_device(sc)) return st;
+    if (const rt_status st = nee_table_ensure(sc)) return st;
+    const bool planes = N.planes != 0;
+    const int32_t n = (int32_t)(planes ? sc->emit_code.size() : sc->nee_index.size());
+    *count = n;
+    const int32_t m = cap < n ? cap : n;
+    for (int32_t k = 0; k < m; ++k) {
+        kind[k] = planes ? (sc->emit_code[(size_t)k] & 1) : 0;
+        index[k] = planes ? (sc->emit_code[(size_t)k] >> 1) : sc->nee_index[(size_t)k];
+        cdf[k] = planes ? sc->emit_cdf[(size_t)k] : sc->nee_cdf[(size_t)k];
+        pmf[k] = planes ? sc->emit_pmf[(size_t)k] : sc->nee_pmf[(size_t)k];
+        area[k] = planes ? sc->emit_area[(size_t)k] : 0.0f;
+    }
+    return RT_OK;
+}
+
 rt_status rt_trace_samples_nee(rt_scene *sc, const rt_camera_data *cam, const rt_nee_params *params, int32_t n, const int32_t *ijs,
                                float *radiance, int32_t *rays, uint32_t *final_seed, uint32_t *final_nee_seed) {
-    int32_t mis = 1;
-    if (const rt_status st = nee_setup("rt_trace_samples_nee", params, mis)) return st;
+    NeeSetup N;
+    if (const rt_status st = nee_setup("rt_trace_samples_nee", params, N)) return st;
     if (n < 0 || (n > 0 && (!ijs || !radiance || !rays || !final_seed || !final_nee_seed))) return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_nee: null argument");
     rtk::KParams P;
     rt_status st = fill_params(sc, cam, nullptr, P);
@@ -2291,7 +2404,8 @@ rt_status rt_trace_samples_nee(rt_scene *sc, const rt_camera_data *cam, const rt
     if ((st = check_device(sc)) != RT_OK) return st;
     return run_probe("rt_trace_samples_nee: ", P, cam, n, ijs, radiance, rays, final_seed, final_nee_seed, nullptr, [&](const rtk::KParams &KP, uint32_t *d_nee, uint32_t *) {
         if (const rt_status ts = nee_table_ensure(sc)) return ts;
-        hipLaunchKernelGGL(rtk::nee_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, KP, nee_table_of(sc, mis), d_nee);
+        if (emit_planes_on(sc, N)) hipLaunchKernelGGL(rtk::emit_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, KP, emit_table_of(sc, N.mis), d_nee);
+        else hipLaunchKernelGGL(rtk::nee_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, KP, nee_table_of(sc, N.mis), d_nee);
         return RT_OK;
     });
 }
@@ -2525,7 +2639,7 @@ rt_status rt_render_env(rt_scene *sc, const rt_camera_data *cam, const rt_env *e
     if (const rt_status st = env_setup("rt_render_env", params, np)) return st;
     if (!env) return fail(RT_ERR_INVALID_ARG, "rt_render_env: null environment");
     if (!sc) return fail(RT_ERR_INVALID_ARG, "rt_render_env: null scene");
-    auto make_env = [&](rtk::EnvDev &E) {
+    auto make_env = [&](rtk::EnvDev &E, const void *&) {
         E = env_dev_of(env, np);
         return RT_OK;
     };
@@ -2563,7 +2677,7 @@ struct LitSetup {
     rtk::LensCam C;
     bool lens = false;            // the camera draws more than the pinhole's: the kLens kernels
     bool emitters = true;
-    int32_t mis = 1;
+    NeeSetup nee;
     const rt_env *env = nullptr;
     rt_env_params ep;
 };
@@ -2576,22 +2690,35 @@ rt_status lit_setup(const char *what, const rt_camera_data *cam_open, const rt_l
     S.lens = S.C.motion != 0 || S.C.radius > 0.0f;
     S.emitters = lp.sample_emitters != 0;
     if (S.emitters)
-        if (const rt_status st = nee_setup(what, lp.nee, S.mis)) return st;
+        if (const rt_status st = nee_setup(what, lp.nee, S.nee)) return st;
     S.env = lp.env;
     if (S.env)
         if (const rt_status st = env_setup(what, lp.env_params, S.ep)) return st;
     return RT_OK;
 }
-// the kernels' light: the handle's emitter table (emitters off: an empty one) and the environment (none: off)
-rt_status lit_light_of(rt_scene *sc, const LitSetup &S, rtk::LitLight &T) {
-    T = rtk::LitLight{};
+// the kernels' light: the handle's emitter table (emitters off: an empty one) and the environment (none: off).  planes: the table is the
+// two-kind one, in T.emit, for the lit_emit kernels; else T.lit
+union LitEither {
+    rtk::LitLight lit;
+    rtk::LitEmitLight emit;
+};
+rt_status lit_light_of(rt_scene *sc, const LitSetup &S, LitEither &T, bool &planes) {
+    planes = false;
     if (S.emitters) {
         if (const rt_status st = nee_table_ensure(sc)) return st;
-        T.N = nee_table_of(sc, S.mis);
+        planes = emit_planes_on(sc, S.nee);
+    }
+    if (planes) {
+        T.emit = rtk::LitEmitLight{};
+        T.emit.N = emit_table_of(sc, S.nee.mis);
+    } else {
+        T.lit = rtk::LitLight{};
+        if (S.emitters) T.lit.N = nee_table_of(sc, S.nee.mis);
     }
     if (S.env) {
-        T.E = env_dev_of(S.env, S.ep);
-        T.env_on = 1;
+        // (E and env_on follow the table, whose size differs between the two)
+        if (planes) { T.emit.E = env_dev_of(S.env, S.ep); T.emit.env_on = 1; }
+        else { T.lit.E = env_dev_of(S.env, S.ep); T.lit.env_on = 1; }
     }
     return RT_OK;
 }
@@ -2603,8 +2730,14 @@ rt_status rt_render_lit(rt_scene *sc, const rt_camera_data *cam_open, const rt_l
     if (const rt_status st = lit_setup("rt_render_lit", cam_open, lit, S)) return st;
     if (!sc) return fail(RT_ERR_INVALID_ARG, "rt_render_lit: null scene");
     const void *kernel = S.lens ? (const void *)rtk::lit_render_kernel<true> : (const void *)rtk::lit_render_kernel<false>;
-    return render_light_impl<rtk::LitLight>("rt_render_lit", kernel, S.env ? &S.env->device : nullptr, [&](rtk::LitLight &T) { return lit_light_of(sc, S, T); },
-                                            sc, cam_open, shard, sample_first, d_fb_sum, hip_stream, sync, timing, &S.C);
+    auto make_light = [&](LitEither &T, const void *&k) {
+        bool planes;
+        if (const rt_status st = lit_light_of(sc, S, T, planes)) return st;
+        if (planes) k = S.lens ? (const void *)rtk::lit_emit_render_kernel<true> : (const void *)rtk::lit_emit_render_kernel<false>;
+        return RT_OK;
+    };
+    return render_light_impl<LitEither>("rt_render_lit", kernel, S.env ? &S.env->device : nullptr, make_light, sc, cam_open, shard, sample_first, d_fb_sum,
+                                        hip_stream, sync, timing, &S.C);
 }
 
 rt_status rt_trace_samples_lit(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, int32_t n, const int32_t *ijs, float *radiance,
@@ -2620,10 +2753,14 @@ rt_status rt_trace_samples_lit(rt_scene *sc, const rt_camera_data *cam_open, con
     if (S.env && S.env->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_lit: the environment was created on another device than the scene");
     return run_probe("rt_trace_samples_lit: ", P, cam_open, n, ijs, radiance, rays, final_seed, final_nee_seed, final_env_seed,
                      [&](const rtk::KParams &KP, uint32_t *d_nee, uint32_t *d_env) {
-        rtk::LitLight T;
-        if (const rt_status ts = lit_light_of(sc, S, T)) return ts;
-        if (S.lens) hipLaunchKernelGGL(rtk::lit_probe_kernel<true>, dim3((n + 255) / 256), dim3(256), 0, 0, KP, T, S.C, d_nee, d_env);
-        else hipLaunchKernelGGL(rtk::lit_probe_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, 0, KP, T, S.C, d_nee, d_env);
+        LitEither T;
+        bool planes;
+        if (const rt_status ts = lit_light_of(sc, S, T, planes)) return ts;
+        const dim3 grid((n + 255) / 256), block(256);
+        if (planes && S.lens) hipLaunchKernelGGL(rtk::lit_emit_probe_kernel<true>, grid, block, 0, 0, KP, T.emit, S.C, d_nee, d_env);
+        else if (planes) hipLaunchKernelGGL(rtk::lit_emit_probe_kernel<false>, grid, block, 0, 0, KP, T.emit, S.C, d_nee, d_env);
+        else if (S.lens) hipLaunchKernelGGL(rtk::lit_probe_kernel<true>, grid, block, 0, 0, KP, T.lit, S.C, d_nee, d_env);
+        else hipLaunchKernelGGL(rtk::lit_probe_kernel<false>, grid, block, 0, 0, KP, T.lit, S.C, d_nee, d_env);
         return RT_OK;
     });
 }

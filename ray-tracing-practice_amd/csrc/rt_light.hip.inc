@@ -1,5 +1,5 @@
 // rt_light.hip.inc — the path that takes light samples, written once for both kinds of light: the emissive spheres of rt_render_nee
-// (NeeTable, rt_nee.hip.inc; DESIGN.md §13) and the environment of rt_render_env (EnvDev, rt_env.hip.inc; §14) — and, at the end, for
+// (NeeTable, rt_nee.hip.inc; DESIGN.md §13; with emissive planes: EmitTable, §17) and the environment of rt_render_env (EnvDev, rt_env.hip.inc; §14) — and, at the end, for
 // both at once from the lens camera (rt_render_lit, LitLight; §16).  Included by rt_capi.hip after both.  A light is its table type; what the two do differently is the overloads below, everything else — the lit vertex, the
 // walk step, the probe and the trace kernel — is one text.
 #pragma once
@@ -13,9 +13,11 @@ constexpr int kLightShadeLanes = 32;                         // a wave shades on
 // ---- what a light is ---------------------------------------------------------------------------------------------------------------
 // the key of its RNG stream: light = wang_hash(sample_seed ^ key)
 __device__ __forceinline__ uint32_t light_key(const NeeTable &) { return kNeeStreamKey; }
+__device__ __forceinline__ uint32_t light_key(const EmitTable &) { return kNeeStreamKey; }
 __device__ __forceinline__ uint32_t light_key(const EnvDev &) { return kEnvStreamKey; }
 // are light samples drawn at all?
 __device__ __forceinline__ bool light_on(const NeeTable &T) { return T.count > 0; }
+__device__ __forceinline__ bool light_on(const EmitTable &T) { return T.count > 0; }
 __device__ __forceinline__ bool light_on(const EnvDev &E) { return E.sampled != 0; }
 // Is its shadow ray an occlusion query?  The environment's is: it contributes when it hits nothing, an answer that does not depend on
 // the visit order, and up to the first accepted hit the walk is the closest-hit search's own (closest is still 1e30) — so the walk ends
@@ -25,6 +27,7 @@ template <> constexpr bool kLightOcclusion<EnvDev> = true;
 
 // miss: what the lane's ray adds when it hits nothing
 __device__ __forceinline__ f3 light_miss(const KParams &P, const NeeTable &, const Lane &L, bool) { return mul(L.beta, mk(P.bg[0], P.bg[1], P.bg[2])); }
+__device__ __forceinline__ f3 light_miss(const KParams &P, const EmitTable &, const Lane &L, bool) { return mul(L.beta, mk(P.bg[0], P.bg[1], P.bg[2])); }
 __device__ __forceinline__ f3 light_miss(const KParams &P, const EnvDev &E, const Lane &L, bool prev_diffuse) {
     if (L.depth == 0 && !E.camera_visible) return mul(L.beta, mk(P.bg[0], P.bg[1], P.bg[2]));
     return env_miss(E, L.d, L.beta, prev_diffuse);
@@ -44,17 +47,41 @@ __device__ __forceinline__ f3 light_emitted(const KParams &P, const NeeTable &T,
     }
     return emitted;
 }
+// (the two-kind table: a table sphere as above, a table plane by step 3p from the ray's origin to the vertex's point)
+__device__ __forceinline__ f3 light_emitted(const KParams &P, const EmitTable &T, const Lane &L, int32_t idx, bool is_plane, bool prev_diffuse, f3 emitted) {
+    if (prev_diffuse) {
+        const int32_t e = emit_find(T, L.hit);
+        if (e >= 0) {
+            f3 w;
+            float pl = 0.0f;
+            if (is_plane) {
+                float pa;
+                if (emit_plane_pa(P, idx, T.area[e], L.o, add(L.o, scale(L.closest, L.d)), w, pa)) pl = T.pmf[e] * pa;
+            } else {
+                float d2, om;
+                if (nee_cone(L.o, P.spheres[idx], w, d2, om)) pl = T.pmf[e] * nee_pdf_cone(om);
+            }
+            const float wb = T.mis ? (kNeePb * kNeePb) / (kNeePb * kNeePb + pl * pl) : (pl > 0.0f ? 0.0f : 1.0f);
+            emitted = scale(wb, emitted);
+        }
+    }
+    return emitted;
+}
 __device__ __forceinline__ f3 light_emitted(const KParams &, const EnvDev &, const Lane &, int32_t, bool, bool, f3 emitted) { return emitted; }
 // sample: the light sample of a diffuse vertex at x (face-forwarded normal n, albedo a, throughput beta before the attenuation).  false:
 // none; else the shadow ray's direction, what it adds when it reaches the light, and (emitters) the code of the sphere to reach
 __device__ __forceinline__ bool light_sample(const KParams &P, const NeeTable &T, uint32_t &ls, f3 x, f3 n, f3 a, f3 beta, f3 &dir, f3 &c, int32_t &code) {
     return nee_sample(P, T, ls, x, n, a, beta, dir, c, code);
 }
+__device__ __forceinline__ bool light_sample(const KParams &P, const EmitTable &T, uint32_t &ls, f3 x, f3 n, f3 a, f3 beta, f3 &dir, f3 &c, int32_t &code) {
+    return emit_sample(P, T, ls, x, n, a, beta, dir, c, code);
+}
 __device__ __forceinline__ bool light_sample(const KParams &, const EnvDev &E, uint32_t &ls, f3, f3 n, f3 a, f3 beta, f3 &dir, f3 &c, int32_t &) {
     return env_sample(E, ls, n, a, beta, dir, c);
 }
 // reached: the verdict of a finished shadow walk
 __device__ __forceinline__ bool light_reached(const NeeTable &, const Lane &L, int32_t code) { return L.hit == code; }
+__device__ __forceinline__ bool light_reached(const EmitTable &, const Lane &L, int32_t code) { return L.hit == code; }
 __device__ __forceinline__ bool light_reached(const EnvDev &, const Lane &L, int32_t) { return L.hit < 0; }
 
 // the light samples' RNG state of a sample (the path's own is start_sample's)
@@ -353,13 +380,22 @@ __global__ void __launch_bounds__(256) nee_probe_kernel(const KParams P, const N
 __global__ void __launch_bounds__(256) env_probe_kernel(const KParams P, const EnvDev E, uint32_t *env_seed_out) { light_probe_body(P, E, env_seed_out); }
 __global__ void __launch_bounds__(kLightBlock) nee_render_kernel(const KParams P, const NeeTable T) { light_render_body(P, T); }
 __global__ void __launch_bounds__(kLightBlock) env_render_kernel(const KParams P, const EnvDev E) { light_render_body(P, E); }
+// (sample_planes = 1 on a handle whose table holds a plane: DESIGN.md §17)
+__global__ void __launch_bounds__(256) emit_probe_kernel(const KParams P, const EmitTable T, uint32_t *nee_seed_out) { light_probe_body(P, T, nee_seed_out); }
+__global__ void __launch_bounds__(kLightBlock) emit_render_kernel(const KParams P, const EmitTable T) { light_render_body(P, T); }
 
 // ---- rt_render_lit: the emitter table and an environment at once, from the lens camera (DESIGN.md §16) -------------------------------
 // The third light: both tables, either of which may be off (an emitter table with count 0 — sample_emitters = 0 or no emitter; env_on = 0
 // — no environment: a miss adds the background).  Spheres are hits and the map is misses, so the two never weight the same radiance:
 // miss and emitted are the single lights' own, and a vertex takes one sample of each light that is on, from that light's own stream.
+// The emitter table is NeeTable (LitLight) or, with sample_planes = 1 on a handle whose table holds a plane, EmitTable (LitEmitLight).
 struct LitLight {
     NeeTable N;
+    EnvDev E;
+    int32_t env_on;
+};
+struct LitEmitLight {
+    EmitTable N;
     EnvDev E;
     int32_t env_on;
 };
@@ -371,15 +407,24 @@ __device__ __forceinline__ f3 light_emitted(const KParams &P, const LitLight &T,
     return light_emitted(P, T.N, L, idx, is_plane, prev_diffuse, emitted);
 }
 __device__ __forceinline__ bool env_sampled(const LitLight &T) { return T.env_on && light_on(T.E); }
+__device__ __forceinline__ f3 light_miss(const KParams &P, const LitEmitLight &T, const Lane &L, bool prev_diffuse) {
+    if (T.env_on) return light_miss(P, T.E, L, prev_diffuse);
+    return light_miss(P, T.N, L, prev_diffuse);
+}
+__device__ __forceinline__ f3 light_emitted(const KParams &P, const LitEmitLight &T, const Lane &L, int32_t idx, bool is_plane, bool prev_diffuse, f3 emitted) {
+    return light_emitted(P, T.N, L, idx, is_plane, prev_diffuse, emitted);
+}
+__device__ __forceinline__ bool env_sampled(const LitEmitLight &T) { return T.env_on && light_on(T.E); }
 
-// The two light samples of a lit vertex: the emitter's (a: the shadow ray has to reach sphere `code`) and the environment's (b: it has
+// The two light samples of a lit vertex: the emitter's (a: the shadow ray has to reach the primitive `code`) and the environment's (b: it has
 // to reach nothing).  Both are drawn at shade time — the streams are independent, and the order of the adds is the caller's.
 struct LitSamples {
     f3 adir, ac, bdir, bc;
     int32_t code;
     bool a, b;
 };
-__device__ __forceinline__ bool shade_lit2(Lane &L, const KParams &P, const LitLight &T, bool prev_diffuse, uint32_t &nee, uint32_t &env, f3 &out_o,
+template <class Lit>
+__device__ __forceinline__ bool shade_lit2(Lane &L, const KParams &P, const Lit &T, bool prev_diffuse, uint32_t &nee, uint32_t &env, f3 &out_o,
                                            f3 &out_d, LitSamples &S, bool &diffuse_out) {
     S.a = false;
     S.b = false;
@@ -407,8 +452,8 @@ __device__ __forceinline__ void lit_step(Lane &L, const KParams &P, bool occlusi
 }
 
 // ---- probe (rt_trace_samples_lit) ----------------------------------------------------------------------------------------------------
-template <bool kLens>
-__device__ __forceinline__ void lit_probe_body(const KParams &P, const LitLight &T, const LensCam &C, uint32_t *nee_seed_out, uint32_t *env_seed_out) {
+template <bool kLens, class Lit>
+__device__ __forceinline__ void lit_probe_body(const KParams &P, const Lit &T, const LensCam &C, uint32_t *nee_seed_out, uint32_t *env_seed_out) {
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= P.probe_n) return;
     const int32_t i = P.probe_ijs[3 * g], j = P.probe_ijs[3 * g + 1], s = P.probe_ijs[3 * g + 2];
@@ -458,8 +503,8 @@ __device__ __forceinline__ void lit_probe_body(const KParams &P, const LitLight 
 // environment sample still waits.  Across the emitter's walk a lane holds the next direction, both pending contributions, the
 // environment's direction and the target (thirteen registers); across the environment's, the next direction and its contribution.
 constexpr int32_t kLitShadowA = 2, kLitShadowAB = 3, kLitShadowB = 4;
-template <bool kLens>
-__device__ __forceinline__ void lit_render_body(const KParams &P, const LitLight &T, const LensCam &C) {
+template <bool kLens, class Lit>
+__device__ __forceinline__ void lit_render_body(const KParams &P, const Lit &T, const LensCam &C) {
     const int lane = (int)(threadIdx.x & (kWave - 1));
     Lane L;
     L.node = kBlocked;
@@ -575,5 +620,12 @@ __global__ void __launch_bounds__(256) lit_probe_kernel(const KParams P, const L
 }
 template <bool kLens>
 __global__ void __launch_bounds__(kLightBlock, 4) lit_render_kernel(const KParams P, const LitLight T, const LensCam C) { lit_render_body<kLens>(P, T, C); }
+// (sample_planes = 1 on a handle whose table holds a plane)
+template <bool kLens>
+__global__ void __launch_bounds__(256) lit_emit_probe_kernel(const KParams P, const LitEmitLight T, const LensCam C, uint32_t *nee_seed_out, uint32_t *env_seed_out) {
+    lit_probe_body<kLens>(P, T, C, nee_seed_out, env_seed_out);
+}
+template <bool kLens>
+__global__ void __launch_bounds__(kLightBlock, 4) lit_emit_render_kernel(const KParams P, const LitEmitLight T, const LensCam C) { lit_render_body<kLens>(P, T, C); }
 
 }  // namespace rtk

@@ -15,7 +15,7 @@ constexpr uint32_t kNeeStreamKey = RT_NEE_STREAM_KEY;       // nee = wang_hash(s
 constexpr float kNeeTwoPi = RT_NEE_TWO_PI;
 constexpr float kNeePb = RT_NEE_PB;                          // density of the uniform-hemisphere direction, 1 / (2 pi)
 
-// The emitter table of a handle (global memory, sphere order): sphere index, cdf (last entry 1), pmf
+// The sphere-only emitter table of a handle (global memory, sphere order): sphere index, cdf (last entry 1), pmf
 struct NeeTable {
     const int32_t *index;
     const float *cdf;
@@ -24,8 +24,22 @@ struct NeeTable {
     int32_t mis;          // 1: power heuristic, 0: light sampling alone
 };
 
+// The emitter table of sample_planes = 1 (DESIGN.md §17), used when it holds a plane: the table's spheres first (sphere order), then
+// its planes (plane order).  code = 2 * index + kind (0 sphere, 1 plane) — what a hit on that primitive is (Lane::hit), increasing
+// within each of the two ranges; area: A of a plane, 0 for a sphere
+struct EmitTable {
+    const int32_t *code;
+    const float *cdf;
+    const float *pmf;
+    const float *area;
+    int32_t count;
+    int32_t spheres;      // entries [0, spheres) are spheres, [spheres, count) planes
+    int32_t mis;
+};
+
 // smallest e with u < cdf[e]; count when there is none (u == 1.0f)
-__device__ __forceinline__ int32_t nee_pick(const NeeTable &T, float u) {
+template <class Table>
+__device__ __forceinline__ int32_t nee_pick(const Table &T, float u) {
     int32_t lo = 0, hi = T.count;
     while (lo < hi) {
         const int32_t mid = (lo + hi) >> 1;
@@ -44,6 +58,18 @@ __device__ __forceinline__ int32_t nee_find(const NeeTable &T, int32_t sphere) {
     }
     return (lo < T.count && T.index[lo] == sphere) ? lo : -1;
 }
+// the table entry of a hit (code), -1 when that primitive is not in the table: a bisection of the range of its kind
+__device__ __forceinline__ int32_t emit_find(const EmitTable &T, int32_t code) {
+    const bool plane = (code & 1) != 0;
+    int32_t lo = plane ? T.spheres : 0, hi = plane ? T.count : T.spheres;
+    const int32_t end = hi;
+    while (lo < hi) {
+        const int32_t mid = (lo + hi) >> 1;
+        if (T.code[mid] < code) lo = mid + 1;
+        else hi = mid;
+    }
+    return (lo < end && T.code[lo] == code) ? lo : -1;
+}
 // step 2 of the header: the cone of sphere s seen from x.  false: no contribution (x inside or on the sphere, or a cone too narrow
 // for float); else w = c - x, d2 = dot(w, w), om = 1 - cos_max
 __device__ __forceinline__ bool nee_cone(f3 x, float4 s, f3 &w, float &d2, float &om) {
@@ -59,11 +85,9 @@ __device__ __forceinline__ float nee_pdf_cone(float om) { return 1.0f / (kNeeTwo
 
 // The light sample of a diffuse vertex at x (face-forwarded normal n, albedo a, throughput beta before the attenuation): false = no
 // contribution; else the shadow ray's direction (from x), the code of the sphere it has to reach and what it adds then
-__device__ __forceinline__ bool nee_sample(const KParams &P, const NeeTable &T, uint32_t &nee, f3 x, f3 n, f3 a, f3 beta, f3 &dir, f3 &c, int32_t &code) {
-    const float u = random_float(nee);
-    const int32_t e = nee_pick(T, u);
-    if (e >= T.count) return false;
-    const int32_t sphere = T.index[e];
+// steps 2 to 4 for a picked sphere (pmf: where its entry's stands — read only by a sample that counts)
+__device__ __forceinline__ bool nee_sample_sphere(const KParams &P, int32_t sphere, const float *pmf, int32_t mis, uint32_t &nee, f3 x, f3 n, f3 a, f3 beta, f3 &dir,
+                                                  f3 &c, int32_t &code) {
     f3 w;
     float d2, om;
     if (!nee_cone(x, P.spheres[sphere], w, d2, om)) return false;
@@ -89,12 +113,82 @@ __device__ __forceinline__ bool nee_sample(const KParams &P, const NeeTable &T, 
     const float sx = sin_t * cx, sy = sin_t * cy;
     dir = mk((t1.x * sx + t2.x * sy) + wn.x * cos_t, (t1.y * sx + t2.y * sy) + wn.y * cos_t, (t1.z * sx + t2.z * sy) + wn.z * cos_t);
     if (!(dot(dir, n) > 0.0f)) return false;
-    const float pl = T.pmf[e] * nee_pdf_cone(om);
-    const float f = T.mis ? (kNeePb * pl) / (pl * pl + kNeePb * kNeePb) : kNeePb / pl;
+    const float pl = *pmf * nee_pdf_cone(om);
+    const float f = mis ? (kNeePb * pl) / (pl * pl + kNeePb * kNeePb) : kNeePb / pl;
     const float4 ME = P.materials[3 * P.sphere_mat[sphere] + 1];
     c = scale(f, mul(mul(beta, a), mk(ME.x, ME.y, ME.z)));
     code = 2 * sphere;
     return true;
+}
+__device__ __forceinline__ bool nee_sample(const KParams &P, const NeeTable &T, uint32_t &nee, f3 x, f3 n, f3 a, f3 beta, f3 &dir, f3 &c, int32_t &code) {
+    const float u = random_float(nee);
+    const int32_t e = nee_pick(T, u);
+    if (e >= T.count) return false;
+    return nee_sample_sphere(P, T.index[e], T.pmf + e, T.mis, nee, x, n, a, beta, dir, c, code);
+}
+
+// ---- emissive planes (sample_planes = 1) ----------------------------------------------------------------------------------------------
+// step 3p of the header: the point y of plane `plane` (area A) seen from x.  false: no contribution; else wl = (y - x) / |y - x| and
+// pa, the density of y in solid angle at x
+__device__ __forceinline__ bool emit_plane_pa(const KParams &P, int32_t plane, float A, f3 x, f3 y, f3 &wl, float &pa) {
+    const f3 w = sub(y, x);
+    const float d2 = dot(w, w);
+    if (!(d2 > 0.0f)) return false;
+    const float len = sqrt_cr(d2);
+    wl = mk(w.x / len, w.y / len, w.z / len);
+    const float4 P0 = P.planes[5 * plane + 0];
+    const float cos_l = fabsf(dot(mk(P0.x, P0.y, P0.z), wl));
+    if (!(cos_l >= 1e-8f)) return false;
+    pa = d2 / (cos_l * A);
+    return true;
+}
+// steps 2p to 4p for the picked entry e, a plane: a point uniform in area (QUAD: the parallelogram; TRIANGLE: its lower half, by the
+// fold; ELLIPSE: the inscribed ellipse, by the disc's rejection loop), two-sided
+__device__ __forceinline__ bool emit_sample_plane(const KParams &P, const EmitTable &T, int32_t e, uint32_t &nee, f3 x, f3 n, f3 a, f3 beta, f3 &dir, f3 &c,
+                                                  int32_t &code) {
+    const int32_t hit = T.code[e];
+    const int32_t plane = hit >> 1;
+    const float4 P1 = P.planes[5 * plane + 1];
+    const float4 P2 = P.planes[5 * plane + 2];
+    const float4 P3 = P.planes[5 * plane + 3];
+    const float4 P4 = P.planes[5 * plane + 4];
+    const int32_t type = as_int(P1.w);
+    float ua, ub;
+    if (type == RT_PLANE_ELLIPSE) {
+        float px, py, q2;
+        do {
+            px = random_pm1(nee);
+            py = random_pm1(nee);
+            q2 = px * px + py * py;
+        } while (q2 >= 1.0f);
+        ua = 0.5f + 0.5f * px;
+        ub = 0.5f + 0.5f * py;
+    } else {
+        ua = random_float(nee);
+        ub = random_float(nee);
+        if (type == RT_PLANE_TRIANGLE && ua + ub > 1.0f) {
+            ua = 1.0f - ua;
+            ub = 1.0f - ub;
+        }
+    }
+    const f3 y = mk((P4.x + ua * P2.x) + ub * P3.x, (P4.y + ua * P2.y) + ub * P3.y, (P4.z + ua * P2.z) + ub * P3.z);
+    float pa;
+    if (!emit_plane_pa(P, plane, T.area[e], x, y, dir, pa)) return false;
+    if (!(dot(dir, n) > 0.0f)) return false;
+    const float pl = T.pmf[e] * pa;
+    const float f = T.mis ? (kNeePb * pl) / (pl * pl + kNeePb * kNeePb) : kNeePb / pl;
+    const float4 ME = P.materials[3 * as_int(P2.w) + 1];
+    c = scale(f, mul(mul(beta, a), mk(ME.x, ME.y, ME.z)));
+    code = hit;
+    return true;
+}
+// the light sample of the two-kind table: step 1, then the steps of the entry's kind
+__device__ __forceinline__ bool emit_sample(const KParams &P, const EmitTable &T, uint32_t &nee, f3 x, f3 n, f3 a, f3 beta, f3 &dir, f3 &c, int32_t &code) {
+    const float u = random_float(nee);
+    const int32_t e = nee_pick(T, u);
+    if (e >= T.count) return false;
+    if (e < T.spheres) return nee_sample_sphere(P, T.code[e] >> 1, T.pmf + e, T.mis, nee, x, n, a, beta, dir, c, code);
+    return emit_sample_plane(P, T, e, nee, x, n, a, beta, dir, c, code);
 }
 
 }  // namespace rtk

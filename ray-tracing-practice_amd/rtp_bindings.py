@@ -163,7 +163,16 @@ def lens_camera_rays(cam_open, cam_close, lens, ijs):
 class NeeParams(C.Structure):
     """rt_nee_params (include/rtp_amd.h): an IN structure of the caller's size — struct_bytes is set on construction; the other
     fields are 0 until rt_nee_params_init (nee_params()) fills the defaults."""
-    _fields_ = [("struct_bytes", C.c_uint32), ("mis", C.c_int32), ("reserved", C.c_int32 * 2)]
+    class _Tail(C.Union):
+        """The struct's last 8 bytes: sample_planes and one reserved word — and, over the same bytes, the two-word `reserved` view of
+        the struct before sample_planes was taken from it."""
+        class _Words(C.Structure):
+            _fields_ = [("sample_planes", C.c_int32), ("_reserved1", C.c_int32)]
+        _anonymous_ = ("_words",)
+        _fields_ = [("_words", _Words), ("reserved", C.c_int32 * 2)]
+    _anonymous_ = ("_tail",)
+    _fields_ = [("struct_bytes", C.c_uint32), ("mis", C.c_int32), ("_tail", _Tail)]
+    FIELDS = ("struct_bytes", "mis", "sample_planes")          # what nee_params() sets
 
     def __init__(self, *args, **kw):
         super().__init__(*args, **kw)
@@ -171,11 +180,11 @@ class NeeParams(C.Structure):
 
 
 def nee_params(**params):
-    """rt_nee_params with the library's defaults (mis = 1), then the given fields."""
+    """rt_nee_params with the library's defaults (mis = 1, sample_planes = 0), then the given fields."""
     p = NeeParams()
     amd_lib().rt_nee_params_init(C.byref(p))
     for k, v in params.items():
-        if k not in dict(NeeParams._fields_) or k == "reserved":
+        if k not in NeeParams.FIELDS:
             raise RtError(f"rt_nee_params has no field {k}")
         setattr(p, k, v)
     return p
@@ -378,7 +387,7 @@ RTP_AMD_SYMBOLS = [
     "rt_render_samples", "rt_render_aov_samples", "rt_denoise_history_bytes", "rt_denoise_temporal",
     "rt_adaptive_params_init", "rt_render_adaptive", "rt_tonemap_spp",
     "rt_lens_params_init", "rt_render_lens", "rt_render_aov_lens", "rt_lens_camera_rays",
-    "rt_nee_params_init", "rt_render_nee", "rt_nee_light_table", "rt_trace_samples_nee",
+    "rt_nee_params_init", "rt_render_nee", "rt_nee_light_table", "rt_trace_samples_nee", "rt_nee_emitter_table",
     "rt_env_params_init", "rt_env_create", "rt_env_destroy", "rt_env_table", "rt_env_lookup", "rt_env_from_equirect", "rt_render_env",
     "rt_trace_samples_env",
     "rt_lit_params_init", "rt_render_lit", "rt_trace_samples_lit",
@@ -491,6 +500,9 @@ def amd_lib():
             lib.rt_render_nee.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(NeeParams), C.POINTER(Shard), C.c_int32, C.c_void_p,
                                           C.c_void_p, C.c_int32, C.POINTER(Timing)]
             lib.rt_nee_light_table.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
+            if hasattr(lib, "rt_nee_emitter_table"):
+                lib.rt_nee_emitter_table.argtypes = [C.c_void_p, C.POINTER(NeeParams), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                     C.c_void_p, C.POINTER(C.c_int32)]
             lib.rt_trace_samples_nee.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(NeeParams), C.c_int32, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.c_void_p]
         if hasattr(lib, "rt_render_env"):
@@ -1127,6 +1139,20 @@ class DeviceScene:
             _check(lib.rt_nee_light_table(self._h, n.value, idx.ctypes.data, cdf.ctypes.data, pmf.ctypes.data, C.byref(n)),
                    "rt_nee_light_table")
         return idx, cdf, pmf
+
+    def nee_emitter_table(self, params=None):
+        """rt_nee_emitter_table: (kind int32 — 0 sphere, 1 plane —, index int32, cdf float32, pmf float32, area float32) of the emitter
+        table that params (None, a NeeParams or a dict) select."""
+        lib = amd_lib()
+        n = C.c_int32()
+        p = _nee_struct(params)
+        _check(lib.rt_nee_emitter_table(self._h, p, 0, None, None, None, None, None, C.byref(n)), "rt_nee_emitter_table")
+        kind, idx = np.zeros(n.value, dtype=np.int32), np.zeros(n.value, dtype=np.int32)
+        cdf, pmf, area = (np.zeros(n.value, dtype=np.float32) for _ in range(3))
+        if n.value:
+            _check(lib.rt_nee_emitter_table(self._h, p, n.value, kind.ctypes.data, idx.ctypes.data, cdf.ctypes.data, pmf.ctypes.data,
+                                            area.ctypes.data, C.byref(n)), "rt_nee_emitter_table")
+        return kind, idx, cdf, pmf, area
 
     def trace_samples_nee(self, cam, ijs, params=None):
         """rt_trace_samples_nee: ijs (n, 3) → (radiance (n, 3), rays (n,), final seeds (n,), final light-sample seeds (n,))."""
