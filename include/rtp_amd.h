@@ -630,8 +630,34 @@ rt_status rt_lens_camera_rays(const rt_camera_data *cam_open, const rt_camera_da
  *         contribution are step 4's with this pl and the plane's material's emit.  Emission is two-sided: no facing test on the light.
  *     BSDF hits: the hit of the query k + 1 ray that leaves a diffuse event at x, on a plane e of the table at the point p, is weighted
  *     by w_b with pl from step 3p for w = p - x (0 where 3p gives none).  Planes outside the table keep weight 1.
+ *   select = 1 (read only when struct_bytes >= 16, an older caller gets 0): the entry of a light sample is picked by a light
+ *     tree — a bounding-sphere hierarchy over the entries of the table that sample_planes selects, descended by an importance that knows
+ *     the shaded point (Conty Estevez and Kulla 2018).  select = 0 runs the kernels of the power table, bit for bit.  A handle keeps a tree
+ *     per table, built on the first call that selects it, from the read-back the tables are made from.  An empty table samples nothing
+ *     under either setting.
+ *     Tree: built on the host in double from the float scene data, over the table's N entries in table order.  Entry e has a centre c_e,
+ *       a radius rho_e and its table weight w_e (above, in double).  Sphere: its centre and r.  QUAD and ELLIPSE: c_k = (base_k + 0.5 * u_k)
+ *       + 0.5 * v_k, rho = 0.5 * max(|u + v|, |u - v|).  TRIANGLE: c_k = base_k + (u_k + v_k) / 3, rho = the largest of |base - c|,
+ *       |(base + u) - c|, |(base + v) - c|.  |a| = sqrt((a0*a0 + a1*a1) + a2*a2).
+ *       The node over a list S of entries: m_k = 0.5 * (min_e(c_e,k - rho_e) + max_e(c_e,k + rho_e)), R = max_e(|c_e - m| + rho_e); stored
+ *       as float: centre (float)m_k, radius nextafterf((float)R, +inf), weight W = (float)(sum over S of w_e / sum over all entries of w_e),
+ *       both sums in list order.  |S| = 1: a leaf naming its entry.  Otherwise the split axis is the one on which the centres c_e extend
+ *       furthest (max - min; ties: x, then y, then z); S is sorted by that coordinate with a stable sort (equal coordinates keep list
+ *       order); the left child is the node over the first ceil(|S| / 2), the right child the node over the rest, and the node stores the
+ *       fallback q = (float)(W_left / (W_left + W_right)) of the children's double sums.  Nodes are numbered in preorder (a node, its left
+ *       subtree, its right subtree).  Entry e has a path of depth_e <= ceil(log2 N) steps: bit i set when step i goes right, LSB first.
+ *     Pick (in place of step 1; the steps 2 to 4 and 2p to 4p follow from the same state): p = 1.0f at the root.  At an interior node, for
+ *       each child c (centre m, radius R, weight W as stored): w = m - x; d2 = dot(w, w); I_c = W / fmaxf(d2, R * R).  s = I_L + I_R;
+ *       pL = (s > 0 && s < INFINITY) ? I_L / s : q.  u = random_float(nee), one fresh draw per level: u < pL goes left with p = p * pL,
+ *       otherwise right with p = p * (1.0f - pL).  At the leaf e is its entry and pmf_e(x) = p takes the place of the table's pmf_e in pl;
+ *       f and the contribution are unchanged.  A tree of one entry draws nothing and has pmf = 1: select = 1 is not select = 0 bit for bit
+ *       even there (the table's pick draws u).  The importance knows distance and extent only: no normal or orientation term.
+ *     BSDF hits: the table entry of the hit is found as above; pmf_e(x) is the same product, computed root-down along the entry's stored
+ *       path from the ray's origin x, with the same expressions in the same order, and w_b is as written (pl = 0 gives weight 1: an entry
+ *       the pick cannot reach from x).
  * Checks and limits: rt_render_samples's (rows of a shard only: no tiles, no rt_context); every refusal comes before anything is
- * enqueued; RT_ERR_INVALID_ARG for params with struct_bytes below 8, mis outside {0, 1} or sample_planes outside {0, 1}.  The light samples run on the
+ * enqueued; RT_ERR_INVALID_ARG for params with struct_bytes below 8, mis outside {0, 1}, sample_planes outside {0, 1} or select outside
+ * {0, 1} (checked in that order).  The light samples run on the
  * reference-order walk only.  Handle state: the call leaves the handle's own decisions alone, as rt_render_lens does — its walk choice,
  * a pause of the guarded walk, the re-pack of its tree, its cached view lists and what rt_last_timing reports; timing (may be NULL)
  * is this call's record (kernel_ms with sync != 0). */
@@ -642,7 +668,7 @@ typedef struct rt_nee_params {   /* IN, grows like rt_lens_params: the library r
     uint32_t struct_bytes;       /* sizeof(rt_nee_params) as the caller compiled it */
     int32_t  mis;                /* 1 (default): power heuristic; 0: light sampling alone (the BSDF hit of a table sphere counts 0) */
     int32_t  sample_planes;      /* 0 (default): spheres only; 1: emissive QUAD / ELLIPSE / TRIANGLE planes are sampled too (struct_bytes >= 12) */
-    int32_t  reserved[1];        /* 0: room to grow */
+    int32_t  select;             /* 0 (default): the entry by the power table's cdf; 1: by the light tree (struct_bytes >= 16) */
 } rt_nee_params;
 /* Defaults into *p, struct_bytes = sizeof(rt_nee_params). */
 void rt_nee_params_init(rt_nee_params *p);
@@ -657,6 +683,14 @@ rt_status rt_nee_light_table(rt_scene *scene, int32_t cap, int32_t *sphere_index
  * are rt_render_nee's and come first. */
 rt_status rt_nee_emitter_table(rt_scene *scene, const rt_nee_params *params, int32_t cap, int32_t *kind, int32_t *index, float *cdf, float *pmf,
                                float *area, int32_t *count);
+/* Probe for tests, HOST memory: the light tree over the table that params select (NULL: the defaults; select itself is checked, not read),
+ * built if the handle has none yet.  Per node, in preorder: sphere (centre and radius, 4 floats), weight, q (0 at a leaf), left and right
+ * (node indices, -1 at a leaf) and entry (-1 at an interior node); per table entry: path and depth.  *node_count = 2 N - 1 (0 for an empty
+ * table), *entry_count = N; the first min(cap, count) rows go to each column (each may be NULL when its cap is 0).  The parameter checks
+ * are rt_render_nee's and come first. */
+rt_status rt_nee_light_tree(rt_scene *scene, const rt_nee_params *params, int32_t cap_nodes, int32_t cap_entries, float *sphere, float *weight,
+                            float *q, int32_t *left, int32_t *right, int32_t *entry, uint32_t *path, int32_t *depth, int32_t *node_count,
+                            int32_t *entry_count);
 /* Probe for tests, HOST memory: rt_trace_samples for the estimator of rt_render_nee — radiance, rays (closest-hit queries, shadow rays
  * included), the path's final RNG state and the light samples' final state per (i, j, s). */
 rt_status rt_trace_samples_nee(rt_scene *scene, const rt_camera_data *cam, const rt_nee_params *params, int32_t n, const int32_t *ijs,

@@ -313,6 +313,18 @@ struct rt_scene {
     int32_t emit_spheres = 0, emit_planes = 0;
     int32_t *emit_code_dev = nullptr;
     float *emit_cdf_dev = nullptr, *emit_pmf_dev = nullptr, *emit_area_dev = nullptr;
+    // … and the light trees of select = 1, one per table ([0] the sphere-only one, [1] the two-kind one), each built by
+    // the first call that selects it from what the tables' read-back left: every entry's centre (3 doubles), radius and weight
+    struct LightTreeHost {
+        bool built = false;
+        std::vector<float> node;               // 8 words per node, preorder: centre, radius, weight, q, right, entry (int bits)
+        std::vector<uint32_t> path;            // per entry
+        std::vector<int32_t> depth;
+        float4 *node_dev = nullptr;
+        uint32_t *path_dev = nullptr;
+        int32_t *depth_dev = nullptr;
+    } tree[2];
+    std::vector<double> emit_geom;             // per entry of the two-kind table (the sphere-only one is its first emit_spheres): c0 c1 c2 rho w
 };
 
 namespace {
@@ -682,6 +694,7 @@ rt_status rt_scene_destroy(rt_scene *sc) {
     (void)hipFree(sc->adapt_mom); (void)hipFree(sc->adapt_list); (void)hipFree(sc->adapt_work); (void)hipFree(sc->adapt_counters);
     (void)hipFree(sc->nee_index_dev); (void)hipFree(sc->nee_cdf_dev); (void)hipFree(sc->nee_pmf_dev);
     (void)hipFree(sc->emit_code_dev); (void)hipFree(sc->emit_cdf_dev); (void)hipFree(sc->emit_pmf_dev); (void)hipFree(sc->emit_area_dev);
+    for (auto &t : sc->tree) { (void)hipFree(t.node_dev); (void)hipFree(t.path_dev); (void)hipFree(t.depth_dev); }
     for (rt_scene::Feedback &f : sc->feedback) {
         if (f.done) { if (f.pending) (void)hipEventSynchronize(f.done); (void)hipEventDestroy(f.done); }
         if (f.start) (void)hipEventDestroy(f.start);
@@ -2193,6 +2206,7 @@ namespace {
 struct NeeSetup {
     int32_t mis = 1;
     int32_t planes = 0;           // sample_planes
+    int32_t select = 0;           // 0: the power table; 1: the light tree
 };
 rt_status nee_setup(const char *what, const rt_nee_params *params, NeeSetup &N) {
     const std::string w(what);
@@ -2201,9 +2215,12 @@ rt_status nee_setup(const char *what, const rt_nee_params *params, NeeSetup &N) 
     if (const rt_status st = take_params(w, "rt_nee_params", params, np)) return st;
     if (params && params->struct_bytes < 12u) np.sample_planes = 0;          // (an older caller's struct ends before the field)
     if (np.mis != 0 && np.mis != 1) return fail(RT_ERR_INVALID_ARG, w + ": mis must be 0 or 1");
+    if (params && params->struct_bytes < 16u) np.select = 0;
     if (np.sample_planes != 0 && np.sample_planes != 1) return fail(RT_ERR_INVALID_ARG, w + ": sample_planes must be 0 or 1");
+    if (np.select != 0 && np.select != 1) return fail(RT_ERR_INVALID_ARG, w + ": select must be 0 or 1");
     N.mis = np.mis;
     N.planes = np.sample_planes;
+    N.select = np.select;
     return RT_OK;
 }
 
@@ -2248,13 +2265,15 @@ rt_status nee_table_ensure(rt_scene *sc) {
         return ok && lit ? (double)e.x + (double)e.y + (double)e.z : -1.0;
     };
     std::vector<int32_t> index;
-    std::vector<double> weight;
+    std::vector<double> weight, geom;
     for (int32_t i = 0; i < ns; ++i) {
         const float r = spheres[(size_t)i].w;
         const double e = emit_sum(smat[(size_t)i]);
         if (!(r > 0.0f) || e < 0.0) continue;
         index.push_back(i);
         weight.push_back(e * ((double)r * (double)r));
+        const float4 s = spheres[(size_t)i];
+        geom.insert(geom.end(), {(double)s.x, (double)s.y, (double)s.z, (double)r, weight.back()});
     }
     const size_t n = index.size();
     std::vector<float> cdf, pmf;
@@ -2279,6 +2298,22 @@ rt_status nee_table_ensure(rt_scene *sc) {
         code.push_back(2 * i + 1);
         area.push_back(A);
         weight.push_back(e * (double)A / 3.14159265358979323846);
+        // (the light tree's bound of the entry: header, "Tree")
+        const float4 B = planes[(size_t)i * 5 + 4];
+        const double b[3] = {B.x, B.y, B.z}, u[3] = {ux, uy, uz}, v[3] = {vx, vy, vz};
+        double c[3], rho = 0.0;
+        auto len3 = [](double x, double y, double z) { return std::sqrt((x * x + y * y) + z * z); };
+        if (type == RT_PLANE_TRIANGLE) {
+            for (int k = 0; k < 3; ++k) c[k] = b[k] + (u[k] + v[k]) / 3.0;
+            const double d0 = len3(b[0] - c[0], b[1] - c[1], b[2] - c[2]);
+            const double d1 = len3((b[0] + u[0]) - c[0], (b[1] + u[1]) - c[1], (b[2] + u[2]) - c[2]);
+            const double d2 = len3((b[0] + v[0]) - c[0], (b[1] + v[1]) - c[1], (b[2] + v[2]) - c[2]);
+            rho = std::max(d0, std::max(d1, d2));
+        } else {
+            for (int k = 0; k < 3; ++k) c[k] = (b[k] + 0.5 * u[k]) + 0.5 * v[k];
+            rho = 0.5 * std::max(len3(u[0] + v[0], u[1] + v[1], u[2] + v[2]), len3(u[0] - v[0], u[1] - v[1], u[2] - v[2]));
+        }
+        geom.insert(geom.end(), {c[0], c[1], c[2], rho, weight.back()});
     }
     const int32_t emit_planes = (int32_t)(code.size() - n);
     std::vector<float> ecdf, epmf;
@@ -2300,6 +2335,7 @@ rt_status nee_table_ensure(rt_scene *sc) {
     sc->emit_area = std::move(area);
     sc->emit_spheres = (int32_t)n;
     sc->emit_planes = emit_planes;
+    sc->emit_geom = std::move(geom);
     sc->nee_index = std::move(index);
     sc->nee_cdf = std::move(cdf);
     sc->nee_pmf = std::move(pmf);
@@ -2322,6 +2358,8 @@ rtk::NeeTable nee_table_of(const rt_scene *sc, int32_t mis) {
 union NeeEither {
     rtk::NeeTable nee;
     rtk::EmitTable emit;
+    rtk::TreeTable tree;
+    rtk::TreeEmitTable tree_emit;
 };
 bool emit_planes_on(const rt_scene *sc, const NeeSetup &N) { return N.planes != 0 && sc->emit_planes > 0; }
 rtk::EmitTable emit_table_of(const rt_scene *sc, int32_t mis) {
@@ -2336,6 +2374,104 @@ rtk::EmitTable emit_table_of(const rt_scene *sc, int32_t mis) {
     return T;
 }
 
+
+// ---- the light tree (header, "Tree") -----------------------------------------------------------------------------------
+// which table a call's parameters select: 1 the two-kind one (it holds a plane), 0 the sphere-only one
+int tree_which(const rt_scene *sc, const NeeSetup &N) { return emit_planes_on(sc, N) ? 1 : 0; }
+int32_t tree_entries(const rt_scene *sc, int which) { return (int32_t)(which ? sc->emit_code.size() : sc->nee_index.size()); }
+// does the call run the tree kernels?  (an empty table samples nothing: the kernels of select = 0; the tables must have been made)
+bool tree_on(const rt_scene *sc, const NeeSetup &N) { return N.select == 1 && tree_entries(sc, tree_which(sc, N)) > 0; }
+
+struct TreeBuilder {
+    const double *geom;                        // 5 per entry: c0 c1 c2 rho w
+    double total;
+    std::vector<float> node;
+    std::vector<uint32_t> path;
+    std::vector<int32_t> depth;
+    // the node over list S (reached by `bits` in `level` steps): its index; *weight_out: the double sum of its weights in list order
+    int32_t build(std::vector<int32_t> &S, uint32_t bits, int32_t level, double *weight_out) {
+        const int32_t id = (int32_t)(node.size() / 8);
+        node.resize(node.size() + 8);
+        double lo[3], hi[3], clo[3], chi[3], W = 0.0;
+        for (size_t k = 0; k < S.size(); ++k) {
+            const double *g = geom + 5 * (size_t)S[k];
+            for (int a = 0; a < 3; ++a) {
+                const double l = g[a] - g[3], h = g[a] + g[3];
+                if (k == 0 || l < lo[a]) lo[a] = l;
+                if (k == 0 || h > hi[a]) hi[a] = h;
+                if (k == 0 || g[a] < clo[a]) clo[a] = g[a];
+                if (k == 0 || g[a] > chi[a]) chi[a] = g[a];
+            }
+            W += g[4];
+        }
+        double m[3], R = 0.0;
+        for (int a = 0; a < 3; ++a) m[a] = 0.5 * (lo[a] + hi[a]);
+        for (int32_t e : S) {
+            const double *g = geom + 5 * (size_t)e;
+            const double dx = g[0] - m[0], dy = g[1] - m[1], dz = g[2] - m[2];
+            const double r = std::sqrt((dx * dx + dy * dy) + dz * dz) + g[3];
+            if (r > R) R = r;
+        }
+        float rec[8] = {(float)m[0], (float)m[1], (float)m[2], std::nextafterf((float)R, INFINITY), (float)(W / total), 0.0f, 0.0f, 0.0f};
+        int32_t right = -1, entry = -1;
+        if (S.size() == 1) {
+            entry = S[0];
+            path[(size_t)entry] = bits;
+            depth[(size_t)entry] = level;
+        } else {
+            int axis = 0;
+            for (int a = 1; a < 3; ++a)
+                if (chi[a] - clo[a] > chi[axis] - clo[axis]) axis = a;
+            std::stable_sort(S.begin(), S.end(), [&](int32_t x, int32_t y) { return geom[5 * (size_t)x + axis] < geom[5 * (size_t)y + axis]; });
+            const size_t nl = (S.size() + 1) / 2;
+            std::vector<int32_t> L(S.begin(), S.begin() + (ptrdiff_t)nl), Rr(S.begin() + (ptrdiff_t)nl, S.end());
+            double wl = 0.0, wr = 0.0;
+            build(L, bits, level + 1, &wl);
+            right = build(Rr, bits | (1u << level), level + 1, &wr);
+            rec[5] = (float)(wl / (wl + wr));
+        }
+        std::memcpy(&rec[6], &right, 4);
+        std::memcpy(&rec[7], &entry, 4);
+        std::memcpy(&node[(size_t)id * 8], rec, sizeof(rec));
+        if (weight_out) *weight_out = W;
+        return id;
+    }
+};
+// the tree of table `which`, built on its first use (the tables must have been made)
+rt_status tree_ensure(rt_scene *sc, int which) {
+    auto &t = sc->tree[which];
+    if (t.built) return RT_OK;
+    const int32_t n = tree_entries(sc, which);
+    if (n > 0) {
+        TreeBuilder B;
+        B.geom = sc->emit_geom.data();
+        B.total = 0.0;
+        for (int32_t e = 0; e < n; ++e) B.total += B.geom[5 * (size_t)e + 4];
+        B.path.assign((size_t)n, 0u);
+        B.depth.assign((size_t)n, 0);
+        std::vector<int32_t> all((size_t)n);
+        for (int32_t e = 0; e < n; ++e) all[(size_t)e] = e;
+        B.build(all, 0u, 0, nullptr);
+        if (const rt_status st = upload(B.node, (void **)&t.node_dev)) return st;
+        if (const rt_status st = upload(B.path, (void **)&t.path_dev)) return st;
+        if (const rt_status st = upload(B.depth, (void **)&t.depth_dev)) return st;
+        t.node = std::move(B.node);
+        t.path = std::move(B.path);
+        t.depth = std::move(B.depth);
+    }
+    t.built = true;
+    return RT_OK;
+}
+rtk::LightTree light_tree_of(const rt_scene *sc, int which) {
+    rtk::LightTree L;
+    L.node = sc->tree[which].node_dev;
+    L.path = sc->tree[which].path_dev;
+    L.depth = sc->tree[which].depth_dev;
+    return L;
+}
+rtk::TreeTable tree_table_of(const rt_scene *sc, int32_t mis) { return rtk::TreeTable{nee_table_of(sc, mis), light_tree_of(sc, 0)}; }
+rtk::TreeEmitTable tree_emit_table_of(const rt_scene *sc, int32_t mis) { return rtk::TreeEmitTable{emit_table_of(sc, mis), light_tree_of(sc, 1)}; }
+
 }  // namespace
 
 rt_status rt_render_nee(rt_scene *sc, const rt_camera_data *cam, const rt_nee_params *params, const rt_shard *shard, int32_t sample_first,
@@ -2345,7 +2481,17 @@ rt_status rt_render_nee(rt_scene *sc, const rt_camera_data *cam, const rt_nee_pa
     if (!sc) return fail(RT_ERR_INVALID_ARG, "rt_render_nee: null scene");
     auto make_table = [&](NeeEither &T, const void *&kernel) {
         if (const rt_status st = nee_table_ensure(sc)) return st;
-        if (emit_planes_on(sc, N)) {
+        if (tree_on(sc, N)) {
+            const int which = tree_which(sc, N);
+            if (const rt_status st = tree_ensure(sc, which)) return st;
+            if (which) {
+                T.tree_emit = tree_emit_table_of(sc, N.mis);
+                kernel = (const void *)rtk::tree_emit_render_kernel;
+            } else {
+                T.tree = tree_table_of(sc, N.mis);
+                kernel = (const void *)rtk::tree_render_kernel;
+            }
+        } else if (emit_planes_on(sc, N)) {
             T.emit = emit_table_of(sc, N.mis);
             kernel = (const void *)rtk::emit_render_kernel;
         } else {
@@ -2393,6 +2539,37 @@ rt_status rt_nee_emitter_table(rt_scene *sc, const rt_nee_params *params, int32_
     return RT_OK;
 }
 
+rt_status rt_nee_light_tree(rt_scene *sc, const rt_nee_params *params, int32_t cap_nodes, int32_t cap_entries, float *sphere, float *weight, float *q,
+                            int32_t *left, int32_t *right, int32_t *entry, uint32_t *path, int32_t *depth, int32_t *node_count, int32_t *entry_count) {
+    NeeSetup N;
+    if (const rt_status st = nee_setup("rt_nee_light_tree", params, N)) return st;
+    if (!sc || !node_count || !entry_count || cap_nodes < 0 || cap_entries < 0 || (cap_nodes > 0 && (!sphere || !weight || !q || !left || !right || !entry)) ||
+        (cap_entries > 0 && (!path || !depth)))
+        return fail(RT_ERR_INVALID_ARG, "rt_nee_light_tree: null argument or negative cap");
+    if (const rt_status st = check_device(sc)) return st;
+    if (const rt_status st = nee_table_ensure(sc)) return st;
+    const int which = tree_which(sc, N);
+    if (const rt_status st = tree_ensure(sc, which)) return st;
+    const auto &t = sc->tree[which];
+    const int32_t nn = (int32_t)(t.node.size() / 8), ne = (int32_t)t.path.size();
+    *node_count = nn;
+    *entry_count = ne;
+    for (int32_t k = 0; k < (cap_nodes < nn ? cap_nodes : nn); ++k) {
+        const float *rec = &t.node[(size_t)k * 8];
+        std::memcpy(sphere + 4 * k, rec, 16);
+        weight[k] = rec[4];
+        q[k] = rec[5];
+        std::memcpy(&right[k], &rec[6], 4);
+        std::memcpy(&entry[k], &rec[7], 4);
+        left[k] = right[k] >= 0 ? k + 1 : -1;
+    }
+    for (int32_t k = 0; k < (cap_entries < ne ? cap_entries : ne); ++k) {
+        path[k] = t.path[(size_t)k];
+        depth[k] = t.depth[(size_t)k];
+    }
+    return RT_OK;
+}
+
 rt_status rt_trace_samples_nee(rt_scene *sc, const rt_camera_data *cam, const rt_nee_params *params, int32_t n, const int32_t *ijs,
                                float *radiance, int32_t *rays, uint32_t *final_seed, uint32_t *final_nee_seed) {
     NeeSetup N;
@@ -2404,7 +2581,12 @@ rt_status rt_trace_samples_nee(rt_scene *sc, const rt_camera_data *cam, const rt
     if ((st = check_device(sc)) != RT_OK) return st;
     return run_probe("rt_trace_samples_nee: ", P, cam, n, ijs, radiance, rays, final_seed, final_nee_seed, nullptr, [&](const rtk::KParams &KP, uint32_t *d_nee, uint32_t *) {
         if (const rt_status ts = nee_table_ensure(sc)) return ts;
-        if (emit_planes_on(sc, N)) hipLaunchKernelGGL(rtk::emit_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, KP, emit_table_of(sc, N.mis), d_nee);
+        if (tree_on(sc, N)) {
+            const int which = tree_which(sc, N);
+            if (const rt_status ts = tree_ensure(sc, which)) return ts;
+            if (which) hipLaunchKernelGGL(rtk::tree_emit_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, KP, tree_emit_table_of(sc, N.mis), d_nee);
+            else hipLaunchKernelGGL(rtk::tree_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, KP, tree_table_of(sc, N.mis), d_nee);
+        } else if (emit_planes_on(sc, N)) hipLaunchKernelGGL(rtk::emit_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, KP, emit_table_of(sc, N.mis), d_nee);
         else hipLaunchKernelGGL(rtk::nee_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, KP, nee_table_of(sc, N.mis), d_nee);
         return RT_OK;
     });
@@ -2701,12 +2883,30 @@ rt_status lit_setup(const char *what, const rt_camera_data *cam_open, const rt_l
 union LitEither {
     rtk::LitLight lit;
     rtk::LitEmitLight emit;
+    rtk::LitTreeOf<rtk::TreeTable> tree;
+    rtk::LitTreeOf<rtk::TreeEmitTable> tree_emit;
 };
-rt_status lit_light_of(rt_scene *sc, const LitSetup &S, LitEither &T, bool &planes) {
+// (tree: select = 1 on a table that is not empty — the tree table is T.tree_emit with planes, else T.tree)
+rt_status lit_light_of(rt_scene *sc, const LitSetup &S, LitEither &T, bool &planes, bool &tree) {
     planes = false;
+    tree = false;
     if (S.emitters) {
         if (const rt_status st = nee_table_ensure(sc)) return st;
         planes = emit_planes_on(sc, S.nee);
+        tree = tree_on(sc, S.nee);
+    }
+    if (tree) {
+        if (const rt_status st = tree_ensure(sc, planes ? 1 : 0)) return st;
+        if (planes) {
+            T.tree_emit = rtk::LitTreeOf<rtk::TreeEmitTable>{};
+            T.tree_emit.N = tree_emit_table_of(sc, S.nee.mis);
+            if (S.env) { T.tree_emit.E = env_dev_of(S.env, S.ep); T.tree_emit.env_on = 1; }
+        } else {
+            T.tree = rtk::LitTreeOf<rtk::TreeTable>{};
+            T.tree.N = tree_table_of(sc, S.nee.mis);
+            if (S.env) { T.tree.E = env_dev_of(S.env, S.ep); T.tree.env_on = 1; }
+        }
+        return RT_OK;
     }
     if (planes) {
         T.emit = rtk::LitEmitLight{};
@@ -2731,9 +2931,11 @@ rt_status rt_render_lit(rt_scene *sc, const rt_camera_data *cam_open, const rt_l
     if (!sc) return fail(RT_ERR_INVALID_ARG, "rt_render_lit: null scene");
     const void *kernel = S.lens ? (const void *)rtk::lit_render_kernel<true> : (const void *)rtk::lit_render_kernel<false>;
     auto make_light = [&](LitEither &T, const void *&k) {
-        bool planes;
-        if (const rt_status st = lit_light_of(sc, S, T, planes)) return st;
-        if (planes) k = S.lens ? (const void *)rtk::lit_emit_render_kernel<true> : (const void *)rtk::lit_emit_render_kernel<false>;
+        bool planes, tree;
+        if (const rt_status st = lit_light_of(sc, S, T, planes, tree)) return st;
+        if (tree && planes) k = S.lens ? (const void *)rtk::lit_tree_render_kernel<true, rtk::TreeEmitTable> : (const void *)rtk::lit_tree_render_kernel<false, rtk::TreeEmitTable>;
+        else if (tree) k = S.lens ? (const void *)rtk::lit_tree_render_kernel<true, rtk::TreeTable> : (const void *)rtk::lit_tree_render_kernel<false, rtk::TreeTable>;
+        else if (planes) k = S.lens ? (const void *)rtk::lit_emit_render_kernel<true> : (const void *)rtk::lit_emit_render_kernel<false>;
         return RT_OK;
     };
     return render_light_impl<LitEither>("rt_render_lit", kernel, S.env ? &S.env->device : nullptr, make_light, sc, cam_open, shard, sample_first, d_fb_sum,
@@ -2754,10 +2956,14 @@ rt_status rt_trace_samples_lit(rt_scene *sc, const rt_camera_data *cam_open, con
     return run_probe("rt_trace_samples_lit: ", P, cam_open, n, ijs, radiance, rays, final_seed, final_nee_seed, final_env_seed,
                      [&](const rtk::KParams &KP, uint32_t *d_nee, uint32_t *d_env) {
         LitEither T;
-        bool planes;
-        if (const rt_status ts = lit_light_of(sc, S, T, planes)) return ts;
+        bool planes, tree;
+        if (const rt_status ts = lit_light_of(sc, S, T, planes, tree)) return ts;
         const dim3 grid((n + 255) / 256), block(256);
-        if (planes && S.lens) hipLaunchKernelGGL(rtk::lit_emit_probe_kernel<true>, grid, block, 0, 0, KP, T.emit, S.C, d_nee, d_env);
+        if (tree && planes && S.lens) hipLaunchKernelGGL((rtk::lit_tree_probe_kernel<true, rtk::TreeEmitTable>), grid, block, 0, 0, KP, T.tree_emit, S.C, d_nee, d_env);
+        else if (tree && planes) hipLaunchKernelGGL((rtk::lit_tree_probe_kernel<false, rtk::TreeEmitTable>), grid, block, 0, 0, KP, T.tree_emit, S.C, d_nee, d_env);
+        else if (tree && S.lens) hipLaunchKernelGGL((rtk::lit_tree_probe_kernel<true, rtk::TreeTable>), grid, block, 0, 0, KP, T.tree, S.C, d_nee, d_env);
+        else if (tree) hipLaunchKernelGGL((rtk::lit_tree_probe_kernel<false, rtk::TreeTable>), grid, block, 0, 0, KP, T.tree, S.C, d_nee, d_env);
+        else if (planes && S.lens) hipLaunchKernelGGL(rtk::lit_emit_probe_kernel<true>, grid, block, 0, 0, KP, T.emit, S.C, d_nee, d_env);
         else if (planes) hipLaunchKernelGGL(rtk::lit_emit_probe_kernel<false>, grid, block, 0, 0, KP, T.emit, S.C, d_nee, d_env);
         else if (S.lens) hipLaunchKernelGGL(rtk::lit_probe_kernel<true>, grid, block, 0, 0, KP, T.lit, S.C, d_nee, d_env);
         else hipLaunchKernelGGL(rtk::lit_probe_kernel<false>, grid, block, 0, 0, KP, T.lit, S.C, d_nee, d_env);

@@ -83,6 +83,54 @@ __device__ __forceinline__ bool light_sample(const KParams &, const EnvDev &E, u
 __device__ __forceinline__ bool light_reached(const NeeTable &, const Lane &L, int32_t code) { return L.hit == code; }
 __device__ __forceinline__ bool light_reached(const EmitTable &, const Lane &L, int32_t code) { return L.hit == code; }
 __device__ __forceinline__ bool light_reached(const EnvDev &, const Lane &L, int32_t) { return L.hit < 0; }
+// (the light tree, select = 1: the tables' own overloads with the pick by tree_pick and pmf_e(x) by tree_pmf from the ray's origin;
+// DESIGN.md §18.  A tree table is never empty: the host hands an empty table to the kernels above)
+__device__ __forceinline__ uint32_t light_key(const TreeTable &) { return kNeeStreamKey; }
+__device__ __forceinline__ uint32_t light_key(const TreeEmitTable &) { return kNeeStreamKey; }
+__device__ __forceinline__ bool light_on(const TreeTable &T) { return T.N.count > 0; }
+__device__ __forceinline__ bool light_on(const TreeEmitTable &T) { return T.N.count > 0; }
+__device__ __forceinline__ f3 light_miss(const KParams &P, const TreeTable &, const Lane &L, bool) { return mul(L.beta, mk(P.bg[0], P.bg[1], P.bg[2])); }
+__device__ __forceinline__ f3 light_miss(const KParams &P, const TreeEmitTable &, const Lane &L, bool) { return mul(L.beta, mk(P.bg[0], P.bg[1], P.bg[2])); }
+__device__ __forceinline__ f3 light_emitted(const KParams &P, const TreeTable &T, const Lane &L, int32_t idx, bool is_plane, bool prev_diffuse, f3 emitted) {
+    if (prev_diffuse && !is_plane) {
+        const int32_t e = nee_find(T.N, idx);
+        if (e >= 0) {
+            f3 w;
+            float d2, om, pl = 0.0f;
+            if (nee_cone(L.o, P.spheres[idx], w, d2, om)) pl = tree_pmf(T.L, e, L.o) * nee_pdf_cone(om);
+            const float wb = T.N.mis ? (kNeePb * kNeePb) / (kNeePb * kNeePb + pl * pl) : (pl > 0.0f ? 0.0f : 1.0f);
+            emitted = scale(wb, emitted);
+        }
+    }
+    return emitted;
+}
+__device__ __forceinline__ f3 light_emitted(const KParams &P, const TreeEmitTable &T, const Lane &L, int32_t idx, bool is_plane, bool prev_diffuse, f3 emitted) {
+    if (prev_diffuse) {
+        const int32_t e = emit_find(T.N, L.hit);
+        if (e >= 0) {
+            f3 w;
+            float pl = 0.0f;
+            if (is_plane) {
+                float pa;
+                if (emit_plane_pa(P, idx, T.N.area[e], L.o, add(L.o, scale(L.closest, L.d)), w, pa)) pl = tree_pmf(T.L, e, L.o) * pa;
+            } else {
+                float d2, om;
+                if (nee_cone(L.o, P.spheres[idx], w, d2, om)) pl = tree_pmf(T.L, e, L.o) * nee_pdf_cone(om);
+            }
+            const float wb = T.N.mis ? (kNeePb * kNeePb) / (kNeePb * kNeePb + pl * pl) : (pl > 0.0f ? 0.0f : 1.0f);
+            emitted = scale(wb, emitted);
+        }
+    }
+    return emitted;
+}
+__device__ __forceinline__ bool light_sample(const KParams &P, const TreeTable &T, uint32_t &ls, f3 x, f3 n, f3 a, f3 beta, f3 &dir, f3 &c, int32_t &code) {
+    return tree_sample(P, T, ls, x, n, a, beta, dir, c, code);
+}
+__device__ __forceinline__ bool light_sample(const KParams &P, const TreeEmitTable &T, uint32_t &ls, f3 x, f3 n, f3 a, f3 beta, f3 &dir, f3 &c, int32_t &code) {
+    return tree_sample(P, T, ls, x, n, a, beta, dir, c, code);
+}
+__device__ __forceinline__ bool light_reached(const TreeTable &, const Lane &L, int32_t code) { return L.hit == code; }
+__device__ __forceinline__ bool light_reached(const TreeEmitTable &, const Lane &L, int32_t code) { return L.hit == code; }
 
 // the light samples' RNG state of a sample (the path's own is start_sample's)
 template <class Light>
@@ -383,6 +431,11 @@ __global__ void __launch_bounds__(kLightBlock) env_render_kernel(const KParams P
 // (sample_planes = 1 on a handle whose table holds a plane: DESIGN.md §17)
 __global__ void __launch_bounds__(256) emit_probe_kernel(const KParams P, const EmitTable T, uint32_t *nee_seed_out) { light_probe_body(P, T, nee_seed_out); }
 __global__ void __launch_bounds__(kLightBlock) emit_render_kernel(const KParams P, const EmitTable T) { light_render_body(P, T); }
+// (select = 1: the light tree over either table; DESIGN.md §18)
+__global__ void __launch_bounds__(256) tree_probe_kernel(const KParams P, const TreeTable T, uint32_t *nee_seed_out) { light_probe_body(P, T, nee_seed_out); }
+__global__ void __launch_bounds__(kLightBlock) tree_render_kernel(const KParams P, const TreeTable T) { light_render_body(P, T); }
+__global__ void __launch_bounds__(256) tree_emit_probe_kernel(const KParams P, const TreeEmitTable T, uint32_t *nee_seed_out) { light_probe_body(P, T, nee_seed_out); }
+__global__ void __launch_bounds__(kLightBlock) tree_emit_render_kernel(const KParams P, const TreeEmitTable T) { light_render_body(P, T); }
 
 // ---- rt_render_lit: the emitter table and an environment at once, from the lens camera (DESIGN.md §16) -------------------------------
 // The third light: both tables, either of which may be off (an emitter table with count 0 — sample_emitters = 0 or no emitter; env_on = 0
@@ -415,6 +468,24 @@ __device__ __forceinline__ f3 light_emitted(const KParams &P, const LitEmitLight
     return light_emitted(P, T.N, L, idx, is_plane, prev_diffuse, emitted);
 }
 __device__ __forceinline__ bool env_sampled(const LitEmitLight &T) { return T.env_on && light_on(T.E); }
+// (select = 1: the emitter table is a tree table — LitTreeOf<TreeTable> or LitTreeOf<TreeEmitTable>)
+template <class Table>
+struct LitTreeOf {
+    Table N;
+    EnvDev E;
+    int32_t env_on;
+};
+template <class Table>
+__device__ __forceinline__ f3 light_miss(const KParams &P, const LitTreeOf<Table> &T, const Lane &L, bool prev_diffuse) {
+    if (T.env_on) return light_miss(P, T.E, L, prev_diffuse);
+    return light_miss(P, T.N, L, prev_diffuse);
+}
+template <class Table>
+__device__ __forceinline__ f3 light_emitted(const KParams &P, const LitTreeOf<Table> &T, const Lane &L, int32_t idx, bool is_plane, bool prev_diffuse, f3 emitted) {
+    return light_emitted(P, T.N, L, idx, is_plane, prev_diffuse, emitted);
+}
+template <class Table>
+__device__ __forceinline__ bool env_sampled(const LitTreeOf<Table> &T) { return T.env_on && light_on(T.E); }
 
 // The two light samples of a lit vertex: the emitter's (a: the shadow ray has to reach the primitive `code`) and the environment's (b: it has
 // to reach nothing).  Both are drawn at shade time — the streams are independent, and the order of the adds is the caller's.
@@ -627,5 +698,12 @@ __global__ void __launch_bounds__(256) lit_emit_probe_kernel(const KParams P, co
 }
 template <bool kLens>
 __global__ void __launch_bounds__(kLightBlock, 4) lit_emit_render_kernel(const KParams P, const LitEmitLight T, const LensCam C) { lit_render_body<kLens>(P, T, C); }
+// (select = 1: Table is TreeTable or TreeEmitTable)
+template <bool kLens, class Table>
+__global__ void __launch_bounds__(256) lit_tree_probe_kernel(const KParams P, const LitTreeOf<Table> T, const LensCam C, uint32_t *nee_seed_out, uint32_t *env_seed_out) {
+    lit_probe_body<kLens>(P, T, C, nee_seed_out, env_seed_out);
+}
+template <bool kLens, class Table>
+__global__ void __launch_bounds__(kLightBlock, 4) lit_tree_render_kernel(const KParams P, const LitTreeOf<Table> T, const LensCam C) { lit_render_body<kLens>(P, T, C); }
 
 }  // namespace rtk

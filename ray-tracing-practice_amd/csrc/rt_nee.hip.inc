@@ -5,7 +5,8 @@
 // The path draws exactly what rt_render draws; at every diffuse event (LAMBERTIAN, or METAL's hemisphere branch) whose next query is
 // still inside max_depth, one light sample is taken from a second RNG stream: an emitter sphere from the handle's table (cdf, by
 // bisection), a direction uniform in the cone the sphere subtends, and a shadow ray through the same walk.  The BSDF ray that leaves
-// the same vertex has its hit on a table sphere weighted by the power heuristic (or by 0: light sampling alone).  Every expression is
+// the same vertex has its hit on a table sphere weighted by the power heuristic (or by 0: light sampling alone).  With select = 1 the
+// entry comes from a descent of the light tree at the end of this file instead of the cdf (DESIGN.md §18).  Every expression is
 // the header's, in its order (the project's float rules: nothing fused, correctly rounded division and sqrt).
 #pragma once
 
@@ -144,44 +145,54 @@ __device__ __forceinline__ bool emit_plane_pa(const KParams &P, int32_t plane, f
 }
 // steps 2p to 4p for the picked entry e, a plane: a point uniform in area (QUAD: the parallelogram; TRIANGLE: its lower half, by the
 // fold; ELLIPSE: the inscribed ellipse, by the disc's rejection loop), two-sided
+// (one text for the table's pick and the light tree's: RTP_EMIT_PLANE_STEPS, the body of a function with P, T, e, nee, x, n, a, beta, dir,
+// c and code in scope; PMF: the probability of the pick that gave e)
+#define RTP_EMIT_PLANE_STEPS(PMF)                                                                                                        \
+    const int32_t hit = T.code[e];                                                                                                       \
+    const int32_t plane = hit >> 1;                                                                                                      \
+    const float4 P1 = P.planes[5 * plane + 1];                                                                                           \
+    const float4 P2 = P.planes[5 * plane + 2];                                                                                           \
+    const float4 P3 = P.planes[5 * plane + 3];                                                                                           \
+    const float4 P4 = P.planes[5 * plane + 4];                                                                                           \
+    const int32_t type = as_int(P1.w);                                                                                                   \
+    float ua, ub;                                                                                                                        \
+    if (type == RT_PLANE_ELLIPSE) {                                                                                                      \
+        float px, py, q2;                                                                                                                \
+        do {                                                                                                                             \
+            px = random_pm1(nee);                                                                                                        \
+            py = random_pm1(nee);                                                                                                        \
+            q2 = px * px + py * py;                                                                                                      \
+        } while (q2 >= 1.0f);                                                                                                            \
+        ua = 0.5f + 0.5f * px;                                                                                                           \
+        ub = 0.5f + 0.5f * py;                                                                                                           \
+    } else {                                                                                                                             \
+        ua = random_float(nee);                                                                                                          \
+        ub = random_float(nee);                                                                                                          \
+        if (type == RT_PLANE_TRIANGLE && ua + ub > 1.0f) {                                                                               \
+            ua = 1.0f - ua;                                                                                                              \
+            ub = 1.0f - ub;                                                                                                              \
+        }                                                                                                                                \
+    }                                                                                                                                    \
+    const f3 y = mk((P4.x + ua * P2.x) + ub * P3.x, (P4.y + ua * P2.y) + ub * P3.y, (P4.z + ua * P2.z) + ub * P3.z);                     \
+    float pa;                                                                                                                            \
+    if (!emit_plane_pa(P, plane, T.area[e], x, y, dir, pa)) return false;                                                                \
+    if (!(dot(dir, n) > 0.0f)) return false;                                                                                             \
+    const float pl = PMF * pa;                                                                                                           \
+    const float f = T.mis ? (kNeePb * pl) / (pl * pl + kNeePb * kNeePb) : kNeePb / pl;                                                   \
+    const float4 ME = P.materials[3 * as_int(P2.w) + 1];                                                                                 \
+    c = scale(f, mul(mul(beta, a), mk(ME.x, ME.y, ME.z)));                                                                               \
+    code = hit;                                                                                                                          \
+    return true;
 __device__ __forceinline__ bool emit_sample_plane(const KParams &P, const EmitTable &T, int32_t e, uint32_t &nee, f3 x, f3 n, f3 a, f3 beta, f3 &dir, f3 &c,
                                                   int32_t &code) {
-    const int32_t hit = T.code[e];
-    const int32_t plane = hit >> 1;
-    const float4 P1 = P.planes[5 * plane + 1];
-    const float4 P2 = P.planes[5 * plane + 2];
-    const float4 P3 = P.planes[5 * plane + 3];
-    const float4 P4 = P.planes[5 * plane + 4];
-    const int32_t type = as_int(P1.w);
-    float ua, ub;
-    if (type == RT_PLANE_ELLIPSE) {
-        float px, py, q2;
-        do {
-            px = random_pm1(nee);
-            py = random_pm1(nee);
-            q2 = px * px + py * py;
-        } while (q2 >= 1.0f);
-        ua = 0.5f + 0.5f * px;
-        ub = 0.5f + 0.5f * py;
-    } else {
-        ua = random_float(nee);
-        ub = random_float(nee);
-        if (type == RT_PLANE_TRIANGLE && ua + ub > 1.0f) {
-            ua = 1.0f - ua;
-            ub = 1.0f - ub;
-        }
-    }
-    const f3 y = mk((P4.x + ua * P2.x) + ub * P3.x, (P4.y + ua * P2.y) + ub * P3.y, (P4.z + ua * P2.z) + ub * P3.z);
-    float pa;
-    if (!emit_plane_pa(P, plane, T.area[e], x, y, dir, pa)) return false;
-    if (!(dot(dir, n) > 0.0f)) return false;
-    const float pl = T.pmf[e] * pa;
-    const float f = T.mis ? (kNeePb * pl) / (pl * pl + kNeePb * kNeePb) : kNeePb / pl;
-    const float4 ME = P.materials[3 * as_int(P2.w) + 1];
-    c = scale(f, mul(mul(beta, a), mk(ME.x, ME.y, ME.z)));
-    code = hit;
-    return true;
+    RTP_EMIT_PLANE_STEPS(T.pmf[e])
 }
+// (the light tree's: pmf is the descent's product)
+__device__ __forceinline__ bool tree_sample_plane(const KParams &P, const EmitTable &T, int32_t e, float pmf, uint32_t &nee, f3 x, f3 n, f3 a, f3 beta, f3 &dir,
+                                                  f3 &c, int32_t &code) {
+    RTP_EMIT_PLANE_STEPS(pmf)
+}
+#undef RTP_EMIT_PLANE_STEPS
 // the light sample of the two-kind table: step 1, then the steps of the entry's kind
 __device__ __forceinline__ bool emit_sample(const KParams &P, const EmitTable &T, uint32_t &nee, f3 x, f3 n, f3 a, f3 beta, f3 &dir, f3 &c, int32_t &code) {
     const float u = random_float(nee);
@@ -189,6 +200,88 @@ __device__ __forceinline__ bool emit_sample(const KParams &P, const EmitTable &T
     if (e >= T.count) return false;
     if (e < T.spheres) return nee_sample_sphere(P, T.code[e] >> 1, T.pmf + e, T.mis, nee, x, n, a, beta, dir, c, code);
     return emit_sample_plane(P, T, e, nee, x, n, a, beta, dir, c, code);
+}
+
+// ---- the light tree (select = 1; DESIGN.md §18) ---------------------------------------------------------------------------------------
+// A bounding-sphere hierarchy over a table's entries, built on the host (rt_capi.hip, TreeBuilder), in preorder: the left child of an
+// interior node i is node i + 1.  Two float4 per node, read through L1 / L2: (centre, radius) and (weight, q, right, entry) — right and
+// entry as int bits, right = -1 at a leaf, entry = -1 at an interior node.  Per entry: its path from the root (bit i set: step i goes
+// right) and its depth.  The pick replaces step 1 of the header; the steps after it are the table's own with the descent's pmf.
+struct LightTree {
+    const float4 *node;
+    const uint32_t *path;
+    const int32_t *depth;
+};
+struct TreeTable {          // the sphere-only table and its tree
+    NeeTable N;
+    LightTree L;
+};
+struct TreeEmitTable {      // the two-kind table and its tree
+    EmitTable N;
+    LightTree L;
+};
+// the importance of a child (A: centre and radius, W: weight) from x
+__device__ __forceinline__ float tree_importance(float4 A, float W, f3 x) {
+    const f3 w = sub(mk(A.x, A.y, A.z), x);
+    const float d2 = dot(w, w);
+    return W / fmaxf(d2, A.w * A.w);
+}
+// One level below the interior node `node` (B: its second word) from x: the probability pL of its left child, and both children's second
+// words.  The descent and the path product take every level through here — the same expressions in the same order
+__device__ __forceinline__ float tree_level(const LightTree &L, int32_t node, float4 B, f3 x, float4 &LB, float4 &RB) {
+    const int32_t l = node + 1, r = as_int(B.z);
+    const float4 LA = L.node[2 * l];
+    LB = L.node[2 * l + 1];
+    const float4 RA = L.node[2 * r];
+    RB = L.node[2 * r + 1];
+    const float il = tree_importance(LA, LB.x, x);
+    const float ir = tree_importance(RA, RB.x, x);
+    const float s = il + ir;
+    return (s > 0.0f && s < INFINITY) ? il / s : B.y;
+}
+// the pick: one draw per level; the entry of the leaf it ends on and p, the probability of that descent
+__device__ __forceinline__ int32_t tree_pick(const LightTree &L, uint32_t &nee, f3 x, float &p) {
+    int32_t node = 0;
+    float4 B = L.node[1];
+    p = 1.0f;
+    while (as_int(B.z) >= 0) {
+        float4 LB, RB;
+        const float pl = tree_level(L, node, B, x, LB, RB);
+        const float u = random_float(nee);
+        const bool left = u < pl;
+        p = p * (left ? pl : 1.0f - pl);
+        node = left ? node + 1 : as_int(B.z);
+        B = left ? LB : RB;
+    }
+    return as_int(B.w);
+}
+// pmf_e(x): the same product root-down along entry e's stored path
+__device__ __forceinline__ float tree_pmf(const LightTree &L, int32_t e, f3 x) {
+    const uint32_t path = L.path[e];
+    const int32_t depth = L.depth[e];
+    int32_t node = 0;
+    float4 B = L.node[1];
+    float p = 1.0f;
+    for (int32_t i = 0; i < depth; ++i) {
+        float4 LB, RB;
+        const float pl = tree_level(L, node, B, x, LB, RB);
+        const bool left = ((path >> i) & 1u) == 0u;
+        p = p * (left ? pl : 1.0f - pl);
+        node = left ? node + 1 : as_int(B.z);
+        B = left ? LB : RB;
+    }
+    return p;
+}
+__device__ __forceinline__ bool tree_sample(const KParams &P, const TreeTable &T, uint32_t &nee, f3 x, f3 n, f3 a, f3 beta, f3 &dir, f3 &c, int32_t &code) {
+    float p;
+    const int32_t e = tree_pick(T.L, nee, x, p);
+    return nee_sample_sphere(P, T.N.index[e], &p, T.N.mis, nee, x, n, a, beta, dir, c, code);
+}
+__device__ __forceinline__ bool tree_sample(const KParams &P, const TreeEmitTable &T, uint32_t &nee, f3 x, f3 n, f3 a, f3 beta, f3 &dir, f3 &c, int32_t &code) {
+    float p;
+    const int32_t e = tree_pick(T.L, nee, x, p);
+    if (e < T.N.spheres) return nee_sample_sphere(P, T.N.code[e] >> 1, &p, T.N.mis, nee, x, n, a, beta, dir, c, code);
+    return tree_sample_plane(P, T.N, e, p, nee, x, n, a, beta, dir, c, code);
 }
 
 }  // namespace rtk

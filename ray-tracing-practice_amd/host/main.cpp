@@ -150,9 +150,10 @@ int main(int argc, char *argv[]) {
     // extension: `--gpu --nee [mis|light]`: every frame through rt_render_nee on one GPU (direct light sampling of the emissive spheres,
     // combined with the path's own sample by the power heuristic, or alone), the same saver bytes; --aov / --denoise as without it
     // (first-hit AOVs do not depend on the estimator).  Not with --lens, --motion-blur, --adaptive, --denoise-temporal, --devices,
-    // --shard or RTP_DEVICES.
+    // --shard or RTP_DEVICES.  `--light-tree` (with --nee, or with --lit, whose emitters are sampled): the emitter of a light sample is
+    // picked by the light tree, by where the shaded point is (rt_nee_params.select = 1), instead of the power table.
     {
-        bool nee_on = false, nee_bad = false, nee_others = getenv("RTP_DEVICES") != nullptr;
+        bool nee_on = false, nee_bad = false, tree_on = false, nee_others = getenv("RTP_DEVICES") != nullptr;
         rt_nee_params nee;
         rt_nee_params_init(&nee);
         for (int a = 2; a < argc; ++a) {
@@ -160,6 +161,7 @@ int main(int argc, char *argv[]) {
             if (arg == "--lens" || arg == "--motion-blur" || arg == "--adaptive" || arg == "--denoise-temporal" || arg == "--devices" ||
                 arg == "--shard")
                 nee_others = true;
+            if (arg == "--light-tree") tree_on = true;
             if (arg == "--nee") {
                 nee_on = true;
                 if (a + 1 < argc && argv[a + 1][0] != '-') {
@@ -169,6 +171,14 @@ int main(int argc, char *argv[]) {
                     else nee_bad = true;
                 }
             }
+        }
+        if (tree_on && !nee_on && !lit_on) {
+            std::cerr << "rtp_main: --light-tree picks the emitter of a light sample: it needs --nee or --lit\n";
+            return 99;
+        }
+        if (tree_on) {
+            nee.select = 1;
+            lit_nee.select = 1;
         }
         if (nee_on) {
             if (nee_bad) {

@@ -164,15 +164,15 @@ class NeeParams(C.Structure):
     """rt_nee_params (include/rtp_amd.h): an IN structure of the caller's size — struct_bytes is set on construction; the other
     fields are 0 until rt_nee_params_init (nee_params()) fills the defaults."""
     class _Tail(C.Union):
-        """The struct's last 8 bytes: sample_planes and one reserved word — and, over the same bytes, the two-word `reserved` view of
-        the struct before sample_planes was taken from it."""
+        """The struct's last 8 bytes: sample_planes and select — and, over the same bytes, the two-word `reserved` view of the struct
+        before the two were taken from it (reserved[1] is select: 0 by default)."""
         class _Words(C.Structure):
-            _fields_ = [("sample_planes", C.c_int32), ("_reserved1", C.c_int32)]
+            _fields_ = [("sample_planes", C.c_int32), ("select", C.c_int32)]
         _anonymous_ = ("_words",)
         _fields_ = [("_words", _Words), ("reserved", C.c_int32 * 2)]
     _anonymous_ = ("_tail",)
     _fields_ = [("struct_bytes", C.c_uint32), ("mis", C.c_int32), ("_tail", _Tail)]
-    FIELDS = ("struct_bytes", "mis", "sample_planes")          # what nee_params() sets
+    FIELDS = ("struct_bytes", "mis", "sample_planes", "select")          # what nee_params() sets
 
     def __init__(self, *args, **kw):
         super().__init__(*args, **kw)
@@ -180,7 +180,7 @@ class NeeParams(C.Structure):
 
 
 def nee_params(**params):
-    """rt_nee_params with the library's defaults (mis = 1, sample_planes = 0), then the given fields."""
+    """rt_nee_params with the library's defaults (mis = 1, sample_planes = 0, select = 0), then the given fields."""
     p = NeeParams()
     amd_lib().rt_nee_params_init(C.byref(p))
     for k, v in params.items():
@@ -388,6 +388,7 @@ RTP_AMD_SYMBOLS = [
     "rt_adaptive_params_init", "rt_render_adaptive", "rt_tonemap_spp",
     "rt_lens_params_init", "rt_render_lens", "rt_render_aov_lens", "rt_lens_camera_rays",
     "rt_nee_params_init", "rt_render_nee", "rt_nee_light_table", "rt_trace_samples_nee", "rt_nee_emitter_table",
+    "rt_nee_light_tree",
     "rt_env_params_init", "rt_env_create", "rt_env_destroy", "rt_env_table", "rt_env_lookup", "rt_env_from_equirect", "rt_render_env",
     "rt_trace_samples_env",
     "rt_lit_params_init", "rt_render_lit", "rt_trace_samples_lit",
@@ -503,6 +504,8 @@ def amd_lib():
             if hasattr(lib, "rt_nee_emitter_table"):
                 lib.rt_nee_emitter_table.argtypes = [C.c_void_p, C.POINTER(NeeParams), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                      C.c_void_p, C.POINTER(C.c_int32)]
+            if hasattr(lib, "rt_nee_light_tree"):
+                lib.rt_nee_light_tree.argtypes = [C.c_void_p, C.POINTER(NeeParams), C.c_int32, C.c_int32] + [C.c_void_p] * 8 + [C.POINTER(C.c_int32)] * 2
             lib.rt_trace_samples_nee.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(NeeParams), C.c_int32, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.c_void_p]
         if hasattr(lib, "rt_render_env"):
@@ -1153,6 +1156,23 @@ class DeviceScene:
             _check(lib.rt_nee_emitter_table(self._h, p, n.value, kind.ctypes.data, idx.ctypes.data, cdf.ctypes.data, pmf.ctypes.data,
                                             area.ctypes.data, C.byref(n)), "rt_nee_emitter_table")
         return kind, idx, cdf, pmf, area
+
+    def nee_light_tree(self, params=None):
+        """rt_nee_light_tree: the light tree over the emitter table that params (None, a NeeParams or a dict) select, as a dict of columns
+        — per node (preorder) sphere (n, 4) float32, weight, q float32, left, right, entry int32; per table entry path uint32, depth
+        int32."""
+        lib = amd_lib()
+        nn, ne = C.c_int32(), C.c_int32()
+        p = _nee_struct(params)
+        _check(lib.rt_nee_light_tree(self._h, p, 0, 0, *([None] * 8), C.byref(nn), C.byref(ne)), "rt_nee_light_tree")
+        t = {"sphere": np.zeros((nn.value, 4), np.float32), "weight": np.zeros(nn.value, np.float32), "q": np.zeros(nn.value, np.float32),
+             "left": np.zeros(nn.value, np.int32), "right": np.zeros(nn.value, np.int32), "entry": np.zeros(nn.value, np.int32),
+             "path": np.zeros(ne.value, np.uint32), "depth": np.zeros(ne.value, np.int32)}
+        if nn.value:
+            _check(lib.rt_nee_light_tree(self._h, p, nn.value, ne.value, *(t[k].ctypes.data for k in ("sphere", "weight", "q", "left", "right",
+                                                                                                      "entry", "path", "depth")),
+                                         C.byref(nn), C.byref(ne)), "rt_nee_light_tree")
+        return t
 
     def trace_samples_nee(self, cam, ijs, params=None):
         """rt_trace_samples_nee: ijs (n, 3) → (radiance (n, 3), rays (n,), final seeds (n,), final light-sample seeds (n,))."""

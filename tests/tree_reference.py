@@ -1,0 +1,106 @@
+"""CPU reference of rt_nee_params.select — the light tree of rt_render_nee / rt_render_lit (TEST INFRASTRUCTURE):
+tests/cpu_native/tree_ref.c, which includes emit_ref.c (and through it oracle/rt_oracle.c), built into a shared library (gcc
+-ffp-contract=off, like the oracle) the first time it is needed, in a temporary directory.  Threads split the rows; every pixel is still
+summed in sample order."""
+import ctypes as C
+import os
+import subprocess
+import tempfile
+
+import numpy as np
+
+import emit_reference as emr
+import rtp_bindings as rb
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+_lib = None
+COLUMNS = ("sphere", "weight", "q", "left", "right", "entry", "path", "depth")
+
+
+class TreeCfg(C.Structure):
+    """tree_ref.c's tree_cfg."""
+    _fields_ = [("base", emr.EmitCfg), ("select", C.c_int32)]
+
+
+def lib():
+    global _lib
+    if _lib is None:
+        out = os.path.join(tempfile.mkdtemp(prefix="tree_ref_"), "libtree_ref.so")
+        subprocess.run(["gcc", "-O2", "-std=gnu11", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-w", "-o", out,
+                        os.path.join(HERE, "cpu_native", "tree_ref.c"), "-lm", "-lpthread"], check=True)
+        l = C.CDLL(out)
+        desc, cam, cfg = C.POINTER(rb.SceneDesc), C.POINTER(rb.CameraData), C.POINTER(TreeCfg)
+        l.tree_columns.restype = C.c_int32
+        l.tree_columns.argtypes = [desc, C.c_int32] + [C.c_void_p] * 8 + [C.POINTER(C.c_int32)]
+        l.tree_pmf_points.restype = None
+        l.tree_pmf_points.argtypes = [desc, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]
+        l.tree_pick_counts.restype = C.c_int64
+        l.tree_pick_counts.argtypes = [desc, C.c_int32, C.c_void_p, C.c_int64, C.c_uint32, C.c_void_p]
+        l.tree_trace.restype = None
+        l.tree_trace.argtypes = [desc, cam, cfg, C.c_int64] + [C.c_void_p] * 6 + [C.c_int32, C.c_void_p]
+        l.tree_frame.restype = None
+        l.tree_frame.argtypes = [desc, cam, cfg, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        _lib = l
+    return _lib
+
+
+def tree(host, planes=0):
+    """The tree over the table of sample_planes = planes: a dict of the columns DeviceScene.nee_light_tree returns."""
+    cap = 2 * (host.desc.num_spheres + host.desc.num_planes) + 1
+    t = {"sphere": np.zeros((cap, 4), np.float32), "weight": np.zeros(cap, np.float32), "q": np.zeros(cap, np.float32),
+         "left": np.zeros(cap, np.int32), "right": np.zeros(cap, np.int32), "entry": np.zeros(cap, np.int32),
+         "path": np.zeros(cap, np.uint32), "depth": np.zeros(cap, np.int32)}
+    ne = C.c_int32()
+    nn = lib().tree_columns(C.byref(host.desc), planes, *(t[k].ctypes.data for k in COLUMNS), C.byref(ne))
+    return {k: (v[:ne.value] if k in ("path", "depth") else v[:nn]).copy() for k, v in t.items()}
+
+
+def pmf(host, points, planes=0):
+    """pmf_e(x) by the path product: points (m, 3) → (m, N) float32."""
+    points = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+    n = len(emr.table(host, planes)[0])
+    out = np.zeros((points.shape[0], n), np.float32)
+    lib().tree_pmf_points(C.byref(host.desc), planes, points.shape[0], points.ctypes.data, out.ctypes.data)
+    return out
+
+
+def pick_counts(host, point, draws, seed, planes=0):
+    """`draws` picks from one point → (counts (N,) int64, how many picks' p was not their entry's path product bit for bit)."""
+    point = np.ascontiguousarray(point, dtype=np.float32)
+    counts = np.zeros(len(emr.table(host, planes)[0]), np.int64)
+    bad = lib().tree_pick_counts(C.byref(host.desc), planes, point.ctypes.data, draws, seed, counts.ctypes.data)
+    return counts, bad
+
+
+def _cfg(select, cam_close, lens, emitters, nee_mis, planes, rgb, env_params):
+    base, keep = emr._cfg(cam_close, lens, emitters, nee_mis, planes, rgb, env_params)
+    c = TreeCfg()
+    c.base = base
+    c.select = select
+    return c, keep
+
+
+def trace(host, cam, ijs, select=1, cam_close=None, lens=None, emitters=True, nee_mis=1, planes=0, rgb=None, env_params=None, linear=True, stats=False):
+    """emit_reference.trace with the pick by select.  stats=True adds (sampling vertices inside the sphere of their picked leaf's parent,
+    weighted BSDF hits on table entries)."""
+    c, keep = _cfg(select, cam_close, lens, emitters, nee_mis, planes, rgb, env_params)
+    ijs = np.ascontiguousarray(ijs, dtype=np.int32).reshape(-1, 3)
+    m = ijs.shape[0]
+    rad, rays = np.empty((m, 3), np.float32), np.empty(m, np.int32)
+    seeds, nee, env = np.empty(m, np.uint32), np.empty(m, np.uint32), np.empty(m, np.uint32)
+    st = np.zeros(2, np.int64)
+    lib().tree_trace(C.byref(host.desc), C.byref(cam), C.byref(c), m, ijs.ctypes.data, rad.ctypes.data, rays.ctypes.data, seeds.ctypes.data,
+                     nee.ctypes.data, env.ctypes.data, 1 if linear else 0, st.ctypes.data)
+    return (rad, rays, seeds, nee, env) + ((tuple(int(x) for x in st),) if stats else ())
+
+
+def frame(host, cam, select=1, cam_close=None, lens=None, emitters=True, nee_mis=1, planes=0, rgb=None, env_params=None, shard=None, sample_first=0,
+          threads=16, moments=False):
+    """emit_reference.frame with the pick by select."""
+    c, keep = _cfg(select, cam_close, lens, emitters, nee_mis, planes, rgb, env_params)
+    rows = np.asarray(emr.image_rows(cam, shard), dtype=np.int32)
+    fb = np.zeros((len(rows), cam.image_width, 3), np.float32)
+    mom = np.zeros((len(rows), cam.image_width, 6), np.float64) if moments else None
+    lib().tree_frame(C.byref(host.desc), C.byref(cam), C.byref(c), rows.ctypes.data, len(rows), sample_first, threads, fb.ctypes.data,
+                     mom.ctypes.data if moments else None)
+    return (fb, mom) if moments else fb
