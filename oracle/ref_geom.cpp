@@ -1,13 +1,12 @@
 /*
- * ref_geom.cpp — TEST INFRASTRUCTURE.  Harness around the part of the reference's OWN hot-path headers that compiles in this
- * image without any stand-in: include/vec3.h, ray.h, interval.h, aabb.h, hittable_object.h, sphere.h, plane.h, bvh.h and
+ * ref_geom.cpp — TEST INFRASTRUCTURE.  Harness around the part of the reference's OWN hot-path headers that needs nothing but the
+ * C++ library and ROCm's runtime header: include/vec3.h, ray.h, interval.h, aabb.h, hittable_object.h, sphere.h, plane.h, bvh.h and
  * bvh_builder.h, #included from where they lie under /root/reference (never copied into this repo) and compiled by
  * `hipcc -x hip --cuda-host-only` (the headers say __host__ __device__; only the host side is built and run).  The one thing
  * they need beyond the C++ library — `__align__(16)` on SphereData / PlaneData, which nvcc's implicit cuda_runtime.h supplies —
- * comes from ROCm's own <hip/hip_runtime.h> (amd_hip_runtime.h defines it), included below: a header this image HAS, nothing
- * written for the purpose.  random_utils.h and materials.h (#include <curand_kernel.h>) and camera.cuh (<cuda_runtime.h>) do not
- * compile here and are NOT part of this: the RNG, the materials and the camera stay pinned by SURVEY-session records only
- * (DESIGN.md §2).
+ * comes from ROCm's own <hip/hip_runtime.h> (amd_hip_runtime.h defines it), included below.  random_utils.h and materials.h
+ * (#include <curand_kernel.h>), camera.cuh (<cuda_runtime.h>) and src/camera.cu are the other harness, oracle/ref_shade.cpp, which
+ * finds those two vendor SDK headers as the alias headers oracle/shim/ (DESIGN.md §2).
  *
  * What it exposes, in batches (n items per call, plain C arrays): AABB::hit (include/aabb.h:42-65), the AABB constructors with
  * expand_to_min (:14-33, :92-97), vec3 operator/ and unit_vector (include/vec3.h:97,105), reflect / refract / near_zero / dot /

@@ -273,27 +273,37 @@ int orc_closest_hit(const rt_scene_desc *scene, const float origin[3], const flo
     return h;
 }
 
-int orc_closest_hit_bruteforce(const rt_scene_desc *sc, const float origin[3], const float dir[3],
-                               float *t, int *prim_type, int *prim_index) {
-    ray r;
-    memcpy(r.o.e, origin, 12);
-    memcpy(r.d.e, dir, 12);
+/* every leaf in node order, with hit_bvh's own leaf-box gate and primitive tests */
+static int bruteforce_hit(const rt_scene_desc *sc, const ray *r, float *t, int *prim_type, int *prim_index) {
     float closest = 1e30f;
     int found = 0;
     for (int n = 0; n < sc->num_nodes; n++) {
         const rt_bvh_node *node = &sc->nodes[n];
         if (node->left >= 0) continue;
-        if (!aabb_hit(node->box, &r, 0.001f, closest)) continue;
+        if (!aabb_hit(node->box, r, 0.001f, closest)) continue;
         hitrec tmp;
         int hit = 0;
-        if (node->type == 0) hit = hit_sphere(&r, 0.001f, closest, &tmp, &sc->spheres[node->right]);
-        else if (node->type == 1) hit = hit_plane(&r, 0.001f, closest, &tmp, &sc->planes[node->right]);
+        if (node->type == 0) hit = hit_sphere(r, 0.001f, closest, &tmp, &sc->spheres[node->right]);
+        else if (node->type == 1) hit = hit_plane(r, 0.001f, closest, &tmp, &sc->planes[node->right]);
         if (hit) { found = 1; closest = tmp.t; *t = tmp.t; *prim_type = node->type; *prim_index = node->right; }
     }
     return found;
 }
+int orc_closest_hit_bruteforce(const rt_scene_desc *sc, const float origin[3], const float dir[3],
+                               float *t, int *prim_type, int *prim_index) {
+    ray r;
+    memcpy(r.o.e, origin, 12);
+    memcpy(r.d.e, dir, 12);
+    return bruteforce_hit(sc, &r, t, prim_type, prim_index);
+}
 
 /* ---- texture: include/materials.h:20-51 ------------------------------------------------------ */
+/* orc_shade_* bookkeeping (per thread): fetches in which the x0 / y0 wrap below changed an index, i.e. where the reference reads
+ * outside its rows; and, while order_check is set, path rays whose closest hit depends on the order leaves are visited in. */
+static __thread uint64_t tex_wraps;
+static __thread int order_check;
+static __thread uint64_t order_sensitive;
+
 void orc_tex2d(const rt_texture *tex, float u, float v, float rgb[3]) {
     if (!tex || !tex->rgba) { rgb[0] = rgb[1] = rgb[2] = 1; return; }
     u = u - floorf(u);
@@ -309,6 +319,7 @@ void orc_tex2d(const rt_texture *tex, float u, float v, float rgb[3]) {
     /* deviation: the reference indexes x0,y0 unwrapped and reads past the row/image when
      * u or v lands exactly on 1.0; wrap them instead of reading out of bounds. */
     int x0w = x0 % tex->width, y0w = y0 % tex->height;
+    if (x0w != x0 || y0w != y0) tex_wraps++;
     const float *d = tex->rgba;
     int W = tex->width;
 #define PX(x, y) V(d[((y) * W + (x)) * 4], d[((y) * W + (x)) * 4 + 1], d[((y) * W + (x)) * 4 + 2])
@@ -405,6 +416,11 @@ static v3 ray_color(ray r, uint32_t *seed, const rt_scene_desc *sc, const rt_cam
         nrays++;
         if (st) st->rays++;
         int h = sc->num_nodes > 0 ? hit_bvh(sc, &cur, 0.001f, 1e30f, &rec, &pt, &pi, st) : 0;
+        if (order_check) {   /* only under orc_shade_trace_samples: a path's rays exist only here, and a second copy of this loop could drift */
+            float bt = 0;
+            int bpt = -1, bpi = -1, bh = bruteforce_hit(sc, &cur, &bt, &bpt, &bpi);
+            if (bh != h || (h && (memcmp(&bt, &rec.t, 4) != 0 || bpt != pt || bpi != pi))) order_sensitive++;
+        }
         if (!h) {
             final_color = add(final_color, mulv(beta, from_rt(cam->background)));
             break;
@@ -598,5 +614,87 @@ void orc_geom_hit_bvh(const rt_scene_desc *scene, int64_t n, const float *origin
         int pt = -1, pi = -1;
         out_hit[k] = scene->num_nodes > 0 ? hit_bvh(scene, &r, tmin, tmax, &rec, &pt, &pi, NULL) : 0;
         if (out_hit[k]) put_rec(out_rec9 + 9 * k, out_code + k, &rec, 2 * pi + pt);
+    }
+}
+
+/* ---- batched views of the RNG, the materials, the camera and the saver, for tests/test_ref_shade.py ------------------------------
+ * The same calls, on the same arrays, as oracle/ref_shade.cpp makes on the reference's own random_utils.h / materials.h /
+ * camera.cuh / src/camera.cu: loops over the static functions orc_render itself runs.  Nothing here computes anything new. */
+void orc_shade_wang_hash(int64_t n, const uint32_t *in, uint32_t *out) {
+    for (int64_t k = 0; k < n; ++k) out[k] = orc_wang_hash(in[k]);
+}
+void orc_shade_random_float(int64_t n, const uint32_t *seeds, float *out, uint32_t *out_seeds) {
+    for (int64_t k = 0; k < n; ++k) { uint32_t s = seeds[k]; out[k] = orc_random_float(&s); out_seeds[k] = s; }
+}
+void orc_shade_random_range(int64_t n, const uint32_t *seeds, const float *lo, const float *hi, float *out, uint32_t *out_seeds) {
+    for (int64_t k = 0; k < n; ++k) { uint32_t s = seeds[k]; out[k] = random_range(&s, lo[k], hi[k]); out_seeds[k] = s; }
+}
+void orc_shade_random_pm1(int64_t n, const uint32_t *seeds, float *out, uint32_t *out_seeds) {
+    for (int64_t k = 0; k < n; ++k) { uint32_t s = seeds[k]; out[k] = random_range(&s, -1.0, 1.0); out_seeds[k] = s; }
+}
+void orc_shade_random_in_unit_sphere(int64_t n, const uint32_t *seeds, float *out, uint32_t *out_seeds) {
+    for (int64_t k = 0; k < n; ++k) { uint32_t s = seeds[k]; v3 r = random_in_unit_sphere(&s); memcpy(out + 3 * k, r.e, 12); out_seeds[k] = s; }
+}
+void orc_shade_random_unit_vector(int64_t n, const uint32_t *seeds, float *out, uint32_t *out_seeds) {
+    for (int64_t k = 0; k < n; ++k) { uint32_t s = seeds[k]; v3 r = random_unit_vector(&s); memcpy(out + 3 * k, r.e, 12); out_seeds[k] = s; }
+}
+void orc_shade_random_in_hemisphere(int64_t n, const uint32_t *seeds, const float *normals, float *out, uint32_t *out_seeds) {
+    for (int64_t k = 0; k < n; ++k) {
+        uint32_t s = seeds[k];
+        v3 r = random_in_hemisphere(V(normals[3 * k], normals[3 * k + 1], normals[3 * k + 2]), &s);
+        memcpy(out + 3 * k, r.e, 12); out_seeds[k] = s;
+    }
+}
+void orc_shade_reflectance(int64_t n, const float *cosine, const float *ref_idx, float *out) {
+    for (int64_t k = 0; k < n; ++k) out[k] = reflectance(cosine[k], ref_idx[k]);
+}
+/* material_scatter with the material's own albedo; attenuation and the scattered ray are written only where it returns 1 */
+void orc_shade_material_scatter(int64_t n, const float *ray_o, const float *ray_d, const float *point, const float *normal, const int32_t *front,
+                                const rt_material *mats, const uint32_t *seeds, int32_t *out_ret, float *out_att, float *out_o, float *out_d,
+                                uint32_t *out_seeds) {
+    for (int64_t k = 0; k < n; ++k) {
+        ray r = ray_of(ray_o + 3 * k, ray_d + 3 * k), scattered;
+        hitrec rec;
+        memset(&rec, 0, sizeof(rec));
+        memset(&scattered, 0, sizeof(scattered));
+        memcpy(rec.point.e, point + 3 * k, 12);
+        memcpy(rec.normal.e, normal + 3 * k, 12);
+        rec.front_face = front[k] != 0;
+        v3 att = V(0, 0, 0);
+        uint32_t s = seeds[k];
+        out_ret[k] = material_scatter(&r, &rec, &att, &scattered, &s, &mats[k], from_rt(mats[k].albedo));
+        out_seeds[k] = s;
+        if (out_ret[k]) { memcpy(out_att + 3 * k, att.e, 12); memcpy(out_o + 3 * k, scattered.o.e, 12); memcpy(out_d + 3 * k, scattered.d.e, 12); }
+    }
+}
+void orc_shade_material_emit(int64_t n, const rt_material *mats, float *out) {
+    for (int64_t k = 0; k < n; ++k) { v3 e = from_rt(mats[k].emit); memcpy(out + 3 * k, e.e, 12); }
+}
+/* orc_tex2d; out_wrapped[k] = 1 where the x0 / y0 wrap fired (the reference reads outside its rows there) */
+void orc_shade_tex2d(const rt_texture *tex, int64_t n, const float *u, const float *v, float *out, int32_t *out_wrapped) {
+    for (int64_t k = 0; k < n; ++k) {
+        const uint64_t before = tex_wraps;
+        orc_tex2d(tex, u[k], v[k], out + 3 * k);
+        out_wrapped[k] = tex_wraps != before;
+    }
+}
+void orc_shade_get_ray(int64_t n, const rt_camera_data *cams, const int32_t *ij, const uint32_t *seeds, float *out_o, float *out_d, uint32_t *out_seeds) {
+    for (int64_t k = 0; k < n; ++k) { uint32_t s = seeds[k]; orc_get_ray(&cams[k], ij[2 * k], ij[2 * k + 1], &s, out_o + 3 * k, out_d + 3 * k); out_seeds[k] = s; }
+}
+void orc_shade_write_color(int64_t n, const float *sums, int32_t spp, uint8_t *out) {
+    for (int64_t k = 0; k < n; ++k) orc_write_color(sums + 3 * k, spp, out + 3 * k);
+}
+/* orc_trace_sample for n samples (i, j, s).  out_flags[k]: bit 0 = a texture fetch of the sample wrapped (the reference reads outside
+ * its rows there), bit 1 = one of its rays has a closest hit that depends on the order of the visit (brute force over the leaves
+ * disagrees with hit_bvh: an exact tie, where the reference's own out-of-bounds child-order read decides). */
+void orc_shade_trace_samples(const rt_scene_desc *scene, const rt_camera_data *cam, int64_t n, const int32_t *ijs, float *out_rad,
+                             uint32_t *out_seeds, int32_t *out_flags) {
+    for (int64_t k = 0; k < n; ++k) {
+        const uint64_t wraps = tex_wraps;
+        order_check = 1;
+        order_sensitive = 0;
+        orc_trace_sample(scene, cam, ijs[3 * k], ijs[3 * k + 1], ijs[3 * k + 2], out_rad + 3 * k, NULL, out_seeds + k);
+        order_check = 0;
+        out_flags[k] = (tex_wraps != wraps ? 1 : 0) | (order_sensitive ? 2 : 0);
     }
 }

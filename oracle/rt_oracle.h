@@ -5,16 +5,15 @@
  * tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg.  Nothing under
  * ray-tracing-practice_amd/ may include, link or call it.
  *
- * Pinning.  What of the reference compiles here from its own sources without a stand-in is compiled
- * (oracle/Makefile target `_ref`) and compared with this restatement bit for bit: its vec3 / ray / interval / aabb /
+ * Pinning.  The reference's hot path is compiled from its own sources, where they lie
+ * (oracle/Makefile target `_ref`), and compared with this restatement bit for bit: its vec3 / ray / interval / aabb /
  * hittable_object / sphere / plane / bvh / bvh_builder headers behind oracle/ref_geom.cpp (tests/test_ref_geom.py: AABB::hit,
  * the vector algebra, hit_sphere, hit_plane, hit_bvh, build_bvh — a million crafted and random inputs, plus a recorded fixture
- * that runs everywhere), and its vendored stb_image.h behind oracle/ref_stb_decode.c.  random_utils.h, materials.h
- * (<curand_kernel.h>) and camera.cuh (<cuda_runtime.h>) do not compile in this image and stand-ins are not allowed: the RNG,
- * material_scatter, get_ray / build_camera_data and the frame loop are pinned only by the known answers SURVEY.md §4 recorded
- * from the reference's own CPU path (wang_hash / random_float vectors, the CameraData of the create_test_config.py scene, the
- * sha256 of two whole BinarySaver files) — tests/test_oracle_pins.py.  By the rule that makes the oracle as a whole
- * "parity unpinned": those records are not fixtures the reference holds.
+ * that runs everywhere), its vendored stb_image.h behind oracle/ref_stb_decode.c, and its random_utils.h, materials.h, camera.cuh and
+ * src/camera.cu behind oracle/ref_shade.cpp (tests/test_ref_shade.py: the RNG, reflectance, material_scatter, tex2D_cpu, get_ray,
+ * build_camera_data, writeColor, ray_color_host per sample and render_cpu frames; <curand_kernel.h> and <cuda_runtime.h> are the
+ * alias headers oracle/shim/).  src/main.cu — config parsing, texture loading, the frame loop's camera path — is not compiled: there
+ * the known answers SURVEY.md §4 recorded from the reference's own CPU path remain the only pin (tests/test_oracle_pins.py).
  *
  * Data layouts are the reference's own (include/rtp_amd.h documents offsets and cites them).
  */
@@ -94,6 +93,30 @@ void orc_geom_hit_plane(int64_t n, const float *origins, const float *dirs, cons
                         int32_t *out_hit, float *out_rec9, int32_t *out_code);
 void orc_geom_hit_bvh(const rt_scene_desc *scene, int64_t n, const float *origins, const float *dirs, float tmin, float tmax,
                       int32_t *out_hit, float *out_rec9, int32_t *out_code);
+
+/* Batched views of the RNG, materials, camera and saver restatements (wang_hash, random_float in both forms, random_in_unit_sphere /
+ * _unit_vector / _in_hemisphere, reflectance, material_scatter, the emission, orc_tex2d, orc_get_ray, orc_write_color,
+ * orc_trace_sample) with the argument lists of oracle/ref_shade.cpp — the same calls made on the reference's own random_utils.h,
+ * materials.h, camera.cuh and src/camera.cu; tests/test_ref_shade.py compares the two bit for bit.  Loops over the functions
+ * orc_render runs, never copies of them. */
+void orc_shade_wang_hash(int64_t n, const uint32_t *in, uint32_t *out);
+void orc_shade_random_float(int64_t n, const uint32_t *seeds, float *out, uint32_t *out_seeds);
+void orc_shade_random_range(int64_t n, const uint32_t *seeds, const float *lo, const float *hi, float *out, uint32_t *out_seeds);
+void orc_shade_random_pm1(int64_t n, const uint32_t *seeds, float *out, uint32_t *out_seeds);      /* (seed, -1.0, 1.0) */
+void orc_shade_random_in_unit_sphere(int64_t n, const uint32_t *seeds, float *out, uint32_t *out_seeds);
+void orc_shade_random_unit_vector(int64_t n, const uint32_t *seeds, float *out, uint32_t *out_seeds);
+void orc_shade_random_in_hemisphere(int64_t n, const uint32_t *seeds, const float *normals, float *out, uint32_t *out_seeds);
+void orc_shade_reflectance(int64_t n, const float *cosine, const float *ref_idx, float *out);
+void orc_shade_material_scatter(int64_t n, const float *ray_o, const float *ray_d, const float *point, const float *normal, const int32_t *front,
+                                const rt_material *mats, const uint32_t *seeds, int32_t *out_ret, float *out_att, float *out_o, float *out_d,
+                                uint32_t *out_seeds);
+void orc_shade_material_emit(int64_t n, const rt_material *mats, float *out);
+void orc_shade_tex2d(const rt_texture *tex, int64_t n, const float *u, const float *v, float *out, int32_t *out_wrapped);
+void orc_shade_get_ray(int64_t n, const rt_camera_data *cams, const int32_t *ij, const uint32_t *seeds, float *out_o, float *out_d, uint32_t *out_seeds);
+void orc_shade_write_color(int64_t n, const float *sums, int32_t spp, uint8_t *out);
+/* out_flags: bit 0 a texture fetch wrapped where the reference reads outside its rows, bit 1 a closest hit depended on visit order */
+void orc_shade_trace_samples(const rt_scene_desc *scene, const rt_camera_data *cam, int64_t n, const int32_t *ijs, float *out_rad,
+                             uint32_t *out_seeds, int32_t *out_flags);
 
 #ifdef __cplusplus
 }

@@ -1,14 +1,14 @@
 """The oracle's geometry against the REFERENCE'S OWN HEADERS (oracle/ref_geom.cpp → oracle/_ref/libref_geom.so, built from where
-they lie, build container only): vec3 / ray / interval / aabb / hittable_object / sphere / plane / bvh / bvh_builder — everything
-of the hot path that compiles in this image without a stand-in.  Bit for bit, on crafted extremes (zeros, ±inf reciprocals, NaN
+they lie, build container only): vec3 / ray / interval / aabb / hittable_object / sphere / plane / bvh / bvh_builder — the geometry
+half of the hot path.  Bit for bit, on crafted extremes (zeros, ±inf reciprocals, NaN
 planes, denormals, exact interval ends) and random values.
 
 The reference's side is also recorded (tests/golden/make_ref_geom_golden.py): per-output sha256 digests of what the library
 returns on the full runs (tests/golden/ref_geom_digests.json), and the outputs themselves on a smaller set
 (tests/golden/ref_geom.npz).  The oracle is checked against the recordings everywhere, and item by item against the library
 where it is built.
-Not covered, because it does not compile here (<curand_kernel.h>, <cuda_runtime.h>): random_utils.h, materials.h, camera.cuh —
-the RNG, the materials and the camera stay pinned by SURVEY-session records only (tests/test_oracle_pins.py).
+Not covered here: random_utils.h, materials.h, camera.cuh and src/camera.cu — the RNG, the materials, the camera, the saver and the
+path loop are compared with the reference's own code by tests/test_ref_shade.py (oracle/ref_shade.cpp).
 """
 import ctypes as C
 import json
