@@ -829,6 +829,46 @@ rt_status rt_render_lit(rt_scene *scene, const rt_camera_data *cam_open, const r
 rt_status rt_trace_samples_lit(rt_scene *scene, const rt_camera_data *cam_open, const rt_lit_params *lit, int32_t n, const int32_t *ijs,
                                float *radiance, int32_t *rays, uint32_t *final_seed, uint32_t *final_nee_seed, uint32_t *final_env_seed);
 
+/* ---- adaptive sampling on the lit path ----------------------------------------------------------------------------
+ * rt_render_adaptive's rounds on rt_render_lit's estimator.  No new arithmetic: the sample is the section above's, the statistics and
+ * the rule are the adaptive section's, float32 in the order written there, nothing fused; this section fixes the composition only.
+ *
+ * Per-pixel parity.  Pixel p receives n_p samples, namely samples sample_first … sample_first + n_p - 1 of rt_render_lit's estimator
+ * under the same lit — the lens and shutter, the emitter table with mis, sample_planes and select, the environment with its mode — and
+ * d_fb_sum[p] equals, bit for bit, pixel p of rt_render_lit with samples_per_pixel = n_p and the same sample_first: the sum added in
+ * sample order, starting from 0.  d_spp[p] = n_p, and n_p is min_spp + k * batch_spp for some k >= 0 with n_p <= max_spp.
+ * cam_open->samples_per_pixel is ignored (cam_close, when given, still has to agree with cam_open in it).
+ *
+ * Statistics and rule: rt_render_adaptive's, from rt_adaptive_params.  y = (0.2126f*r + 0.7152f*g) + 0.0722f*b of the radiance
+ * (r, g, b) rt_render_lit adds for the sample — its light-sample contributions and MIS weights included; S1 += y, S2 += y*y, float32,
+ * from 0, in sample order; goes_on(S1, S2, n) as written there, judged after the min_spp samples and after every round but the last of
+ * R = (max_spp - min_spp) / batch_spp.  d_moments (may be NULL) receives (S1, S2) per pixel.
+ *
+ * Identities, bit for bit: threshold = 0 gives rt_render_lit at min_spp + R * batch_spp samples, every count equal to that;
+ * sample_emitters = 0, env == NULL, no lens, no motion and sample_first = 0 give rt_render_adaptive's d_fb_sum, d_spp and d_moments.
+ *
+ * Checks, all before anything is enqueued, in this order: (1) rt_render_adaptive's parameter checks with its codes (params NULL is
+ * refused; lit NULL means the defaults); (2) rt_render_lit's — lens, then nee when sample_emitters != 0, then env_params when
+ * env != NULL; (3) RT_ERR_INVALID_ARG for sample_first < 0 and RT_ERR_UNSUPPORTED for sample_first + min_spp + R * batch_spp above
+ * 2^30; (4) RT_ERR_INVALID_ARG for d_fb_sum or d_spp NULL; (5) the scene's and the camera's, as rt_render_lit; (6) RT_ERR_UNSUPPORTED
+ * for pixels x batch_spp at or above 2^31 - 4096 when R > 0.  Rows of a shard only: no tiles, no rt_context.
+ *
+ * Work.  All R rounds are enqueued up front; which pixels go on, and how many, lives on the device only, and a round whose list is
+ * empty costs a few empty launches.  With sync == 0 the call only enqueues (it may wait for the stream once, when it grows the
+ * handle's buffers).  max_depth <= 0: zero sums and moments, the counts by the rule (min_spp, or min_spp + R * batch_spp when
+ * threshold = 0).
+ * Handle state: as rt_render_lit — the walk choice, a pause of the guarded walk, the view lists and rt_last_timing are left alone; the
+ * emitter tables and light trees are the handle's, built by whichever call comes first.  The moments, lists, work indices and counters
+ * are rt_render_adaptive's handle buffers: a handle renders one frame at a time.
+ * timing (may be NULL) is this call's record: kernel_ms from the first to the last kernel of the call (sync != 0), trace_launches =
+ * the min_spp frame's passes + R, num_workgroups = the grid of the rounds' trace launches when R > 0 and the min_spp frame's first
+ * pass's otherwise, traced_samples = pixels x min_spp (the rest is the sum of d_spp, which the caller has), guarded = 0.
+ * d_fb_sum: 3 floats per pixel, d_spp: 1 int32 per pixel, d_moments: NULL or 2 floats per pixel — DEVICE memory, compacted like
+ * rt_render's buffer.  rt_tonemap_spp turns the frame into bytes. */
+rt_status rt_render_lit_adaptive(rt_scene *scene, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_adaptive_params *params,
+                                 const rt_shard *shard, int32_t sample_first, float *d_fb_sum, int32_t *d_spp, float *d_moments,
+                                 void *hip_stream, int32_t sync, rt_timing *timing);
+
 /* Milliseconds of the most recent rt_render kernel of this scene (waits for it). */
 rt_status rt_last_kernel_ms(rt_scene *scene, float *ms);
 /* The whole rt_timing of the most recent rt_render of this scene (waits for it). */

@@ -1816,18 +1816,24 @@ void adaptive_defaults(rt_adaptive_params &p) {
     p.max_spp = 256;
     p.threshold = 0.02f;
 }
+// the parameter checks of rt_render_adaptive and rt_render_lit_adaptive (what: the call's name) → a: the caller's fields over the defaults
+rt_status adaptive_check(const char *what, const rt_adaptive_params *params, rt_adaptive_params &a) {
+    const std::string w(what);
+    if (!params || params->struct_bytes < 8) return fail(RT_ERR_INVALID_ARG, w + ": null params (or struct_bytes below 8)");
+    adaptive_defaults(a);
+    std::memcpy(&a, params, params->struct_bytes < sizeof(a) ? params->struct_bytes : sizeof(a));
+    if (a.min_spp < 2) return fail(RT_ERR_INVALID_ARG, w + ": min_spp below 2");
+    if (a.batch_spp < 1) return fail(RT_ERR_INVALID_ARG, w + ": batch_spp below 1");
+    if (a.max_spp < a.min_spp) return fail(RT_ERR_INVALID_ARG, w + ": max_spp below min_spp");
+    if (!(a.threshold >= 0.0f) || !std::isfinite(a.threshold)) return fail(RT_ERR_INVALID_ARG, w + ": threshold negative, NaN or infinite");
+    if (a.max_spp > 65536) return fail(RT_ERR_UNSUPPORTED, w + ": max_spp above 65536");
+    return RT_OK;
+}
 rt_status adaptive_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shard, const rt_adaptive_params *params, float *d_fb_sum,
                         int32_t *d_spp, float *d_moments, void *hip_stream, int32_t sync, rt_timing *timing) {
     // ---- 1. every check before anything is enqueued
-    if (!params || params->struct_bytes < 8) return fail(RT_ERR_INVALID_ARG, "rt_render_adaptive: null params (or struct_bytes below 8)");
     rt_adaptive_params a;
-    adaptive_defaults(a);
-    std::memcpy(&a, params, params->struct_bytes < sizeof(a) ? params->struct_bytes : sizeof(a));
-    if (a.min_spp < 2) return fail(RT_ERR_INVALID_ARG, "rt_render_adaptive: min_spp below 2");
-    if (a.batch_spp < 1) return fail(RT_ERR_INVALID_ARG, "rt_render_adaptive: batch_spp below 1");
-    if (a.max_spp < a.min_spp) return fail(RT_ERR_INVALID_ARG, "rt_render_adaptive: max_spp below min_spp");
-    if (!(a.threshold >= 0.0f) || !std::isfinite(a.threshold)) return fail(RT_ERR_INVALID_ARG, "rt_render_adaptive: threshold negative, NaN or infinite");
-    if (a.max_spp > 65536) return fail(RT_ERR_UNSUPPORTED, "rt_render_adaptive: max_spp above 65536");
+    if (const rt_status cs = adaptive_check("rt_render_adaptive", params, a)) return cs;
     if (!cam) return fail(RT_ERR_INVALID_ARG, "null scene or camera");
     rt_camera_data base = *cam;
     base.samples_per_pixel = a.min_spp;
@@ -1939,6 +1945,40 @@ rt_status adaptive_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard 
 //   light_device: the device of a light that is an object of its own (null: the light is the handle's);
 //   make_light(T, kernel): fills the kernel's second argument, once the call is known to trace — and may name another kernel for it (a
 //   Light that is a union of two table types: which one the handle's emitter table needs is known only then)
+// Workgroups per CU of a lit trace kernel as the loaded code object allows, and the grid of a launch on `work` work indices: what fills
+// the device, fewer where the work does not give every wave a chunk
+int light_wgs_per_cu(const void *kernel) {
+    int per_cu = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, rtk::kLightBlock, 0) != hipSuccess || per_cu < 1) {
+        (void)hipGetLastError();
+        per_cu = 1;
+    }
+    return per_cu;
+}
+int light_grid(int wgs, uint32_t work) {
+    const int waves_per_wg = rtk::kLightBlock / rtk::kWave;
+    const uint32_t need = (work + rtk::kLightChunk - 1) / rtk::kLightChunk;          // waves that can get work at all
+    int grid = wgs;
+    if ((uint64_t)grid * waves_per_wg > need) grid = (int)((need + waves_per_wg - 1) / waves_per_wg);
+    return grid < 1 ? 1 : grid;
+}
+// The passes of a light frame: each pass's trace launch (kernel on P, light and — rt_render_lit's kernels — lens; its work counter is
+// queue[pass]) and its accumulate.  moments (rt_render_lit_adaptive's min_spp frame; null for every other call): each pass's luminance
+// moments are added there as well — every pixel of a light frame has a slab row.  first_grid: the first pass's workgroups.
+rt_status light_passes(const void *kernel, const void *light, const rtk::LensCam *lens, rtk::KParams &P, const rtaccel::PassPlan &passes, uint32_t num_pixels,
+                       int32_t sample_first, int wgs, uint32_t *queue, hipStream_t stream, float *moments, uint32_t &first_grid) {
+    for (int pass = 0; pass < passes.passes; ++pass) {
+        if (const rt_status st = set_pass(P, passes, pass, num_pixels, sample_first)) return st;
+        P.queue = queue + pass;
+        const int grid = light_grid(wgs, P.total_work);
+        HIP_TRY(launch(kernel, (uint32_t)rtk::kLightBlock, grid, 0, stream, P, light, lens));
+        launch_accumulate(stream, P, Acc::every_pixel(pass));
+        if (moments) launch_moments(stream, moments, P, pass == 0 ? 1 : 0);
+        HIP_TRY(hipGetLastError());
+        if (pass == 0) first_grid = (uint32_t)grid;
+    }
+    return RT_OK;
+}
 template <class Light, class MakeLight>
 rt_status render_light_impl(const char *what, const void *trace, const int *light_device, MakeLight make_light, rt_scene *sc,
                             const rt_camera_data *cam, const rt_shard *shard, int32_t sample_first, float *d_fb_sum, void *hip_stream, int32_t sync,
@@ -1959,11 +1999,7 @@ rt_status render_light_impl(const char *what, const void *trace, const int *ligh
     rtaccel::PassPlan passes;
     if ((st = reserve_slab(sc, num_pixels, P.spp, stream, passes)) != RT_OK) return st;
     bind_slab(sc, P, num_pixels, passes.pass_size);          // (no candidate lists: fill_params left P.cand and P.order null)
-    int per_cu = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, rtk::kLightBlock, 0) != hipSuccess || per_cu < 1) {
-        (void)hipGetLastError();
-        per_cu = 1;
-    }
+    const int per_cu = light_wgs_per_cu(kernel);
     rt_timing t{};
     kernel_resources(kernel, t.trace_vgprs, t.trace_scratch_bytes);
     // (a clock and work counters of the lit calls' own, one per pass — one set: a handle renders one frame at a time)
@@ -1971,20 +2007,8 @@ rt_status render_light_impl(const char *what, const void *trace, const int *ligh
     if ((st = clock.make(kMaxPasses)) != RT_OK) return st;
     HIP_TRY(hipMemsetAsync(clock.words, 0, kMaxPasses * 4, stream));
     if ((st = clock.start(stream)) != RT_OK) return st;
-    const int wgs = sc->num_cus * per_cu;
-    const int waves_per_wg = rtk::kLightBlock / rtk::kWave;
-    for (int pass = 0; pass < passes.passes; ++pass) {
-        if ((st = set_pass(P, passes, pass, num_pixels, sample_first)) != RT_OK) return st;
-        P.queue = clock.words + pass;
-        const uint32_t need = (P.total_work + rtk::kLightChunk - 1) / rtk::kLightChunk;          // waves that can get work at all
-        int grid = wgs;
-        if ((uint64_t)grid * waves_per_wg > need) grid = (int)((need + waves_per_wg - 1) / waves_per_wg);
-        if (grid < 1) grid = 1;
-        HIP_TRY(launch(kernel, (uint32_t)rtk::kLightBlock, grid, 0, stream, P, &T, lens));
-        launch_accumulate(stream, P, Acc::every_pixel(pass));
-        HIP_TRY(hipGetLastError());
-        if (pass == 0) t.num_workgroups = (uint32_t)grid;
-    }
+    if ((st = light_passes(kernel, &T, lens, P, passes, num_pixels, sample_first, sc->num_cus * per_cu, clock.words, stream, nullptr, t.num_workgroups)) != RT_OK)
+        return st;
     if ((st = clock.stop(stream)) != RT_OK) return st;
     t.workgroup_size = (uint32_t)rtk::kLightBlock;
     t.trace_launches = (uint32_t)passes.passes;
@@ -2940,6 +2964,145 @@ rt_status rt_render_lit(rt_scene *sc, const rt_camera_data *cam_open, const rt_l
     };
     return render_light_impl<LitEither>("rt_render_lit", kernel, S.env ? &S.env->device : nullptr, make_light, sc, cam_open, shard, sample_first, d_fb_sum,
                                         hip_stream, sync, timing, &S.C);
+}
+
+// ---- rt_render_lit_adaptive (rtp_amd.h): rt_render_adaptive's rule and rounds on rt_render_lit's estimator.  The min_spp
+// frame is render_light_impl's passes with the moments; a round is adaptive_impl's — expand, trace, add, moments, select — with the list
+// variant of the frame's kernel as its trace launch.  Every round is enqueued up front; the light is made once.
+rt_status rt_render_lit_adaptive(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_adaptive_params *params,
+                                 const rt_shard *shard, int32_t sample_first, float *d_fb_sum, int32_t *d_spp, float *d_moments, void *hip_stream,
+                                 int32_t sync, rt_timing *timing) {
+    // ---- 1. every check before anything is enqueued
+    const char *what = "rt_render_lit_adaptive";
+    rt_adaptive_params a;
+    rt_status st = adaptive_check(what, params, a);
+    if (st != RT_OK) return st;
+    LitSetup S;
+    if ((st = lit_setup(what, cam_open, lit, S)) != RT_OK) return st;
+    const int32_t batch = a.batch_spp, rounds = (a.max_spp - a.min_spp) / a.batch_spp;
+    if ((st = check_sample_range(what, sample_first, a.min_spp + rounds * batch)) != RT_OK) return st;
+    if (!d_fb_sum || !d_spp) return fail(RT_ERR_INVALID_ARG, "rt_render_lit_adaptive: null framebuffer or sample counts");
+    if (!sc) return fail(RT_ERR_INVALID_ARG, "rt_render_lit_adaptive: null scene");
+    rt_camera_data base = *cam_open;
+    base.samples_per_pixel = a.min_spp;
+    Frame F;
+    st = frame_prologue(what, sc, &base, shard, nullptr, sample_first, S.env ? &S.env->device : nullptr, nullptr, hip_stream, timing, F, [&] {
+        if (rounds > 0 && (uint64_t)F.num_pixels * (uint64_t)batch >= (1ull << 31) - 4096)
+            return fail(RT_ERR_UNSUPPORTED, "rt_render_lit_adaptive: pixels x batch_spp beyond the work index arithmetic");
+        return refuse_retired(sc->cfg);
+    });
+    if (st != RT_OK) return st;
+    if (F.nothing_to_do()) return RT_OK;
+    rtk::KParams &P = F.P;
+    const hipStream_t stream = F.stream;
+    const uint32_t num_pixels = F.num_pixels;
+
+    // ---- 2. the handle's buffers (rt_render_adaptive's: a handle renders one frame at a time) and a slab for the frame's passes and a round's batch
+    float *mom = d_moments;
+    if (!mom && (st = grow(sc->adapt_mom, sc->adapt_mom_pixels, (size_t)num_pixels * 2, stream)) != RT_OK) return st;
+    if (!mom) mom = sc->adapt_mom;
+    if (P.max_depth <= 0) {
+        // (no depth: every sample is 0, so is every moment — and the rule stops every pixel at min_spp unless the threshold is 0)
+        HIP_TRY(hipMemsetAsync(d_fb_sum, 0, (size_t)num_pixels * 3 * sizeof(float), stream));
+        HIP_TRY(hipMemsetAsync(mom, 0, (size_t)num_pixels * 8, stream));
+        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)d_spp, a.threshold == 0.0f ? a.min_spp + rounds * batch : a.min_spp, num_pixels, stream));
+        if (sync) HIP_TRY(hipStreamSynchronize(stream));
+        return RT_OK;
+    }
+    if ((st = grow(sc->adapt_list, sc->adapt_pixels, (size_t)num_pixels * 2, stream)) != RT_OK) return st;
+    if ((st = grow(sc->adapt_counters, sc->adapt_counter_words, (size_t)3 * (size_t)(rounds + 1), stream)) != RT_OK) return st;
+    rtaccel::PassPlan passes;
+    if ((st = reserve_slab(sc, num_pixels, a.min_spp, stream, passes)) != RT_OK) return st;
+    if (rounds > 0) {
+        if ((st = grow(sc->adapt_work, sc->adapt_work_cap, (size_t)num_pixels * (size_t)batch, stream)) != RT_OK) return st;
+        if ((st = grow(sc->slab, sc->slab_floats, (size_t)num_pixels * slab_pitch_of(batch) * 3, stream)) != RT_OK) return st;
+    }
+
+    // ---- 3. the light, once, and the two kernels it needs: the frame's and its list variant
+    LitEither T;
+    bool planes, tree;
+    if ((st = lit_light_of(sc, S, T, planes, tree)) != RT_OK) return st;
+    const void *frame_kernel, *list_kernel;
+    if (tree && planes) {
+        frame_kernel = S.lens ? (const void *)rtk::lit_tree_render_kernel<true, rtk::TreeEmitTable> : (const void *)rtk::lit_tree_render_kernel<false, rtk::TreeEmitTable>;
+        list_kernel = S.lens ? (const void *)rtk::lit_tree_list_render_kernel<true, rtk::TreeEmitTable> : (const void *)rtk::lit_tree_list_render_kernel<false, rtk::TreeEmitTable>;
+    } else if (tree) {
+        frame_kernel = S.lens ? (const void *)rtk::lit_tree_render_kernel<true, rtk::TreeTable> : (const void *)rtk::lit_tree_render_kernel<false, rtk::TreeTable>;
+        list_kernel = S.lens ? (const void *)rtk::lit_tree_list_render_kernel<true, rtk::TreeTable> : (const void *)rtk::lit_tree_list_render_kernel<false, rtk::TreeTable>;
+    } else if (planes) {
+        frame_kernel = S.lens ? (const void *)rtk::lit_emit_render_kernel<true> : (const void *)rtk::lit_emit_render_kernel<false>;
+        list_kernel = S.lens ? (const void *)rtk::lit_emit_list_render_kernel<true> : (const void *)rtk::lit_emit_list_render_kernel<false>;
+    } else {
+        frame_kernel = S.lens ? (const void *)rtk::lit_render_kernel<true> : (const void *)rtk::lit_render_kernel<false>;
+        list_kernel = S.lens ? (const void *)rtk::lit_list_render_kernel<true> : (const void *)rtk::lit_list_render_kernel<false>;
+    }
+    rt_timing t{};
+    kernel_resources(rounds > 0 ? list_kernel : frame_kernel, t.trace_vgprs, t.trace_scratch_bytes);
+    CallClock &clock = sc->clock[kClockLight];
+    if ((st = clock.make(kMaxPasses)) != RT_OK) return st;
+    HIP_TRY(hipMemsetAsync(clock.words, 0, kMaxPasses * 4, stream));
+    uint32_t *const counters = sc->adapt_counters;          // round r (1 …): [3(r-1)] its list's length, [3(r-1) + 1] its work indices, [3(r-1) + 2] its queue
+    HIP_TRY(hipMemsetAsync(counters, 0, (size_t)3 * (size_t)(rounds + 1) * sizeof(uint32_t), stream));
+    if ((st = clock.start(stream)) != RT_OK) return st;
+
+    // ---- 4. the min_spp frame: rt_render_lit's passes, with the moments
+    P.fb = d_fb_sum;
+    bind_slab(sc, P, num_pixels, passes.pass_size);
+    if ((st = light_passes(frame_kernel, &T, &S.C, P, passes, num_pixels, sample_first, sc->num_cus * light_wgs_per_cu(frame_kernel), clock.words, stream, mom,
+                           t.num_workgroups)) != RT_OK)
+        return st;
+
+    // ---- 5. every pixel is judged (and its count written); then the rounds, on a list whose length only the device knows
+    const dim3 pix_grid((num_pixels + rtk::kAdaptBlock - 1) / rtk::kAdaptBlock), pix_block(rtk::kAdaptBlock);
+    uint32_t *lists[2] = {sc->adapt_list, sc->adapt_list + num_pixels};
+    int32_t n = a.min_spp;
+    hipLaunchKernelGGL(rtk::adaptive_select_kernel<true>, pix_grid, pix_block, 0, stream, (const float *)mom, d_spp, num_pixels, (const uint32_t *)nullptr,
+                       (const uint32_t *)nullptr, lists[0], counters, n, batch, a.max_spp, a.threshold);
+    HIP_TRY(hipGetLastError());
+    if (rounds > 0) {
+        const uint64_t expand_items = (uint64_t)num_pixels * (uint64_t)batch;
+        const uint32_t expand_grid = (uint32_t)std::min<uint64_t>((expand_items + rtk::kAdaptBlock - 1) / rtk::kAdaptBlock, (uint64_t)sc->num_cus * 8u);
+        // samples [sample_first + n, … + batch) of the listed pixels: work index = local pixel * batch + slot, in the pixel's own slab row
+        bind_slab(sc, P, num_pixels, batch);
+        P.pass_count = batch;
+        P.total_work = num_pixels * (uint32_t)batch;
+        if (!make_magic((uint32_t)batch, (uint64_t)P.total_work + 64, P.magic_count)) return fail(RT_ERR_UNSUPPORTED, "image too large for the work index arithmetic");
+        P.work_list = sc->adapt_work;
+        P.work_cap = P.total_work;
+        // (the grid: for the worst case — every pixel goes on)
+        const int grid = light_grid(sc->num_cus * light_wgs_per_cu(list_kernel), P.total_work);
+        t.num_workgroups = (uint32_t)grid;
+        for (int32_t r = 1; r <= rounds; ++r) {
+            const uint32_t *list = lists[(r - 1) & 1];
+            const uint32_t *listed = counters + 3 * (r - 1);
+            hipLaunchKernelGGL(rtk::adaptive_expand_kernel, dim3(expand_grid), pix_block, 0, stream, list, listed, (uint32_t)batch, sc->adapt_work,
+                               counters + 3 * (r - 1) + 1);
+            P.pass_first = sample_first + n;
+            P.work_count = counters + 3 * (r - 1) + 1;
+            P.queue = counters + 3 * (r - 1) + 2;
+            HIP_TRY(launch(list_kernel, (uint32_t)rtk::kLightBlock, grid, 0, stream, P, &T, &S.C));
+            // … added onto the running sums in slot order, and onto the moments
+            launch_accumulate(stream, P, Acc::onto_sums(list, listed));
+            hipLaunchKernelGGL(rtk::moments_kernel<true>, pix_grid, pix_block, 0, stream, mom, (const float *)P.slab, num_pixels, P.slab_pitch, batch, 0, list, listed,
+                               (const uint32_t *)nullptr, 0u, 0.0f, 0.0f, 0.0f);
+            n += batch;
+            if (r < rounds)
+                hipLaunchKernelGGL(rtk::adaptive_select_kernel<false>, pix_grid, pix_block, 0, stream, (const float *)mom, d_spp, num_pixels, list, listed,
+                                   lists[r & 1], counters + 3 * r, n, batch, a.max_spp, a.threshold);
+            HIP_TRY(hipGetLastError());
+        }
+    }
+    if ((st = clock.stop(stream)) != RT_OK) return st;
+    t.workgroup_size = (uint32_t)rtk::kLightBlock;
+    t.trace_launches = (uint32_t)(passes.passes + rounds);
+    t.kernel = RT_KERNEL_MEGA;
+    t.traced_samples = (uint64_t)num_pixels * (uint64_t)a.min_spp;          // (the rounds': the sum of d_spp, which only the device knows)
+    t.guard_paused = sc->guard_paused ? 1u : 0u;
+    if (sync) {
+        if ((st = clock.elapsed(t.kernel_ms)) != RT_OK) return st;
+    }
+    timing_out(t, timing);
+    return RT_OK;
 }
 
 rt_status rt_trace_samples_lit(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, int32_t n, const int32_t *ijs, float *radiance,

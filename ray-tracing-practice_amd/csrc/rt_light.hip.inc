@@ -574,116 +574,135 @@ __device__ __forceinline__ void lit_probe_body(const KParams &P, const Lit &T, c
 // environment sample still waits.  Across the emitter's walk a lane holds the next direction, both pending contributions, the
 // environment's direction and the target (thirteen registers); across the environment's, the next direction and its contribution.
 constexpr int32_t kLitShadowA = 2, kLitShadowAB = 3, kLitShadowB = 4;
-template <bool kLens, class Lit>
+// The wave loop is one text for both of its forms — RTP_LIT_RENDER_BODY, the body of a function with P, T and C in scope: TOTAL is the
+// number of work indices (wave-uniform) and WORK_OF_MINE what the fetched index `mine` stands for.  Expanded twice rather than branched
+// on inside, so that the frame kernels compile to what they compiled to before the list variants existed (DESIGN.md §19).
+#define RTP_LIT_RENDER_BODY(TOTAL, WORK_OF_MINE)                                                                    \
+    const int lane = (int)(threadIdx.x & (kWave - 1));                                                              \
+    Lane L;                                                                                                         \
+    L.node = kBlocked;                                                                                              \
+    L.sp = 0;                                                                                                       \
+    L.hit = -1;                                                                                                     \
+    L.closest = 1e30f;                                                                                              \
+    L.color = mk(0.0f, 0.0f, 0.0f);                                                                                 \
+    L.beta = mk(1.0f, 1.0f, 1.0f);                                                                                  \
+    L.depth = 0;                                                                                                    \
+    L.seed = 0;                                                                                                     \
+    int32_t phase = kLightIdle;                                                                                     \
+    uint32_t w = 0, nee = 0, env = 0;                                                                               \
+    bool prev_diffuse = false;                                                                                      \
+    f3 next_d = mk(0, 0, 0);                                                                                        \
+    LitSamples S;                                                                                                   \
+    S.adir = S.ac = S.bdir = S.bc = mk(0, 0, 0);                                                                    \
+    S.code = -1;                                                                                                    \
+    S.a = S.b = false;                                                                                              \
+    uint32_t pool_next = 0, pool_end = 0;  /* (wave-uniform) */                                                     \
+    bool exhausted = false;                                                                                         \
+    for (;;) {                                                                                                      \
+        /* ---- lanes without a sample take the next work indices of the wave's pool (refilled with one atomic) */  \
+        const uint64_t idle = __ballot(phase == kLightIdle);                                                        \
+        if (idle != 0 && !exhausted) {                                                                              \
+            const uint32_t cnt = (uint32_t)__popcll(idle);                                                          \
+            const uint32_t rank = (uint32_t)lane_rank(idle);                                                        \
+            const uint32_t avail = pool_end - pool_next;                                                            \
+            uint32_t mine;                                                                                          \
+            if (avail < cnt) {                                                                                      \
+                uint32_t base = 0;                                                                                  \
+                if (lane == 0) base = atomicAdd(P.queue, kLightChunk);                                              \
+                base = __builtin_amdgcn_readfirstlane(base);                                                        \
+                mine = rank < avail ? pool_next + rank : base + (rank - avail);                                     \
+                pool_next = base + (cnt - avail);                                                                   \
+                pool_end = base + kLightChunk;                                                                      \
+                if (base >= (TOTAL)) exhausted = true;                                                              \
+            } else {                                                                                                \
+                mine = pool_next + rank;                                                                            \
+                pool_next += cnt;                                                                                   \
+            }                                                                                                       \
+            if (phase == kLightIdle && mine < (TOTAL)) {                                                            \
+                w = (WORK_OF_MINE);                                                                                 \
+                int32_t pi, pj;                                                                                     \
+                uint32_t k;                                                                                         \
+                map_work(P, w, pi, pj, k);                                                                          \
+                const int32_t s = P.pass_first + (int32_t)k;                                                        \
+                const uint32_t base_seed = wang_hash((uint32_t)pi * (uint32_t)P.width + (uint32_t)pj);              \
+                nee = light_seed_of(T.N, base_seed, s);                                                             \
+                env = light_seed_of(T.E, base_seed, s);                                                             \
+                f3 o, d;                                                                                            \
+                lit_start<kLens>(L, P, C, pi, pj, base_seed, s, o, d);                                              \
+                begin_ray(L, o, d, 0);                                                                              \
+                prev_diffuse = false;                                                                               \
+                phase = kLightPath;                                                                                 \
+            }                                                                                                       \
+        }                                                                                                           \
+        const bool busy = phase != kLightIdle;                                                                      \
+        if (!__any(busy)) {                                                                                         \
+            if (exhausted) break;                                                                                   \
+            continue;                                                                                               \
+        }                                                                                                           \
+        const bool walking = busy && !traversal_finished<true>(L, kBlocked);                                        \
+        const bool ready = busy && !walking;                                                                        \
+        const int n_walk = __popcll(__ballot(walking));                                                             \
+        const int n_ready = __popcll(__ballot(ready));                                                              \
+        if (n_walk == 0 || n_ready >= kLightShadeLanes) {                                                           \
+            if (ready) {                                                                                            \
+                if (phase == kLightPath) {                                                                          \
+                    f3 next_o;                                                                                      \
+                    bool diffuse;                                                                                   \
+                    const bool more = shade_lit2(L, P, T, prev_diffuse, nee, env, next_o, next_d, S, diffuse);      \
+                    prev_diffuse = diffuse;                                                                         \
+                    if (S.a) {                                                                                      \
+                        begin_ray(L, next_o, S.adir, 0);                                                            \
+                        phase = S.b ? kLitShadowAB : kLitShadowA;                                                   \
+                    } else if (S.b) {                                                                               \
+                        begin_ray(L, next_o, S.bdir, 0);                                                            \
+                        phase = kLitShadowB;                                                                        \
+                    } else if (more) {                                                                              \
+                        begin_ray(L, next_o, next_d, 0);                                                            \
+                    } else {                                                                                        \
+                        store_sample(P, w, L.color);                                                                \
+                        phase = kLightIdle;                                                                         \
+                    }                                                                                               \
+                } else if (phase == kLitShadowB) {                                                                  \
+                    if (L.hit < 0) L.color = add(L.color, S.bc);                                                    \
+                    begin_ray(L, L.o, next_d, 0);                                                                   \
+                    phase = kLightPath;                                                                             \
+                } else {                                                                                            \
+                    if (L.hit == S.code) L.color = add(L.color, S.ac);                                              \
+                    const bool then_env = phase == kLitShadowAB;                                                    \
+                    begin_ray(L, L.o, then_env ? S.bdir : next_d, 0);                                               \
+                    phase = then_env ? kLitShadowB : kLightPath;                                                    \
+                }                                                                                                   \
+                if (phase == kLightIdle) {                                                                          \
+                    L.node = kBlocked;                                                                              \
+                    L.sp = 0;                                                                                       \
+                }                                                                                                   \
+            }                                                                                                       \
+        } else {                                                                                                    \
+            const bool occlusion = phase == kLitShadowB;                                                            \
+            _Pragma("unroll")                                                                                       \
+            for (int u = 0; u < 4; ++u) {                                                                           \
+                if (!traversal_finished<true>(L, kBlocked)) lit_step(L, P, occlusion);                              \
+            }                                                                                                       \
+        }                                                                                                           \
+    }
+// kList = false: the work indices are [0, P.total_work) — a pass of rt_render_lit's.
+// kList = true (rt_render_lit_adaptive's rounds; DESIGN.md §19): they are the first *P.work_count entries of P.work_list — a length that lives
+// on the device, read once per wave and wave-uniform; a fetched index `mine` then stands for P.work_list[mine], in map_work and in
+// store_sample alike.  The fetch itself is the same: chunks of kLightChunk from P.queue until a chunk starts at or past the length, so an
+// empty list leaves before the first atomic, a list shorter than a chunk is one wave's (every other wave's first chunk starts past the
+// end), and the lanes of a last chunk that reaches past the end stay idle until the wave's next fetch finds the queue dry.
+template <bool kLens, class Lit, bool kList = false>
 __device__ __forceinline__ void lit_render_body(const KParams &P, const Lit &T, const LensCam &C) {
-    const int lane = (int)(threadIdx.x & (kWave - 1));
-    Lane L;
-    L.node = kBlocked;
-    L.sp = 0;
-    L.hit = -1;
-    L.closest = 1e30f;
-    L.color = mk(0.0f, 0.0f, 0.0f);
-    L.beta = mk(1.0f, 1.0f, 1.0f);
-    L.depth = 0;
-    L.seed = 0;
-    int32_t phase = kLightIdle;
-    uint32_t w = 0, nee = 0, env = 0;
-    bool prev_diffuse = false;
-    f3 next_d = mk(0, 0, 0);
-    LitSamples S;
-    S.adir = S.ac = S.bdir = S.bc = mk(0, 0, 0);
-    S.code = -1;
-    S.a = S.b = false;
-    uint32_t pool_next = 0, pool_end = 0;        // (wave-uniform)
-    bool exhausted = false;
-    for (;;) {
-        // ---- lanes without a sample take the next work indices of the wave's pool (refilled with one atomic)
-        const uint64_t idle = __ballot(phase == kLightIdle);
-        if (idle != 0 && !exhausted) {
-            const uint32_t cnt = (uint32_t)__popcll(idle);
-            const uint32_t rank = (uint32_t)lane_rank(idle);
-            const uint32_t avail = pool_end - pool_next;
-            uint32_t mine;
-            if (avail < cnt) {
-                uint32_t base = 0;
-                if (lane == 0) base = atomicAdd(P.queue, kLightChunk);
-                base = __builtin_amdgcn_readfirstlane(base);
-                mine = rank < avail ? pool_next + rank : base + (rank - avail);
-                pool_next = base + (cnt - avail);
-                pool_end = base + kLightChunk;
-                if (base >= P.total_work) exhausted = true;
-            } else {
-                mine = pool_next + rank;
-                pool_next += cnt;
-            }
-            if (phase == kLightIdle && mine < P.total_work) {
-                w = mine;
-                int32_t pi, pj;
-                uint32_t k;
-                map_work(P, w, pi, pj, k);
-                const int32_t s = P.pass_first + (int32_t)k;
-                const uint32_t base_seed = wang_hash((uint32_t)pi * (uint32_t)P.width + (uint32_t)pj);
-                nee = light_seed_of(T.N, base_seed, s);
-                env = light_seed_of(T.E, base_seed, s);
-                f3 o, d;
-                lit_start<kLens>(L, P, C, pi, pj, base_seed, s, o, d);
-                begin_ray(L, o, d, 0);
-                prev_diffuse = false;
-                phase = kLightPath;
-            }
-        }
-        const bool busy = phase != kLightIdle;
-        if (!__any(busy)) {
-            if (exhausted) break;
-            continue;
-        }
-        const bool walking = busy && !traversal_finished<true>(L, kBlocked);
-        const bool ready = busy && !walking;
-        const int n_walk = __popcll(__ballot(walking));
-        const int n_ready = __popcll(__ballot(ready));
-        if (n_walk == 0 || n_ready >= kLightShadeLanes) {
-            if (ready) {
-                if (phase == kLightPath) {
-                    f3 next_o;
-                    bool diffuse;
-                    const bool more = shade_lit2(L, P, T, prev_diffuse, nee, env, next_o, next_d, S, diffuse);
-                    prev_diffuse = diffuse;
-                    if (S.a) {
-                        begin_ray(L, next_o, S.adir, 0);
-                        phase = S.b ? kLitShadowAB : kLitShadowA;
-                    } else if (S.b) {
-                        begin_ray(L, next_o, S.bdir, 0);
-                        phase = kLitShadowB;
-                    } else if (more) {
-                        begin_ray(L, next_o, next_d, 0);
-                    } else {
-                        store_sample(P, w, L.color);
-                        phase = kLightIdle;
-                    }
-                } else if (phase == kLitShadowB) {
-                    if (L.hit < 0) L.color = add(L.color, S.bc);
-                    begin_ray(L, L.o, next_d, 0);
-                    phase = kLightPath;
-                } else {
-                    if (L.hit == S.code) L.color = add(L.color, S.ac);
-                    const bool then_env = phase == kLitShadowAB;
-                    begin_ray(L, L.o, then_env ? S.bdir : next_d, 0);
-                    phase = then_env ? kLitShadowB : kLightPath;
-                }
-                if (phase == kLightIdle) {
-                    L.node = kBlocked;
-                    L.sp = 0;
-                }
-            }
-        } else {
-            const bool occlusion = phase == kLitShadowB;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                if (!traversal_finished<true>(L, kBlocked)) lit_step(L, P, occlusion);
-            }
-        }
+    if constexpr (kList) {
+        uint32_t listed = (uint32_t)__builtin_amdgcn_readfirstlane((int32_t)*P.work_count);
+        if (listed > P.work_cap) listed = P.work_cap;          // (never more entries than the list has room for)
+        if (listed == 0u) return;
+        RTP_LIT_RENDER_BODY(listed, P.work_list[mine])
+    } else {
+        RTP_LIT_RENDER_BODY(P.total_work, mine)
     }
 }
+#undef RTP_LIT_RENDER_BODY
 
 template <bool kLens>
 __global__ void __launch_bounds__(256) lit_probe_kernel(const KParams P, const LitLight T, const LensCam C, uint32_t *nee_seed_out, uint32_t *env_seed_out) {
@@ -705,5 +724,13 @@ __global__ void __launch_bounds__(256) lit_tree_probe_kernel(const KParams P, co
 }
 template <bool kLens, class Table>
 __global__ void __launch_bounds__(kLightBlock, 4) lit_tree_render_kernel(const KParams P, const LitTreeOf<Table> T, const LensCam C) { lit_render_body<kLens>(P, T, C); }
+
+// ---- the list variants: rt_render_lit_adaptive's rounds (DESIGN.md §19) — the same bodies on a list whose length lives on the device
+template <bool kLens>
+__global__ void __launch_bounds__(kLightBlock, 4) lit_list_render_kernel(const KParams P, const LitLight T, const LensCam C) { lit_render_body<kLens, LitLight, true>(P, T, C); }
+template <bool kLens>
+__global__ void __launch_bounds__(kLightBlock, 4) lit_emit_list_render_kernel(const KParams P, const LitEmitLight T, const LensCam C) { lit_render_body<kLens, LitEmitLight, true>(P, T, C); }
+template <bool kLens, class Table>
+__global__ void __launch_bounds__(kLightBlock, 4) lit_tree_list_render_kernel(const KParams P, const LitTreeOf<Table> T, const LensCam C) { lit_render_body<kLens, LitTreeOf<Table>, true>(P, T, C); }
 
 }  // namespace rtk

@@ -143,7 +143,7 @@ void gpu_render_pipelined(const SceneParams &params, const rt_scene_desc &desc, 
 // lit->cam_close are set per frame here), aov / denoise from rt_render_aov_lens
 void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const rt_lens_params &lens, float shutter, bool aov, bool denoise,
                      const rt_nee_params *nee = nullptr, const rt_env *env = nullptr, const rt_env_params *env_params = nullptr,
-                     const rt_lit_params *lit = nullptr);
+                     const rt_lit_params *lit = nullptr, const rt_adaptive_params *noise = nullptr);
 // rtp_main --gpu --adaptive: the orbit frame after frame on one GPU, each frame through rt_render_adaptive and rt_tonemap_spp
 void gpu_render_adaptive(const SceneParams &params, const rt_scene_desc &desc, const rt_adaptive_params &ap);
 

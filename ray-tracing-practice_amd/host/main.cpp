@@ -46,7 +46,12 @@ int main(int argc, char *argv[]) {
     // `--motion-blur S` in any combination; --aov / --denoise as with --lens (first hits do not depend on the estimator).  Each of those
     // flags is parsed by its own block below, which hands its value on instead of rendering.  Not with --adaptive, --denoise-temporal,
     // --devices, --shard or RTP_DEVICES.
-    bool lit_on = false;
+    // `--lit --noise-target T [--noise-spp min:batch:max]`: those frames through rt_render_lit_adaptive (adaptive sampling on the lit path,
+    // default 16:16:256) and rt_tonemap_spp.  --noise-target needs --lit and is not for --adaptive, --denoise or --aov; --noise-spp needs
+    // --noise-target.
+    bool lit_on = false, noise_on = false;
+    rt_adaptive_params noise;
+    rt_adaptive_params_init(&noise);
     rt_env *lit_env = nullptr;
     rt_env_params lit_ep;
     rt_env_params_init(&lit_ep);
@@ -58,6 +63,35 @@ int main(int argc, char *argv[]) {
             const std::string arg = argv[a];
             if (arg == "--lit") lit_on = true;
             if (arg == "--adaptive" || arg == "--denoise-temporal" || arg == "--devices" || arg == "--shard") lit_others = true;
+        }
+        bool noise_spp = false, noise_adaptive = false;
+        std::string noise_bad;
+        for (int a = 2; a < argc; ++a) {
+            const std::string arg = argv[a];
+            const std::string value = a + 1 < argc ? argv[a + 1] : "";
+            if (arg == "--adaptive") noise_adaptive = true;
+            if (arg == "--noise-target") {
+                noise_on = true;
+                char *end = nullptr;
+                noise.threshold = strtof(value.c_str(), &end);
+                if (value.empty() || *end != 0 || !(std::isfinite(noise.threshold) && noise.threshold >= 0.0f))
+                    noise_bad = "--noise-target takes a finite threshold that is not negative";
+            }
+            if (arg == "--noise-spp") {
+                noise_spp = true;
+                char tail = 0;
+                if (sscanf(value.c_str(), "%d:%d:%d%c", &noise.min_spp, &noise.batch_spp, &noise.max_spp, &tail) != 3 || noise.min_spp < 2 ||
+                    noise.batch_spp < 1 || noise.max_spp < noise.min_spp || noise.max_spp > 65536)
+                    noise_bad = "--noise-spp takes min:batch:max with min >= 2, batch >= 1 and min <= max <= 65536";
+            }
+        }
+        if (noise_spp && !noise_on) noise_bad = "--noise-spp needs --noise-target T";
+        else if (noise_on && !lit_on) noise_bad = "--noise-target sets the noise target of --lit frames: it needs --lit";
+        else if (noise_on && noise_bad.empty() && (noise_adaptive || aov || denoise))
+            noise_bad = "--noise-target cannot be combined with --adaptive, --denoise or --aov";
+        if (!noise_bad.empty()) {
+            std::cerr << "rtp_main: " << noise_bad << "\n";
+            return 99;
         }
         if (lit_on && lit_others) {
             std::cerr << "rtp_main: --lit renders frame after frame on one GPU: it cannot be combined with --adaptive, --denoise-temporal, "
@@ -245,7 +279,7 @@ int main(int argc, char *argv[]) {
                 lit.nee = &lit_nee;
                 lit.env = lit_env;
                 lit.env_params = &lit_ep;
-                rtp::gpu_render_lens(params, desc, lens, shutter, aov, denoise, nullptr, nullptr, nullptr, &lit);
+                rtp::gpu_render_lens(params, desc, lens, shutter, aov, denoise, nullptr, nullptr, nullptr, &lit, noise_on ? &noise : nullptr);
                 rt_env_destroy(lit_env);
                 return 0;
             }

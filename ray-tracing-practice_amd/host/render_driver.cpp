@@ -258,9 +258,11 @@ void gpu_render_pipelined(const SceneParams &params, const rt_scene_desc &desc, 
 // these sums.  aov / denoise as in gpu_render, from rt_render_aov_lens.
 // nee: the frames through rt_render_nee (rtp_main --nee), the AOVs through rt_render_aov_samples — the same first hits; env: through
 // rt_render_env with env_params (rtp_main --env), the AOVs likewise; lit: through rt_render_lit (rtp_main --lit) with this lens and
-// shutter, the AOVs through rt_render_aov_lens
+// shutter, the AOVs through rt_render_aov_lens; noise (with lit; rtp_main --lit --noise-target): through
+// rt_render_lit_adaptive and rt_tonemap_spp — every pixel's bytes at its own sample count — and the printed count is the samples taken
 void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const rt_lens_params &lens, float shutter, bool aov, bool denoise,
-                     const rt_nee_params *nee, const rt_env *env, const rt_env_params *env_params, const rt_lit_params *lit) {
+                     const rt_nee_params *nee, const rt_env *env, const rt_env_params *env_params, const rt_lit_params *lit,
+                     const rt_adaptive_params *noise) {
     rt_scene *scene = nullptr;
     RTP_CHECK(rt_scene_create(&desc, &scene));
     const size_t num_pixels = static_cast<size_t>(params.width) * params.height;
@@ -270,6 +272,12 @@ void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const
     const uint64_t workspace_bytes = denoise ? rt_denoise_workspace_bytes(params.width, params.height) : 0;
     RTP_CHECK(rt_device_alloc(num_pixels * 3 * sizeof(float), reinterpret_cast<void **>(&d_fb)));
     RTP_CHECK(rt_device_alloc(num_pixels * 3, reinterpret_cast<void **>(&d_rgb)));
+    int32_t *d_spp = nullptr;
+    std::vector<int32_t> h_spp;
+    if (lit && noise) {
+        RTP_CHECK(rt_device_alloc(num_pixels * sizeof(int32_t), reinterpret_cast<void **>(&d_spp)));
+        h_spp.resize(num_pixels);
+    }
     rt_aov_buffers aov_bufs;
     rt_aov_buffers_init(&aov_bufs);
     std::vector<float> h_albedo, h_normal, h_depth, h_denoised;
@@ -305,7 +313,13 @@ void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const
         const rt_camera_data close = camera_at(static_cast<float>(n) + shutter);
         const rt_camera_data *cam_close = shutter > 0.0f ? &close : nullptr;
         const auto t0 = std::chrono::steady_clock::now();
-        if (lit) {
+        long long total_rays = static_cast<long long>(params.width) * params.height * params.sqrt_spp * params.sqrt_spp;
+        if (lit && noise) {
+            rt_lit_params frame_lit = *lit;
+            frame_lit.cam_close = cam_close;
+            frame_lit.lens = &lens;
+            RTP_CHECK(rt_render_lit_adaptive(scene, &cam, &frame_lit, noise, nullptr, 0, d_fb, d_spp, nullptr, nullptr, 1, nullptr));
+        } else if (lit) {
             rt_lit_params frame_lit = *lit;
             frame_lit.cam_close = cam_close;
             frame_lit.lens = &lens;
@@ -313,13 +327,19 @@ void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const
         } else if (env) RTP_CHECK(rt_render_env(scene, &cam, env, env_params, nullptr, 0, d_fb, nullptr, 1, nullptr));
         else if (nee) RTP_CHECK(rt_render_nee(scene, &cam, nee, nullptr, 0, d_fb, nullptr, 1, nullptr));
         else RTP_CHECK(rt_render_lens(scene, &cam, cam_close, &lens, nullptr, 0, d_fb, nullptr, 1, nullptr));
-        RTP_CHECK(rt_tonemap(d_fb, d_rgb, static_cast<int64_t>(num_pixels) * 3, params.sqrt_spp, nullptr));
+        if (d_spp) {
+            RTP_CHECK(rt_tonemap_spp(d_fb, d_spp, d_rgb, static_cast<int64_t>(num_pixels), nullptr));
+            RTP_CHECK(rt_copy_to_host(h_spp.data(), d_spp, num_pixels * sizeof(int32_t)));
+            total_rays = 0;
+            for (int32_t k : h_spp) total_rays += k;
+        } else {
+            RTP_CHECK(rt_tonemap(d_fb, d_rgb, static_cast<int64_t>(num_pixels) * 3, params.sqrt_spp, nullptr));
+        }
         RTP_CHECK(rt_copy_to_host(file.rgb.data(), d_rgb, num_pixels * 3));
         file.path = filename;
         write_binary_frame(file);
         const auto t1 = std::chrono::steady_clock::now();
         const float ms = std::chrono::duration<float, std::milli>(t1 - t0).count();
-        const long long total_rays = static_cast<long long>(params.width) * params.height * params.sqrt_spp * params.sqrt_spp;
         std::cout << n << "\t" << ms << "\t" << total_rays << "\n";
         if (aov || denoise) {          // (outside the frame's timed span, as in gpu_render)
             if (!lit && (nee || env)) RTP_CHECK(rt_render_aov_samples(scene, &cam, nullptr, 0, &aov_bufs, nullptr, 1, nullptr));
@@ -348,6 +368,7 @@ void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const
     }
     rt_device_free(d_fb);
     rt_device_free(d_rgb);
+    rt_device_free(d_spp);
     rt_device_free(aov_bufs.albedo_sum);
     rt_device_free(aov_bufs.normal_sum);
     rt_device_free(aov_bufs.depth_sum);

@@ -392,6 +392,7 @@ RTP_AMD_SYMBOLS = [
     "rt_env_params_init", "rt_env_create", "rt_env_destroy", "rt_env_table", "rt_env_lookup", "rt_env_from_equirect", "rt_render_env",
     "rt_trace_samples_env",
     "rt_lit_params_init", "rt_render_lit", "rt_trace_samples_lit",
+    "rt_render_lit_adaptive",
 ]
 
 _host = None
@@ -527,6 +528,10 @@ def amd_lib():
                                           C.c_void_p, C.c_int32, C.POINTER(Timing)]
             lib.rt_trace_samples_lit.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(LitParams), C.c_int32, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(lib, "rt_render_lit_adaptive"):
+            lib.rt_render_lit_adaptive.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(LitParams), C.POINTER(AdaptiveParams),
+                                                   C.POINTER(Shard), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                                   C.POINTER(Timing)]
         lib.rt_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         lib.rt_last_timing.argtypes = [C.c_void_p, C.POINTER(Timing)]
         lib.rt_timing_init.argtypes = [C.POINTER(Timing)]
@@ -1246,6 +1251,45 @@ class DeviceScene:
         finally:
             lib.rt_device_free(d)
         return fb, t
+
+    def render_lit_adaptive(self, cam, d_fb_ptr, d_spp_ptr, d_moments_ptr=None, *, cam_close=None, lens=None, emitters=True, nee=None, env=None,
+                            env_params=None, shard=None, stream=None, sync=True, sample_first=0, **params):
+        """rt_render_lit_adaptive: rt_render_adaptive's rounds on rt_render_lit's estimator.  d_fb_ptr (3 floats per pixel), d_spp_ptr
+        (1 int32 per pixel), d_moments_ptr (None, or 2 floats per pixel) are integer device addresses; the keywords are lit_params()'s
+        arguments; params are rt_adaptive_params fields (min_spp, batch_spp, max_spp, threshold).  Returns the rt_timing of this call."""
+        p = adaptive_params(**params)
+        t = Timing()
+        self._apply_config()
+        lit = lit_params(cam_close=cam_close, lens=lens, emitters=emitters, nee=nee, env=env, env_params=env_params)
+        _check(amd_lib().rt_render_lit_adaptive(self._h, C.byref(cam), C.byref(lit), C.byref(p), C.byref(shard) if shard else None, sample_first,
+                                                C.c_void_p(d_fb_ptr), C.c_void_p(d_spp_ptr), C.c_void_p(d_moments_ptr or 0), C.c_void_p(stream or 0),
+                                                1 if sync else 0, C.byref(t)), "rt_render_lit_adaptive")
+        return t
+
+    def render_lit_adaptive_to_host(self, cam, *, cam_close=None, lens=None, emitters=True, nee=None, env=None, env_params=None, shard=None,
+                                    sample_first=0, **params):
+        """rt_render_lit_adaptive through fresh device buffers: (fb (rows, w, 3) float32 sums, spp (rows, w) int32, moments (rows, w, 2)
+        float32 (S1, S2)) and the rt_timing."""
+        lib = amd_lib()
+        rows = lib.rt_shard_rows(cam.image_height, C.byref(shard) if shard else None)
+        w = cam.image_width
+        fb = np.empty((rows, w, 3), dtype=np.float32)
+        spp = np.empty((rows, w), dtype=np.int32)
+        mom = np.empty((rows, w, 2), dtype=np.float32)
+        dev = []
+        try:
+            for a in (fb, spp, mom):
+                d = C.c_void_p()
+                _check(lib.rt_device_alloc(a.nbytes or 12, C.byref(d)), "rt_device_alloc")
+                dev.append(d)
+            t = self.render_lit_adaptive(cam, dev[0].value, dev[1].value, dev[2].value, cam_close=cam_close, lens=lens, emitters=emitters, nee=nee,
+                                         env=env, env_params=env_params, shard=shard, sample_first=sample_first, **params)
+            for a, d in zip((fb, spp, mom), dev):
+                _check(lib.rt_copy_to_host(a.ctypes.data, d, a.nbytes), "rt_copy_to_host")
+        finally:
+            for d in dev:
+                lib.rt_device_free(d)
+        return fb, spp, mom, t
 
     def trace_samples_lit(self, cam, ijs, *, cam_close=None, lens=None, emitters=True, nee=None, env=None, env_params=None):
         """rt_trace_samples_lit: ijs (n, 3) → (radiance (n, 3), rays (n,), final seeds (n,), final emitter-stream seeds (n,), final
