@@ -535,6 +535,42 @@ rt_status rt_render_adaptive(rt_scene *scene, const rt_camera_data *cam, const r
  * uniform frame at n_p.  num_pixels pixels; device pointers; enqueued on hip_stream. */
 rt_status rt_tonemap_spp(const float *d_fb_sum, const int32_t *d_spp, uint8_t *d_rgb8, int64_t num_pixels, void *hip_stream);
 
+/* ---- denoising an adaptively sampled frame: rt_denoise with per-pixel counts and the samples' own variance -------
+ * rt_denoise's filter for the whole-frame outputs of rt_render_adaptive or rt_render_lit_adaptive: d_fb_sum, d_spp and, optionally,
+ * d_moments.  Each pixel is normalised and remodulated by its own count, and with d_moments the variance that steers the luminance
+ * edge-stopping is the variance of the pixel's mean luminance as its own samples estimate it (SVGF's per-pixel variance, Schied et
+ * al. 2017 §4.2, filtered by the paper's 3x3 Gaussian) instead of the 3x3 spatial estimate.  aov holds the sums of rt_render_aov[_samples]
+ * or rt_render_aov_lens for the same camera at a uniform aov_samples per pixel (typically min_spp); albedo_sum, normal_sum, depth_sum
+ * and hit_count are required.  The workspace is rt_denoise's (rt_denoise_workspace_bytes), params rt_denoise_params.
+ *
+ * The arithmetic extends rt_denoise's contract (same rules: float32 in the order written, nothing fused, correctly rounded division
+ * and sqrtf, exp = expf).  n = d_spp[p], inv_p = (float)(1.0 / (double)n) as rt_tonemap_spp computes it, A = aov_samples,
+ * invA = (float)(1.0 / (double)A).  A pixel is a HIT pixel when hit_count > 0 and n >= 1.
+ *   Every other pixel (sky, or a count below 1): out = fb_sum bit for bit; such a pixel is never a tap of another pixel.
+ *   Prepass, per hit pixel:  c_k = fb_sum_k * inv_p,  a_k = albedo_sum_k * invA,  d_k = fmaxf(a_k, 1e-3f),  L_k = c_k / d_k;
+ *     n (the unit normal), z and lum are rt_denoise's.
+ *   Sample variance (only with d_moments; (S1, S2) the pixel's moments):  v = 0 when n < 2; otherwise
+ *     mean = S1 / (float)n,  vs = fmaxf(0, (S2 - S1 * mean) / (float)(n - 1))  (rt_render_adaptive's var),  vm = vs / (float)n,
+ *     dl = lum(d_0, d_1, d_2),  v = vm / (dl * dl): the variance of the mean luminance carried into demodulated space as if the
+ *     albedo were grey.
+ *   Second prepass, per hit pixel p:  gz_p is rt_denoise's.  With d_moments == NULL var_p is rt_denoise's 3x3 luminance variance.
+ *     With d_moments it is the 3x3 Gaussian of v: dy = -1..1 outer, dx = -1..1 inner, hit pixels inside the image only,
+ *     g = k[|dx|] * k[|dy|] with k = {1/2, 1/4};  G += g,  SV += g * v_q  (both from 0);  var_p = SV / G.
+ *   Iterations: rt_denoise's, on (L, var).
+ *   Remodulation, per hit pixel: out_k = (L_k * d_k) * (float)n  (with iterations = 0: the prepass's L).
+ * d_out has an adaptive frame's convention (each pixel the sum over its own n samples): rt_tonemap_spp(d_out, d_spp, …) takes it.
+ * Identities, bit for bit: with d_moments == NULL and every d_spp[p] == S == aov_samples, d_out is rt_denoise's at S; out == fb_sum on
+ * every pixel that is not a hit pixel.
+ *
+ * Enqueues on hip_stream (NULL = default stream): no allocation, no synchronisation.  All pointers but aov and params are DEVICE
+ * memory.  RT_ERR_INVALID_ARG: a required pointer (d_spp included) NULL, width or height below 1, aov_samples outside 1 … 65536, a
+ * parameter outside its range, workspace_bytes below rt_denoise_workspace_bytes, d_out or the workspace overlapping an input (d_spp
+ * counts as 4 bytes per pixel, d_moments as 8) or each other.  RT_ERR_UNSUPPORTED: more than 2^24 pixels.  Every check comes before
+ * any HIP call. */
+rt_status rt_denoise_spp(const float *d_fb_sum, const int32_t *d_spp, const float *d_moments /* NULL or 2 floats per pixel */,
+                         const rt_aov_buffers *aov, int32_t aov_samples, int32_t width, int32_t height,
+                         const rt_denoise_params *params, void *d_workspace, uint64_t workspace_bytes, float *d_out, void *hip_stream);
+
 /* ---- thin-lens depth of field and shutter motion blur ---------------------------------------------------------
  * rt_render_samples / rt_render_aov_samples with a camera that has a lens and / or an open shutter.  Pixel (i, j), sample s; the
  * draws come from the same RNG as the pinhole's, and the path goes on from the state they leave:

@@ -22,6 +22,11 @@
 //     position (X, 0)                mean first-hit point
 //     normal   (n, 0)                unit normal of the prepass
 // With an empty history every pixel is disoccluded, denoise_temporal writes back what moments wrote, and d_out is rt_denoise's.
+//
+// rt_denoise_spp (adaptively sampled frames: a count per pixel) runs the same launches with three kernels of its own:
+// denoise_prepass_spp normalises with the pixel's count and leaves the variance of its samples in lv.w, denoise_moments_spp replaces
+// the 3x3 spatial variance by the 3x3 Gaussian of that (without moments: denoise_moments as it is), and denoise_step_spp is the last
+// step remodulating with the pixel's count.  The taps (rt_denoise_taps.inc) and the depth gradient are one text, expanded in rt_denoise's kernels and in these.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -107,6 +112,67 @@ __global__ __launch_bounds__(256) void denoise_prepass(Image im, Inputs in, floa
     dg[p] = make_float4(d[0], d[1], d[2], 0.0f);
 }
 
+// rt_denoise_spp's prepass: denoise_prepass with the pixel's own count n = spp[p] under the beauty sums (the AOVs keep one count, inv_aov)
+// and a count below 1 making the pixel sky.  With moments the sample variance of the mean luminance, in demodulated space, goes into
+// lv.w for denoise_moments_spp (0 without: denoise_moments overwrites it).
+__global__ __launch_bounds__(256) void denoise_prepass_spp(Image im, Inputs in, const int32_t *spp, const float *moments, float inv_aov, float4 *lv,
+                                                           float4 *nz, float4 *dg, float *out) {
+    int32_t x, y;
+    if (!pixel_of(im, x, y)) return;
+    const int64_t p = (int64_t)y * im.width + x;
+    const uint32_t hits = in.hits[p];
+    const int32_t n = spp[p];
+    if (hits == 0 || n < 1) {
+        if (out) copy3(out, in.fb, p);
+        else nz[p] = make_float4(__builtin_inff(), 0.0f, 0.0f, 0.0f);
+        return;
+    }
+    const float inv = (float)(1.0 / (double)n), fn = (float)n;
+    float L[3], d[3];
+    for (int k = 0; k < 3; ++k) {
+        const float c = in.fb[3 * p + k] * inv;
+        const float a = in.albedo[3 * p + k] * inv_aov;
+        d[k] = fmaxf(a, 1e-3f);
+        L[k] = c / d[k];
+    }
+    if (out) {
+        for (int k = 0; k < 3; ++k) out[3 * p + k] = (L[k] * d[k]) * fn;
+        return;
+    }
+    float v = 0.0f;
+    if (moments && n >= 2) {
+        const float S1 = moments[2 * p], S2 = moments[2 * p + 1];
+        const float mean = S1 / fn;
+        const float vs = fmaxf(0.0f, (S2 - S1 * mean) / (float)(n - 1));
+        const float vm = vs / fn;
+        const float dl = lum(d[0], d[1], d[2]);
+        v = vm / (dl * dl);
+    }
+    const float Nx = in.normal[3 * p], Ny = in.normal[3 * p + 1], Nz = in.normal[3 * p + 2];
+    const float len2 = (Nx * Nx + Ny * Ny) + Nz * Nz;
+    float4 nrm = make_float4(0.0f, 0.0f, 0.0f, in.depth[p] / (float)hits);
+    if (len2 != 0.0f) {
+        const float len = rtd::sqrt_cr(len2);
+        nrm.x = Nx / len;
+        nrm.y = Ny / len;
+        nrm.z = Nz / len;
+    }
+    lv[p] = make_float4(L[0], L[1], L[2], v);
+    nz[p] = nrm;
+    dg[p] = make_float4(d[0], d[1], d[2], 0.0f);
+}
+
+// The depth gradient of hit pixel p = (x, y) with record np, as the statements of the kernel that uses it (a helper function moved
+// denoise_moments' instructions; this text is its old one): the smaller one-sided difference per axis, +inf for a missing neighbour,
+// 0 when both are missing.  Defines gx and gy.
+#define RTP_DENOISE_DEPTH_GRADIENT                                                                                                        \
+    const float inf = __builtin_inff();                                                                                                   \
+    const bool right = x + 1 < im.width && !is_sky(nz[p + 1]), left = x > 0 && !is_sky(nz[p - 1]);                                        \
+    const float gx = (right || left) ? fminf(right ? fabsf(nz[p + 1].w - np.w) : inf, left ? fabsf(np.w - nz[p - 1].w) : inf) : 0.0f;     \
+    const bool below = y + 1 < im.height && !is_sky(nz[p + im.width]), above = y > 0 && !is_sky(nz[p - im.width]);                        \
+    const float gy = (below || above) ? fminf(below ? fabsf(nz[p + im.width].w - np.w) : inf, above ? fabsf(np.w - nz[p - im.width].w) : inf) \
+                                      : 0.0f;
+
 // The second prepass: the 3x3 luminance variance (lv_in → lv_out) and the depth gradient (into dg.w).
 __global__ __launch_bounds__(256) void denoise_moments(Image im, const float4 *lv_in, const float4 *nz, float4 *dg, float4 *lv_out) {
     int32_t x, y;
@@ -134,15 +200,42 @@ __global__ __launch_bounds__(256) void denoise_moments(Image im, const float4 *l
     }
     const float mean = m1 / k;
     const float var = fmaxf(0.0f, m2 / k - mean * mean);
-    // depth gradient: the smaller one-sided difference per axis, +inf for a missing neighbour, 0 when both are missing
-    const float inf = __builtin_inff();
-    const bool right = x + 1 < im.width && !is_sky(nz[p + 1]), left = x > 0 && !is_sky(nz[p - 1]);
-    const float gx = (right || left) ? fminf(right ? fabsf(nz[p + 1].w - np.w) : inf, left ? fabsf(np.w - nz[p - 1].w) : inf) : 0.0f;
-    const bool below = y + 1 < im.height && !is_sky(nz[p + im.width]), above = y > 0 && !is_sky(nz[p - im.width]);
-    const float gy = (below || above) ? fminf(below ? fabsf(nz[p + im.width].w - np.w) : inf, above ? fabsf(np.w - nz[p - im.width].w) : inf)
-                                      : 0.0f;
+    RTP_DENOISE_DEPTH_GRADIENT
     const float4 lp = lv_in[p];
     lv_out[p] = make_float4(lp.x, lp.y, lp.z, var);
+    float4 g = dg[p];
+    g.w = gx + gy;
+    dg[p] = g;
+}
+
+// rt_denoise_spp's second prepass with moments: the 3x3 Gaussian of the sample variance the prepass left in lv.w, and the depth
+// gradient as above.
+__global__ __launch_bounds__(256) void denoise_moments_spp(Image im, const float4 *lv_in, const float4 *nz, float4 *dg, float4 *lv_out) {
+    int32_t x, y;
+    if (!pixel_of(im, x, y)) return;
+    const int64_t p = (int64_t)y * im.width + x;
+    const float4 np = nz[p];
+    if (is_sky(np)) return;
+    const float kern[2] = {0.5f, 0.25f};
+    float G = 0.0f, SV = 0.0f;
+#pragma unroll
+    for (int dy = -1; dy <= 1; ++dy) {
+        const int32_t yy = y + dy;
+        if (yy < 0 || yy >= im.height) continue;
+#pragma unroll
+        for (int dx = -1; dx <= 1; ++dx) {
+            const int32_t xx = x + dx;
+            if (xx < 0 || xx >= im.width) continue;
+            const int64_t q = (int64_t)yy * im.width + xx;
+            if (is_sky(nz[q])) continue;
+            const float g = kern[dx < 0 ? -dx : dx] * kern[dy < 0 ? -dy : dy];
+            G += g;
+            SV += g * lv_in[q].w;
+        }
+    }
+    RTP_DENOISE_DEPTH_GRADIENT
+    const float4 lp = lv_in[p];
+    lv_out[p] = make_float4(lp.x, lp.y, lp.z, SV / G);
     float4 g = dg[p];
     g.w = gx + gy;
     dg[p] = g;
@@ -166,42 +259,7 @@ __global__ __launch_bounds__(256) void denoise_step(Image im, int32_t s, Sigmas 
         if (kFinal) copy3(out, fb, p);
         return;
     }
-    const float4 vp = lv_in[p];
-    const float gz = dg[p].w;
-    const float lp = lum(vp.x, vp.y, vp.z);
-    const float rl = rtd::recip(sg.luminance * rtd::sqrt_cr(vp.w) + 1e-4f);
-    float rz[5];
-#pragma unroll
-    for (int m = 0; m < 5; ++m) rz[m] = rtd::recip((sg.depth * gz) * (float)(s * m) + 1e-4f);
-    const float kern[3] = {0.375f, 0.25f, 0.0625f};
-    float W = 0.0f, S0 = 0.0f, S1 = 0.0f, S2 = 0.0f, SV = 0.0f;
-#pragma unroll
-    for (int dy = -2; dy <= 2; ++dy) {
-        const int32_t yy = y + dy * s;
-        if (yy < 0 || yy >= im.height) continue;
-#pragma unroll
-        for (int dx = -2; dx <= 2; ++dx) {
-            const int32_t xx = x + dx * s;
-            if (xx < 0 || xx >= im.width) continue;
-            const int64_t q = (int64_t)yy * im.width + xx;
-            const float4 nq = nz[q];
-            if (is_sky(nq)) continue;
-            const float4 vq = lv_in[q];
-            const int ax = dx < 0 ? -dx : dx, ay = dy < 0 ? -dy : dy;
-            const float h = kern[ax] * kern[ay];
-            float wn = fmaxf(0.0f, (np.x * nq.x + np.y * nq.y) + np.z * nq.z);
-            for (int k = 0; k < sg.squarings; ++k) wn = wn * wn;
-            const float e = fabsf(np.w - nq.w) * rz[ax + ay] + fabsf(lp - lum(vq.x, vq.y, vq.z)) * rl;
-            const float w = (h * wn) * rtd::exp_libm(-e);
-            W += w;
-            S0 += w * vq.x;
-            S1 += w * vq.y;
-            S2 += w * vq.z;
-            SV += (w * w) * vq.w;
-        }
-    }
-    float4 r = vp;
-    if (W != 0.0f) r = make_float4(S0 / W, S1 / W, S2 / W, SV / (W * W));
+#include "rt_denoise_taps.inc"
     if (kFeedback) feedback[p] = r;
     if (kFinal) {
         const float4 d = dg[p];
@@ -211,6 +269,25 @@ __global__ __launch_bounds__(256) void denoise_step(Image im, int32_t s, Sigmas 
     } else {
         lv_out[p] = r;
     }
+}
+
+// rt_denoise_spp's last pass: denoise_step<true> remodulating with the pixel's own sample count
+__global__ __launch_bounds__(256) void denoise_step_spp(Image im, int32_t s, Sigmas sg, const float4 *lv_in, const float4 *nz, const float4 *dg,
+                                                        const float *fb, const int32_t *spp, float *out) {
+    int32_t x, y;
+    if (!pixel_of(im, x, y)) return;
+    const int64_t p = (int64_t)y * im.width + x;
+    const float4 np = nz[p];
+    if (is_sky(np)) {
+        copy3(out, fb, p);
+        return;
+    }
+#include "rt_denoise_taps.inc"
+    const float4 d = dg[p];
+    const float n = (float)spp[p];
+    out[3 * p] = (r.x * d.x) * n;
+    out[3 * p + 1] = (r.y * d.y) * n;
+    out[3 * p + 2] = (r.z * d.z) * n;
 }
 
 // ---- the temporal half (rt_denoise_temporal) ------------------------------------------------------------------------------------
@@ -406,8 +483,10 @@ rt_status launched(const char *what) {
     return RT_OK;
 }
 
-// The iterations: lv[1] → lv[0] → lv[1] …, the last one remodulating into out; feedback != nullptr: iteration 0 also writes it
-rt_status enqueue_steps(const Launch &l, const rt_denoise_params &prm, const float *fb, float spp, float *out, float4 *feedback, hipStream_t stream) {
+// The iterations: lv[1] → lv[0] → lv[1] …, the last one remodulating into out; feedback != nullptr: iteration 0 also writes it;
+// d_spp != nullptr (rt_denoise_spp; no feedback then): the last one remodulates with each pixel's own count instead of spp
+rt_status enqueue_steps(const Launch &l, const rt_denoise_params &prm, const float *fb, float spp, float *out, float4 *feedback, hipStream_t stream,
+                        const int32_t *d_spp = nullptr) {
     const Sigmas sg = {prm.sigma_depth, prm.sigma_luminance, prm.normal_squarings};
     for (int32_t i = 0; i < prm.iterations; ++i) {
         const float4 *src = l.lv[(i + 1) & 1];
@@ -416,6 +495,8 @@ rt_status enqueue_steps(const Launch &l, const rt_denoise_params &prm, const flo
         if (i == 0 && feedback) {
             if (!last) hipLaunchKernelGGL((denoise_step<false, true>), l.grid, l.block, 0, stream, l.im, 1 << i, sg, src, l.nz, l.dg, dst, fb, spp, out, feedback);
             else hipLaunchKernelGGL((denoise_step<true, true>), l.grid, l.block, 0, stream, l.im, 1 << i, sg, src, l.nz, l.dg, dst, fb, spp, out, feedback);
+        } else if (last && d_spp) {
+            hipLaunchKernelGGL(denoise_step_spp, l.grid, l.block, 0, stream, l.im, 1 << i, sg, src, l.nz, l.dg, fb, d_spp, out);
         } else if (!last) {
             hipLaunchKernelGGL(denoise_step<false>, l.grid, l.block, 0, stream, l.im, 1 << i, sg, src, l.nz, l.dg, dst, fb, spp, out, nullptr);
         } else {
@@ -487,6 +568,51 @@ rt_status rt_denoise(const float *d_fb_sum, const rt_aov_buffers *aov, int32_t w
     hipLaunchKernelGGL(rtdn::denoise_moments, l.grid, l.block, 0, stream, l.im, l.lv[0], l.nz, l.dg, l.lv[1]);
     if ((st = launched("denoise_moments")) != RT_OK) return st;
     return rtdn::enqueue_steps(l, prm, d_fb_sum, spp, d_out, nullptr, stream);
+}
+
+rt_status rt_denoise_spp(const float *d_fb_sum, const int32_t *d_spp, const float *d_moments, const rt_aov_buffers *aov, int32_t aov_samples,
+                         int32_t width, int32_t height, const rt_denoise_params *params, void *d_workspace, uint64_t workspace_bytes, float *d_out,
+                         void *hip_stream) {
+    using rtdn::fail;
+    if (!d_fb_sum || !d_spp || !aov || !d_workspace || !d_out) return fail(RT_ERR_INVALID_ARG, "rt_denoise_spp: null argument");
+    rt_aov_buffers b;
+    rt_aov_buffers_init(&b);
+    const uint32_t ab = aov->struct_bytes < sizeof(b) ? aov->struct_bytes : (uint32_t)sizeof(b);
+    memcpy(&b, aov, ab);
+    if (ab < offsetof(rt_aov_buffers, hit_count) + sizeof(b.hit_count) || !b.albedo_sum || !b.normal_sum || !b.depth_sum || !b.hit_count)
+        return fail(RT_ERR_INVALID_ARG, "rt_denoise_spp: albedo_sum, normal_sum, depth_sum and hit_count are required");
+    if (width < 1 || height < 1) return fail(RT_ERR_INVALID_ARG, "rt_denoise_spp: width and height must be at least 1");
+    if (aov_samples < 1 || aov_samples > 65536) return fail(RT_ERR_INVALID_ARG, "rt_denoise_spp: aov_samples outside 1 … 65536");
+    rt_denoise_params prm;
+    rt_status st = rtdn::read_params("rt_denoise_spp", params, prm);
+    if (st != RT_OK) return st;
+    const uint64_t pixels = (uint64_t)width * (uint64_t)height;
+    if (pixels > (1ull << 24)) return fail(RT_ERR_UNSUPPORTED, "rt_denoise_spp: more than 2^24 pixels");
+    const uint64_t need = rt_denoise_workspace_bytes(width, height);
+    if (workspace_bytes < need)
+        return fail(RT_ERR_INVALID_ARG, "rt_denoise_spp: workspace_bytes below rt_denoise_workspace_bytes (" + std::to_string(need) + ")");
+    const struct { const void *ptr; uint64_t bytes; } inputs[] = {
+        {d_fb_sum, 12 * pixels}, {d_spp, 4 * pixels}, {d_moments, d_moments ? 8 * pixels : 0}, {b.albedo_sum, 12 * pixels},
+        {b.normal_sum, 12 * pixels}, {b.depth_sum, 4 * pixels}, {b.hit_count, 4 * pixels}};
+    for (const auto &in : inputs) {
+        if (rtdn::overlap(d_out, 12 * pixels, in.ptr, in.bytes)) return fail(RT_ERR_INVALID_ARG, "rt_denoise_spp: d_out overlaps an input");
+        if (rtdn::overlap(d_workspace, need, in.ptr, in.bytes)) return fail(RT_ERR_INVALID_ARG, "rt_denoise_spp: the workspace overlaps an input");
+    }
+    if (rtdn::overlap(d_out, 12 * pixels, d_workspace, need)) return fail(RT_ERR_INVALID_ARG, "rt_denoise_spp: d_out overlaps the workspace");
+
+    // ---- enqueue: the prepass with counts · the Gaussian of the sample variance (or rt_denoise's moments) · the iterations -------------
+    const hipStream_t stream = (hipStream_t)hip_stream;
+    const rtdn::Launch l(width, height, d_workspace);
+    const rtdn::Inputs in = {d_fb_sum, b.albedo_sum, b.normal_sum, b.depth_sum, b.hit_count};
+    const float inv_aov = (float)(1.0 / (double)aov_samples);
+    using rtdn::launched;
+    hipLaunchKernelGGL(rtdn::denoise_prepass_spp, l.grid, l.block, 0, stream, l.im, in, d_spp, d_moments, inv_aov, l.lv[0], l.nz, l.dg,
+                       prm.iterations == 0 ? d_out : nullptr);
+    if ((st = launched("denoise_prepass_spp")) != RT_OK || prm.iterations == 0) return st;
+    if (d_moments) hipLaunchKernelGGL(rtdn::denoise_moments_spp, l.grid, l.block, 0, stream, l.im, l.lv[0], l.nz, l.dg, l.lv[1]);
+    else hipLaunchKernelGGL(rtdn::denoise_moments, l.grid, l.block, 0, stream, l.im, l.lv[0], l.nz, l.dg, l.lv[1]);
+    if ((st = launched("denoise_moments")) != RT_OK) return st;
+    return rtdn::enqueue_steps(l, prm, d_fb_sum, 0.0f, d_out, nullptr, stream, d_spp);
 }
 
 uint64_t rt_denoise_history_bytes(int32_t width, int32_t height) {

@@ -140,12 +140,17 @@ void gpu_render_pipelined(const SceneParams &params, const rt_scene_desc &desc, 
 // nee (rtp_main --nee): frames through rt_render_nee with these parameters instead (the lens and shutter then unused: a pinhole at frame n);
 // env (rtp_main --env): through rt_render_env with env_params, likewise;
 // lit (rtp_main --lit): through rt_render_lit with lit's emitters and environment, this lens and this shutter (lit->lens and
-// lit->cam_close are set per frame here), aov / denoise from rt_render_aov_lens
+// lit->cam_close are set per frame here), aov / denoise from rt_render_aov_lens;
+// noise (with lit; rtp_main --lit --noise-target): through rt_render_lit_adaptive and rt_tonemap_spp; denoise_adaptive (with noise;
+// rtp_main --denoise-adaptive): each frame also filtered by rt_denoise_spp with its counts and moments and rt_render_aov_lens AOVs at
+// noise->min_spp, written through rt_tonemap_spp to "<frame file>.denoised"
 void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const rt_lens_params &lens, float shutter, bool aov, bool denoise,
                      const rt_nee_params *nee = nullptr, const rt_env *env = nullptr, const rt_env_params *env_params = nullptr,
-                     const rt_lit_params *lit = nullptr, const rt_adaptive_params *noise = nullptr);
-// rtp_main --gpu --adaptive: the orbit frame after frame on one GPU, each frame through rt_render_adaptive and rt_tonemap_spp
-void gpu_render_adaptive(const SceneParams &params, const rt_scene_desc &desc, const rt_adaptive_params &ap);
+                     const rt_lit_params *lit = nullptr, const rt_adaptive_params *noise = nullptr, bool denoise_adaptive = false);
+// rtp_main --gpu --adaptive: the orbit frame after frame on one GPU, each frame through rt_render_adaptive and rt_tonemap_spp;
+// denoise_adaptive (rtp_main --denoise-adaptive): each frame also filtered by rt_denoise_spp with its counts and moments and
+// rt_render_aov AOVs at ap.min_spp, written through rt_tonemap_spp to "<frame file>.denoised"
+void gpu_render_adaptive(const SceneParams &params, const rt_scene_desc &desc, const rt_adaptive_params &ap, bool denoise_adaptive = false);
 
 // … and the other split: every frame sharded in row bands over num_devices GPUs (<= 0: all) with one RCCL gather per
 // frame (rt_context, rt_render_sharded).  Same files, byte for byte.

@@ -41,6 +41,30 @@ int main(int argc, char *argv[]) {
         if (std::string(argv[a]) == "--denoise") denoise = true;
         if (std::string(argv[a]) == "--denoise-temporal") temporal = true;
     }
+    // extension: `--denoise-adaptive`, with `--adaptive T` or with `--lit … --noise-target T` and only with them: each adaptively sampled
+    // frame is also filtered by rt_denoise_spp — its own counts and moments, AOVs rendered at min_spp (rt_render_aov; on the lit path
+    // rt_render_aov_lens with the frame's lens and shutter) — and written through rt_tonemap_spp to "<frame file>.denoised".  Not with
+    // --denoise, --denoise-temporal or --aov.
+    bool denoise_adaptive = false;
+    {
+        bool adaptive_on = false, lit_flag = false, target_flag = false;
+        for (int a = 2; a < argc; ++a) {
+            const std::string arg = argv[a];
+            if (arg == "--denoise-adaptive") denoise_adaptive = true;
+            if (arg == "--adaptive") adaptive_on = true;
+            if (arg == "--lit") lit_flag = true;
+            if (arg == "--noise-target") target_flag = true;
+        }
+        if (denoise_adaptive && (denoise || temporal || aov)) {
+            std::cerr << "rtp_main: --denoise-adaptive writes <frame>.denoised from AOVs of its own: it cannot be combined with --denoise, "
+                         "--denoise-temporal or --aov\n";
+            return 2;
+        }
+        if (denoise_adaptive && !adaptive_on && !(lit_flag && target_flag)) {
+            std::cerr << "rtp_main: --denoise-adaptive filters adaptively sampled frames: it needs --adaptive T or --lit --noise-target T\n";
+            return 2;
+        }
+    }
     // extension: `--gpu --lit`: every frame through rt_render_lit on one GPU — light samples of the emissive spheres (`--nee [mis|light]`
     // picks their weighting), and with it, and only with it, `--env FILE[:N]` (with --env-mode, --env-scale, --env-up), `--lens R:F` and
     // `--motion-blur S` in any combination; --aov / --denoise as with --lens (first hits do not depend on the estimator).  Each of those
@@ -279,7 +303,8 @@ int main(int argc, char *argv[]) {
                 lit.nee = &lit_nee;
                 lit.env = lit_env;
                 lit.env_params = &lit_ep;
-                rtp::gpu_render_lens(params, desc, lens, shutter, aov, denoise, nullptr, nullptr, nullptr, &lit, noise_on ? &noise : nullptr);
+                rtp::gpu_render_lens(params, desc, lens, shutter, aov, denoise, nullptr, nullptr, nullptr, &lit, noise_on ? &noise : nullptr,
+                                     denoise_adaptive);
                 rt_env_destroy(lit_env);
                 return 0;
             }
@@ -329,7 +354,7 @@ int main(int argc, char *argv[]) {
                     std::cerr << "rtp_main: --adaptive cannot be combined with --shard\n";
                     return 2;
                 }
-            rtp::gpu_render_adaptive(params, desc, ap);
+            rtp::gpu_render_adaptive(params, desc, ap, denoise_adaptive);
             return 0;
         }
     // extension: `--gpu --shard N` splits EVERY frame over N GPUs (0 = all of the node) with one RCCL gather per frame

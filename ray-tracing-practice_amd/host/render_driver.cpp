@@ -196,6 +196,53 @@ void write_binary_frame(const PendingFile &f) {
     out.write(reinterpret_cast<const char *>(f.rgb.data()), static_cast<std::streamsize>(f.rgb.size()));
 }
 
+// rtp_main --denoise-adaptive: what both adaptive drivers keep for it — the frame's moments, AOVs at min_spp, rt_denoise's workspace
+// and the filtered frame — and the step after a frame's AOVs are rendered: rt_denoise_spp, rt_tonemap_spp, "<frame file>.denoised"
+struct AdaptiveDenoiser {
+    int width = 0, height = 0;
+    size_t num_pixels = 0;
+    float *d_moments = nullptr, *d_denoised = nullptr;
+    void *d_workspace = nullptr;
+    uint64_t workspace_bytes = 0;
+    rt_aov_buffers aov;
+
+    AdaptiveDenoiser(int w, int h) : width(w), height(h), num_pixels(static_cast<size_t>(w) * h) {
+        rt_aov_buffers_init(&aov);
+        workspace_bytes = rt_denoise_workspace_bytes(w, h);
+        RTP_CHECK(rt_device_alloc(num_pixels * 8, reinterpret_cast<void **>(&d_moments)));
+        RTP_CHECK(rt_device_alloc(num_pixels * 12, reinterpret_cast<void **>(&d_denoised)));
+        RTP_CHECK(rt_device_alloc(workspace_bytes, &d_workspace));
+        RTP_CHECK(rt_device_alloc(num_pixels * 12, reinterpret_cast<void **>(&aov.albedo_sum)));
+        RTP_CHECK(rt_device_alloc(num_pixels * 12, reinterpret_cast<void **>(&aov.normal_sum)));
+        RTP_CHECK(rt_device_alloc(num_pixels * 4, reinterpret_cast<void **>(&aov.depth_sum)));
+        RTP_CHECK(rt_device_alloc(num_pixels * 4, reinterpret_cast<void **>(&aov.hit_count)));
+    }
+    ~AdaptiveDenoiser() {
+        rt_device_free(d_moments);
+        rt_device_free(d_denoised);
+        rt_device_free(d_workspace);
+        rt_device_free(aov.albedo_sum);
+        rt_device_free(aov.normal_sum);
+        rt_device_free(aov.depth_sum);
+        rt_device_free(aov.hit_count);
+    }
+    AdaptiveDenoiser(const AdaptiveDenoiser &) = delete;
+    AdaptiveDenoiser &operator=(const AdaptiveDenoiser &) = delete;
+
+    // d_rgb: the frame's own byte buffer, free again once the frame's file is written
+    void write(const std::string &filename, const float *d_fb, const int32_t *d_spp, int32_t aov_samples, uint8_t *d_rgb) {
+        RTP_CHECK(rt_denoise_spp(d_fb, d_spp, d_moments, &aov, aov_samples, width, height, nullptr, d_workspace, workspace_bytes, d_denoised, nullptr));
+        RTP_CHECK(rt_tonemap_spp(d_denoised, d_spp, d_rgb, static_cast<int64_t>(num_pixels), nullptr));
+        PendingFile file;
+        file.path = filename + ".denoised";
+        file.width = width;
+        file.height = height;
+        file.rgb.resize(num_pixels * 3);
+        RTP_CHECK(rt_copy_to_host(file.rgb.data(), d_rgb, num_pixels * 3));
+        write_binary_frame(file);
+    }
+};
+
 }  // namespace
 
 void gpu_render_pipelined(const SceneParams &params, const rt_scene_desc &desc, int num_devices) {
@@ -260,9 +307,10 @@ void gpu_render_pipelined(const SceneParams &params, const rt_scene_desc &desc, 
 // rt_render_env with env_params (rtp_main --env), the AOVs likewise; lit: through rt_render_lit (rtp_main --lit) with this lens and
 // shutter, the AOVs through rt_render_aov_lens; noise (with lit; rtp_main --lit --noise-target): through
 // rt_render_lit_adaptive and rt_tonemap_spp — every pixel's bytes at its own sample count — and the printed count is the samples taken
+// denoise_adaptive (with noise; rtp_main --denoise-adaptive): as in gpu_render_adaptive, the AOVs from rt_render_aov_lens at noise->min_spp
 void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const rt_lens_params &lens, float shutter, bool aov, bool denoise,
                      const rt_nee_params *nee, const rt_env *env, const rt_env_params *env_params, const rt_lit_params *lit,
-                     const rt_adaptive_params *noise) {
+                     const rt_adaptive_params *noise, bool denoise_adaptive) {
     rt_scene *scene = nullptr;
     RTP_CHECK(rt_scene_create(&desc, &scene));
     const size_t num_pixels = static_cast<size_t>(params.width) * params.height;
@@ -278,6 +326,8 @@ void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const
         RTP_CHECK(rt_device_alloc(num_pixels * sizeof(int32_t), reinterpret_cast<void **>(&d_spp)));
         h_spp.resize(num_pixels);
     }
+    std::unique_ptr<AdaptiveDenoiser> spp_denoiser;
+    if (lit && noise && denoise_adaptive) spp_denoiser = std::make_unique<AdaptiveDenoiser>(params.width, params.height);
     rt_aov_buffers aov_bufs;
     rt_aov_buffers_init(&aov_bufs);
     std::vector<float> h_albedo, h_normal, h_depth, h_denoised;
@@ -318,7 +368,8 @@ void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const
             rt_lit_params frame_lit = *lit;
             frame_lit.cam_close = cam_close;
             frame_lit.lens = &lens;
-            RTP_CHECK(rt_render_lit_adaptive(scene, &cam, &frame_lit, noise, nullptr, 0, d_fb, d_spp, nullptr, nullptr, 1, nullptr));
+            RTP_CHECK(rt_render_lit_adaptive(scene, &cam, &frame_lit, noise, nullptr, 0, d_fb, d_spp, spp_denoiser ? spp_denoiser->d_moments : nullptr,
+                                             nullptr, 1, nullptr));
         } else if (lit) {
             rt_lit_params frame_lit = *lit;
             frame_lit.cam_close = cam_close;
@@ -341,6 +392,12 @@ void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const
         const auto t1 = std::chrono::steady_clock::now();
         const float ms = std::chrono::duration<float, std::milli>(t1 - t0).count();
         std::cout << n << "\t" << ms << "\t" << total_rays << "\n";
+        if (spp_denoiser) {          // (outside the frame's timed span) the first hits of this lens and shutter at min_spp samples
+            rt_camera_data aov_open = cam, aov_close = close;
+            aov_open.samples_per_pixel = aov_close.samples_per_pixel = noise->min_spp;
+            RTP_CHECK(rt_render_aov_lens(scene, &aov_open, cam_close ? &aov_close : nullptr, &lens, nullptr, 0, &spp_denoiser->aov, nullptr, 1, nullptr));
+            spp_denoiser->write(filename, d_fb, d_spp, noise->min_spp, d_rgb);
+        }
         if (aov || denoise) {          // (outside the frame's timed span, as in gpu_render)
             if (!lit && (nee || env)) RTP_CHECK(rt_render_aov_samples(scene, &cam, nullptr, 0, &aov_bufs, nullptr, 1, nullptr));
             else RTP_CHECK(rt_render_aov_lens(scene, &cam, cam_close, &lens, nullptr, 0, &aov_bufs, nullptr, 1, nullptr));
@@ -381,8 +438,9 @@ void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const
 // ---- adaptive sampling (rtp_main --gpu --adaptive) ----------------------------------------------------------
 // The orbit of gpu_render, each frame rendered by rt_render_adaptive and saved through rt_tonemap_spp: every pixel's bytes are the
 // saver arithmetic with its own sample count as the divisor (the mean of its samples).  Prints frame, milliseconds and the samples
-// the frame took.
-void gpu_render_adaptive(const SceneParams &params, const rt_scene_desc &desc, const rt_adaptive_params &ap) {
+// the frame took.  denoise_adaptive (rtp_main --denoise-adaptive): the frame's moments are kept, its AOVs rendered at
+// min_spp, and rt_denoise_spp's output goes through rt_tonemap_spp to "<frame file>.denoised".
+void gpu_render_adaptive(const SceneParams &params, const rt_scene_desc &desc, const rt_adaptive_params &ap, bool denoise_adaptive) {
     rt_scene *scene = nullptr;
     RTP_CHECK(rt_scene_create(&desc, &scene));
     const size_t num_pixels = static_cast<size_t>(params.width) * params.height;
@@ -393,6 +451,8 @@ void gpu_render_adaptive(const SceneParams &params, const rt_scene_desc &desc, c
     RTP_CHECK(rt_device_alloc(num_pixels * sizeof(int32_t), reinterpret_cast<void **>(&d_spp)));
     RTP_CHECK(rt_device_alloc(num_pixels * 3, reinterpret_cast<void **>(&d_rgb)));
     std::vector<int32_t> spp(num_pixels);
+    std::unique_ptr<AdaptiveDenoiser> spp_denoiser;
+    if (denoise_adaptive) spp_denoiser = std::make_unique<AdaptiveDenoiser>(params.width, params.height);
     for (int n = 0; n < params.num_frames; ++n) {
         Vec3 eye, target;
         orbit_pose(params, n, eye, target);
@@ -403,7 +463,7 @@ void gpu_render_adaptive(const SceneParams &params, const rt_scene_desc &desc, c
         camera.background_color = Vec3(0, 0, 0);
         const rt_camera_data cam = camera.build_camera_data();
         const auto t0 = std::chrono::steady_clock::now();
-        RTP_CHECK(rt_render_adaptive(scene, &cam, nullptr, &ap, d_fb, d_spp, nullptr, nullptr, 1, nullptr));
+        RTP_CHECK(rt_render_adaptive(scene, &cam, nullptr, &ap, d_fb, d_spp, spp_denoiser ? spp_denoiser->d_moments : nullptr, nullptr, 1, nullptr));
         RTP_CHECK(rt_tonemap_spp(d_fb, d_spp, d_rgb, static_cast<int64_t>(num_pixels), nullptr));
         PendingFile file;
         file.path = frame_filename(params.output_pattern, n);
@@ -417,7 +477,12 @@ void gpu_render_adaptive(const SceneParams &params, const rt_scene_desc &desc, c
         long long samples = 0;
         for (int32_t k : spp) samples += k;
         std::cout << n << "\t" << ms << "\t" << samples << "\n";
+        if (spp_denoiser) {          // (outside the frame's timed span) cam carries min_spp: the AOVs of the frame's first samples
+            RTP_CHECK(rt_render_aov(scene, &cam, nullptr, &spp_denoiser->aov, nullptr, 1, nullptr));
+            spp_denoiser->write(file.path, d_fb, d_spp, ap.min_spp, d_rgb);
+        }
     }
+    spp_denoiser.reset();
     rt_device_free(d_fb);
     rt_device_free(d_spp);
     rt_device_free(d_rgb);

@@ -393,6 +393,7 @@ RTP_AMD_SYMBOLS = [
     "rt_trace_samples_env",
     "rt_lit_params_init", "rt_render_lit", "rt_trace_samples_lit",
     "rt_render_lit_adaptive",
+    "rt_denoise_spp",
 ]
 
 _host = None
@@ -532,6 +533,9 @@ def amd_lib():
             lib.rt_render_lit_adaptive.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(LitParams), C.POINTER(AdaptiveParams),
                                                    C.POINTER(Shard), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                                    C.POINTER(Timing)]
+        if hasattr(lib, "rt_denoise_spp"):
+            lib.rt_denoise_spp.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(AovBuffers), C.c_int32, C.c_int32, C.c_int32,
+                                           C.POINTER(DenoiseParams), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         lib.rt_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         lib.rt_last_timing.argtypes = [C.c_void_p, C.POINTER(Timing)]
         lib.rt_timing_init.argtypes = [C.POINTER(Timing)]
@@ -688,23 +692,25 @@ def denoise_params(**params):
 _denoise_workspaces = {}
 
 
+def _denoise_workspace(width, height):
+    """(address, bytes) of the shared rt_denoise workspace of a width x height image ((None, 0) for an empty image)."""
+    lib = amd_lib()
+    need = lib.rt_denoise_workspace_bytes(width, height)
+    workspace = _denoise_workspaces.get(need)
+    if workspace is None and need > 0:
+        d = C.c_void_p()
+        _check(lib.rt_device_alloc(need, C.byref(d)), "rt_device_alloc")
+        workspace = _denoise_workspaces[need] = (d.value, need)
+    return workspace or (None, 0)
+
+
 def denoise(d_fb, aov_ptrs, width, height, spp, d_out, stream=None, workspace=None, **params):
     """rt_denoise on device addresses: d_fb (the beauty sums), aov_ptrs {"albedo", "normal", "depth", "hits"} → device address (as
     DeviceScene.render_aov takes them), d_out (width * height * 3 floats).  Only enqueues on `stream` (None = default stream).
     params: rt_denoise_params fields."""
     lib = amd_lib()
-    b = AovBuffers()
-    for key, field, _, _ in AOV_CHANNELS:
-        if aov_ptrs.get(key):
-            setattr(b, field, aov_ptrs[key])
-    if workspace is None:
-        need = lib.rt_denoise_workspace_bytes(width, height)
-        workspace = _denoise_workspaces.get(need)
-        if workspace is None and need > 0:
-            d = C.c_void_p()
-            _check(lib.rt_device_alloc(need, C.byref(d)), "rt_device_alloc")
-            workspace = _denoise_workspaces[need] = (d.value, need)
-    ws_ptr, ws_bytes = workspace or (None, 0)
+    b = _aov_struct(aov_ptrs)
+    ws_ptr, ws_bytes = workspace or _denoise_workspace(width, height)
     p = denoise_params(**params)
     _check(lib.rt_denoise(C.c_void_p(d_fb), C.byref(b), width, height, spp, C.byref(p), C.c_void_p(ws_ptr), ws_bytes, C.c_void_p(d_out),
                           C.c_void_p(stream or 0)), "rt_denoise")
@@ -716,6 +722,18 @@ def _aov_struct(aov_ptrs):
         if aov_ptrs.get(key):
             setattr(b, field, aov_ptrs[key])
     return b
+
+
+def denoise_spp(d_fb, d_spp, d_moments, aov_ptrs, aov_spp, width, height, d_out, stream=None, workspace=None, **params):
+    """rt_denoise_spp on device addresses: d_fb, d_spp and d_moments (or None) as DeviceScene.render_adaptive / render_lit_adaptive
+    wrote them for a whole frame, aov_ptrs {"albedo", "normal", "depth", "hits"} → device address of the AOV sums at aov_spp samples
+    per pixel, d_out (width * height * 3 floats).  Only enqueues on `stream` (None = default stream).  params: rt_denoise_params
+    fields."""
+    b = _aov_struct(aov_ptrs)
+    ws_ptr, ws_bytes = workspace or _denoise_workspace(width, height)
+    p = denoise_params(**params)
+    _check(amd_lib().rt_denoise_spp(C.c_void_p(d_fb), C.c_void_p(d_spp), C.c_void_p(d_moments or 0), C.byref(b), aov_spp, width, height,
+                                    C.byref(p), C.c_void_p(ws_ptr), ws_bytes, C.c_void_p(d_out), C.c_void_p(stream or 0)), "rt_denoise_spp")
 
 
 def denoise_temporal(d_fb, aov_ptrs, cam, d_history_prev, d_history_next, history_bytes, d_out, workspace, stream=None, **params):
@@ -774,6 +792,35 @@ def denoise_to_host(fb_sum, aov, spp, **params):
         _check(lib.rt_device_alloc(fb.nbytes or 4, C.byref(d_out)), "rt_device_alloc")
         dev["out"] = d_out
         denoise(dev["fb"].value, {k: dev[k].value for k in ("albedo", "normal", "depth", "hits")}, width, height, spp, d_out.value, **params)
+        out = np.empty_like(fb)
+        _check(lib.rt_copy_to_host(out.ctypes.data, d_out, out.nbytes), "rt_copy_to_host")
+    finally:
+        for d in dev.values():
+            lib.rt_device_free(d)
+    return out
+
+
+def denoise_spp_to_host(fb_sum, spp, moments, aov, aov_spp, **params):
+    """rt_denoise_spp of host arrays: fb_sum (H, W, 3) float32, spp (H, W) int32 and moments (H, W, 2) float32 or None as
+    DeviceScene.render_adaptive_to_host returns them, aov the dict of DeviceScene.render_aov_to_host at aov_spp samples per pixel.
+    Returns the (H, W, 3) float32 output, each pixel the sum over its own samples like fb_sum.  Synchronous (default stream)."""
+    lib = amd_lib()
+    fb = np.ascontiguousarray(fb_sum, dtype=np.float32)
+    height, width = fb.shape[:2]
+    arrays = {"fb": fb, "spp": np.ascontiguousarray(spp, dtype=np.int32)}
+    if moments is not None:
+        arrays["moments"] = np.ascontiguousarray(moments, dtype=np.float32)
+    for key, _, dtype, _ in AOV_CHANNELS[:4]:
+        arrays[key] = np.ascontiguousarray(aov[key], dtype=dtype)
+    dev = {}
+    try:
+        for key, a in arrays.items():
+            dev[key] = _upload(a)
+        d_out = C.c_void_p()
+        _check(lib.rt_device_alloc(fb.nbytes or 4, C.byref(d_out)), "rt_device_alloc")
+        dev["out"] = d_out
+        denoise_spp(dev["fb"].value, dev["spp"].value, dev["moments"].value if "moments" in dev else None,
+                    {k: dev[k].value for k in ("albedo", "normal", "depth", "hits")}, aov_spp, width, height, d_out.value, **params)
         out = np.empty_like(fb)
         _check(lib.rt_copy_to_host(out.ctypes.data, d_out, out.nbytes), "rt_copy_to_host")
     finally:
