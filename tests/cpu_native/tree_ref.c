@@ -139,16 +139,19 @@ static float importance(const light_tree *t, int32_t c, v3 x) {
     const float rho = t->sphere[4 * c + 3];
     return t->weight[c] / fmaxf(d2, rho * rho);
 }
-static float left_probability(const light_tree *t, int32_t node, v3 x) {
+/* *fell (may be NULL) is set when the node's q stood in for the importances; it is never cleared here */
+static float left_probability(const light_tree *t, int32_t node, v3 x, int *fell) {
     const float il = importance(t, t->left[node], x), ir = importance(t, t->right[node], x);
     const float s = il + ir;
-    return (s > 0.0f && s < INFINITY) ? il / s : t->q[node];
+    if (s > 0.0f && s < INFINITY) return il / s;
+    if (fell) *fell = 1;
+    return t->q[node];
 }
-static int32_t tree_pick(const light_tree *t, uint32_t *nee, v3 x, float *p_out) {
+static int32_t tree_pick(const light_tree *t, uint32_t *nee, v3 x, float *p_out, int *fell) {
     int32_t node = 0;
     float p = 1.0f;
     while (t->entry[node] < 0) {
-        const float pl = left_probability(t, node, x);
+        const float pl = left_probability(t, node, x, fell);
         const float u = orc_random_float(nee);
         if (u < pl) {
             p = p * pl;
@@ -161,11 +164,11 @@ static int32_t tree_pick(const light_tree *t, uint32_t *nee, v3 x, float *p_out)
     *p_out = p;
     return t->entry[node];
 }
-static float tree_pmf(const light_tree *t, int32_t e, v3 x) {
+static float tree_pmf(const light_tree *t, int32_t e, v3 x, int *fell) {
     int32_t node = 0;
     float p = 1.0f;
     for (int32_t i = 0; i < t->depth[e]; ++i) {
-        const float pl = left_probability(t, node, x);
+        const float pl = left_probability(t, node, x, fell);
         if ((t->path[e] >> i) & 1u) {
             p = p * (1.0f - pl);
             node = t->right[node];
@@ -177,8 +180,25 @@ static float tree_pmf(const light_tree *t, int32_t e, v3 x) {
     return p;
 }
 
-/* steps 2 to 4 / 2p to 4p for the picked entry e with the probability pmf of that pick: 1 = a shadow ray is asked for */
-static int entry_sample(const rt_scene_desc *sc, const emit_tab *T, int32_t e, float pmf, uint32_t *nee, v3 x, v3 n, v3 a, v3 beta, v3 *dir, v3 *c) {
+/* the tallies of tree_trace's stats, in its order (tests/tree_reference.py names them the same way) */
+enum {
+    ST_INSIDE_PARENT = 0,   /* sampling vertices inside the sphere of their picked leaf's parent */
+    ST_WEIGHTED,            /* BSDF hits on table entries that were weighted */
+    ST_DROP_INSIDE,         /* light samples dropped at step 2: the point is not outside the sphere (!(d2 > rr)) */
+    ST_DROP_OMEGA,          /* light samples dropped at step 2: om <= 0 */
+    ST_DROP_COS,            /* light samples dropped at 3p: cos_l < 1e-8 */
+    ST_SHADOW_OTHER_ENTRY,  /* shadow rays whose closest hit is another table entry */
+    ST_SHADOW_NON_TABLE,    /* shadow rays whose closest hit is a primitive outside the table */
+    ST_HIT_PL_ZERO,         /* weighted BSDF hits with pl == 0 */
+    ST_Q_FALLBACK,          /* descents and path products in which a node's q stood in for the importances */
+    ST_PICK_NONE,           /* picks that returned no entry */
+    ST_COUNT
+};
+
+/* steps 2 to 4 / 2p to 4p for the picked entry e with the probability pmf of that pick: 1 = a shadow ray is asked for.  stats (may be NULL)
+ * counts why a sample was dropped; it changes nothing else */
+static int entry_sample(const rt_scene_desc *sc, const emit_tab *T, int32_t e, float pmf, uint32_t *nee, v3 x, v3 n, v3 a, v3 beta, v3 *dir, v3 *c,
+                        int64_t *stats) {
     const float pb = RT_NEE_PB;
     float pl;
     v3 emit;
@@ -205,7 +225,11 @@ static int entry_sample(const rt_scene_desc *sc, const emit_tab *T, int32_t e, f
         v3 y;
         for (int k = 0; k < 3; ++k) y.e[k] = (p->base.e[k] + ua * p->u.e[k]) + ub * p->v.e[k];
         float pa;
-        if (!plane_pa(x, y, p, T->area[e], dir, &pa)) return 0;
+        if (!plane_pa(x, y, p, T->area[e], dir, &pa)) {
+            const v3 xy = sub(y, x);
+            if (stats && dot(xy, xy) > 0.0f) stats[ST_DROP_COS]++;      /* (plane_pa's other refusal is d2 == 0) */
+            return 0;
+        }
         if (!(dot(*dir, n) > 0.0f)) return 0;
         pl = pmf * pa;
         emit = from_rt(sc->materials[p->material_idx].emit);
@@ -213,7 +237,10 @@ static int entry_sample(const rt_scene_desc *sc, const emit_tab *T, int32_t e, f
         const rt_sphere *s = &sc->spheres[T->index[e]];
         v3 w;
         float d2, om;
-        if (!cone_of(x, s, &w, &d2, &om)) return 0;
+        if (!cone_of(x, s, &w, &d2, &om)) {
+            if (stats) stats[d2 > s->radius * s->radius ? ST_DROP_OMEGA : ST_DROP_INSIDE]++;
+            return 0;
+        }
         const float u1 = orc_random_float(nee);
         const float cos_t = 1.0f - u1 * om;
         const float sin_t = sqrtf(fmaxf(0.0f, 1.0f - cos_t * cos_t));
@@ -248,7 +275,7 @@ typedef struct {
     lit_ctx X;
     const light_tree *tree;
     int32_t select;
-    int64_t *stats;        /* NULL, or: [0] vertices that sampled inside the root's left or right child's sphere … (tree_trace) */
+    int64_t *stats;        /* NULL, or the ST_COUNT tallies above (tree_trace) */
 } tree_ctx;
 
 static v3 ray_color_tree(const tree_ctx *Y, ray r, uint32_t *seed, uint32_t *nee, uint32_t *env, int32_t *rays_out) {
@@ -299,12 +326,19 @@ static v3 ray_color_tree(const tree_ctx *Y, ray r, uint32_t *seed, uint32_t *nee
             if (e >= 0) {
                 v3 w;
                 float d2, om, pa, pl = 0.0f;
+                int fell = 0;
                 if (pt == 1) {
-                    if (plane_pa(cur.o, rec.point, &sc->planes[pi], T->area[e], &w, &pa)) pl = (Y->select ? tree_pmf(Y->tree, e, cur.o) : T->pmf[e]) * pa;
-                } else if (cone_of(cur.o, &sc->spheres[pi], &w, &d2, &om)) pl = (Y->select ? tree_pmf(Y->tree, e, cur.o) : T->pmf[e]) * pdf_cone(om);
+                    if (plane_pa(cur.o, rec.point, &sc->planes[pi], T->area[e], &w, &pa))
+                        pl = (Y->select ? tree_pmf(Y->tree, e, cur.o, &fell) : T->pmf[e]) * pa;
+                } else if (cone_of(cur.o, &sc->spheres[pi], &w, &d2, &om))
+                    pl = (Y->select ? tree_pmf(Y->tree, e, cur.o, &fell) : T->pmf[e]) * pdf_cone(om);
                 const float wb = T->mis ? (pb * pb) / (pb * pb + pl * pl) : (pl > 0.0f ? 0.0f : 1.0f);
                 emitted = scale(wb, emitted);
-                if (Y->stats) Y->stats[1]++;
+                if (Y->stats) {
+                    Y->stats[ST_WEIGHTED]++;
+                    if (pl == 0.0f) Y->stats[ST_HIT_PL_ZERO]++;
+                    if (fell) Y->stats[ST_Q_FALLBACK]++;
+                }
             }
         }
         final_color = add(final_color, emitted);
@@ -339,7 +373,9 @@ static v3 ray_color_tree(const tree_ctx *Y, ray r, uint32_t *seed, uint32_t *nee
                 int32_t e;
                 float pmf = 0.0f;
                 if (Y->select) {
-                    e = tree_pick(Y->tree, nee, rec.point, &pmf);
+                    int fell = 0;
+                    e = tree_pick(Y->tree, nee, rec.point, &pmf, &fell);
+                    if (Y->stats && fell) Y->stats[ST_Q_FALLBACK]++;
                     if (Y->stats && Y->tree->nodes > 1) {
                         /* is the vertex inside the sphere of the picked leaf's parent?  (the importance's clamp is at work there) */
                         int32_t node = 0, parent = 0;
@@ -349,7 +385,7 @@ static v3 ray_color_tree(const tree_ctx *Y, ray r, uint32_t *seed, uint32_t *nee
                         }
                         const float *s = Y->tree->sphere + 4 * parent;
                         const v3 w = sub(V(s[0], s[1], s[2]), rec.point);
-                        if (dot(w, w) < s[3] * s[3]) Y->stats[0]++;
+                        if (dot(w, w) < s[3] * s[3]) Y->stats[ST_INSIDE_PARENT]++;
                     }
                 } else {
                     const float u = orc_random_float(nee);
@@ -357,9 +393,12 @@ static v3 ray_color_tree(const tree_ctx *Y, ray r, uint32_t *seed, uint32_t *nee
                     while (e < T->count && !(u < T->cdf[e])) ++e;
                     if (e < T->count) pmf = T->pmf[e];
                 }
-                if (e < T->count && entry_sample(sc, T, e, pmf, nee, rec.point, rec.normal, albedo, beta, &shadow.d, &c)) {
+                if (Y->stats && !(e < T->count)) Y->stats[ST_PICK_NONE]++;
+                if (e < T->count && entry_sample(sc, T, e, pmf, nee, rec.point, rec.normal, albedo, beta, &shadow.d, &c, Y->stats)) {
                     nrays++;
-                    if (closest(sc, &shadow, &srec, &spt, &spi) && spt == T->kind[e] && spi == T->index[e]) final_color = add(final_color, c);
+                    const int hit = closest(sc, &shadow, &srec, &spt, &spi);
+                    if (hit && spt == T->kind[e] && spi == T->index[e]) final_color = add(final_color, c);
+                    else if (hit && Y->stats) Y->stats[tab_find(T, spt, spi) >= 0 ? ST_SHADOW_OTHER_ENTRY : ST_SHADOW_NON_TABLE]++;
                 }
             }
             if (sky_sampled && sky_sample(X->M, ep, env, rec.normal, albedo, beta, &shadow.d, &c, X->linear)) {
@@ -418,7 +457,7 @@ void tree_pmf_points(const rt_scene_desc *sc, int32_t sample_planes, int64_t cou
     make_tab(sc, 1, 1, sample_planes, &T);
     make_tree(sc, &T, &t);
     for (int64_t k = 0; k < count; ++k)
-        for (int32_t e = 0; e < t.entries; ++e) pmf[k * t.entries + e] = tree_pmf(&t, e, V(points[3 * k], points[3 * k + 1], points[3 * k + 2]));
+        for (int32_t e = 0; e < t.entries; ++e) pmf[k * t.entries + e] = tree_pmf(&t, e, V(points[3 * k], points[3 * k + 1], points[3 * k + 2]), NULL);
     free_tree(&t);
     free_tab(&T);
 }
@@ -434,9 +473,9 @@ int64_t tree_pick_counts(const rt_scene_desc *sc, int32_t sample_planes, const f
     for (int32_t e = 0; e < t.entries; ++e) counts[e] = 0;
     for (int64_t k = 0; k < draws && t.entries > 0; ++k) {
         float p;
-        const int32_t e = tree_pick(&t, &seed, x, &p);
+        const int32_t e = tree_pick(&t, &seed, x, &p, NULL);
         counts[e]++;
-        if (p != tree_pmf(&t, e, x)) bad++;
+        if (p != tree_pmf(&t, e, x, NULL)) bad++;
     }
     free_tree(&t);
     free_tab(&T);
@@ -451,8 +490,9 @@ static void make_tree_ctx(const rt_scene_desc *sc, const rt_camera_data *cam, co
     Y->stats = NULL;
 }
 
-/* count samples (ijs: i, j, s) → radiance, rays, the three final RNG states; stats (2 words, may be NULL): how many sampling vertices lay
- * inside the sphere of their picked leaf's parent, and how many BSDF hits on table entries were weighted */
+/* count samples (ijs: i, j, s) → radiance, rays, the three final RNG states; stats (ST_COUNT words, may be NULL): the tallies named above —
+ * the first two are how many sampling vertices lay inside the sphere of their picked leaf's parent, and how many BSDF hits on table entries
+ * were weighted */
 void tree_trace(const rt_scene_desc *sc, const rt_camera_data *cam, const tree_cfg *cfg, int64_t count, const int32_t *ijs, float *radiance, int32_t *rays,
                 uint32_t *seeds, uint32_t *nee_seeds, uint32_t *env_seeds, int32_t linear, int64_t *stats) {
     emit_tab T;
@@ -460,7 +500,7 @@ void tree_trace(const rt_scene_desc *sc, const rt_camera_data *cam, const tree_c
     light_tree t;
     tree_ctx Y;
     make_tree_ctx(sc, cam, cfg, &T, &M, &t, linear, &Y);
-    if (stats) stats[0] = stats[1] = 0;
+    if (stats) memset(stats, 0, ST_COUNT * sizeof(int64_t));
     Y.stats = stats;
     for (int64_t k = 0; k < count; ++k) {
         const v3 c = tree_sample_of(&Y, ijs[3 * k], ijs[3 * k + 1], ijs[3 * k + 2], &rays[k], &seeds[k], &nee_seeds[k], &env_seeds[k]);

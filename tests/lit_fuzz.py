@@ -1,0 +1,359 @@
+"""Random lit scenes for the light-sampling kernels (TEST INFRASTRUCTURE): scenes, environment maps, rotations, cameras and
+lenses made deterministically from a seed and a trial index, the one large night scene, the dispatch rule of rt_capi.hip as a pure
+function, and the parameter lists tests/test_lit_fuzz.py iterates over — on the CPU to show that every kernel is reached, and on the GPU to
+reach them.
+
+What a scene is made of follows the clauses of include/rtp_amd.h that no hand-made scene exercises: points inside an emissive sphere (a
+dome), overlapping, concentric and touching emitters, coincident emissive planes, degenerate planes between table entries (gaps), an
+emissive plane of an unsupported type, a DIFFUSE_LIGHT that emits nothing, scattering materials that emit, emit with zero channels and
+weights over many decades."""
+import collections
+import functools
+
+import numpy as np
+
+import emit_reference as emr
+import rtp_bindings as rb
+import tree_reference as tr
+
+MAT_LAMBERTIAN, MAT_METAL, MAT_DIELECTRIC, MAT_LIGHT = 0, 1, 2, 3
+QUAD, ELLIPSE, TRIANGLE, UNSUPPORTED = 0, 1, 2, 3
+
+# material slots of a fuzz scene
+(M_LAMB_A, M_LAMB_B, M_METAL, M_GLASS, M_LIGHT_A, M_LIGHT_B, M_LIGHT_GREEN, M_LAMB_GLOW, M_LIGHT_DARK, M_DOME, M_GROUND, M_FAINT) = range(12)
+EMISSIVE = (M_LIGHT_A, M_LIGHT_B, M_LIGHT_GREEN, M_LAMB_GLOW)
+DULL = (M_LAMB_A, M_LAMB_B, M_METAL, M_GLASS, M_LIGHT_DARK)
+
+# eight scenes: trial = position in the list.  Trials 0, 3, 6 have the dome; 1, 4, 7 the overlapping group; even ones the ground
+SEEDS = (2101, 2102, 2103, 2104, 2105, 2116, 2107, 2108)          # (2116 replaces 2106: test_lit_fuzz.py says why)
+DARK_TRIAL = 5          # the trial whose dark twin (every emit zeroed: an empty table) the identity test runs
+ENV_SIZES = (1, 2, 3, 5, 16, 37)
+
+
+def material(kind, albedo=(0.5, 0.5, 0.5), emit=(0, 0, 0), fuzz=0.0, ir=1.5):
+    m = rb.Material()
+    m.type = kind
+    m.fuzz = fuzz
+    m.ir = ir
+    for k in range(3):
+        m.albedo.e[k] = albedo[k]
+        m.emit.e[k] = emit[k]
+    return m
+
+
+def random_rot(rng):
+    """A rotation matrix (rows: world → environment) from the QR of a normal matrix; det +1."""
+    q, r = np.linalg.qr(rng.normal(size=(3, 3)))
+    q = q * np.sign(np.diag(r))[None, :]
+    if np.linalg.det(q) < 0:
+        q[:, 0] = -q[:, 0]
+    return q.astype(np.float32)
+
+
+def random_env(rng, trial):
+    """(n, n, 3) float32: n cycles through ENV_SIZES; for n >= 3 one whole row and every component below 0.3 are zero; for odd trials
+    with n >= 5 the map is near-black but for one hot texel."""
+    n = ENV_SIZES[trial % len(ENV_SIZES)]
+    m = rng.uniform(0.0, 1.5, size=(n, n, 3))
+    dark_row = -1
+    if n >= 3:
+        m[m < 0.3] = 0.0
+        dark_row = int(rng.integers(0, n))
+        m[dark_row] = 0.0
+    if trial % 2 == 1 and n >= 5:
+        m *= 0.05
+        row, col = int(rng.integers(0, n)), int(rng.integers(0, n))
+        m[(row + 1) % n if row == dark_row else row, col] = (300.0, 250.0, 200.0)          # (the row of weight 0 stays one)
+    return m.astype(np.float32)
+
+
+def random_lit_scene(rng, trial, dark=False):
+    """An rb.HostScene of 3 – 40 random spheres and 0 – 14 random planes (none on one trial in four), about a third of them emissive, plus
+    what `trial` adds.  dark: the same scene with every emit zeroed — its emitter table is empty."""
+    u = rng.uniform
+    mats = [None] * 12
+    mats[M_LAMB_A] = material(MAT_LAMBERTIAN, u(0.2, 0.9, 3))
+    mats[M_LAMB_B] = material(MAT_LAMBERTIAN, u(0.2, 0.9, 3))
+    mats[M_METAL] = material(MAT_METAL, u(0.4, 0.9, 3), fuzz=float(u(0.0, 0.7)))
+    mats[M_GLASS] = material(MAT_DIELECTRIC, ir=1.5)
+    mats[M_LIGHT_A] = material(MAT_LIGHT, emit=u(0.5, 8.0, 3))
+    mats[M_LIGHT_B] = material(MAT_LIGHT, emit=u(0.5, 8.0, 3))
+    mats[M_LIGHT_GREEN] = material(MAT_LIGHT, emit=(0.0, float(u(0.5, 8.0)), 0.0))
+    mats[M_LAMB_GLOW] = material(MAT_LAMBERTIAN, u(0.2, 0.8, 3), emit=u(0.2, 2.0, 3))
+    mats[M_LIGHT_DARK] = material(MAT_LIGHT, emit=(0.0, 0.0, 0.0))
+    mats[M_DOME] = material(MAT_LIGHT, emit=u(0.2, 1.0, 3))
+    mats[M_GROUND] = material(MAT_LAMBERTIAN, (0.5, 0.5, 0.5))
+    mats[M_FAINT] = material(MAT_LIGHT, emit=(0.5, 0.5, 0.5))
+
+    def pick_material():
+        return int(rng.choice(EMISSIVE)) if rng.random() < 1.0 / 3.0 else int(rng.choice(DULL))
+
+    spheres = []
+    for _ in range(int(rng.integers(3, 41))):
+        spheres.append([*u(-5, 5, 3), 10.0 ** u(-1.3, 0.2), pick_material()])
+    planes = []
+    for _ in range(int(rng.integers(0, 15)) * (trial % 4 != 3)):
+        mat = int(rng.choice(EMISSIVE)) if rng.random() < 0.4 else int(rng.choice(DULL))
+        planes.append([*u(-5, 5, 3), *u(-3, 3, 3), *u(-3, 3, 3), mat, int(rng.integers(0, 3))])
+    if trial % 2 == 0:
+        spheres.append([0.0, -1006.0, 0.0, 1000.0, M_GROUND])
+    if trial % 3 == 0:
+        spheres.append([0.0, 0.0, 0.0, 40.0, M_DOME])
+        if trial % 2 == 0:
+            # weights over more than six decades: 1.5 * 0.01^2 beside the dome's >= 0.6 * 40^2, at a distance where its cone rounds away
+            spheres.append([0.0, 30.0, 0.0, 0.01, M_FAINT])
+    if trial % 3 == 1:
+        c = u(-4, 4, 3)
+        spheres.append([*c, 0.8, M_LIGHT_A])                                   # two overlapping emitters …
+        spheres.append([c[0] + 0.7, c[1], c[2], 0.6, M_LIGHT_B])
+        spheres.append([*c, 0.3, M_LIGHT_GREEN])                               # … a third, concentric inside the first
+        d = u(-4, 4, 3)
+        spheres.append([*d, 0.5, M_LAMB_A])                                    # a non-emitter and an emitter that touches it
+        spheres.append([d[0], d[1] + 0.75, d[2], 0.25, M_LIGHT_A])
+    if len(planes) >= 3:
+        planes[1][6:9] = [2.0 * x for x in planes[1][3:6]]                     # u ∥ v: no area, so it is in no table …
+        planes[1][9] = M_LIGHT_A                                               # … though it emits
+        planes[0][9] = M_LIGHT_A
+        planes[2] = list(planes[0])                                            # two coincident emissive planes
+        planes[2][9] = M_LIGHT_B
+    if len(planes) >= 5:
+        planes[4][9], planes[4][10] = M_LIGHT_B, UNSUPPORTED                   # an emissive plane of a type the table does not take
+    if dark:
+        for m in mats:
+            m.emit.e[0] = m.emit.e[1] = m.emit.e[2] = 0.0
+    return rb.HostScene.from_arrays(np.array(spheres, np.float32), np.array(planes, np.float32).reshape(-1, 11), mats)
+
+
+class Case:
+    """One fuzz case: the scene and everything a call on it needs.  camera(w, h, spp, depth) → the open camera, close(…) → the camera at
+    shutter close (None on the trials without motion); env: an (n, n, 3) map or None; rot: the 9 floats of rt_env_params.rot."""
+
+    def __init__(self, trial, dark=False):
+        self.trial = trial
+        self.seed = SEEDS[trial]
+        rng = np.random.default_rng([self.seed, trial])
+        self.host = random_lit_scene(rng, trial, dark)
+        d = rng.normal(size=3)
+        d[1] = abs(d[1]) + 0.3
+        self.eye = tuple(float(x) for x in 9.0 * d / np.linalg.norm(d))
+        self.eye_close = tuple(float(x) for x in np.array(self.eye) + rng.uniform(-0.3, 0.3, 3))
+        self.background = tuple(float(x) for x in rng.uniform(0.0, 0.3, 3))
+        self.vfov = float(rng.uniform(30.0, 50.0))
+        self.lens = (float(rng.uniform(0.05, 0.3)), 9.0)
+        self.motion = trial % 2 == 1
+        self.dome = trial % 3 == 0
+        # the dome hides the sky, so the scenes under it have no environment
+        self.env = None if self.dome else random_env(rng, trial)
+        self.rot = tuple(float(x) for x in random_rot(rng).ravel())
+        self.name = f"trial {trial} seed {self.seed}"
+
+    def camera(self, w, h, spp, depth=50):
+        return rb.make_camera(w, h, self.vfov, self.eye, (0, 0, 0), self.background, spp, depth)
+
+    def close(self, w, h, spp, depth=50):
+        return rb.make_camera(w, h, self.vfov, self.eye_close, (0, 0, 0), self.background, spp, depth) if self.motion else None
+
+    def env_params(self, mode, scale=0.8):
+        return dict(mode=mode, scale=scale, rot=self.rot)
+
+    def lens_dict(self):
+        return dict(lens_radius=self.lens[0], focus_distance=self.lens[1])
+
+    def has_planes(self, sample_planes=1):
+        """Does the table of sample_planes hold a plane?"""
+        return bool(sample_planes) and bool((emr.table(self.host, 1)[0] == 1).any())
+
+    def entries(self, sample_planes):
+        return len(emr.table(self.host, sample_planes)[0])
+
+
+@functools.lru_cache(maxsize=None)
+def case(trial, dark=False):
+    return Case(trial, dark)
+
+
+TRIALS = tuple(range(len(SEEDS)))
+ENV_TRIALS = tuple(t for t in TRIALS if t % 3 != 0)
+
+
+def large_night_scene():
+    """HostScene.rtiow(half_extent=40) with every eighth small sphere made a light, as test_light_tree.night_rtiow does it."""
+    base = rb.HostScene.rtiow(half_extent=40)
+    d = base.desc
+    spheres, mats = [], []
+    for i in range(d.num_spheres):
+        s = d.spheres[i]
+        m = d.materials[s.material_idx]
+        if 0 < i < d.num_spheres - 3 and i % 8 == 5:
+            m = material(MAT_LIGHT, emit=(6.0, 4.5, 3.0) if i % 16 == 5 else (1.5, 2.0, 3.0))
+        spheres.append([s.center.e[0], s.center.e[1], s.center.e[2], s.radius, len(mats)])
+        mats.append(rb.Material.from_buffer_copy(m))
+    night = rb.HostScene.from_arrays(np.array(spheres, np.float32), np.zeros((0, 11), np.float32), mats)
+    base.close()
+    return night
+
+
+@functools.lru_cache(maxsize=None)
+def large():
+    host = large_night_scene()
+    t = tr.tree(host, 0)
+    assert len(t["path"]) >= 512 and int(t["depth"].max()) >= 10, (len(t["path"]), int(t["depth"].max()))
+    return host
+
+
+def large_camera(w, h, spp, depth=50):
+    return rb.make_camera(w, h, 20.0, (13, 3, 2), (0, 0, 0), (0, 0, 0), spp, depth)
+
+
+FAINT_A, FAINT_B = (1e-42, 2e-42, 0.0), (3e-42, 0.0, 0.0)
+
+
+def fallback_scene():
+    """A crafted scene for the descent's fallback to q (no seed reaches it): a floor, a dome of weight 24 * 40^2, and two spheres whose
+    weights — about 1e-42 — round to 0 in float32 next to it.  The split on x puts the two faint ones in one node, whose children's
+    importances are 0 + 0."""
+    mats = [material(MAT_LAMBERTIAN, (0.6, 0.6, 0.6)), material(MAT_LIGHT, emit=(8, 8, 8)), material(MAT_LIGHT, emit=FAINT_A),
+            material(MAT_LIGHT, emit=FAINT_B)]
+    sph = [[0, -100, 0, 100, 0], [5, 0, 0, 40, 1], [-0.6, 0.5, 0, 0.5, 2], [0.6, 0.5, 0, 0.5, 3]]
+    return rb.HostScene.from_arrays(np.array(sph, np.float32), np.zeros((0, 11), np.float32), mats)
+
+
+def fallback_camera(w, h, spp, depth=8):
+    return rb.make_camera(w, h, 30.0, (0, 2, 6), (0, 0.5, 0), (0, 0, 0), spp, depth)
+
+
+# ---- the dispatch rule of rt_capi.hip, once ---------------------------------------------------------------------------------------------
+# entry points: the frame calls, their probes, and the adaptive call (which launches the frame kernel and its list variant)
+NEE_FRAME, NEE_PROBE, ENV_FRAME, ENV_PROBE, LIT_FRAME, LIT_PROBE, LIT_ADAPTIVE = ("rt_render_nee", "rt_trace_samples_nee", "rt_render_env",
+                                                                                 "rt_trace_samples_env", "rt_render_lit",
+                                                                                 "rt_trace_samples_lit", "rt_render_lit_adaptive")
+
+
+def kernels_of(entry, lens=False, sample_planes=0, select=0, table_has_plane=False, table_entries=1):
+    """The kernels a call launches, as a tuple of names with their template arguments: rt_capi.hip's rule.  lens: the call has a lens
+    radius > 0 or a closing camera; table_has_plane: the two-kind table holds a plane; table_entries: the length of the table the
+    call selects (0: the tree kernels are not used, rt_capi.hip's tree_on)."""
+    planes = bool(sample_planes) and table_has_plane                       # emit_planes_on
+    tree = select == 1 and table_entries > 0                               # tree_on
+    if entry in (ENV_FRAME, ENV_PROBE):
+        return ("env_render_kernel",) if entry == ENV_FRAME else ("env_probe_kernel",)
+    if entry in (NEE_FRAME, NEE_PROBE):
+        stem = ("tree_emit" if planes else "tree") if tree else ("emit" if planes else "nee")
+        return (f"{stem}_{'render' if entry == NEE_FRAME else 'probe'}_kernel",)
+    l = "true" if lens else "false"
+    if tree:
+        stem, args = "lit_tree", f"<{l}, {'TreeEmitTable' if planes else 'TreeTable'}>"
+    else:
+        stem, args = ("lit_emit" if planes else "lit"), f"<{l}>"
+    if entry == LIT_FRAME:
+        return (f"{stem}_render_kernel{args}",)
+    if entry == LIT_PROBE:
+        return (f"{stem}_probe_kernel{args}",)
+    assert entry == LIT_ADAPTIVE, entry
+    return (f"{stem}_render_kernel{args}", f"{stem}_list_render_kernel{args}")
+
+
+def all_kernels():
+    """The light-sampling family: every instantiation rt_capi.hip can launch (34)."""
+    out = [f"{s}_{k}_kernel" for s in ("nee", "emit", "tree", "tree_emit", "env") for k in ("render", "probe")]
+    for k in ("render", "list_render", "probe"):
+        for l in ("true", "false"):
+            out += [f"lit_{k}_kernel<{l}>", f"lit_emit_{k}_kernel<{l}>", f"lit_tree_{k}_kernel<{l}, TreeTable>",
+                    f"lit_tree_{k}_kernel<{l}, TreeEmitTable>"]
+    return sorted(out)
+
+
+# ---- the calls of the GPU tests: made here once, walked by the coverage test on the CPU and by the GPU tests ------------------------------
+# test: which GPU test makes the call; lens: a lens radius and (on the trials with motion) a closing camera; env: None or the environment's
+# mode; shard: None, or which of SHARDS a frame call uses
+Call = collections.namedtuple("Call", "test entry trial lens planes select mis env shard")
+MIS_PLANES_SELECT = tuple((mis, planes, select) for mis in (1, 0) for planes in (0, 1) for select in (0, 1))
+PLANES_SELECT = tuple((planes, select) for planes in (0, 1) for select in (0, 1))
+SHARDS = ((None, 0), (rb.Shard(4, 3, 2), 0), (None, 37))
+ADAPTIVE_TRIALS = (1, 2, 4)
+
+
+def _cells(test, trial, nee_entry, env_entry, lit_entry):
+    c = case(trial)
+    out = [Call(test, nee_entry, trial, False, planes, select, mis, None, None) for mis, planes, select in MIS_PLANES_SELECT]
+    if c.env is not None:
+        out += [Call(test, env_entry, trial, False, 0, 0, 1, mode, None) for mode in (1, 2)]
+    for planes, select in PLANES_SELECT:
+        for lens in (True, False):
+            # the environment rides on one lens value per cell, alternating, so that every lit kernel meets it on some trial
+            env = (1 if select else 2) if c.env is not None and lens == ((trial + planes + select) % 2 == 0) else None
+            out.append(Call(test, lit_entry, trial, lens, planes, select, 1 if lens else 0, env, None))
+    return out
+
+
+def probe_calls(trial):
+    return _cells("probes", trial, NEE_PROBE, ENV_PROBE, LIT_PROBE)
+
+
+@functools.lru_cache(maxsize=None)
+def _all_frame_calls():
+    """The frame cells of every trial; each kernel's calls go through SHARDS in turn, so that every kernel meets all three."""
+    turn, out = collections.Counter(), {}
+    for t in TRIALS:
+        out[t] = []
+        for c in _cells("frames", t, NEE_FRAME, ENV_FRAME, LIT_FRAME):
+            k = kernels_of_call(c)[0]
+            out[t].append(c._replace(shard=turn[k] % 3))
+            turn[k] += 1
+    return out
+
+
+def frame_calls(trial):
+    return list(_all_frame_calls()[trial])
+
+
+def adaptive_calls(trial):
+    c = case(trial)
+    return [Call("adaptive", LIT_ADAPTIVE, trial, lens, planes, select, 1, (1 if c.env is not None and lens else None), None)
+            for lens in (False, True) for planes, select in PLANES_SELECT]
+
+
+def large_calls():
+    return [Call("large", NEE_PROBE, "large", False, 0, 1, 1, None, None), Call("large", NEE_FRAME, "large", False, 0, 0, 1, None, 0),
+            Call("large", NEE_FRAME, "large", False, 0, 1, 1, None, 0), Call("large", LIT_FRAME, "large", True, 0, 1, 1, 1, 0)]
+
+
+def calls():
+    """Every call the GPU tests make on the light-sampling kernels."""
+    out = []
+    for t in TRIALS:
+        out += probe_calls(t) + frame_calls(t)
+    for t in ADAPTIVE_TRIALS:
+        out += adaptive_calls(t)
+    return out + large_calls()
+
+
+def kernels_of_call(call):
+    if call.trial == "large":
+        return kernels_of(call.entry, call.lens, call.planes, call.select, False, len(tr.tree(large(), 0)["path"]))
+    c = case(call.trial)
+    has = c.has_planes(1)
+    return kernels_of(call.entry, call.lens, call.planes, call.select, has, c.entries(1 if (call.planes and has) else 0))
+
+
+# ---- a call's keywords, for the device and for the restatement ----------------------------------------------------------------------------
+def reference_keywords(call, w, h, spp, depth):
+    """tree_reference.trace / frame keywords of a lit or nee call (the camera apart)."""
+    c = case(call.trial)
+    kw = dict(select=call.select, nee_mis=call.mis, planes=call.planes)
+    if call.lens:
+        kw.update(lens=c.lens, cam_close=c.close(w, h, spp, depth))
+    if call.env is not None:
+        kw.update(rgb=c.env, env_params=c.env_params(call.env))
+    return kw
+
+
+def device_keywords(call, env, w, h, spp, depth):
+    """DeviceScene.render_lit / trace_samples_lit keywords of a lit call; env: an rb.Env of the case's map (or None)."""
+    c = case(call.trial)
+    kw = dict(nee={"mis": call.mis, "sample_planes": call.planes, "select": call.select})
+    if call.lens:
+        kw.update(lens=c.lens_dict(), cam_close=c.close(w, h, spp, depth))
+    if call.env is not None:
+        kw.update(env=env, env_params=c.env_params(call.env))
+    return kw

@@ -145,55 +145,7 @@ def _zscores(m_a, m_b, spp):
     return (ma - mb) / np.sqrt((va + vb) / spp + 1e-30)
 
 
-# ---- an independent build of the tree: numpy, double, from the scene's arrays ----------------------------------------------------------
-def numpy_tree(host, planes):
-    """The header's tree over the table of sample_planes = planes, as a dict of float64 / int columns (nothing rounded to float32)."""
-    d = host.desc
-    kind, idx, _, _, area = emr.table(host, planes)
-    n = len(kind)
-    c, rho, w = np.zeros((n, 3)), np.zeros(n), np.zeros(n)
-    for e in range(n):
-        if kind[e] == 0:
-            s = d.spheres[int(idx[e])]
-            c[e], rho[e] = np.array(s.center.e[:], np.float64), s.radius
-            w[e] = np.float64(np.array(d.materials[s.material_idx].emit.e[:], np.float64).sum()) * np.float64(s.radius) ** 2
-        else:
-            p = d.planes[int(idx[e])]
-            b, u, v = (np.array(x.e[:], np.float64) for x in (p.base, p.u, p.v))
-            if p.type == TRIANGLE:
-                c[e] = b + (u + v) / 3
-                rho[e] = max(np.linalg.norm(q - c[e]) for q in (b, b + u, b + v))
-            else:
-                c[e] = b + u / 2 + v / 2
-                rho[e] = max(np.linalg.norm(u + v), np.linalg.norm(u - v)) / 2
-            w[e] = np.array(d.materials[p.material_idx].emit.e[:], np.float64).sum() * np.float64(area[e]) / np.pi
-    cols = {k: [] for k in ("centre", "radius", "weight", "q", "left", "right", "entry")}
-    path, depth = np.zeros(n, np.uint32), np.zeros(n, np.int32)
-
-    def node(S, bits, level):
-        me = len(cols["entry"])
-        lo, hi = (c[S] - rho[S, None]).min(0), (c[S] + rho[S, None]).max(0)
-        m = (lo + hi) / 2
-        for k, v in (("centre", m), ("radius", (np.linalg.norm(c[S] - m, axis=1) + rho[S]).max()), ("weight", w[S].sum() / w.sum()), ("q", 0.0),
-                     ("left", -1), ("right", -1), ("entry", -1)):
-            cols[k].append(v)
-        if len(S) == 1:
-            cols["entry"][me] = int(S[0])
-            path[S[0]], depth[S[0]] = bits, level
-            return me
-        extent = c[S].max(0) - c[S].min(0)
-        axis = int(np.argmax(extent))                      # (the first of equal maxima: x, then y, then z)
-        S = S[np.argsort(c[S, axis], kind="stable")]
-        nl = (len(S) + 1) // 2
-        cols["left"][me] = node(S[:nl], bits, level + 1)
-        cols["right"][me] = node(S[nl:], bits | (1 << level), level + 1)
-        cols["q"][me] = w[S[:nl]].sum() / w[S].sum()
-        return me
-    if n:
-        node(np.arange(n), 0, 0)
-    out = {k: np.array(v) for k, v in cols.items()}
-    out.update(path=path, depth=depth, c=c, rho=rho)
-    return out
+numpy_tree = tr.numpy_tree          # (the independent numpy build lives beside the restatement's binding: test_lit_fuzz.py uses it too)
 
 
 # ---- no GPU needed -----------------------------------------------------------------------------------------------------------

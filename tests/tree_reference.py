@@ -15,6 +15,9 @@ import rtp_bindings as rb
 HERE = os.path.dirname(os.path.abspath(__file__))
 _lib = None
 COLUMNS = ("sphere", "weight", "q", "left", "right", "entry", "path", "depth")
+# tree_ref.c's tallies, in its order (trace(stats=True) returns the first two, trace(stats="all") a dict of all of them)
+STATS = ("inside_parent", "weighted", "drop_inside", "drop_omega", "drop_cos", "shadow_other_entry", "shadow_non_table", "hit_pl_zero",
+         "q_fallback", "pick_none")
 
 
 class TreeCfg(C.Structure):
@@ -82,16 +85,18 @@ def _cfg(select, cam_close, lens, emitters, nee_mis, planes, rgb, env_params):
 
 def trace(host, cam, ijs, select=1, cam_close=None, lens=None, emitters=True, nee_mis=1, planes=0, rgb=None, env_params=None, linear=True, stats=False):
     """emit_reference.trace with the pick by select.  stats=True adds (sampling vertices inside the sphere of their picked leaf's parent,
-    weighted BSDF hits on table entries)."""
+    weighted BSDF hits on table entries); stats="all" adds a dict of every tally in STATS instead."""
     c, keep = _cfg(select, cam_close, lens, emitters, nee_mis, planes, rgb, env_params)
     ijs = np.ascontiguousarray(ijs, dtype=np.int32).reshape(-1, 3)
     m = ijs.shape[0]
     rad, rays = np.empty((m, 3), np.float32), np.empty(m, np.int32)
     seeds, nee, env = np.empty(m, np.uint32), np.empty(m, np.uint32), np.empty(m, np.uint32)
-    st = np.zeros(2, np.int64)
+    st = np.zeros(len(STATS), np.int64)
     lib().tree_trace(C.byref(host.desc), C.byref(cam), C.byref(c), m, ijs.ctypes.data, rad.ctypes.data, rays.ctypes.data, seeds.ctypes.data,
                      nee.ctypes.data, env.ctypes.data, 1 if linear else 0, st.ctypes.data)
-    return (rad, rays, seeds, nee, env) + ((tuple(int(x) for x in st),) if stats else ())
+    if stats == "all":
+        return rad, rays, seeds, nee, env, {k: int(x) for k, x in zip(STATS, st)}
+    return (rad, rays, seeds, nee, env) + ((tuple(int(x) for x in st[:2]),) if stats else ())
 
 
 def frame(host, cam, select=1, cam_close=None, lens=None, emitters=True, nee_mis=1, planes=0, rgb=None, env_params=None, shard=None, sample_first=0,
@@ -104,3 +109,54 @@ def frame(host, cam, select=1, cam_close=None, lens=None, emitters=True, nee_mis
     lib().tree_frame(C.byref(host.desc), C.byref(cam), C.byref(c), rows.ctypes.data, len(rows), sample_first, threads, fb.ctypes.data,
                      mom.ctypes.data if moments else None)
     return (fb, mom) if moments else fb
+
+
+# ---- an independent build of the tree: numpy, double, from the scene's arrays ----------------------------------------------------------
+def numpy_tree(host, planes):
+    """The header's tree over the table of sample_planes = planes, as a dict of float64 / int columns (nothing rounded to float32)."""
+    d = host.desc
+    kind, idx, _, _, area = emr.table(host, planes)
+    n = len(kind)
+    c, rho, w = np.zeros((n, 3)), np.zeros(n), np.zeros(n)
+    for e in range(n):
+        if kind[e] == 0:
+            s = d.spheres[int(idx[e])]
+            c[e], rho[e] = np.array(s.center.e[:], np.float64), s.radius
+            w[e] = np.float64(np.array(d.materials[s.material_idx].emit.e[:], np.float64).sum()) * np.float64(s.radius) ** 2
+        else:
+            p = d.planes[int(idx[e])]
+            b, u, v = (np.array(x.e[:], np.float64) for x in (p.base, p.u, p.v))
+            if p.type == 2:
+                c[e] = b + (u + v) / 3
+                rho[e] = max(np.linalg.norm(q - c[e]) for q in (b, b + u, b + v))
+            else:
+                c[e] = b + u / 2 + v / 2
+                rho[e] = max(np.linalg.norm(u + v), np.linalg.norm(u - v)) / 2
+            w[e] = np.array(d.materials[p.material_idx].emit.e[:], np.float64).sum() * np.float64(area[e]) / np.pi
+    cols = {k: [] for k in ("centre", "radius", "weight", "q", "left", "right", "entry")}
+    path, depth = np.zeros(n, np.uint32), np.zeros(n, np.int32)
+
+    def node(S, bits, level):
+        me = len(cols["entry"])
+        lo, hi = (c[S] - rho[S, None]).min(0), (c[S] + rho[S, None]).max(0)
+        m = (lo + hi) / 2
+        for k, v in (("centre", m), ("radius", (np.linalg.norm(c[S] - m, axis=1) + rho[S]).max()), ("weight", w[S].sum() / w.sum()), ("q", 0.0),
+                     ("left", -1), ("right", -1), ("entry", -1)):
+            cols[k].append(v)
+        if len(S) == 1:
+            cols["entry"][me] = int(S[0])
+            path[S[0]], depth[S[0]] = bits, level
+            return me
+        extent = c[S].max(0) - c[S].min(0)
+        axis = int(np.argmax(extent))                      # (the first of equal maxima: x, then y, then z)
+        S = S[np.argsort(c[S, axis], kind="stable")]
+        nl = (len(S) + 1) // 2
+        cols["left"][me] = node(S[:nl], bits, level + 1)
+        cols["right"][me] = node(S[nl:], bits | (1 << level), level + 1)
+        cols["q"][me] = w[S[:nl]].sum() / w[S].sum()
+        return me
+    if n:
+        node(np.arange(n), 0, 0)
+    out = {k: np.array(v) for k, v in cols.items()}
+    out.update(path=path, depth=depth, c=c, rho=rho)
+    return out
