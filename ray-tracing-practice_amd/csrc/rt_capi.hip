@@ -1829,6 +1829,83 @@ rt_status adaptive_check(const char *what, const rt_adaptive_params *params, rt_
     if (a.max_spp > 65536) return fail(RT_ERR_UNSUPPORTED, w + ": max_spp above 65536");
     return RT_OK;
 }
+// What rt_render_adaptive and rt_render_lit_adaptive share — the two differ in the frame that takes the min_spp samples and in the kernel
+// that traces a round's list.
+// The moments: the caller's d_moments, or the handle's own buffer
+rt_status adaptive_moments(rt_scene *sc, uint32_t num_pixels, float *d_moments, hipStream_t stream, float *&mom) {
+    mom = d_moments;
+    if (mom) return RT_OK;
+    if (const rt_status st = grow(sc->adapt_mom, sc->adapt_mom_pixels, (size_t)num_pixels * 2, stream)) return st;
+    mom = sc->adapt_mom;
+    return RT_OK;
+}
+// The handle's other buffers: lists, counters and — where there are rounds — work indices and a slab with rows of a round's batch.  grow
+// never shrinks, so after this the slab holds a batch; a reserve_slab that runs later may free and shorten it (rt_render_adaptive checks,
+// rt_render_lit_adaptive reserves its frame's slab first)
+rt_status adaptive_reserve(rt_scene *sc, uint32_t num_pixels, int32_t rounds, int32_t batch, hipStream_t stream) {
+    rt_status st;
+    if ((st = grow(sc->adapt_list, sc->adapt_pixels, (size_t)num_pixels * 2, stream)) != RT_OK) return st;
+    if ((st = grow(sc->adapt_counters, sc->adapt_counter_words, (size_t)3 * (size_t)(rounds + 1), stream)) != RT_OK) return st;
+    if (rounds > 0) {
+        if ((st = grow(sc->adapt_work, sc->adapt_work_cap, (size_t)num_pixels * (size_t)batch, stream)) != RT_OK) return st;
+        if ((st = grow(sc->slab, sc->slab_floats, (size_t)num_pixels * slab_pitch_of(batch) * 3, stream)) != RT_OK) return st;
+    }
+    return RT_OK;
+}
+// No depth: every sample is 0, so is every moment — and the rule stops every pixel at min_spp unless the threshold is 0
+rt_status adaptive_no_depth(const rt_adaptive_params &a, float *mom, int32_t *d_spp, uint32_t num_pixels, hipStream_t stream) {
+    const int32_t rounds = (a.max_spp - a.min_spp) / a.batch_spp;
+    HIP_TRY(hipMemsetAsync(mom, 0, (size_t)num_pixels * 8, stream));
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)d_spp, a.threshold == 0.0f ? a.min_spp + rounds * a.batch_spp : a.min_spp, num_pixels, stream));
+    return RT_OK;
+}
+// After the min_spp frame (sums in P.fb, moments in mom): every pixel is judged and its count written, then every round is enqueued —
+// expand the list of pixels still going on into work indices, trace them, add them onto the sums in slot order and onto the moments,
+// judge again.  Lists and their lengths live on the device only.  Round r (1 …) traces samples [first + (r - 1) batch, … + batch) of the
+// listed pixels — work index = local pixel * batch + slot, in the pixel's own slab row — by trace(P) → hipError_t: one launch on P, whose
+// pass, slab, list (work_list, work_count, work_cap) and queue are set here.
+template <class Trace>
+rt_status adaptive_rounds(rt_scene *sc, const rt_adaptive_params &a, rtk::KParams &P, float *mom, int32_t *d_spp, uint32_t num_pixels, int32_t first,
+                          hipStream_t stream, Trace trace) {
+    const int32_t batch = a.batch_spp, rounds = (a.max_spp - a.min_spp) / a.batch_spp;
+    const dim3 pix_grid((num_pixels + rtk::kAdaptBlock - 1) / rtk::kAdaptBlock), pix_block(rtk::kAdaptBlock);
+    const uint64_t expand_items = (uint64_t)num_pixels * (uint64_t)batch;
+    const uint32_t expand_grid = (uint32_t)std::min<uint64_t>((expand_items + rtk::kAdaptBlock - 1) / rtk::kAdaptBlock, (uint64_t)sc->num_cus * 8u);
+    uint32_t *lists[2] = {sc->adapt_list, sc->adapt_list + num_pixels};
+    uint32_t *const counters = sc->adapt_counters;          // round r (1 …): [3(r-1)] its list's length, [3(r-1) + 1] its work indices, [3(r-1) + 2] its queue
+    HIP_TRY(hipMemsetAsync(counters, 0, (size_t)3 * (size_t)(rounds + 1) * sizeof(uint32_t), stream));
+    int32_t n = a.min_spp;
+    hipLaunchKernelGGL(rtk::adaptive_select_kernel<true>, pix_grid, pix_block, 0, stream, (const float *)mom, d_spp, num_pixels, (const uint32_t *)nullptr,
+                       (const uint32_t *)nullptr, lists[0], counters, n, batch, a.max_spp, a.threshold);
+    HIP_TRY(hipGetLastError());
+    if (rounds > 0) {
+        bind_slab(sc, P, num_pixels, batch);
+        P.pass_count = batch;
+        P.total_work = num_pixels * (uint32_t)batch;
+        if (!make_magic((uint32_t)batch, (uint64_t)P.total_work + 64, P.magic_count)) return fail(RT_ERR_UNSUPPORTED, "image too large for the work index arithmetic");
+        P.work_list = sc->adapt_work;
+        P.work_cap = P.total_work;                              // (the list never stands for "every sample")
+    }
+    for (int32_t r = 1; r <= rounds; ++r) {
+        const uint32_t *list = lists[(r - 1) & 1];
+        const uint32_t *listed = counters + 3 * (r - 1);
+        hipLaunchKernelGGL(rtk::adaptive_expand_kernel, dim3(expand_grid), pix_block, 0, stream, list, listed, (uint32_t)batch, sc->adapt_work,
+                           counters + 3 * (r - 1) + 1);
+        P.pass_first = first + (r - 1) * batch;
+        P.work_count = counters + 3 * (r - 1) + 1;
+        P.queue = counters + 3 * (r - 1) + 2;
+        HIP_TRY(trace(P));
+        launch_accumulate(stream, P, Acc::onto_sums(list, listed));
+        hipLaunchKernelGGL(rtk::moments_kernel<true>, pix_grid, pix_block, 0, stream, mom, (const float *)P.slab, num_pixels, P.slab_pitch, batch, 0, list, listed,
+                           (const uint32_t *)nullptr, 0u, 0.0f, 0.0f, 0.0f);
+        n += batch;
+        if (r < rounds)
+            hipLaunchKernelGGL(rtk::adaptive_select_kernel<false>, pix_grid, pix_block, 0, stream, (const float *)mom, d_spp, num_pixels, list, listed,
+                               lists[r & 1], counters + 3 * r, n, batch, a.max_spp, a.threshold);
+        HIP_TRY(hipGetLastError());
+    }
+    return RT_OK;
+}
 rt_status adaptive_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shard, const rt_adaptive_params *params, float *d_fb_sum,
                         int32_t *d_spp, float *d_moments, void *hip_stream, int32_t sync, rt_timing *timing) {
     // ---- 1. every check before anything is enqueued
@@ -1851,17 +1928,11 @@ rt_status adaptive_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard 
     const hipStream_t stream = F.stream;
     const uint32_t num_pixels = F.num_pixels;
 
-    // ---- 2. the handle's buffers: moments, lists, work indices, counters, and a slab with rows of a round's batch
-    float *mom = d_moments;
-    if (!mom && (st = grow(sc->adapt_mom, sc->adapt_mom_pixels, (size_t)num_pixels * 2, stream)) != RT_OK) return st;
-    if (!mom) mom = sc->adapt_mom;
-    if ((st = grow(sc->adapt_list, sc->adapt_pixels, (size_t)num_pixels * 2, stream)) != RT_OK) return st;
-    if ((st = grow(sc->adapt_counters, sc->adapt_counter_words, (size_t)3 * (size_t)(rounds + 1), stream)) != RT_OK) return st;
+    // ---- 2. the handle's buffers
+    float *mom;
+    if ((st = adaptive_moments(sc, num_pixels, d_moments, stream, mom)) != RT_OK) return st;
+    if ((st = adaptive_reserve(sc, num_pixels, rounds, batch, stream)) != RT_OK) return st;
     const size_t slab_need = rounds > 0 ? (size_t)num_pixels * slab_pitch_of(batch) * 3 : 0;
-    if (rounds > 0) {
-        if ((st = grow(sc->adapt_work, sc->adapt_work_cap, (size_t)num_pixels * (size_t)batch, stream)) != RT_OK) return st;
-        if ((st = grow(sc->slab, sc->slab_floats, slab_need, stream)) != RT_OK) return st;
-    }
     CallClock &clock = sc->clock[kClockAdaptive];
     if ((st = clock.make()) != RT_OK) return st;
     if ((st = clock.start(stream)) != RT_OK) return st;
@@ -1869,10 +1940,8 @@ rt_status adaptive_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard 
     // ---- 3. the min_spp round: rt_render's frame, with the moments
     if ((st = render_impl(sc, &base, shard, nullptr, d_fb_sum, hip_stream, 0, nullptr, 0, mom)) != RT_OK) return st;
     if (P.max_depth <= 0) {
-        // (render_impl wrote all-zero sums without a pass: every sample is 0, so is every moment — and the rule stops every pixel at
-        // min_spp unless the threshold is 0)
-        HIP_TRY(hipMemsetAsync(mom, 0, (size_t)num_pixels * 8, stream));
-        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)d_spp, a.threshold == 0.0f ? a.min_spp + rounds * batch : a.min_spp, num_pixels, stream));
+        // (render_impl wrote all-zero sums without a pass)
+        if ((st = adaptive_no_depth(a, mom, d_spp, num_pixels, stream)) != RT_OK) return st;
         if ((st = clock.stop(stream)) != RT_OK) return st;
         if (sync) HIP_TRY(hipStreamSynchronize(stream));
         return RT_OK;
@@ -1883,49 +1952,15 @@ rt_status adaptive_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard 
     if ((st = fill_params(sc, &base, shard, P)) != RT_OK) return st;
     const LaunchPlan plan = plan_launch(sc, &base, P, false);
     P.fb = d_fb_sum;
-    bind_slab(sc, P, num_pixels, batch);
     set_exact_rewalk(P, sc->cfg, plan);          // (lists: finest granularity, as the exact re-walk of flagged samples)
-    P.cand = nullptr; P.order = nullptr; P.traced_pixels = nullptr;       // every sample starts from the camera …
+    P.cand = nullptr; P.order = nullptr; P.traced_pixels = nullptr;       // every sample starts from the camera
     P.resume_tag = nullptr; P.resume_state = nullptr; P.abandon = nullptr; P.dirty = nullptr; P.dirty_list = nullptr;
-    P.work_list = sc->adapt_work;
-    P.work_cap = num_pixels * (uint32_t)batch;                            // … and the list never stands for "every sample"
     const void *exact = rewalk_kernel(plan);
     const int wgs = grid_for(sc, plan.exact, num_pixels, batch);
-    const dim3 pix_grid((num_pixels + rtk::kAdaptBlock - 1) / rtk::kAdaptBlock), pix_block(rtk::kAdaptBlock);
-    const uint64_t expand_items = (uint64_t)num_pixels * (uint64_t)batch;
-    const uint32_t expand_grid = (uint32_t)std::min<uint64_t>((expand_items + rtk::kAdaptBlock - 1) / rtk::kAdaptBlock, (uint64_t)sc->num_cus * 8u);
-    uint32_t *lists[2] = {sc->adapt_list, sc->adapt_list + num_pixels};
-    uint32_t *const counters = sc->adapt_counters;          // round r (1 …): [3(r-1)] its list's length, [3(r-1) + 1] its work indices, [3(r-1) + 2] its queue
-    HIP_TRY(hipMemsetAsync(counters, 0, (size_t)3 * (size_t)(rounds + 1) * sizeof(uint32_t), stream));
-    int32_t n = a.min_spp;
-    // after the min_spp round: every pixel is judged (and its count written)
-    hipLaunchKernelGGL(rtk::adaptive_select_kernel<true>, pix_grid, pix_block, 0, stream, (const float *)mom, d_spp, num_pixels, (const uint32_t *)nullptr,
-                       (const uint32_t *)nullptr, lists[0], counters, n, batch, a.max_spp, a.threshold);
-    HIP_TRY(hipGetLastError());
-    for (int32_t r = 1; r <= rounds; ++r) {
-        const uint32_t *list = lists[(r - 1) & 1];
-        const uint32_t *listed = counters + 3 * (r - 1);
-        hipLaunchKernelGGL(rtk::adaptive_expand_kernel, dim3(expand_grid), pix_block, 0, stream, list, listed, (uint32_t)batch, sc->adapt_work,
-                           counters + 3 * (r - 1) + 1);
-        // samples [n, n + batch) of the listed pixels: work index = local pixel * batch + slot, in the pixel's own slab row
-        P.pass_first = n;
-        P.pass_count = batch;
-        P.total_work = num_pixels * (uint32_t)batch;
-        if (!make_magic((uint32_t)batch, (uint64_t)P.total_work + 64, P.magic_count)) return fail(RT_ERR_UNSUPPORTED, "image too large for the work index arithmetic");
-        P.work_count = counters + 3 * (r - 1) + 1;
-        P.queue = counters + 3 * (r - 1) + 2;
-        reservation(P.total_work, (uint64_t)wgs * (rtk::kBlock / rtk::kWave), P.full_chunk, P.full_taper);
-        HIP_TRY(launch(exact, (uint32_t)rtk::kBlock, wgs, plan.exact.lds_bytes, stream, P));
-        // … added onto the running sums in slot order, and onto the moments
-        launch_accumulate(stream, P, Acc::onto_sums(list, listed));
-        hipLaunchKernelGGL(rtk::moments_kernel<true>, pix_grid, pix_block, 0, stream, mom, (const float *)P.slab, num_pixels, P.slab_pitch, batch, 0, list, listed,
-                           (const uint32_t *)nullptr, 0u, 0.0f, 0.0f, 0.0f);
-        n += batch;
-        if (r < rounds)
-            hipLaunchKernelGGL(rtk::adaptive_select_kernel<false>, pix_grid, pix_block, 0, stream, (const float *)mom, d_spp, num_pixels, list, listed,
-                               lists[r & 1], counters + 3 * r, n, batch, a.max_spp, a.threshold);
-        HIP_TRY(hipGetLastError());
-    }
+    reservation(num_pixels * (uint32_t)batch, (uint64_t)wgs * (rtk::kBlock / rtk::kWave), P.full_chunk, P.full_taper);
+    st = adaptive_rounds(sc, a, P, mom, d_spp, num_pixels, a.min_spp, stream,
+                         [&](const rtk::KParams &KP) { return launch(exact, (uint32_t)rtk::kBlock, wgs, plan.exact.lds_bytes, stream, KP); });
+    if (st != RT_OK) return st;
     if ((st = clock.stop(stream)) != RT_OK) return st;
     if (!sync) return RT_OK;
     // what rt_last_timing reports for the min_spp round, with the whole call's kernel_ms and every trace launch of it
@@ -1941,10 +1976,9 @@ rt_status adaptive_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard 
 // ---- what the lit calls share: the frame driver of rt_render_nee / rt_render_env / rt_render_lit, the probe of rt_trace_samples and its
 // lit kin.  The passes of render_impl (plan_passes, the slab, accumulate_kernel in sample order) with a trace kernel of rt_light.hip.inc as
 // the trace launch; nothing of the handle's walk machinery is touched.
-//   trace: a kernel (KParams, Light) — or, with lens, (KParams, Light, LensCam): rt_render_lit's;
 //   light_device: the device of a light that is an object of its own (null: the light is the handle's);
-//   make_light(T, kernel): fills the kernel's second argument, once the call is known to trace — and may name another kernel for it (a
-//   Light that is a union of two table types: which one the handle's emitter table needs is known only then)
+//   with_light(frame): makes the light, once the call is known to trace, and returns frame(kernel, &light) — the kernel of that light's
+//   type, (KParams, Light) or, with lens, (KParams, Light, LensCam): rt_render_lit's — while the light lives
 // Workgroups per CU of a lit trace kernel as the loaded code object allows, and the grid of a launch on `work` work indices: what fills
 // the device, fewer where the work does not give every wave a chunk
 int light_wgs_per_cu(const void *kernel) {
@@ -1979,10 +2013,9 @@ rt_status light_passes(const void *kernel, const void *light, const rtk::LensCam
     }
     return RT_OK;
 }
-template <class Light, class MakeLight>
-rt_status render_light_impl(const char *what, const void *trace, const int *light_device, MakeLight make_light, rt_scene *sc,
-                            const rt_camera_data *cam, const rt_shard *shard, int32_t sample_first, float *d_fb_sum, void *hip_stream, int32_t sync,
-                            rt_timing *timing, const rtk::LensCam *lens = nullptr) {
+template <class WithLight>
+rt_status render_light_impl(const char *what, const int *light_device, WithLight with_light, rt_scene *sc, const rt_camera_data *cam, const rt_shard *shard,
+                            int32_t sample_first, float *d_fb_sum, void *hip_stream, int32_t sync, rt_timing *timing, const rtk::LensCam *lens = nullptr) {
     Frame F;
     rt_status st = frame_prologue(what, sc, cam, shard, nullptr, sample_first, light_device, d_fb_sum ? nullptr : "null framebuffer", hip_stream, timing, F,
                                   [&] { return refuse_retired(sc->cfg); });
@@ -1992,35 +2025,34 @@ rt_status render_light_impl(const char *what, const void *trace, const int *ligh
     const hipStream_t stream = F.stream;
     const uint32_t num_pixels = F.num_pixels;
     if (P.spp <= 0 || P.max_depth <= 0) return blank_frame(d_fb_sum, F, sync);
-    Light T;
-    const void *kernel = trace;
-    if ((st = make_light(T, kernel)) != RT_OK) return st;
-    P.fb = d_fb_sum;
-    rtaccel::PassPlan passes;
-    if ((st = reserve_slab(sc, num_pixels, P.spp, stream, passes)) != RT_OK) return st;
-    bind_slab(sc, P, num_pixels, passes.pass_size);          // (no candidate lists: fill_params left P.cand and P.order null)
-    const int per_cu = light_wgs_per_cu(kernel);
-    rt_timing t{};
-    kernel_resources(kernel, t.trace_vgprs, t.trace_scratch_bytes);
-    // (a clock and work counters of the lit calls' own, one per pass — one set: a handle renders one frame at a time)
-    CallClock &clock = sc->clock[kClockLight];
-    if ((st = clock.make(kMaxPasses)) != RT_OK) return st;
-    HIP_TRY(hipMemsetAsync(clock.words, 0, kMaxPasses * 4, stream));
-    if ((st = clock.start(stream)) != RT_OK) return st;
-    if ((st = light_passes(kernel, &T, lens, P, passes, num_pixels, sample_first, sc->num_cus * per_cu, clock.words, stream, nullptr, t.num_workgroups)) != RT_OK)
-        return st;
-    if ((st = clock.stop(stream)) != RT_OK) return st;
-    t.workgroup_size = (uint32_t)rtk::kLightBlock;
-    t.trace_launches = (uint32_t)passes.passes;
-    t.kernel = RT_KERNEL_MEGA;
-    t.traced_samples = (uint64_t)num_pixels * (uint64_t)P.spp;
-    t.guard_paused = sc->guard_paused ? 1u : 0u;
-    if (sync) {
-        if ((st = clock.elapsed(t.kernel_ms)) != RT_OK) return st;
-        t.trace_ms = t.kernel_ms;
-    }
-    timing_out(t, timing);
-    return RT_OK;
+    return with_light([&](const void *kernel, const void *light) -> rt_status {
+        P.fb = d_fb_sum;
+        rtaccel::PassPlan passes;
+        if ((st = reserve_slab(sc, num_pixels, P.spp, stream, passes)) != RT_OK) return st;
+        bind_slab(sc, P, num_pixels, passes.pass_size);          // (no candidate lists: fill_params left P.cand and P.order null)
+        const int per_cu = light_wgs_per_cu(kernel);
+        rt_timing t{};
+        kernel_resources(kernel, t.trace_vgprs, t.trace_scratch_bytes);
+        // (a clock and work counters of the lit calls' own, one per pass — one set: a handle renders one frame at a time)
+        CallClock &clock = sc->clock[kClockLight];
+        if ((st = clock.make(kMaxPasses)) != RT_OK) return st;
+        HIP_TRY(hipMemsetAsync(clock.words, 0, kMaxPasses * 4, stream));
+        if ((st = clock.start(stream)) != RT_OK) return st;
+        if ((st = light_passes(kernel, light, lens, P, passes, num_pixels, sample_first, sc->num_cus * per_cu, clock.words, stream, nullptr, t.num_workgroups)) != RT_OK)
+            return st;
+        if ((st = clock.stop(stream)) != RT_OK) return st;
+        t.workgroup_size = (uint32_t)rtk::kLightBlock;
+        t.trace_launches = (uint32_t)passes.passes;
+        t.kernel = RT_KERNEL_MEGA;
+        t.traced_samples = (uint64_t)num_pixels * (uint64_t)P.spp;
+        t.guard_paused = sc->guard_paused ? 1u : 0u;
+        if (sync) {
+            if ((st = clock.elapsed(t.kernel_ms)) != RT_OK) return st;
+            t.trace_ms = t.kernel_ms;
+        }
+        timing_out(t, timing);
+        return RT_OK;
+    });
 }
 
 // a caller's params struct over the defaults already in `into` (compiled against an older, shorter struct: the fields it has)
@@ -2378,13 +2410,6 @@ rtk::NeeTable nee_table_of(const rt_scene *sc, int32_t mis) {
 }
 // does a call with these parameters run the two-kind kernels?  Only where the table holds a plane: without one both tables are the same
 // and the sphere-only kernels give sample_planes = 0 bit for bit (the tables must have been made: nee_table_ensure)
-// a trace kernel's table argument: either table type, at the same address
-union NeeEither {
-    rtk::NeeTable nee;
-    rtk::EmitTable emit;
-    rtk::TreeTable tree;
-    rtk::TreeEmitTable tree_emit;
-};
 bool emit_planes_on(const rt_scene *sc, const NeeSetup &N) { return N.planes != 0 && sc->emit_planes > 0; }
 rtk::EmitTable emit_table_of(const rt_scene *sc, int32_t mis) {
     rtk::EmitTable T;
@@ -2496,6 +2521,24 @@ rtk::LightTree light_tree_of(const rt_scene *sc, int which) {
 rtk::TreeTable tree_table_of(const rt_scene *sc, int32_t mis) { return rtk::TreeTable{nee_table_of(sc, mis), light_tree_of(sc, 0)}; }
 rtk::TreeEmitTable tree_emit_table_of(const rt_scene *sc, int32_t mis) { return rtk::TreeEmitTable{emit_table_of(sc, mis), light_tree_of(sc, 1)}; }
 
+// Which emitter table a call uses — and so, by the table's type, which kernels: the rule of every lit call, once.  Makes the tables (and
+// the tree, where the call selects by it) on their first use and returns f(table), called exactly once: the tree over the two-kind or the
+// sphere-only table (tree_on), else the two-kind table (emit_planes_on), else the sphere-only one.  emitters off (rt_lit_params.
+// sample_emitters = 0): an empty sphere-only table, and nothing is made.  (extern "C++": a template, among the entry points)
+// The order in which f(…) is named below — NeeTable, TreeEmitTable, TreeTable, EmitTable — is the order in which the kernels a call site
+// names are instantiated, and so the layout of the device code: reordering these returns moves kernels in the code object.
+extern "C++" template <class F>
+rt_status with_emitter_table(rt_scene *sc, const NeeSetup &N, bool emitters, F &&f) {
+    if (!emitters) return f(rtk::NeeTable{});
+    if (const rt_status st = nee_table_ensure(sc)) return st;
+    const bool planes = emit_planes_on(sc, N);
+    if (tree_on(sc, N)) {
+        if (const rt_status st = tree_ensure(sc, planes ? 1 : 0)) return st;
+        return planes ? f(tree_emit_table_of(sc, N.mis)) : f(tree_table_of(sc, N.mis));
+    }
+    return planes ? f(emit_table_of(sc, N.mis)) : f(nee_table_of(sc, N.mis));
+}
+
 }  // namespace
 
 rt_status rt_render_nee(rt_scene *sc, const rt_camera_data *cam, const rt_nee_params *params, const rt_shard *shard, int32_t sample_first,
@@ -2503,27 +2546,10 @@ rt_status rt_render_nee(rt_scene *sc, const rt_camera_data *cam, const rt_nee_pa
     NeeSetup N;
     if (const rt_status st = nee_setup("rt_render_nee", params, N)) return st;
     if (!sc) return fail(RT_ERR_INVALID_ARG, "rt_render_nee: null scene");
-    auto make_table = [&](NeeEither &T, const void *&kernel) {
-        if (const rt_status st = nee_table_ensure(sc)) return st;
-        if (tree_on(sc, N)) {
-            const int which = tree_which(sc, N);
-            if (const rt_status st = tree_ensure(sc, which)) return st;
-            if (which) {
-                T.tree_emit = tree_emit_table_of(sc, N.mis);
-                kernel = (const void *)rtk::tree_emit_render_kernel;
-            } else {
-                T.tree = tree_table_of(sc, N.mis);
-                kernel = (const void *)rtk::tree_render_kernel;
-            }
-        } else if (emit_planes_on(sc, N)) {
-            T.emit = emit_table_of(sc, N.mis);
-            kernel = (const void *)rtk::emit_render_kernel;
-        } else {
-            T.nee = nee_table_of(sc, N.mis);
-        }
-        return RT_OK;
+    auto with_table = [&](auto frame) {
+        return with_emitter_table(sc, N, true, [&](const auto &T) { return frame((const void *)rtk::light_render_kernel<std::decay_t<decltype(T)>>, &T); });
     };
-    return render_light_impl<NeeEither>("rt_render_nee", (const void *)rtk::nee_render_kernel, nullptr, make_table, sc, cam, shard, sample_first, d_fb_sum, hip_stream, sync, timing);
+    return render_light_impl("rt_render_nee", nullptr, with_table, sc, cam, shard, sample_first, d_fb_sum, hip_stream, sync, timing);
 }
 
 rt_status rt_nee_light_table(rt_scene *sc, int32_t cap, int32_t *sphere_index, float *cdf, float *pmf, int32_t *count) {
@@ -2604,15 +2630,10 @@ rt_status rt_trace_samples_nee(rt_scene *sc, const rt_camera_data *cam, const rt
     if (st != RT_OK) return st;
     if ((st = check_device(sc)) != RT_OK) return st;
     return run_probe("rt_trace_samples_nee: ", P, cam, n, ijs, radiance, rays, final_seed, final_nee_seed, nullptr, [&](const rtk::KParams &KP, uint32_t *d_nee, uint32_t *) {
-        if (const rt_status ts = nee_table_ensure(sc)) return ts;
-        if (tree_on(sc, N)) {
-            const int which = tree_which(sc, N);
-            if (const rt_status ts = tree_ensure(sc, which)) return ts;
-            if (which) hipLaunchKernelGGL(rtk::tree_emit_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, KP, tree_emit_table_of(sc, N.mis), d_nee);
-            else hipLaunchKernelGGL(rtk::tree_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, KP, tree_table_of(sc, N.mis), d_nee);
-        } else if (emit_planes_on(sc, N)) hipLaunchKernelGGL(rtk::emit_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, KP, emit_table_of(sc, N.mis), d_nee);
-        else hipLaunchKernelGGL(rtk::nee_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, KP, nee_table_of(sc, N.mis), d_nee);
-        return RT_OK;
+        return with_emitter_table(sc, N, true, [&](const auto &T) {
+            hipLaunchKernelGGL(rtk::light_probe_kernel<std::decay_t<decltype(T)>>, dim3((n + 255) / 256), dim3(256), 0, 0, KP, T, d_nee);
+            return RT_OK;
+        });
     });
 }
 
@@ -2845,11 +2866,11 @@ rt_status rt_render_env(rt_scene *sc, const rt_camera_data *cam, const rt_env *e
     if (const rt_status st = env_setup("rt_render_env", params, np)) return st;
     if (!env) return fail(RT_ERR_INVALID_ARG, "rt_render_env: null environment");
     if (!sc) return fail(RT_ERR_INVALID_ARG, "rt_render_env: null scene");
-    auto make_env = [&](rtk::EnvDev &E, const void *&) {
-        E = env_dev_of(env, np);
-        return RT_OK;
+    auto with_env = [&](auto frame) {
+        const rtk::EnvDev E = env_dev_of(env, np);
+        return frame((const void *)rtk::light_render_kernel<rtk::EnvDev>, &E);
     };
-    return render_light_impl<rtk::EnvDev>("rt_render_env", (const void *)rtk::env_render_kernel, &env->device, make_env, sc, cam, shard, sample_first, d_fb_sum, hip_stream, sync, timing);
+    return render_light_impl("rt_render_env", &env->device, with_env, sc, cam, shard, sample_first, d_fb_sum, hip_stream, sync, timing);
 }
 
 rt_status rt_trace_samples_env(rt_scene *sc, const rt_camera_data *cam, const rt_env *env, const rt_env_params *params, int32_t n,
@@ -2864,7 +2885,7 @@ rt_status rt_trace_samples_env(rt_scene *sc, const rt_camera_data *cam, const rt
     if ((st = check_device(sc)) != RT_OK) return st;
     if (env->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_env: the environment was created on another device than the scene");
     return run_probe("rt_trace_samples_env: ", P, cam, n, ijs, radiance, rays, final_seed, final_env_seed, nullptr, [&](const rtk::KParams &KP, uint32_t *d_env, uint32_t *) {
-        hipLaunchKernelGGL(rtk::env_probe_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, KP, env_dev_of(env, np), d_env);
+        hipLaunchKernelGGL(rtk::light_probe_kernel<rtk::EnvDev>, dim3((n + 255) / 256), dim3(256), 0, 0, KP, env_dev_of(env, np), d_env);
         return RT_OK;
     });
 }
@@ -2902,49 +2923,19 @@ rt_status lit_setup(const char *what, const rt_camera_data *cam_open, const rt_l
         if (const rt_status st = env_setup(what, lp.env_params, S.ep)) return st;
     return RT_OK;
 }
-// the kernels' light: the handle's emitter table (emitters off: an empty one) and the environment (none: off).  planes: the table is the
-// two-kind one, in T.emit, for the lit_emit kernels; else T.lit
-union LitEither {
-    rtk::LitLight lit;
-    rtk::LitEmitLight emit;
-    rtk::LitTreeOf<rtk::TreeTable> tree;
-    rtk::LitTreeOf<rtk::TreeEmitTable> tree_emit;
-};
-// (tree: select = 1 on a table that is not empty — the tree table is T.tree_emit with planes, else T.tree)
-rt_status lit_light_of(rt_scene *sc, const LitSetup &S, LitEither &T, bool &planes, bool &tree) {
-    planes = false;
-    tree = false;
-    if (S.emitters) {
-        if (const rt_status st = nee_table_ensure(sc)) return st;
-        planes = emit_planes_on(sc, S.nee);
-        tree = tree_on(sc, S.nee);
-    }
-    if (tree) {
-        if (const rt_status st = tree_ensure(sc, planes ? 1 : 0)) return st;
-        if (planes) {
-            T.tree_emit = rtk::LitTreeOf<rtk::TreeEmitTable>{};
-            T.tree_emit.N = tree_emit_table_of(sc, S.nee.mis);
-            if (S.env) { T.tree_emit.E = env_dev_of(S.env, S.ep); T.tree_emit.env_on = 1; }
-        } else {
-            T.tree = rtk::LitTreeOf<rtk::TreeTable>{};
-            T.tree.N = tree_table_of(sc, S.nee.mis);
-            if (S.env) { T.tree.E = env_dev_of(S.env, S.ep); T.tree.env_on = 1; }
+// The kernels' light: the call's emitter table (with_emitter_table; emitters off: an empty one) and the environment (none: off).
+// Returns f(light), light a Lit<Table> of the table's type
+extern "C++" template <class F>
+rt_status with_lit(rt_scene *sc, const LitSetup &S, F &&f) {
+    return with_emitter_table(sc, S.nee, S.emitters, [&](const auto &table) {
+        rtk::Lit<std::decay_t<decltype(table)>> T{};
+        T.N = table;
+        if (S.env) {
+            T.E = env_dev_of(S.env, S.ep);
+            T.env_on = 1;
         }
-        return RT_OK;
-    }
-    if (planes) {
-        T.emit = rtk::LitEmitLight{};
-        T.emit.N = emit_table_of(sc, S.nee.mis);
-    } else {
-        T.lit = rtk::LitLight{};
-        if (S.emitters) T.lit.N = nee_table_of(sc, S.nee.mis);
-    }
-    if (S.env) {
-        // (E and env_on follow the table, whose size differs between the two)
-        if (planes) { T.emit.E = env_dev_of(S.env, S.ep); T.emit.env_on = 1; }
-        else { T.lit.E = env_dev_of(S.env, S.ep); T.lit.env_on = 1; }
-    }
-    return RT_OK;
+        return f(T);
+    });
 }
 }  // namespace
 
@@ -2953,22 +2944,19 @@ rt_status rt_render_lit(rt_scene *sc, const rt_camera_data *cam_open, const rt_l
     LitSetup S;
     if (const rt_status st = lit_setup("rt_render_lit", cam_open, lit, S)) return st;
     if (!sc) return fail(RT_ERR_INVALID_ARG, "rt_render_lit: null scene");
-    const void *kernel = S.lens ? (const void *)rtk::lit_render_kernel<true> : (const void *)rtk::lit_render_kernel<false>;
-    auto make_light = [&](LitEither &T, const void *&k) {
-        bool planes, tree;
-        if (const rt_status st = lit_light_of(sc, S, T, planes, tree)) return st;
-        if (tree && planes) k = S.lens ? (const void *)rtk::lit_tree_render_kernel<true, rtk::TreeEmitTable> : (const void *)rtk::lit_tree_render_kernel<false, rtk::TreeEmitTable>;
-        else if (tree) k = S.lens ? (const void *)rtk::lit_tree_render_kernel<true, rtk::TreeTable> : (const void *)rtk::lit_tree_render_kernel<false, rtk::TreeTable>;
-        else if (planes) k = S.lens ? (const void *)rtk::lit_emit_render_kernel<true> : (const void *)rtk::lit_emit_render_kernel<false>;
-        return RT_OK;
+    auto with_light = [&](auto frame) {
+        return with_lit(sc, S, [&](const auto &T) {
+            using Table = decltype(T.N);
+            return frame(S.lens ? (const void *)rtk::lit_render_kernel<true, Table> : (const void *)rtk::lit_render_kernel<false, Table>, &T);
+        });
     };
-    return render_light_impl<LitEither>("rt_render_lit", kernel, S.env ? &S.env->device : nullptr, make_light, sc, cam_open, shard, sample_first, d_fb_sum,
-                                        hip_stream, sync, timing, &S.C);
+    return render_light_impl("rt_render_lit", S.env ? &S.env->device : nullptr, with_light, sc, cam_open, shard, sample_first, d_fb_sum, hip_stream, sync, timing,
+                             &S.C);
 }
 
 // ---- rt_render_lit_adaptive (rtp_amd.h): rt_render_adaptive's rule and rounds on rt_render_lit's estimator.  The min_spp
-// frame is render_light_impl's passes with the moments; a round is adaptive_impl's — expand, trace, add, moments, select — with the list
-// variant of the frame's kernel as its trace launch.  Every round is enqueued up front; the light is made once.
+// frame is render_light_impl's passes with the moments; the rounds are rt_render_adaptive's (adaptive_rounds) with the list variant of
+// the frame's kernel as their trace launch.  Every round is enqueued up front; the light is made once.
 rt_status rt_render_lit_adaptive(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_adaptive_params *params,
                                  const rt_shard *shard, int32_t sample_first, float *d_fb_sum, int32_t *d_spp, float *d_moments, void *hip_stream,
                                  int32_t sync, rt_timing *timing) {
@@ -2997,112 +2985,61 @@ rt_status rt_render_lit_adaptive(rt_scene *sc, const rt_camera_data *cam_open, c
     const hipStream_t stream = F.stream;
     const uint32_t num_pixels = F.num_pixels;
 
-    // ---- 2. the handle's buffers (rt_render_adaptive's: a handle renders one frame at a time) and a slab for the frame's passes and a round's batch
-    float *mom = d_moments;
-    if (!mom && (st = grow(sc->adapt_mom, sc->adapt_mom_pixels, (size_t)num_pixels * 2, stream)) != RT_OK) return st;
-    if (!mom) mom = sc->adapt_mom;
+    // ---- 2. the handle's buffers (rt_render_adaptive's: a handle renders one frame at a time) and a slab for the frame's passes — the
+    // frame's slab first: reserve_slab may free and shorten the slab, the batch's grow after it cannot
+    float *mom;
+    if ((st = adaptive_moments(sc, num_pixels, d_moments, stream, mom)) != RT_OK) return st;
     if (P.max_depth <= 0) {
-        // (no depth: every sample is 0, so is every moment — and the rule stops every pixel at min_spp unless the threshold is 0)
         HIP_TRY(hipMemsetAsync(d_fb_sum, 0, (size_t)num_pixels * 3 * sizeof(float), stream));
-        HIP_TRY(hipMemsetAsync(mom, 0, (size_t)num_pixels * 8, stream));
-        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)d_spp, a.threshold == 0.0f ? a.min_spp + rounds * batch : a.min_spp, num_pixels, stream));
+        if ((st = adaptive_no_depth(a, mom, d_spp, num_pixels, stream)) != RT_OK) return st;
         if (sync) HIP_TRY(hipStreamSynchronize(stream));
         return RT_OK;
     }
-    if ((st = grow(sc->adapt_list, sc->adapt_pixels, (size_t)num_pixels * 2, stream)) != RT_OK) return st;
-    if ((st = grow(sc->adapt_counters, sc->adapt_counter_words, (size_t)3 * (size_t)(rounds + 1), stream)) != RT_OK) return st;
     rtaccel::PassPlan passes;
     if ((st = reserve_slab(sc, num_pixels, a.min_spp, stream, passes)) != RT_OK) return st;
-    if (rounds > 0) {
-        if ((st = grow(sc->adapt_work, sc->adapt_work_cap, (size_t)num_pixels * (size_t)batch, stream)) != RT_OK) return st;
-        if ((st = grow(sc->slab, sc->slab_floats, (size_t)num_pixels * slab_pitch_of(batch) * 3, stream)) != RT_OK) return st;
-    }
+    if ((st = adaptive_reserve(sc, num_pixels, rounds, batch, stream)) != RT_OK) return st;
 
     // ---- 3. the light, once, and the two kernels it needs: the frame's and its list variant
-    LitEither T;
-    bool planes, tree;
-    if ((st = lit_light_of(sc, S, T, planes, tree)) != RT_OK) return st;
-    const void *frame_kernel, *list_kernel;
-    if (tree && planes) {
-        frame_kernel = S.lens ? (const void *)rtk::lit_tree_render_kernel<true, rtk::TreeEmitTable> : (const void *)rtk::lit_tree_render_kernel<false, rtk::TreeEmitTable>;
-        list_kernel = S.lens ? (const void *)rtk::lit_tree_list_render_kernel<true, rtk::TreeEmitTable> : (const void *)rtk::lit_tree_list_render_kernel<false, rtk::TreeEmitTable>;
-    } else if (tree) {
-        frame_kernel = S.lens ? (const void *)rtk::lit_tree_render_kernel<true, rtk::TreeTable> : (const void *)rtk::lit_tree_render_kernel<false, rtk::TreeTable>;
-        list_kernel = S.lens ? (const void *)rtk::lit_tree_list_render_kernel<true, rtk::TreeTable> : (const void *)rtk::lit_tree_list_render_kernel<false, rtk::TreeTable>;
-    } else if (planes) {
-        frame_kernel = S.lens ? (const void *)rtk::lit_emit_render_kernel<true> : (const void *)rtk::lit_emit_render_kernel<false>;
-        list_kernel = S.lens ? (const void *)rtk::lit_emit_list_render_kernel<true> : (const void *)rtk::lit_emit_list_render_kernel<false>;
-    } else {
-        frame_kernel = S.lens ? (const void *)rtk::lit_render_kernel<true> : (const void *)rtk::lit_render_kernel<false>;
-        list_kernel = S.lens ? (const void *)rtk::lit_list_render_kernel<true> : (const void *)rtk::lit_list_render_kernel<false>;
-    }
-    rt_timing t{};
-    kernel_resources(rounds > 0 ? list_kernel : frame_kernel, t.trace_vgprs, t.trace_scratch_bytes);
-    CallClock &clock = sc->clock[kClockLight];
-    if ((st = clock.make(kMaxPasses)) != RT_OK) return st;
-    HIP_TRY(hipMemsetAsync(clock.words, 0, kMaxPasses * 4, stream));
-    uint32_t *const counters = sc->adapt_counters;          // round r (1 …): [3(r-1)] its list's length, [3(r-1) + 1] its work indices, [3(r-1) + 2] its queue
-    HIP_TRY(hipMemsetAsync(counters, 0, (size_t)3 * (size_t)(rounds + 1) * sizeof(uint32_t), stream));
-    if ((st = clock.start(stream)) != RT_OK) return st;
+    return with_lit(sc, S, [&](const auto &T) -> rt_status {
+        using Table = decltype(T.N);
+        const void *frame_kernel = S.lens ? (const void *)rtk::lit_render_kernel<true, Table> : (const void *)rtk::lit_render_kernel<false, Table>;
+        const void *list_kernel = S.lens ? (const void *)rtk::lit_list_render_kernel<true, Table> : (const void *)rtk::lit_list_render_kernel<false, Table>;
+        rt_timing t{};
+        kernel_resources(rounds > 0 ? list_kernel : frame_kernel, t.trace_vgprs, t.trace_scratch_bytes);
+        CallClock &clock = sc->clock[kClockLight];
+        if ((st = clock.make(kMaxPasses)) != RT_OK) return st;
+        HIP_TRY(hipMemsetAsync(clock.words, 0, kMaxPasses * 4, stream));
+        if ((st = clock.start(stream)) != RT_OK) return st;
 
-    // ---- 4. the min_spp frame: rt_render_lit's passes, with the moments
-    P.fb = d_fb_sum;
-    bind_slab(sc, P, num_pixels, passes.pass_size);
-    if ((st = light_passes(frame_kernel, &T, &S.C, P, passes, num_pixels, sample_first, sc->num_cus * light_wgs_per_cu(frame_kernel), clock.words, stream, mom,
-                           t.num_workgroups)) != RT_OK)
-        return st;
+        // ---- 4. the min_spp frame: rt_render_lit's passes, with the moments
+        P.fb = d_fb_sum;
+        bind_slab(sc, P, num_pixels, passes.pass_size);
+        if ((st = light_passes(frame_kernel, &T, &S.C, P, passes, num_pixels, sample_first, sc->num_cus * light_wgs_per_cu(frame_kernel), clock.words, stream, mom,
+                               t.num_workgroups)) != RT_OK)
+            return st;
 
-    // ---- 5. every pixel is judged (and its count written); then the rounds, on a list whose length only the device knows
-    const dim3 pix_grid((num_pixels + rtk::kAdaptBlock - 1) / rtk::kAdaptBlock), pix_block(rtk::kAdaptBlock);
-    uint32_t *lists[2] = {sc->adapt_list, sc->adapt_list + num_pixels};
-    int32_t n = a.min_spp;
-    hipLaunchKernelGGL(rtk::adaptive_select_kernel<true>, pix_grid, pix_block, 0, stream, (const float *)mom, d_spp, num_pixels, (const uint32_t *)nullptr,
-                       (const uint32_t *)nullptr, lists[0], counters, n, batch, a.max_spp, a.threshold);
-    HIP_TRY(hipGetLastError());
-    if (rounds > 0) {
-        const uint64_t expand_items = (uint64_t)num_pixels * (uint64_t)batch;
-        const uint32_t expand_grid = (uint32_t)std::min<uint64_t>((expand_items + rtk::kAdaptBlock - 1) / rtk::kAdaptBlock, (uint64_t)sc->num_cus * 8u);
-        // samples [sample_first + n, … + batch) of the listed pixels: work index = local pixel * batch + slot, in the pixel's own slab row
-        bind_slab(sc, P, num_pixels, batch);
-        P.pass_count = batch;
-        P.total_work = num_pixels * (uint32_t)batch;
-        if (!make_magic((uint32_t)batch, (uint64_t)P.total_work + 64, P.magic_count)) return fail(RT_ERR_UNSUPPORTED, "image too large for the work index arithmetic");
-        P.work_list = sc->adapt_work;
-        P.work_cap = P.total_work;
-        // (the grid: for the worst case — every pixel goes on)
-        const int grid = light_grid(sc->num_cus * light_wgs_per_cu(list_kernel), P.total_work);
-        t.num_workgroups = (uint32_t)grid;
-        for (int32_t r = 1; r <= rounds; ++r) {
-            const uint32_t *list = lists[(r - 1) & 1];
-            const uint32_t *listed = counters + 3 * (r - 1);
-            hipLaunchKernelGGL(rtk::adaptive_expand_kernel, dim3(expand_grid), pix_block, 0, stream, list, listed, (uint32_t)batch, sc->adapt_work,
-                               counters + 3 * (r - 1) + 1);
-            P.pass_first = sample_first + n;
-            P.work_count = counters + 3 * (r - 1) + 1;
-            P.queue = counters + 3 * (r - 1) + 2;
-            HIP_TRY(launch(list_kernel, (uint32_t)rtk::kLightBlock, grid, 0, stream, P, &T, &S.C));
-            // … added onto the running sums in slot order, and onto the moments
-            launch_accumulate(stream, P, Acc::onto_sums(list, listed));
-            hipLaunchKernelGGL(rtk::moments_kernel<true>, pix_grid, pix_block, 0, stream, mom, (const float *)P.slab, num_pixels, P.slab_pitch, batch, 0, list, listed,
-                               (const uint32_t *)nullptr, 0u, 0.0f, 0.0f, 0.0f);
-            n += batch;
-            if (r < rounds)
-                hipLaunchKernelGGL(rtk::adaptive_select_kernel<false>, pix_grid, pix_block, 0, stream, (const float *)mom, d_spp, num_pixels, list, listed,
-                                   lists[r & 1], counters + 3 * r, n, batch, a.max_spp, a.threshold);
-            HIP_TRY(hipGetLastError());
+        // ---- 5. every pixel is judged; then the rounds, on a list whose length only the device knows (the grid: for the worst case —
+        // every pixel goes on)
+        int grid = 0;
+        if (rounds > 0) {
+            grid = light_grid(sc->num_cus * light_wgs_per_cu(list_kernel), num_pixels * (uint32_t)batch);
+            t.num_workgroups = (uint32_t)grid;
         }
-    }
-    if ((st = clock.stop(stream)) != RT_OK) return st;
-    t.workgroup_size = (uint32_t)rtk::kLightBlock;
-    t.trace_launches = (uint32_t)(passes.passes + rounds);
-    t.kernel = RT_KERNEL_MEGA;
-    t.traced_samples = (uint64_t)num_pixels * (uint64_t)a.min_spp;          // (the rounds': the sum of d_spp, which only the device knows)
-    t.guard_paused = sc->guard_paused ? 1u : 0u;
-    if (sync) {
-        if ((st = clock.elapsed(t.kernel_ms)) != RT_OK) return st;
-    }
-    timing_out(t, timing);
-    return RT_OK;
+        st = adaptive_rounds(sc, a, P, mom, d_spp, num_pixels, sample_first + a.min_spp, stream,
+                             [&](const rtk::KParams &KP) { return launch(list_kernel, (uint32_t)rtk::kLightBlock, grid, 0, stream, KP, &T, &S.C); });
+        if (st != RT_OK) return st;
+        if ((st = clock.stop(stream)) != RT_OK) return st;
+        t.workgroup_size = (uint32_t)rtk::kLightBlock;
+        t.trace_launches = (uint32_t)(passes.passes + rounds);
+        t.kernel = RT_KERNEL_MEGA;
+        t.traced_samples = (uint64_t)num_pixels * (uint64_t)a.min_spp;          // (the rounds': the sum of d_spp, which only the device knows)
+        t.guard_paused = sc->guard_paused ? 1u : 0u;
+        if (sync) {
+            if ((st = clock.elapsed(t.kernel_ms)) != RT_OK) return st;
+        }
+        timing_out(t, timing);
+        return RT_OK;
+    });
 }
 
 rt_status rt_trace_samples_lit(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, int32_t n, const int32_t *ijs, float *radiance,
@@ -3118,19 +3055,13 @@ rt_status rt_trace_samples_lit(rt_scene *sc, const rt_camera_data *cam_open, con
     if (S.env && S.env->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_lit: the environment was created on another device than the scene");
     return run_probe("rt_trace_samples_lit: ", P, cam_open, n, ijs, radiance, rays, final_seed, final_nee_seed, final_env_seed,
                      [&](const rtk::KParams &KP, uint32_t *d_nee, uint32_t *d_env) {
-        LitEither T;
-        bool planes, tree;
-        if (const rt_status ts = lit_light_of(sc, S, T, planes, tree)) return ts;
-        const dim3 grid((n + 255) / 256), block(256);
-        if (tree && planes && S.lens) hipLaunchKernelGGL((rtk::lit_tree_probe_kernel<true, rtk::TreeEmitTable>), grid, block, 0, 0, KP, T.tree_emit, S.C, d_nee, d_env);
-        else if (tree && planes) hipLaunchKernelGGL((rtk::lit_tree_probe_kernel<false, rtk::TreeEmitTable>), grid, block, 0, 0, KP, T.tree_emit, S.C, d_nee, d_env);
-        else if (tree && S.lens) hipLaunchKernelGGL((rtk::lit_tree_probe_kernel<true, rtk::TreeTable>), grid, block, 0, 0, KP, T.tree, S.C, d_nee, d_env);
-        else if (tree) hipLaunchKernelGGL((rtk::lit_tree_probe_kernel<false, rtk::TreeTable>), grid, block, 0, 0, KP, T.tree, S.C, d_nee, d_env);
-        else if (planes && S.lens) hipLaunchKernelGGL(rtk::lit_emit_probe_kernel<true>, grid, block, 0, 0, KP, T.emit, S.C, d_nee, d_env);
-        else if (planes) hipLaunchKernelGGL(rtk::lit_emit_probe_kernel<false>, grid, block, 0, 0, KP, T.emit, S.C, d_nee, d_env);
-        else if (S.lens) hipLaunchKernelGGL(rtk::lit_probe_kernel<true>, grid, block, 0, 0, KP, T.lit, S.C, d_nee, d_env);
-        else hipLaunchKernelGGL(rtk::lit_probe_kernel<false>, grid, block, 0, 0, KP, T.lit, S.C, d_nee, d_env);
-        return RT_OK;
+        return with_lit(sc, S, [&](const auto &T) {
+            using Table = decltype(T.N);
+            const dim3 grid((n + 255) / 256), block(256);
+            if (S.lens) hipLaunchKernelGGL((rtk::lit_probe_kernel<true, Table>), grid, block, 0, 0, KP, T, S.C, d_nee, d_env);
+            else hipLaunchKernelGGL((rtk::lit_probe_kernel<false, Table>), grid, block, 0, 0, KP, T, S.C, d_nee, d_env);
+            return RT_OK;
+        });
     });
 }
 

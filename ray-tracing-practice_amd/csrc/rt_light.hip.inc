@@ -1,6 +1,6 @@
 // rt_light.hip.inc — the path that takes light samples, written once for both kinds of light: the emissive spheres of rt_render_nee
 // (NeeTable, rt_nee.hip.inc; DESIGN.md §13; with emissive planes: EmitTable, §17) and the environment of rt_render_env (EnvDev, rt_env.hip.inc; §14) — and, at the end, for
-// both at once from the lens camera (rt_render_lit, LitLight; §16).  Included by rt_capi.hip after both.  A light is its table type; what the two do differently is the overloads below, everything else — the lit vertex, the
+// both at once from the lens camera (rt_render_lit, Lit<Table>; §16).  Included by rt_capi.hip after both.  A light is its table type; what the two do differently is the overloads below, everything else — the lit vertex, the
 // walk step, the probe and the trace kernel — is one text.
 #pragma once
 
@@ -11,13 +11,25 @@ constexpr uint32_t kLightChunk = 128u;                       // work indices a w
 constexpr int kLightShadeLanes = 32;                         // a wave shades once this many lanes are ready (or none is walking)
 
 // ---- what a light is ---------------------------------------------------------------------------------------------------------------
+// An emitter table is one of four: the sphere-only table, the two-kind one (sample_planes = 1 on a handle whose table holds a plane;
+// DESIGN.md §17), or either under a light tree (select = 1; §18).  What the four share is written once, on the table inside:
+__device__ __forceinline__ const NeeTable &emitter_base(const NeeTable &T) { return T; }
+__device__ __forceinline__ const EmitTable &emitter_base(const EmitTable &T) { return T; }
+__device__ __forceinline__ const NeeTable &emitter_base(const TreeTable &T) { return T.N; }
+__device__ __forceinline__ const EmitTable &emitter_base(const TreeEmitTable &T) { return T.N; }
+// pmf_e of entry e for a vertex at x: the table's own, or the tree's (tree_pmf, from x)
+template <class Table> __device__ __forceinline__ float entry_pmf(const Table &T, int32_t e, f3) { return T.pmf[e]; }
+__device__ __forceinline__ float entry_pmf(const TreeTable &T, int32_t e, f3 x) { return tree_pmf(T.L, e, x); }
+__device__ __forceinline__ float entry_pmf(const TreeEmitTable &T, int32_t e, f3 x) { return tree_pmf(T.L, e, x); }
+// Below, an overload on `const Table &` is every emitter table's — these four and no other type — and the one on EnvDev the environment's.
+template <class T>
+constexpr bool kEmitterTable = std::is_same_v<T, NeeTable> || std::is_same_v<T, EmitTable> || std::is_same_v<T, TreeTable> || std::is_same_v<T, TreeEmitTable>;
+
 // the key of its RNG stream: light = wang_hash(sample_seed ^ key)
-__device__ __forceinline__ uint32_t light_key(const NeeTable &) { return kNeeStreamKey; }
-__device__ __forceinline__ uint32_t light_key(const EmitTable &) { return kNeeStreamKey; }
+template <class Table> __device__ __forceinline__ uint32_t light_key(const Table &) { static_assert(kEmitterTable<Table>, "not an emitter table"); return kNeeStreamKey; }
 __device__ __forceinline__ uint32_t light_key(const EnvDev &) { return kEnvStreamKey; }
-// are light samples drawn at all?
-__device__ __forceinline__ bool light_on(const NeeTable &T) { return T.count > 0; }
-__device__ __forceinline__ bool light_on(const EmitTable &T) { return T.count > 0; }
+// are light samples drawn at all?  (A tree table is never empty: the host hands an empty table to the kernels of select = 0)
+template <class Table> __device__ __forceinline__ bool light_on(const Table &T) { return emitter_base(T).count > 0; }
 __device__ __forceinline__ bool light_on(const EnvDev &E) { return E.sampled != 0; }
 // Is its shadow ray an occlusion query?  The environment's is: it contributes when it hits nothing, an answer that does not depend on
 // the visit order, and up to the first accepted hit the walk is the closest-hit search's own (closest is still 1e30) — so the walk ends
@@ -26,111 +38,76 @@ template <class Light> constexpr bool kLightOcclusion = false;
 template <> constexpr bool kLightOcclusion<EnvDev> = true;
 
 // miss: what the lane's ray adds when it hits nothing
-__device__ __forceinline__ f3 light_miss(const KParams &P, const NeeTable &, const Lane &L, bool) { return mul(L.beta, mk(P.bg[0], P.bg[1], P.bg[2])); }
-__device__ __forceinline__ f3 light_miss(const KParams &P, const EmitTable &, const Lane &L, bool) { return mul(L.beta, mk(P.bg[0], P.bg[1], P.bg[2])); }
+template <class Table> __device__ __forceinline__ f3 light_miss(const KParams &P, const Table &, const Lane &L, bool) {
+    static_assert(kEmitterTable<Table>, "not an emitter table");
+    return mul(L.beta, mk(P.bg[0], P.bg[1], P.bg[2]));
+}
 __device__ __forceinline__ f3 light_miss(const KParams &P, const EnvDev &E, const Lane &L, bool prev_diffuse) {
     if (L.depth == 0 && !E.camera_visible) return mul(L.beta, mk(P.bg[0], P.bg[1], P.bg[2]));
     return env_miss(E, L.d, L.beta, prev_diffuse);
 }
 // emitted: beta * emitted of the hit (sphere or plane idx) — weighted when a BSDF ray from a diffuse event found a table sphere; the
-// environment leaves it to the path alone
-__device__ __forceinline__ f3 light_emitted(const KParams &P, const NeeTable &T, const Lane &L, int32_t idx, bool is_plane, bool prev_diffuse, f3 emitted) {
+// environment leaves it to the path alone.  Once per kind of table (B: T's emitter_base), with pmf_e by entry_pmf from the ray's origin
+template <class Table>
+__device__ __forceinline__ f3 emitter_emitted(const KParams &P, const Table &T, const NeeTable &B, const Lane &L, int32_t idx, bool is_plane, bool prev_diffuse, f3 emitted) {
     if (prev_diffuse && !is_plane) {
-        const int32_t e = nee_find(T, idx);
+        const int32_t e = nee_find(B, idx);
         if (e >= 0) {
             f3 w;
             float d2, om, pl = 0.0f;
-            if (nee_cone(L.o, P.spheres[idx], w, d2, om)) pl = T.pmf[e] * nee_pdf_cone(om);
-            const float wb = T.mis ? (kNeePb * kNeePb) / (kNeePb * kNeePb + pl * pl) : (pl > 0.0f ? 0.0f : 1.0f);
+            if (nee_cone(L.o, P.spheres[idx], w, d2, om)) pl = entry_pmf(T, e, L.o) * nee_pdf_cone(om);
+            const float wb = B.mis ? (kNeePb * kNeePb) / (kNeePb * kNeePb + pl * pl) : (pl > 0.0f ? 0.0f : 1.0f);
             emitted = scale(wb, emitted);
         }
     }
     return emitted;
 }
 // (the two-kind table: a table sphere as above, a table plane by step 3p from the ray's origin to the vertex's point)
-__device__ __forceinline__ f3 light_emitted(const KParams &P, const EmitTable &T, const Lane &L, int32_t idx, bool is_plane, bool prev_diffuse, f3 emitted) {
+template <class Table>
+__device__ __forceinline__ f3 emitter_emitted(const KParams &P, const Table &T, const EmitTable &B, const Lane &L, int32_t idx, bool is_plane, bool prev_diffuse, f3 emitted) {
     if (prev_diffuse) {
-        const int32_t e = emit_find(T, L.hit);
+        const int32_t e = emit_find(B, L.hit);
         if (e >= 0) {
             f3 w;
             float pl = 0.0f;
             if (is_plane) {
                 float pa;
-                if (emit_plane_pa(P, idx, T.area[e], L.o, add(L.o, scale(L.closest, L.d)), w, pa)) pl = T.pmf[e] * pa;
+                if (emit_plane_pa(P, idx, B.area[e], L.o, add(L.o, scale(L.closest, L.d)), w, pa)) pl = entry_pmf(T, e, L.o) * pa;
             } else {
                 float d2, om;
-                if (nee_cone(L.o, P.spheres[idx], w, d2, om)) pl = T.pmf[e] * nee_pdf_cone(om);
+                if (nee_cone(L.o, P.spheres[idx], w, d2, om)) pl = entry_pmf(T, e, L.o) * nee_pdf_cone(om);
             }
-            const float wb = T.mis ? (kNeePb * kNeePb) / (kNeePb * kNeePb + pl * pl) : (pl > 0.0f ? 0.0f : 1.0f);
+            const float wb = B.mis ? (kNeePb * kNeePb) / (kNeePb * kNeePb + pl * pl) : (pl > 0.0f ? 0.0f : 1.0f);
             emitted = scale(wb, emitted);
         }
     }
     return emitted;
 }
+template <class Table>
+__device__ __forceinline__ f3 light_emitted(const KParams &P, const Table &T, const Lane &L, int32_t idx, bool is_plane, bool prev_diffuse, f3 emitted) {
+    return emitter_emitted(P, T, emitter_base(T), L, idx, is_plane, prev_diffuse, emitted);
+}
 __device__ __forceinline__ f3 light_emitted(const KParams &, const EnvDev &, const Lane &, int32_t, bool, bool, f3 emitted) { return emitted; }
 // sample: the light sample of a diffuse vertex at x (face-forwarded normal n, albedo a, throughput beta before the attenuation).  false:
-// none; else the shadow ray's direction, what it adds when it reaches the light, and (emitters) the code of the sphere to reach
+// none; else the shadow ray's direction, what it adds when it reaches the light, and (emitters) the code of the sphere to reach.  A tree
+// table picks by tree_pick, with pmf_e(x) from the descent
 __device__ __forceinline__ bool light_sample(const KParams &P, const NeeTable &T, uint32_t &ls, f3 x, f3 n, f3 a, f3 beta, f3 &dir, f3 &c, int32_t &code) {
     return nee_sample(P, T, ls, x, n, a, beta, dir, c, code);
 }
 __device__ __forceinline__ bool light_sample(const KParams &P, const EmitTable &T, uint32_t &ls, f3 x, f3 n, f3 a, f3 beta, f3 &dir, f3 &c, int32_t &code) {
     return emit_sample(P, T, ls, x, n, a, beta, dir, c, code);
 }
+template <class Tree>
+__device__ __forceinline__ bool light_sample(const KParams &P, const Tree &T, uint32_t &ls, f3 x, f3 n, f3 a, f3 beta, f3 &dir, f3 &c, int32_t &code) {
+    static_assert(std::is_same_v<Tree, TreeTable> || std::is_same_v<Tree, TreeEmitTable>, "not a tree table");
+    return tree_sample(P, T, ls, x, n, a, beta, dir, c, code);
+}
 __device__ __forceinline__ bool light_sample(const KParams &, const EnvDev &E, uint32_t &ls, f3, f3 n, f3 a, f3 beta, f3 &dir, f3 &c, int32_t &) {
     return env_sample(E, ls, n, a, beta, dir, c);
 }
 // reached: the verdict of a finished shadow walk
-__device__ __forceinline__ bool light_reached(const NeeTable &, const Lane &L, int32_t code) { return L.hit == code; }
-__device__ __forceinline__ bool light_reached(const EmitTable &, const Lane &L, int32_t code) { return L.hit == code; }
+template <class Table> __device__ __forceinline__ bool light_reached(const Table &, const Lane &L, int32_t code) { static_assert(kEmitterTable<Table>, "not an emitter table"); return L.hit == code; }
 __device__ __forceinline__ bool light_reached(const EnvDev &, const Lane &L, int32_t) { return L.hit < 0; }
-// (the light tree, select = 1: the tables' own overloads with the pick by tree_pick and pmf_e(x) by tree_pmf from the ray's origin;
-// DESIGN.md §18.  A tree table is never empty: the host hands an empty table to the kernels above)
-__device__ __forceinline__ uint32_t light_key(const TreeTable &) { return kNeeStreamKey; }
-__device__ __forceinline__ uint32_t light_key(const TreeEmitTable &) { return kNeeStreamKey; }
-__device__ __forceinline__ bool light_on(const TreeTable &T) { return T.N.count > 0; }
-__device__ __forceinline__ bool light_on(const TreeEmitTable &T) { return T.N.count > 0; }
-__device__ __forceinline__ f3 light_miss(const KParams &P, const TreeTable &, const Lane &L, bool) { return mul(L.beta, mk(P.bg[0], P.bg[1], P.bg[2])); }
-__device__ __forceinline__ f3 light_miss(const KParams &P, const TreeEmitTable &, const Lane &L, bool) { return mul(L.beta, mk(P.bg[0], P.bg[1], P.bg[2])); }
-__device__ __forceinline__ f3 light_emitted(const KParams &P, const TreeTable &T, const Lane &L, int32_t idx, bool is_plane, bool prev_diffuse, f3 emitted) {
-    if (prev_diffuse && !is_plane) {
-        const int32_t e = nee_find(T.N, idx);
-        if (e >= 0) {
-            f3 w;
-            float d2, om, pl = 0.0f;
-            if (nee_cone(L.o, P.spheres[idx], w, d2, om)) pl = tree_pmf(T.L, e, L.o) * nee_pdf_cone(om);
-            const float wb = T.N.mis ? (kNeePb * kNeePb) / (kNeePb * kNeePb + pl * pl) : (pl > 0.0f ? 0.0f : 1.0f);
-            emitted = scale(wb, emitted);
-        }
-    }
-    return emitted;
-}
-__device__ __forceinline__ f3 light_emitted(const KParams &P, const TreeEmitTable &T, const Lane &L, int32_t idx, bool is_plane, bool prev_diffuse, f3 emitted) {
-    if (prev_diffuse) {
-        const int32_t e = emit_find(T.N, L.hit);
-        if (e >= 0) {
-            f3 w;
-            float pl = 0.0f;
-            if (is_plane) {
-                float pa;
-                if (emit_plane_pa(P, idx, T.N.area[e], L.o, add(L.o, scale(L.closest, L.d)), w, pa)) pl = tree_pmf(T.L, e, L.o) * pa;
-            } else {
-                float d2, om;
-                if (nee_cone(L.o, P.spheres[idx], w, d2, om)) pl = tree_pmf(T.L, e, L.o) * nee_pdf_cone(om);
-            }
-            const float wb = T.N.mis ? (kNeePb * kNeePb) / (kNeePb * kNeePb + pl * pl) : (pl > 0.0f ? 0.0f : 1.0f);
-            emitted = scale(wb, emitted);
-        }
-    }
-    return emitted;
-}
-__device__ __forceinline__ bool light_sample(const KParams &P, const TreeTable &T, uint32_t &ls, f3 x, f3 n, f3 a, f3 beta, f3 &dir, f3 &c, int32_t &code) {
-    return tree_sample(P, T, ls, x, n, a, beta, dir, c, code);
-}
-__device__ __forceinline__ bool light_sample(const KParams &P, const TreeEmitTable &T, uint32_t &ls, f3 x, f3 n, f3 a, f3 beta, f3 &dir, f3 &c, int32_t &code) {
-    return tree_sample(P, T, ls, x, n, a, beta, dir, c, code);
-}
-__device__ __forceinline__ bool light_reached(const TreeTable &, const Lane &L, int32_t code) { return L.hit == code; }
-__device__ __forceinline__ bool light_reached(const TreeEmitTable &, const Lane &L, int32_t code) { return L.hit == code; }
 
 // the light samples' RNG state of a sample (the path's own is start_sample's)
 template <class Light>
@@ -424,68 +401,34 @@ __device__ __forceinline__ void light_render_body(const KParams &P, const Light 
     }
 }
 
-__global__ void __launch_bounds__(256) nee_probe_kernel(const KParams P, const NeeTable T, uint32_t *nee_seed_out) { light_probe_body(P, T, nee_seed_out); }
-__global__ void __launch_bounds__(256) env_probe_kernel(const KParams P, const EnvDev E, uint32_t *env_seed_out) { light_probe_body(P, E, env_seed_out); }
-__global__ void __launch_bounds__(kLightBlock) nee_render_kernel(const KParams P, const NeeTable T) { light_render_body(P, T); }
-__global__ void __launch_bounds__(kLightBlock) env_render_kernel(const KParams P, const EnvDev E) { light_render_body(P, E); }
-// (sample_planes = 1 on a handle whose table holds a plane: DESIGN.md §17)
-__global__ void __launch_bounds__(256) emit_probe_kernel(const KParams P, const EmitTable T, uint32_t *nee_seed_out) { light_probe_body(P, T, nee_seed_out); }
-__global__ void __launch_bounds__(kLightBlock) emit_render_kernel(const KParams P, const EmitTable T) { light_render_body(P, T); }
-// (select = 1: the light tree over either table; DESIGN.md §18)
-__global__ void __launch_bounds__(256) tree_probe_kernel(const KParams P, const TreeTable T, uint32_t *nee_seed_out) { light_probe_body(P, T, nee_seed_out); }
-__global__ void __launch_bounds__(kLightBlock) tree_render_kernel(const KParams P, const TreeTable T) { light_render_body(P, T); }
-__global__ void __launch_bounds__(256) tree_emit_probe_kernel(const KParams P, const TreeEmitTable T, uint32_t *nee_seed_out) { light_probe_body(P, T, nee_seed_out); }
-__global__ void __launch_bounds__(kLightBlock) tree_emit_render_kernel(const KParams P, const TreeEmitTable T) { light_render_body(P, T); }
+// Light: NeeTable, EmitTable, TreeTable, TreeEmitTable or EnvDev
+template <class Light>
+__global__ void __launch_bounds__(256) light_probe_kernel(const KParams P, const Light T, uint32_t *light_seed_out) { light_probe_body(P, T, light_seed_out); }
+template <class Light>
+__global__ void __launch_bounds__(kLightBlock) light_render_kernel(const KParams P, const Light T) { light_render_body(P, T); }
 
 // ---- rt_render_lit: the emitter table and an environment at once, from the lens camera (DESIGN.md §16) -------------------------------
 // The third light: both tables, either of which may be off (an emitter table with count 0 — sample_emitters = 0 or no emitter; env_on = 0
 // — no environment: a miss adds the background).  Spheres are hits and the map is misses, so the two never weight the same radiance:
 // miss and emitted are the single lights' own, and a vertex takes one sample of each light that is on, from that light's own stream.
-// The emitter table is NeeTable (LitLight) or, with sample_planes = 1 on a handle whose table holds a plane, EmitTable (LitEmitLight).
-struct LitLight {
-    NeeTable N;
-    EnvDev E;
-    int32_t env_on;
-};
-struct LitEmitLight {
-    EmitTable N;
-    EnvDev E;
-    int32_t env_on;
-};
-__device__ __forceinline__ f3 light_miss(const KParams &P, const LitLight &T, const Lane &L, bool prev_diffuse) {
-    if (T.env_on) return light_miss(P, T.E, L, prev_diffuse);
-    return light_miss(P, T.N, L, prev_diffuse);
-}
-__device__ __forceinline__ f3 light_emitted(const KParams &P, const LitLight &T, const Lane &L, int32_t idx, bool is_plane, bool prev_diffuse, f3 emitted) {
-    return light_emitted(P, T.N, L, idx, is_plane, prev_diffuse, emitted);
-}
-__device__ __forceinline__ bool env_sampled(const LitLight &T) { return T.env_on && light_on(T.E); }
-__device__ __forceinline__ f3 light_miss(const KParams &P, const LitEmitLight &T, const Lane &L, bool prev_diffuse) {
-    if (T.env_on) return light_miss(P, T.E, L, prev_diffuse);
-    return light_miss(P, T.N, L, prev_diffuse);
-}
-__device__ __forceinline__ f3 light_emitted(const KParams &P, const LitEmitLight &T, const Lane &L, int32_t idx, bool is_plane, bool prev_diffuse, f3 emitted) {
-    return light_emitted(P, T.N, L, idx, is_plane, prev_diffuse, emitted);
-}
-__device__ __forceinline__ bool env_sampled(const LitEmitLight &T) { return T.env_on && light_on(T.E); }
-// (select = 1: the emitter table is a tree table — LitTreeOf<TreeTable> or LitTreeOf<TreeEmitTable>)
+// Table: the call's emitter table, any of the four.
 template <class Table>
-struct LitTreeOf {
+struct Lit {
     Table N;
     EnvDev E;
     int32_t env_on;
 };
 template <class Table>
-__device__ __forceinline__ f3 light_miss(const KParams &P, const LitTreeOf<Table> &T, const Lane &L, bool prev_diffuse) {
+__device__ __forceinline__ f3 light_miss(const KParams &P, const Lit<Table> &T, const Lane &L, bool prev_diffuse) {
     if (T.env_on) return light_miss(P, T.E, L, prev_diffuse);
     return light_miss(P, T.N, L, prev_diffuse);
 }
 template <class Table>
-__device__ __forceinline__ f3 light_emitted(const KParams &P, const LitTreeOf<Table> &T, const Lane &L, int32_t idx, bool is_plane, bool prev_diffuse, f3 emitted) {
+__device__ __forceinline__ f3 light_emitted(const KParams &P, const Lit<Table> &T, const Lane &L, int32_t idx, bool is_plane, bool prev_diffuse, f3 emitted) {
     return light_emitted(P, T.N, L, idx, is_plane, prev_diffuse, emitted);
 }
 template <class Table>
-__device__ __forceinline__ bool env_sampled(const LitTreeOf<Table> &T) { return T.env_on && light_on(T.E); }
+__device__ __forceinline__ bool env_sampled(const Lit<Table> &T) { return T.env_on && light_on(T.E); }
 
 // The two light samples of a lit vertex: the emitter's (a: the shadow ray has to reach the primitive `code`) and the environment's (b: it has
 // to reach nothing).  Both are drawn at shade time — the streams are independent, and the order of the adds is the caller's.
@@ -704,33 +647,14 @@ __device__ __forceinline__ void lit_render_body(const KParams &P, const Lit &T, 
 }
 #undef RTP_LIT_RENDER_BODY
 
-template <bool kLens>
-__global__ void __launch_bounds__(256) lit_probe_kernel(const KParams P, const LitLight T, const LensCam C, uint32_t *nee_seed_out, uint32_t *env_seed_out) {
-    lit_probe_body<kLens>(P, T, C, nee_seed_out, env_seed_out);
-}
-template <bool kLens>
-__global__ void __launch_bounds__(kLightBlock, 4) lit_render_kernel(const KParams P, const LitLight T, const LensCam C) { lit_render_body<kLens>(P, T, C); }
-// (sample_planes = 1 on a handle whose table holds a plane)
-template <bool kLens>
-__global__ void __launch_bounds__(256) lit_emit_probe_kernel(const KParams P, const LitEmitLight T, const LensCam C, uint32_t *nee_seed_out, uint32_t *env_seed_out) {
-    lit_probe_body<kLens>(P, T, C, nee_seed_out, env_seed_out);
-}
-template <bool kLens>
-__global__ void __launch_bounds__(kLightBlock, 4) lit_emit_render_kernel(const KParams P, const LitEmitLight T, const LensCam C) { lit_render_body<kLens>(P, T, C); }
-// (select = 1: Table is TreeTable or TreeEmitTable)
 template <bool kLens, class Table>
-__global__ void __launch_bounds__(256) lit_tree_probe_kernel(const KParams P, const LitTreeOf<Table> T, const LensCam C, uint32_t *nee_seed_out, uint32_t *env_seed_out) {
+__global__ void __launch_bounds__(256) lit_probe_kernel(const KParams P, const Lit<Table> T, const LensCam C, uint32_t *nee_seed_out, uint32_t *env_seed_out) {
     lit_probe_body<kLens>(P, T, C, nee_seed_out, env_seed_out);
 }
 template <bool kLens, class Table>
-__global__ void __launch_bounds__(kLightBlock, 4) lit_tree_render_kernel(const KParams P, const LitTreeOf<Table> T, const LensCam C) { lit_render_body<kLens>(P, T, C); }
-
-// ---- the list variants: rt_render_lit_adaptive's rounds (DESIGN.md §19) — the same bodies on a list whose length lives on the device
-template <bool kLens>
-__global__ void __launch_bounds__(kLightBlock, 4) lit_list_render_kernel(const KParams P, const LitLight T, const LensCam C) { lit_render_body<kLens, LitLight, true>(P, T, C); }
-template <bool kLens>
-__global__ void __launch_bounds__(kLightBlock, 4) lit_emit_list_render_kernel(const KParams P, const LitEmitLight T, const LensCam C) { lit_render_body<kLens, LitEmitLight, true>(P, T, C); }
+__global__ void __launch_bounds__(kLightBlock, 4) lit_render_kernel(const KParams P, const Lit<Table> T, const LensCam C) { lit_render_body<kLens>(P, T, C); }
+// the list variant: rt_render_lit_adaptive's rounds (DESIGN.md §19) — the same body on a list whose length lives on the device
 template <bool kLens, class Table>
-__global__ void __launch_bounds__(kLightBlock, 4) lit_tree_list_render_kernel(const KParams P, const LitTreeOf<Table> T, const LensCam C) { lit_render_body<kLens, LitTreeOf<Table>, true>(P, T, C); }
+__global__ void __launch_bounds__(kLightBlock, 4) lit_list_render_kernel(const KParams P, const Lit<Table> T, const LensCam C) { lit_render_body<kLens, Lit<Table>, true>(P, T, C); }
 
 }  // namespace rtk

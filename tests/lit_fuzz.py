@@ -236,30 +236,24 @@ def kernels_of(entry, lens=False, sample_planes=0, select=0, table_has_plane=Fal
     planes = bool(sample_planes) and table_has_plane                       # emit_planes_on
     tree = select == 1 and table_entries > 0                               # tree_on
     if entry in (ENV_FRAME, ENV_PROBE):
-        return ("env_render_kernel",) if entry == ENV_FRAME else ("env_probe_kernel",)
+        return ("light_render_kernel<EnvDev>",) if entry == ENV_FRAME else ("light_probe_kernel<EnvDev>",)
+    table = ("TreeEmitTable" if planes else "TreeTable") if tree else ("EmitTable" if planes else "NeeTable")     # with_emitter_table
     if entry in (NEE_FRAME, NEE_PROBE):
-        stem = ("tree_emit" if planes else "tree") if tree else ("emit" if planes else "nee")
-        return (f"{stem}_{'render' if entry == NEE_FRAME else 'probe'}_kernel",)
-    l = "true" if lens else "false"
-    if tree:
-        stem, args = "lit_tree", f"<{l}, {'TreeEmitTable' if planes else 'TreeTable'}>"
-    else:
-        stem, args = ("lit_emit" if planes else "lit"), f"<{l}>"
+        return (f"light_{'render' if entry == NEE_FRAME else 'probe'}_kernel<{table}>",)
+    args = f"<{'true' if lens else 'false'}, {table}>"
     if entry == LIT_FRAME:
-        return (f"{stem}_render_kernel{args}",)
+        return (f"lit_render_kernel{args}",)
     if entry == LIT_PROBE:
-        return (f"{stem}_probe_kernel{args}",)
+        return (f"lit_probe_kernel{args}",)
     assert entry == LIT_ADAPTIVE, entry
-    return (f"{stem}_render_kernel{args}", f"{stem}_list_render_kernel{args}")
+    return (f"lit_render_kernel{args}", f"lit_list_render_kernel{args}")
 
 
 def all_kernels():
     """The light-sampling family: every instantiation rt_capi.hip can launch (34)."""
-    out = [f"{s}_{k}_kernel" for s in ("nee", "emit", "tree", "tree_emit", "env") for k in ("render", "probe")]
-    for k in ("render", "list_render", "probe"):
-        for l in ("true", "false"):
-            out += [f"lit_{k}_kernel<{l}>", f"lit_emit_{k}_kernel<{l}>", f"lit_tree_{k}_kernel<{l}, TreeTable>",
-                    f"lit_tree_{k}_kernel<{l}, TreeEmitTable>"]
+    tables = ("NeeTable", "EmitTable", "TreeTable", "TreeEmitTable")
+    out = [f"light_{k}_kernel<{t}>" for t in tables + ("EnvDev",) for k in ("render", "probe")]
+    out += [f"lit_{k}_kernel<{l}, {t}>" for k in ("render", "list_render", "probe") for l in ("true", "false") for t in tables]
     return sorted(out)
 
 

@@ -226,10 +226,10 @@ def test_every_kernel_is_reached():
             envs = {call.env is not None for call in lf.calls() if k in lf.kernels_of_call(call)}
             assert envs == {True, False}, (k, envs)
     # the rule itself, on the cases its inputs distinguish
-    assert lf.kernels_of(lf.NEE_FRAME, sample_planes=1, select=1, table_has_plane=False) == ("tree_render_kernel",)
-    assert lf.kernels_of(lf.NEE_PROBE, sample_planes=1, select=1, table_has_plane=True, table_entries=0) == ("emit_probe_kernel",)
-    assert lf.kernels_of(lf.LIT_ADAPTIVE, True, 1, 1, True) == ("lit_tree_render_kernel<true, TreeEmitTable>", "lit_tree_list_render_kernel<true, TreeEmitTable>")
-    assert lf.kernels_of(lf.LIT_FRAME, False, 0, 1, True, 0) == ("lit_render_kernel<false>",)
+    assert lf.kernels_of(lf.NEE_FRAME, sample_planes=1, select=1, table_has_plane=False) == ("light_render_kernel<TreeTable>",)
+    assert lf.kernels_of(lf.NEE_PROBE, sample_planes=1, select=1, table_has_plane=True, table_entries=0) == ("light_probe_kernel<EmitTable>",)
+    assert lf.kernels_of(lf.LIT_ADAPTIVE, True, 1, 1, True) == ("lit_render_kernel<true, TreeEmitTable>", "lit_list_render_kernel<true, TreeEmitTable>")
+    assert lf.kernels_of(lf.LIT_FRAME, False, 0, 1, True, 0) == ("lit_render_kernel<false, NeeTable>",)
     for t in sorted({k for call in lf.calls() for k in lf.kernels_of_call(call)}):
         print(t, sorted(reached[t], key=str)[:4])
 
