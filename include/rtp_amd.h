@@ -535,6 +535,50 @@ rt_status rt_render_adaptive(rt_scene *scene, const rt_camera_data *cam, const r
  * uniform frame at n_p.  num_pixels pixels; device pointers; enqueued on hip_stream. */
 rt_status rt_tonemap_spp(const float *d_fb_sum, const int32_t *d_spp, uint8_t *d_rgb8, int64_t num_pixels, void *hip_stream);
 
+/* ---- the stopping rule of the adaptive calls: rule 1, the neighbourhood rule -----------------------------------
+ * rt_render_adaptive_rule is rt_render_adaptive with a choice of stopping rule.  stop == NULL or rule == 0: rt_render_adaptive, bit for
+ * bit — the same kernels and launches.  rule == 1 changes goes_on alone: the statistics, the rounds, R, the counts n_p = min_spp +
+ * k * batch_spp and the per-pixel parity promise are rt_render_adaptive's.
+ *
+ * Rule 1.  At a judgement where the pixels still going on have n samples (float32, in this order, nothing fused, division correctly
+ * rounded; t = threshold):
+ *     mean    = S1 / (float)n;   var = fmaxf(0, (S2 - S1 * mean) / (float)(n - 1));
+ *     noisy_p = var / (float)n > (t * t) * (mean + 0.01f)
+ *     c_p     = (p is still going on) && noisy_p
+ *     goes_on_p = n + batch_spp <= max_spp && (t == 0 || c_q holds for some q in N(p))
+ * A NaN makes noisy_p false.  threshold = 0 never stops early, as under rule 0.
+ * The window.  N(p) is p and those of its 8 image neighbours that lie in the call's buffer: at the image border the window is clipped.
+ * Under a shard a row above or below counts only when it is a row of the same band of this part — the two rows are adjacent both in
+ * the image and in the compacted buffer; a pixel on the first or last row of a band sees no row of another part.  So the frame of a
+ * sharded render is NOT the rows of the whole frame's render under rule 1 (under rule 0 it is): each part is a frame of its own.
+ * Stopping.  A pixel goes on iff it went on in every earlier judgement and goes_on_p holds now; a pixel that stops never resumes.  It
+ * stops only when its whole window, itself included, is quiet, so its own c is false from then on and its statistics are frozen: the
+ * rule never reads a neighbour's count.
+ * Checks: rt_render_adaptive's, and right after its rt_adaptive_params checks RT_ERR_INVALID_ARG for stop->struct_bytes below 8 or a
+ * rule outside 0 … 1 (the message names rt_render_adaptive_rule) — before anything is enqueued.  Limits, stream contract, handle state,
+ * timing and the max_depth <= 0 case (counts by the rule: min_spp, or min_spp + R * batch_spp when threshold = 0) are
+ * rt_render_adaptive's.  Work under rule 1: two small launches per judgement instead of one, and one byte per pixel on the handle. */
+typedef struct rt_stop_params {       /* IN, grows like rt_adaptive_params: the library reads at most struct_bytes; below 8 = RT_ERR_INVALID_ARG */
+    uint32_t struct_bytes;            /* sizeof(rt_stop_params) as the caller compiled it */
+    int32_t  rule;                    /* 0 (default): the pixel's own relative error (rt_render_adaptive); 1: the neighbourhood rule */
+    int32_t  reserved[2];             /* 0 */
+} rt_stop_params;
+/* Defaults into *p, struct_bytes = sizeof(rt_stop_params). */
+void rt_stop_params_init(rt_stop_params *p);
+rt_status rt_render_adaptive_rule(rt_scene *scene, const rt_camera_data *cam, const rt_shard *shard, const rt_adaptive_params *params,
+                                  const rt_stop_params *stop, float *d_fb_sum, int32_t *d_spp, float *d_moments, void *hip_stream,
+                                  int32_t sync, rt_timing *timing);
+/* Probe (tests): ONE judgement of either rule over device arrays, through the kernels the rounds launch — so that the window logic
+ * can be fed moments nobody rendered.  The buffer is rows x width pixels (rows: of the call's buffer — a shard's compacted rows;
+ * shard gives band_rows and num_parts, NULL = one band); d_moments: (S1, S2) per pixel; d_going_on_in: one byte per pixel, non-zero =
+ * the pixel is still going on with n samples (NULL = every pixel); d_goes_on_out: one byte per pixel, 1 = it goes on to the next
+ * round, else 0.  params gives batch_spp, max_spp and threshold (min_spp is checked and otherwise unused).  Every byte of the mask set
+ * takes the first judgement's launches (every pixel), anything else a round's (a list).  Allocates, copies and waits: not for a hot
+ * path.  RT_ERR_INVALID_ARG: rt_render_adaptive's parameter checks, the stop checks above, width or rows below 1, n below 2, a bad
+ * shard, d_moments or d_goes_on_out NULL; RT_ERR_UNSUPPORTED: more than 2^24 pixels. */
+rt_status rt_adaptive_judge(int32_t width, int32_t rows, const rt_shard *shard, const rt_adaptive_params *params, const rt_stop_params *stop,
+                            int32_t n, const float *d_moments, const uint8_t *d_going_on_in, uint8_t *d_goes_on_out, void *hip_stream);
+
 /* ---- denoising an adaptively sampled frame: rt_denoise with per-pixel counts and the samples' own variance -------
  * rt_denoise's filter for the whole-frame outputs of rt_render_adaptive or rt_render_lit_adaptive: d_fb_sum, d_spp and, optionally,
  * d_moments.  Each pixel is normalised and remodulated by its own count, and with d_moments the variance that steers the luminance
@@ -904,6 +948,14 @@ rt_status rt_trace_samples_lit(rt_scene *scene, const rt_camera_data *cam_open, 
 rt_status rt_render_lit_adaptive(rt_scene *scene, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_adaptive_params *params,
                                  const rt_shard *shard, int32_t sample_first, float *d_fb_sum, int32_t *d_spp, float *d_moments,
                                  void *hip_stream, int32_t sync, rt_timing *timing);
+
+/* rt_render_lit_adaptive with a choice of stopping rule (the stopping-rule section above): stop == NULL or rule == 0 is
+ * rt_render_lit_adaptive bit for bit; rule == 1 judges by the neighbourhood rule, everything else — estimator, statistics, rounds,
+ * parity, handle state, timing — unchanged.  The stop checks come right after check (1), before (2); their message names
+ * rt_render_lit_adaptive_rule. */
+rt_status rt_render_lit_adaptive_rule(rt_scene *scene, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_adaptive_params *params,
+                                      const rt_stop_params *stop, const rt_shard *shard, int32_t sample_first, float *d_fb_sum, int32_t *d_spp,
+                                      float *d_moments, void *hip_stream, int32_t sync, rt_timing *timing);
 
 /* Milliseconds of the most recent rt_render kernel of this scene (waits for it). */
 rt_status rt_last_kernel_ms(rt_scene *scene, float *ms);

@@ -90,6 +90,75 @@ __global__ void __launch_bounds__(kAdaptBlock) adaptive_select_kernel(const floa
     if (on) list_out[block_base + wave_total[wave] + at] = q;
 }
 
+// ---- rule 1, the neighbourhood rule (rtp_amd.h, rt_render_adaptive_rule; DESIGN.md §22).  A judgement is two launches: the flag kernel
+// writes c_p = "p is still going on and noisy" as one byte per pixel, the select kernel reads the up to 9 bytes of a pixel's window and
+// builds the list.  No kernel both writes a pixel's byte and reads its neighbours': the launch boundary is the only ordering needed, and
+// the result does not depend on how workgroups are scheduled.
+
+// The buffer a judgement's window lives in: rows x width pixels, row-major; banded: rows r and r' are image neighbours only when
+// r / band_rows == r' / band_rows (the compacted rows of a shard part: the next band of the buffer is not the next band of the image)
+struct AdaptWindow {
+    uint32_t width, rows, band_rows, banded;
+};
+
+// noisy_p of rule 1 for a pixel with n samples and moments (s1, s2); a NaN anywhere compares false
+__device__ __forceinline__ bool adapt_noisy(float s1, float s2, int32_t n, float t) {
+    const float mean = s1 / (float)n;
+    const float var = fmaxf(0.0f, (s2 - s1 * mean) / (float)(n - 1));
+    return var / (float)n > (t * t) * (mean + 0.01f);
+}
+
+// c of the pixels of the previous round's list (kAll: of every local pixel — after the min_spp round), which have n samples now.  A
+// pixel that stopped earlier is not listed: it stopped with its whole window quiet, so its byte is 0 already and stays 0.
+template <bool kAll>
+__global__ void __launch_bounds__(kAdaptBlock) adaptive_flag_kernel(const float *mom, uint8_t *flag, uint32_t num_pixels, const uint32_t *list_in,
+                                                                    const uint32_t *count_in, int32_t n, float t) {
+    const uint32_t i = blockIdx.x * (uint32_t)kAdaptBlock + threadIdx.x;
+    const uint32_t listed = kAll ? num_pixels : *count_in;
+    if (i >= listed) return;
+    const uint32_t q = kAll ? i : list_in[i];
+    flag[q] = adapt_noisy(mom[2 * (size_t)q], mom[2 * (size_t)q + 1], n, t) ? (uint8_t)1 : (uint8_t)0;
+}
+
+// adaptive_select_kernel under rule 1: a listed pixel goes on iff the cap allows it and some byte of its window is set.  The window is
+// the pixel's 3 x 3 clipped to the buffer — columns max(col - 1, 0) … min(col + 1, width - 1), and of the rows above and below those
+// that exist and lie in the pixel's band — so every byte read has row < rows and column < width: an index below width x rows.
+template <bool kAll>
+__global__ void __launch_bounds__(kAdaptBlock) adaptive_select_near_kernel(const uint8_t *flag, int32_t *spp, uint32_t num_pixels, AdaptWindow W,
+                                                                           const uint32_t *list_in, const uint32_t *count_in, uint32_t *list_out,
+                                                                           uint32_t *count_out, int32_t n, int32_t batch, int32_t max_spp) {
+    __shared__ uint32_t wave_total[kAdaptBlock / kWave], block_base;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint32_t i = blockIdx.x * (uint32_t)kAdaptBlock + threadIdx.x;
+    const uint32_t listed = kAll ? num_pixels : *count_in;
+    bool on = false;
+    uint32_t q = 0;
+    if (i < listed) {
+        q = kAll ? i : list_in[i];
+        if (n + batch <= max_spp) {
+            const uint32_t row = q / W.width, col = q - row * W.width;
+            const uint32_t c0 = col > 0u ? col - 1u : 0u, c1 = col + 1u < W.width ? col + 1u : col;
+            const uint32_t band = W.banded ? row / W.band_rows : 0u;
+            const uint32_t r0 = row > 0u && (!W.banded || (row - 1u) / W.band_rows == band) ? row - 1u : row;
+            const uint32_t r1 = row + 1u < W.rows && (!W.banded || (row + 1u) / W.band_rows == band) ? row + 1u : row;
+            for (uint32_t r = r0; r <= r1; ++r)
+                for (uint32_t c = c0; c <= c1; ++c) on = on || flag[(size_t)r * W.width + c] != 0;
+        }
+        if (kAll || on) spp[q] = on ? n + batch : n;
+    }
+    const uint64_t m = __ballot(on);
+    const uint32_t at = (uint32_t)lane_rank(m);
+    if (lane == 0) wave_total[wave] = (uint32_t)__popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t sum = 0;
+        for (int w = 0; w < kAdaptBlock / kWave; ++w) { const uint32_t c = wave_total[w]; wave_total[w] = sum; sum += c; }
+        block_base = sum ? atomicAdd(count_out, sum) : 0u;
+    }
+    __syncthreads();
+    if (on) list_out[block_base + wave_total[wave] + at] = q;
+}
+
 // The list of a round → the work indices of its trace launch, q * batch + slot for slot = 0 … batch - 1 (the pass's own numbering:
 // local pixel * pass_count + slot), and their number.  count * batch stays below 2^31 - 4096 (rt_render_adaptive checks
 // num_pixels * batch).  Grid-stride: a round whose list is empty costs one short launch.

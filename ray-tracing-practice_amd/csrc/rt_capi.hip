@@ -300,6 +300,9 @@ struct rt_scene {
     float *adapt_mom = nullptr;
     uint32_t *adapt_list = nullptr, *adapt_work = nullptr, *adapt_counters = nullptr;
     size_t adapt_mom_pixels = 0, adapt_pixels = 0, adapt_work_cap = 0, adapt_counter_words = 0;
+    // rule 1 (rt_render_adaptive_rule): c, one byte per local pixel
+    uint8_t *adapt_flag = nullptr;
+    size_t adapt_flag_pixels = 0;
     // rt_render_nee (rt_nee.hip.inc): the emitter table, made by the handle's first call (host copy + device columns)
     bool nee_built = false;
     std::vector<int32_t> nee_index;
@@ -692,6 +695,7 @@ rt_status rt_scene_destroy(rt_scene *sc) {
     for (hipEvent_t e : sc->aov_events) (void)hipEventDestroy(e);
     for (CallClock &c : sc->clock) c.destroy();         // (every family's events and counter words)
     (void)hipFree(sc->adapt_mom); (void)hipFree(sc->adapt_list); (void)hipFree(sc->adapt_work); (void)hipFree(sc->adapt_counters);
+    (void)hipFree(sc->adapt_flag);
     (void)hipFree(sc->nee_index_dev); (void)hipFree(sc->nee_cdf_dev); (void)hipFree(sc->nee_pmf_dev);
     (void)hipFree(sc->emit_code_dev); (void)hipFree(sc->emit_cdf_dev); (void)hipFree(sc->emit_pmf_dev); (void)hipFree(sc->emit_area_dev);
     for (auto &t : sc->tree) { (void)hipFree(t.node_dev); (void)hipFree(t.path_dev); (void)hipFree(t.depth_dev); }
@@ -1829,6 +1833,16 @@ rt_status adaptive_check(const char *what, const rt_adaptive_params *params, rt_
     if (a.max_spp > 65536) return fail(RT_ERR_UNSUPPORTED, w + ": max_spp above 65536");
     return RT_OK;
 }
+// rt_stop_params of the _rule calls (what: the old call's name) → the rule; NULL is rule 0
+rt_status stop_check(const char *what, const rt_stop_params *stop, int32_t &rule) {
+    rule = 0;
+    if (!stop) return RT_OK;
+    const std::string w = std::string(what) + "_rule";
+    if (stop->struct_bytes < 8) return fail(RT_ERR_INVALID_ARG, w + ": rt_stop_params struct_bytes below 8");
+    rule = stop->rule;
+    if (rule != 0 && rule != 1) return fail(RT_ERR_INVALID_ARG, w + ": rule outside 0 … 1");
+    return RT_OK;
+}
 // What rt_render_adaptive and rt_render_lit_adaptive share — the two differ in the frame that takes the min_spp samples and in the kernel
 // that traces a round's list.
 // The moments: the caller's d_moments, or the handle's own buffer
@@ -1842,8 +1856,9 @@ rt_status adaptive_moments(rt_scene *sc, uint32_t num_pixels, float *d_moments, 
 // The handle's other buffers: lists, counters and — where there are rounds — work indices and a slab with rows of a round's batch.  grow
 // never shrinks, so after this the slab holds a batch; a reserve_slab that runs later may free and shorten it (rt_render_adaptive checks,
 // rt_render_lit_adaptive reserves its frame's slab first)
-rt_status adaptive_reserve(rt_scene *sc, uint32_t num_pixels, int32_t rounds, int32_t batch, hipStream_t stream) {
+rt_status adaptive_reserve(rt_scene *sc, uint32_t num_pixels, int32_t rounds, int32_t batch, int32_t rule, hipStream_t stream) {
     rt_status st;
+    if (rule == 1 && (st = grow(sc->adapt_flag, sc->adapt_flag_pixels, (size_t)num_pixels, stream)) != RT_OK) return st;
     if ((st = grow(sc->adapt_list, sc->adapt_pixels, (size_t)num_pixels * 2, stream)) != RT_OK) return st;
     if ((st = grow(sc->adapt_counters, sc->adapt_counter_words, (size_t)3 * (size_t)(rounds + 1), stream)) != RT_OK) return st;
     if (rounds > 0) {
@@ -1864,20 +1879,57 @@ rt_status adaptive_no_depth(const rt_adaptive_params &a, float *mom, int32_t *d_
 // judge again.  Lists and their lengths live on the device only.  Round r (1 …) traces samples [first + (r - 1) batch, … + batch) of the
 // listed pixels — work index = local pixel * batch + slot, in the pixel's own slab row — by trace(P) → hipError_t: one launch on P, whose
 // pass, slab, list (work_list, work_count, work_cap) and queue are set here.
+// One judgement of the pixels with n samples — those of list_in (null: every local pixel) — into list_out / count_out and the counts.
+// Rule 0: adaptive_select_kernel.  Rule 1 (flag: one byte per pixel, W: the buffer's shape): the flag kernel, then the select kernel
+// that reads the windows; with threshold 0 nothing is judged noisy or quiet — every pixel goes on while the cap allows — which is rule
+// 0's launch.
+rtk::AdaptWindow adapt_window(int32_t width, int32_t rows, int32_t band_rows, int32_t num_parts) {
+    rtk::AdaptWindow W;
+    W.width = (uint32_t)width;
+    W.rows = (uint32_t)rows;
+    W.band_rows = (uint32_t)band_rows;
+    W.banded = num_parts > 1 ? 1u : 0u;
+    return W;
+}
+rt_status adaptive_judge(const rt_adaptive_params &a, int32_t rule, const float *mom, int32_t *d_spp, uint8_t *flag, const rtk::AdaptWindow &W,
+                         uint32_t num_pixels, const uint32_t *list_in, const uint32_t *count_in, uint32_t *list_out, uint32_t *count_out, int32_t n,
+                         hipStream_t stream) {
+    const dim3 pix_grid((num_pixels + rtk::kAdaptBlock - 1) / rtk::kAdaptBlock), pix_block(rtk::kAdaptBlock);
+    const int32_t batch = a.batch_spp;
+    if (rule != 1 || a.threshold == 0.0f) {
+        if (!list_in)
+            hipLaunchKernelGGL(rtk::adaptive_select_kernel<true>, pix_grid, pix_block, 0, stream, mom, d_spp, num_pixels, (const uint32_t *)nullptr,
+                               (const uint32_t *)nullptr, list_out, count_out, n, batch, a.max_spp, a.threshold);
+        else
+            hipLaunchKernelGGL(rtk::adaptive_select_kernel<false>, pix_grid, pix_block, 0, stream, mom, d_spp, num_pixels, list_in, count_in, list_out,
+                               count_out, n, batch, a.max_spp, a.threshold);
+    } else if (!list_in) {
+        hipLaunchKernelGGL(rtk::adaptive_flag_kernel<true>, pix_grid, pix_block, 0, stream, mom, flag, num_pixels, (const uint32_t *)nullptr,
+                           (const uint32_t *)nullptr, n, a.threshold);
+        hipLaunchKernelGGL(rtk::adaptive_select_near_kernel<true>, pix_grid, pix_block, 0, stream, (const uint8_t *)flag, d_spp, num_pixels, W,
+                           (const uint32_t *)nullptr, (const uint32_t *)nullptr, list_out, count_out, n, batch, a.max_spp);
+    } else {
+        hipLaunchKernelGGL(rtk::adaptive_flag_kernel<false>, pix_grid, pix_block, 0, stream, mom, flag, num_pixels, list_in, count_in, n, a.threshold);
+        hipLaunchKernelGGL(rtk::adaptive_select_near_kernel<false>, pix_grid, pix_block, 0, stream, (const uint8_t *)flag, d_spp, num_pixels, W, list_in,
+                           count_in, list_out, count_out, n, batch, a.max_spp);
+    }
+    HIP_TRY(hipGetLastError());
+    return RT_OK;
+}
 template <class Trace>
-rt_status adaptive_rounds(rt_scene *sc, const rt_adaptive_params &a, rtk::KParams &P, float *mom, int32_t *d_spp, uint32_t num_pixels, int32_t first,
-                          hipStream_t stream, Trace trace) {
+rt_status adaptive_rounds(rt_scene *sc, const rt_adaptive_params &a, int32_t rule, rtk::KParams &P, float *mom, int32_t *d_spp, uint32_t num_pixels,
+                          int32_t first, hipStream_t stream, Trace trace) {
     const int32_t batch = a.batch_spp, rounds = (a.max_spp - a.min_spp) / a.batch_spp;
     const dim3 pix_grid((num_pixels + rtk::kAdaptBlock - 1) / rtk::kAdaptBlock), pix_block(rtk::kAdaptBlock);
     const uint64_t expand_items = (uint64_t)num_pixels * (uint64_t)batch;
     const uint32_t expand_grid = (uint32_t)std::min<uint64_t>((expand_items + rtk::kAdaptBlock - 1) / rtk::kAdaptBlock, (uint64_t)sc->num_cus * 8u);
     uint32_t *lists[2] = {sc->adapt_list, sc->adapt_list + num_pixels};
     uint32_t *const counters = sc->adapt_counters;          // round r (1 …): [3(r-1)] its list's length, [3(r-1) + 1] its work indices, [3(r-1) + 2] its queue
+    const rtk::AdaptWindow W = adapt_window(P.row_w, P.local_rows, P.band_rows, P.num_parts);
+    rt_status st;
     HIP_TRY(hipMemsetAsync(counters, 0, (size_t)3 * (size_t)(rounds + 1) * sizeof(uint32_t), stream));
     int32_t n = a.min_spp;
-    hipLaunchKernelGGL(rtk::adaptive_select_kernel<true>, pix_grid, pix_block, 0, stream, (const float *)mom, d_spp, num_pixels, (const uint32_t *)nullptr,
-                       (const uint32_t *)nullptr, lists[0], counters, n, batch, a.max_spp, a.threshold);
-    HIP_TRY(hipGetLastError());
+    if ((st = adaptive_judge(a, rule, mom, d_spp, sc->adapt_flag, W, num_pixels, nullptr, nullptr, lists[0], counters, n, stream)) != RT_OK) return st;
     if (rounds > 0) {
         bind_slab(sc, P, num_pixels, batch);
         P.pass_count = batch;
@@ -1899,18 +1951,19 @@ rt_status adaptive_rounds(rt_scene *sc, const rt_adaptive_params &a, rtk::KParam
         hipLaunchKernelGGL(rtk::moments_kernel<true>, pix_grid, pix_block, 0, stream, mom, (const float *)P.slab, num_pixels, P.slab_pitch, batch, 0, list, listed,
                            (const uint32_t *)nullptr, 0u, 0.0f, 0.0f, 0.0f);
         n += batch;
-        if (r < rounds)
-            hipLaunchKernelGGL(rtk::adaptive_select_kernel<false>, pix_grid, pix_block, 0, stream, (const float *)mom, d_spp, num_pixels, list, listed,
-                               lists[r & 1], counters + 3 * r, n, batch, a.max_spp, a.threshold);
         HIP_TRY(hipGetLastError());
+        if (r < rounds && (st = adaptive_judge(a, rule, mom, d_spp, sc->adapt_flag, W, num_pixels, list, listed, lists[r & 1], counters + 3 * r, n, stream)) != RT_OK)
+            return st;
     }
     return RT_OK;
 }
-rt_status adaptive_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shard, const rt_adaptive_params *params, float *d_fb_sum,
-                        int32_t *d_spp, float *d_moments, void *hip_stream, int32_t sync, rt_timing *timing) {
+rt_status adaptive_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shard, const rt_adaptive_params *params, const rt_stop_params *stop,
+                        float *d_fb_sum, int32_t *d_spp, float *d_moments, void *hip_stream, int32_t sync, rt_timing *timing) {
     // ---- 1. every check before anything is enqueued
     rt_adaptive_params a;
+    int32_t rule;
     if (const rt_status cs = adaptive_check("rt_render_adaptive", params, a)) return cs;
+    if (const rt_status cs = stop_check("rt_render_adaptive", stop, rule)) return cs;
     if (!cam) return fail(RT_ERR_INVALID_ARG, "null scene or camera");
     rt_camera_data base = *cam;
     base.samples_per_pixel = a.min_spp;
@@ -1931,7 +1984,7 @@ rt_status adaptive_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard 
     // ---- 2. the handle's buffers
     float *mom;
     if ((st = adaptive_moments(sc, num_pixels, d_moments, stream, mom)) != RT_OK) return st;
-    if ((st = adaptive_reserve(sc, num_pixels, rounds, batch, stream)) != RT_OK) return st;
+    if ((st = adaptive_reserve(sc, num_pixels, rounds, batch, rule, stream)) != RT_OK) return st;
     const size_t slab_need = rounds > 0 ? (size_t)num_pixels * slab_pitch_of(batch) * 3 : 0;
     CallClock &clock = sc->clock[kClockAdaptive];
     if ((st = clock.make()) != RT_OK) return st;
@@ -1958,7 +2011,7 @@ rt_status adaptive_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard 
     const void *exact = rewalk_kernel(plan);
     const int wgs = grid_for(sc, plan.exact, num_pixels, batch);
     reservation(num_pixels * (uint32_t)batch, (uint64_t)wgs * (rtk::kBlock / rtk::kWave), P.full_chunk, P.full_taper);
-    st = adaptive_rounds(sc, a, P, mom, d_spp, num_pixels, a.min_spp, stream,
+    st = adaptive_rounds(sc, a, rule, P, mom, d_spp, num_pixels, a.min_spp, stream,
                          [&](const rtk::KParams &KP) { return launch(exact, (uint32_t)rtk::kBlock, wgs, plan.exact.lds_bytes, stream, KP); });
     if (st != RT_OK) return st;
     if ((st = clock.stop(stream)) != RT_OK) return st;
@@ -2153,8 +2206,19 @@ void rt_adaptive_params_init(rt_adaptive_params *p) {
 
 rt_status rt_render_adaptive(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shard, const rt_adaptive_params *params, float *d_fb_sum,
                              int32_t *d_spp, float *d_moments, void *hip_stream, int32_t sync, rt_timing *timing) {
-    return adaptive_impl(sc, cam, shard, params, d_fb_sum, d_spp, d_moments, hip_stream, sync, timing);
+    return adaptive_impl(sc, cam, shard, params, nullptr, d_fb_sum, d_spp, d_moments, hip_stream, sync, timing);
 }
+void rt_stop_params_init(rt_stop_params *p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->struct_bytes = (uint32_t)sizeof(*p);
+}
+rt_status rt_render_adaptive_rule(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shard, const rt_adaptive_params *params,
+                                  const rt_stop_params *stop, float *d_fb_sum, int32_t *d_spp, float *d_moments, void *hip_stream, int32_t sync,
+                                  rt_timing *timing) {
+    return adaptive_impl(sc, cam, shard, params, stop, d_fb_sum, d_spp, d_moments, hip_stream, sync, timing);
+}
+
 
 // ---- rt_render_lens / rt_render_aov_lens / rt_lens_camera_rays (rtp_amd.h) -------------------------------------
 void rt_lens_params_init(rt_lens_params *p) {
@@ -2957,14 +3021,16 @@ rt_status rt_render_lit(rt_scene *sc, const rt_camera_data *cam_open, const rt_l
 // ---- rt_render_lit_adaptive (rtp_amd.h): rt_render_adaptive's rule and rounds on rt_render_lit's estimator.  The min_spp
 // frame is render_light_impl's passes with the moments; the rounds are rt_render_adaptive's (adaptive_rounds) with the list variant of
 // the frame's kernel as their trace launch.  Every round is enqueued up front; the light is made once.
-rt_status rt_render_lit_adaptive(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_adaptive_params *params,
-                                 const rt_shard *shard, int32_t sample_first, float *d_fb_sum, int32_t *d_spp, float *d_moments, void *hip_stream,
-                                 int32_t sync, rt_timing *timing) {
+rt_status rt_render_lit_adaptive_rule(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_adaptive_params *params,
+                                      const rt_stop_params *stop, const rt_shard *shard, int32_t sample_first, float *d_fb_sum, int32_t *d_spp,
+                                      float *d_moments, void *hip_stream, int32_t sync, rt_timing *timing) {
     // ---- 1. every check before anything is enqueued
     const char *what = "rt_render_lit_adaptive";
     rt_adaptive_params a;
+    int32_t rule;
     rt_status st = adaptive_check(what, params, a);
     if (st != RT_OK) return st;
+    if ((st = stop_check(what, stop, rule)) != RT_OK) return st;
     LitSetup S;
     if ((st = lit_setup(what, cam_open, lit, S)) != RT_OK) return st;
     const int32_t batch = a.batch_spp, rounds = (a.max_spp - a.min_spp) / a.batch_spp;
@@ -2997,7 +3063,7 @@ rt_status rt_render_lit_adaptive(rt_scene *sc, const rt_camera_data *cam_open, c
     }
     rtaccel::PassPlan passes;
     if ((st = reserve_slab(sc, num_pixels, a.min_spp, stream, passes)) != RT_OK) return st;
-    if ((st = adaptive_reserve(sc, num_pixels, rounds, batch, stream)) != RT_OK) return st;
+    if ((st = adaptive_reserve(sc, num_pixels, rounds, batch, rule, stream)) != RT_OK) return st;
 
     // ---- 3. the light, once, and the two kernels it needs: the frame's and its list variant
     return with_lit(sc, S, [&](const auto &T) -> rt_status {
@@ -3025,7 +3091,7 @@ rt_status rt_render_lit_adaptive(rt_scene *sc, const rt_camera_data *cam_open, c
             grid = light_grid(sc->num_cus * light_wgs_per_cu(list_kernel), num_pixels * (uint32_t)batch);
             t.num_workgroups = (uint32_t)grid;
         }
-        st = adaptive_rounds(sc, a, P, mom, d_spp, num_pixels, sample_first + a.min_spp, stream,
+        st = adaptive_rounds(sc, a, rule, P, mom, d_spp, num_pixels, sample_first + a.min_spp, stream,
                              [&](const rtk::KParams &KP) { return launch(list_kernel, (uint32_t)rtk::kLightBlock, grid, 0, stream, KP, &T, &S.C); });
         if (st != RT_OK) return st;
         if ((st = clock.stop(stream)) != RT_OK) return st;
@@ -3040,6 +3106,83 @@ rt_status rt_render_lit_adaptive(rt_scene *sc, const rt_camera_data *cam_open, c
         timing_out(t, timing);
         return RT_OK;
     });
+}
+
+rt_status rt_render_lit_adaptive(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_adaptive_params *params,
+                                 const rt_shard *shard, int32_t sample_first, float *d_fb_sum, int32_t *d_spp, float *d_moments, void *hip_stream,
+                                 int32_t sync, rt_timing *timing) {
+    return rt_render_lit_adaptive_rule(sc, cam_open, lit, params, nullptr, shard, sample_first, d_fb_sum, d_spp, d_moments, hip_stream, sync, timing);
+}
+
+// The probe of the stopping rules (rtp_amd.h): one judgement over caller-made moments and a going-on mask, through adaptive_judge — the
+// launches of the rounds.  Test infrastructure: it allocates, copies and waits.
+rt_status rt_adaptive_judge(int32_t width, int32_t rows, const rt_shard *shard, const rt_adaptive_params *params, const rt_stop_params *stop, int32_t n,
+                            const float *d_moments, const uint8_t *d_going_on_in, uint8_t *d_goes_on_out, void *hip_stream) {
+    const char *what = "rt_adaptive_judge";
+    rt_adaptive_params a;
+    int32_t rule;
+    rt_status st = adaptive_check(what, params, a);
+    if (st != RT_OK) return st;
+    if (stop) {
+        if (stop->struct_bytes < 8) return fail(RT_ERR_INVALID_ARG, "rt_adaptive_judge: rt_stop_params struct_bytes below 8");
+        if (stop->rule != 0 && stop->rule != 1) return fail(RT_ERR_INVALID_ARG, "rt_adaptive_judge: rule outside 0 … 1");
+    }
+    rule = stop ? stop->rule : 0;
+    if (width < 1 || rows < 1) return fail(RT_ERR_INVALID_ARG, "rt_adaptive_judge: width or rows below 1");
+    if ((uint64_t)width * (uint64_t)rows > (1u << 24)) return fail(RT_ERR_UNSUPPORTED, "rt_adaptive_judge: more than 2^24 pixels");
+    if (n < 2) return fail(RT_ERR_INVALID_ARG, "rt_adaptive_judge: n below 2");
+    if (shard && shard->num_parts > 1 && (shard->part < 0 || shard->part >= shard->num_parts || shard->band_rows <= 0))
+        return fail(RT_ERR_INVALID_ARG, "rt_adaptive_judge: bad shard");
+    if (!d_moments || !d_goes_on_out) return fail(RT_ERR_INVALID_ARG, "rt_adaptive_judge: null moments or output");
+    const hipStream_t stream = (hipStream_t)hip_stream;
+    const uint32_t num_pixels = (uint32_t)width * (uint32_t)rows;
+    rt_shard s;
+    normalise_shard(shard, rows, s);
+    const rtk::AdaptWindow W = adapt_window(width, rows, s.band_rows, s.num_parts);
+    // the pixels going on, as the list a round would hand on (null mask, or every byte set: every pixel — the first judgement's launch)
+    std::vector<uint8_t> mask(num_pixels, 1);
+    if (d_going_on_in) {
+        HIP_TRY(hipMemcpyAsync(mask.data(), d_going_on_in, num_pixels, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+    }
+    std::vector<uint32_t> list;
+    for (uint32_t q = 0; q < num_pixels; ++q)
+        if (mask[q]) list.push_back(q);
+    const bool all = list.size() == num_pixels;
+    // one allocation: list in, list out, two counters, counts, flags
+    uint32_t *words = nullptr;
+    const size_t num_words = (size_t)num_pixels * 3 + 2;
+    HIP_TRY(hipMalloc((void **)&words, num_words * sizeof(uint32_t) + num_pixels));
+    uint32_t *list_in = words, *list_out = words + num_pixels, *counts = words + 2 * (size_t)num_pixels;
+    int32_t *spp = (int32_t *)(counts + 2);
+    uint8_t *flag = (uint8_t *)(words + num_words);
+    const uint32_t host_counts[2] = {(uint32_t)list.size(), 0u};
+    auto body = [&]() -> rt_status {
+        HIP_TRY(hipMemsetAsync(words, 0, num_words * sizeof(uint32_t) + num_pixels, stream));
+        if (!list.empty()) HIP_TRY(hipMemcpyAsync(list_in, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(counts, host_counts, sizeof(host_counts), hipMemcpyHostToDevice, stream));
+        if ((st = adaptive_judge(a, rule, d_moments, spp, flag, W, num_pixels, all ? nullptr : list_in, all ? nullptr : counts, list_out, counts + 1, n,
+                                 stream)) != RT_OK)
+            return st;
+        uint32_t kept = 0;
+        HIP_TRY(hipMemcpyAsync(&kept, counts + 1, sizeof(kept), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        if (kept > num_pixels) return fail(RT_ERR_HIP, "rt_adaptive_judge: the list is longer than the image");
+        std::vector<uint32_t> out(kept);
+        if (kept) HIP_TRY(hipMemcpyAsync(out.data(), list_out, kept * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        std::fill(mask.begin(), mask.end(), (uint8_t)0);
+        for (const uint32_t q : out) {
+            if (q >= num_pixels) return fail(RT_ERR_HIP, "rt_adaptive_judge: a listed pixel outside the image");
+            mask[q] = 1;
+        }
+        HIP_TRY(hipMemcpyAsync(d_goes_on_out, mask.data(), num_pixels, hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        return RT_OK;
+    };
+    st = body();
+    (void)hipFree(words);
+    return st;
 }
 
 rt_status rt_trace_samples_lit(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, int32_t n, const int32_t *ijs, float *radiance,

@@ -65,6 +65,34 @@ int main(int argc, char *argv[]) {
             return 2;
         }
     }
+    // extension: `--stop-rule own|near`, with `--adaptive T` or with `--lit … --noise-target T` and only with them: the stopping rule of
+    // the adaptive frames (rt_render_adaptive_rule / rt_render_lit_adaptive_rule).  own, the default: the pixel's own
+    // relative error — the frames without the flag; near: the neighbourhood rule.
+    rt_stop_params stop_rule;
+    rt_stop_params_init(&stop_rule);
+    {
+        bool adaptive_on = false, lit_flag = false, target_flag = false, given = false;
+        std::string word;
+        for (int a = 2; a < argc; ++a) {
+            const std::string arg = argv[a];
+            if (arg == "--adaptive") adaptive_on = true;
+            if (arg == "--lit") lit_flag = true;
+            if (arg == "--noise-target") target_flag = true;
+            if (arg == "--stop-rule") {
+                given = true;
+                word = a + 1 < argc ? argv[a + 1] : "";
+            }
+        }
+        if (given && word != "own" && word != "near") {
+            std::cerr << "rtp_main: --stop-rule takes own or near\n";
+            return 2;
+        }
+        if (given && !adaptive_on && !(lit_flag && target_flag)) {
+            std::cerr << "rtp_main: --stop-rule picks the stopping rule of adaptively sampled frames: it needs --adaptive T or --lit --noise-target T\n";
+            return 2;
+        }
+        stop_rule.rule = word == "near" ? 1 : 0;
+    }
     // extension: `--gpu --lit`: every frame through rt_render_lit on one GPU — light samples of the emissive spheres (`--nee [mis|light]`
     // picks their weighting), and with it, and only with it, `--env FILE[:N]` (with --env-mode, --env-scale, --env-up), `--lens R:F` and
     // `--motion-blur S` in any combination; --aov / --denoise as with --lens (first hits do not depend on the estimator).  Each of those
@@ -304,7 +332,7 @@ int main(int argc, char *argv[]) {
                 lit.env = lit_env;
                 lit.env_params = &lit_ep;
                 rtp::gpu_render_lens(params, desc, lens, shutter, aov, denoise, nullptr, nullptr, nullptr, &lit, noise_on ? &noise : nullptr,
-                                     denoise_adaptive);
+                                     denoise_adaptive, &stop_rule);
                 rt_env_destroy(lit_env);
                 return 0;
             }
@@ -354,7 +382,7 @@ int main(int argc, char *argv[]) {
                     std::cerr << "rtp_main: --adaptive cannot be combined with --shard\n";
                     return 2;
                 }
-            rtp::gpu_render_adaptive(params, desc, ap, denoise_adaptive);
+            rtp::gpu_render_adaptive(params, desc, ap, denoise_adaptive, &stop_rule);
             return 0;
         }
     // extension: `--gpu --shard N` splits EVERY frame over N GPUs (0 = all of the node) with one RCCL gather per frame

@@ -310,7 +310,7 @@ void gpu_render_pipelined(const SceneParams &params, const rt_scene_desc &desc, 
 // denoise_adaptive (with noise; rtp_main --denoise-adaptive): as in gpu_render_adaptive, the AOVs from rt_render_aov_lens at noise->min_spp
 void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const rt_lens_params &lens, float shutter, bool aov, bool denoise,
                      const rt_nee_params *nee, const rt_env *env, const rt_env_params *env_params, const rt_lit_params *lit,
-                     const rt_adaptive_params *noise, bool denoise_adaptive) {
+                     const rt_adaptive_params *noise, bool denoise_adaptive, const rt_stop_params *stop) {
     rt_scene *scene = nullptr;
     RTP_CHECK(rt_scene_create(&desc, &scene));
     const size_t num_pixels = static_cast<size_t>(params.width) * params.height;
@@ -368,8 +368,8 @@ void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const
             rt_lit_params frame_lit = *lit;
             frame_lit.cam_close = cam_close;
             frame_lit.lens = &lens;
-            RTP_CHECK(rt_render_lit_adaptive(scene, &cam, &frame_lit, noise, nullptr, 0, d_fb, d_spp, spp_denoiser ? spp_denoiser->d_moments : nullptr,
-                                             nullptr, 1, nullptr));
+            RTP_CHECK(rt_render_lit_adaptive_rule(scene, &cam, &frame_lit, noise, stop, nullptr, 0, d_fb, d_spp, spp_denoiser ? spp_denoiser->d_moments : nullptr,
+                                                  nullptr, 1, nullptr));
         } else if (lit) {
             rt_lit_params frame_lit = *lit;
             frame_lit.cam_close = cam_close;
@@ -440,7 +440,8 @@ void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const
 // saver arithmetic with its own sample count as the divisor (the mean of its samples).  Prints frame, milliseconds and the samples
 // the frame took.  denoise_adaptive (rtp_main --denoise-adaptive): the frame's moments are kept, its AOVs rendered at
 // min_spp, and rt_denoise_spp's output goes through rt_tonemap_spp to "<frame file>.denoised".
-void gpu_render_adaptive(const SceneParams &params, const rt_scene_desc &desc, const rt_adaptive_params &ap, bool denoise_adaptive) {
+void gpu_render_adaptive(const SceneParams &params, const rt_scene_desc &desc, const rt_adaptive_params &ap, bool denoise_adaptive,
+                         const rt_stop_params *stop) {
     rt_scene *scene = nullptr;
     RTP_CHECK(rt_scene_create(&desc, &scene));
     const size_t num_pixels = static_cast<size_t>(params.width) * params.height;
@@ -463,7 +464,7 @@ void gpu_render_adaptive(const SceneParams &params, const rt_scene_desc &desc, c
         camera.background_color = Vec3(0, 0, 0);
         const rt_camera_data cam = camera.build_camera_data();
         const auto t0 = std::chrono::steady_clock::now();
-        RTP_CHECK(rt_render_adaptive(scene, &cam, nullptr, &ap, d_fb, d_spp, spp_denoiser ? spp_denoiser->d_moments : nullptr, nullptr, 1, nullptr));
+        RTP_CHECK(rt_render_adaptive_rule(scene, &cam, nullptr, &ap, stop, d_fb, d_spp, spp_denoiser ? spp_denoiser->d_moments : nullptr, nullptr, 1, nullptr));
         RTP_CHECK(rt_tonemap_spp(d_fb, d_spp, d_rgb, static_cast<int64_t>(num_pixels), nullptr));
         PendingFile file;
         file.path = frame_filename(params.output_pattern, n);

@@ -120,6 +120,26 @@ def adaptive_params(**params):
     return p
 
 
+class StopParams(C.Structure):
+    """rt_stop_params (include/rtp_amd.h): an IN structure of the caller's size — struct_bytes is set on construction."""
+    _fields_ = [("struct_bytes", C.c_uint32), ("rule", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_bytes = C.sizeof(StopParams)
+
+
+def stop_params(**params):
+    """rt_stop_params with the library's defaults, then the given fields (rule)."""
+    p = StopParams()
+    amd_lib().rt_stop_params_init(C.byref(p))
+    for k, v in params.items():
+        if k not in ("rule",):
+            raise RtError(f"rt_stop_params has no field {k}")
+        setattr(p, k, v)
+    return p
+
+
 class LensParams(C.Structure):
     """rt_lens_params (include/rtp_amd.h): an IN structure of the caller's size — struct_bytes is set on construction; the other
     fields are 0 until rt_lens_params_init (lens_params()) fills the defaults."""
@@ -394,6 +414,7 @@ RTP_AMD_SYMBOLS = [
     "rt_lit_params_init", "rt_render_lit", "rt_trace_samples_lit",
     "rt_render_lit_adaptive",
     "rt_denoise_spp",
+    "rt_stop_params_init", "rt_render_adaptive_rule", "rt_render_lit_adaptive_rule", "rt_adaptive_judge",
 ]
 
 _host = None
@@ -533,6 +554,17 @@ def amd_lib():
             lib.rt_render_lit_adaptive.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(LitParams), C.POINTER(AdaptiveParams),
                                                    C.POINTER(Shard), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                                    C.POINTER(Timing)]
+        if hasattr(lib, "rt_render_adaptive_rule"):
+            lib.rt_stop_params_init.argtypes = [C.POINTER(StopParams)]
+            lib.rt_stop_params_init.restype = None
+            lib.rt_render_adaptive_rule.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(Shard), C.POINTER(AdaptiveParams),
+                                                    C.POINTER(StopParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                                    C.POINTER(Timing)]
+            lib.rt_render_lit_adaptive_rule.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(LitParams), C.POINTER(AdaptiveParams),
+                                                        C.POINTER(StopParams), C.POINTER(Shard), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                        C.c_void_p, C.c_int32, C.POINTER(Timing)]
+            lib.rt_adaptive_judge.argtypes = [C.c_int32, C.c_int32, C.POINTER(Shard), C.POINTER(AdaptiveParams), C.POINTER(StopParams), C.c_int32,
+                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         if hasattr(lib, "rt_denoise_spp"):
             lib.rt_denoise_spp.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(AovBuffers), C.c_int32, C.c_int32, C.c_int32,
                                            C.POINTER(DenoiseParams), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
@@ -839,6 +871,29 @@ def _upload(a):
     return d
 
 
+def adaptive_judge(moments, n, going_on=None, shard=None, rule=0, **params):
+    """rt_adaptive_judge: one judgement of a stopping rule on the current device.  moments (rows, width, 2) float32 (S1, S2); going_on
+    None (every pixel) or (rows, width) bool; params are rt_adaptive_params fields.  Returns goes_on (rows, width) bool."""
+    lib = amd_lib()
+    mom = np.ascontiguousarray(moments, dtype=np.float32)
+    rows, width = mom.shape[:2]
+    out = np.empty((rows, width), dtype=np.uint8)
+    p, stop = adaptive_params(**params), stop_params(rule=rule)
+    dev = []
+    try:
+        dev.append(_upload(mom))
+        dev.append(None if going_on is None else _upload(np.ascontiguousarray(np.asarray(going_on).reshape(rows, width), dtype=np.uint8)))
+        dev.append(_upload(out))
+        _check(lib.rt_adaptive_judge(width, rows, C.byref(shard) if shard else None, C.byref(p), C.byref(stop), n, dev[0], dev[1], dev[2], None),
+               "rt_adaptive_judge")
+        _check(lib.rt_copy_to_host(out.ctypes.data, dev[2], out.nbytes), "rt_copy_to_host")
+    finally:
+        for d in dev:
+            if d is not None:
+                lib.rt_device_free(d)
+    return out.astype(bool)
+
+
 class TemporalDenoiser:
     """rt_denoise_temporal over the frames of an animation: owns the two history buffers and the workspace of a width x height
     image on the device current at construction.  step_to_host() denoises one frame and keeps its history for the next one;
@@ -1066,14 +1121,21 @@ class DeviceScene:
 
     def render_adaptive(self, cam, d_fb_ptr, d_spp_ptr, d_moments_ptr=None, shard=None, stream=None, sync=True, **params):
         """rt_render_adaptive: d_fb_ptr (3 floats per pixel), d_spp_ptr (1 int32 per pixel), d_moments_ptr (None, or 2 floats per pixel)
-        are integer device addresses; params are rt_adaptive_params fields (min_spp, batch_spp, max_spp, threshold).  Returns the
-        rt_timing."""
+        are integer device addresses; params are rt_adaptive_params fields (min_spp, batch_spp, max_spp, threshold) and rule (0 or 1:
+        given, the call goes through rt_render_adaptive_rule with that rt_stop_params.rule).  Returns the rt_timing."""
+        rule = params.pop("rule", None)
         p = adaptive_params(**params)
         t = Timing()
         self._apply_config()
-        _check(amd_lib().rt_render_adaptive(self._h, C.byref(cam), C.byref(shard) if shard else None, C.byref(p), C.c_void_p(d_fb_ptr),
-                                            C.c_void_p(d_spp_ptr), C.c_void_p(d_moments_ptr or 0), C.c_void_p(stream or 0), 1 if sync else 0,
-                                            C.byref(t)), "rt_render_adaptive")
+        if rule is None:
+            _check(amd_lib().rt_render_adaptive(self._h, C.byref(cam), C.byref(shard) if shard else None, C.byref(p), C.c_void_p(d_fb_ptr),
+                                                C.c_void_p(d_spp_ptr), C.c_void_p(d_moments_ptr or 0), C.c_void_p(stream or 0), 1 if sync else 0,
+                                                C.byref(t)), "rt_render_adaptive")
+        else:
+            stop = stop_params(rule=rule)
+            _check(amd_lib().rt_render_adaptive_rule(self._h, C.byref(cam), C.byref(shard) if shard else None, C.byref(p), C.byref(stop),
+                                                     C.c_void_p(d_fb_ptr), C.c_void_p(d_spp_ptr), C.c_void_p(d_moments_ptr or 0),
+                                                     C.c_void_p(stream or 0), 1 if sync else 0, C.byref(t)), "rt_render_adaptive_rule")
         return t
 
     def render_adaptive_to_host(self, cam, shard=None, **params):
@@ -1303,14 +1365,23 @@ class DeviceScene:
                             env_params=None, shard=None, stream=None, sync=True, sample_first=0, **params):
         """rt_render_lit_adaptive: rt_render_adaptive's rounds on rt_render_lit's estimator.  d_fb_ptr (3 floats per pixel), d_spp_ptr
         (1 int32 per pixel), d_moments_ptr (None, or 2 floats per pixel) are integer device addresses; the keywords are lit_params()'s
-        arguments; params are rt_adaptive_params fields (min_spp, batch_spp, max_spp, threshold).  Returns the rt_timing of this call."""
+        arguments; params are rt_adaptive_params fields (min_spp, batch_spp, max_spp, threshold) and rule (0 or 1: given, the call goes
+        through rt_render_lit_adaptive_rule with that rt_stop_params.rule).  Returns the rt_timing of this call."""
+        rule = params.pop("rule", None)
         p = adaptive_params(**params)
         t = Timing()
         self._apply_config()
         lit = lit_params(cam_close=cam_close, lens=lens, emitters=emitters, nee=nee, env=env, env_params=env_params)
-        _check(amd_lib().rt_render_lit_adaptive(self._h, C.byref(cam), C.byref(lit), C.byref(p), C.byref(shard) if shard else None, sample_first,
-                                                C.c_void_p(d_fb_ptr), C.c_void_p(d_spp_ptr), C.c_void_p(d_moments_ptr or 0), C.c_void_p(stream or 0),
-                                                1 if sync else 0, C.byref(t)), "rt_render_lit_adaptive")
+        if rule is None:
+            _check(amd_lib().rt_render_lit_adaptive(self._h, C.byref(cam), C.byref(lit), C.byref(p), C.byref(shard) if shard else None, sample_first,
+                                                    C.c_void_p(d_fb_ptr), C.c_void_p(d_spp_ptr), C.c_void_p(d_moments_ptr or 0),
+                                                    C.c_void_p(stream or 0), 1 if sync else 0, C.byref(t)), "rt_render_lit_adaptive")
+        else:
+            stop = stop_params(rule=rule)
+            _check(amd_lib().rt_render_lit_adaptive_rule(self._h, C.byref(cam), C.byref(lit), C.byref(p), C.byref(stop),
+                                                         C.byref(shard) if shard else None, sample_first, C.c_void_p(d_fb_ptr), C.c_void_p(d_spp_ptr),
+                                                         C.c_void_p(d_moments_ptr or 0), C.c_void_p(stream or 0), 1 if sync else 0, C.byref(t)),
+                   "rt_render_lit_adaptive_rule")
         return t
 
     def render_lit_adaptive_to_host(self, cam, *, cam_close=None, lens=None, emitters=True, nee=None, env=None, env_params=None, shard=None,
