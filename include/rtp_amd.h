@@ -736,19 +736,44 @@ rt_status rt_lens_camera_rays(const rt_camera_data *cam_open, const rt_camera_da
  *       path from the ray's origin x, with the same expressions in the same order, and w_b is as written (pl = 0 gives weight 1: an entry
  *       the pick cannot reach from x).
  * Checks and limits: rt_render_samples's (rows of a shard only: no tiles, no rt_context); every refusal comes before anything is
- * enqueued; RT_ERR_INVALID_ARG for params with struct_bytes below 8, mis outside {0, 1}, sample_planes outside {0, 1} or select outside
- * {0, 1} (checked in that order).  The light samples run on the
+ *   glossy = 1 (read only when struct_bytes >= 20, an older caller gets 0): METAL's reflect branch takes light samples too.
+ *     glossy = 0 is the call as written above, bit for bit.  The same switch exists in rt_env_params — its mode must be 1 or 2 to matter —
+ *     and acts on that light; rt_render_lit and its adaptive forms read each light's switch from its own params.
+ *     pg(w; r, fuzz), the density in solid angle of unit(r + fuzz * B), B uniform in the unit ball, r a unit vector — the integral of
+ *       t^2 over the chord the direction w cuts through the ball of radius fuzz about r, over the ball's volume:
+ *         c = dot(w, r); ff = fuzz * fuzz; disc = (c * c - 1) + ff; !(disc > 0): pg = 0.  s = sqrtf(disc); t2 = c + s; !(t2 > 0): pg = 0.
+ *         t1 = c - s; f3 = ff * fuzz.  t1 > 0: pg = (s * (3 * (c * c) + s * s)) / (RT_NEE_TWO_PI * f3) — the factored form, no
+ *         cancellation; otherwise (fuzz > 1: the vertex is inside the ball) pg = ((t2 * t2) * t2) / ((2 * RT_NEE_TWO_PI) * f3).
+ *     Glossy event: a METAL hit at query k whose branch draw chose the reflect branch (random_float < 0.8f), with
+ *       fuzz >= RT_GLOSSY_MIN_FUZZ, k + 1 < max_depth, the light on (a table that is not empty) and its glossy = 1.  Below that fuzz the
+ *       event is a mirror as before: no sample, and its ray keeps weight 1 (unbiased: the choice depends on the vertex alone; and pg, at
+ *       most about 1 / (pi fuzz^2), stays finite).  r = reflect(unit(d), n) as the path computes it; the main stream draws what it draws
+ *       without the switch — the branch draw, the point in the unit sphere — and new_d = r + fuzz * in_sphere, absorbed when
+ *       !(dot(new_d, n) > 0), is the same next ray.
+ *     Its light sample: the steps above (1, then 2 to 4 or 2p to 4p; the tree's pick under select = 1) from the nee state, the same draws
+ *       in the same order, with pb = pg(wl; r, fuzz) in place of RT_NEE_PB in f — wl as the steps give it — and one more way to give no
+ *       contribution after !(dot(wl, n) > 0): pb == 0.  The draws are consumed either way; a sample without contribution casts no shadow
+ *       ray (rt_trace_samples_*'s rays do not count one).  contribution_k = ((beta_k * a_k) * emit_e,k) * f with the METAL's albedo a.
+ *       The sample is taken whether or not new_d is absorbed: it estimates the branch's integral, independently of the path's draw.
+ *     The ray that leaves a glossy event carries pc = pg(unit(new_d); r, fuzz): its hit on a table entry is weighted by w_b with pc in
+ *       place of pb (light alone: pl > 0 ? 0 : 1), and pc == 0 — pg rounded to 0 at the lobe's rim — means weight 1, never 0 / 0.
+ *     Identities, bit for bit: glossy = 1 on a scene without METAL of fuzz >= RT_GLOSSY_MIN_FUZZ, or with an empty table, = glossy = 0.
+ * Checks and limits: rt_render_samples's (rows of a shard only: no tiles, no rt_context); every refusal comes before anything is
+ * enqueued; RT_ERR_INVALID_ARG for params with struct_bytes below 8, mis outside {0, 1}, sample_planes outside {0, 1}, select outside
+ * {0, 1} or glossy outside {0, 1} (checked in that order).  The light samples run on the
  * reference-order walk only.  Handle state: the call leaves the handle's own decisions alone, as rt_render_lens does — its walk choice,
  * a pause of the guarded walk, the re-pack of its tree, its cached view lists and what rt_last_timing reports; timing (may be NULL)
  * is this call's record (kernel_ms with sync != 0). */
 #define RT_NEE_STREAM_KEY 0x4E454531u
 #define RT_NEE_TWO_PI 6.28318548f          /* (float)(2 pi) */
 #define RT_NEE_PB 0.159154937f             /* (float)(1 / (2 pi)): the density of the uniform-hemisphere direction */
+#define RT_GLOSSY_MIN_FUZZ 0.0009765625f   /* 2^-10: a METAL reflect branch below this fuzz is a mirror — no light sample (glossy = 1) */
 typedef struct rt_nee_params {   /* IN, grows like rt_lens_params: the library reads at most struct_bytes; < 8 = RT_ERR_INVALID_ARG */
     uint32_t struct_bytes;       /* sizeof(rt_nee_params) as the caller compiled it */
     int32_t  mis;                /* 1 (default): power heuristic; 0: light sampling alone (the BSDF hit of a table sphere counts 0) */
     int32_t  sample_planes;      /* 0 (default): spheres only; 1: emissive QUAD / ELLIPSE / TRIANGLE planes are sampled too (struct_bytes >= 12) */
     int32_t  select;             /* 0 (default): the entry by the power table's cdf; 1: by the light tree (struct_bytes >= 16) */
+    int32_t  glossy;             /* 0 (default): light samples at diffuse events only; 1: at METAL's reflect branch too (struct_bytes >= 20) */
 } rt_nee_params;
 /* Defaults into *p, struct_bytes = sizeof(rt_nee_params). */
 void rt_nee_params_init(rt_nee_params *p);
@@ -821,7 +846,12 @@ rt_status rt_trace_samples_nee(rt_scene *scene, const rt_camera_data *cam, const
  * Checks and limits: rt_render_nee's (rows of a shard only: no tiles, no rt_context; every refusal before anything is enqueued; the
  * handle's walk decisions, view lists and rt_last_timing left alone).  RT_ERR_INVALID_ARG: params with struct_bytes below 8, mode
  * outside {0, 1, 2}, scale negative or not finite, camera_visible outside {0, 1}, rot with |dot(Ra, Rb) - (a == b)| above 1e-4 for
- * some pair of rows, a null env, an env created on another device than the scene's. */
+ * some pair of rows, glossy outside {0, 1}, a null env, an env created on another device than the scene's.
+ *   glossy = 1 (the first of the former reserved slots; rt_env_params_init leaves it 0): rt_render_nee's glossy events with this light —
+ *     the event needs mode != 0 and a table that is not empty; its sample is steps 1 to 4 from the env state with pb = pg(wl; r, fuzz)
+ *     and pb == 0 as one more "none"; the ray that leaves it carries pc = pg(unit(new_d); r, fuzz), and its miss is weighted by w_b with
+ *     pc for pb (pc == 0: weight 1).  glossy = 0, a scene without METAL of fuzz >= RT_GLOSSY_MIN_FUZZ, mode 0 or an empty table: the
+ *     call as written above, bit for bit. */
 #define RT_ENV_STREAM_KEY 0x454E5631u
 #define RT_ENV_MAX_N 4096
 typedef struct rt_env rt_env;
@@ -836,7 +866,8 @@ typedef struct rt_env_params {   /* IN, grows like rt_nee_params: the library re
     float    scale;              /* 1 (default): multiplies the map's radiance; finite, >= 0 */
     float    rot[9];             /* identity (default): rows of the world → environment rotation */
     int32_t  camera_visible;     /* 1 (default); 0: camera rays that miss add cam->background instead (compositing) */
-    int32_t  reserved[3];        /* 0: room to grow */
+    int32_t  glossy;             /* 0 (default); 1: light samples at METAL's reflect branch too (rt_render_nee, "glossy = 1"); modes 1 and 2 */
+    int32_t  reserved[2];        /* 0: room to grow */
 } rt_env_params;
 /* Defaults into *p, struct_bytes = sizeof(rt_env_params). */
 void rt_env_params_init(rt_env_params *p);
@@ -878,6 +909,10 @@ rt_status rt_env_from_equirect(const float *rgb, int32_t w, int32_t h, int32_t n
  *        ray's closest hit must be sphere e (nee->sample_planes = 1: steps 2p … 4p for a plane entry, and the hit must be entry e); its contribution is added to the sample's radiance as soon as it is known to count;
  *     5. at the same event: the environment sample, rt_render_env's steps 1 … 4 from the env state; its shadow ray is an occlusion
  *        query from the same point x; its contribution is added after the emitter's.
+ *   Glossy events (nee->glossy, env_params->glossy): a METAL reflect vertex with fuzz >= RT_GLOSSY_MIN_FUZZ and
+ *     k + 1 < max_depth is a glossy event when at least one light is on with its switch at 1.  It takes the emitter sample, then the
+ *     environment sample, each if its own light is on and its own switch is 1 — the order of a diffuse vertex — and the ray that leaves
+ *     it is weighted (by pc) only against the lights whose switch is 1; against the other it keeps weight 1.
  *   Spheres are hits and the map is misses: the two estimators never weight the same radiance, each keeps its own two-strategy MIS
  *   against the BSDF ray, and the sum has rt_render's expectation under that map.
  *   Identities, bit for bit: env == NULL, no lens, no motion, sample_emitters = 1 = rt_render_nee with the same nee parameters;

@@ -2327,6 +2327,7 @@ struct NeeSetup {
     int32_t mis = 1;
     int32_t planes = 0;           // sample_planes
     int32_t select = 0;           // 0: the power table; 1: the light tree
+    int32_t glossy = 0;           // 1: METAL's reflect branch takes light samples too (the glossy kernels)
 };
 rt_status nee_setup(const char *what, const rt_nee_params *params, NeeSetup &N) {
     const std::string w(what);
@@ -2338,6 +2339,9 @@ rt_status nee_setup(const char *what, const rt_nee_params *params, NeeSetup &N) 
     if (params && params->struct_bytes < 16u) np.select = 0;
     if (np.sample_planes != 0 && np.sample_planes != 1) return fail(RT_ERR_INVALID_ARG, w + ": sample_planes must be 0 or 1");
     if (np.select != 0 && np.select != 1) return fail(RT_ERR_INVALID_ARG, w + ": select must be 0 or 1");
+    if (params && params->struct_bytes < 20u) np.glossy = 0;
+    if (np.glossy != 0 && np.glossy != 1) return fail(RT_ERR_INVALID_ARG, w + ": glossy must be 0 or 1");
+    N.glossy = np.glossy;
     N.mis = np.mis;
     N.planes = np.sample_planes;
     N.select = np.select;
@@ -2611,7 +2615,10 @@ rt_status rt_render_nee(rt_scene *sc, const rt_camera_data *cam, const rt_nee_pa
     if (const rt_status st = nee_setup("rt_render_nee", params, N)) return st;
     if (!sc) return fail(RT_ERR_INVALID_ARG, "rt_render_nee: null scene");
     auto with_table = [&](auto frame) {
-        return with_emitter_table(sc, N, true, [&](const auto &T) { return frame((const void *)rtk::light_render_kernel<std::decay_t<decltype(T)>>, &T); });
+        return with_emitter_table(sc, N, true, [&](const auto &T) {
+            using Table = std::decay_t<decltype(T)>;
+            return frame(N.glossy ? (const void *)rtk::light_gloss_render_kernel<Table> : (const void *)rtk::light_render_kernel<Table>, &T);
+        });
     };
     return render_light_impl("rt_render_nee", nullptr, with_table, sc, cam, shard, sample_first, d_fb_sum, hip_stream, sync, timing);
 }
@@ -2695,7 +2702,9 @@ rt_status rt_trace_samples_nee(rt_scene *sc, const rt_camera_data *cam, const rt
     if ((st = check_device(sc)) != RT_OK) return st;
     return run_probe("rt_trace_samples_nee: ", P, cam, n, ijs, radiance, rays, final_seed, final_nee_seed, nullptr, [&](const rtk::KParams &KP, uint32_t *d_nee, uint32_t *) {
         return with_emitter_table(sc, N, true, [&](const auto &T) {
-            hipLaunchKernelGGL(rtk::light_probe_kernel<std::decay_t<decltype(T)>>, dim3((n + 255) / 256), dim3(256), 0, 0, KP, T, d_nee);
+            using Table = std::decay_t<decltype(T)>;
+            if (N.glossy) hipLaunchKernelGGL(rtk::light_gloss_probe_kernel<Table>, dim3((n + 255) / 256), dim3(256), 0, 0, KP, T, d_nee);
+            else hipLaunchKernelGGL(rtk::light_probe_kernel<Table>, dim3((n + 255) / 256), dim3(256), 0, 0, KP, T, d_nee);
             return RT_OK;
         });
     });
@@ -2753,6 +2762,7 @@ rt_status env_setup(const char *what, const rt_env_params *params, rt_env_params
     if (np.mode < 0 || np.mode > 2) return fail(RT_ERR_INVALID_ARG, w + ": mode must be 0, 1 or 2");
     if (!(std::isfinite(np.scale) && np.scale >= 0.0f)) return fail(RT_ERR_INVALID_ARG, w + ": scale must be finite and not negative");
     if (np.camera_visible != 0 && np.camera_visible != 1) return fail(RT_ERR_INVALID_ARG, w + ": camera_visible must be 0 or 1");
+    if (np.glossy != 0 && np.glossy != 1) return fail(RT_ERR_INVALID_ARG, w + ": glossy must be 0 or 1");
     for (int a = 0; a < 3; ++a)
         for (int b = a; b < 3; ++b) {
             double d = 0.0;
@@ -2932,7 +2942,7 @@ rt_status rt_render_env(rt_scene *sc, const rt_camera_data *cam, const rt_env *e
     if (!sc) return fail(RT_ERR_INVALID_ARG, "rt_render_env: null scene");
     auto with_env = [&](auto frame) {
         const rtk::EnvDev E = env_dev_of(env, np);
-        return frame((const void *)rtk::light_render_kernel<rtk::EnvDev>, &E);
+        return frame(np.glossy ? (const void *)rtk::light_gloss_render_kernel<rtk::EnvDev> : (const void *)rtk::light_render_kernel<rtk::EnvDev>, &E);
     };
     return render_light_impl("rt_render_env", &env->device, with_env, sc, cam, shard, sample_first, d_fb_sum, hip_stream, sync, timing);
 }
@@ -2949,7 +2959,8 @@ rt_status rt_trace_samples_env(rt_scene *sc, const rt_camera_data *cam, const rt
     if ((st = check_device(sc)) != RT_OK) return st;
     if (env->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_env: the environment was created on another device than the scene");
     return run_probe("rt_trace_samples_env: ", P, cam, n, ijs, radiance, rays, final_seed, final_env_seed, nullptr, [&](const rtk::KParams &KP, uint32_t *d_env, uint32_t *) {
-        hipLaunchKernelGGL(rtk::light_probe_kernel<rtk::EnvDev>, dim3((n + 255) / 256), dim3(256), 0, 0, KP, env_dev_of(env, np), d_env);
+        if (np.glossy) hipLaunchKernelGGL(rtk::light_gloss_probe_kernel<rtk::EnvDev>, dim3((n + 255) / 256), dim3(256), 0, 0, KP, env_dev_of(env, np), d_env);
+        else hipLaunchKernelGGL(rtk::light_probe_kernel<rtk::EnvDev>, dim3((n + 255) / 256), dim3(256), 0, 0, KP, env_dev_of(env, np), d_env);
         return RT_OK;
     });
 }
@@ -2988,16 +2999,28 @@ rt_status lit_setup(const char *what, const rt_camera_data *cam_open, const rt_l
     return RT_OK;
 }
 // The kernels' light: the call's emitter table (with_emitter_table; emitters off: an empty one) and the environment (none: off).
-// Returns f(light), light a Lit<Table> of the table's type
+// Returns f(light), light a Lit<Table> of the table's type — a GlossLit<Table> when a light's glossy switch is on
 extern "C++" template <class F>
 rt_status with_lit(rt_scene *sc, const LitSetup &S, F &&f) {
     return with_emitter_table(sc, S.nee, S.emitters, [&](const auto &table) {
-        rtk::Lit<std::decay_t<decltype(table)>> T{};
-        T.N = table;
-        if (S.env) {
-            T.E = env_dev_of(S.env, S.ep);
-            T.env_on = 1;
+        using Table = std::decay_t<decltype(table)>;
+        auto fill = [&](rtk::Lit<Table> &T) {
+            T.N = table;
+            if (S.env) {
+                T.E = env_dev_of(S.env, S.ep);
+                T.env_on = 1;
+            }
+        };
+        const int32_t gn = S.emitters && S.nee.glossy ? 1 : 0, ge = S.env && S.ep.glossy ? 1 : 0;
+        if (gn || ge) {
+            rtk::GlossLit<Table> G{};
+            fill(G);
+            G.gn = gn;
+            G.ge = ge;
+            return f(G);
         }
+        rtk::Lit<Table> T{};
+        fill(T);
         return f(T);
     });
 }
@@ -3010,8 +3033,7 @@ rt_status rt_render_lit(rt_scene *sc, const rt_camera_data *cam_open, const rt_l
     if (!sc) return fail(RT_ERR_INVALID_ARG, "rt_render_lit: null scene");
     auto with_light = [&](auto frame) {
         return with_lit(sc, S, [&](const auto &T) {
-            using Table = decltype(T.N);
-            return frame(S.lens ? (const void *)rtk::lit_render_kernel<true, Table> : (const void *)rtk::lit_render_kernel<false, Table>, &T);
+            return frame(S.lens ? rtk::lit_frame_kernel_of<true>(T) : rtk::lit_frame_kernel_of<false>(T), &T);
         });
     };
     return render_light_impl("rt_render_lit", S.env ? &S.env->device : nullptr, with_light, sc, cam_open, shard, sample_first, d_fb_sum, hip_stream, sync, timing,
@@ -3067,9 +3089,8 @@ rt_status rt_render_lit_adaptive_rule(rt_scene *sc, const rt_camera_data *cam_op
 
     // ---- 3. the light, once, and the two kernels it needs: the frame's and its list variant
     return with_lit(sc, S, [&](const auto &T) -> rt_status {
-        using Table = decltype(T.N);
-        const void *frame_kernel = S.lens ? (const void *)rtk::lit_render_kernel<true, Table> : (const void *)rtk::lit_render_kernel<false, Table>;
-        const void *list_kernel = S.lens ? (const void *)rtk::lit_list_render_kernel<true, Table> : (const void *)rtk::lit_list_render_kernel<false, Table>;
+        const void *frame_kernel = S.lens ? rtk::lit_frame_kernel_of<true>(T) : rtk::lit_frame_kernel_of<false>(T);
+        const void *list_kernel = S.lens ? rtk::lit_list_kernel_of<true>(T) : rtk::lit_list_kernel_of<false>(T);
         rt_timing t{};
         kernel_resources(rounds > 0 ? list_kernel : frame_kernel, t.trace_vgprs, t.trace_scratch_bytes);
         CallClock &clock = sc->clock[kClockLight];
@@ -3201,8 +3222,13 @@ rt_status rt_trace_samples_lit(rt_scene *sc, const rt_camera_data *cam_open, con
         return with_lit(sc, S, [&](const auto &T) {
             using Table = decltype(T.N);
             const dim3 grid((n + 255) / 256), block(256);
-            if (S.lens) hipLaunchKernelGGL((rtk::lit_probe_kernel<true, Table>), grid, block, 0, 0, KP, T, S.C, d_nee, d_env);
-            else hipLaunchKernelGGL((rtk::lit_probe_kernel<false, Table>), grid, block, 0, 0, KP, T, S.C, d_nee, d_env);
+            if constexpr (rtk::kLitGlossy<std::decay_t<decltype(T)>>) {
+                if (S.lens) hipLaunchKernelGGL((rtk::lit_gloss_probe_kernel<true, Table>), grid, block, 0, 0, KP, T, S.C, d_nee, d_env);
+                else hipLaunchKernelGGL((rtk::lit_gloss_probe_kernel<false, Table>), grid, block, 0, 0, KP, T, S.C, d_nee, d_env);
+            } else {
+                if (S.lens) hipLaunchKernelGGL((rtk::lit_probe_kernel<true, Table>), grid, block, 0, 0, KP, T, S.C, d_nee, d_env);
+                else hipLaunchKernelGGL((rtk::lit_probe_kernel<false, Table>), grid, block, 0, 0, KP, T, S.C, d_nee, d_env);
+            }
             return RT_OK;
         });
     });

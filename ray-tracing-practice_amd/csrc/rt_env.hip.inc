@@ -68,15 +68,18 @@ __device__ __forceinline__ int32_t env_pick(const float *cdf, int32_t n, float u
 }
 
 // what a ray of direction d and throughput beta that hits nothing adds: beta * sE(d), weighted when the ray left a diffuse event
-__device__ __forceinline__ f3 env_miss(const EnvDev &E, f3 d, f3 beta, bool prev_diffuse) {
+// (prev: the carried fact — rt_light.hip.inc, "the carried value" — whose pb is RT_NEE_PB after a diffuse event, pg after a glossy one)
+template <class Carry>
+__device__ __forceinline__ f3 env_miss(const EnvDev &E, f3 d, f3 beta, Carry prev) {
     f3 p;
     const int32_t t = env_texel(env_rotate(E, d), E.n, p);
     const float4 T = E.texels[t];
     f3 term = mul(beta, mk(E.scale * T.x, E.scale * T.y, E.scale * T.z));
-    if (prev_diffuse && E.sampled) {
+    if (carry_on(prev) && E.sampled) {
         const float q2 = dot(p, p);
         const float pl = env_pl(E, T.w, q2, sqrt_cr(q2));
-        const float wb = E.mis ? (kNeePb * kNeePb) / (kNeePb * kNeePb + pl * pl) : (pl > 0.0f ? 0.0f : 1.0f);
+        const float pb = carry_pb(prev);
+        const float wb = E.mis ? (pb * pb) / (pb * pb + pl * pl) : (pl > 0.0f ? 0.0f : 1.0f);
         term = scale(wb, term);
     }
     return term;
@@ -84,7 +87,8 @@ __device__ __forceinline__ f3 env_miss(const EnvDev &E, f3 d, f3 beta, bool prev
 
 // The light sample of a diffuse vertex with face-forwarded normal n, albedo a and throughput beta (before the attenuation): false =
 // no contribution; else the shadow ray's direction and what it adds when it hits nothing
-__device__ __forceinline__ bool env_sample(const EnvDev &E, uint32_t &env, f3 n, f3 a, f3 beta, f3 &dir, f3 &c) {
+template <class Pb>
+__device__ __forceinline__ bool env_sample(const EnvDev &E, uint32_t &env, f3 n, f3 a, f3 beta, Pb PB, f3 &dir, f3 &c) {
     const float ua = random_float(env);
     const int32_t iy = env_pick(E.row_cdf, E.n, ua);
     if (iy >= E.n) return false;
@@ -102,9 +106,11 @@ __device__ __forceinline__ bool env_sample(const EnvDev &E, uint32_t &env, f3 n,
     dir = mk((E.rot[0] * we.x + E.rot[3] * we.y) + E.rot[6] * we.z, (E.rot[1] * we.x + E.rot[4] * we.y) + E.rot[7] * we.z,
              (E.rot[2] * we.x + E.rot[5] * we.y) + E.rot[8] * we.z);
     if (!(dot(dir, n) > 0.0f)) return false;
+    const float pb = PB(dir);
+    if (Pb::kGlossy && pb == 0.0f) return false;
     const float4 T = E.texels[(size_t)iy * (size_t)E.n + (size_t)ix];
     const float pl = env_pl(E, T.w, q2, q);
-    const float f = E.mis ? (kNeePb * pl) / (pl * pl + kNeePb * kNeePb) : kNeePb / pl;
+    const float f = E.mis ? (pb * pl) / (pl * pl + pb * pb) : pb / pl;
     c = scale(f, mul(mul(beta, a), mk(E.scale * T.x, E.scale * T.y, E.scale * T.z)));
     return true;
 }

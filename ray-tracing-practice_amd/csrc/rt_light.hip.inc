@@ -38,34 +38,36 @@ template <class Light> constexpr bool kLightOcclusion = false;
 template <> constexpr bool kLightOcclusion<EnvDev> = true;
 
 // miss: what the lane's ray adds when it hits nothing
-template <class Table> __device__ __forceinline__ f3 light_miss(const KParams &P, const Table &, const Lane &L, bool) {
+// (Carry: the carried value's type — bool in the kernels without glossy events, float in those with; rt_nee.hip.inc)
+template <class Table, class Carry> __device__ __forceinline__ f3 light_miss(const KParams &P, const Table &, const Lane &L, Carry) {
     static_assert(kEmitterTable<Table>, "not an emitter table");
     return mul(L.beta, mk(P.bg[0], P.bg[1], P.bg[2]));
 }
-__device__ __forceinline__ f3 light_miss(const KParams &P, const EnvDev &E, const Lane &L, bool prev_diffuse) {
+template <class Carry> __device__ __forceinline__ f3 light_miss(const KParams &P, const EnvDev &E, const Lane &L, Carry prev_diffuse) {
     if (L.depth == 0 && !E.camera_visible) return mul(L.beta, mk(P.bg[0], P.bg[1], P.bg[2]));
     return env_miss(E, L.d, L.beta, prev_diffuse);
 }
 // emitted: beta * emitted of the hit (sphere or plane idx) — weighted when a BSDF ray from a diffuse event found a table sphere; the
 // environment leaves it to the path alone.  Once per kind of table (B: T's emitter_base), with pmf_e by entry_pmf from the ray's origin
-template <class Table>
-__device__ __forceinline__ f3 emitter_emitted(const KParams &P, const Table &T, const NeeTable &B, const Lane &L, int32_t idx, bool is_plane, bool prev_diffuse, f3 emitted) {
-    if (prev_diffuse && !is_plane) {
+template <class Table, class Carry>
+__device__ __forceinline__ f3 emitter_emitted(const KParams &P, const Table &T, const NeeTable &B, const Lane &L, int32_t idx, bool is_plane, Carry prev_diffuse, f3 emitted) {
+    if (carry_on(prev_diffuse) && !is_plane) {
         const int32_t e = nee_find(B, idx);
         if (e >= 0) {
             f3 w;
             float d2, om, pl = 0.0f;
             if (nee_cone(L.o, P.spheres[idx], w, d2, om)) pl = entry_pmf(T, e, L.o) * nee_pdf_cone(om);
-            const float wb = B.mis ? (kNeePb * kNeePb) / (kNeePb * kNeePb + pl * pl) : (pl > 0.0f ? 0.0f : 1.0f);
+            const float pb = carry_pb(prev_diffuse);
+            const float wb = B.mis ? (pb * pb) / (pb * pb + pl * pl) : (pl > 0.0f ? 0.0f : 1.0f);
             emitted = scale(wb, emitted);
         }
     }
     return emitted;
 }
 // (the two-kind table: a table sphere as above, a table plane by step 3p from the ray's origin to the vertex's point)
-template <class Table>
-__device__ __forceinline__ f3 emitter_emitted(const KParams &P, const Table &T, const EmitTable &B, const Lane &L, int32_t idx, bool is_plane, bool prev_diffuse, f3 emitted) {
-    if (prev_diffuse) {
+template <class Table, class Carry>
+__device__ __forceinline__ f3 emitter_emitted(const KParams &P, const Table &T, const EmitTable &B, const Lane &L, int32_t idx, bool is_plane, Carry prev_diffuse, f3 emitted) {
+    if (carry_on(prev_diffuse)) {
         const int32_t e = emit_find(B, L.hit);
         if (e >= 0) {
             f3 w;
@@ -77,33 +79,42 @@ __device__ __forceinline__ f3 emitter_emitted(const KParams &P, const Table &T, 
                 float d2, om;
                 if (nee_cone(L.o, P.spheres[idx], w, d2, om)) pl = entry_pmf(T, e, L.o) * nee_pdf_cone(om);
             }
-            const float wb = B.mis ? (kNeePb * kNeePb) / (kNeePb * kNeePb + pl * pl) : (pl > 0.0f ? 0.0f : 1.0f);
+            const float pb = carry_pb(prev_diffuse);
+            const float wb = B.mis ? (pb * pb) / (pb * pb + pl * pl) : (pl > 0.0f ? 0.0f : 1.0f);
             emitted = scale(wb, emitted);
         }
     }
     return emitted;
 }
-template <class Table>
-__device__ __forceinline__ f3 light_emitted(const KParams &P, const Table &T, const Lane &L, int32_t idx, bool is_plane, bool prev_diffuse, f3 emitted) {
+template <class Table, class Carry>
+__device__ __forceinline__ f3 light_emitted(const KParams &P, const Table &T, const Lane &L, int32_t idx, bool is_plane, Carry prev_diffuse, f3 emitted) {
     return emitter_emitted(P, T, emitter_base(T), L, idx, is_plane, prev_diffuse, emitted);
 }
-__device__ __forceinline__ f3 light_emitted(const KParams &, const EnvDev &, const Lane &, int32_t, bool, bool, f3 emitted) { return emitted; }
+template <class Carry>
+__device__ __forceinline__ f3 light_emitted(const KParams &, const EnvDev &, const Lane &, int32_t, bool, Carry, f3 emitted) { return emitted; }
 // sample: the light sample of a diffuse vertex at x (face-forwarded normal n, albedo a, throughput beta before the attenuation).  false:
 // none; else the shadow ray's direction, what it adds when it reaches the light, and (emitters) the code of the sphere to reach.  A tree
-// table picks by tree_pick, with pmf_e(x) from the descent
-__device__ __forceinline__ bool light_sample(const KParams &P, const NeeTable &T, uint32_t &ls, f3 x, f3 n, f3 a, f3 beta, f3 &dir, f3 &c, int32_t &code) {
-    return nee_sample(P, T, ls, x, n, a, beta, dir, c, code);
+// table picks by tree_pick, with pmf_e(x) from the descent.  PB: the BSDF strategy's density in the sampled direction (PbDiffuse, or
+// PbGlossy at a glossy event)
+template <class Pb>
+__device__ __forceinline__ bool light_sample(const KParams &P, const NeeTable &T, uint32_t &ls, f3 x, f3 n, f3 a, f3 beta, Pb PB, f3 &dir, f3 &c, int32_t &code) {
+    return nee_sample(P, T, ls, x, n, a, beta, PB, dir, c, code);
 }
-__device__ __forceinline__ bool light_sample(const KParams &P, const EmitTable &T, uint32_t &ls, f3 x, f3 n, f3 a, f3 beta, f3 &dir, f3 &c, int32_t &code) {
-    return emit_sample(P, T, ls, x, n, a, beta, dir, c, code);
+template <class Pb>
+__device__ __forceinline__ bool light_sample(const KParams &P, const EmitTable &T, uint32_t &ls, f3 x, f3 n, f3 a, f3 beta, Pb PB, f3 &dir, f3 &c, int32_t &code) {
+    return emit_sample(P, T, ls, x, n, a, beta, PB, dir, c, code);
 }
-template <class Tree>
-__device__ __forceinline__ bool light_sample(const KParams &P, const Tree &T, uint32_t &ls, f3 x, f3 n, f3 a, f3 beta, f3 &dir, f3 &c, int32_t &code) {
-    static_assert(std::is_same_v<Tree, TreeTable> || std::is_same_v<Tree, TreeEmitTable>, "not a tree table");
-    return tree_sample(P, T, ls, x, n, a, beta, dir, c, code);
+template <class Pb>
+__device__ __forceinline__ bool light_sample(const KParams &P, const TreeTable &T, uint32_t &ls, f3 x, f3 n, f3 a, f3 beta, Pb PB, f3 &dir, f3 &c, int32_t &code) {
+    return tree_sample(P, T, ls, x, n, a, beta, PB, dir, c, code);
 }
-__device__ __forceinline__ bool light_sample(const KParams &, const EnvDev &E, uint32_t &ls, f3, f3 n, f3 a, f3 beta, f3 &dir, f3 &c, int32_t &) {
-    return env_sample(E, ls, n, a, beta, dir, c);
+template <class Pb>
+__device__ __forceinline__ bool light_sample(const KParams &P, const TreeEmitTable &T, uint32_t &ls, f3 x, f3 n, f3 a, f3 beta, Pb PB, f3 &dir, f3 &c, int32_t &code) {
+    return tree_sample(P, T, ls, x, n, a, beta, PB, dir, c, code);
+}
+template <class Pb>
+__device__ __forceinline__ bool light_sample(const KParams &, const EnvDev &E, uint32_t &ls, f3, f3 n, f3 a, f3 beta, Pb PB, f3 &dir, f3 &c, int32_t &) {
+    return env_sample(E, ls, n, a, beta, PB, dir, c);
 }
 // reached: the verdict of a finished shadow walk
 template <class Table> __device__ __forceinline__ bool light_reached(const Table &, const Lane &L, int32_t code) { static_assert(kEmitterTable<Table>, "not an emitter table"); return L.hit == code; }
@@ -119,14 +130,17 @@ __device__ __forceinline__ uint32_t light_seed_of(const Light &T, uint32_t base_
 // shade() of the exact walk (kGuard = false, the global material table, the general build) with light samples:
 //   prev_diffuse: the ray that found this hit (or nothing) left a diffuse event at its origin L.o; diffuse_out: this vertex is one (the
 //   next ray's prev_diffuse); sample: it takes a light sample — the shadow ray (out_o, sdir), which adds c when it reaches the light
-//   (code).  Only a diffuse event whose next query is inside max_depth samples, so a vertex that samples always has a next ray, and
-//   out_o — the hit point — is both rays' origin.
+//   (code).  Only an event whose next query is inside max_depth samples, and out_o — the hit point — is both rays' origin.  A diffuse
+//   event that samples always has a next ray.  A glossy event (METAL's reflect branch with fuzz >= RT_GLOSSY_MIN_FUZZ, in the
+//   instantiations that have them: DESIGN.md §23) samples before the absorption test, so it may sample and return false — "sample, but
+//   no next ray": the caller ends the path behind the shadow verdict.
 // The main stream's draws, the branches, the roulette and the next ray are shade()'s.
 // The vertex is one text for both of its forms — shade_lit (one light sample) and, at the end of this file, shade_lit2 (the emitter's
 // and the environment's): RTP_LIT_VERTEX, the body of a function with L, P, T, prev_diffuse, out_o, out_d and diffuse_out (set to false)
 // in scope.  TAKE_SAMPLES is the statement a diffuse event runs for its light samples, with point, normal, albedo and beta_in (the
-// throughput before the attenuation) at hand.
-#define RTP_LIT_VERTEX(TAKE_SAMPLES)                                                                                                                 \
+// throughput before the attenuation) at hand; GLOSSY_SAMPLES the one METAL's reflect branch runs before its absorption test, with refl
+// (the mirror direction), new_d and absorbed at hand as well — empty where there are no glossy events.
+#define RTP_LIT_VERTEX(TAKE_SAMPLES, GLOSSY_SAMPLES)                                                                                                 \
     if (L.hit < 0) {                                                                                                                                 \
         L.color = add(L.color, light_miss(P, T, L, prev_diffuse));                                                                                   \
         return false;                                                                                                                                \
@@ -222,11 +236,14 @@ __device__ __forceinline__ uint32_t light_seed_of(const Light &T, uint32_t base_
         const float side = dot(new_d, normal) > 0 ? 1.0f : -1.0f;                                                                                    \
         new_o = add(point, scale(side, scale(1e-4f, normal)));                                                                                       \
     } else if (metal_reflect) {                                                                                                                      \
-        new_d = add(reflect(ud, normal), scale(ME.w, in_sphere));                                                                                    \
-        if (!(dot(new_d, normal) > 0)) return false;                                                                                                 \
+        const f3 refl = reflect(ud, normal);                                                                                                         \
+        new_d = add(refl, scale(ME.w, in_sphere));                                                                                                   \
+        const bool absorbed = !(dot(new_d, normal) > 0);                                                                                             \
+        GLOSSY_SAMPLES                                                                                                                               \
+        if (absorbed) return false;                                                                                                                  \
     } else {  /* LAMBERTIAN and METAL's 20 % branch: a diffuse event */                                                                              \
         new_d = scatter_diffuse_dir(in_sphere, normal);                                                                                              \
-        diffuse_out = true;                                                                                                                          \
+        carry_diffuse(diffuse_out);                                                                                                                  \
         TAKE_SAMPLES                                                                                                                                 \
     }                                                                                                                                                \
     L.beta = mul(L.beta, att);                                                                                                                       \
@@ -235,13 +252,24 @@ __device__ __forceinline__ uint32_t light_seed_of(const Light &T, uint32_t base_
     out_o = new_o;                                                                                                                                   \
     out_d = new_d;                                                                                                                                   \
     return true;
-template <class Light>
-__device__ __forceinline__ bool shade_lit(Lane &L, const KParams &P, const Light &T, bool prev_diffuse, uint32_t &ls, f3 &out_o, f3 &out_d,
-                                          f3 &sdir, f3 &c, int32_t &code, bool &sample, bool &diffuse_out) {
+// Carry = bool: the vertex without glossy events (glossy = 0: the kernels as they were); Carry = float: with them (the light's glossy = 1)
+template <class Light, class Carry>
+__device__ __forceinline__ bool shade_lit(Lane &L, const KParams &P, const Light &T, Carry prev_diffuse, uint32_t &ls, f3 &out_o, f3 &out_d,
+                                          f3 &sdir, f3 &c, int32_t &code, bool &sample, Carry &diffuse_out) {
     sample = false;
-    diffuse_out = false;
-    RTP_LIT_VERTEX(if (L.depth + 1 < P.max_depth && light_on(T)) sample = light_sample(P, T, ls, point, normal, albedo, beta_in, sdir, c, code);)
+    diffuse_out = Carry(0);
+    RTP_LIT_VERTEX(if (L.depth + 1 < P.max_depth && light_on(T)) sample = light_sample(P, T, ls, point, normal, albedo, beta_in, PbDiffuse{}, sdir, c, code);,
+                   if constexpr (std::is_same_v<Carry, float>) {
+                       if (ME.w >= kGlossMinFuzz && L.depth + 1 < P.max_depth && light_on(T)) {
+                           sample = light_sample(P, T, ls, point, normal, albedo, beta_in, gloss_pb(refl, ME.w), sdir, c, code);
+                           out_o = point;
+                           if (!absorbed) diffuse_out = gloss_pg(unit(new_d), refl, ME.w);
+                       }
+                   })
 }
+// "sample, but no next ray" across a shadow walk: the pending direction is zeroed (a next ray's never is: dot(new_d, normal) > 0), so
+// the glossy instantiations hold no register more than the others
+__device__ __forceinline__ bool no_next_ray(f3 d) { return d.x == 0.0f && d.y == 0.0f && d.z == 0.0f; }
 
 // one step of the lane's armed ray: reference order, through L1 / L2 (shadow: the ray is a shadow ray)
 template <class Light>
@@ -255,8 +283,9 @@ __device__ __forceinline__ void light_step(Lane &L, const KParams &P, bool shado
 }
 
 // ---- probe (rt_trace_samples_nee / _env): one lane traces one (i, j, s) sample -------------------------------------------------------
-template <class Light>
+template <class Light, bool kGlossy = false>
 __device__ __forceinline__ void light_probe_body(const KParams &P, const Light &T, uint32_t *light_seed_out) {
+    using Carry = std::conditional_t<kGlossy, float, bool>;
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= P.probe_n) return;
     const int32_t i = P.probe_ijs[3 * g], j = P.probe_ijs[3 * g + 1], s = P.probe_ijs[3 * g + 2];
@@ -267,14 +296,15 @@ __device__ __forceinline__ void light_probe_body(const KParams &P, const Light &
     start_sample(L, P, i, j, base_seed, s, ray_o, ray_d);
     begin_ray(L, ray_o, ray_d, 0);
     int32_t rays = 0;
-    bool prev_diffuse = false;
+    Carry prev_diffuse = Carry(0);
     if (P.max_depth > 0) {
         for (;;) {
             rays++;
             while (!traversal_finished<true>(L, kBlocked)) light_step<Light>(L, P, false);
             f3 sdir, c;
             int32_t code = -1;
-            bool sample, diffuse;
+            bool sample;
+            Carry diffuse;
             const bool more = shade_lit(L, P, T, prev_diffuse, ls, ray_o, ray_d, sdir, c, code, sample, diffuse);
             if (sample) {
                 rays++;
@@ -300,10 +330,12 @@ __device__ __forceinline__ void light_probe_body(const KParams &P, const Light &
 // path's shade (shade_lit), or the shadow ray's verdict.
 // Across a shadow walk a lane holds the next ray's direction, the pending contribution and the code to reach (seven registers; the
 // code is dead for the environment): the next ray's origin is the shadow ray's own (L.o), and a vertex that samples always has a next
-// ray, so no flag for it either.
+// ray, so no flag for it either.  kGlossy (the light's glossy = 1): a glossy event may sample without a next ray — the pending
+// direction is then zero, and the shadow verdict ends the path (no_next_ray); the carried value is a float.
 constexpr int32_t kLightIdle = 0, kLightPath = 1, kLightShadow = 2;
-template <class Light>
+template <class Light, bool kGlossy = false>
 __device__ __forceinline__ void light_render_body(const KParams &P, const Light &T) {
+    using Carry = std::conditional_t<kGlossy, float, bool>;
     const int lane = (int)(threadIdx.x & (kWave - 1));
     Lane L;
     L.node = kBlocked;
@@ -316,7 +348,7 @@ __device__ __forceinline__ void light_render_body(const KParams &P, const Light 
     L.seed = 0;
     int32_t phase = kLightIdle;
     uint32_t w = 0, ls = 0;
-    bool prev_diffuse = false;
+    Carry prev_diffuse = Carry(0);
     f3 next_d = mk(0, 0, 0), contrib = mk(0, 0, 0);
     int32_t target = -1;
     uint32_t pool_next = 0, pool_end = 0;        // (wave-uniform)
@@ -352,7 +384,7 @@ __device__ __forceinline__ void light_render_body(const KParams &P, const Light 
                 f3 o, d;
                 start_sample(L, P, pi, pj, base_seed, s, o, d);
                 begin_ray(L, o, d, 0);
-                prev_diffuse = false;
+                prev_diffuse = Carry(0);
                 phase = kLightPath;
             }
         }
@@ -369,10 +401,14 @@ __device__ __forceinline__ void light_render_body(const KParams &P, const Light 
             if (ready) {
                 if (phase == kLightPath) {
                     f3 next_o, sdir;
-                    bool sample, diffuse;
+                    bool sample;
+                    Carry diffuse;
                     const bool more = shade_lit(L, P, T, prev_diffuse, ls, next_o, next_d, sdir, contrib, target, sample, diffuse);
                     prev_diffuse = diffuse;
                     if (sample) {
+                        if constexpr (kGlossy) {
+                            if (!more) next_d = mk(0, 0, 0);
+                        }
                         begin_ray(L, next_o, sdir, 0);
                         phase = kLightShadow;
                     } else if (more) {
@@ -383,8 +419,13 @@ __device__ __forceinline__ void light_render_body(const KParams &P, const Light 
                     }
                 } else {
                     if (light_reached(T, L, target)) L.color = add(L.color, contrib);
-                    begin_ray(L, L.o, next_d, 0);
-                    phase = kLightPath;
+                    if (kGlossy && no_next_ray(next_d)) {
+                        store_sample(P, w, L.color);
+                        phase = kLightIdle;
+                    } else {
+                        begin_ray(L, L.o, next_d, 0);
+                        phase = kLightPath;
+                    }
                 }
                 if (phase == kLightIdle) {
                     L.node = kBlocked;
@@ -406,6 +447,12 @@ template <class Light>
 __global__ void __launch_bounds__(256) light_probe_kernel(const KParams P, const Light T, uint32_t *light_seed_out) { light_probe_body(P, T, light_seed_out); }
 template <class Light>
 __global__ void __launch_bounds__(kLightBlock) light_render_kernel(const KParams P, const Light T) { light_render_body(P, T); }
+// the same two with glossy events (the light's glossy = 1; DESIGN.md §23): instantiations of their own, so that glossy = 0 launches the
+// kernels above as they were
+template <class Light>
+__global__ void __launch_bounds__(256) light_gloss_probe_kernel(const KParams P, const Light T, uint32_t *light_seed_out) { light_probe_body<Light, true>(P, T, light_seed_out); }
+template <class Light>
+__global__ void __launch_bounds__(kLightBlock) light_gloss_render_kernel(const KParams P, const Light T) { light_render_body<Light, true>(P, T); }
 
 // ---- rt_render_lit: the emitter table and an environment at once, from the lens camera (DESIGN.md §16) -------------------------------
 // The third light: both tables, either of which may be off (an emitter table with count 0 — sample_emitters = 0 or no emitter; env_on = 0
@@ -429,6 +476,27 @@ __device__ __forceinline__ f3 light_emitted(const KParams &P, const Lit<Table> &
 }
 template <class Table>
 __device__ __forceinline__ bool env_sampled(const Lit<Table> &T) { return T.env_on && light_on(T.E); }
+// The light of a lit call with a glossy switch on (DESIGN.md §23): a type of its own, so that a call with both off launches the kernels
+// of Lit<Table> as they were.  gn, ge: the emitters' and the environment's switch.  Its carried value is a float with a sign: RT_NEE_PB
+// after a diffuse event, -pg after a glossy one — a ray from a glossy event is weighted only against the lights whose switch is on
+// (the switches are the call's, so "on at that vertex" is "on"), and -0 is none.
+template <class Table>
+struct GlossLit : Lit<Table> {
+    int32_t gn, ge;
+};
+__device__ __forceinline__ float lit_carry(float c, int32_t on) { return c >= 0.0f ? c : (on ? -c : 0.0f); }
+template <class Table>
+__device__ __forceinline__ f3 light_miss(const KParams &P, const GlossLit<Table> &T, const Lane &L, float prev) {
+    if (T.env_on) return light_miss(P, T.E, L, lit_carry(prev, T.ge));
+    return light_miss(P, T.N, L, prev);
+}
+template <class Table>
+__device__ __forceinline__ f3 light_emitted(const KParams &P, const GlossLit<Table> &T, const Lane &L, int32_t idx, bool is_plane, float prev, f3 emitted) {
+    return light_emitted(P, T.N, L, idx, is_plane, lit_carry(prev, T.gn), emitted);
+}
+template <class L> constexpr bool kLitGlossy = false;
+template <class Table> constexpr bool kLitGlossy<GlossLit<Table>> = true;
+template <class L> using LitCarry = std::conditional_t<kLitGlossy<L>, float, bool>;
 
 // The two light samples of a lit vertex: the emitter's (a: the shadow ray has to reach the primitive `code`) and the environment's (b: it has
 // to reach nothing).  Both are drawn at shade time — the streams are independent, and the order of the adds is the caller's.
@@ -438,14 +506,27 @@ struct LitSamples {
     bool a, b;
 };
 template <class Lit>
-__device__ __forceinline__ bool shade_lit2(Lane &L, const KParams &P, const Lit &T, bool prev_diffuse, uint32_t &nee, uint32_t &env, f3 &out_o,
-                                           f3 &out_d, LitSamples &S, bool &diffuse_out) {
+__device__ __forceinline__ bool shade_lit2(Lane &L, const KParams &P, const Lit &T, LitCarry<Lit> prev_diffuse, uint32_t &nee, uint32_t &env, f3 &out_o,
+                                           f3 &out_d, LitSamples &S, LitCarry<Lit> &diffuse_out) {
     S.a = false;
     S.b = false;
-    diffuse_out = false;
+    diffuse_out = LitCarry<Lit>(0);
     RTP_LIT_VERTEX(if (L.depth + 1 < P.max_depth) {
-        if (light_on(T.N)) S.a = light_sample(P, T.N, nee, point, normal, albedo, beta_in, S.adir, S.ac, S.code);
-        if (env_sampled(T)) S.b = light_sample(P, T.E, env, point, normal, albedo, beta_in, S.bdir, S.bc, S.code);
+        if (light_on(T.N)) S.a = light_sample(P, T.N, nee, point, normal, albedo, beta_in, PbDiffuse{}, S.adir, S.ac, S.code);
+        if (env_sampled(T)) S.b = light_sample(P, T.E, env, point, normal, albedo, beta_in, PbDiffuse{}, S.bdir, S.bc, S.code);
+    },
+    if constexpr (kLitGlossy<Lit>) {
+        if (ME.w >= kGlossMinFuzz && L.depth + 1 < P.max_depth) {
+            const bool ga = T.gn && light_on(T.N);
+            const bool gb = T.ge && env_sampled(T);
+            if (ga || gb) {
+                if (!absorbed) diffuse_out = -gloss_pg(unit(new_d), refl, ME.w);
+                const PbGlossy pbg = gloss_pb(refl, ME.w);
+                if (ga) S.a = light_sample(P, T.N, nee, point, normal, albedo, beta_in, pbg, S.adir, S.ac, S.code);
+                if (gb) S.b = light_sample(P, T.E, env, point, normal, albedo, beta_in, pbg, S.bdir, S.bc, S.code);
+                out_o = point;
+            }
+        }
     })
 }
 #undef RTP_LIT_VERTEX
@@ -478,14 +559,14 @@ __device__ __forceinline__ void lit_probe_body(const KParams &P, const Lit &T, c
     lit_start<kLens>(L, P, C, i, j, base_seed, s, ray_o, ray_d);
     begin_ray(L, ray_o, ray_d, 0);
     int32_t rays = 0;
-    bool prev_diffuse = false;
+    LitCarry<Lit> prev_diffuse = LitCarry<Lit>(0);
     if (P.max_depth > 0) {
         for (;;) {
             rays++;
             while (!traversal_finished<true>(L, kBlocked)) lit_step(L, P, false);
             LitSamples S;
             S.code = -1;
-            bool diffuse;
+            LitCarry<Lit> diffuse;
             const bool more = shade_lit2(L, P, T, prev_diffuse, nee, env, ray_o, ray_d, S, diffuse);
             if (S.a) {
                 rays++;
@@ -533,7 +614,7 @@ constexpr int32_t kLitShadowA = 2, kLitShadowAB = 3, kLitShadowB = 4;
     L.seed = 0;                                                                                                     \
     int32_t phase = kLightIdle;                                                                                     \
     uint32_t w = 0, nee = 0, env = 0;                                                                               \
-    bool prev_diffuse = false;                                                                                      \
+    LitCarry<Lit> prev_diffuse = LitCarry<Lit>(0);                                                                  \
     f3 next_d = mk(0, 0, 0);                                                                                        \
     LitSamples S;                                                                                                   \
     S.adir = S.ac = S.bdir = S.bc = mk(0, 0, 0);                                                                    \
@@ -573,7 +654,7 @@ constexpr int32_t kLitShadowA = 2, kLitShadowAB = 3, kLitShadowB = 4;
                 f3 o, d;                                                                                            \
                 lit_start<kLens>(L, P, C, pi, pj, base_seed, s, o, d);                                              \
                 begin_ray(L, o, d, 0);                                                                              \
-                prev_diffuse = false;                                                                               \
+                prev_diffuse = LitCarry<Lit>(0);                                                                    \
                 phase = kLightPath;                                                                                 \
             }                                                                                                       \
         }                                                                                                           \
@@ -590,9 +671,10 @@ constexpr int32_t kLitShadowA = 2, kLitShadowAB = 3, kLitShadowB = 4;
             if (ready) {                                                                                            \
                 if (phase == kLightPath) {                                                                          \
                     f3 next_o;                                                                                      \
-                    bool diffuse;                                                                                   \
+                    LitCarry<Lit> diffuse;                                                                          \
                     const bool more = shade_lit2(L, P, T, prev_diffuse, nee, env, next_o, next_d, S, diffuse);      \
                     prev_diffuse = diffuse;                                                                         \
+                    if (kLitGlossy<Lit> && !more && (S.a || S.b)) next_d = mk(0, 0, 0);                             \
                     if (S.a) {                                                                                      \
                         begin_ray(L, next_o, S.adir, 0);                                                            \
                         phase = S.b ? kLitShadowAB : kLitShadowA;                                                   \
@@ -607,13 +689,23 @@ constexpr int32_t kLitShadowA = 2, kLitShadowAB = 3, kLitShadowB = 4;
                     }                                                                                               \
                 } else if (phase == kLitShadowB) {                                                                  \
                     if (L.hit < 0) L.color = add(L.color, S.bc);                                                    \
-                    begin_ray(L, L.o, next_d, 0);                                                                   \
-                    phase = kLightPath;                                                                             \
+                    if (kLitGlossy<Lit> && no_next_ray(next_d)) {                                                   \
+                        store_sample(P, w, L.color);                                                                \
+                        phase = kLightIdle;                                                                         \
+                    } else {                                                                                        \
+                        begin_ray(L, L.o, next_d, 0);                                                               \
+                        phase = kLightPath;                                                                         \
+                    }                                                                                               \
                 } else {                                                                                            \
                     if (L.hit == S.code) L.color = add(L.color, S.ac);                                              \
                     const bool then_env = phase == kLitShadowAB;                                                    \
-                    begin_ray(L, L.o, then_env ? S.bdir : next_d, 0);                                               \
-                    phase = then_env ? kLitShadowB : kLightPath;                                                    \
+                    if (kLitGlossy<Lit> && !then_env && no_next_ray(next_d)) {                                      \
+                        store_sample(P, w, L.color);                                                                \
+                        phase = kLightIdle;                                                                         \
+                    } else {                                                                                        \
+                        begin_ray(L, L.o, then_env ? S.bdir : next_d, 0);                                           \
+                        phase = then_env ? kLitShadowB : kLightPath;                                                \
+                    }                                                                                               \
                 }                                                                                                   \
                 if (phase == kLightIdle) {                                                                          \
                     L.node = kBlocked;                                                                              \
@@ -628,6 +720,7 @@ constexpr int32_t kLitShadowA = 2, kLitShadowAB = 3, kLitShadowB = 4;
             }                                                                                                       \
         }                                                                                                           \
     }
+// With a GlossLit light a glossy event may sample without a next ray: next_d is zeroed, and the last shadow verdict ends the path.
 // kList = false: the work indices are [0, P.total_work) — a pass of rt_render_lit's.
 // kList = true (rt_render_lit_adaptive's rounds; DESIGN.md §19): they are the first *P.work_count entries of P.work_list — a length that lives
 // on the device, read once per wave and wave-uniform; a fetched index `mine` then stands for P.work_list[mine], in map_work and in
@@ -656,5 +749,26 @@ __global__ void __launch_bounds__(kLightBlock, 4) lit_render_kernel(const KParam
 // the list variant: rt_render_lit_adaptive's rounds (DESIGN.md §19) — the same body on a list whose length lives on the device
 template <bool kLens, class Table>
 __global__ void __launch_bounds__(kLightBlock, 4) lit_list_render_kernel(const KParams P, const Lit<Table> T, const LensCam C) { lit_render_body<kLens, Lit<Table>, true>(P, T, C); }
+
+// the same three with a glossy switch on (GlossLit<Table>; DESIGN.md §23)
+template <bool kLens, class Table>
+__global__ void __launch_bounds__(256) lit_gloss_probe_kernel(const KParams P, const GlossLit<Table> T, const LensCam C, uint32_t *nee_seed_out, uint32_t *env_seed_out) {
+    lit_probe_body<kLens>(P, T, C, nee_seed_out, env_seed_out);
+}
+// (waves per SIMD the compiler is held to: 4 like the kernels above, except from the lens camera over the sphere-only tree — that vertex
+// holds the mirror direction, the fuzz and the carried value on top of lit_render_kernel<true, TreeTable>'s 128 VGPRs, and at 4 waves it
+// would spill three of them to scratch; 3 waves it is, without scratch: DESIGN.md §23)
+template <bool kLens, class Table> constexpr int kLitGlossWaves = (kLens && std::is_same_v<Table, TreeTable>) ? 3 : 4;
+template <bool kLens, class Table>
+__global__ void __launch_bounds__(kLightBlock, (kLitGlossWaves<kLens, Table>)) lit_gloss_render_kernel(const KParams P, const GlossLit<Table> T, const LensCam C) { lit_render_body<kLens>(P, T, C); }
+template <bool kLens, class Table>
+__global__ void __launch_bounds__(kLightBlock, (kLitGlossWaves<kLens, Table>)) lit_gloss_list_render_kernel(const KParams P, const GlossLit<Table> T, const LensCam C) {
+    lit_render_body<kLens, GlossLit<Table>, true>(P, T, C);
+}
+// the kernels of a lit light, by its type
+template <bool kLens, class Table> const void *lit_frame_kernel_of(const Lit<Table> &) { return (const void *)lit_render_kernel<kLens, Table>; }
+template <bool kLens, class Table> const void *lit_list_kernel_of(const Lit<Table> &) { return (const void *)lit_list_render_kernel<kLens, Table>; }
+template <bool kLens, class Table> const void *lit_frame_kernel_of(const GlossLit<Table> &) { return (const void *)lit_gloss_render_kernel<kLens, Table>; }
+template <bool kLens, class Table> const void *lit_list_kernel_of(const GlossLit<Table> &) { return (const void *)lit_gloss_list_render_kernel<kLens, Table>; }
 
 }  // namespace rtk

@@ -15,6 +15,50 @@ namespace rtk {
 constexpr uint32_t kNeeStreamKey = RT_NEE_STREAM_KEY;       // nee = wang_hash(sample_seed ^ key)
 constexpr float kNeeTwoPi = RT_NEE_TWO_PI;
 constexpr float kNeePb = RT_NEE_PB;                          // density of the uniform-hemisphere direction, 1 / (2 pi)
+constexpr float kGlossMinFuzz = RT_GLOSSY_MIN_FUZZ;          // a METAL reflect branch below this fuzz is a mirror: no light sample
+
+// pg of the header ("glossy events"): the density in solid angle of unit(r + fuzz * B), B uniform in the unit ball, at the direction w —
+// the integral of t^2 over the chord w cuts through the ball of radius fuzz about r, over the ball's volume
+__device__ __forceinline__ float gloss_pg(f3 w, f3 r, float fuzz) {
+    const float c = dot(w, r);
+    const float ff = fuzz * fuzz;
+    const float disc = (c * c - 1.0f) + ff;
+    if (!(disc > 0.0f)) return 0.0f;
+    const float s = sqrt_cr(disc);
+    const float t2 = c + s;
+    if (!(t2 > 0.0f)) return 0.0f;
+    const float t1 = c - s;
+    const float f3v = ff * fuzz;
+    if (t1 > 0.0f) return (s * (3.0f * (c * c) + s * s)) / (kNeeTwoPi * f3v);
+    return ((t2 * t2) * t2) / ((2.0f * kNeeTwoPi) * f3v);        // fuzz > 1: the vertex is inside the ball
+}
+// pb of a light sample in the direction w: the BSDF strategy's density there.  A diffuse event's is the constant (the expressions fold to
+// what they were when kNeePb stood in them); a glossy event's is pg about its mirror direction
+// The carried value: what a ray remembers of the event it left, for the weight of what it finds.  The kernels of today carry a bool
+// (diffuse or not: pb is the constant); the glossy instantiations a float — 0 none, RT_NEE_PB diffuse, pg(unit(new_d)) glossy, and a pg
+// that rounded to 0 is "none": weight 1, never 0 / 0
+__device__ __forceinline__ bool carry_on(bool c) { return c; }
+__device__ __forceinline__ bool carry_on(float c) { return c != 0.0f; }
+__device__ __forceinline__ float carry_pb(bool) { return kNeePb; }
+__device__ __forceinline__ float carry_pb(float c) { return c; }
+__device__ __forceinline__ void carry_diffuse(bool &c) { c = true; }
+__device__ __forceinline__ void carry_diffuse(float &c) { c = kNeePb; }
+struct PbDiffuse {
+    static constexpr bool kGlossy = false;
+    __device__ __forceinline__ float operator()(f3) const { return kNeePb; }
+};
+struct PbGlossy {
+    static constexpr bool kGlossy = true;
+    f3 r;
+    float fuzz;
+    __device__ __forceinline__ float operator()(f3 w) const { return gloss_pg(w, r, fuzz); }
+};
+__device__ __forceinline__ PbGlossy gloss_pb(f3 r, float fuzz) {
+    PbGlossy g;
+    g.r = r;
+    g.fuzz = fuzz;
+    return g;
+}
 
 // The sphere-only emitter table of a handle (global memory, sphere order): sphere index, cdf (last entry 1), pmf
 struct NeeTable {
@@ -85,10 +129,12 @@ __device__ __forceinline__ bool nee_cone(f3 x, float4 s, f3 &w, float &d2, float
 __device__ __forceinline__ float nee_pdf_cone(float om) { return 1.0f / (kNeeTwoPi * om); }
 
 // The light sample of a diffuse vertex at x (face-forwarded normal n, albedo a, throughput beta before the attenuation): false = no
-// contribution; else the shadow ray's direction (from x), the code of the sphere it has to reach and what it adds then
+// contribution; else the shadow ray's direction (from x), the code of the sphere it has to reach and what it adds then.  PB: the BSDF
+// strategy's density in that direction (PbDiffuse, or at a glossy event PbGlossy — whose 0 is "no contribution" too)
 // steps 2 to 4 for a picked sphere (pmf: where its entry's stands — read only by a sample that counts)
-__device__ __forceinline__ bool nee_sample_sphere(const KParams &P, int32_t sphere, const float *pmf, int32_t mis, uint32_t &nee, f3 x, f3 n, f3 a, f3 beta, f3 &dir,
-                                                  f3 &c, int32_t &code) {
+template <class Pb>
+__device__ __forceinline__ bool nee_sample_sphere(const KParams &P, int32_t sphere, const float *pmf, int32_t mis, uint32_t &nee, f3 x, f3 n, f3 a, f3 beta, Pb PB,
+                                                  f3 &dir, f3 &c, int32_t &code) {
     f3 w;
     float d2, om;
     if (!nee_cone(x, P.spheres[sphere], w, d2, om)) return false;
@@ -114,18 +160,21 @@ __device__ __forceinline__ bool nee_sample_sphere(const KParams &P, int32_t sphe
     const float sx = sin_t * cx, sy = sin_t * cy;
     dir = mk((t1.x * sx + t2.x * sy) + wn.x * cos_t, (t1.y * sx + t2.y * sy) + wn.y * cos_t, (t1.z * sx + t2.z * sy) + wn.z * cos_t);
     if (!(dot(dir, n) > 0.0f)) return false;
+    const float pb = PB(dir);
+    if (Pb::kGlossy && pb == 0.0f) return false;
     const float pl = *pmf * nee_pdf_cone(om);
-    const float f = mis ? (kNeePb * pl) / (pl * pl + kNeePb * kNeePb) : kNeePb / pl;
+    const float f = mis ? (pb * pl) / (pl * pl + pb * pb) : pb / pl;
     const float4 ME = P.materials[3 * P.sphere_mat[sphere] + 1];
     c = scale(f, mul(mul(beta, a), mk(ME.x, ME.y, ME.z)));
     code = 2 * sphere;
     return true;
 }
-__device__ __forceinline__ bool nee_sample(const KParams &P, const NeeTable &T, uint32_t &nee, f3 x, f3 n, f3 a, f3 beta, f3 &dir, f3 &c, int32_t &code) {
+template <class Pb>
+__device__ __forceinline__ bool nee_sample(const KParams &P, const NeeTable &T, uint32_t &nee, f3 x, f3 n, f3 a, f3 beta, Pb PB, f3 &dir, f3 &c, int32_t &code) {
     const float u = random_float(nee);
     const int32_t e = nee_pick(T, u);
     if (e >= T.count) return false;
-    return nee_sample_sphere(P, T.index[e], T.pmf + e, T.mis, nee, x, n, a, beta, dir, c, code);
+    return nee_sample_sphere(P, T.index[e], T.pmf + e, T.mis, nee, x, n, a, beta, PB, dir, c, code);
 }
 
 // ---- emissive planes (sample_planes = 1) ----------------------------------------------------------------------------------------------
@@ -177,29 +226,34 @@ __device__ __forceinline__ bool emit_plane_pa(const KParams &P, int32_t plane, f
     float pa;                                                                                                                            \
     if (!emit_plane_pa(P, plane, T.area[e], x, y, dir, pa)) return false;                                                                \
     if (!(dot(dir, n) > 0.0f)) return false;                                                                                             \
+    const float pb = PB(dir);                                                                                                            \
+    if (Pb::kGlossy && pb == 0.0f) return false;                                                                                         \
     const float pl = PMF * pa;                                                                                                           \
-    const float f = T.mis ? (kNeePb * pl) / (pl * pl + kNeePb * kNeePb) : kNeePb / pl;                                                   \
+    const float f = T.mis ? (pb * pl) / (pl * pl + pb * pb) : pb / pl;                                                                   \
     const float4 ME = P.materials[3 * as_int(P2.w) + 1];                                                                                 \
     c = scale(f, mul(mul(beta, a), mk(ME.x, ME.y, ME.z)));                                                                               \
     code = hit;                                                                                                                          \
     return true;
-__device__ __forceinline__ bool emit_sample_plane(const KParams &P, const EmitTable &T, int32_t e, uint32_t &nee, f3 x, f3 n, f3 a, f3 beta, f3 &dir, f3 &c,
+template <class Pb>
+__device__ __forceinline__ bool emit_sample_plane(const KParams &P, const EmitTable &T, int32_t e, uint32_t &nee, f3 x, f3 n, f3 a, f3 beta, Pb PB, f3 &dir, f3 &c,
                                                   int32_t &code) {
     RTP_EMIT_PLANE_STEPS(T.pmf[e])
 }
 // (the light tree's: pmf is the descent's product)
-__device__ __forceinline__ bool tree_sample_plane(const KParams &P, const EmitTable &T, int32_t e, float pmf, uint32_t &nee, f3 x, f3 n, f3 a, f3 beta, f3 &dir,
+template <class Pb>
+__device__ __forceinline__ bool tree_sample_plane(const KParams &P, const EmitTable &T, int32_t e, float pmf, uint32_t &nee, f3 x, f3 n, f3 a, f3 beta, Pb PB, f3 &dir,
                                                   f3 &c, int32_t &code) {
     RTP_EMIT_PLANE_STEPS(pmf)
 }
 #undef RTP_EMIT_PLANE_STEPS
 // the light sample of the two-kind table: step 1, then the steps of the entry's kind
-__device__ __forceinline__ bool emit_sample(const KParams &P, const EmitTable &T, uint32_t &nee, f3 x, f3 n, f3 a, f3 beta, f3 &dir, f3 &c, int32_t &code) {
+template <class Pb>
+__device__ __forceinline__ bool emit_sample(const KParams &P, const EmitTable &T, uint32_t &nee, f3 x, f3 n, f3 a, f3 beta, Pb PB, f3 &dir, f3 &c, int32_t &code) {
     const float u = random_float(nee);
     const int32_t e = nee_pick(T, u);
     if (e >= T.count) return false;
-    if (e < T.spheres) return nee_sample_sphere(P, T.code[e] >> 1, T.pmf + e, T.mis, nee, x, n, a, beta, dir, c, code);
-    return emit_sample_plane(P, T, e, nee, x, n, a, beta, dir, c, code);
+    if (e < T.spheres) return nee_sample_sphere(P, T.code[e] >> 1, T.pmf + e, T.mis, nee, x, n, a, beta, PB, dir, c, code);
+    return emit_sample_plane(P, T, e, nee, x, n, a, beta, PB, dir, c, code);
 }
 
 // ---- the light tree (select = 1; DESIGN.md §18) ---------------------------------------------------------------------------------------
@@ -272,16 +326,18 @@ __device__ __forceinline__ float tree_pmf(const LightTree &L, int32_t e, f3 x) {
     }
     return p;
 }
-__device__ __forceinline__ bool tree_sample(const KParams &P, const TreeTable &T, uint32_t &nee, f3 x, f3 n, f3 a, f3 beta, f3 &dir, f3 &c, int32_t &code) {
+template <class Pb>
+__device__ __forceinline__ bool tree_sample(const KParams &P, const TreeTable &T, uint32_t &nee, f3 x, f3 n, f3 a, f3 beta, Pb PB, f3 &dir, f3 &c, int32_t &code) {
     float p;
     const int32_t e = tree_pick(T.L, nee, x, p);
-    return nee_sample_sphere(P, T.N.index[e], &p, T.N.mis, nee, x, n, a, beta, dir, c, code);
+    return nee_sample_sphere(P, T.N.index[e], &p, T.N.mis, nee, x, n, a, beta, PB, dir, c, code);
 }
-__device__ __forceinline__ bool tree_sample(const KParams &P, const TreeEmitTable &T, uint32_t &nee, f3 x, f3 n, f3 a, f3 beta, f3 &dir, f3 &c, int32_t &code) {
+template <class Pb>
+__device__ __forceinline__ bool tree_sample(const KParams &P, const TreeEmitTable &T, uint32_t &nee, f3 x, f3 n, f3 a, f3 beta, Pb PB, f3 &dir, f3 &c, int32_t &code) {
     float p;
     const int32_t e = tree_pick(T.L, nee, x, p);
-    if (e < T.N.spheres) return nee_sample_sphere(P, T.N.code[e] >> 1, &p, T.N.mis, nee, x, n, a, beta, dir, c, code);
-    return tree_sample_plane(P, T.N, e, p, nee, x, n, a, beta, dir, c, code);
+    if (e < T.N.spheres) return nee_sample_sphere(P, T.N.code[e] >> 1, &p, T.N.mis, nee, x, n, a, beta, PB, dir, c, code);
+    return tree_sample_plane(P, T.N, e, p, nee, x, n, a, beta, PB, dir, c, code);
 }
 
 }  // namespace rtk

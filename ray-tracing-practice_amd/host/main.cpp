@@ -151,6 +151,31 @@ int main(int argc, char *argv[]) {
             return 99;
         }
     }
+    // extension: `--glossy`, with `--nee`, with `--env` in mode mis or light, or with `--lit`, and only with them: METAL's reflect branch
+    // takes light samples too (rt_nee_params.glossy / rt_env_params.glossy = 1) — the switch of every light that is on.
+    bool glossy_on = false;
+    {
+        bool sampled = lit_on;
+        for (int a = 2; a < argc; ++a) {
+            const std::string arg = argv[a];
+            if (arg == "--glossy") glossy_on = true;
+            if (arg == "--nee") sampled = true;
+        }
+        if (glossy_on && !sampled) {
+            bool env_flag = false, env_path = false;
+            for (int a = 2; a < argc; ++a) {
+                const std::string arg = argv[a];
+                if (arg == "--env") env_flag = true;
+                if (arg == "--env-mode" && a + 1 < argc && std::string(argv[a + 1]) == "path") env_path = true;
+            }
+            sampled = env_flag && !env_path;
+        }
+        if (glossy_on && !sampled) {
+            std::cerr << "rtp_main: --glossy takes light samples at METAL's reflect branch: it needs --nee, --env (mode mis or light) or --lit\n";
+            return 99;
+        }
+        if (glossy_on) lit_nee.glossy = 1;
+    }
     // extension: `--gpu --env FILE[:N] [--env-mode path|mis|light] [--env-scale S] [--env-up y|z]`: every frame through rt_render_env on one
     // GPU, lit by the lat-long image FILE (PFM or Radiance .hdr) resampled into an N x N octahedral map (N defaults to 1024); mis is the
     // default mode, --env-up z turns the map for a z-up scene such as the default configuration; the same saver bytes, --aov /
@@ -195,6 +220,7 @@ int main(int argc, char *argv[]) {
                 }
             }
         }
+        if (glossy_on && ep.mode != 0) ep.glossy = 1;
         if (!env_on)
             for (int a = 2; a < argc; ++a)
                 if (std::string(argv[a]).compare(0, 6, "--env-") == 0) env_bad = std::string(argv[a]) + " needs --env FILE";
@@ -266,6 +292,7 @@ int main(int argc, char *argv[]) {
             nee.select = 1;
             lit_nee.select = 1;
         }
+        if (glossy_on) nee.glossy = 1;
         if (nee_on) {
             if (nee_bad) {
                 std::cerr << "rtp_main: --nee takes mis (default) or light\n";

@@ -196,15 +196,28 @@ class NeeParams(C.Structure):
 
     def __init__(self, *args, **kw):
         super().__init__(*args, **kw)
-        self.struct_bytes = C.sizeof(NeeParams)
+        self.struct_bytes = C.sizeof(type(self))
+
+
+class NeeParamsGlossy(NeeParams):
+    """rt_nee_params as the library compiles it today: NeeParams — the 16-byte struct of a caller from before the glossy switch, which the
+    library reads as glossy = 0 — and the trailing field `glossy` (read when struct_bytes >= 20)."""
+    _fields_ = [("glossy", C.c_int32)]
+    FIELDS = NeeParams.FIELDS + ("glossy",)
 
 
 def nee_params(**params):
-    """rt_nee_params with the library's defaults (mis = 1, sample_planes = 0, select = 0), then the given fields."""
-    p = NeeParams()
-    amd_lib().rt_nee_params_init(C.byref(p))
+    """rt_nee_params with the library's defaults (mis = 1, sample_planes = 0, select = 0, glossy = 0), then the given fields.  Without
+    `glossy` the result is the 16-byte NeeParams (an older caller's struct: glossy = 0); with it, the 20-byte NeeParamsGlossy."""
+    full = NeeParamsGlossy()
+    amd_lib().rt_nee_params_init(C.byref(full))
+    p = full
+    if "glossy" not in params:
+        p = NeeParams()
+        C.memmove(C.byref(p), C.byref(full), C.sizeof(NeeParams))
+        p.struct_bytes = C.sizeof(NeeParams)
     for k, v in params.items():
-        if k not in NeeParams.FIELDS:
+        if k not in type(p).FIELDS:
             raise RtError(f"rt_nee_params has no field {k}")
         setattr(p, k, v)
     return p
@@ -220,8 +233,17 @@ def _nee_struct(params):
 class EnvParams(C.Structure):
     """rt_env_params (include/rtp_amd.h): an IN structure of the caller's size — struct_bytes is set on construction; the other
     fields are 0 until rt_env_params_init (env_params()) fills the defaults."""
+    class _Tail(C.Union):
+        """The struct's last 12 bytes: glossy and the two words still reserved — and, over the same bytes, the three-word `reserved` view
+        of the struct before the switch was taken from it (reserved[0] is glossy: 0 by default)."""
+        class _Words(C.Structure):
+            _fields_ = [("glossy", C.c_int32), ("reserved2", C.c_int32 * 2)]
+        _anonymous_ = ("_words",)
+        _fields_ = [("_words", _Words), ("reserved", C.c_int32 * 3)]
+    _anonymous_ = ("_tail",)
     _fields_ = [("struct_bytes", C.c_uint32), ("mode", C.c_int32), ("scale", C.c_float), ("rot", C.c_float * 9),
-                ("camera_visible", C.c_int32), ("reserved", C.c_int32 * 3)]
+                ("camera_visible", C.c_int32), ("_tail", _Tail)]
+    FIELDS = ("struct_bytes", "mode", "scale", "rot", "camera_visible", "glossy")          # what env_params() sets
 
     def __init__(self, *args, **kw):
         super().__init__(*args, **kw)
@@ -232,12 +254,12 @@ ENV_PATH, ENV_MIS, ENV_LIGHT = 0, 1, 2
 
 
 def env_params(**params):
-    """rt_env_params with the library's defaults (mode = 1, scale = 1, rot = identity, camera_visible = 1), then the given fields
+    """rt_env_params with the library's defaults (mode = 1, scale = 1, rot = identity, camera_visible = 1, glossy = 0), then the given fields
     (rot: nine numbers, the rows of the world → environment rotation)."""
     p = EnvParams()
     amd_lib().rt_env_params_init(C.byref(p))
     for k, v in params.items():
-        if k not in dict(EnvParams._fields_) or k == "reserved":
+        if k not in EnvParams.FIELDS:
             raise RtError(f"rt_env_params has no field {k}")
         if k == "rot":
             v = np.asarray(v, dtype=np.float32).ravel()
@@ -286,7 +308,7 @@ def lit_params(cam_close=None, lens=None, emitters=True, nee=None, env=None, env
         if value is not None:
             value = value if isinstance(value, kind) else make(**value)
             keep.append(value)
-            setattr(p, field, C.pointer(value))
+            setattr(p, field, C.cast(C.pointer(value), C.POINTER(kind)))          # (the field's type: value may be of a subclass)
     if env is not None:
         p.env = env._h
         keep.append(env)
@@ -519,7 +541,7 @@ def amd_lib():
             lib.rt_lens_camera_rays.argtypes = [C.POINTER(CameraData), C.POINTER(CameraData), C.POINTER(LensParams), C.c_int32, C.c_void_p,
                                                 C.c_void_p, C.c_void_p, C.c_void_p]
         if hasattr(lib, "rt_render_nee"):
-            lib.rt_nee_params_init.argtypes = [C.POINTER(NeeParams)]
+            lib.rt_nee_params_init.argtypes = [C.POINTER(NeeParamsGlossy)]
             lib.rt_nee_params_init.restype = None
             lib.rt_render_nee.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(NeeParams), C.POINTER(Shard), C.c_int32, C.c_void_p,
                                           C.c_void_p, C.c_int32, C.POINTER(Timing)]
