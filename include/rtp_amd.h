@@ -615,6 +615,51 @@ rt_status rt_denoise_spp(const float *d_fb_sum, const int32_t *d_spp, const floa
                          const rt_aov_buffers *aov, int32_t aov_samples, int32_t width, int32_t height,
                          const rt_denoise_params *params, void *d_workspace, uint64_t workspace_bytes, float *d_out, void *hip_stream);
 
+/* ---- temporal denoising of adaptively sampled frames: rt_denoise_temporal with per-pixel counts ----------------
+ * rt_denoise_temporal's reprojected history for the whole-frame outputs of rt_render_adaptive[_rule] or rt_render_lit_adaptive[_rule]
+ * (pinhole frames: the reprojection is a pinhole's): d_fb_sum, d_spp and, optionally, d_moments, as rt_denoise_spp takes them.  The
+ * history is blended with the frame by the samples behind each, not by frames, and the variance of the blend is propagated through
+ * it.  aov holds the sums of rt_render_aov[_samples] for the same camera at a uniform aov_samples per pixel; all five buffers are
+ * required, first_prim included.  cam (HOST memory) supplies the image size and the reprojection camera; its samples_per_pixel is
+ * ignored.  The workspace is rt_denoise_workspace_bytes, each history rt_denoise_history_bytes.
+ *
+ * The arithmetic extends the contracts above (same rules: float32 in the order written, nothing fused, correctly rounded division
+ * and sqrtf, exp = expf; rt_denoise_temporal's constants and dot).
+ *   Hit pixels, prepass, sample variance and second prepass: rt_denoise_spp's (n = d_spp[p], inv_p, invA; a HIT pixel has hit_count > 0
+ *     and n >= 1), giving per hit pixel L_cur, d, n, z, gz and var_cur: with d_moments the 3x3 Gaussian of v, without it rt_denoise's
+ *     3x3 spatial variance.  The second prepass always runs, also with iterations = 0.
+ *   Every pixel that is not a hit pixel: out = fb_sum bit for bit, its four history records are zero, and it is never a tap.
+ *   Temporal pass, per hit pixel p = (x, y), with prim = first_prim_p, m1 = lum(L_cur) and nf = (float)n:
+ *     X, reach2, the projection, the four taps in their order and the four conditions of a tap that counts are rt_denoise_temporal's.
+ *       The history is EMPTY when history_prev is NULL or its header is not one this call writes for this width, height and use of
+ *       d_moments (an all-zero buffer and a history of rt_denoise_temporal are empty).  With cnt_q and V_q the fourth floats of tap
+ *       q's position and normal records, the taps that count accumulate, from 0: W += w, S_k += w * Lh_q,k, SM1 += w * M1_q,
+ *       SM2 += w * M2_q, SN += w * len_q, SC += w * cnt_q, SV += w * V_q.
+ *     With W >= min_weight: len = fminf(SN / W + 1, max_len);  ch = SC / W,  s = ch + nf,  a = nf / s,  cnt = s;  when !(a >= min_alpha):
+ *       a = min_alpha and cnt = nf / min_alpha;  b = 1 - a;
+ *       L_k = b * (S_k / W) + a * L_cur,k,  M1 = b * (SM1 / W) + a * m1,  M2 = b * (SM2 / W) + a * (m1 * m1);
+ *       V = (b * b) * (SV / W) + (a * a) * var_cur.
+ *     Otherwise the pixel is disoccluded: L = L_cur, M1 = m1, M2 = m1 * m1, len = 1, cnt = nf, V = var_cur.
+ *     With d_moments: var = V.  Without: var = len >= moments_len ? fmaxf(0, M2 - M1 * M1) : var_cur.
+ *   Iterations: rt_denoise's, on (L, var).  Remodulation, per hit pixel: out_k = (L_k * d_k) * nf  (with iterations = 0: of L).
+ * d_out has an adaptive frame's convention: rt_tonemap_spp(d_out, d_spp, …) takes it.
+ * Identity, bit for bit: with an empty history and iterations >= 1, d_out is rt_denoise_spp's output, with and without d_moments.
+ *
+ * History buffer: rt_denoise_temporal's size, header layout and planes, with uint32 magic 0x32485452, the header's fourth word 1
+ * when written without d_moments and 2 when written with, cnt in the position record's fourth float and V in the normal record's:
+ *   colour (L'_0, L'_1, L'_2, var')   moments (M1, M2, len, prim)   position (X_0, X_1, X_2, cnt)   normal (n_0, n_1, n_2, V)
+ * rt_denoise_temporal takes a history of this call as empty, and this call one of rt_denoise_temporal's or of the other use of
+ * d_moments: alternating the calls on one pair of buffers restarts the history each time.
+ *
+ * Enqueues on hip_stream (NULL = default stream): no allocation, no synchronisation.  All pointers but aov, cam and params are DEVICE
+ * memory.  The checks are rt_denoise_temporal's, in its order and with its codes, with d_spp required, aov_samples outside 1 … 65536
+ * where it checks samples_per_pixel, and d_spp (4 bytes per pixel) and d_moments (8) among the inputs of every overlap check.  Every
+ * check comes before any HIP call. */
+rt_status rt_denoise_temporal_spp(const float *d_fb_sum, const int32_t *d_spp, const float *d_moments /* NULL or 2 floats per pixel */,
+                                  const rt_aov_buffers *aov, int32_t aov_samples, const rt_camera_data *cam,
+                                  const rt_denoise_params *params, const void *d_history_prev, void *d_history_next, uint64_t history_bytes,
+                                  void *d_workspace, uint64_t workspace_bytes, float *d_out, void *hip_stream);
+
 /* ---- thin-lens depth of field and shutter motion blur ---------------------------------------------------------
  * rt_render_samples / rt_render_aov_samples with a camera that has a lens and / or an open shutter.  Pixel (i, j), sample s; the
  * draws come from the same RNG as the pinhole's, and the path goes on from the state they leave:

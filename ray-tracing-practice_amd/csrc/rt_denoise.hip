@@ -27,6 +27,12 @@
 // denoise_prepass_spp normalises with the pixel's count and leaves the variance of its samples in lv.w, denoise_moments_spp replaces
 // the 3x3 spatial variance by the 3x3 Gaussian of that (without moments: denoise_moments as it is), and denoise_step_spp is the last
 // step remodulating with the pixel's count.  The taps (rt_denoise_taps.inc) and the depth gradient are one text, expanded in rt_denoise's kernels and in these.
+//
+// rt_denoise_temporal_spp (the two together) runs rt_denoise_spp's prepasses, then denoise_temporal_spp: denoise_temporal
+// with the history and the frame weighed by the samples behind them and the variance of that blend carried along.  Its history has a
+// magic of its own, the use of moments in the header's fourth word, the accumulated count in position.w and the propagated variance
+// in normal.w.  With one iteration the step is first and last at once: denoise_step_spp_feedback.  The reprojection and the tap loop
+// are one text (rt_denoise_reproject.inc) expanded in denoise_temporal and in denoise_temporal_spp, which hook their sums and blend in.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -290,16 +296,38 @@ __global__ __launch_bounds__(256) void denoise_step_spp(Image im, int32_t s, Sig
     out[3 * p + 2] = (r.z * d.z) * n;
 }
 
+// rt_denoise_temporal_spp's only pass when iterations = 1: denoise_step_spp that also writes its result into the history's colour plane
+__global__ __launch_bounds__(256) void denoise_step_spp_feedback(Image im, int32_t s, Sigmas sg, const float4 *lv_in, const float4 *nz, const float4 *dg,
+                                                                 const float *fb, const int32_t *spp, float *out, float4 *feedback) {
+    int32_t x, y;
+    if (!pixel_of(im, x, y)) return;
+    const int64_t p = (int64_t)y * im.width + x;
+    const float4 np = nz[p];
+    if (is_sky(np)) {
+        copy3(out, fb, p);
+        return;
+    }
+#include "rt_denoise_taps.inc"
+    feedback[p] = r;
+    const float4 d = dg[p];
+    const float n = (float)spp[p];
+    out[3 * p] = (r.x * d.x) * n;
+    out[3 * p + 1] = (r.y * d.y) * n;
+    out[3 * p + 2] = (r.z * d.z) * n;
+}
+
 // ---- the temporal half (rt_denoise_temporal) ------------------------------------------------------------------------------------
 
 constexpr uint32_t kHistMagic = 0x31485452u;          // "RTH1"
+constexpr uint32_t kHistMagicSpp = 0x32485452u;       // "RTH2": rt_denoise_temporal_spp's histories
+constexpr uint32_t kModeSpatial = 1, kModeMoments = 2;   // their fourth word: written without / with d_moments
 constexpr uint64_t kHistHeader = 256, kHistPlanes = 4;
 constexpr float kTau2 = 0.0025f, kMinWeight = 0.01f, kMaxLen = 32.0f, kMinAlpha = 0.2f, kMomentsLen = 4.0f, kMinNormalDot = 0.9f;
 
 struct History {            // the header: written by denoise_temporal's first lane, read by all of them
     uint32_t magic;
     int32_t width, height;
-    uint32_t zero;
+    uint32_t mode;          // 0 (rt_denoise_temporal), kModeSpatial or kModeMoments (rt_denoise_temporal_spp)
     rt_camera_data cam;     // the camera the history was made with
     uint32_t zeros[(kHistHeader - 16 - sizeof(rt_camera_data)) / 4];
 };
@@ -345,76 +373,19 @@ __global__ __launch_bounds__(256) void denoise_temporal(Image im, rt_camera_data
     const int32_t prim = first_prim[p];
     const float Lc[3] = {cur.x, cur.y, cur.z};
     const float m1 = lum(cur.x, cur.y, cur.z);
-    // the mean first-hit point along the pixel-centre ray
-    const float O[3] = {cam.origin.e[0], cam.origin.e[1], cam.origin.e[2]};
-    float X[3], OX[3];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float pc = (cam.pixel00_loc.e[k] + (float)x * cam.pixel_delta_u.e[k]) + (float)y * cam.pixel_delta_v.e[k];
-        X[k] = O[k] + np.w * (pc - O[k]);
-        OX[k] = X[k] - O[k];
-    }
-    const float reach2 = kTau2 * dot3(OX, OX);
-    float L[3] = {Lc[0], Lc[1], Lc[2]}, M1 = m1, M2 = m1 * m1, len = 1.0f;
-    if (prev && prev->magic == kHistMagic && prev->width == im.width && prev->height == im.height) {
-        // projection through the old viewport plane (normal du' x dv'), pixel units with integers at pixel centres
-        const rt_camera_data &c = prev->cam;
-        const float du[3] = {c.pixel_delta_u.e[0], c.pixel_delta_u.e[1], c.pixel_delta_u.e[2]};
-        const float dv[3] = {c.pixel_delta_v.e[0], c.pixel_delta_v.e[1], c.pixel_delta_v.e[2]};
-        const float N[3] = {du[1] * dv[2] - du[2] * dv[1], du[2] * dv[0] - du[0] * dv[2], du[0] * dv[1] - du[1] * dv[0]};
-        float E[3], D[3];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            E[k] = c.pixel00_loc.e[k] - c.origin.e[k];
-            D[k] = X[k] - c.origin.e[k];
-        }
-        const float t = dot3(E, N) / dot3(D, N);
-        if (t > 0.0f && t < __builtin_inff()) {
-            float R[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) R[k] = t * D[k] - E[k];
-            const float u = dot3(R, du) / dot3(du, du), v = dot3(R, dv) / dot3(dv, dv);
-            if (u > -1.0f && u < (float)im.width && v > -1.0f && v < (float)im.height) {
-                const float fu = floorf(u), fv = floorf(v);
-                const int32_t x0 = (int32_t)fu, y0 = (int32_t)fv;
-                const float fx = u - fu, fy = v - fv;
-                const float4 *h_colour = plane((void *)prev, pixels, 0), *h_moments = plane((void *)prev, pixels, 1);
-                const float4 *h_pos = plane((void *)prev, pixels, 2), *h_normal = plane((void *)prev, pixels, 3);
-                float W = 0.0f, S0 = 0.0f, S1 = 0.0f, S2 = 0.0f, SM1 = 0.0f, SM2 = 0.0f, SN = 0.0f;
-#pragma unroll
-                for (int tap = 0; tap < 4; ++tap) {
-                    const int32_t qx = x0 + (tap & 1), qy = y0 + (tap >> 1);
-                    if (qx < 0 || qx >= im.width || qy < 0 || qy >= im.height) continue;
-                    const int64_t q = (int64_t)qy * im.width + qx;
-                    const float4 mq = h_moments[q];
-                    if (!(mq.z > 0.0f) || __float_as_int(mq.w) != prim) continue;
-                    const float4 nq = h_normal[q];
-                    if (!((np.x * nq.x + np.y * nq.y) + np.z * nq.z >= kMinNormalDot)) continue;
-                    const float4 xq = h_pos[q];
-                    const float e[3] = {xq.x - X[0], xq.y - X[1], xq.z - X[2]};
-                    if (!(dot3(e, e) <= reach2)) continue;
-                    const float w = ((tap & 1) ? fx : 1.0f - fx) * ((tap >> 1) ? fy : 1.0f - fy);
-                    const float4 cq = h_colour[q];
-                    W += w;
-                    S0 += w * cq.x;
-                    S1 += w * cq.y;
-                    S2 += w * cq.z;
-                    SM1 += w * mq.x;
-                    SM2 += w * mq.y;
-                    SN += w * mq.z;
-                }
-                if (W >= kMinWeight) {
-                    len = fminf(SN / W + 1.0f, kMaxLen);
-                    const float a = fmaxf(kMinAlpha, 1.0f / len), b = 1.0f - a;
-                    L[0] = b * (S0 / W) + a * Lc[0];
-                    L[1] = b * (S1 / W) + a * Lc[1];
-                    L[2] = b * (S2 / W) + a * Lc[2];
-                    M1 = b * (SM1 / W) + a * m1;
-                    M2 = b * (SM2 / W) + a * (m1 * m1);
-                }
-            }
-        }
-    }
+#define RTP_REPROJECT_STATE float L[3] = {Lc[0], Lc[1], Lc[2]}, M1 = m1, M2 = m1 * m1, len = 1.0f;
+#define RTP_REPROJECT_HISTORY_OK prev && prev->magic == kHistMagic && prev->width == im.width && prev->height == im.height
+#define RTP_REPROJECT_SUMS
+#define RTP_REPROJECT_TAP
+#define RTP_REPROJECT_ALPHA const float a = fmaxf(kMinAlpha, 1.0f / len), b = 1.0f - a;
+#define RTP_REPROJECT_VARIANCE
+#include "rt_denoise_reproject.inc"
+#undef RTP_REPROJECT_STATE
+#undef RTP_REPROJECT_HISTORY_OK
+#undef RTP_REPROJECT_SUMS
+#undef RTP_REPROJECT_TAP
+#undef RTP_REPROJECT_ALPHA
+#undef RTP_REPROJECT_VARIANCE
     const float var = len >= kMomentsLen ? fmaxf(0.0f, M2 - M1 * M1) : cur.w;
     const float4 r = make_float4(L[0], L[1], L[2], var);
     lv[p] = r;
@@ -427,6 +398,79 @@ __global__ __launch_bounds__(256) void denoise_temporal(Image im, rt_camera_data
         out[3 * p] = (L[0] * d.x) * spp;
         out[3 * p + 1] = (L[1] * d.y) * spp;
         out[3 * p + 2] = (L[2] * d.z) * spp;
+    }
+}
+
+// rt_denoise_temporal_spp's temporal pass: denoise_temporal's reprojection (rt_denoise_reproject.inc, expanded in both) with the
+// blend weighed by sample counts (n = spp[p] against the count the history carries in position.w), the variance of that blend
+// propagated (normal.w) and steering the iterations when the frames come with moments (mode 2; mode 1: the accumulated moments as in
+// denoise_temporal), and the pixel's count in the remodulation.
+__global__ __launch_bounds__(256) void denoise_temporal_spp(Image im, rt_camera_data cam, const int32_t *first_prim, const int32_t *spp, uint32_t mode,
+                                                            const History *prev, History *next, float4 *lv, const float4 *nz, const float4 *dg,
+                                                            const float *fb, float *out) {
+    const uint64_t pixels = (uint64_t)im.width * (uint64_t)im.height;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        History h;
+        memset(&h, 0, sizeof(h));
+        h.magic = kHistMagicSpp;
+        h.width = im.width;
+        h.height = im.height;
+        h.mode = mode;
+        h.cam = cam;
+        *next = h;
+    }
+    int32_t x, y;
+    if (!pixel_of(im, x, y)) return;
+    const int64_t p = (int64_t)y * im.width + x;
+    float4 *const colour = plane(next, pixels, 0);
+    const float4 np = nz[p];
+    if (is_sky(np)) {
+        const float4 zero = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        colour[p] = zero;
+        plane(next, pixels, 1)[p] = zero;
+        plane(next, pixels, 2)[p] = zero;
+        plane(next, pixels, 3)[p] = zero;
+        if (out) copy3(out, fb, p);
+        return;
+    }
+    const float4 cur = lv[p];
+    const int32_t prim = first_prim[p];
+    const float nf = (float)spp[p];
+    const float Lc[3] = {cur.x, cur.y, cur.z};
+    const float m1 = lum(cur.x, cur.y, cur.z);
+#define RTP_REPROJECT_STATE float L[3] = {Lc[0], Lc[1], Lc[2]}, M1 = m1, M2 = m1 * m1, len = 1.0f, cnt = nf, V = cur.w;
+#define RTP_REPROJECT_HISTORY_OK prev && prev->magic == kHistMagicSpp && prev->width == im.width && prev->height == im.height && prev->mode == mode
+#define RTP_REPROJECT_SUMS float SC = 0.0f, SV = 0.0f;
+#define RTP_REPROJECT_TAP SC += w * xq.w, SV += w * nq.w;
+#define RTP_REPROJECT_ALPHA                       \
+    const float ch = SC / W, s = ch + nf;         \
+    float a = nf / s;                             \
+    cnt = s;                                      \
+    if (!(a >= kMinAlpha)) {                      \
+        a = kMinAlpha;                            \
+        cnt = nf / kMinAlpha;                     \
+    }                                             \
+    const float b = 1.0f - a;
+#define RTP_REPROJECT_VARIANCE V = (b * b) * (SV / W) + (a * a) * cur.w;
+#include "rt_denoise_reproject.inc"
+#undef RTP_REPROJECT_STATE
+#undef RTP_REPROJECT_HISTORY_OK
+#undef RTP_REPROJECT_SUMS
+#undef RTP_REPROJECT_TAP
+#undef RTP_REPROJECT_ALPHA
+#undef RTP_REPROJECT_VARIANCE
+    const float var = mode == kModeMoments ? V : (len >= kMomentsLen ? fmaxf(0.0f, M2 - M1 * M1) : cur.w);
+    const float4 r = make_float4(L[0], L[1], L[2], var);
+    lv[p] = r;
+    plane(next, pixels, 1)[p] = make_float4(M1, M2, len, __int_as_float(prim));
+    plane(next, pixels, 2)[p] = make_float4(X[0], X[1], X[2], cnt);
+    plane(next, pixels, 3)[p] = make_float4(np.x, np.y, np.z, V);
+    if (out) {
+        colour[p] = r;
+        const float4 d = dg[p];
+        out[3 * p] = (L[0] * d.x) * nf;
+        out[3 * p + 1] = (L[1] * d.y) * nf;
+        out[3 * p + 2] = (L[2] * d.z) * nf;
     }
 }
 
@@ -484,7 +528,7 @@ rt_status launched(const char *what) {
 }
 
 // The iterations: lv[1] → lv[0] → lv[1] …, the last one remodulating into out; feedback != nullptr: iteration 0 also writes it;
-// d_spp != nullptr (rt_denoise_spp; no feedback then): the last one remodulates with each pixel's own count instead of spp
+// d_spp != nullptr (rt_denoise_spp, rt_denoise_temporal_spp): the last one remodulates with each pixel's own count instead of spp
 rt_status enqueue_steps(const Launch &l, const rt_denoise_params &prm, const float *fb, float spp, float *out, float4 *feedback, hipStream_t stream,
                         const int32_t *d_spp = nullptr) {
     const Sigmas sg = {prm.sigma_depth, prm.sigma_luminance, prm.normal_squarings};
@@ -492,7 +536,9 @@ rt_status enqueue_steps(const Launch &l, const rt_denoise_params &prm, const flo
         const float4 *src = l.lv[(i + 1) & 1];
         float4 *dst = l.lv[i & 1];
         const bool last = i + 1 == prm.iterations;
-        if (i == 0 && feedback) {
+        if (i == 0 && feedback && last && d_spp) {
+            hipLaunchKernelGGL(denoise_step_spp_feedback, l.grid, l.block, 0, stream, l.im, 1 << i, sg, src, l.nz, l.dg, fb, d_spp, out, feedback);
+        } else if (i == 0 && feedback) {
             if (!last) hipLaunchKernelGGL((denoise_step<false, true>), l.grid, l.block, 0, stream, l.im, 1 << i, sg, src, l.nz, l.dg, dst, fb, spp, out, feedback);
             else hipLaunchKernelGGL((denoise_step<true, true>), l.grid, l.block, 0, stream, l.im, 1 << i, sg, src, l.nz, l.dg, dst, fb, spp, out, feedback);
         } else if (last && d_spp) {
@@ -679,6 +725,67 @@ rt_status rt_denoise_temporal(const float *d_fb_sum, const rt_aov_buffers *aov, 
                        (rtdn::History *)d_history_next, l.lv[1], l.nz, l.dg, d_fb_sum, spp, prm.iterations == 0 ? d_out : nullptr);
     if ((st = launched("denoise_temporal")) != RT_OK || prm.iterations == 0) return st;
     return rtdn::enqueue_steps(l, prm, d_fb_sum, spp, d_out, rtdn::plane(d_history_next, pixels, 0), stream);
+}
+
+rt_status rt_denoise_temporal_spp(const float *d_fb_sum, const int32_t *d_spp, const float *d_moments, const rt_aov_buffers *aov, int32_t aov_samples,
+                                  const rt_camera_data *cam, const rt_denoise_params *params, const void *d_history_prev, void *d_history_next,
+                                  uint64_t history_bytes, void *d_workspace, uint64_t workspace_bytes, float *d_out, void *hip_stream) {
+    using rtdn::fail;
+    using rtdn::overlap;
+    if (!d_fb_sum || !d_spp || !aov || !cam || !d_history_next || !d_workspace || !d_out) return fail(RT_ERR_INVALID_ARG, "rt_denoise_temporal_spp: null argument");
+    rt_aov_buffers b;
+    rt_aov_buffers_init(&b);
+    const uint32_t ab = aov->struct_bytes < sizeof(b) ? aov->struct_bytes : (uint32_t)sizeof(b);
+    memcpy(&b, aov, ab);
+    if (ab < offsetof(rt_aov_buffers, first_prim) + sizeof(b.first_prim) || !b.albedo_sum || !b.normal_sum || !b.depth_sum || !b.hit_count ||
+        !b.first_prim)
+        return fail(RT_ERR_INVALID_ARG, "rt_denoise_temporal_spp: albedo_sum, normal_sum, depth_sum, hit_count and first_prim are required");
+    const int32_t width = cam->image_width, height = cam->image_height;
+    if (width < 1 || height < 1) return fail(RT_ERR_INVALID_ARG, "rt_denoise_temporal_spp: image width and height must be at least 1");
+    if (aov_samples < 1 || aov_samples > 65536) return fail(RT_ERR_INVALID_ARG, "rt_denoise_temporal_spp: aov_samples outside 1 … 65536");
+    rt_denoise_params prm;
+    rt_status st = rtdn::read_params("rt_denoise_temporal_spp", params, prm);
+    if (st != RT_OK) return st;
+    const uint64_t pixels = (uint64_t)width * (uint64_t)height;
+    if (pixels > (1ull << 24)) return fail(RT_ERR_UNSUPPORTED, "rt_denoise_temporal_spp: more than 2^24 pixels");
+    const uint64_t need = rt_denoise_workspace_bytes(width, height), hist = rt_denoise_history_bytes(width, height);
+    if (workspace_bytes < need)
+        return fail(RT_ERR_INVALID_ARG, "rt_denoise_temporal_spp: workspace_bytes below rt_denoise_workspace_bytes (" + std::to_string(need) + ")");
+    if (history_bytes < hist)
+        return fail(RT_ERR_INVALID_ARG, "rt_denoise_temporal_spp: history_bytes below rt_denoise_history_bytes (" + std::to_string(hist) + ")");
+    if (((uintptr_t)d_history_prev | (uintptr_t)d_history_next) & 15u)
+        return fail(RT_ERR_INVALID_ARG, "rt_denoise_temporal_spp: a history buffer is not 16-byte aligned");
+    const struct { const void *ptr; uint64_t bytes; } inputs[] = {{d_fb_sum, 12 * pixels}, {d_spp, 4 * pixels}, {d_moments, d_moments ? 8 * pixels : 0}, {b.albedo_sum, 12 * pixels}, {b.normal_sum, 12 * pixels},
+                                                                   {b.depth_sum, 4 * pixels}, {b.hit_count, 4 * pixels}, {b.first_prim, 4 * pixels}};
+    const uint64_t prev_bytes = d_history_prev ? hist : 0;
+    for (const auto &in : inputs) {
+        if (overlap(d_history_next, hist, in.ptr, in.bytes)) return fail(RT_ERR_INVALID_ARG, "rt_denoise_temporal_spp: history_next overlaps an input");
+        if (overlap(d_out, 12 * pixels, in.ptr, in.bytes)) return fail(RT_ERR_INVALID_ARG, "rt_denoise_temporal_spp: d_out overlaps an input");
+        if (overlap(d_workspace, need, in.ptr, in.bytes)) return fail(RT_ERR_INVALID_ARG, "rt_denoise_temporal_spp: the workspace overlaps an input");
+    }
+    if (overlap(d_history_next, hist, d_history_prev, prev_bytes)) return fail(RT_ERR_INVALID_ARG, "rt_denoise_temporal_spp: history_next overlaps history_prev");
+    if (overlap(d_history_next, hist, d_workspace, need)) return fail(RT_ERR_INVALID_ARG, "rt_denoise_temporal_spp: history_next overlaps the workspace");
+    if (overlap(d_history_next, hist, d_out, 12 * pixels)) return fail(RT_ERR_INVALID_ARG, "rt_denoise_temporal_spp: history_next overlaps d_out");
+    if (overlap(d_out, 12 * pixels, d_workspace, need)) return fail(RT_ERR_INVALID_ARG, "rt_denoise_temporal_spp: d_out overlaps the workspace");
+    if (overlap(d_out, 12 * pixels, d_history_prev, prev_bytes)) return fail(RT_ERR_INVALID_ARG, "rt_denoise_temporal_spp: d_out overlaps history_prev");
+    if (overlap(d_workspace, need, d_history_prev, prev_bytes)) return fail(RT_ERR_INVALID_ARG, "rt_denoise_temporal_spp: the workspace overlaps history_prev");
+
+    // ---- enqueue: rt_denoise_spp's prepasses · temporal · the iterations, the first feeding the history, the last with the counts ----
+    const hipStream_t stream = (hipStream_t)hip_stream;
+    const rtdn::Launch l(width, height, d_workspace);
+    const rtdn::Inputs in = {d_fb_sum, b.albedo_sum, b.normal_sum, b.depth_sum, b.hit_count};
+    const float inv_aov = (float)(1.0 / (double)aov_samples);
+    using rtdn::launched;
+    hipLaunchKernelGGL(rtdn::denoise_prepass_spp, l.grid, l.block, 0, stream, l.im, in, d_spp, d_moments, inv_aov, l.lv[0], l.nz, l.dg, nullptr);
+    if ((st = launched("denoise_prepass_spp")) != RT_OK) return st;
+    if (d_moments) hipLaunchKernelGGL(rtdn::denoise_moments_spp, l.grid, l.block, 0, stream, l.im, l.lv[0], l.nz, l.dg, l.lv[1]);
+    else hipLaunchKernelGGL(rtdn::denoise_moments, l.grid, l.block, 0, stream, l.im, l.lv[0], l.nz, l.dg, l.lv[1]);
+    if ((st = launched("denoise_moments")) != RT_OK) return st;
+    hipLaunchKernelGGL(rtdn::denoise_temporal_spp, l.grid, l.block, 0, stream, l.im, *cam, (const int32_t *)b.first_prim, d_spp,
+                       d_moments ? rtdn::kModeMoments : rtdn::kModeSpatial, (const rtdn::History *)d_history_prev, (rtdn::History *)d_history_next, l.lv[1],
+                       l.nz, l.dg, d_fb_sum, prm.iterations == 0 ? d_out : nullptr);
+    if ((st = launched("denoise_temporal_spp")) != RT_OK || prm.iterations == 0) return st;
+    return rtdn::enqueue_steps(l, prm, d_fb_sum, 0.0f, d_out, rtdn::plane(d_history_next, pixels, 0), stream, d_spp);
 }
 
 }  // extern "C"

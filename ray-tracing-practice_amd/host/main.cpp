@@ -41,6 +41,33 @@ int main(int argc, char *argv[]) {
         if (std::string(argv[a]) == "--denoise") denoise = true;
         if (std::string(argv[a]) == "--denoise-temporal") temporal = true;
     }
+    // extension: `--denoise-adaptive-temporal`, with `--adaptive T` or with `--lit … --noise-target T` (pinhole frames only: the
+    // reprojection assumes one): --denoise-adaptive with the history carried from frame to frame — rt_denoise_temporal_spp with each
+    // frame's counts and moments and AOVs (first_prim included) at min_spp, through rt_tonemap_spp to "<frame file>.denoised".  Not
+    // with --denoise, --denoise-temporal, --denoise-adaptive, --aov, --lens, --motion-blur, --devices, --shard or RTP_DEVICES: this
+    // block comes before those flags' own, so that whatever else is given the refusal names this flag.
+    bool denoise_adaptive_temporal = false;
+    {
+        bool adaptive_on = false, lit_flag = false, target_flag = false, others = getenv("RTP_DEVICES") != nullptr;
+        for (int a = 2; a < argc; ++a) {
+            const std::string arg = argv[a];
+            if (arg == "--denoise-adaptive-temporal") denoise_adaptive_temporal = true;
+            if (arg == "--adaptive") adaptive_on = true;
+            if (arg == "--lit") lit_flag = true;
+            if (arg == "--noise-target") target_flag = true;
+            if (arg == "--denoise-adaptive" || arg == "--lens" || arg == "--motion-blur" || arg == "--devices" || arg == "--shard") others = true;
+        }
+        if (denoise_adaptive_temporal && (denoise || temporal || aov || others)) {
+            std::cerr << "rtp_main: --denoise-adaptive-temporal writes <frame>.denoised from pinhole frames and AOVs of its own on one GPU: it cannot "
+                         "be combined with --denoise, --denoise-temporal, --denoise-adaptive, --aov, --lens, --motion-blur, --devices, --shard or "
+                         "RTP_DEVICES\n";
+            return 2;
+        }
+        if (denoise_adaptive_temporal && !adaptive_on && !(lit_flag && target_flag)) {
+            std::cerr << "rtp_main: --denoise-adaptive-temporal filters adaptively sampled frames: it needs --adaptive T or --lit --noise-target T\n";
+            return 2;
+        }
+    }
     // extension: `--denoise-adaptive`, with `--adaptive T` or with `--lit … --noise-target T` and only with them: each adaptively sampled
     // frame is also filtered by rt_denoise_spp — its own counts and moments, AOVs rendered at min_spp (rt_render_aov; on the lit path
     // rt_render_aov_lens with the frame's lens and shutter) — and written through rt_tonemap_spp to "<frame file>.denoised".  Not with
@@ -359,7 +386,7 @@ int main(int argc, char *argv[]) {
                 lit.env = lit_env;
                 lit.env_params = &lit_ep;
                 rtp::gpu_render_lens(params, desc, lens, shutter, aov, denoise, nullptr, nullptr, nullptr, &lit, noise_on ? &noise : nullptr,
-                                     denoise_adaptive, &stop_rule);
+                                     denoise_adaptive, &stop_rule, denoise_adaptive_temporal);
                 rt_env_destroy(lit_env);
                 return 0;
             }
@@ -409,7 +436,7 @@ int main(int argc, char *argv[]) {
                     std::cerr << "rtp_main: --adaptive cannot be combined with --shard\n";
                     return 2;
                 }
-            rtp::gpu_render_adaptive(params, desc, ap, denoise_adaptive, &stop_rule);
+            rtp::gpu_render_adaptive(params, desc, ap, denoise_adaptive, &stop_rule, denoise_adaptive_temporal);
             return 0;
         }
     // extension: `--gpu --shard N` splits EVERY frame over N GPUs (0 = all of the node) with one RCCL gather per frame

@@ -197,7 +197,9 @@ void write_binary_frame(const PendingFile &f) {
 }
 
 // rtp_main --denoise-adaptive: what both adaptive drivers keep for it — the frame's moments, AOVs at min_spp, rt_denoise's workspace
-// and the filtered frame — and the step after a frame's AOVs are rendered: rt_denoise_spp, rt_tonemap_spp, "<frame file>.denoised"
+// and the filtered frame — and the step after a frame's AOVs are rendered: rt_denoise_spp, rt_tonemap_spp, "<frame file>.denoised".
+// temporal (rtp_main --denoise-adaptive-temporal): first_prim as well and two history buffers swapped after every
+// frame, and the step is rt_denoise_temporal_spp with the frame's camera
 struct AdaptiveDenoiser {
     int width = 0, height = 0;
     size_t num_pixels = 0;
@@ -205,8 +207,12 @@ struct AdaptiveDenoiser {
     void *d_workspace = nullptr;
     uint64_t workspace_bytes = 0;
     rt_aov_buffers aov;
+    bool temporal = false;
+    void *d_history[2] = {nullptr, nullptr};
+    uint64_t history_bytes = 0;
+    int frames = 0;
 
-    AdaptiveDenoiser(int w, int h) : width(w), height(h), num_pixels(static_cast<size_t>(w) * h) {
+    AdaptiveDenoiser(int w, int h, bool temporal_ = false) : width(w), height(h), num_pixels(static_cast<size_t>(w) * h), temporal(temporal_) {
         rt_aov_buffers_init(&aov);
         workspace_bytes = rt_denoise_workspace_bytes(w, h);
         RTP_CHECK(rt_device_alloc(num_pixels * 8, reinterpret_cast<void **>(&d_moments)));
@@ -216,8 +222,17 @@ struct AdaptiveDenoiser {
         RTP_CHECK(rt_device_alloc(num_pixels * 12, reinterpret_cast<void **>(&aov.normal_sum)));
         RTP_CHECK(rt_device_alloc(num_pixels * 4, reinterpret_cast<void **>(&aov.depth_sum)));
         RTP_CHECK(rt_device_alloc(num_pixels * 4, reinterpret_cast<void **>(&aov.hit_count)));
+        if (temporal) {
+            history_bytes = rt_denoise_history_bytes(w, h);
+            RTP_CHECK(rt_device_alloc(num_pixels * 4, reinterpret_cast<void **>(&aov.first_prim)));
+            RTP_CHECK(rt_device_alloc(history_bytes, &d_history[0]));
+            RTP_CHECK(rt_device_alloc(history_bytes, &d_history[1]));
+        }
     }
     ~AdaptiveDenoiser() {
+        rt_device_free(aov.first_prim);
+        rt_device_free(d_history[0]);
+        rt_device_free(d_history[1]);
         rt_device_free(d_moments);
         rt_device_free(d_denoised);
         rt_device_free(d_workspace);
@@ -230,8 +245,15 @@ struct AdaptiveDenoiser {
     AdaptiveDenoiser &operator=(const AdaptiveDenoiser &) = delete;
 
     // d_rgb: the frame's own byte buffer, free again once the frame's file is written
-    void write(const std::string &filename, const float *d_fb, const int32_t *d_spp, int32_t aov_samples, uint8_t *d_rgb) {
-        RTP_CHECK(rt_denoise_spp(d_fb, d_spp, d_moments, &aov, aov_samples, width, height, nullptr, d_workspace, workspace_bytes, d_denoised, nullptr));
+    // cam: the frame's camera (the temporal filter's reprojection; unused without it)
+    void write(const std::string &filename, const float *d_fb, const int32_t *d_spp, int32_t aov_samples, uint8_t *d_rgb, const rt_camera_data &cam) {
+        if (temporal) {
+            RTP_CHECK(rt_denoise_temporal_spp(d_fb, d_spp, d_moments, &aov, aov_samples, &cam, nullptr, frames == 0 ? nullptr : d_history[(frames + 1) & 1],
+                                              d_history[frames & 1], history_bytes, d_workspace, workspace_bytes, d_denoised, nullptr));
+            ++frames;
+        } else {
+            RTP_CHECK(rt_denoise_spp(d_fb, d_spp, d_moments, &aov, aov_samples, width, height, nullptr, d_workspace, workspace_bytes, d_denoised, nullptr));
+        }
         RTP_CHECK(rt_tonemap_spp(d_denoised, d_spp, d_rgb, static_cast<int64_t>(num_pixels), nullptr));
         PendingFile file;
         file.path = filename + ".denoised";
@@ -310,7 +332,7 @@ void gpu_render_pipelined(const SceneParams &params, const rt_scene_desc &desc, 
 // denoise_adaptive (with noise; rtp_main --denoise-adaptive): as in gpu_render_adaptive, the AOVs from rt_render_aov_lens at noise->min_spp
 void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const rt_lens_params &lens, float shutter, bool aov, bool denoise,
                      const rt_nee_params *nee, const rt_env *env, const rt_env_params *env_params, const rt_lit_params *lit,
-                     const rt_adaptive_params *noise, bool denoise_adaptive, const rt_stop_params *stop) {
+                     const rt_adaptive_params *noise, bool denoise_adaptive, const rt_stop_params *stop, bool denoise_adaptive_temporal) {
     rt_scene *scene = nullptr;
     RTP_CHECK(rt_scene_create(&desc, &scene));
     const size_t num_pixels = static_cast<size_t>(params.width) * params.height;
@@ -327,7 +349,8 @@ void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const
         h_spp.resize(num_pixels);
     }
     std::unique_ptr<AdaptiveDenoiser> spp_denoiser;
-    if (lit && noise && denoise_adaptive) spp_denoiser = std::make_unique<AdaptiveDenoiser>(params.width, params.height);
+    if (lit && noise && (denoise_adaptive || denoise_adaptive_temporal))
+        spp_denoiser = std::make_unique<AdaptiveDenoiser>(params.width, params.height, denoise_adaptive_temporal);
     rt_aov_buffers aov_bufs;
     rt_aov_buffers_init(&aov_bufs);
     std::vector<float> h_albedo, h_normal, h_depth, h_denoised;
@@ -395,8 +418,9 @@ void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const
         if (spp_denoiser) {          // (outside the frame's timed span) the first hits of this lens and shutter at min_spp samples
             rt_camera_data aov_open = cam, aov_close = close;
             aov_open.samples_per_pixel = aov_close.samples_per_pixel = noise->min_spp;
-            RTP_CHECK(rt_render_aov_lens(scene, &aov_open, cam_close ? &aov_close : nullptr, &lens, nullptr, 0, &spp_denoiser->aov, nullptr, 1, nullptr));
-            spp_denoiser->write(filename, d_fb, d_spp, noise->min_spp, d_rgb);
+            if (spp_denoiser->temporal) RTP_CHECK(rt_render_aov(scene, &aov_open, nullptr, &spp_denoiser->aov, nullptr, 1, nullptr));       // (a pinhole, no shutter)
+            else RTP_CHECK(rt_render_aov_lens(scene, &aov_open, cam_close ? &aov_close : nullptr, &lens, nullptr, 0, &spp_denoiser->aov, nullptr, 1, nullptr));
+            spp_denoiser->write(filename, d_fb, d_spp, noise->min_spp, d_rgb, cam);
         }
         if (aov || denoise) {          // (outside the frame's timed span, as in gpu_render)
             if (!lit && (nee || env)) RTP_CHECK(rt_render_aov_samples(scene, &cam, nullptr, 0, &aov_bufs, nullptr, 1, nullptr));
@@ -439,9 +463,10 @@ void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const
 // The orbit of gpu_render, each frame rendered by rt_render_adaptive and saved through rt_tonemap_spp: every pixel's bytes are the
 // saver arithmetic with its own sample count as the divisor (the mean of its samples).  Prints frame, milliseconds and the samples
 // the frame took.  denoise_adaptive (rtp_main --denoise-adaptive): the frame's moments are kept, its AOVs rendered at
-// min_spp, and rt_denoise_spp's output goes through rt_tonemap_spp to "<frame file>.denoised".
+// min_spp, and rt_denoise_spp's output goes through rt_tonemap_spp to "<frame file>.denoised".  denoise_adaptive_temporal (rtp_main
+// --denoise-adaptive-temporal): the same with rt_denoise_temporal_spp and its history from the frame before.
 void gpu_render_adaptive(const SceneParams &params, const rt_scene_desc &desc, const rt_adaptive_params &ap, bool denoise_adaptive,
-                         const rt_stop_params *stop) {
+                         const rt_stop_params *stop, bool denoise_adaptive_temporal) {
     rt_scene *scene = nullptr;
     RTP_CHECK(rt_scene_create(&desc, &scene));
     const size_t num_pixels = static_cast<size_t>(params.width) * params.height;
@@ -453,7 +478,8 @@ void gpu_render_adaptive(const SceneParams &params, const rt_scene_desc &desc, c
     RTP_CHECK(rt_device_alloc(num_pixels * 3, reinterpret_cast<void **>(&d_rgb)));
     std::vector<int32_t> spp(num_pixels);
     std::unique_ptr<AdaptiveDenoiser> spp_denoiser;
-    if (denoise_adaptive) spp_denoiser = std::make_unique<AdaptiveDenoiser>(params.width, params.height);
+    if (denoise_adaptive || denoise_adaptive_temporal)
+        spp_denoiser = std::make_unique<AdaptiveDenoiser>(params.width, params.height, denoise_adaptive_temporal);
     for (int n = 0; n < params.num_frames; ++n) {
         Vec3 eye, target;
         orbit_pose(params, n, eye, target);
@@ -480,7 +506,7 @@ void gpu_render_adaptive(const SceneParams &params, const rt_scene_desc &desc, c
         std::cout << n << "\t" << ms << "\t" << samples << "\n";
         if (spp_denoiser) {          // (outside the frame's timed span) cam carries min_spp: the AOVs of the frame's first samples
             RTP_CHECK(rt_render_aov(scene, &cam, nullptr, &spp_denoiser->aov, nullptr, 1, nullptr));
-            spp_denoiser->write(file.path, d_fb, d_spp, ap.min_spp, d_rgb);
+            spp_denoiser->write(file.path, d_fb, d_spp, ap.min_spp, d_rgb, cam);
         }
     }
     spp_denoiser.reset();

@@ -437,6 +437,7 @@ RTP_AMD_SYMBOLS = [
     "rt_render_lit_adaptive",
     "rt_denoise_spp",
     "rt_stop_params_init", "rt_render_adaptive_rule", "rt_render_lit_adaptive_rule", "rt_adaptive_judge",
+    "rt_denoise_temporal_spp",
 ]
 
 _host = None
@@ -590,6 +591,10 @@ def amd_lib():
         if hasattr(lib, "rt_denoise_spp"):
             lib.rt_denoise_spp.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(AovBuffers), C.c_int32, C.c_int32, C.c_int32,
                                            C.POINTER(DenoiseParams), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        if hasattr(lib, "rt_denoise_temporal_spp"):
+            lib.rt_denoise_temporal_spp.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(AovBuffers), C.c_int32, C.POINTER(CameraData),
+                                                    C.POINTER(DenoiseParams), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                                    C.c_void_p, C.c_void_p]
         lib.rt_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         lib.rt_last_timing.argtypes = [C.c_void_p, C.POINTER(Timing)]
         lib.rt_timing_init.argtypes = [C.POINTER(Timing)]
@@ -803,6 +808,21 @@ def denoise_temporal(d_fb, aov_ptrs, cam, d_history_prev, d_history_next, histor
                                          C.c_void_p(stream or 0)), "rt_denoise_temporal")
 
 
+def denoise_temporal_spp(d_fb, d_spp, d_moments, aov_ptrs, aov_spp, cam, d_history_prev, d_history_next, history_bytes, d_out, workspace,
+                         stream=None, **params):
+    """rt_denoise_temporal_spp on device addresses: d_fb, d_spp and d_moments (or None) as DeviceScene.render_adaptive /
+    render_lit_adaptive wrote them for a whole frame of cam, aov_ptrs {"albedo", "normal", "depth", "hits", "prim"} → device address
+    of the AOV sums at aov_spp samples per pixel, d_history_prev (None: no history) and d_history_next (history_bytes each), d_out
+    (3 floats per pixel), workspace = (address, bytes) of at least rt_denoise_workspace_bytes.  Only enqueues on `stream` (None =
+    default stream).  params: rt_denoise_params fields."""
+    b = _aov_struct(aov_ptrs)
+    p = denoise_params(**params)
+    ws_ptr, ws_bytes = workspace
+    _check(amd_lib().rt_denoise_temporal_spp(C.c_void_p(d_fb), C.c_void_p(d_spp), C.c_void_p(d_moments or 0), C.byref(b), aov_spp, C.byref(cam),
+                                             C.byref(p), C.c_void_p(d_history_prev or 0), C.c_void_p(d_history_next), history_bytes,
+                                             C.c_void_p(ws_ptr), ws_bytes, C.c_void_p(d_out), C.c_void_p(stream or 0)), "rt_denoise_temporal_spp")
+
+
 _hip_rt = None
 
 
@@ -919,7 +939,9 @@ def adaptive_judge(moments, n, going_on=None, shard=None, rule=0, **params):
 class TemporalDenoiser:
     """rt_denoise_temporal over the frames of an animation: owns the two history buffers and the workspace of a width x height
     image on the device current at construction.  step_to_host() denoises one frame and keeps its history for the next one;
-    reset() forgets the history (a cut).  params: rt_denoise_params fields, the same for every frame."""
+    reset() forgets the history (a cut).  params: rt_denoise_params fields, the same for every frame.  step_spp() and
+    step_spp_to_host() are the same for adaptively sampled frames (rt_denoise_temporal_spp); a history of the one call is empty to
+    the other, so mixing them on one object restarts the history at every change."""
 
     def __init__(self, width, height, **params):
         lib = amd_lib()
@@ -971,6 +993,43 @@ class TemporalDenoiser:
             _check(lib.rt_device_alloc(fb.nbytes or 4, C.byref(d_out)), "rt_device_alloc")
             dev["out"] = d_out
             self.step(dev["fb"].value, {k: dev[k].value for k, _, _, _ in AOV_CHANNELS}, cam, d_out.value)
+            out = np.empty_like(fb)
+            _check(lib.rt_copy_to_host(out.ctypes.data, d_out, out.nbytes), "rt_copy_to_host")
+        finally:
+            for d in dev.values():
+                lib.rt_device_free(d)
+        return out
+
+    def step_spp(self, d_fb, d_spp, d_moments, aov_ptrs, aov_spp, cam, d_out, stream=None):
+        """One adaptively sampled frame on device addresses (denoise_temporal_spp); only enqueues on `stream`."""
+        if (cam.image_width, cam.image_height) != (self.width, self.height):
+            raise RtError(f"TemporalDenoiser: a {cam.image_width} x {cam.image_height} frame for a {self.width} x {self.height} history")
+        denoise_temporal_spp(d_fb, d_spp, d_moments, aov_ptrs, aov_spp, cam, self._prev if self._have else None, self._next, self.history_bytes,
+                             d_out, (self._dev[2].value, self.workspace_bytes), stream=stream, **self.params)
+        self._prev, self._next = self._next, self._prev
+        self._have = True
+
+    def step_spp_to_host(self, fb_sum, spp, moments, aov, aov_spp, cam):
+        """One frame of host arrays: fb_sum (H, W, 3) float32, spp (H, W) int32 and moments (H, W, 2) float32 or None as
+        DeviceScene.render_adaptive_to_host returns them, aov the dict of DeviceScene.render_aov_to_host (prim included) at aov_spp
+        samples per pixel, cam their camera.  Returns the (H, W, 3) float32 output, each pixel the sum over its own samples like
+        fb_sum.  Synchronous (default stream)."""
+        lib = amd_lib()
+        fb = np.ascontiguousarray(fb_sum, dtype=np.float32)
+        arrays = {"fb": fb, "spp": np.ascontiguousarray(spp, dtype=np.int32)}
+        if moments is not None:
+            arrays["moments"] = np.ascontiguousarray(moments, dtype=np.float32)
+        for key, _, dtype, _ in AOV_CHANNELS:
+            arrays[key] = np.ascontiguousarray(aov[key], dtype=dtype)
+        dev = {}
+        try:
+            for key, a in arrays.items():
+                dev[key] = _upload(a)
+            d_out = C.c_void_p()
+            _check(lib.rt_device_alloc(fb.nbytes or 4, C.byref(d_out)), "rt_device_alloc")
+            dev["out"] = d_out
+            self.step_spp(dev["fb"].value, dev["spp"].value, dev["moments"].value if "moments" in dev else None,
+                          {k: dev[k].value for k, _, _, _ in AOV_CHANNELS}, aov_spp, cam, d_out.value)
             out = np.empty_like(fb)
             _check(lib.rt_copy_to_host(out.ctypes.data, d_out, out.nbytes), "rt_copy_to_host")
         finally:
