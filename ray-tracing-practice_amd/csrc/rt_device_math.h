@@ -106,12 +106,14 @@ RT_HD uint32_t wang_hash(uint32_t s) {
 }
 RT_HD float random_float(uint32_t &seed) {      // may return exactly 1.0f
     seed = wang_hash(seed);
-    // / 4294967296.0f: an exact scaling, so ldexp gives the bits of the multiplication (include/random_utils.h:18).  On the
-    // device it also keeps the constant 2^-32 out of the vector registers: as a multiplier the compiler paired it with another
-    // product into one v_pk_mul_f32, and the register pair it pinned for that across the render kernel's main loop was the one
-    // thing the 64-register build had to spill (reloaded in every glass shade step); v_ldexp_f32 takes its exponent from a
-    // scalar register.
-    return __builtin_ldexpf((float)seed, -32);
+    // / 4294967296.0f is an exact scaling (a power of two, never denormal: the smallest non-zero value is 2^-32), so the
+    // multiplication by 2^-32 gives the bits of the division (include/random_utils.h:18; tests/cpu_native/random_float_ref.cpp
+    // compares the two for the edge seeds and a sweep).  On the device it is one full-rate v_mul_f32.  Rounds 4 to 23 wrote it
+    // as ldexp — a half-rate v_ldexp_f32 — only because the SLP vectoriser paired this product with another one into a
+    // v_pk_mul_f32 whose register pair, pinned across the render kernel's main loop, was the one thing the 64-register build had
+    // to spill; the render kernels are compiled without that vectoriser now (Makefile: RENDERFLAGS; docs/LOG.md round 24), and
+    // with the multiplication the headline kernel stays at 64 VGPRs without scratch.
+    return (float)seed * 2.3283064365386962890625e-10f;
 }
 // min + (max - min) * r = -1 + 2 * r.  r = (float)seed * 2^-32 and 2 * r are exact (powers of two), so the one rounding of
 // the sum is the one rounding of fma((float)seed, 2^-31, -1): two instructions per coordinate instead of four in the
