@@ -1037,6 +1037,86 @@ rt_status rt_render_lit_adaptive_rule(rt_scene *scene, const rt_camera_data *cam
                                       const rt_stop_params *stop, const rt_shard *shard, int32_t sample_first, float *d_fb_sum, int32_t *d_spp,
                                       float *d_moments, void *hip_stream, int32_t sync, rt_timing *timing);
 
+/* ---- participating medium ---------------------------------------------------------------------------------------
+ * rt_render_lit's estimator — lens, shutter, the emitter table with mis / sample_planes / select / glossy, the environment with its mode
+ * and glossy — with ONE homogeneous grey medium in a region of space: all space, a ball or an axis-aligned box.  Between two vertices a
+ * path ray may scatter in the medium instead of reaching its surface; every light sample is attenuated by the medium it crosses.
+ * float32 in the order written, nothing fused, division and sqrtf correctly rounded; log_libm and exp_libm are csrc/rt_device_math.h's
+ * stated algorithms (float in, a double table and polynomial, one rounding to float).  FOUR_PI = 2.0f * RT_NEE_TWO_PI.
+ *
+ * Stream.  med = wang_hash(wang_hash(base + s) ^ RT_MEDIUM_STREAM_KEY), base = wang_hash(i * W + j), with random_float.  The path, nee
+ *   and env streams draw exactly what they draw in rt_render_lit for the same sequence of vertices; the medium never touches them, except
+ *   that a medium vertex stands where a surface vertex would have stood.  Without an event med is never advanced.
+ *
+ * Region on a ray.  interval(o, d, t_end) of the ray o + t d over [0, t_end] (t_end may be +inf) is [t0, t1], or empty:
+ *   region 0 (all space): t0 = 0, t1 = t_end.
+ *   region 1 (ball, centre a, radius R = b[0]): oc = o - a; A = lensq(d); hb = dot(oc, d); cc = lensq(oc) - R * R; disc = hb * hb - A * cc;
+ *     empty unless disc > 0; sq = sqrtf(disc); ta = (-hb - sq) / A; tb = (-hb + sq) / A; t0 = ta > 0 ? ta : 0; t1 = tb < t_end ? tb : t_end.
+ *   region 2 (box, lo = a, hi = b): t0 = 0, t1 = t_end; then for the axes x, y, z in turn: when d_k == 0 the interval is empty unless
+ *     lo_k < o_k and o_k < hi_k (no division); otherwise ta = (lo_k - o_k) / d_k, tb = (hi_k - o_k) / d_k, swapped when ta > tb, then
+ *     t0 = ta when ta > t0 and t1 = tb when tb < t1.
+ *   In every region the interval is empty unless t1 > t0.  The region ignores surfaces.
+ *
+ * Segment.  For every PATH ray (o, d) whose closest-hit query k has finished — a hit at parameter t_hit, or a miss: t_hit = +inf — with
+ *   sigma_t > 0: len = sqrtf(lensq(d)) (directions are not unit), [t0, t1] = interval(o, d, t_hit).  An empty interval: no draw, and the
+ *   vertex is rt_render_lit's.
+ * Free flight.  u = random_float(med).  u == 0: no event.  Otherwise s = -log_libm(u) / sigma_t, and there is an event iff
+ *   s < (t1 - t0) * len, at x = o + (t0 + s / len) * d (componentwise o_k + t * d_k).  No event: the surface vertex (or the miss) of
+ *   rt_render_lit with UNCHANGED throughput — sampling the distance of a grey medium has weight 1, so the path never calls exp.
+ * Medium vertex (counts as vertex k for max_depth; medium_events counts them).  ud = unit(d).  beta_in = beta; beta = beta * albedo.  If
+ *   all three channels of the new beta are 0 the path ends here, before any draw.  If k + 1 >= max_depth the path ends here as well.
+ *   Otherwise, in this order:
+ *   1. the emitter sample when the emitters are on, then the environment sample when the environment is sampled: rt_render_lit's steps
+ *      4 and 5 from x with beta_in, a = albedo, no hemisphere test (there is no normal), and pb = ph(dot(ud, wl) / sqrtf(lensq(wl))) for
+ *      the sampled direction wl; pb == 0: no contribution;
+ *   2. the next direction: cos_t from one med draw u1 — g == 0: cos_t = 1 - 2 * u1; otherwise q = (1 - g * g) / ((1 - g) + (2 * g) * u1),
+ *      cos_t = ((1 + g * g) - q * q) / (2 * g), clamped to [-1, 1] — sin_t = sqrtf(max(0, 1 - cos_t * cos_t)); the azimuth (cx, cy) from
+ *      med by rt_render_nee's disc loop (px, py = random_float(med, -1, 1) until 0 < px^2 + py^2 < 1, divided by the root); Duff's basis
+ *      (t1, t2) of rt_render_nee's step 3 around ud; new_d = (t1 * (sin_t * cx) + t2 * (sin_t * cy)) + ud * cos_t.  The next ray is
+ *      (x, new_d) with throughput beta (weight 1: the phase function is sampled exactly), and it carries pb = ph(cos_t) the way a glossy
+ *      event's ray carries pg: the emitter entry or the miss it finds is weighted with that pb against every light that is on; a ph that
+ *      rounds to 0 is "none".
+ *   ph(c): g == 0: 1 / FOUR_PI; otherwise den = (1 + g * g) - (2 * g) * c, ph = (1 - g * g) / (FOUR_PI * (den * sqrtf(den))).
+ * Transmittance.  Every light-sample contribution c, from a surface vertex or a medium one, is added as Tr * c, Tr = exp_libm(-(sigma_t *
+ *   L)), L = (t1 - t0) * len of interval(x, wl, t_end) of its shadow ray: t_end is the parameter of the hit the emitter's shadow ray
+ *   reached (known at the verdict), +inf for the environment's.  An empty interval: Tr = 1 exactly, exp is not called.  With region 0 and
+ *   sigma_t > 0 the environment's Tr is 0: the environment counts as not sampled for the whole call (no light sample is drawn, its stream
+ *   never advances, and a miss keeps weight 1).
+ *   The MIS weights stay those of the directional densities alone: both strategies estimate the same integrand f * Tr * Le — the light
+ *   sample carries Tr as a factor, the path ray carries it as its probability of surviving to the light — so Tr cancels from the ratio of
+ *   the two strategies' densities, and w_l + w_b = 1 per direction as before.
+ *
+ * Identities, bit for bit: medium == NULL or sigma_t == 0 = rt_render_lit with the same lit (and every probe column: medium_events 0, the
+ *   med state as initialised).  sigma_t > 0 with a region that no path ray and no shadow ray of the frame touches = rt_render_lit as well,
+ *   through the medium's own kernels.
+ * Left out: heterogeneous or chromatic extinction; more than one region; regions bounded by scene surfaces (fog inside a glass ball that
+ *   sits in the region is still fog); emission in the medium; the guarded walk; tiles and rt_context; rt_render_lit_adaptive with a
+ *   medium, AOVs of the medium and the denoisers' handling of it (the first-hit AOVs do not see it).
+ * Checks, all before anything is enqueued: rt_render_lit's parameter checks come first, in its order (lens, nee, env_params); then the
+ *   medium's, still before the scene is looked at; then the scene's and the camera's as in rt_render_lit.  RT_ERR_INVALID_ARG for struct_bytes below 8,
+ *   region outside {0, 1, 2}, a sigma_t that is negative, NaN or infinite, an albedo channel outside [0, 1], |g| > 0.95 or NaN, a ball's
+ *   radius <= 0 (or NaN), a box with lo_k >= hi_k in any axis (region 1 and 2 also need finite a and b).  a and b are read only for the
+ *   region that uses them.  Rows of a shard only: no tiles, no rt_context.  Handle state and timing: as rt_render_lit. */
+#define RT_MEDIUM_STREAM_KEY 0x4D454431u   /* "MED1" */
+typedef struct rt_medium_params {   /* IN, caller-sized like rt_lit_params */
+    uint32_t struct_bytes;
+    int32_t  region;        /* 0: all space, 1: ball (centre, radius), 2: axis-aligned box (lo, hi) */
+    float    sigma_t;       /* extinction per unit length, grey, >= 0 and finite; 0 = no medium */
+    float    albedo[3];     /* single-scattering albedo per channel, each in [0, 1] */
+    float    g;             /* Henyey–Greenstein anisotropy, |g| <= 0.95; 0 = isotropic (its own branch, no division by g) */
+    float    a[3], b[3];    /* ball: centre = a, radius = b[0] > 0; box: lo = a < hi = b componentwise */
+} rt_medium_params;
+/* Defaults into *p: region 0, sigma_t 0 (no medium), albedo 1, g 0, a = b = 0; struct_bytes = sizeof(rt_medium_params). */
+void rt_medium_params_init(rt_medium_params *p);
+/* rt_render_lit under the medium (medium NULL: the defaults — no medium). */
+rt_status rt_render_medium(rt_scene *scene, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium,
+                           const rt_shard *shard, int32_t sample_first, float *d_fb_sum, void *hip_stream, int32_t sync, rt_timing *timing);
+/* Probe for tests, HOST memory: rt_trace_samples_lit for the estimator of rt_render_medium, with the number of medium vertices and the
+ * medium stream's final state per (i, j, s) as well. */
+rt_status rt_trace_samples_medium(rt_scene *scene, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium,
+                                  int32_t n, const int32_t *ijs, float *radiance, int32_t *rays, int32_t *medium_events,
+                                  uint32_t *final_seed, uint32_t *final_nee_seed, uint32_t *final_env_seed, uint32_t *final_medium_seed);
+
 /* Milliseconds of the most recent rt_render kernel of this scene (waits for it). */
 rt_status rt_last_kernel_ms(rt_scene *scene, float *ms);
 /* The whole rt_timing of the most recent rt_render of this scene (waits for it). */

@@ -20,6 +20,7 @@
 #include "rt_nee.hip.inc"
 #include "rt_env.hip.inc"
 #include "rt_light.hip.inc"
+#include "rt_medium.hip.inc"
 // Developer build only (make dev → librtp_amd_dev.so, -DRTP_DEV_BUILD): the rt_debug_* entry points (exhaustive on-device checks of
 // recip / sqrt_cr / sphere_root, the device LBVH builder on its own, the tripwire, the RTP_STATS counters) at the end of this file.
 // The shipped library contains none of them.
@@ -3232,6 +3233,134 @@ rt_status rt_trace_samples_lit(rt_scene *sc, const rt_camera_data *cam_open, con
             return RT_OK;
         });
     });
+}
+
+// ---- rt_render_medium / rt_trace_samples_medium (rtp_amd.h, "participating medium"): rt_render_lit under one homogeneous
+// medium.  No medium (NULL, or sigma_t == 0) is rt_render_lit itself; otherwise the kernels of rt_medium.hip.inc, on the call's emitter
+// table like every lit call's.
+void rt_medium_params_init(rt_medium_params *p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->struct_bytes = (uint32_t)sizeof(*p);
+    p->albedo[0] = p->albedo[1] = p->albedo[2] = 1.0f;
+}
+
+namespace {
+// the medium's checks (after rt_render_lit's parameter checks, before the scene is looked at) → M; M.sigma_t == 0: no medium
+rt_status medium_setup(const char *what, const rt_medium_params *medium, rtk::MediumDev &M) {
+    const std::string w(what);
+    rt_medium_params mp;
+    rt_medium_params_init(&mp);
+    if (const rt_status st = take_params(w, "rt_medium_params", medium, mp)) return st;
+    if (mp.region < 0 || mp.region > 2) return fail(RT_ERR_INVALID_ARG, w + ": region must be 0, 1 or 2");
+    if (!(std::isfinite(mp.sigma_t) && mp.sigma_t >= 0.0f)) return fail(RT_ERR_INVALID_ARG, w + ": sigma_t must be finite and not negative");
+    for (int k = 0; k < 3; ++k)
+        if (!(mp.albedo[k] >= 0.0f && mp.albedo[k] <= 1.0f)) return fail(RT_ERR_INVALID_ARG, w + ": an albedo channel outside [0, 1]");
+    if (!(std::fabs(mp.g) <= 0.95f)) return fail(RT_ERR_INVALID_ARG, w + ": |g| must be at most 0.95");
+    if (mp.region != 0)
+        for (int k = 0; k < 3; ++k)
+            if (!std::isfinite(mp.a[k]) || !std::isfinite(mp.b[mp.region == 1 ? 0 : k]))
+                return fail(RT_ERR_INVALID_ARG, w + ": the region's a and b must be finite");
+    if (mp.region == 1 && !(mp.b[0] > 0.0f)) return fail(RT_ERR_INVALID_ARG, w + ": the ball's radius must be positive");
+    if (mp.region == 2)
+        for (int k = 0; k < 3; ++k)
+            if (!(mp.a[k] < mp.b[k])) return fail(RT_ERR_INVALID_ARG, w + ": the box needs lo < hi in every axis");
+    M.region = mp.region;
+    M.sigma_t = mp.sigma_t;
+    M.g = mp.g;
+    for (int k = 0; k < 3; ++k) {
+        M.albedo[k] = mp.albedo[k];
+        M.a[k] = mp.a[k];
+        M.b[k] = mp.b[k];
+    }
+    return RT_OK;
+}
+// The medium kernels' light: with_lit's, always with the float carry (a GlossLit<Table>, its switches the call's), and the medium beside
+// it.  Under a medium that fills all space no environment sample can count (its Tr is 0): the environment is not sampled
+extern "C++" template <class F>
+rt_status with_medium_lit(rt_scene *sc, const LitSetup &S, const rtk::MediumDev &M, F &&f) {
+    return with_emitter_table(sc, S.nee, S.emitters, [&](const auto &table) {
+        using Table = std::decay_t<decltype(table)>;
+        rtk::MediumLit<Table> T{};
+        T.G.N = table;
+        if (S.env) {
+            T.G.E = env_dev_of(S.env, S.ep);
+            T.G.env_on = 1;
+            if (M.region == 0) T.G.E.sampled = 0;
+        }
+        T.G.gn = S.emitters && S.nee.glossy ? 1 : 0;
+        T.G.ge = S.env && S.ep.glossy ? 1 : 0;
+        T.M = M;
+        return f(T);
+    });
+}
+}  // namespace
+
+rt_status rt_render_medium(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium, const rt_shard *shard,
+                           int32_t sample_first, float *d_fb_sum, void *hip_stream, int32_t sync, rt_timing *timing) {
+    LitSetup S;
+    if (const rt_status st = lit_setup("rt_render_medium", cam_open, lit, S)) return st;
+    rtk::MediumDev M{};
+    if (const rt_status st = medium_setup("rt_render_medium", medium, M)) return st;
+    if (!sc) return fail(RT_ERR_INVALID_ARG, "rt_render_medium: null scene");
+    auto with_light = [&](auto frame) {
+        if (!(M.sigma_t > 0.0f))
+            return with_lit(sc, S, [&](const auto &T) { return frame(S.lens ? rtk::lit_frame_kernel_of<true>(T) : rtk::lit_frame_kernel_of<false>(T), &T); });
+        return with_medium_lit(sc, S, M, [&](const auto &T) {
+            using Table = decltype(T.G.N);
+            return frame(S.lens ? (const void *)rtk::medium_render_kernel<true, Table> : (const void *)rtk::medium_render_kernel<false, Table>, &T);
+        });
+    };
+    return render_light_impl("rt_render_medium", S.env ? &S.env->device : nullptr, with_light, sc, cam_open, shard, sample_first, d_fb_sum, hip_stream, sync, timing,
+                             &S.C);
+}
+
+rt_status rt_trace_samples_medium(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium, int32_t n,
+                                  const int32_t *ijs, float *radiance, int32_t *rays, int32_t *medium_events, uint32_t *final_seed, uint32_t *final_nee_seed,
+                                  uint32_t *final_env_seed, uint32_t *final_medium_seed) {
+    const char *what = "rt_trace_samples_medium";
+    LitSetup S;
+    if (const rt_status st = lit_setup(what, cam_open, lit, S)) return st;
+    rtk::MediumDev M{};
+    if (const rt_status ms = medium_setup(what, medium, M)) return ms;
+    if (n < 0 || (n > 0 && (!ijs || !radiance || !rays || !medium_events || !final_seed || !final_nee_seed || !final_env_seed || !final_medium_seed)))
+        return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_medium: null argument");
+    rtk::KParams P;
+    rt_status st = fill_params(sc, cam_open, nullptr, P);
+    if (st != RT_OK) return st;
+    if ((st = check_device(sc)) != RT_OK) return st;
+    if (S.env && S.env->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_medium: the environment was created on another device than the scene");
+    if (n == 0) return RT_OK;
+    if (!(M.sigma_t > 0.0f)) {          // no medium: rt_trace_samples_lit's columns, no event, the med state as initialised
+        if ((st = rt_trace_samples_lit(sc, cam_open, lit, n, ijs, radiance, rays, final_seed, final_nee_seed, final_env_seed)) != RT_OK) return st;
+        for (int32_t k = 0; k < n; ++k) {
+            medium_events[k] = 0;
+            const uint32_t base = rtd::wang_hash((uint32_t)ijs[3 * k] * (uint32_t)cam_open->image_width + (uint32_t)ijs[3 * k + 1]);
+            final_medium_seed[k] = rtd::wang_hash(rtd::wang_hash(base + (uint32_t)ijs[3 * k + 2]) ^ RT_MEDIUM_STREAM_KEY);
+        }
+        return RT_OK;
+    }
+    uint32_t *d_med = nullptr;
+    int32_t *d_events = nullptr;
+    Scratch mem;
+    if (mem.alloc(d_med, (size_t)n * 4) != hipSuccess || mem.alloc(d_events, (size_t)n * 4) != hipSuccess)
+        return fail(RT_ERR_OUT_OF_MEMORY, "rt_trace_samples_medium: hipMalloc failed");
+    st = run_probe("rt_trace_samples_medium: ", P, cam_open, n, ijs, radiance, rays, final_seed, final_nee_seed, final_env_seed,
+                   [&](const rtk::KParams &KP, uint32_t *d_nee, uint32_t *d_env) {
+        return with_medium_lit(sc, S, M, [&](const auto &T) {
+            using Table = decltype(T.G.N);
+            const dim3 grid((n + 255) / 256), block(256);
+            if (S.lens) hipLaunchKernelGGL((rtk::medium_probe_kernel<true, Table>), grid, block, 0, 0, KP, T, S.C, d_nee, d_env, d_med, d_events);
+            else hipLaunchKernelGGL((rtk::medium_probe_kernel<false, Table>), grid, block, 0, 0, KP, T, S.C, d_nee, d_env, d_med, d_events);
+            return RT_OK;
+        });
+    });
+    if (st != RT_OK) return st;
+    // (run_probe has waited for the device)
+    if (hipMemcpy(final_medium_seed, d_med, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(medium_events, d_events, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(RT_ERR_HIP, "rt_trace_samples_medium: hipMemcpy D2H failed");
+    return RT_OK;
 }
 
 void rt_timing_init(rt_timing *t) {

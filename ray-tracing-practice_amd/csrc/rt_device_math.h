@@ -196,6 +196,64 @@ RT_HD float exp_libm(float x) {
     return (float)y;
 }
 
+// ---- logf: the host libm's algorithm ------------------------------------------------------------------
+// The free-flight distance of rt_render_medium, -log(u) / sigma_t (include/rtp_amd.h, "participating medium").
+// glibc >= 2.27 sysdeps/ieee754/flt-32/e_logf.c: x = 2^k z with z in [0x1.66p-1, 0x1.66p0), 16 intervals of z with (1/c, log c) from
+// a table (c near the interval's centre), r = z / c - 1, log x = k ln 2 + log c + log1p(r), log1p(r) - r by a cubic's worth of terms
+// — all in double, rounded once to float.  The CONTRACT is this text, nothing fused, not the libm.  Its restatement for the host
+// (tests/cpu_native/log_ref.h) gives glibc 2.35's logf bits for every float of (0, 1] (1 065 353 216 inputs, 0 differ); this routine
+// compiled for the host equals that restatement on all 2^32 floats (tests/test_medium.py), and so does this routine compiled for gfx950
+// (tests/dev_log_checks.py).
+// Specials: log(1) = +0, log(+-0) = -inf, log(+inf) = +inf, a negative argument gives +qNaN, a NaN comes back as x + x.
+#if defined(__HIPCC__)
+__device__ __constant__
+#endif
+static const double kLogTab[16][2] = {
+    {0x1.661ec79f8f3bep+0, -0x1.57bf7808caadep-2}, {0x1.571ed4aaf883dp+0, -0x1.2bef0a7c06ddbp-2},
+    {0x1.49539f0f010bp+0, -0x1.01eae7f513a67p-2},  {0x1.3c995b0b80385p+0, -0x1.b31d8a68224e9p-3},
+    {0x1.30d190c8864a5p+0, -0x1.6574f0ac07758p-3}, {0x1.25e227b0b8eap+0, -0x1.1aa2bc79c81p-3},
+    {0x1.1bb4a4a1a343fp+0, -0x1.a4e76ce8c0e5ep-4}, {0x1.12358f08ae5bap+0, -0x1.1973c5a611cccp-4},
+    {0x1.0953f419900a7p+0, -0x1.252f438e10c1ep-5}, {0x1p+0, 0x0p+0},
+    {0x1.e608cfd9a47acp-1, 0x1.aa5aa5df25984p-5},  {0x1.ca4b31f026aap-1, 0x1.c5e53aa362eb4p-4},
+    {0x1.b2036576afce6p-1, 0x1.526e57720db08p-3},  {0x1.9c2d163a1aa2dp-1, 0x1.bc2860d22477p-3},
+    {0x1.886e6037841edp-1, 0x1.1058bc8a07ee1p-2},  {0x1.767dcf5534862p-1, 0x1.4043057b6ee09p-2},
+};
+RT_HD float log_libm(float x) {
+    uint32_t ix;
+    memcpy(&ix, &x, 4);
+    if (ix == 0x3f800000u) return 0.0f;
+    if (ix - 0x00800000u >= 0x7f800000u - 0x00800000u) {            // x < 2^-126, negative, inf or NaN
+        if ((ix << 1) == 0u) return -INFINITY;
+        if (ix == 0x7f800000u) return x;
+        if ((ix & 0x80000000u) || (ix << 1) >= 0xff000000u) {
+            uint32_t qnan = 0x7fc00000u;
+            float q;
+            memcpy(&q, &qnan, 4);
+            return x != x ? x + x : q;
+        }
+        const float ax = x * 0x1p23f;                                 // subnormal: normalise, the exponent goes negative
+        memcpy(&ix, &ax, 4);
+        ix -= 23u << 23;
+    }
+    const uint32_t tmp = ix - 0x3f330000u;
+    const uint32_t i = (tmp >> 19) % 16u;
+    const uint32_t top = tmp & 0xff800000u;
+    const uint32_t iz = ix - top;
+    const int32_t k = (int32_t)tmp >> 23;
+    float zf;
+    memcpy(&zf, &iz, 4);
+    const double invc = kLogTab[i][0], logc = kLogTab[i][1], z = (double)zf;
+    const double ln2 = 0x1.62e42fefa39efp-1;
+    const double a0 = -0x1.00ea348b88334p-2, a1 = 0x1.5575b0be00b6ap-2, a2 = -0x1.ffffef20a4123p-2;
+    const double r = z * invc - 1.0;
+    const double y0 = logc + (double)k * ln2;
+    const double r2 = r * r;
+    double y = a1 * r + a2;
+    y = a0 * r2 + y;
+    y = y * r2 + (y0 + r);
+    return (float)y;
+}
+
 // ---- powf(x, 5): the host libm's algorithm ----------------------------------------------------------
 // (1 - cos)^5 of the Schlick term (include/materials.h:67).  glibc >= 2.28 sysdeps/ieee754/flt-32/e_powf.c: log2(x) from a
 // 16-entry table (1/c, log2 c) and a degree-5 polynomial, times y, then 2^(.) with the table and cubic exp_libm uses — all in

@@ -105,7 +105,7 @@ __device__ __forceinline__ bool env_sample(const EnvDev &E, uint32_t &env, f3 n,
     const f3 we = mk(p.x / q, p.y / q, p.z / q);
     dir = mk((E.rot[0] * we.x + E.rot[3] * we.y) + E.rot[6] * we.z, (E.rot[1] * we.x + E.rot[4] * we.y) + E.rot[7] * we.z,
              (E.rot[2] * we.x + E.rot[5] * we.y) + E.rot[8] * we.z);
-    if (!(dot(dir, n) > 0.0f)) return false;
+    if (kPbHemisphere<Pb> && !(dot(dir, n) > 0.0f)) return false;
     const float pb = PB(dir);
     if (Pb::kGlossy && pb == 0.0f) return false;
     const float4 T = E.texels[(size_t)iy * (size_t)E.n + (size_t)ix];

@@ -598,31 +598,10 @@ __device__ __forceinline__ void lit_probe_body(const KParams &P, const Lit &T, c
 // environment sample still waits.  Across the emitter's walk a lane holds the next direction, both pending contributions, the
 // environment's direction and the target (thirteen registers); across the environment's, the next direction and its contribution.
 constexpr int32_t kLitShadowA = 2, kLitShadowAB = 3, kLitShadowB = 4;
-// The wave loop is one text for both of its forms — RTP_LIT_RENDER_BODY, the body of a function with P, T and C in scope: TOTAL is the
-// number of work indices (wave-uniform) and WORK_OF_MINE what the fetched index `mine` stands for.  Expanded twice rather than branched
-// on inside, so that the frame kernels compile to what they compiled to before the list variants existed (DESIGN.md §19).
-#define RTP_LIT_RENDER_BODY(TOTAL, WORK_OF_MINE)                                                                    \
-    const int lane = (int)(threadIdx.x & (kWave - 1));                                                              \
-    Lane L;                                                                                                         \
-    L.node = kBlocked;                                                                                              \
-    L.sp = 0;                                                                                                       \
-    L.hit = -1;                                                                                                     \
-    L.closest = 1e30f;                                                                                              \
-    L.color = mk(0.0f, 0.0f, 0.0f);                                                                                 \
-    L.beta = mk(1.0f, 1.0f, 1.0f);                                                                                  \
-    L.depth = 0;                                                                                                    \
-    L.seed = 0;                                                                                                     \
-    int32_t phase = kLightIdle;                                                                                     \
-    uint32_t w = 0, nee = 0, env = 0;                                                                               \
-    LitCarry<Lit> prev_diffuse = LitCarry<Lit>(0);                                                                  \
-    f3 next_d = mk(0, 0, 0);                                                                                        \
-    LitSamples S;                                                                                                   \
-    S.adir = S.ac = S.bdir = S.bc = mk(0, 0, 0);                                                                    \
-    S.code = -1;                                                                                                    \
-    S.a = S.b = false;                                                                                              \
-    uint32_t pool_next = 0, pool_end = 0;  /* (wave-uniform) */                                                     \
-    bool exhausted = false;                                                                                         \
-    for (;;) {                                                                                                      \
+// The fetch of the wave loop — RTP_LIT_POOL_FETCH, a statement with lane, L, P, C, phase, w, nee, env, prev_diffuse, pool_next, pool_end and
+// exhausted in scope: LIGHT is the Lit<Table> whose streams start, ALSO a statement run for a lane that takes a sample, with base_seed and s
+// at hand (empty in the lit kernels; rt_medium.hip.inc starts its own stream there, and undefines the macro)
+#define RTP_LIT_POOL_FETCH(TOTAL, WORK_OF_MINE, LIGHT, ALSO)                                                        \
         /* ---- lanes without a sample take the next work indices of the wave's pool (refilled with one atomic) */  \
         const uint64_t idle = __ballot(phase == kLightIdle);                                                        \
         if (idle != 0 && !exhausted) {                                                                              \
@@ -649,15 +628,42 @@ constexpr int32_t kLitShadowA = 2, kLitShadowAB = 3, kLitShadowB = 4;
                 map_work(P, w, pi, pj, k);                                                                          \
                 const int32_t s = P.pass_first + (int32_t)k;                                                        \
                 const uint32_t base_seed = wang_hash((uint32_t)pi * (uint32_t)P.width + (uint32_t)pj);              \
-                nee = light_seed_of(T.N, base_seed, s);                                                             \
-                env = light_seed_of(T.E, base_seed, s);                                                             \
+                nee = light_seed_of((LIGHT).N, base_seed, s);                                                       \
+                env = light_seed_of((LIGHT).E, base_seed, s);                                                       \
                 f3 o, d;                                                                                            \
                 lit_start<kLens>(L, P, C, pi, pj, base_seed, s, o, d);                                              \
+                ALSO                                                                                                \
                 begin_ray(L, o, d, 0);                                                                              \
                 prev_diffuse = LitCarry<Lit>(0);                                                                    \
                 phase = kLightPath;                                                                                 \
             }                                                                                                       \
-        }                                                                                                           \
+        }
+// The wave loop is one text for both of its forms — RTP_LIT_RENDER_BODY, the body of a function with P, T and C in scope: TOTAL is the
+// number of work indices (wave-uniform) and WORK_OF_MINE what the fetched index `mine` stands for.  Expanded twice rather than branched
+// on inside, so that the frame kernels compile to what they compiled to before the list variants existed (DESIGN.md §19).
+#define RTP_LIT_RENDER_BODY(TOTAL, WORK_OF_MINE)                                                                    \
+    const int lane = (int)(threadIdx.x & (kWave - 1));                                                              \
+    Lane L;                                                                                                         \
+    L.node = kBlocked;                                                                                              \
+    L.sp = 0;                                                                                                       \
+    L.hit = -1;                                                                                                     \
+    L.closest = 1e30f;                                                                                              \
+    L.color = mk(0.0f, 0.0f, 0.0f);                                                                                 \
+    L.beta = mk(1.0f, 1.0f, 1.0f);                                                                                  \
+    L.depth = 0;                                                                                                    \
+    L.seed = 0;                                                                                                     \
+    int32_t phase = kLightIdle;                                                                                     \
+    uint32_t w = 0, nee = 0, env = 0;                                                                               \
+    LitCarry<Lit> prev_diffuse = LitCarry<Lit>(0);                                                                  \
+    f3 next_d = mk(0, 0, 0);                                                                                        \
+    LitSamples S;                                                                                                   \
+    S.adir = S.ac = S.bdir = S.bc = mk(0, 0, 0);                                                                    \
+    S.code = -1;                                                                                                    \
+    S.a = S.b = false;                                                                                              \
+    uint32_t pool_next = 0, pool_end = 0;  /* (wave-uniform) */                                                     \
+    bool exhausted = false;                                                                                         \
+    for (;;) {                                                                                                      \
+        RTP_LIT_POOL_FETCH(TOTAL, WORK_OF_MINE, T, )                                                                \
         const bool busy = phase != kLightIdle;                                                                      \
         if (!__any(busy)) {                                                                                         \
             if (exhausted) break;                                                                                   \
@@ -739,6 +745,7 @@ __device__ __forceinline__ void lit_render_body(const KParams &P, const Lit &T, 
     }
 }
 #undef RTP_LIT_RENDER_BODY
+// (RTP_LIT_POOL_FETCH stays defined: rt_medium.hip.inc, included right after this file, expands it once more and undefines it)
 
 template <bool kLens, class Table>
 __global__ void __launch_bounds__(256) lit_probe_kernel(const KParams P, const Lit<Table> T, const LensCam C, uint32_t *nee_seed_out, uint32_t *env_seed_out) {

@@ -17,8 +17,11 @@ enum Routine : int32_t {
     kTonemap = 6,    // u8:  tonemap_u8(bits k, inv_divisor = bits arg)
     kPow5Float = 7,  // u32: pow5_float(bits k)
     kSchlick = 8,    // 6 x u64 in all (not per input): see schlick_check; arg = bits of r0
-    kRoutines = 9
+    kRoutines = 9,   // the routines numbered consecutively end here; 9 itself stays refused (the hook's argument test pins it as unknown)
+    kLog = 10        // u32: log_libm(bits k)
 };
+// Is `routine` one of the above?  (Not a range test: 9 is none.  A further routine gets the next number after kLog and a line here.)
+RT_HD bool is_routine(int32_t routine) { return (routine >= 0 && routine < kRoutines) || routine == kLog; }
 
 // ---- atan2 pairs: index → (y, x) -------------------------------------------------------------------------------------
 // [0, kSpecialPairs): every (y, x) of kSpecials x kSpecials — signed zeros, denormals, the normal range's ends, +-1 and its

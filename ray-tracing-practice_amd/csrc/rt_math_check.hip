@@ -43,6 +43,7 @@ __global__ void __launch_bounds__(kThreads) eval_kernel(int32_t routine, uint32_
         }
         case kTonemap: ((uint8_t *)out)[k] = rtd::tonemap_u8(x, farg); break;
         case kPow5Float: w[k] = float_to_bits(rtd::pow5_float(x)); break;
+        case kLog: w[k] = float_to_bits(rtd::log_libm(x)); break;
         default: break;
         }
     }
@@ -78,7 +79,7 @@ rt_status rt_debug_math_eval(int32_t routine, uint32_t first, uint64_t count, ui
         rt_internal_set_error("rt_debug_math_eval: null d_out");
         return RT_ERR_INVALID_ARG;
     }
-    if (routine < 0 || routine >= rtm::kRoutines) {
+    if (!rtm::is_routine(routine)) {
         rt_internal_set_error("rt_debug_math_eval: unknown routine " + std::to_string(routine));
         return RT_ERR_INVALID_ARG;
     }

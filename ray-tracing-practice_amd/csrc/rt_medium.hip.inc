@@ -1,0 +1,319 @@
+// rt_medium.hip.inc — a homogeneous participating medium on the lit path (rt_render_medium; include/rtp_amd.h, "participating medium";
+// DESIGN.md §25).  Included by rt_capi.hip after rt_light.hip.inc, whose vertex (shade_lit2), camera (lit_start), walk step (lit_step),
+// light samples (light_sample) and pool fetch (RTP_LIT_POOL_FETCH) it uses as they are.
+//
+// What is new here: the region's interval on a ray, the free-flight draw in front of the surface vertex, the medium vertex — both light
+// samples with the phase function as the BSDF strategy's density (PbPhase, no hemisphere) and a Henyey-Greenstein direction whose density
+// the next ray carries like a glossy event's pg — and the transmittance of a shadow ray at its verdict.  The light is always a
+// GlossLit<Table> (the float carry); whether METAL's reflect branch samples is its runtime gn / ge.  Every expression is the header's, in
+// its order.
+#pragma once
+
+namespace rtk {
+
+constexpr uint32_t kMediumStreamKey = RT_MEDIUM_STREAM_KEY;       // med = wang_hash(sample_seed ^ key)
+constexpr float kFourPi = 2.0f * RT_NEE_TWO_PI;
+
+// The call's medium, by value beside its light
+struct MediumDev {
+    int32_t region;       // 0 all space, 1 ball (a, b[0]), 2 box (a, b)
+    float sigma_t;        // > 0: sigma_t == 0 never reaches these kernels (the host hands such a call to rt_render_lit's)
+    float albedo[3];
+    float g;
+    float a[3], b[3];
+};
+template <class Table>
+struct MediumLit {
+    GlossLit<Table> G;
+    MediumDev M;
+};
+
+// interval(o, d, t_end) of the header: false = empty
+__device__ __forceinline__ bool medium_interval(const MediumDev &M, f3 o, f3 d, float t_end, float &t0, float &t1) {
+    t0 = 0.0f;
+    t1 = t_end;
+    if (M.region == 1) {
+        const f3 oc = sub(o, mk(M.a[0], M.a[1], M.a[2]));
+        const float A = lensq(d);
+        const float hb = dot(oc, d);
+        const float cc = lensq(oc) - M.b[0] * M.b[0];
+        const float disc = hb * hb - A * cc;
+        if (!(disc > 0.0f)) return false;
+        const float sq = sqrt_cr(disc);
+        const float ta = (-hb - sq) / A;
+        const float tb = (-hb + sq) / A;
+        t0 = ta > 0.0f ? ta : 0.0f;
+        t1 = tb < t_end ? tb : t_end;
+    } else if (M.region == 2) {
+        const float oo[3] = {o.x, o.y, o.z}, dd[3] = {d.x, d.y, d.z};
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            if (dd[k] == 0.0f) {
+                if (!(M.a[k] < oo[k] && oo[k] < M.b[k])) return false;
+            } else {
+                float ta = (M.a[k] - oo[k]) / dd[k];
+                float tb = (M.b[k] - oo[k]) / dd[k];
+                if (ta > tb) {
+                    const float tt = ta;
+                    ta = tb;
+                    tb = tt;
+                }
+                if (ta > t0) t0 = ta;
+                if (tb < t1) t1 = tb;
+            }
+        }
+    }
+    return t1 > t0;
+}
+// ph(c) of the header: Henyey-Greenstein's density in solid angle at the cosine c between the direction of travel and the new direction
+__device__ __forceinline__ float medium_ph(float g, float c) {
+    if (g == 0.0f) return 1.0f / kFourPi;
+    const float den = (1.0f + g * g) - (2.0f * g) * c;
+    return (1.0f - g * g) / (kFourPi * (den * sqrt_cr(den)));
+}
+// pb of a light sample at a medium vertex: ph at the sampled direction (which need not be unit).  Its 0 is "no contribution", and there
+// is no hemisphere
+struct PbPhase {
+    static constexpr bool kGlossy = true;
+    f3 ud;
+    float g;
+    __device__ __forceinline__ float operator()(f3 w) const { return medium_ph(g, dot(ud, w) / sqrt_cr(lensq(w))); }
+};
+template <> constexpr bool kPbHemisphere<PbPhase> = false;
+
+// Tr of a shadow ray (o, d) that ended at t_end, as a factor on its contribution c
+__device__ __forceinline__ f3 medium_attenuate(const MediumDev &M, f3 o, f3 d, float t_end, f3 c) {
+    float t0, t1;
+    if (!medium_interval(M, o, d, t_end, t0, t1)) return c;
+    const float len = sqrt_cr(lensq(d));
+    const float tr = exp_libm(-(M.sigma_t * ((t1 - t0) * len)));
+    return scale(tr, c);
+}
+__device__ __forceinline__ uint32_t medium_seed_of(uint32_t base_seed, int32_t s) { return wang_hash(wang_hash(base_seed + (uint32_t)s) ^ kMediumStreamKey); }
+
+// The free-flight step of a lane whose path ray has finished its closest-hit query (L.hit, L.closest), in front of the surface vertex.
+// false: no event — the caller runs shade_lit2, with nothing changed but (perhaps) one draw of med.  true: the vertex is a medium vertex and
+// is done: `more` as shade_lit2 returns it, the light samples in S, the next ray (out_o, out_d) and what it carries
+template <class Table>
+__device__ __forceinline__ bool medium_vertex(Lane &L, const KParams &P, const MediumLit<Table> &T, uint32_t &nee, uint32_t &env, uint32_t &med, f3 &out_o,
+                                              f3 &out_d, LitSamples &S, float &carry_out, bool &more, int32_t &events) {
+    const MediumDev &M = T.M;
+    float t0, t1;
+    if (!medium_interval(M, L.o, L.d, L.hit < 0 ? INFINITY : L.closest, t0, t1)) return false;
+    const float len = sqrt_cr(lensq(L.d));
+    const float u = random_float(med);
+    if (u == 0.0f) return false;
+    const float s = -log_libm(u) / M.sigma_t;
+    if (!(s < (t1 - t0) * len)) return false;
+    events++;
+    S.a = false;
+    S.b = false;
+    carry_out = 0.0f;
+    more = false;
+    const f3 x = add(L.o, scale(t0 + s / len, L.d));
+    const f3 ud = unit(L.d);
+    const f3 beta_in = L.beta;
+    const f3 alb = mk(M.albedo[0], M.albedo[1], M.albedo[2]);
+    L.beta = mul(L.beta, alb);
+    if (L.beta.x == 0.0f && L.beta.y == 0.0f && L.beta.z == 0.0f) return true;
+    if (!(L.depth + 1 < P.max_depth)) return true;
+    PbPhase pb;
+    pb.ud = ud;
+    pb.g = M.g;
+    if (light_on(T.G.N)) S.a = light_sample(P, T.G.N, nee, x, ud, alb, beta_in, pb, S.adir, S.ac, S.code);
+    if (env_sampled(T.G)) S.b = light_sample(P, T.G.E, env, x, ud, alb, beta_in, pb, S.bdir, S.bc, S.code);
+    // the next direction: Henyey-Greenstein's cosine by inversion, the azimuth by the disc loop, Duff's basis around ud
+    const float u1 = random_float(med);
+    float cos_t;
+    if (M.g == 0.0f) {
+        cos_t = 1.0f - 2.0f * u1;
+    } else {
+        const float q = (1.0f - M.g * M.g) / ((1.0f - M.g) + (2.0f * M.g) * u1);
+        cos_t = ((1.0f + M.g * M.g) - q * q) / (2.0f * M.g);
+        cos_t = cos_t < -1.0f ? -1.0f : (cos_t > 1.0f ? 1.0f : cos_t);
+    }
+    const float sin_t = sqrt_cr(fmaxf(0.0f, 1.0f - cos_t * cos_t));
+    float px, py, q2;
+    do {
+        px = random_pm1(med);
+        py = random_pm1(med);
+        q2 = px * px + py * py;
+    } while (q2 >= 1.0f || q2 == 0.0f);
+    const float qq = sqrt_cr(q2);
+    const float cx = px / qq, cy = py / qq;
+    const float sgn = copysignf(1.0f, ud.z);
+    const float ba = -1.0f / (sgn + ud.z);
+    const float bb = (ud.x * ud.y) * ba;
+    const f3 b1 = mk(1.0f + ((sgn * ud.x) * ud.x) * ba, sgn * bb, -sgn * ud.x);
+    const f3 b2 = mk(bb, sgn + (ud.y * ud.y) * ba, -ud.y);
+    const float sx = sin_t * cx, sy = sin_t * cy;
+    out_d = mk((b1.x * sx + b2.x * sy) + ud.x * cos_t, (b1.y * sx + b2.y * sy) + ud.y * cos_t, (b1.z * sx + b2.z * sy) + ud.z * cos_t);
+    out_o = x;
+    carry_out = medium_ph(M.g, cos_t);
+    L.depth++;
+    more = true;
+    return true;
+}
+
+// ---- probe (rt_trace_samples_medium): lit_probe_body with the free-flight step and the transmittance --------------------------------
+template <bool kLens, class Table>
+__device__ __forceinline__ void medium_probe_body(const KParams &P, const MediumLit<Table> &T, const LensCam &C, uint32_t *nee_seed_out, uint32_t *env_seed_out,
+                                                  uint32_t *med_seed_out, int32_t *events_out) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= P.probe_n) return;
+    const int32_t i = P.probe_ijs[3 * g], j = P.probe_ijs[3 * g + 1], s = P.probe_ijs[3 * g + 2];
+    Lane L;
+    const uint32_t base_seed = wang_hash((uint32_t)i * (uint32_t)P.width + (uint32_t)j);
+    uint32_t nee = light_seed_of(T.G.N, base_seed, s), env = light_seed_of(T.G.E, base_seed, s), med = medium_seed_of(base_seed, s);
+    f3 ray_o, ray_d;
+    lit_start<kLens>(L, P, C, i, j, base_seed, s, ray_o, ray_d);
+    begin_ray(L, ray_o, ray_d, 0);
+    int32_t rays = 0, events = 0;
+    float prev = 0.0f;
+    if (P.max_depth > 0) {
+        for (;;) {
+            rays++;
+            while (!traversal_finished<true>(L, kBlocked)) lit_step(L, P, false);
+            LitSamples S;
+            S.code = -1;
+            float carry;
+            bool more;
+            if (!medium_vertex(L, P, T, nee, env, med, ray_o, ray_d, S, carry, more, events)) more = shade_lit2(L, P, T.G, prev, nee, env, ray_o, ray_d, S, carry);
+            if (S.a) {
+                rays++;
+                begin_ray(L, ray_o, S.adir, 0);
+                while (!traversal_finished<true>(L, kBlocked)) lit_step(L, P, false);
+                if (L.hit == S.code) L.color = add(L.color, medium_attenuate(T.M, L.o, L.d, L.closest, S.ac));
+            }
+            if (S.b) {
+                rays++;
+                begin_ray(L, ray_o, S.bdir, 0);
+                while (!traversal_finished<true>(L, kBlocked)) lit_step(L, P, true);
+                if (L.hit < 0) L.color = add(L.color, medium_attenuate(T.M, L.o, L.d, INFINITY, S.bc));
+            }
+            if (!more) break;
+            prev = carry;
+            begin_ray(L, ray_o, ray_d, 0);
+        }
+    }
+    P.probe_rad[3 * g] = L.color.x; P.probe_rad[3 * g + 1] = L.color.y; P.probe_rad[3 * g + 2] = L.color.z;
+    P.probe_rays[g] = rays;
+    P.probe_seed[g] = L.seed;
+    nee_seed_out[g] = nee;
+    env_seed_out[g] = env;
+    med_seed_out[g] = med;
+    events_out[g] = events;
+}
+
+// ---- the trace kernel of rt_render_medium ---------------------------------------------------------------------------------------------
+// lit_render_body's wave loop (the fetch is its own text, RTP_LIT_POOL_FETCH; the rest is RTP_LIT_RENDER_BODY's, restated: a change
+// to either loop has to be made in both) with the free-flight step in front of the path's shade and the
+// transmittance at the two shadow verdicts.  One register more than the lit kernel lives across the walks: the med state.  The emitter's
+// verdict needs nothing new — the shadow ray's origin, direction and the parameter of the hit it reached are the lane's own L.o, L.d and
+// L.closest — nor does the environment's.
+template <bool kLens, class Table>
+__device__ __forceinline__ void medium_render_body(const KParams &P, const MediumLit<Table> &T, const LensCam &C) {
+    using Lit = GlossLit<Table>;
+    const int lane = (int)(threadIdx.x & (kWave - 1));
+    Lane L;
+    L.node = kBlocked;
+    L.sp = 0;
+    L.hit = -1;
+    L.closest = 1e30f;
+    L.color = mk(0.0f, 0.0f, 0.0f);
+    L.beta = mk(1.0f, 1.0f, 1.0f);
+    L.depth = 0;
+    L.seed = 0;
+    int32_t phase = kLightIdle;
+    uint32_t w = 0, nee = 0, env = 0, med = 0;
+    LitCarry<Lit> prev_diffuse = LitCarry<Lit>(0);
+    f3 next_d = mk(0, 0, 0);
+    LitSamples S;
+    S.adir = S.ac = S.bdir = S.bc = mk(0, 0, 0);
+    S.code = -1;
+    S.a = S.b = false;
+    uint32_t pool_next = 0, pool_end = 0;  // (wave-uniform)
+    bool exhausted = false;
+    for (;;) {
+        RTP_LIT_POOL_FETCH(P.total_work, mine, T.G, med = medium_seed_of(base_seed, s);)
+        const bool busy = phase != kLightIdle;
+        if (!__any(busy)) {
+            if (exhausted) break;
+            continue;
+        }
+        const bool walking = busy && !traversal_finished<true>(L, kBlocked);
+        const bool ready = busy && !walking;
+        const int n_walk = __popcll(__ballot(walking));
+        const int n_ready = __popcll(__ballot(ready));
+        if (n_walk == 0 || n_ready >= kLightShadeLanes) {
+            if (ready) {
+                if (phase == kLightPath) {
+                    f3 next_o;
+                    float carry;
+                    bool more;
+                    int32_t events = 0;
+                    if (!medium_vertex(L, P, T, nee, env, med, next_o, next_d, S, carry, more, events))
+                        more = shade_lit2(L, P, T.G, prev_diffuse, nee, env, next_o, next_d, S, carry);
+                    prev_diffuse = carry;
+                    if (!more && (S.a || S.b)) next_d = mk(0, 0, 0);
+                    if (S.a) {
+                        begin_ray(L, next_o, S.adir, 0);
+                        phase = S.b ? kLitShadowAB : kLitShadowA;
+                    } else if (S.b) {
+                        begin_ray(L, next_o, S.bdir, 0);
+                        phase = kLitShadowB;
+                    } else if (more) {
+                        begin_ray(L, next_o, next_d, 0);
+                    } else {
+                        store_sample(P, w, L.color);
+                        phase = kLightIdle;
+                    }
+                } else if (phase == kLitShadowB) {
+                    if (L.hit < 0) L.color = add(L.color, medium_attenuate(T.M, L.o, L.d, INFINITY, S.bc));
+                    if (no_next_ray(next_d)) {
+                        store_sample(P, w, L.color);
+                        phase = kLightIdle;
+                    } else {
+                        begin_ray(L, L.o, next_d, 0);
+                        phase = kLightPath;
+                    }
+                } else {
+                    if (L.hit == S.code) L.color = add(L.color, medium_attenuate(T.M, L.o, L.d, L.closest, S.ac));
+                    const bool then_env = phase == kLitShadowAB;
+                    if (!then_env && no_next_ray(next_d)) {
+                        store_sample(P, w, L.color);
+                        phase = kLightIdle;
+                    } else {
+                        begin_ray(L, L.o, then_env ? S.bdir : next_d, 0);
+                        phase = then_env ? kLitShadowB : kLightPath;
+                    }
+                }
+                if (phase == kLightIdle) {
+                    L.node = kBlocked;
+                    L.sp = 0;
+                }
+            }
+        } else {
+            const bool occlusion = phase == kLitShadowB;
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                if (!traversal_finished<true>(L, kBlocked)) lit_step(L, P, occlusion);
+            }
+        }
+    }
+}
+#undef RTP_LIT_POOL_FETCH          // (defined in rt_light.hip.inc, which leaves it for this file: no expansion of it may follow)
+
+template <bool kLens, class Table>
+__global__ void __launch_bounds__(256) medium_probe_kernel(const KParams P, const MediumLit<Table> T, const LensCam C, uint32_t *nee_seed_out, uint32_t *env_seed_out,
+                                                           uint32_t *med_seed_out, int32_t *events_out) {
+    medium_probe_body<kLens>(P, T, C, nee_seed_out, env_seed_out, med_seed_out, events_out);
+}
+// (waves per SIMD the compiler is held to, for all eight: DESIGN.md §25, profiles/r25/kernel_resource_usage.txt)
+constexpr int kMediumWaves = 3;
+template <bool kLens, class Table>
+__global__ void __launch_bounds__(kLightBlock, kMediumWaves) medium_render_kernel(const KParams P, const MediumLit<Table> T, const LensCam C) {
+    medium_render_body<kLens>(P, T, C);
+}
+
+}  // namespace rtk

@@ -53,6 +53,9 @@ struct PbGlossy {
     float fuzz;
     __device__ __forceinline__ float operator()(f3 w) const { return gloss_pg(w, r, fuzz); }
 };
+// Does a light sample at this kind of vertex have a hemisphere — is a direction with dot(dir, n) <= 0 refused?  Every surface vertex's has;
+// a vertex in a participating medium has no normal (PbPhase, rt_medium.hip.inc)
+template <class Pb> constexpr bool kPbHemisphere = true;
 __device__ __forceinline__ PbGlossy gloss_pb(f3 r, float fuzz) {
     PbGlossy g;
     g.r = r;
@@ -159,7 +162,7 @@ __device__ __forceinline__ bool nee_sample_sphere(const KParams &P, int32_t sphe
     const f3 t2 = mk(bb, sgn + (wn.y * wn.y) * ba, -wn.y);
     const float sx = sin_t * cx, sy = sin_t * cy;
     dir = mk((t1.x * sx + t2.x * sy) + wn.x * cos_t, (t1.y * sx + t2.y * sy) + wn.y * cos_t, (t1.z * sx + t2.z * sy) + wn.z * cos_t);
-    if (!(dot(dir, n) > 0.0f)) return false;
+    if (kPbHemisphere<Pb> && !(dot(dir, n) > 0.0f)) return false;
     const float pb = PB(dir);
     if (Pb::kGlossy && pb == 0.0f) return false;
     const float pl = *pmf * nee_pdf_cone(om);
@@ -225,7 +228,7 @@ __device__ __forceinline__ bool emit_plane_pa(const KParams &P, int32_t plane, f
     const f3 y = mk((P4.x + ua * P2.x) + ub * P3.x, (P4.y + ua * P2.y) + ub * P3.y, (P4.z + ua * P2.z) + ub * P3.z);                     \
     float pa;                                                                                                                            \
     if (!emit_plane_pa(P, plane, T.area[e], x, y, dir, pa)) return false;                                                                \
-    if (!(dot(dir, n) > 0.0f)) return false;                                                                                             \
+    if (kPbHemisphere<Pb> && !(dot(dir, n) > 0.0f)) return false;                                                                        \
     const float pb = PB(dir);                                                                                                            \
     if (Pb::kGlossy && pb == 0.0f) return false;                                                                                         \
     const float pl = PMF * pa;                                                                                                           \

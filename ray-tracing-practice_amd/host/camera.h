@@ -149,7 +149,7 @@ void gpu_render_pipelined(const SceneParams &params, const rt_scene_desc &desc, 
 void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const rt_lens_params &lens, float shutter, bool aov, bool denoise,
                      const rt_nee_params *nee = nullptr, const rt_env *env = nullptr, const rt_env_params *env_params = nullptr,
                      const rt_lit_params *lit = nullptr, const rt_adaptive_params *noise = nullptr, bool denoise_adaptive = false,
-                     const rt_stop_params *stop = nullptr, bool denoise_adaptive_temporal = false);
+                     const rt_stop_params *stop = nullptr, bool denoise_adaptive_temporal = false, const rt_medium_params *medium = nullptr);
 // rtp_main --gpu --adaptive: the orbit frame after frame on one GPU, each frame through rt_render_adaptive and rt_tonemap_spp;
 // denoise_adaptive (rtp_main --denoise-adaptive): each frame also filtered by rt_denoise_spp with its counts and moments and
 // rt_render_aov AOVs at ap.min_spp, written through rt_tonemap_spp to "<frame file>.denoised"; denoise_adaptive_temporal (rtp_main

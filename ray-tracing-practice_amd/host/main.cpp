@@ -178,6 +178,64 @@ int main(int argc, char *argv[]) {
             return 99;
         }
     }
+    // extension: `--lit … --fog SIGMA[:ALBEDO[:G]] [--fog-ball cx,cy,cz,r | --fog-box x0,y0,z0,x1,y1,z1]`: the --lit frames through
+    // rt_render_medium — a homogeneous grey medium of extinction SIGMA, single-scattering albedo ALBEDO (default 1) and Henyey-Greenstein g
+    // G (default 0) in all space, a ball or a box.  --fog needs --lit and is not for --noise-target (adaptive sampling under
+    // a medium is left out); --fog-ball / --fog-box need --fog and exclude each other.
+    bool fog_on = false;
+    rt_medium_params fog;
+    rt_medium_params_init(&fog);
+    {
+        bool ball = false, box = false;
+        std::string fog_bad;
+        for (int a = 2; a < argc; ++a) {
+            const std::string arg = argv[a];
+            const char *value = a + 1 < argc ? argv[a + 1] : "";
+            char tail = 0;
+            if (arg == "--fog") {
+                fog_on = true;
+                float alb = 1.0f, g = 0.0f;
+                // one to three numbers between colons, each read to its end
+                float *into[3] = {&fog.sigma_t, &alb, &g};
+                int got = 0;
+                bool ok = *value != 0;
+                for (const char *at = value; ok; ++got) {
+                    char *end = nullptr;
+                    if (got == 3) { ok = false; break; }
+                    *into[got] = strtof(at, &end);
+                    ok = end != at && (*end == 0 || *end == ':');
+                    if (!ok || *end == 0) { ++got; break; }
+                    at = end + 1;
+                }
+                if (!ok || !(std::isfinite(fog.sigma_t) && fog.sigma_t >= 0.0f) || !(alb >= 0.0f && alb <= 1.0f) || !(std::fabs(g) <= 0.95f))
+                    fog_bad = "--fog takes SIGMA[:ALBEDO[:G]] with SIGMA >= 0 and finite, 0 <= ALBEDO <= 1 and |G| <= 0.95";
+                fog.albedo[0] = fog.albedo[1] = fog.albedo[2] = alb;
+                fog.g = g;
+            }
+            if (arg == "--fog-ball") {
+                ball = true;
+                fog.region = 1;
+                if (sscanf(value, "%f,%f,%f,%f%c", &fog.a[0], &fog.a[1], &fog.a[2], &fog.b[0], &tail) != 4 || !(fog.b[0] > 0.0f) || !std::isfinite(fog.b[0]) ||
+                    !std::isfinite(fog.a[0]) || !std::isfinite(fog.a[1]) || !std::isfinite(fog.a[2]))
+                    fog_bad = "--fog-ball takes cx,cy,cz,r with finite numbers and r > 0";
+            }
+            if (arg == "--fog-box") {
+                box = true;
+                fog.region = 2;
+                bool ok = sscanf(value, "%f,%f,%f,%f,%f,%f%c", &fog.a[0], &fog.a[1], &fog.a[2], &fog.b[0], &fog.b[1], &fog.b[2], &tail) == 6;
+                for (int k = 0; ok && k < 3; ++k) ok = std::isfinite(fog.a[k]) && std::isfinite(fog.b[k]) && fog.a[k] < fog.b[k];
+                if (!ok) fog_bad = "--fog-box takes x0,y0,z0,x1,y1,z1 with finite numbers and x0 < x1, y0 < y1, z0 < z1";
+            }
+        }
+        if ((ball || box) && !fog_on) fog_bad = "--fog-ball and --fog-box bound the medium of --fog: they need --fog SIGMA";
+        else if (ball && box) fog_bad = "--fog-ball and --fog-box exclude each other: the medium has one region";
+        else if (fog_on && !lit_on) fog_bad = "--fog puts a medium into --lit frames: it needs --lit";
+        else if (fog_on && noise_on) fog_bad = "--fog cannot be combined with --noise-target: adaptive sampling under a medium is left out";
+        if (!fog_bad.empty()) {
+            std::cerr << "rtp_main: " << fog_bad << "\n";
+            return 99;
+        }
+    }
     // extension: `--glossy`, with `--nee`, with `--env` in mode mis or light, or with `--lit`, and only with them: METAL's reflect branch
     // takes light samples too (rt_nee_params.glossy / rt_env_params.glossy = 1) — the switch of every light that is on.
     bool glossy_on = false;
@@ -386,7 +444,7 @@ int main(int argc, char *argv[]) {
                 lit.env = lit_env;
                 lit.env_params = &lit_ep;
                 rtp::gpu_render_lens(params, desc, lens, shutter, aov, denoise, nullptr, nullptr, nullptr, &lit, noise_on ? &noise : nullptr,
-                                     denoise_adaptive, &stop_rule, denoise_adaptive_temporal);
+                                     denoise_adaptive, &stop_rule, denoise_adaptive_temporal, fog_on ? &fog : nullptr);
                 rt_env_destroy(lit_env);
                 return 0;
             }

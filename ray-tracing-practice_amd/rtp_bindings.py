@@ -316,6 +316,55 @@ def lit_params(cam_close=None, lens=None, emitters=True, nee=None, env=None, env
     return p
 
 
+class MediumParams(C.Structure):
+    """rt_medium_params (include/rtp_amd.h, "participating medium"): an IN structure of the caller's size — struct_bytes is set on
+    construction; the other fields are 0 until rt_medium_params_init (medium_params()) fills the defaults."""
+    _fields_ = [("struct_bytes", C.c_uint32), ("region", C.c_int32), ("sigma_t", C.c_float), ("albedo", C.c_float * 3), ("g", C.c_float),
+                ("a", C.c_float * 3), ("b", C.c_float * 3)]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_bytes = C.sizeof(MediumParams)
+
+
+def medium_params(sigma_t=0.0, albedo=1.0, g=0.0, ball=None, box=None):
+    """rt_medium_params with the library's defaults, then: sigma_t; albedo one number or three; g; the region — ball=(cx, cy, cz, r) or
+    box=(x0, y0, z0, x1, y1, z1), neither: all space.  Nothing is checked here: the library refuses what it does not take."""
+    if ball is not None and box is not None:
+        raise RtError("rt_medium_params takes one region: ball or box")
+    p = MediumParams()
+    amd_lib().rt_medium_params_init(C.byref(p))
+    p.sigma_t = float(sigma_t)
+    alb = np.broadcast_to(np.asarray(albedo, dtype=np.float32), (3,))
+    for k in range(3):
+        p.albedo[k] = float(alb[k])
+    p.g = float(g)
+    if ball is not None:
+        v = np.asarray(ball, dtype=np.float32).ravel()
+        if v.size != 4:
+            raise RtError("rt_medium_params: ball takes four numbers (cx, cy, cz, r)")
+        p.region = 1
+        for k in range(3):
+            p.a[k] = float(v[k])
+        p.b[0] = float(v[3])
+    elif box is not None:
+        v = np.asarray(box, dtype=np.float32).ravel()
+        if v.size != 6:
+            raise RtError("rt_medium_params: box takes six numbers (x0, y0, z0, x1, y1, z1)")
+        p.region = 2
+        for k in range(3):
+            p.a[k] = float(v[k])
+            p.b[k] = float(v[3 + k])
+    return p
+
+
+def _medium_struct(medium):
+    """None → NULL (no medium); a MediumParams as it is; a dict → medium_params(**dict)."""
+    if medium is None:
+        return None
+    return C.byref(medium if isinstance(medium, MediumParams) else medium_params(**medium))
+
+
 class Env:
     """rt_env: an octahedral environment map with its sampling table on the current device.  Env(rgb) takes an (n, n, 3) array;
     Env.from_equirect(image, n) resamples a lat-long image first.  A context manager; close() destroys the object."""
@@ -434,6 +483,7 @@ RTP_AMD_SYMBOLS = [
     "rt_env_params_init", "rt_env_create", "rt_env_destroy", "rt_env_table", "rt_env_lookup", "rt_env_from_equirect", "rt_render_env",
     "rt_trace_samples_env",
     "rt_lit_params_init", "rt_render_lit", "rt_trace_samples_lit",
+    "rt_medium_params_init", "rt_render_medium", "rt_trace_samples_medium",
     "rt_render_lit_adaptive",
     "rt_denoise_spp",
     "rt_stop_params_init", "rt_render_adaptive_rule", "rt_render_lit_adaptive_rule", "rt_adaptive_judge",
@@ -573,6 +623,13 @@ def amd_lib():
                                           C.c_void_p, C.c_int32, C.POINTER(Timing)]
             lib.rt_trace_samples_lit.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(LitParams), C.c_int32, C.c_void_p, C.c_void_p,
                                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(lib, "rt_render_medium"):
+            lib.rt_medium_params_init.argtypes = [C.POINTER(MediumParams)]
+            lib.rt_medium_params_init.restype = None
+            lib.rt_render_medium.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(LitParams), C.POINTER(MediumParams), C.POINTER(Shard),
+                                             C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(Timing)]
+            lib.rt_trace_samples_medium.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(LitParams), C.POINTER(MediumParams), C.c_int32] + \
+                                                   [C.c_void_p] * 8
         if hasattr(lib, "rt_render_lit_adaptive"):
             lib.rt_render_lit_adaptive.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(LitParams), C.POINTER(AdaptiveParams),
                                                    C.POINTER(Shard), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
@@ -1502,6 +1559,47 @@ class DeviceScene:
         _check(amd_lib().rt_trace_samples_lit(self._h, C.byref(cam), C.byref(lit), n, ijs.ctypes.data, rad.ctypes.data, rays.ctypes.data,
                                               seeds.ctypes.data, ns.ctypes.data, es.ctypes.data), "rt_trace_samples_lit")
         return rad, rays, seeds, ns, es
+
+    def render_medium(self, cam, d_fb_ptr, *, medium=None, cam_close=None, lens=None, emitters=True, nee=None, env=None, env_params=None, shard=None,
+                      stream=None, sync=True, sample_first=0):
+        """rt_render_medium: rt_render_lit under a homogeneous medium (medium: None, a MediumParams or a dict of medium_params()'s
+        arguments; the other keywords are lit_params()'s).  Returns the rt_timing of this call."""
+        t = Timing()
+        self._apply_config()
+        lit = lit_params(cam_close=cam_close, lens=lens, emitters=emitters, nee=nee, env=env, env_params=env_params)
+        _check(amd_lib().rt_render_medium(self._h, C.byref(cam), C.byref(lit), _medium_struct(medium), C.byref(shard) if shard else None, sample_first,
+                                          C.c_void_p(d_fb_ptr), C.c_void_p(stream or 0), 1 if sync else 0, C.byref(t)), "rt_render_medium")
+        return t
+
+    def render_medium_to_host(self, cam, *, medium=None, cam_close=None, lens=None, emitters=True, nee=None, env=None, env_params=None, shard=None,
+                              sample_first=0):
+        """rt_render_medium through a fresh device buffer: (rows, width, 3) float32 sums and the rt_timing."""
+        lib = amd_lib()
+        rows = lib.rt_shard_rows(cam.image_height, C.byref(shard) if shard else None)
+        fb = np.empty((rows, cam.image_width, 3), dtype=np.float32)
+        d = C.c_void_p()
+        _check(lib.rt_device_alloc(fb.nbytes or 12, C.byref(d)), "rt_device_alloc")
+        try:
+            t = self.render_medium(cam, d.value, medium=medium, cam_close=cam_close, lens=lens, emitters=emitters, nee=nee, env=env,
+                                   env_params=env_params, shard=shard, sample_first=sample_first)
+            _check(lib.rt_copy_to_host(fb.ctypes.data, d, fb.nbytes), "rt_copy_to_host")
+        finally:
+            lib.rt_device_free(d)
+        return fb, t
+
+    def trace_samples_medium(self, cam, ijs, *, medium=None, cam_close=None, lens=None, emitters=True, nee=None, env=None, env_params=None):
+        """rt_trace_samples_medium: ijs (n, 3) → (radiance (n, 3), rays (n,), medium events (n,), final seeds (n,), final emitter-stream
+        seeds (n,), final environment-stream seeds (n,), final medium-stream seeds (n,))."""
+        ijs = np.ascontiguousarray(ijs, dtype=np.int32).reshape(-1, 3)
+        n = ijs.shape[0]
+        rad = np.empty((n, 3), dtype=np.float32)
+        rays, events = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
+        seeds, ns, es, ms = (np.empty(n, dtype=np.uint32) for _ in range(4))
+        lit = lit_params(cam_close=cam_close, lens=lens, emitters=emitters, nee=nee, env=env, env_params=env_params)
+        _check(amd_lib().rt_trace_samples_medium(self._h, C.byref(cam), C.byref(lit), _medium_struct(medium), n, ijs.ctypes.data, rad.ctypes.data,
+                                                 rays.ctypes.data, events.ctypes.data, seeds.ctypes.data, ns.ctypes.data, es.ctypes.data,
+                                                 ms.ctypes.data), "rt_trace_samples_medium")
+        return rad, rays, events, seeds, ns, es, ms
 
     def last_kernel_ms(self):
         ms = C.c_float()
