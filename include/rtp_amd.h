@@ -660,6 +660,60 @@ rt_status rt_denoise_temporal_spp(const float *d_fb_sum, const int32_t *d_spp, c
                                   const rt_denoise_params *params, const void *d_history_prev, void *d_history_next, uint64_t history_bytes,
                                   void *d_workspace, uint64_t workspace_bytes, float *d_out, void *hip_stream);
 
+/* ---- a history-aware stopping rule: the adaptive calls with a prior from rt_denoise_temporal_spp's history ---------
+ * In an animation denoised by rt_denoise_temporal_spp a pixel whose blended estimate is already quiet need not be sampled to the
+ * frame's own target again.  rt_adaptive_prior turns the history the next rt_denoise_temporal_spp will read into a PRIOR per pixel
+ * of the frame about to be rendered, (ch, vh): the samples behind the pixel's reprojected history and the variance of its mean
+ * luminance in the frame's own space.  The _prior calls are the _rule calls whose rules compare ve, the variance that
+ * rt_denoise_temporal_spp's blend will carry for the pixel (before its spatial filter), where the _rule calls compare the variance
+ * vm of the frame's own mean.  Pinhole frames: the reprojection is a pinhole's.
+ *
+ * rt_adaptive_prior covers a whole frame of cam (HOST memory: image size and reprojection camera; samples_per_pixel ignored).  aov
+ * holds the sums of rt_render_aov[_samples] for that frame at a uniform aov_samples = A per pixel; all five buffers are required.
+ * d_prior receives 2 floats per pixel.  Arithmetic by the rules of the denoise sections (float32 in the order written, nothing fused,
+ * correctly rounded division and sqrtf), invA = (float)(1.0 / (double)A):
+ *   A pixel with hit_count == 0: (0, 0).
+ *   A hit pixel p = (x, y): the unit normal n and the depth z are rt_denoise's prepass, prim = first_prim_p,
+ *     d_k = fmaxf(albedo_sum_k * invA, 1e-3f), dl = lum(d_0, d_1, d_2).
+ *     X, reach2, the projection, the four taps in their order and the four conditions of a tap that counts are rt_denoise_temporal's.
+ *     The history is taken only when d_history_prev is non-NULL, has magic 0x32485452, this width and height and the mode word 2
+ *     (written with moments); anything else — NULL, all zero, another size, rt_denoise_temporal's magic, mode 1 — is EMPTY.
+ *     The taps that count accumulate, from 0: W += w, SC += w * cnt_q, SV += w * V_q.
+ *     With a history taken and W >= min_weight: ch = SC / W, vh = (SV / W) * (dl * dl) — rt_denoise_spp's v = vm / (dl * dl) undone.
+ *     Otherwise (0, 0).
+ * Reads the moments, position and normal planes of the history, never the colour plane.  Enqueues one launch on hip_stream: no
+ * allocation, no synchronisation.  The checks are rt_denoise_temporal_spp's, in its order and with its codes, under this call's name
+ * and all before any HIP call: a NULL aov, cam or d_prior, a missing AOV buffer, width or height below 1, A outside 1 … 65536
+ * (RT_ERR_INVALID_ARG); more than 2^24 pixels (RT_ERR_UNSUPPORTED); with a history given, history_bytes below
+ * rt_denoise_history_bytes; a history that is not 16-byte aligned; d_prior (8 bytes per pixel) overlapping the history or an AOV buffer
+ * (RT_ERR_INVALID_ARG). */
+rt_status rt_adaptive_prior(const rt_aov_buffers *aov, int32_t aov_samples, const rt_camera_data *cam, const void *d_history_prev,
+                            uint64_t history_bytes, float *d_prior, void *hip_stream);
+/* The _rule calls with a prior: their arguments, then d_prior — DEVICE memory, 2 floats (ch, vh) per LOCAL pixel, compacted like d_spp
+ * (under a shard the caller supplies the part's rows of a whole-frame prior).  d_prior == NULL: the _rule call bit for bit, the same
+ * kernels and launches.  At a judgement of a pixel with n samples, nf = (float)n, t = threshold (float32, in this order, nothing fused):
+ *     mean = S1 / nf;   var = fmaxf(0, (S2 - S1 * mean) / (float)(n - 1));   vm = var / nf;
+ *     if (ch > 0 && vh >= 0) { s = ch + nf;  a = nf / s;  if (!(a >= 0.2f)) a = 0.2f;  b = 1 - a;  ve = (b * b) * vh + (a * a) * vm; }
+ *     else ve = vm;
+ *     rule 0:  goes_on = n + batch_spp <= max_spp && (t == 0 || ve > (t * t) * (mean * mean + 1e-4f))
+ *     rule 1:  noisy_p = ve > (t * t) * (mean + 0.01f);  the window, c_p and goes_on_p are rt_render_adaptive_rule's
+ * a and b are rt_denoise_temporal_spp's blend weights.  A NaN ch or vh fails the test: the pixel is judged by its own samples.  A prior
+ * of all zeros gives ve = vm, the expression the _rule calls compare: that frame is the _rule call's bit for bit.  Everything else is
+ * the _rule call's: statistics, rounds, R, the counts min_spp + k * batch_spp, a pixel that stops never resumes, the per-pixel parity
+ * promise (each pixel bit-identical to rt_render / rt_render_lit at its own count), threshold = 0, and the max_depth <= 0 case, where
+ * the prior is not read.  Checks: the _rule call's, with its messages; right after its stop checks, and so before anything is
+ * enqueued, RT_ERR_INVALID_ARG when d_prior (8 bytes per local pixel, as cam and shard give their number) overlaps d_fb_sum, d_spp or
+ * d_moments — the message names the _prior call. */
+rt_status rt_render_adaptive_prior(rt_scene *scene, const rt_camera_data *cam, const rt_shard *shard, const rt_adaptive_params *params,
+                                   const rt_stop_params *stop, float *d_fb_sum, int32_t *d_spp, float *d_moments, void *hip_stream,
+                                   int32_t sync, rt_timing *timing, const float *d_prior);
+/* (rt_render_lit_adaptive_prior, the same on the lit path, is declared beside rt_render_lit_adaptive_rule below) */
+/* rt_adaptive_judge with a prior (tests): its arguments, then d_prior (2 floats per pixel of the buffer; NULL: rt_adaptive_judge's
+ * launches).  Its checks under this call's name, and RT_ERR_INVALID_ARG when d_prior overlaps d_goes_on_out. */
+rt_status rt_adaptive_judge_prior(int32_t width, int32_t rows, const rt_shard *shard, const rt_adaptive_params *params,
+                                  const rt_stop_params *stop, int32_t n, const float *d_moments, const uint8_t *d_going_on_in,
+                                  uint8_t *d_goes_on_out, void *hip_stream, const float *d_prior);
+
 /* ---- thin-lens depth of field and shutter motion blur ---------------------------------------------------------
  * rt_render_samples / rt_render_aov_samples with a camera that has a lens and / or an open shutter.  Pixel (i, j), sample s; the
  * draws come from the same RNG as the pinhole's, and the path goes on from the state they leave:
@@ -1036,6 +1090,11 @@ rt_status rt_render_lit_adaptive(rt_scene *scene, const rt_camera_data *cam_open
 rt_status rt_render_lit_adaptive_rule(rt_scene *scene, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_adaptive_params *params,
                                       const rt_stop_params *stop, const rt_shard *shard, int32_t sample_first, float *d_fb_sum, int32_t *d_spp,
                                       float *d_moments, void *hip_stream, int32_t sync, rt_timing *timing);
+/* rt_render_lit_adaptive_rule with a prior ("a history-aware stopping rule" above): its arguments, then d_prior. */
+rt_status rt_render_lit_adaptive_prior(rt_scene *scene, const rt_camera_data *cam_open, const rt_lit_params *lit,
+                                       const rt_adaptive_params *params, const rt_stop_params *stop, const rt_shard *shard,
+                                       int32_t sample_first, float *d_fb_sum, int32_t *d_spp, float *d_moments, void *hip_stream,
+                                       int32_t sync, rt_timing *timing, const float *d_prior);
 
 /* ---- participating medium ---------------------------------------------------------------------------------------
  * rt_render_lit's estimator — lens, shutter, the emitter table with mis / sample_planes / select / glossy, the environment with its mode

@@ -159,6 +159,78 @@ __global__ void __launch_bounds__(kAdaptBlock) adaptive_select_near_kernel(const
     if (on) list_out[block_base + wave_total[wave] + at] = q;
 }
 
+// ---- the rules with a prior (rtp_amd.h, rt_render_adaptive_prior; DESIGN.md §26).  prior: (ch, vh) per local pixel, the samples behind
+// the pixel's reprojected history and the variance of its mean luminance (rt_adaptive_prior).  The rules compare ve, the variance
+// rt_denoise_temporal_spp's blend of that history with this frame will carry, where the kernels above compare vm = var / n.  They are
+// kernels of their own, not a template parameter of those above, so that those keep their arguments and their instructions.
+
+// ve of a pixel with n samples (nf = (float)n) whose own samples give vm; a prior that is not (ch > 0, vh >= 0) — a NaN included — is none
+__device__ __forceinline__ float adapt_blended_variance(float vm, float nf, float ch, float vh) {
+    if (!(ch > 0.0f && vh >= 0.0f)) return vm;
+    const float s = ch + nf;
+    float a = nf / s;
+    if (!(a >= 0.2f)) a = 0.2f;
+    const float b = 1.0f - a;
+    return (b * b) * vh + (a * a) * vm;
+}
+
+// mean and ve of local pixel q with n samples
+__device__ __forceinline__ float adapt_prior_variance(const float *mom, const float *prior, uint32_t q, int32_t n, float &mean) {
+    const float s1 = mom[2 * (size_t)q], s2 = mom[2 * (size_t)q + 1], nf = (float)n;
+    mean = s1 / nf;
+    const float var = fmaxf(0.0f, (s2 - s1 * mean) / (float)(n - 1));
+    return adapt_blended_variance(var / nf, nf, prior[2 * (size_t)q], prior[2 * (size_t)q + 1]);
+}
+
+// adaptive_select_kernel with a prior (rule 0)
+template <bool kAll>
+__global__ void __launch_bounds__(kAdaptBlock) adaptive_select_prior_kernel(const float *mom, const float *prior, int32_t *spp, uint32_t num_pixels,
+                                                                            const uint32_t *list_in, const uint32_t *count_in, uint32_t *list_out,
+                                                                            uint32_t *count_out, int32_t n, int32_t batch, int32_t max_spp, float t) {
+    __shared__ uint32_t wave_total[kAdaptBlock / kWave], block_base;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const uint32_t i = blockIdx.x * (uint32_t)kAdaptBlock + threadIdx.x;
+    const uint32_t listed = kAll ? num_pixels : *count_in;
+    bool on = false;
+    uint32_t q = 0;
+    if (i < listed) {
+        q = kAll ? i : list_in[i];
+        if (n + batch <= max_spp) {
+            on = t == 0.0f;
+            if (!on) {
+                float mean;
+                const float ve = adapt_prior_variance(mom, prior, q, n, mean);
+                on = ve > (t * t) * (mean * mean + 1e-4f);
+            }
+        }
+        if (kAll || on) spp[q] = on ? n + batch : n;
+    }
+    const uint64_t m = __ballot(on);
+    const uint32_t at = (uint32_t)lane_rank(m);
+    if (lane == 0) wave_total[wave] = (uint32_t)__popcll(m);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t sum = 0;
+        for (int w = 0; w < kAdaptBlock / kWave; ++w) { const uint32_t c = wave_total[w]; wave_total[w] = sum; sum += c; }
+        block_base = sum ? atomicAdd(count_out, sum) : 0u;
+    }
+    __syncthreads();
+    if (on) list_out[block_base + wave_total[wave] + at] = q;
+}
+
+// adaptive_flag_kernel with a prior (rule 1): noisy_p compares ve.  adaptive_select_near_kernel reads the bytes as it is.
+template <bool kAll>
+__global__ void __launch_bounds__(kAdaptBlock) adaptive_flag_prior_kernel(const float *mom, const float *prior, uint8_t *flag, uint32_t num_pixels,
+                                                                          const uint32_t *list_in, const uint32_t *count_in, int32_t n, float t) {
+    const uint32_t i = blockIdx.x * (uint32_t)kAdaptBlock + threadIdx.x;
+    const uint32_t listed = kAll ? num_pixels : *count_in;
+    if (i >= listed) return;
+    const uint32_t q = kAll ? i : list_in[i];
+    float mean;
+    const float ve = adapt_prior_variance(mom, prior, q, n, mean);
+    flag[q] = ve > (t * t) * (mean + 0.01f) ? (uint8_t)1 : (uint8_t)0;
+}
+
 // The list of a round → the work indices of its trace launch, q * batch + slot for slot = 0 … batch - 1 (the pass's own numbering:
 // local pixel * pass_count + slot), and their number.  count * batch stays below 2^31 - 4096 (rt_render_adaptive checks
 // num_pixels * batch).  Grid-stride: a round whose list is empty costs one short launch.

@@ -1883,7 +1883,7 @@ rt_status adaptive_no_depth(const rt_adaptive_params &a, float *mom, int32_t *d_
 // One judgement of the pixels with n samples — those of list_in (null: every local pixel) — into list_out / count_out and the counts.
 // Rule 0: adaptive_select_kernel.  Rule 1 (flag: one byte per pixel, W: the buffer's shape): the flag kernel, then the select kernel
 // that reads the windows; with threshold 0 nothing is judged noisy or quiet — every pixel goes on while the cap allows — which is rule
-// 0's launch.
+// 0's launch.  prior (null: none): the prior variants of the select and flag kernels (rt_render_adaptive_prior), which compare ve.
 rtk::AdaptWindow adapt_window(int32_t width, int32_t rows, int32_t band_rows, int32_t num_parts) {
     rtk::AdaptWindow W;
     W.width = (uint32_t)width;
@@ -1892,12 +1892,32 @@ rtk::AdaptWindow adapt_window(int32_t width, int32_t rows, int32_t band_rows, in
     W.banded = num_parts > 1 ? 1u : 0u;
     return W;
 }
-rt_status adaptive_judge(const rt_adaptive_params &a, int32_t rule, const float *mom, int32_t *d_spp, uint8_t *flag, const rtk::AdaptWindow &W,
-                         uint32_t num_pixels, const uint32_t *list_in, const uint32_t *count_in, uint32_t *list_out, uint32_t *count_out, int32_t n,
-                         hipStream_t stream) {
+rt_status adaptive_judge(const rt_adaptive_params &a, int32_t rule, const float *mom, const float *prior, int32_t *d_spp, uint8_t *flag,
+                         const rtk::AdaptWindow &W, uint32_t num_pixels, const uint32_t *list_in, const uint32_t *count_in, uint32_t *list_out,
+                         uint32_t *count_out, int32_t n, hipStream_t stream) {
     const dim3 pix_grid((num_pixels + rtk::kAdaptBlock - 1) / rtk::kAdaptBlock), pix_block(rtk::kAdaptBlock);
     const int32_t batch = a.batch_spp;
-    if (rule != 1 || a.threshold == 0.0f) {
+    if (prior && (rule != 1 || a.threshold == 0.0f)) {
+        if (!list_in)
+            hipLaunchKernelGGL(rtk::adaptive_select_prior_kernel<true>, pix_grid, pix_block, 0, stream, mom, prior, d_spp, num_pixels,
+                               (const uint32_t *)nullptr, (const uint32_t *)nullptr, list_out, count_out, n, batch, a.max_spp, a.threshold);
+        else
+            hipLaunchKernelGGL(rtk::adaptive_select_prior_kernel<false>, pix_grid, pix_block, 0, stream, mom, prior, d_spp, num_pixels, list_in, count_in,
+                               list_out, count_out, n, batch, a.max_spp, a.threshold);
+    } else if (prior) {
+        if (!list_in)
+            hipLaunchKernelGGL(rtk::adaptive_flag_prior_kernel<true>, pix_grid, pix_block, 0, stream, mom, prior, flag, num_pixels, (const uint32_t *)nullptr,
+                               (const uint32_t *)nullptr, n, a.threshold);
+        else
+            hipLaunchKernelGGL(rtk::adaptive_flag_prior_kernel<false>, pix_grid, pix_block, 0, stream, mom, prior, flag, num_pixels, list_in, count_in, n,
+                               a.threshold);
+        if (!list_in)
+            hipLaunchKernelGGL(rtk::adaptive_select_near_kernel<true>, pix_grid, pix_block, 0, stream, (const uint8_t *)flag, d_spp, num_pixels, W,
+                               (const uint32_t *)nullptr, (const uint32_t *)nullptr, list_out, count_out, n, batch, a.max_spp);
+        else
+            hipLaunchKernelGGL(rtk::adaptive_select_near_kernel<false>, pix_grid, pix_block, 0, stream, (const uint8_t *)flag, d_spp, num_pixels, W, list_in,
+                               count_in, list_out, count_out, n, batch, a.max_spp);
+    } else if (rule != 1 || a.threshold == 0.0f) {
         if (!list_in)
             hipLaunchKernelGGL(rtk::adaptive_select_kernel<true>, pix_grid, pix_block, 0, stream, mom, d_spp, num_pixels, (const uint32_t *)nullptr,
                                (const uint32_t *)nullptr, list_out, count_out, n, batch, a.max_spp, a.threshold);
@@ -1918,8 +1938,8 @@ rt_status adaptive_judge(const rt_adaptive_params &a, int32_t rule, const float 
     return RT_OK;
 }
 template <class Trace>
-rt_status adaptive_rounds(rt_scene *sc, const rt_adaptive_params &a, int32_t rule, rtk::KParams &P, float *mom, int32_t *d_spp, uint32_t num_pixels,
-                          int32_t first, hipStream_t stream, Trace trace) {
+rt_status adaptive_rounds(rt_scene *sc, const rt_adaptive_params &a, int32_t rule, rtk::KParams &P, float *mom, const float *prior, int32_t *d_spp,
+                          uint32_t num_pixels, int32_t first, hipStream_t stream, Trace trace) {
     const int32_t batch = a.batch_spp, rounds = (a.max_spp - a.min_spp) / a.batch_spp;
     const dim3 pix_grid((num_pixels + rtk::kAdaptBlock - 1) / rtk::kAdaptBlock), pix_block(rtk::kAdaptBlock);
     const uint64_t expand_items = (uint64_t)num_pixels * (uint64_t)batch;
@@ -1930,7 +1950,7 @@ rt_status adaptive_rounds(rt_scene *sc, const rt_adaptive_params &a, int32_t rul
     rt_status st;
     HIP_TRY(hipMemsetAsync(counters, 0, (size_t)3 * (size_t)(rounds + 1) * sizeof(uint32_t), stream));
     int32_t n = a.min_spp;
-    if ((st = adaptive_judge(a, rule, mom, d_spp, sc->adapt_flag, W, num_pixels, nullptr, nullptr, lists[0], counters, n, stream)) != RT_OK) return st;
+    if ((st = adaptive_judge(a, rule, mom, prior, d_spp, sc->adapt_flag, W, num_pixels, nullptr, nullptr, lists[0], counters, n, stream)) != RT_OK) return st;
     if (rounds > 0) {
         bind_slab(sc, P, num_pixels, batch);
         P.pass_count = batch;
@@ -1953,18 +1973,32 @@ rt_status adaptive_rounds(rt_scene *sc, const rt_adaptive_params &a, int32_t rul
                            (const uint32_t *)nullptr, 0u, 0.0f, 0.0f, 0.0f);
         n += batch;
         HIP_TRY(hipGetLastError());
-        if (r < rounds && (st = adaptive_judge(a, rule, mom, d_spp, sc->adapt_flag, W, num_pixels, list, listed, lists[r & 1], counters + 3 * r, n, stream)) != RT_OK)
+        if (r < rounds && (st = adaptive_judge(a, rule, mom, prior, d_spp, sc->adapt_flag, W, num_pixels, list, listed, lists[r & 1], counters + 3 * r, n, stream)) != RT_OK)
             return st;
     }
     return RT_OK;
 }
+// The check of the _prior calls (what: the new call's name), right after the stop checks: d_prior (8 bytes per local pixel; null: none)
+// shares no byte with what the call writes.  The local pixel count is what cam and shard give without a scene; where they give none (a
+// null camera, an image or a part without pixels) a later check refuses the call or the call has nothing to do.
+rt_status prior_check(const char *what, const float *d_prior, const rt_camera_data *cam, const rt_shard *shard, const float *d_fb_sum,
+                      const int32_t *d_spp, const float *d_moments) {
+    if (!d_prior || !cam || cam->image_width <= 0) return RT_OK;
+    const uint64_t num_pixels = (uint64_t)rt_shard_rows(cam->image_height, shard) * (uint64_t)cam->image_width;
+    const uintptr_t lo = (uintptr_t)d_prior, hi = lo + (uintptr_t)num_pixels * 8;
+    const auto shares = [&](const void *ptr, uintptr_t bytes) { return ptr && lo < (uintptr_t)ptr + bytes && (uintptr_t)ptr < hi; };
+    if (shares(d_fb_sum, (uintptr_t)num_pixels * 12) || shares(d_spp, (uintptr_t)num_pixels * 4) || shares(d_moments, (uintptr_t)num_pixels * 8))
+        return fail(RT_ERR_INVALID_ARG, std::string(what) + ": d_prior overlaps d_fb_sum, d_spp or d_moments");
+    return RT_OK;
+}
 rt_status adaptive_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shard, const rt_adaptive_params *params, const rt_stop_params *stop,
-                        float *d_fb_sum, int32_t *d_spp, float *d_moments, void *hip_stream, int32_t sync, rt_timing *timing) {
+                        const float *d_prior, float *d_fb_sum, int32_t *d_spp, float *d_moments, void *hip_stream, int32_t sync, rt_timing *timing) {
     // ---- 1. every check before anything is enqueued
     rt_adaptive_params a;
     int32_t rule;
     if (const rt_status cs = adaptive_check("rt_render_adaptive", params, a)) return cs;
     if (const rt_status cs = stop_check("rt_render_adaptive", stop, rule)) return cs;
+    if (const rt_status cs = prior_check("rt_render_adaptive_prior", d_prior, cam, shard, d_fb_sum, d_spp, d_moments)) return cs;
     if (!cam) return fail(RT_ERR_INVALID_ARG, "null scene or camera");
     rt_camera_data base = *cam;
     base.samples_per_pixel = a.min_spp;
@@ -2012,7 +2046,7 @@ rt_status adaptive_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard 
     const void *exact = rewalk_kernel(plan);
     const int wgs = grid_for(sc, plan.exact, num_pixels, batch);
     reservation(num_pixels * (uint32_t)batch, (uint64_t)wgs * (rtk::kBlock / rtk::kWave), P.full_chunk, P.full_taper);
-    st = adaptive_rounds(sc, a, rule, P, mom, d_spp, num_pixels, a.min_spp, stream,
+    st = adaptive_rounds(sc, a, rule, P, mom, d_prior, d_spp, num_pixels, a.min_spp, stream,
                          [&](const rtk::KParams &KP) { return launch(exact, (uint32_t)rtk::kBlock, wgs, plan.exact.lds_bytes, stream, KP); });
     if (st != RT_OK) return st;
     if ((st = clock.stop(stream)) != RT_OK) return st;
@@ -2207,7 +2241,7 @@ void rt_adaptive_params_init(rt_adaptive_params *p) {
 
 rt_status rt_render_adaptive(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shard, const rt_adaptive_params *params, float *d_fb_sum,
                              int32_t *d_spp, float *d_moments, void *hip_stream, int32_t sync, rt_timing *timing) {
-    return adaptive_impl(sc, cam, shard, params, nullptr, d_fb_sum, d_spp, d_moments, hip_stream, sync, timing);
+    return adaptive_impl(sc, cam, shard, params, nullptr, nullptr, d_fb_sum, d_spp, d_moments, hip_stream, sync, timing);
 }
 void rt_stop_params_init(rt_stop_params *p) {
     if (!p) return;
@@ -2217,7 +2251,12 @@ void rt_stop_params_init(rt_stop_params *p) {
 rt_status rt_render_adaptive_rule(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shard, const rt_adaptive_params *params,
                                   const rt_stop_params *stop, float *d_fb_sum, int32_t *d_spp, float *d_moments, void *hip_stream, int32_t sync,
                                   rt_timing *timing) {
-    return adaptive_impl(sc, cam, shard, params, stop, d_fb_sum, d_spp, d_moments, hip_stream, sync, timing);
+    return adaptive_impl(sc, cam, shard, params, stop, nullptr, d_fb_sum, d_spp, d_moments, hip_stream, sync, timing);
+}
+rt_status rt_render_adaptive_prior(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shard, const rt_adaptive_params *params,
+                                   const rt_stop_params *stop, float *d_fb_sum, int32_t *d_spp, float *d_moments, void *hip_stream, int32_t sync,
+                                   rt_timing *timing, const float *d_prior) {
+    return adaptive_impl(sc, cam, shard, params, stop, d_prior, d_fb_sum, d_spp, d_moments, hip_stream, sync, timing);
 }
 
 
@@ -3044,9 +3083,9 @@ rt_status rt_render_lit(rt_scene *sc, const rt_camera_data *cam_open, const rt_l
 // ---- rt_render_lit_adaptive (rtp_amd.h): rt_render_adaptive's rule and rounds on rt_render_lit's estimator.  The min_spp
 // frame is render_light_impl's passes with the moments; the rounds are rt_render_adaptive's (adaptive_rounds) with the list variant of
 // the frame's kernel as their trace launch.  Every round is enqueued up front; the light is made once.
-rt_status rt_render_lit_adaptive_rule(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_adaptive_params *params,
-                                      const rt_stop_params *stop, const rt_shard *shard, int32_t sample_first, float *d_fb_sum, int32_t *d_spp,
-                                      float *d_moments, void *hip_stream, int32_t sync, rt_timing *timing) {
+rt_status rt_render_lit_adaptive_prior(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_adaptive_params *params,
+                                       const rt_stop_params *stop, const rt_shard *shard, int32_t sample_first, float *d_fb_sum, int32_t *d_spp,
+                                       float *d_moments, void *hip_stream, int32_t sync, rt_timing *timing, const float *d_prior) {
     // ---- 1. every check before anything is enqueued
     const char *what = "rt_render_lit_adaptive";
     rt_adaptive_params a;
@@ -3054,6 +3093,7 @@ rt_status rt_render_lit_adaptive_rule(rt_scene *sc, const rt_camera_data *cam_op
     rt_status st = adaptive_check(what, params, a);
     if (st != RT_OK) return st;
     if ((st = stop_check(what, stop, rule)) != RT_OK) return st;
+    if ((st = prior_check("rt_render_lit_adaptive_prior", d_prior, cam_open, shard, d_fb_sum, d_spp, d_moments)) != RT_OK) return st;
     LitSetup S;
     if ((st = lit_setup(what, cam_open, lit, S)) != RT_OK) return st;
     const int32_t batch = a.batch_spp, rounds = (a.max_spp - a.min_spp) / a.batch_spp;
@@ -3113,7 +3153,7 @@ rt_status rt_render_lit_adaptive_rule(rt_scene *sc, const rt_camera_data *cam_op
             grid = light_grid(sc->num_cus * light_wgs_per_cu(list_kernel), num_pixels * (uint32_t)batch);
             t.num_workgroups = (uint32_t)grid;
         }
-        st = adaptive_rounds(sc, a, rule, P, mom, d_spp, num_pixels, sample_first + a.min_spp, stream,
+        st = adaptive_rounds(sc, a, rule, P, mom, d_prior, d_spp, num_pixels, sample_first + a.min_spp, stream,
                              [&](const rtk::KParams &KP) { return launch(list_kernel, (uint32_t)rtk::kLightBlock, grid, 0, stream, KP, &T, &S.C); });
         if (st != RT_OK) return st;
         if ((st = clock.stop(stream)) != RT_OK) return st;
@@ -3130,6 +3170,12 @@ rt_status rt_render_lit_adaptive_rule(rt_scene *sc, const rt_camera_data *cam_op
     });
 }
 
+rt_status rt_render_lit_adaptive_rule(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_adaptive_params *params,
+                                      const rt_stop_params *stop, const rt_shard *shard, int32_t sample_first, float *d_fb_sum, int32_t *d_spp,
+                                      float *d_moments, void *hip_stream, int32_t sync, rt_timing *timing) {
+    return rt_render_lit_adaptive_prior(sc, cam_open, lit, params, stop, shard, sample_first, d_fb_sum, d_spp, d_moments, hip_stream, sync, timing, nullptr);
+}
+
 rt_status rt_render_lit_adaptive(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_adaptive_params *params,
                                  const rt_shard *shard, int32_t sample_first, float *d_fb_sum, int32_t *d_spp, float *d_moments, void *hip_stream,
                                  int32_t sync, rt_timing *timing) {
@@ -3138,26 +3184,30 @@ rt_status rt_render_lit_adaptive(rt_scene *sc, const rt_camera_data *cam_open, c
 
 // The probe of the stopping rules (rtp_amd.h): one judgement over caller-made moments and a going-on mask, through adaptive_judge — the
 // launches of the rounds.  Test infrastructure: it allocates, copies and waits.
-rt_status rt_adaptive_judge(int32_t width, int32_t rows, const rt_shard *shard, const rt_adaptive_params *params, const rt_stop_params *stop, int32_t n,
-                            const float *d_moments, const uint8_t *d_going_on_in, uint8_t *d_goes_on_out, void *hip_stream) {
-    const char *what = "rt_adaptive_judge";
+// (what: the call's name, which every refusal starts with; d_prior: rt_adaptive_judge_prior's, null for none)
+static rt_status judge_impl(const char *what, int32_t width, int32_t rows, const rt_shard *shard, const rt_adaptive_params *params,
+                            const rt_stop_params *stop, int32_t n, const float *d_moments, const uint8_t *d_going_on_in, uint8_t *d_goes_on_out,
+                            void *hip_stream, const float *d_prior) {
+    const std::string w(what);
     rt_adaptive_params a;
     int32_t rule;
     rt_status st = adaptive_check(what, params, a);
     if (st != RT_OK) return st;
     if (stop) {
-        if (stop->struct_bytes < 8) return fail(RT_ERR_INVALID_ARG, "rt_adaptive_judge: rt_stop_params struct_bytes below 8");
-        if (stop->rule != 0 && stop->rule != 1) return fail(RT_ERR_INVALID_ARG, "rt_adaptive_judge: rule outside 0 … 1");
+        if (stop->struct_bytes < 8) return fail(RT_ERR_INVALID_ARG, w + ": rt_stop_params struct_bytes below 8");
+        if (stop->rule != 0 && stop->rule != 1) return fail(RT_ERR_INVALID_ARG, w + ": rule outside 0 … 1");
     }
     rule = stop ? stop->rule : 0;
-    if (width < 1 || rows < 1) return fail(RT_ERR_INVALID_ARG, "rt_adaptive_judge: width or rows below 1");
-    if ((uint64_t)width * (uint64_t)rows > (1u << 24)) return fail(RT_ERR_UNSUPPORTED, "rt_adaptive_judge: more than 2^24 pixels");
-    if (n < 2) return fail(RT_ERR_INVALID_ARG, "rt_adaptive_judge: n below 2");
+    if (width < 1 || rows < 1) return fail(RT_ERR_INVALID_ARG, w + ": width or rows below 1");
+    if ((uint64_t)width * (uint64_t)rows > (1u << 24)) return fail(RT_ERR_UNSUPPORTED, w + ": more than 2^24 pixels");
+    if (n < 2) return fail(RT_ERR_INVALID_ARG, w + ": n below 2");
     if (shard && shard->num_parts > 1 && (shard->part < 0 || shard->part >= shard->num_parts || shard->band_rows <= 0))
-        return fail(RT_ERR_INVALID_ARG, "rt_adaptive_judge: bad shard");
-    if (!d_moments || !d_goes_on_out) return fail(RT_ERR_INVALID_ARG, "rt_adaptive_judge: null moments or output");
+        return fail(RT_ERR_INVALID_ARG, w + ": bad shard");
+    if (!d_moments || !d_goes_on_out) return fail(RT_ERR_INVALID_ARG, w + ": null moments or output");
     const hipStream_t stream = (hipStream_t)hip_stream;
     const uint32_t num_pixels = (uint32_t)width * (uint32_t)rows;
+    if (d_prior && (uintptr_t)d_prior < (uintptr_t)d_goes_on_out + num_pixels && (uintptr_t)d_goes_on_out < (uintptr_t)d_prior + (uintptr_t)num_pixels * 8)
+        return fail(RT_ERR_INVALID_ARG, w + ": d_prior overlaps d_goes_on_out");
     rt_shard s;
     normalise_shard(shard, rows, s);
     const rtk::AdaptWindow W = adapt_window(width, rows, s.band_rows, s.num_parts);
@@ -3183,19 +3233,19 @@ rt_status rt_adaptive_judge(int32_t width, int32_t rows, const rt_shard *shard, 
         HIP_TRY(hipMemsetAsync(words, 0, num_words * sizeof(uint32_t) + num_pixels, stream));
         if (!list.empty()) HIP_TRY(hipMemcpyAsync(list_in, list.data(), list.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
         HIP_TRY(hipMemcpyAsync(counts, host_counts, sizeof(host_counts), hipMemcpyHostToDevice, stream));
-        if ((st = adaptive_judge(a, rule, d_moments, spp, flag, W, num_pixels, all ? nullptr : list_in, all ? nullptr : counts, list_out, counts + 1, n,
+        if ((st = adaptive_judge(a, rule, d_moments, d_prior, spp, flag, W, num_pixels, all ? nullptr : list_in, all ? nullptr : counts, list_out, counts + 1, n,
                                  stream)) != RT_OK)
             return st;
         uint32_t kept = 0;
         HIP_TRY(hipMemcpyAsync(&kept, counts + 1, sizeof(kept), hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipStreamSynchronize(stream));
-        if (kept > num_pixels) return fail(RT_ERR_HIP, "rt_adaptive_judge: the list is longer than the image");
+        if (kept > num_pixels) return fail(RT_ERR_HIP, w + ": the list is longer than the image");
         std::vector<uint32_t> out(kept);
         if (kept) HIP_TRY(hipMemcpyAsync(out.data(), list_out, kept * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipStreamSynchronize(stream));
         std::fill(mask.begin(), mask.end(), (uint8_t)0);
         for (const uint32_t q : out) {
-            if (q >= num_pixels) return fail(RT_ERR_HIP, "rt_adaptive_judge: a listed pixel outside the image");
+            if (q >= num_pixels) return fail(RT_ERR_HIP, w + ": a listed pixel outside the image");
             mask[q] = 1;
         }
         HIP_TRY(hipMemcpyAsync(d_goes_on_out, mask.data(), num_pixels, hipMemcpyHostToDevice, stream));
@@ -3205,6 +3255,15 @@ rt_status rt_adaptive_judge(int32_t width, int32_t rows, const rt_shard *shard, 
     st = body();
     (void)hipFree(words);
     return st;
+}
+rt_status rt_adaptive_judge(int32_t width, int32_t rows, const rt_shard *shard, const rt_adaptive_params *params, const rt_stop_params *stop, int32_t n,
+                            const float *d_moments, const uint8_t *d_going_on_in, uint8_t *d_goes_on_out, void *hip_stream) {
+    return judge_impl("rt_adaptive_judge", width, rows, shard, params, stop, n, d_moments, d_going_on_in, d_goes_on_out, hip_stream, nullptr);
+}
+rt_status rt_adaptive_judge_prior(int32_t width, int32_t rows, const rt_shard *shard, const rt_adaptive_params *params, const rt_stop_params *stop,
+                                  int32_t n, const float *d_moments, const uint8_t *d_going_on_in, uint8_t *d_goes_on_out, void *hip_stream,
+                                  const float *d_prior) {
+    return judge_impl("rt_adaptive_judge_prior", width, rows, shard, params, stop, n, d_moments, d_going_on_in, d_goes_on_out, hip_stream, d_prior);
 }
 
 rt_status rt_trace_samples_lit(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, int32_t n, const int32_t *ijs, float *radiance,

@@ -33,6 +33,9 @@
 // magic of its own, the use of moments in the header's fourth word, the accumulated count in position.w and the propagated variance
 // in normal.w.  With one iteration the step is first and last at once: denoise_step_spp_feedback.  The reprojection and the tap loop
 // are one text (rt_denoise_reproject.inc) expanded in denoise_temporal and in denoise_temporal_spp, which hook their sums and blend in.
+//
+// rt_adaptive_prior is one kernel, adaptive_prior: that text a third time, over the frame's AOVs instead of a workspace,
+// keeping the reprojected count and variance of a history of rt_denoise_temporal_spp for the stopping rule of the next adaptive frame.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -474,6 +477,58 @@ __global__ __launch_bounds__(256) void denoise_temporal_spp(Image im, rt_camera_
     }
 }
 
+// rt_adaptive_prior: what the history holds for each pixel of the frame about to be rendered — the samples behind it
+// (ch) and the variance of its mean luminance in the frame's own space (vh) — for the stopping rules of the _prior calls.  The frame's
+// AOVs stand in for the prepass (n, z, d as denoise_prepass_spp makes them); the reprojection is denoise_temporal_spp's
+// (rt_denoise_reproject.inc) with a third set of hooks that keeps cnt and V alone: nothing is blended, so the colour plane's loads and
+// the sums over it are dead and the compiler drops them.  Reads the moments, normal and position planes; writes 2 floats per pixel.
+__global__ __launch_bounds__(256) void adaptive_prior(Image im, rt_camera_data cam, Inputs in, const int32_t *first_prim, float inv_aov,
+                                                      const History *prev, float *prior) {
+    const uint64_t pixels = (uint64_t)im.width * (uint64_t)im.height;
+    int32_t x, y;
+    if (!pixel_of(im, x, y)) return;
+    const int64_t p = (int64_t)y * im.width + x;
+    const uint32_t hits = in.hits[p];
+    if (hits == 0) {
+        prior[2 * p] = 0.0f;
+        prior[2 * p + 1] = 0.0f;
+        return;
+    }
+    float d[3];
+    for (int k = 0; k < 3; ++k) d[k] = fmaxf(in.albedo[3 * p + k] * inv_aov, 1e-3f);
+    const float dl = lum(d[0], d[1], d[2]);
+    const float Nx = in.normal[3 * p], Ny = in.normal[3 * p + 1], Nz = in.normal[3 * p + 2];
+    const float len2 = (Nx * Nx + Ny * Ny) + Nz * Nz;
+    float4 np = make_float4(0.0f, 0.0f, 0.0f, in.depth[p] / (float)hits);
+    if (len2 != 0.0f) {
+        const float nl = rtd::sqrt_cr(len2);
+        np.x = Nx / nl;
+        np.y = Ny / nl;
+        np.z = Nz / nl;
+    }
+    const int32_t prim = first_prim[p];
+    const float Lc[3] = {0.0f, 0.0f, 0.0f}, m1 = 0.0f;          // (no colour here: what the shared text blends is not kept)
+#define RTP_REPROJECT_STATE float L[3], M1, M2, len, ch = 0.0f, vh = 0.0f;
+#define RTP_REPROJECT_HISTORY_OK prev && prev->magic == kHistMagicSpp && prev->width == im.width && prev->height == im.height && prev->mode == kModeMoments
+#define RTP_REPROJECT_SUMS float SC = 0.0f, SV = 0.0f;
+#define RTP_REPROJECT_TAP SC += w * xq.w, SV += w * nq.w;
+#define RTP_REPROJECT_ALPHA const float a = 0.0f, b = 0.0f;
+#define RTP_REPROJECT_VARIANCE  \
+    (void)L, (void)M1, (void)M2; \
+    ch = SC / W;                 \
+    vh = (SV / W) * (dl * dl);
+#include "rt_denoise_reproject.inc"
+#undef RTP_REPROJECT_STATE
+#undef RTP_REPROJECT_HISTORY_OK
+#undef RTP_REPROJECT_SUMS
+#undef RTP_REPROJECT_TAP
+#undef RTP_REPROJECT_ALPHA
+#undef RTP_REPROJECT_VARIANCE
+    (void)len;
+    prior[2 * p] = ch;
+    prior[2 * p + 1] = vh;
+}
+
 // [a, a + na) and [b, b + nb) share a byte
 bool overlap(const void *a, uint64_t na, const void *b, uint64_t nb) {
     const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
@@ -786,6 +841,43 @@ rt_status rt_denoise_temporal_spp(const float *d_fb_sum, const int32_t *d_spp, c
                        l.nz, l.dg, d_fb_sum, prm.iterations == 0 ? d_out : nullptr);
     if ((st = launched("denoise_temporal_spp")) != RT_OK || prm.iterations == 0) return st;
     return rtdn::enqueue_steps(l, prm, d_fb_sum, 0.0f, d_out, rtdn::plane(d_history_next, pixels, 0), stream, d_spp);
+}
+
+rt_status rt_adaptive_prior(const rt_aov_buffers *aov, int32_t aov_samples, const rt_camera_data *cam, const void *d_history_prev,
+                            uint64_t history_bytes, float *d_prior, void *hip_stream) {
+    using rtdn::fail;
+    using rtdn::overlap;
+    if (!aov || !cam || !d_prior) return fail(RT_ERR_INVALID_ARG, "rt_adaptive_prior: null argument");
+    rt_aov_buffers b;
+    rt_aov_buffers_init(&b);
+    const uint32_t ab = aov->struct_bytes < sizeof(b) ? aov->struct_bytes : (uint32_t)sizeof(b);
+    memcpy(&b, aov, ab);
+    if (ab < offsetof(rt_aov_buffers, first_prim) + sizeof(b.first_prim) || !b.albedo_sum || !b.normal_sum || !b.depth_sum || !b.hit_count ||
+        !b.first_prim)
+        return fail(RT_ERR_INVALID_ARG, "rt_adaptive_prior: albedo_sum, normal_sum, depth_sum, hit_count and first_prim are required");
+    const int32_t width = cam->image_width, height = cam->image_height;
+    if (width < 1 || height < 1) return fail(RT_ERR_INVALID_ARG, "rt_adaptive_prior: image width and height must be at least 1");
+    if (aov_samples < 1 || aov_samples > 65536) return fail(RT_ERR_INVALID_ARG, "rt_adaptive_prior: aov_samples outside 1 … 65536");
+    const uint64_t pixels = (uint64_t)width * (uint64_t)height;
+    if (pixels > (1ull << 24)) return fail(RT_ERR_UNSUPPORTED, "rt_adaptive_prior: more than 2^24 pixels");
+    const uint64_t hist = rt_denoise_history_bytes(width, height);
+    if (d_history_prev && history_bytes < hist)
+        return fail(RT_ERR_INVALID_ARG, "rt_adaptive_prior: history_bytes below rt_denoise_history_bytes (" + std::to_string(hist) + ")");
+    if ((uintptr_t)d_history_prev & 15u) return fail(RT_ERR_INVALID_ARG, "rt_adaptive_prior: the history buffer is not 16-byte aligned");
+    if (overlap(d_prior, 8 * pixels, d_history_prev, d_history_prev ? hist : 0))
+        return fail(RT_ERR_INVALID_ARG, "rt_adaptive_prior: d_prior overlaps history_prev");
+    const struct { const void *ptr; uint64_t bytes; } inputs[] = {{b.albedo_sum, 12 * pixels}, {b.normal_sum, 12 * pixels}, {b.depth_sum, 4 * pixels},
+                                                                   {b.hit_count, 4 * pixels}, {b.first_prim, 4 * pixels}};
+    for (const auto &in : inputs)
+        if (overlap(d_prior, 8 * pixels, in.ptr, in.bytes)) return fail(RT_ERR_INVALID_ARG, "rt_adaptive_prior: d_prior overlaps an input");
+
+    // ---- enqueue: one launch
+    const hipStream_t stream = (hipStream_t)hip_stream;
+    const rtdn::Launch l(width, height, nullptr);
+    const rtdn::Inputs in = {nullptr, b.albedo_sum, b.normal_sum, b.depth_sum, b.hit_count};
+    hipLaunchKernelGGL(rtdn::adaptive_prior, l.grid, l.block, 0, stream, l.im, *cam, in, (const int32_t *)b.first_prim, (float)(1.0 / (double)aov_samples),
+                       (const rtdn::History *)d_history_prev, d_prior);
+    return rtdn::launched("adaptive_prior");
 }
 
 }  // extern "C"

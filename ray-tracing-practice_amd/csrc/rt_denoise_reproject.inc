@@ -1,6 +1,6 @@
 // rt_denoise_reproject.inc — the reprojection of one hit pixel into the previous frame's history, as the statements of the kernels
-// that include it (rt_denoise.hip: denoise_temporal and denoise_temporal_spp).  One text expanded in each, like rt_denoise_taps.inc, so
-// that the two calls cannot drift apart and denoise_temporal's instructions stay what they were.  In scope: im, cam, prev, pixels, x, y,
+// that include it (rt_denoise.hip: denoise_temporal, denoise_temporal_spp and adaptive_prior).  One text expanded in each, like
+// rt_denoise_taps.inc, so that the calls cannot drift apart and denoise_temporal's instructions stay what they were.  In scope: im, cam, prev, pixels, x, y,
 // np (the record of hit pixel p), prim, Lc, m1.  Defines X, reach2 and what RTP_REPROJECT_STATE declares: L, M1, M2, len (and the
 // including kernel's own accumulated quantities), left at their disoccluded values unless the history is taken.  The hooks, defined by
 // the including kernel and undefined after it:

@@ -68,6 +68,16 @@ int main(int argc, char *argv[]) {
             return 2;
         }
     }
+    // extension: `--stop-history`, only with `--denoise-adaptive-temporal`: each frame's AOVs at min_spp are rendered
+    // first, rt_adaptive_prior makes the prior from the previous frame's history (none on frame 0) and the frame goes through
+    // rt_render_adaptive_prior / rt_render_lit_adaptive_prior; the denoiser runs as without the flag.
+    bool stop_history = false;
+    for (int a = 2; a < argc; ++a)
+        if (std::string(argv[a]) == "--stop-history") stop_history = true;
+    if (stop_history && !denoise_adaptive_temporal) {
+        std::cerr << "rtp_main: --stop-history feeds the history of --denoise-adaptive-temporal back into the stopping rule: it needs that flag\n";
+        return 2;
+    }
     // extension: `--denoise-adaptive`, with `--adaptive T` or with `--lit … --noise-target T` and only with them: each adaptively sampled
     // frame is also filtered by rt_denoise_spp — its own counts and moments, AOVs rendered at min_spp (rt_render_aov; on the lit path
     // rt_render_aov_lens with the frame's lens and shutter) — and written through rt_tonemap_spp to "<frame file>.denoised".  Not with
@@ -444,7 +454,7 @@ int main(int argc, char *argv[]) {
                 lit.env = lit_env;
                 lit.env_params = &lit_ep;
                 rtp::gpu_render_lens(params, desc, lens, shutter, aov, denoise, nullptr, nullptr, nullptr, &lit, noise_on ? &noise : nullptr,
-                                     denoise_adaptive, &stop_rule, denoise_adaptive_temporal, fog_on ? &fog : nullptr);
+                                     denoise_adaptive, &stop_rule, denoise_adaptive_temporal, fog_on ? &fog : nullptr, stop_history);
                 rt_env_destroy(lit_env);
                 return 0;
             }
@@ -494,7 +504,7 @@ int main(int argc, char *argv[]) {
                     std::cerr << "rtp_main: --adaptive cannot be combined with --shard\n";
                     return 2;
                 }
-            rtp::gpu_render_adaptive(params, desc, ap, denoise_adaptive, &stop_rule, denoise_adaptive_temporal);
+            rtp::gpu_render_adaptive(params, desc, ap, denoise_adaptive, &stop_rule, denoise_adaptive_temporal, stop_history);
             return 0;
         }
     // extension: `--gpu --shard N` splits EVERY frame over N GPUs (0 = all of the node) with one RCCL gather per frame

@@ -211,8 +211,10 @@ struct AdaptiveDenoiser {
     void *d_history[2] = {nullptr, nullptr};
     uint64_t history_bytes = 0;
     int frames = 0;
+    float *d_prior = nullptr;          // rtp_main --stop-history: the prior of the frame about to be rendered
 
-    AdaptiveDenoiser(int w, int h, bool temporal_ = false) : width(w), height(h), num_pixels(static_cast<size_t>(w) * h), temporal(temporal_) {
+    AdaptiveDenoiser(int w, int h, bool temporal_ = false, bool stop_history = false)
+        : width(w), height(h), num_pixels(static_cast<size_t>(w) * h), temporal(temporal_) {
         rt_aov_buffers_init(&aov);
         workspace_bytes = rt_denoise_workspace_bytes(w, h);
         RTP_CHECK(rt_device_alloc(num_pixels * 8, reinterpret_cast<void **>(&d_moments)));
@@ -227,10 +229,12 @@ struct AdaptiveDenoiser {
             RTP_CHECK(rt_device_alloc(num_pixels * 4, reinterpret_cast<void **>(&aov.first_prim)));
             RTP_CHECK(rt_device_alloc(history_bytes, &d_history[0]));
             RTP_CHECK(rt_device_alloc(history_bytes, &d_history[1]));
+            if (stop_history) RTP_CHECK(rt_device_alloc(num_pixels * 8, reinterpret_cast<void **>(&d_prior)));
         }
     }
     ~AdaptiveDenoiser() {
         rt_device_free(aov.first_prim);
+        rt_device_free(d_prior);
         rt_device_free(d_history[0]);
         rt_device_free(d_history[1]);
         rt_device_free(d_moments);
@@ -243,6 +247,11 @@ struct AdaptiveDenoiser {
     }
     AdaptiveDenoiser(const AdaptiveDenoiser &) = delete;
     AdaptiveDenoiser &operator=(const AdaptiveDenoiser &) = delete;
+
+    // With the frame's AOVs at aov_samples in place: the prior from the history the frame's write() will read (none on the first frame)
+    void make_prior(int32_t aov_samples, const rt_camera_data &cam) {
+        RTP_CHECK(rt_adaptive_prior(&aov, aov_samples, &cam, frames == 0 ? nullptr : d_history[(frames + 1) & 1], history_bytes, d_prior, nullptr));
+    }
 
     // d_rgb: the frame's own byte buffer, free again once the frame's file is written
     // cam: the frame's camera (the temporal filter's reprojection; unused without it)
@@ -334,7 +343,7 @@ void gpu_render_pipelined(const SceneParams &params, const rt_scene_desc &desc, 
 void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const rt_lens_params &lens, float shutter, bool aov, bool denoise,
                      const rt_nee_params *nee, const rt_env *env, const rt_env_params *env_params, const rt_lit_params *lit,
                      const rt_adaptive_params *noise, bool denoise_adaptive, const rt_stop_params *stop, bool denoise_adaptive_temporal,
-                     const rt_medium_params *medium) {
+                     const rt_medium_params *medium, bool stop_history) {
     rt_scene *scene = nullptr;
     RTP_CHECK(rt_scene_create(&desc, &scene));
     const size_t num_pixels = static_cast<size_t>(params.width) * params.height;
@@ -352,7 +361,8 @@ void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const
     }
     std::unique_ptr<AdaptiveDenoiser> spp_denoiser;
     if (lit && noise && (denoise_adaptive || denoise_adaptive_temporal))
-        spp_denoiser = std::make_unique<AdaptiveDenoiser>(params.width, params.height, denoise_adaptive_temporal);
+        spp_denoiser = std::make_unique<AdaptiveDenoiser>(params.width, params.height, denoise_adaptive_temporal, stop_history);
+    const bool with_prior = spp_denoiser && spp_denoiser->d_prior;
     rt_aov_buffers aov_bufs;
     rt_aov_buffers_init(&aov_bufs);
     std::vector<float> h_albedo, h_normal, h_depth, h_denoised;
@@ -389,7 +399,17 @@ void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const
         const rt_camera_data *cam_close = shutter > 0.0f ? &close : nullptr;
         const auto t0 = std::chrono::steady_clock::now();
         long long total_rays = static_cast<long long>(params.width) * params.height * params.sqrt_spp * params.sqrt_spp;
-        if (lit && noise) {
+        if (lit && noise && with_prior) {          // (a pinhole, no shutter) the first hits at min_spp, the prior, the frame
+            rt_lit_params frame_lit = *lit;
+            frame_lit.cam_close = cam_close;
+            frame_lit.lens = &lens;
+            rt_camera_data aov_cam = cam;
+            aov_cam.samples_per_pixel = noise->min_spp;
+            RTP_CHECK(rt_render_aov(scene, &aov_cam, nullptr, &spp_denoiser->aov, nullptr, 1, nullptr));
+            spp_denoiser->make_prior(noise->min_spp, cam);
+            RTP_CHECK(rt_render_lit_adaptive_prior(scene, &cam, &frame_lit, noise, stop, nullptr, 0, d_fb, d_spp, spp_denoiser->d_moments, nullptr, 1, nullptr,
+                                                   spp_denoiser->d_prior));
+        } else if (lit && noise) {
             rt_lit_params frame_lit = *lit;
             frame_lit.cam_close = cam_close;
             frame_lit.lens = &lens;
@@ -421,8 +441,12 @@ void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const
         if (spp_denoiser) {          // (outside the frame's timed span) the first hits of this lens and shutter at min_spp samples
             rt_camera_data aov_open = cam, aov_close = close;
             aov_open.samples_per_pixel = aov_close.samples_per_pixel = noise->min_spp;
-            if (spp_denoiser->temporal) RTP_CHECK(rt_render_aov(scene, &aov_open, nullptr, &spp_denoiser->aov, nullptr, 1, nullptr));       // (a pinhole, no shutter)
-            else RTP_CHECK(rt_render_aov_lens(scene, &aov_open, cam_close ? &aov_close : nullptr, &lens, nullptr, 0, &spp_denoiser->aov, nullptr, 1, nullptr));
+            if (with_prior) {          // (rendered before the frame)
+            } else if (spp_denoiser->temporal) {
+                RTP_CHECK(rt_render_aov(scene, &aov_open, nullptr, &spp_denoiser->aov, nullptr, 1, nullptr));       // (a pinhole, no shutter)
+            } else {
+                RTP_CHECK(rt_render_aov_lens(scene, &aov_open, cam_close ? &aov_close : nullptr, &lens, nullptr, 0, &spp_denoiser->aov, nullptr, 1, nullptr));
+            }
             spp_denoiser->write(filename, d_fb, d_spp, noise->min_spp, d_rgb, cam);
         }
         if (aov || denoise) {          // (outside the frame's timed span, as in gpu_render)
@@ -469,7 +493,7 @@ void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const
 // min_spp, and rt_denoise_spp's output goes through rt_tonemap_spp to "<frame file>.denoised".  denoise_adaptive_temporal (rtp_main
 // --denoise-adaptive-temporal): the same with rt_denoise_temporal_spp and its history from the frame before.
 void gpu_render_adaptive(const SceneParams &params, const rt_scene_desc &desc, const rt_adaptive_params &ap, bool denoise_adaptive,
-                         const rt_stop_params *stop, bool denoise_adaptive_temporal) {
+                         const rt_stop_params *stop, bool denoise_adaptive_temporal, bool stop_history) {
     rt_scene *scene = nullptr;
     RTP_CHECK(rt_scene_create(&desc, &scene));
     const size_t num_pixels = static_cast<size_t>(params.width) * params.height;
@@ -482,7 +506,8 @@ void gpu_render_adaptive(const SceneParams &params, const rt_scene_desc &desc, c
     std::vector<int32_t> spp(num_pixels);
     std::unique_ptr<AdaptiveDenoiser> spp_denoiser;
     if (denoise_adaptive || denoise_adaptive_temporal)
-        spp_denoiser = std::make_unique<AdaptiveDenoiser>(params.width, params.height, denoise_adaptive_temporal);
+        spp_denoiser = std::make_unique<AdaptiveDenoiser>(params.width, params.height, denoise_adaptive_temporal, stop_history);
+    const bool with_prior = spp_denoiser && spp_denoiser->d_prior;
     for (int n = 0; n < params.num_frames; ++n) {
         Vec3 eye, target;
         orbit_pose(params, n, eye, target);
@@ -493,7 +518,13 @@ void gpu_render_adaptive(const SceneParams &params, const rt_scene_desc &desc, c
         camera.background_color = Vec3(0, 0, 0);
         const rt_camera_data cam = camera.build_camera_data();
         const auto t0 = std::chrono::steady_clock::now();
-        RTP_CHECK(rt_render_adaptive_rule(scene, &cam, nullptr, &ap, stop, d_fb, d_spp, spp_denoiser ? spp_denoiser->d_moments : nullptr, nullptr, 1, nullptr));
+        if (with_prior) {          // cam carries min_spp: the first hits, the prior from the frame before, the frame
+            RTP_CHECK(rt_render_aov(scene, &cam, nullptr, &spp_denoiser->aov, nullptr, 1, nullptr));
+            spp_denoiser->make_prior(ap.min_spp, cam);
+            RTP_CHECK(rt_render_adaptive_prior(scene, &cam, nullptr, &ap, stop, d_fb, d_spp, spp_denoiser->d_moments, nullptr, 1, nullptr, spp_denoiser->d_prior));
+        } else {
+            RTP_CHECK(rt_render_adaptive_rule(scene, &cam, nullptr, &ap, stop, d_fb, d_spp, spp_denoiser ? spp_denoiser->d_moments : nullptr, nullptr, 1, nullptr));
+        }
         RTP_CHECK(rt_tonemap_spp(d_fb, d_spp, d_rgb, static_cast<int64_t>(num_pixels), nullptr));
         PendingFile file;
         file.path = frame_filename(params.output_pattern, n);
@@ -508,7 +539,7 @@ void gpu_render_adaptive(const SceneParams &params, const rt_scene_desc &desc, c
         for (int32_t k : spp) samples += k;
         std::cout << n << "\t" << ms << "\t" << samples << "\n";
         if (spp_denoiser) {          // (outside the frame's timed span) cam carries min_spp: the AOVs of the frame's first samples
-            RTP_CHECK(rt_render_aov(scene, &cam, nullptr, &spp_denoiser->aov, nullptr, 1, nullptr));
+            if (!with_prior) RTP_CHECK(rt_render_aov(scene, &cam, nullptr, &spp_denoiser->aov, nullptr, 1, nullptr));
             spp_denoiser->write(file.path, d_fb, d_spp, ap.min_spp, d_rgb, cam);
         }
     }

@@ -488,6 +488,7 @@ RTP_AMD_SYMBOLS = [
     "rt_denoise_spp",
     "rt_stop_params_init", "rt_render_adaptive_rule", "rt_render_lit_adaptive_rule", "rt_adaptive_judge",
     "rt_denoise_temporal_spp",
+    "rt_adaptive_prior", "rt_render_adaptive_prior", "rt_render_lit_adaptive_prior", "rt_adaptive_judge_prior",
 ]
 
 _host = None
@@ -652,6 +653,11 @@ def amd_lib():
             lib.rt_denoise_temporal_spp.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(AovBuffers), C.c_int32, C.POINTER(CameraData),
                                                     C.POINTER(DenoiseParams), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                                                     C.c_void_p, C.c_void_p]
+        if hasattr(lib, "rt_adaptive_prior"):
+            lib.rt_adaptive_prior.argtypes = [C.POINTER(AovBuffers), C.c_int32, C.POINTER(CameraData), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+            lib.rt_render_adaptive_prior.argtypes = lib.rt_render_adaptive_rule.argtypes + [C.c_void_p]
+            lib.rt_render_lit_adaptive_prior.argtypes = lib.rt_render_lit_adaptive_rule.argtypes + [C.c_void_p]
+            lib.rt_adaptive_judge_prior.argtypes = lib.rt_adaptive_judge.argtypes + [C.c_void_p]
         lib.rt_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         lib.rt_last_timing.argtypes = [C.c_void_p, C.POINTER(Timing)]
         lib.rt_timing_init.argtypes = [C.POINTER(Timing)]
@@ -880,6 +886,15 @@ def denoise_temporal_spp(d_fb, d_spp, d_moments, aov_ptrs, aov_spp, cam, d_histo
                                              C.c_void_p(ws_ptr), ws_bytes, C.c_void_p(d_out), C.c_void_p(stream or 0)), "rt_denoise_temporal_spp")
 
 
+def adaptive_prior(aov_ptrs, aov_spp, cam, d_history_prev, history_bytes, d_prior, stream=None):
+    """rt_adaptive_prior on device addresses: aov_ptrs {"albedo", "normal", "depth", "hits", "prim"} → device address of the AOV sums of
+    the frame about to be rendered at aov_spp samples per pixel, cam its camera, d_history_prev (None: no history) a history of
+    rt_denoise_temporal_spp of history_bytes, d_prior 2 floats per pixel.  Only enqueues on `stream` (None = default stream)."""
+    b = _aov_struct(aov_ptrs)
+    _check(amd_lib().rt_adaptive_prior(C.byref(b), aov_spp, C.byref(cam), C.c_void_p(d_history_prev or 0), history_bytes, C.c_void_p(d_prior),
+                                       C.c_void_p(stream or 0)), "rt_adaptive_prior")
+
+
 _hip_rt = None
 
 
@@ -970,9 +985,10 @@ def _upload(a):
     return d
 
 
-def adaptive_judge(moments, n, going_on=None, shard=None, rule=0, **params):
+def adaptive_judge(moments, n, going_on=None, shard=None, rule=0, prior=None, **params):
     """rt_adaptive_judge: one judgement of a stopping rule on the current device.  moments (rows, width, 2) float32 (S1, S2); going_on
-    None (every pixel) or (rows, width) bool; params are rt_adaptive_params fields.  Returns goes_on (rows, width) bool."""
+    None (every pixel) or (rows, width) bool; prior None or (rows, width, 2) float32 (ch, vh): given, the call is
+    rt_adaptive_judge_prior; params are rt_adaptive_params fields.  Returns goes_on (rows, width) bool."""
     lib = amd_lib()
     mom = np.ascontiguousarray(moments, dtype=np.float32)
     rows, width = mom.shape[:2]
@@ -983,8 +999,13 @@ def adaptive_judge(moments, n, going_on=None, shard=None, rule=0, **params):
         dev.append(_upload(mom))
         dev.append(None if going_on is None else _upload(np.ascontiguousarray(np.asarray(going_on).reshape(rows, width), dtype=np.uint8)))
         dev.append(_upload(out))
-        _check(lib.rt_adaptive_judge(width, rows, C.byref(shard) if shard else None, C.byref(p), C.byref(stop), n, dev[0], dev[1], dev[2], None),
-               "rt_adaptive_judge")
+        if prior is None:
+            _check(lib.rt_adaptive_judge(width, rows, C.byref(shard) if shard else None, C.byref(p), C.byref(stop), n, dev[0], dev[1], dev[2], None),
+                   "rt_adaptive_judge")
+        else:
+            dev.append(_upload(np.ascontiguousarray(np.asarray(prior, dtype=np.float32).reshape(rows, width, 2))))
+            _check(lib.rt_adaptive_judge_prior(width, rows, C.byref(shard) if shard else None, C.byref(p), C.byref(stop), n, dev[0], dev[1], dev[2],
+                                               None, dev[3]), "rt_adaptive_judge_prior")
         _check(lib.rt_copy_to_host(out.ctypes.data, dev[2], out.nbytes), "rt_copy_to_host")
     finally:
         for d in dev:
@@ -1089,6 +1110,31 @@ class TemporalDenoiser:
                           {k: dev[k].value for k, _, _, _ in AOV_CHANNELS}, aov_spp, cam, d_out.value)
             out = np.empty_like(fb)
             _check(lib.rt_copy_to_host(out.ctypes.data, d_out, out.nbytes), "rt_copy_to_host")
+        finally:
+            for d in dev.values():
+                lib.rt_device_free(d)
+        return out
+
+    def prior(self, aov_ptrs, aov_spp, cam, d_prior, stream=None):
+        """rt_adaptive_prior of the frame about to be rendered (its AOVs at aov_spp samples per pixel and its camera) on the history the
+        next step_spp will read — none before the first step and after reset() — into d_prior (2 floats per pixel); only enqueues on
+        `stream`."""
+        if (cam.image_width, cam.image_height) != (self.width, self.height):
+            raise RtError(f"TemporalDenoiser: a {cam.image_width} x {cam.image_height} frame for a {self.width} x {self.height} history")
+        adaptive_prior(aov_ptrs, aov_spp, cam, self._prev if self._have else None, self.history_bytes, d_prior, stream=stream)
+
+    def prior_to_host(self, aov, aov_spp, cam):
+        """prior() of host arrays: aov the dict of DeviceScene.render_aov_to_host (prim included).  Returns (H, W, 2) float32 (ch, vh).
+        Synchronous (default stream)."""
+        lib = amd_lib()
+        out = np.empty((self.height, self.width, 2), dtype=np.float32)
+        dev = {}
+        try:
+            for key, _, dtype, _ in AOV_CHANNELS:
+                dev[key] = _upload(np.ascontiguousarray(aov[key], dtype=dtype))
+            dev["prior"] = _upload(out)
+            self.prior({k: dev[k].value for k, _, _, _ in AOV_CHANNELS}, aov_spp, cam, dev["prior"].value)
+            _check(lib.rt_copy_to_host(out.ctypes.data, dev["prior"], out.nbytes), "rt_copy_to_host")
         finally:
             for d in dev.values():
                 lib.rt_device_free(d)
@@ -1257,15 +1303,22 @@ class DeviceScene:
                 lib.rt_device_free(d)
         return out, t
 
-    def render_adaptive(self, cam, d_fb_ptr, d_spp_ptr, d_moments_ptr=None, shard=None, stream=None, sync=True, **params):
+    def render_adaptive(self, cam, d_fb_ptr, d_spp_ptr, d_moments_ptr=None, shard=None, stream=None, sync=True, prior=None, **params):
         """rt_render_adaptive: d_fb_ptr (3 floats per pixel), d_spp_ptr (1 int32 per pixel), d_moments_ptr (None, or 2 floats per pixel)
         are integer device addresses; params are rt_adaptive_params fields (min_spp, batch_spp, max_spp, threshold) and rule (0 or 1:
-        given, the call goes through rt_render_adaptive_rule with that rt_stop_params.rule).  Returns the rt_timing."""
+        given, the call goes through rt_render_adaptive_rule with that rt_stop_params.rule); prior: None, or the device address of 2
+        floats per local pixel (rt_render_adaptive_prior, rule 0 unless given).  Returns the rt_timing."""
         rule = params.pop("rule", None)
         p = adaptive_params(**params)
         t = Timing()
         self._apply_config()
-        if rule is None:
+        if prior is not None:
+            stop = stop_params(rule=rule or 0)
+            _check(amd_lib().rt_render_adaptive_prior(self._h, C.byref(cam), C.byref(shard) if shard else None, C.byref(p), C.byref(stop),
+                                                      C.c_void_p(d_fb_ptr), C.c_void_p(d_spp_ptr), C.c_void_p(d_moments_ptr or 0),
+                                                      C.c_void_p(stream or 0), 1 if sync else 0, C.byref(t), C.c_void_p(prior)),
+                   "rt_render_adaptive_prior")
+        elif rule is None:
             _check(amd_lib().rt_render_adaptive(self._h, C.byref(cam), C.byref(shard) if shard else None, C.byref(p), C.c_void_p(d_fb_ptr),
                                                 C.c_void_p(d_spp_ptr), C.c_void_p(d_moments_ptr or 0), C.c_void_p(stream or 0), 1 if sync else 0,
                                                 C.byref(t)), "rt_render_adaptive")
@@ -1276,9 +1329,9 @@ class DeviceScene:
                                                      C.c_void_p(stream or 0), 1 if sync else 0, C.byref(t)), "rt_render_adaptive_rule")
         return t
 
-    def render_adaptive_to_host(self, cam, shard=None, **params):
+    def render_adaptive_to_host(self, cam, shard=None, prior=None, **params):
         """rt_render_adaptive through fresh device buffers: (fb (rows, w, 3) float32 sums, spp (rows, w) int32, moments (rows, w, 2)
-        float32 (S1, S2)) and the rt_timing."""
+        float32 (S1, S2)) and the rt_timing.  prior: None or a host array (rows, w, 2) float32 (ch, vh)."""
         lib = amd_lib()
         rows = lib.rt_shard_rows(cam.image_height, C.byref(shard) if shard else None)
         w = cam.image_width
@@ -1291,6 +1344,9 @@ class DeviceScene:
                 d = C.c_void_p()
                 _check(lib.rt_device_alloc(a.nbytes or 12, C.byref(d)), "rt_device_alloc")
                 dev.append(d)
+            if prior is not None:
+                dev.append(_upload(np.ascontiguousarray(np.asarray(prior, dtype=np.float32).reshape(rows, w, 2))))
+                params = {**params, "prior": dev[3].value}
             t = self.render_adaptive(cam, dev[0].value, dev[1].value, dev[2].value, shard=shard, **params)
             for a, d in zip((fb, spp, mom), dev):
                 _check(lib.rt_copy_to_host(a.ctypes.data, d, a.nbytes), "rt_copy_to_host")
@@ -1500,17 +1556,24 @@ class DeviceScene:
         return fb, t
 
     def render_lit_adaptive(self, cam, d_fb_ptr, d_spp_ptr, d_moments_ptr=None, *, cam_close=None, lens=None, emitters=True, nee=None, env=None,
-                            env_params=None, shard=None, stream=None, sync=True, sample_first=0, **params):
+                            env_params=None, shard=None, stream=None, sync=True, sample_first=0, prior=None, **params):
         """rt_render_lit_adaptive: rt_render_adaptive's rounds on rt_render_lit's estimator.  d_fb_ptr (3 floats per pixel), d_spp_ptr
         (1 int32 per pixel), d_moments_ptr (None, or 2 floats per pixel) are integer device addresses; the keywords are lit_params()'s
         arguments; params are rt_adaptive_params fields (min_spp, batch_spp, max_spp, threshold) and rule (0 or 1: given, the call goes
-        through rt_render_lit_adaptive_rule with that rt_stop_params.rule).  Returns the rt_timing of this call."""
+        through rt_render_lit_adaptive_rule with that rt_stop_params.rule); prior: None, or the device address of 2 floats per local
+        pixel (rt_render_lit_adaptive_prior, rule 0 unless given).  Returns the rt_timing of this call."""
         rule = params.pop("rule", None)
         p = adaptive_params(**params)
         t = Timing()
         self._apply_config()
         lit = lit_params(cam_close=cam_close, lens=lens, emitters=emitters, nee=nee, env=env, env_params=env_params)
-        if rule is None:
+        if prior is not None:
+            stop = stop_params(rule=rule or 0)
+            _check(amd_lib().rt_render_lit_adaptive_prior(self._h, C.byref(cam), C.byref(lit), C.byref(p), C.byref(stop),
+                                                          C.byref(shard) if shard else None, sample_first, C.c_void_p(d_fb_ptr), C.c_void_p(d_spp_ptr),
+                                                          C.c_void_p(d_moments_ptr or 0), C.c_void_p(stream or 0), 1 if sync else 0, C.byref(t),
+                                                          C.c_void_p(prior)), "rt_render_lit_adaptive_prior")
+        elif rule is None:
             _check(amd_lib().rt_render_lit_adaptive(self._h, C.byref(cam), C.byref(lit), C.byref(p), C.byref(shard) if shard else None, sample_first,
                                                     C.c_void_p(d_fb_ptr), C.c_void_p(d_spp_ptr), C.c_void_p(d_moments_ptr or 0),
                                                     C.c_void_p(stream or 0), 1 if sync else 0, C.byref(t)), "rt_render_lit_adaptive")
@@ -1523,9 +1586,9 @@ class DeviceScene:
         return t
 
     def render_lit_adaptive_to_host(self, cam, *, cam_close=None, lens=None, emitters=True, nee=None, env=None, env_params=None, shard=None,
-                                    sample_first=0, **params):
+                                    sample_first=0, prior=None, **params):
         """rt_render_lit_adaptive through fresh device buffers: (fb (rows, w, 3) float32 sums, spp (rows, w) int32, moments (rows, w, 2)
-        float32 (S1, S2)) and the rt_timing."""
+        float32 (S1, S2)) and the rt_timing.  prior: None or a host array (rows, w, 2) float32 (ch, vh)."""
         lib = amd_lib()
         rows = lib.rt_shard_rows(cam.image_height, C.byref(shard) if shard else None)
         w = cam.image_width
@@ -1538,6 +1601,9 @@ class DeviceScene:
                 d = C.c_void_p()
                 _check(lib.rt_device_alloc(a.nbytes or 12, C.byref(d)), "rt_device_alloc")
                 dev.append(d)
+            if prior is not None:
+                dev.append(_upload(np.ascontiguousarray(np.asarray(prior, dtype=np.float32).reshape(rows, w, 2))))
+                params = {**params, "prior": dev[3].value}
             t = self.render_lit_adaptive(cam, dev[0].value, dev[1].value, dev[2].value, cam_close=cam_close, lens=lens, emitters=emitters, nee=nee,
                                          env=env, env_params=env_params, shard=shard, sample_first=sample_first, **params)
             for a, d in zip((fb, spp, mom), dev):
