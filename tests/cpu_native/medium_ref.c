@@ -17,13 +17,34 @@ typedef struct {
     rt_medium_params medium;
 } medium_cfg;
 
+/* the tallies of medium_trace_stats, in its order (tests/medium_reference.py names them the same way); they only count */
+enum {
+    MST_EVENTS,              /* medium vertices */
+    MST_INTERVAL_EMPTY,      /* a path ray whose interval is empty */
+    MST_ORIGIN_INSIDE,       /* a path ray whose interval starts at t0 == 0 */
+    MST_BOX_PARALLEL_IN,     /* the box, a direction component of exactly 0, the origin strictly inside that slab (any ray, shadow rays included) */
+    MST_BOX_PARALLEL_OUT,    /* … the origin on a face or outside: empty */
+    MST_U_ZERO,              /* the free-flight draw was exactly 0 */
+    MST_EVENT_AT_DEPTH_CUT,  /* a medium vertex at the last depth: no light sample, no next ray */
+    MST_BLACK,               /* the throughput was black after the albedo */
+    MST_TR_EMITTER,          /* Tr applied (a non-empty interval) where a shadow ray reached its emitter */
+    MST_TR_ENV,              /* … where an environment shadow ray escaped */
+    MST_ENV_SUPPRESSED,      /* a vertex that would have taken an environment sample, under a medium that fills all space */
+    MST_CARRY_HIT,           /* a medium vertex's ph weighted a hit on a table entry */
+    MST_CARRY_MISS,          /* … a miss */
+    MST_GLOSSY_INSIDE,       /* a glossy event at a surface point the path ray reached inside the region */
+    MST_EVENT_FIRST_RAY,     /* a medium vertex on the camera ray */
+    MST_COUNT
+};
+
 typedef struct {
     gloss_ctx G;
     rt_medium_params m;
+    int64_t *stats;          /* NULL, or the MST_COUNT tallies above (medium_trace_stats) */
 } medium_ctx;
 
-/* interval(o, d, t_end) of the header: 0 = empty */
-static int med_interval(const rt_medium_params *m, v3 o, v3 d, float t_end, float *t0_out, float *t1_out) {
+/* interval(o, d, t_end) of the header: 0 = empty.  st: NULL or the tallies */
+static int med_interval(const rt_medium_params *m, v3 o, v3 d, float t_end, float *t0_out, float *t1_out, int64_t *st) {
     float t0 = 0.0f, t1 = t_end;
     if (m->region == 1) {
         const v3 oc = sub(o, V(m->a[0], m->a[1], m->a[2]));
@@ -41,7 +62,11 @@ static int med_interval(const rt_medium_params *m, v3 o, v3 d, float t_end, floa
     } else if (m->region == 2) {
         for (int k = 0; k < 3; ++k) {
             if (d.e[k] == 0.0f) {
-                if (!(m->a[k] < o.e[k] && o.e[k] < m->b[k])) return 0;
+                if (!(m->a[k] < o.e[k] && o.e[k] < m->b[k])) {
+                    if (st) st[MST_BOX_PARALLEL_OUT]++;
+                    return 0;
+                }
+                if (st) st[MST_BOX_PARALLEL_IN]++;
                 continue;
             }
             float ta = (m->a[k] - o.e[k]) / d.e[k];
@@ -69,10 +94,11 @@ static float med_ph(float g, float c) {
 /* pb of a light sample at a medium vertex travelling along ud, in the sampled direction wl */
 static float med_pb(float g, v3 ud, v3 wl) { return med_ph(g, dot(ud, wl) / sqrtf(dot(wl, wl))); }
 
-/* Tr * c for the shadow ray (x, wl) that ended at t_end */
-static v3 med_attenuate(const rt_medium_params *m, v3 x, v3 wl, float t_end, v3 c) {
+/* Tr * c for the shadow ray (x, wl) that ended at t_end.  st: NULL or the tallies, which: the tally of a Tr that was applied */
+static v3 med_attenuate(const rt_medium_params *m, v3 x, v3 wl, float t_end, v3 c, int64_t *st, int which) {
     float t0, t1;
-    if (!(m->sigma_t > 0.0f) || !med_interval(m, x, wl, t_end, &t0, &t1)) return c;
+    if (!(m->sigma_t > 0.0f) || !med_interval(m, x, wl, t_end, &t0, &t1, st)) return c;
+    if (st) st[which]++;
     const float len = sqrtf(dot(wl, wl));
     const float L = (t1 - t0) * len;
     const float tr = expf(-(m->sigma_t * L));
@@ -207,6 +233,8 @@ static v3 ray_color_medium(const medium_ctx *Mc, ray r, uint32_t *seed, uint32_t
     const int emitters_on = T->count > 0;
     /* with region 0 and sigma_t > 0 the environment counts as not sampled for the whole call */
     const int sky_sampled = X->M && ep->mode != 0 && !X->M->empty && !(fog && m->region == 0);
+    int64_t *st = Mc->stats;
+    const int sky_suppressed = X->M && ep->mode != 0 && !X->M->empty && !sky_sampled;          /* (for the tallies alone) */
     v3 final_color = V(0.0f, 0.0f, 0.0f);
     v3 beta = V(1.0f, 1.0f, 1.0f);
     ray cur = r;
@@ -216,29 +244,44 @@ static v3 ray_color_medium(const medium_ctx *Mc, ray r, uint32_t *seed, uint32_t
     for (int depth = 0; depth < cam->max_depth; depth++) {
         hitrec rec;
         int pt, pi;
+        int reached_inside = fog && m->region == 0;          /* (for the tallies alone) the path ray ends inside the region */
         nrays++;
         const int hit = closest(sc, &cur, &rec, &pt, &pi);
         /* ---- the segment and the free flight */
         if (fog) {
             float t0, t1;
-            if (med_interval(m, cur.o, cur.d, hit ? rec.t : INFINITY, &t0, &t1)) {
+            const int crossed = med_interval(m, cur.o, cur.d, hit ? rec.t : INFINITY, &t0, &t1, st);
+            if (st && !crossed) st[MST_INTERVAL_EMPTY]++;
+            reached_inside = crossed && hit && t1 == rec.t;
+            if (crossed) {
+                if (st && t0 == 0.0f) st[MST_ORIGIN_INSIDE]++;
                 const float len = sqrtf(dot(cur.d, cur.d));
                 const float u = orc_random_float(med);
+                if (st && u == 0.0f) st[MST_U_ZERO]++;
                 if (u != 0.0f) {
                     const float s = -log_ref(u) / m->sigma_t;
                     if (s < (t1 - t0) * len) {
                         /* ---- the medium vertex */
                         events++;
+                        if (st) {
+                            st[MST_EVENTS]++;
+                            if (depth == 0) st[MST_EVENT_FIRST_RAY]++;
+                        }
                         const v3 x = add(cur.o, scale(t0 + s / len, cur.d));
                         const v3 ud = unit(cur.d);
                         const v3 beta_in = beta;
                         const v3 a = V(m->albedo[0], m->albedo[1], m->albedo[2]);
                         beta = mulv(beta, a);
                         if (beta.e[0] == 0.0f && beta.e[1] == 0.0f && beta.e[2] == 0.0f) {
+                            if (st) st[MST_BLACK]++;
                             end = 3;
                             break;
                         }
-                        if (!(depth + 1 < cam->max_depth)) break;
+                        if (!(depth + 1 < cam->max_depth)) {
+                            if (st) st[MST_EVENT_AT_DEPTH_CUT]++;
+                            break;
+                        }
+                        if (st && sky_suppressed) st[MST_ENV_SUPPRESSED]++;
                         hitrec srec;
                         int spt, spi;
                         ray shadow;
@@ -258,12 +301,12 @@ static v3 ray_color_medium(const medium_ctx *Mc, ray r, uint32_t *seed, uint32_t
                             if (e < T->count && med_entry_sample(sc, T, e, pmf, nee, x, a, beta_in, m->g, ud, &shadow.d, &c)) {
                                 nrays++;
                                 const int sh = closest(sc, &shadow, &srec, &spt, &spi);
-                                if (sh && spt == T->kind[e] && spi == T->index[e]) final_color = add(final_color, med_attenuate(m, x, shadow.d, srec.t, c));
+                                if (sh && spt == T->kind[e] && spi == T->index[e]) final_color = add(final_color, med_attenuate(m, x, shadow.d, srec.t, c, st, MST_TR_EMITTER));
                             }
                         }
                         if (sky_sampled && med_sky_sample(X->M, ep, env, a, beta_in, m->g, ud, &shadow.d, &c, X->linear)) {
                             nrays++;
-                            if (!closest(sc, &shadow, &srec, &spt, &spi)) final_color = add(final_color, med_attenuate(m, x, shadow.d, INFINITY, c));
+                            if (!closest(sc, &shadow, &srec, &spt, &spi)) final_color = add(final_color, med_attenuate(m, x, shadow.d, INFINITY, c, st, MST_TR_ENV));
                         }
                         const float u1 = orc_random_float(med);
                         const float cos_t = med_cos(m->g, u1);
@@ -296,6 +339,7 @@ static v3 ray_color_medium(const medium_ctx *Mc, ray r, uint32_t *seed, uint32_t
             v3 term = mulv(beta, scaled(X->M, ep, t));
             const int weighted = carried == 1 || carried == 3 || (carried == 2 && G->glossy_env && carry_pb != 0.0f);
             if (weighted && sky_sampled) {
+                if (st && carried == 3) st[MST_CARRY_MISS]++;
                 const float pb = carried == 1 ? RT_NEE_PB : carry_pb;
                 const float q2 = dot(p, p);
                 const float pl = pl_of(X->M, t, q2, sqrtf(q2));
@@ -317,6 +361,7 @@ static v3 ray_color_medium(const medium_ctx *Mc, ray r, uint32_t *seed, uint32_t
         if (hit_weighted && (pt == 0 || pt == 1) && emitters_on) {
             const int e = tab_find(T, pt, pi);
             if (e >= 0) {
+                if (st && carried == 3) st[MST_CARRY_HIT]++;
                 const float pb = carried == 1 ? RT_NEE_PB : carry_pb;
                 v3 w;
                 float d2, om, pa, pl = 0.0f;
@@ -367,6 +412,11 @@ static v3 ray_color_medium(const medium_ctx *Mc, ray r, uint32_t *seed, uint32_t
             }
         }
         const int glossy_event = B.glossy && (take_nee || take_env);
+        if (st) {
+            if (glossy_event && reached_inside) st[MST_GLOSSY_INSIDE]++;
+            /* the environment sample this vertex would have taken were the environment sampled */
+            if (sky_suppressed && depth + 1 < cam->max_depth && ((event == 1 && ok) || (B.glossy && G->glossy_env))) st[MST_ENV_SUPPRESSED]++;
+        }
         if (take_nee || take_env) {
             hitrec srec;
             int spt, spi;
@@ -388,14 +438,14 @@ static v3 ray_color_medium(const medium_ctx *Mc, ray r, uint32_t *seed, uint32_t
                 if (e < T->count && entry_sample_pb(sc, T, e, pmf, nee, rec.point, rec.normal, albedo, beta, &B, &shadow.d, &c, &pg_zero)) {
                     nrays++;
                     const int sh = closest(sc, &shadow, &srec, &spt, &spi);
-                    if (sh && spt == T->kind[e] && spi == T->index[e]) final_color = add(final_color, med_attenuate(m, rec.point, shadow.d, srec.t, c));
+                    if (sh && spt == T->kind[e] && spi == T->index[e]) final_color = add(final_color, med_attenuate(m, rec.point, shadow.d, srec.t, c, st, MST_TR_EMITTER));
                 }
             }
             if (take_env) {
                 int pg_zero = 0;
                 if (sky_sample_pb(X->M, ep, env, rec.normal, albedo, beta, &B, &shadow.d, &c, X->linear, &pg_zero)) {
                     nrays++;
-                    if (!closest(sc, &shadow, &srec, &spt, &spi)) final_color = add(final_color, med_attenuate(m, rec.point, shadow.d, INFINITY, c));
+                    if (!closest(sc, &shadow, &srec, &spt, &spi)) final_color = add(final_color, med_attenuate(m, rec.point, shadow.d, INFINITY, c, st, MST_TR_ENV));
                 }
             }
         }
@@ -438,6 +488,7 @@ static void make_medium_ctx(const rt_scene_desc *sc, const rt_camera_data *cam, 
                             medium_ctx *Mc) {
     make_gloss_ctx(sc, cam, &cfg->base, T, M, t, linear, &Mc->G);
     Mc->m = cfg->medium;
+    Mc->stats = NULL;
 }
 
 /* ---- what tests/medium_reference.py calls -------------------------------------------------------------------------------------------- */
@@ -453,18 +504,21 @@ void medium_cos_draws(int64_t count, float g, uint32_t seed, float *c) {
 void medium_intervals(const rt_medium_params *m, int64_t count, const float *o, const float *d, const float *t_end, int32_t *hit, float *t0, float *t1) {
     for (int64_t k = 0; k < count; ++k) {
         t0[k] = t1[k] = 0.0f;
-        hit[k] = med_interval(m, V(o[3 * k], o[3 * k + 1], o[3 * k + 2]), V(d[3 * k], d[3 * k + 1], d[3 * k + 2]), t_end[k], &t0[k], &t1[k]);
+        hit[k] = med_interval(m, V(o[3 * k], o[3 * k + 1], o[3 * k + 2]), V(d[3 * k], d[3 * k + 1], d[3 * k + 2]), t_end[k], &t0[k], &t1[k], NULL);
     }
 }
 
-/* count samples (ijs: i, j, s) → radiance, rays, medium events, how each path ended, and the four final RNG states (seed, nee, env, med) */
-void medium_trace(const rt_scene_desc *sc, const rt_camera_data *cam, const medium_cfg *cfg, int64_t count, const int32_t *ijs, float *radiance, int32_t *rays,
-                  int32_t *events, int32_t *ends, uint32_t *seeds4, int32_t linear) {
+/* count samples (ijs: i, j, s) → radiance, rays, medium events, how each path ended, and the four final RNG states (seed, nee, env, med);
+ * stats (MST_COUNT words, may be NULL): the tallies named above, summed over the samples */
+void medium_trace_stats(const rt_scene_desc *sc, const rt_camera_data *cam, const medium_cfg *cfg, int64_t count, const int32_t *ijs, float *radiance,
+                        int32_t *rays, int32_t *events, int32_t *ends, uint32_t *seeds4, int32_t linear, int64_t *stats) {
     emit_tab T;
     sky_map M;
     light_tree t;
     medium_ctx Mc;
     make_medium_ctx(sc, cam, cfg, &T, &M, &t, linear, &Mc);
+    if (stats) memset(stats, 0, MST_COUNT * sizeof(int64_t));
+    Mc.stats = stats;
     for (int64_t k = 0; k < count; ++k) {
         med_out o;
         const v3 c = medium_sample_of(&Mc, ijs[3 * k], ijs[3 * k + 1], ijs[3 * k + 2], &o, seeds4 + 4 * k);
@@ -475,6 +529,11 @@ void medium_trace(const rt_scene_desc *sc, const rt_camera_data *cam, const medi
     }
     free_tree(&t);
     free_ctx(&cfg->base.base.base, &T, &M);
+}
+
+void medium_trace(const rt_scene_desc *sc, const rt_camera_data *cam, const medium_cfg *cfg, int64_t count, const int32_t *ijs, float *radiance, int32_t *rays,
+                  int32_t *events, int32_t *ends, uint32_t *seeds4, int32_t linear) {
+    medium_trace_stats(sc, cam, cfg, count, ijs, radiance, rays, events, ends, seeds4, linear, NULL);
 }
 
 typedef struct {

@@ -56,13 +56,14 @@ def device_keywords(setting, env):
     return kw
 
 
-def radiances(host, cam, samples, sample_first=0, rows=None, **kw):
+def radiances(host, cam, samples, sample_first=0, rows=None, tracer=None, **kw):
     """Per-sample radiances of rt_render_lit's estimator: (len(rows), W, samples, 3) float32 for samples sample_first … + samples - 1 of every
-    pixel of the image rows `rows` (default: all).  ijs rows are (column, row, sample)."""
+    pixel of the image rows `rows` (default: all).  ijs rows are (column, row, sample).  tracer: the restatement whose first column is the
+    radiance (default tree_reference.trace; gloss_reference.trace for the glossy switches)."""
     rows = list(range(cam.image_height)) if rows is None else list(rows)
     jj, ii, ss = np.meshgrid(np.asarray(rows), np.arange(cam.image_width), sample_first + np.arange(samples), indexing="ij")
     ijs = np.stack([ii.ravel(), jj.ravel(), ss.ravel()], axis=1).astype(np.int32)
-    rad = tr.trace(host, cam, ijs, **kw)[0]
+    rad = (tracer or tr.trace)(host, cam, ijs, **kw)[0]
     return rad.reshape(len(rows), cam.image_width, samples, 3)
 
 
@@ -77,10 +78,10 @@ def from_radiances(rad, min_spp, batch_spp, max_spp, threshold):
     return fb.reshape(rows, w, 3), n.astype(np.int32).reshape(rows, w), np.stack([s1, s2], axis=1).astype(F).reshape(rows, w, 2)
 
 
-def reference(host, cam, min_spp, batch_spp, max_spp, threshold, sample_first=0, shard=None, **kw):
-    """What render_lit_adaptive_to_host returns (without the timing), from the restatement."""
+def reference(host, cam, min_spp, batch_spp, max_spp, threshold, sample_first=0, shard=None, tracer=None, **kw):
+    """What render_lit_adaptive_to_host returns (without the timing), from the restatement (tracer: radiances')."""
     total = min_spp + (max_spp - min_spp) // batch_spp * batch_spp
-    rad = radiances(host, cam, total, sample_first, er.image_rows(cam, shard), **kw)
+    rad = radiances(host, cam, total, sample_first, er.image_rows(cam, shard), tracer=tracer, **kw)
     return from_radiances(rad, min_spp, batch_spp, max_spp, threshold)
 
 

@@ -6,7 +6,10 @@ reach them.
 What a scene is made of follows the clauses of include/rtp_amd.h that no hand-made scene exercises: points inside an emissive sphere (a
 dome), overlapping, concentric and touching emitters, coincident emissive planes, degenerate planes between table entries (gaps), an
 emissive plane of an unsupported type, a DIFFUSE_LIGHT that emits nothing, scattering materials that emit, emit with zero channels and
-weights over many decades."""
+weights over many decades.
+
+DESIGN.md §27 adds, for the glossy (§23) and the medium (§25) kernels: gloss_case — a glossy twin of every trial —, fuzz_medium — one
+medium per trial —, the glossy switches and the medium in the dispatch rule, and the call lists of tests/test_lit_fuzz_gloss_medium.py."""
 import collections
 import functools
 
@@ -17,6 +20,7 @@ import rtp_bindings as rb
 import tree_reference as tr
 
 MAT_LAMBERTIAN, MAT_METAL, MAT_DIELECTRIC, MAT_LIGHT = 0, 1, 2, 3
+RT_GLOSSY_MIN_FUZZ = 2.0 ** -10
 QUAD, ELLIPSE, TRIANGLE, UNSUPPORTED = 0, 1, 2, 3
 
 # material slots of a fuzz scene
@@ -67,9 +71,10 @@ def random_env(rng, trial):
     return m.astype(np.float32)
 
 
-def random_lit_scene(rng, trial, dark=False):
+def random_lit_scene(rng, trial, dark=False, remat=None):
     """An rb.HostScene of 3 – 40 random spheres and 0 – 14 random planes (none on one trial in four), about a third of them emissive, plus
-    what `trial` adds.  dark: the same scene with every emit zeroed — its emitter table is empty."""
+    what `trial` adds.  dark: the same scene with every emit zeroed — its emitter table is empty.  remat(spheres, planes, mats): called
+    after the last draw from rng, it may re-material the lists in place (gloss_case's rule; it has no access to rng)."""
     u = rng.uniform
     mats = [None] * 12
     mats[M_LAMB_A] = material(MAT_LAMBERTIAN, u(0.2, 0.9, 3))
@@ -121,6 +126,8 @@ def random_lit_scene(rng, trial, dark=False):
     if dark:
         for m in mats:
             m.emit.e[0] = m.emit.e[1] = m.emit.e[2] = 0.0
+    if remat is not None:
+        remat(spheres, planes, mats)
     return rb.HostScene.from_arrays(np.array(spheres, np.float32), np.array(planes, np.float32).reshape(-1, 11), mats)
 
 
@@ -128,11 +135,11 @@ class Case:
     """One fuzz case: the scene and everything a call on it needs.  camera(w, h, spp, depth) → the open camera, close(…) → the camera at
     shutter close (None on the trials without motion); env: an (n, n, 3) map or None; rot: the 9 floats of rt_env_params.rot."""
 
-    def __init__(self, trial, dark=False):
+    def __init__(self, trial, dark=False, remat=None):
         self.trial = trial
         self.seed = SEEDS[trial]
         rng = np.random.default_rng([self.seed, trial])
-        self.host = random_lit_scene(rng, trial, dark)
+        self.host = random_lit_scene(rng, trial, dark, remat)
         d = rng.normal(size=3)
         d[1] = abs(d[1]) + 0.3
         self.eye = tuple(float(x) for x in 9.0 * d / np.linalg.norm(d))
@@ -229,24 +236,36 @@ NEE_FRAME, NEE_PROBE, ENV_FRAME, ENV_PROBE, LIT_FRAME, LIT_PROBE, LIT_ADAPTIVE =
                                                                                  "rt_trace_samples_lit", "rt_render_lit_adaptive")
 
 
-def kernels_of(entry, lens=False, sample_planes=0, select=0, table_has_plane=False, table_entries=1):
+MEDIUM_FRAME, MEDIUM_PROBE = "rt_render_medium", "rt_trace_samples_medium"
+
+
+def kernels_of(entry, lens=False, sample_planes=0, select=0, table_has_plane=False, table_entries=1, glossy_nee=0, glossy_env=0, medium_on=False,
+               emitters=True, env=False):
     """The kernels a call launches, as a tuple of names with their template arguments: rt_capi.hip's rule.  lens: the call has a lens
     radius > 0 or a closing camera; table_has_plane: the two-kind table holds a plane; table_entries: the length of the table the
-    call selects (0: the tree kernels are not used, rt_capi.hip's tree_on)."""
+    call selects (0: the tree kernels are not used, rt_capi.hip's tree_on).  glossy_nee / glossy_env: rt_nee_params.glossy and
+    rt_env_params.glossy; env: the call has an environment; emitters: rt_lit_params.sample_emitters (the lit and medium calls; off: the
+    empty sphere-only table, with_emitter_table's first line); medium_on: sigma_t > 0 (the medium calls)."""
     planes = bool(sample_planes) and table_has_plane                       # emit_planes_on
     tree = select == 1 and table_entries > 0                               # tree_on
     if entry in (ENV_FRAME, ENV_PROBE):
-        return ("light_render_kernel<EnvDev>",) if entry == ENV_FRAME else ("light_probe_kernel<EnvDev>",)
+        return (f"light_{'gloss_' if glossy_env else ''}{'render' if entry == ENV_FRAME else 'probe'}_kernel<EnvDev>",)
     table = ("TreeEmitTable" if planes else "TreeTable") if tree else ("EmitTable" if planes else "NeeTable")     # with_emitter_table
     if entry in (NEE_FRAME, NEE_PROBE):
-        return (f"light_{'render' if entry == NEE_FRAME else 'probe'}_kernel<{table}>",)
+        return (f"light_{'gloss_' if glossy_nee else ''}{'render' if entry == NEE_FRAME else 'probe'}_kernel<{table}>",)
+    if not emitters:
+        table = "NeeTable"
     args = f"<{'true' if lens else 'false'}, {table}>"
-    if entry == LIT_FRAME:
-        return (f"lit_render_kernel{args}",)
-    if entry == LIT_PROBE:
-        return (f"lit_probe_kernel{args}",)
+    gn, ge = bool(emitters and glossy_nee), bool(env and glossy_env)        # with_lit, with_medium_lit
+    if entry in (MEDIUM_FRAME, MEDIUM_PROBE) and medium_on:                 # sigma_t > 0: the medium kernels whatever the switches are
+        return (f"medium_{'render' if entry == MEDIUM_FRAME else 'probe'}_kernel{args}",)
+    lit = "lit_gloss" if gn or ge else "lit"
+    if entry in (LIT_FRAME, MEDIUM_FRAME):
+        return (f"{lit}_render_kernel{args}",)
+    if entry in (LIT_PROBE, MEDIUM_PROBE):
+        return (f"{lit}_probe_kernel{args}",)
     assert entry == LIT_ADAPTIVE, entry
-    return (f"lit_render_kernel{args}", f"lit_list_render_kernel{args}")
+    return (f"{lit}_render_kernel{args}", f"{lit}_list_render_kernel{args}")
 
 
 def all_kernels():
@@ -255,6 +274,21 @@ def all_kernels():
     out = [f"light_{k}_kernel<{t}>" for t in tables + ("EnvDev",) for k in ("render", "probe")]
     out += [f"lit_{k}_kernel<{l}, {t}>" for k in ("render", "list_render", "probe") for l in ("true", "false") for t in tables]
     return sorted(out)
+
+
+TABLES = ("NeeTable", "EmitTable", "TreeTable", "TreeEmitTable")
+
+
+def all_gloss_kernels():
+    """The glossy instantiations: 34."""
+    out = [f"light_gloss_{k}_kernel<{t}>" for t in TABLES + ("EnvDev",) for k in ("render", "probe")]
+    out += [f"lit_gloss_{k}_kernel<{l}, {t}>" for k in ("render", "list_render", "probe") for l in ("true", "false") for t in TABLES]
+    return sorted(out)
+
+
+def all_medium_kernels():
+    """The medium instantiations: 16."""
+    return sorted(f"medium_{k}_kernel<{l}, {t}>" for k in ("render", "probe") for l in ("true", "false") for t in TABLES)
 
 
 # ---- the calls of the GPU tests: made here once, walked by the coverage test on the CPU and by the GPU tests ------------------------------
@@ -350,4 +384,218 @@ def device_keywords(call, env, w, h, spp, depth):
         kw.update(lens=c.lens_dict(), cam_close=c.close(w, h, spp, depth))
     if call.env is not None:
         kw.update(env=env, env_params=c.env_params(call.env))
+    return kw
+
+
+# ---- glossy twins and random media ---------------------------------------------------------------------------------------
+# The twin of a trial: the same draws — geometry, emitter table, tree, camera, lens, map and rotation — with the non-emissive materials made
+# METAL afterwards.  The fuzz values over the eight twins are exactly GLOSS_FUZZ: 0 and 2^-11 (mirrors for the switch), 2^-10 (the
+# threshold itself: a glossy event), 0.05, 0.35, 1.0 (the boundary between pg's two forms) and 1.5 (the vertex inside the lobe's ball).
+M_GLOSS_GROUND = 12
+GLOSS_FUZZ = (0.0, 2.0 ** -11, 2.0 ** -10, 0.05, 0.35, 1.0, 1.5)
+# the twins that carry the narrow lobes (fuzz < 0.3); the others have 0.35, 1.0 and 1.5 alone, so that a light-only estimator's weight
+# pg / pl stays bounded by pg <= (3 + fuzz^2) / (2 pi fuzz^2) < 4.1 there (test_lit_fuzz_gloss_medium.py's light-only comparison needs that).
+# 0 and 6 are the dome with the faint sphere, where light-only weights are unbounded anyway; 7 has a map, so that the threshold fuzz
+# meets the environment's switch too
+NARROW_TRIALS = (0, 6, 7)
+
+
+def gloss_rule(seed, trial):
+    """The re-materialling of a twin, a function of (seed, trial) alone; its draws (the albedos) come from a generator of its own.
+    On NARROW_TRIALS: M_LAMB_A → METAL of fuzz 2^-11, M_LAMB_B → 2^-10, M_METAL → 0.05 (trial 6: fuzz 0); on the others M_LAMB_A → 1.0,
+    M_LAMB_B → 1.5 and M_METAL → 0.35.  Everywhere M_GROUND and, on the odd trials, an added ground sphere (the last sphere: no index
+    of the table moves) → 0.35, and M_LIGHT_DARK → 1.5 (trial 0: 1.0)."""
+    g = np.random.default_rng([seed, trial, 23])
+    narrow = trial in NARROW_TRIALS
+
+    def remat(spheres, planes, mats):
+        def metal(fuzz):
+            return material(MAT_METAL, g.uniform(0.6, 0.95, 3), fuzz=fuzz)
+        mats[M_LAMB_A] = metal(2.0 ** -11 if narrow else 1.0)
+        mats[M_LAMB_B] = metal(2.0 ** -10 if narrow else 1.5)
+        mats[M_METAL] = metal((0.0 if trial == 6 else 0.05) if narrow else 0.35)
+        mats[M_GROUND] = metal(0.35)
+        mats[M_LIGHT_DARK] = metal(1.0 if trial == 0 else 1.5)
+        mats.append(metal(0.35))
+        if trial % 2 == 1:
+            spheres.append([0.0, -1006.0, 0.0, 1000.0, M_GLOSS_GROUND])
+    return remat
+
+
+@functools.lru_cache(maxsize=None)
+def gloss_case(trial):
+    c = Case(trial, remat=gloss_rule(SEEDS[trial], trial))
+    c.name = f"twin {trial} seed {c.seed}"
+    return c
+
+
+def fuzz_medium(trial):
+    """The medium of a trial (medium_reference / rb.medium_params keywords), a function of (SEEDS[trial], trial) alone with a generator of
+    its own.  Over the eight: all space on two trials with a map (2, 5: the environment is not sampled there), balls (0: around the eye;
+    4: optically thick, albedo 1 — paths end by depth inside it; 6) and boxes (1: half the scene, an albedo with a channel of exactly 0
+    and one of exactly 1; 3: around the eye; 7: drawn), g over {0, 0.7, -0.5, 0.95, -0.95}, sigma_t from 0.02 to 5."""
+    c = case(trial)
+    g = np.random.default_rng([SEEDS[trial], trial, 25])
+    eye = np.array(c.eye, np.float32)
+    alb = tuple(float(np.float32(x)) for x in g.uniform(0.7, 0.98, 3))
+    r = float(np.float32(g.uniform(2.0, 3.0)))
+    centre = tuple(float(np.float32(x)) for x in g.uniform(-2.0, 2.0, 3))
+    lo = g.uniform(-5.0, -1.0, 3)
+    hi = lo + g.uniform(3.0, 6.0, 3)
+    if trial == 0:
+        return dict(sigma_t=0.3, albedo=alb, g=0.7, ball=(float(eye[0]), float(eye[1]), float(eye[2]), 4.0))
+    if trial == 1:
+        return dict(sigma_t=0.25, albedo=(1.0, 0.9, 0.0), g=-0.5, box=(-5.5, -5.5, -5.5, 0.5, 5.5, 5.5))
+    if trial == 2:
+        return dict(sigma_t=0.02, albedo=alb, g=0.95)
+    if trial == 3:
+        return dict(sigma_t=0.4, albedo=alb, g=-0.95, box=tuple(float(x) for x in np.concatenate([eye - np.float32(3.0), eye + np.float32(3.0)])))
+    if trial == 4:
+        return dict(sigma_t=5.0, albedo=1.0, g=0.0, ball=(0.0, 0.0, 0.0, 3.5))
+    if trial == 5:
+        return dict(sigma_t=0.1, albedo=alb, g=0.7)
+    if trial == 6:
+        return dict(sigma_t=1.0, albedo=alb, g=-0.5, ball=centre + (r,))
+    return dict(sigma_t=0.6, albedo=alb, g=0.95, box=tuple(float(np.float32(x)) for x in np.concatenate([lo, hi])))
+
+
+def medium_extent(m):
+    """The region's largest chord (None: all space)."""
+    if m.get("ball") is not None:
+        return 2.0 * m["ball"][3]
+    if m.get("box") is not None:
+        return float(np.linalg.norm(np.array(m["box"][3:]) - np.array(m["box"][:3])))
+    return None
+
+
+def inside_medium(m, p):
+    if m.get("ball") is not None:
+        return float(np.sum((np.asarray(p, np.float64) - np.array(m["ball"][:3])) ** 2)) < m["ball"][3] ** 2
+    if m.get("box") is not None:
+        return all(m["box"][k] < p[k] < m["box"][3 + k] for k in range(3))
+    return True
+
+
+# A call on a twin.  gn, ge: rt_nee_params.glossy and rt_env_params.glossy; medium: the call goes to rt_render_medium /
+# rt_trace_samples_medium under fuzz_medium(trial); the rest as in Call
+GCall = collections.namedtuple("GCall", "test entry trial lens planes select mis env shard gn ge medium")
+
+
+def _gloss_cells(test, trial, nee_entry, env_entry, lit_entry):
+    """The glossy calls of one twin: the eight nee settings, the environment in both modes, and every (lens, planes, select) of the lit
+    call with the emitters' switch alone and no environment and — where the trial has a map — with the environment's switch alone and
+    with both."""
+    c = gloss_case(trial)
+    out = [GCall(test, nee_entry, trial, False, planes, select, mis, None, None, 1, 0, False) for mis, planes, select in MIS_PLANES_SELECT]
+    if c.env is not None:
+        out += [GCall(test, env_entry, trial, False, 0, 0, 1, mode, None, 0, 1, False) for mode in (1, 2)]
+    for planes, select in PLANES_SELECT:
+        for lens in (True, False):
+            mis = 1 if lens else 0
+            out.append(GCall(test, lit_entry, trial, lens, planes, select, mis, None, None, 1, 0, False))
+            if c.env is not None:
+                mode = 1 if select else 2
+                out.append(GCall(test, lit_entry, trial, lens, planes, select, mis, mode, None, 0, 1, False))
+                out.append(GCall(test, lit_entry, trial, lens, planes, select, 1, mode, None, 1, 1, False))
+    return out
+
+
+def gloss_probe_calls(trial):
+    return _gloss_cells("gloss probes", trial, NEE_PROBE, ENV_PROBE, LIT_PROBE)
+
+
+def _medium_cells(test, trial, entry):
+    """The medium calls of one twin under fuzz_medium(trial): every (lens, planes, select) without an environment and, where the trial has
+    a map, with it; the glossy switches alternate."""
+    c = gloss_case(trial)
+    out = []
+    for planes, select in PLANES_SELECT:
+        for lens in (True, False):
+            gn = (trial + planes + int(lens)) % 2
+            out.append(GCall(test, entry, trial, lens, planes, select, 1 if lens else 0, None, None, gn, 0, True))
+            if c.env is not None:
+                out.append(GCall(test, entry, trial, lens, planes, select, 1, 1 if select else 2, None, 1 - gn, (trial + select) % 2, True))
+    return out
+
+
+def medium_probe_calls(trial):
+    return _medium_cells("medium probes", trial, MEDIUM_PROBE)
+
+
+@functools.lru_cache(maxsize=None)
+def _all_gloss_frame_calls():
+    """The frame cells of every twin, glossy and medium; each kernel's calls go through SHARDS in turn."""
+    turn, out = collections.Counter(), {"gloss": {}, "medium": {}}
+    for t in TRIALS:
+        for which, cells in (("gloss", _gloss_cells("gloss frames", t, NEE_FRAME, ENV_FRAME, LIT_FRAME)), ("medium", _medium_cells("medium frames", t, MEDIUM_FRAME))):
+            out[which][t] = []
+            for c in cells:
+                k = kernels_of_gcall(c)[0]
+                out[which][t].append(c._replace(shard=turn[k] % 3))
+                turn[k] += 1
+    return out
+
+
+def gloss_frame_calls(trial):
+    return list(_all_gloss_frame_calls()["gloss"][trial])
+
+
+def medium_frame_calls(trial):
+    return list(_all_gloss_frame_calls()["medium"][trial])
+
+
+def gloss_adaptive_calls(trial):
+    """rt_render_lit_adaptive on a twin: every (lens, planes, select) with the emitters' switch alone and no environment, the
+    environment's alone, and both (the adaptive trials all have a map)."""
+    c = gloss_case(trial)
+    assert c.env is not None
+    out = []
+    for lens in (False, True):
+        for planes, select in PLANES_SELECT:
+            out += [GCall("gloss adaptive", LIT_ADAPTIVE, trial, lens, planes, select, 1, env, None, gn, ge, False)
+                    for env, gn, ge in ((None, 1, 0), (1, 0, 1), (1, 1, 1))]
+    return out
+
+
+def gloss_calls():
+    """Every call the GPU tests of test_lit_fuzz_gloss_medium.py make on the glossy and medium kernels."""
+    out = []
+    for t in TRIALS:
+        out += gloss_probe_calls(t) + gloss_frame_calls(t) + medium_probe_calls(t) + medium_frame_calls(t)
+    for t in ADAPTIVE_TRIALS:
+        out += gloss_adaptive_calls(t)
+    return out
+
+
+def kernels_of_gcall(call):
+    c = gloss_case(call.trial)
+    has = c.has_planes(1)
+    return kernels_of(call.entry, call.lens, call.planes, call.select, has, c.entries(1 if (call.planes and has) else 0), glossy_nee=call.gn,
+                      glossy_env=call.ge, medium_on=call.medium and fuzz_medium(call.trial)["sigma_t"] > 0, emitters=True, env=call.env is not None)
+
+
+def gloss_reference_keywords(call, w, h, spp, depth):
+    """gloss_reference / medium_reference trace / frame keywords of a lit, nee or medium call on a twin (the camera apart)."""
+    c = gloss_case(call.trial)
+    kw = dict(select=call.select, nee_mis=call.mis, planes=call.planes, glossy=call.gn, glossy_env=call.ge)
+    if call.lens:
+        kw.update(lens=c.lens, cam_close=c.close(w, h, spp, depth))
+    if call.env is not None:
+        kw.update(rgb=c.env, env_params=c.env_params(call.env))
+    if call.medium:
+        kw.update(medium=fuzz_medium(call.trial))
+    return kw
+
+
+def gloss_device_keywords(call, env, w, h, spp, depth):
+    """DeviceScene.render_lit / trace_samples_lit / render_medium / … keywords of a lit or medium call on a twin; env: an rb.Env of the
+    twin's map (or None)."""
+    c = gloss_case(call.trial)
+    kw = dict(nee={"mis": call.mis, "sample_planes": call.planes, "select": call.select, "glossy": call.gn})
+    if call.lens:
+        kw.update(lens=c.lens_dict(), cam_close=c.close(w, h, spp, depth))
+    if call.env is not None:
+        kw.update(env=env, env_params=dict(glossy=call.ge, **c.env_params(call.env)))
+    if call.medium:
+        kw.update(medium=fuzz_medium(call.trial))
     return kw

@@ -17,6 +17,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 _lib = None
 # how a path ended (medium_ref.c's med_out.end)
 END_MISS, END_DEPTH, END_ABSORBED, END_BLACK = range(4)
+# medium_ref.c's tallies, in its order (trace(stats=True) adds a dict of them; they only count)
+STATS = ("events", "interval_empty", "origin_inside", "box_parallel_in", "box_parallel_out", "u_zero", "event_at_depth_cut", "black", "tr_emitter",
+         "tr_env", "env_suppressed", "carry_hit", "carry_miss", "glossy_inside", "event_first_ray")
 
 
 class MediumCfg(C.Structure):
@@ -40,6 +43,8 @@ def lib():
         l.medium_intervals.argtypes = [C.POINTER(rb.MediumParams), C.c_int64] + [C.c_void_p] * 6
         l.medium_trace.restype = None
         l.medium_trace.argtypes = [desc, cam, cfg, C.c_int64] + [C.c_void_p] * 6 + [C.c_int32]
+        l.medium_trace_stats.restype = None
+        l.medium_trace_stats.argtypes = [desc, cam, cfg, C.c_int64] + [C.c_void_p] * 6 + [C.c_int32, C.c_void_p]
         l.medium_frame.restype = None
         l.medium_frame.argtypes = [desc, cam, cfg, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         _lib = l
@@ -106,15 +111,20 @@ def _cfg(medium, glossy, glossy_env, select, cam_close, lens, emitters, nee_mis,
 
 
 def trace(host, cam, ijs, medium=None, glossy=0, glossy_env=0, select=0, cam_close=None, lens=None, emitters=True, nee_mis=1, planes=0, rgb=None,
-          env_params=None, linear=True):
+          env_params=None, linear=True, stats=False):
     """gloss_reference.trace under the medium → (radiance (m, 3), rays, medium events, ends (END_*), seeds (m, 4) uint32: path, nee, env,
-    med)."""
+    med); stats=True adds a dict of the tallies in STATS, summed over the samples."""
     c, keep = _cfg(medium, glossy, glossy_env, select, cam_close, lens, emitters, nee_mis, planes, rgb, env_params)
     ijs = np.ascontiguousarray(ijs, dtype=np.int32).reshape(-1, 3)
     m = ijs.shape[0]
     rad = np.empty((m, 3), np.float32)
     rays, events, ends = np.empty(m, np.int32), np.empty(m, np.int32), np.empty(m, np.int32)
     seeds = np.empty((m, 4), np.uint32)
+    if stats:
+        st = np.zeros(len(STATS), np.int64)
+        lib().medium_trace_stats(C.byref(host.desc), C.byref(cam), C.byref(c), m, ijs.ctypes.data, rad.ctypes.data, rays.ctypes.data, events.ctypes.data,
+                                 ends.ctypes.data, seeds.ctypes.data, 1 if linear else 0, st.ctypes.data)
+        return rad, rays, events, ends, seeds, {k: int(x) for k, x in zip(STATS, st)}
     lib().medium_trace(C.byref(host.desc), C.byref(cam), C.byref(c), m, ijs.ctypes.data, rad.ctypes.data, rays.ctypes.data, events.ctypes.data,
                        ends.ctypes.data, seeds.ctypes.data, 1 if linear else 0)
     return rad, rays, events, ends, seeds
