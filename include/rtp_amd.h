@@ -1148,7 +1148,7 @@ rt_status rt_render_lit_adaptive_prior(rt_scene *scene, const rt_camera_data *ca
  * Identities, bit for bit: medium == NULL or sigma_t == 0 = rt_render_lit with the same lit (and every probe column: medium_events 0, the
  *   med state as initialised).  sigma_t > 0 with a region that no path ray and no shadow ray of the frame touches = rt_render_lit as well,
  *   through the medium's own kernels.
- * Left out: heterogeneous or chromatic extinction; more than one region; regions bounded by scene surfaces (fog inside a glass ball that
+ * Left out: ~~heterogeneous~~ (rt_render_volume, "density grid" below) or chromatic extinction; more than one region; regions bounded by scene surfaces (fog inside a glass ball that
  *   sits in the region is still fog); emission in the medium; the guarded walk; tiles and rt_context; rt_render_lit_adaptive with a
  *   medium, AOVs of the medium and the denoisers' handling of it (the first-hit AOVs do not see it).
  * Checks, all before anything is enqueued: rt_render_lit's parameter checks come first, in its order (lens, nee, env_params); then the
@@ -1175,6 +1175,62 @@ rt_status rt_render_medium(rt_scene *scene, const rt_camera_data *cam_open, cons
 rt_status rt_trace_samples_medium(rt_scene *scene, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium,
                                   int32_t n, const int32_t *ijs, float *radiance, int32_t *rays, int32_t *medium_events,
                                   uint32_t *final_seed, uint32_t *final_nee_seed, uint32_t *final_env_seed, uint32_t *final_medium_seed);
+
+/* ---- density grid ------------------------------------------------------------------------------------------------
+ * rt_render_medium's estimator with a HETEROGENEOUS extinction in its box region: the density is piecewise constant on a regular grid of
+ * nx * ny * nz cells that fills the box, and cell c has the extinction sigma_c = sigma_t * rho_c (one float32 product).  Albedo and g stay
+ * the medium's.  Everything of "participating medium" holds as written there — the stream, the interval, the medium vertex, the light
+ * samples, the MIS weights — except the two places where the extinction enters: the free flight of a path ray and the optical depth
+ * of a shadow ray.  Both run ONE walk through the cells the ray's interval crosses (regular tracking: the free flight is exact by
+ * inversion with a single draw of med, the optical depth is a deterministic sum).  float32 in the order written, nothing fused, division
+ * correctly rounded.
+ *
+ * Walk of the ray o + t d over its interval [t0, t1] = interval(o, d, t_end) of the box (lo = a, hi = b), len = sqrtf(lensq(d)).  An empty
+ *   interval: no walk, no draw, no cells.  Per axis k with n_k cells:
+ *   w_k = (hi_k - lo_k) / (float)n_k;  plane_k(m) = lo_k for m == 0, hi_k for m == n_k (the box's own face, not lo + n * w), otherwise
+ *     lo_k + (float)m * w_k.
+ *   Entry: p_k = o_k + t0 * d_k; c_k = (int)floorf((p_k - lo_k) / w_k), clamped to [0, n_k - 1].
+ *   tnext_k = (plane_k(c_k + 1) - o_k) / d_k for d_k > 0, (plane_k(c_k) - o_k) / d_k for d_k < 0, +inf for d_k == 0: recomputed from the
+ *     plane at every cell, never accumulated.
+ *   Per cell: ta = the previous cell's tb (t0 at the first cell).  tm = tnext_x, axis x; ty < tm: tm = ty, axis y; tz < tm: tm = tz, axis z
+ *     (ties go to x before y before z).  tb = tm < t1 ? tm : t1, raised to ta when below it.  seg = (tb - ta) * len (never negative).  The
+ *     cell (c_x, c_y, c_z) is visited with seg (below).  The walk stops when tb >= t1; otherwise c_axis moves by one in the direction of
+ *     d_axis, and the walk stops when that leaves the grid.  One axis moves per step, so a walk visits at most n_x + n_y + n_z cells, and
+ *     the walk is cut there.
+ * Free flight (every finished PATH ray with a non-empty interval).  u = random_float(med); u == 0: no event and no walk.  rem =
+ *   -log_libm(u).  A visited cell with sigma_c > 0: s = rem / sigma_c; s < seg: an event at t = ta + s / len, x = o + t * d (componentwise
+ *   o_k + t * d_k), and the walk ends; otherwise rem = rem - sigma_c * seg.  A cell with sigma_c == 0 changes nothing.  No event in any
+ *   cell: the surface vertex (or the miss) of rt_render_lit with unchanged throughput.  The medium vertex at x is rt_render_medium's.
+ * Transmittance (the two shadow verdicts).  acc = 0; every visited cell: acc = acc + sigma_c * seg, in visit order; Tr = exp_libm(-acc).
+ *   An empty interval: Tr = 1 exactly, exp is not called.
+ *
+ * Identities, bit for bit: a 1 x 1 x 1 grid of density 1 = rt_render_medium with the same box (through the grid's own kernels: tnext of
+ *   the only cell is the box's own exit, so tb = t1 and seg = (t1 - t0) * len).  volume == NULL = rt_render_medium with the same
+ *   arguments, whatever its region.  sigma_t == 0 = rt_render_lit.  A grid of zeros = rt_render_lit in radiance, rays and the path, nee
+ *   and env streams; med advances one draw per non-empty path interval.
+ * Left out: chromatic extinction; more than one region or grid; emission in the medium; interpolation between cells (trilinear or any
+ *   other: the density is piecewise constant); rt_render_lit_adaptive with a grid; AOVs of the medium; tiles and rt_context.
+ * rt_volume: the grid on the device it was created on (the calling thread's current one), like an rt_env.  density is HOST memory, nx * ny
+ *   * nz floats, copied: cell (x, y, z) at (z * ny + y) * nx + x.  RT_ERR_INVALID_ARG for a null pointer, a dimension below 1 or above
+ *   RT_VOLUME_MAX_N, a density that is negative, NaN or infinite.  A volume outlives every call that was given it; destroy it after the
+ *   last such call has finished.  A volume on another device than the scene is refused.
+ * Checks of the calls, all before anything is enqueued: rt_render_medium's, in its order up to and including the medium's; then, with a
+ *   volume, RT_ERR_INVALID_ARG unless medium is given with region == 2; then the null scene and the volume's device against the scene's; then the scene's and the camera's as in rt_render_lit.  Rows
+ *   of a shard only: no tiles, no rt_context.  Handle state and timing: as rt_render_lit. */
+#define RT_VOLUME_MAX_N 256
+typedef struct rt_volume rt_volume;
+rt_status rt_volume_create(const float *density, int32_t nx, int32_t ny, int32_t nz, rt_volume **out_volume);
+rt_status rt_volume_destroy(rt_volume *volume);
+/* rt_render_medium with the grid in the medium's box (volume NULL: rt_render_medium itself). */
+rt_status rt_render_volume(rt_scene *scene, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium,
+                           const rt_volume *volume, const rt_shard *shard, int32_t sample_first, float *d_fb_sum, void *hip_stream,
+                           int32_t sync, rt_timing *timing);
+/* Probe for tests, HOST memory: rt_trace_samples_medium's columns for the estimator of rt_render_volume, and cells: the grid cells
+ * visited per sample, path rays and shadow rays together (0 without a volume).  It only counts. */
+rt_status rt_trace_samples_volume(rt_scene *scene, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium,
+                                  const rt_volume *volume, int32_t n, const int32_t *ijs, float *radiance, int32_t *rays,
+                                  int32_t *medium_events, uint32_t *final_seed, uint32_t *final_nee_seed, uint32_t *final_env_seed,
+                                  uint32_t *final_medium_seed, int32_t *cells);
 
 /* Milliseconds of the most recent rt_render kernel of this scene (waits for it). */
 rt_status rt_last_kernel_ms(rt_scene *scene, float *ms);

@@ -21,6 +21,7 @@
 #include "rt_env.hip.inc"
 #include "rt_light.hip.inc"
 #include "rt_medium.hip.inc"
+#include "rt_volume.hip.inc"
 // Developer build only (make dev → librtp_amd_dev.so, -DRTP_DEV_BUILD): the rt_debug_* entry points (exhaustive on-device checks of
 // recip / sqrt_cr / sphere_root, the device LBVH builder on its own, the tripwire, the RTP_STATS counters) at the end of this file.
 // The shipped library contains none of them.
@@ -3419,6 +3420,144 @@ rt_status rt_trace_samples_medium(rt_scene *sc, const rt_camera_data *cam_open, 
     if (hipMemcpy(final_medium_seed, d_med, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess ||
         hipMemcpy(medium_events, d_events, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess)
         return fail(RT_ERR_HIP, "rt_trace_samples_medium: hipMemcpy D2H failed");
+    return RT_OK;
+}
+
+// ---- rt_volume / rt_render_volume / rt_trace_samples_volume (rtp_amd.h, "density grid"): rt_render_medium with a density
+// grid in its box.  No volume is rt_render_medium itself, sigma_t == 0 rt_render_lit; otherwise the kernels of rt_volume.hip.inc.
+struct rt_volume {
+    int device = 0;
+    int32_t nx = 0, ny = 0, nz = 0;
+    float *rho = nullptr;              // nx * ny * nz, x fastest
+};
+
+rt_status rt_volume_create(const float *density, int32_t nx, int32_t ny, int32_t nz, rt_volume **out_volume) {
+    if (!density || !out_volume) return fail(RT_ERR_INVALID_ARG, "rt_volume_create: null argument");
+    *out_volume = nullptr;
+    if (nx < 1 || ny < 1 || nz < 1 || nx > RT_VOLUME_MAX_N || ny > RT_VOLUME_MAX_N || nz > RT_VOLUME_MAX_N)
+        return fail(RT_ERR_INVALID_ARG, "rt_volume_create: every dimension must be 1 … " + std::to_string(RT_VOLUME_MAX_N));
+    const size_t count = (size_t)nx * (size_t)ny * (size_t)nz;
+    for (size_t k = 0; k < count; ++k)
+        if (!(std::isfinite(density[k]) && density[k] >= 0.0f)) return fail(RT_ERR_INVALID_ARG, "rt_volume_create: a density is negative, NaN or infinite");
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(RT_ERR_NO_DEVICE, "rt_volume_create: no current HIP device");
+    }
+    rt_volume *vol = new (std::nothrow) rt_volume();
+    if (!vol) return fail(RT_ERR_OUT_OF_MEMORY, "rt_volume_create: out of host memory");
+    vol->device = dev;
+    vol->nx = nx;
+    vol->ny = ny;
+    vol->nz = nz;
+    const rt_status st = upload(std::vector<float>(density, density + count), (void **)&vol->rho);
+    if (st != RT_OK) {
+        (void)rt_volume_destroy(vol);
+        return st;
+    }
+    *out_volume = vol;
+    return RT_OK;
+}
+
+rt_status rt_volume_destroy(rt_volume *volume) {
+    if (!volume) return RT_OK;
+    (void)hipFree(volume->rho);
+    delete volume;
+    return RT_OK;
+}
+
+namespace {
+// the volume's check among the parameters (after the medium's, before the scene is looked at)
+rt_status volume_setup(const char *what, const rt_medium_params *medium, const rtk::MediumDev &M, const rt_volume *volume) {
+    if (volume && !(medium && M.region == 2)) return fail(RT_ERR_INVALID_ARG, std::string(what) + ": a volume needs a medium with region 2 (the box the grid fills)");
+    return RT_OK;
+}
+// with_medium_lit with the grid beside the medium
+extern "C++" template <class F>
+rt_status with_volume_lit(rt_scene *sc, const LitSetup &S, const rtk::MediumDev &M, const rt_volume *volume, F &&f) {
+    return with_medium_lit(sc, S, M, [&](const auto &ML) {
+        using Table = std::decay_t<decltype(ML.G.N)>;
+        rtk::VolumeLit<Table> T{};
+        T.G = ML.G;
+        T.M = ML.M;
+        T.V.rho = volume->rho;
+        T.V.nx = volume->nx;
+        T.V.ny = volume->ny;
+        T.V.nz = volume->nz;
+        return f(T);
+    });
+}
+}  // namespace
+
+rt_status rt_render_volume(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium, const rt_volume *volume,
+                           const rt_shard *shard, int32_t sample_first, float *d_fb_sum, void *hip_stream, int32_t sync, rt_timing *timing) {
+    if (!volume) return rt_render_medium(sc, cam_open, lit, medium, shard, sample_first, d_fb_sum, hip_stream, sync, timing);
+    LitSetup S;
+    if (const rt_status st = lit_setup("rt_render_volume", cam_open, lit, S)) return st;
+    rtk::MediumDev M{};
+    if (const rt_status st = medium_setup("rt_render_volume", medium, M)) return st;
+    if (const rt_status st = volume_setup("rt_render_volume", medium, M, volume)) return st;
+    if (!sc) return fail(RT_ERR_INVALID_ARG, "rt_render_volume: null scene");
+    if (volume->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_render_volume: the volume was created on another device than the scene");
+    auto with_light = [&](auto frame) {
+        if (!(M.sigma_t > 0.0f))
+            return with_lit(sc, S, [&](const auto &T) { return frame(S.lens ? rtk::lit_frame_kernel_of<true>(T) : rtk::lit_frame_kernel_of<false>(T), &T); });
+        return with_volume_lit(sc, S, M, volume, [&](const auto &T) {
+            using Table = decltype(T.G.N);
+            return frame(S.lens ? (const void *)rtk::volume_render_kernel<true, Table> : (const void *)rtk::volume_render_kernel<false, Table>, &T);
+        });
+    };
+    return render_light_impl("rt_render_volume", S.env ? &S.env->device : nullptr, with_light, sc, cam_open, shard, sample_first, d_fb_sum, hip_stream, sync, timing,
+                             &S.C);
+}
+
+rt_status rt_trace_samples_volume(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium, const rt_volume *volume,
+                                  int32_t n, const int32_t *ijs, float *radiance, int32_t *rays, int32_t *medium_events, uint32_t *final_seed,
+                                  uint32_t *final_nee_seed, uint32_t *final_env_seed, uint32_t *final_medium_seed, int32_t *cells) {
+    const char *what = "rt_trace_samples_volume";
+    LitSetup S;
+    if (const rt_status st = lit_setup(what, cam_open, lit, S)) return st;
+    rtk::MediumDev M{};
+    if (const rt_status ms = medium_setup(what, medium, M)) return ms;
+    if (const rt_status vs = volume_setup(what, medium, M, volume)) return vs;
+    if (n < 0 ||
+        (n > 0 && (!ijs || !radiance || !rays || !medium_events || !final_seed || !final_nee_seed || !final_env_seed || !final_medium_seed || !cells)))
+        return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_volume: null argument");
+    rtk::KParams P;
+    rt_status st = fill_params(sc, cam_open, nullptr, P);
+    if (st != RT_OK) return st;
+    if ((st = check_device(sc)) != RT_OK) return st;
+    if (S.env && S.env->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_volume: the environment was created on another device than the scene");
+    if (volume && volume->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_volume: the volume was created on another device than the scene");
+    if (n == 0) return RT_OK;
+    if (!volume || !(M.sigma_t > 0.0f)) {          // no grid, or no medium: rt_trace_samples_medium's columns, no cell
+        if ((st = rt_trace_samples_medium(sc, cam_open, lit, medium, n, ijs, radiance, rays, medium_events, final_seed, final_nee_seed, final_env_seed,
+                                          final_medium_seed)) != RT_OK)
+            return st;
+        for (int32_t k = 0; k < n; ++k) cells[k] = 0;
+        return RT_OK;
+    }
+    uint32_t *d_med = nullptr;
+    int32_t *d_events = nullptr, *d_cells = nullptr;
+    Scratch mem;
+    if (mem.alloc(d_med, (size_t)n * 4) != hipSuccess || mem.alloc(d_events, (size_t)n * 4) != hipSuccess || mem.alloc(d_cells, (size_t)n * 4) != hipSuccess)
+        return fail(RT_ERR_OUT_OF_MEMORY, "rt_trace_samples_volume: hipMalloc failed");
+    st = run_probe("rt_trace_samples_volume: ", P, cam_open, n, ijs, radiance, rays, final_seed, final_nee_seed, final_env_seed,
+                   [&](const rtk::KParams &KP, uint32_t *d_nee, uint32_t *d_env) {
+        return with_volume_lit(sc, S, M, volume, [&](const auto &T) {
+            using Table = decltype(T.G.N);
+            const dim3 grid((n + 255) / 256), block(256);
+            if (S.lens) hipLaunchKernelGGL((rtk::volume_probe_kernel<true, Table>), grid, block, 0, 0, KP, T, S.C, d_nee, d_env, d_med, d_events, d_cells);
+            else hipLaunchKernelGGL((rtk::volume_probe_kernel<false, Table>), grid, block, 0, 0, KP, T, S.C, d_nee, d_env, d_med, d_events, d_cells);
+            return RT_OK;
+        });
+    });
+    if (st != RT_OK) return st;
+    // (run_probe has waited for the device)
+    if (hipMemcpy(final_medium_seed, d_med, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(medium_events, d_events, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(cells, d_cells, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(RT_ERR_HIP, "rt_trace_samples_volume: hipMemcpy D2H failed");
     return RT_OK;
 }
 

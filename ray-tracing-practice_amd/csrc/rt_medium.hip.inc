@@ -1,6 +1,6 @@
 // rt_medium.hip.inc — a homogeneous participating medium on the lit path (rt_render_medium; include/rtp_amd.h, "participating medium";
 // DESIGN.md §25).  Included by rt_capi.hip after rt_light.hip.inc, whose vertex (shade_lit2), camera (lit_start), walk step (lit_step),
-// light samples (light_sample) and pool fetch (RTP_LIT_POOL_FETCH) it uses as they are.
+// light samples (light_sample) and pool fetch (RTP_LIT_POOL_FETCH) it uses as they are; rt_volume.hip.inc follows and uses the same.
 //
 // What is new here: the region's interval on a ray, the free-flight draw in front of the surface vertex, the medium vertex — both light
 // samples with the phase function as the BSDF strategy's density (PbPhase, no hemisphere) and a Henyey-Greenstein direction whose density
@@ -91,37 +91,28 @@ __device__ __forceinline__ f3 medium_attenuate(const MediumDev &M, f3 o, f3 d, f
 }
 __device__ __forceinline__ uint32_t medium_seed_of(uint32_t base_seed, int32_t s) { return wang_hash(wang_hash(base_seed + (uint32_t)s) ^ kMediumStreamKey); }
 
-// The free-flight step of a lane whose path ray has finished its closest-hit query (L.hit, L.closest), in front of the surface vertex.
-// false: no event — the caller runs shade_lit2, with nothing changed but (perhaps) one draw of med.  true: the vertex is a medium vertex and
-// is done: `more` as shade_lit2 returns it, the light samples in S, the next ray (out_o, out_d) and what it carries
-template <class Table>
-__device__ __forceinline__ bool medium_vertex(Lane &L, const KParams &P, const MediumLit<Table> &T, uint32_t &nee, uint32_t &env, uint32_t &med, f3 &out_o,
-                                              f3 &out_d, LitSamples &S, float &carry_out, bool &more, int32_t &events) {
-    const MediumDev &M = T.M;
-    float t0, t1;
-    if (!medium_interval(M, L.o, L.d, L.hit < 0 ? INFINITY : L.closest, t0, t1)) return false;
-    const float len = sqrt_cr(lensq(L.d));
-    const float u = random_float(med);
-    if (u == 0.0f) return false;
-    const float s = -log_libm(u) / M.sigma_t;
-    if (!(s < (t1 - t0) * len)) return false;
+// The medium vertex at x, the point a free flight along the lane's path ray (L.o, L.d) ended at — the homogeneous flight below, or the
+// cell walk of rt_volume.hip.inc.  The vertex is done on return: `more` as shade_lit2 returns it, the light samples in S, the next ray
+// (out_o, out_d) and what it carries
+template <class Lit>
+__device__ __forceinline__ void medium_vertex_at(Lane &L, const KParams &P, const Lit &G, const MediumDev &M, uint32_t &nee, uint32_t &env, uint32_t &med,
+                                                 const f3 x, f3 &out_o, f3 &out_d, LitSamples &S, float &carry_out, bool &more, int32_t &events) {
     events++;
     S.a = false;
     S.b = false;
     carry_out = 0.0f;
     more = false;
-    const f3 x = add(L.o, scale(t0 + s / len, L.d));
     const f3 ud = unit(L.d);
     const f3 beta_in = L.beta;
     const f3 alb = mk(M.albedo[0], M.albedo[1], M.albedo[2]);
     L.beta = mul(L.beta, alb);
-    if (L.beta.x == 0.0f && L.beta.y == 0.0f && L.beta.z == 0.0f) return true;
-    if (!(L.depth + 1 < P.max_depth)) return true;
+    if (L.beta.x == 0.0f && L.beta.y == 0.0f && L.beta.z == 0.0f) return;
+    if (!(L.depth + 1 < P.max_depth)) return;
     PbPhase pb;
     pb.ud = ud;
     pb.g = M.g;
-    if (light_on(T.G.N)) S.a = light_sample(P, T.G.N, nee, x, ud, alb, beta_in, pb, S.adir, S.ac, S.code);
-    if (env_sampled(T.G)) S.b = light_sample(P, T.G.E, env, x, ud, alb, beta_in, pb, S.bdir, S.bc, S.code);
+    if (light_on(G.N)) S.a = light_sample(P, G.N, nee, x, ud, alb, beta_in, pb, S.adir, S.ac, S.code);
+    if (env_sampled(G)) S.b = light_sample(P, G.E, env, x, ud, alb, beta_in, pb, S.bdir, S.bc, S.code);
     // the next direction: Henyey-Greenstein's cosine by inversion, the azimuth by the disc loop, Duff's basis around ud
     const float u1 = random_float(med);
     float cos_t;
@@ -152,6 +143,23 @@ __device__ __forceinline__ bool medium_vertex(Lane &L, const KParams &P, const M
     carry_out = medium_ph(M.g, cos_t);
     L.depth++;
     more = true;
+}
+
+// The free-flight step of a lane whose path ray has finished its closest-hit query (L.hit, L.closest), in front of the surface vertex.
+// false: no event — the caller runs shade_lit2, with nothing changed but (perhaps) one draw of med.  true: the vertex is a medium vertex and
+// is done: `more` as shade_lit2 returns it, the light samples in S, the next ray (out_o, out_d) and what it carries
+template <class Table>
+__device__ __forceinline__ bool medium_vertex(Lane &L, const KParams &P, const MediumLit<Table> &T, uint32_t &nee, uint32_t &env, uint32_t &med, f3 &out_o,
+                                              f3 &out_d, LitSamples &S, float &carry_out, bool &more, int32_t &events) {
+    const MediumDev &M = T.M;
+    float t0, t1;
+    if (!medium_interval(M, L.o, L.d, L.hit < 0 ? INFINITY : L.closest, t0, t1)) return false;
+    const float len = sqrt_cr(lensq(L.d));
+    const float u = random_float(med);
+    if (u == 0.0f) return false;
+    const float s = -log_libm(u) / M.sigma_t;
+    if (!(s < (t1 - t0) * len)) return false;
+    medium_vertex_at(L, P, T.G, M, nee, env, med, add(L.o, scale(t0 + s / len, L.d)), out_o, out_d, S, carry_out, more, events);
     return true;
 }
 
@@ -302,8 +310,6 @@ __device__ __forceinline__ void medium_render_body(const KParams &P, const Mediu
         }
     }
 }
-#undef RTP_LIT_POOL_FETCH          // (defined in rt_light.hip.inc, which leaves it for this file: no expansion of it may follow)
-
 template <bool kLens, class Table>
 __global__ void __launch_bounds__(256) medium_probe_kernel(const KParams P, const MediumLit<Table> T, const LensCam C, uint32_t *nee_seed_out, uint32_t *env_seed_out,
                                                            uint32_t *med_seed_out, int32_t *events_out) {

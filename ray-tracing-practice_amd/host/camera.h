@@ -146,12 +146,13 @@ void gpu_render_pipelined(const SceneParams &params, const rt_scene_desc &desc, 
 // noise->min_spp, written through rt_tonemap_spp to "<frame file>.denoised"; denoise_adaptive_temporal (with noise, a pinhole and a closed
 // shutter; rtp_main --denoise-adaptive-temporal): that file from rt_denoise_temporal_spp instead, the AOVs (first_prim included) from
 // rt_render_aov at noise->min_spp and the two histories swapped per frame; stop_history (with that; rtp_main --stop-history): those AOVs
-// first, rt_adaptive_prior on the previous frame's history, the frame through rt_render_lit_adaptive_prior
+// first, rt_adaptive_prior on the previous frame's history, the frame through rt_render_lit_adaptive_prior; medium (rtp_main --fog): the
+// lit frames through rt_render_medium; volume (with medium; rtp_main --fog-grid): through rt_render_volume, this grid in the medium's box
 void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const rt_lens_params &lens, float shutter, bool aov, bool denoise,
                      const rt_nee_params *nee = nullptr, const rt_env *env = nullptr, const rt_env_params *env_params = nullptr,
                      const rt_lit_params *lit = nullptr, const rt_adaptive_params *noise = nullptr, bool denoise_adaptive = false,
                      const rt_stop_params *stop = nullptr, bool denoise_adaptive_temporal = false, const rt_medium_params *medium = nullptr,
-                     bool stop_history = false);
+                     bool stop_history = false, const rt_volume *volume = nullptr);
 // rtp_main --gpu --adaptive: the orbit frame after frame on one GPU, each frame through rt_render_adaptive and rt_tonemap_spp;
 // denoise_adaptive (rtp_main --denoise-adaptive): each frame also filtered by rt_denoise_spp with its counts and moments and
 // rt_render_aov AOVs at ap.min_spp, written through rt_tonemap_spp to "<frame file>.denoised"; denoise_adaptive_temporal (rtp_main

@@ -6,6 +6,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <iostream>
 #include <string>
 #include <vector>
@@ -192,11 +193,16 @@ int main(int argc, char *argv[]) {
     // rt_render_medium — a homogeneous grey medium of extinction SIGMA, single-scattering albedo ALBEDO (default 1) and Henyey-Greenstein g
     // G (default 0) in all space, a ball or a box.  --fog needs --lit and is not for --noise-target (adaptive sampling under
     // a medium is left out); --fog-ball / --fog-box need --fog and exclude each other.
+    // `--fog-grid FILE` (with --fog-box): the frames through rt_render_volume — the density grid of FILE fills the box and scales SIGMA cell
+    // by cell.  FILE is the ASCII header "VOL1\nnx ny nz\n" and then nx * ny * nz little-endian float32, x fastest.
     bool fog_on = false;
     rt_medium_params fog;
     rt_medium_params_init(&fog);
+    std::vector<float> fog_grid;
+    int fog_n[3] = {0, 0, 0};
     {
-        bool ball = false, box = false;
+        bool ball = false, box = false, grid = false;
+        std::string grid_file;
         std::string fog_bad;
         for (int a = 2; a < argc; ++a) {
             const std::string arg = argv[a];
@@ -236,11 +242,36 @@ int main(int argc, char *argv[]) {
                 for (int k = 0; ok && k < 3; ++k) ok = std::isfinite(fog.a[k]) && std::isfinite(fog.b[k]) && fog.a[k] < fog.b[k];
                 if (!ok) fog_bad = "--fog-box takes x0,y0,z0,x1,y1,z1 with finite numbers and x0 < x1, y0 < y1, z0 < z1";
             }
+            if (arg == "--fog-grid") {
+                grid = true;
+                grid_file = value;
+            }
         }
         if ((ball || box) && !fog_on) fog_bad = "--fog-ball and --fog-box bound the medium of --fog: they need --fog SIGMA";
         else if (ball && box) fog_bad = "--fog-ball and --fog-box exclude each other: the medium has one region";
         else if (fog_on && !lit_on) fog_bad = "--fog puts a medium into --lit frames: it needs --lit";
         else if (fog_on && noise_on) fog_bad = "--fog cannot be combined with --noise-target: adaptive sampling under a medium is left out";
+        else if (grid && ball) fog_bad = "--fog-grid fills a box: it cannot be combined with --fog-ball";
+        else if (grid && !box) fog_bad = "--fog-grid fills the box of --fog-box: it needs --fog SIGMA and --fog-box";
+        if (fog_bad.empty() && grid) {
+            // the header's two lines, then exactly nx * ny * nz floats (this build's hosts are little-endian, like the file)
+            FILE *f = grid_file.empty() ? nullptr : fopen(grid_file.c_str(), "rb");
+            char magic[8] = {0}, eol = 0;
+            size_t count = 0;
+            bool ok = f && fgets(magic, sizeof(magic), f) && std::strcmp(magic, "VOL1\n") == 0 &&
+                      fscanf(f, "%d %d %d%c", &fog_n[0], &fog_n[1], &fog_n[2], &eol) == 4 && eol == '\n';
+            for (int k = 0; ok && k < 3; ++k) ok = fog_n[k] >= 1 && fog_n[k] <= RT_VOLUME_MAX_N;
+            if (ok) {
+                count = static_cast<size_t>(fog_n[0]) * fog_n[1] * fog_n[2];
+                fog_grid.resize(count);
+                ok = fread(fog_grid.data(), sizeof(float), count, f) == count && fgetc(f) == EOF;
+            }
+            for (size_t k = 0; ok && k < count; ++k) ok = std::isfinite(fog_grid[k]) && fog_grid[k] >= 0.0f;
+            if (f) fclose(f);
+            if (!ok)
+                fog_bad = "--fog-grid takes a FILE of the header \"VOL1\\nnx ny nz\\n\" (each 1 … " + std::to_string(RT_VOLUME_MAX_N) +
+                          ") and then exactly nx*ny*nz little-endian float32 densities, finite and not negative: " + grid_file;
+        }
         if (!fog_bad.empty()) {
             std::cerr << "rtp_main: " << fog_bad << "\n";
             return 99;
@@ -453,8 +484,14 @@ int main(int argc, char *argv[]) {
                 lit.nee = &lit_nee;
                 lit.env = lit_env;
                 lit.env_params = &lit_ep;
+                rt_volume *fog_volume = nullptr;
+                if (!fog_grid.empty() && rt_volume_create(fog_grid.data(), fog_n[0], fog_n[1], fog_n[2], &fog_volume) != RT_OK) {
+                    std::cerr << "rtp_main: --fog-grid: " << rt_get_last_error_string() << "\n";
+                    return 99;
+                }
                 rtp::gpu_render_lens(params, desc, lens, shutter, aov, denoise, nullptr, nullptr, nullptr, &lit, noise_on ? &noise : nullptr,
-                                     denoise_adaptive, &stop_rule, denoise_adaptive_temporal, fog_on ? &fog : nullptr, stop_history);
+                                     denoise_adaptive, &stop_rule, denoise_adaptive_temporal, fog_on ? &fog : nullptr, stop_history, fog_volume);
+                rt_volume_destroy(fog_volume);
                 rt_env_destroy(lit_env);
                 return 0;
             }

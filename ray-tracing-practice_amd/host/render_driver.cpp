@@ -338,12 +338,13 @@ void gpu_render_pipelined(const SceneParams &params, const rt_scene_desc &desc, 
 // rt_render_env with env_params (rtp_main --env), the AOVs likewise; lit: through rt_render_lit (rtp_main --lit) with this lens and
 // shutter, the AOVs through rt_render_aov_lens; noise (with lit; rtp_main --lit --noise-target): through
 // rt_render_lit_adaptive and rt_tonemap_spp — every pixel's bytes at its own sample count — and the printed count is the samples taken
-// medium (with lit, without noise; rtp_main --lit --fog): through rt_render_medium.
+// medium (with lit, without noise; rtp_main --lit --fog): through rt_render_medium; volume (with medium; rtp_main --fog-grid,
+// DESIGN.md §28): through rt_render_volume with this grid in the medium's box.
 // denoise_adaptive (with noise; rtp_main --denoise-adaptive): as in gpu_render_adaptive, the AOVs from rt_render_aov_lens at noise->min_spp
 void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const rt_lens_params &lens, float shutter, bool aov, bool denoise,
                      const rt_nee_params *nee, const rt_env *env, const rt_env_params *env_params, const rt_lit_params *lit,
                      const rt_adaptive_params *noise, bool denoise_adaptive, const rt_stop_params *stop, bool denoise_adaptive_temporal,
-                     const rt_medium_params *medium, bool stop_history) {
+                     const rt_medium_params *medium, bool stop_history, const rt_volume *volume) {
     rt_scene *scene = nullptr;
     RTP_CHECK(rt_scene_create(&desc, &scene));
     const size_t num_pixels = static_cast<size_t>(params.width) * params.height;
@@ -419,7 +420,8 @@ void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const
             rt_lit_params frame_lit = *lit;
             frame_lit.cam_close = cam_close;
             frame_lit.lens = &lens;
-            if (medium) RTP_CHECK(rt_render_medium(scene, &cam, &frame_lit, medium, nullptr, 0, d_fb, nullptr, 1, nullptr));
+            if (medium && volume) RTP_CHECK(rt_render_volume(scene, &cam, &frame_lit, medium, volume, nullptr, 0, d_fb, nullptr, 1, nullptr));
+            else if (medium) RTP_CHECK(rt_render_medium(scene, &cam, &frame_lit, medium, nullptr, 0, d_fb, nullptr, 1, nullptr));
             else RTP_CHECK(rt_render_lit(scene, &cam, &frame_lit, nullptr, 0, d_fb, nullptr, 1, nullptr));
         } else if (env) RTP_CHECK(rt_render_env(scene, &cam, env, env_params, nullptr, 0, d_fb, nullptr, 1, nullptr));
         else if (nee) RTP_CHECK(rt_render_nee(scene, &cam, nee, nullptr, 0, d_fb, nullptr, 1, nullptr));

@@ -426,6 +426,46 @@ class Env:
             pass
 
 
+class Volume:
+    """rt_volume: a density grid on the current device.  Volume(density) takes an (nz, ny, nx) float32 array — x fastest, as the library
+    reads it.  A context manager; close() destroys the object."""
+
+    def __init__(self, density):
+        density = np.ascontiguousarray(density, dtype=np.float32)
+        if density.ndim != 3:
+            raise RtError(f"Volume takes an (nz, ny, nx) array, not {density.shape}")
+        self.nz, self.ny, self.nx = (int(n) for n in density.shape)
+        h = C.c_void_p()
+        _check(amd_lib().rt_volume_create(density.ctypes.data, self.nx, self.ny, self.nz, C.byref(h)), "rt_volume_create")
+        self._h = h
+
+    def close(self):
+        if self._h is not None:
+            amd_lib().rt_volume_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _volume_handle(volume):
+    """None → NULL (no grid: rt_render_medium itself); a Volume → its handle."""
+    if volume is None:
+        return None
+    if not isinstance(volume, Volume) or volume._h is None:
+        raise RtError("volume must be an open rtp_bindings.Volume (or None)")
+    return volume._h
+
+
 TRAVERSAL_AUTO, TRAVERSAL_EXACT, TRAVERSAL_GUARDED = 0, 1, 2
 BUILD_HOST_SAH, BUILD_DEVICE_LBVH = 0, 1
 KERNEL_AUTO, KERNEL_MEGA, KERNEL_WAVEFRONT = 0, 1, 2
@@ -484,6 +524,7 @@ RTP_AMD_SYMBOLS = [
     "rt_trace_samples_env",
     "rt_lit_params_init", "rt_render_lit", "rt_trace_samples_lit",
     "rt_medium_params_init", "rt_render_medium", "rt_trace_samples_medium",
+    "rt_volume_create", "rt_volume_destroy", "rt_render_volume", "rt_trace_samples_volume",
     "rt_render_lit_adaptive",
     "rt_denoise_spp",
     "rt_stop_params_init", "rt_render_adaptive_rule", "rt_render_lit_adaptive_rule", "rt_adaptive_judge",
@@ -631,6 +672,13 @@ def amd_lib():
                                              C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(Timing)]
             lib.rt_trace_samples_medium.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(LitParams), C.POINTER(MediumParams), C.c_int32] + \
                                                    [C.c_void_p] * 8
+        if hasattr(lib, "rt_render_volume"):
+            lib.rt_volume_create.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
+            lib.rt_volume_destroy.argtypes = [C.c_void_p]
+            lib.rt_render_volume.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(LitParams), C.POINTER(MediumParams), C.c_void_p,
+                                             C.POINTER(Shard), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(Timing)]
+            lib.rt_trace_samples_volume.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(LitParams), C.POINTER(MediumParams), C.c_void_p,
+                                                    C.c_int32] + [C.c_void_p] * 9
         if hasattr(lib, "rt_render_lit_adaptive"):
             lib.rt_render_lit_adaptive.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(LitParams), C.POINTER(AdaptiveParams),
                                                    C.POINTER(Shard), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
@@ -1666,6 +1714,47 @@ class DeviceScene:
                                                  rays.ctypes.data, events.ctypes.data, seeds.ctypes.data, ns.ctypes.data, es.ctypes.data,
                                                  ms.ctypes.data), "rt_trace_samples_medium")
         return rad, rays, events, seeds, ns, es, ms
+
+    def render_volume(self, cam, d_fb_ptr, *, medium=None, volume=None, cam_close=None, lens=None, emitters=True, nee=None, env=None, env_params=None,
+                      shard=None, stream=None, sync=True, sample_first=0):
+        """rt_render_volume: rt_render_medium with a density grid in the medium's box (volume: None or a Volume; the other keywords are
+        render_medium's).  Returns the rt_timing of this call."""
+        t = Timing()
+        self._apply_config()
+        lit = lit_params(cam_close=cam_close, lens=lens, emitters=emitters, nee=nee, env=env, env_params=env_params)
+        _check(amd_lib().rt_render_volume(self._h, C.byref(cam), C.byref(lit), _medium_struct(medium), _volume_handle(volume),
+                                          C.byref(shard) if shard else None, sample_first, C.c_void_p(d_fb_ptr), C.c_void_p(stream or 0),
+                                          1 if sync else 0, C.byref(t)), "rt_render_volume")
+        return t
+
+    def render_volume_to_host(self, cam, *, medium=None, volume=None, cam_close=None, lens=None, emitters=True, nee=None, env=None, env_params=None,
+                              shard=None, sample_first=0):
+        """rt_render_volume through a fresh device buffer: (rows, width, 3) float32 sums and the rt_timing."""
+        lib = amd_lib()
+        rows = lib.rt_shard_rows(cam.image_height, C.byref(shard) if shard else None)
+        fb = np.empty((rows, cam.image_width, 3), dtype=np.float32)
+        d = C.c_void_p()
+        _check(lib.rt_device_alloc(fb.nbytes or 12, C.byref(d)), "rt_device_alloc")
+        try:
+            t = self.render_volume(cam, d.value, medium=medium, volume=volume, cam_close=cam_close, lens=lens, emitters=emitters, nee=nee, env=env,
+                                   env_params=env_params, shard=shard, sample_first=sample_first)
+            _check(lib.rt_copy_to_host(fb.ctypes.data, d, fb.nbytes), "rt_copy_to_host")
+        finally:
+            lib.rt_device_free(d)
+        return fb, t
+
+    def trace_samples_volume(self, cam, ijs, *, medium=None, volume=None, cam_close=None, lens=None, emitters=True, nee=None, env=None, env_params=None):
+        """rt_trace_samples_volume: trace_samples_medium's seven columns and the grid cells visited per sample (n,)."""
+        ijs = np.ascontiguousarray(ijs, dtype=np.int32).reshape(-1, 3)
+        n = ijs.shape[0]
+        rad = np.empty((n, 3), dtype=np.float32)
+        rays, events, cells = (np.empty(n, dtype=np.int32) for _ in range(3))
+        seeds, ns, es, ms = (np.empty(n, dtype=np.uint32) for _ in range(4))
+        lit = lit_params(cam_close=cam_close, lens=lens, emitters=emitters, nee=nee, env=env, env_params=env_params)
+        _check(amd_lib().rt_trace_samples_volume(self._h, C.byref(cam), C.byref(lit), _medium_struct(medium), _volume_handle(volume), n, ijs.ctypes.data,
+                                                 rad.ctypes.data, rays.ctypes.data, events.ctypes.data, seeds.ctypes.data, ns.ctypes.data,
+                                                 es.ctypes.data, ms.ctypes.data, cells.ctypes.data), "rt_trace_samples_volume")
+        return rad, rays, events, seeds, ns, es, ms, cells
 
     def last_kernel_ms(self):
         ms = C.c_float()
