@@ -846,9 +846,9 @@ rt_status reserve_slab(rt_scene *sc, uint32_t num_pixels, int32_t spp, hipStream
     }
     return RT_OK;
 }
-// Room for the per-pixel candidate lists of the primary-visibility pass (64 bytes per pixel) + 4 bytes per pixel for the fetch
-// order and 12 per 256 pixels for its counting sort (order_* kernels).  A device short of memory renders without the pass
-// rather than not at all: prim = false.
+// Room for the per-pixel candidate lists of the primary-visibility pass (64 bytes per pixel) + 16 bytes per pixel for the fetch
+// order's table (a row of rtk::kOrderRowWords words per pixel) and 12 per 256 pixels for its counting sort (order_* kernels).
+// A device short of memory renders without the pass rather than not at all: prim = false.
 rt_status reserve_view_lists(rt_scene *sc, uint32_t num_pixels, hipStream_t stream, bool &prim) {
     if (!prim || sc->cand_pixels >= (size_t)num_pixels) return RT_OK;
     HIP_TRY(hipStreamSynchronize(stream));
@@ -856,7 +856,7 @@ rt_status reserve_view_lists(rt_scene *sc, uint32_t num_pixels, hipStream_t stre
     sc->cand = nullptr;
     sc->cand_pixels = 0;
     sc->cand_key.valid = false;
-    const size_t cand_words = (size_t)num_pixels * (rtk::kCandWords + 1) + 3 * (((size_t)num_pixels + rtk::kOrderBlock - 1) / rtk::kOrderBlock);
+    const size_t cand_words = (size_t)num_pixels * (rtk::kCandWords + rtk::kOrderRowWords) + 3 * (((size_t)num_pixels + rtk::kOrderBlock - 1) / rtk::kOrderBlock);
     if (hipMalloc((void **)&sc->cand, cand_words * sizeof(uint32_t)) == hipSuccess) {
         sc->cand_pixels = (size_t)num_pixels;
     } else {
@@ -866,11 +866,12 @@ rt_status reserve_view_lists(rt_scene *sc, uint32_t num_pixels, hipStream_t stre
     }
     return RT_OK;
 }
-// P's view of them: the lists, the fetch order behind them and the count of pixels with a list (counts[2 * blocks] after the scan)
+// P's view of them: the lists, the fetch order's table behind them (16-byte rows on a 64-byte boundary: kCandWords words per pixel before
+// it) and, behind the table, the sort's counts with the count of pixels with a list (counts[2 * blocks] after the scan)
 void bind_view_lists(const rt_scene *sc, rtk::KParams &P, uint32_t num_pixels, bool prim) {
     P.cand = prim ? sc->cand : nullptr;
     P.order = prim ? sc->cand + sc->cand_pixels * rtk::kCandWords : nullptr;
-    P.traced_pixels = prim ? P.order + sc->cand_pixels + 2 * (((size_t)num_pixels + rtk::kOrderBlock - 1) / rtk::kOrderBlock) : nullptr;
+    P.traced_pixels = prim ? P.order + sc->cand_pixels * rtk::kOrderRowWords + 2 * (((size_t)num_pixels + rtk::kOrderBlock - 1) / rtk::kOrderBlock) : nullptr;
 }
 // The candidate lists and the fetch order made from them, for this view on this stream — unless the handle holds them already
 // (rt_config.reuse_view_lists): the same camera, image, shard and tree on the same stream
@@ -889,11 +890,11 @@ rt_status make_view_lists(rt_scene *sc, const rt_camera_data *cam, const rtk::KP
     hipLaunchKernelGGL(rtk::cand_kernel, dim3((num_pixels + 255u) / 256u), dim3(256), 0, stream, P, sc->cand, coord_max);
     HIP_TRY(hipGetLastError());
     // the order the trace kernel fetches the pixels in: expensive ones first (rt_primary.hip.inc)
-    uint32_t *order = sc->cand + sc->cand_pixels * rtk::kCandWords, *counts = order + sc->cand_pixels;
+    uint32_t *order = sc->cand + sc->cand_pixels * rtk::kCandWords, *counts = order + sc->cand_pixels * rtk::kOrderRowWords;
     const uint32_t order_blocks = (num_pixels + (uint32_t)rtk::kOrderBlock - 1u) / (uint32_t)rtk::kOrderBlock;
     hipLaunchKernelGGL(rtk::order_count_kernel, dim3(order_blocks), dim3(rtk::kOrderBlock), 0, stream, (const uint32_t *)sc->cand, num_pixels, order_blocks, counts);
     hipLaunchKernelGGL(rtk::order_scan_kernel, dim3(1), dim3(1024), 0, stream, counts, 3u * order_blocks);
-    hipLaunchKernelGGL(rtk::order_scatter_kernel, dim3(order_blocks), dim3(rtk::kOrderBlock), 0, stream, (const uint32_t *)sc->cand, num_pixels, order_blocks,
+    hipLaunchKernelGGL(rtk::order_scatter_kernel, dim3(order_blocks), dim3(rtk::kOrderBlock), 0, stream, P, (const uint32_t *)sc->cand, num_pixels, order_blocks,
                        (const uint32_t *)counts, order);
     HIP_TRY(hipGetLastError());
     sc->cand_key = key;

@@ -162,7 +162,8 @@ struct KParams {
     // primary visibility (rt_primary.hip.inc): per local pixel kCandWords words — the number of candidate leaves of the pixel's
     // primary rays (kCandNone: no list) and their codes; null: every sample walks the tree from the camera
     const uint32_t *cand;
-    // … and the order the trace kernel takes the pixels in (order_* kernels): position of the fetch order → local pixel
+    // … and the order the trace kernel takes the pixels in (order_* kernels): one row of kOrderRowWords words (16 bytes) per position
+    // of the fetch order — the centre of that pixel on the image plane (what camera_ray builds from the pixel) and the local pixel
     const uint32_t *order;
     const uint32_t *traced_pixels;      // one word: how many pixels the table's front part holds (those with candidates; the others are finished by the primary pass)
     // probe mode (rt_trace_samples)
@@ -1099,7 +1100,7 @@ __device__ __forceinline__ bool shade(Lane &L, const KParams &P, SphereTab spher
 //   [6] magic_count.m .s-32, magic_width.m .s-32                                  [7] width, slab_pitch, pass_first, pass_count
 //   [8] flag_list, flag_count (pointers as two words each)   [9] dirty, dirty_list   [10] dirty_count, flag_cap, chunk   [11] queue, taper_shift
 //   [11].w flag_chunk_words | bail_share << 8 | bail_floor << 16
-//   [12] order (kPrim: the pixel each position of the fetch order stands for), abandon
+//   [12] order (kPrim: the row — pixel centre, local pixel — each position of the fetch order stands for), abandon
 //   [13] the codes of the front primitives (kNoFront: none in that slot)
 typedef float f4v __attribute__((ext_vector_type(4)));       // (a native vector: HIP's float4 struct has no address-space-qualified copy)
 typedef uint32_t u4v __attribute__((ext_vector_type(4)));
@@ -1146,6 +1147,26 @@ __device__ __forceinline__ uint32_t div_magic_v(uint32_t n, uint32_t m, uint32_t
     return m ? r : n;
 }
 
+// The centre of pixel (i, j) on the image plane: this very expression, in this order, is what order_scatter_kernel (rt_primary.hip.inc)
+// leaves in the pixel's row of the fetch-order table, compiled in the same translation unit with the same flags.
+__device__ __forceinline__ f3 pixel_center(f3 p00, f3 du, f3 dv, int32_t i, int32_t j) { return add(add(p00, scale((float)i, du)), scale((float)j, dv)); }
+// camera_ray (below, its kFromLds form) behind the pixel's centre — kPrim takes the centre from the fetch-order table (map_fetch).
+// (A function of its own, not a call from camera_ray: the other kernels keep the code they had, instruction for instruction.)
+__device__ __forceinline__ void camera_ray_from_center(Lane &L, f3 center, uint32_t seed1, f3 &out_o, f3 &out_d, uint32_t consts_lds) {
+    uint32_t seed = seed1;
+    const float ox = (float)seed * 2.3283064365386962890625e-10f - 0.5f;
+    const f4v a = ((lds_cfloat4 *)(uintptr_t)consts_lds)[3], b = ((lds_cfloat4 *)(uintptr_t)consts_lds)[4], c = ((lds_cfloat4 *)(uintptr_t)consts_lds)[5];
+    const f3 du = mk(a.x, a.y, a.z), dv = mk(b.x, b.y, b.z);
+    const float oy = random_float(seed) - 0.5f;
+    const f3 sample = add(add(center, scale(ox, du)), scale(oy, dv));
+    const f3 org = mk(c.x, c.y, c.z);
+    L.seed = seed;
+    L.beta = mk(1.0f, 1.0f, 1.0f);
+    L.color = mk(0.0f, 0.0f, 0.0f);
+    L.depth = 0;
+    out_o = org;
+    out_d = sub(sample, org);
+}
 // Seeds + CameraData::get_ray (src/camera.cu:25-29, include/camera.cuh:97-109).
 // seed1: the RNG state after the first draw's hash, wang_hash(wang_hash(base_seed + s)) — the value the primary-visibility
 // pass leaves in the third word of a sample's record, so that the trace kernel does not hash the pixel and the sample again.
@@ -1156,7 +1177,7 @@ __device__ __forceinline__ void camera_ray(Lane &L, const KParams &P, int32_t i,
     if (kFromLds) {
         const f4v a = ((lds_cfloat4 *)(uintptr_t)consts_lds)[3], b = ((lds_cfloat4 *)(uintptr_t)consts_lds)[4], c = ((lds_cfloat4 *)(uintptr_t)consts_lds)[5];
         const f3 du = mk(a.x, a.y, a.z), dv = mk(b.x, b.y, b.z);
-        const f3 center = add(add(mk(a.w, b.w, c.w), scale((float)i, du)), scale((float)j, dv));
+        const f3 center = pixel_center(mk(a.w, b.w, c.w), du, dv, i, j);
         const float oy = random_float(seed) - 0.5f;
         const f3 sample = add(add(center, scale(ox, du)), scale(oy, dv));
         const f3 org = mk(c.x, c.y, c.z);
@@ -1171,7 +1192,7 @@ __device__ __forceinline__ void camera_ray(Lane &L, const KParams &P, int32_t i,
     // (direct member reads of the kernel argument: scalar loads into SGPRs; through a pointer — ld3(P.du) — the compiler
     // emitted per-lane global loads with a wait on every use, one exposed memory round trip per shade step)
     const f3 du = mk(P.du[0], P.du[1], P.du[2]), dv = mk(P.dv[0], P.dv[1], P.dv[2]);
-    const f3 center = add(add(mk(P.p00[0], P.p00[1], P.p00[2]), scale((float)i, du)), scale((float)j, dv));
+    const f3 center = pixel_center(mk(P.p00[0], P.p00[1], P.p00[2]), du, dv, i, j);
     const float oy = random_float(seed) - 0.5f;
     const f3 sample = add(add(center, scale(ox, du)), scale(oy, dv));
     const f3 org = mk(P.origin[0], P.origin[1], P.origin[2]);
@@ -1270,22 +1291,27 @@ __device__ __forceinline__ void store_sample(const KParams &P, uint32_t w, f3 co
     rec[0] = color.x; rec[1] = color.y; rec[2] = color.z;
 }
 
+// local pixel q of the call's rows (a tile, or a shard's bands) → image pixel
+__device__ __forceinline__ void local_to_image(const KParams &P, uint32_t q, int32_t &pi, int32_t &pj) {
+    const uint32_t pjl = div_magic(q, P.magic_width);
+    pi = (int32_t)(q - pjl * (uint32_t)P.row_w) + P.tile_x0;
+    // local row → image row: band b = pjl / band_rows belongs to part, bands interleave
+    if (P.num_parts == 1) {
+        pj = (int32_t)pjl + P.tile_y0;
+    } else {
+        const uint32_t band = div_magic(pjl, P.magic_band);
+        pj = (int32_t)((band * (uint32_t)P.num_parts + (uint32_t)P.part) * (uint32_t)P.band_rows + (pjl - band * (uint32_t)P.band_rows));
+    }
+}
 // work index of a pass → (local pixel, slot) → image pixel and first ray of the sample
 // (kFromLds: also returns the image width and the pass's first sample, which the caller needs next)
 template <bool kFromLds = false>
 __device__ __forceinline__ void map_work(const KParams &P, uint32_t w, int32_t &pi, int32_t &pj, uint32_t &k, uint32_t consts_lds = 0,
-                                         uint32_t *width_out = nullptr, int32_t *first_out = nullptr, uint32_t *record_out = nullptr,
-                                         uint32_t *canonical_out = nullptr) {
+                                         uint32_t *width_out = nullptr, int32_t *first_out = nullptr, uint32_t *record_out = nullptr) {
     if (kFromLds) {
         const u4v mg = ((lds_cuint4 *)(uintptr_t)consts_lds)[6], wd = ((lds_cuint4 *)(uintptr_t)consts_lds)[7];
-        uint32_t q = div_magic_v(w, mg.x, mg.y);
+        const uint32_t q = div_magic_v(w, mg.x, mg.y);
         k = w - q * wd.w;
-        if (canonical_out) {        // fetch order → pixel (order_kernels, rt_primary.hip.inc); the sample is known by pixel * count + slot from here on
-            typedef uint32_t u2v __attribute__((ext_vector_type(2)));
-            const u2v od = *(__attribute__((address_space(3))) const u2v *)(uintptr_t)(consts_lds + 16u * 12u);
-            q = ptr_from(od.x, od.y)[q];
-            *canonical_out = q * wd.w + k;
-        }
         if (record_out) *record_out = q * wd.y + k;          // the sample's record of the slab (store_sample)
         const uint32_t pjl = div_magic_v(q, mg.z, mg.w);
         pi = (int32_t)(q - pjl * wd.x + (mg.y >> 8));
@@ -1299,22 +1325,28 @@ __device__ __forceinline__ void map_work(const KParams &P, uint32_t w, int32_t &
         *first_out = (int32_t)wd.z;
         return;
     }
-    uint32_t q = P.pass_count == 64 ? (w >> 6) : div_magic(w, P.magic_count);
+    const uint32_t q = P.pass_count == 64 ? (w >> 6) : div_magic(w, P.magic_count);
     k = w - q * (uint32_t)P.pass_count;
-    if (canonical_out) {
-        q = P.order[q];
-        *canonical_out = q * (uint32_t)P.pass_count + k;
-    }
     if (record_out) *record_out = q * P.slab_pitch + k;
-    const uint32_t pjl = div_magic(q, P.magic_width);
-    pi = (int32_t)(q - pjl * (uint32_t)P.row_w) + P.tile_x0;
-    // local row → image row: band b = pjl / band_rows belongs to part, bands interleave
-    if (P.num_parts == 1) {
-        pj = (int32_t)pjl + P.tile_y0;
-    } else {
-        const uint32_t band = div_magic(pjl, P.magic_band);
-        pj = (int32_t)((band * (uint32_t)P.num_parts + (uint32_t)P.part) * (uint32_t)P.band_rows + (pjl - band * (uint32_t)P.band_rows));
-    }
+    local_to_image(P, q, pi, pj);
+}
+
+// kPrim: the work index counts in fetch order (expensive pixels first).  Position of the fetch order → its row of the table
+// (order_scatter_kernel, rt_primary.hip.inc): the pixel's centre on the image plane and the local pixel, in ONE 16-byte load where
+// there was the pixel's word, so nothing of the pixel's own arithmetic (column, row, band, two conversions, the centre's six products
+// and sums) is left to the few lanes that fetch.  The sample is known by pixel * count + slot from here on (canonical), and
+// record is its slot of the slab (store_sample).
+constexpr int kOrderRowWords = 4;
+__device__ __forceinline__ void map_fetch(uint32_t w, uint32_t consts_lds, uint32_t &canonical, uint32_t &record, f3 &center) {
+    const u4v mg = ((lds_cuint4 *)(uintptr_t)consts_lds)[6], wd = ((lds_cuint4 *)(uintptr_t)consts_lds)[7];
+    const uint32_t pos = div_magic_v(w, mg.x, mg.y);
+    const uint32_t k = w - pos * wd.w;
+    typedef uint32_t u2v __attribute__((ext_vector_type(2)));
+    const u2v od = *(__attribute__((address_space(3))) const u2v *)(uintptr_t)(consts_lds + 16u * 12u);
+    const u4v row = *reinterpret_cast<const u4v *>(ptr_from(od.x, od.y) + (size_t)pos * kOrderRowWords);
+    center = mk(__uint_as_float(row.x), __uint_as_float(row.y), __uint_as_float(row.z));
+    canonical = row.w * wd.w + k;
+    record = row.w * wd.y + k;
 }
 
 __device__ __forceinline__ int lane_rank(uint64_t mask) {

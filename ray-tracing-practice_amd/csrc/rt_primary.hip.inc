@@ -93,9 +93,12 @@ __global__ void __launch_bounds__(1024) order_scan_kernel(uint32_t *counts, uint
     uint32_t run = sums[threadIdx.x] - s;
     for (uint32_t k = lo; k < hi; ++k) { const uint32_t c = counts[k]; counts[k] = run; run += c; }
 }
-// (3) each pixel to its place: offset of its (class, block) + its rank among the block's pixels of that class
-__global__ void __launch_bounds__(kOrderBlock) order_scatter_kernel(const uint32_t *cand, uint32_t num_pixels, uint32_t num_blocks, const uint32_t *offsets,
-                                                                    uint32_t *order) {
+// (3) each pixel to its place: offset of its (class, block) + its rank among the block's pixels of that class.  A place is one row of
+// kOrderRowWords words, everything about the pixel that the trace kernel needs where it starts a sample (map_fetch): the pixel's
+// centre on the image plane — pixel_center, camera_ray's own expression on the same operands — and the local pixel.  Computed here
+// once per pixel and view by a full wave, instead of once per sample by the few lanes of a wave whose paths have just ended.
+__global__ void __launch_bounds__(kOrderBlock) order_scatter_kernel(const KParams P, const uint32_t *cand, uint32_t num_pixels, uint32_t num_blocks,
+                                                                    const uint32_t *offsets, uint32_t *order) {
     __shared__ uint32_t part[3][kOrderBlock / 64];
     const uint32_t q = blockIdx.x * (uint32_t)kOrderBlock + threadIdx.x;
     const uint32_t cls = q < num_pixels ? pixel_class(cand[(size_t)q * kCandWords]) : 3u;
@@ -109,7 +112,11 @@ __global__ void __launch_bounds__(kOrderBlock) order_scatter_kernel(const uint32
     __syncthreads();
     if (cls < 3u) {
         for (int w = 0; w < wave; ++w) rank += part[cls][w];
-        order[offsets[cls * num_blocks + blockIdx.x] + rank] = q;
+        int32_t pi, pj;
+        local_to_image(P, q, pi, pj);
+        const f3 center = pixel_center(mk(P.p00[0], P.p00[1], P.p00[2]), mk(P.du[0], P.du[1], P.du[2]), mk(P.dv[0], P.dv[1], P.dv[2]), pi, pj);
+        const size_t place = (size_t)(offsets[cls * num_blocks + blockIdx.x] + rank);         // < num_pixels: the table has a row for every pixel
+        *reinterpret_cast<u4v *>(order + place * kOrderRowWords) = u4v{__float_as_uint(center.x), __float_as_uint(center.y), __float_as_uint(center.z), q};
     }
 }
 

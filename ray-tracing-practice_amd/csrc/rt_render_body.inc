@@ -155,6 +155,7 @@
 #ifdef RTP_STATS
     uint32_t st_iters[4] = {0, 0, 0, 0}, st_lanes[4] = {0, 0, 0, 0};
     uint64_t st_cycles[7] = {0, 0, 0, 0, 0, 0, 0}, st_last = __builtin_amdgcn_s_memtime();
+    uint32_t st_fetch_rounds = 0;          // kPrim: rounds of (A) in which some lane of the wave fetched (each traced sample is fetched once)
 #endif
     // the flagged-sample list: flag_collect above, called where a sample is retired
     const uint32_t chunk_lds = consts_lds + 16u * (uint32_t)kConstRows;       // the flag stages: behind the constants block
@@ -254,7 +255,13 @@
                 int32_t first = P.pass_first;
                 uint32_t record = 0;
                 uint32_t wc = wm;           // kPrim: wm counts in fetch order (expensive pixels first); wc = pixel * count + slot is the sample's name
-                map_work<kConsts>(P, wm, pi, pj, k, consts_lds, &width, &first, kPrim ? &record : nullptr, kPrim ? &wc : nullptr);
+                f3 center;
+                if constexpr (kPrim) {      // the pixel's row of the fetch-order table: its centre on the image plane and its name
+                    static_assert(kConsts, "primary visibility feeds guarded kernels: all of them keep the constants block");
+                    map_fetch(wm, consts_lds, wc, record, center);
+                } else {
+                    map_work<kConsts>(P, wm, pi, pj, k, consts_lds, &width, &first);
+                }
                 if (kPrim) {            // (hit distance, code, RNG state after the first draw's hash)
                     // (all twelve bytes in ONE load: read word by word, the third — needed only where the ray hit something — came
                     // with a second round trip behind the wait for the first two)
@@ -263,7 +270,7 @@
                     prim_t = rec.x;
                     prim_code = __float_as_int(rec.y);
                     if (prim_code != kPrimMiss) {
-                        camera_ray<kConsts>(L, P, pi, pj, __float_as_uint(rec.z), ray_o, ray_d, consts_lds);
+                        camera_ray_from_center(L, center, __float_as_uint(rec.z), ray_o, ray_d, consts_lds);
                     } else {            // no ray: the next store / fetch round adds beta * background = the background to this sample
                         L.beta = mk(1.0f, 1.0f, 1.0f);
                         L.color = mk(0.0f, 0.0f, 0.0f);
@@ -356,6 +363,9 @@
                 bool go = over();
                 for (int it = 0;; ++it) {
                     // (A): the lane's old path is over, so the camera ray of the next one goes straight into its place
+#ifdef RTP_STATS_SHADE_SPLIT
+                    st_fetch_rounds += __any(go) ? 1u : 0u;
+#endif
                     if (go) {
                         if (path_open) {
                             if (L.hit < 0 && !(L.depth & (kFlagBit | kEndBit)))      // src/camera.cu:227-229: the ray left the scene
@@ -530,6 +540,6 @@
             atomicAdd(&P.stats[8 + k], (uint32_t)(st_cycles[k] >> 10));   // kilo-ticks of s_memtime
         }
 #ifdef RTP_STATS_SHADE_SPLIT
-    if (lane == 0) { atomicAdd(&P.stats[12], (uint32_t)(st_cycles[4] >> 10)); atomicAdd(&P.stats[13], (uint32_t)(st_cycles[5] >> 10)); }
+    if (lane == 0) { atomicAdd(&P.stats[12], (uint32_t)(st_cycles[4] >> 10)); atomicAdd(&P.stats[13], (uint32_t)(st_cycles[5] >> 10)); atomicAdd(&P.stats[14], st_fetch_rounds); }
 #endif
 #endif

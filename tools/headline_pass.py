@@ -18,6 +18,8 @@ print('HL %d spp: kernel_ms %.2f trace_ms %.2f primary %.2f rework %.2f  Msample
 if os.environ.get('STATS'):
     lib=rb.amd_lib(); out=(C.c_uint32*16)(); lib.rt_debug_read_stats(ds._h, out)
     print('  shade block split (kticks): (A) store+fetch %d   (C)+(B) material+arm %d   rest %d   votes %d' % (out[12], out[13], out[10], out[11]))
+    # (RTP_STATS_SHADE_SPLIT builds: word 14 counts the rounds of (A) in which a lane fetched; every traced sample is fetched once)
+    print('  fetch rounds %d   traced samples %d   lanes fetching per round %.2f   share of wave time in (A) %.3f' % (out[14], tm.traced_samples, tm.traced_samples/max(out[14],1), out[12]/max(sum(out[8:14]),1)))
     for k,n in enumerate(['pair','leaf','shadeblock','vote']):
         it,ln=out[2*k],out[2*k+1]
         print('  %-10s kticks %9d wave-steps %10d full-wave-equiv %10d util %.3f per-sample lane-steps %.2f wave-steps/sample %.4f'%(n,out[8+k],it,ln,ln/max(it,1),ln*64/ns,it/ns))
