@@ -1149,8 +1149,8 @@ rt_status rt_render_lit_adaptive_prior(rt_scene *scene, const rt_camera_data *ca
  *   med state as initialised).  sigma_t > 0 with a region that no path ray and no shadow ray of the frame touches = rt_render_lit as well,
  *   through the medium's own kernels.
  * Left out: ~~heterogeneous~~ (rt_render_volume, "density grid" below) or chromatic extinction; more than one region; regions bounded by scene surfaces (fog inside a glass ball that
- *   sits in the region is still fog); emission in the medium; the guarded walk; tiles and rt_context; rt_render_lit_adaptive with a
- *   medium, AOVs of the medium and the denoisers' handling of it (the first-hit AOVs do not see it).
+ *   sits in the region is still fog); emission in the medium; the guarded walk; tiles and rt_context; ~~rt_render_lit_adaptive with a
+ *   medium~~ (rt_render_volume_adaptive, "adaptive sampling under fog" below), AOVs of the medium and the denoisers' handling of it (the first-hit AOVs do not see it).
  * Checks, all before anything is enqueued: rt_render_lit's parameter checks come first, in its order (lens, nee, env_params); then the
  *   medium's, still before the scene is looked at; then the scene's and the camera's as in rt_render_lit.  RT_ERR_INVALID_ARG for struct_bytes below 8,
  *   region outside {0, 1, 2}, a sigma_t that is negative, NaN or infinite, an albedo channel outside [0, 1], |g| > 0.95 or NaN, a ball's
@@ -1209,7 +1209,8 @@ rt_status rt_trace_samples_medium(rt_scene *scene, const rt_camera_data *cam_ope
  *   arguments, whatever its region.  sigma_t == 0 = rt_render_lit.  A grid of zeros = rt_render_lit in radiance, rays and the path, nee
  *   and env streams; med advances one draw per non-empty path interval.
  * Left out: chromatic extinction; more than one region or grid; emission in the medium; interpolation between cells (trilinear or any
- *   other: the density is piecewise constant); rt_render_lit_adaptive with a grid; AOVs of the medium; tiles and rt_context.
+ *   other: the density is piecewise constant); ~~rt_render_lit_adaptive with a grid~~ (rt_render_volume_adaptive, "adaptive sampling under fog"
+ *   below); AOVs of the medium; tiles and rt_context.
  * rt_volume: the grid on the device it was created on (the calling thread's current one), like an rt_env.  density is HOST memory, nx * ny
  *   * nz floats, copied: cell (x, y, z) at (z * ny + y) * nx + x.  RT_ERR_INVALID_ARG for a null pointer, a dimension below 1 or above
  *   RT_VOLUME_MAX_N, a density that is negative, NaN or infinite.  A volume outlives every call that was given it; destroy it after the
@@ -1231,6 +1232,34 @@ rt_status rt_trace_samples_volume(rt_scene *scene, const rt_camera_data *cam_ope
                                   const rt_volume *volume, int32_t n, const int32_t *ijs, float *radiance, int32_t *rays,
                                   int32_t *medium_events, uint32_t *final_seed, uint32_t *final_nee_seed, uint32_t *final_env_seed,
                                   uint32_t *final_medium_seed, int32_t *cells);
+
+/* ---- adaptive sampling under fog -----------------------------------------------------------------------------------
+ * rt_render_lit_adaptive_prior's rule, statistics, rounds and prior on rt_render_volume's estimator.  No new arithmetic: a sample is
+ * rt_render_volume's under the same lit, medium and volume; the moments, the stopping rules and the prior are those of the adaptive
+ * sections above.  stop == NULL or rule == 0, and d_prior == NULL, mean what they mean in rt_render_lit_adaptive_prior.
+ *
+ * Per-pixel parity.  Pixel p receives samples sample_first … sample_first + n_p - 1 of rt_render_volume; d_fb_sum[p] is rt_render_volume's
+ * pixel at samples_per_pixel = n_p and the same sample_first (added in sample order from 0); d_spp[p] = n_p in {min_spp + k * batch_spp <=
+ * max_spp}; d_moments (NULL or 2 floats per pixel) holds (S1, S2) of the luminance of the radiance as rt_render_volume adds it —
+ * transmittance factors, the medium vertices' light samples and the MIS weights included — float32, in sample order.
+ *
+ * Identities, bit for bit, in all three outputs: threshold = 0 is rt_render_volume at min_spp + R * batch_spp, every count equal to that.
+ * volume == NULL is the same call on rt_render_medium's estimator (the medium's kernels), whatever the region.  A 1 x 1 x 1 grid of density
+ * 1 equals volume == NULL with the same box.  medium == NULL or sigma_t == 0 is rt_render_lit_adaptive_prior with the same remaining
+ * arguments, handed over after this call's own parameter checks.  A grid of zeros, and a region that no ray of the frame touches, give
+ * rt_render_lit_adaptive_prior's outputs through the fog kernels.
+ *
+ * Checks, all before anything is enqueued, in this order: rt_render_adaptive's parameter checks; the stop parameters'; the prior's;
+ * rt_render_lit's (lens, nee, env_params); the medium's; the volume's (a medium with region 2); the sample range of sample_first + min_spp
+ * + R * batch_spp; d_fb_sum or d_spp NULL; the null scene; the volume's device against the scene's; the scene's and the camera's as in
+ * rt_render_lit; RT_ERR_UNSUPPORTED for pixels x batch_spp at or above 2^31 - 4096 when R > 0.  Messages name rt_render_volume_adaptive.
+ * max_depth <= 0: zero sums and moments, the counts by the rule.  Rows of a shard only: no tiles, no rt_context.  Handle state, buffers
+ * and timing: as rt_render_lit_adaptive (trace_launches = the min_spp frame's passes + R).
+ * Left out: tiles and rt_context; the guarded walk; the denoisers on fogged frames; empty-space skipping. */
+rt_status rt_render_volume_adaptive(rt_scene *scene, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium,
+                                    const rt_volume *volume, const rt_adaptive_params *params, const rt_stop_params *stop, const float *d_prior,
+                                    const rt_shard *shard, int32_t sample_first, float *d_fb_sum, int32_t *d_spp, float *d_moments,
+                                    void *hip_stream, int32_t sync, rt_timing *timing);
 
 /* Milliseconds of the most recent rt_render kernel of this scene (waits for it). */
 rt_status rt_last_kernel_ms(rt_scene *scene, float *ms);

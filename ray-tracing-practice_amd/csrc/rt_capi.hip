@@ -1836,11 +1836,12 @@ rt_status adaptive_check(const char *what, const rt_adaptive_params *params, rt_
     if (a.max_spp > 65536) return fail(RT_ERR_UNSUPPORTED, w + ": max_spp above 65536");
     return RT_OK;
 }
-// rt_stop_params of the _rule calls (what: the old call's name) → the rule; NULL is rule 0
-rt_status stop_check(const char *what, const rt_stop_params *stop, int32_t &rule) {
+// rt_stop_params of the _rule calls (what: the old call's name; suffix: what the _rule call adds to it — nothing for a call that takes
+// the stop parameters from the start) → the rule; NULL is rule 0
+rt_status stop_check(const char *what, const rt_stop_params *stop, int32_t &rule, const char *suffix = "_rule") {
     rule = 0;
     if (!stop) return RT_OK;
-    const std::string w = std::string(what) + "_rule";
+    const std::string w = std::string(what) + suffix;
     if (stop->struct_bytes < 8) return fail(RT_ERR_INVALID_ARG, w + ": rt_stop_params struct_bytes below 8");
     rule = stop->rule;
     if (rule != 0 && rule != 1) return fail(RT_ERR_INVALID_ARG, w + ": rule outside 0 … 1");
@@ -3085,29 +3086,22 @@ rt_status rt_render_lit(rt_scene *sc, const rt_camera_data *cam_open, const rt_l
 // ---- rt_render_lit_adaptive (rtp_amd.h): rt_render_adaptive's rule and rounds on rt_render_lit's estimator.  The min_spp
 // frame is render_light_impl's passes with the moments; the rounds are rt_render_adaptive's (adaptive_rounds) with the list variant of
 // the frame's kernel as their trace launch.  Every round is enqueued up front; the light is made once.
-rt_status rt_render_lit_adaptive_prior(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_adaptive_params *params,
-                                       const rt_stop_params *stop, const rt_shard *shard, int32_t sample_first, float *d_fb_sum, int32_t *d_spp,
-                                       float *d_moments, void *hip_stream, int32_t sync, rt_timing *timing, const float *d_prior) {
-    // ---- 1. every check before anything is enqueued
-    const char *what = "rt_render_lit_adaptive";
-    rt_adaptive_params a;
-    int32_t rule;
-    rt_status st = adaptive_check(what, params, a);
-    if (st != RT_OK) return st;
-    if ((st = stop_check(what, stop, rule)) != RT_OK) return st;
-    if ((st = prior_check("rt_render_lit_adaptive_prior", d_prior, cam_open, shard, d_fb_sum, d_spp, d_moments)) != RT_OK) return st;
-    LitSetup S;
-    if ((st = lit_setup(what, cam_open, lit, S)) != RT_OK) return st;
+namespace {
+// The adaptive lit calls from their frame prologue on (rt_render_lit_adaptive_prior, rt_render_volume_adaptive): the caller has made its
+// parameter checks, down to the null scene.  with_light(f) makes the call's light once and returns f(frame kernel, its list variant,
+// &light); `what` starts every refusal.
+extern "C++" template <class WithLight>
+rt_status lit_adaptive_run(const char *what, rt_scene *sc, const rt_camera_data *cam_open, const LitSetup &S, const rt_adaptive_params &a, int32_t rule,
+                           const float *d_prior, const rt_shard *shard, int32_t sample_first, float *d_fb_sum, int32_t *d_spp, float *d_moments,
+                           void *hip_stream, int32_t sync, rt_timing *timing, WithLight &&with_light) {
+    rt_status st;
     const int32_t batch = a.batch_spp, rounds = (a.max_spp - a.min_spp) / a.batch_spp;
-    if ((st = check_sample_range(what, sample_first, a.min_spp + rounds * batch)) != RT_OK) return st;
-    if (!d_fb_sum || !d_spp) return fail(RT_ERR_INVALID_ARG, "rt_render_lit_adaptive: null framebuffer or sample counts");
-    if (!sc) return fail(RT_ERR_INVALID_ARG, "rt_render_lit_adaptive: null scene");
     rt_camera_data base = *cam_open;
     base.samples_per_pixel = a.min_spp;
     Frame F;
     st = frame_prologue(what, sc, &base, shard, nullptr, sample_first, S.env ? &S.env->device : nullptr, nullptr, hip_stream, timing, F, [&] {
         if (rounds > 0 && (uint64_t)F.num_pixels * (uint64_t)batch >= (1ull << 31) - 4096)
-            return fail(RT_ERR_UNSUPPORTED, "rt_render_lit_adaptive: pixels x batch_spp beyond the work index arithmetic");
+            return fail(RT_ERR_UNSUPPORTED, std::string(what) + ": pixels x batch_spp beyond the work index arithmetic");
         return refuse_retired(sc->cfg);
     });
     if (st != RT_OK) return st;
@@ -3131,9 +3125,8 @@ rt_status rt_render_lit_adaptive_prior(rt_scene *sc, const rt_camera_data *cam_o
     if ((st = adaptive_reserve(sc, num_pixels, rounds, batch, rule, stream)) != RT_OK) return st;
 
     // ---- 3. the light, once, and the two kernels it needs: the frame's and its list variant
-    return with_lit(sc, S, [&](const auto &T) -> rt_status {
-        const void *frame_kernel = S.lens ? rtk::lit_frame_kernel_of<true>(T) : rtk::lit_frame_kernel_of<false>(T);
-        const void *list_kernel = S.lens ? rtk::lit_list_kernel_of<true>(T) : rtk::lit_list_kernel_of<false>(T);
+    return with_light([&](const void *frame_kernel, const void *list_kernel, const auto *light) -> rt_status {
+        const auto &T = *light;
         rt_timing t{};
         kernel_resources(rounds > 0 ? list_kernel : frame_kernel, t.trace_vgprs, t.trace_scratch_bytes);
         CallClock &clock = sc->clock[kClockLight];
@@ -3169,6 +3162,31 @@ rt_status rt_render_lit_adaptive_prior(rt_scene *sc, const rt_camera_data *cam_o
         }
         timing_out(t, timing);
         return RT_OK;
+    });
+}
+}  // namespace
+
+rt_status rt_render_lit_adaptive_prior(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_adaptive_params *params,
+                                       const rt_stop_params *stop, const rt_shard *shard, int32_t sample_first, float *d_fb_sum, int32_t *d_spp,
+                                       float *d_moments, void *hip_stream, int32_t sync, rt_timing *timing, const float *d_prior) {
+    // every check before anything is enqueued
+    const char *what = "rt_render_lit_adaptive";
+    rt_adaptive_params a;
+    int32_t rule;
+    rt_status st = adaptive_check(what, params, a);
+    if (st != RT_OK) return st;
+    if ((st = stop_check(what, stop, rule)) != RT_OK) return st;
+    if ((st = prior_check("rt_render_lit_adaptive_prior", d_prior, cam_open, shard, d_fb_sum, d_spp, d_moments)) != RT_OK) return st;
+    LitSetup S;
+    if ((st = lit_setup(what, cam_open, lit, S)) != RT_OK) return st;
+    if ((st = check_sample_range(what, sample_first, a.min_spp + (a.max_spp - a.min_spp) / a.batch_spp * a.batch_spp)) != RT_OK) return st;
+    if (!d_fb_sum || !d_spp) return fail(RT_ERR_INVALID_ARG, "rt_render_lit_adaptive: null framebuffer or sample counts");
+    if (!sc) return fail(RT_ERR_INVALID_ARG, "rt_render_lit_adaptive: null scene");
+    return lit_adaptive_run(what, sc, cam_open, S, a, rule, d_prior, shard, sample_first, d_fb_sum, d_spp, d_moments, hip_stream, sync, timing, [&](auto run) {
+        return with_lit(sc, S, [&](const auto &T) {
+            return run(S.lens ? rtk::lit_frame_kernel_of<true>(T) : rtk::lit_frame_kernel_of<false>(T),
+                       S.lens ? rtk::lit_list_kernel_of<true>(T) : rtk::lit_list_kernel_of<false>(T), &T);
+        });
     });
 }
 
@@ -3510,6 +3528,45 @@ rt_status rt_render_volume(rt_scene *sc, const rt_camera_data *cam_open, const r
     };
     return render_light_impl("rt_render_volume", S.env ? &S.env->device : nullptr, with_light, sc, cam_open, shard, sample_first, d_fb_sum, hip_stream, sync, timing,
                              &S.C);
+}
+
+// ---- rt_render_volume_adaptive (rtp_amd.h): rt_render_lit_adaptive_prior's steps (lit_adaptive_run) on rt_render_volume's
+// estimator — the frame kernel of the medium or of the grid for the min_spp frame, its list variant for the rounds.  No medium is
+// rt_render_lit_adaptive_prior itself, once this call's own checks have passed.
+rt_status rt_render_volume_adaptive(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium, const rt_volume *volume,
+                                    const rt_adaptive_params *params, const rt_stop_params *stop, const float *d_prior, const rt_shard *shard,
+                                    int32_t sample_first, float *d_fb_sum, int32_t *d_spp, float *d_moments, void *hip_stream, int32_t sync, rt_timing *timing) {
+    const char *what = "rt_render_volume_adaptive";
+    rt_adaptive_params a;
+    int32_t rule;
+    rt_status st = adaptive_check(what, params, a);
+    if (st != RT_OK) return st;
+    if ((st = stop_check(what, stop, rule, "")) != RT_OK) return st;
+    if ((st = prior_check(what, d_prior, cam_open, shard, d_fb_sum, d_spp, d_moments)) != RT_OK) return st;
+    LitSetup S;
+    if ((st = lit_setup(what, cam_open, lit, S)) != RT_OK) return st;
+    rtk::MediumDev M{};
+    if ((st = medium_setup(what, medium, M)) != RT_OK) return st;
+    if ((st = volume_setup(what, medium, M, volume)) != RT_OK) return st;
+    if ((st = check_sample_range(what, sample_first, a.min_spp + (a.max_spp - a.min_spp) / a.batch_spp * a.batch_spp)) != RT_OK) return st;
+    if (!d_fb_sum || !d_spp) return fail(RT_ERR_INVALID_ARG, "rt_render_volume_adaptive: null framebuffer or sample counts");
+    if (!sc) return fail(RT_ERR_INVALID_ARG, "rt_render_volume_adaptive: null scene");
+    if (volume && volume->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_render_volume_adaptive: the volume was created on another device than the scene");
+    if (!(M.sigma_t > 0.0f))
+        return rt_render_lit_adaptive_prior(sc, cam_open, lit, params, stop, shard, sample_first, d_fb_sum, d_spp, d_moments, hip_stream, sync, timing, d_prior);
+    return lit_adaptive_run(what, sc, cam_open, S, a, rule, d_prior, shard, sample_first, d_fb_sum, d_spp, d_moments, hip_stream, sync, timing, [&](auto run) {
+        if (!volume)
+            return with_medium_lit(sc, S, M, [&](const auto &T) {
+                using Table = decltype(T.G.N);
+                return run(S.lens ? (const void *)rtk::medium_render_kernel<true, Table> : (const void *)rtk::medium_render_kernel<false, Table>,
+                           S.lens ? (const void *)rtk::medium_list_render_kernel<true, Table> : (const void *)rtk::medium_list_render_kernel<false, Table>, &T);
+            });
+        return with_volume_lit(sc, S, M, volume, [&](const auto &T) {
+            using Table = decltype(T.G.N);
+            return run(S.lens ? (const void *)rtk::volume_render_kernel<true, Table> : (const void *)rtk::volume_render_kernel<false, Table>,
+                       S.lens ? (const void *)rtk::volume_list_render_kernel<true, Table> : (const void *)rtk::volume_list_render_kernel<false, Table>, &T);
+        });
+    });
 }
 
 rt_status rt_trace_samples_volume(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium, const rt_volume *volume,

@@ -219,97 +219,116 @@ __device__ __forceinline__ void medium_probe_body(const KParams &P, const Medium
 // transmittance at the two shadow verdicts.  One register more than the lit kernel lives across the walks: the med state.  The emitter's
 // verdict needs nothing new — the shadow ray's origin, direction and the parameter of the hit it reached are the lane's own L.o, L.d and
 // L.closest — nor does the environment's.
-template <bool kLens, class Table>
+// The wave loop is one text for both of its forms, like lit_render_body's (RTP_LIT_RENDER_BODY) — RTP_MEDIUM_RENDER_BODY, the body of a
+// function with P, T and C in scope: TOTAL is the number of work indices (wave-uniform) and WORK_OF_MINE what the fetched index `mine`
+// stands for.  Expanded twice rather than branched on inside, so that the frame kernels compile to what they compiled to before the list
+// variants existed (DESIGN.md §19, §29).
+#define RTP_MEDIUM_RENDER_BODY(TOTAL, WORK_OF_MINE)                                                                                                   \
+    using Lit = GlossLit<Table>;                                                                                                                      \
+    const int lane = (int)(threadIdx.x & (kWave - 1));                                                                                                \
+    Lane L;                                                                                                                                           \
+    L.node = kBlocked;                                                                                                                                \
+    L.sp = 0;                                                                                                                                         \
+    L.hit = -1;                                                                                                                                       \
+    L.closest = 1e30f;                                                                                                                                \
+    L.color = mk(0.0f, 0.0f, 0.0f);                                                                                                                   \
+    L.beta = mk(1.0f, 1.0f, 1.0f);                                                                                                                    \
+    L.depth = 0;                                                                                                                                      \
+    L.seed = 0;                                                                                                                                       \
+    int32_t phase = kLightIdle;                                                                                                                       \
+    uint32_t w = 0, nee = 0, env = 0, med = 0;                                                                                                        \
+    LitCarry<Lit> prev_diffuse = LitCarry<Lit>(0);                                                                                                    \
+    f3 next_d = mk(0, 0, 0);                                                                                                                          \
+    LitSamples S;                                                                                                                                     \
+    S.adir = S.ac = S.bdir = S.bc = mk(0, 0, 0);                                                                                                      \
+    S.code = -1;                                                                                                                                      \
+    S.a = S.b = false;                                                                                                                                \
+    uint32_t pool_next = 0, pool_end = 0;  /* (wave-uniform) */                                                                                       \
+    bool exhausted = false;                                                                                                                           \
+    for (;;) {                                                                                                                                        \
+        RTP_LIT_POOL_FETCH(TOTAL, WORK_OF_MINE, T.G, med = medium_seed_of(base_seed, s);)                                                             \
+        const bool busy = phase != kLightIdle;                                                                                                        \
+        if (!__any(busy)) {                                                                                                                           \
+            if (exhausted) break;                                                                                                                     \
+            continue;                                                                                                                                 \
+        }                                                                                                                                             \
+        const bool walking = busy && !traversal_finished<true>(L, kBlocked);                                                                          \
+        const bool ready = busy && !walking;                                                                                                          \
+        const int n_walk = __popcll(__ballot(walking));                                                                                               \
+        const int n_ready = __popcll(__ballot(ready));                                                                                                \
+        if (n_walk == 0 || n_ready >= kLightShadeLanes) {                                                                                             \
+            if (ready) {                                                                                                                              \
+                if (phase == kLightPath) {                                                                                                            \
+                    f3 next_o;                                                                                                                        \
+                    float carry;                                                                                                                      \
+                    bool more;                                                                                                                        \
+                    int32_t events = 0;                                                                                                               \
+                    if (!medium_vertex(L, P, T, nee, env, med, next_o, next_d, S, carry, more, events))                                               \
+                        more = shade_lit2(L, P, T.G, prev_diffuse, nee, env, next_o, next_d, S, carry);                                               \
+                    prev_diffuse = carry;                                                                                                             \
+                    if (!more && (S.a || S.b)) next_d = mk(0, 0, 0);                                                                                  \
+                    if (S.a) {                                                                                                                        \
+                        begin_ray(L, next_o, S.adir, 0);                                                                                              \
+                        phase = S.b ? kLitShadowAB : kLitShadowA;                                                                                     \
+                    } else if (S.b) {                                                                                                                 \
+                        begin_ray(L, next_o, S.bdir, 0);                                                                                              \
+                        phase = kLitShadowB;                                                                                                          \
+                    } else if (more) {                                                                                                                \
+                        begin_ray(L, next_o, next_d, 0);                                                                                              \
+                    } else {                                                                                                                          \
+                        store_sample(P, w, L.color);                                                                                                  \
+                        phase = kLightIdle;                                                                                                           \
+                    }                                                                                                                                 \
+                } else if (phase == kLitShadowB) {                                                                                                    \
+                    if (L.hit < 0) L.color = add(L.color, medium_attenuate(T.M, L.o, L.d, INFINITY, S.bc));                                           \
+                    if (no_next_ray(next_d)) {                                                                                                        \
+                        store_sample(P, w, L.color);                                                                                                  \
+                        phase = kLightIdle;                                                                                                           \
+                    } else {                                                                                                                          \
+                        begin_ray(L, L.o, next_d, 0);                                                                                                 \
+                        phase = kLightPath;                                                                                                           \
+                    }                                                                                                                                 \
+                } else {                                                                                                                              \
+                    if (L.hit == S.code) L.color = add(L.color, medium_attenuate(T.M, L.o, L.d, L.closest, S.ac));                                    \
+                    const bool then_env = phase == kLitShadowAB;                                                                                      \
+                    if (!then_env && no_next_ray(next_d)) {                                                                                           \
+                        store_sample(P, w, L.color);                                                                                                  \
+                        phase = kLightIdle;                                                                                                           \
+                    } else {                                                                                                                          \
+                        begin_ray(L, L.o, then_env ? S.bdir : next_d, 0);                                                                             \
+                        phase = then_env ? kLitShadowB : kLightPath;                                                                                  \
+                    }                                                                                                                                 \
+                }                                                                                                                                     \
+                if (phase == kLightIdle) {                                                                                                            \
+                    L.node = kBlocked;                                                                                                                \
+                    L.sp = 0;                                                                                                                         \
+                }                                                                                                                                     \
+            }                                                                                                                                         \
+        } else {                                                                                                                                      \
+            const bool occlusion = phase == kLitShadowB;                                                                                              \
+            _Pragma("unroll")                                                                                                                         \
+            for (int u = 0; u < 4; ++u) {                                                                                                             \
+                if (!traversal_finished<true>(L, kBlocked)) lit_step(L, P, occlusion);                                                                \
+            }                                                                                                                                         \
+        }                                                                                                                                             \
+    }
+// kList = false: the work indices are [0, P.total_work) — a pass of rt_render_medium's.
+// kList = true (rt_render_volume_adaptive's rounds without a grid; DESIGN.md §29): the first *P.work_count entries of P.work_list, exactly as
+// lit_render_body takes them — the length read once per wave, wave-uniform and clamped to P.work_cap; an empty list leaves before the first
+// atomic; a fetched index `mine` stands for P.work_list[mine], in map_work and in store_sample alike.
+template <bool kLens, class Table, bool kList = false>
 __device__ __forceinline__ void medium_render_body(const KParams &P, const MediumLit<Table> &T, const LensCam &C) {
-    using Lit = GlossLit<Table>;
-    const int lane = (int)(threadIdx.x & (kWave - 1));
-    Lane L;
-    L.node = kBlocked;
-    L.sp = 0;
-    L.hit = -1;
-    L.closest = 1e30f;
-    L.color = mk(0.0f, 0.0f, 0.0f);
-    L.beta = mk(1.0f, 1.0f, 1.0f);
-    L.depth = 0;
-    L.seed = 0;
-    int32_t phase = kLightIdle;
-    uint32_t w = 0, nee = 0, env = 0, med = 0;
-    LitCarry<Lit> prev_diffuse = LitCarry<Lit>(0);
-    f3 next_d = mk(0, 0, 0);
-    LitSamples S;
-    S.adir = S.ac = S.bdir = S.bc = mk(0, 0, 0);
-    S.code = -1;
-    S.a = S.b = false;
-    uint32_t pool_next = 0, pool_end = 0;  // (wave-uniform)
-    bool exhausted = false;
-    for (;;) {
-        RTP_LIT_POOL_FETCH(P.total_work, mine, T.G, med = medium_seed_of(base_seed, s);)
-        const bool busy = phase != kLightIdle;
-        if (!__any(busy)) {
-            if (exhausted) break;
-            continue;
-        }
-        const bool walking = busy && !traversal_finished<true>(L, kBlocked);
-        const bool ready = busy && !walking;
-        const int n_walk = __popcll(__ballot(walking));
-        const int n_ready = __popcll(__ballot(ready));
-        if (n_walk == 0 || n_ready >= kLightShadeLanes) {
-            if (ready) {
-                if (phase == kLightPath) {
-                    f3 next_o;
-                    float carry;
-                    bool more;
-                    int32_t events = 0;
-                    if (!medium_vertex(L, P, T, nee, env, med, next_o, next_d, S, carry, more, events))
-                        more = shade_lit2(L, P, T.G, prev_diffuse, nee, env, next_o, next_d, S, carry);
-                    prev_diffuse = carry;
-                    if (!more && (S.a || S.b)) next_d = mk(0, 0, 0);
-                    if (S.a) {
-                        begin_ray(L, next_o, S.adir, 0);
-                        phase = S.b ? kLitShadowAB : kLitShadowA;
-                    } else if (S.b) {
-                        begin_ray(L, next_o, S.bdir, 0);
-                        phase = kLitShadowB;
-                    } else if (more) {
-                        begin_ray(L, next_o, next_d, 0);
-                    } else {
-                        store_sample(P, w, L.color);
-                        phase = kLightIdle;
-                    }
-                } else if (phase == kLitShadowB) {
-                    if (L.hit < 0) L.color = add(L.color, medium_attenuate(T.M, L.o, L.d, INFINITY, S.bc));
-                    if (no_next_ray(next_d)) {
-                        store_sample(P, w, L.color);
-                        phase = kLightIdle;
-                    } else {
-                        begin_ray(L, L.o, next_d, 0);
-                        phase = kLightPath;
-                    }
-                } else {
-                    if (L.hit == S.code) L.color = add(L.color, medium_attenuate(T.M, L.o, L.d, L.closest, S.ac));
-                    const bool then_env = phase == kLitShadowAB;
-                    if (!then_env && no_next_ray(next_d)) {
-                        store_sample(P, w, L.color);
-                        phase = kLightIdle;
-                    } else {
-                        begin_ray(L, L.o, then_env ? S.bdir : next_d, 0);
-                        phase = then_env ? kLitShadowB : kLightPath;
-                    }
-                }
-                if (phase == kLightIdle) {
-                    L.node = kBlocked;
-                    L.sp = 0;
-                }
-            }
-        } else {
-            const bool occlusion = phase == kLitShadowB;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                if (!traversal_finished<true>(L, kBlocked)) lit_step(L, P, occlusion);
-            }
-        }
+    if constexpr (kList) {
+        uint32_t listed = (uint32_t)__builtin_amdgcn_readfirstlane((int32_t)*P.work_count);
+        if (listed > P.work_cap) listed = P.work_cap;          // (never more entries than the list has room for)
+        if (listed == 0u) return;
+        RTP_MEDIUM_RENDER_BODY(listed, P.work_list[mine])
+    } else {
+        RTP_MEDIUM_RENDER_BODY(P.total_work, mine)
     }
 }
+#undef RTP_MEDIUM_RENDER_BODY
+
 template <bool kLens, class Table>
 __global__ void __launch_bounds__(256) medium_probe_kernel(const KParams P, const MediumLit<Table> T, const LensCam C, uint32_t *nee_seed_out, uint32_t *env_seed_out,
                                                            uint32_t *med_seed_out, int32_t *events_out) {
@@ -320,6 +339,11 @@ constexpr int kMediumWaves = 3;
 template <bool kLens, class Table>
 __global__ void __launch_bounds__(kLightBlock, kMediumWaves) medium_render_kernel(const KParams P, const MediumLit<Table> T, const LensCam C) {
     medium_render_body<kLens>(P, T, C);
+}
+// the list variant: rt_render_volume_adaptive's rounds without a grid (DESIGN.md §29) — the same body on a list whose length lives on the device
+template <bool kLens, class Table>
+__global__ void __launch_bounds__(kLightBlock, kMediumWaves) medium_list_render_kernel(const KParams P, const MediumLit<Table> T, const LensCam C) {
+    medium_render_body<kLens, Table, true>(P, T, C);
 }
 
 }  // namespace rtk

@@ -179,98 +179,112 @@ __device__ __forceinline__ void volume_probe_body(const KParams &P, const Volume
 // medium_render_body's wave loop, restated (a change to either loop has to be made in both, and in lit_render_body's), with the cell walk
 // as the free flight and as the optical depth at the two shadow verdicts.  Nothing more lives across the tree walks than in the medium
 // kernel: the walk's cell indices and plane parameters begin and end inside the shade branch.
-template <bool kLens, class Table>
+// One text for both of its forms, like medium_render_body's (RTP_MEDIUM_RENDER_BODY): TOTAL is the number of work indices (wave-uniform)
+// and WORK_OF_MINE what the fetched index `mine` stands for.
+#define RTP_VOLUME_RENDER_BODY(TOTAL, WORK_OF_MINE)                                                                                                   \
+    using Lit = GlossLit<Table>;                                                                                                                      \
+    const int lane = (int)(threadIdx.x & (kWave - 1));                                                                                                \
+    Lane L;                                                                                                                                           \
+    L.node = kBlocked;                                                                                                                                \
+    L.sp = 0;                                                                                                                                         \
+    L.hit = -1;                                                                                                                                       \
+    L.closest = 1e30f;                                                                                                                                \
+    L.color = mk(0.0f, 0.0f, 0.0f);                                                                                                                   \
+    L.beta = mk(1.0f, 1.0f, 1.0f);                                                                                                                    \
+    L.depth = 0;                                                                                                                                      \
+    L.seed = 0;                                                                                                                                       \
+    int32_t phase = kLightIdle;                                                                                                                       \
+    uint32_t w = 0, nee = 0, env = 0, med = 0;                                                                                                        \
+    LitCarry<Lit> prev_diffuse = LitCarry<Lit>(0);                                                                                                    \
+    f3 next_d = mk(0, 0, 0);                                                                                                                          \
+    LitSamples S;                                                                                                                                     \
+    S.adir = S.ac = S.bdir = S.bc = mk(0, 0, 0);                                                                                                      \
+    S.code = -1;                                                                                                                                      \
+    S.a = S.b = false;                                                                                                                                \
+    uint32_t pool_next = 0, pool_end = 0;  /* (wave-uniform) */                                                                                       \
+    bool exhausted = false;                                                                                                                           \
+    for (;;) {                                                                                                                                        \
+        RTP_LIT_POOL_FETCH(TOTAL, WORK_OF_MINE, T.G, med = medium_seed_of(base_seed, s);)                                                             \
+        const bool busy = phase != kLightIdle;                                                                                                        \
+        if (!__any(busy)) {                                                                                                                           \
+            if (exhausted) break;                                                                                                                     \
+            continue;                                                                                                                                 \
+        }                                                                                                                                             \
+        const bool walking = busy && !traversal_finished<true>(L, kBlocked);                                                                          \
+        const bool ready = busy && !walking;                                                                                                          \
+        const int n_walk = __popcll(__ballot(walking));                                                                                               \
+        const int n_ready = __popcll(__ballot(ready));                                                                                                \
+        if (n_walk == 0 || n_ready >= kLightShadeLanes) {                                                                                             \
+            if (ready) {                                                                                                                              \
+                int32_t cells = 0;          /* (never read: the probe's column) */                                                                    \
+                if (phase == kLightPath) {                                                                                                            \
+                    f3 next_o;                                                                                                                        \
+                    float carry;                                                                                                                      \
+                    bool more;                                                                                                                        \
+                    int32_t events = 0;                                                                                                               \
+                    if (!volume_vertex(L, P, T, nee, env, med, next_o, next_d, S, carry, more, events, cells))                                        \
+                        more = shade_lit2(L, P, T.G, prev_diffuse, nee, env, next_o, next_d, S, carry);                                               \
+                    prev_diffuse = carry;                                                                                                             \
+                    if (!more && (S.a || S.b)) next_d = mk(0, 0, 0);                                                                                  \
+                    if (S.a) {                                                                                                                        \
+                        begin_ray(L, next_o, S.adir, 0);                                                                                              \
+                        phase = S.b ? kLitShadowAB : kLitShadowA;                                                                                     \
+                    } else if (S.b) {                                                                                                                 \
+                        begin_ray(L, next_o, S.bdir, 0);                                                                                              \
+                        phase = kLitShadowB;                                                                                                          \
+                    } else if (more) {                                                                                                                \
+                        begin_ray(L, next_o, next_d, 0);                                                                                              \
+                    } else {                                                                                                                          \
+                        store_sample(P, w, L.color);                                                                                                  \
+                        phase = kLightIdle;                                                                                                           \
+                    }                                                                                                                                 \
+                } else if (phase == kLitShadowB) {                                                                                                    \
+                    if (L.hit < 0) L.color = add(L.color, volume_attenuate(T, L.o, L.d, INFINITY, S.bc, cells));                                      \
+                    if (no_next_ray(next_d)) {                                                                                                        \
+                        store_sample(P, w, L.color);                                                                                                  \
+                        phase = kLightIdle;                                                                                                           \
+                    } else {                                                                                                                          \
+                        begin_ray(L, L.o, next_d, 0);                                                                                                 \
+                        phase = kLightPath;                                                                                                           \
+                    }                                                                                                                                 \
+                } else {                                                                                                                              \
+                    if (L.hit == S.code) L.color = add(L.color, volume_attenuate(T, L.o, L.d, L.closest, S.ac, cells));                               \
+                    const bool then_env = phase == kLitShadowAB;                                                                                      \
+                    if (!then_env && no_next_ray(next_d)) {                                                                                           \
+                        store_sample(P, w, L.color);                                                                                                  \
+                        phase = kLightIdle;                                                                                                           \
+                    } else {                                                                                                                          \
+                        begin_ray(L, L.o, then_env ? S.bdir : next_d, 0);                                                                             \
+                        phase = then_env ? kLitShadowB : kLightPath;                                                                                  \
+                    }                                                                                                                                 \
+                }                                                                                                                                     \
+                if (phase == kLightIdle) {                                                                                                            \
+                    L.node = kBlocked;                                                                                                                \
+                    L.sp = 0;                                                                                                                         \
+                }                                                                                                                                     \
+            }                                                                                                                                         \
+        } else {                                                                                                                                      \
+            const bool occlusion = phase == kLitShadowB;                                                                                              \
+            _Pragma("unroll")                                                                                                                         \
+            for (int u = 0; u < 4; ++u) {                                                                                                             \
+                if (!traversal_finished<true>(L, kBlocked)) lit_step(L, P, occlusion);                                                                \
+            }                                                                                                                                         \
+        }                                                                                                                                             \
+    }
+// kList = false: a pass of rt_render_volume's.  kList = true: rt_render_volume_adaptive's rounds (DESIGN.md §29), the list as
+// medium_render_body takes it.
+template <bool kLens, class Table, bool kList = false>
 __device__ __forceinline__ void volume_render_body(const KParams &P, const VolumeLit<Table> &T, const LensCam &C) {
-    using Lit = GlossLit<Table>;
-    const int lane = (int)(threadIdx.x & (kWave - 1));
-    Lane L;
-    L.node = kBlocked;
-    L.sp = 0;
-    L.hit = -1;
-    L.closest = 1e30f;
-    L.color = mk(0.0f, 0.0f, 0.0f);
-    L.beta = mk(1.0f, 1.0f, 1.0f);
-    L.depth = 0;
-    L.seed = 0;
-    int32_t phase = kLightIdle;
-    uint32_t w = 0, nee = 0, env = 0, med = 0;
-    LitCarry<Lit> prev_diffuse = LitCarry<Lit>(0);
-    f3 next_d = mk(0, 0, 0);
-    LitSamples S;
-    S.adir = S.ac = S.bdir = S.bc = mk(0, 0, 0);
-    S.code = -1;
-    S.a = S.b = false;
-    uint32_t pool_next = 0, pool_end = 0;  // (wave-uniform)
-    bool exhausted = false;
-    for (;;) {
-        RTP_LIT_POOL_FETCH(P.total_work, mine, T.G, med = medium_seed_of(base_seed, s);)
-        const bool busy = phase != kLightIdle;
-        if (!__any(busy)) {
-            if (exhausted) break;
-            continue;
-        }
-        const bool walking = busy && !traversal_finished<true>(L, kBlocked);
-        const bool ready = busy && !walking;
-        const int n_walk = __popcll(__ballot(walking));
-        const int n_ready = __popcll(__ballot(ready));
-        if (n_walk == 0 || n_ready >= kLightShadeLanes) {
-            if (ready) {
-                int32_t cells = 0;          // (never read: the probe's column)
-                if (phase == kLightPath) {
-                    f3 next_o;
-                    float carry;
-                    bool more;
-                    int32_t events = 0;
-                    if (!volume_vertex(L, P, T, nee, env, med, next_o, next_d, S, carry, more, events, cells))
-                        more = shade_lit2(L, P, T.G, prev_diffuse, nee, env, next_o, next_d, S, carry);
-                    prev_diffuse = carry;
-                    if (!more && (S.a || S.b)) next_d = mk(0, 0, 0);
-                    if (S.a) {
-                        begin_ray(L, next_o, S.adir, 0);
-                        phase = S.b ? kLitShadowAB : kLitShadowA;
-                    } else if (S.b) {
-                        begin_ray(L, next_o, S.bdir, 0);
-                        phase = kLitShadowB;
-                    } else if (more) {
-                        begin_ray(L, next_o, next_d, 0);
-                    } else {
-                        store_sample(P, w, L.color);
-                        phase = kLightIdle;
-                    }
-                } else if (phase == kLitShadowB) {
-                    if (L.hit < 0) L.color = add(L.color, volume_attenuate(T, L.o, L.d, INFINITY, S.bc, cells));
-                    if (no_next_ray(next_d)) {
-                        store_sample(P, w, L.color);
-                        phase = kLightIdle;
-                    } else {
-                        begin_ray(L, L.o, next_d, 0);
-                        phase = kLightPath;
-                    }
-                } else {
-                    if (L.hit == S.code) L.color = add(L.color, volume_attenuate(T, L.o, L.d, L.closest, S.ac, cells));
-                    const bool then_env = phase == kLitShadowAB;
-                    if (!then_env && no_next_ray(next_d)) {
-                        store_sample(P, w, L.color);
-                        phase = kLightIdle;
-                    } else {
-                        begin_ray(L, L.o, then_env ? S.bdir : next_d, 0);
-                        phase = then_env ? kLitShadowB : kLightPath;
-                    }
-                }
-                if (phase == kLightIdle) {
-                    L.node = kBlocked;
-                    L.sp = 0;
-                }
-            }
-        } else {
-            const bool occlusion = phase == kLitShadowB;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                if (!traversal_finished<true>(L, kBlocked)) lit_step(L, P, occlusion);
-            }
-        }
+    if constexpr (kList) {
+        uint32_t listed = (uint32_t)__builtin_amdgcn_readfirstlane((int32_t)*P.work_count);
+        if (listed > P.work_cap) listed = P.work_cap;          // (never more entries than the list has room for)
+        if (listed == 0u) return;
+        RTP_VOLUME_RENDER_BODY(listed, P.work_list[mine])
+    } else {
+        RTP_VOLUME_RENDER_BODY(P.total_work, mine)
     }
 }
+#undef RTP_VOLUME_RENDER_BODY
 #undef RTP_LIT_POOL_FETCH          // (defined in rt_light.hip.inc, which leaves it for rt_medium.hip.inc and this file: no expansion of it may follow)
 
 template <bool kLens, class Table>
@@ -283,6 +297,11 @@ constexpr int kVolumeWaves = kMediumWaves;
 template <bool kLens, class Table>
 __global__ void __launch_bounds__(kLightBlock, kVolumeWaves) volume_render_kernel(const KParams P, const VolumeLit<Table> T, const LensCam C) {
     volume_render_body<kLens>(P, T, C);
+}
+// the list variant: rt_render_volume_adaptive's rounds (DESIGN.md §29) — the same body on a list whose length lives on the device
+template <bool kLens, class Table>
+__global__ void __launch_bounds__(kLightBlock, kVolumeWaves) volume_list_render_kernel(const KParams P, const VolumeLit<Table> T, const LensCam C) {
+    volume_render_body<kLens, Table, true>(P, T, C);
 }
 
 }  // namespace rtk

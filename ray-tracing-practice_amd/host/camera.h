@@ -147,7 +147,8 @@ void gpu_render_pipelined(const SceneParams &params, const rt_scene_desc &desc, 
 // shutter; rtp_main --denoise-adaptive-temporal): that file from rt_denoise_temporal_spp instead, the AOVs (first_prim included) from
 // rt_render_aov at noise->min_spp and the two histories swapped per frame; stop_history (with that; rtp_main --stop-history): those AOVs
 // first, rt_adaptive_prior on the previous frame's history, the frame through rt_render_lit_adaptive_prior; medium (rtp_main --fog): the
-// lit frames through rt_render_medium; volume (with medium; rtp_main --fog-grid): through rt_render_volume, this grid in the medium's box
+// lit frames through rt_render_medium; volume (with medium; rtp_main --fog-grid): through rt_render_volume, this grid in the medium's box;
+// medium with noise (rtp_main --fog-noise-target): through rt_render_volume_adaptive (volume may be null) and rt_tonemap_spp
 void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const rt_lens_params &lens, float shutter, bool aov, bool denoise,
                      const rt_nee_params *nee = nullptr, const rt_env *env = nullptr, const rt_env_params *env_params = nullptr,
                      const rt_lit_params *lit = nullptr, const rt_adaptive_params *noise = nullptr, bool denoise_adaptive = false,

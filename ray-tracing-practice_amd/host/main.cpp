@@ -42,6 +42,47 @@ int main(int argc, char *argv[]) {
         if (std::string(argv[a]) == "--denoise") denoise = true;
         if (std::string(argv[a]) == "--denoise-temporal") temporal = true;
     }
+    // extension: `--lit … --fog SIGMA … [--fog-grid FILE] --fog-noise-target T[:min:batch:max]`: the fogged frames through
+    // rt_render_volume_adaptive (adaptive sampling under the medium or the grid, default 16:16:256) and rt_tonemap_spp.  The flag needs --fog
+    // and is not for --adaptive, --denoise*, --aov, --stop-rule, --stop-history or --noise-target.  This block comes before those flags' own,
+    // so that whatever else is given the refusal names this flag.
+    bool fog_noise_on = false;
+    rt_adaptive_params fog_noise;
+    rt_adaptive_params_init(&fog_noise);
+    {
+        bool fog_flag = false;
+        std::string bad, other;
+        for (int a = 2; a < argc; ++a) {
+            const std::string arg = argv[a];
+            if (arg == "--fog") fog_flag = true;
+            if (arg == "--adaptive" || arg.compare(0, 9, "--denoise") == 0 || arg == "--aov" || arg == "--stop-rule" || arg == "--stop-history" ||
+                arg == "--noise-target")
+                other = arg;
+            if (arg == "--fog-noise-target") {
+                fog_noise_on = true;
+                const char *value = a + 1 < argc ? argv[a + 1] : "";
+                char *end = nullptr;
+                fog_noise.threshold = strtof(value, &end);
+                bool ok = end != value && std::isfinite(fog_noise.threshold) && fog_noise.threshold >= 0.0f;
+                if (ok && *end == ':') {
+                    char tail = 0;
+                    ok = sscanf(end + 1, "%d:%d:%d%c", &fog_noise.min_spp, &fog_noise.batch_spp, &fog_noise.max_spp, &tail) == 3 && fog_noise.min_spp >= 2 &&
+                         fog_noise.batch_spp >= 1 && fog_noise.max_spp >= fog_noise.min_spp && fog_noise.max_spp <= 65536;
+                } else if (ok) {
+                    ok = *end == 0;
+                }
+                if (!ok)
+                    bad = "--fog-noise-target takes T[:min:batch:max] with T finite and not negative, min >= 2, batch >= 1 and min <= max <= 65536";
+            }
+        }
+        if (fog_noise_on && bad.empty() && !fog_flag) bad = "--fog-noise-target sets the noise target of fogged frames: it needs --lit --fog SIGMA";
+        if (fog_noise_on && bad.empty() && !other.empty())
+            bad = "--fog-noise-target cannot be combined with " + other + " (not with --adaptive, --denoise*, --aov, --stop-rule, --stop-history or --noise-target)";
+        if (!bad.empty()) {
+            std::cerr << "rtp_main: " << bad << "\n";
+            return 99;
+        }
+    }
     // extension: `--denoise-adaptive-temporal`, with `--adaptive T` or with `--lit … --noise-target T` (pinhole frames only: the
     // reprojection assumes one): --denoise-adaptive with the history carried from frame to frame — rt_denoise_temporal_spp with each
     // frame's counts and moments and AOVs (first_prim included) at min_spp, through rt_tonemap_spp to "<frame file>.denoised".  Not
@@ -192,7 +233,7 @@ int main(int argc, char *argv[]) {
     // extension: `--lit … --fog SIGMA[:ALBEDO[:G]] [--fog-ball cx,cy,cz,r | --fog-box x0,y0,z0,x1,y1,z1]`: the --lit frames through
     // rt_render_medium — a homogeneous grey medium of extinction SIGMA, single-scattering albedo ALBEDO (default 1) and Henyey-Greenstein g
     // G (default 0) in all space, a ball or a box.  --fog needs --lit and is not for --noise-target (adaptive sampling under
-    // a medium is left out); --fog-ball / --fog-box need --fog and exclude each other.
+    // a medium is --fog-noise-target, above); --fog-ball / --fog-box need --fog and exclude each other.
     // `--fog-grid FILE` (with --fog-box): the frames through rt_render_volume — the density grid of FILE fills the box and scales SIGMA cell
     // by cell.  FILE is the ASCII header "VOL1\nnx ny nz\n" and then nx * ny * nz little-endian float32, x fastest.
     bool fog_on = false;
@@ -250,7 +291,7 @@ int main(int argc, char *argv[]) {
         if ((ball || box) && !fog_on) fog_bad = "--fog-ball and --fog-box bound the medium of --fog: they need --fog SIGMA";
         else if (ball && box) fog_bad = "--fog-ball and --fog-box exclude each other: the medium has one region";
         else if (fog_on && !lit_on) fog_bad = "--fog puts a medium into --lit frames: it needs --lit";
-        else if (fog_on && noise_on) fog_bad = "--fog cannot be combined with --noise-target: adaptive sampling under a medium is left out";
+        else if (fog_on && noise_on) fog_bad = "--fog cannot be combined with --noise-target: adaptive sampling under a medium is --fog-noise-target T";
         else if (grid && ball) fog_bad = "--fog-grid fills a box: it cannot be combined with --fog-ball";
         else if (grid && !box) fog_bad = "--fog-grid fills the box of --fog-box: it needs --fog SIGMA and --fog-box";
         if (fog_bad.empty() && grid) {
@@ -489,7 +530,7 @@ int main(int argc, char *argv[]) {
                     std::cerr << "rtp_main: --fog-grid: " << rt_get_last_error_string() << "\n";
                     return 99;
                 }
-                rtp::gpu_render_lens(params, desc, lens, shutter, aov, denoise, nullptr, nullptr, nullptr, &lit, noise_on ? &noise : nullptr,
+                rtp::gpu_render_lens(params, desc, lens, shutter, aov, denoise, nullptr, nullptr, nullptr, &lit, fog_noise_on ? &fog_noise : noise_on ? &noise : nullptr,
                                      denoise_adaptive, &stop_rule, denoise_adaptive_temporal, fog_on ? &fog : nullptr, stop_history, fog_volume);
                 rt_volume_destroy(fog_volume);
                 rt_env_destroy(lit_env);

@@ -339,7 +339,8 @@ void gpu_render_pipelined(const SceneParams &params, const rt_scene_desc &desc, 
 // shutter, the AOVs through rt_render_aov_lens; noise (with lit; rtp_main --lit --noise-target): through
 // rt_render_lit_adaptive and rt_tonemap_spp — every pixel's bytes at its own sample count — and the printed count is the samples taken
 // medium (with lit, without noise; rtp_main --lit --fog): through rt_render_medium; volume (with medium; rtp_main --fog-grid,
-// DESIGN.md §28): through rt_render_volume with this grid in the medium's box.
+// DESIGN.md §28): through rt_render_volume with this grid in the medium's box.  medium with noise (rtp_main --fog-noise-target, DESIGN.md
+// §29): through rt_render_volume_adaptive (the volume may be null) and rt_tonemap_spp, without a stop rule, a prior or a denoiser.
 // denoise_adaptive (with noise; rtp_main --denoise-adaptive): as in gpu_render_adaptive, the AOVs from rt_render_aov_lens at noise->min_spp
 void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const rt_lens_params &lens, float shutter, bool aov, bool denoise,
                      const rt_nee_params *nee, const rt_env *env, const rt_env_params *env_params, const rt_lit_params *lit,
@@ -414,8 +415,12 @@ void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const
             rt_lit_params frame_lit = *lit;
             frame_lit.cam_close = cam_close;
             frame_lit.lens = &lens;
-            RTP_CHECK(rt_render_lit_adaptive_rule(scene, &cam, &frame_lit, noise, stop, nullptr, 0, d_fb, d_spp, spp_denoiser ? spp_denoiser->d_moments : nullptr,
-                                                  nullptr, 1, nullptr));
+            if (medium)          // (rtp_main --fog-noise-target: no denoiser, no stop rule, no prior)
+                RTP_CHECK(rt_render_volume_adaptive(scene, &cam, &frame_lit, medium, volume, noise, nullptr, nullptr, nullptr, 0, d_fb, d_spp, nullptr, nullptr, 1,
+                                                    nullptr));
+            else
+                RTP_CHECK(rt_render_lit_adaptive_rule(scene, &cam, &frame_lit, noise, stop, nullptr, 0, d_fb, d_spp,
+                                                      spp_denoiser ? spp_denoiser->d_moments : nullptr, nullptr, 1, nullptr));
         } else if (lit) {
             rt_lit_params frame_lit = *lit;
             frame_lit.cam_close = cam_close;

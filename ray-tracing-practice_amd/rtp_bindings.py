@@ -530,6 +530,7 @@ RTP_AMD_SYMBOLS = [
     "rt_stop_params_init", "rt_render_adaptive_rule", "rt_render_lit_adaptive_rule", "rt_adaptive_judge",
     "rt_denoise_temporal_spp",
     "rt_adaptive_prior", "rt_render_adaptive_prior", "rt_render_lit_adaptive_prior", "rt_adaptive_judge_prior",
+    "rt_render_volume_adaptive",
 ]
 
 _host = None
@@ -706,6 +707,10 @@ def amd_lib():
             lib.rt_render_adaptive_prior.argtypes = lib.rt_render_adaptive_rule.argtypes + [C.c_void_p]
             lib.rt_render_lit_adaptive_prior.argtypes = lib.rt_render_lit_adaptive_rule.argtypes + [C.c_void_p]
             lib.rt_adaptive_judge_prior.argtypes = lib.rt_adaptive_judge.argtypes + [C.c_void_p]
+        if hasattr(lib, "rt_render_volume_adaptive"):
+            lib.rt_render_volume_adaptive.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(LitParams), C.POINTER(MediumParams), C.c_void_p,
+                                                      C.POINTER(AdaptiveParams), C.POINTER(StopParams), C.c_void_p, C.POINTER(Shard), C.c_int32,
+                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(Timing)]
         lib.rt_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         lib.rt_last_timing.argtypes = [C.c_void_p, C.POINTER(Timing)]
         lib.rt_timing_init.argtypes = [C.POINTER(Timing)]
@@ -1742,6 +1747,53 @@ class DeviceScene:
         finally:
             lib.rt_device_free(d)
         return fb, t
+
+    def render_volume_adaptive(self, cam, d_fb_ptr, d_spp_ptr, d_moments_ptr=None, *, medium=None, volume=None, cam_close=None, lens=None,
+                               emitters=True, nee=None, env=None, env_params=None, shard=None, stream=None, sync=True, sample_first=0, prior=None,
+                               **params):
+        """rt_render_volume_adaptive: render_lit_adaptive's rounds on render_volume's estimator.  The device addresses are
+        render_lit_adaptive's, medium and volume render_volume's; params are rt_adaptive_params fields and rule (None: a NULL
+        rt_stop_params); prior: None, or the device address of 2 floats per local pixel.  Returns the rt_timing of this call."""
+        rule = params.pop("rule", None)
+        p = adaptive_params(**params)
+        t = Timing()
+        self._apply_config()
+        lit = lit_params(cam_close=cam_close, lens=lens, emitters=emitters, nee=nee, env=env, env_params=env_params)
+        stop = None if rule is None else C.byref(stop_params(rule=rule))
+        _check(amd_lib().rt_render_volume_adaptive(self._h, C.byref(cam), C.byref(lit), _medium_struct(medium), _volume_handle(volume), C.byref(p), stop,
+                                                   C.c_void_p(prior or 0), C.byref(shard) if shard else None, sample_first, C.c_void_p(d_fb_ptr),
+                                                   C.c_void_p(d_spp_ptr), C.c_void_p(d_moments_ptr or 0), C.c_void_p(stream or 0),
+                                                   1 if sync else 0, C.byref(t)), "rt_render_volume_adaptive")
+        return t
+
+    def render_volume_adaptive_to_host(self, cam, *, medium=None, volume=None, cam_close=None, lens=None, emitters=True, nee=None, env=None,
+                                       env_params=None, shard=None, sample_first=0, prior=None, **params):
+        """rt_render_volume_adaptive through fresh device buffers: (fb (rows, w, 3) float32 sums, spp (rows, w) int32, moments (rows, w, 2)
+        float32 (S1, S2)) and the rt_timing.  prior: None or a host array (rows, w, 2) float32 (ch, vh)."""
+        lib = amd_lib()
+        rows = lib.rt_shard_rows(cam.image_height, C.byref(shard) if shard else None)
+        w = cam.image_width
+        fb = np.empty((rows, w, 3), dtype=np.float32)
+        spp = np.empty((rows, w), dtype=np.int32)
+        mom = np.empty((rows, w, 2), dtype=np.float32)
+        dev = []
+        try:
+            for a in (fb, spp, mom):
+                d = C.c_void_p()
+                _check(lib.rt_device_alloc(a.nbytes or 12, C.byref(d)), "rt_device_alloc")
+                dev.append(d)
+            if prior is not None:
+                dev.append(_upload(np.ascontiguousarray(np.asarray(prior, dtype=np.float32).reshape(rows, w, 2))))
+                params = {**params, "prior": dev[3].value}
+            t = self.render_volume_adaptive(cam, dev[0].value, dev[1].value, dev[2].value, medium=medium, volume=volume, cam_close=cam_close, lens=lens,
+                                            emitters=emitters, nee=nee, env=env, env_params=env_params, shard=shard, sample_first=sample_first,
+                                            **params)
+            for a, d in zip((fb, spp, mom), dev):
+                _check(lib.rt_copy_to_host(a.ctypes.data, d, a.nbytes), "rt_copy_to_host")
+        finally:
+            for d in dev:
+                lib.rt_device_free(d)
+        return fb, spp, mom, t
 
     def trace_samples_volume(self, cam, ijs, *, medium=None, volume=None, cam_close=None, lens=None, emitters=True, nee=None, env=None, env_params=None):
         """rt_trace_samples_volume: trace_samples_medium's seven columns and the grid cells visited per sample (n,)."""
