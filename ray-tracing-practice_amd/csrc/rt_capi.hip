@@ -3067,6 +3067,15 @@ rt_status with_lit(rt_scene *sc, const LitSetup &S, F &&f) {
         return f(T);
     });
 }
+// the frame kernel of a lit light (any of the four types) from the call's camera, and its list variant
+struct LitKernels {
+    const void *frame, *list;
+};
+extern "C++" template <class Light>
+LitKernels lit_kernels_of(bool lens, const Light &T) {
+    if (lens) return {rtk::lit_frame_kernel_of<true>(T), rtk::lit_list_kernel_of<true>(T)};
+    return {rtk::lit_frame_kernel_of<false>(T), rtk::lit_list_kernel_of<false>(T)};
+}
 }  // namespace
 
 rt_status rt_render_lit(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_shard *shard, int32_t sample_first,
@@ -3074,11 +3083,7 @@ rt_status rt_render_lit(rt_scene *sc, const rt_camera_data *cam_open, const rt_l
     LitSetup S;
     if (const rt_status st = lit_setup("rt_render_lit", cam_open, lit, S)) return st;
     if (!sc) return fail(RT_ERR_INVALID_ARG, "rt_render_lit: null scene");
-    auto with_light = [&](auto frame) {
-        return with_lit(sc, S, [&](const auto &T) {
-            return frame(S.lens ? rtk::lit_frame_kernel_of<true>(T) : rtk::lit_frame_kernel_of<false>(T), &T);
-        });
-    };
+    auto with_light = [&](auto frame) { return with_lit(sc, S, [&](const auto &T) { return frame(lit_kernels_of(S.lens, T).frame, &T); }); };
     return render_light_impl("rt_render_lit", S.env ? &S.env->device : nullptr, with_light, sc, cam_open, shard, sample_first, d_fb_sum, hip_stream, sync, timing,
                              &S.C);
 }
@@ -3183,10 +3188,7 @@ rt_status rt_render_lit_adaptive_prior(rt_scene *sc, const rt_camera_data *cam_o
     if (!d_fb_sum || !d_spp) return fail(RT_ERR_INVALID_ARG, "rt_render_lit_adaptive: null framebuffer or sample counts");
     if (!sc) return fail(RT_ERR_INVALID_ARG, "rt_render_lit_adaptive: null scene");
     return lit_adaptive_run(what, sc, cam_open, S, a, rule, d_prior, shard, sample_first, d_fb_sum, d_spp, d_moments, hip_stream, sync, timing, [&](auto run) {
-        return with_lit(sc, S, [&](const auto &T) {
-            return run(S.lens ? rtk::lit_frame_kernel_of<true>(T) : rtk::lit_frame_kernel_of<false>(T),
-                       S.lens ? rtk::lit_list_kernel_of<true>(T) : rtk::lit_list_kernel_of<false>(T), &T);
-        });
+        return with_lit(sc, S, [&](const auto &T) { return run(lit_kernels_of(S.lens, T).frame, lit_kernels_of(S.lens, T).list, &T); });
     });
 }
 
@@ -3324,6 +3326,13 @@ void rt_medium_params_init(rt_medium_params *p) {
     p->albedo[0] = p->albedo[1] = p->albedo[2] = 1.0f;
 }
 
+// the density grid of rt_render_volume (rt_volume_create, below)
+struct rt_volume {
+    int device = 0;
+    int32_t nx = 0, ny = 0, nz = 0;
+    float *rho = nullptr;              // nx * ny * nz, x fastest
+};
+
 namespace {
 // the medium's checks (after rt_render_lit's parameter checks, before the scene is looked at) → M; M.sigma_t == 0: no medium
 rt_status medium_setup(const char *what, const rt_medium_params *medium, rtk::MediumDev &M) {
@@ -3373,6 +3382,66 @@ rt_status with_medium_lit(rt_scene *sc, const LitSetup &S, const rtk::MediumDev 
         return f(T);
     });
 }
+// the volume's check among the parameters (after the medium's, before the scene is looked at)
+rt_status volume_setup(const char *what, const rt_medium_params *medium, const rtk::MediumDev &M, const rt_volume *volume) {
+    if (volume && !(medium && M.region == 2)) return fail(RT_ERR_INVALID_ARG, std::string(what) + ": a volume needs a medium with region 2 (the box the grid fills)");
+    return RT_OK;
+}
+// with_medium_lit with the grid beside the medium
+extern "C++" template <class F>
+rt_status with_volume_lit(rt_scene *sc, const LitSetup &S, const rtk::MediumDev &M, const rt_volume *volume, F &&f) {
+    return with_medium_lit(sc, S, M, [&](const auto &ML) {
+        const rtk::VolumeLit<std::decay_t<decltype(ML.G.N)>> T{ML, {volume->rho, volume->nx, volume->ny, volume->nz}};
+        return f(T);
+    });
+}
+// The light of a call that may have fog: no medium (sigma_t == 0) is with_lit's, no volume with_medium_lit's
+extern "C++" template <class F>
+rt_status with_fog_lit(rt_scene *sc, const LitSetup &S, const rtk::MediumDev &M, const rt_volume *volume, F &&f) {
+    if (!(M.sigma_t > 0.0f)) return with_lit(sc, S, f);
+    if (!volume) return with_medium_lit(sc, S, M, f);
+    return with_volume_lit(sc, S, M, volume, f);
+}
+
+// the probe kernel of a light with fog (d_cells: the grid's column)
+extern "C++" template <bool kLens, class Table>
+void launch_fog_probe(const rtk::KParams &KP, const rtk::MediumLit<Table> &T, const rtk::LensCam &C, int32_t n, uint32_t *d_nee, uint32_t *d_env, uint32_t *d_med,
+                      int32_t *d_events, int32_t *) {
+    hipLaunchKernelGGL((rtk::medium_probe_kernel<kLens, Table>), dim3((n + 255) / 256), dim3(256), 0, 0, KP, T, C, d_nee, d_env, d_med, d_events);
+}
+extern "C++" template <bool kLens, class Table>
+void launch_fog_probe(const rtk::KParams &KP, const rtk::VolumeLit<Table> &T, const rtk::LensCam &C, int32_t n, uint32_t *d_nee, uint32_t *d_env, uint32_t *d_med,
+                      int32_t *d_events, int32_t *d_cells) {
+    hipLaunchKernelGGL((rtk::volume_probe_kernel<kLens, Table>), dim3((n + 255) / 256), dim3(256), 0, 0, KP, T, C, d_nee, d_env, d_med, d_events, d_cells);
+}
+// rt_trace_samples_medium and rt_trace_samples_volume (volume, cells: the latter's; null in the former) from their probe launch on: the
+// caller has made its checks and handed over what has no medium or no grid.  `what` starts every refusal.
+rt_status fog_probe(const char *what, rt_scene *sc, const rt_camera_data *cam_open, const LitSetup &S, const rtk::MediumDev &M, const rt_volume *volume, rtk::KParams &P,
+                    int32_t n, const int32_t *ijs, float *radiance, int32_t *rays, int32_t *medium_events, uint32_t *final_seed, uint32_t *final_nee_seed,
+                    uint32_t *final_env_seed, uint32_t *final_medium_seed, int32_t *cells) {
+    const std::string w(what);
+    uint32_t *d_med = nullptr;
+    int32_t *d_events = nullptr, *d_cells = nullptr;
+    Scratch mem;
+    if (mem.alloc(d_med, (size_t)n * 4) != hipSuccess || mem.alloc(d_events, (size_t)n * 4) != hipSuccess || (cells && mem.alloc(d_cells, (size_t)n * 4) != hipSuccess))
+        return fail(RT_ERR_OUT_OF_MEMORY, w + ": hipMalloc failed");
+    const rt_status st = run_probe(w + ": ", P, cam_open, n, ijs, radiance, rays, final_seed, final_nee_seed, final_env_seed,
+                                   [&](const rtk::KParams &KP, uint32_t *d_nee, uint32_t *d_env) {
+        auto probe = [&](const auto &T) {
+            if (S.lens) launch_fog_probe<true>(KP, T, S.C, n, d_nee, d_env, d_med, d_events, d_cells);
+            else launch_fog_probe<false>(KP, T, S.C, n, d_nee, d_env, d_med, d_events, d_cells);
+            return RT_OK;
+        };
+        return volume ? with_volume_lit(sc, S, M, volume, probe) : with_medium_lit(sc, S, M, probe);
+    });
+    if (st != RT_OK) return st;
+    // (run_probe has waited for the device)
+    if (hipMemcpy(final_medium_seed, d_med, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(medium_events, d_events, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+        (cells && hipMemcpy(cells, d_cells, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess))
+        return fail(RT_ERR_HIP, w + ": hipMemcpy D2H failed");
+    return RT_OK;
+}
 }  // namespace
 
 rt_status rt_render_medium(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium, const rt_shard *shard,
@@ -3382,14 +3451,7 @@ rt_status rt_render_medium(rt_scene *sc, const rt_camera_data *cam_open, const r
     rtk::MediumDev M{};
     if (const rt_status st = medium_setup("rt_render_medium", medium, M)) return st;
     if (!sc) return fail(RT_ERR_INVALID_ARG, "rt_render_medium: null scene");
-    auto with_light = [&](auto frame) {
-        if (!(M.sigma_t > 0.0f))
-            return with_lit(sc, S, [&](const auto &T) { return frame(S.lens ? rtk::lit_frame_kernel_of<true>(T) : rtk::lit_frame_kernel_of<false>(T), &T); });
-        return with_medium_lit(sc, S, M, [&](const auto &T) {
-            using Table = decltype(T.G.N);
-            return frame(S.lens ? (const void *)rtk::medium_render_kernel<true, Table> : (const void *)rtk::medium_render_kernel<false, Table>, &T);
-        });
-    };
+    auto with_light = [&](auto frame) { return with_fog_lit(sc, S, M, nullptr, [&](const auto &T) { return frame(lit_kernels_of(S.lens, T).frame, &T); }); };
     return render_light_impl("rt_render_medium", S.env ? &S.env->device : nullptr, with_light, sc, cam_open, shard, sample_first, d_fb_sum, hip_stream, sync, timing,
                              &S.C);
 }
@@ -3419,37 +3481,12 @@ rt_status rt_trace_samples_medium(rt_scene *sc, const rt_camera_data *cam_open, 
         }
         return RT_OK;
     }
-    uint32_t *d_med = nullptr;
-    int32_t *d_events = nullptr;
-    Scratch mem;
-    if (mem.alloc(d_med, (size_t)n * 4) != hipSuccess || mem.alloc(d_events, (size_t)n * 4) != hipSuccess)
-        return fail(RT_ERR_OUT_OF_MEMORY, "rt_trace_samples_medium: hipMalloc failed");
-    st = run_probe("rt_trace_samples_medium: ", P, cam_open, n, ijs, radiance, rays, final_seed, final_nee_seed, final_env_seed,
-                   [&](const rtk::KParams &KP, uint32_t *d_nee, uint32_t *d_env) {
-        return with_medium_lit(sc, S, M, [&](const auto &T) {
-            using Table = decltype(T.G.N);
-            const dim3 grid((n + 255) / 256), block(256);
-            if (S.lens) hipLaunchKernelGGL((rtk::medium_probe_kernel<true, Table>), grid, block, 0, 0, KP, T, S.C, d_nee, d_env, d_med, d_events);
-            else hipLaunchKernelGGL((rtk::medium_probe_kernel<false, Table>), grid, block, 0, 0, KP, T, S.C, d_nee, d_env, d_med, d_events);
-            return RT_OK;
-        });
-    });
-    if (st != RT_OK) return st;
-    // (run_probe has waited for the device)
-    if (hipMemcpy(final_medium_seed, d_med, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(medium_events, d_events, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(RT_ERR_HIP, "rt_trace_samples_medium: hipMemcpy D2H failed");
-    return RT_OK;
+    return fog_probe(what, sc, cam_open, S, M, nullptr, P, n, ijs, radiance, rays, medium_events, final_seed, final_nee_seed, final_env_seed, final_medium_seed, nullptr);
 }
 
 // ---- rt_volume / rt_render_volume / rt_trace_samples_volume (rtp_amd.h, "density grid"): rt_render_medium with a density
 // grid in its box.  No volume is rt_render_medium itself, sigma_t == 0 rt_render_lit; otherwise the kernels of rt_volume.hip.inc.
-struct rt_volume {
-    int device = 0;
-    int32_t nx = 0, ny = 0, nz = 0;
-    float *rho = nullptr;              // nx * ny * nz, x fastest
-};
-
+// (struct rt_volume, volume_setup and with_volume_lit stand with the medium's helpers above, where with_fog_lit needs them.)
 rt_status rt_volume_create(const float *density, int32_t nx, int32_t ny, int32_t nz, rt_volume **out_volume) {
     if (!density || !out_volume) return fail(RT_ERR_INVALID_ARG, "rt_volume_create: null argument");
     *out_volume = nullptr;
@@ -3485,29 +3522,6 @@ rt_status rt_volume_destroy(rt_volume *volume) {
     return RT_OK;
 }
 
-namespace {
-// the volume's check among the parameters (after the medium's, before the scene is looked at)
-rt_status volume_setup(const char *what, const rt_medium_params *medium, const rtk::MediumDev &M, const rt_volume *volume) {
-    if (volume && !(medium && M.region == 2)) return fail(RT_ERR_INVALID_ARG, std::string(what) + ": a volume needs a medium with region 2 (the box the grid fills)");
-    return RT_OK;
-}
-// with_medium_lit with the grid beside the medium
-extern "C++" template <class F>
-rt_status with_volume_lit(rt_scene *sc, const LitSetup &S, const rtk::MediumDev &M, const rt_volume *volume, F &&f) {
-    return with_medium_lit(sc, S, M, [&](const auto &ML) {
-        using Table = std::decay_t<decltype(ML.G.N)>;
-        rtk::VolumeLit<Table> T{};
-        T.G = ML.G;
-        T.M = ML.M;
-        T.V.rho = volume->rho;
-        T.V.nx = volume->nx;
-        T.V.ny = volume->ny;
-        T.V.nz = volume->nz;
-        return f(T);
-    });
-}
-}  // namespace
-
 rt_status rt_render_volume(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium, const rt_volume *volume,
                            const rt_shard *shard, int32_t sample_first, float *d_fb_sum, void *hip_stream, int32_t sync, rt_timing *timing) {
     if (!volume) return rt_render_medium(sc, cam_open, lit, medium, shard, sample_first, d_fb_sum, hip_stream, sync, timing);
@@ -3518,14 +3532,7 @@ rt_status rt_render_volume(rt_scene *sc, const rt_camera_data *cam_open, const r
     if (const rt_status st = volume_setup("rt_render_volume", medium, M, volume)) return st;
     if (!sc) return fail(RT_ERR_INVALID_ARG, "rt_render_volume: null scene");
     if (volume->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_render_volume: the volume was created on another device than the scene");
-    auto with_light = [&](auto frame) {
-        if (!(M.sigma_t > 0.0f))
-            return with_lit(sc, S, [&](const auto &T) { return frame(S.lens ? rtk::lit_frame_kernel_of<true>(T) : rtk::lit_frame_kernel_of<false>(T), &T); });
-        return with_volume_lit(sc, S, M, volume, [&](const auto &T) {
-            using Table = decltype(T.G.N);
-            return frame(S.lens ? (const void *)rtk::volume_render_kernel<true, Table> : (const void *)rtk::volume_render_kernel<false, Table>, &T);
-        });
-    };
+    auto with_light = [&](auto frame) { return with_fog_lit(sc, S, M, volume, [&](const auto &T) { return frame(lit_kernels_of(S.lens, T).frame, &T); }); };
     return render_light_impl("rt_render_volume", S.env ? &S.env->device : nullptr, with_light, sc, cam_open, shard, sample_first, d_fb_sum, hip_stream, sync, timing,
                              &S.C);
 }
@@ -3555,17 +3562,7 @@ rt_status rt_render_volume_adaptive(rt_scene *sc, const rt_camera_data *cam_open
     if (!(M.sigma_t > 0.0f))
         return rt_render_lit_adaptive_prior(sc, cam_open, lit, params, stop, shard, sample_first, d_fb_sum, d_spp, d_moments, hip_stream, sync, timing, d_prior);
     return lit_adaptive_run(what, sc, cam_open, S, a, rule, d_prior, shard, sample_first, d_fb_sum, d_spp, d_moments, hip_stream, sync, timing, [&](auto run) {
-        if (!volume)
-            return with_medium_lit(sc, S, M, [&](const auto &T) {
-                using Table = decltype(T.G.N);
-                return run(S.lens ? (const void *)rtk::medium_render_kernel<true, Table> : (const void *)rtk::medium_render_kernel<false, Table>,
-                           S.lens ? (const void *)rtk::medium_list_render_kernel<true, Table> : (const void *)rtk::medium_list_render_kernel<false, Table>, &T);
-            });
-        return with_volume_lit(sc, S, M, volume, [&](const auto &T) {
-            using Table = decltype(T.G.N);
-            return run(S.lens ? (const void *)rtk::volume_render_kernel<true, Table> : (const void *)rtk::volume_render_kernel<false, Table>,
-                       S.lens ? (const void *)rtk::volume_list_render_kernel<true, Table> : (const void *)rtk::volume_list_render_kernel<false, Table>, &T);
-        });
+        return with_fog_lit(sc, S, M, volume, [&](const auto &T) { return run(lit_kernels_of(S.lens, T).frame, lit_kernels_of(S.lens, T).list, &T); });
     });
 }
 
@@ -3595,28 +3592,7 @@ rt_status rt_trace_samples_volume(rt_scene *sc, const rt_camera_data *cam_open, 
         for (int32_t k = 0; k < n; ++k) cells[k] = 0;
         return RT_OK;
     }
-    uint32_t *d_med = nullptr;
-    int32_t *d_events = nullptr, *d_cells = nullptr;
-    Scratch mem;
-    if (mem.alloc(d_med, (size_t)n * 4) != hipSuccess || mem.alloc(d_events, (size_t)n * 4) != hipSuccess || mem.alloc(d_cells, (size_t)n * 4) != hipSuccess)
-        return fail(RT_ERR_OUT_OF_MEMORY, "rt_trace_samples_volume: hipMalloc failed");
-    st = run_probe("rt_trace_samples_volume: ", P, cam_open, n, ijs, radiance, rays, final_seed, final_nee_seed, final_env_seed,
-                   [&](const rtk::KParams &KP, uint32_t *d_nee, uint32_t *d_env) {
-        return with_volume_lit(sc, S, M, volume, [&](const auto &T) {
-            using Table = decltype(T.G.N);
-            const dim3 grid((n + 255) / 256), block(256);
-            if (S.lens) hipLaunchKernelGGL((rtk::volume_probe_kernel<true, Table>), grid, block, 0, 0, KP, T, S.C, d_nee, d_env, d_med, d_events, d_cells);
-            else hipLaunchKernelGGL((rtk::volume_probe_kernel<false, Table>), grid, block, 0, 0, KP, T, S.C, d_nee, d_env, d_med, d_events, d_cells);
-            return RT_OK;
-        });
-    });
-    if (st != RT_OK) return st;
-    // (run_probe has waited for the device)
-    if (hipMemcpy(final_medium_seed, d_med, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(medium_events, d_events, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(cells, d_cells, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess)
-        return fail(RT_ERR_HIP, "rt_trace_samples_volume: hipMemcpy D2H failed");
-    return RT_OK;
+    return fog_probe(what, sc, cam_open, S, M, volume, P, n, ijs, radiance, rays, medium_events, final_seed, final_nee_seed, final_env_seed, final_medium_seed, cells);
 }
 
 void rt_timing_init(rt_timing *t) {

@@ -333,6 +333,27 @@ __device__ __forceinline__ void light_probe_body(const KParams &P, const Light &
 // ray, so no flag for it either.  kGlossy (the light's glossy = 1): a glossy event may sample without a next ray — the pending
 // direction is then zero, and the shadow verdict ends the path (no_next_ray); the carried value is a float.
 constexpr int32_t kLightIdle = 0, kLightPath = 1, kLightShadow = 2;
+// The first half of a wave loop's fetch — RTP_LIGHT_POOL_RESERVE, statements inside `if (idle != 0 && !exhausted)` with lane, idle, P, pool_next,
+// pool_end and exhausted in scope: every idle lane gets the next work index of the wave's pool as `mine` (the pool refilled with one atomic per
+// wave, kLightChunk indices at a time); a chunk that starts at or past TOTAL (wave-uniform) marks the wave exhausted.  `mine` may lie past
+// TOTAL.  Used by light_render_body and by lit_render_body's fetch (RTP_LIT_POOL_FETCH), and undefined after the latter.
+#define RTP_LIGHT_POOL_RESERVE(TOTAL)                                                                                 \
+            const uint32_t cnt = (uint32_t)__popcll(idle);                                                            \
+            const uint32_t rank = (uint32_t)lane_rank(idle);                                                          \
+            const uint32_t avail = pool_end - pool_next;                                                              \
+            uint32_t mine;                                                                                            \
+            if (avail < cnt) {                                                                                        \
+                uint32_t base = 0;                                                                                    \
+                if (lane == 0) base = atomicAdd(P.queue, kLightChunk);                                                \
+                base = __builtin_amdgcn_readfirstlane(base);                                                          \
+                mine = rank < avail ? pool_next + rank : base + (rank - avail);                                       \
+                pool_next = base + (cnt - avail);                                                                     \
+                pool_end = base + kLightChunk;                                                                        \
+                if (base >= (TOTAL)) exhausted = true;                                                                \
+            } else {                                                                                                  \
+                mine = pool_next + rank;                                                                              \
+                pool_next += cnt;                                                                                     \
+            }
 template <class Light, bool kGlossy = false>
 __device__ __forceinline__ void light_render_body(const KParams &P, const Light &T) {
     using Carry = std::conditional_t<kGlossy, float, bool>;
@@ -357,22 +378,7 @@ __device__ __forceinline__ void light_render_body(const KParams &P, const Light 
         // ---- lanes without a sample take the next work indices of the wave's pool (refilled with one atomic)
         const uint64_t idle = __ballot(phase == kLightIdle);
         if (idle != 0 && !exhausted) {
-            const uint32_t cnt = (uint32_t)__popcll(idle);
-            const uint32_t rank = (uint32_t)lane_rank(idle);
-            const uint32_t avail = pool_end - pool_next;
-            uint32_t mine;
-            if (avail < cnt) {
-                uint32_t base = 0;
-                if (lane == 0) base = atomicAdd(P.queue, kLightChunk);
-                base = __builtin_amdgcn_readfirstlane(base);
-                mine = rank < avail ? pool_next + rank : base + (rank - avail);
-                pool_next = base + (cnt - avail);
-                pool_end = base + kLightChunk;
-                if (base >= P.total_work) exhausted = true;
-            } else {
-                mine = pool_next + rank;
-                pool_next += cnt;
-            }
+            RTP_LIGHT_POOL_RESERVE(P.total_work)
             if (phase == kLightIdle && mine < P.total_work) {
                 w = mine;
                 int32_t pi, pj;
@@ -546,19 +552,58 @@ __device__ __forceinline__ void lit_step(Lane &L, const KParams &P, bool occlusi
     }
 }
 
-// ---- probe (rt_trace_samples_lit) ----------------------------------------------------------------------------------------------------
-template <bool kLens, class Lit>
-__device__ __forceinline__ void lit_probe_body(const KParams &P, const Lit &T, const LensCam &C, uint32_t *nee_seed_out, uint32_t *env_seed_out) {
+// ---- what fog adds to a lit light (DESIGN.md §31) --------------------------------------------------------------------------------------
+// The probe and the wave loop below are written once, for a light with or without fog (Lit<Table>, GlossLit<Table>; MediumLit<Table> and
+// VolumeLit<Table> of rt_medium.hip.inc and rt_volume.hip.inc).  What differs is four functions overloaded on the light's type; those of a
+// light with fog stand in its own file and are found through the light's type where the bodies are instantiated:
+//   fog_lit(T)                           the light that shade_lit2 and the streams see: T itself, or the GlossLit inside
+//   fog_seed(T, base_seed, s)            the start of the sample's medium stream (0: there is none)
+//   fog_vertex(L, P, T, …, n)            the free flight in front of the surface vertex.  false: no event — the caller runs shade_lit2, with
+//                                        nothing changed but (perhaps) one draw of med.  true: the vertex was a medium vertex and is done:
+//                                        `more` as shade_lit2 returns it, the light samples in S, the next ray (out_o, out_d), what it carries
+//   fog_tr(T, o, d, t_end, c, n)         the contribution c of a shadow ray (o, d) that ended at t_end, times its transmittance
+// n counts for the probes (FogCount); the wave loop calls the two forms without it, whose counters are their own locals and never read.
+struct FogCount {
+    int32_t events = 0, cells = 0;       // medium vertices; grid cells visited
+};
+template <class Table> __device__ __forceinline__ const Lit<Table> &fog_lit(const Lit<Table> &T) { return T; }
+template <class Table> __device__ __forceinline__ const GlossLit<Table> &fog_lit(const GlossLit<Table> &T) { return T; }
+template <class Table> __device__ __forceinline__ uint32_t fog_seed(const Lit<Table> &, uint32_t, int32_t) { return 0; }
+template <class Table, class Carry>
+__device__ __forceinline__ bool fog_vertex(Lane &, const KParams &, const Lit<Table> &, uint32_t &, uint32_t &, uint32_t &, f3 &, f3 &, LitSamples &, Carry &, bool &,
+                                           FogCount &) {
+    return false;
+}
+template <class Table> __device__ __forceinline__ f3 fog_tr(const Lit<Table> &, f3, f3, float, f3 c, FogCount &) { return c; }
+template <class Light, class Carry>
+__device__ __forceinline__ bool fog_vertex(Lane &L, const KParams &P, const Light &T, uint32_t &nee, uint32_t &env, uint32_t &med, f3 &out_o, f3 &out_d, LitSamples &S,
+                                           Carry &carry_out, bool &more) {
+    FogCount n;
+    return fog_vertex(L, P, T, nee, env, med, out_o, out_d, S, carry_out, more, n);
+}
+template <class Light>
+__device__ __forceinline__ f3 fog_tr(const Light &T, f3 o, f3 d, float t_end, f3 c) {
+    FogCount n;
+    return fog_tr(T, o, d, t_end, c, n);
+}
+
+// ---- probe (rt_trace_samples_lit, _medium, _volume) ------------------------------------------------------------------------------------
+// med_seed_out and events_out (a light under a medium), cells_out (a density grid): null where the call has no such column
+template <bool kLens, class Light>
+__device__ __forceinline__ void lit_probe_body(const KParams &P, const Light &T, const LensCam &C, uint32_t *nee_seed_out, uint32_t *env_seed_out,
+                                               uint32_t *med_seed_out = nullptr, int32_t *events_out = nullptr, int32_t *cells_out = nullptr) {
+    using Lit = std::decay_t<decltype(fog_lit(T))>;
     const int g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= P.probe_n) return;
     const int32_t i = P.probe_ijs[3 * g], j = P.probe_ijs[3 * g + 1], s = P.probe_ijs[3 * g + 2];
     Lane L;
     const uint32_t base_seed = wang_hash((uint32_t)i * (uint32_t)P.width + (uint32_t)j);
-    uint32_t nee = light_seed_of(T.N, base_seed, s), env = light_seed_of(T.E, base_seed, s);
+    uint32_t nee = light_seed_of(fog_lit(T).N, base_seed, s), env = light_seed_of(fog_lit(T).E, base_seed, s), med = fog_seed(T, base_seed, s);
     f3 ray_o, ray_d;
     lit_start<kLens>(L, P, C, i, j, base_seed, s, ray_o, ray_d);
     begin_ray(L, ray_o, ray_d, 0);
     int32_t rays = 0;
+    FogCount n;
     LitCarry<Lit> prev_diffuse = LitCarry<Lit>(0);
     if (P.max_depth > 0) {
         for (;;) {
@@ -567,18 +612,20 @@ __device__ __forceinline__ void lit_probe_body(const KParams &P, const Lit &T, c
             LitSamples S;
             S.code = -1;
             LitCarry<Lit> diffuse;
-            const bool more = shade_lit2(L, P, T, prev_diffuse, nee, env, ray_o, ray_d, S, diffuse);
+            bool more;
+            if (!fog_vertex(L, P, T, nee, env, med, ray_o, ray_d, S, diffuse, more, n))
+                more = shade_lit2(L, P, fog_lit(T), prev_diffuse, nee, env, ray_o, ray_d, S, diffuse);
             if (S.a) {
                 rays++;
                 begin_ray(L, ray_o, S.adir, 0);
                 while (!traversal_finished<true>(L, kBlocked)) lit_step(L, P, false);
-                if (L.hit == S.code) L.color = add(L.color, S.ac);
+                if (L.hit == S.code) L.color = add(L.color, fog_tr(T, L.o, L.d, L.closest, S.ac, n));
             }
             if (S.b) {
                 rays++;
                 begin_ray(L, ray_o, S.bdir, 0);
                 while (!traversal_finished<true>(L, kBlocked)) lit_step(L, P, true);
-                if (L.hit < 0) L.color = add(L.color, S.bc);
+                if (L.hit < 0) L.color = add(L.color, fog_tr(T, L.o, L.d, INFINITY, S.bc, n));
             }
             if (!more) break;
             prev_diffuse = diffuse;
@@ -590,37 +637,28 @@ __device__ __forceinline__ void lit_probe_body(const KParams &P, const Lit &T, c
     P.probe_seed[g] = L.seed;
     nee_seed_out[g] = nee;
     env_seed_out[g] = env;
+    if (med_seed_out) {
+        med_seed_out[g] = med;
+        events_out[g] = n.events;
+    }
+    if (cells_out) cells_out[g] = n.cells;
 }
 
-// ---- the trace kernel of rt_render_lit -----------------------------------------------------------------------------------------------
+// ---- the trace kernel of rt_render_lit, rt_render_medium and rt_render_volume ---------------------------------------------------------
+// (one wave loop for the four lights, through the hooks above: a light with fog keeps one register more across the walks, the med state,
+// and nothing else — a shadow verdict's transmittance needs only the lane's own L.o, L.d and L.closest; DESIGN.md §31)
 // light_render_body's wave loop with a second shadow phase: path → emitter shadow (a full closest-hit walk) → environment shadow (ends at
 // its first hit) → path; a phase is skipped when its light gave no sample.  kLitShadowAB is the emitter's walk of a vertex whose
 // environment sample still waits.  Across the emitter's walk a lane holds the next direction, both pending contributions, the
 // environment's direction and the target (thirteen registers); across the environment's, the next direction and its contribution.
 constexpr int32_t kLitShadowA = 2, kLitShadowAB = 3, kLitShadowB = 4;
-// The fetch of the wave loop — RTP_LIT_POOL_FETCH, a statement with lane, L, P, C, phase, w, nee, env, prev_diffuse, pool_next, pool_end and
-// exhausted in scope: LIGHT is the Lit<Table> whose streams start, ALSO a statement run for a lane that takes a sample, with base_seed and s
-// at hand (empty in the lit kernels; rt_medium.hip.inc starts its own stream there, and undefines the macro)
-#define RTP_LIT_POOL_FETCH(TOTAL, WORK_OF_MINE, LIGHT, ALSO)                                                        \
+// The fetch of the wave loop — RTP_LIT_POOL_FETCH, a statement with lane, L, P, T, C, phase, w, nee, env, med, prev_diffuse, pool_next,
+// pool_end and exhausted in scope: RTP_LIGHT_POOL_RESERVE's index, and the start of the sample it stands for
+#define RTP_LIT_POOL_FETCH(TOTAL, WORK_OF_MINE)                                                                     \
         /* ---- lanes without a sample take the next work indices of the wave's pool (refilled with one atomic) */  \
         const uint64_t idle = __ballot(phase == kLightIdle);                                                        \
         if (idle != 0 && !exhausted) {                                                                              \
-            const uint32_t cnt = (uint32_t)__popcll(idle);                                                          \
-            const uint32_t rank = (uint32_t)lane_rank(idle);                                                        \
-            const uint32_t avail = pool_end - pool_next;                                                            \
-            uint32_t mine;                                                                                          \
-            if (avail < cnt) {                                                                                      \
-                uint32_t base = 0;                                                                                  \
-                if (lane == 0) base = atomicAdd(P.queue, kLightChunk);                                              \
-                base = __builtin_amdgcn_readfirstlane(base);                                                        \
-                mine = rank < avail ? pool_next + rank : base + (rank - avail);                                     \
-                pool_next = base + (cnt - avail);                                                                   \
-                pool_end = base + kLightChunk;                                                                      \
-                if (base >= (TOTAL)) exhausted = true;                                                              \
-            } else {                                                                                                \
-                mine = pool_next + rank;                                                                            \
-                pool_next += cnt;                                                                                   \
-            }                                                                                                       \
+            RTP_LIGHT_POOL_RESERVE(TOTAL)                                                                           \
             if (phase == kLightIdle && mine < (TOTAL)) {                                                            \
                 w = (WORK_OF_MINE);                                                                                 \
                 int32_t pi, pj;                                                                                     \
@@ -628,11 +666,11 @@ constexpr int32_t kLitShadowA = 2, kLitShadowAB = 3, kLitShadowB = 4;
                 map_work(P, w, pi, pj, k);                                                                          \
                 const int32_t s = P.pass_first + (int32_t)k;                                                        \
                 const uint32_t base_seed = wang_hash((uint32_t)pi * (uint32_t)P.width + (uint32_t)pj);              \
-                nee = light_seed_of((LIGHT).N, base_seed, s);                                                       \
-                env = light_seed_of((LIGHT).E, base_seed, s);                                                       \
+                nee = light_seed_of(fog_lit(T).N, base_seed, s);                                                    \
+                env = light_seed_of(fog_lit(T).E, base_seed, s);                                                    \
                 f3 o, d;                                                                                            \
                 lit_start<kLens>(L, P, C, pi, pj, base_seed, s, o, d);                                              \
-                ALSO                                                                                                \
+                med = fog_seed(T, base_seed, s);                                                                    \
                 begin_ray(L, o, d, 0);                                                                              \
                 prev_diffuse = LitCarry<Lit>(0);                                                                    \
                 phase = kLightPath;                                                                                 \
@@ -640,7 +678,10 @@ constexpr int32_t kLitShadowA = 2, kLitShadowAB = 3, kLitShadowB = 4;
         }
 // The wave loop is one text for both of its forms — RTP_LIT_RENDER_BODY, the body of a function with P, T and C in scope: TOTAL is the
 // number of work indices (wave-uniform) and WORK_OF_MINE what the fetched index `mine` stands for.  Expanded twice rather than branched
-// on inside, so that the frame kernels compile to what they compiled to before the list variants existed (DESIGN.md §19).
+// on inside, so that the frame kernels compile to what they compiled to before the list variants existed (DESIGN.md §19).  Lit is the type
+// of fog_lit(T); the guards kLitGlossy<Lit> are constant-true under fog, whose light is always a GlossLit.  kFog (T has a medium) stands in
+// front of the free flight so that without fog the front end emits `more = shade_lit2(…)` alone: with a call that returns false in its
+// place, the lit kernels' instructions came out in another order (DESIGN.md §31).
 #define RTP_LIT_RENDER_BODY(TOTAL, WORK_OF_MINE)                                                                    \
     const int lane = (int)(threadIdx.x & (kWave - 1));                                                              \
     Lane L;                                                                                                         \
@@ -653,7 +694,7 @@ constexpr int32_t kLitShadowA = 2, kLitShadowAB = 3, kLitShadowB = 4;
     L.depth = 0;                                                                                                    \
     L.seed = 0;                                                                                                     \
     int32_t phase = kLightIdle;                                                                                     \
-    uint32_t w = 0, nee = 0, env = 0;                                                                               \
+    uint32_t w = 0, nee = 0, env = 0, med = 0;                                                                      \
     LitCarry<Lit> prev_diffuse = LitCarry<Lit>(0);                                                                  \
     f3 next_d = mk(0, 0, 0);                                                                                        \
     LitSamples S;                                                                                                   \
@@ -663,7 +704,7 @@ constexpr int32_t kLitShadowA = 2, kLitShadowAB = 3, kLitShadowB = 4;
     uint32_t pool_next = 0, pool_end = 0;  /* (wave-uniform) */                                                     \
     bool exhausted = false;                                                                                         \
     for (;;) {                                                                                                      \
-        RTP_LIT_POOL_FETCH(TOTAL, WORK_OF_MINE, T, )                                                                \
+        RTP_LIT_POOL_FETCH(TOTAL, WORK_OF_MINE)                                                                     \
         const bool busy = phase != kLightIdle;                                                                      \
         if (!__any(busy)) {                                                                                         \
             if (exhausted) break;                                                                                   \
@@ -678,7 +719,9 @@ constexpr int32_t kLitShadowA = 2, kLitShadowAB = 3, kLitShadowB = 4;
                 if (phase == kLightPath) {                                                                          \
                     f3 next_o;                                                                                      \
                     LitCarry<Lit> diffuse;                                                                          \
-                    const bool more = shade_lit2(L, P, T, prev_diffuse, nee, env, next_o, next_d, S, diffuse);      \
+                    bool more;                                                                                      \
+                    if (!kFog || !fog_vertex(L, P, T, nee, env, med, next_o, next_d, S, diffuse, more))             \
+                        more = shade_lit2(L, P, fog_lit(T), prev_diffuse, nee, env, next_o, next_d, S, diffuse);    \
                     prev_diffuse = diffuse;                                                                         \
                     if (kLitGlossy<Lit> && !more && (S.a || S.b)) next_d = mk(0, 0, 0);                             \
                     if (S.a) {                                                                                      \
@@ -694,7 +737,7 @@ constexpr int32_t kLitShadowA = 2, kLitShadowAB = 3, kLitShadowB = 4;
                         phase = kLightIdle;                                                                         \
                     }                                                                                               \
                 } else if (phase == kLitShadowB) {                                                                  \
-                    if (L.hit < 0) L.color = add(L.color, S.bc);                                                    \
+                    if (L.hit < 0) L.color = add(L.color, fog_tr(T, L.o, L.d, INFINITY, S.bc));                     \
                     if (kLitGlossy<Lit> && no_next_ray(next_d)) {                                                   \
                         store_sample(P, w, L.color);                                                                \
                         phase = kLightIdle;                                                                         \
@@ -703,7 +746,7 @@ constexpr int32_t kLitShadowA = 2, kLitShadowAB = 3, kLitShadowB = 4;
                         phase = kLightPath;                                                                         \
                     }                                                                                               \
                 } else {                                                                                            \
-                    if (L.hit == S.code) L.color = add(L.color, S.ac);                                              \
+                    if (L.hit == S.code) L.color = add(L.color, fog_tr(T, L.o, L.d, L.closest, S.ac));              \
                     const bool then_env = phase == kLitShadowAB;                                                    \
                     if (kLitGlossy<Lit> && !then_env && no_next_ray(next_d)) {                                      \
                         store_sample(P, w, L.color);                                                                \
@@ -733,8 +776,10 @@ constexpr int32_t kLitShadowA = 2, kLitShadowAB = 3, kLitShadowB = 4;
 // store_sample alike.  The fetch itself is the same: chunks of kLightChunk from P.queue until a chunk starts at or past the length, so an
 // empty list leaves before the first atomic, a list shorter than a chunk is one wave's (every other wave's first chunk starts past the
 // end), and the lanes of a last chunk that reaches past the end stay idle until the wave's next fetch finds the queue dry.
-template <bool kLens, class Lit, bool kList = false>
-__device__ __forceinline__ void lit_render_body(const KParams &P, const Lit &T, const LensCam &C) {
+template <bool kLens, class Light, bool kList = false>
+__device__ __forceinline__ void lit_render_body(const KParams &P, const Light &T, const LensCam &C) {
+    using Lit = std::decay_t<decltype(fog_lit(T))>;
+    constexpr bool kFog = !std::is_same_v<Lit, Light>;
     if constexpr (kList) {
         uint32_t listed = (uint32_t)__builtin_amdgcn_readfirstlane((int32_t)*P.work_count);
         if (listed > P.work_cap) listed = P.work_cap;          // (never more entries than the list has room for)
@@ -745,7 +790,8 @@ __device__ __forceinline__ void lit_render_body(const KParams &P, const Lit &T, 
     }
 }
 #undef RTP_LIT_RENDER_BODY
-// (RTP_LIT_POOL_FETCH stays defined: rt_medium.hip.inc, included right after this file, expands it once more and undefines it)
+#undef RTP_LIT_POOL_FETCH
+#undef RTP_LIGHT_POOL_RESERVE
 
 template <bool kLens, class Table>
 __global__ void __launch_bounds__(256) lit_probe_kernel(const KParams P, const Lit<Table> T, const LensCam C, uint32_t *nee_seed_out, uint32_t *env_seed_out) {

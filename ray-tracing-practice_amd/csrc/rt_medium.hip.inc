@@ -145,12 +145,16 @@ __device__ __forceinline__ void medium_vertex_at(Lane &L, const KParams &P, cons
     more = true;
 }
 
-// The free-flight step of a lane whose path ray has finished its closest-hit query (L.hit, L.closest), in front of the surface vertex.
-// false: no event — the caller runs shade_lit2, with nothing changed but (perhaps) one draw of med.  true: the vertex is a medium vertex and
-// is done: `more` as shade_lit2 returns it, the light samples in S, the next ray (out_o, out_d) and what it carries
+// ---- the medium's hooks in lit_probe_body and lit_render_body (rt_light.hip.inc, "what fog adds to a lit light"; DESIGN.md §31) ------------
+template <class Table> __device__ __forceinline__ const GlossLit<Table> &fog_lit(const MediumLit<Table> &T) { return T.G; }
+template <class Table> __device__ __forceinline__ uint32_t fog_seed(const MediumLit<Table> &, uint32_t base_seed, int32_t s) { return medium_seed_of(base_seed, s); }
+template <class Table> __device__ __forceinline__ f3 fog_tr(const MediumLit<Table> &T, f3 o, f3 d, float t_end, f3 c, FogCount &) {
+    return medium_attenuate(T.M, o, d, t_end, c);
+}
+// The free-flight step of a lane whose path ray has finished its closest-hit query (L.hit, L.closest), in front of the surface vertex
 template <class Table>
-__device__ __forceinline__ bool medium_vertex(Lane &L, const KParams &P, const MediumLit<Table> &T, uint32_t &nee, uint32_t &env, uint32_t &med, f3 &out_o,
-                                              f3 &out_d, LitSamples &S, float &carry_out, bool &more, int32_t &events) {
+__device__ __forceinline__ bool fog_vertex(Lane &L, const KParams &P, const MediumLit<Table> &T, uint32_t &nee, uint32_t &env, uint32_t &med, f3 &out_o, f3 &out_d,
+                                           LitSamples &S, float &carry_out, bool &more, FogCount &n) {
     const MediumDev &M = T.M;
     float t0, t1;
     if (!medium_interval(M, L.o, L.d, L.hit < 0 ? INFINITY : L.closest, t0, t1)) return false;
@@ -159,191 +163,28 @@ __device__ __forceinline__ bool medium_vertex(Lane &L, const KParams &P, const M
     if (u == 0.0f) return false;
     const float s = -log_libm(u) / M.sigma_t;
     if (!(s < (t1 - t0) * len)) return false;
-    medium_vertex_at(L, P, T.G, M, nee, env, med, add(L.o, scale(t0 + s / len, L.d)), out_o, out_d, S, carry_out, more, events);
+    medium_vertex_at(L, P, T.G, M, nee, env, med, add(L.o, scale(t0 + s / len, L.d)), out_o, out_d, S, carry_out, more, n.events);
     return true;
 }
 
-// ---- probe (rt_trace_samples_medium): lit_probe_body with the free-flight step and the transmittance --------------------------------
-template <bool kLens, class Table>
-__device__ __forceinline__ void medium_probe_body(const KParams &P, const MediumLit<Table> &T, const LensCam &C, uint32_t *nee_seed_out, uint32_t *env_seed_out,
-                                                  uint32_t *med_seed_out, int32_t *events_out) {
-    const int g = blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= P.probe_n) return;
-    const int32_t i = P.probe_ijs[3 * g], j = P.probe_ijs[3 * g + 1], s = P.probe_ijs[3 * g + 2];
-    Lane L;
-    const uint32_t base_seed = wang_hash((uint32_t)i * (uint32_t)P.width + (uint32_t)j);
-    uint32_t nee = light_seed_of(T.G.N, base_seed, s), env = light_seed_of(T.G.E, base_seed, s), med = medium_seed_of(base_seed, s);
-    f3 ray_o, ray_d;
-    lit_start<kLens>(L, P, C, i, j, base_seed, s, ray_o, ray_d);
-    begin_ray(L, ray_o, ray_d, 0);
-    int32_t rays = 0, events = 0;
-    float prev = 0.0f;
-    if (P.max_depth > 0) {
-        for (;;) {
-            rays++;
-            while (!traversal_finished<true>(L, kBlocked)) lit_step(L, P, false);
-            LitSamples S;
-            S.code = -1;
-            float carry;
-            bool more;
-            if (!medium_vertex(L, P, T, nee, env, med, ray_o, ray_d, S, carry, more, events)) more = shade_lit2(L, P, T.G, prev, nee, env, ray_o, ray_d, S, carry);
-            if (S.a) {
-                rays++;
-                begin_ray(L, ray_o, S.adir, 0);
-                while (!traversal_finished<true>(L, kBlocked)) lit_step(L, P, false);
-                if (L.hit == S.code) L.color = add(L.color, medium_attenuate(T.M, L.o, L.d, L.closest, S.ac));
-            }
-            if (S.b) {
-                rays++;
-                begin_ray(L, ray_o, S.bdir, 0);
-                while (!traversal_finished<true>(L, kBlocked)) lit_step(L, P, true);
-                if (L.hit < 0) L.color = add(L.color, medium_attenuate(T.M, L.o, L.d, INFINITY, S.bc));
-            }
-            if (!more) break;
-            prev = carry;
-            begin_ray(L, ray_o, ray_d, 0);
-        }
-    }
-    P.probe_rad[3 * g] = L.color.x; P.probe_rad[3 * g + 1] = L.color.y; P.probe_rad[3 * g + 2] = L.color.z;
-    P.probe_rays[g] = rays;
-    P.probe_seed[g] = L.seed;
-    nee_seed_out[g] = nee;
-    env_seed_out[g] = env;
-    med_seed_out[g] = med;
-    events_out[g] = events;
-}
-
-// ---- the trace kernel of rt_render_medium ---------------------------------------------------------------------------------------------
-// lit_render_body's wave loop (the fetch is its own text, RTP_LIT_POOL_FETCH; the rest is RTP_LIT_RENDER_BODY's, restated: a change
-// to either loop has to be made in both) with the free-flight step in front of the path's shade and the
-// transmittance at the two shadow verdicts.  One register more than the lit kernel lives across the walks: the med state.  The emitter's
-// verdict needs nothing new — the shadow ray's origin, direction and the parameter of the hit it reached are the lane's own L.o, L.d and
-// L.closest — nor does the environment's.
-// The wave loop is one text for both of its forms, like lit_render_body's (RTP_LIT_RENDER_BODY) — RTP_MEDIUM_RENDER_BODY, the body of a
-// function with P, T and C in scope: TOTAL is the number of work indices (wave-uniform) and WORK_OF_MINE what the fetched index `mine`
-// stands for.  Expanded twice rather than branched on inside, so that the frame kernels compile to what they compiled to before the list
-// variants existed (DESIGN.md §19, §29).
-#define RTP_MEDIUM_RENDER_BODY(TOTAL, WORK_OF_MINE)                                                                                                   \
-    using Lit = GlossLit<Table>;                                                                                                                      \
-    const int lane = (int)(threadIdx.x & (kWave - 1));                                                                                                \
-    Lane L;                                                                                                                                           \
-    L.node = kBlocked;                                                                                                                                \
-    L.sp = 0;                                                                                                                                         \
-    L.hit = -1;                                                                                                                                       \
-    L.closest = 1e30f;                                                                                                                                \
-    L.color = mk(0.0f, 0.0f, 0.0f);                                                                                                                   \
-    L.beta = mk(1.0f, 1.0f, 1.0f);                                                                                                                    \
-    L.depth = 0;                                                                                                                                      \
-    L.seed = 0;                                                                                                                                       \
-    int32_t phase = kLightIdle;                                                                                                                       \
-    uint32_t w = 0, nee = 0, env = 0, med = 0;                                                                                                        \
-    LitCarry<Lit> prev_diffuse = LitCarry<Lit>(0);                                                                                                    \
-    f3 next_d = mk(0, 0, 0);                                                                                                                          \
-    LitSamples S;                                                                                                                                     \
-    S.adir = S.ac = S.bdir = S.bc = mk(0, 0, 0);                                                                                                      \
-    S.code = -1;                                                                                                                                      \
-    S.a = S.b = false;                                                                                                                                \
-    uint32_t pool_next = 0, pool_end = 0;  /* (wave-uniform) */                                                                                       \
-    bool exhausted = false;                                                                                                                           \
-    for (;;) {                                                                                                                                        \
-        RTP_LIT_POOL_FETCH(TOTAL, WORK_OF_MINE, T.G, med = medium_seed_of(base_seed, s);)                                                             \
-        const bool busy = phase != kLightIdle;                                                                                                        \
-        if (!__any(busy)) {                                                                                                                           \
-            if (exhausted) break;                                                                                                                     \
-            continue;                                                                                                                                 \
-        }                                                                                                                                             \
-        const bool walking = busy && !traversal_finished<true>(L, kBlocked);                                                                          \
-        const bool ready = busy && !walking;                                                                                                          \
-        const int n_walk = __popcll(__ballot(walking));                                                                                               \
-        const int n_ready = __popcll(__ballot(ready));                                                                                                \
-        if (n_walk == 0 || n_ready >= kLightShadeLanes) {                                                                                             \
-            if (ready) {                                                                                                                              \
-                if (phase == kLightPath) {                                                                                                            \
-                    f3 next_o;                                                                                                                        \
-                    float carry;                                                                                                                      \
-                    bool more;                                                                                                                        \
-                    int32_t events = 0;                                                                                                               \
-                    if (!medium_vertex(L, P, T, nee, env, med, next_o, next_d, S, carry, more, events))                                               \
-                        more = shade_lit2(L, P, T.G, prev_diffuse, nee, env, next_o, next_d, S, carry);                                               \
-                    prev_diffuse = carry;                                                                                                             \
-                    if (!more && (S.a || S.b)) next_d = mk(0, 0, 0);                                                                                  \
-                    if (S.a) {                                                                                                                        \
-                        begin_ray(L, next_o, S.adir, 0);                                                                                              \
-                        phase = S.b ? kLitShadowAB : kLitShadowA;                                                                                     \
-                    } else if (S.b) {                                                                                                                 \
-                        begin_ray(L, next_o, S.bdir, 0);                                                                                              \
-                        phase = kLitShadowB;                                                                                                          \
-                    } else if (more) {                                                                                                                \
-                        begin_ray(L, next_o, next_d, 0);                                                                                              \
-                    } else {                                                                                                                          \
-                        store_sample(P, w, L.color);                                                                                                  \
-                        phase = kLightIdle;                                                                                                           \
-                    }                                                                                                                                 \
-                } else if (phase == kLitShadowB) {                                                                                                    \
-                    if (L.hit < 0) L.color = add(L.color, medium_attenuate(T.M, L.o, L.d, INFINITY, S.bc));                                           \
-                    if (no_next_ray(next_d)) {                                                                                                        \
-                        store_sample(P, w, L.color);                                                                                                  \
-                        phase = kLightIdle;                                                                                                           \
-                    } else {                                                                                                                          \
-                        begin_ray(L, L.o, next_d, 0);                                                                                                 \
-                        phase = kLightPath;                                                                                                           \
-                    }                                                                                                                                 \
-                } else {                                                                                                                              \
-                    if (L.hit == S.code) L.color = add(L.color, medium_attenuate(T.M, L.o, L.d, L.closest, S.ac));                                    \
-                    const bool then_env = phase == kLitShadowAB;                                                                                      \
-                    if (!then_env && no_next_ray(next_d)) {                                                                                           \
-                        store_sample(P, w, L.color);                                                                                                  \
-                        phase = kLightIdle;                                                                                                           \
-                    } else {                                                                                                                          \
-                        begin_ray(L, L.o, then_env ? S.bdir : next_d, 0);                                                                             \
-                        phase = then_env ? kLitShadowB : kLightPath;                                                                                  \
-                    }                                                                                                                                 \
-                }                                                                                                                                     \
-                if (phase == kLightIdle) {                                                                                                            \
-                    L.node = kBlocked;                                                                                                                \
-                    L.sp = 0;                                                                                                                         \
-                }                                                                                                                                     \
-            }                                                                                                                                         \
-        } else {                                                                                                                                      \
-            const bool occlusion = phase == kLitShadowB;                                                                                              \
-            _Pragma("unroll")                                                                                                                         \
-            for (int u = 0; u < 4; ++u) {                                                                                                             \
-                if (!traversal_finished<true>(L, kBlocked)) lit_step(L, P, occlusion);                                                                \
-            }                                                                                                                                         \
-        }                                                                                                                                             \
-    }
-// kList = false: the work indices are [0, P.total_work) — a pass of rt_render_medium's.
-// kList = true (rt_render_volume_adaptive's rounds without a grid; DESIGN.md §29): the first *P.work_count entries of P.work_list, exactly as
-// lit_render_body takes them — the length read once per wave, wave-uniform and clamped to P.work_cap; an empty list leaves before the first
-// atomic; a fetched index `mine` stands for P.work_list[mine], in map_work and in store_sample alike.
-template <bool kLens, class Table, bool kList = false>
-__device__ __forceinline__ void medium_render_body(const KParams &P, const MediumLit<Table> &T, const LensCam &C) {
-    if constexpr (kList) {
-        uint32_t listed = (uint32_t)__builtin_amdgcn_readfirstlane((int32_t)*P.work_count);
-        if (listed > P.work_cap) listed = P.work_cap;          // (never more entries than the list has room for)
-        if (listed == 0u) return;
-        RTP_MEDIUM_RENDER_BODY(listed, P.work_list[mine])
-    } else {
-        RTP_MEDIUM_RENDER_BODY(P.total_work, mine)
-    }
-}
-#undef RTP_MEDIUM_RENDER_BODY
-
+// ---- the kernels of rt_render_medium and rt_trace_samples_medium: lit_render_body and lit_probe_body on a MediumLit<Table> ------------
 template <bool kLens, class Table>
 __global__ void __launch_bounds__(256) medium_probe_kernel(const KParams P, const MediumLit<Table> T, const LensCam C, uint32_t *nee_seed_out, uint32_t *env_seed_out,
                                                            uint32_t *med_seed_out, int32_t *events_out) {
-    medium_probe_body<kLens>(P, T, C, nee_seed_out, env_seed_out, med_seed_out, events_out);
+    lit_probe_body<kLens>(P, T, C, nee_seed_out, env_seed_out, med_seed_out, events_out);
 }
 // (waves per SIMD the compiler is held to, for all eight: DESIGN.md §25, profiles/r25/kernel_resource_usage.txt)
 constexpr int kMediumWaves = 3;
 template <bool kLens, class Table>
 __global__ void __launch_bounds__(kLightBlock, kMediumWaves) medium_render_kernel(const KParams P, const MediumLit<Table> T, const LensCam C) {
-    medium_render_body<kLens>(P, T, C);
+    lit_render_body<kLens>(P, T, C);
 }
 // the list variant: rt_render_volume_adaptive's rounds without a grid (DESIGN.md §29) — the same body on a list whose length lives on the device
 template <bool kLens, class Table>
 __global__ void __launch_bounds__(kLightBlock, kMediumWaves) medium_list_render_kernel(const KParams P, const MediumLit<Table> T, const LensCam C) {
-    medium_render_body<kLens, Table, true>(P, T, C);
+    lit_render_body<kLens, MediumLit<Table>, true>(P, T, C);
 }
+template <bool kLens, class Table> const void *lit_frame_kernel_of(const MediumLit<Table> &) { return (const void *)medium_render_kernel<kLens, Table>; }
+template <bool kLens, class Table> const void *lit_list_kernel_of(const MediumLit<Table> &) { return (const void *)medium_list_render_kernel<kLens, Table>; }
 
 }  // namespace rtk
