@@ -165,6 +165,10 @@ typedef struct rt_timing {
                                   flagged more than the bail share of its samples; rt_config.guard_keep = 1 prevents it) */
     uint32_t front_primitives; /* primitives the guarded walk tested at the start of every ray instead of keeping them in its tree
                                   (rt_config.guard_front_primitives); 0 when the exact walk ran */
+    uint32_t dark_kernel;     /* 1: the sphere-only kernel behind the primary-visibility pass ran in its build for scenes without emitters
+                                  (rt_config.dark_kernel): no radiance carried, each ray's sphere-test constants instead (2: a developer
+                                  build of it without those constants, RTP_DARK_CARRY=0); 0 with sphere_only, primary_visibility and
+                                  scene_in_lds all 1: the build that carries radiance ran (render_emit_kernel) */
 } rt_timing;
 /* *t = zeros with struct_bytes = sizeof(rt_timing). */
 void rt_timing_init(rt_timing *t);
@@ -255,6 +259,11 @@ typedef struct rt_config {
                                      the path's state at that point is left in a 17 MB table of the handle (a sample whose slot is taken, or
                                      that was flagged inside a shade step, is redone from its camera ray as before); -1: every flagged
                                      sample is redone from the camera.  The same frame bit for bit: up to the flagged ray both walks agree */
+    int32_t  dark_kernel;         /* 0 (default): a scene in which nothing emits — every material's emit is +0.0f bit for bit, no albedo component
+                                     beyond 1 in magnitude — that rt_render gives to the sphere-only kernel behind the primary-visibility pass is
+                                     traced by that kernel's variant without a radiance accumulator (the radiance of such a path is +0 until it
+                                     leaves the scene), which keeps each ray's |d|^2 and fp64 reciprocal for all its sphere tests in the freed
+                                     registers; the same frame bit for bit; -1: never */
 } rt_config;
 
 /* ---- entry points -------------------------------------------------------------------------- */

@@ -13,6 +13,7 @@
 // the same SAH build over leaf boxes inflated by a per-primitive margin, see Packed::Guard.
 #pragma once
 #include <cstdint>
+#include <cstring>
 #include <string>
 #include <vector>
 #include "../../include/rtp_amd.h"
@@ -127,6 +128,29 @@ uint16_t float_to_half_dir(float f, bool toward_minus_inf);
 // too (a camera far outside the scene).
 std::string pack_scene(const rt_scene_desc &desc, TreeMode mode, Packed &out, const PackOptions &opt = PackOptions(),
                        const float *camera_hint = nullptr);
+
+// ---- what a scene's materials allow the trace kernel to leave out (rt_scene_create; tests/cpu_native/test_scene_emits.cpp) ----
+// The scene emits if any `emit` component of any material has a bit pattern other than +0.0f: -0.0f, NaN, denormals and every
+// non-zero value count as emitting (only (+0) + beta * (+0) is +0 for every finite beta).  No materials: nothing emits.
+inline bool scene_emits(const rt_material *materials, int32_t num_materials) {
+    for (int32_t m = 0; m < num_materials; ++m)
+        for (int k = 0; k < 3; ++k) {
+            uint32_t bits;
+            std::memcpy(&bits, &materials[m].emit.e[k], 4);
+            if (bits != 0u) return true;
+        }
+    return false;
+}
+// … and a path's throughput, a product of albedos, stays finite however long the path: no albedo component beyond 1 in magnitude
+// (NaN fails).  What keeps beta * (+0) from being NaN in a scene without textures and absorbing glass.
+inline bool albedo_bounded(const rt_material *materials, int32_t num_materials) {
+    for (int32_t m = 0; m < num_materials; ++m)
+        for (int k = 0; k < 3; ++k) {
+            const float c = materials[m].albedo.e[k];
+            if (!(c >= -1.0f && c <= 1.0f)) return false;
+        }
+    return true;
+}
 
 // ---- pass sizing of rt_render (pure host arithmetic, checked over a grid by tests/cpu_native/test_accel.cpp) ----
 

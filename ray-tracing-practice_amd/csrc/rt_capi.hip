@@ -118,6 +118,7 @@ void config_defaults(rt_config &c) {
     c.guard_front_primitives = 0;
     c.reuse_view_lists = 0;
     c.resume_flagged = 0;
+    c.dark_kernel = 0;
 }
 
 // A caller compiled against an older, shorter rt_config: its fields, defaults for the rest.
@@ -295,6 +296,7 @@ struct rt_scene {
     uint64_t device_bytes = 0;      // total memory of the device (workspace default: a sixteenth of it)
     float build_ms = 0.0f;          // device BVH build time (RTP_BUILD=device), else 0
     bool absorbing_glass = false;   // some DIELECTRIC material has a non-zero absorption (Beer-Lambert code needed)
+    bool dark = false;              // no material emits and no albedo exceeds 1 (rt_accel.h, scene_emits / albedo_bounded): a path's radiance is +0 until it leaves the scene
     std::vector<hipEvent_t> aov_events;    // rt_render_aov, per timed pass: before the primary pass, before the resolve launch, after it
     // rt_render_adaptive (rt_adaptive.hip.inc): the moments of a caller who passes none (2 floats per local pixel), two lists of pixels
     // (2 x adapt_pixels words: one round reads the previous round's list while it writes its own), the work indices of a round
@@ -565,6 +567,7 @@ void rt_config_from_env(rt_config *user) {
     if (env_int("RTP_NO_TAPER", 0)) cfg->reserve_taper = 0;
     cfg->wide_nodes = env_int("RTP_WIDE", cfg->wide_nodes);
     if (env_int("RTP_NO_SIMPLE", 0)) cfg->sphere_only_kernel = -1;
+    if (env_int("RTP_NO_DARK", 0)) cfg->dark_kernel = -1;
     if (env_int("RTP_NO_OVERLAP", 0)) cfg->overlap_rework = -1;
     if (env_int("RTP_NO_PRIMARY", 0)) cfg->primary_visibility = -1;
     cfg->guard_bail_share = env_int("RTP_BAIL_SHARE", cfg->guard_bail_share);
@@ -659,6 +662,7 @@ rt_status rt_scene_create_ex(const rt_scene_desc *desc, const rt_config *user_cf
         const rt_material &mat = desc->materials[m];
         if (mat.type == RT_MAT_DIELECTRIC && !(mat.absorption.e[0] == 0.0f && mat.absorption.e[1] == 0.0f && mat.absorption.e[2] == 0.0f)) sc->absorbing_glass = true;
     }
+    sc->dark = !rtaccel::scene_emits(desc->materials, desc->num_materials) && rtaccel::albedo_bounded(desc->materials, desc->num_materials);
     if (pk.guard.ok) {
         sc->host_spheres.assign(desc->spheres, desc->spheres + desc->num_spheres);
         sc->host_planes.assign(desc->planes, desc->planes + desc->num_planes);
@@ -993,6 +997,7 @@ struct LaunchPlan {
     bool dyn = false;                       // guarded walk with distance-aware margins
     bool simple = false;                    // guarded walk, sphere-only build
     bool prim = false;                      // primary-visibility pass before the trace launch
+    bool dark = false;                      // the sphere-only octant walk behind the primary pass, in a scene without emitters: its build without a radiance accumulator
     bool overlap = false;                   // exact re-walk on the handle's second stream
     bool resume = false;                    // resume table for flagged samples
     uint32_t flag_chunk_words = 0;          // LDS words per wave for its chunk of the flagged-sample list (rt_kernel.hip.inc, flag_collect): 2, or 0
@@ -1157,6 +1162,10 @@ LaunchPlan plan_launch(const rt_scene *sc, const rt_camera_data *cam, const rtk:
     // with static margins, and the walk with distance-aware margins (through L1/L2) — and a camera inside the margins
     L.prim = pinhole && guarded && (L.dyn || fast.in_lds) && cfg.primary_visibility >= 0 && sc->nodes != nullptr && P.max_depth < rtk::kMaxPrimDepth &&
              camera_inside_margins(sc, cam);
+    // … and behind it, for the sphere-only octant walk of a scene in which nothing emits, the build that carries no radiance
+    // (rt_kernel.hip.inc, kDark; else render_emit_kernel.  rt_render, rt_render_tile and rt_render_samples: render_impl drops it for
+    // the call that keeps its kernel)
+    L.dark = L.prim && L.simple && fast.in_lds && !L.dyn && sc->dark && cfg.dark_kernel >= 0;
     // resume table: not for paths longer than the depth field
     L.resume = guarded && cfg.resume_flagged >= 0 && P.max_depth < rtk::kMaxPrimDepth;
     // vote thresholds: the octant walk's (its pair steps are cheaper, so a block of them is worth starting for fewer idle lanes
@@ -1229,8 +1238,9 @@ const void *trace_kernel(const LaunchPlan &L) {
     if (L.dyn && L.simple)          // sphere-only scenes beyond what LDS holds: step_pair_par at 64 registers, 8 waves per SIMD
         return L.prim ? (const void *)render_kernel<false, false, true, false, true, true> : (const void *)render_kernel<false, false, true, false, true>;
     if (L.dyn) return L.prim ? (const void *)render_kernel<false, false, true, false, false, true> : (const void *)render_kernel<false, false, true>;
-    if (L.fast.in_lds && L.simple)
-        return L.prim ? (const void *)render_kernel<true, false, false, false, true, true> : (const void *)render_kernel<true, false, false, false, true>;
+    if (L.fast.in_lds && L.simple && L.prim)        // behind the primary pass: the build for scenes without emitters, or the one that carries radiance
+        return L.dark ? (const void *)render_kernel<true, false, false, false, true, true> : (const void *)rtk::render_emit_kernel;
+    if (L.fast.in_lds && L.simple) return (const void *)render_kernel<true, false, false, false, true>;
     if (L.fast.in_lds) return L.prim ? (const void *)render_kernel<true, false, false, false, false, true> : (const void *)render_kernel<true, false>;
     return (const void *)render_kernel<false, false>;
 }
@@ -1418,6 +1428,7 @@ rt_timing plan_timing(const rt_scene *sc, const LaunchPlan &plan, int wgs, int p
     t.front_primitives = plan.guarded() ? (uint32_t)sc->guard.num_front : 0u;
     t.wide_nodes = plan.wide ? 1u : 0u;
     t.sphere_only = plan.sphere_only() ? 1u : 0u;
+    t.dark_kernel = plan.dark ? (RTP_DARK_CARRY != 0 ? 1u : 2u) : 0u;
     t.primary_visibility = plan.prim ? 1u : 0u;
     kernel_resources(trace, t.trace_vgprs, t.trace_scratch_bytes);
     return t;
@@ -1548,6 +1559,7 @@ rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *s
     // ---- 3. launch shapes
     LaunchPlan plan = plan_launch(sc, cam, P, guarded, lens == nullptr);
     guarded = plan.guarded();
+    if (moments != nullptr) plan.dark = false;        // (rt_render_adaptive's min_spp round keeps its kernel)
     // ---- 4. buffers.  Samples per pass (rt_accel.h, plan_passes): as many as the workspace budget admits (rt_config.workspace_bytes,
     // default a sixteenth of the device; 12 bytes per sample), at least 64 where the work-index bound allows, and never more than the
     // bound num_pixels * pass + 64 <= 2^30 of the kernel's 32-bit work index (div_magic, kFlagHole, kAbandonedCounter) —

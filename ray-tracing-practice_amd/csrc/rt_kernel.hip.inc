@@ -698,6 +698,17 @@ __device__ __forceinline__ void test_sphere_ray(Lane &L, float4 s, int32_t prim,
         L.hit = prim;
     }
 }
+// the constants of a ray that every sphere test needs: a = |d|^2, (double)a, 1 / (double)a — test_sphere's own expressions, so
+// test_sphere_ray<kGuard, false> with them gives test_sphere<kGuard>'s bits.  The primary pass makes them once per sample, the trace
+// kernel of a scene without emitters (the headline kernel, RTP_BODY_CARRY) once per armed ray: there the lane keeps them.
+struct RayConst { float a; double da, y; };
+__device__ __forceinline__ RayConst ray_const(const Lane &L) {
+    RayConst r;
+    r.a = lensq(L.d);
+    r.da = (double)r.a;
+    r.y = sphere_root_rcp(r.da);
+    return r;
+}
 
 // hit_plane + is_interior_* (include/plane.h:30-96), acceptance only.
 template <bool kGuard = false, class PlaneTab>
@@ -773,6 +784,14 @@ __device__ __forceinline__ void step_leaf_parked(Lane &L, SphereTab spheres, Pla
     else test_sphere<true>(L, spheres[idx], code);
     L.pend = 0;
     if (kPark) park_leaf<kSent>(L, stack);          // a lane that was stuck at a second leaf parks that one and walks on
+}
+// … of a sphere-only scene, with the ray's constants the lane carries (RTP_BODY_CARRY: arm_ray made them, ray_const)
+template <bool kSent, class SphereTab>
+__device__ __forceinline__ void step_leaf_parked_ray(Lane &L, SphereTab spheres, const uint32_t *stack, float ray_a, double ray_y) {
+    const int32_t code = -(L.pend + 1);
+    test_sphere_ray<true, false>(L, spheres[code >> 1], code, ray_a, (double)ray_a, ray_y);
+    L.pend = 0;
+    park_leaf<kSent>(L, stack);
 }
 
 // ---- threaded (reference-order) traversal --------------------------------------------------------
@@ -937,12 +956,16 @@ __device__ __forceinline__ f3 scatter_diffuse_dir(f3 in_sphere, f3 normal) {
 // two rows every hit needs — the third, absorption and index of refraction, is read from the global table by
 // the DIELECTRIC branch alone; the 16 bytes per material saved buy three more entries of traversal stack).
 // kSimple: the scene has no planes, no textures, no leaf-box table and no absorbing DIELECTRIC: those branches are compiled out.
-template <bool kGuard = false, int kMatStride = 3, bool kSimple = false, bool kPrim = false, bool kClamped = false, class SphereTab, class PlaneTab, class MatTab, class IdxTab>
+// kDark: every material's `emit` is +0 and no albedo component exceeds 1 in magnitude (rtaccel::scene_emits, albedo_bounded: the host
+// checked; a kSimple scene has no texture and no absorption to scale beta by), so beta — a product of albedos — stays finite and each
+// addition to the radiance below is (+0) + beta * (+0) = +0: they are compiled out and L.color is never touched.
+template <bool kGuard = false, int kMatStride = 3, bool kSimple = false, bool kPrim = false, bool kClamped = false, bool kDark = false, class SphereTab, class PlaneTab, class MatTab, class IdxTab>
 __device__ __forceinline__ bool shade(Lane &L, const KParams &P, SphereTab spheres, PlaneTab planes, MatTab materials,
                                       IdxTab sphere_mat, f3 &out_o, f3 &out_d) {
     if (kGuard && (L.depth & kFlagBit)) return false;     // the exact walk redoes this sample
     if (L.hit < 0) {
-        L.color = add(L.color, mul(L.beta, mk(P.bg[0], P.bg[1], P.bg[2])));
+        static_assert(!kDark || kPrim, "a kDark kernel retires a ray that left the scene in its shade step's own store round");
+        if (!kDark) L.color = add(L.color, mul(L.beta, mk(P.bg[0], P.bg[1], P.bg[2])));
         return false;
     }
     const int32_t code = L.hit;
@@ -1013,7 +1036,7 @@ __device__ __forceinline__ bool shade(Lane &L, const KParams &P, SphereTab spher
     const bool is_metal = type == RT_MAT_METAL;
     const bool is_glass = type == RT_MAT_DIELECTRIC;
     if (!(is_lamb || is_metal || is_glass)) {                        // DIFFUSE_LIGHT (:135-137)
-        L.color = add(L.color, mul(beta_in, mk(ME.x, ME.y, ME.z)));
+        if (!kDark) L.color = add(L.color, mul(beta_in, mk(ME.x, ME.y, ME.z)));
         return false;
     }
     // absorption and index of refraction live in global memory (kMatStride == 2): issue the read NOW, so that its
@@ -1027,7 +1050,7 @@ __device__ __forceinline__ bool shade(Lane &L, const KParams &P, SphereTab spher
     if (is_metal) metal_reflect = random_float(L.seed) < 0.8f;       // p_metal draw comes first (:82-83)
     f3 in_sphere = mk(0, 0, 0);
     if (is_lamb || is_metal) in_sphere = random_in_unit_sphere(L.seed);
-    L.color = add(L.color, mul(beta_in, mk(ME.x, ME.y, ME.z)));      // final_color += beta * emitted
+    if (!kDark) L.color = add(L.color, mul(beta_in, mk(ME.x, ME.y, ME.z)));      // final_color += beta * emitted
     f3 ud = mk(0, 0, 0);
     if (metal_reflect || is_glass) ud = unit(L.d);                   // unit_vector(r_in.direction())
     if (is_glass) {                                                  // :98-133
@@ -1564,20 +1587,59 @@ __device__ __forceinline__ bool resume_load(const KParams &P, uint32_t w, Lane &
 // kSimple: the sphere-only specialisation of the octant walk (above, kSimpleBlock).
 constexpr uint32_t kShortListLanes = 8;      // exact re-walk: up to this many paths per wave count as a short list (below)
 // The trace kernels' body is one text, rt_render_body.inc, included by each; RTP_CAMERA_START is how it starts a sample's path.
+//
+// The headline kernel, render_kernel<true, false, false, false, true, true> — the sphere-only octant walk fed by the primary pass — is
+// built for a scene in which nothing emits (kDark; rt_scene_create: no material with an `emit` bit pattern other than +0, no albedo
+// beyond 1).  There the radiance a path carries is +0 from its camera ray until the ray that leaves the scene, so the lane holds no
+// Lane::color: a retired sample is (+0) + beta * background or +0, and a flagged one leaves zeros in the resume table (the exact
+// re-walk, not specialised, reads them back as ever).  RTP_BODY_CARRY: the three registers hold the ray's own constants of the sphere
+// test instead (ray_const: |d|^2 and the fp64 reciprocal with its Newton steps, which test_sphere remakes for each of a ray's 2.9
+// tests) — made once where the ray is armed.  A scene of that shape WITH emitters, or rt_config.dark_kernel = -1, takes render_emit_kernel
+// below: the same instantiation without kDark, instruction for instruction what the headline kernel was before.  (The name of the
+// headline kernel stays with the kernel the headline scene runs: profiles, tools and tests know it by that name.)
+#ifndef RTP_DARK_CARRY
+#define RTP_DARK_CARRY 1        /* 0: kDark without the carried constants (the A/B of docs/LOG.md round 32) */
+#endif
 template <bool kLds, bool kThreaded, bool kDyn = false, bool kWide = false, bool kSimple = false, bool kPrim = false>
 __global__ void __launch_bounds__(kSimple ? kSimpleBlock : RTP_BLOCK, kSimple ? kSimpleWaves : RTP_MIN_WAVES) render_kernel(const KParams P) {
+    constexpr bool kDark = false;
+#define RTP_BODY_CARRY 0
 #define RTP_CAMERA_START(L_, P_, i_, j_, base_, s_, o_, d_, lds_) start_sample<kConsts>(L_, P_, i_, j_, base_, s_, o_, d_, lds_)
 #include "rt_render_body.inc"
 #undef RTP_CAMERA_START
+#undef RTP_BODY_CARRY
+}
+// (the headline kernel: an explicit specialisation, so that the lines of the body only it compiles — RTP_BODY_CARRY — are its own)
+template <>
+__global__ void __launch_bounds__(kSimpleBlock, kSimpleWaves) render_kernel<true, false, false, false, true, true>(const KParams P) {
+    constexpr bool kLds = true, kThreaded = false, kDyn = false, kWide = false, kSimple = true, kPrim = true;
+    constexpr bool kDark = true;
+#define RTP_BODY_CARRY RTP_DARK_CARRY
+#define RTP_CAMERA_START(L_, P_, i_, j_, base_, s_, o_, d_, lds_) start_sample<kConsts>(L_, P_, i_, j_, base_, s_, o_, d_, lds_)
+#include "rt_render_body.inc"
+#undef RTP_CAMERA_START
+#undef RTP_BODY_CARRY
+}
+__global__ void __launch_bounds__(kSimpleBlock, kSimpleWaves) render_emit_kernel(const KParams P) {
+    constexpr bool kLds = true, kThreaded = false, kDyn = false, kWide = false, kSimple = true, kPrim = true;
+    constexpr bool kDark = false;
+#define RTP_BODY_CARRY 0
+#define RTP_CAMERA_START(L_, P_, i_, j_, base_, s_, o_, d_, lds_) start_sample<kConsts>(L_, P_, i_, j_, base_, s_, o_, d_, lds_)
+#include "rt_render_body.inc"
+#undef RTP_CAMERA_START
+#undef RTP_BODY_CARRY
 }
 // Lens frames (rt_render_lens): the general builds of every walk, every sample started from its camera by lens_camera_ray.  The
 // camera pair rides in a kernel argument of its own (scalar loads into SGPRs); the pinhole kernels' argument stays what it was.
 template <bool kLds, bool kThreaded, bool kDyn = false, bool kWide = false>
 __global__ void __launch_bounds__(RTP_BLOCK, RTP_MIN_WAVES) render_lens_kernel(const KParams P, const LensCam C) {
     constexpr bool kSimple = false, kPrim = false;        // (no sphere-only build, no candidate lists)
+    constexpr bool kDark = false;
+#define RTP_BODY_CARRY 0
 #define RTP_CAMERA_START(L_, P_, i_, j_, base_, s_, o_, d_, lds_) lens_camera_ray(L_, C, i_, j_, sample_seed1(base_, s_), o_, d_)
 #include "rt_render_body.inc"
 #undef RTP_CAMERA_START
+#undef RTP_BODY_CARRY
 }
 
 // ---- probe kernel: one lane traces one (i, j, s) sample with the exact walk's step functions -------

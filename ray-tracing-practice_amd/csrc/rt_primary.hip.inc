@@ -129,15 +129,7 @@ typedef __attribute__((address_space(4))) const uint32_t k_u32;         // const
 typedef float kf4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(4))) const kf4 k_f4;
 
-// the constants of a ray that every sphere test needs: a = |d|^2, (double)a, 1 / (double)a
-struct RayConst { float a; double da, y; };
-__device__ __forceinline__ RayConst ray_const(const Lane &L) {
-    RayConst r;
-    r.a = lensq(L.d);
-    r.da = (double)r.a;
-    r.y = sphere_root_rcp(r.da);
-    return r;
-}
+// (RayConst / ray_const, the constants of a ray that every sphere test needs: rt_kernel.hip.inc, beside test_sphere_ray)
 
 // candidate C of a wave-uniform list: the list is read four words at a time into scalar registers (word 0 is the count, so
 // a group boundary falls before candidates 3, 7 and 11), the sphere record with a scalar load too

@@ -2,8 +2,12 @@
 //
 // One text for both, so that the pinhole kernels compile to exactly the code they did before lens frames existed: each kernel defines
 // RTP_CAMERA_START, how a sample's camera ray is made from (lane, params, i, j, base seed, sample, out origin, out direction, LDS
-// constants), before including this file.
+// constants), before including this file, and RTP_BODY_CARRY (0, or 1: the lane keeps its ray's sphere-test constants, which only the
+// headline kernel's build for scenes without emitters does: kDark) — text the other kernels do not compile at all, since even two
+// unused variables that a lambda captures moved registers about in their listings.
     static_assert(!kPrim || !kThreaded, "primary visibility feeds the guarded walk");
+    static_assert(!kDark || (kLds && !kThreaded && !kDyn && !kWide && kSimple && kPrim), "the kernel of scenes without emitters is a variant of the sphere-only octant walk fed by the primary pass");
+    static_assert(!RTP_BODY_CARRY || kDark, "the ray's constants take the registers of Lane::color");
     constexpr int kBlock = kSimple ? kSimpleBlock : rtk::kBlock;      // (shadows the namespace constant inside this kernel)
     static_assert(!kWide || kDyn, "the 4-wide nodes are walked only with distance-aware margins (step_wide_par)");
     static_assert(!kSimple || (kLds && !kDyn && !kWide) || (!kLds && !kThreaded && kDyn && !kWide),
@@ -127,6 +131,11 @@
     Lane L;
     L.node = end_node; L.hit = -1; L.sp = 0; L.pend = 0; L.depth = 0; L.closest = 0; L.seed = 0; L.e = 0;
     L.o = L.d = L.inv = L.beta = L.color = mk(0, 0, 0);
+#if RTP_BODY_CARRY
+    // the constants of the lane's ray that every sphere test needs — |d|^2 and its fp64 reciprocal (ray_const) — made by arm_ray
+    float ray_a = 0.0f;
+    double ray_y = 0.0;
+#endif
     constexpr bool kDefer = !kThreaded;        // parked primitive tests (guarded walk)
     // a lane with nothing left to walk goes to the shade step with its parked test still open: the step tests it first
     auto finished = [&]() { return kDefer ? (L.node == kDone) : traversal_finished<kThreaded>(L, end_node); };
@@ -296,6 +305,9 @@
         if (kSent) L.sp = kLevelBytes;              // above the sentinel
         if (kDefer && L.node < 0 && L.node != kDone) { L.pend = L.node; L.node = kDone; }      // a tree of one primitive
         if (kGuard && !kDyn) guard_origin<kConsts>(L, P, consts_lds);
+#if RTP_BODY_CARRY      // |d|^2 and its fp64 reciprocal, once for every sphere test of this ray: the front primitives' below, the parked ones'
+        { const RayConst rc = ray_const(L); ray_a = rc.a; ray_y = rc.y; }
+#endif
         // Front primitives (rt_accel.h): the few primitives that span the scene are not in the tree; every ray tests them here,
         // where all armed lanes of the wave do the same thing on the same record, and walks with their hit as its `closest`.
         // Which primitives are tested first makes no difference to the result: ties are flagged (test_sphere / test_plane).
@@ -306,7 +318,11 @@
                                               : (f < P.num_front ? (uint32_t)P.front_code[f] : kNoFront);
                 if (code == kNoFront) break;
                 if (!kSimple && (code & 1u)) test_plane<true>(L, planes, (int32_t)(code >> 1), (int32_t)code);
+#if RTP_BODY_CARRY
+                else test_sphere_ray<true, false>(L, spheres[code >> 1], (int32_t)code, ray_a, (double)ray_a, ray_y);
+#else
                 else test_sphere<true>(L, spheres[code >> 1], (int32_t)code);
+#endif
             }
         }
         if (kDynPar) {
@@ -358,7 +374,11 @@
             // A lane that misses therefore goes from the end of one path to the second ray of the next path within one
             // step, and the walk only ever sees rays that left a surface.
             if (alive && finished()) {
+#if RTP_BODY_CARRY
+                if (L.pend != 0) step_leaf_parked_ray<kSent>(L, spheres, l_stack, ray_a, ray_y);
+#else
                 if (kDefer && L.pend != 0) step_leaf_parked<kSent, kSimple>(L, spheres, planes, l_stack);
+#endif
                 auto over = [&]() { return alive && L.node == kDone && (!path_open || (L.hit < 0 && !(L.depth & kArmBit)) || (L.depth & (kFlagBit | kEndBit)) != 0); };
                 bool go = over();
                 for (int it = 0;; ++it) {
@@ -371,6 +391,11 @@
                             if (L.hit < 0 && !(L.depth & (kFlagBit | kEndBit)))      // src/camera.cu:227-229: the ray left the scene
                                 L.color = add(L.color, mul(L.beta, mk(P.bg[0], P.bg[1], P.bg[2])));
                             retire_sample();
+                            // kDark: shade() adds nothing to the radiance, so it is +0 from the camera ray to the sum above — the
+                            // same sum, from a constant: a product of -0 still stores as +0 — and with the sample stored it is +0
+                            // again, for a lane that finds the pass dry as well: L.color is +0 wherever the loop comes round,
+                            // which costs no register
+                            if (kDark) L.color = mk(0.0f, 0.0f, 0.0f);
                         }
                         f3 ray_o = mk(0, 0, 0), ray_d = mk(0, 0, 0);
                         float prim_t = 0.0f;
@@ -399,7 +424,7 @@
                         bool cont = false;
                         if (ready) {
                             f3 unused_o, unused_d;          // (kPrim: shade() leaves the scattered ray in L.o / L.d)
-                            cont = shade<kGuard, (kLds && !kSimple) ? RTP_LDS_MAT_ROWS : 3, kSimple, true, kWidePar>(L, P, spheres, planes, materials, sphere_mat, unused_o, unused_d);
+                            cont = shade<kGuard, (kLds && !kSimple) ? RTP_LDS_MAT_ROWS : 3, kSimple, true, kWidePar, kDark>(L, P, spheres, planes, materials, sphere_mat, unused_o, unused_d);
                             if (!cont) L.depth |= kEndBit;
                         }
                         if (arm_walk) L.depth &= ~kArmBit;
@@ -498,7 +523,11 @@
                             if (park_leaf<kSent>(L, l_stack)) L.e = er;
                         }
                     } else
+#if RTP_BODY_CARRY
+                    if (alive && L.pend != 0) step_leaf_parked_ray<kSent>(L, spheres, l_stack, ray_a, ray_y);
+#else
                     if (alive && L.pend != 0) step_leaf_parked<kSent, kSimple>(L, spheres, planes, l_stack);
+#endif
                 } else {
                     RTP_COUNT(1, is_leaf);
                     if (is_leaf) {

@@ -66,7 +66,8 @@ class Timing(C.Structure):
                 ("guard_unproven", C.c_uint32), ("kernel", C.c_uint32), ("guard_dynamic", C.c_uint32), ("wide_nodes", C.c_uint32),
                 ("sphere_only", C.c_uint32), ("primary_visibility", C.c_uint32), ("primary_ms", C.c_float),
                 ("trace_vgprs", C.c_uint32), ("trace_scratch_bytes", C.c_uint32), ("abandoned_passes", C.c_uint32),
-                ("traced_samples", C.c_uint64), ("guard_paused", C.c_uint32), ("front_primitives", C.c_uint32)]
+                ("traced_samples", C.c_uint64), ("guard_paused", C.c_uint32), ("front_primitives", C.c_uint32),
+                ("dark_kernel", C.c_uint32)]
 
     def __init__(self, *args, **kw):
         super().__init__(*args, **kw)
@@ -481,7 +482,8 @@ class Config(C.Structure):
                 ("reserve_chunk", C.c_int32), ("reserve_taper", C.c_int32), ("wavefront_paths", C.c_int32),
                 ("wavefront_exchange", C.c_int32), ("wide_nodes", C.c_int32), ("guard_dynamic_margins", C.c_int32),
                 ("sphere_only_kernel", C.c_int32), ("overlap_rework", C.c_int32), ("primary_visibility", C.c_int32),
-                ("guard_bail_share", C.c_int32), ("guard_front_primitives", C.c_int32), ("reuse_view_lists", C.c_int32), ("resume_flagged", C.c_int32)]
+                ("guard_bail_share", C.c_int32), ("guard_front_primitives", C.c_int32), ("reuse_view_lists", C.c_int32), ("resume_flagged", C.c_int32),
+                ("dark_kernel", C.c_int32)]
 
 
 def new_config():
@@ -1823,6 +1825,12 @@ class DeviceScene:
         """Name (as rocprofv3 prints it) of the dominant kernel of the most recent rt_render."""
         t = self.last_timing()
         lds = "true" if t.scene_in_lds else "false"
+        # the sphere-only octant kernel behind the primary pass: render_kernel<true, false, false, false, true, true> is its build for
+        # scenes without emitters (rt_timing.dark_kernel); with emitters, or rt_config.dark_kernel = -1, render_emit_kernel ran
+        # (an older library loaded through RTP_AMD_LIB for an A/B run writes a shorter rt_timing and has the one kernel of that name)
+        knows_dark = t.struct_bytes >= Timing.dark_kernel.offset + 4
+        if knows_dark and t.guarded and t.scene_in_lds and t.sphere_only and t.primary_visibility and not t.guard_dynamic and not t.dark_kernel:
+            return "rtk::render_emit_kernel(rtk::KParams)"
         return (f"void rtk::render_kernel<{lds}, {'false' if t.guarded else 'true'}, {'true' if t.guard_dynamic else 'false'}, "
                 f"{'true' if t.wide_nodes else 'false'}, {'true' if t.sphere_only else 'false'}, "
                 f"{'true' if t.primary_visibility else 'false'}>(rtk::KParams)")

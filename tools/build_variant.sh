@@ -4,7 +4,10 @@
 # → ray-tracing-practice_amd/variants/librtp_amd_NAME.so, used through RTP_AMD_LIB.
 # The flags are the product's (`make print-render-flags`); a later flag on the line overrides one of them, so
 #   tools/build_variant.sh slp -fslp-vectorize
-# is the build WITH the SLP vectoriser for an A/B against the shipped flag set (docs/LOG.md round 24).  The variant is a developer
+# is the build WITH the SLP vectoriser for an A/B against the shipped flag set (docs/LOG.md round 24), and
+#   DEV= tools/build_variant.sh nocarry -DRTP_DARK_CARRY=0
+# the headline kernel without a radiance accumulator but also without the carried ray constants (round 32's A/B of the two steps;
+# rt_timing.dark_kernel reports 2 for it).  The variant is a developer
 # build without the tripwire (rt_debug_* entry points for RTP_STATS and the like); `DEV= tools/build_variant.sh NAME …` builds it
 # exactly as the product's rt_capi.o is built.
 set -e

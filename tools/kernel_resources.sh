@@ -54,7 +54,7 @@ report() {
 }
 {
   echo "# hipcc $RENDERFLAGS -Rpass-analysis=kernel-resource-usage --cuda-device-only -S csrc/rt_capi.hip   ($(/opt/rocm/bin/hipcc --version | head -1))"
-  echo "# render_kernel<kLds, kThreaded, kDyn, kWide, kSimple, kPrim>: <true,false,false,false,true,true> = the headline trace kernel (sphere-only build fed by the primary-visibility pass), <false,false,true,true,false,true> = BASELINE configs[4] (distance-aware margins in parametric form on 4-wide nodes, records through L1/L2), <true,false,false,false,false,*> = the general octant kernel, <*,true,…> = the exact walks"
+  echo "# render_kernel<kLds, kThreaded, kDyn, kWide, kSimple, kPrim>: <true,false,false,false,true,true> = the headline trace kernel (sphere-only build fed by the primary-visibility pass, for scenes without emitters: no radiance accumulator, the ray's sphere-test constants carried; -DRTP_DARK_CARRY=0 as an extra flag lists it without them), render_emit_kernel = the same walk carrying radiance (scenes with emitters, rt_config.dark_kernel = -1: the headline kernel's listing up to round 29), <false,false,true,true,false,true> = BASELINE configs[4] (distance-aware margins in parametric form on 4-wide nodes, records through L1/L2), <true,false,false,false,false,*> = the general octant kernel, <*,true,…> = the exact walks"
   echo "# Instructions: static counts of the kernel's listing (not executed counts): VALU = v_* without v_nop; packed-fp32 = v_pk_mul/add/fma_f32; v_mov = v_mov_* + v_pk_mov_* (inside VALU too); lane-moves = readlane/readfirstlane/writelane/permlane/DPP/ds_(b)permute/ds_swizzle; SALU = s_* without s_nop, s_waitcnt, memory loads, branches, barriers (those follow as \"other s_*\"); s_nop = hazard padding"
   report $TMP/rt_capi.s $TMP/rt_capi_ru.txt
   echo "# hipcc $FLAGS -Rpass-analysis=kernel-resource-usage --cuda-device-only -S csrc/rt_denoise.hip   (the denoiser's image-space kernels, rt_denoise)"
