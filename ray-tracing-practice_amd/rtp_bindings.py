@@ -58,7 +58,16 @@ class Shard(C.Structure):
     _fields_ = [("band_rows", C.c_int32), ("num_parts", C.c_int32), ("part", C.c_int32)]
 
 
-class Timing(C.Structure):
+class _Sized(C.Structure):
+    """A structure of the caller's size: struct_bytes is set on construction, to the size of the object's own type (a subclass that
+    appends fields says its own)."""
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self.struct_bytes = C.sizeof(type(self))
+
+
+class Timing(_Sized):
     """rt_timing (include/rtp_amd.h): an out-structure of the caller's size — struct_bytes is set on construction."""
     _fields_ = [("struct_bytes", C.c_uint32), ("kernel_ms", C.c_float), ("num_workgroups", C.c_uint32), ("workgroup_size", C.c_uint32),
                 ("lds_bytes", C.c_uint32), ("scene_in_lds", C.c_uint32), ("trace_launches", C.c_uint32),
@@ -69,19 +78,11 @@ class Timing(C.Structure):
                 ("traced_samples", C.c_uint64), ("guard_paused", C.c_uint32), ("front_primitives", C.c_uint32),
                 ("dark_kernel", C.c_uint32)]
 
-    def __init__(self, *args, **kw):
-        super().__init__(*args, **kw)
-        self.struct_bytes = C.sizeof(Timing)
 
-
-class AovBuffers(C.Structure):
+class AovBuffers(_Sized):
     """rt_aov_buffers (include/rtp_amd.h): DEVICE addresses of the first-hit AOV sums, each may be NULL."""
     _fields_ = [("struct_bytes", C.c_uint32), ("reserved", C.c_uint32), ("albedo_sum", C.c_void_p), ("normal_sum", C.c_void_p),
                 ("depth_sum", C.c_void_p), ("hit_count", C.c_void_p), ("first_prim", C.c_void_p)]
-
-    def __init__(self, *args, **kw):
-        super().__init__(*args, **kw)
-        self.struct_bytes = C.sizeof(AovBuffers)
 
 
 # rt_aov_buffers field of each AOV, its numpy type and its values per pixel (render_aov_to_host)
@@ -89,99 +90,103 @@ AOV_CHANNELS = (("albedo", "albedo_sum", np.float32, 3), ("normal", "normal_sum"
                 ("hits", "hit_count", np.uint32, 1), ("prim", "first_prim", np.int32, 1))
 
 
-class DenoiseParams(C.Structure):
+def _fill(p, name, fields, given, unknown=None, setters={}):
+    """Sets the `given` fields of p, the mirror of the C struct `name`: one outside `fields` raises unknown(field) (default: an RtError
+    that names the struct); setters[field](p, value) stands in for plain assignment."""
+    for k, v in given.items():
+        if k not in fields:
+            raise unknown(k) if unknown else RtError(f"{name} has no field {k}")
+        if k in setters:
+            setters[k](p, v)
+        else:
+            setattr(p, k, v)
+    return p
+
+
+def _params(kind, name, fields, given, **how):
+    """kind() with the library's defaults (the call <name>_init), then the `given` fields as _fill sets them."""
+    p = kind()
+    getattr(amd_lib(), name + "_init")(C.byref(p))
+    return _fill(p, name, fields, given, **how)
+
+
+def _struct(value, kind, make):
+    """An optional params argument of a call: None → NULL (the call's defaults); a `kind` as it is; a dict → make(**dict)."""
+    return None if value is None else C.byref(value if isinstance(value, kind) else make(**value))
+
+
+def _ref(struct):
+    """An optional structure argument of a call (shard, cam_close): None → NULL."""
+    return C.byref(struct) if struct else None
+
+
+def _stream_sync(stream, sync):
+    """The (hip_stream, sync) arguments of a render call: stream None = the default stream."""
+    return C.c_void_p(stream or 0), 1 if sync else 0
+
+
+def _probe(ijs, *columns):
+    """The preamble of a probe call: ijs as contiguous (n, 3) int32, n, and one empty output array per column (dtype, trailing shape)."""
+    ijs = np.ascontiguousarray(ijs, dtype=np.int32).reshape(-1, 3)
+    n = ijs.shape[0]
+    return ijs, n, tuple(np.empty((n, *shape), dtype=dtype) for dtype, shape in columns)
+
+
+_RGB, _COUNT, _SEED = (np.float32, (3,)), (np.int32, ()), (np.uint32, ())          # the columns probes return
+
+
+class DenoiseParams(_Sized):
     """rt_denoise_params (include/rtp_amd.h): an IN structure of the caller's size — struct_bytes is set on construction; the
     other fields are 0 until rt_denoise_params_init (denoise_params()) fills the defaults."""
     _fields_ = [("struct_bytes", C.c_uint32), ("iterations", C.c_int32), ("sigma_depth", C.c_float), ("sigma_luminance", C.c_float),
                 ("normal_squarings", C.c_int32)]
 
-    def __init__(self, *args, **kw):
-        super().__init__(*args, **kw)
-        self.struct_bytes = C.sizeof(DenoiseParams)
 
-
-class AdaptiveParams(C.Structure):
+class AdaptiveParams(_Sized):
     """rt_adaptive_params (include/rtp_amd.h): an IN structure of the caller's size — struct_bytes is set on construction; the other
     fields are 0 until rt_adaptive_params_init (adaptive_params()) fills the defaults."""
     _fields_ = [("struct_bytes", C.c_uint32), ("min_spp", C.c_int32), ("batch_spp", C.c_int32), ("max_spp", C.c_int32), ("threshold", C.c_float)]
 
-    def __init__(self, *args, **kw):
-        super().__init__(*args, **kw)
-        self.struct_bytes = C.sizeof(AdaptiveParams)
-
 
 def adaptive_params(**params):
     """rt_adaptive_params with the library's defaults, then the given fields (min_spp, batch_spp, max_spp, threshold)."""
-    p = AdaptiveParams()
-    amd_lib().rt_adaptive_params_init(C.byref(p))
-    for k, v in params.items():
-        if k not in dict(AdaptiveParams._fields_):
-            raise RtError(f"rt_adaptive_params has no field {k}")
-        setattr(p, k, v)
-    return p
+    return _params(AdaptiveParams, "rt_adaptive_params", dict(AdaptiveParams._fields_), params)
 
 
-class StopParams(C.Structure):
+class StopParams(_Sized):
     """rt_stop_params (include/rtp_amd.h): an IN structure of the caller's size — struct_bytes is set on construction."""
     _fields_ = [("struct_bytes", C.c_uint32), ("rule", C.c_int32), ("reserved", C.c_int32 * 2)]
-
-    def __init__(self, *args, **kw):
-        super().__init__(*args, **kw)
-        self.struct_bytes = C.sizeof(StopParams)
 
 
 def stop_params(**params):
     """rt_stop_params with the library's defaults, then the given fields (rule)."""
-    p = StopParams()
-    amd_lib().rt_stop_params_init(C.byref(p))
-    for k, v in params.items():
-        if k not in ("rule",):
-            raise RtError(f"rt_stop_params has no field {k}")
-        setattr(p, k, v)
-    return p
+    return _params(StopParams, "rt_stop_params", ("rule",), params)
 
 
-class LensParams(C.Structure):
+class LensParams(_Sized):
     """rt_lens_params (include/rtp_amd.h): an IN structure of the caller's size — struct_bytes is set on construction; the other
     fields are 0 until rt_lens_params_init (lens_params()) fills the defaults."""
     _fields_ = [("struct_bytes", C.c_uint32), ("lens_radius", C.c_float), ("focus_distance", C.c_float)]
 
-    def __init__(self, *args, **kw):
-        super().__init__(*args, **kw)
-        self.struct_bytes = C.sizeof(LensParams)
-
 
 def lens_params(**params):
     """rt_lens_params with the library's defaults, then the given fields (lens_radius, focus_distance)."""
-    p = LensParams()
-    amd_lib().rt_lens_params_init(C.byref(p))
-    for k, v in params.items():
-        if k not in dict(LensParams._fields_):
-            raise RtError(f"rt_lens_params has no field {k}")
-        setattr(p, k, v)
-    return p
+    return _params(LensParams, "rt_lens_params", dict(LensParams._fields_), params)
 
 
 def _lens_struct(lens):
-    """None → NULL (the defaults); a LensParams as it is; a dict → lens_params(**dict)."""
-    if lens is None:
-        return None
-    return C.byref(lens if isinstance(lens, LensParams) else lens_params(**lens))
+    return _struct(lens, LensParams, lens_params)
 
 
 def lens_camera_rays(cam_open, cam_close, lens, ijs):
     """rt_lens_camera_rays: ijs (n, 3) int32 (i, j, s) → (origins (n, 3) float32, directions (n, 3) float32, final seeds (n,) uint32)."""
-    ijs = np.ascontiguousarray(ijs, dtype=np.int32).reshape(-1, 3)
-    n = ijs.shape[0]
-    org = np.empty((n, 3), dtype=np.float32)
-    dirs = np.empty((n, 3), dtype=np.float32)
-    seeds = np.empty(n, dtype=np.uint32)
-    _check(amd_lib().rt_lens_camera_rays(C.byref(cam_open), C.byref(cam_close) if cam_close is not None else None, _lens_struct(lens), n,
-                                         ijs.ctypes.data, org.ctypes.data, dirs.ctypes.data, seeds.ctypes.data), "rt_lens_camera_rays")
-    return org, dirs, seeds
+    ijs, n, out = _probe(ijs, _RGB, _RGB, _SEED)
+    _check(amd_lib().rt_lens_camera_rays(C.byref(cam_open), _ref(cam_close), _lens_struct(lens), n, ijs.ctypes.data,
+                                         *(a.ctypes.data for a in out)), "rt_lens_camera_rays")
+    return out
 
 
-class NeeParams(C.Structure):
+class NeeParams(_Sized):
     """rt_nee_params (include/rtp_amd.h): an IN structure of the caller's size — struct_bytes is set on construction; the other
     fields are 0 until rt_nee_params_init (nee_params()) fills the defaults."""
     class _Tail(C.Union):
@@ -195,10 +200,6 @@ class NeeParams(C.Structure):
     _fields_ = [("struct_bytes", C.c_uint32), ("mis", C.c_int32), ("_tail", _Tail)]
     FIELDS = ("struct_bytes", "mis", "sample_planes", "select")          # what nee_params() sets
 
-    def __init__(self, *args, **kw):
-        super().__init__(*args, **kw)
-        self.struct_bytes = C.sizeof(type(self))
-
 
 class NeeParamsGlossy(NeeParams):
     """rt_nee_params as the library compiles it today: NeeParams — the 16-byte struct of a caller from before the glossy switch, which the
@@ -210,28 +211,19 @@ class NeeParamsGlossy(NeeParams):
 def nee_params(**params):
     """rt_nee_params with the library's defaults (mis = 1, sample_planes = 0, select = 0, glossy = 0), then the given fields.  Without
     `glossy` the result is the 16-byte NeeParams (an older caller's struct: glossy = 0); with it, the 20-byte NeeParamsGlossy."""
-    full = NeeParamsGlossy()
-    amd_lib().rt_nee_params_init(C.byref(full))
-    p = full
-    if "glossy" not in params:
-        p = NeeParams()
-        C.memmove(C.byref(p), C.byref(full), C.sizeof(NeeParams))
-        p.struct_bytes = C.sizeof(NeeParams)
-    for k, v in params.items():
-        if k not in type(p).FIELDS:
-            raise RtError(f"rt_nee_params has no field {k}")
-        setattr(p, k, v)
-    return p
+    if "glossy" in params:
+        return _params(NeeParamsGlossy, "rt_nee_params", NeeParamsGlossy.FIELDS, params)
+    p = NeeParams()          # (the library's init writes its own 20 bytes: the defaults come through the full struct)
+    C.memmove(C.byref(p), C.byref(_params(NeeParamsGlossy, "rt_nee_params", (), {})), C.sizeof(NeeParams))
+    p.struct_bytes = C.sizeof(NeeParams)
+    return _fill(p, "rt_nee_params", NeeParams.FIELDS, params)
 
 
 def _nee_struct(params):
-    """None → NULL (the defaults); a NeeParams as it is; a dict → nee_params(**dict)."""
-    if params is None:
-        return None
-    return C.byref(params if isinstance(params, NeeParams) else nee_params(**params))
+    return _struct(params, NeeParams, nee_params)
 
 
-class EnvParams(C.Structure):
+class EnvParams(_Sized):
     """rt_env_params (include/rtp_amd.h): an IN structure of the caller's size — struct_bytes is set on construction; the other
     fields are 0 until rt_env_params_init (env_params()) fills the defaults."""
     class _Tail(C.Union):
@@ -246,10 +238,6 @@ class EnvParams(C.Structure):
                 ("camera_visible", C.c_int32), ("_tail", _Tail)]
     FIELDS = ("struct_bytes", "mode", "scale", "rot", "camera_visible", "glossy")          # what env_params() sets
 
-    def __init__(self, *args, **kw):
-        super().__init__(*args, **kw)
-        self.struct_bytes = C.sizeof(EnvParams)
-
 
 ENV_PATH, ENV_MIS, ENV_LIGHT = 0, 1, 2
 
@@ -257,49 +245,36 @@ ENV_PATH, ENV_MIS, ENV_LIGHT = 0, 1, 2
 def env_params(**params):
     """rt_env_params with the library's defaults (mode = 1, scale = 1, rot = identity, camera_visible = 1, glossy = 0), then the given fields
     (rot: nine numbers, the rows of the world → environment rotation)."""
-    p = EnvParams()
-    amd_lib().rt_env_params_init(C.byref(p))
-    for k, v in params.items():
-        if k not in EnvParams.FIELDS:
-            raise RtError(f"rt_env_params has no field {k}")
-        if k == "rot":
-            v = np.asarray(v, dtype=np.float32).ravel()
-            if v.size != 9:
-                raise RtError("rt_env_params.rot takes nine numbers")
-            for i in range(9):
-                p.rot[i] = float(v[i])
-        else:
-            setattr(p, k, v)
-    return p
+    return _params(EnvParams, "rt_env_params", EnvParams.FIELDS, params, setters={"rot": _set_env_rot})
+
+
+def _set_env_rot(p, v):
+    v = np.asarray(v, dtype=np.float32).ravel()
+    if v.size != 9:
+        raise RtError("rt_env_params.rot takes nine numbers")
+    for i in range(9):
+        p.rot[i] = float(v[i])
 
 
 env_params_of = env_params      # (lit_params has an argument of that name)
 
 
 def _env_struct(params):
-    """None → NULL (the defaults); an EnvParams as it is; a dict → env_params(**dict)."""
-    if params is None:
-        return None
-    return C.byref(params if isinstance(params, EnvParams) else env_params(**params))
+    return _struct(params, EnvParams, env_params)
 
 
-class LitParams(C.Structure):
+class LitParams(_Sized):
     """rt_lit_params (include/rtp_amd.h): an IN structure of the caller's size — struct_bytes is set on construction; the other fields
     are 0 until rt_lit_params_init (lit_params()) fills the defaults.  The pointers are borrowed: lit_params() keeps what it points
     into alive in `_keep`."""
     _fields_ = [("struct_bytes", C.c_uint32), ("sample_emitters", C.c_int32), ("cam_close", C.POINTER(CameraData)),
                 ("lens", C.POINTER(LensParams)), ("nee", C.POINTER(NeeParams)), ("env", C.c_void_p), ("env_params", C.POINTER(EnvParams))]
 
-    def __init__(self, *args, **kw):
-        super().__init__(*args, **kw)
-        self.struct_bytes = C.sizeof(LitParams)
-
 
 def lit_params(cam_close=None, lens=None, emitters=True, nee=None, env=None, env_params=None):
     """rt_lit_params with the library's defaults, then: cam_close a CameraData (None: no motion); lens, nee, env_params None (the
     defaults), the params structure or a dict of its fields; emitters False: no light samples of the emitter table; env an Env."""
-    p = LitParams()
-    amd_lib().rt_lit_params_init(C.byref(p))
+    p = _params(LitParams, "rt_lit_params", (), {})
     p.sample_emitters = int(emitters) if not isinstance(emitters, bool) else (1 if emitters else 0)
     keep = []
     if cam_close is not None:
@@ -317,15 +292,11 @@ def lit_params(cam_close=None, lens=None, emitters=True, nee=None, env=None, env
     return p
 
 
-class MediumParams(C.Structure):
+class MediumParams(_Sized):
     """rt_medium_params (include/rtp_amd.h, "participating medium"): an IN structure of the caller's size — struct_bytes is set on
     construction; the other fields are 0 until rt_medium_params_init (medium_params()) fills the defaults."""
     _fields_ = [("struct_bytes", C.c_uint32), ("region", C.c_int32), ("sigma_t", C.c_float), ("albedo", C.c_float * 3), ("g", C.c_float),
                 ("a", C.c_float * 3), ("b", C.c_float * 3)]
-
-    def __init__(self, *args, **kw):
-        super().__init__(*args, **kw)
-        self.struct_bytes = C.sizeof(MediumParams)
 
 
 def medium_params(sigma_t=0.0, albedo=1.0, g=0.0, ball=None, box=None):
@@ -333,8 +304,7 @@ def medium_params(sigma_t=0.0, albedo=1.0, g=0.0, ball=None, box=None):
     box=(x0, y0, z0, x1, y1, z1), neither: all space.  Nothing is checked here: the library refuses what it does not take."""
     if ball is not None and box is not None:
         raise RtError("rt_medium_params takes one region: ball or box")
-    p = MediumParams()
-    amd_lib().rt_medium_params_init(C.byref(p))
+    p = _params(MediumParams, "rt_medium_params", (), {})
     p.sigma_t = float(sigma_t)
     alb = np.broadcast_to(np.asarray(albedo, dtype=np.float32), (3,))
     for k in range(3):
@@ -360,10 +330,7 @@ def medium_params(sigma_t=0.0, albedo=1.0, g=0.0, ball=None, box=None):
 
 
 def _medium_struct(medium):
-    """None → NULL (no medium); a MediumParams as it is; a dict → medium_params(**dict)."""
-    if medium is None:
-        return None
-    return C.byref(medium if isinstance(medium, MediumParams) else medium_params(**medium))
+    return _struct(medium, MediumParams, medium_params)
 
 
 class Env:
@@ -507,33 +474,138 @@ class ConfigInfo(C.Structure):
 assert C.sizeof(Sphere) == 32 and C.sizeof(Plane) == 80 and C.sizeof(Material) == 64
 assert C.sizeof(BvhNode) == 36 and C.sizeof(CameraData) == 76
 
+# The C ABI as ctypes has to be told it: function → (restype — None: void —, argtypes).  A call without a row still "works" (ctypes
+# passes a Python int as a 32-bit C int and cuts a device address short), so tests/test_bindings_abi.py holds AMD_ABI against
+# include/rtp_amd.h, prototype by prototype.  A new call of the library is one row here and one short method below.
+_P, _VP, _STR, _INT, _I32, _U32, _I64, _U64 = C.POINTER, C.c_void_p, C.c_char_p, C.c_int, C.c_int32, C.c_uint32, C.c_int64, C.c_uint64
+_STATUS = C.c_int
+_DESC, _CFG, _CAM, _SHARD, _TIMING, _AOV = _P(SceneDesc), _P(Config), _P(CameraData), _P(Shard), _P(Timing), _P(AovBuffers)
+_DENOISE, _ADAPTIVE, _STOP, _LENS, _NEE, _ENV = _P(DenoiseParams), _P(AdaptiveParams), _P(StopParams), _P(LensParams), _P(NeeParams), _P(EnvParams)
+_LIT, _MEDIUM = _P(LitParams), _P(MediumParams)
+_OUT = [_VP, _I32, _TIMING]          # how a render call ends: void *hip_stream, int32_t sync, rt_timing *timing
+
+# the calls every build has: a library without one of them fails at load
+_AMD_CORE = {
+    "rt_timing_init": (None, [_TIMING]),
+    "rt_set_device": (_STATUS, [_I32]),
+    "rt_scene_create": (_STATUS, [_DESC, _P(_VP)]),
+    "rt_config_init": (None, [_CFG]),
+    "rt_config_from_env": (None, [_CFG]),
+    "rt_scene_create_ex": (_STATUS, [_DESC, _CFG, _P(_VP)]),
+    "rt_scene_set_config": (_STATUS, [_VP, _CFG]),
+    "rt_scene_get_config": (_STATUS, [_VP, _CFG]),
+    "rt_scene_destroy": (_STATUS, [_VP]),
+    "rt_scene_guard_reason": (_STR, [_VP]),
+    "rt_shard_rows": (_I32, [_I32, _SHARD]),
+    "rt_render": (_STATUS, [_VP, _CAM, _SHARD, _VP, *_OUT]),
+    "rt_render_tile": (_STATUS, [_VP, _CAM, _I32, _I32, _I32, _I32, _VP, *_OUT]),
+    "rt_last_kernel_ms": (_STATUS, [_VP, _P(C.c_float)]),
+    "rt_last_timing": (_STATUS, [_VP, _TIMING]),
+    "rt_render_to_host": (_STATUS, [_VP, _CAM, _SHARD, _VP, _TIMING]),
+    "rt_trace_samples": (_STATUS, [_VP, _CAM, _I32] + [_VP] * 4),
+    "rt_closest_hits": (_STATUS, [_VP, _I32] + [_VP] * 5),
+    "rt_device_alloc": (_STATUS, [_U64, _P(_VP)]),
+    "rt_device_free": (_STATUS, [_VP]),
+    "rt_copy_to_host": (_STATUS, [_VP, _VP, _U64]),
+    "rt_tonemap": (_STATUS, [_VP, _VP, _I64, _I32, _VP]),
+    "rt_context_create": (_STATUS, [_I32, _P(_I32), _P(_VP)]),
+    "rt_context_destroy": (_STATUS, [_VP]),
+    "rt_context_num_devices": (_I32, [_VP]),
+    "rt_context_transport": (_STR, [_VP]),
+    "rt_context_scene_create": (_STATUS, [_VP, _DESC, _CFG]),
+    "rt_render_sharded": (_STATUS, [_VP, _CAM, _I32, _VP, _TIMING]),
+    "rt_gather": (_STATUS, [_VP, _I32, _I32, _I32, _VP]),
+    "rt_get_last_error_string": (_STR, []),
+    "rt_version_string": (_STR, []),
+}
+# the calls added since: an older build loaded through RTP_AMD_LIB for an A/B run (developer tools) lacks some and still loads
+_AMD_LATER = {
+    "rt_config_init_sized": (None, [_CFG, _U32]),
+    "rt_render_samples": (_STATUS, [_VP, _CAM, _SHARD, _I32, _VP, *_OUT]),
+    "rt_aov_buffers_init": (None, [_AOV]),
+    "rt_render_aov": (_STATUS, [_VP, _CAM, _SHARD, _AOV, *_OUT]),
+    "rt_render_aov_tile": (_STATUS, [_VP, _CAM, _I32, _I32, _I32, _I32, _AOV, *_OUT]),
+    "rt_render_aov_samples": (_STATUS, [_VP, _CAM, _SHARD, _I32, _AOV, *_OUT]),
+    "rt_denoise_params_init": (None, [_DENOISE]),
+    "rt_denoise_workspace_bytes": (_U64, [_I32, _I32]),
+    "rt_denoise": (_STATUS, [_VP, _AOV, _I32, _I32, _I32, _DENOISE, _VP, _U64, _VP, _VP]),
+    "rt_denoise_history_bytes": (_U64, [_I32, _I32]),
+    "rt_denoise_temporal": (_STATUS, [_VP, _AOV, _CAM, _DENOISE, _VP, _VP, _U64, _VP, _U64, _VP, _VP]),
+    "rt_adaptive_params_init": (None, [_ADAPTIVE]),
+    "rt_render_adaptive": (_STATUS, [_VP, _CAM, _SHARD, _ADAPTIVE, _VP, _VP, _VP, *_OUT]),
+    "rt_tonemap_spp": (_STATUS, [_VP, _VP, _VP, _I64, _VP]),
+    "rt_stop_params_init": (None, [_STOP]),
+    "rt_render_adaptive_rule": (_STATUS, [_VP, _CAM, _SHARD, _ADAPTIVE, _STOP, _VP, _VP, _VP, *_OUT]),
+    "rt_adaptive_judge": (_STATUS, [_I32, _I32, _SHARD, _ADAPTIVE, _STOP, _I32] + [_VP] * 4),
+    "rt_denoise_spp": (_STATUS, [_VP, _VP, _VP, _AOV, _I32, _I32, _I32, _DENOISE, _VP, _U64, _VP, _VP]),
+    "rt_denoise_temporal_spp": (_STATUS, [_VP, _VP, _VP, _AOV, _I32, _CAM, _DENOISE, _VP, _VP, _U64, _VP, _U64, _VP, _VP]),
+    "rt_adaptive_prior": (_STATUS, [_AOV, _I32, _CAM, _VP, _U64, _VP, _VP]),
+    "rt_lens_params_init": (None, [_LENS]),
+    "rt_render_lens": (_STATUS, [_VP, _CAM, _CAM, _LENS, _SHARD, _I32, _VP, *_OUT]),
+    "rt_render_aov_lens": (_STATUS, [_VP, _CAM, _CAM, _LENS, _SHARD, _I32, _AOV, *_OUT]),
+    "rt_lens_camera_rays": (_STATUS, [_CAM, _CAM, _LENS, _I32] + [_VP] * 4),
+    "rt_nee_params_init": (None, [_P(NeeParamsGlossy)]),
+    "rt_render_nee": (_STATUS, [_VP, _CAM, _NEE, _SHARD, _I32, _VP, *_OUT]),
+    "rt_nee_light_table": (_STATUS, [_VP, _I32, _VP, _VP, _VP, _P(_I32)]),
+    "rt_nee_emitter_table": (_STATUS, [_VP, _NEE, _I32] + [_VP] * 5 + [_P(_I32)]),
+    "rt_nee_light_tree": (_STATUS, [_VP, _NEE, _I32, _I32] + [_VP] * 8 + [_P(_I32)] * 2),
+    "rt_trace_samples_nee": (_STATUS, [_VP, _CAM, _NEE, _I32] + [_VP] * 5),
+    "rt_env_create": (_STATUS, [_VP, _I32, _P(_VP)]),
+    "rt_env_destroy": (_STATUS, [_VP]),
+    "rt_env_params_init": (None, [_ENV]),
+    "rt_render_env": (_STATUS, [_VP, _CAM, _VP, _ENV, _SHARD, _I32, _VP, *_OUT]),
+    "rt_env_table": (_STATUS, [_VP, _I32] + [_VP] * 4 + [_P(_I32)]),
+    "rt_env_lookup": (_STATUS, [_VP, _I32] + [_VP] * 4),
+    "rt_trace_samples_env": (_STATUS, [_VP, _CAM, _VP, _ENV, _I32] + [_VP] * 5),
+    "rt_env_from_equirect": (_STATUS, [_VP, _I32, _I32, _I32, _VP]),
+    "rt_lit_params_init": (None, [_LIT]),
+    "rt_render_lit": (_STATUS, [_VP, _CAM, _LIT, _SHARD, _I32, _VP, *_OUT]),
+    "rt_trace_samples_lit": (_STATUS, [_VP, _CAM, _LIT, _I32] + [_VP] * 6),
+    "rt_render_lit_adaptive": (_STATUS, [_VP, _CAM, _LIT, _ADAPTIVE, _SHARD, _I32, _VP, _VP, _VP, *_OUT]),
+    "rt_render_lit_adaptive_rule": (_STATUS, [_VP, _CAM, _LIT, _ADAPTIVE, _STOP, _SHARD, _I32, _VP, _VP, _VP, *_OUT]),
+    "rt_medium_params_init": (None, [_MEDIUM]),
+    "rt_render_medium": (_STATUS, [_VP, _CAM, _LIT, _MEDIUM, _SHARD, _I32, _VP, *_OUT]),
+    "rt_trace_samples_medium": (_STATUS, [_VP, _CAM, _LIT, _MEDIUM, _I32] + [_VP] * 8),
+    "rt_volume_create": (_STATUS, [_VP, _I32, _I32, _I32, _P(_VP)]),
+    "rt_volume_destroy": (_STATUS, [_VP]),
+    "rt_render_volume": (_STATUS, [_VP, _CAM, _LIT, _MEDIUM, _VP, _SHARD, _I32, _VP, *_OUT]),
+    "rt_trace_samples_volume": (_STATUS, [_VP, _CAM, _LIT, _MEDIUM, _VP, _I32] + [_VP] * 9),
+    "rt_render_volume_adaptive": (_STATUS, [_VP, _CAM, _LIT, _MEDIUM, _VP, _ADAPTIVE, _STOP, _VP, _SHARD, _I32, _VP, _VP, _VP, *_OUT]),
+}
+# the calls that take a prior: their _rule call (the judgement: the call itself) and, last, the device address of the prior
+for _base, _prior in (("rt_render_adaptive_rule", "rt_render_adaptive_prior"), ("rt_render_lit_adaptive_rule", "rt_render_lit_adaptive_prior"),
+                      ("rt_adaptive_judge", "rt_adaptive_judge_prior")):
+    _AMD_LATER[_prior] = (_STATUS, _AMD_LATER[_base][1] + [_VP])
+AMD_ABI = {**_AMD_CORE, **_AMD_LATER}
 # Every symbol include/rtp_amd.h declares (tests check that the library exports all of them).
-RTP_AMD_SYMBOLS = [
-    "rt_set_device", "rt_scene_create", "rt_scene_create_ex", "rt_config_init", "rt_config_init_sized", "rt_config_from_env", "rt_scene_set_config",
-    "rt_scene_get_config", "rt_scene_destroy", "rt_scene_guard_reason", "rt_shard_rows", "rt_render", "rt_render_tile", "rt_last_kernel_ms",
-    "rt_last_timing", "rt_timing_init",
-    "rt_render_to_host", "rt_trace_samples", "rt_closest_hits", "rt_device_alloc", "rt_device_free", "rt_copy_to_host", "rt_tonemap",
-    "rt_get_last_error_string", "rt_version_string",
-    "rt_context_create", "rt_context_destroy", "rt_context_num_devices", "rt_context_transport", "rt_context_scene_create",
-    "rt_render_sharded", "rt_gather", "rt_aov_buffers_init", "rt_render_aov", "rt_render_aov_tile",
-    "rt_denoise_params_init", "rt_denoise_workspace_bytes", "rt_denoise",
-    "rt_render_samples", "rt_render_aov_samples", "rt_denoise_history_bytes", "rt_denoise_temporal",
-    "rt_adaptive_params_init", "rt_render_adaptive", "rt_tonemap_spp",
-    "rt_lens_params_init", "rt_render_lens", "rt_render_aov_lens", "rt_lens_camera_rays",
-    "rt_nee_params_init", "rt_render_nee", "rt_nee_light_table", "rt_trace_samples_nee", "rt_nee_emitter_table",
-    "rt_nee_light_tree",
-    "rt_env_params_init", "rt_env_create", "rt_env_destroy", "rt_env_table", "rt_env_lookup", "rt_env_from_equirect", "rt_render_env",
-    "rt_trace_samples_env",
-    "rt_lit_params_init", "rt_render_lit", "rt_trace_samples_lit",
-    "rt_medium_params_init", "rt_render_medium", "rt_trace_samples_medium",
-    "rt_volume_create", "rt_volume_destroy", "rt_render_volume", "rt_trace_samples_volume",
-    "rt_render_lit_adaptive",
-    "rt_denoise_spp",
-    "rt_stop_params_init", "rt_render_adaptive_rule", "rt_render_lit_adaptive_rule", "rt_adaptive_judge",
-    "rt_denoise_temporal_spp",
-    "rt_adaptive_prior", "rt_render_adaptive_prior", "rt_render_lit_adaptive_prior", "rt_adaptive_judge_prior",
-    "rt_render_volume_adaptive",
-]
+RTP_AMD_SYMBOLS = list(AMD_ABI)
+
+HOST_ABI = {
+    "rtp_host_scene_from_config": (_VP, [_STR, _STR]),
+    "rtp_host_scene_rtiow": (_VP, [_U32, _I32, _I32, _I32]),
+    "rtp_host_scene_from_arrays": (_VP, [_VP, _I32, _VP, _I32, _P(Material), _I32]),
+    "rtp_host_scene_free": (_INT, [_VP]),
+    "rtp_host_scene_desc": (_INT, [_VP, _DESC]),
+    "rtp_host_scene_config": (_INT, [_VP, _P(ConfigInfo)]),
+    "rtp_host_frame_camera": (_INT, [_VP, _I32, _CAM]),
+    "rtp_host_frame_camera_at": (_INT, [_VP, C.c_float, _CAM]),
+    "rtp_host_make_camera": (_INT, [_I32, _I32, C.c_float, _P(C.c_float), _P(C.c_float), _P(C.c_float), _I32, _I32, _CAM]),
+    "rtp_host_quantize": (_INT, [_VP, _I64, _I32, _VP]),
+    "rtp_host_write_binary_image": (_INT, [_STR, _VP, _I32, _I32, _I32]),
+    "rtp_host_write_png": (_INT, [_STR, _VP, _I32, _I32, _I32]),
+    "rtp_host_load_hdr": (_INT, [_STR, _P(_I32), _P(_I32), _VP]),
+    "rtp_host_default_config": (_STR, []),
+}
+
+
+def _declare(lib, abi, required):
+    """Gives the functions of lib their rows of abi.  One of `required` that lib lacks fails here, at load; the others are skipped."""
+    for name, (restype, argtypes) in abi.items():
+        if name in required or hasattr(lib, name):
+            f = getattr(lib, name)
+            f.restype, f.argtypes = restype, argtypes
+    return lib
+
 
 _host = None
 _amd = None
@@ -546,25 +618,7 @@ def host_lib():
         path = os.path.join(_HERE, "librtp_host.so")
         if not os.path.exists(path):
             raise RuntimeError(f"{path} is missing: run __graft_entry__.build() (or make -C ray-tracing-practice_amd)")
-        lib = C.CDLL(path)
-        lib.rtp_host_scene_from_config.restype = C.c_void_p
-        lib.rtp_host_scene_from_config.argtypes = [C.c_char_p, C.c_char_p]
-        lib.rtp_host_scene_rtiow.restype = C.c_void_p
-        lib.rtp_host_scene_rtiow.argtypes = [C.c_uint32, C.c_int32, C.c_int32, C.c_int32]
-        lib.rtp_host_scene_from_arrays.restype = C.c_void_p
-        lib.rtp_host_scene_from_arrays.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(Material), C.c_int32]
-        lib.rtp_host_scene_free.argtypes = [C.c_void_p]
-        lib.rtp_host_scene_desc.argtypes = [C.c_void_p, C.POINTER(SceneDesc)]
-        lib.rtp_host_scene_config.argtypes = [C.c_void_p, C.POINTER(ConfigInfo)]
-        lib.rtp_host_frame_camera.argtypes = [C.c_void_p, C.c_int32, C.POINTER(CameraData)]
-        lib.rtp_host_frame_camera_at.argtypes = [C.c_void_p, C.c_float, C.POINTER(CameraData)]
-        lib.rtp_host_make_camera.argtypes = [C.c_int32, C.c_int32, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float),
-                                             C.POINTER(C.c_float), C.c_int32, C.c_int32, C.POINTER(CameraData)]
-        lib.rtp_host_quantize.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
-        lib.rtp_host_write_binary_image.argtypes = [C.c_char_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
-        lib.rtp_host_write_png.argtypes = [C.c_char_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
-        lib.rtp_host_default_config.restype = C.c_char_p
-        _host = lib
+        _host = _declare(C.CDLL(path), HOST_ABI, HOST_ABI)
     return _host
 
 
@@ -576,167 +630,7 @@ def amd_lib():
         path = os.environ.get("RTP_AMD_LIB") or os.path.join(_HERE, "librtp_amd.so")
         if not os.path.exists(path):
             raise RuntimeError(f"{path} is missing: the HIP render library must be built (no CPU fallback exists)")
-        lib = C.CDLL(path)
-        lib.rt_set_device.argtypes = [C.c_int32]
-        lib.rt_scene_create.argtypes = [C.POINTER(SceneDesc), C.POINTER(C.c_void_p)]
-        lib.rt_scene_destroy.argtypes = [C.c_void_p]
-        lib.rt_config_init.argtypes = [C.POINTER(Config)]
-        lib.rt_config_init.restype = None
-        if hasattr(lib, "rt_config_init_sized"):
-            lib.rt_config_init_sized.argtypes = [C.POINTER(Config), C.c_uint32]
-            lib.rt_config_init_sized.restype = None
-        lib.rt_config_from_env.argtypes = [C.POINTER(Config)]
-        lib.rt_config_from_env.restype = None
-        lib.rt_scene_create_ex.argtypes = [C.POINTER(SceneDesc), C.POINTER(Config), C.POINTER(C.c_void_p)]
-        lib.rt_scene_set_config.argtypes = [C.c_void_p, C.POINTER(Config)]
-        lib.rt_scene_get_config.argtypes = [C.c_void_p, C.POINTER(Config)]
-        lib.rt_scene_guard_reason.argtypes = [C.c_void_p]
-        lib.rt_scene_guard_reason.restype = C.c_char_p
-        lib.rt_shard_rows.argtypes = [C.c_int32, C.POINTER(Shard)]
-        lib.rt_shard_rows.restype = C.c_int32
-        lib.rt_render.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(Shard), C.c_void_p, C.c_void_p,
-                                  C.c_int32, C.POINTER(Timing)]
-        lib.rt_render_tile.argtypes = [C.c_void_p, C.POINTER(CameraData), C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
-                                       C.c_int32, C.POINTER(Timing)]
-        if hasattr(lib, "rt_render_aov"):        # (an older build loaded through RTP_AMD_LIB for an A/B run has no AOV calls)
-            lib.rt_aov_buffers_init.argtypes = [C.POINTER(AovBuffers)]
-            lib.rt_aov_buffers_init.restype = None
-            lib.rt_render_aov.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(Shard), C.POINTER(AovBuffers), C.c_void_p, C.c_int32,
-                                          C.POINTER(Timing)]
-            lib.rt_render_aov_tile.argtypes = [C.c_void_p, C.POINTER(CameraData), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
-                                               C.POINTER(AovBuffers), C.c_void_p, C.c_int32, C.POINTER(Timing)]
-        if hasattr(lib, "rt_denoise"):
-            lib.rt_denoise_params_init.argtypes = [C.POINTER(DenoiseParams)]
-            lib.rt_denoise_params_init.restype = None
-            lib.rt_denoise_workspace_bytes.argtypes = [C.c_int32, C.c_int32]
-            lib.rt_denoise_workspace_bytes.restype = C.c_uint64
-            lib.rt_denoise.argtypes = [C.c_void_p, C.POINTER(AovBuffers), C.c_int32, C.c_int32, C.c_int32, C.POINTER(DenoiseParams),
-                                       C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
-        if hasattr(lib, "rt_render_adaptive"):
-            lib.rt_adaptive_params_init.argtypes = [C.POINTER(AdaptiveParams)]
-            lib.rt_adaptive_params_init.restype = None
-            lib.rt_render_adaptive.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(Shard), C.POINTER(AdaptiveParams), C.c_void_p,
-                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(Timing)]
-            lib.rt_tonemap_spp.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-        if hasattr(lib, "rt_denoise_temporal"):
-            lib.rt_render_samples.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(Shard), C.c_int32, C.c_void_p, C.c_void_p,
-                                              C.c_int32, C.POINTER(Timing)]
-            lib.rt_render_aov_samples.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(Shard), C.c_int32, C.POINTER(AovBuffers),
-                                                  C.c_void_p, C.c_int32, C.POINTER(Timing)]
-            lib.rt_denoise_history_bytes.argtypes = [C.c_int32, C.c_int32]
-            lib.rt_denoise_history_bytes.restype = C.c_uint64
-            lib.rt_denoise_temporal.argtypes = [C.c_void_p, C.POINTER(AovBuffers), C.POINTER(CameraData), C.POINTER(DenoiseParams),
-                                                C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
-        if hasattr(lib, "rt_render_lens"):
-            lib.rt_lens_params_init.argtypes = [C.POINTER(LensParams)]
-            lib.rt_lens_params_init.restype = None
-            lib.rt_render_lens.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(CameraData), C.POINTER(LensParams), C.POINTER(Shard),
-                                           C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(Timing)]
-            lib.rt_render_aov_lens.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(CameraData), C.POINTER(LensParams),
-                                               C.POINTER(Shard), C.c_int32, C.POINTER(AovBuffers), C.c_void_p, C.c_int32, C.POINTER(Timing)]
-            lib.rt_lens_camera_rays.argtypes = [C.POINTER(CameraData), C.POINTER(CameraData), C.POINTER(LensParams), C.c_int32, C.c_void_p,
-                                                C.c_void_p, C.c_void_p, C.c_void_p]
-        if hasattr(lib, "rt_render_nee"):
-            lib.rt_nee_params_init.argtypes = [C.POINTER(NeeParamsGlossy)]
-            lib.rt_nee_params_init.restype = None
-            lib.rt_render_nee.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(NeeParams), C.POINTER(Shard), C.c_int32, C.c_void_p,
-                                          C.c_void_p, C.c_int32, C.POINTER(Timing)]
-            lib.rt_nee_light_table.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
-            if hasattr(lib, "rt_nee_emitter_table"):
-                lib.rt_nee_emitter_table.argtypes = [C.c_void_p, C.POINTER(NeeParams), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                     C.c_void_p, C.POINTER(C.c_int32)]
-            if hasattr(lib, "rt_nee_light_tree"):
-                lib.rt_nee_light_tree.argtypes = [C.c_void_p, C.POINTER(NeeParams), C.c_int32, C.c_int32] + [C.c_void_p] * 8 + [C.POINTER(C.c_int32)] * 2
-            lib.rt_trace_samples_nee.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(NeeParams), C.c_int32, C.c_void_p, C.c_void_p,
-                                                 C.c_void_p, C.c_void_p, C.c_void_p]
-        if hasattr(lib, "rt_render_env"):
-            lib.rt_env_params_init.argtypes = [C.POINTER(EnvParams)]
-            lib.rt_env_params_init.restype = None
-            lib.rt_env_create.argtypes = [C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]
-            lib.rt_env_destroy.argtypes = [C.c_void_p]
-            lib.rt_env_table.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]
-            lib.rt_env_lookup.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-            lib.rt_env_from_equirect.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
-            lib.rt_render_env.argtypes = [C.c_void_p, C.POINTER(CameraData), C.c_void_p, C.POINTER(EnvParams), C.POINTER(Shard), C.c_int32,
-                                          C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(Timing)]
-            lib.rt_trace_samples_env.argtypes = [C.c_void_p, C.POINTER(CameraData), C.c_void_p, C.POINTER(EnvParams), C.c_int32, C.c_void_p,
-                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        if hasattr(lib, "rt_render_lit"):
-            lib.rt_lit_params_init.argtypes = [C.POINTER(LitParams)]
-            lib.rt_lit_params_init.restype = None
-            lib.rt_render_lit.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(LitParams), C.POINTER(Shard), C.c_int32, C.c_void_p,
-                                          C.c_void_p, C.c_int32, C.POINTER(Timing)]
-            lib.rt_trace_samples_lit.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(LitParams), C.c_int32, C.c_void_p, C.c_void_p,
-                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        if hasattr(lib, "rt_render_medium"):
-            lib.rt_medium_params_init.argtypes = [C.POINTER(MediumParams)]
-            lib.rt_medium_params_init.restype = None
-            lib.rt_render_medium.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(LitParams), C.POINTER(MediumParams), C.POINTER(Shard),
-                                             C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(Timing)]
-            lib.rt_trace_samples_medium.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(LitParams), C.POINTER(MediumParams), C.c_int32] + \
-                                                   [C.c_void_p] * 8
-        if hasattr(lib, "rt_render_volume"):
-            lib.rt_volume_create.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]
-            lib.rt_volume_destroy.argtypes = [C.c_void_p]
-            lib.rt_render_volume.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(LitParams), C.POINTER(MediumParams), C.c_void_p,
-                                             C.POINTER(Shard), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(Timing)]
-            lib.rt_trace_samples_volume.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(LitParams), C.POINTER(MediumParams), C.c_void_p,
-                                                    C.c_int32] + [C.c_void_p] * 9
-        if hasattr(lib, "rt_render_lit_adaptive"):
-            lib.rt_render_lit_adaptive.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(LitParams), C.POINTER(AdaptiveParams),
-                                                   C.POINTER(Shard), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
-                                                   C.POINTER(Timing)]
-        if hasattr(lib, "rt_render_adaptive_rule"):
-            lib.rt_stop_params_init.argtypes = [C.POINTER(StopParams)]
-            lib.rt_stop_params_init.restype = None
-            lib.rt_render_adaptive_rule.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(Shard), C.POINTER(AdaptiveParams),
-                                                    C.POINTER(StopParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
-                                                    C.POINTER(Timing)]
-            lib.rt_render_lit_adaptive_rule.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(LitParams), C.POINTER(AdaptiveParams),
-                                                        C.POINTER(StopParams), C.POINTER(Shard), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                                        C.c_void_p, C.c_int32, C.POINTER(Timing)]
-            lib.rt_adaptive_judge.argtypes = [C.c_int32, C.c_int32, C.POINTER(Shard), C.POINTER(AdaptiveParams), C.POINTER(StopParams), C.c_int32,
-                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        if hasattr(lib, "rt_denoise_spp"):
-            lib.rt_denoise_spp.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(AovBuffers), C.c_int32, C.c_int32, C.c_int32,
-                                           C.POINTER(DenoiseParams), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
-        if hasattr(lib, "rt_denoise_temporal_spp"):
-            lib.rt_denoise_temporal_spp.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(AovBuffers), C.c_int32, C.POINTER(CameraData),
-                                                    C.POINTER(DenoiseParams), C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
-                                                    C.c_void_p, C.c_void_p]
-        if hasattr(lib, "rt_adaptive_prior"):
-            lib.rt_adaptive_prior.argtypes = [C.POINTER(AovBuffers), C.c_int32, C.POINTER(CameraData), C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
-            lib.rt_render_adaptive_prior.argtypes = lib.rt_render_adaptive_rule.argtypes + [C.c_void_p]
-            lib.rt_render_lit_adaptive_prior.argtypes = lib.rt_render_lit_adaptive_rule.argtypes + [C.c_void_p]
-            lib.rt_adaptive_judge_prior.argtypes = lib.rt_adaptive_judge.argtypes + [C.c_void_p]
-        if hasattr(lib, "rt_render_volume_adaptive"):
-            lib.rt_render_volume_adaptive.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(LitParams), C.POINTER(MediumParams), C.c_void_p,
-                                                      C.POINTER(AdaptiveParams), C.POINTER(StopParams), C.c_void_p, C.POINTER(Shard), C.c_int32,
-                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(Timing)]
-        lib.rt_last_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
-        lib.rt_last_timing.argtypes = [C.c_void_p, C.POINTER(Timing)]
-        lib.rt_timing_init.argtypes = [C.POINTER(Timing)]
-        lib.rt_timing_init.restype = None
-        lib.rt_render_to_host.argtypes = [C.c_void_p, C.POINTER(CameraData), C.POINTER(Shard), C.c_void_p,
-                                          C.POINTER(Timing)]
-        lib.rt_trace_samples.argtypes = [C.c_void_p, C.POINTER(CameraData), C.c_int32, C.c_void_p, C.c_void_p,
-                                         C.c_void_p, C.c_void_p]
-        lib.rt_closest_hits.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        lib.rt_device_alloc.argtypes = [C.c_uint64, C.POINTER(C.c_void_p)]
-        lib.rt_device_free.argtypes = [C.c_void_p]
-        lib.rt_copy_to_host.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64]
-        lib.rt_tonemap.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
-        lib.rt_get_last_error_string.restype = C.c_char_p
-        lib.rt_version_string.restype = C.c_char_p
-        lib.rt_context_create.argtypes = [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_void_p)]
-        lib.rt_context_destroy.argtypes = [C.c_void_p]
-        lib.rt_context_num_devices.argtypes = [C.c_void_p]
-        lib.rt_context_transport.argtypes = [C.c_void_p]
-        lib.rt_context_transport.restype = C.c_char_p
-        lib.rt_context_scene_create.argtypes = [C.c_void_p, C.POINTER(SceneDesc), C.POINTER(Config)]
-        lib.rt_render_sharded.argtypes = [C.c_void_p, C.POINTER(CameraData), C.c_int32, C.c_void_p, C.POINTER(Timing)]
-        lib.rt_gather.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
-        _amd = lib
+        _amd = _declare(C.CDLL(path), AMD_ABI, _AMD_CORE)
     return _amd
 
 
@@ -810,7 +704,6 @@ class HostScene:
 def load_hdr_image(path):
     """rtp_main --env's loader (host/texture_io.cpp): a PFM or Radiance .hdr file → (h, w, 3) float32, top row first."""
     lib = host_lib()
-    lib.rtp_host_load_hdr.argtypes = [C.c_char_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_void_p]
     w, h = C.c_int32(), C.c_int32()
     if lib.rtp_host_load_hdr(os.fsencode(path), C.byref(w), C.byref(h), None) != 0:
         raise RtError(f"cannot load {path} as a PFM or Radiance image")
@@ -855,13 +748,8 @@ DEFAULTS = {}
 def denoise_params(**params):
     """rt_denoise_params with the library's defaults (rt_denoise_params_init), then the given fields (iterations, sigma_depth,
     sigma_luminance, normal_squarings)."""
-    p = DenoiseParams()
-    amd_lib().rt_denoise_params_init(C.byref(p))
-    for k, v in params.items():
-        if k not in ("iterations", "sigma_depth", "sigma_luminance", "normal_squarings"):
-            raise TypeError(f"rt_denoise_params has no field {k!r}")
-        setattr(p, k, v)
-    return p
+    return _params(DenoiseParams, "rt_denoise_params", ("iterations", "sigma_depth", "sigma_luminance", "normal_squarings"), params,
+                   unknown=lambda k: TypeError(f"rt_denoise_params has no field {k!r}"))
 
 
 # rt_denoise workspaces, one per size: allocated on the device current at their first use (a caller that switches devices
@@ -955,7 +843,7 @@ _hip_rt = None
 
 def _hip():
     """The HIP runtime librtp_amd.so itself runs on (already loaded with it: found by soname, never loaded a second time), for the
-    host-to-device copies of denoise_to_host — the C ABI has no upload call of its own."""
+    host-to-device copies of _DeviceBuffers.upload — the C ABI has no upload call of its own."""
     global _hip_rt
     if _hip_rt is None:
         amd_lib()
@@ -971,101 +859,124 @@ def _hip():
     return _hip_rt
 
 
+class _DeviceBuffers:
+    """The temporary device buffers of one call, as integer device addresses: `with _DeviceBuffers() as dev:` frees every one of them
+    on exit, whether the call returned or raised."""
+
+    def __enter__(self):
+        self._held = []
+        return self
+
+    def __exit__(self, *exc):
+        for d in self._held:
+            amd_lib().rt_device_free(d)
+
+    def alloc(self, nbytes):
+        """A fresh buffer of nbytes — of 12 bytes, one pixel, for an empty request: every call gets an address to pass."""
+        d = C.c_void_p()
+        _check(amd_lib().rt_device_alloc(nbytes or 12, C.byref(d)), "rt_device_alloc")
+        self._held.append(d)
+        return d.value
+
+    def upload(self, a):
+        """A fresh buffer holding the host array a (for an empty one no copy is issued)."""
+        d = self.alloc(a.nbytes)
+        if a.nbytes and _hip().hipMemcpy(d, a.ctypes.data, a.nbytes, 1) != 0:       # hipMemcpyHostToDevice
+            raise RtError("hipMemcpy host to device failed")
+        return d
+
+    def upload_aov(self, aov, channels=AOV_CHANNELS):
+        """The arrays of render_aov_to_host's dict in fresh buffers: {key: address}, as the calls on device addresses take them."""
+        return {key: self.upload(np.ascontiguousarray(aov[key], dtype=dtype)) for key, _, dtype, _ in channels}
+
+    def download(self, d, a):
+        """The buffer at d into the host array a, which it returns."""
+        _check(amd_lib().rt_copy_to_host(a.ctypes.data, d, a.nbytes), "rt_copy_to_host")
+        return a
+
+
+def _frame_to_host(cam, shard, render):
+    """The body of a render_*_to_host: the rows of rt_shard_rows, render(device address of rows x width x 3 floats) → rt_timing, the
+    copy back.  Returns ((rows, width, 3) float32 sums, rt_timing)."""
+    fb = np.empty((amd_lib().rt_shard_rows(cam.image_height, _ref(shard)), cam.image_width, 3), dtype=np.float32)
+    with _DeviceBuffers() as dev:
+        d = dev.alloc(fb.nbytes)
+        t = render(d)
+        dev.download(d, fb)
+    return fb, t
+
+
+def _adaptive_to_host(cam, shard, prior, render):
+    """The body of a render_*_adaptive_to_host: render(d_fb, d_spp, d_moments, d_prior) → rt_timing, d_prior None or the address of the
+    uploaded host array prior (rows, w, 2).  Returns (fb (rows, w, 3) float32, spp (rows, w) int32, moments (rows, w, 2) float32,
+    rt_timing)."""
+    rows, w = amd_lib().rt_shard_rows(cam.image_height, _ref(shard)), cam.image_width
+    out = np.empty((rows, w, 3), dtype=np.float32), np.empty((rows, w), dtype=np.int32), np.empty((rows, w, 2), dtype=np.float32)
+    with _DeviceBuffers() as dev:
+        ptrs = [dev.alloc(a.nbytes) for a in out]
+        d_prior = None if prior is None else dev.upload(np.ascontiguousarray(np.asarray(prior, dtype=np.float32).reshape(rows, w, 2)))
+        t = render(*ptrs, d_prior)
+        for d, a in zip(ptrs, out):
+            dev.download(d, a)
+    return (*out, t)
+
+
+def _aov_to_host(rows, w, render):
+    """The body of a render_aov_*_to_host: render({key: device address} of the five AOV_CHANNELS, rows x w pixels each) → rt_timing.
+    Returns ({key: array}, rt_timing)."""
+    pixels = max(w, 0) * max(rows, 0)
+    with _DeviceBuffers() as dev:
+        ptrs = {key: dev.alloc(pixels * per * 4) for key, _, _, per in AOV_CHANNELS}
+        t = render(ptrs)
+        out = {key: dev.download(ptrs[key], np.empty((rows, w, per) if per > 1 else (rows, w), dtype=dtype))
+               for key, _, dtype, per in AOV_CHANNELS}
+    return out, t
+
+
 def denoise_to_host(fb_sum, aov, spp, **params):
     """rt_denoise of host arrays: fb_sum (H, W, 3) float32 as DeviceScene.render_to_host returns it, aov the dict of
     DeviceScene.render_aov_to_host (albedo, normal, depth, hits; prim is not used).  Returns the (H, W, 3) float32 output, the sum
     over samples like fb_sum.  Synchronous (default stream)."""
-    lib = amd_lib()
     fb = np.ascontiguousarray(fb_sum, dtype=np.float32)
     height, width = fb.shape[:2]
-    arrays = {"fb": fb}
-    for key, _, dtype, _ in AOV_CHANNELS[:4]:
-        arrays[key] = np.ascontiguousarray(aov[key], dtype=dtype)
-    dev = {}
-    try:
-        for key, a in arrays.items():
-            d = C.c_void_p()
-            _check(lib.rt_device_alloc(a.nbytes or 4, C.byref(d)), "rt_device_alloc")
-            dev[key] = d
-            if _hip().hipMemcpy(d, a.ctypes.data, a.nbytes, 1) != 0:       # hipMemcpyHostToDevice
-                raise RtError("hipMemcpy host to device failed")
-        d_out = C.c_void_p()
-        _check(lib.rt_device_alloc(fb.nbytes or 4, C.byref(d_out)), "rt_device_alloc")
-        dev["out"] = d_out
-        denoise(dev["fb"].value, {k: dev[k].value for k in ("albedo", "normal", "depth", "hits")}, width, height, spp, d_out.value, **params)
-        out = np.empty_like(fb)
-        _check(lib.rt_copy_to_host(out.ctypes.data, d_out, out.nbytes), "rt_copy_to_host")
-    finally:
-        for d in dev.values():
-            lib.rt_device_free(d)
-    return out
+    with _DeviceBuffers() as dev:
+        d_out = dev.alloc(fb.nbytes)
+        denoise(dev.upload(fb), dev.upload_aov(aov, AOV_CHANNELS[:4]), width, height, spp, d_out, **params)
+        return dev.download(d_out, np.empty_like(fb))
 
 
 def denoise_spp_to_host(fb_sum, spp, moments, aov, aov_spp, **params):
     """rt_denoise_spp of host arrays: fb_sum (H, W, 3) float32, spp (H, W) int32 and moments (H, W, 2) float32 or None as
     DeviceScene.render_adaptive_to_host returns them, aov the dict of DeviceScene.render_aov_to_host at aov_spp samples per pixel.
     Returns the (H, W, 3) float32 output, each pixel the sum over its own samples like fb_sum.  Synchronous (default stream)."""
-    lib = amd_lib()
     fb = np.ascontiguousarray(fb_sum, dtype=np.float32)
     height, width = fb.shape[:2]
-    arrays = {"fb": fb, "spp": np.ascontiguousarray(spp, dtype=np.int32)}
-    if moments is not None:
-        arrays["moments"] = np.ascontiguousarray(moments, dtype=np.float32)
-    for key, _, dtype, _ in AOV_CHANNELS[:4]:
-        arrays[key] = np.ascontiguousarray(aov[key], dtype=dtype)
-    dev = {}
-    try:
-        for key, a in arrays.items():
-            dev[key] = _upload(a)
-        d_out = C.c_void_p()
-        _check(lib.rt_device_alloc(fb.nbytes or 4, C.byref(d_out)), "rt_device_alloc")
-        dev["out"] = d_out
-        denoise_spp(dev["fb"].value, dev["spp"].value, dev["moments"].value if "moments" in dev else None,
-                    {k: dev[k].value for k in ("albedo", "normal", "depth", "hits")}, aov_spp, width, height, d_out.value, **params)
-        out = np.empty_like(fb)
-        _check(lib.rt_copy_to_host(out.ctypes.data, d_out, out.nbytes), "rt_copy_to_host")
-    finally:
-        for d in dev.values():
-            lib.rt_device_free(d)
-    return out
-
-
-def _upload(a):
-    """A fresh device buffer holding the host array a (rt_device_alloc: the caller frees it)."""
-    d = C.c_void_p()
-    _check(amd_lib().rt_device_alloc(a.nbytes or 4, C.byref(d)), "rt_device_alloc")
-    if a.nbytes and _hip().hipMemcpy(d, a.ctypes.data, a.nbytes, 1) != 0:       # hipMemcpyHostToDevice
-        amd_lib().rt_device_free(d)
-        raise RtError("hipMemcpy host to device failed")
-    return d
+    with _DeviceBuffers() as dev:
+        d_moments = None if moments is None else dev.upload(np.ascontiguousarray(moments, dtype=np.float32))
+        d_out = dev.alloc(fb.nbytes)
+        denoise_spp(dev.upload(fb), dev.upload(np.ascontiguousarray(spp, dtype=np.int32)), d_moments, dev.upload_aov(aov, AOV_CHANNELS[:4]),
+                    aov_spp, width, height, d_out, **params)
+        return dev.download(d_out, np.empty_like(fb))
 
 
 def adaptive_judge(moments, n, going_on=None, shard=None, rule=0, prior=None, **params):
     """rt_adaptive_judge: one judgement of a stopping rule on the current device.  moments (rows, width, 2) float32 (S1, S2); going_on
     None (every pixel) or (rows, width) bool; prior None or (rows, width, 2) float32 (ch, vh): given, the call is
     rt_adaptive_judge_prior; params are rt_adaptive_params fields.  Returns goes_on (rows, width) bool."""
-    lib = amd_lib()
     mom = np.ascontiguousarray(moments, dtype=np.float32)
     rows, width = mom.shape[:2]
     out = np.empty((rows, width), dtype=np.uint8)
     p, stop = adaptive_params(**params), stop_params(rule=rule)
-    dev = []
-    try:
-        dev.append(_upload(mom))
-        dev.append(None if going_on is None else _upload(np.ascontiguousarray(np.asarray(going_on).reshape(rows, width), dtype=np.uint8)))
-        dev.append(_upload(out))
+    with _DeviceBuffers() as dev:
+        d_going_on = None if going_on is None else dev.upload(np.ascontiguousarray(np.asarray(going_on).reshape(rows, width), dtype=np.uint8))
+        d_out = dev.alloc(out.nbytes)
+        args = (width, rows, _ref(shard), C.byref(p), C.byref(stop), n, dev.upload(mom), d_going_on, d_out, None)
         if prior is None:
-            _check(lib.rt_adaptive_judge(width, rows, C.byref(shard) if shard else None, C.byref(p), C.byref(stop), n, dev[0], dev[1], dev[2], None),
-                   "rt_adaptive_judge")
+            _check(amd_lib().rt_adaptive_judge(*args), "rt_adaptive_judge")
         else:
-            dev.append(_upload(np.ascontiguousarray(np.asarray(prior, dtype=np.float32).reshape(rows, width, 2))))
-            _check(lib.rt_adaptive_judge_prior(width, rows, C.byref(shard) if shard else None, C.byref(p), C.byref(stop), n, dev[0], dev[1], dev[2],
-                                               None, dev[3]), "rt_adaptive_judge_prior")
-        _check(lib.rt_copy_to_host(out.ctypes.data, dev[2], out.nbytes), "rt_copy_to_host")
-    finally:
-        for d in dev:
-            if d is not None:
-                lib.rt_device_free(d)
+            d_prior = dev.upload(np.ascontiguousarray(np.asarray(prior, dtype=np.float32).reshape(rows, width, 2)))
+            _check(amd_lib().rt_adaptive_judge_prior(*args, d_prior), "rt_adaptive_judge_prior")
+        dev.download(d_out, out)
     return out.astype(bool)
 
 
@@ -1113,25 +1024,11 @@ class TemporalDenoiser:
         """One frame of host arrays: fb_sum (H, W, 3) float32 as DeviceScene.render_to_host returns it, aov the dict of
         DeviceScene.render_aov_to_host (prim included), cam its camera.  Returns the (H, W, 3) float32 output, the sum over samples
         like fb_sum.  Synchronous (default stream)."""
-        lib = amd_lib()
         fb = np.ascontiguousarray(fb_sum, dtype=np.float32)
-        arrays = {"fb": fb}
-        for key, _, dtype, _ in AOV_CHANNELS:
-            arrays[key] = np.ascontiguousarray(aov[key], dtype=dtype)
-        dev = {}
-        try:
-            for key, a in arrays.items():
-                dev[key] = _upload(a)
-            d_out = C.c_void_p()
-            _check(lib.rt_device_alloc(fb.nbytes or 4, C.byref(d_out)), "rt_device_alloc")
-            dev["out"] = d_out
-            self.step(dev["fb"].value, {k: dev[k].value for k, _, _, _ in AOV_CHANNELS}, cam, d_out.value)
-            out = np.empty_like(fb)
-            _check(lib.rt_copy_to_host(out.ctypes.data, d_out, out.nbytes), "rt_copy_to_host")
-        finally:
-            for d in dev.values():
-                lib.rt_device_free(d)
-        return out
+        with _DeviceBuffers() as dev:
+            d_out = dev.alloc(fb.nbytes)
+            self.step(dev.upload(fb), dev.upload_aov(aov), cam, d_out)
+            return dev.download(d_out, np.empty_like(fb))
 
     def step_spp(self, d_fb, d_spp, d_moments, aov_ptrs, aov_spp, cam, d_out, stream=None):
         """One adaptively sampled frame on device addresses (denoise_temporal_spp); only enqueues on `stream`."""
@@ -1147,28 +1044,12 @@ class TemporalDenoiser:
         DeviceScene.render_adaptive_to_host returns them, aov the dict of DeviceScene.render_aov_to_host (prim included) at aov_spp
         samples per pixel, cam their camera.  Returns the (H, W, 3) float32 output, each pixel the sum over its own samples like
         fb_sum.  Synchronous (default stream)."""
-        lib = amd_lib()
         fb = np.ascontiguousarray(fb_sum, dtype=np.float32)
-        arrays = {"fb": fb, "spp": np.ascontiguousarray(spp, dtype=np.int32)}
-        if moments is not None:
-            arrays["moments"] = np.ascontiguousarray(moments, dtype=np.float32)
-        for key, _, dtype, _ in AOV_CHANNELS:
-            arrays[key] = np.ascontiguousarray(aov[key], dtype=dtype)
-        dev = {}
-        try:
-            for key, a in arrays.items():
-                dev[key] = _upload(a)
-            d_out = C.c_void_p()
-            _check(lib.rt_device_alloc(fb.nbytes or 4, C.byref(d_out)), "rt_device_alloc")
-            dev["out"] = d_out
-            self.step_spp(dev["fb"].value, dev["spp"].value, dev["moments"].value if "moments" in dev else None,
-                          {k: dev[k].value for k, _, _, _ in AOV_CHANNELS}, aov_spp, cam, d_out.value)
-            out = np.empty_like(fb)
-            _check(lib.rt_copy_to_host(out.ctypes.data, d_out, out.nbytes), "rt_copy_to_host")
-        finally:
-            for d in dev.values():
-                lib.rt_device_free(d)
-        return out
+        with _DeviceBuffers() as dev:
+            d_moments = None if moments is None else dev.upload(np.ascontiguousarray(moments, dtype=np.float32))
+            d_out = dev.alloc(fb.nbytes)
+            self.step_spp(dev.upload(fb), dev.upload(np.ascontiguousarray(spp, dtype=np.int32)), d_moments, dev.upload_aov(aov), aov_spp, cam, d_out)
+            return dev.download(d_out, np.empty_like(fb))
 
     def prior(self, aov_ptrs, aov_spp, cam, d_prior, stream=None):
         """rt_adaptive_prior of the frame about to be rendered (its AOVs at aov_spp samples per pixel and its camera) on the history the
@@ -1181,19 +1062,11 @@ class TemporalDenoiser:
     def prior_to_host(self, aov, aov_spp, cam):
         """prior() of host arrays: aov the dict of DeviceScene.render_aov_to_host (prim included).  Returns (H, W, 2) float32 (ch, vh).
         Synchronous (default stream)."""
-        lib = amd_lib()
         out = np.empty((self.height, self.width, 2), dtype=np.float32)
-        dev = {}
-        try:
-            for key, _, dtype, _ in AOV_CHANNELS:
-                dev[key] = _upload(np.ascontiguousarray(aov[key], dtype=dtype))
-            dev["prior"] = _upload(out)
-            self.prior({k: dev[k].value for k, _, _, _ in AOV_CHANNELS}, aov_spp, cam, dev["prior"].value)
-            _check(lib.rt_copy_to_host(out.ctypes.data, dev["prior"], out.nbytes), "rt_copy_to_host")
-        finally:
-            for d in dev.values():
-                lib.rt_device_free(d)
-        return out
+        with _DeviceBuffers() as dev:
+            d_prior = dev.alloc(out.nbytes)
+            self.prior(dev.upload_aov(aov), aov_spp, cam, d_prior)
+            return dev.download(d_prior, out)
 
     def history_to_host(self):
         """The history the last step wrote (uint8 array of rt_denoise_history_bytes; the header's layout)."""
@@ -1211,6 +1084,17 @@ class TemporalDenoiser:
             self.close()
         except Exception:
             pass
+
+
+def _adaptive_entry(base, rule, prior):
+    """Which of the three entry points of an adaptive render call (rule, prior) ask for: (its name, its rt_stop_params argument, its
+    arguments after the rt_timing).  No rule and no prior: the call `base` itself; a prior: base_prior, with rule 0 unless given; else
+    base_rule.  Three symbols of the ABI, each reached."""
+    if prior is not None:
+        return base + "_prior", (C.byref(stop_params(rule=rule or 0)),), (C.c_void_p(prior),)
+    if rule is None:
+        return base, (), ()
+    return base + "_rule", (C.byref(stop_params(rule=rule)),), ()
 
 
 class DeviceScene:
@@ -1256,107 +1140,55 @@ class DeviceScene:
         _check(amd_lib().rt_scene_get_config(self._h, C.byref(cfg)), "rt_scene_get_config")
         return cfg
 
+    def _call(self, name, *args, after=()):
+        """The library's call `name` on this handle with the handle's configuration in force — name(handle, *args, rt_timing, *after) —
+        and the rt_timing it filled."""
+        t = Timing()
+        self._apply_config()
+        _check(getattr(amd_lib(), name)(self._h, *args, C.byref(t), *after), name)
+        return t
+
     def render_to_host(self, cam, shard=None, sample_first=0):
         """The frame's sums as a (rows, width, 3) float32 array and the rt_timing; sample_first != 0: samples sample_first … of
         every pixel (rt_render_samples through a fresh device buffer)."""
-        lib = amd_lib()
-        rows = lib.rt_shard_rows(cam.image_height, C.byref(shard) if shard else None)
-        fb = np.empty((rows, cam.image_width, 3), dtype=np.float32)
-        t = Timing()
         if sample_first:
-            d = C.c_void_p()
-            _check(lib.rt_device_alloc(fb.nbytes or 12, C.byref(d)), "rt_device_alloc")
-            try:
-                t = self.render(cam, d.value, shard=shard, sample_first=sample_first)
-                _check(lib.rt_copy_to_host(fb.ctypes.data, d, fb.nbytes), "rt_copy_to_host")
-            finally:
-                lib.rt_device_free(d)
-            return fb, t
-        self._apply_config()
-        _check(lib.rt_render_to_host(self._h, C.byref(cam), C.byref(shard) if shard else None, fb.ctypes.data,
-                                     C.byref(t)), "rt_render_to_host")
-        return fb, t
+            return _frame_to_host(cam, shard, lambda d: self.render(cam, d, shard=shard, sample_first=sample_first))
+        fb = np.empty((amd_lib().rt_shard_rows(cam.image_height, _ref(shard)), cam.image_width, 3), dtype=np.float32)
+        return fb, self._call("rt_render_to_host", C.byref(cam), _ref(shard), fb.ctypes.data)
 
     def render(self, cam, d_fb_ptr, shard=None, stream=None, sync=True, sample_first=0):
         """d_fb_ptr: integer device address (e.g. torch tensor.data_ptr()).  sample_first != 0: rt_render_samples."""
-        t = Timing()
-        self._apply_config()
         if sample_first:
-            _check(amd_lib().rt_render_samples(self._h, C.byref(cam), C.byref(shard) if shard else None, sample_first, C.c_void_p(d_fb_ptr),
-                                               C.c_void_p(stream or 0), 1 if sync else 0, C.byref(t)), "rt_render_samples")
-            return t
-        _check(amd_lib().rt_render(self._h, C.byref(cam), C.byref(shard) if shard else None, C.c_void_p(d_fb_ptr),
-                                   C.c_void_p(stream or 0), 1 if sync else 0, C.byref(t)), "rt_render")
-        return t
+            return self._call("rt_render_samples", C.byref(cam), _ref(shard), sample_first, C.c_void_p(d_fb_ptr), *_stream_sync(stream, sync))
+        return self._call("rt_render", C.byref(cam), _ref(shard), C.c_void_p(d_fb_ptr), *_stream_sync(stream, sync))
 
     def render_tile_to_host(self, cam, x0, y0, w, h):
         """rt_render_tile into a fresh device buffer, copied to the host: (h, w, 3) float32 sums and the rt_timing."""
-        lib = amd_lib()
-        d = C.c_void_p()
-        _check(lib.rt_device_alloc(max(w, 0) * max(h, 0) * 12 or 12, C.byref(d)), "rt_device_alloc")
-        t = Timing()
-        self._apply_config()
-        try:
-            _check(lib.rt_render_tile(self._h, C.byref(cam), x0, y0, w, h, d, C.c_void_p(0), 1, C.byref(t)), "rt_render_tile")
-            fb = np.empty((h, w, 3), dtype=np.float32)
-            _check(lib.rt_copy_to_host(fb.ctypes.data, d, fb.nbytes), "rt_copy_to_host")
-        finally:
-            lib.rt_device_free(d)
-        return fb, t
+        with _DeviceBuffers() as dev:          # (not _frame_to_host: the result is the tile's, made once the library has taken the tile)
+            d = dev.alloc(max(w, 0) * max(h, 0) * 12)
+            t = self._call("rt_render_tile", C.byref(cam), x0, y0, w, h, d, C.c_void_p(0), 1)
+            return dev.download(d, np.empty((h, w, 3), dtype=np.float32)), t
 
     def render_aov(self, cam, ptrs, shard=None, stream=None, sync=True, sample_first=0):
         """rt_render_aov (rt_render_aov_samples for sample_first != 0).  ptrs: {"albedo", "normal", "depth", "hits", "prim"} →
         integer device address (missing / None: not written).  Returns the rt_timing."""
         b = _aov_struct(ptrs)
-        t = Timing()
-        self._apply_config()
         if sample_first:
-            _check(amd_lib().rt_render_aov_samples(self._h, C.byref(cam), C.byref(shard) if shard else None, sample_first, C.byref(b),
-                                                   C.c_void_p(stream or 0), 1 if sync else 0, C.byref(t)), "rt_render_aov_samples")
-            return t
-        _check(amd_lib().rt_render_aov(self._h, C.byref(cam), C.byref(shard) if shard else None, C.byref(b), C.c_void_p(stream or 0),
-                                       1 if sync else 0, C.byref(t)), "rt_render_aov")
-        return t
+            return self._call("rt_render_aov_samples", C.byref(cam), _ref(shard), sample_first, C.byref(b), *_stream_sync(stream, sync))
+        return self._call("rt_render_aov", C.byref(cam), _ref(shard), C.byref(b), *_stream_sync(stream, sync))
 
     def render_aov_to_host(self, cam, shard=None, tile=None, sample_first=0):
         """The AOVs of the frame, a shard of its rows or a tile (x0, y0, w, h) through fresh device buffers: ({"albedo": (rows, w, 3),
         "normal": (rows, w, 3), "depth": (rows, w), "hits": (rows, w) uint32, "prim": (rows, w) int32}, rt_timing).  sample_first
         != 0: samples sample_first … (rt_render_aov_samples; not for a tile)."""
-        lib = amd_lib()
         if tile is not None and sample_first:
             raise RtError("render_aov_to_host: a tile has no sample_first (rt_render_aov_samples renders rows)")
         if tile is not None:
             x0, y0, w, rows = tile
-        else:
-            w, rows = cam.image_width, lib.rt_shard_rows(cam.image_height, C.byref(shard) if shard else None)
-        pixels = max(w, 0) * max(rows, 0)
-        b = AovBuffers()
-        dev = {}
-        t = Timing()
-        try:
-            for key, field, dtype, per in AOV_CHANNELS:
-                d = C.c_void_p()
-                _check(lib.rt_device_alloc(pixels * per * 4 or 4, C.byref(d)), "rt_device_alloc")
-                dev[key] = d
-                setattr(b, field, d.value)
-            self._apply_config()
-            if tile is not None:
-                _check(lib.rt_render_aov_tile(self._h, C.byref(cam), x0, y0, w, rows, C.byref(b), C.c_void_p(0), 1, C.byref(t)), "rt_render_aov_tile")
-            elif sample_first:
-                _check(lib.rt_render_aov_samples(self._h, C.byref(cam), C.byref(shard) if shard else None, sample_first, C.byref(b), C.c_void_p(0),
-                                                 1, C.byref(t)), "rt_render_aov_samples")
-            else:
-                _check(lib.rt_render_aov(self._h, C.byref(cam), C.byref(shard) if shard else None, C.byref(b), C.c_void_p(0), 1, C.byref(t)),
-                       "rt_render_aov")
-            out = {}
-            for key, field, dtype, per in AOV_CHANNELS:
-                a = np.empty((rows, w, per) if per > 1 else (rows, w), dtype=dtype)
-                _check(lib.rt_copy_to_host(a.ctypes.data, dev[key], a.nbytes), "rt_copy_to_host")
-                out[key] = a
-        finally:
-            for d in dev.values():
-                lib.rt_device_free(d)
-        return out, t
+            return _aov_to_host(rows, w, lambda ptrs: self._call("rt_render_aov_tile", C.byref(cam), x0, y0, w, rows, C.byref(_aov_struct(ptrs)),
+                                                                 C.c_void_p(0), 1))
+        return _aov_to_host(amd_lib().rt_shard_rows(cam.image_height, _ref(shard)), cam.image_width,
+                            lambda ptrs: self.render_aov(cam, ptrs, shard=shard, sample_first=sample_first))
 
     def render_adaptive(self, cam, d_fb_ptr, d_spp_ptr, d_moments_ptr=None, shard=None, stream=None, sync=True, prior=None, **params):
         """rt_render_adaptive: d_fb_ptr (3 floats per pixel), d_spp_ptr (1 int32 per pixel), d_moments_ptr (None, or 2 floats per pixel)
@@ -1365,107 +1197,36 @@ class DeviceScene:
         floats per local pixel (rt_render_adaptive_prior, rule 0 unless given).  Returns the rt_timing."""
         rule = params.pop("rule", None)
         p = adaptive_params(**params)
-        t = Timing()
-        self._apply_config()
-        if prior is not None:
-            stop = stop_params(rule=rule or 0)
-            _check(amd_lib().rt_render_adaptive_prior(self._h, C.byref(cam), C.byref(shard) if shard else None, C.byref(p), C.byref(stop),
-                                                      C.c_void_p(d_fb_ptr), C.c_void_p(d_spp_ptr), C.c_void_p(d_moments_ptr or 0),
-                                                      C.c_void_p(stream or 0), 1 if sync else 0, C.byref(t), C.c_void_p(prior)),
-                   "rt_render_adaptive_prior")
-        elif rule is None:
-            _check(amd_lib().rt_render_adaptive(self._h, C.byref(cam), C.byref(shard) if shard else None, C.byref(p), C.c_void_p(d_fb_ptr),
-                                                C.c_void_p(d_spp_ptr), C.c_void_p(d_moments_ptr or 0), C.c_void_p(stream or 0), 1 if sync else 0,
-                                                C.byref(t)), "rt_render_adaptive")
-        else:
-            stop = stop_params(rule=rule)
-            _check(amd_lib().rt_render_adaptive_rule(self._h, C.byref(cam), C.byref(shard) if shard else None, C.byref(p), C.byref(stop),
-                                                     C.c_void_p(d_fb_ptr), C.c_void_p(d_spp_ptr), C.c_void_p(d_moments_ptr or 0),
-                                                     C.c_void_p(stream or 0), 1 if sync else 0, C.byref(t)), "rt_render_adaptive_rule")
-        return t
+        name, stop, after = _adaptive_entry("rt_render_adaptive", rule, prior)
+        return self._call(name, C.byref(cam), _ref(shard), C.byref(p), *stop, C.c_void_p(d_fb_ptr), C.c_void_p(d_spp_ptr),
+                          C.c_void_p(d_moments_ptr or 0), *_stream_sync(stream, sync), after=after)
 
     def render_adaptive_to_host(self, cam, shard=None, prior=None, **params):
         """rt_render_adaptive through fresh device buffers: (fb (rows, w, 3) float32 sums, spp (rows, w) int32, moments (rows, w, 2)
         float32 (S1, S2)) and the rt_timing.  prior: None or a host array (rows, w, 2) float32 (ch, vh)."""
-        lib = amd_lib()
-        rows = lib.rt_shard_rows(cam.image_height, C.byref(shard) if shard else None)
-        w = cam.image_width
-        fb = np.empty((rows, w, 3), dtype=np.float32)
-        spp = np.empty((rows, w), dtype=np.int32)
-        mom = np.empty((rows, w, 2), dtype=np.float32)
-        dev = []
-        try:
-            for a in (fb, spp, mom):
-                d = C.c_void_p()
-                _check(lib.rt_device_alloc(a.nbytes or 12, C.byref(d)), "rt_device_alloc")
-                dev.append(d)
-            if prior is not None:
-                dev.append(_upload(np.ascontiguousarray(np.asarray(prior, dtype=np.float32).reshape(rows, w, 2))))
-                params = {**params, "prior": dev[3].value}
-            t = self.render_adaptive(cam, dev[0].value, dev[1].value, dev[2].value, shard=shard, **params)
-            for a, d in zip((fb, spp, mom), dev):
-                _check(lib.rt_copy_to_host(a.ctypes.data, d, a.nbytes), "rt_copy_to_host")
-        finally:
-            for d in dev:
-                lib.rt_device_free(d)
-        return fb, spp, mom, t
+        return _adaptive_to_host(cam, shard, prior, lambda d_fb, d_spp, d_moments, d_prior: self.render_adaptive(
+            cam, d_fb, d_spp, d_moments, shard=shard, prior=d_prior, **params))
 
     def render_lens(self, cam_open, d_fb_ptr, cam_close=None, lens=None, shard=None, stream=None, sync=True, sample_first=0):
         """rt_render_lens: cam_close None = no motion; lens None (defaults), a LensParams or a dict of its fields.  Returns the
         rt_timing of this call."""
-        t = Timing()
-        self._apply_config()
-        _check(amd_lib().rt_render_lens(self._h, C.byref(cam_open), C.byref(cam_close) if cam_close is not None else None, _lens_struct(lens),
-                                        C.byref(shard) if shard else None, sample_first, C.c_void_p(d_fb_ptr), C.c_void_p(stream or 0),
-                                        1 if sync else 0, C.byref(t)), "rt_render_lens")
-        return t
+        return self._call("rt_render_lens", C.byref(cam_open), _ref(cam_close), _lens_struct(lens), _ref(shard), sample_first,
+                          C.c_void_p(d_fb_ptr), *_stream_sync(stream, sync))
 
     def render_lens_to_host(self, cam_open, cam_close=None, lens=None, shard=None, sample_first=0):
         """rt_render_lens through a fresh device buffer: (rows, width, 3) float32 sums and the rt_timing."""
-        lib = amd_lib()
-        rows = lib.rt_shard_rows(cam_open.image_height, C.byref(shard) if shard else None)
-        fb = np.empty((rows, cam_open.image_width, 3), dtype=np.float32)
-        d = C.c_void_p()
-        _check(lib.rt_device_alloc(fb.nbytes or 12, C.byref(d)), "rt_device_alloc")
-        try:
-            t = self.render_lens(cam_open, d.value, cam_close=cam_close, lens=lens, shard=shard, sample_first=sample_first)
-            _check(lib.rt_copy_to_host(fb.ctypes.data, d, fb.nbytes), "rt_copy_to_host")
-        finally:
-            lib.rt_device_free(d)
-        return fb, t
+        return _frame_to_host(cam_open, shard, lambda d: self.render_lens(cam_open, d, cam_close=cam_close, lens=lens, shard=shard,
+                                                                          sample_first=sample_first))
 
     def render_aov_lens(self, cam_open, ptrs, cam_close=None, lens=None, shard=None, stream=None, sync=True, sample_first=0):
         """rt_render_aov_lens.  ptrs as render_aov takes them.  Returns the rt_timing."""
-        b = _aov_struct(ptrs)
-        t = Timing()
-        self._apply_config()
-        _check(amd_lib().rt_render_aov_lens(self._h, C.byref(cam_open), C.byref(cam_close) if cam_close is not None else None,
-                                            _lens_struct(lens), C.byref(shard) if shard else None, sample_first, C.byref(b),
-                                            C.c_void_p(stream or 0), 1 if sync else 0, C.byref(t)), "rt_render_aov_lens")
-        return t
+        return self._call("rt_render_aov_lens", C.byref(cam_open), _ref(cam_close), _lens_struct(lens), _ref(shard), sample_first,
+                          C.byref(_aov_struct(ptrs)), *_stream_sync(stream, sync))
 
     def render_aov_lens_to_host(self, cam_open, cam_close=None, lens=None, shard=None, sample_first=0):
         """rt_render_aov_lens through fresh device buffers: (the dict render_aov_to_host returns, rt_timing)."""
-        lib = amd_lib()
-        w, rows = cam_open.image_width, lib.rt_shard_rows(cam_open.image_height, C.byref(shard) if shard else None)
-        pixels = max(w, 0) * max(rows, 0)
-        dev = {}
-        try:
-            for key, field, dtype, per in AOV_CHANNELS:
-                d = C.c_void_p()
-                _check(lib.rt_device_alloc(pixels * per * 4 or 4, C.byref(d)), "rt_device_alloc")
-                dev[key] = d
-            t = self.render_aov_lens(cam_open, {k: d.value for k, d in dev.items()}, cam_close=cam_close, lens=lens, shard=shard,
-                                     sample_first=sample_first)
-            out = {}
-            for key, field, dtype, per in AOV_CHANNELS:
-                a = np.empty((rows, w, per) if per > 1 else (rows, w), dtype=dtype)
-                _check(lib.rt_copy_to_host(a.ctypes.data, dev[key], a.nbytes), "rt_copy_to_host")
-                out[key] = a
-        finally:
-            for d in dev.values():
-                lib.rt_device_free(d)
-        return out, t
+        return _aov_to_host(amd_lib().rt_shard_rows(cam_open.image_height, _ref(shard)), cam_open.image_width,
+                            lambda ptrs: self.render_aov_lens(cam_open, ptrs, cam_close=cam_close, lens=lens, shard=shard, sample_first=sample_first))
 
     def lens_camera_rays(self, cam_open, cam_close, lens, ijs):
         """rt_lens_camera_rays (the module function lens_camera_rays: no scene involved, the current device)."""
@@ -1473,25 +1234,12 @@ class DeviceScene:
 
     def render_nee(self, cam, d_fb_ptr, params=None, shard=None, stream=None, sync=True, sample_first=0):
         """rt_render_nee: params None (defaults: mis = 1), a NeeParams or a dict of its fields.  Returns the rt_timing of this call."""
-        t = Timing()
-        self._apply_config()
-        _check(amd_lib().rt_render_nee(self._h, C.byref(cam), _nee_struct(params), C.byref(shard) if shard else None, sample_first,
-                                       C.c_void_p(d_fb_ptr), C.c_void_p(stream or 0), 1 if sync else 0, C.byref(t)), "rt_render_nee")
-        return t
+        return self._call("rt_render_nee", C.byref(cam), _nee_struct(params), _ref(shard), sample_first, C.c_void_p(d_fb_ptr),
+                          *_stream_sync(stream, sync))
 
     def render_nee_to_host(self, cam, params=None, shard=None, sample_first=0):
         """rt_render_nee through a fresh device buffer: (rows, width, 3) float32 sums and the rt_timing."""
-        lib = amd_lib()
-        rows = lib.rt_shard_rows(cam.image_height, C.byref(shard) if shard else None)
-        fb = np.empty((rows, cam.image_width, 3), dtype=np.float32)
-        d = C.c_void_p()
-        _check(lib.rt_device_alloc(fb.nbytes or 12, C.byref(d)), "rt_device_alloc")
-        try:
-            t = self.render_nee(cam, d.value, params=params, shard=shard, sample_first=sample_first)
-            _check(lib.rt_copy_to_host(fb.ctypes.data, d, fb.nbytes), "rt_copy_to_host")
-        finally:
-            lib.rt_device_free(d)
-        return fb, t
+        return _frame_to_host(cam, shard, lambda d: self.render_nee(cam, d, params=params, shard=shard, sample_first=sample_first))
 
     def nee_light_table(self):
         """rt_nee_light_table: (sphere indices int32, cdf float32, pmf float32) of the handle's emitter table."""
@@ -1539,76 +1287,39 @@ class DeviceScene:
 
     def trace_samples_nee(self, cam, ijs, params=None):
         """rt_trace_samples_nee: ijs (n, 3) → (radiance (n, 3), rays (n,), final seeds (n,), final light-sample seeds (n,))."""
-        ijs = np.ascontiguousarray(ijs, dtype=np.int32).reshape(-1, 3)
-        n = ijs.shape[0]
-        rad = np.empty((n, 3), dtype=np.float32)
-        rays = np.empty(n, dtype=np.int32)
-        seeds = np.empty(n, dtype=np.uint32)
-        nee = np.empty(n, dtype=np.uint32)
-        _check(amd_lib().rt_trace_samples_nee(self._h, C.byref(cam), _nee_struct(params), n, ijs.ctypes.data, rad.ctypes.data,
-                                              rays.ctypes.data, seeds.ctypes.data, nee.ctypes.data), "rt_trace_samples_nee")
-        return rad, rays, seeds, nee
+        ijs, n, out = _probe(ijs, _RGB, _COUNT, _SEED, _SEED)
+        _check(amd_lib().rt_trace_samples_nee(self._h, C.byref(cam), _nee_struct(params), n, ijs.ctypes.data, *(a.ctypes.data for a in out)),
+               "rt_trace_samples_nee")
+        return out
 
     def render_env(self, cam, env, d_fb_ptr, params=None, shard=None, stream=None, sync=True, sample_first=0):
         """rt_render_env: env an Env; params None (defaults: MIS, scale 1, no rotation), an EnvParams or a dict of its fields.  Returns the
         rt_timing of this call."""
-        t = Timing()
-        self._apply_config()
-        _check(amd_lib().rt_render_env(self._h, C.byref(cam), env._h, _env_struct(params), C.byref(shard) if shard else None, sample_first,
-                                       C.c_void_p(d_fb_ptr), C.c_void_p(stream or 0), 1 if sync else 0, C.byref(t)), "rt_render_env")
-        return t
+        return self._call("rt_render_env", C.byref(cam), env._h, _env_struct(params), _ref(shard), sample_first, C.c_void_p(d_fb_ptr),
+                          *_stream_sync(stream, sync))
 
     def render_env_to_host(self, cam, env, params=None, shard=None, sample_first=0):
         """rt_render_env through a fresh device buffer: (rows, width, 3) float32 sums and the rt_timing."""
-        lib = amd_lib()
-        rows = lib.rt_shard_rows(cam.image_height, C.byref(shard) if shard else None)
-        fb = np.empty((rows, cam.image_width, 3), dtype=np.float32)
-        d = C.c_void_p()
-        _check(lib.rt_device_alloc(fb.nbytes or 12, C.byref(d)), "rt_device_alloc")
-        try:
-            t = self.render_env(cam, env, d.value, params=params, shard=shard, sample_first=sample_first)
-            _check(lib.rt_copy_to_host(fb.ctypes.data, d, fb.nbytes), "rt_copy_to_host")
-        finally:
-            lib.rt_device_free(d)
-        return fb, t
+        return _frame_to_host(cam, shard, lambda d: self.render_env(cam, env, d, params=params, shard=shard, sample_first=sample_first))
 
     def trace_samples_env(self, cam, env, ijs, params=None):
         """rt_trace_samples_env: ijs (n, 3) → (radiance (n, 3), rays (n,), final seeds (n,), final light-sample seeds (n,))."""
-        ijs = np.ascontiguousarray(ijs, dtype=np.int32).reshape(-1, 3)
-        n = ijs.shape[0]
-        rad = np.empty((n, 3), dtype=np.float32)
-        rays = np.empty(n, dtype=np.int32)
-        seeds = np.empty(n, dtype=np.uint32)
-        es = np.empty(n, dtype=np.uint32)
-        _check(amd_lib().rt_trace_samples_env(self._h, C.byref(cam), env._h, _env_struct(params), n, ijs.ctypes.data, rad.ctypes.data,
-                                              rays.ctypes.data, seeds.ctypes.data, es.ctypes.data), "rt_trace_samples_env")
-        return rad, rays, seeds, es
+        ijs, n, out = _probe(ijs, _RGB, _COUNT, _SEED, _SEED)
+        _check(amd_lib().rt_trace_samples_env(self._h, C.byref(cam), env._h, _env_struct(params), n, ijs.ctypes.data,
+                                              *(a.ctypes.data for a in out)), "rt_trace_samples_env")
+        return out
 
     def render_lit(self, cam, d_fb_ptr, *, cam_close=None, lens=None, emitters=True, nee=None, env=None, env_params=None, shard=None,
                    stream=None, sync=True, sample_first=0):
         """rt_render_lit: emitters, environment and lens in one frame (lit_params()'s arguments).  Returns the rt_timing of this call."""
-        t = Timing()
-        self._apply_config()
         lit = lit_params(cam_close=cam_close, lens=lens, emitters=emitters, nee=nee, env=env, env_params=env_params)
-        _check(amd_lib().rt_render_lit(self._h, C.byref(cam), C.byref(lit), C.byref(shard) if shard else None, sample_first,
-                                       C.c_void_p(d_fb_ptr), C.c_void_p(stream or 0), 1 if sync else 0, C.byref(t)), "rt_render_lit")
-        return t
+        return self._call("rt_render_lit", C.byref(cam), C.byref(lit), _ref(shard), sample_first, C.c_void_p(d_fb_ptr), *_stream_sync(stream, sync))
 
     def render_lit_to_host(self, cam, *, cam_close=None, lens=None, emitters=True, nee=None, env=None, env_params=None, shard=None,
                            sample_first=0):
         """rt_render_lit through a fresh device buffer: (rows, width, 3) float32 sums and the rt_timing."""
-        lib = amd_lib()
-        rows = lib.rt_shard_rows(cam.image_height, C.byref(shard) if shard else None)
-        fb = np.empty((rows, cam.image_width, 3), dtype=np.float32)
-        d = C.c_void_p()
-        _check(lib.rt_device_alloc(fb.nbytes or 12, C.byref(d)), "rt_device_alloc")
-        try:
-            t = self.render_lit(cam, d.value, cam_close=cam_close, lens=lens, emitters=emitters, nee=nee, env=env, env_params=env_params,
-                                shard=shard, sample_first=sample_first)
-            _check(lib.rt_copy_to_host(fb.ctypes.data, d, fb.nbytes), "rt_copy_to_host")
-        finally:
-            lib.rt_device_free(d)
-        return fb, t
+        return _frame_to_host(cam, shard, lambda d: self.render_lit(cam, d, cam_close=cam_close, lens=lens, emitters=emitters, nee=nee, env=env, env_params=env_params, shard=shard,
+                                                                    sample_first=sample_first))
 
     def render_lit_adaptive(self, cam, d_fb_ptr, d_spp_ptr, d_moments_ptr=None, *, cam_close=None, lens=None, emitters=True, nee=None, env=None,
                             env_params=None, shard=None, stream=None, sync=True, sample_first=0, prior=None, **params):
@@ -1619,136 +1330,64 @@ class DeviceScene:
         pixel (rt_render_lit_adaptive_prior, rule 0 unless given).  Returns the rt_timing of this call."""
         rule = params.pop("rule", None)
         p = adaptive_params(**params)
-        t = Timing()
-        self._apply_config()
         lit = lit_params(cam_close=cam_close, lens=lens, emitters=emitters, nee=nee, env=env, env_params=env_params)
-        if prior is not None:
-            stop = stop_params(rule=rule or 0)
-            _check(amd_lib().rt_render_lit_adaptive_prior(self._h, C.byref(cam), C.byref(lit), C.byref(p), C.byref(stop),
-                                                          C.byref(shard) if shard else None, sample_first, C.c_void_p(d_fb_ptr), C.c_void_p(d_spp_ptr),
-                                                          C.c_void_p(d_moments_ptr or 0), C.c_void_p(stream or 0), 1 if sync else 0, C.byref(t),
-                                                          C.c_void_p(prior)), "rt_render_lit_adaptive_prior")
-        elif rule is None:
-            _check(amd_lib().rt_render_lit_adaptive(self._h, C.byref(cam), C.byref(lit), C.byref(p), C.byref(shard) if shard else None, sample_first,
-                                                    C.c_void_p(d_fb_ptr), C.c_void_p(d_spp_ptr), C.c_void_p(d_moments_ptr or 0),
-                                                    C.c_void_p(stream or 0), 1 if sync else 0, C.byref(t)), "rt_render_lit_adaptive")
-        else:
-            stop = stop_params(rule=rule)
-            _check(amd_lib().rt_render_lit_adaptive_rule(self._h, C.byref(cam), C.byref(lit), C.byref(p), C.byref(stop),
-                                                         C.byref(shard) if shard else None, sample_first, C.c_void_p(d_fb_ptr), C.c_void_p(d_spp_ptr),
-                                                         C.c_void_p(d_moments_ptr or 0), C.c_void_p(stream or 0), 1 if sync else 0, C.byref(t)),
-                   "rt_render_lit_adaptive_rule")
-        return t
+        name, stop, after = _adaptive_entry("rt_render_lit_adaptive", rule, prior)
+        return self._call(name, C.byref(cam), C.byref(lit), C.byref(p), *stop, _ref(shard), sample_first, C.c_void_p(d_fb_ptr), C.c_void_p(d_spp_ptr),
+                          C.c_void_p(d_moments_ptr or 0), *_stream_sync(stream, sync), after=after)
 
     def render_lit_adaptive_to_host(self, cam, *, cam_close=None, lens=None, emitters=True, nee=None, env=None, env_params=None, shard=None,
                                     sample_first=0, prior=None, **params):
         """rt_render_lit_adaptive through fresh device buffers: (fb (rows, w, 3) float32 sums, spp (rows, w) int32, moments (rows, w, 2)
         float32 (S1, S2)) and the rt_timing.  prior: None or a host array (rows, w, 2) float32 (ch, vh)."""
-        lib = amd_lib()
-        rows = lib.rt_shard_rows(cam.image_height, C.byref(shard) if shard else None)
-        w = cam.image_width
-        fb = np.empty((rows, w, 3), dtype=np.float32)
-        spp = np.empty((rows, w), dtype=np.int32)
-        mom = np.empty((rows, w, 2), dtype=np.float32)
-        dev = []
-        try:
-            for a in (fb, spp, mom):
-                d = C.c_void_p()
-                _check(lib.rt_device_alloc(a.nbytes or 12, C.byref(d)), "rt_device_alloc")
-                dev.append(d)
-            if prior is not None:
-                dev.append(_upload(np.ascontiguousarray(np.asarray(prior, dtype=np.float32).reshape(rows, w, 2))))
-                params = {**params, "prior": dev[3].value}
-            t = self.render_lit_adaptive(cam, dev[0].value, dev[1].value, dev[2].value, cam_close=cam_close, lens=lens, emitters=emitters, nee=nee,
-                                         env=env, env_params=env_params, shard=shard, sample_first=sample_first, **params)
-            for a, d in zip((fb, spp, mom), dev):
-                _check(lib.rt_copy_to_host(a.ctypes.data, d, a.nbytes), "rt_copy_to_host")
-        finally:
-            for d in dev:
-                lib.rt_device_free(d)
-        return fb, spp, mom, t
+        return _adaptive_to_host(cam, shard, prior, lambda d_fb, d_spp, d_moments, d_prior: self.render_lit_adaptive(
+            cam, d_fb, d_spp, d_moments, cam_close=cam_close, lens=lens, emitters=emitters, nee=nee, env=env, env_params=env_params, shard=shard,
+            sample_first=sample_first, prior=d_prior, **params))
 
     def trace_samples_lit(self, cam, ijs, *, cam_close=None, lens=None, emitters=True, nee=None, env=None, env_params=None):
         """rt_trace_samples_lit: ijs (n, 3) → (radiance (n, 3), rays (n,), final seeds (n,), final emitter-stream seeds (n,), final
         environment-stream seeds (n,))."""
-        ijs = np.ascontiguousarray(ijs, dtype=np.int32).reshape(-1, 3)
-        n = ijs.shape[0]
-        rad = np.empty((n, 3), dtype=np.float32)
-        rays = np.empty(n, dtype=np.int32)
-        seeds, ns, es = np.empty(n, dtype=np.uint32), np.empty(n, dtype=np.uint32), np.empty(n, dtype=np.uint32)
+        ijs, n, out = _probe(ijs, _RGB, _COUNT, _SEED, _SEED, _SEED)
         lit = lit_params(cam_close=cam_close, lens=lens, emitters=emitters, nee=nee, env=env, env_params=env_params)
-        _check(amd_lib().rt_trace_samples_lit(self._h, C.byref(cam), C.byref(lit), n, ijs.ctypes.data, rad.ctypes.data, rays.ctypes.data,
-                                              seeds.ctypes.data, ns.ctypes.data, es.ctypes.data), "rt_trace_samples_lit")
-        return rad, rays, seeds, ns, es
+        _check(amd_lib().rt_trace_samples_lit(self._h, C.byref(cam), C.byref(lit), n, ijs.ctypes.data, *(a.ctypes.data for a in out)),
+               "rt_trace_samples_lit")
+        return out
 
     def render_medium(self, cam, d_fb_ptr, *, medium=None, cam_close=None, lens=None, emitters=True, nee=None, env=None, env_params=None, shard=None,
                       stream=None, sync=True, sample_first=0):
         """rt_render_medium: rt_render_lit under a homogeneous medium (medium: None, a MediumParams or a dict of medium_params()'s
         arguments; the other keywords are lit_params()'s).  Returns the rt_timing of this call."""
-        t = Timing()
-        self._apply_config()
         lit = lit_params(cam_close=cam_close, lens=lens, emitters=emitters, nee=nee, env=env, env_params=env_params)
-        _check(amd_lib().rt_render_medium(self._h, C.byref(cam), C.byref(lit), _medium_struct(medium), C.byref(shard) if shard else None, sample_first,
-                                          C.c_void_p(d_fb_ptr), C.c_void_p(stream or 0), 1 if sync else 0, C.byref(t)), "rt_render_medium")
-        return t
+        return self._call("rt_render_medium", C.byref(cam), C.byref(lit), _medium_struct(medium), _ref(shard), sample_first, C.c_void_p(d_fb_ptr),
+                          *_stream_sync(stream, sync))
 
     def render_medium_to_host(self, cam, *, medium=None, cam_close=None, lens=None, emitters=True, nee=None, env=None, env_params=None, shard=None,
                               sample_first=0):
         """rt_render_medium through a fresh device buffer: (rows, width, 3) float32 sums and the rt_timing."""
-        lib = amd_lib()
-        rows = lib.rt_shard_rows(cam.image_height, C.byref(shard) if shard else None)
-        fb = np.empty((rows, cam.image_width, 3), dtype=np.float32)
-        d = C.c_void_p()
-        _check(lib.rt_device_alloc(fb.nbytes or 12, C.byref(d)), "rt_device_alloc")
-        try:
-            t = self.render_medium(cam, d.value, medium=medium, cam_close=cam_close, lens=lens, emitters=emitters, nee=nee, env=env,
-                                   env_params=env_params, shard=shard, sample_first=sample_first)
-            _check(lib.rt_copy_to_host(fb.ctypes.data, d, fb.nbytes), "rt_copy_to_host")
-        finally:
-            lib.rt_device_free(d)
-        return fb, t
+        return _frame_to_host(cam, shard, lambda d: self.render_medium(cam, d, medium=medium, cam_close=cam_close, lens=lens, emitters=emitters, nee=nee, env=env, env_params=env_params,
+                                                                       shard=shard, sample_first=sample_first))
 
     def trace_samples_medium(self, cam, ijs, *, medium=None, cam_close=None, lens=None, emitters=True, nee=None, env=None, env_params=None):
         """rt_trace_samples_medium: ijs (n, 3) → (radiance (n, 3), rays (n,), medium events (n,), final seeds (n,), final emitter-stream
         seeds (n,), final environment-stream seeds (n,), final medium-stream seeds (n,))."""
-        ijs = np.ascontiguousarray(ijs, dtype=np.int32).reshape(-1, 3)
-        n = ijs.shape[0]
-        rad = np.empty((n, 3), dtype=np.float32)
-        rays, events = np.empty(n, dtype=np.int32), np.empty(n, dtype=np.int32)
-        seeds, ns, es, ms = (np.empty(n, dtype=np.uint32) for _ in range(4))
+        ijs, n, out = _probe(ijs, _RGB, _COUNT, _COUNT, _SEED, _SEED, _SEED, _SEED)
         lit = lit_params(cam_close=cam_close, lens=lens, emitters=emitters, nee=nee, env=env, env_params=env_params)
-        _check(amd_lib().rt_trace_samples_medium(self._h, C.byref(cam), C.byref(lit), _medium_struct(medium), n, ijs.ctypes.data, rad.ctypes.data,
-                                                 rays.ctypes.data, events.ctypes.data, seeds.ctypes.data, ns.ctypes.data, es.ctypes.data,
-                                                 ms.ctypes.data), "rt_trace_samples_medium")
-        return rad, rays, events, seeds, ns, es, ms
+        _check(amd_lib().rt_trace_samples_medium(self._h, C.byref(cam), C.byref(lit), _medium_struct(medium), n, ijs.ctypes.data,
+                                                 *(a.ctypes.data for a in out)), "rt_trace_samples_medium")
+        return out
 
     def render_volume(self, cam, d_fb_ptr, *, medium=None, volume=None, cam_close=None, lens=None, emitters=True, nee=None, env=None, env_params=None,
                       shard=None, stream=None, sync=True, sample_first=0):
         """rt_render_volume: rt_render_medium with a density grid in the medium's box (volume: None or a Volume; the other keywords are
         render_medium's).  Returns the rt_timing of this call."""
-        t = Timing()
-        self._apply_config()
         lit = lit_params(cam_close=cam_close, lens=lens, emitters=emitters, nee=nee, env=env, env_params=env_params)
-        _check(amd_lib().rt_render_volume(self._h, C.byref(cam), C.byref(lit), _medium_struct(medium), _volume_handle(volume),
-                                          C.byref(shard) if shard else None, sample_first, C.c_void_p(d_fb_ptr), C.c_void_p(stream or 0),
-                                          1 if sync else 0, C.byref(t)), "rt_render_volume")
-        return t
+        return self._call("rt_render_volume", C.byref(cam), C.byref(lit), _medium_struct(medium), _volume_handle(volume), _ref(shard), sample_first,
+                          C.c_void_p(d_fb_ptr), *_stream_sync(stream, sync))
 
     def render_volume_to_host(self, cam, *, medium=None, volume=None, cam_close=None, lens=None, emitters=True, nee=None, env=None, env_params=None,
                               shard=None, sample_first=0):
         """rt_render_volume through a fresh device buffer: (rows, width, 3) float32 sums and the rt_timing."""
-        lib = amd_lib()
-        rows = lib.rt_shard_rows(cam.image_height, C.byref(shard) if shard else None)
-        fb = np.empty((rows, cam.image_width, 3), dtype=np.float32)
-        d = C.c_void_p()
-        _check(lib.rt_device_alloc(fb.nbytes or 12, C.byref(d)), "rt_device_alloc")
-        try:
-            t = self.render_volume(cam, d.value, medium=medium, volume=volume, cam_close=cam_close, lens=lens, emitters=emitters, nee=nee, env=env,
-                                   env_params=env_params, shard=shard, sample_first=sample_first)
-            _check(lib.rt_copy_to_host(fb.ctypes.data, d, fb.nbytes), "rt_copy_to_host")
-        finally:
-            lib.rt_device_free(d)
-        return fb, t
+        return _frame_to_host(cam, shard, lambda d: self.render_volume(cam, d, medium=medium, volume=volume, cam_close=cam_close, lens=lens, emitters=emitters, nee=nee, env=env, env_params=env_params,
+                                                                       shard=shard, sample_first=sample_first))
 
     def render_volume_adaptive(self, cam, d_fb_ptr, d_spp_ptr, d_moments_ptr=None, *, medium=None, volume=None, cam_close=None, lens=None,
                                emitters=True, nee=None, env=None, env_params=None, shard=None, stream=None, sync=True, sample_first=0, prior=None,
@@ -1758,57 +1397,27 @@ class DeviceScene:
         rt_stop_params); prior: None, or the device address of 2 floats per local pixel.  Returns the rt_timing of this call."""
         rule = params.pop("rule", None)
         p = adaptive_params(**params)
-        t = Timing()
-        self._apply_config()
         lit = lit_params(cam_close=cam_close, lens=lens, emitters=emitters, nee=nee, env=env, env_params=env_params)
         stop = None if rule is None else C.byref(stop_params(rule=rule))
-        _check(amd_lib().rt_render_volume_adaptive(self._h, C.byref(cam), C.byref(lit), _medium_struct(medium), _volume_handle(volume), C.byref(p), stop,
-                                                   C.c_void_p(prior or 0), C.byref(shard) if shard else None, sample_first, C.c_void_p(d_fb_ptr),
-                                                   C.c_void_p(d_spp_ptr), C.c_void_p(d_moments_ptr or 0), C.c_void_p(stream or 0),
-                                                   1 if sync else 0, C.byref(t)), "rt_render_volume_adaptive")
-        return t
+        return self._call("rt_render_volume_adaptive", C.byref(cam), C.byref(lit), _medium_struct(medium), _volume_handle(volume), C.byref(p), stop,
+                          C.c_void_p(prior or 0), _ref(shard), sample_first, C.c_void_p(d_fb_ptr), C.c_void_p(d_spp_ptr),
+                          C.c_void_p(d_moments_ptr or 0), *_stream_sync(stream, sync))
 
     def render_volume_adaptive_to_host(self, cam, *, medium=None, volume=None, cam_close=None, lens=None, emitters=True, nee=None, env=None,
                                        env_params=None, shard=None, sample_first=0, prior=None, **params):
         """rt_render_volume_adaptive through fresh device buffers: (fb (rows, w, 3) float32 sums, spp (rows, w) int32, moments (rows, w, 2)
         float32 (S1, S2)) and the rt_timing.  prior: None or a host array (rows, w, 2) float32 (ch, vh)."""
-        lib = amd_lib()
-        rows = lib.rt_shard_rows(cam.image_height, C.byref(shard) if shard else None)
-        w = cam.image_width
-        fb = np.empty((rows, w, 3), dtype=np.float32)
-        spp = np.empty((rows, w), dtype=np.int32)
-        mom = np.empty((rows, w, 2), dtype=np.float32)
-        dev = []
-        try:
-            for a in (fb, spp, mom):
-                d = C.c_void_p()
-                _check(lib.rt_device_alloc(a.nbytes or 12, C.byref(d)), "rt_device_alloc")
-                dev.append(d)
-            if prior is not None:
-                dev.append(_upload(np.ascontiguousarray(np.asarray(prior, dtype=np.float32).reshape(rows, w, 2))))
-                params = {**params, "prior": dev[3].value}
-            t = self.render_volume_adaptive(cam, dev[0].value, dev[1].value, dev[2].value, medium=medium, volume=volume, cam_close=cam_close, lens=lens,
-                                            emitters=emitters, nee=nee, env=env, env_params=env_params, shard=shard, sample_first=sample_first,
-                                            **params)
-            for a, d in zip((fb, spp, mom), dev):
-                _check(lib.rt_copy_to_host(a.ctypes.data, d, a.nbytes), "rt_copy_to_host")
-        finally:
-            for d in dev:
-                lib.rt_device_free(d)
-        return fb, spp, mom, t
+        return _adaptive_to_host(cam, shard, prior, lambda d_fb, d_spp, d_moments, d_prior: self.render_volume_adaptive(
+            cam, d_fb, d_spp, d_moments, medium=medium, volume=volume, cam_close=cam_close, lens=lens, emitters=emitters, nee=nee, env=env, env_params=env_params,
+            shard=shard, sample_first=sample_first, prior=d_prior, **params))
 
     def trace_samples_volume(self, cam, ijs, *, medium=None, volume=None, cam_close=None, lens=None, emitters=True, nee=None, env=None, env_params=None):
         """rt_trace_samples_volume: trace_samples_medium's seven columns and the grid cells visited per sample (n,)."""
-        ijs = np.ascontiguousarray(ijs, dtype=np.int32).reshape(-1, 3)
-        n = ijs.shape[0]
-        rad = np.empty((n, 3), dtype=np.float32)
-        rays, events, cells = (np.empty(n, dtype=np.int32) for _ in range(3))
-        seeds, ns, es, ms = (np.empty(n, dtype=np.uint32) for _ in range(4))
+        ijs, n, out = _probe(ijs, _RGB, _COUNT, _COUNT, _SEED, _SEED, _SEED, _SEED, _COUNT)
         lit = lit_params(cam_close=cam_close, lens=lens, emitters=emitters, nee=nee, env=env, env_params=env_params)
-        _check(amd_lib().rt_trace_samples_volume(self._h, C.byref(cam), C.byref(lit), _medium_struct(medium), _volume_handle(volume), n, ijs.ctypes.data,
-                                                 rad.ctypes.data, rays.ctypes.data, events.ctypes.data, seeds.ctypes.data, ns.ctypes.data,
-                                                 es.ctypes.data, ms.ctypes.data, cells.ctypes.data), "rt_trace_samples_volume")
-        return rad, rays, events, seeds, ns, es, ms, cells
+        _check(amd_lib().rt_trace_samples_volume(self._h, C.byref(cam), C.byref(lit), _medium_struct(medium), _volume_handle(volume), n,
+                                                 ijs.ctypes.data, *(a.ctypes.data for a in out)), "rt_trace_samples_volume")
+        return out
 
     def last_kernel_ms(self):
         ms = C.c_float()
@@ -1836,14 +1445,9 @@ class DeviceScene:
                 f"{'true' if t.primary_visibility else 'false'}>(rtk::KParams)")
 
     def trace_samples(self, cam, ijs):
-        ijs = np.ascontiguousarray(ijs, dtype=np.int32).reshape(-1, 3)
-        n = ijs.shape[0]
-        rad = np.empty((n, 3), dtype=np.float32)
-        rays = np.empty(n, dtype=np.int32)
-        seeds = np.empty(n, dtype=np.uint32)
-        _check(amd_lib().rt_trace_samples(self._h, C.byref(cam), n, ijs.ctypes.data, rad.ctypes.data, rays.ctypes.data,
-                                          seeds.ctypes.data), "rt_trace_samples")
-        return rad, rays, seeds
+        ijs, n, out = _probe(ijs, _RGB, _COUNT, _SEED)
+        _check(amd_lib().rt_trace_samples(self._h, C.byref(cam), n, ijs.ctypes.data, *(a.ctypes.data for a in out)), "rt_trace_samples")
+        return out
 
     def guard_reason(self):
         """'' when rt_render may use the guarded near-first walk, else why not."""

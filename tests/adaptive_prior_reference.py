@@ -4,33 +4,23 @@ again, built into a shared library (gcc -ffp-contract=off -fno-fast-math, like d
 needed, in a temporary directory.  The judgement with a prior: numpy float32, one operation at a time; reference() and
 from_radiances() take a prior and otherwise mirror adaptive_rule_reference.py."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
 import adaptive_rule_reference as arr
+import cpu_ref
 import test_adaptive as ta
 from denoise_temporal_reference import history_bytes
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 F = np.float32
 MIN_ALPHA = F(0.2)
-_lib = None
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        out = os.path.join(tempfile.mkdtemp(prefix="adaptive_prior_ref_"), "libadaptive_prior_ref.so")
-        subprocess.run(["gcc", "-O2", "-std=gnu11", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-w", "-o", out,
-                        os.path.join(HERE, "cpu_native", "adaptive_prior_ref.c"), "-lm"], check=True)
-        l = C.CDLL(out)
-        l.adaptive_prior_reference.restype = C.c_int
-        l.adaptive_prior_reference.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 7
-        _lib = l
-    return _lib
+    l = cpu_ref.build("adaptive_prior_ref.c")
+    l.adaptive_prior_reference.restype = C.c_int
+    l.adaptive_prior_reference.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 7
+    return l
 
 
 def prior(aov, aov_spp, cam, history_prev=None):

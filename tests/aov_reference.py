@@ -3,32 +3,19 @@ orc_get_ray, orc_geom_hit_bvh (rec9 = t, point, normal, u, v) and orc_tex2d — 
 (gcc -ffp-contract=off, like the oracle) the first time it is needed, in a temporary directory.  Threads split the pixels;
 every pixel is still computed in sample order."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
+import cpu_ref
 import rtp_bindings as rb
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-_lib = None
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        out = os.path.join(tempfile.mkdtemp(prefix="aov_ref_"), "libaov_ref.so")
-        subprocess.run(["gcc", "-O2", "-std=gnu11", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-w", "-o", out,
-                        os.path.join(HERE, "cpu_native", "aov_ref.c"), os.path.join(ROOT, "oracle", "rt_oracle.c"), "-lm", "-lpthread"],
-                       check=True)
-        l = C.CDLL(out)
-        l.aov_reference.restype = C.c_int64
-        l.aov_reference.argtypes = [C.POINTER(rb.SceneDesc), C.POINTER(rb.CameraData), C.c_int64, C.c_void_p, C.c_int,
-                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        _lib = l
-    return _lib
+    l = cpu_ref.build("aov_ref.c", "oracle/rt_oracle.c")
+    l.aov_reference.restype = C.c_int64
+    l.aov_reference.argtypes = [C.POINTER(rb.SceneDesc), C.POINTER(rb.CameraData), C.c_int64, C.c_void_p, C.c_int,
+                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    return l
 
 
 def image_rows(cam, shard=None):

@@ -2,29 +2,19 @@
 expf, built into a shared library (gcc -ffp-contract=off -fno-fast-math, like aov_reference.py builds aov_ref.c) the first time it
 is needed, in a temporary directory.  Threads split the rows of each pass."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-_lib = None
+import cpu_ref
 
 DEFAULTS = {"iterations": 5, "sigma_depth": 1.0, "sigma_luminance": 4.0, "normal_squarings": 7}
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        out = os.path.join(tempfile.mkdtemp(prefix="denoise_ref_"), "libdenoise_ref.so")
-        subprocess.run(["gcc", "-O2", "-std=gnu11", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-w", "-o", out,
-                        os.path.join(HERE, "cpu_native", "denoise_ref.c"), "-lm", "-lpthread"], check=True)
-        l = C.CDLL(out)
-        l.denoise_reference.restype = C.c_int
-        l.denoise_reference.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int] + [C.c_void_p] * 6 + [C.c_int]
-        _lib = l
-    return _lib
+    l = cpu_ref.build("denoise_ref.c")
+    l.denoise_reference.restype = C.c_int
+    l.denoise_reference.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int] + [C.c_void_p] * 6 + [C.c_int]
+    return l
 
 
 def reference(fb_sum, aov, spp, threads=16, **params):

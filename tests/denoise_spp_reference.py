@@ -2,29 +2,18 @@
 libm's expf on top of denoise_ref.c's passes, built into a shared library (gcc -ffp-contract=off -fno-fast-math, like
 denoise_reference.py) the first time it is needed, in a temporary directory."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
+import cpu_ref
 from denoise_reference import DEFAULTS
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-_lib = None
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        out = os.path.join(tempfile.mkdtemp(prefix="denoise_spp_ref_"), "libdenoise_spp_ref.so")
-        subprocess.run(["gcc", "-O2", "-std=gnu11", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-w", "-o", out,
-                        os.path.join(HERE, "cpu_native", "denoise_spp_ref.c"), "-lm", "-lpthread"], check=True)
-        l = C.CDLL(out)
-        l.denoise_spp_reference.restype = C.c_int
-        l.denoise_spp_reference.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int] + [C.c_void_p] * 9 + [C.c_int]
-        _lib = l
-    return _lib
+    l = cpu_ref.build("denoise_spp_ref.c")
+    l.denoise_spp_reference.restype = C.c_int
+    l.denoise_spp_reference.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int] + [C.c_void_p] * 9 + [C.c_int]
+    return l
 
 
 def reference(fb_sum, spp, moments, aov, aov_spp, threads=16, want_var=False, **params):

@@ -2,30 +2,20 @@
 restated with libm's expf on top of denoise_ref.c's spatial passes, built into a shared library (gcc -ffp-contract=off
 -fno-fast-math, like denoise_reference.py) the first time it is needed, in a temporary directory."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
+import cpu_ref
 from denoise_reference import DEFAULTS
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 HEADER_BYTES = 256
-_lib = None
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        out = os.path.join(tempfile.mkdtemp(prefix="denoise_temporal_ref_"), "libdenoise_temporal_ref.so")
-        subprocess.run(["gcc", "-O2", "-std=gnu11", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-w", "-o", out,
-                        os.path.join(HERE, "cpu_native", "denoise_temporal_ref.c"), "-lm", "-lpthread"], check=True)
-        l = C.CDLL(out)
-        l.denoise_temporal_reference.restype = C.c_int
-        l.denoise_temporal_reference.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int] + [C.c_void_p] * 9 + [C.c_int]
-        _lib = l
-    return _lib
+    l = cpu_ref.build("denoise_temporal_ref.c")
+    l.denoise_temporal_reference.restype = C.c_int
+    l.denoise_temporal_reference.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int] + [C.c_void_p] * 9 + [C.c_int]
+    return l
 
 
 def history_bytes(width, height):

@@ -3,17 +3,12 @@ without an environment — (TEST INFRASTRUCTURE): tests/cpu_native/emit_ref.c, w
 oracle/rt_oracle.c (its ray_color and hit_bvh are static), built into a shared library (gcc -ffp-contract=off, like the oracle) the
 first time it is needed, in a temporary directory.  Threads split the rows; every pixel is still summed in sample order."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
+import cpu_ref
 import env_reference as er
 import rtp_bindings as rb
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-_lib = None
 
 
 class EmitCfg(C.Structure):
@@ -24,23 +19,17 @@ class EmitCfg(C.Structure):
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        out = os.path.join(tempfile.mkdtemp(prefix="emit_ref_"), "libemit_ref.so")
-        subprocess.run(["gcc", "-O2", "-std=gnu11", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-w", "-o", out,
-                        os.path.join(HERE, "cpu_native", "emit_ref.c"), "-lm", "-lpthread"], check=True)
-        l = C.CDLL(out)
-        desc, cam, cfg = C.POINTER(rb.SceneDesc), C.POINTER(rb.CameraData), C.POINTER(EmitCfg)
-        l.emit_trace.restype = None
-        l.emit_trace.argtypes = [desc, cam, cfg, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
-        l.emit_frame.restype = None
-        l.emit_frame.argtypes = [desc, cam, cfg, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        l.emit_table.restype = C.c_int32
-        l.emit_table.argtypes = [desc, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        l.emit_first_hit.restype = None
-        l.emit_first_hit.argtypes = [desc, cam, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        _lib = l
-    return _lib
+    l = cpu_ref.build("emit_ref.c")
+    desc, cam, cfg = C.POINTER(rb.SceneDesc), C.POINTER(rb.CameraData), C.POINTER(EmitCfg)
+    l.emit_trace.restype = None
+    l.emit_trace.argtypes = [desc, cam, cfg, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+    l.emit_frame.restype = None
+    l.emit_frame.argtypes = [desc, cam, cfg, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    l.emit_table.restype = C.c_int32
+    l.emit_table.argtypes = [desc, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    l.emit_first_hit.restype = None
+    l.emit_first_hit.argtypes = [desc, cam, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    return l
 
 
 image_rows = er.image_rows

@@ -3,41 +3,30 @@ tests/cpu_native/env_ref.c, which includes oracle/rt_oracle.c (its ray_color and
 (gcc -ffp-contract=off, like the oracle) the first time it is needed, in a temporary directory.  Threads split the rows; every pixel is
 still summed in sample order.  Also the synthetic maps the tests and tools/env_time.py share."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
+import cpu_ref
 import rtp_bindings as rb
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-_lib = None
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        out = os.path.join(tempfile.mkdtemp(prefix="env_ref_"), "libenv_ref.so")
-        subprocess.run(["gcc", "-O2", "-std=gnu11", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-w", "-o", out,
-                        os.path.join(HERE, "cpu_native", "env_ref.c"), "-lm", "-lpthread"], check=True)
-        l = C.CDLL(out)
-        desc, cam, par = C.POINTER(rb.SceneDesc), C.POINTER(rb.CameraData), C.POINTER(rb.EnvParams)
-        l.env_texel_weight.restype = C.c_double
-        l.env_texel_weight.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
-        l.env_table.restype = C.c_int32
-        l.env_table.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        l.env_lookup.restype = None
-        l.env_lookup.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        l.env_decode.restype = None
-        l.env_decode.argtypes = [C.c_int64, C.c_void_p, C.c_void_p]
-        l.env_trace.restype = None
-        l.env_trace.argtypes = [desc, cam, C.c_void_p, C.c_int32, par, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                C.c_int32]
-        l.env_frame.restype = None
-        l.env_frame.argtypes = [desc, cam, C.c_void_p, C.c_int32, par, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        _lib = l
-    return _lib
+    l = cpu_ref.build("env_ref.c")
+    desc, cam, par = C.POINTER(rb.SceneDesc), C.POINTER(rb.CameraData), C.POINTER(rb.EnvParams)
+    l.env_texel_weight.restype = C.c_double
+    l.env_texel_weight.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
+    l.env_table.restype = C.c_int32
+    l.env_table.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    l.env_lookup.restype = None
+    l.env_lookup.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    l.env_decode.restype = None
+    l.env_decode.argtypes = [C.c_int64, C.c_void_p, C.c_void_p]
+    l.env_trace.restype = None
+    l.env_trace.argtypes = [desc, cam, C.c_void_p, C.c_int32, par, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                            C.c_int32]
+    l.env_frame.restype = None
+    l.env_frame.argtypes = [desc, cam, C.c_void_p, C.c_int32, par, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    return l
 
 
 def _map(rgb):

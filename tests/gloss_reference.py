@@ -3,18 +3,14 @@
 into a shared library (gcc -ffp-contract=off, like the oracle) the first time it is needed, in a temporary directory.  Threads split the
 rows; every pixel is still summed in sample order."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
+import cpu_ref
 import emit_reference as emr
 import rtp_bindings as rb
 import tree_reference as tr
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-_lib = None
 # gloss_ref.c's per-sample tallies, in its order
 COUNTERS = ("samples", "absorbed", "pg_zero", "fuzz_gt1", "hit_carried", "miss_carried")
 
@@ -25,23 +21,17 @@ class GlossCfg(C.Structure):
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        out = os.path.join(tempfile.mkdtemp(prefix="gloss_ref_"), "libgloss_ref.so")
-        subprocess.run(["gcc", "-O2", "-std=gnu11", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-w", "-o", out,
-                        os.path.join(HERE, "cpu_native", "gloss_ref.c"), "-lm", "-lpthread"], check=True)
-        l = C.CDLL(out)
-        desc, cam, cfg = C.POINTER(rb.SceneDesc), C.POINTER(rb.CameraData), C.POINTER(GlossCfg)
-        l.gloss_pg_many.restype = None
-        l.gloss_pg_many.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
-        l.gloss_lobe_draws.restype = None
-        l.gloss_lobe_draws.argtypes = [C.c_int64, C.c_void_p, C.c_float, C.c_uint32, C.c_void_p]
-        l.gloss_trace.restype = None
-        l.gloss_trace.argtypes = [desc, cam, cfg, C.c_int64] + [C.c_void_p] * 6 + [C.c_int32, C.c_void_p]
-        l.gloss_frame.restype = None
-        l.gloss_frame.argtypes = [desc, cam, cfg, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        _lib = l
-    return _lib
+    l = cpu_ref.build("gloss_ref.c")
+    desc, cam, cfg = C.POINTER(rb.SceneDesc), C.POINTER(rb.CameraData), C.POINTER(GlossCfg)
+    l.gloss_pg_many.restype = None
+    l.gloss_pg_many.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]
+    l.gloss_lobe_draws.restype = None
+    l.gloss_lobe_draws.argtypes = [C.c_int64, C.c_void_p, C.c_float, C.c_uint32, C.c_void_p]
+    l.gloss_trace.restype = None
+    l.gloss_trace.argtypes = [desc, cam, cfg, C.c_int64] + [C.c_void_p] * 6 + [C.c_int32, C.c_void_p]
+    l.gloss_frame.restype = None
+    l.gloss_frame.argtypes = [desc, cam, cfg, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    return l
 
 
 def pg(w, r, fuzz):

@@ -2,36 +2,25 @@
 which includes oracle/rt_oracle.c (its ray_color is static), built into a shared library (gcc -ffp-contract=off, like the oracle) the
 first time it is needed, in a temporary directory.  Threads split the rows; every pixel is still summed in sample order."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
+import cpu_ref
 import rtp_bindings as rb
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-_lib = None
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        out = os.path.join(tempfile.mkdtemp(prefix="lens_ref_"), "liblens_ref.so")
-        subprocess.run(["gcc", "-O2", "-std=gnu11", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-w", "-o", out,
-                        os.path.join(HERE, "cpu_native", "lens_ref.c"), "-lm", "-lpthread"], check=True)
-        l = C.CDLL(out)
-        cam = C.POINTER(rb.CameraData)
-        l.lens_rays.restype = None
-        l.lens_rays.argtypes = [cam, cam, C.c_float, C.c_float, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                C.c_void_p]
-        l.lens_frame.restype = None
-        l.lens_frame.argtypes = [C.POINTER(rb.SceneDesc), cam, cam, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
-        l.lens_aov.restype = None
-        l.lens_aov.argtypes = [C.POINTER(rb.SceneDesc), cam, cam, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        _lib = l
-    return _lib
+    l = cpu_ref.build("lens_ref.c")
+    cam = C.POINTER(rb.CameraData)
+    l.lens_rays.restype = None
+    l.lens_rays.argtypes = [cam, cam, C.c_float, C.c_float, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                            C.c_void_p]
+    l.lens_frame.restype = None
+    l.lens_frame.argtypes = [C.POINTER(rb.SceneDesc), cam, cam, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    l.lens_aov.restype = None
+    l.lens_aov.argtypes = [C.POINTER(rb.SceneDesc), cam, cam, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    return l
 
 
 def image_rows(cam, shard=None):

@@ -2,17 +2,12 @@
 oracle/rt_oracle.c (its ray_color and hit_bvh are static), built into a shared library (gcc -ffp-contract=off, like the oracle) the
 first time it is needed, in a temporary directory.  Threads split the rows; every pixel is still summed in sample order."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
+import cpu_ref
 import env_reference as er
 import rtp_bindings as rb
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-_lib = None
 
 
 class LitCfg(C.Structure):
@@ -23,19 +18,13 @@ class LitCfg(C.Structure):
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        out = os.path.join(tempfile.mkdtemp(prefix="lit_ref_"), "liblit_ref.so")
-        subprocess.run(["gcc", "-O2", "-std=gnu11", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-w", "-o", out,
-                        os.path.join(HERE, "cpu_native", "lit_ref.c"), "-lm", "-lpthread"], check=True)
-        l = C.CDLL(out)
-        desc, cam, cfg = C.POINTER(rb.SceneDesc), C.POINTER(rb.CameraData), C.POINTER(LitCfg)
-        l.lit_trace.restype = None
-        l.lit_trace.argtypes = [desc, cam, cfg, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
-        l.lit_frame.restype = None
-        l.lit_frame.argtypes = [desc, cam, cfg, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        _lib = l
-    return _lib
+    l = cpu_ref.build("lit_ref.c")
+    desc, cam, cfg = C.POINTER(rb.SceneDesc), C.POINTER(rb.CameraData), C.POINTER(LitCfg)
+    l.lit_trace.restype = None
+    l.lit_trace.argtypes = [desc, cam, cfg, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32]
+    l.lit_frame.restype = None
+    l.lit_frame.argtypes = [desc, cam, cfg, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    return l
 
 
 image_rows = er.image_rows

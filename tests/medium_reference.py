@@ -3,18 +3,14 @@ gloss_ref.c (and through it tree_ref.c, emit_ref.c and oracle/rt_oracle.c) and l
 -ffp-contract=off, like the oracle) the first time it is needed, in a temporary directory.  Threads split the rows; every pixel is still
 summed in sample order."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
+import cpu_ref
 import emit_reference as emr
 import gloss_reference as glr
 import rtp_bindings as rb
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-_lib = None
 # how a path ended (medium_ref.c's med_out.end)
 END_MISS, END_DEPTH, END_ABSORBED, END_BLACK = range(4)
 # medium_ref.c's tallies, in its order (trace(stats=True) adds a dict of them; they only count)
@@ -28,27 +24,21 @@ class MediumCfg(C.Structure):
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        out = os.path.join(tempfile.mkdtemp(prefix="medium_ref_"), "libmedium_ref.so")
-        subprocess.run(["gcc", "-O2", "-std=gnu11", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-w", "-o", out,
-                        os.path.join(HERE, "cpu_native", "medium_ref.c"), "-lm", "-lpthread"], check=True)
-        l = C.CDLL(out)
-        desc, cam, cfg = C.POINTER(rb.SceneDesc), C.POINTER(rb.CameraData), C.POINTER(MediumCfg)
-        l.medium_ph_many.restype = None
-        l.medium_ph_many.argtypes = [C.c_int64, C.c_float, C.c_void_p, C.c_void_p]
-        l.medium_cos_draws.restype = None
-        l.medium_cos_draws.argtypes = [C.c_int64, C.c_float, C.c_uint32, C.c_void_p]
-        l.medium_intervals.restype = None
-        l.medium_intervals.argtypes = [C.POINTER(rb.MediumParams), C.c_int64] + [C.c_void_p] * 6
-        l.medium_trace.restype = None
-        l.medium_trace.argtypes = [desc, cam, cfg, C.c_int64] + [C.c_void_p] * 6 + [C.c_int32]
-        l.medium_trace_stats.restype = None
-        l.medium_trace_stats.argtypes = [desc, cam, cfg, C.c_int64] + [C.c_void_p] * 6 + [C.c_int32, C.c_void_p]
-        l.medium_frame.restype = None
-        l.medium_frame.argtypes = [desc, cam, cfg, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        _lib = l
-    return _lib
+    l = cpu_ref.build("medium_ref.c")
+    desc, cam, cfg = C.POINTER(rb.SceneDesc), C.POINTER(rb.CameraData), C.POINTER(MediumCfg)
+    l.medium_ph_many.restype = None
+    l.medium_ph_many.argtypes = [C.c_int64, C.c_float, C.c_void_p, C.c_void_p]
+    l.medium_cos_draws.restype = None
+    l.medium_cos_draws.argtypes = [C.c_int64, C.c_float, C.c_uint32, C.c_void_p]
+    l.medium_intervals.restype = None
+    l.medium_intervals.argtypes = [C.POINTER(rb.MediumParams), C.c_int64] + [C.c_void_p] * 6
+    l.medium_trace.restype = None
+    l.medium_trace.argtypes = [desc, cam, cfg, C.c_int64] + [C.c_void_p] * 6 + [C.c_int32]
+    l.medium_trace_stats.restype = None
+    l.medium_trace_stats.argtypes = [desc, cam, cfg, C.c_int64] + [C.c_void_p] * 6 + [C.c_int32, C.c_void_p]
+    l.medium_frame.restype = None
+    l.medium_frame.argtypes = [desc, cam, cfg, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    return l
 
 
 def medium_struct(medium):

@@ -2,35 +2,25 @@
 includes oracle/rt_oracle.c (its ray_color and hit_bvh are static), built into a shared library (gcc -ffp-contract=off, like the oracle)
 the first time it is needed, in a temporary directory.  Threads split the rows; every pixel is still summed in sample order."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
+import cpu_ref
 import rtp_bindings as rb
 
-HERE = os.path.dirname(os.path.abspath(__file__))
 PLAIN = -1          # mode of nee_frame: the oracle's ray_color (rt_render)
-_lib = None
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        out = os.path.join(tempfile.mkdtemp(prefix="nee_ref_"), "libnee_ref.so")
-        subprocess.run(["gcc", "-O2", "-std=gnu11", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-w", "-o", out,
-                        os.path.join(HERE, "cpu_native", "nee_ref.c"), "-lm", "-lpthread"], check=True)
-        l = C.CDLL(out)
-        desc, cam = C.POINTER(rb.SceneDesc), C.POINTER(rb.CameraData)
-        l.nee_table.restype = C.c_int32
-        l.nee_table.argtypes = [desc, C.c_void_p, C.c_void_p, C.c_void_p]
-        l.nee_trace.restype = None
-        l.nee_trace.argtypes = [desc, cam, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        l.nee_frame.restype = None
-        l.nee_frame.argtypes = [desc, cam, C.c_int32, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        _lib = l
-    return _lib
+    l = cpu_ref.build("nee_ref.c")
+    desc, cam = C.POINTER(rb.SceneDesc), C.POINTER(rb.CameraData)
+    l.nee_table.restype = C.c_int32
+    l.nee_table.argtypes = [desc, C.c_void_p, C.c_void_p, C.c_void_p]
+    l.nee_trace.restype = None
+    l.nee_trace.argtypes = [desc, cam, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    l.nee_frame.restype = None
+    l.nee_frame.argtypes = [desc, cam, C.c_int32, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    return l
 
 
 def image_rows(cam, shard=None):

@@ -8,11 +8,11 @@ properties on synthetic frames.  Quality: against 1024-spp ground truths, still 
 import ctypes as C
 import os
 import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
+import cpu_ref
 import denoise_reference as dr
 import denoise_temporal_reference as dtr
 import rtp_bindings as rb
@@ -316,19 +316,11 @@ def test_sample_offsets_are_the_samples_they_name():
         dev.close()
 
 
-_aov_lib = None
-
-
 def _aov_samples_lib():
-    global _aov_lib
-    if _aov_lib is None:
-        out = os.path.join(tempfile.mkdtemp(prefix="aov_samples_ref_"), "libaov_samples_ref.so")
-        subprocess.run(["gcc", "-O2", "-std=gnu11", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-w", "-o", out,
-                        os.path.join(HERE, "cpu_native", "aov_samples_ref.c"), os.path.join(ROOT, "oracle", "rt_oracle.c"), "-lm"], check=True)
-        _aov_lib = C.CDLL(out)
-        _aov_lib.aov_samples_reference.argtypes = [C.POINTER(rb.SceneDesc), C.POINTER(rb.CameraData), C.c_int32] + [C.c_void_p] * 5
-        _aov_lib.aov_samples_reference.restype = None
-    return _aov_lib
+    l = cpu_ref.build("aov_samples_ref.c", "oracle/rt_oracle.c")
+    l.aov_samples_reference.argtypes = [C.POINTER(rb.SceneDesc), C.POINTER(rb.CameraData), C.c_int32] + [C.c_void_p] * 5
+    l.aov_samples_reference.restype = None
+    return l
 
 
 def _aov_samples(lib, host, cam, first):

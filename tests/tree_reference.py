@@ -3,17 +3,13 @@ tests/cpu_native/tree_ref.c, which includes emit_ref.c (and through it oracle/rt
 -ffp-contract=off, like the oracle) the first time it is needed, in a temporary directory.  Threads split the rows; every pixel is still
 summed in sample order."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
+import cpu_ref
 import emit_reference as emr
 import rtp_bindings as rb
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-_lib = None
 COLUMNS = ("sphere", "weight", "q", "left", "right", "entry", "path", "depth")
 # tree_ref.c's tallies, in its order (trace(stats=True) returns the first two, trace(stats="all") a dict of all of them)
 STATS = ("inside_parent", "weighted", "drop_inside", "drop_omega", "drop_cos", "shadow_other_entry", "shadow_non_table", "hit_pl_zero",
@@ -26,25 +22,19 @@ class TreeCfg(C.Structure):
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        out = os.path.join(tempfile.mkdtemp(prefix="tree_ref_"), "libtree_ref.so")
-        subprocess.run(["gcc", "-O2", "-std=gnu11", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-w", "-o", out,
-                        os.path.join(HERE, "cpu_native", "tree_ref.c"), "-lm", "-lpthread"], check=True)
-        l = C.CDLL(out)
-        desc, cam, cfg = C.POINTER(rb.SceneDesc), C.POINTER(rb.CameraData), C.POINTER(TreeCfg)
-        l.tree_columns.restype = C.c_int32
-        l.tree_columns.argtypes = [desc, C.c_int32] + [C.c_void_p] * 8 + [C.POINTER(C.c_int32)]
-        l.tree_pmf_points.restype = None
-        l.tree_pmf_points.argtypes = [desc, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]
-        l.tree_pick_counts.restype = C.c_int64
-        l.tree_pick_counts.argtypes = [desc, C.c_int32, C.c_void_p, C.c_int64, C.c_uint32, C.c_void_p]
-        l.tree_trace.restype = None
-        l.tree_trace.argtypes = [desc, cam, cfg, C.c_int64] + [C.c_void_p] * 6 + [C.c_int32, C.c_void_p]
-        l.tree_frame.restype = None
-        l.tree_frame.argtypes = [desc, cam, cfg, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        _lib = l
-    return _lib
+    l = cpu_ref.build("tree_ref.c")
+    desc, cam, cfg = C.POINTER(rb.SceneDesc), C.POINTER(rb.CameraData), C.POINTER(TreeCfg)
+    l.tree_columns.restype = C.c_int32
+    l.tree_columns.argtypes = [desc, C.c_int32] + [C.c_void_p] * 8 + [C.POINTER(C.c_int32)]
+    l.tree_pmf_points.restype = None
+    l.tree_pmf_points.argtypes = [desc, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]
+    l.tree_pick_counts.restype = C.c_int64
+    l.tree_pick_counts.argtypes = [desc, C.c_int32, C.c_void_p, C.c_int64, C.c_uint32, C.c_void_p]
+    l.tree_trace.restype = None
+    l.tree_trace.argtypes = [desc, cam, cfg, C.c_int64] + [C.c_void_p] * 6 + [C.c_int32, C.c_void_p]
+    l.tree_frame.restype = None
+    l.tree_frame.argtypes = [desc, cam, cfg, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    return l
 
 
 def tree(host, planes=0):

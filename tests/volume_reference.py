@@ -2,18 +2,13 @@
 medium_ref.c (and through it everything medium_reference.py's library holds), built into a shared library (gcc -ffp-contract=off, like the
 oracle) the first time it is needed, in a temporary directory.  A grid is an (nz, ny, nx) float32 array, as rb.Volume takes it."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
+import cpu_ref
 import emit_reference as emr
 import medium_reference as mr
 import rtp_bindings as rb
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-_lib = None
 
 
 class VolumeCfg(C.Structure):
@@ -22,23 +17,17 @@ class VolumeCfg(C.Structure):
 
 
 def lib():
-    global _lib
-    if _lib is None:
-        out = os.path.join(tempfile.mkdtemp(prefix="volume_ref_"), "libvolume_ref.so")
-        subprocess.run(["gcc", "-O2", "-std=gnu11", "-fPIC", "-shared", "-ffp-contract=off", "-fno-fast-math", "-w", "-o", out,
-                        os.path.join(HERE, "cpu_native", "volume_ref.c"), "-lm", "-lpthread"], check=True)
-        l = C.CDLL(out)
-        desc, cam, cfg = C.POINTER(rb.SceneDesc), C.POINTER(rb.CameraData), C.POINTER(VolumeCfg)
-        l.volume_walks.restype = None
-        l.volume_walks.argtypes = [C.POINTER(rb.MediumParams), C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 10
-        l.volume_walks_f64.restype = None
-        l.volume_walks_f64.argtypes = [C.POINTER(rb.MediumParams), C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 6
-        l.volume_trace.restype = None
-        l.volume_trace.argtypes = [desc, cam, cfg, C.c_int64] + [C.c_void_p] * 7 + [C.c_int32]
-        l.volume_frame.restype = None
-        l.volume_frame.argtypes = [desc, cam, cfg, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-        _lib = l
-    return _lib
+    l = cpu_ref.build("volume_ref.c")
+    desc, cam, cfg = C.POINTER(rb.SceneDesc), C.POINTER(rb.CameraData), C.POINTER(VolumeCfg)
+    l.volume_walks.restype = None
+    l.volume_walks.argtypes = [C.POINTER(rb.MediumParams), C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 10
+    l.volume_walks_f64.restype = None
+    l.volume_walks_f64.argtypes = [C.POINTER(rb.MediumParams), C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 6
+    l.volume_trace.restype = None
+    l.volume_trace.argtypes = [desc, cam, cfg, C.c_int64] + [C.c_void_p] * 7 + [C.c_int32]
+    l.volume_frame.restype = None
+    l.volume_frame.argtypes = [desc, cam, cfg, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    return l
 
 
 def grid_of(density):
