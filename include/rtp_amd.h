@@ -1159,7 +1159,7 @@ rt_status rt_render_lit_adaptive_prior(rt_scene *scene, const rt_camera_data *ca
  *   through the medium's own kernels.
  * Left out: ~~heterogeneous~~ (rt_render_volume, "density grid" below) or chromatic extinction; more than one region; regions bounded by scene surfaces (fog inside a glass ball that
  *   sits in the region is still fog); emission in the medium; the guarded walk; tiles and rt_context; ~~rt_render_lit_adaptive with a
- *   medium~~ (rt_render_volume_adaptive, "adaptive sampling under fog" below), AOVs of the medium and the denoisers' handling of it (the first-hit AOVs do not see it).
+ *   medium~~ (rt_render_volume_adaptive, "adaptive sampling under fog" below), ~~AOVs of the medium and the denoisers' handling of it~~ (rt_render_aov_volume, "AOVs under fog" below; the first-hit AOVs do not see it).
  * Checks, all before anything is enqueued: rt_render_lit's parameter checks come first, in its order (lens, nee, env_params); then the
  *   medium's, still before the scene is looked at; then the scene's and the camera's as in rt_render_lit.  RT_ERR_INVALID_ARG for struct_bytes below 8,
  *   region outside {0, 1, 2}, a sigma_t that is negative, NaN or infinite, an albedo channel outside [0, 1], |g| > 0.95 or NaN, a ball's
@@ -1219,7 +1219,7 @@ rt_status rt_trace_samples_medium(rt_scene *scene, const rt_camera_data *cam_ope
  *   and env streams; med advances one draw per non-empty path interval.
  * Left out: chromatic extinction; more than one region or grid; emission in the medium; interpolation between cells (trilinear or any
  *   other: the density is piecewise constant); ~~rt_render_lit_adaptive with a grid~~ (rt_render_volume_adaptive, "adaptive sampling under fog"
- *   below); AOVs of the medium; tiles and rt_context.
+ *   below); ~~AOVs of the medium~~ (rt_render_aov_volume, "AOVs under fog" below); tiles and rt_context.
  * rt_volume: the grid on the device it was created on (the calling thread's current one), like an rt_env.  density is HOST memory, nx * ny
  *   * nz floats, copied: cell (x, y, z) at (z * ny + y) * nx + x.  RT_ERR_INVALID_ARG for a null pointer, a dimension below 1 or above
  *   RT_VOLUME_MAX_N, a density that is negative, NaN or infinite.  A volume outlives every call that was given it; destroy it after the
@@ -1264,11 +1264,54 @@ rt_status rt_trace_samples_volume(rt_scene *scene, const rt_camera_data *cam_ope
  * rt_render_lit; RT_ERR_UNSUPPORTED for pixels x batch_spp at or above 2^31 - 4096 when R > 0.  Messages name rt_render_volume_adaptive.
  * max_depth <= 0: zero sums and moments, the counts by the rule.  Rows of a shard only: no tiles, no rt_context.  Handle state, buffers
  * and timing: as rt_render_lit_adaptive (trace_launches = the min_spp frame's passes + R).
- * Left out: tiles and rt_context; the guarded walk; the denoisers on fogged frames; empty-space skipping. */
+ * Left out: tiles and rt_context; the guarded walk; ~~the denoisers on fogged frames~~ (rt_render_aov_volume, "AOVs under fog" below);
+ *   empty-space skipping. */
 rt_status rt_render_volume_adaptive(rt_scene *scene, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium,
                                     const rt_volume *volume, const rt_adaptive_params *params, const rt_stop_params *stop, const float *d_prior,
                                     const rt_shard *shard, int32_t sample_first, float *d_fb_sum, int32_t *d_spp, float *d_moments,
                                     void *hip_stream, int32_t sync, rt_timing *timing);
+
+/* ---- AOVs under fog --------------------------------------------------------------------------------------------------
+ * The guides rt_denoise and rt_denoise_spp want for a frame of rt_render_medium, rt_render_volume or rt_render_volume_adaptive: the five
+ * buffers of rt_render_aov_lens, in which a sample whose camera ray crosses the medium carries the medium's albedo, a normal that faces
+ * the camera and a depth inside the fog, each blended with its surface's by the transmittance of the camera ray — and counts as covered
+ * even when it hit no surface.  The call takes the beauty call's own lit, medium and volume; of lit only cam_close and lens shape the
+ * result, the rest is checked and ignored.  rt_aov_buffers is unchanged; the transmittance is a separate buffer.
+ *
+ * Deterministic: no draw beyond the camera ray's.  float32 in the order written, nothing fused, division and sqrtf correctly rounded,
+ * exp_libm as everywhere.  For sample s of pixel (i, j), sample_first <= s < sample_first + spp, in sample order:
+ *   1. (o, d) is the sample's camera ray as rt_render_aov_lens makes it.  A first hit is rt_render_aov's: parameter t_hit, per-sample
+ *      albedo a, face-forwarded normal n.  A miss has t_hit = +inf and a = the background.
+ *   2. [t0, t1] = interval(o, d, t_hit) of "participating medium"; len = sqrtf(lensq(d)).  Without a volume tau = sigma_t * ((t1 - t0) *
+ *      len); with a volume tau is acc of the transmittance walk of "density grid".  Tr = exp_libm(-tau), F = 1 - Tr.
+ *   3. The sample is CLEAR when the interval is empty or F == 0: it adds exactly what rt_render_aov_lens adds for it (a clear miss: the
+ *      background to the albedo, no count), and 1 to the transmittance.
+ *   4. Every other sample is COVERED.  t_fog without a volume: s = RT_AOV_FOG_REM / sigma_t; t_fog = t0 + s / len when s < (t1 - t0) *
+ *      len, otherwise t1.  With a volume: the free-flight walk of "density grid" with rem = RT_AOV_FOG_REM in the place of -log_libm(u);
+ *      t_fog is its event's t, and t1 without an event.  (t_fog is finite in every region: all-space fog always has the event on a miss.)
+ *      ud = unit(d), the medium vertex's.  The sample adds
+ *        albedo_sum[k] += Tr * a[k] + F * medium.albedo[k]
+ *        normal_sum[k] += Tr * n[k] - F * ud[k]   (a hit)        normal_sum[k] += -(F * ud[k])   (a miss)
+ *        depth_sum     += Tr * t_hit + F * t_fog  (a hit)        depth_sum     += t_fog          (a miss)
+ *        hit_count     += 1  (a hit or a miss)                   transmittance_sum += Tr
+ *      The fog's normal faces the camera: neighbouring fog pixels agree, and a covered pixel never has the zero normal at which
+ *      rt_denoise gives a tap no weight.
+ *   5. first_prim is rt_render_aov_lens's: the surface of sample sample_first, -1 for a miss, covered or not.
+ *
+ * Identities, bit for bit in the five buffers: medium == NULL or sigma_t == 0 is rt_render_aov_lens (its kernels, after this call's own
+ *   checks; the transmittance is (float)spp).  volume == NULL uses the homogeneous formulas in every region.  A 1 x 1 x 1 grid of density
+ *   1, through the grid kernels, equals volume == NULL with the same box.  A grid of zeros, and a region no camera ray touches, give
+ *   rt_render_aov_lens's buffers through the fog kernels.
+ * Checks, all before anything is enqueued: the buffers first, as in rt_render_aov (all five NULL is an error, with a transmittance pointer
+ *   as well); then rt_render_volume's in its order (lit, the medium's, the volume's region 2, the null scene, the volume's device); then
+ *   rt_render_aov_samples' sample range and frame checks.  Every message names rt_render_aov_volume.  spp <= 0: zero sums, first_prim -1,
+ *   transmittance 0.  Rows of a shard only: no tiles, no rt_context.  Handle state and rt_last_timing: as rt_render_aov_lens leaves them.
+ * Left out: the temporal filters (their reprojection takes depth_sum for a surface point, which a fog-blended depth is not); tiles and
+ *   rt_context; a separate in-scatter / surface split of the beauty frame. */
+#define RT_AOV_FOG_REM 0.693147182f   /* (float)ln 2: the optical depth at which half of the light has met the medium */
+rt_status rt_render_aov_volume(rt_scene *scene, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium,
+                               const rt_volume *volume, const rt_shard *shard, int32_t sample_first, const rt_aov_buffers *buffers,
+                               float *d_transmittance_sum /* NULL or 1 float per pixel */, void *hip_stream, int32_t sync, rt_timing *timing);
 
 /* Milliseconds of the most recent rt_render kernel of this scene (waits for it). */
 rt_status rt_last_kernel_ms(rt_scene *scene, float *ms);

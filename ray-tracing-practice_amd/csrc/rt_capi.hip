@@ -22,6 +22,7 @@
 #include "rt_light.hip.inc"
 #include "rt_medium.hip.inc"
 #include "rt_volume.hip.inc"
+#include "rt_aov_fog.hip.inc"
 // Developer build only (make dev → librtp_amd_dev.so, -DRTP_DEV_BUILD): the rt_debug_* entry points (exhaustive on-device checks of
 // recip / sqrt_cr / sphere_root, the device LBVH builder on its own, the tripwire, the RTP_STATS counters) at the end of this file.
 // The shipped library contains none of them.
@@ -1718,17 +1719,21 @@ rt_status render_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *s
 // rt_render calls.
 // lens (rt_render_aov_lens): every sample's first hit from the lens / moving camera's ray, without candidate lists (those of the
 // handle stay as they are).
+// fog (rt_render_aov_volume, with lens): the lens frame's records, accumulated under the medium (rt_aov_fog.hip.inc); fog->tr, or without
+// fog d_tr, takes the transmittance sums.  what: the call the sample-range refusals name.
 rt_status aov_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shard, const Tile *tile, const rt_aov_buffers *buffers, void *hip_stream,
-                   int32_t sync, rt_timing *timing, int32_t sample_first = 0, const rtk::LensCam *lens = nullptr) {
+                   int32_t sync, rt_timing *timing, int32_t sample_first = 0, const rtk::LensCam *lens = nullptr, const char *what = "rt_render_aov_samples",
+                   const rtk::AovFog *fog = nullptr, float *d_tr = nullptr) {
     // (the buffers first: a caller's mistake there is reported as such whatever else is wrong)
     if (!buffers || buffers->struct_bytes < 16u) return fail(RT_ERR_INVALID_ARG, "null AOV buffers (or struct_bytes below 16)");
     rt_aov_buffers b{};
     std::memcpy(&b, buffers, buffers->struct_bytes < sizeof(b) ? buffers->struct_bytes : sizeof(b));
     if (!b.albedo_sum && !b.normal_sum && !b.depth_sum && !b.hit_count && !b.first_prim) return fail(RT_ERR_INVALID_ARG, "every AOV buffer is NULL");
     Frame F;
-    rt_status st = frame_prologue("rt_render_aov_samples", sc, cam, shard, tile, sample_first, nullptr, nullptr, hip_stream, timing, F, nothing_late);
+    rt_status st = frame_prologue(what, sc, cam, shard, tile, sample_first, nullptr, nullptr, hip_stream, timing, F, nothing_late);
     if (st != RT_OK) return st;
     if (F.nothing_to_do()) return RT_OK;
+    if (fog) d_tr = fog->tr;
     rtk::KParams &P = F.P;
     const rt_config &cfg = sc->cfg;
     const hipStream_t stream = F.stream;
@@ -1740,6 +1745,7 @@ rt_status aov_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shar
         if (out.depth) HIP_TRY(hipMemsetAsync(out.depth, 0, (size_t)num_pixels * 4, stream));
         if (out.hits) HIP_TRY(hipMemsetAsync(out.hits, 0, (size_t)num_pixels * 4, stream));
         if (out.prim) HIP_TRY(hipMemsetAsync(out.prim, 0xff, (size_t)num_pixels * 4, stream));
+        if (d_tr) HIP_TRY(hipMemsetAsync(d_tr, 0, (size_t)num_pixels * 4, stream));
         if (sync) HIP_TRY(hipStreamSynchronize(stream));
         return RT_OK;
     }
@@ -1786,8 +1792,14 @@ rt_status aov_impl(rt_scene *sc, const rt_camera_data *cam, const rt_shard *shar
         HIP_TRY(hipGetLastError());
         if (timed_pass) HIP_TRY(hipEventRecord(sc->aov_events[3 * pass + 2], stream));
         // (2) … added to the pixel's sums in sample order
-        if (lens) hipLaunchKernelGGL(rtk::aov_accumulate_lens_kernel, acc_grid(num_pixels), dim3(64 * rtk::kAccWaves), 0, stream, P, *lens, out, pass == 0 ? 1 : 0, walked);
+        if (fog && fog->V.rho) hipLaunchKernelGGL(rtk::aov_accumulate_fog_kernel<true>, acc_grid(num_pixels), dim3(64 * rtk::kAccWaves), 0, stream, P, *lens, *fog, out, pass == 0 ? 1 : 0);
+        else if (fog) hipLaunchKernelGGL(rtk::aov_accumulate_fog_kernel<false>, acc_grid(num_pixels), dim3(64 * rtk::kAccWaves), 0, stream, P, *lens, *fog, out, pass == 0 ? 1 : 0);
+        else if (lens) hipLaunchKernelGGL(rtk::aov_accumulate_lens_kernel, acc_grid(num_pixels), dim3(64 * rtk::kAccWaves), 0, stream, P, *lens, out, pass == 0 ? 1 : 0, walked);
         else hipLaunchKernelGGL(rtk::aov_accumulate_kernel, acc_grid(num_pixels), dim3(64 * rtk::kAccWaves), 0, stream, P, out, pass == 0 ? 1 : 0, walked);
+        HIP_TRY(hipGetLastError());
+    }
+    if (!fog && d_tr) {         // no medium: every sample is clear
+        hipLaunchKernelGGL(rtk::aov_fog_fill_kernel, dim3((num_pixels + 255u) / 256u), dim3(256), 0, stream, d_tr, num_pixels, (float)P.spp);
         HIP_TRY(hipGetLastError());
     }
     if ((st = clock.stop(stream)) != RT_OK) return st;
@@ -3547,6 +3559,30 @@ rt_status rt_render_volume(rt_scene *sc, const rt_camera_data *cam_open, const r
     auto with_light = [&](auto frame) { return with_fog_lit(sc, S, M, volume, [&](const auto &T) { return frame(lit_kernels_of(S.lens, T).frame, &T); }); };
     return render_light_impl("rt_render_volume", S.env ? &S.env->device : nullptr, with_light, sc, cam_open, shard, sample_first, d_fb_sum, hip_stream, sync, timing,
                              &S.C);
+}
+
+// ---- rt_render_aov_volume (rtp_amd.h, "AOVs under fog"): rt_render_aov_lens's frame (aov_impl) with the accumulation of
+// rt_aov_fog.hip.inc.  Of lit only the camera shapes the result.  No medium is rt_render_aov_lens's own kernels, and a transmittance of spp.
+rt_status rt_render_aov_volume(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium, const rt_volume *volume,
+                               const rt_shard *shard, int32_t sample_first, const rt_aov_buffers *buffers, float *d_transmittance_sum, void *hip_stream,
+                               int32_t sync, rt_timing *timing) {
+    const char *what = "rt_render_aov_volume";
+    // (the buffers first, as aov_impl has them)
+    if (!buffers || buffers->struct_bytes < 16u) return fail(RT_ERR_INVALID_ARG, "rt_render_aov_volume: null AOV buffers (or struct_bytes below 16)");
+    rt_aov_buffers b{};
+    std::memcpy(&b, buffers, buffers->struct_bytes < sizeof(b) ? buffers->struct_bytes : sizeof(b));
+    if (!b.albedo_sum && !b.normal_sum && !b.depth_sum && !b.hit_count && !b.first_prim) return fail(RT_ERR_INVALID_ARG, "rt_render_aov_volume: every AOV buffer is NULL");
+    LitSetup S;
+    if (const rt_status st = lit_setup(what, cam_open, lit, S)) return st;
+    rtk::AovFog G{};
+    if (const rt_status st = medium_setup(what, medium, G.M)) return st;
+    if (const rt_status st = volume_setup(what, medium, G.M, volume)) return st;
+    if (!sc) return fail(RT_ERR_INVALID_ARG, "rt_render_aov_volume: null scene");
+    if (volume && volume->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_render_aov_volume: the volume was created on another device than the scene");
+    if (!(G.M.sigma_t > 0.0f)) return aov_impl(sc, cam_open, shard, nullptr, buffers, hip_stream, sync, timing, sample_first, &S.C, what, nullptr, d_transmittance_sum);
+    if (volume) G.V = rtk::VolumeDev{volume->rho, volume->nx, volume->ny, volume->nz};
+    G.tr = d_transmittance_sum;
+    return aov_impl(sc, cam_open, shard, nullptr, buffers, hip_stream, sync, timing, sample_first, &S.C, what, &G);
 }
 
 // ---- rt_render_volume_adaptive (rtp_amd.h): rt_render_lit_adaptive_prior's steps (lit_adaptive_run) on rt_render_volume's

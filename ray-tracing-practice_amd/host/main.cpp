@@ -42,6 +42,30 @@ int main(int argc, char *argv[]) {
         if (std::string(argv[a]) == "--denoise") denoise = true;
         if (std::string(argv[a]) == "--denoise-temporal") temporal = true;
     }
+    // extension: `--lit … --fog SIGMA … --fog-denoise`, with or without --fog-ball, --fog-box, --fog-grid and --fog-noise-target:
+    // each fogged frame is also filtered under the fog-aware AOVs of rt_render_aov_volume — by rt_denoise, or with --fog-noise-target by
+    // rt_denoise_spp with the frame's counts and moments and AOVs at min_spp — and written through the frame's own saver to
+    // "<frame file>.denoised".  The flag needs --fog and is not for --denoise*, --aov, --adaptive, --devices or --shard.  This block comes
+    // before those flags' own, so that whatever else is given the refusal names this flag.
+    bool fog_denoise = false;
+    {
+        bool fog_flag = false;
+        std::string other;
+        for (int a = 2; a < argc; ++a) {
+            const std::string arg = argv[a];
+            if (arg == "--fog-denoise") fog_denoise = true;
+            if (arg == "--fog") fog_flag = true;
+            if (arg.compare(0, 9, "--denoise") == 0 || arg == "--aov" || arg == "--adaptive" || arg == "--devices" || arg == "--shard") other = arg;
+        }
+        std::string bad;
+        if (fog_denoise && !fog_flag) bad = "--fog-denoise filters fogged frames: it needs --lit --fog SIGMA";
+        else if (fog_denoise && !other.empty())
+            bad = "--fog-denoise cannot be combined with " + other + " (not with --denoise*, --aov, --adaptive, --devices or --shard)";
+        if (!bad.empty()) {
+            std::cerr << "rtp_main: " << bad << "\n";
+            return 99;
+        }
+    }
     // extension: `--lit … --fog SIGMA … [--fog-grid FILE] --fog-noise-target T[:min:batch:max]`: the fogged frames through
     // rt_render_volume_adaptive (adaptive sampling under the medium or the grid, default 16:16:256) and rt_tonemap_spp.  The flag needs --fog
     // and is not for --adaptive, --denoise*, --aov, --stop-rule, --stop-history or --noise-target.  This block comes before those flags' own,
@@ -531,7 +555,7 @@ int main(int argc, char *argv[]) {
                     return 99;
                 }
                 rtp::gpu_render_lens(params, desc, lens, shutter, aov, denoise, nullptr, nullptr, nullptr, &lit, fog_noise_on ? &fog_noise : noise_on ? &noise : nullptr,
-                                     denoise_adaptive, &stop_rule, denoise_adaptive_temporal, fog_on ? &fog : nullptr, stop_history, fog_volume);
+                                     denoise_adaptive, &stop_rule, denoise_adaptive_temporal, fog_on ? &fog : nullptr, stop_history, fog_volume, fog_denoise);
                 rt_volume_destroy(fog_volume);
                 rt_env_destroy(lit_env);
                 return 0;

@@ -340,12 +340,16 @@ void gpu_render_pipelined(const SceneParams &params, const rt_scene_desc &desc, 
 // rt_render_lit_adaptive and rt_tonemap_spp — every pixel's bytes at its own sample count — and the printed count is the samples taken
 // medium (with lit, without noise; rtp_main --lit --fog): through rt_render_medium; volume (with medium; rtp_main --fog-grid,
 // DESIGN.md §28): through rt_render_volume with this grid in the medium's box.  medium with noise (rtp_main --fog-noise-target, DESIGN.md
-// §29): through rt_render_volume_adaptive (the volume may be null) and rt_tonemap_spp, without a stop rule, a prior or a denoiser.
+// §29): through rt_render_volume_adaptive (the volume may be null) and rt_tonemap_spp, without a stop rule or a prior.
+// fog_denoise (with medium; rtp_main --fog-denoise): denoise — or with noise denoise_adaptive — with the AOVs from
+// rt_render_aov_volume under the frame's own lit, medium and volume.
 // denoise_adaptive (with noise; rtp_main --denoise-adaptive): as in gpu_render_adaptive, the AOVs from rt_render_aov_lens at noise->min_spp
 void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const rt_lens_params &lens, float shutter, bool aov, bool denoise,
                      const rt_nee_params *nee, const rt_env *env, const rt_env_params *env_params, const rt_lit_params *lit,
                      const rt_adaptive_params *noise, bool denoise_adaptive, const rt_stop_params *stop, bool denoise_adaptive_temporal,
-                     const rt_medium_params *medium, bool stop_history, const rt_volume *volume) {
+                     const rt_medium_params *medium, bool stop_history, const rt_volume *volume, bool fog_denoise) {
+    if (fog_denoise && noise) denoise_adaptive = true;
+    else if (fog_denoise) denoise = true;
     rt_scene *scene = nullptr;
     RTP_CHECK(rt_scene_create(&desc, &scene));
     const size_t num_pixels = static_cast<size_t>(params.width) * params.height;
@@ -415,9 +419,9 @@ void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const
             rt_lit_params frame_lit = *lit;
             frame_lit.cam_close = cam_close;
             frame_lit.lens = &lens;
-            if (medium)          // (rtp_main --fog-noise-target: no denoiser, no stop rule, no prior)
-                RTP_CHECK(rt_render_volume_adaptive(scene, &cam, &frame_lit, medium, volume, noise, nullptr, nullptr, nullptr, 0, d_fb, d_spp, nullptr, nullptr, 1,
-                                                    nullptr));
+            if (medium)          // (rtp_main --fog-noise-target: no stop rule, no prior; the moments for --fog-denoise)
+                RTP_CHECK(rt_render_volume_adaptive(scene, &cam, &frame_lit, medium, volume, noise, nullptr, nullptr, nullptr, 0, d_fb, d_spp,
+                                                    spp_denoiser ? spp_denoiser->d_moments : nullptr, nullptr, 1, nullptr));
             else
                 RTP_CHECK(rt_render_lit_adaptive_rule(scene, &cam, &frame_lit, noise, stop, nullptr, 0, d_fb, d_spp,
                                                       spp_denoiser ? spp_denoiser->d_moments : nullptr, nullptr, 1, nullptr));
@@ -449,6 +453,11 @@ void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const
             rt_camera_data aov_open = cam, aov_close = close;
             aov_open.samples_per_pixel = aov_close.samples_per_pixel = noise->min_spp;
             if (with_prior) {          // (rendered before the frame)
+            } else if (fog_denoise) {
+                rt_lit_params frame_lit = *lit;
+                frame_lit.cam_close = cam_close ? &aov_close : nullptr;
+                frame_lit.lens = &lens;
+                RTP_CHECK(rt_render_aov_volume(scene, &aov_open, &frame_lit, medium, volume, nullptr, 0, &spp_denoiser->aov, nullptr, nullptr, 1, nullptr));
             } else if (spp_denoiser->temporal) {
                 RTP_CHECK(rt_render_aov(scene, &aov_open, nullptr, &spp_denoiser->aov, nullptr, 1, nullptr));       // (a pinhole, no shutter)
             } else {
@@ -458,7 +467,12 @@ void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const
         }
         if (aov || denoise) {          // (outside the frame's timed span, as in gpu_render)
             if (!lit && (nee || env)) RTP_CHECK(rt_render_aov_samples(scene, &cam, nullptr, 0, &aov_bufs, nullptr, 1, nullptr));
-            else RTP_CHECK(rt_render_aov_lens(scene, &cam, cam_close, &lens, nullptr, 0, &aov_bufs, nullptr, 1, nullptr));
+            else if (fog_denoise) {
+                rt_lit_params frame_lit = *lit;
+                frame_lit.cam_close = cam_close;
+                frame_lit.lens = &lens;
+                RTP_CHECK(rt_render_aov_volume(scene, &cam, &frame_lit, medium, volume, nullptr, 0, &aov_bufs, nullptr, nullptr, 1, nullptr));
+            } else RTP_CHECK(rt_render_aov_lens(scene, &cam, cam_close, &lens, nullptr, 0, &aov_bufs, nullptr, 1, nullptr));
             if (aov) {
                 h_albedo.resize(num_pixels * 3); h_normal.resize(num_pixels * 3); h_depth.resize(num_pixels); h_hits.resize(num_pixels);
                 RTP_CHECK(rt_copy_to_host(h_albedo.data(), aov_bufs.albedo_sum, num_pixels * 12));

@@ -571,6 +571,7 @@ _AMD_LATER = {
     "rt_render_volume": (_STATUS, [_VP, _CAM, _LIT, _MEDIUM, _VP, _SHARD, _I32, _VP, *_OUT]),
     "rt_trace_samples_volume": (_STATUS, [_VP, _CAM, _LIT, _MEDIUM, _VP, _I32] + [_VP] * 9),
     "rt_render_volume_adaptive": (_STATUS, [_VP, _CAM, _LIT, _MEDIUM, _VP, _ADAPTIVE, _STOP, _VP, _SHARD, _I32, _VP, _VP, _VP, *_OUT]),
+    "rt_render_aov_volume": (_STATUS, [_VP, _CAM, _LIT, _MEDIUM, _VP, _SHARD, _I32, _AOV, _VP, *_OUT]),
 }
 # the calls that take a prior: their _rule call (the judgement: the call itself) and, last, the device address of the prior
 for _base, _prior in (("rt_render_adaptive_rule", "rt_render_adaptive_prior"), ("rt_render_lit_adaptive_rule", "rt_render_lit_adaptive_prior"),
@@ -1410,6 +1411,25 @@ class DeviceScene:
         return _adaptive_to_host(cam, shard, prior, lambda d_fb, d_spp, d_moments, d_prior: self.render_volume_adaptive(
             cam, d_fb, d_spp, d_moments, medium=medium, volume=volume, cam_close=cam_close, lens=lens, emitters=emitters, nee=nee, env=env, env_params=env_params,
             shard=shard, sample_first=sample_first, prior=d_prior, **params))
+
+    def render_aov_volume(self, cam, ptrs, *, medium=None, volume=None, cam_close=None, lens=None, shard=None, stream=None, sync=True, sample_first=0,
+                          transmittance=None):
+        """rt_render_aov_volume: render_aov_lens's buffers under render_volume's medium and volume.  ptrs as render_aov takes them;
+        transmittance: None, or the device address of 1 float per pixel.  Returns the rt_timing."""
+        lit = lit_params(cam_close=cam_close, lens=lens)
+        return self._call("rt_render_aov_volume", C.byref(cam), C.byref(lit), _medium_struct(medium), _volume_handle(volume), _ref(shard), sample_first,
+                          C.byref(_aov_struct(ptrs)), C.c_void_p(transmittance or 0), *_stream_sync(stream, sync))
+
+    def render_aov_volume_to_host(self, cam, *, medium=None, volume=None, cam_close=None, lens=None, shard=None, sample_first=0):
+        """rt_render_aov_volume through fresh device buffers: (render_aov_lens_to_host's dict plus "transmittance": (rows, w) float32,
+        rt_timing)."""
+        rows, w = amd_lib().rt_shard_rows(cam.image_height, _ref(shard)), cam.image_width
+        with _DeviceBuffers() as dev:
+            d_tr = dev.alloc(max(rows, 0) * max(w, 0) * 4)
+            out, t = _aov_to_host(rows, w, lambda ptrs: self.render_aov_volume(cam, ptrs, medium=medium, volume=volume, cam_close=cam_close, lens=lens,
+                                                                               shard=shard, sample_first=sample_first, transmittance=d_tr))
+            out["transmittance"] = dev.download(d_tr, np.empty((rows, w), dtype=np.float32))
+        return out, t
 
     def trace_samples_volume(self, cam, ijs, *, medium=None, volume=None, cam_close=None, lens=None, emitters=True, nee=None, env=None, env_params=None):
         """rt_trace_samples_volume: trace_samples_medium's seven columns and the grid cells visited per sample (n,)."""
