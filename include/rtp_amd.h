@@ -1157,7 +1157,7 @@ rt_status rt_render_lit_adaptive_prior(rt_scene *scene, const rt_camera_data *ca
  * Identities, bit for bit: medium == NULL or sigma_t == 0 = rt_render_lit with the same lit (and every probe column: medium_events 0, the
  *   med state as initialised).  sigma_t > 0 with a region that no path ray and no shadow ray of the frame touches = rt_render_lit as well,
  *   through the medium's own kernels.
- * Left out: ~~heterogeneous~~ (rt_render_volume, "density grid" below) or chromatic extinction; more than one region; regions bounded by scene surfaces (fog inside a glass ball that
+ * Left out: ~~heterogeneous~~ (rt_render_volume, "density grid" below) or ~~chromatic extinction~~ (rt_render_chroma, "chromatic extinction" below); more than one region; regions bounded by scene surfaces (fog inside a glass ball that
  *   sits in the region is still fog); emission in the medium; the guarded walk; tiles and rt_context; ~~rt_render_lit_adaptive with a
  *   medium~~ (rt_render_volume_adaptive, "adaptive sampling under fog" below), ~~AOVs of the medium and the denoisers' handling of it~~ (rt_render_aov_volume, "AOVs under fog" below; the first-hit AOVs do not see it).
  * Checks, all before anything is enqueued: rt_render_lit's parameter checks come first, in its order (lens, nee, env_params); then the
@@ -1217,7 +1217,7 @@ rt_status rt_trace_samples_medium(rt_scene *scene, const rt_camera_data *cam_ope
  *   the only cell is the box's own exit, so tb = t1 and seg = (t1 - t0) * len).  volume == NULL = rt_render_medium with the same
  *   arguments, whatever its region.  sigma_t == 0 = rt_render_lit.  A grid of zeros = rt_render_lit in radiance, rays and the path, nee
  *   and env streams; med advances one draw per non-empty path interval.
- * Left out: chromatic extinction; more than one region or grid; emission in the medium; interpolation between cells (trilinear or any
+ * Left out: ~~chromatic extinction~~ (rt_render_chroma, "chromatic extinction" below); more than one region or grid; emission in the medium; interpolation between cells (trilinear or any
  *   other: the density is piecewise constant); ~~rt_render_lit_adaptive with a grid~~ (rt_render_volume_adaptive, "adaptive sampling under fog"
  *   below); ~~AOVs of the medium~~ (rt_render_aov_volume, "AOVs under fog" below); tiles and rt_context.
  * rt_volume: the grid on the device it was created on (the calling thread's current one), like an rt_env.  density is HOST memory, nx * ny
@@ -1241,6 +1241,66 @@ rt_status rt_trace_samples_volume(rt_scene *scene, const rt_camera_data *cam_ope
                                   const rt_volume *volume, int32_t n, const int32_t *ijs, float *radiance, int32_t *rays,
                                   int32_t *medium_events, uint32_t *final_seed, uint32_t *final_nee_seed, uint32_t *final_env_seed,
                                   uint32_t *final_medium_seed, int32_t *cells);
+
+/* ---- chromatic extinction ------------------------------------------------------------------------------------------
+ * rt_render_volume's estimator — the medium in its region, with or without a density grid in its box — with an extinction that differs per
+ * colour channel: channel k has sigma_k = sigma_t * tint[k], one float32 product made on the host.  Region, albedo, g, the box, the grid and
+ * RT_MEDIUM_STREAM_KEY stay the medium's and the volume's.  Everything of "participating medium" and "density grid" holds as written there
+ * except the two places where the extinction enters: the free flight of a path ray, which samples its distance by ONE channel's
+ * extinction and carries a weight per channel from then on, and the transmittance of a shadow ray, which is per channel.  float32 in the
+ * order written, nothing fused, division correctly rounded; log_libm and exp_libm as in "participating medium".
+ *
+ * Density length A of a non-empty interval [t0, t1] of a ray (o, d), len = sqrtf(lensq(d)).  Without a grid: A = (t1 - t0) * len.  With a
+ *   grid: the walk of "density grid" with sigma_t taken as 1 (sigma_c = 1.0f * rho_c = rho_c): A = acc, acc = acc + rho_c * seg over the
+ *   visited cells in visit order.  A free-flight walk keeps that sum as well, over the cells it passed without an event.
+ * Transmittance of channel k over A: Tr_k = 1 exactly when sigma_k == 0 (no multiplication: A may be +inf); otherwise
+ *   Tr_k = exp_libm(-(sigma_k * A)).
+ * Free flight (every finished PATH ray with a non-empty interval).  u = random_float(med); u == 0: no event, unchanged throughput, nothing
+ *   more is drawn.  Otherwise uc = random_float(med), j = min(2, (int)(uc * 3.0f)), and the target R = +inf when sigma_j == 0, otherwise
+ *   R = -log_libm(u) / sigma_j.  Without a grid there is an event iff R < (t1 - t0) * len, at t = t0 + R / len.  With a grid the free-flight
+ *   walk of "density grid" runs on rho_c with rem = R: a visited cell with rho_c > 0: s = rem / rho_c; s < seg: an event at t = ta + s / len;
+ *   otherwise rem = rem - rho_c * seg.  x = o + t * d.  At an event A = R, the target itself; without one A is the whole interval's.
+ * Weights: single-sample MIS over the three channels (the balance heuristic of the three distance densities, each chosen with
+ *   probability 1/3), unbiased per channel.
+ *   Event: e_k = sigma_k * Tr_k; den = (e_0 + e_1) + e_2; beta_k = beta_k * w_k, w_k = min(3.0f, (3.0f * e_k) / den); then the medium vertex of "participating
+ *     medium" at x, unchanged (its beta_in is this weighted beta).
+ *   No event: den = (Tr_0 + Tr_1) + Tr_2; beta_k = beta_k * w_k, w_k = min(3.0f, (3.0f * Tr_k) / den); then the surface vertex or the miss of rt_render_lit.
+ *   Each weight lies in [0, 3]: each term of den is one of the numerators over 3, so the exact quotient cannot pass 3; the float32 one can,
+ *   by one ulp (the product and the quotient each round), which the min takes back.  den > 0 in both cases: the channel that was
+ *   sampled contributes Tr_j of about u (and sigma_j > 0) at an event; without one Tr_j > u, up to rounding, or Tr_j = 1 (sigma_j == 0).
+ * Shadow rays.  Channel k of a light-sample contribution is multiplied by Tr_k over the A of its shadow ray's interval.  An empty interval
+ *   leaves it unchanged, and exp is not called.
+ * MIS.  The weights of the light samples stay those of the directional densities: the path's survival to a light is now an unbiased
+ *   per-channel ESTIMATE of Tr_k instead of Tr_k itself, and the weights depend on the direction only.
+ * Region 0: as in "participating medium" — with sigma_t > 0 the environment is not sampled, even when some sigma_k is 0: the path's misses
+ *   carry the environment.
+ *
+ * Identities, bit for bit: tint[0] == tint[1] == tint[2] == e hands the call over whole to rt_render_volume (which hands on to
+ *   rt_render_medium or rt_render_lit as it does) with the medium's sigma_t replaced by the float product sigma_t * e; this covers chroma
+ *   == NULL, the default tint and e == 0, and the probe's cells column is then that call's.  So does a medium with sigma_t == 0 (or no
+ *   medium) under any tint.  A 1 x 1 x 1 grid of density 1 = the homogeneous box under the same tint, through the grid's own chroma kernels
+ *   (s = R / 1, acc = seg).  volume == NULL = the homogeneous chroma kernels, in any region.
+ * Left out: the adaptive, AOV and denoise calls with a tint; choosing the channel by the path's throughput instead of uniformly; a tint per
+ *   cell; emission in the medium; tiles and rt_context; the guarded walk.
+ * Checks, all before anything is enqueued: rt_render_volume's, in its order up to and including the volume's region check; then
+ *   RT_ERR_INVALID_ARG for struct_bytes below 8, a tint channel that is negative, NaN or infinite, a product sigma_t * tint[k] that is not
+ *   finite — still before the scene is looked at; then the null scene, and rt_render_volume's remaining checks.  The messages name
+ *   rt_render_chroma (rt_trace_samples_chroma).  Handle state and timing: as rt_render_lit. */
+typedef struct rt_chroma_params {   /* IN, caller-sized like rt_medium_params */
+    uint32_t struct_bytes;
+    float    tint[3];       /* the factor on sigma_t per channel, each >= 0 and finite */
+} rt_chroma_params;
+/* Defaults into *p: tint = 1, 1, 1 (grey: rt_render_volume itself); struct_bytes = sizeof(rt_chroma_params). */
+void rt_chroma_params_init(rt_chroma_params *p);
+/* rt_render_volume under the tint (chroma NULL: the defaults; volume NULL: no grid). */
+rt_status rt_render_chroma(rt_scene *scene, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium,
+                           const rt_volume *volume, const rt_chroma_params *chroma, const rt_shard *shard, int32_t sample_first,
+                           float *d_fb_sum, void *hip_stream, int32_t sync, rt_timing *timing);
+/* Probe for tests, HOST memory: rt_trace_samples_volume's columns for the estimator of rt_render_chroma. */
+rt_status rt_trace_samples_chroma(rt_scene *scene, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium,
+                                  const rt_volume *volume, const rt_chroma_params *chroma, int32_t n, const int32_t *ijs, float *radiance,
+                                  int32_t *rays, int32_t *medium_events, uint32_t *final_seed, uint32_t *final_nee_seed,
+                                  uint32_t *final_env_seed, uint32_t *final_medium_seed, int32_t *cells);
 
 /* ---- adaptive sampling under fog -----------------------------------------------------------------------------------
  * rt_render_lit_adaptive_prior's rule, statistics, rounds and prior on rt_render_volume's estimator.  No new arithmetic: a sample is

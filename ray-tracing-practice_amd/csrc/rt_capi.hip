@@ -22,6 +22,7 @@
 #include "rt_light.hip.inc"
 #include "rt_medium.hip.inc"
 #include "rt_volume.hip.inc"
+#include "rt_chroma.hip.inc"
 #include "rt_aov_fog.hip.inc"
 // Developer build only (make dev → librtp_amd_dev.so, -DRTP_DEV_BUILD): the rt_debug_* entry points (exhaustive on-device checks of
 // recip / sqrt_cr / sphere_root, the device LBVH builder on its own, the tripwire, the RTP_STATS counters) at the end of this file.
@@ -3438,11 +3439,28 @@ void launch_fog_probe(const rtk::KParams &KP, const rtk::VolumeLit<Table> &T, co
                       int32_t *d_events, int32_t *d_cells) {
     hipLaunchKernelGGL((rtk::volume_probe_kernel<kLens, Table>), dim3((n + 255) / 256), dim3(256), 0, 0, KP, T, C, d_nee, d_env, d_med, d_events, d_cells);
 }
-// rt_trace_samples_medium and rt_trace_samples_volume (volume, cells: the latter's; null in the former) from their probe launch on: the
-// caller has made its checks and handed over what has no medium or no grid.  `what` starts every refusal.
+extern "C++" template <bool kLens, class Base>
+void launch_fog_probe(const rtk::KParams &KP, const rtk::ChromaLit<Base> &T, const rtk::LensCam &C, int32_t n, uint32_t *d_nee, uint32_t *d_env, uint32_t *d_med,
+                      int32_t *d_events, int32_t *d_cells) {
+    hipLaunchKernelGGL((rtk::chroma_probe_kernel<kLens, Base>), dim3((n + 255) / 256), dim3(256), 0, 0, KP, T, C, d_nee, d_env, d_med, d_events, d_cells);
+}
+// The chroma kernels' light (rt_render_chroma): the medium's or the grid's with sigma_t = 1, and the three channels' extinctions beside it
+extern "C++" template <class F>
+rt_status with_chroma_lit(rt_scene *sc, const LitSetup &S, const rtk::MediumDev &M, const rt_volume *volume, const float *sigma, F &&f) {
+    rtk::MediumDev M1 = M;
+    M1.sigma_t = 1.0f;
+    auto chroma = [&](const auto &B) {
+        const rtk::ChromaLit<std::decay_t<decltype(B)>> T{B, sigma[0], sigma[1], sigma[2]};
+        return f(T);
+    };
+    return volume ? with_volume_lit(sc, S, M1, volume, chroma) : with_medium_lit(sc, S, M1, chroma);
+}
+// rt_trace_samples_medium, rt_trace_samples_volume (volume, cells: the latter's; null in the former) and rt_trace_samples_chroma (sigma: its
+// three extinctions; null in the others) from their probe launch on: the caller has made its checks and handed over what has no medium
+// or no grid.  `what` starts every refusal.
 rt_status fog_probe(const char *what, rt_scene *sc, const rt_camera_data *cam_open, const LitSetup &S, const rtk::MediumDev &M, const rt_volume *volume, rtk::KParams &P,
                     int32_t n, const int32_t *ijs, float *radiance, int32_t *rays, int32_t *medium_events, uint32_t *final_seed, uint32_t *final_nee_seed,
-                    uint32_t *final_env_seed, uint32_t *final_medium_seed, int32_t *cells) {
+                    uint32_t *final_env_seed, uint32_t *final_medium_seed, int32_t *cells, const float *sigma = nullptr) {
     const std::string w(what);
     uint32_t *d_med = nullptr;
     int32_t *d_events = nullptr, *d_cells = nullptr;
@@ -3456,6 +3474,7 @@ rt_status fog_probe(const char *what, rt_scene *sc, const rt_camera_data *cam_op
             else launch_fog_probe<false>(KP, T, S.C, n, d_nee, d_env, d_med, d_events, d_cells);
             return RT_OK;
         };
+        if (sigma) return with_chroma_lit(sc, S, M, volume, sigma, probe);
         return volume ? with_volume_lit(sc, S, M, volume, probe) : with_medium_lit(sc, S, M, probe);
     });
     if (st != RT_OK) return st;
@@ -3641,6 +3660,94 @@ rt_status rt_trace_samples_volume(rt_scene *sc, const rt_camera_data *cam_open, 
         return RT_OK;
     }
     return fog_probe(what, sc, cam_open, S, M, volume, P, n, ijs, radiance, rays, medium_events, final_seed, final_nee_seed, final_env_seed, final_medium_seed, cells);
+}
+
+// ---- rt_render_chroma / rt_trace_samples_chroma (rtp_amd.h, "chromatic extinction"): rt_render_volume with an extinction
+// per channel.  Equal tints (and no medium) are rt_render_volume itself at sigma_t * e; otherwise the kernels of rt_chroma.hip.inc.
+void rt_chroma_params_init(rt_chroma_params *p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->struct_bytes = (uint32_t)sizeof(*p);
+    p->tint[0] = p->tint[1] = p->tint[2] = 1.0f;
+}
+namespace {
+// The chroma call's setup.  grey: the call is rt_render_volume's with `handed` as its medium
+struct ChromaSetup {
+    LitSetup S;
+    rtk::MediumDev M{};
+    float sigma[3] = {0.0f, 0.0f, 0.0f};
+    bool grey = false;
+    rt_medium_params handed;
+};
+// rt_render_volume's parameter checks in its order, then the tint's: everything before the scene is looked at
+rt_status chroma_setup(const char *what, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium, const rt_volume *volume,
+                       const rt_chroma_params *chroma, ChromaSetup &X) {
+    const std::string w(what);
+    if (const rt_status st = lit_setup(what, cam_open, lit, X.S)) return st;
+    if (const rt_status st = medium_setup(what, medium, X.M)) return st;
+    if (const rt_status st = volume_setup(what, medium, X.M, volume)) return st;
+    rt_chroma_params cp;
+    rt_chroma_params_init(&cp);
+    if (const rt_status st = take_params(w, "rt_chroma_params", chroma, cp)) return st;
+    for (int k = 0; k < 3; ++k)
+        if (!(std::isfinite(cp.tint[k]) && cp.tint[k] >= 0.0f)) return fail(RT_ERR_INVALID_ARG, w + ": a tint channel is negative, NaN or infinite");
+    for (int k = 0; k < 3; ++k) {
+        X.sigma[k] = X.M.sigma_t * cp.tint[k];
+        if (!std::isfinite(X.sigma[k])) return fail(RT_ERR_INVALID_ARG, w + ": sigma_t * tint is not finite in a channel");
+    }
+    X.grey = (cp.tint[0] == cp.tint[1] && cp.tint[1] == cp.tint[2]) || !(X.M.sigma_t > 0.0f);
+    if (X.grey) {
+        rt_medium_params_init(&X.handed);
+        X.handed.region = X.M.region;
+        X.handed.sigma_t = X.sigma[0];
+        X.handed.g = X.M.g;
+        for (int k = 0; k < 3; ++k) {
+            X.handed.albedo[k] = X.M.albedo[k];
+            X.handed.a[k] = X.M.a[k];
+            X.handed.b[k] = X.M.b[k];
+        }
+    }
+    return RT_OK;
+}
+}  // namespace
+
+rt_status rt_render_chroma(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium, const rt_volume *volume,
+                           const rt_chroma_params *chroma, const rt_shard *shard, int32_t sample_first, float *d_fb_sum, void *hip_stream, int32_t sync,
+                           rt_timing *timing) {
+    ChromaSetup X;
+    if (const rt_status st = chroma_setup("rt_render_chroma", cam_open, lit, medium, volume, chroma, X)) return st;
+    if (!sc) return fail(RT_ERR_INVALID_ARG, "rt_render_chroma: null scene");
+    if (volume && volume->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_render_chroma: the volume was created on another device than the scene");
+    if (X.grey) return rt_render_volume(sc, cam_open, lit, &X.handed, volume, shard, sample_first, d_fb_sum, hip_stream, sync, timing);
+    const LitSetup &S = X.S;
+    auto with_light = [&](auto frame) {
+        return with_chroma_lit(sc, S, X.M, volume, X.sigma, [&](const auto &T) { return frame(lit_kernels_of(S.lens, T).frame, &T); });
+    };
+    return render_light_impl("rt_render_chroma", S.env ? &S.env->device : nullptr, with_light, sc, cam_open, shard, sample_first, d_fb_sum, hip_stream, sync, timing,
+                             &S.C);
+}
+
+rt_status rt_trace_samples_chroma(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium, const rt_volume *volume,
+                                  const rt_chroma_params *chroma, int32_t n, const int32_t *ijs, float *radiance, int32_t *rays, int32_t *medium_events,
+                                  uint32_t *final_seed, uint32_t *final_nee_seed, uint32_t *final_env_seed, uint32_t *final_medium_seed, int32_t *cells) {
+    const char *what = "rt_trace_samples_chroma";
+    ChromaSetup X;
+    if (const rt_status st = chroma_setup(what, cam_open, lit, medium, volume, chroma, X)) return st;
+    if (n < 0 ||
+        (n > 0 && (!ijs || !radiance || !rays || !medium_events || !final_seed || !final_nee_seed || !final_env_seed || !final_medium_seed || !cells)))
+        return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_chroma: null argument");
+    if (X.grey)
+        return rt_trace_samples_volume(sc, cam_open, lit, &X.handed, volume, n, ijs, radiance, rays, medium_events, final_seed, final_nee_seed, final_env_seed,
+                                       final_medium_seed, cells);
+    rtk::KParams P;
+    rt_status st = fill_params(sc, cam_open, nullptr, P);
+    if (st != RT_OK) return st;
+    if ((st = check_device(sc)) != RT_OK) return st;
+    if (X.S.env && X.S.env->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_chroma: the environment was created on another device than the scene");
+    if (volume && volume->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_chroma: the volume was created on another device than the scene");
+    if (n == 0) return RT_OK;
+    return fog_probe(what, sc, cam_open, X.S, X.M, volume, P, n, ijs, radiance, rays, medium_events, final_seed, final_nee_seed, final_env_seed, final_medium_seed, cells,
+                     X.sigma);
 }
 
 void rt_timing_init(rt_timing *t) {

@@ -35,9 +35,9 @@ __device__ __forceinline__ int32_t volume_entry(float lo, float w, int32_t n, fl
 
 // The walk of the header over the non-empty interval [t0, t1] of the ray (o, d), len = |d|.  kFlight: v is rem on entry; true = an event,
 // v its parameter t.  Otherwise v is acc, the optical depth, and the result is false.  cells counts the cells visited (the probe's
-// column; the render kernels drop it)
-template <bool kFlight>
-__device__ __forceinline__ bool volume_walk(const MediumDev &M, const VolumeDev &V, f3 o, f3 d, float t0, float t1, float len, float &v, int32_t &cells) {
+// column; the render kernels drop it).  kAcc (a flight of rt_chroma.hip.inc): the flight keeps the optical depth of the cells it passed in acc as well
+template <bool kFlight, bool kAcc = false>
+__device__ __forceinline__ bool volume_walk(const MediumDev &M, const VolumeDev &V, f3 o, f3 d, float t0, float t1, float len, float &v, int32_t &cells, float &acc) {
     const float wx = (M.b[0] - M.a[0]) / (float)V.nx, wy = (M.b[1] - M.a[1]) / (float)V.ny, wz = (M.b[2] - M.a[2]) / (float)V.nz;
     int32_t cx = volume_entry(M.a[0], wx, V.nx, o.x + t0 * d.x);
     int32_t cy = volume_entry(M.a[1], wy, V.ny, o.y + t0 * d.y);
@@ -73,6 +73,7 @@ __device__ __forceinline__ bool volume_walk(const MediumDev &M, const VolumeDev 
                 }
                 v = v - sigma_c * seg;
             }
+            if (kAcc) acc = acc + sigma_c * seg;
         } else {
             v = v + sigma_c * seg;
         }
@@ -93,6 +94,11 @@ __device__ __forceinline__ bool volume_walk(const MediumDev &M, const VolumeDev 
         ta = tb;
     }
     return false;
+}
+template <bool kFlight>
+__device__ __forceinline__ bool volume_walk(const MediumDev &M, const VolumeDev &V, f3 o, f3 d, float t0, float t1, float len, float &v, int32_t &cells) {
+    float unused = 0.0f;
+    return volume_walk<kFlight, false>(M, V, o, d, t0, t1, len, v, cells, unused);
 }
 
 // ---- the grid's hooks in lit_probe_body and lit_render_body (rt_light.hip.inc, "what fog adds to a lit light"; DESIGN.md §31): the

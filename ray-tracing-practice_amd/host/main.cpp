@@ -66,6 +66,35 @@ int main(int argc, char *argv[]) {
             return 99;
         }
     }
+    // extension: `--lit … --fog SIGMA … [--fog-ball | --fog-box …] [--fog-grid FILE] --fog-tint R,G,B`: the fogged frames through
+    // rt_render_chroma — the extinction of colour channel k is SIGMA times its tint.  The flag needs --fog and is not for --fog-noise-target or
+    // --fog-denoise: no adaptive, AOV or denoise call takes a tint.  This block comes before those flags' own, so that the refusal names this flag.
+    bool fog_tint_on = false;
+    rt_chroma_params fog_tint;
+    rt_chroma_params_init(&fog_tint);
+    {
+        bool fog_flag = false;
+        std::string bad, other;
+        for (int a = 2; a < argc; ++a) {
+            const std::string arg = argv[a];
+            if (arg == "--fog") fog_flag = true;
+            if (arg == "--fog-noise-target" || arg == "--fog-denoise") other = arg;
+            if (arg == "--fog-tint") {
+                fog_tint_on = true;
+                char tail = 0;
+                bool ok = sscanf(a + 1 < argc ? argv[a + 1] : "", "%f,%f,%f%c", &fog_tint.tint[0], &fog_tint.tint[1], &fog_tint.tint[2], &tail) == 3;
+                for (int k = 0; ok && k < 3; ++k) ok = std::isfinite(fog_tint.tint[k]) && fog_tint.tint[k] >= 0.0f;
+                if (!ok) bad = "--fog-tint takes R,G,B: three finite numbers, none negative";
+            }
+        }
+        if (fog_tint_on && bad.empty() && !fog_flag) bad = "--fog-tint colours the extinction of --fog: it needs --lit --fog SIGMA";
+        if (fog_tint_on && bad.empty() && !other.empty())
+            bad = "--fog-tint cannot be combined with " + other + ": the adaptive, AOV and denoise calls take no tint (grey fog only)";
+        if (!bad.empty()) {
+            std::cerr << "rtp_main: " << bad << "\n";
+            return 99;
+        }
+    }
     // extension: `--lit … --fog SIGMA … [--fog-grid FILE] --fog-noise-target T[:min:batch:max]`: the fogged frames through
     // rt_render_volume_adaptive (adaptive sampling under the medium or the grid, default 16:16:256) and rt_tonemap_spp.  The flag needs --fog
     // and is not for --adaptive, --denoise*, --aov, --stop-rule, --stop-history or --noise-target.  This block comes before those flags' own,
@@ -555,7 +584,8 @@ int main(int argc, char *argv[]) {
                     return 99;
                 }
                 rtp::gpu_render_lens(params, desc, lens, shutter, aov, denoise, nullptr, nullptr, nullptr, &lit, fog_noise_on ? &fog_noise : noise_on ? &noise : nullptr,
-                                     denoise_adaptive, &stop_rule, denoise_adaptive_temporal, fog_on ? &fog : nullptr, stop_history, fog_volume, fog_denoise);
+                                     denoise_adaptive, &stop_rule, denoise_adaptive_temporal, fog_on ? &fog : nullptr, stop_history, fog_volume, fog_denoise,
+                                     fog_tint_on ? &fog_tint : nullptr);
                 rt_volume_destroy(fog_volume);
                 rt_env_destroy(lit_env);
                 return 0;

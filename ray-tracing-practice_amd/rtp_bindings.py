@@ -333,6 +333,29 @@ def _medium_struct(medium):
     return _struct(medium, MediumParams, medium_params)
 
 
+class ChromaParams(_Sized):
+    """rt_chroma_params (include/rtp_amd.h, "chromatic extinction"): an IN structure of the caller's size — struct_bytes is set on
+    construction; tint is 0 until rt_chroma_params_init (chroma_params()) fills the defaults."""
+    _fields_ = [("struct_bytes", C.c_uint32), ("tint", C.c_float * 3)]
+
+
+def chroma_params(tint=1.0):
+    """rt_chroma_params with the library's defaults, then tint: one number or three.  Nothing is checked here: the library refuses what it
+    does not take."""
+    p = _params(ChromaParams, "rt_chroma_params", (), {})
+    t = np.broadcast_to(np.asarray(tint, dtype=np.float32), (3,))
+    for k in range(3):
+        p.tint[k] = float(t[k])
+    return p
+
+
+def _chroma_struct(chroma):
+    """None → NULL (grey); a ChromaParams as it is; a dict → chroma_params(**dict); anything else is the tint itself."""
+    if chroma is None or isinstance(chroma, (ChromaParams, dict)):
+        return _struct(chroma, ChromaParams, chroma_params)
+    return C.byref(chroma_params(tint=chroma))
+
+
 class Env:
     """rt_env: an octahedral environment map with its sampling table on the current device.  Env(rgb) takes an (n, n, 3) array;
     Env.from_equirect(image, n) resamples a lat-long image first.  A context manager; close() destroys the object."""
@@ -481,7 +504,7 @@ _P, _VP, _STR, _INT, _I32, _U32, _I64, _U64 = C.POINTER, C.c_void_p, C.c_char_p,
 _STATUS = C.c_int
 _DESC, _CFG, _CAM, _SHARD, _TIMING, _AOV = _P(SceneDesc), _P(Config), _P(CameraData), _P(Shard), _P(Timing), _P(AovBuffers)
 _DENOISE, _ADAPTIVE, _STOP, _LENS, _NEE, _ENV = _P(DenoiseParams), _P(AdaptiveParams), _P(StopParams), _P(LensParams), _P(NeeParams), _P(EnvParams)
-_LIT, _MEDIUM = _P(LitParams), _P(MediumParams)
+_LIT, _MEDIUM, _CHROMA = _P(LitParams), _P(MediumParams), _P(ChromaParams)
 _OUT = [_VP, _I32, _TIMING]          # how a render call ends: void *hip_stream, int32_t sync, rt_timing *timing
 
 # the calls every build has: a library without one of them fails at load
@@ -572,6 +595,9 @@ _AMD_LATER = {
     "rt_trace_samples_volume": (_STATUS, [_VP, _CAM, _LIT, _MEDIUM, _VP, _I32] + [_VP] * 9),
     "rt_render_volume_adaptive": (_STATUS, [_VP, _CAM, _LIT, _MEDIUM, _VP, _ADAPTIVE, _STOP, _VP, _SHARD, _I32, _VP, _VP, _VP, *_OUT]),
     "rt_render_aov_volume": (_STATUS, [_VP, _CAM, _LIT, _MEDIUM, _VP, _SHARD, _I32, _AOV, _VP, *_OUT]),
+    "rt_chroma_params_init": (None, [_CHROMA]),
+    "rt_render_chroma": (_STATUS, [_VP, _CAM, _LIT, _MEDIUM, _VP, _CHROMA, _SHARD, _I32, _VP, *_OUT]),
+    "rt_trace_samples_chroma": (_STATUS, [_VP, _CAM, _LIT, _MEDIUM, _VP, _CHROMA, _I32] + [_VP] * 9),
 }
 # the calls that take a prior: their _rule call (the judgement: the call itself) and, last, the device address of the prior
 for _base, _prior in (("rt_render_adaptive_rule", "rt_render_adaptive_prior"), ("rt_render_lit_adaptive_rule", "rt_render_lit_adaptive_prior"),
@@ -1437,6 +1463,30 @@ class DeviceScene:
         lit = lit_params(cam_close=cam_close, lens=lens, emitters=emitters, nee=nee, env=env, env_params=env_params)
         _check(amd_lib().rt_trace_samples_volume(self._h, C.byref(cam), C.byref(lit), _medium_struct(medium), _volume_handle(volume), n,
                                                  ijs.ctypes.data, *(a.ctypes.data for a in out)), "rt_trace_samples_volume")
+        return out
+
+    def render_chroma(self, cam, d_fb_ptr, *, medium=None, volume=None, tint=None, cam_close=None, lens=None, emitters=True, nee=None, env=None,
+                      env_params=None, shard=None, stream=None, sync=True, sample_first=0):
+        """rt_render_chroma: rt_render_volume with an extinction per colour channel, sigma_t * tint[k] (tint: None, one number or three, a
+        dict of chroma_params' keywords or a ChromaParams; the other keywords are render_volume's).  Returns the rt_timing of this call."""
+        lit = lit_params(cam_close=cam_close, lens=lens, emitters=emitters, nee=nee, env=env, env_params=env_params)
+        return self._call("rt_render_chroma", C.byref(cam), C.byref(lit), _medium_struct(medium), _volume_handle(volume), _chroma_struct(tint), _ref(shard),
+                          sample_first, C.c_void_p(d_fb_ptr), *_stream_sync(stream, sync))
+
+    def render_chroma_to_host(self, cam, *, medium=None, volume=None, tint=None, cam_close=None, lens=None, emitters=True, nee=None, env=None,
+                              env_params=None, shard=None, sample_first=0):
+        """rt_render_chroma through a fresh device buffer: (rows, width, 3) float32 sums and the rt_timing."""
+        return _frame_to_host(cam, shard, lambda d: self.render_chroma(cam, d, medium=medium, volume=volume, tint=tint, cam_close=cam_close, lens=lens,
+                                                                       emitters=emitters, nee=nee, env=env, env_params=env_params, shard=shard,
+                                                                       sample_first=sample_first))
+
+    def trace_samples_chroma(self, cam, ijs, *, medium=None, volume=None, tint=None, cam_close=None, lens=None, emitters=True, nee=None, env=None,
+                             env_params=None):
+        """rt_trace_samples_chroma: trace_samples_volume's eight columns under the tint."""
+        ijs, n, out = _probe(ijs, _RGB, _COUNT, _COUNT, _SEED, _SEED, _SEED, _SEED, _COUNT)
+        lit = lit_params(cam_close=cam_close, lens=lens, emitters=emitters, nee=nee, env=env, env_params=env_params)
+        _check(amd_lib().rt_trace_samples_chroma(self._h, C.byref(cam), C.byref(lit), _medium_struct(medium), _volume_handle(volume), _chroma_struct(tint), n,
+                                                 ijs.ctypes.data, *(a.ctypes.data for a in out)), "rt_trace_samples_chroma")
         return out
 
     def last_kernel_ms(self):
