@@ -1158,7 +1158,7 @@ rt_status rt_render_lit_adaptive_prior(rt_scene *scene, const rt_camera_data *ca
  *   med state as initialised).  sigma_t > 0 with a region that no path ray and no shadow ray of the frame touches = rt_render_lit as well,
  *   through the medium's own kernels.
  * Left out: ~~heterogeneous~~ (rt_render_volume, "density grid" below) or ~~chromatic extinction~~ (rt_render_chroma, "chromatic extinction" below); more than one region; regions bounded by scene surfaces (fog inside a glass ball that
- *   sits in the region is still fog); emission in the medium; the guarded walk; tiles and rt_context; ~~rt_render_lit_adaptive with a
+ *   sits in the region is still fog); ~~emission in the medium~~ (rt_render_glow, "emission in the medium" below); the guarded walk; tiles and rt_context; ~~rt_render_lit_adaptive with a
  *   medium~~ (rt_render_volume_adaptive, "adaptive sampling under fog" below), ~~AOVs of the medium and the denoisers' handling of it~~ (rt_render_aov_volume, "AOVs under fog" below; the first-hit AOVs do not see it).
  * Checks, all before anything is enqueued: rt_render_lit's parameter checks come first, in its order (lens, nee, env_params); then the
  *   medium's, still before the scene is looked at; then the scene's and the camera's as in rt_render_lit.  RT_ERR_INVALID_ARG for struct_bytes below 8,
@@ -1217,7 +1217,7 @@ rt_status rt_trace_samples_medium(rt_scene *scene, const rt_camera_data *cam_ope
  *   the only cell is the box's own exit, so tb = t1 and seg = (t1 - t0) * len).  volume == NULL = rt_render_medium with the same
  *   arguments, whatever its region.  sigma_t == 0 = rt_render_lit.  A grid of zeros = rt_render_lit in radiance, rays and the path, nee
  *   and env streams; med advances one draw per non-empty path interval.
- * Left out: ~~chromatic extinction~~ (rt_render_chroma, "chromatic extinction" below); more than one region or grid; emission in the medium; interpolation between cells (trilinear or any
+ * Left out: ~~chromatic extinction~~ (rt_render_chroma, "chromatic extinction" below); more than one region or grid; ~~emission in the medium~~ (rt_render_glow, "emission in the medium" below); interpolation between cells (trilinear or any
  *   other: the density is piecewise constant); ~~rt_render_lit_adaptive with a grid~~ (rt_render_volume_adaptive, "adaptive sampling under fog"
  *   below); ~~AOVs of the medium~~ (rt_render_aov_volume, "AOVs under fog" below); tiles and rt_context.
  * rt_volume: the grid on the device it was created on (the calling thread's current one), like an rt_env.  density is HOST memory, nx * ny
@@ -1281,7 +1281,7 @@ rt_status rt_trace_samples_volume(rt_scene *scene, const rt_camera_data *cam_ope
  *   medium) under any tint.  A 1 x 1 x 1 grid of density 1 = the homogeneous box under the same tint, through the grid's own chroma kernels
  *   (s = R / 1, acc = seg).  volume == NULL = the homogeneous chroma kernels, in any region.
  * Left out: the adaptive, AOV and denoise calls with a tint; choosing the channel by the path's throughput instead of uniformly; a tint per
- *   cell; emission in the medium; tiles and rt_context; the guarded walk.
+ *   cell; ~~emission in the medium~~ (rt_render_glow, "emission in the medium" below); tiles and rt_context; the guarded walk.
  * Checks, all before anything is enqueued: rt_render_volume's, in its order up to and including the volume's region check; then
  *   RT_ERR_INVALID_ARG for struct_bytes below 8, a tint channel that is negative, NaN or infinite, a product sigma_t * tint[k] that is not
  *   finite — still before the scene is looked at; then the null scene, and rt_render_volume's remaining checks.  The messages name
@@ -1301,6 +1301,60 @@ rt_status rt_trace_samples_chroma(rt_scene *scene, const rt_camera_data *cam_ope
                                   const rt_volume *volume, const rt_chroma_params *chroma, int32_t n, const int32_t *ijs, float *radiance,
                                   int32_t *rays, int32_t *medium_events, uint32_t *final_seed, uint32_t *final_nee_seed,
                                   uint32_t *final_env_seed, uint32_t *final_medium_seed, int32_t *cells);
+
+/* ---- emission in the medium ----------------------------------------------------------------------------------------
+ * rt_render_volume's estimator — the medium in its region, with or without a density grid in its box — with a medium that also EMITS: fire,
+ * glowing gas.  The emission coefficient at a point is radiance_k * h, with h = 1 over the whole region (source 0), the density of the
+ * point's cell (source 1) or the value of the point's cell in a second grid of the volume's dimensions, the heat (source 2).  Everything of
+ * "participating medium" and "density grid" holds as written there, with one addition: after the free flight of every finished PATH ray
+ * with a non-empty interval, and before anything that vertex itself adds to the sample's colour, the radiance the medium emitted towards the
+ * ray's origin is added.  No draw, no exp and no shadow ray are added: the ray's own free flight is an unbiased track-length estimator — it
+ * ends at a distance S with P(S > t) = Tr(t), and the integral of Tr(t) * eps(t) over the interval is the expectation of eps integrated
+ * over the stretch the flight flew.  float32 in the order written, nothing fused, division correctly rounded; log_libm as in "participating
+ * medium".
+ *
+ * Without a grid (source 0 only).  whole = (t1 - t0) * len.  The flight is the grey one: u = random_float(med); u == 0: D = whole and there
+ *   is no event.  Otherwise s = -log_libm(u) / sigma_t; an event iff s < whole, at t = t0 + s / len; D = s at an event, whole without one.
+ *   D finite: color_k = color_k + beta_k * (radiance_k * D), beta the throughput the ray arrived with (before the medium vertex's albedo).
+ *   D = +inf (region 0, a miss, u == 0 — nothing else): nothing is added.
+ * With a grid.  E = 0.  rem = +inf when u == 0 — the walk still runs, finds no event and counts its cells — otherwise rem = -log_libm(u).
+ *   Every visited cell: h_c = 1.0f, rho_c or heat_c by source; seg as in "density grid".  sigma_c > 0: s = rem / sigma_c; s < seg:
+ *   E = E + h_c * s, an event at t = ta + s / len, and the walk ends; otherwise rem = rem - sigma_c * seg.  Every cell that is passed
+ *   without an event, sigma_c == 0 or not: E = E + h_c * seg.  Then color_k = color_k + beta_k * (radiance_k * E).
+ * Then the medium vertex at the event, or the surface vertex or the miss, unchanged.  Shadow rays emit nothing and are attenuated as before.
+ *   The glow is found by path rays only and never light-sampled: it has weight 1 and enters no MIS weight.  The environment rule of region
+ *   0 is unchanged.
+ * Probe: rt_trace_samples_volume's columns and glow_length, the float32 sum of D or E over the sample's path rays in order (0 after a
+ *   handover); cells counts the walk under u == 0 as well.
+ *
+ * Identities, bit for bit: glow == NULL or radiance 0, 0, 0 hands the call over whole to rt_render_volume with the same arguments (heat is
+ *   checked but not read).  A 1 x 1 x 1 grid of density 1 under source 0 or 1 = the homogeneous box under source 0, through the grid's own
+ *   glow kernels (s = rem / sigma_t, E = 0 + 1 * s).  Source 2 with a heat grid equal to the density grid = source 1.
+ * Left out: light-sampling the glow (fire lights a room by the paths that happen to cross it); a glow with sigma_t == 0 (the estimator rides
+ *   on the free flight); a glow under a tint (rt_render_chroma); the adaptive, AOV and denoise calls with a glow; trilinear heat (h is
+ *   piecewise constant like the density); blackbody colour from temperature; tiles and rt_context; the guarded walk.
+ * Checks, all before anything is enqueued: rt_render_volume's, in its order up to and including the volume's region check; then
+ *   RT_ERR_INVALID_ARG for struct_bytes below 8, source outside {0, 1, 2}, a radiance channel that is negative, NaN or infinite, a non-zero
+ *   radiance without a medium or with sigma_t == 0 (a glow without extinction has no kernel), source 1 or 2 without a volume, source 2
+ *   without heat or with a heat grid of other dimensions than the volume's, heat given under source 0 or 1 — still before the scene is
+ *   looked at; then the null scene, heat's device (and the volume's) against the scene's, and rt_render_volume's remaining checks.  The
+ *   messages name rt_render_glow (rt_trace_samples_glow).  Handle state and timing: as rt_render_lit. */
+typedef struct rt_glow_params {   /* IN, caller-sized like rt_chroma_params */
+    uint32_t struct_bytes;
+    int32_t  source;        /* 0: uniform over the region (h = 1); 1: the density grid (h_c = rho_c); 2: a heat grid (h_c = heat_c) */
+    float    radiance[3];   /* emitted radiance per unit length at h = 1, per channel, each >= 0 and finite; 0, 0, 0 = no glow */
+} rt_glow_params;
+/* Defaults into *p: source 0, radiance 0, 0, 0 (no glow: rt_render_volume itself); struct_bytes = sizeof(rt_glow_params). */
+void rt_glow_params_init(rt_glow_params *p);
+/* rt_render_volume with the glow (glow NULL: the defaults; volume NULL: no grid; heat: an rt_volume of the volume's dimensions, source 2 only). */
+rt_status rt_render_glow(rt_scene *scene, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium,
+                         const rt_volume *volume, const rt_glow_params *glow, const rt_volume *heat, const rt_shard *shard, int32_t sample_first,
+                         float *d_fb_sum, void *hip_stream, int32_t sync, rt_timing *timing);
+/* Probe for tests, HOST memory: rt_trace_samples_volume's columns and glow_length for the estimator of rt_render_glow. */
+rt_status rt_trace_samples_glow(rt_scene *scene, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium,
+                                const rt_volume *volume, const rt_glow_params *glow, const rt_volume *heat, int32_t n, const int32_t *ijs,
+                                float *radiance, int32_t *rays, int32_t *medium_events, uint32_t *final_seed, uint32_t *final_nee_seed,
+                                uint32_t *final_env_seed, uint32_t *final_medium_seed, int32_t *cells, float *glow_length);
 
 /* ---- adaptive sampling under fog -----------------------------------------------------------------------------------
  * rt_render_lit_adaptive_prior's rule, statistics, rounds and prior on rt_render_volume's estimator.  No new arithmetic: a sample is

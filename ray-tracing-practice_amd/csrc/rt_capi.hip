@@ -22,6 +22,7 @@
 #include "rt_light.hip.inc"
 #include "rt_medium.hip.inc"
 #include "rt_volume.hip.inc"
+#include "rt_glow.hip.inc"
 #include "rt_chroma.hip.inc"
 #include "rt_aov_fog.hip.inc"
 // Developer build only (make dev → librtp_amd_dev.so, -DRTP_DEV_BUILD): the rt_debug_* entry points (exhaustive on-device checks of
@@ -3431,18 +3432,23 @@ rt_status with_fog_lit(rt_scene *sc, const LitSetup &S, const rtk::MediumDev &M,
 // the probe kernel of a light with fog (d_cells: the grid's column)
 extern "C++" template <bool kLens, class Table>
 void launch_fog_probe(const rtk::KParams &KP, const rtk::MediumLit<Table> &T, const rtk::LensCam &C, int32_t n, uint32_t *d_nee, uint32_t *d_env, uint32_t *d_med,
-                      int32_t *d_events, int32_t *) {
+                      int32_t *d_events, int32_t *, float *) {
     hipLaunchKernelGGL((rtk::medium_probe_kernel<kLens, Table>), dim3((n + 255) / 256), dim3(256), 0, 0, KP, T, C, d_nee, d_env, d_med, d_events);
 }
 extern "C++" template <bool kLens, class Table>
 void launch_fog_probe(const rtk::KParams &KP, const rtk::VolumeLit<Table> &T, const rtk::LensCam &C, int32_t n, uint32_t *d_nee, uint32_t *d_env, uint32_t *d_med,
-                      int32_t *d_events, int32_t *d_cells) {
+                      int32_t *d_events, int32_t *d_cells, float *) {
     hipLaunchKernelGGL((rtk::volume_probe_kernel<kLens, Table>), dim3((n + 255) / 256), dim3(256), 0, 0, KP, T, C, d_nee, d_env, d_med, d_events, d_cells);
 }
 extern "C++" template <bool kLens, class Base>
 void launch_fog_probe(const rtk::KParams &KP, const rtk::ChromaLit<Base> &T, const rtk::LensCam &C, int32_t n, uint32_t *d_nee, uint32_t *d_env, uint32_t *d_med,
-                      int32_t *d_events, int32_t *d_cells) {
+                      int32_t *d_events, int32_t *d_cells, float *) {
     hipLaunchKernelGGL((rtk::chroma_probe_kernel<kLens, Base>), dim3((n + 255) / 256), dim3(256), 0, 0, KP, T, C, d_nee, d_env, d_med, d_events, d_cells);
+}
+extern "C++" template <bool kLens, class Base>
+void launch_fog_probe(const rtk::KParams &KP, const rtk::GlowLit<Base> &T, const rtk::LensCam &C, int32_t n, uint32_t *d_nee, uint32_t *d_env, uint32_t *d_med,
+                      int32_t *d_events, int32_t *d_cells, float *d_glow) {
+    hipLaunchKernelGGL((rtk::glow_probe_kernel<kLens, Base>), dim3((n + 255) / 256), dim3(256), 0, 0, KP, T, C, d_nee, d_env, d_med, d_events, d_cells, d_glow);
 }
 // The chroma kernels' light (rt_render_chroma): the medium's or the grid's with sigma_t = 1, and the three channels' extinctions beside it
 extern "C++" template <class F>
@@ -3455,25 +3461,47 @@ rt_status with_chroma_lit(rt_scene *sc, const LitSetup &S, const rtk::MediumDev 
     };
     return volume ? with_volume_lit(sc, S, M1, volume, chroma) : with_medium_lit(sc, S, M1, chroma);
 }
-// rt_trace_samples_medium, rt_trace_samples_volume (volume, cells: the latter's; null in the former) and rt_trace_samples_chroma (sigma: its
-// three extinctions; null in the others) from their probe launch on: the caller has made its checks and handed over what has no medium
-// or no grid.  `what` starts every refusal.
+// The glow kernels' light (rt_render_glow): the medium's or the grid's as the grey kernels hold it, and the radiance beside it; over a grid
+// also the cells' h (heat: null = 1, source 0; the density itself, source 1; a heat grid's values, source 2)
+struct GlowDev {
+    float radiance[3];
+    const float *heat;
+};
+extern "C++" template <class F>
+rt_status with_glow_lit(rt_scene *sc, const LitSetup &S, const rtk::MediumDev &M, const rt_volume *volume, const GlowDev &G, F &&f) {
+    if (volume)
+        return with_volume_lit(sc, S, M, volume, [&](const auto &B) {
+            const rtk::GlowLit<std::decay_t<decltype(B)>> T{B, G.radiance[0], G.radiance[1], G.radiance[2], G.heat};
+            return f(T);
+        });
+    return with_medium_lit(sc, S, M, [&](const auto &B) {
+        const rtk::GlowLit<std::decay_t<decltype(B)>> T{B, G.radiance[0], G.radiance[1], G.radiance[2]};
+        return f(T);
+    });
+}
+// rt_trace_samples_medium, rt_trace_samples_volume (volume, cells: the latter's; null in the former), rt_trace_samples_chroma (sigma: its
+// three extinctions; null in the others) and rt_trace_samples_glow (glow, glow_length: its radiance and column; null in the others) from
+// their probe launch on: the caller has made its checks and handed over what has no medium or no grid.  `what` starts every refusal.
 rt_status fog_probe(const char *what, rt_scene *sc, const rt_camera_data *cam_open, const LitSetup &S, const rtk::MediumDev &M, const rt_volume *volume, rtk::KParams &P,
                     int32_t n, const int32_t *ijs, float *radiance, int32_t *rays, int32_t *medium_events, uint32_t *final_seed, uint32_t *final_nee_seed,
-                    uint32_t *final_env_seed, uint32_t *final_medium_seed, int32_t *cells, const float *sigma = nullptr) {
+                    uint32_t *final_env_seed, uint32_t *final_medium_seed, int32_t *cells, const float *sigma = nullptr, const GlowDev *glow = nullptr,
+                    float *glow_length = nullptr) {
     const std::string w(what);
     uint32_t *d_med = nullptr;
     int32_t *d_events = nullptr, *d_cells = nullptr;
+    float *d_glow = nullptr;
     Scratch mem;
-    if (mem.alloc(d_med, (size_t)n * 4) != hipSuccess || mem.alloc(d_events, (size_t)n * 4) != hipSuccess || (cells && mem.alloc(d_cells, (size_t)n * 4) != hipSuccess))
+    if (mem.alloc(d_med, (size_t)n * 4) != hipSuccess || mem.alloc(d_events, (size_t)n * 4) != hipSuccess || (cells && mem.alloc(d_cells, (size_t)n * 4) != hipSuccess) ||
+        (glow && mem.alloc(d_glow, (size_t)n * 4) != hipSuccess))
         return fail(RT_ERR_OUT_OF_MEMORY, w + ": hipMalloc failed");
     const rt_status st = run_probe(w + ": ", P, cam_open, n, ijs, radiance, rays, final_seed, final_nee_seed, final_env_seed,
                                    [&](const rtk::KParams &KP, uint32_t *d_nee, uint32_t *d_env) {
         auto probe = [&](const auto &T) {
-            if (S.lens) launch_fog_probe<true>(KP, T, S.C, n, d_nee, d_env, d_med, d_events, d_cells);
-            else launch_fog_probe<false>(KP, T, S.C, n, d_nee, d_env, d_med, d_events, d_cells);
+            if (S.lens) launch_fog_probe<true>(KP, T, S.C, n, d_nee, d_env, d_med, d_events, d_cells, d_glow);
+            else launch_fog_probe<false>(KP, T, S.C, n, d_nee, d_env, d_med, d_events, d_cells, d_glow);
             return RT_OK;
         };
+        if (glow) return with_glow_lit(sc, S, M, volume, *glow, probe);
         if (sigma) return with_chroma_lit(sc, S, M, volume, sigma, probe);
         return volume ? with_volume_lit(sc, S, M, volume, probe) : with_medium_lit(sc, S, M, probe);
     });
@@ -3481,7 +3509,8 @@ rt_status fog_probe(const char *what, rt_scene *sc, const rt_camera_data *cam_op
     // (run_probe has waited for the device)
     if (hipMemcpy(final_medium_seed, d_med, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess ||
         hipMemcpy(medium_events, d_events, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-        (cells && hipMemcpy(cells, d_cells, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess))
+        (cells && hipMemcpy(cells, d_cells, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess) ||
+        (glow && hipMemcpy(glow_length, d_glow, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess))
         return fail(RT_ERR_HIP, w + ": hipMemcpy D2H failed");
     return RT_OK;
 }
@@ -3748,6 +3777,101 @@ rt_status rt_trace_samples_chroma(rt_scene *sc, const rt_camera_data *cam_open, 
     if (n == 0) return RT_OK;
     return fog_probe(what, sc, cam_open, X.S, X.M, volume, P, n, ijs, radiance, rays, medium_events, final_seed, final_nee_seed, final_env_seed, final_medium_seed, cells,
                      X.sigma);
+}
+
+// ---- rt_render_glow / rt_trace_samples_glow (rtp_amd.h, "emission in the medium"): rt_render_volume with a medium that
+// emits.  No glow (NULL, or radiance 0, 0, 0) is rt_render_volume itself; otherwise the kernels of rt_glow.hip.inc.
+void rt_glow_params_init(rt_glow_params *p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->struct_bytes = (uint32_t)sizeof(*p);
+}
+namespace {
+// The glow call's setup.  dark: the call is rt_render_volume's with the same arguments
+struct GlowSetup {
+    LitSetup S;
+    rtk::MediumDev M{};
+    GlowDev G{};          // (heat: glow_heat_of fills it once the scene has been looked at — the handles are not read before)
+    int32_t source = 0;
+    bool dark = false;
+};
+const float *glow_heat_of(const GlowSetup &X, const rt_volume *volume, const rt_volume *heat) {
+    return X.source == 0 ? nullptr : (X.source == 1 ? volume->rho : heat->rho);
+}
+// rt_render_volume's parameter checks in its order, then the glow's: everything before the scene is looked at
+rt_status glow_setup(const char *what, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium, const rt_volume *volume,
+                     const rt_glow_params *glow, const rt_volume *heat, GlowSetup &X) {
+    const std::string w(what);
+    if (const rt_status st = lit_setup(what, cam_open, lit, X.S)) return st;
+    if (const rt_status st = medium_setup(what, medium, X.M)) return st;
+    if (const rt_status st = volume_setup(what, medium, X.M, volume)) return st;
+    rt_glow_params gp;
+    rt_glow_params_init(&gp);
+    if (const rt_status st = take_params(w, "rt_glow_params", glow, gp)) return st;
+    if (gp.source < 0 || gp.source > 2) return fail(RT_ERR_INVALID_ARG, w + ": source must be 0, 1 or 2");
+    for (int k = 0; k < 3; ++k)
+        if (!(std::isfinite(gp.radiance[k]) && gp.radiance[k] >= 0.0f)) return fail(RT_ERR_INVALID_ARG, w + ": a radiance channel is negative, NaN or infinite");
+    X.dark = gp.radiance[0] == 0.0f && gp.radiance[1] == 0.0f && gp.radiance[2] == 0.0f;
+    if (!X.dark && !(X.M.sigma_t > 0.0f))
+        return fail(RT_ERR_INVALID_ARG, w + ": a glow needs a medium with sigma_t > 0 (the emission rides on the free flight: a glow without extinction has no kernel)");
+    if (gp.source != 0 && !volume) return fail(RT_ERR_INVALID_ARG, w + ": source 1 and 2 need a volume (the grid the emission follows)");
+    if (gp.source == 2 && !heat) return fail(RT_ERR_INVALID_ARG, w + ": source 2 needs a heat grid");
+    if (gp.source == 2 && (heat->nx != volume->nx || heat->ny != volume->ny || heat->nz != volume->nz))
+        return fail(RT_ERR_INVALID_ARG, w + ": the heat grid's dimensions differ from the volume's");
+    if (gp.source != 2 && heat) return fail(RT_ERR_INVALID_ARG, w + ": a heat grid is for source 2 only");
+    for (int k = 0; k < 3; ++k) X.G.radiance[k] = gp.radiance[k];
+    X.source = gp.source;
+    return RT_OK;
+}
+}  // namespace
+
+rt_status rt_render_glow(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium, const rt_volume *volume,
+                         const rt_glow_params *glow, const rt_volume *heat, const rt_shard *shard, int32_t sample_first, float *d_fb_sum, void *hip_stream,
+                         int32_t sync, rt_timing *timing) {
+    GlowSetup X;
+    if (const rt_status st = glow_setup("rt_render_glow", cam_open, lit, medium, volume, glow, heat, X)) return st;
+    if (!sc) return fail(RT_ERR_INVALID_ARG, "rt_render_glow: null scene");
+    if (volume && volume->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_render_glow: the volume was created on another device than the scene");
+    if (heat && heat->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_render_glow: the heat grid was created on another device than the scene");
+    if (X.dark) return rt_render_volume(sc, cam_open, lit, medium, volume, shard, sample_first, d_fb_sum, hip_stream, sync, timing);
+    X.G.heat = glow_heat_of(X, volume, heat);
+    const LitSetup &S = X.S;
+    auto with_light = [&](auto frame) {
+        return with_glow_lit(sc, S, X.M, volume, X.G, [&](const auto &T) { return frame(lit_kernels_of(S.lens, T).frame, &T); });
+    };
+    return render_light_impl("rt_render_glow", S.env ? &S.env->device : nullptr, with_light, sc, cam_open, shard, sample_first, d_fb_sum, hip_stream, sync, timing,
+                             &S.C);
+}
+
+rt_status rt_trace_samples_glow(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium, const rt_volume *volume,
+                                const rt_glow_params *glow, const rt_volume *heat, int32_t n, const int32_t *ijs, float *radiance, int32_t *rays,
+                                int32_t *medium_events, uint32_t *final_seed, uint32_t *final_nee_seed, uint32_t *final_env_seed, uint32_t *final_medium_seed,
+                                int32_t *cells, float *glow_length) {
+    const char *what = "rt_trace_samples_glow";
+    GlowSetup X;
+    if (const rt_status st = glow_setup(what, cam_open, lit, medium, volume, glow, heat, X)) return st;
+    if (n < 0 || (n > 0 && (!ijs || !radiance || !rays || !medium_events || !final_seed || !final_nee_seed || !final_env_seed || !final_medium_seed || !cells ||
+                            !glow_length)))
+        return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_glow: null argument");
+    if (!sc) return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_glow: null scene");
+    if (volume && volume->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_glow: the volume was created on another device than the scene");
+    if (heat && heat->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_glow: the heat grid was created on another device than the scene");
+    if (X.dark) {
+        const rt_status st = rt_trace_samples_volume(sc, cam_open, lit, medium, volume, n, ijs, radiance, rays, medium_events, final_seed, final_nee_seed,
+                                                     final_env_seed, final_medium_seed, cells);
+        if (st == RT_OK)
+            for (int32_t k = 0; k < n; ++k) glow_length[k] = 0.0f;
+        return st;
+    }
+    rtk::KParams P;
+    rt_status st = fill_params(sc, cam_open, nullptr, P);
+    if (st != RT_OK) return st;
+    if ((st = check_device(sc)) != RT_OK) return st;
+    if (X.S.env && X.S.env->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_glow: the environment was created on another device than the scene");
+    if (n == 0) return RT_OK;
+    X.G.heat = glow_heat_of(X, volume, heat);
+    return fog_probe(what, sc, cam_open, X.S, X.M, volume, P, n, ijs, radiance, rays, medium_events, final_seed, final_nee_seed, final_env_seed, final_medium_seed, cells,
+                     nullptr, &X.G, glow_length);
 }
 
 void rt_timing_init(rt_timing *t) {

@@ -554,14 +554,16 @@ __device__ __forceinline__ void lit_step(Lane &L, const KParams &P, bool occlusi
 
 // ---- what fog adds to a lit light (DESIGN.md §31) --------------------------------------------------------------------------------------
 // The probe and the wave loop below are written once, for a light with or without fog (Lit<Table>, GlossLit<Table>; MediumLit<Table> and
-// VolumeLit<Table> of rt_medium.hip.inc and rt_volume.hip.inc; ChromaLit<Base> of rt_chroma.hip.inc over either).  What differs is four
+// VolumeLit<Table> of rt_medium.hip.inc and rt_volume.hip.inc; ChromaLit<Base> of rt_chroma.hip.inc and GlowLit<Base> of rt_glow.hip.inc
+// over either).  What differs is four
 // functions overloaded on the light's type; those of a light with fog stand in its own file and are found through the light's type where
 // the bodies are instantiated:
 //   fog_lit(T)                           the light that shade_lit2 and the streams see: T itself, or the GlossLit inside
 //   fog_seed(T, base_seed, s)            the start of the sample's medium stream (0: there is none)
 //   fog_vertex(L, P, T, …, n)            the free flight in front of the surface vertex.  false: no event — the caller runs shade_lit2, with
 //                                        nothing changed but (perhaps) draws of med and, under a chromatic medium, L.beta scaled by the
-//                                        channels' weights of having passed the interval.  true: the vertex was a medium vertex and is done:
+//                                        channels' weights of having passed the interval and, under a medium that glows, L.color with what it
+//                                        emitted over the flight.  true: the vertex was a medium vertex and is done:
 //                                        `more` as shade_lit2 returns it, the light samples in S, the next ray (out_o, out_d), what it carries
 //   fog_tr(T, o, d, t_end, c, n)         the contribution c of a shadow ray (o, d) that ended at t_end, times its transmittance
 // n counts for the probes (FogCount); the wave loop calls the two forms without it, whose counters are their own locals and never read.

@@ -35,9 +35,11 @@ __device__ __forceinline__ int32_t volume_entry(float lo, float w, int32_t n, fl
 
 // The walk of the header over the non-empty interval [t0, t1] of the ray (o, d), len = |d|.  kFlight: v is rem on entry; true = an event,
 // v its parameter t.  Otherwise v is acc, the optical depth, and the result is false.  cells counts the cells visited (the probe's
-// column; the render kernels drop it).  kAcc (a flight of rt_chroma.hip.inc): the flight keeps the optical depth of the cells it passed in acc as well
-template <bool kFlight, bool kAcc = false>
-__device__ __forceinline__ bool volume_walk(const MediumDev &M, const VolumeDev &V, f3 o, f3 d, float t0, float t1, float len, float &v, int32_t &cells, float &acc) {
+// column; the render kernels drop it).  kAcc (a flight of rt_chroma.hip.inc): the flight keeps the optical depth of the cells it passed in acc as well.
+// kGlow (a flight of rt_glow.hip.inc): the flight keeps E, the length it flew weighted per cell by h_c — heat's value at the cell, or 1 where heat is null
+template <bool kFlight, bool kAcc, bool kGlow>
+__device__ __forceinline__ bool volume_walk(const MediumDev &M, const VolumeDev &V, f3 o, f3 d, float t0, float t1, float len, float &v, int32_t &cells, float &acc,
+                                            const float *heat, float &E) {
     const float wx = (M.b[0] - M.a[0]) / (float)V.nx, wy = (M.b[1] - M.a[1]) / (float)V.ny, wz = (M.b[2] - M.a[2]) / (float)V.nz;
     int32_t cx = volume_entry(M.a[0], wx, V.nx, o.x + t0 * d.x);
     int32_t cy = volume_entry(M.a[1], wy, V.ny, o.y + t0 * d.y);
@@ -62,18 +64,23 @@ __device__ __forceinline__ bool volume_walk(const MediumDev &M, const VolumeDev 
         float tb = tm < t1 ? tm : t1;
         if (tb < ta) tb = ta;
         const float seg = (tb - ta) * len;
-        const float sigma_c = M.sigma_t * V.rho[((size_t)cz * (size_t)V.ny + (size_t)cy) * (size_t)V.nx + (size_t)cx];
+        const size_t at = ((size_t)cz * (size_t)V.ny + (size_t)cy) * (size_t)V.nx + (size_t)cx;
+        const float sigma_c = M.sigma_t * V.rho[at];
         cells++;
         if (kFlight) {
+            float h_c = 1.0f;
+            if (kGlow && heat) h_c = heat[at];
             if (sigma_c > 0.0f) {
                 const float s = v / sigma_c;
                 if (s < seg) {
+                    if (kGlow) E = E + h_c * s;
                     v = ta + s / len;
                     return true;
                 }
                 v = v - sigma_c * seg;
             }
             if (kAcc) acc = acc + sigma_c * seg;
+            if (kGlow) E = E + h_c * seg;
         } else {
             v = v + sigma_c * seg;
         }
@@ -94,6 +101,11 @@ __device__ __forceinline__ bool volume_walk(const MediumDev &M, const VolumeDev 
         ta = tb;
     }
     return false;
+}
+template <bool kFlight, bool kAcc = false>
+__device__ __forceinline__ bool volume_walk(const MediumDev &M, const VolumeDev &V, f3 o, f3 d, float t0, float t1, float len, float &v, int32_t &cells, float &acc) {
+    float unused = 0.0f;
+    return volume_walk<kFlight, kAcc, false>(M, V, o, d, t0, t1, len, v, cells, acc, nullptr, unused);
 }
 template <bool kFlight>
 __device__ __forceinline__ bool volume_walk(const MediumDev &M, const VolumeDev &V, f3 o, f3 d, float t0, float t1, float len, float &v, int32_t &cells) {

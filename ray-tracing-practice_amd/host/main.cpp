@@ -16,6 +16,24 @@
 #include "scene_params.h"
 #include "texture_io.h"
 
+// A grid file of --fog-grid and --fog-heat: the ASCII header "VOL1\nnx ny nz\n" and then exactly nx * ny * nz little-endian float32 (this
+// build's hosts are little-endian, like the file), finite and not negative, x fastest
+static bool read_grid_file(const std::string &file, int n[3], std::vector<float> &grid) {
+    FILE *f = file.empty() ? nullptr : fopen(file.c_str(), "rb");
+    char magic[8] = {0}, eol = 0;
+    size_t count = 0;
+    bool ok = f && fgets(magic, sizeof(magic), f) && std::strcmp(magic, "VOL1\n") == 0 && fscanf(f, "%d %d %d%c", &n[0], &n[1], &n[2], &eol) == 4 && eol == '\n';
+    for (int k = 0; ok && k < 3; ++k) ok = n[k] >= 1 && n[k] <= RT_VOLUME_MAX_N;
+    if (ok) {
+        count = static_cast<size_t>(n[0]) * n[1] * n[2];
+        grid.resize(count);
+        ok = fread(grid.data(), sizeof(float), count, f) == count && fgetc(f) == EOF;
+    }
+    for (size_t k = 0; ok && k < count; ++k) ok = std::isfinite(grid[k]) && grid[k] >= 0.0f;
+    if (f) fclose(f);
+    return ok;
+}
+
 int main(int argc, char *argv[]) {
     const std::string mode = argc < 2 ? "--gpu" : argv[1];
     if (mode == "--default") {
@@ -65,6 +83,52 @@ int main(int argc, char *argv[]) {
             std::cerr << "rtp_main: " << bad << "\n";
             return 99;
         }
+    }
+    // extension: `--lit … --fog SIGMA … [--fog-ball | --fog-box …] [--fog-grid FILE] --fog-glow R,G,B[:density] [--fog-heat FILE]`:
+    // the fogged frames through rt_render_glow — the medium emits R,G,B per unit length, uniformly over its region, scaled cell by cell by
+    // the density grid (`:density`) or by a second grid (--fog-heat FILE, --fog-grid's format and dimensions).  The flag needs --fog and is
+    // not for --fog-tint, --fog-noise-target or --fog-denoise: no chroma, adaptive, AOV or denoise call takes a glow.  This block comes
+    // before those flags' own, so that the refusal names this flag.  (The heat file is read below, after the grid's.)
+    bool fog_glow_on = false;
+    rt_glow_params fog_glow;
+    rt_glow_params_init(&fog_glow);
+    std::string fog_heat_file;
+    {
+        bool fog_flag = false, grid_flag = false, heat_flag = false, by_density = false;
+        std::string bad, other;
+        for (int a = 2; a < argc; ++a) {
+            const std::string arg = argv[a];
+            if (arg == "--fog") fog_flag = true;
+            if (arg == "--fog-grid") grid_flag = true;
+            if (arg == "--fog-tint" || arg == "--fog-noise-target" || arg == "--fog-denoise") other = arg;
+            if (arg == "--fog-heat") {
+                heat_flag = true;
+                fog_heat_file = a + 1 < argc ? argv[a + 1] : "";
+            }
+            if (arg == "--fog-glow") {
+                fog_glow_on = true;
+                std::string value = a + 1 < argc ? argv[a + 1] : "";
+                const std::string suffix = ":density";
+                by_density = value.size() > suffix.size() && value.compare(value.size() - suffix.size(), suffix.size(), suffix) == 0;
+                if (by_density) value.resize(value.size() - suffix.size());
+                char tail = 0;
+                bool ok = sscanf(value.c_str(), "%f,%f,%f%c", &fog_glow.radiance[0], &fog_glow.radiance[1], &fog_glow.radiance[2], &tail) == 3;
+                for (int k = 0; ok && k < 3; ++k) ok = std::isfinite(fog_glow.radiance[k]) && fog_glow.radiance[k] >= 0.0f;
+                if (!ok) bad = "--fog-glow takes R,G,B[:density]: three finite numbers, none negative";
+            }
+        }
+        if (heat_flag && !fog_glow_on && bad.empty()) bad = "--fog-heat shapes the emission of --fog-glow: it needs --fog-glow R,G,B";
+        if (fog_glow_on && bad.empty() && !fog_flag) bad = "--fog-glow makes the medium of --fog emit: it needs --lit --fog SIGMA with SIGMA > 0";
+        if (fog_glow_on && bad.empty() && !other.empty())
+            bad = "--fog-glow cannot be combined with " + other + ": the chroma, adaptive, AOV and denoise calls take no glow";
+        if (fog_glow_on && bad.empty() && heat_flag && by_density) bad = "--fog-glow R,G,B:density and --fog-heat exclude each other: the emission follows one grid";
+        if (fog_glow_on && bad.empty() && by_density && !grid_flag) bad = "--fog-glow R,G,B:density follows the density grid: it needs --fog-grid FILE";
+        if (fog_glow_on && bad.empty() && heat_flag && !grid_flag) bad = "--fog-heat has the dimensions of the density grid: it needs --fog-grid FILE";
+        if (!bad.empty()) {
+            std::cerr << "rtp_main: " << bad << "\n";
+            return 99;
+        }
+        fog_glow.source = heat_flag ? 2 : (by_density ? 1 : 0);
     }
     // extension: `--lit … --fog SIGMA … [--fog-ball | --fog-box …] [--fog-grid FILE] --fog-tint R,G,B`: the fogged frames through
     // rt_render_chroma — the extinction of colour channel k is SIGMA times its tint.  The flag needs --fog and is not for --fog-noise-target or
@@ -292,8 +356,8 @@ int main(int argc, char *argv[]) {
     bool fog_on = false;
     rt_medium_params fog;
     rt_medium_params_init(&fog);
-    std::vector<float> fog_grid;
-    int fog_n[3] = {0, 0, 0};
+    std::vector<float> fog_grid, fog_heat;
+    int fog_n[3] = {0, 0, 0}, fog_heat_n[3] = {0, 0, 0};
     {
         bool ball = false, box = false, grid = false;
         std::string grid_file;
@@ -348,24 +412,19 @@ int main(int argc, char *argv[]) {
         else if (grid && ball) fog_bad = "--fog-grid fills a box: it cannot be combined with --fog-ball";
         else if (grid && !box) fog_bad = "--fog-grid fills the box of --fog-box: it needs --fog SIGMA and --fog-box";
         if (fog_bad.empty() && grid) {
-            // the header's two lines, then exactly nx * ny * nz floats (this build's hosts are little-endian, like the file)
-            FILE *f = grid_file.empty() ? nullptr : fopen(grid_file.c_str(), "rb");
-            char magic[8] = {0}, eol = 0;
-            size_t count = 0;
-            bool ok = f && fgets(magic, sizeof(magic), f) && std::strcmp(magic, "VOL1\n") == 0 &&
-                      fscanf(f, "%d %d %d%c", &fog_n[0], &fog_n[1], &fog_n[2], &eol) == 4 && eol == '\n';
-            for (int k = 0; ok && k < 3; ++k) ok = fog_n[k] >= 1 && fog_n[k] <= RT_VOLUME_MAX_N;
-            if (ok) {
-                count = static_cast<size_t>(fog_n[0]) * fog_n[1] * fog_n[2];
-                fog_grid.resize(count);
-                ok = fread(fog_grid.data(), sizeof(float), count, f) == count && fgetc(f) == EOF;
-            }
-            for (size_t k = 0; ok && k < count; ++k) ok = std::isfinite(fog_grid[k]) && fog_grid[k] >= 0.0f;
-            if (f) fclose(f);
-            if (!ok)
+            if (!read_grid_file(grid_file, fog_n, fog_grid))
                 fog_bad = "--fog-grid takes a FILE of the header \"VOL1\\nnx ny nz\\n\" (each 1 … " + std::to_string(RT_VOLUME_MAX_N) +
                           ") and then exactly nx*ny*nz little-endian float32 densities, finite and not negative: " + grid_file;
         }
+        // --fog-heat FILE (with --fog-glow and --fog-grid, checked above): the grid the emission follows, of the density grid's dimensions
+        if (fog_bad.empty() && fog_glow_on && fog_glow.source == 2) {
+            if (!read_grid_file(fog_heat_file, fog_heat_n, fog_heat))
+                fog_bad = "--fog-heat takes a FILE of --fog-grid's format, finite and not negative: " + fog_heat_file;
+            else if (fog_heat_n[0] != fog_n[0] || fog_heat_n[1] != fog_n[1] || fog_heat_n[2] != fog_n[2])
+                fog_bad = "--fog-heat: the heat grid's dimensions differ from the density grid's: " + fog_heat_file;
+        }
+        if (fog_bad.empty() && fog_glow_on && !(fog.sigma_t > 0.0f) && (fog_glow.radiance[0] > 0.0f || fog_glow.radiance[1] > 0.0f || fog_glow.radiance[2] > 0.0f))
+            fog_bad = "--fog-glow needs --fog SIGMA with SIGMA > 0: a glow without extinction has no kernel";
         if (!fog_bad.empty()) {
             std::cerr << "rtp_main: " << fog_bad << "\n";
             return 99;
@@ -583,9 +642,15 @@ int main(int argc, char *argv[]) {
                     std::cerr << "rtp_main: --fog-grid: " << rt_get_last_error_string() << "\n";
                     return 99;
                 }
+                rt_volume *fog_heat_volume = nullptr;
+                if (!fog_heat.empty() && rt_volume_create(fog_heat.data(), fog_heat_n[0], fog_heat_n[1], fog_heat_n[2], &fog_heat_volume) != RT_OK) {
+                    std::cerr << "rtp_main: --fog-heat: " << rt_get_last_error_string() << "\n";
+                    return 99;
+                }
                 rtp::gpu_render_lens(params, desc, lens, shutter, aov, denoise, nullptr, nullptr, nullptr, &lit, fog_noise_on ? &fog_noise : noise_on ? &noise : nullptr,
                                      denoise_adaptive, &stop_rule, denoise_adaptive_temporal, fog_on ? &fog : nullptr, stop_history, fog_volume, fog_denoise,
-                                     fog_tint_on ? &fog_tint : nullptr);
+                                     fog_tint_on ? &fog_tint : nullptr, fog_glow_on ? &fog_glow : nullptr, fog_heat_volume);
+                rt_volume_destroy(fog_heat_volume);
                 rt_volume_destroy(fog_volume);
                 rt_env_destroy(lit_env);
                 return 0;

@@ -356,6 +356,30 @@ def _chroma_struct(chroma):
     return C.byref(chroma_params(tint=chroma))
 
 
+class GlowParams(_Sized):
+    """rt_glow_params (include/rtp_amd.h, "emission in the medium"): an IN structure of the caller's size — struct_bytes is set on
+    construction; source and radiance are 0 until rt_glow_params_init (glow_params()) fills the defaults (which are 0 as well)."""
+    _fields_ = [("struct_bytes", C.c_uint32), ("source", C.c_int32), ("radiance", C.c_float * 3)]
+
+
+def glow_params(radiance=0.0, source=0):
+    """rt_glow_params with the library's defaults, then radiance (one number or three) and source (0 uniform, 1 the density grid, 2 a heat
+    grid).  Nothing is checked here: the library refuses what it does not take."""
+    p = _params(GlowParams, "rt_glow_params", (), {})
+    r = np.broadcast_to(np.asarray(radiance, dtype=np.float32), (3,))
+    for k in range(3):
+        p.radiance[k] = float(r[k])
+    p.source = int(source)
+    return p
+
+
+def _glow_struct(glow):
+    """None → NULL (no glow); a GlowParams as it is; a dict → glow_params(**dict); anything else is the radiance itself (source 0)."""
+    if glow is None or isinstance(glow, (GlowParams, dict)):
+        return _struct(glow, GlowParams, glow_params)
+    return C.byref(glow_params(radiance=glow))
+
+
 class Env:
     """rt_env: an octahedral environment map with its sampling table on the current device.  Env(rgb) takes an (n, n, 3) array;
     Env.from_equirect(image, n) resamples a lat-long image first.  A context manager; close() destroys the object."""
@@ -504,7 +528,7 @@ _P, _VP, _STR, _INT, _I32, _U32, _I64, _U64 = C.POINTER, C.c_void_p, C.c_char_p,
 _STATUS = C.c_int
 _DESC, _CFG, _CAM, _SHARD, _TIMING, _AOV = _P(SceneDesc), _P(Config), _P(CameraData), _P(Shard), _P(Timing), _P(AovBuffers)
 _DENOISE, _ADAPTIVE, _STOP, _LENS, _NEE, _ENV = _P(DenoiseParams), _P(AdaptiveParams), _P(StopParams), _P(LensParams), _P(NeeParams), _P(EnvParams)
-_LIT, _MEDIUM, _CHROMA = _P(LitParams), _P(MediumParams), _P(ChromaParams)
+_LIT, _MEDIUM, _CHROMA, _GLOW = _P(LitParams), _P(MediumParams), _P(ChromaParams), _P(GlowParams)
 _OUT = [_VP, _I32, _TIMING]          # how a render call ends: void *hip_stream, int32_t sync, rt_timing *timing
 
 # the calls every build has: a library without one of them fails at load
@@ -598,6 +622,9 @@ _AMD_LATER = {
     "rt_chroma_params_init": (None, [_CHROMA]),
     "rt_render_chroma": (_STATUS, [_VP, _CAM, _LIT, _MEDIUM, _VP, _CHROMA, _SHARD, _I32, _VP, *_OUT]),
     "rt_trace_samples_chroma": (_STATUS, [_VP, _CAM, _LIT, _MEDIUM, _VP, _CHROMA, _I32] + [_VP] * 9),
+    "rt_glow_params_init": (None, [_GLOW]),
+    "rt_render_glow": (_STATUS, [_VP, _CAM, _LIT, _MEDIUM, _VP, _GLOW, _VP, _SHARD, _I32, _VP, *_OUT]),
+    "rt_trace_samples_glow": (_STATUS, [_VP, _CAM, _LIT, _MEDIUM, _VP, _GLOW, _VP, _I32] + [_VP] * 10),
 }
 # the calls that take a prior: their _rule call (the judgement: the call itself) and, last, the device address of the prior
 for _base, _prior in (("rt_render_adaptive_rule", "rt_render_adaptive_prior"), ("rt_render_lit_adaptive_rule", "rt_render_lit_adaptive_prior"),
@@ -1487,6 +1514,31 @@ class DeviceScene:
         lit = lit_params(cam_close=cam_close, lens=lens, emitters=emitters, nee=nee, env=env, env_params=env_params)
         _check(amd_lib().rt_trace_samples_chroma(self._h, C.byref(cam), C.byref(lit), _medium_struct(medium), _volume_handle(volume), _chroma_struct(tint), n,
                                                  ijs.ctypes.data, *(a.ctypes.data for a in out)), "rt_trace_samples_chroma")
+        return out
+
+    def render_glow(self, cam, d_fb_ptr, *, medium=None, volume=None, glow=None, heat=None, cam_close=None, lens=None, emitters=True, nee=None,
+                    env=None, env_params=None, shard=None, stream=None, sync=True, sample_first=0):
+        """rt_render_glow: rt_render_volume with a medium that emits (glow: None, the radiance as one number or three, a dict of
+        glow_params' keywords or a GlowParams; heat: a Volume of the volume's dimensions, source 2 only; the other keywords are
+        render_volume's).  Returns the rt_timing of this call."""
+        lit = lit_params(cam_close=cam_close, lens=lens, emitters=emitters, nee=nee, env=env, env_params=env_params)
+        return self._call("rt_render_glow", C.byref(cam), C.byref(lit), _medium_struct(medium), _volume_handle(volume), _glow_struct(glow), _volume_handle(heat),
+                          _ref(shard), sample_first, C.c_void_p(d_fb_ptr), *_stream_sync(stream, sync))
+
+    def render_glow_to_host(self, cam, *, medium=None, volume=None, glow=None, heat=None, cam_close=None, lens=None, emitters=True, nee=None, env=None,
+                            env_params=None, shard=None, sample_first=0):
+        """rt_render_glow through a fresh device buffer: (rows, width, 3) float32 sums and the rt_timing."""
+        return _frame_to_host(cam, shard, lambda d: self.render_glow(cam, d, medium=medium, volume=volume, glow=glow, heat=heat, cam_close=cam_close, lens=lens,
+                                                                     emitters=emitters, nee=nee, env=env, env_params=env_params, shard=shard,
+                                                                     sample_first=sample_first))
+
+    def trace_samples_glow(self, cam, ijs, *, medium=None, volume=None, glow=None, heat=None, cam_close=None, lens=None, emitters=True, nee=None, env=None,
+                           env_params=None):
+        """rt_trace_samples_glow: trace_samples_volume's eight columns and glow_length (float32) under the glow."""
+        ijs, n, out = _probe(ijs, _RGB, _COUNT, _COUNT, _SEED, _SEED, _SEED, _SEED, _COUNT, (np.float32, ()))
+        lit = lit_params(cam_close=cam_close, lens=lens, emitters=emitters, nee=nee, env=env, env_params=env_params)
+        _check(amd_lib().rt_trace_samples_glow(self._h, C.byref(cam), C.byref(lit), _medium_struct(medium), _volume_handle(volume), _glow_struct(glow),
+                                               _volume_handle(heat), n, ijs.ctypes.data, *(a.ctypes.data for a in out)), "rt_trace_samples_glow")
         return out
 
     def last_kernel_ms(self):
