@@ -1330,7 +1330,7 @@ rt_status rt_trace_samples_chroma(rt_scene *scene, const rt_camera_data *cam_ope
  * Identities, bit for bit: glow == NULL or radiance 0, 0, 0 hands the call over whole to rt_render_volume with the same arguments (heat is
  *   checked but not read).  A 1 x 1 x 1 grid of density 1 under source 0 or 1 = the homogeneous box under source 0, through the grid's own
  *   glow kernels (s = rem / sigma_t, E = 0 + 1 * s).  Source 2 with a heat grid equal to the density grid = source 1.
- * Left out: light-sampling the glow (fire lights a room by the paths that happen to cross it); a glow with sigma_t == 0 (the estimator rides
+ * Left out: ~~light-sampling the glow (fire lights a room by the paths that happen to cross it)~~ (rt_render_glow_sampled, "light samples of the glow" below); a glow with sigma_t == 0 (the estimator rides
  *   on the free flight); a glow under a tint (rt_render_chroma); the adaptive, AOV and denoise calls with a glow; trilinear heat (h is
  *   piecewise constant like the density); blackbody colour from temperature; tiles and rt_context; the guarded walk.
  * Checks, all before anything is enqueued: rt_render_volume's, in its order up to and including the volume's region check; then
@@ -1355,6 +1355,86 @@ rt_status rt_trace_samples_glow(rt_scene *scene, const rt_camera_data *cam_open,
                                 const rt_volume *volume, const rt_glow_params *glow, const rt_volume *heat, int32_t n, const int32_t *ijs,
                                 float *radiance, int32_t *rays, int32_t *medium_events, uint32_t *final_seed, uint32_t *final_nee_seed,
                                 uint32_t *final_env_seed, uint32_t *final_medium_seed, int32_t *cells, float *glow_length);
+
+/* ---- light samples of the glow --------------------------------------------------------------------------------------
+ * rt_render_glow's estimator over a density grid, with the glowing medium as a third light that a vertex can aim at: beside the emitter's
+ * and the environment's sample, a sampling vertex takes one of the glow, and the track-length add of the path ray that leaves the vertex
+ * is weighted against it by the power heuristic (or by 0: light sampling alone).  Everything of "emission in the medium" holds as written
+ * there.  float32 in the order written, nothing fused, division correctly rounded, exp_libm as in "participating medium".
+ *
+ * A point of the emitting volume has the kernel 1 / r^2 — infinite variance at a vertex inside or next to the glow — so the sample chooses
+ * a DIRECTION, and the whole line along it is evaluated.  With wx, wy, wz the cell's widths as in "density grid":
+ * glow_pl(o, d), the density in solid angle of the direction d at o: "density grid"'s walk, cell for cell, over interval(o, d, +inf); an
+ *   empty interval gives 0.  len = sqrt(lensq(d)), q = 0; every visited cell c with its stretch [ta, tb]: seg = (tb - ta) * len,
+ *   ra = ta * len, rb = tb * len, q = q + pc_c * (seg * ((rb * rb + rb * ra) + ra * ra)).  pl = q * inv3v, inv3v = 1.0f / (3.0f * ((wx * wy)
+ *   * wz)) — the sum over the cells of pc_c (rb^3 - ra^3) / (3 V_cell).
+ * glow_line(o, d, t_end), the emission along the ray per unit radiance: the walk over interval(o, d, t_end); Tr = 1, G = 0; every visited
+ *   cell: x = sigma_c * seg, e = exp_libm(-x), m = x < 0.0625f ? seg * (1.0f - x * (0.5f - x * (1.0f / 6.0f - x * (1.0f / 24.0f)))) :
+ *   (1.0f - e) / sigma_c (the series' error is below x^4 / 120; it covers sigma_c == 0), G = G + Tr * (h_c * m), Tr = Tr * e.  h_c by source.
+ *
+ * The light sample.  Where: every diffuse event, every medium vertex, and METAL's glossy events (fuzz >= RT_GLOSSY_MIN_FUZZ) when emitters
+ *   are sampled with nee.glossy = 1 — whether or not the emitter table holds an entry; each only with depth + 1 < max_depth, as the other
+ *   samples.  It is drawn from the med stream behind the emitter's and the environment's sample — at a medium vertex behind the draws of
+ *   the next direction as well — six draws in this order: us, ur, uc, ux, uy, uz.  z = pick(slab_cdf, nz, us), y = pick(row_cdf + z * ny,
+ *   ny, ur), x = pick(cell_cdf + (z * ny + y) * nx, nx, uc), pick the rule of rt_env's table (the smallest e with u < cdf[e]); a pick that
+ *   finds nothing: no sample.  p = (a0 + ((float)x + ux) * wx, a1 + ((float)y + uy) * wy, a2 + ((float)z + uz) * wz), dir = p - vertex.
+ *   No sample when lensq(dir) == 0; at a surface when !(dot(dir, n) > 0); when pb == 0 at a glossy event or a medium vertex, pb the BSDF
+ *   strategy's density (RT_NEE_PB, pg or ph) at dir / sqrt(lensq(dir)), divided per component; when !(pl > 0), pl = glow_pl(vertex, dir).
+ *   Otherwise f = mis ? (pb * pl) / (pl * pl + pb * pb) : pb / pl, and a shadow ray (vertex, dir) is traced as a full closest-hit query,
+ *   after the emitter's and the environment's.  At its verdict, with a non-empty interval: G = glow_line(vertex, dir, closest hit or +inf),
+ *   color_k = color_k + (beta_in_k * a_k) * (f * (radiance_k * G)), a the vertex's albedo.  The adds of a vertex: emitter, environment, glow.
+ * The path side.  The add beta * radiance * E of a path ray that left such a vertex — with or without a sample there — is scaled by
+ *   wb = mis ? (pb * pb) / (pb * pb + pl * pl) : (pl > 0 ? 0 : 1), pb the value the ray carries (RT_NEE_PB, pg, ph; a carried 0 is none),
+ *   pl = glow_pl of the ray: color_k = color_k + wb * (beta_k * (radiance_k * E)).  Camera rays, rays out of DIELECTRIC, mirror METAL and
+ *   glossy METAL without the switch have weight 1 and walk nothing more.  Nothing else of the ray is weighted.
+ *
+ * rt_glow_sampler: the table, built once from the grids on the device they live on.  h_c = 1, rho_c or heat_c by source.  In float64, in
+ *   index order: a row's sum over its cells (x), a slab's over its rows' sums (y), the total over the slabs' sums (z).  cell_cdf[(z * ny +
+ *   y) * nx + x] = (float)(running sum of the row / the row's sum), row_cdf[z * ny + y] likewise of the slab's rows, slab_cdf[z] of the
+ *   slabs; the last entry of every cdf with a positive sum is 1.0f, a cdf with sum 0 is all zero.  pc_c = (slab_pmf * row_pmf) * cell_pmf,
+ *   each pmf the float32 difference of adjacent cdf entries (the first entry itself), stored per cell.  All h == 0: the sampler is empty.
+ *   A sampler belongs to its source, its volume and (source 2) its heat grid, and is destroyed before them.
+ * Probe: rt_trace_samples_glow's columns and glow_samples, the number of glow shadow rays (they count in rays too); cells counts the
+ *   cells of glow_pl's and glow_line's walks as well.
+ *
+ * Identities, bit for bit: params NULL, sample == 0, an empty sampler or radiance 0, 0, 0 hands the call over whole to rt_render_glow
+ *   (rt_trace_samples_glow; glow_samples 0).  max_depth = 1 under mis 0 or 1 = rt_render_glow's radiance, through these kernels.
+ * Left out: a tint; the adaptive, AOV and denoise calls; a glow without a grid (a homogeneous box can pass a 1 x 1 x 1 grid); a sample that
+ *   picks the cell by its distance to the vertex; tiles and rt_context; the guarded walk.
+ * Checks, all before anything is enqueued: rt_render_glow's parameter checks in its order; then RT_ERR_INVALID_ARG for struct_bytes below
+ *   8, sample or mis outside {0, 1}, sample = 1 without a volume, sample = 1 without a sampler, a sampler built for another source, other
+ *   dimensions or other grids than the call's — still before the scene is looked at; then the null scene, the volume's, the heat's and
+ *   the sampler's device against the scene's, and rt_render_glow's remaining checks.  The messages name rt_render_glow_sampled
+ *   (rt_trace_samples_glow_sampled); a call that is handed over is rt_render_glow's from there on, and what that call still refuses
+ *   (the camera, the environment's device, …) names rt_render_glow.  Handle state and timing: as rt_render_lit. */
+typedef struct rt_glow_sample_params {   /* IN, caller-sized like rt_glow_params */
+    uint32_t struct_bytes;
+    int32_t  sample;        /* 0: off — rt_render_glow itself; 1: the glow is light-sampled */
+    int32_t  mis;           /* 1: power heuristic; 0: light sampling alone */
+} rt_glow_sample_params;
+/* Defaults into *p: sample 0, mis 1; struct_bytes = sizeof(rt_glow_sample_params). */
+void rt_glow_sample_params_init(rt_glow_sample_params *p);
+typedef struct rt_glow_sampler rt_glow_sampler;
+/* The table of `volume` under `source` (heat: source 2 only, the volume's dimensions), on the volume's device, which must be the calling
+ * thread's current one.  RT_ERR_INVALID_ARG for a null argument, source outside {0, 1, 2}, heat that is missing under source 2, of other
+ * dimensions or on another device, or given under source 0 or 1. */
+rt_status rt_glow_sampler_create(const rt_volume *volume, int32_t source, const rt_volume *heat, rt_glow_sampler **out_sampler);
+rt_status rt_glow_sampler_destroy(rt_glow_sampler *sampler);
+/* The table as the device holds it, HOST memory, each pointer optional: slab_cdf (nz), the rows' cdf of slab z (ny), the cells' cdf and
+ * the cells' pc of row y of slab z (nx each); *count = nx * ny * nz, or 0 for an empty sampler. */
+rt_status rt_glow_sampler_table(const rt_glow_sampler *sampler, int32_t z, int32_t y, float *slab_cdf, float *row_cdf, float *cell_cdf, float *pc_row,
+                                int32_t *count);
+/* rt_render_glow with light samples of the glow (sample NULL: the defaults — rt_render_glow itself; sampler: read under sample = 1). */
+rt_status rt_render_glow_sampled(rt_scene *scene, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium,
+                                 const rt_volume *volume, const rt_glow_params *glow, const rt_volume *heat, const rt_glow_sample_params *sample,
+                                 const rt_glow_sampler *sampler, const rt_shard *shard, int32_t sample_first, float *d_fb_sum, void *hip_stream,
+                                 int32_t sync, rt_timing *timing);
+/* Probe for tests, HOST memory: rt_trace_samples_glow's columns and glow_samples for the estimator of rt_render_glow_sampled. */
+rt_status rt_trace_samples_glow_sampled(rt_scene *scene, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium,
+                                        const rt_volume *volume, const rt_glow_params *glow, const rt_volume *heat, const rt_glow_sample_params *sample,
+                                        const rt_glow_sampler *sampler, int32_t n, const int32_t *ijs, float *radiance, int32_t *rays,
+                                        int32_t *medium_events, uint32_t *final_seed, uint32_t *final_nee_seed, uint32_t *final_env_seed,
+                                        uint32_t *final_medium_seed, int32_t *cells, float *glow_length, int32_t *glow_samples);
 
 /* ---- adaptive sampling under fog -----------------------------------------------------------------------------------
  * rt_render_lit_adaptive_prior's rule, statistics, rounds and prior on rt_render_volume's estimator.  No new arithmetic: a sample is

@@ -23,6 +23,7 @@
 #include "rt_medium.hip.inc"
 #include "rt_volume.hip.inc"
 #include "rt_glow.hip.inc"
+#include "rt_glow_sample.hip.inc"
 #include "rt_chroma.hip.inc"
 #include "rt_aov_fog.hip.inc"
 // Developer build only (make dev → librtp_amd_dev.so, -DRTP_DEV_BUILD): the rt_debug_* entry points (exhaustive on-device checks of
@@ -3432,23 +3433,29 @@ rt_status with_fog_lit(rt_scene *sc, const LitSetup &S, const rtk::MediumDev &M,
 // the probe kernel of a light with fog (d_cells: the grid's column)
 extern "C++" template <bool kLens, class Table>
 void launch_fog_probe(const rtk::KParams &KP, const rtk::MediumLit<Table> &T, const rtk::LensCam &C, int32_t n, uint32_t *d_nee, uint32_t *d_env, uint32_t *d_med,
-                      int32_t *d_events, int32_t *, float *) {
+                      int32_t *d_events, int32_t *, float *, int32_t *) {
     hipLaunchKernelGGL((rtk::medium_probe_kernel<kLens, Table>), dim3((n + 255) / 256), dim3(256), 0, 0, KP, T, C, d_nee, d_env, d_med, d_events);
 }
 extern "C++" template <bool kLens, class Table>
 void launch_fog_probe(const rtk::KParams &KP, const rtk::VolumeLit<Table> &T, const rtk::LensCam &C, int32_t n, uint32_t *d_nee, uint32_t *d_env, uint32_t *d_med,
-                      int32_t *d_events, int32_t *d_cells, float *) {
+                      int32_t *d_events, int32_t *d_cells, float *, int32_t *) {
     hipLaunchKernelGGL((rtk::volume_probe_kernel<kLens, Table>), dim3((n + 255) / 256), dim3(256), 0, 0, KP, T, C, d_nee, d_env, d_med, d_events, d_cells);
 }
 extern "C++" template <bool kLens, class Base>
 void launch_fog_probe(const rtk::KParams &KP, const rtk::ChromaLit<Base> &T, const rtk::LensCam &C, int32_t n, uint32_t *d_nee, uint32_t *d_env, uint32_t *d_med,
-                      int32_t *d_events, int32_t *d_cells, float *) {
+                      int32_t *d_events, int32_t *d_cells, float *, int32_t *) {
     hipLaunchKernelGGL((rtk::chroma_probe_kernel<kLens, Base>), dim3((n + 255) / 256), dim3(256), 0, 0, KP, T, C, d_nee, d_env, d_med, d_events, d_cells);
 }
 extern "C++" template <bool kLens, class Base>
 void launch_fog_probe(const rtk::KParams &KP, const rtk::GlowLit<Base> &T, const rtk::LensCam &C, int32_t n, uint32_t *d_nee, uint32_t *d_env, uint32_t *d_med,
-                      int32_t *d_events, int32_t *d_cells, float *d_glow) {
+                      int32_t *d_events, int32_t *d_cells, float *d_glow, int32_t *) {
     hipLaunchKernelGGL((rtk::glow_probe_kernel<kLens, Base>), dim3((n + 255) / 256), dim3(256), 0, 0, KP, T, C, d_nee, d_env, d_med, d_events, d_cells, d_glow);
+}
+extern "C++" template <bool kLens, class Table>
+void launch_fog_probe(const rtk::KParams &KP, const rtk::GlowSampleLit<Table> &T, const rtk::LensCam &C, int32_t n, uint32_t *d_nee, uint32_t *d_env, uint32_t *d_med,
+                      int32_t *d_events, int32_t *d_cells, float *d_glow, int32_t *d_shots) {
+    hipLaunchKernelGGL((rtk::glow_sample_probe_kernel<kLens, Table>), dim3((n + 255) / 256), dim3(256), 0, 0, KP, T, C, d_nee, d_env, d_med, d_events, d_cells, d_glow,
+                       d_shots);
 }
 // The chroma kernels' light (rt_render_chroma): the medium's or the grid's with sigma_t = 1, and the three channels' extinctions beside it
 extern "C++" template <class F>
@@ -3479,28 +3486,38 @@ rt_status with_glow_lit(rt_scene *sc, const LitSetup &S, const rtk::MediumDev &M
         return f(T);
     });
 }
+// The sampled glow kernels' light (rt_render_glow_sampled): the glow's over the grid, and the sampler's table beside it
+extern "C++" template <class F>
+rt_status with_glow_sample_lit(rt_scene *sc, const LitSetup &S, const rtk::MediumDev &M, const rt_volume *volume, const GlowDev &G, const rtk::GlowSamplerDev &Q, F &&f) {
+    return with_volume_lit(sc, S, M, volume, [&](const auto &B) {
+        const rtk::GlowSampleLit<std::decay_t<decltype(B.G.N)>> T{{B, G.radiance[0], G.radiance[1], G.radiance[2], G.heat}, Q};
+        return f(T);
+    });
+}
 // rt_trace_samples_medium, rt_trace_samples_volume (volume, cells: the latter's; null in the former), rt_trace_samples_chroma (sigma: its
-// three extinctions; null in the others) and rt_trace_samples_glow (glow, glow_length: its radiance and column; null in the others) from
+// three extinctions; null in the others), rt_trace_samples_glow (glow, glow_length: its radiance and column; null in the others) and
+// rt_trace_samples_glow_sampled (sampler, glow_samples: its table and column, beside the glow's; null in the others) from
 // their probe launch on: the caller has made its checks and handed over what has no medium or no grid.  `what` starts every refusal.
 rt_status fog_probe(const char *what, rt_scene *sc, const rt_camera_data *cam_open, const LitSetup &S, const rtk::MediumDev &M, const rt_volume *volume, rtk::KParams &P,
                     int32_t n, const int32_t *ijs, float *radiance, int32_t *rays, int32_t *medium_events, uint32_t *final_seed, uint32_t *final_nee_seed,
                     uint32_t *final_env_seed, uint32_t *final_medium_seed, int32_t *cells, const float *sigma = nullptr, const GlowDev *glow = nullptr,
-                    float *glow_length = nullptr) {
+                    float *glow_length = nullptr, const rtk::GlowSamplerDev *sampler = nullptr, int32_t *glow_samples = nullptr) {
     const std::string w(what);
     uint32_t *d_med = nullptr;
-    int32_t *d_events = nullptr, *d_cells = nullptr;
+    int32_t *d_events = nullptr, *d_cells = nullptr, *d_shots = nullptr;
     float *d_glow = nullptr;
     Scratch mem;
     if (mem.alloc(d_med, (size_t)n * 4) != hipSuccess || mem.alloc(d_events, (size_t)n * 4) != hipSuccess || (cells && mem.alloc(d_cells, (size_t)n * 4) != hipSuccess) ||
-        (glow && mem.alloc(d_glow, (size_t)n * 4) != hipSuccess))
+        (glow && mem.alloc(d_glow, (size_t)n * 4) != hipSuccess) || (sampler && mem.alloc(d_shots, (size_t)n * 4) != hipSuccess))
         return fail(RT_ERR_OUT_OF_MEMORY, w + ": hipMalloc failed");
     const rt_status st = run_probe(w + ": ", P, cam_open, n, ijs, radiance, rays, final_seed, final_nee_seed, final_env_seed,
                                    [&](const rtk::KParams &KP, uint32_t *d_nee, uint32_t *d_env) {
         auto probe = [&](const auto &T) {
-            if (S.lens) launch_fog_probe<true>(KP, T, S.C, n, d_nee, d_env, d_med, d_events, d_cells, d_glow);
-            else launch_fog_probe<false>(KP, T, S.C, n, d_nee, d_env, d_med, d_events, d_cells, d_glow);
+            if (S.lens) launch_fog_probe<true>(KP, T, S.C, n, d_nee, d_env, d_med, d_events, d_cells, d_glow, d_shots);
+            else launch_fog_probe<false>(KP, T, S.C, n, d_nee, d_env, d_med, d_events, d_cells, d_glow, d_shots);
             return RT_OK;
         };
+        if (sampler) return with_glow_sample_lit(sc, S, M, volume, *glow, *sampler, probe);
         if (glow) return with_glow_lit(sc, S, M, volume, *glow, probe);
         if (sigma) return with_chroma_lit(sc, S, M, volume, sigma, probe);
         return volume ? with_volume_lit(sc, S, M, volume, probe) : with_medium_lit(sc, S, M, probe);
@@ -3510,7 +3527,8 @@ rt_status fog_probe(const char *what, rt_scene *sc, const rt_camera_data *cam_op
     if (hipMemcpy(final_medium_seed, d_med, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess ||
         hipMemcpy(medium_events, d_events, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess ||
         (cells && hipMemcpy(cells, d_cells, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess) ||
-        (glow && hipMemcpy(glow_length, d_glow, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess))
+        (glow && hipMemcpy(glow_length, d_glow, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess) ||
+        (sampler && hipMemcpy(glow_samples, d_shots, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess))
         return fail(RT_ERR_HIP, w + ": hipMemcpy D2H failed");
     return RT_OK;
 }
@@ -3872,6 +3890,214 @@ rt_status rt_trace_samples_glow(rt_scene *sc, const rt_camera_data *cam_open, co
     X.G.heat = glow_heat_of(X, volume, heat);
     return fog_probe(what, sc, cam_open, X.S, X.M, volume, P, n, ijs, radiance, rays, medium_events, final_seed, final_nee_seed, final_env_seed, final_medium_seed, cells,
                      nullptr, &X.G, glow_length);
+}
+
+// ---- rt_glow_sampler / rt_render_glow_sampled / rt_trace_samples_glow_sampled (rtp_amd.h, "light samples of the glow"):
+// rt_render_glow over a grid with the glow as a third light.  No sample (NULL, sample == 0), an empty sampler or no glow is rt_render_glow
+// itself; otherwise the kernels of rt_glow_sample.hip.inc.
+void rt_glow_sample_params_init(rt_glow_sample_params *p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->struct_bytes = (uint32_t)sizeof(*p);
+    p->mis = 1;
+}
+
+struct rt_glow_sampler {
+    int device = 0;
+    int32_t source = 0, nx = 0, ny = 0, nz = 0;
+    const rt_volume *volume = nullptr, *heat = nullptr;          // what it was built from (compared, never read again)
+    bool empty = false;
+    float *slab_cdf = nullptr, *row_cdf = nullptr, *cell_cdf = nullptr, *pc = nullptr;
+};
+
+rt_status rt_glow_sampler_create(const rt_volume *volume, int32_t source, const rt_volume *heat, rt_glow_sampler **out_sampler) {
+    if (!volume || !out_sampler) return fail(RT_ERR_INVALID_ARG, "rt_glow_sampler_create: null argument");
+    *out_sampler = nullptr;
+    if (source < 0 || source > 2) return fail(RT_ERR_INVALID_ARG, "rt_glow_sampler_create: source must be 0, 1 or 2");
+    if (source == 2 && !heat) return fail(RT_ERR_INVALID_ARG, "rt_glow_sampler_create: source 2 needs a heat grid");
+    if (source != 2 && heat) return fail(RT_ERR_INVALID_ARG, "rt_glow_sampler_create: a heat grid is for source 2 only");
+    if (heat && (heat->nx != volume->nx || heat->ny != volume->ny || heat->nz != volume->nz))
+        return fail(RT_ERR_INVALID_ARG, "rt_glow_sampler_create: the heat grid's dimensions differ from the volume's");
+    if (heat && heat->device != volume->device) return fail(RT_ERR_INVALID_ARG, "rt_glow_sampler_create: the heat grid was created on another device than the volume");
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(RT_ERR_NO_DEVICE, "rt_glow_sampler_create: no current HIP device");
+    }
+    if (dev != volume->device) return fail(RT_ERR_INVALID_ARG, "rt_glow_sampler_create: the volume was created on another device than the current one");
+    const int32_t nx = volume->nx, ny = volume->ny, nz = volume->nz;
+    const size_t rows = (size_t)nz * (size_t)ny, count = rows * (size_t)nx;
+    std::vector<float> h(count, 1.0f);
+    if (source != 0) HIP_TRY(hipMemcpy(h.data(), source == 1 ? volume->rho : heat->rho, count * 4, hipMemcpyDeviceToHost));
+    // the sums, float64 in index order: a row's over its cells, a slab's over its rows', the total over the slabs'
+    std::vector<double> row_sum(rows, 0.0), slab_sum((size_t)nz, 0.0);
+    double total = 0.0;
+    for (size_t r = 0; r < rows; ++r)
+        for (int32_t x = 0; x < nx; ++x) row_sum[r] += (double)h[r * (size_t)nx + (size_t)x];
+    for (int32_t z = 0; z < nz; ++z) {
+        for (int32_t y = 0; y < ny; ++y) slab_sum[(size_t)z] += row_sum[(size_t)z * (size_t)ny + (size_t)y];
+        total += slab_sum[(size_t)z];
+    }
+    // a cdf over n values with sum `sum`: the float32 of running sum / sum, the last entry 1.0f; sum 0: all zero
+    auto cdf_of = [](auto value, int32_t n, double sum, float *cdf) {
+        double run = 0.0;
+        for (int32_t k = 0; k < n; ++k) {
+            run += value(k);
+            cdf[k] = sum > 0.0 ? (float)(run / sum) : 0.0f;
+        }
+        if (sum > 0.0) cdf[n - 1] = 1.0f;
+    };
+    std::vector<float> slab_cdf((size_t)nz), row_cdf(rows), cell_cdf(count), pc(count);
+    cdf_of([&](int32_t z) { return slab_sum[(size_t)z]; }, nz, total, slab_cdf.data());
+    for (int32_t z = 0; z < nz; ++z)
+        cdf_of([&](int32_t y) { return row_sum[(size_t)z * (size_t)ny + (size_t)y]; }, ny, slab_sum[(size_t)z], row_cdf.data() + (size_t)z * (size_t)ny);
+    for (size_t r = 0; r < rows; ++r)
+        cdf_of([&](int32_t x) { return (double)h[r * (size_t)nx + (size_t)x]; }, nx, row_sum[r], cell_cdf.data() + r * (size_t)nx);
+    auto pmf_of = [](const float *cdf, int32_t k) { return cdf[k] - (k == 0 ? 0.0f : cdf[k - 1]); };
+    for (int32_t z = 0; z < nz; ++z)
+        for (int32_t y = 0; y < ny; ++y) {
+            const size_t r = (size_t)z * (size_t)ny + (size_t)y;
+            const float sr = pmf_of(slab_cdf.data(), z) * pmf_of(row_cdf.data() + (size_t)z * (size_t)ny, y);
+            for (int32_t x = 0; x < nx; ++x) pc[r * (size_t)nx + (size_t)x] = sr * pmf_of(cell_cdf.data() + r * (size_t)nx, x);
+        }
+    rt_glow_sampler *q = new (std::nothrow) rt_glow_sampler();
+    if (!q) return fail(RT_ERR_OUT_OF_MEMORY, "rt_glow_sampler_create: out of host memory");
+    q->device = dev;
+    q->source = source;
+    q->nx = nx;
+    q->ny = ny;
+    q->nz = nz;
+    q->volume = volume;
+    q->heat = heat;
+    q->empty = !(total > 0.0);
+    rt_status st = upload(slab_cdf, (void **)&q->slab_cdf);
+    if (st == RT_OK) st = upload(row_cdf, (void **)&q->row_cdf);
+    if (st == RT_OK) st = upload(cell_cdf, (void **)&q->cell_cdf);
+    if (st == RT_OK) st = upload(pc, (void **)&q->pc);
+    if (st != RT_OK) {
+        (void)rt_glow_sampler_destroy(q);
+        return st;
+    }
+    *out_sampler = q;
+    return RT_OK;
+}
+
+rt_status rt_glow_sampler_destroy(rt_glow_sampler *sampler) {
+    if (!sampler) return RT_OK;
+    (void)hipFree(sampler->slab_cdf);
+    (void)hipFree(sampler->row_cdf);
+    (void)hipFree(sampler->cell_cdf);
+    (void)hipFree(sampler->pc);
+    delete sampler;
+    return RT_OK;
+}
+
+rt_status rt_glow_sampler_table(const rt_glow_sampler *sampler, int32_t z, int32_t y, float *slab_cdf, float *row_cdf, float *cell_cdf, float *pc_row,
+                                int32_t *count) {
+    if (!sampler) return fail(RT_ERR_INVALID_ARG, "rt_glow_sampler_table: null sampler");
+    if (z < 0 || z >= sampler->nz || y < 0 || y >= sampler->ny) return fail(RT_ERR_INVALID_ARG, "rt_glow_sampler_table: slab or row out of range");
+    int dev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev != sampler->device) {
+        (void)hipGetLastError();
+        return fail(RT_ERR_INVALID_ARG, "rt_glow_sampler_table: the sampler was created on another device than the current one");
+    }
+    const size_t nx = (size_t)sampler->nx, ny = (size_t)sampler->ny, row = (size_t)z * ny + (size_t)y;
+    if (slab_cdf) HIP_TRY(hipMemcpy(slab_cdf, sampler->slab_cdf, (size_t)sampler->nz * 4, hipMemcpyDeviceToHost));
+    if (row_cdf) HIP_TRY(hipMemcpy(row_cdf, sampler->row_cdf + (size_t)z * ny, ny * 4, hipMemcpyDeviceToHost));
+    if (cell_cdf) HIP_TRY(hipMemcpy(cell_cdf, sampler->cell_cdf + row * nx, nx * 4, hipMemcpyDeviceToHost));
+    if (pc_row) HIP_TRY(hipMemcpy(pc_row, sampler->pc + row * nx, nx * 4, hipMemcpyDeviceToHost));
+    if (count) *count = sampler->empty ? 0 : sampler->nx * sampler->ny * sampler->nz;
+    return RT_OK;
+}
+
+namespace {
+// The sampled call's setup: rt_render_glow's parameter checks, then the sample's — everything before the scene is looked at.
+// sampled == false: the call is rt_render_glow's with the same arguments (as far as the parameters say: an empty sampler and no glow are
+// found by the caller, behind the devices' checks)
+struct GlowSampleSetup {
+    GlowSetup X;
+    rtk::GlowSamplerDev Q{};
+    bool sampled = false;
+};
+rt_status glow_sample_setup(const char *what, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium, const rt_volume *volume,
+                            const rt_glow_params *glow, const rt_volume *heat, const rt_glow_sample_params *sample, const rt_glow_sampler *sampler,
+                            GlowSampleSetup &Y) {
+    const std::string w(what);
+    if (const rt_status st = glow_setup(what, cam_open, lit, medium, volume, glow, heat, Y.X)) return st;
+    rt_glow_sample_params sp;
+    rt_glow_sample_params_init(&sp);
+    if (const rt_status st = take_params(w, "rt_glow_sample_params", sample, sp)) return st;
+    if (sp.sample != 0 && sp.sample != 1) return fail(RT_ERR_INVALID_ARG, w + ": sample must be 0 or 1");
+    if (sp.mis != 0 && sp.mis != 1) return fail(RT_ERR_INVALID_ARG, w + ": mis must be 0 or 1");
+    if (!sample || sp.sample == 0) return RT_OK;
+    if (!volume) return fail(RT_ERR_INVALID_ARG, w + ": light samples of the glow need a volume (a homogeneous box can pass a 1 x 1 x 1 grid of density 1)");
+    if (!sampler) return fail(RT_ERR_INVALID_ARG, w + ": sample = 1 needs a sampler (rt_glow_sampler_create)");
+    if (sampler->source != Y.X.source) return fail(RT_ERR_INVALID_ARG, w + ": the sampler was built for another source than the call's");
+    if (sampler->nx != volume->nx || sampler->ny != volume->ny || sampler->nz != volume->nz)
+        return fail(RT_ERR_INVALID_ARG, w + ": the sampler's dimensions differ from the volume's");
+    if (sampler->volume != volume || sampler->heat != heat) return fail(RT_ERR_INVALID_ARG, w + ": the sampler was built from other grids than the call's");
+    Y.Q = {sampler->slab_cdf, sampler->row_cdf, sampler->cell_cdf, sampler->pc, sp.mis};
+    Y.sampled = true;
+    return RT_OK;
+}
+}  // namespace
+
+rt_status rt_render_glow_sampled(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium, const rt_volume *volume,
+                                 const rt_glow_params *glow, const rt_volume *heat, const rt_glow_sample_params *sample, const rt_glow_sampler *sampler,
+                                 const rt_shard *shard, int32_t sample_first, float *d_fb_sum, void *hip_stream, int32_t sync, rt_timing *timing) {
+    const char *what = "rt_render_glow_sampled";
+    GlowSampleSetup Y;
+    if (const rt_status st = glow_sample_setup(what, cam_open, lit, medium, volume, glow, heat, sample, sampler, Y)) return st;
+    if (!sc) return fail(RT_ERR_INVALID_ARG, "rt_render_glow_sampled: null scene");
+    if (volume && volume->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_render_glow_sampled: the volume was created on another device than the scene");
+    if (heat && heat->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_render_glow_sampled: the heat grid was created on another device than the scene");
+    if (Y.sampled && sampler->device != sc->device)
+        return fail(RT_ERR_INVALID_ARG, "rt_render_glow_sampled: the sampler was created on another device than the scene");
+    GlowSetup &X = Y.X;
+    if (!Y.sampled || sampler->empty || X.dark)
+        return rt_render_glow(sc, cam_open, lit, medium, volume, glow, heat, shard, sample_first, d_fb_sum, hip_stream, sync, timing);
+    X.G.heat = glow_heat_of(X, volume, heat);
+    const LitSetup &S = X.S;
+    auto with_light = [&](auto frame) {
+        return with_glow_sample_lit(sc, S, X.M, volume, X.G, Y.Q, [&](const auto &T) { return frame(lit_kernels_of(S.lens, T).frame, &T); });
+    };
+    return render_light_impl(what, S.env ? &S.env->device : nullptr, with_light, sc, cam_open, shard, sample_first, d_fb_sum, hip_stream, sync, timing, &S.C);
+}
+
+rt_status rt_trace_samples_glow_sampled(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium,
+                                        const rt_volume *volume, const rt_glow_params *glow, const rt_volume *heat, const rt_glow_sample_params *sample,
+                                        const rt_glow_sampler *sampler, int32_t n, const int32_t *ijs, float *radiance, int32_t *rays, int32_t *medium_events,
+                                        uint32_t *final_seed, uint32_t *final_nee_seed, uint32_t *final_env_seed, uint32_t *final_medium_seed, int32_t *cells,
+                                        float *glow_length, int32_t *glow_samples) {
+    const char *what = "rt_trace_samples_glow_sampled";
+    GlowSampleSetup Y;
+    if (const rt_status st = glow_sample_setup(what, cam_open, lit, medium, volume, glow, heat, sample, sampler, Y)) return st;
+    if (n < 0 || (n > 0 && (!ijs || !radiance || !rays || !medium_events || !final_seed || !final_nee_seed || !final_env_seed || !final_medium_seed || !cells ||
+                            !glow_length || !glow_samples)))
+        return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_glow_sampled: null argument");
+    if (!sc) return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_glow_sampled: null scene");
+    if (volume && volume->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_glow_sampled: the volume was created on another device than the scene");
+    if (heat && heat->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_glow_sampled: the heat grid was created on another device than the scene");
+    if (Y.sampled && sampler->device != sc->device)
+        return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_glow_sampled: the sampler was created on another device than the scene");
+    GlowSetup &X = Y.X;
+    if (!Y.sampled || sampler->empty || X.dark) {
+        const rt_status st = rt_trace_samples_glow(sc, cam_open, lit, medium, volume, glow, heat, n, ijs, radiance, rays, medium_events, final_seed, final_nee_seed,
+                                                   final_env_seed, final_medium_seed, cells, glow_length);
+        if (st == RT_OK)
+            for (int32_t k = 0; k < n; ++k) glow_samples[k] = 0;
+        return st;
+    }
+    rtk::KParams P;
+    rt_status st = fill_params(sc, cam_open, nullptr, P);
+    if (st != RT_OK) return st;
+    if ((st = check_device(sc)) != RT_OK) return st;
+    if (X.S.env && X.S.env->device != sc->device)
+        return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_glow_sampled: the environment was created on another device than the scene");
+    if (n == 0) return RT_OK;
+    X.G.heat = glow_heat_of(X, volume, heat);
+    return fog_probe(what, sc, cam_open, X.S, X.M, volume, P, n, ijs, radiance, rays, medium_events, final_seed, final_nee_seed, final_env_seed, final_medium_seed, cells,
+                     nullptr, &X.G, glow_length, &Y.Q, glow_samples);
 }
 
 void rt_timing_init(rt_timing *t) {

@@ -336,7 +336,7 @@ constexpr int32_t kLightIdle = 0, kLightPath = 1, kLightShadow = 2;
 // The first half of a wave loop's fetch — RTP_LIGHT_POOL_RESERVE, statements inside `if (idle != 0 && !exhausted)` with lane, idle, P, pool_next,
 // pool_end and exhausted in scope: every idle lane gets the next work index of the wave's pool as `mine` (the pool refilled with one atomic per
 // wave, kLightChunk indices at a time); a chunk that starts at or past TOTAL (wave-uniform) marks the wave exhausted.  `mine` may lie past
-// TOTAL.  Used by light_render_body and by lit_render_body's fetch (RTP_LIT_POOL_FETCH), and undefined after the latter.
+// TOTAL.  Used by light_render_body and by lit_render_body's fetch (RTP_LIT_POOL_FETCH) and, through it, rt_glow_sample.hip.inc's, which undefines it.
 #define RTP_LIGHT_POOL_RESERVE(TOTAL)                                                                                 \
             const uint32_t cnt = (uint32_t)__popcll(idle);                                                            \
             const uint32_t rank = (uint32_t)lane_rank(idle);                                                          \
@@ -535,7 +535,7 @@ __device__ __forceinline__ bool shade_lit2(Lane &L, const KParams &P, const Lit 
         }
     })
 }
-#undef RTP_LIT_VERTEX
+// (RTP_LIT_VERTEX stays defined for rt_glow_sample.hip.inc, whose vertex takes a third light sample; it is undefined at that file's end)
 // a sample's camera ray: the pinhole's (start_sample), or kLens: the lens / moving camera's
 template <bool kLens>
 __device__ __forceinline__ void lit_start(Lane &L, const KParams &P, const LensCam &C, int32_t i, int32_t j, uint32_t base_seed, int32_t s, f3 &o, f3 &d) {
@@ -794,8 +794,7 @@ __device__ __forceinline__ void lit_render_body(const KParams &P, const Light &T
     }
 }
 #undef RTP_LIT_RENDER_BODY
-#undef RTP_LIT_POOL_FETCH
-#undef RTP_LIGHT_POOL_RESERVE
+// (RTP_LIT_POOL_FETCH and RTP_LIGHT_POOL_RESERVE stay defined for the wave loop of rt_glow_sample.hip.inc, and are undefined at its end)
 
 template <bool kLens, class Table>
 __global__ void __launch_bounds__(256) lit_probe_kernel(const KParams P, const Lit<Table> T, const LensCam C, uint32_t *nee_seed_out, uint32_t *env_seed_out) {

@@ -37,6 +37,9 @@ __device__ __forceinline__ int32_t volume_entry(float lo, float w, int32_t n, fl
 // v its parameter t.  Otherwise v is acc, the optical depth, and the result is false.  cells counts the cells visited (the probe's
 // column; the render kernels drop it).  kAcc (a flight of rt_chroma.hip.inc): the flight keeps the optical depth of the cells it passed in acc as well.
 // kGlow (a flight of rt_glow.hip.inc): the flight keeps E, the length it flew weighted per cell by h_c — heat's value at the cell, or 1 where heat is null
+// (volume_cells of rt_glow_sample.hip.inc states the same cells, bounds and order once more, with what a cell does passed in — this text
+// could not take a callback without moving the listings of the kernels on it; gs_cells of tests/cpu_native/glow_sample_ref.c restates
+// that one.  A change to the entry cell, tnext, the clamp, the step or the break here is made there as well)
 template <bool kFlight, bool kAcc, bool kGlow>
 __device__ __forceinline__ bool volume_walk(const MediumDev &M, const VolumeDev &V, f3 o, f3 d, float t0, float t1, float len, float &v, int32_t &cells, float &acc,
                                             const float *heat, float &E) {

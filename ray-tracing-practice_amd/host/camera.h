@@ -152,13 +152,15 @@ void gpu_render_pipelined(const SceneParams &params, const rt_scene_desc &desc, 
 // fog_denoise (with medium; rtp_main --fog-denoise): each frame also filtered under rt_render_aov_volume's AOVs — by rt_denoise, or with
 // noise by rt_denoise_spp with the frame's counts and moments and AOVs at noise->min_spp — to "<frame file>.denoised";
 // chroma (with medium; rtp_main --fog-tint): the lit frames through rt_render_chroma, with or without the volume;
-// glow (with medium, without chroma; rtp_main --fog-glow): through rt_render_glow, with or without the volume, heat the grid of its source 2
+// glow (with medium, without chroma; rtp_main --fog-glow): through rt_render_glow, with or without the volume, heat the grid of its source 2;
+// glow_sample (with glow and volume; rtp_main --fog-glow-sample): through rt_render_glow_sampled with the sampler of these grids
 void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const rt_lens_params &lens, float shutter, bool aov, bool denoise,
                      const rt_nee_params *nee = nullptr, const rt_env *env = nullptr, const rt_env_params *env_params = nullptr,
                      const rt_lit_params *lit = nullptr, const rt_adaptive_params *noise = nullptr, bool denoise_adaptive = false,
                      const rt_stop_params *stop = nullptr, bool denoise_adaptive_temporal = false, const rt_medium_params *medium = nullptr,
                      bool stop_history = false, const rt_volume *volume = nullptr, bool fog_denoise = false, const rt_chroma_params *chroma = nullptr,
-                     const rt_glow_params *glow = nullptr, const rt_volume *heat = nullptr);
+                     const rt_glow_params *glow = nullptr, const rt_volume *heat = nullptr, const rt_glow_sample_params *glow_sample = nullptr,
+                     const rt_glow_sampler *sampler = nullptr);
 // rtp_main --gpu --adaptive: the orbit frame after frame on one GPU, each frame through rt_render_adaptive and rt_tonemap_spp;
 // denoise_adaptive (rtp_main --denoise-adaptive): each frame also filtered by rt_denoise_spp with its counts and moments and
 // rt_render_aov AOVs at ap.min_spp, written through rt_tonemap_spp to "<frame file>.denoised"; denoise_adaptive_temporal (rtp_main

@@ -89,9 +89,13 @@ int main(int argc, char *argv[]) {
     // the density grid (`:density`) or by a second grid (--fog-heat FILE, --fog-grid's format and dimensions).  The flag needs --fog and is
     // not for --fog-tint, --fog-noise-target or --fog-denoise: no chroma, adaptive, AOV or denoise call takes a glow.  This block comes
     // before those flags' own, so that the refusal names this flag.  (The heat file is read below, after the grid's.)
-    bool fog_glow_on = false;
+    // `--fog-glow … --fog-grid FILE --fog-glow-sample mis|light`: through rt_render_glow_sampled — the glow is light-sampled,
+    // with the power heuristic (mis) or alone (light).  The flag needs --fog-glow and --fog-grid: the sample picks a cell of the grid.
+    bool fog_glow_on = false, fog_glow_sample_on = false;
     rt_glow_params fog_glow;
     rt_glow_params_init(&fog_glow);
+    rt_glow_sample_params fog_glow_sample;
+    rt_glow_sample_params_init(&fog_glow_sample);
     std::string fog_heat_file;
     {
         bool fog_flag = false, grid_flag = false, heat_flag = false, by_density = false;
@@ -104,6 +108,13 @@ int main(int argc, char *argv[]) {
             if (arg == "--fog-heat") {
                 heat_flag = true;
                 fog_heat_file = a + 1 < argc ? argv[a + 1] : "";
+            }
+            if (arg == "--fog-glow-sample") {
+                fog_glow_sample_on = true;
+                const std::string value = a + 1 < argc ? argv[a + 1] : "";
+                if (value != "mis" && value != "light") bad = "--fog-glow-sample takes mis or light";
+                fog_glow_sample.sample = 1;
+                fog_glow_sample.mis = value == "light" ? 0 : 1;
             }
             if (arg == "--fog-glow") {
                 fog_glow_on = true;
@@ -124,6 +135,9 @@ int main(int argc, char *argv[]) {
         if (fog_glow_on && bad.empty() && heat_flag && by_density) bad = "--fog-glow R,G,B:density and --fog-heat exclude each other: the emission follows one grid";
         if (fog_glow_on && bad.empty() && by_density && !grid_flag) bad = "--fog-glow R,G,B:density follows the density grid: it needs --fog-grid FILE";
         if (fog_glow_on && bad.empty() && heat_flag && !grid_flag) bad = "--fog-heat has the dimensions of the density grid: it needs --fog-grid FILE";
+        if (fog_glow_sample_on && bad.empty() && !fog_glow_on) bad = "--fog-glow-sample aims at the glow: it needs --fog-glow R,G,B";
+        if (fog_glow_sample_on && bad.empty() && !grid_flag)
+            bad = "--fog-glow-sample picks a cell of the density grid: it needs --fog-grid FILE (a homogeneous box can pass a 1 x 1 x 1 grid)";
         if (!bad.empty()) {
             std::cerr << "rtp_main: " << bad << "\n";
             return 99;
@@ -647,9 +661,16 @@ int main(int argc, char *argv[]) {
                     std::cerr << "rtp_main: --fog-heat: " << rt_get_last_error_string() << "\n";
                     return 99;
                 }
+                rt_glow_sampler *fog_sampler = nullptr;
+                if (fog_glow_sample_on && rt_glow_sampler_create(fog_volume, fog_glow.source, fog_heat_volume, &fog_sampler) != RT_OK) {
+                    std::cerr << "rtp_main: --fog-glow-sample: " << rt_get_last_error_string() << "\n";
+                    return 99;
+                }
                 rtp::gpu_render_lens(params, desc, lens, shutter, aov, denoise, nullptr, nullptr, nullptr, &lit, fog_noise_on ? &fog_noise : noise_on ? &noise : nullptr,
                                      denoise_adaptive, &stop_rule, denoise_adaptive_temporal, fog_on ? &fog : nullptr, stop_history, fog_volume, fog_denoise,
-                                     fog_tint_on ? &fog_tint : nullptr, fog_glow_on ? &fog_glow : nullptr, fog_heat_volume);
+                                     fog_tint_on ? &fog_tint : nullptr, fog_glow_on ? &fog_glow : nullptr, fog_heat_volume,
+                                     fog_glow_sample_on ? &fog_glow_sample : nullptr, fog_sampler);
+                rt_glow_sampler_destroy(fog_sampler);
                 rt_volume_destroy(fog_heat_volume);
                 rt_volume_destroy(fog_volume);
                 rt_env_destroy(lit_env);

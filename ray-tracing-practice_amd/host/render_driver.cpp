@@ -348,7 +348,7 @@ void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const
                      const rt_nee_params *nee, const rt_env *env, const rt_env_params *env_params, const rt_lit_params *lit,
                      const rt_adaptive_params *noise, bool denoise_adaptive, const rt_stop_params *stop, bool denoise_adaptive_temporal,
                      const rt_medium_params *medium, bool stop_history, const rt_volume *volume, bool fog_denoise, const rt_chroma_params *chroma,
-                     const rt_glow_params *glow, const rt_volume *heat) {
+                     const rt_glow_params *glow, const rt_volume *heat, const rt_glow_sample_params *glow_sample, const rt_glow_sampler *sampler) {
     if (fog_denoise && noise) denoise_adaptive = true;
     else if (fog_denoise) denoise = true;
     rt_scene *scene = nullptr;
@@ -431,6 +431,8 @@ void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const
             frame_lit.cam_close = cam_close;
             frame_lit.lens = &lens;
             if (medium && chroma) RTP_CHECK(rt_render_chroma(scene, &cam, &frame_lit, medium, volume, chroma, nullptr, 0, d_fb, nullptr, 1, nullptr));
+            else if (medium && glow && glow_sample)
+                RTP_CHECK(rt_render_glow_sampled(scene, &cam, &frame_lit, medium, volume, glow, heat, glow_sample, sampler, nullptr, 0, d_fb, nullptr, 1, nullptr));
             else if (medium && glow) RTP_CHECK(rt_render_glow(scene, &cam, &frame_lit, medium, volume, glow, heat, nullptr, 0, d_fb, nullptr, 1, nullptr));
             else if (medium && volume) RTP_CHECK(rt_render_volume(scene, &cam, &frame_lit, medium, volume, nullptr, 0, d_fb, nullptr, 1, nullptr));
             else if (medium) RTP_CHECK(rt_render_medium(scene, &cam, &frame_lit, medium, nullptr, 0, d_fb, nullptr, 1, nullptr));

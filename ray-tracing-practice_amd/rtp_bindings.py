@@ -380,6 +380,29 @@ def _glow_struct(glow):
     return C.byref(glow_params(radiance=glow))
 
 
+class GlowSampleParams(_Sized):
+    """rt_glow_sample_params (include/rtp_amd.h, "light samples of the glow"): an IN structure of the caller's size — struct_bytes is set
+    on construction; sample and mis are 0 until rt_glow_sample_params_init (glow_sample_params()) fills the defaults."""
+    _fields_ = [("struct_bytes", C.c_uint32), ("sample", C.c_int32), ("mis", C.c_int32)]
+
+
+def glow_sample_params(sample=0, mis=1):
+    """rt_glow_sample_params with the library's defaults, then sample (0 off, 1 the glow is light-sampled) and mis (1 the power heuristic,
+    0 light sampling alone).  Nothing is checked here: the library refuses what it does not take."""
+    p = _params(GlowSampleParams, "rt_glow_sample_params", (), {})
+    p.sample = int(sample)
+    p.mis = int(mis)
+    return p
+
+
+def _glow_sample_struct(sample):
+    """None → NULL (no light samples); a GlowSampleParams as it is; a dict → glow_sample_params(**dict); "mis" and "light" → sample = 1
+    with mis 1 and 0."""
+    if isinstance(sample, str):
+        return C.byref(glow_sample_params(sample=1, mis={"mis": 1, "light": 0}[sample]))
+    return _struct(sample, GlowSampleParams, glow_sample_params)
+
+
 class Env:
     """rt_env: an octahedral environment map with its sampling table on the current device.  Env(rgb) takes an (n, n, 3) array;
     Env.from_equirect(image, n) resamples a lat-long image first.  A context manager; close() destroys the object."""
@@ -472,6 +495,51 @@ class Volume:
             pass
 
 
+class GlowSampler:
+    """rt_glow_sampler: the table that light samples of a glow pick their cell from, on the volume's device.  GlowSampler(volume, source,
+    heat) takes the Volumes of the call it is for (heat: source 2 only) and is closed before them.  A context manager."""
+
+    def __init__(self, volume, source=0, heat=None):
+        self.nx, self.ny, self.nz = volume.nx, volume.ny, volume.nz
+        h = C.c_void_p()
+        _check(amd_lib().rt_glow_sampler_create(_volume_handle(volume), int(source), _volume_handle(heat), C.byref(h)), "rt_glow_sampler_create")
+        self._h = h
+
+    def table(self, z=0, y=0):
+        """rt_glow_sampler_table: (count, slab cdf (nz), slab z's row cdf (ny), row (z, y)'s cell cdf and its cells' pc (nx each));
+        count = nx * ny * nz, or 0 for an empty sampler."""
+        out = [np.zeros(n, dtype=np.float32) for n in (self.nz, self.ny, self.nx, self.nx)]
+        count = C.c_int32()
+        _check(amd_lib().rt_glow_sampler_table(self._h, z, y, *(a.ctypes.data for a in out), C.byref(count)), "rt_glow_sampler_table")
+        return (count.value, *out)
+
+    def close(self):
+        if self._h is not None:
+            amd_lib().rt_glow_sampler_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _sampler_handle(sampler):
+    """None → NULL; a GlowSampler → its handle."""
+    if sampler is None:
+        return None
+    if not isinstance(sampler, GlowSampler) or sampler._h is None:
+        raise RtError("sampler must be an open rtp_bindings.GlowSampler (or None)")
+    return sampler._h
+
+
 def _volume_handle(volume):
     """None → NULL (no grid: rt_render_medium itself); a Volume → its handle."""
     if volume is None:
@@ -528,7 +596,7 @@ _P, _VP, _STR, _INT, _I32, _U32, _I64, _U64 = C.POINTER, C.c_void_p, C.c_char_p,
 _STATUS = C.c_int
 _DESC, _CFG, _CAM, _SHARD, _TIMING, _AOV = _P(SceneDesc), _P(Config), _P(CameraData), _P(Shard), _P(Timing), _P(AovBuffers)
 _DENOISE, _ADAPTIVE, _STOP, _LENS, _NEE, _ENV = _P(DenoiseParams), _P(AdaptiveParams), _P(StopParams), _P(LensParams), _P(NeeParams), _P(EnvParams)
-_LIT, _MEDIUM, _CHROMA, _GLOW = _P(LitParams), _P(MediumParams), _P(ChromaParams), _P(GlowParams)
+_LIT, _MEDIUM, _CHROMA, _GLOW, _GLOW_SAMPLE = _P(LitParams), _P(MediumParams), _P(ChromaParams), _P(GlowParams), _P(GlowSampleParams)
 _OUT = [_VP, _I32, _TIMING]          # how a render call ends: void *hip_stream, int32_t sync, rt_timing *timing
 
 # the calls every build has: a library without one of them fails at load
@@ -625,6 +693,12 @@ _AMD_LATER = {
     "rt_glow_params_init": (None, [_GLOW]),
     "rt_render_glow": (_STATUS, [_VP, _CAM, _LIT, _MEDIUM, _VP, _GLOW, _VP, _SHARD, _I32, _VP, *_OUT]),
     "rt_trace_samples_glow": (_STATUS, [_VP, _CAM, _LIT, _MEDIUM, _VP, _GLOW, _VP, _I32] + [_VP] * 10),
+    "rt_glow_sample_params_init": (None, [_GLOW_SAMPLE]),
+    "rt_glow_sampler_create": (_STATUS, [_VP, _I32, _VP, _P(_VP)]),
+    "rt_glow_sampler_destroy": (_STATUS, [_VP]),
+    "rt_glow_sampler_table": (_STATUS, [_VP, _I32, _I32] + [_VP] * 4 + [_P(_I32)]),
+    "rt_render_glow_sampled": (_STATUS, [_VP, _CAM, _LIT, _MEDIUM, _VP, _GLOW, _VP, _GLOW_SAMPLE, _VP, _SHARD, _I32, _VP, *_OUT]),
+    "rt_trace_samples_glow_sampled": (_STATUS, [_VP, _CAM, _LIT, _MEDIUM, _VP, _GLOW, _VP, _GLOW_SAMPLE, _VP, _I32] + [_VP] * 11),
 }
 # the calls that take a prior: their _rule call (the judgement: the call itself) and, last, the device address of the prior
 for _base, _prior in (("rt_render_adaptive_rule", "rt_render_adaptive_prior"), ("rt_render_lit_adaptive_rule", "rt_render_lit_adaptive_prior"),
@@ -1539,6 +1613,33 @@ class DeviceScene:
         lit = lit_params(cam_close=cam_close, lens=lens, emitters=emitters, nee=nee, env=env, env_params=env_params)
         _check(amd_lib().rt_trace_samples_glow(self._h, C.byref(cam), C.byref(lit), _medium_struct(medium), _volume_handle(volume), _glow_struct(glow),
                                                _volume_handle(heat), n, ijs.ctypes.data, *(a.ctypes.data for a in out)), "rt_trace_samples_glow")
+        return out
+
+    def render_glow_sampled(self, cam, d_fb_ptr, *, medium=None, volume=None, glow=None, heat=None, sample=None, sampler=None, cam_close=None, lens=None,
+                            emitters=True, nee=None, env=None, env_params=None, shard=None, stream=None, sync=True, sample_first=0):
+        """rt_render_glow_sampled: rt_render_glow with light samples of the glow (sample: None, "mis", "light", a dict of
+        glow_sample_params' keywords or a GlowSampleParams; sampler: the GlowSampler of the call's grids and source; the other keywords
+        are render_glow's).  Returns the rt_timing of this call."""
+        lit = lit_params(cam_close=cam_close, lens=lens, emitters=emitters, nee=nee, env=env, env_params=env_params)
+        return self._call("rt_render_glow_sampled", C.byref(cam), C.byref(lit), _medium_struct(medium), _volume_handle(volume), _glow_struct(glow),
+                          _volume_handle(heat), _glow_sample_struct(sample), _sampler_handle(sampler), _ref(shard), sample_first, C.c_void_p(d_fb_ptr),
+                          *_stream_sync(stream, sync))
+
+    def render_glow_sampled_to_host(self, cam, *, medium=None, volume=None, glow=None, heat=None, sample=None, sampler=None, cam_close=None, lens=None,
+                                    emitters=True, nee=None, env=None, env_params=None, shard=None, sample_first=0):
+        """rt_render_glow_sampled through a fresh device buffer: (rows, width, 3) float32 sums and the rt_timing."""
+        return _frame_to_host(cam, shard, lambda d: self.render_glow_sampled(cam, d, medium=medium, volume=volume, glow=glow, heat=heat, sample=sample,
+                                                                             sampler=sampler, cam_close=cam_close, lens=lens, emitters=emitters, nee=nee,
+                                                                             env=env, env_params=env_params, shard=shard, sample_first=sample_first))
+
+    def trace_samples_glow_sampled(self, cam, ijs, *, medium=None, volume=None, glow=None, heat=None, sample=None, sampler=None, cam_close=None, lens=None,
+                                   emitters=True, nee=None, env=None, env_params=None):
+        """rt_trace_samples_glow_sampled: trace_samples_glow's nine columns and glow_samples, the glow shadow rays per sample (n,)."""
+        ijs, n, out = _probe(ijs, _RGB, _COUNT, _COUNT, _SEED, _SEED, _SEED, _SEED, _COUNT, (np.float32, ()), _COUNT)
+        lit = lit_params(cam_close=cam_close, lens=lens, emitters=emitters, nee=nee, env=env, env_params=env_params)
+        _check(amd_lib().rt_trace_samples_glow_sampled(self._h, C.byref(cam), C.byref(lit), _medium_struct(medium), _volume_handle(volume), _glow_struct(glow),
+                                                       _volume_handle(heat), _glow_sample_struct(sample), _sampler_handle(sampler), n, ijs.ctypes.data,
+                                                       *(a.ctypes.data for a in out)), "rt_trace_samples_glow_sampled")
         return out
 
     def last_kernel_ms(self):
