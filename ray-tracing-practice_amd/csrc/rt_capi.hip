@@ -3343,14 +3343,31 @@ rt_status rt_trace_samples_lit(rt_scene *sc, const rt_camera_data *cam_open, con
     });
 }
 
-// ---- rt_render_medium / rt_trace_samples_medium (rtp_amd.h, "participating medium"): rt_render_lit under one homogeneous
-// medium.  No medium (NULL, or sigma_t == 0) is rt_render_lit itself; otherwise the kernels of rt_medium.hip.inc, on the call's emitter
-// table like every lit call's.
+// ---- rt_render_medium / rt_trace_samples_medium and the fog calls above them: one setup (fog_setup), one light
+// (with_fog_light), one frame tail (fog_frame) and one probe tail (fog_probe) under rt_render_lit with a medium (§25), a density grid in
+// its box (§28; its AOVs §33, its adaptive call §29), a tint (§34) or a glow (§35), and light samples of the glow (§36).
 void rt_medium_params_init(rt_medium_params *p) {
     if (!p) return;
     std::memset(p, 0, sizeof(*p));
     p->struct_bytes = (uint32_t)sizeof(*p);
     p->albedo[0] = p->albedo[1] = p->albedo[2] = 1.0f;
+}
+void rt_chroma_params_init(rt_chroma_params *p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->struct_bytes = (uint32_t)sizeof(*p);
+    p->tint[0] = p->tint[1] = p->tint[2] = 1.0f;
+}
+void rt_glow_params_init(rt_glow_params *p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->struct_bytes = (uint32_t)sizeof(*p);
+}
+void rt_glow_sample_params_init(rt_glow_sample_params *p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->struct_bytes = (uint32_t)sizeof(*p);
+    p->mis = 1;
 }
 
 // the density grid of rt_render_volume (rt_volume_create, below)
@@ -3358,6 +3375,14 @@ struct rt_volume {
     int device = 0;
     int32_t nx = 0, ny = 0, nz = 0;
     float *rho = nullptr;              // nx * ny * nz, x fastest
+};
+// the table of rt_render_glow_sampled (rt_glow_sampler_create, below)
+struct rt_glow_sampler {
+    int device = 0;
+    int32_t source = 0, nx = 0, ny = 0, nz = 0;
+    const rt_volume *volume = nullptr, *heat = nullptr;          // what it was built from (compared, never read again)
+    bool empty = false;
+    float *slab_cdf = nullptr, *row_cdf = nullptr, *cell_cdf = nullptr, *pc = nullptr;
 };
 
 namespace {
@@ -3409,11 +3434,6 @@ rt_status with_medium_lit(rt_scene *sc, const LitSetup &S, const rtk::MediumDev 
         return f(T);
     });
 }
-// the volume's check among the parameters (after the medium's, before the scene is looked at)
-rt_status volume_setup(const char *what, const rt_medium_params *medium, const rtk::MediumDev &M, const rt_volume *volume) {
-    if (volume && !(medium && M.region == 2)) return fail(RT_ERR_INVALID_ARG, std::string(what) + ": a volume needs a medium with region 2 (the box the grid fills)");
-    return RT_OK;
-}
 // with_medium_lit with the grid beside the medium
 extern "C++" template <class F>
 rt_status with_volume_lit(rt_scene *sc, const LitSetup &S, const rtk::MediumDev &M, const rt_volume *volume, F &&f) {
@@ -3422,40 +3442,37 @@ rt_status with_volume_lit(rt_scene *sc, const LitSetup &S, const rtk::MediumDev 
         return f(T);
     });
 }
-// The light of a call that may have fog: no medium (sigma_t == 0) is with_lit's, no volume with_medium_lit's
-extern "C++" template <class F>
-rt_status with_fog_lit(rt_scene *sc, const LitSetup &S, const rtk::MediumDev &M, const rt_volume *volume, F &&f) {
-    if (!(M.sigma_t > 0.0f)) return with_lit(sc, S, f);
-    if (!volume) return with_medium_lit(sc, S, M, f);
-    return with_volume_lit(sc, S, M, volume, f);
-}
 
-// the probe kernel of a light with fog (d_cells: the grid's column)
+// The columns a fog probe has beyond the lit probe's (the caller's on the host, the probe's own on the device): the medium stream's
+// final state and the event count of every fog call, the grid's cells, the glow's length, the glow's light samples.  Null: the call has no
+// such column
+struct FogColumns {
+    uint32_t *med;
+    int32_t *events, *cells;
+    float *glow_length;
+    int32_t *glow_samples;
+};
+// the probe kernel of a light with fog, on the columns its light has
 extern "C++" template <bool kLens, class Table>
-void launch_fog_probe(const rtk::KParams &KP, const rtk::MediumLit<Table> &T, const rtk::LensCam &C, int32_t n, uint32_t *d_nee, uint32_t *d_env, uint32_t *d_med,
-                      int32_t *d_events, int32_t *, float *, int32_t *) {
-    hipLaunchKernelGGL((rtk::medium_probe_kernel<kLens, Table>), dim3((n + 255) / 256), dim3(256), 0, 0, KP, T, C, d_nee, d_env, d_med, d_events);
+void launch_fog_probe(const rtk::KParams &KP, const rtk::MediumLit<Table> &T, const rtk::LensCam &C, int32_t n, uint32_t *d_nee, uint32_t *d_env, const FogColumns &d) {
+    hipLaunchKernelGGL((rtk::medium_probe_kernel<kLens, Table>), dim3((n + 255) / 256), dim3(256), 0, 0, KP, T, C, d_nee, d_env, d.med, d.events);
 }
 extern "C++" template <bool kLens, class Table>
-void launch_fog_probe(const rtk::KParams &KP, const rtk::VolumeLit<Table> &T, const rtk::LensCam &C, int32_t n, uint32_t *d_nee, uint32_t *d_env, uint32_t *d_med,
-                      int32_t *d_events, int32_t *d_cells, float *, int32_t *) {
-    hipLaunchKernelGGL((rtk::volume_probe_kernel<kLens, Table>), dim3((n + 255) / 256), dim3(256), 0, 0, KP, T, C, d_nee, d_env, d_med, d_events, d_cells);
+void launch_fog_probe(const rtk::KParams &KP, const rtk::VolumeLit<Table> &T, const rtk::LensCam &C, int32_t n, uint32_t *d_nee, uint32_t *d_env, const FogColumns &d) {
+    hipLaunchKernelGGL((rtk::volume_probe_kernel<kLens, Table>), dim3((n + 255) / 256), dim3(256), 0, 0, KP, T, C, d_nee, d_env, d.med, d.events, d.cells);
 }
 extern "C++" template <bool kLens, class Base>
-void launch_fog_probe(const rtk::KParams &KP, const rtk::ChromaLit<Base> &T, const rtk::LensCam &C, int32_t n, uint32_t *d_nee, uint32_t *d_env, uint32_t *d_med,
-                      int32_t *d_events, int32_t *d_cells, float *, int32_t *) {
-    hipLaunchKernelGGL((rtk::chroma_probe_kernel<kLens, Base>), dim3((n + 255) / 256), dim3(256), 0, 0, KP, T, C, d_nee, d_env, d_med, d_events, d_cells);
+void launch_fog_probe(const rtk::KParams &KP, const rtk::ChromaLit<Base> &T, const rtk::LensCam &C, int32_t n, uint32_t *d_nee, uint32_t *d_env, const FogColumns &d) {
+    hipLaunchKernelGGL((rtk::chroma_probe_kernel<kLens, Base>), dim3((n + 255) / 256), dim3(256), 0, 0, KP, T, C, d_nee, d_env, d.med, d.events, d.cells);
 }
 extern "C++" template <bool kLens, class Base>
-void launch_fog_probe(const rtk::KParams &KP, const rtk::GlowLit<Base> &T, const rtk::LensCam &C, int32_t n, uint32_t *d_nee, uint32_t *d_env, uint32_t *d_med,
-                      int32_t *d_events, int32_t *d_cells, float *d_glow, int32_t *) {
-    hipLaunchKernelGGL((rtk::glow_probe_kernel<kLens, Base>), dim3((n + 255) / 256), dim3(256), 0, 0, KP, T, C, d_nee, d_env, d_med, d_events, d_cells, d_glow);
+void launch_fog_probe(const rtk::KParams &KP, const rtk::GlowLit<Base> &T, const rtk::LensCam &C, int32_t n, uint32_t *d_nee, uint32_t *d_env, const FogColumns &d) {
+    hipLaunchKernelGGL((rtk::glow_probe_kernel<kLens, Base>), dim3((n + 255) / 256), dim3(256), 0, 0, KP, T, C, d_nee, d_env, d.med, d.events, d.cells, d.glow_length);
 }
 extern "C++" template <bool kLens, class Table>
-void launch_fog_probe(const rtk::KParams &KP, const rtk::GlowSampleLit<Table> &T, const rtk::LensCam &C, int32_t n, uint32_t *d_nee, uint32_t *d_env, uint32_t *d_med,
-                      int32_t *d_events, int32_t *d_cells, float *d_glow, int32_t *d_shots) {
-    hipLaunchKernelGGL((rtk::glow_sample_probe_kernel<kLens, Table>), dim3((n + 255) / 256), dim3(256), 0, 0, KP, T, C, d_nee, d_env, d_med, d_events, d_cells, d_glow,
-                       d_shots);
+void launch_fog_probe(const rtk::KParams &KP, const rtk::GlowSampleLit<Table> &T, const rtk::LensCam &C, int32_t n, uint32_t *d_nee, uint32_t *d_env, const FogColumns &d) {
+    hipLaunchKernelGGL((rtk::glow_sample_probe_kernel<kLens, Table>), dim3((n + 255) / 256), dim3(256), 0, 0, KP, T, C, d_nee, d_env, d.med, d.events, d.cells,
+                       d.glow_length, d.glow_samples);
 }
 // The chroma kernels' light (rt_render_chroma): the medium's or the grid's with sigma_t = 1, and the three channels' extinctions beside it
 extern "C++" template <class F>
@@ -3469,7 +3486,7 @@ rt_status with_chroma_lit(rt_scene *sc, const LitSetup &S, const rtk::MediumDev 
     return volume ? with_volume_lit(sc, S, M1, volume, chroma) : with_medium_lit(sc, S, M1, chroma);
 }
 // The glow kernels' light (rt_render_glow): the medium's or the grid's as the grey kernels hold it, and the radiance beside it; over a grid
-// also the cells' h (heat: null = 1, source 0; the density itself, source 1; a heat grid's values, source 2)
+// also the cells' h (heat: null = 1, source 0; the density itself, source 1; a heat grid's values, source 2: with_fogged_light)
 struct GlowDev {
     float radiance[3];
     const float *heat;
@@ -3494,89 +3511,220 @@ rt_status with_glow_sample_lit(rt_scene *sc, const LitSetup &S, const rtk::Mediu
         return f(T);
     });
 }
-// rt_trace_samples_medium, rt_trace_samples_volume (volume, cells: the latter's; null in the former), rt_trace_samples_chroma (sigma: its
-// three extinctions; null in the others), rt_trace_samples_glow (glow, glow_length: its radiance and column; null in the others) and
-// rt_trace_samples_glow_sampled (sampler, glow_samples: its table and column, beside the glow's; null in the others) from
-// their probe launch on: the caller has made its checks and handed over what has no medium or no grid.  `what` starts every refusal.
-rt_status fog_probe(const char *what, rt_scene *sc, const rt_camera_data *cam_open, const LitSetup &S, const rtk::MediumDev &M, const rt_volume *volume, rtk::KParams &P,
-                    int32_t n, const int32_t *ijs, float *radiance, int32_t *rays, int32_t *medium_events, uint32_t *final_seed, uint32_t *final_nee_seed,
-                    uint32_t *final_env_seed, uint32_t *final_medium_seed, int32_t *cells, const float *sigma = nullptr, const GlowDev *glow = nullptr,
-                    float *glow_length = nullptr, const rtk::GlowSamplerDev *sampler = nullptr, int32_t *glow_samples = nullptr) {
+
+// The ladder of the fog calls, each rung the one below with one thing more: a medium, a grid in its box, then either a tint or a glow, and
+// light samples of the glow.  A call names the rung it goes up to (fog_setup) and refuses under that rung's name
+enum FogRung { kFogMedium, kFogVolume, kFogTint, kFogGlow, kFogSample };
+const char *const kFogFrame[] = {"rt_render_medium", "rt_render_volume", "rt_render_chroma", "rt_render_glow", "rt_render_glow_sampled"};
+const char *const kFogProbe[] = {"rt_trace_samples_medium", "rt_trace_samples_volume", "rt_trace_samples_chroma", "rt_trace_samples_glow",
+                                 "rt_trace_samples_glow_sampled"};
+// What a fog call is made of, after its parameter checks.  What a call has not (or has without effect) stays as it is here, and the call
+// is the lower rung's by that alone: grey (no tint, equal tints, no medium: M.sigma_t then holds sigma_t * e), dark (no glow, radiance 0),
+// not sampled (no sample, an empty sampler, a dark glow)
+struct FogSetup {
+    FogRung rung = kFogMedium;          // how far up the ladder the call goes
+    LitSetup S;
+    rtk::MediumDev M{};                 // sigma_t == 0: no medium
+    const rt_volume *volume = nullptr;
+    float sigma[3] = {0.0f, 0.0f, 0.0f};
+    bool grey = true;
+    GlowDev G{};                        // (heat: with_fogged_light fills it — the handles are not read before the scene has been looked at)
+    const rt_volume *heat = nullptr;
+    int32_t source = 0;
+    bool dark = true;
+    rtk::GlowSamplerDev Q{};
+    const rt_glow_sampler *sampler = nullptr;          // of a call that asks for samples (also an empty one's, for its device's check)
+    bool sampled = false;
+};
+// the caller's arguments that the rungs' checks look at, lowest rung first (left out or null: not the call's, or not given)
+struct FogArgs {
+    const rt_lit_params *lit;
+    const rt_medium_params *medium;
+    const rt_volume *volume;
+    const rt_chroma_params *chroma;
+    const rt_glow_params *glow;
+    const rt_volume *heat;
+    const rt_glow_sample_params *sample;
+    const rt_glow_sampler *sampler;
+};
+// The parameter checks of a fog call up to its rung, in the ladder's order — lit, medium, volume, then the tint's or the glow's, then the
+// sample's: everything before the scene is looked at.  What lies above the rung is not looked at
+rt_status fog_setup(const char *what, FogRung rung, const rt_camera_data *cam_open, const FogArgs &A, FogSetup &X) {
+    const auto [lit, medium, volume, chroma, glow, heat, sample, sampler] = A;
     const std::string w(what);
-    uint32_t *d_med = nullptr;
-    int32_t *d_events = nullptr, *d_cells = nullptr, *d_shots = nullptr;
-    float *d_glow = nullptr;
-    Scratch mem;
-    if (mem.alloc(d_med, (size_t)n * 4) != hipSuccess || mem.alloc(d_events, (size_t)n * 4) != hipSuccess || (cells && mem.alloc(d_cells, (size_t)n * 4) != hipSuccess) ||
-        (glow && mem.alloc(d_glow, (size_t)n * 4) != hipSuccess) || (sampler && mem.alloc(d_shots, (size_t)n * 4) != hipSuccess))
-        return fail(RT_ERR_OUT_OF_MEMORY, w + ": hipMalloc failed");
-    const rt_status st = run_probe(w + ": ", P, cam_open, n, ijs, radiance, rays, final_seed, final_nee_seed, final_env_seed,
-                                   [&](const rtk::KParams &KP, uint32_t *d_nee, uint32_t *d_env) {
-        auto probe = [&](const auto &T) {
-            if (S.lens) launch_fog_probe<true>(KP, T, S.C, n, d_nee, d_env, d_med, d_events, d_cells, d_glow, d_shots);
-            else launch_fog_probe<false>(KP, T, S.C, n, d_nee, d_env, d_med, d_events, d_cells, d_glow, d_shots);
-            return RT_OK;
-        };
-        if (sampler) return with_glow_sample_lit(sc, S, M, volume, *glow, *sampler, probe);
-        if (glow) return with_glow_lit(sc, S, M, volume, *glow, probe);
-        if (sigma) return with_chroma_lit(sc, S, M, volume, sigma, probe);
-        return volume ? with_volume_lit(sc, S, M, volume, probe) : with_medium_lit(sc, S, M, probe);
-    });
-    if (st != RT_OK) return st;
-    // (run_probe has waited for the device)
-    if (hipMemcpy(final_medium_seed, d_med, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(medium_events, d_events, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess ||
-        (cells && hipMemcpy(cells, d_cells, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess) ||
-        (glow && hipMemcpy(glow_length, d_glow, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess) ||
-        (sampler && hipMemcpy(glow_samples, d_shots, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess))
-        return fail(RT_ERR_HIP, w + ": hipMemcpy D2H failed");
+    X.rung = rung;
+    if (const rt_status st = lit_setup(what, cam_open, lit, X.S)) return st;
+    if (const rt_status st = medium_setup(what, medium, X.M)) return st;
+    if (volume && !(medium && X.M.region == 2)) return fail(RT_ERR_INVALID_ARG, w + ": a volume needs a medium with region 2 (the box the grid fills)");
+    X.volume = volume;
+    if (rung == kFogTint) {
+        rt_chroma_params cp;
+        rt_chroma_params_init(&cp);
+        if (const rt_status st = take_params(w, "rt_chroma_params", chroma, cp)) return st;
+        for (int k = 0; k < 3; ++k)
+            if (!(std::isfinite(cp.tint[k]) && cp.tint[k] >= 0.0f)) return fail(RT_ERR_INVALID_ARG, w + ": a tint channel is negative, NaN or infinite");
+        for (int k = 0; k < 3; ++k) {
+            X.sigma[k] = X.M.sigma_t * cp.tint[k];
+            if (!std::isfinite(X.sigma[k])) return fail(RT_ERR_INVALID_ARG, w + ": sigma_t * tint is not finite in a channel");
+        }
+        X.grey = (cp.tint[0] == cp.tint[1] && cp.tint[1] == cp.tint[2]) || !(X.M.sigma_t > 0.0f);
+        if (X.grey) X.M.sigma_t = X.sigma[0];
+    }
+    if (rung >= kFogGlow) {
+        rt_glow_params gp;
+        rt_glow_params_init(&gp);
+        if (const rt_status st = take_params(w, "rt_glow_params", glow, gp)) return st;
+        if (gp.source < 0 || gp.source > 2) return fail(RT_ERR_INVALID_ARG, w + ": source must be 0, 1 or 2");
+        for (int k = 0; k < 3; ++k)
+            if (!(std::isfinite(gp.radiance[k]) && gp.radiance[k] >= 0.0f)) return fail(RT_ERR_INVALID_ARG, w + ": a radiance channel is negative, NaN or infinite");
+        X.dark = gp.radiance[0] == 0.0f && gp.radiance[1] == 0.0f && gp.radiance[2] == 0.0f;
+        if (!X.dark && !(X.M.sigma_t > 0.0f))
+            return fail(RT_ERR_INVALID_ARG, w + ": a glow needs a medium with sigma_t > 0 (the emission rides on the free flight: a glow without extinction has no kernel)");
+        if (gp.source != 0 && !volume) return fail(RT_ERR_INVALID_ARG, w + ": source 1 and 2 need a volume (the grid the emission follows)");
+        if (gp.source == 2 && !heat) return fail(RT_ERR_INVALID_ARG, w + ": source 2 needs a heat grid");
+        if (gp.source == 2 && (heat->nx != volume->nx || heat->ny != volume->ny || heat->nz != volume->nz))
+            return fail(RT_ERR_INVALID_ARG, w + ": the heat grid's dimensions differ from the volume's");
+        if (gp.source != 2 && heat) return fail(RT_ERR_INVALID_ARG, w + ": a heat grid is for source 2 only");
+        for (int k = 0; k < 3; ++k) X.G.radiance[k] = gp.radiance[k];
+        X.source = gp.source;
+        X.heat = heat;
+    }
+    if (rung == kFogSample) {
+        rt_glow_sample_params sp;
+        rt_glow_sample_params_init(&sp);
+        if (const rt_status st = take_params(w, "rt_glow_sample_params", sample, sp)) return st;
+        if (sp.sample != 0 && sp.sample != 1) return fail(RT_ERR_INVALID_ARG, w + ": sample must be 0 or 1");
+        if (sp.mis != 0 && sp.mis != 1) return fail(RT_ERR_INVALID_ARG, w + ": mis must be 0 or 1");
+        if (!sample || sp.sample == 0) return RT_OK;
+        if (!volume) return fail(RT_ERR_INVALID_ARG, w + ": light samples of the glow need a volume (a homogeneous box can pass a 1 x 1 x 1 grid of density 1)");
+        if (!sampler) return fail(RT_ERR_INVALID_ARG, w + ": sample = 1 needs a sampler (rt_glow_sampler_create)");
+        if (sampler->source != X.source) return fail(RT_ERR_INVALID_ARG, w + ": the sampler was built for another source than the call's");
+        if (sampler->nx != volume->nx || sampler->ny != volume->ny || sampler->nz != volume->nz)
+            return fail(RT_ERR_INVALID_ARG, w + ": the sampler's dimensions differ from the volume's");
+        if (sampler->volume != volume || sampler->heat != heat) return fail(RT_ERR_INVALID_ARG, w + ": the sampler was built from other grids than the call's");
+        X.Q = {sampler->slab_cdf, sampler->row_cdf, sampler->cell_cdf, sampler->pc, sp.mis};
+        X.sampler = sampler;
+        X.sampled = !sampler->empty && !X.dark;
+    }
+    return RT_OK;
+}
+// the null scene's refusal, then the device of every handle the call holds against the scene's
+rt_status fog_scene(const std::string &w, const rt_scene *sc, const FogSetup &X) {
+    if (!sc) return fail(RT_ERR_INVALID_ARG, w + ": null scene");
+    if (X.volume && X.volume->device != sc->device) return fail(RT_ERR_INVALID_ARG, w + ": the volume was created on another device than the scene");
+    if (X.heat && X.heat->device != sc->device) return fail(RT_ERR_INVALID_ARG, w + ": the heat grid was created on another device than the scene");
+    if (X.sampler && X.sampler->device != sc->device) return fail(RT_ERR_INVALID_ARG, w + ": the sampler was created on another device than the scene");
+    return RT_OK;
+}
+// the rung whose kernels a call runs, by what it holds: the hand-overs, all at once (no medium at all: with_fog_light's)
+FogRung fog_rung_of(const FogSetup &X) { return X.sampled ? kFogSample : !X.dark ? kFogGlow : !X.grey ? kFogTint : X.volume ? kFogVolume : kFogMedium; }
+// The light of a call with a medium (M.sigma_t > 0), of fog_rung_of's rung: a GlowSampleLit, GlowLit, ChromaLit, VolumeLit or MediumLit
+extern "C++" template <class F>
+rt_status with_fogged_light(rt_scene *sc, const FogSetup &X, F &&f) {
+    if (!X.dark) {
+        GlowDev G = X.G;
+        G.heat = X.source == 0 ? nullptr : (X.source == 1 ? X.volume->rho : X.heat->rho);
+        if (X.sampled) return with_glow_sample_lit(sc, X.S, X.M, X.volume, G, X.Q, f);
+        return with_glow_lit(sc, X.S, X.M, X.volume, G, f);
+    }
+    if (!X.grey) return with_chroma_lit(sc, X.S, X.M, X.volume, X.sigma, f);
+    return X.volume ? with_volume_lit(sc, X.S, X.M, X.volume, f) : with_medium_lit(sc, X.S, X.M, f);
+}
+// the light of a fog call: no medium is with_lit's (a Lit or GlossLit)
+extern "C++" template <class F>
+rt_status with_fog_light(rt_scene *sc, const FogSetup &X, F &&f) {
+    return X.M.sigma_t > 0.0f ? with_fogged_light(sc, X, f) : with_lit(sc, X.S, f);
+}
+// The frame calls behind their parameter checks: the scene and the devices under the call's own name, then render_light_impl under the
+// name of the rung the call has become
+rt_status fog_frame(const FogSetup &X, rt_scene *sc, const rt_camera_data *cam_open, const rt_shard *shard, int32_t sample_first, float *d_fb_sum, void *hip_stream,
+                    int32_t sync, rt_timing *timing) {
+    if (const rt_status st = fog_scene(kFogFrame[X.rung], sc, X)) return st;
+    const LitSetup &S = X.S;
+    auto with_light = [&](auto frame) { return with_fog_light(sc, X, [&](const auto &T) { return frame(lit_kernels_of(S.lens, T).frame, &T); }); };
+    return render_light_impl(kFogFrame[fog_rung_of(X)], S.env ? &S.env->device : nullptr, with_light, sc, cam_open, shard, sample_first, d_fb_sum, hip_stream, sync, timing,
+                             &S.C);
+}
+// The probe calls behind their parameter checks.  `out` holds the columns of the call's rung (the others null); a column of a rung the
+// call has left on the way down is filled on the way back: cells 0, glow_length 0, glow_samples 0, and under no medium no event and the
+// medium stream's state as initialised.  The order is every probe's own: the glow rungs look at the scene and the devices
+// and hand over before the preamble, the volume and the medium behind it, and the lower rungs look at the volume's device last
+rt_status fog_probe(const FogSetup &X, rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, int32_t n, const int32_t *ijs, float *radiance,
+                    int32_t *rays, uint32_t *final_seed, uint32_t *final_nee_seed, uint32_t *final_env_seed, const FogColumns &out) {
+    const LitSetup &S = X.S;
+    if (n < 0 || (n > 0 && (!ijs || !radiance || !rays || !out.events || !final_seed || !final_nee_seed || !final_env_seed || !out.med ||
+                            (X.rung >= kFogVolume && !out.cells) || (X.rung >= kFogGlow && !out.glow_length) || (X.rung == kFogSample && !out.glow_samples))))
+        return fail(RT_ERR_INVALID_ARG, std::string(kFogProbe[X.rung]) + ": null argument");
+    rt_status st;
+    if (X.rung >= kFogGlow && (st = fog_scene(kFogProbe[X.rung], sc, X)) != RT_OK) return st;
+    // (a call above the medium's is the volume's at the lowest until the preamble has passed)
+    FogRung rung = X.rung == kFogMedium ? kFogMedium : std::max(fog_rung_of(X), kFogVolume);
+    rtk::KParams P;
+    if ((st = fill_params(sc, cam_open, nullptr, P)) != RT_OK) return st;
+    if ((st = check_device(sc)) != RT_OK) return st;
+    if (S.env && S.env->device != sc->device)
+        return fail(RT_ERR_INVALID_ARG, std::string(kFogProbe[rung]) + ": the environment was created on another device than the scene");
+    if (X.rung < kFogGlow && (st = fog_scene(kFogProbe[rung], sc, X)) != RT_OK) return st;
+    if (n == 0) return RT_OK;
+    if (rung == kFogVolume && !(X.volume && X.M.sigma_t > 0.0f)) rung = kFogMedium;
+    const std::string w(kFogProbe[rung]);
+    const FogColumns own{out.med, out.events, rung >= kFogVolume ? out.cells : nullptr, rung >= kFogGlow ? out.glow_length : nullptr,
+                         rung == kFogSample ? out.glow_samples : nullptr};
+    if (!(X.M.sigma_t > 0.0f)) {          // no medium (the rung is the medium's): rt_trace_samples_lit's columns
+        if ((st = rt_trace_samples_lit(sc, cam_open, lit, n, ijs, radiance, rays, final_seed, final_nee_seed, final_env_seed)) != RT_OK) return st;
+        for (int32_t k = 0; k < n; ++k) {
+            out.events[k] = 0;
+            const uint32_t base = rtd::wang_hash((uint32_t)ijs[3 * k] * (uint32_t)cam_open->image_width + (uint32_t)ijs[3 * k + 1]);
+            out.med[k] = rtd::wang_hash(rtd::wang_hash(base + (uint32_t)ijs[3 * k + 2]) ^ RT_MEDIUM_STREAM_KEY);
+        }
+    } else {
+        FogColumns d{};
+        Scratch mem;
+        if (mem.alloc(d.med, (size_t)n * 4) != hipSuccess || mem.alloc(d.events, (size_t)n * 4) != hipSuccess ||
+            (own.cells && mem.alloc(d.cells, (size_t)n * 4) != hipSuccess) || (own.glow_length && mem.alloc(d.glow_length, (size_t)n * 4) != hipSuccess) ||
+            (own.glow_samples && mem.alloc(d.glow_samples, (size_t)n * 4) != hipSuccess))
+            return fail(RT_ERR_OUT_OF_MEMORY, w + ": hipMalloc failed");
+        st = run_probe(w + ": ", P, cam_open, n, ijs, radiance, rays, final_seed, final_nee_seed, final_env_seed, [&](const rtk::KParams &KP, uint32_t *d_nee, uint32_t *d_env) {
+            return with_fogged_light(sc, X, [&](const auto &T) {
+                if (S.lens) launch_fog_probe<true>(KP, T, S.C, n, d_nee, d_env, d);
+                else launch_fog_probe<false>(KP, T, S.C, n, d_nee, d_env, d);
+                return RT_OK;
+            });
+        });
+        if (st != RT_OK) return st;
+        // (run_probe has waited for the device)
+        if (hipMemcpy(own.med, d.med, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(own.events, d.events, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+            (own.cells && hipMemcpy(own.cells, d.cells, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess) ||
+            (own.glow_length && hipMemcpy(own.glow_length, d.glow_length, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess) ||
+            (own.glow_samples && hipMemcpy(own.glow_samples, d.glow_samples, (size_t)n * 4, hipMemcpyDeviceToHost) != hipSuccess))
+            return fail(RT_ERR_HIP, w + ": hipMemcpy D2H failed");
+    }
+    for (int32_t k = 0; k < n; ++k) {
+        if (out.cells && !own.cells) out.cells[k] = 0;
+        if (out.glow_length && !own.glow_length) out.glow_length[k] = 0.0f;
+        if (out.glow_samples && !own.glow_samples) out.glow_samples[k] = 0;
+    }
     return RT_OK;
 }
 }  // namespace
 
 rt_status rt_render_medium(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium, const rt_shard *shard,
                            int32_t sample_first, float *d_fb_sum, void *hip_stream, int32_t sync, rt_timing *timing) {
-    LitSetup S;
-    if (const rt_status st = lit_setup("rt_render_medium", cam_open, lit, S)) return st;
-    rtk::MediumDev M{};
-    if (const rt_status st = medium_setup("rt_render_medium", medium, M)) return st;
-    if (!sc) return fail(RT_ERR_INVALID_ARG, "rt_render_medium: null scene");
-    auto with_light = [&](auto frame) { return with_fog_lit(sc, S, M, nullptr, [&](const auto &T) { return frame(lit_kernels_of(S.lens, T).frame, &T); }); };
-    return render_light_impl("rt_render_medium", S.env ? &S.env->device : nullptr, with_light, sc, cam_open, shard, sample_first, d_fb_sum, hip_stream, sync, timing,
-                             &S.C);
+    FogSetup X;
+    if (const rt_status st = fog_setup(kFogFrame[kFogMedium], kFogMedium, cam_open, {lit, medium}, X)) return st;
+    return fog_frame(X, sc, cam_open, shard, sample_first, d_fb_sum, hip_stream, sync, timing);
 }
 
 rt_status rt_trace_samples_medium(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium, int32_t n,
                                   const int32_t *ijs, float *radiance, int32_t *rays, int32_t *medium_events, uint32_t *final_seed, uint32_t *final_nee_seed,
                                   uint32_t *final_env_seed, uint32_t *final_medium_seed) {
-    const char *what = "rt_trace_samples_medium";
-    LitSetup S;
-    if (const rt_status st = lit_setup(what, cam_open, lit, S)) return st;
-    rtk::MediumDev M{};
-    if (const rt_status ms = medium_setup(what, medium, M)) return ms;
-    if (n < 0 || (n > 0 && (!ijs || !radiance || !rays || !medium_events || !final_seed || !final_nee_seed || !final_env_seed || !final_medium_seed)))
-        return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_medium: null argument");
-    rtk::KParams P;
-    rt_status st = fill_params(sc, cam_open, nullptr, P);
-    if (st != RT_OK) return st;
-    if ((st = check_device(sc)) != RT_OK) return st;
-    if (S.env && S.env->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_medium: the environment was created on another device than the scene");
-    if (n == 0) return RT_OK;
-    if (!(M.sigma_t > 0.0f)) {          // no medium: rt_trace_samples_lit's columns, no event, the med state as initialised
-        if ((st = rt_trace_samples_lit(sc, cam_open, lit, n, ijs, radiance, rays, final_seed, final_nee_seed, final_env_seed)) != RT_OK) return st;
-        for (int32_t k = 0; k < n; ++k) {
-            medium_events[k] = 0;
-            const uint32_t base = rtd::wang_hash((uint32_t)ijs[3 * k] * (uint32_t)cam_open->image_width + (uint32_t)ijs[3 * k + 1]);
-            final_medium_seed[k] = rtd::wang_hash(rtd::wang_hash(base + (uint32_t)ijs[3 * k + 2]) ^ RT_MEDIUM_STREAM_KEY);
-        }
-        return RT_OK;
-    }
-    return fog_probe(what, sc, cam_open, S, M, nullptr, P, n, ijs, radiance, rays, medium_events, final_seed, final_nee_seed, final_env_seed, final_medium_seed, nullptr);
+    FogSetup X;
+    if (const rt_status st = fog_setup(kFogProbe[kFogMedium], kFogMedium, cam_open, {lit, medium}, X)) return st;
+    return fog_probe(X, sc, cam_open, lit, n, ijs, radiance, rays, final_seed, final_nee_seed, final_env_seed, {final_medium_seed, medium_events, nullptr, nullptr, nullptr});
 }
 
 // ---- rt_volume / rt_render_volume / rt_trace_samples_volume (rtp_amd.h, "density grid"): rt_render_medium with a density
 // grid in its box.  No volume is rt_render_medium itself, sigma_t == 0 rt_render_lit; otherwise the kernels of rt_volume.hip.inc.
-// (struct rt_volume, volume_setup and with_volume_lit stand with the medium's helpers above, where with_fog_lit needs them.)
 rt_status rt_volume_create(const float *density, int32_t nx, int32_t ny, int32_t nz, rt_volume **out_volume) {
     if (!density || !out_volume) return fail(RT_ERR_INVALID_ARG, "rt_volume_create: null argument");
     *out_volume = nullptr;
@@ -3614,17 +3762,10 @@ rt_status rt_volume_destroy(rt_volume *volume) {
 
 rt_status rt_render_volume(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium, const rt_volume *volume,
                            const rt_shard *shard, int32_t sample_first, float *d_fb_sum, void *hip_stream, int32_t sync, rt_timing *timing) {
-    if (!volume) return rt_render_medium(sc, cam_open, lit, medium, shard, sample_first, d_fb_sum, hip_stream, sync, timing);
-    LitSetup S;
-    if (const rt_status st = lit_setup("rt_render_volume", cam_open, lit, S)) return st;
-    rtk::MediumDev M{};
-    if (const rt_status st = medium_setup("rt_render_volume", medium, M)) return st;
-    if (const rt_status st = volume_setup("rt_render_volume", medium, M, volume)) return st;
-    if (!sc) return fail(RT_ERR_INVALID_ARG, "rt_render_volume: null scene");
-    if (volume->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_render_volume: the volume was created on another device than the scene");
-    auto with_light = [&](auto frame) { return with_fog_lit(sc, S, M, volume, [&](const auto &T) { return frame(lit_kernels_of(S.lens, T).frame, &T); }); };
-    return render_light_impl("rt_render_volume", S.env ? &S.env->device : nullptr, with_light, sc, cam_open, shard, sample_first, d_fb_sum, hip_stream, sync, timing,
-                             &S.C);
+    const FogRung rung = volume ? kFogVolume : kFogMedium;          // (no volume is rt_render_medium from its first check on)
+    FogSetup X;
+    if (const rt_status st = fog_setup(kFogFrame[rung], rung, cam_open, {lit, medium, volume}, X)) return st;
+    return fog_frame(X, sc, cam_open, shard, sample_first, d_fb_sum, hip_stream, sync, timing);
 }
 
 // ---- rt_render_aov_volume (rtp_amd.h, "AOVs under fog"): rt_render_aov_lens's frame (aov_impl) with the accumulation of
@@ -3638,14 +3779,13 @@ rt_status rt_render_aov_volume(rt_scene *sc, const rt_camera_data *cam_open, con
     rt_aov_buffers b{};
     std::memcpy(&b, buffers, buffers->struct_bytes < sizeof(b) ? buffers->struct_bytes : sizeof(b));
     if (!b.albedo_sum && !b.normal_sum && !b.depth_sum && !b.hit_count && !b.first_prim) return fail(RT_ERR_INVALID_ARG, "rt_render_aov_volume: every AOV buffer is NULL");
-    LitSetup S;
-    if (const rt_status st = lit_setup(what, cam_open, lit, S)) return st;
+    FogSetup X;
+    if (const rt_status st = fog_setup(what, kFogVolume, cam_open, {lit, medium, volume}, X)) return st;
+    if (const rt_status st = fog_scene(what, sc, X)) return st;
+    const LitSetup &S = X.S;
+    if (!(X.M.sigma_t > 0.0f)) return aov_impl(sc, cam_open, shard, nullptr, buffers, hip_stream, sync, timing, sample_first, &S.C, what, nullptr, d_transmittance_sum);
     rtk::AovFog G{};
-    if (const rt_status st = medium_setup(what, medium, G.M)) return st;
-    if (const rt_status st = volume_setup(what, medium, G.M, volume)) return st;
-    if (!sc) return fail(RT_ERR_INVALID_ARG, "rt_render_aov_volume: null scene");
-    if (volume && volume->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_render_aov_volume: the volume was created on another device than the scene");
-    if (!(G.M.sigma_t > 0.0f)) return aov_impl(sc, cam_open, shard, nullptr, buffers, hip_stream, sync, timing, sample_first, &S.C, what, nullptr, d_transmittance_sum);
+    G.M = X.M;
     if (volume) G.V = rtk::VolumeDev{volume->rho, volume->nx, volume->ny, volume->nz};
     G.tr = d_transmittance_sum;
     return aov_impl(sc, cam_open, shard, nullptr, buffers, hip_stream, sync, timing, sample_first, &S.C, what, &G);
@@ -3664,252 +3804,67 @@ rt_status rt_render_volume_adaptive(rt_scene *sc, const rt_camera_data *cam_open
     if (st != RT_OK) return st;
     if ((st = stop_check(what, stop, rule, "")) != RT_OK) return st;
     if ((st = prior_check(what, d_prior, cam_open, shard, d_fb_sum, d_spp, d_moments)) != RT_OK) return st;
-    LitSetup S;
-    if ((st = lit_setup(what, cam_open, lit, S)) != RT_OK) return st;
-    rtk::MediumDev M{};
-    if ((st = medium_setup(what, medium, M)) != RT_OK) return st;
-    if ((st = volume_setup(what, medium, M, volume)) != RT_OK) return st;
+    FogSetup X;
+    if ((st = fog_setup(what, kFogVolume, cam_open, {lit, medium, volume}, X)) != RT_OK) return st;
     if ((st = check_sample_range(what, sample_first, a.min_spp + (a.max_spp - a.min_spp) / a.batch_spp * a.batch_spp)) != RT_OK) return st;
     if (!d_fb_sum || !d_spp) return fail(RT_ERR_INVALID_ARG, "rt_render_volume_adaptive: null framebuffer or sample counts");
-    if (!sc) return fail(RT_ERR_INVALID_ARG, "rt_render_volume_adaptive: null scene");
-    if (volume && volume->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_render_volume_adaptive: the volume was created on another device than the scene");
-    if (!(M.sigma_t > 0.0f))
+    if ((st = fog_scene(what, sc, X)) != RT_OK) return st;
+    if (!(X.M.sigma_t > 0.0f))
         return rt_render_lit_adaptive_prior(sc, cam_open, lit, params, stop, shard, sample_first, d_fb_sum, d_spp, d_moments, hip_stream, sync, timing, d_prior);
+    const LitSetup &S = X.S;
     return lit_adaptive_run(what, sc, cam_open, S, a, rule, d_prior, shard, sample_first, d_fb_sum, d_spp, d_moments, hip_stream, sync, timing, [&](auto run) {
-        return with_fog_lit(sc, S, M, volume, [&](const auto &T) { return run(lit_kernels_of(S.lens, T).frame, lit_kernels_of(S.lens, T).list, &T); });
+        return with_fog_light(sc, X, [&](const auto &T) { return run(lit_kernels_of(S.lens, T).frame, lit_kernels_of(S.lens, T).list, &T); });
     });
 }
 
 rt_status rt_trace_samples_volume(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium, const rt_volume *volume,
                                   int32_t n, const int32_t *ijs, float *radiance, int32_t *rays, int32_t *medium_events, uint32_t *final_seed,
                                   uint32_t *final_nee_seed, uint32_t *final_env_seed, uint32_t *final_medium_seed, int32_t *cells) {
-    const char *what = "rt_trace_samples_volume";
-    LitSetup S;
-    if (const rt_status st = lit_setup(what, cam_open, lit, S)) return st;
-    rtk::MediumDev M{};
-    if (const rt_status ms = medium_setup(what, medium, M)) return ms;
-    if (const rt_status vs = volume_setup(what, medium, M, volume)) return vs;
-    if (n < 0 ||
-        (n > 0 && (!ijs || !radiance || !rays || !medium_events || !final_seed || !final_nee_seed || !final_env_seed || !final_medium_seed || !cells)))
-        return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_volume: null argument");
-    rtk::KParams P;
-    rt_status st = fill_params(sc, cam_open, nullptr, P);
-    if (st != RT_OK) return st;
-    if ((st = check_device(sc)) != RT_OK) return st;
-    if (S.env && S.env->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_volume: the environment was created on another device than the scene");
-    if (volume && volume->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_volume: the volume was created on another device than the scene");
-    if (n == 0) return RT_OK;
-    if (!volume || !(M.sigma_t > 0.0f)) {          // no grid, or no medium: rt_trace_samples_medium's columns, no cell
-        if ((st = rt_trace_samples_medium(sc, cam_open, lit, medium, n, ijs, radiance, rays, medium_events, final_seed, final_nee_seed, final_env_seed,
-                                          final_medium_seed)) != RT_OK)
-            return st;
-        for (int32_t k = 0; k < n; ++k) cells[k] = 0;
-        return RT_OK;
-    }
-    return fog_probe(what, sc, cam_open, S, M, volume, P, n, ijs, radiance, rays, medium_events, final_seed, final_nee_seed, final_env_seed, final_medium_seed, cells);
+    FogSetup X;
+    if (const rt_status st = fog_setup(kFogProbe[kFogVolume], kFogVolume, cam_open, {lit, medium, volume}, X)) return st;
+    return fog_probe(X, sc, cam_open, lit, n, ijs, radiance, rays, final_seed, final_nee_seed, final_env_seed, {final_medium_seed, medium_events, cells, nullptr, nullptr});
 }
 
 // ---- rt_render_chroma / rt_trace_samples_chroma (rtp_amd.h, "chromatic extinction"): rt_render_volume with an extinction
 // per channel.  Equal tints (and no medium) are rt_render_volume itself at sigma_t * e; otherwise the kernels of rt_chroma.hip.inc.
-void rt_chroma_params_init(rt_chroma_params *p) {
-    if (!p) return;
-    std::memset(p, 0, sizeof(*p));
-    p->struct_bytes = (uint32_t)sizeof(*p);
-    p->tint[0] = p->tint[1] = p->tint[2] = 1.0f;
-}
-namespace {
-// The chroma call's setup.  grey: the call is rt_render_volume's with `handed` as its medium
-struct ChromaSetup {
-    LitSetup S;
-    rtk::MediumDev M{};
-    float sigma[3] = {0.0f, 0.0f, 0.0f};
-    bool grey = false;
-    rt_medium_params handed;
-};
-// rt_render_volume's parameter checks in its order, then the tint's: everything before the scene is looked at
-rt_status chroma_setup(const char *what, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium, const rt_volume *volume,
-                       const rt_chroma_params *chroma, ChromaSetup &X) {
-    const std::string w(what);
-    if (const rt_status st = lit_setup(what, cam_open, lit, X.S)) return st;
-    if (const rt_status st = medium_setup(what, medium, X.M)) return st;
-    if (const rt_status st = volume_setup(what, medium, X.M, volume)) return st;
-    rt_chroma_params cp;
-    rt_chroma_params_init(&cp);
-    if (const rt_status st = take_params(w, "rt_chroma_params", chroma, cp)) return st;
-    for (int k = 0; k < 3; ++k)
-        if (!(std::isfinite(cp.tint[k]) && cp.tint[k] >= 0.0f)) return fail(RT_ERR_INVALID_ARG, w + ": a tint channel is negative, NaN or infinite");
-    for (int k = 0; k < 3; ++k) {
-        X.sigma[k] = X.M.sigma_t * cp.tint[k];
-        if (!std::isfinite(X.sigma[k])) return fail(RT_ERR_INVALID_ARG, w + ": sigma_t * tint is not finite in a channel");
-    }
-    X.grey = (cp.tint[0] == cp.tint[1] && cp.tint[1] == cp.tint[2]) || !(X.M.sigma_t > 0.0f);
-    if (X.grey) {
-        rt_medium_params_init(&X.handed);
-        X.handed.region = X.M.region;
-        X.handed.sigma_t = X.sigma[0];
-        X.handed.g = X.M.g;
-        for (int k = 0; k < 3; ++k) {
-            X.handed.albedo[k] = X.M.albedo[k];
-            X.handed.a[k] = X.M.a[k];
-            X.handed.b[k] = X.M.b[k];
-        }
-    }
-    return RT_OK;
-}
-}  // namespace
-
 rt_status rt_render_chroma(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium, const rt_volume *volume,
                            const rt_chroma_params *chroma, const rt_shard *shard, int32_t sample_first, float *d_fb_sum, void *hip_stream, int32_t sync,
                            rt_timing *timing) {
-    ChromaSetup X;
-    if (const rt_status st = chroma_setup("rt_render_chroma", cam_open, lit, medium, volume, chroma, X)) return st;
-    if (!sc) return fail(RT_ERR_INVALID_ARG, "rt_render_chroma: null scene");
-    if (volume && volume->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_render_chroma: the volume was created on another device than the scene");
-    if (X.grey) return rt_render_volume(sc, cam_open, lit, &X.handed, volume, shard, sample_first, d_fb_sum, hip_stream, sync, timing);
-    const LitSetup &S = X.S;
-    auto with_light = [&](auto frame) {
-        return with_chroma_lit(sc, S, X.M, volume, X.sigma, [&](const auto &T) { return frame(lit_kernels_of(S.lens, T).frame, &T); });
-    };
-    return render_light_impl("rt_render_chroma", S.env ? &S.env->device : nullptr, with_light, sc, cam_open, shard, sample_first, d_fb_sum, hip_stream, sync, timing,
-                             &S.C);
+    FogSetup X;
+    if (const rt_status st = fog_setup(kFogFrame[kFogTint], kFogTint, cam_open, {lit, medium, volume, chroma}, X)) return st;
+    return fog_frame(X, sc, cam_open, shard, sample_first, d_fb_sum, hip_stream, sync, timing);
 }
 
 rt_status rt_trace_samples_chroma(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium, const rt_volume *volume,
                                   const rt_chroma_params *chroma, int32_t n, const int32_t *ijs, float *radiance, int32_t *rays, int32_t *medium_events,
                                   uint32_t *final_seed, uint32_t *final_nee_seed, uint32_t *final_env_seed, uint32_t *final_medium_seed, int32_t *cells) {
-    const char *what = "rt_trace_samples_chroma";
-    ChromaSetup X;
-    if (const rt_status st = chroma_setup(what, cam_open, lit, medium, volume, chroma, X)) return st;
-    if (n < 0 ||
-        (n > 0 && (!ijs || !radiance || !rays || !medium_events || !final_seed || !final_nee_seed || !final_env_seed || !final_medium_seed || !cells)))
-        return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_chroma: null argument");
-    if (X.grey)
-        return rt_trace_samples_volume(sc, cam_open, lit, &X.handed, volume, n, ijs, radiance, rays, medium_events, final_seed, final_nee_seed, final_env_seed,
-                                       final_medium_seed, cells);
-    rtk::KParams P;
-    rt_status st = fill_params(sc, cam_open, nullptr, P);
-    if (st != RT_OK) return st;
-    if ((st = check_device(sc)) != RT_OK) return st;
-    if (X.S.env && X.S.env->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_chroma: the environment was created on another device than the scene");
-    if (volume && volume->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_chroma: the volume was created on another device than the scene");
-    if (n == 0) return RT_OK;
-    return fog_probe(what, sc, cam_open, X.S, X.M, volume, P, n, ijs, radiance, rays, medium_events, final_seed, final_nee_seed, final_env_seed, final_medium_seed, cells,
-                     X.sigma);
+    FogSetup X;
+    if (const rt_status st = fog_setup(kFogProbe[kFogTint], kFogTint, cam_open, {lit, medium, volume, chroma}, X)) return st;
+    return fog_probe(X, sc, cam_open, lit, n, ijs, radiance, rays, final_seed, final_nee_seed, final_env_seed, {final_medium_seed, medium_events, cells, nullptr, nullptr});
 }
 
 // ---- rt_render_glow / rt_trace_samples_glow (rtp_amd.h, "emission in the medium"): rt_render_volume with a medium that
 // emits.  No glow (NULL, or radiance 0, 0, 0) is rt_render_volume itself; otherwise the kernels of rt_glow.hip.inc.
-void rt_glow_params_init(rt_glow_params *p) {
-    if (!p) return;
-    std::memset(p, 0, sizeof(*p));
-    p->struct_bytes = (uint32_t)sizeof(*p);
-}
-namespace {
-// The glow call's setup.  dark: the call is rt_render_volume's with the same arguments
-struct GlowSetup {
-    LitSetup S;
-    rtk::MediumDev M{};
-    GlowDev G{};          // (heat: glow_heat_of fills it once the scene has been looked at — the handles are not read before)
-    int32_t source = 0;
-    bool dark = false;
-};
-const float *glow_heat_of(const GlowSetup &X, const rt_volume *volume, const rt_volume *heat) {
-    return X.source == 0 ? nullptr : (X.source == 1 ? volume->rho : heat->rho);
-}
-// rt_render_volume's parameter checks in its order, then the glow's: everything before the scene is looked at
-rt_status glow_setup(const char *what, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium, const rt_volume *volume,
-                     const rt_glow_params *glow, const rt_volume *heat, GlowSetup &X) {
-    const std::string w(what);
-    if (const rt_status st = lit_setup(what, cam_open, lit, X.S)) return st;
-    if (const rt_status st = medium_setup(what, medium, X.M)) return st;
-    if (const rt_status st = volume_setup(what, medium, X.M, volume)) return st;
-    rt_glow_params gp;
-    rt_glow_params_init(&gp);
-    if (const rt_status st = take_params(w, "rt_glow_params", glow, gp)) return st;
-    if (gp.source < 0 || gp.source > 2) return fail(RT_ERR_INVALID_ARG, w + ": source must be 0, 1 or 2");
-    for (int k = 0; k < 3; ++k)
-        if (!(std::isfinite(gp.radiance[k]) && gp.radiance[k] >= 0.0f)) return fail(RT_ERR_INVALID_ARG, w + ": a radiance channel is negative, NaN or infinite");
-    X.dark = gp.radiance[0] == 0.0f && gp.radiance[1] == 0.0f && gp.radiance[2] == 0.0f;
-    if (!X.dark && !(X.M.sigma_t > 0.0f))
-        return fail(RT_ERR_INVALID_ARG, w + ": a glow needs a medium with sigma_t > 0 (the emission rides on the free flight: a glow without extinction has no kernel)");
-    if (gp.source != 0 && !volume) return fail(RT_ERR_INVALID_ARG, w + ": source 1 and 2 need a volume (the grid the emission follows)");
-    if (gp.source == 2 && !heat) return fail(RT_ERR_INVALID_ARG, w + ": source 2 needs a heat grid");
-    if (gp.source == 2 && (heat->nx != volume->nx || heat->ny != volume->ny || heat->nz != volume->nz))
-        return fail(RT_ERR_INVALID_ARG, w + ": the heat grid's dimensions differ from the volume's");
-    if (gp.source != 2 && heat) return fail(RT_ERR_INVALID_ARG, w + ": a heat grid is for source 2 only");
-    for (int k = 0; k < 3; ++k) X.G.radiance[k] = gp.radiance[k];
-    X.source = gp.source;
-    return RT_OK;
-}
-}  // namespace
-
 rt_status rt_render_glow(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium, const rt_volume *volume,
                          const rt_glow_params *glow, const rt_volume *heat, const rt_shard *shard, int32_t sample_first, float *d_fb_sum, void *hip_stream,
                          int32_t sync, rt_timing *timing) {
-    GlowSetup X;
-    if (const rt_status st = glow_setup("rt_render_glow", cam_open, lit, medium, volume, glow, heat, X)) return st;
-    if (!sc) return fail(RT_ERR_INVALID_ARG, "rt_render_glow: null scene");
-    if (volume && volume->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_render_glow: the volume was created on another device than the scene");
-    if (heat && heat->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_render_glow: the heat grid was created on another device than the scene");
-    if (X.dark) return rt_render_volume(sc, cam_open, lit, medium, volume, shard, sample_first, d_fb_sum, hip_stream, sync, timing);
-    X.G.heat = glow_heat_of(X, volume, heat);
-    const LitSetup &S = X.S;
-    auto with_light = [&](auto frame) {
-        return with_glow_lit(sc, S, X.M, volume, X.G, [&](const auto &T) { return frame(lit_kernels_of(S.lens, T).frame, &T); });
-    };
-    return render_light_impl("rt_render_glow", S.env ? &S.env->device : nullptr, with_light, sc, cam_open, shard, sample_first, d_fb_sum, hip_stream, sync, timing,
-                             &S.C);
+    FogSetup X;
+    if (const rt_status st = fog_setup(kFogFrame[kFogGlow], kFogGlow, cam_open, {lit, medium, volume, nullptr, glow, heat}, X)) return st;
+    return fog_frame(X, sc, cam_open, shard, sample_first, d_fb_sum, hip_stream, sync, timing);
 }
 
 rt_status rt_trace_samples_glow(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium, const rt_volume *volume,
                                 const rt_glow_params *glow, const rt_volume *heat, int32_t n, const int32_t *ijs, float *radiance, int32_t *rays,
                                 int32_t *medium_events, uint32_t *final_seed, uint32_t *final_nee_seed, uint32_t *final_env_seed, uint32_t *final_medium_seed,
                                 int32_t *cells, float *glow_length) {
-    const char *what = "rt_trace_samples_glow";
-    GlowSetup X;
-    if (const rt_status st = glow_setup(what, cam_open, lit, medium, volume, glow, heat, X)) return st;
-    if (n < 0 || (n > 0 && (!ijs || !radiance || !rays || !medium_events || !final_seed || !final_nee_seed || !final_env_seed || !final_medium_seed || !cells ||
-                            !glow_length)))
-        return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_glow: null argument");
-    if (!sc) return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_glow: null scene");
-    if (volume && volume->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_glow: the volume was created on another device than the scene");
-    if (heat && heat->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_glow: the heat grid was created on another device than the scene");
-    if (X.dark) {
-        const rt_status st = rt_trace_samples_volume(sc, cam_open, lit, medium, volume, n, ijs, radiance, rays, medium_events, final_seed, final_nee_seed,
-                                                     final_env_seed, final_medium_seed, cells);
-        if (st == RT_OK)
-            for (int32_t k = 0; k < n; ++k) glow_length[k] = 0.0f;
-        return st;
-    }
-    rtk::KParams P;
-    rt_status st = fill_params(sc, cam_open, nullptr, P);
-    if (st != RT_OK) return st;
-    if ((st = check_device(sc)) != RT_OK) return st;
-    if (X.S.env && X.S.env->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_glow: the environment was created on another device than the scene");
-    if (n == 0) return RT_OK;
-    X.G.heat = glow_heat_of(X, volume, heat);
-    return fog_probe(what, sc, cam_open, X.S, X.M, volume, P, n, ijs, radiance, rays, medium_events, final_seed, final_nee_seed, final_env_seed, final_medium_seed, cells,
-                     nullptr, &X.G, glow_length);
+    FogSetup X;
+    if (const rt_status st = fog_setup(kFogProbe[kFogGlow], kFogGlow, cam_open, {lit, medium, volume, nullptr, glow, heat}, X)) return st;
+    return fog_probe(X, sc, cam_open, lit, n, ijs, radiance, rays, final_seed, final_nee_seed, final_env_seed, {final_medium_seed, medium_events, cells, glow_length, nullptr});
 }
 
 // ---- rt_glow_sampler / rt_render_glow_sampled / rt_trace_samples_glow_sampled (rtp_amd.h, "light samples of the glow"):
 // rt_render_glow over a grid with the glow as a third light.  No sample (NULL, sample == 0), an empty sampler or no glow is rt_render_glow
 // itself; otherwise the kernels of rt_glow_sample.hip.inc.
-void rt_glow_sample_params_init(rt_glow_sample_params *p) {
-    if (!p) return;
-    std::memset(p, 0, sizeof(*p));
-    p->struct_bytes = (uint32_t)sizeof(*p);
-    p->mis = 1;
-}
-
-struct rt_glow_sampler {
-    int device = 0;
-    int32_t source = 0, nx = 0, ny = 0, nz = 0;
-    const rt_volume *volume = nullptr, *heat = nullptr;          // what it was built from (compared, never read again)
-    bool empty = false;
-    float *slab_cdf = nullptr, *row_cdf = nullptr, *cell_cdf = nullptr, *pc = nullptr;
-};
-
 rt_status rt_glow_sampler_create(const rt_volume *volume, int32_t source, const rt_volume *heat, rt_glow_sampler **out_sampler) {
     if (!volume || !out_sampler) return fail(RT_ERR_INVALID_ARG, "rt_glow_sampler_create: null argument");
     *out_sampler = nullptr;
@@ -4010,58 +3965,12 @@ rt_status rt_glow_sampler_table(const rt_glow_sampler *sampler, int32_t z, int32
     return RT_OK;
 }
 
-namespace {
-// The sampled call's setup: rt_render_glow's parameter checks, then the sample's — everything before the scene is looked at.
-// sampled == false: the call is rt_render_glow's with the same arguments (as far as the parameters say: an empty sampler and no glow are
-// found by the caller, behind the devices' checks)
-struct GlowSampleSetup {
-    GlowSetup X;
-    rtk::GlowSamplerDev Q{};
-    bool sampled = false;
-};
-rt_status glow_sample_setup(const char *what, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium, const rt_volume *volume,
-                            const rt_glow_params *glow, const rt_volume *heat, const rt_glow_sample_params *sample, const rt_glow_sampler *sampler,
-                            GlowSampleSetup &Y) {
-    const std::string w(what);
-    if (const rt_status st = glow_setup(what, cam_open, lit, medium, volume, glow, heat, Y.X)) return st;
-    rt_glow_sample_params sp;
-    rt_glow_sample_params_init(&sp);
-    if (const rt_status st = take_params(w, "rt_glow_sample_params", sample, sp)) return st;
-    if (sp.sample != 0 && sp.sample != 1) return fail(RT_ERR_INVALID_ARG, w + ": sample must be 0 or 1");
-    if (sp.mis != 0 && sp.mis != 1) return fail(RT_ERR_INVALID_ARG, w + ": mis must be 0 or 1");
-    if (!sample || sp.sample == 0) return RT_OK;
-    if (!volume) return fail(RT_ERR_INVALID_ARG, w + ": light samples of the glow need a volume (a homogeneous box can pass a 1 x 1 x 1 grid of density 1)");
-    if (!sampler) return fail(RT_ERR_INVALID_ARG, w + ": sample = 1 needs a sampler (rt_glow_sampler_create)");
-    if (sampler->source != Y.X.source) return fail(RT_ERR_INVALID_ARG, w + ": the sampler was built for another source than the call's");
-    if (sampler->nx != volume->nx || sampler->ny != volume->ny || sampler->nz != volume->nz)
-        return fail(RT_ERR_INVALID_ARG, w + ": the sampler's dimensions differ from the volume's");
-    if (sampler->volume != volume || sampler->heat != heat) return fail(RT_ERR_INVALID_ARG, w + ": the sampler was built from other grids than the call's");
-    Y.Q = {sampler->slab_cdf, sampler->row_cdf, sampler->cell_cdf, sampler->pc, sp.mis};
-    Y.sampled = true;
-    return RT_OK;
-}
-}  // namespace
-
 rt_status rt_render_glow_sampled(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium, const rt_volume *volume,
                                  const rt_glow_params *glow, const rt_volume *heat, const rt_glow_sample_params *sample, const rt_glow_sampler *sampler,
                                  const rt_shard *shard, int32_t sample_first, float *d_fb_sum, void *hip_stream, int32_t sync, rt_timing *timing) {
-    const char *what = "rt_render_glow_sampled";
-    GlowSampleSetup Y;
-    if (const rt_status st = glow_sample_setup(what, cam_open, lit, medium, volume, glow, heat, sample, sampler, Y)) return st;
-    if (!sc) return fail(RT_ERR_INVALID_ARG, "rt_render_glow_sampled: null scene");
-    if (volume && volume->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_render_glow_sampled: the volume was created on another device than the scene");
-    if (heat && heat->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_render_glow_sampled: the heat grid was created on another device than the scene");
-    if (Y.sampled && sampler->device != sc->device)
-        return fail(RT_ERR_INVALID_ARG, "rt_render_glow_sampled: the sampler was created on another device than the scene");
-    GlowSetup &X = Y.X;
-    if (!Y.sampled || sampler->empty || X.dark)
-        return rt_render_glow(sc, cam_open, lit, medium, volume, glow, heat, shard, sample_first, d_fb_sum, hip_stream, sync, timing);
-    X.G.heat = glow_heat_of(X, volume, heat);
-    const LitSetup &S = X.S;
-    auto with_light = [&](auto frame) {
-        return with_glow_sample_lit(sc, S, X.M, volume, X.G, Y.Q, [&](const auto &T) { return frame(lit_kernels_of(S.lens, T).frame, &T); });
-    };
-    return render_light_impl(what, S.env ? &S.env->device : nullptr, with_light, sc, cam_open, shard, sample_first, d_fb_sum, hip_stream, sync, timing, &S.C);
+    FogSetup X;
+    if (const rt_status st = fog_setup(kFogFrame[kFogSample], kFogSample, cam_open, {lit, medium, volume, nullptr, glow, heat, sample, sampler}, X)) return st;
+    return fog_frame(X, sc, cam_open, shard, sample_first, d_fb_sum, hip_stream, sync, timing);
 }
 
 rt_status rt_trace_samples_glow_sampled(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium,
@@ -4069,35 +3978,10 @@ rt_status rt_trace_samples_glow_sampled(rt_scene *sc, const rt_camera_data *cam_
                                         const rt_glow_sampler *sampler, int32_t n, const int32_t *ijs, float *radiance, int32_t *rays, int32_t *medium_events,
                                         uint32_t *final_seed, uint32_t *final_nee_seed, uint32_t *final_env_seed, uint32_t *final_medium_seed, int32_t *cells,
                                         float *glow_length, int32_t *glow_samples) {
-    const char *what = "rt_trace_samples_glow_sampled";
-    GlowSampleSetup Y;
-    if (const rt_status st = glow_sample_setup(what, cam_open, lit, medium, volume, glow, heat, sample, sampler, Y)) return st;
-    if (n < 0 || (n > 0 && (!ijs || !radiance || !rays || !medium_events || !final_seed || !final_nee_seed || !final_env_seed || !final_medium_seed || !cells ||
-                            !glow_length || !glow_samples)))
-        return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_glow_sampled: null argument");
-    if (!sc) return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_glow_sampled: null scene");
-    if (volume && volume->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_glow_sampled: the volume was created on another device than the scene");
-    if (heat && heat->device != sc->device) return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_glow_sampled: the heat grid was created on another device than the scene");
-    if (Y.sampled && sampler->device != sc->device)
-        return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_glow_sampled: the sampler was created on another device than the scene");
-    GlowSetup &X = Y.X;
-    if (!Y.sampled || sampler->empty || X.dark) {
-        const rt_status st = rt_trace_samples_glow(sc, cam_open, lit, medium, volume, glow, heat, n, ijs, radiance, rays, medium_events, final_seed, final_nee_seed,
-                                                   final_env_seed, final_medium_seed, cells, glow_length);
-        if (st == RT_OK)
-            for (int32_t k = 0; k < n; ++k) glow_samples[k] = 0;
-        return st;
-    }
-    rtk::KParams P;
-    rt_status st = fill_params(sc, cam_open, nullptr, P);
-    if (st != RT_OK) return st;
-    if ((st = check_device(sc)) != RT_OK) return st;
-    if (X.S.env && X.S.env->device != sc->device)
-        return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_glow_sampled: the environment was created on another device than the scene");
-    if (n == 0) return RT_OK;
-    X.G.heat = glow_heat_of(X, volume, heat);
-    return fog_probe(what, sc, cam_open, X.S, X.M, volume, P, n, ijs, radiance, rays, medium_events, final_seed, final_nee_seed, final_env_seed, final_medium_seed, cells,
-                     nullptr, &X.G, glow_length, &Y.Q, glow_samples);
+    FogSetup X;
+    if (const rt_status st = fog_setup(kFogProbe[kFogSample], kFogSample, cam_open, {lit, medium, volume, nullptr, glow, heat, sample, sampler}, X)) return st;
+    return fog_probe(X, sc, cam_open, lit, n, ijs, radiance, rays, final_seed, final_nee_seed, final_env_seed,
+                     {final_medium_seed, medium_events, cells, glow_length, glow_samples});
 }
 
 void rt_timing_init(rt_timing *t) {
