@@ -135,40 +135,51 @@ bool write_aov_file(const std::string &path, int32_t width, int32_t height, int3
 // Animation driver beyond the reference: frames dealt round-robin to num_devices GPUs, saver
 // arithmetic on the device, file output overlapped with the next frame.  Same files, byte for byte.
 void gpu_render_pipelined(const SceneParams &params, const rt_scene_desc &desc, int num_devices);
-// rtp_main --gpu --lens R:F / --motion-blur S: the orbit frame after frame on one GPU through rt_render_lens (shutter S: open at frame
-// n, closed at n + S; 0: no motion), saved with rt_tonemap; aov / denoise from rt_render_aov_lens
-// nee (rtp_main --nee): frames through rt_render_nee with these parameters instead (the lens and shutter then unused: a pinhole at frame n);
-// env (rtp_main --env): through rt_render_env with env_params, likewise;
-// lit (rtp_main --lit): through rt_render_lit with lit's emitters and environment, this lens and this shutter (lit->lens and
-// lit->cam_close are set per frame here), aov / denoise from rt_render_aov_lens;
-// noise (with lit; rtp_main --lit --noise-target): through rt_render_lit_adaptive and rt_tonemap_spp; denoise_adaptive (with noise;
-// rtp_main --denoise-adaptive): each frame also filtered by rt_denoise_spp with its counts and moments and rt_render_aov_lens AOVs at
-// noise->min_spp, written through rt_tonemap_spp to "<frame file>.denoised"; denoise_adaptive_temporal (with noise, a pinhole and a closed
-// shutter; rtp_main --denoise-adaptive-temporal): that file from rt_denoise_temporal_spp instead, the AOVs (first_prim included) from
-// rt_render_aov at noise->min_spp and the two histories swapped per frame; stop_history (with that; rtp_main --stop-history): those AOVs
-// first, rt_adaptive_prior on the previous frame's history, the frame through rt_render_lit_adaptive_prior; medium (rtp_main --fog): the
-// lit frames through rt_render_medium; volume (with medium; rtp_main --fog-grid): through rt_render_volume, this grid in the medium's box;
-// medium with noise (rtp_main --fog-noise-target): through rt_render_volume_adaptive (volume may be null) and rt_tonemap_spp;
-// fog_denoise (with medium; rtp_main --fog-denoise): each frame also filtered under rt_render_aov_volume's AOVs — by rt_denoise, or with
-// noise by rt_denoise_spp with the frame's counts and moments and AOVs at noise->min_spp — to "<frame file>.denoised";
-// chroma (with medium; rtp_main --fog-tint): the lit frames through rt_render_chroma, with or without the volume;
-// glow (with medium, without chroma; rtp_main --fog-glow): through rt_render_glow, with or without the volume, heat the grid of its source 2;
-// glow_sample (with glow and volume; rtp_main --fog-glow-sample): through rt_render_glow_sampled with the sampler of these grids
-void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const rt_lens_params &lens, float shutter, bool aov, bool denoise,
-                     const rt_nee_params *nee = nullptr, const rt_env *env = nullptr, const rt_env_params *env_params = nullptr,
-                     const rt_lit_params *lit = nullptr, const rt_adaptive_params *noise = nullptr, bool denoise_adaptive = false,
-                     const rt_stop_params *stop = nullptr, bool denoise_adaptive_temporal = false, const rt_medium_params *medium = nullptr,
-                     bool stop_history = false, const rt_volume *volume = nullptr, bool fog_denoise = false, const rt_chroma_params *chroma = nullptr,
-                     const rt_glow_params *glow = nullptr, const rt_volume *heat = nullptr, const rt_glow_sample_params *glow_sample = nullptr,
-                     const rt_glow_sampler *sampler = nullptr);
-// rtp_main --gpu --adaptive: the orbit frame after frame on one GPU, each frame through rt_render_adaptive and rt_tonemap_spp;
-// denoise_adaptive (rtp_main --denoise-adaptive): each frame also filtered by rt_denoise_spp with its counts and moments and
-// rt_render_aov AOVs at ap.min_spp, written through rt_tonemap_spp to "<frame file>.denoised"; denoise_adaptive_temporal (rtp_main
-// --denoise-adaptive-temporal): that file from rt_denoise_temporal_spp instead, the history carried from frame to frame; stop_history
-// (with that; rtp_main --stop-history): the AOVs first, rt_adaptive_prior on the previous frame's history, the frame through
-// rt_render_adaptive_prior
-void gpu_render_adaptive(const SceneParams &params, const rt_scene_desc &desc, const rt_adaptive_params &ap, bool denoise_adaptive = false,
-                         const rt_stop_params *stop = nullptr, bool denoise_adaptive_temporal = false, bool stop_history = false);
+// What gpu_render_lens and gpu_render_adaptive render, member by member (rtp_main fills one from its command line).  The
+// pointers are borrowed for the call; a null pointer or a false flag is that feature off.
+struct FrameJob {
+    const rt_lens_params *lens = nullptr;          // rtp_main --lens R:F: the thin lens; null: rt_lens_params_init's pinhole
+    float shutter = 0.0f;                          // --motion-blur S: open at frame n, closed at n + S; 0: no motion
+    bool aov = false;                              // --aov: each frame's first-hit AOVs to "<frame file>.aov" (from rt_render_aov_lens)
+    bool denoise = false;                          // --denoise: each frame also filtered by rt_denoise to "<frame file>.denoised"
+    const rt_nee_params *nee = nullptr;            // --nee: frames through rt_render_nee (the lens and shutter then unused: a pinhole at frame n)
+    const rt_env *env = nullptr;                   // --env: through rt_render_env with env_params, likewise
+    const rt_env_params *env_params = nullptr;
+    // --lit: through rt_render_lit with lit's emitters and environment, this lens and this shutter (lit->lens and lit->cam_close are set
+    // per frame by the driver), aov / denoise from rt_render_aov_lens
+    const rt_lit_params *lit = nullptr;
+    // with lit, --lit --noise-target: through rt_render_lit_adaptive and rt_tonemap_spp.  gpu_render_adaptive (--adaptive T): its
+    // parameters, never null there
+    const rt_adaptive_params *noise = nullptr;
+    // with noise, --denoise-adaptive: each frame also filtered by rt_denoise_spp with its counts and moments and AOVs at noise->min_spp
+    // (rt_render_aov_lens; gpu_render_adaptive: rt_render_aov), written through rt_tonemap_spp to "<frame file>.denoised"
+    bool denoise_adaptive = false;
+    const rt_stop_params *stop = nullptr;          // --stop-rule: the stopping rule of the adaptive frames; null: the pixel's own error
+    // with noise, a pinhole and a closed shutter, --denoise-adaptive-temporal: that file from rt_denoise_temporal_spp instead, the AOVs
+    // (first_prim included) from rt_render_aov at noise->min_spp and the two histories swapped per frame
+    bool denoise_adaptive_temporal = false;
+    const rt_medium_params *medium = nullptr;      // --fog: the lit frames through rt_render_medium
+    // with denoise_adaptive_temporal, --stop-history: those AOVs first, rt_adaptive_prior on the previous frame's history, the frame
+    // through rt_render_lit_adaptive_prior (gpu_render_adaptive: rt_render_adaptive_prior)
+    bool stop_history = false;
+    // with medium, --fog-grid: through rt_render_volume, this grid in the medium's box; medium with noise (--fog-noise-target): through
+    // rt_render_volume_adaptive (volume may be null) and rt_tonemap_spp
+    const rt_volume *volume = nullptr;
+    // with medium, --fog-denoise: each frame also filtered under rt_render_aov_volume's AOVs — by rt_denoise, or with noise by
+    // rt_denoise_spp with the frame's counts and moments and AOVs at noise->min_spp — to "<frame file>.denoised"
+    bool fog_denoise = false;
+    const rt_chroma_params *chroma = nullptr;      // with medium, --fog-tint: the lit frames through rt_render_chroma, with or without the volume
+    const rt_glow_params *glow = nullptr;          // with medium, without chroma, --fog-glow: through rt_render_glow, with or without the volume
+    const rt_volume *heat = nullptr;               // the grid of glow's source 2 (--fog-heat)
+    const rt_glow_sample_params *glow_sample = nullptr;          // with glow and volume, --fog-glow-sample: through rt_render_glow_sampled …
+    const rt_glow_sampler *sampler = nullptr;                    // … with the sampler of these grids
+};
+// rtp_main --gpu --lens R:F / --motion-blur S / --nee / --env / --lit: the orbit frame after frame on one GPU through the render call the
+// job's members pick (rt_render_lens when none does), saved with rt_tonemap
+void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const FrameJob &job);
+// rtp_main --gpu --adaptive: the orbit frame after frame on one GPU, each frame through rt_render_adaptive and rt_tonemap_spp.  Reads
+// job.noise, denoise_adaptive, stop, denoise_adaptive_temporal and stop_history
+void gpu_render_adaptive(const SceneParams &params, const rt_scene_desc &desc, const FrameJob &job);
 
 // … and the other split: every frame sharded in row bands over num_devices GPUs (<= 0: all) with one RCCL gather per
 // frame (rt_context, rt_render_sharded).  Same files, byte for byte.

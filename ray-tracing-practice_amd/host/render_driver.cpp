@@ -344,13 +344,19 @@ void gpu_render_pipelined(const SceneParams &params, const rt_scene_desc &desc, 
 // fog_denoise (with medium; rtp_main --fog-denoise): denoise — or with noise denoise_adaptive — with the AOVs from
 // rt_render_aov_volume under the frame's own lit, medium and volume.
 // denoise_adaptive (with noise; rtp_main --denoise-adaptive): as in gpu_render_adaptive, the AOVs from rt_render_aov_lens at noise->min_spp
-void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const rt_lens_params &lens, float shutter, bool aov, bool denoise,
-                     const rt_nee_params *nee, const rt_env *env, const rt_env_params *env_params, const rt_lit_params *lit,
-                     const rt_adaptive_params *noise, bool denoise_adaptive, const rt_stop_params *stop, bool denoise_adaptive_temporal,
-                     const rt_medium_params *medium, bool stop_history, const rt_volume *volume, bool fog_denoise, const rt_chroma_params *chroma,
-                     const rt_glow_params *glow, const rt_volume *heat, const rt_glow_sample_params *glow_sample, const rt_glow_sampler *sampler) {
-    if (fog_denoise && noise) denoise_adaptive = true;
-    else if (fog_denoise) denoise = true;
+void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const FrameJob &job) {
+    rt_lens_params pinhole;
+    rt_lens_params_init(&pinhole);
+    const rt_lens_params &lens = job.lens ? *job.lens : pinhole;
+    const float shutter = job.shutter;
+    const bool aov = job.aov, fog_denoise = job.fog_denoise, denoise_adaptive_temporal = job.denoise_adaptive_temporal;
+    const rt_nee_params *nee = job.nee;
+    const rt_env *env = job.env;
+    const rt_lit_params *lit = job.lit;
+    const rt_adaptive_params *noise = job.noise;
+    const rt_medium_params *medium = job.medium;
+    const rt_volume *volume = job.volume;
+    const bool denoise = job.denoise || (fog_denoise && !noise), denoise_adaptive = job.denoise_adaptive || (fog_denoise && noise);
     rt_scene *scene = nullptr;
     RTP_CHECK(rt_scene_create(&desc, &scene));
     const size_t num_pixels = static_cast<size_t>(params.width) * params.height;
@@ -368,7 +374,7 @@ void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const
     }
     std::unique_ptr<AdaptiveDenoiser> spp_denoiser;
     if (lit && noise && (denoise_adaptive || denoise_adaptive_temporal))
-        spp_denoiser = std::make_unique<AdaptiveDenoiser>(params.width, params.height, denoise_adaptive_temporal, stop_history);
+        spp_denoiser = std::make_unique<AdaptiveDenoiser>(params.width, params.height, denoise_adaptive_temporal, job.stop_history);
     const bool with_prior = spp_denoiser && spp_denoiser->d_prior;
     rt_aov_buffers aov_bufs;
     rt_aov_buffers_init(&aov_bufs);
@@ -395,6 +401,12 @@ void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const
         camera.background_color = Vec3(0, 0, 0);
         return camera.build_camera_data();
     };
+    auto frame_lit = [&](const rt_camera_data *cam_close) {          // the job's lit call with this frame's lens and closing camera
+        rt_lit_params l = *lit;
+        l.cam_close = cam_close;
+        l.lens = &lens;
+        return l;
+    };
     PendingFile file;
     file.width = params.width;
     file.height = params.height;
@@ -407,37 +419,31 @@ void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const
         const auto t0 = std::chrono::steady_clock::now();
         long long total_rays = static_cast<long long>(params.width) * params.height * params.sqrt_spp * params.sqrt_spp;
         if (lit && noise && with_prior) {          // (a pinhole, no shutter) the first hits at min_spp, the prior, the frame
-            rt_lit_params frame_lit = *lit;
-            frame_lit.cam_close = cam_close;
-            frame_lit.lens = &lens;
+            const rt_lit_params lit_now = frame_lit(cam_close);
             rt_camera_data aov_cam = cam;
             aov_cam.samples_per_pixel = noise->min_spp;
             RTP_CHECK(rt_render_aov(scene, &aov_cam, nullptr, &spp_denoiser->aov, nullptr, 1, nullptr));
             spp_denoiser->make_prior(noise->min_spp, cam);
-            RTP_CHECK(rt_render_lit_adaptive_prior(scene, &cam, &frame_lit, noise, stop, nullptr, 0, d_fb, d_spp, spp_denoiser->d_moments, nullptr, 1, nullptr,
+            RTP_CHECK(rt_render_lit_adaptive_prior(scene, &cam, &lit_now, noise, job.stop, nullptr, 0, d_fb, d_spp, spp_denoiser->d_moments, nullptr, 1, nullptr,
                                                    spp_denoiser->d_prior));
         } else if (lit && noise) {
-            rt_lit_params frame_lit = *lit;
-            frame_lit.cam_close = cam_close;
-            frame_lit.lens = &lens;
+            const rt_lit_params lit_now = frame_lit(cam_close);
             if (medium)          // (rtp_main --fog-noise-target: no stop rule, no prior; the moments for --fog-denoise)
-                RTP_CHECK(rt_render_volume_adaptive(scene, &cam, &frame_lit, medium, volume, noise, nullptr, nullptr, nullptr, 0, d_fb, d_spp,
+                RTP_CHECK(rt_render_volume_adaptive(scene, &cam, &lit_now, medium, volume, noise, nullptr, nullptr, nullptr, 0, d_fb, d_spp,
                                                     spp_denoiser ? spp_denoiser->d_moments : nullptr, nullptr, 1, nullptr));
             else
-                RTP_CHECK(rt_render_lit_adaptive_rule(scene, &cam, &frame_lit, noise, stop, nullptr, 0, d_fb, d_spp,
+                RTP_CHECK(rt_render_lit_adaptive_rule(scene, &cam, &lit_now, noise, job.stop, nullptr, 0, d_fb, d_spp,
                                                       spp_denoiser ? spp_denoiser->d_moments : nullptr, nullptr, 1, nullptr));
         } else if (lit) {
-            rt_lit_params frame_lit = *lit;
-            frame_lit.cam_close = cam_close;
-            frame_lit.lens = &lens;
-            if (medium && chroma) RTP_CHECK(rt_render_chroma(scene, &cam, &frame_lit, medium, volume, chroma, nullptr, 0, d_fb, nullptr, 1, nullptr));
-            else if (medium && glow && glow_sample)
-                RTP_CHECK(rt_render_glow_sampled(scene, &cam, &frame_lit, medium, volume, glow, heat, glow_sample, sampler, nullptr, 0, d_fb, nullptr, 1, nullptr));
-            else if (medium && glow) RTP_CHECK(rt_render_glow(scene, &cam, &frame_lit, medium, volume, glow, heat, nullptr, 0, d_fb, nullptr, 1, nullptr));
-            else if (medium && volume) RTP_CHECK(rt_render_volume(scene, &cam, &frame_lit, medium, volume, nullptr, 0, d_fb, nullptr, 1, nullptr));
-            else if (medium) RTP_CHECK(rt_render_medium(scene, &cam, &frame_lit, medium, nullptr, 0, d_fb, nullptr, 1, nullptr));
-            else RTP_CHECK(rt_render_lit(scene, &cam, &frame_lit, nullptr, 0, d_fb, nullptr, 1, nullptr));
-        } else if (env) RTP_CHECK(rt_render_env(scene, &cam, env, env_params, nullptr, 0, d_fb, nullptr, 1, nullptr));
+            const rt_lit_params lit_now = frame_lit(cam_close);
+            if (medium && job.chroma) RTP_CHECK(rt_render_chroma(scene, &cam, &lit_now, medium, volume, job.chroma, nullptr, 0, d_fb, nullptr, 1, nullptr));
+            else if (medium && job.glow && job.glow_sample)
+                RTP_CHECK(rt_render_glow_sampled(scene, &cam, &lit_now, medium, volume, job.glow, job.heat, job.glow_sample, job.sampler, nullptr, 0, d_fb, nullptr, 1, nullptr));
+            else if (medium && job.glow) RTP_CHECK(rt_render_glow(scene, &cam, &lit_now, medium, volume, job.glow, job.heat, nullptr, 0, d_fb, nullptr, 1, nullptr));
+            else if (medium && volume) RTP_CHECK(rt_render_volume(scene, &cam, &lit_now, medium, volume, nullptr, 0, d_fb, nullptr, 1, nullptr));
+            else if (medium) RTP_CHECK(rt_render_medium(scene, &cam, &lit_now, medium, nullptr, 0, d_fb, nullptr, 1, nullptr));
+            else RTP_CHECK(rt_render_lit(scene, &cam, &lit_now, nullptr, 0, d_fb, nullptr, 1, nullptr));
+        } else if (env) RTP_CHECK(rt_render_env(scene, &cam, env, job.env_params, nullptr, 0, d_fb, nullptr, 1, nullptr));
         else if (nee) RTP_CHECK(rt_render_nee(scene, &cam, nee, nullptr, 0, d_fb, nullptr, 1, nullptr));
         else RTP_CHECK(rt_render_lens(scene, &cam, cam_close, &lens, nullptr, 0, d_fb, nullptr, 1, nullptr));
         if (d_spp) {
@@ -459,10 +465,8 @@ void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const
             aov_open.samples_per_pixel = aov_close.samples_per_pixel = noise->min_spp;
             if (with_prior) {          // (rendered before the frame)
             } else if (fog_denoise) {
-                rt_lit_params frame_lit = *lit;
-                frame_lit.cam_close = cam_close ? &aov_close : nullptr;
-                frame_lit.lens = &lens;
-                RTP_CHECK(rt_render_aov_volume(scene, &aov_open, &frame_lit, medium, volume, nullptr, 0, &spp_denoiser->aov, nullptr, nullptr, 1, nullptr));
+                const rt_lit_params lit_now = frame_lit(cam_close ? &aov_close : nullptr);
+                RTP_CHECK(rt_render_aov_volume(scene, &aov_open, &lit_now, medium, volume, nullptr, 0, &spp_denoiser->aov, nullptr, nullptr, 1, nullptr));
             } else if (spp_denoiser->temporal) {
                 RTP_CHECK(rt_render_aov(scene, &aov_open, nullptr, &spp_denoiser->aov, nullptr, 1, nullptr));       // (a pinhole, no shutter)
             } else {
@@ -473,10 +477,8 @@ void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const
         if (aov || denoise) {          // (outside the frame's timed span, as in gpu_render)
             if (!lit && (nee || env)) RTP_CHECK(rt_render_aov_samples(scene, &cam, nullptr, 0, &aov_bufs, nullptr, 1, nullptr));
             else if (fog_denoise) {
-                rt_lit_params frame_lit = *lit;
-                frame_lit.cam_close = cam_close;
-                frame_lit.lens = &lens;
-                RTP_CHECK(rt_render_aov_volume(scene, &cam, &frame_lit, medium, volume, nullptr, 0, &aov_bufs, nullptr, nullptr, 1, nullptr));
+                const rt_lit_params lit_now = frame_lit(cam_close);
+                RTP_CHECK(rt_render_aov_volume(scene, &cam, &lit_now, medium, volume, nullptr, 0, &aov_bufs, nullptr, nullptr, 1, nullptr));
             } else RTP_CHECK(rt_render_aov_lens(scene, &cam, cam_close, &lens, nullptr, 0, &aov_bufs, nullptr, 1, nullptr));
             if (aov) {
                 h_albedo.resize(num_pixels * 3); h_normal.resize(num_pixels * 3); h_depth.resize(num_pixels); h_hits.resize(num_pixels);
@@ -518,8 +520,9 @@ void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const
 // the frame took.  denoise_adaptive (rtp_main --denoise-adaptive): the frame's moments are kept, its AOVs rendered at
 // min_spp, and rt_denoise_spp's output goes through rt_tonemap_spp to "<frame file>.denoised".  denoise_adaptive_temporal (rtp_main
 // --denoise-adaptive-temporal): the same with rt_denoise_temporal_spp and its history from the frame before.
-void gpu_render_adaptive(const SceneParams &params, const rt_scene_desc &desc, const rt_adaptive_params &ap, bool denoise_adaptive,
-                         const rt_stop_params *stop, bool denoise_adaptive_temporal, bool stop_history) {
+void gpu_render_adaptive(const SceneParams &params, const rt_scene_desc &desc, const FrameJob &job) {
+    const rt_adaptive_params &ap = *job.noise;
+    const rt_stop_params *stop = job.stop;
     rt_scene *scene = nullptr;
     RTP_CHECK(rt_scene_create(&desc, &scene));
     const size_t num_pixels = static_cast<size_t>(params.width) * params.height;
@@ -531,8 +534,8 @@ void gpu_render_adaptive(const SceneParams &params, const rt_scene_desc &desc, c
     RTP_CHECK(rt_device_alloc(num_pixels * 3, reinterpret_cast<void **>(&d_rgb)));
     std::vector<int32_t> spp(num_pixels);
     std::unique_ptr<AdaptiveDenoiser> spp_denoiser;
-    if (denoise_adaptive || denoise_adaptive_temporal)
-        spp_denoiser = std::make_unique<AdaptiveDenoiser>(params.width, params.height, denoise_adaptive_temporal, stop_history);
+    if (job.denoise_adaptive || job.denoise_adaptive_temporal)
+        spp_denoiser = std::make_unique<AdaptiveDenoiser>(params.width, params.height, job.denoise_adaptive_temporal, job.stop_history);
     const bool with_prior = spp_denoiser && spp_denoiser->d_prior;
     for (int n = 0; n < params.num_frames; ++n) {
         Vec3 eye, target;
