@@ -4144,6 +4144,182 @@ rt_status rt_debug_read_stats(rt_scene *sc, uint32_t out[16]) {
     return RT_OK;
 }
 
+// Developer hook (not part of the ABI header): the fog family's ray routines on the caller's rays, one ray per lane, for the ray-by-ray
+// check against the CPU restatements (tests/dev_fog_ray_checks.py, tests/fog_ray_cases.py).  The kernel calls the inline
+// functions the render kernels call — medium_interval, volume_walk, chroma_flight / chroma_tr, glow_flight, glow_pl, glow_line — on lights
+// whose emitter table is value-initialised (these routines never read it), and writes eight words per ray:
+//   0  medium_interval                                   hit, t0, t1
+//   1  volume_walk<false> as fog_tr uses it              hit, acc, cells, exp_libm(-acc)
+//   2  volume_walk<true> with rem = arg                  hit, event, v (the event's t, else the rem left over), cells
+//   3  chroma_flight to the target R = arg, chroma_tr    hit, event, t, A (R at an event, as fog_vertex holds it), cells, tr of the three sigma_k
+//   4  glow_flight of the draw u = arg                   hit, event, t, E, cells
+//   5  glow_pl                                           pl, cells
+//   6  glow_line                                         hit, G, cells
+// An empty interval writes hit = 0 and zeros, an absent event t = 0; the words a routine does not name are 0.
+namespace rtk {
+struct FogRays {
+    int32_t routine, n, grid;          // grid: 3 and 4 run on the VolumeLit base (else on the MediumLit one)
+    MediumDev M;
+    VolumeDev V;
+    const float *heat, *pc;
+    float s0, s1, s2;
+    const float *o, *d, *t_end, *arg;
+    uint32_t *out;
+};
+__global__ void __launch_bounds__(256) fog_rays_kernel(const FogRays A) {
+    using Table = NeeTable;
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= A.n) return;
+    const f3 o = mk(A.o[3 * g], A.o[3 * g + 1], A.o[3 * g + 2]), d = mk(A.d[3 * g], A.d[3 * g + 1], A.d[3 * g + 2]);
+    const float t_end = A.t_end[g], arg = A.arg[g];
+    uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    FogCount n;
+    float t0, t1;
+    if (A.routine == 5) {
+        w[0] = __float_as_uint(glow_pl(A.M, A.V, A.pc, o, d, n.cells));
+        w[1] = (uint32_t)n.cells;
+    } else if (A.routine == 6) {
+        float G;
+        if (glow_line(A.M, A.V, A.heat, o, d, t_end, G, n.cells)) {
+            w[0] = 1;
+            w[1] = __float_as_uint(G);
+            w[2] = (uint32_t)n.cells;
+        }
+    } else if (medium_interval(A.M, o, d, t_end, t0, t1)) {
+        w[0] = 1;
+        const float len = sqrt_cr(lensq(d));
+        if (A.routine == 0) {
+            w[1] = __float_as_uint(t0);
+            w[2] = __float_as_uint(t1);
+        } else if (A.routine == 1) {
+            float acc = 0.0f;
+            volume_walk<false>(A.M, A.V, o, d, t0, t1, len, acc, n.cells);
+            w[1] = __float_as_uint(acc);
+            w[2] = (uint32_t)n.cells;
+            w[3] = __float_as_uint(exp_libm(-acc));
+        } else if (A.routine == 2) {
+            float v = arg;
+            w[1] = volume_walk<true>(A.M, A.V, o, d, t0, t1, len, v, n.cells) ? 1 : 0;
+            w[2] = __float_as_uint(v);
+            w[3] = (uint32_t)n.cells;
+        } else if (A.routine == 3) {
+            float t = 0.0f, Ad = 0.0f;
+            bool event;
+            if (A.grid) {
+                VolumeLit<Table> B{};
+                B.M = A.M;
+                B.V = A.V;
+                event = chroma_flight(B, o, d, t0, t1, len, arg, t, Ad, n);
+            } else {
+                MediumLit<Table> B{};
+                B.M = A.M;
+                event = chroma_flight(B, o, d, t0, t1, len, arg, t, Ad, n);
+            }
+            if (event) Ad = arg;
+            w[1] = event ? 1 : 0;
+            w[2] = event ? __float_as_uint(t) : 0;
+            w[3] = __float_as_uint(Ad);
+            w[4] = (uint32_t)n.cells;
+            w[5] = __float_as_uint(chroma_tr(A.s0, Ad));
+            w[6] = __float_as_uint(chroma_tr(A.s1, Ad));
+            w[7] = __float_as_uint(chroma_tr(A.s2, Ad));
+        } else {
+            float t = 0.0f, E = 0.0f;
+            bool event;
+            if (A.grid) {
+                GlowLit<VolumeLit<Table>> T{};
+                T.B.M = A.M;
+                T.B.V = A.V;
+                T.heat = A.heat;
+                event = glow_flight(T, o, d, t0, t1, len, arg, t, E, n);
+            } else {
+                GlowLit<MediumLit<Table>> T{};
+                T.B.M = A.M;
+                event = glow_flight(T, o, d, t0, t1, len, arg, t, E, n);
+            }
+            w[1] = event ? 1 : 0;
+            w[2] = event ? __float_as_uint(t) : 0;
+            w[3] = __float_as_uint(E);
+            w[4] = (uint32_t)n.cells;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) A.out[8 * (size_t)g + k] = w[k];
+}
+}  // namespace rtk
+// rt_debug_fog_rays: routine 0 … 6 (above) over n rays (o, d: 3 floats each; t_end and arg: one each; all host arrays) → out, 8 words per
+// ray (a host array).  The medium, the grid, the heat (source 0: h = 1; 1: the density; 2: the heat grid, of the volume's dimensions) and
+// the sampler are the public objects, converted as the render calls convert them: medium_setup's checks, the extinctions sigma_t * tint[k]
+// over a base of sigma_t = 1 (routine 3), the cells' h by the source (4 and 6), the sampler's pc (5).  0 needs no grid; 1, 2, 5 and 6 need
+// one; 3 and 4 run on the grid's base with one and on the homogeneous base without
+rt_status rt_debug_fog_rays(int32_t routine, const rt_medium_params *medium, const rt_volume *volume, int32_t source, const rt_volume *heat,
+                            const rt_glow_sampler *sampler, const float *tint, int32_t n, const float *o, const float *d, const float *t_end, const float *arg,
+                            uint32_t *out) {
+    const std::string w("rt_debug_fog_rays");
+    if (routine < 0 || routine > 6) return fail(RT_ERR_INVALID_ARG, w + ": unknown routine " + std::to_string(routine));
+    if (n <= 0 || !o || !d || !t_end || !arg || !out) return fail(RT_ERR_INVALID_ARG, w + ": null argument or n <= 0");
+    rtk::FogRays A{};
+    if (const rt_status st = medium_setup("rt_debug_fog_rays", medium, A.M)) return st;
+    if (routine != 0 && !(A.M.sigma_t > 0.0f)) return fail(RT_ERR_INVALID_ARG, w + ": the routines behind the interval need sigma_t > 0");
+    const bool needs_grid = routine == 1 || routine == 2 || routine == 5 || routine == 6;
+    if (needs_grid && !volume) return fail(RT_ERR_INVALID_ARG, w + ": this routine needs a volume");
+    if (volume && !(medium && A.M.region == 2)) return fail(RT_ERR_INVALID_ARG, w + ": a volume needs a medium with region 2 (the box the grid fills)");
+    if (source < 0 || source > 2) return fail(RT_ERR_INVALID_ARG, w + ": source must be 0, 1 or 2");
+    if (source != 0 && !volume) return fail(RT_ERR_INVALID_ARG, w + ": source 1 and 2 need a volume");
+    if ((source == 2) != (heat != nullptr)) return fail(RT_ERR_INVALID_ARG, w + ": a heat grid is for source 2, and source 2 needs one");
+    if (heat && (heat->nx != volume->nx || heat->ny != volume->ny || heat->nz != volume->nz))
+        return fail(RT_ERR_INVALID_ARG, w + ": the heat grid's dimensions differ from the volume's");
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    if ((volume && volume->device != dev) || (heat && heat->device != dev) || (sampler && sampler->device != dev))
+        return fail(RT_ERR_INVALID_ARG, w + ": a handle was created on another device than the current one");
+    if (routine == 5) {
+        if (!sampler || sampler->empty || !sampler->pc) return fail(RT_ERR_INVALID_ARG, w + ": glow_pl needs a sampler that is not empty");
+        if (sampler->source != source || sampler->volume != volume || sampler->heat != heat)
+            return fail(RT_ERR_INVALID_ARG, w + ": the sampler was built for another source or from other grids than the call's");
+        A.pc = sampler->pc;
+    }
+    if (routine == 3) {
+        if (!tint) return fail(RT_ERR_INVALID_ARG, w + ": chroma_flight needs a tint");
+        float sigma[3];
+        for (int k = 0; k < 3; ++k) {
+            if (!(std::isfinite(tint[k]) && tint[k] >= 0.0f)) return fail(RT_ERR_INVALID_ARG, w + ": a tint channel is negative, NaN or infinite");
+            sigma[k] = A.M.sigma_t * tint[k];
+            if (!std::isfinite(sigma[k])) return fail(RT_ERR_INVALID_ARG, w + ": sigma_t * tint is not finite in a channel");
+        }
+        A.s0 = sigma[0];
+        A.s1 = sigma[1];
+        A.s2 = sigma[2];
+        A.M.sigma_t = 1.0f;
+    }
+    A.routine = routine;
+    A.n = n;
+    A.grid = volume ? 1 : 0;
+    if (volume) A.V = rtk::VolumeDev{volume->rho, volume->nx, volume->ny, volume->nz};
+    A.heat = source == 0 ? nullptr : (source == 1 ? volume->rho : heat->rho);
+    float *d_o = nullptr, *d_d = nullptr, *d_t = nullptr, *d_arg = nullptr;
+    uint32_t *d_out = nullptr;
+    Scratch mem;
+    const size_t n3 = (size_t)n * 12, n1 = (size_t)n * 4, n8 = (size_t)n * 32;
+    if (mem.alloc(d_o, n3) != hipSuccess || mem.alloc(d_d, n3) != hipSuccess || mem.alloc(d_t, n1) != hipSuccess || mem.alloc(d_arg, n1) != hipSuccess ||
+        mem.alloc(d_out, n8) != hipSuccess)
+        return fail(RT_ERR_OUT_OF_MEMORY, "hipMalloc failed");
+    HIP_TRY(hipMemcpy(d_o, o, n3, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_d, d, n3, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_t, t_end, n1, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_arg, arg, n1, hipMemcpyHostToDevice));
+    A.o = d_o;
+    A.d = d_d;
+    A.t_end = d_t;
+    A.arg = d_arg;
+    A.out = d_out;
+    hipLaunchKernelGGL(rtk::fog_rays_kernel, dim3((n + 255) / 256), dim3(256), 0, 0, A);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, d_out, n8, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
 #endif      // RTP_DEV_BUILD
 
 rt_status rt_last_kernel_ms(rt_scene *sc, float *ms) {

@@ -22,6 +22,8 @@ def lib():
     desc, cam, cfg = C.POINTER(rb.SceneDesc), C.POINTER(rb.CameraData), C.POINTER(ChromaCfg)
     l.chroma_weights.restype = None
     l.chroma_weights.argtypes = [C.c_int64] + [C.c_void_p] * 8
+    l.chroma_flights.restype = None
+    l.chroma_flights.argtypes = [C.POINTER(rb.MediumParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 10
     l.chroma_trace.restype = None
     l.chroma_trace.argtypes = [desc, cam, cfg, C.c_int64] + [C.c_void_p] * 7 + [C.c_int32]
     l.chroma_frame.restype = None
@@ -43,6 +45,25 @@ def weights(u, uc, A, sigma):
     event, w, den, trj = np.empty(m, np.int32), np.empty((m, 3), np.float32), np.empty(m, np.float32), np.empty(m, np.float32)
     lib().chroma_weights(m, u.ctypes.data, uc.ctypes.data, A.ctypes.data, sigma.ctypes.data, event.ctypes.data, w.ctypes.data, den.ctypes.data, trj.ctypes.data)
     return dict(event=event, w=w, den=den, trj=trj)
+
+
+def flights(medium, density, tint, o, d, t_end, R):
+    """chr_flight and chr_tr alone, as the vertex loop uses them, on rays (o, d) (m, 3) over [0, t_end] to the targets R (m,): the base
+    (density None: the homogeneous one) at sigma_t = 1, the channels' extinctions the float32 products sigma_t * tint[k] → dict: hit, event,
+    t (0 without an event), A (R at an event, else the interval's density length), cells, tr (m, 3)."""
+    import medium_reference as mr
+    m = mr.medium_struct(medium)
+    sigma = (np.float32(m.sigma_t) * tint_of(tint)).astype(np.float32)
+    g, n = vr.grid_of(density) if density is not None else (None, None)
+    o, d, t_end = vr._rays(o, d, t_end)
+    k = o.shape[0]
+    R = np.ascontiguousarray(np.broadcast_to(np.asarray(R, dtype=np.float32), (k,)))
+    hit, event, cells = (np.empty(k, np.int32) for _ in range(3))
+    t, A, tr = np.empty(k, np.float32), np.empty(k, np.float32), np.empty((k, 3), np.float32)
+    lib().chroma_flights(C.byref(m), g.ctypes.data if g is not None else None, n.ctypes.data if g is not None else None, sigma.ctypes.data, k, o.ctypes.data,
+                         d.ctypes.data, t_end.ctypes.data, R.ctypes.data, hit.ctypes.data, event.ctypes.data, t.ctypes.data, A.ctypes.data, cells.ctypes.data,
+                         tr.ctypes.data)
+    return dict(hit=hit, event=event, t=t, A=A, cells=cells, tr=tr)
 
 
 def _cfg(medium, density, tint, kw):

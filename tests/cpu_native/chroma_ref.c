@@ -392,6 +392,35 @@ void chroma_weights(int64_t count, const float *u, const float *uc, const float 
     }
 }
 
+/* chr_flight and chr_tr alone on count rays (o, d: 3 floats each) over [0, t_end] to the targets R, as the vertex loop uses them: the base
+ * (rho NULL: the homogeneous one; else the grid rho of n: nx, ny, nz, in the box of m) holds sigma_t = 1, sigma is the three channels'
+ * sigma_t * tint[k].  hit 1/0 (the interval), event 1/0, its t (0 without one), A (R at an event, the interval's density length otherwise),
+ * cells, and tr: chr_tr(sigma[k], A), 3 floats per ray.  An empty interval leaves zeros */
+void chroma_flights(const rt_medium_params *m, const float *rho, const int32_t *n, const float *sigma, int64_t count, const float *o, const float *d,
+                    const float *t_end, const float *R, int32_t *hit, int32_t *event, float *t, float *A, int32_t *cells, float *tr) {
+    volume_ctx Vc;
+    memset(&Vc, 0, sizeof(Vc));
+    Vc.Mc.m = *m;
+    Vc.Mc.m.sigma_t = 1.0f;
+    Vc.rho = rho;
+    for (int k = 0; k < 3; ++k) Vc.n[k] = rho ? n[k] : 0;
+    for (int64_t r = 0; r < count; ++r) {
+        const v3 oo = V(o[3 * r], o[3 * r + 1], o[3 * r + 2]), dd = V(d[3 * r], d[3 * r + 1], d[3 * r + 2]);
+        float t0, t1;
+        event[r] = cells[r] = 0;
+        t[r] = A[r] = tr[3 * r] = tr[3 * r + 1] = tr[3 * r + 2] = 0.0f;
+        hit[r] = med_interval(&Vc.Mc.m, oo, dd, t_end[r], &t0, &t1, NULL);
+        if (!hit[r]) continue;
+        const float len = sqrtf(dot(dd, dd));
+        float tt = 0.0f, AA = 0.0f;
+        event[r] = chr_flight(&Vc, oo, dd, t0, t1, len, R[r], &tt, &AA, &cells[r]);
+        if (event[r]) AA = R[r];
+        t[r] = event[r] ? tt : 0.0f;
+        A[r] = AA;
+        for (int k = 0; k < 3; ++k) tr[3 * r + k] = chr_tr(sigma[k], AA);
+    }
+}
+
 /* count samples (ijs: i, j, s) → volume_trace's columns */
 void chroma_trace(const rt_scene_desc *sc, const rt_camera_data *cam, const chroma_cfg *cfg, int64_t count, const int32_t *ijs, float *radiance, int32_t *rays,
                   int32_t *events, int32_t *ends, uint32_t *seeds4, int32_t *cells, int32_t linear) {

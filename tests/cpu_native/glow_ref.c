@@ -357,6 +357,32 @@ static void make_glow_ctx(const rt_scene_desc *sc, const rt_camera_data *cam, co
 }
 
 /* ---- what tests/glow_reference.py calls ---------------------------------------------------------------------------------------------- */
+/* glow_flight alone on count rays (o, d: 3 floats each) over [0, t_end] with the draws u: the base is the homogeneous one (rho NULL) or the
+ * grid rho of n (nx, ny, nz) in the box of m, h the cells' emission (NULL: 1).  hit 1/0 (the interval), event 1/0, its t (0 without one), E
+ * and cells.  An empty interval leaves zeros */
+void glow_flights(const rt_medium_params *m, const float *rho, const float *h, const int32_t *n, int64_t count, const float *o, const float *d, const float *t_end,
+                  const float *u, int32_t *hit, int32_t *event, float *t, float *E, int32_t *cells) {
+    glow_ctx Gc;
+    memset(&Gc, 0, sizeof(Gc));
+    Gc.V.Mc.m = *m;
+    Gc.V.rho = rho;
+    Gc.h = h;
+    for (int k = 0; k < 3; ++k) Gc.V.n[k] = rho ? n[k] : 0;
+    for (int64_t r = 0; r < count; ++r) {
+        const v3 oo = V(o[3 * r], o[3 * r + 1], o[3 * r + 2]), dd = V(d[3 * r], d[3 * r + 1], d[3 * r + 2]);
+        float t0, t1;
+        event[r] = cells[r] = 0;
+        t[r] = E[r] = 0.0f;
+        hit[r] = med_interval(m, oo, dd, t_end[r], &t0, &t1, NULL);
+        if (!hit[r]) continue;
+        const float len = sqrtf(dot(dd, dd));
+        float tt = 0.0f, EE = 0.0f;
+        event[r] = glow_flight(&Gc, oo, dd, t0, t1, len, u[r], &tt, &EE, &cells[r]);
+        t[r] = event[r] ? tt : 0.0f;
+        E[r] = EE;
+    }
+}
+
 /* count samples (ijs: i, j, s) → volume_trace's columns and glow_length per sample */
 void glow_trace(const rt_scene_desc *sc, const rt_camera_data *cam, const glow_cfg *cfg, int64_t count, const int32_t *ijs, float *radiance, int32_t *rays,
                 int32_t *events, int32_t *ends, uint32_t *seeds4, int32_t *cells, float *glow_length, int32_t linear) {

@@ -28,6 +28,12 @@ static float vol_plane(const rt_medium_params *m, const int32_t *n, int k, int32
     return m->a[k] + (float)i * w;
 }
 
+/* Tallies of one walk, a bit each (tests/volume_reference.py's TALLIES names them in this order).  They only count: vol_tally is NULL except
+ * inside volume_walks, which runs on one thread, and no value of the walk depends on them */
+enum { VT_TIE2, VT_TIE3, VT_CLAMP, VT_ENTRY_CLAMPED, VT_LEFT_T1, VT_LEFT_INDEX, VT_D_ZERO, VT_FL_EMPTY, VT_FL_FIRST, VT_FL_AFTER_EMPTY, VT_FL_NONE };
+static int32_t *vol_tally = NULL;
+#define VOL_TALLY(bit) do { if (vol_tally) *vol_tally |= 1 << (bit); } while (0)
+
 /* The walk of the header over the non-empty interval [t0, t1] of (o, d), len = |d|.  flight 1: *v is rem on entry; 1 = an event, *v its
  * parameter t.  flight 0: *v is acc (0 on entry), the result 0.  cells: the visited cells are added.  segs: NULL, or 3 doubles — the sum of
  * the segments (each a float, summed in double), the smallest segment, the number of cells of this walk */
@@ -39,10 +45,13 @@ static int vol_walk(const volume_ctx *Vc, int flight, v3 o, v3 d, float t0, floa
         const float w = (m->b[k] - m->a[k]) / (float)n[k];
         const float p = o.e[k] + t0 * d.e[k];
         c[k] = (int32_t)floorf((p - m->a[k]) / w);
+        if (c[k] < 0 || c[k] > n[k] - 1) VOL_TALLY(VT_ENTRY_CLAMPED);
+        if (d.e[k] == 0.0f) VOL_TALLY(VT_D_ZERO);
         if (c[k] < 0) c[k] = 0;
         if (c[k] > n[k] - 1) c[k] = n[k] - 1;
     }
     float ta = t0;
+    int first = 1, passed_empty = 0;          /* (for the tallies alone) */
     for (int32_t left = n[0] + n[1] + n[2]; left > 0; --left) {
         float tn[3];
         for (int k = 0; k < 3; ++k) {
@@ -60,7 +69,13 @@ static int vol_walk(const volume_ctx *Vc, int flight, v3 o, v3 d, float t0, floa
             tm = tn[2];
             axis = 2;
         }
+        if (vol_tally && tm < INFINITY) {
+            const int ties = (tn[0] == tm) + (tn[1] == tm) + (tn[2] == tm);
+            if (ties == 2) VOL_TALLY(VT_TIE2);
+            if (ties == 3) VOL_TALLY(VT_TIE3);
+        }
         float tb = tm < t1 ? tm : t1;
+        if (tb < ta) VOL_TALLY(VT_CLAMP);
         if (tb < ta) tb = ta;
         const float seg = (tb - ta) * len;
         const float sigma_c = m->sigma_t * Vc->rho[((size_t)c[2] * (size_t)n[1] + (size_t)c[1]) * (size_t)n[0] + (size_t)c[0]];
@@ -74,19 +89,28 @@ static int vol_walk(const volume_ctx *Vc, int flight, v3 o, v3 d, float t0, floa
             if (sigma_c > 0.0f) {
                 const float s = *v / sigma_c;
                 if (s < seg) {
+                    if (first) VOL_TALLY(VT_FL_FIRST);
+                    if (passed_empty) VOL_TALLY(VT_FL_AFTER_EMPTY);
                     *v = ta + s / len;
                     return 1;
                 }
                 *v = *v - sigma_c * seg;
+            } else {
+                VOL_TALLY(VT_FL_EMPTY);
+                passed_empty = 1;
             }
+            first = 0;
         } else {
             *v = *v + sigma_c * seg;
         }
+        if (tb >= t1) VOL_TALLY(VT_LEFT_T1);
         if (tb >= t1) break;
         c[axis] += d.e[axis] > 0.0f ? 1 : -1;
+        if (c[axis] < 0 || c[axis] >= n[axis]) VOL_TALLY(VT_LEFT_INDEX);
         if (c[axis] < 0 || c[axis] >= n[axis]) break;
         ta = tb;
     }
+    if (flight) VOL_TALLY(VT_FL_NONE);
     return 0;
 }
 
@@ -387,9 +411,11 @@ static void make_volume_ctx(const rt_scene_desc *sc, const rt_camera_data *cam, 
 /* The walk alone on count rays (o, d: 3 floats each) over [0, t_end] through the grid rho (n: nx, ny, nz) in the box of m: hit 1/0 (the
  * interval), acc = the optical depth (float32, the header's sum), cells, and per ray three doubles: the sum of the segments, the smallest
  * segment, (t1 - t0) * len as the walk's float32 computes it.  rem (may be NULL): per ray a remaining optical depth for a free flight over
- * the same interval → event 1/0 and its t (0 without an event) */
+ * the same interval → event 1/0, its t (0 without an event), rem_left, the rem the flight ended with (0 with an event), and the cells the
+ * flight visited.  tr: expf(-acc) as
+ * vol_attenuate takes it (0, like every column, where the interval is empty).  flags (may be NULL): per ray the tallies of its walks, a bit each (VT_*) */
 void volume_walks(const rt_medium_params *m, const float *rho, const int32_t *n, int64_t count, const float *o, const float *d, const float *t_end, int32_t *hit,
-                  float *acc, int32_t *cells, double *segs, const float *rem, int32_t *event, float *t_event) {
+                  float *acc, int32_t *cells, double *segs, const float *rem, int32_t *event, float *t_event, float *tr, float *rem_left, int32_t *flight_cells, int32_t *flags) {
     volume_ctx Vc;
     memset(&Vc, 0, sizeof(Vc));
     Vc.Mc.m = *m;
@@ -405,21 +431,28 @@ void volume_walks(const rt_medium_params *m, const float *rho, const int32_t *n,
         if (rem) {
             event[r] = 0;
             t_event[r] = 0.0f;
+            rem_left[r] = 0.0f;
+            flight_cells[r] = 0;
         }
+        tr[r] = 0.0f;
+        if (flags) flags[r] = 0;
         hit[r] = med_interval(m, oo, dd, t_end[r], &t0, &t1, NULL);
         if (!hit[r]) continue;
         const float len = sqrtf(dot(dd, dd));
         double sg[3] = {0.0, INFINITY, 0.0};
+        vol_tally = flags ? &flags[r] : NULL;
         vol_walk(&Vc, 0, oo, dd, t0, t1, len, &acc[r], &cells[r], sg);
+        tr[r] = expf(-acc[r]);
         segs[3 * r] = sg[0];
         segs[3 * r + 1] = sg[1];
         segs[3 * r + 2] = (double)((t1 - t0) * len);
         if (rem) {
             float v = rem[r];
-            int32_t unused = 0;
-            event[r] = vol_walk(&Vc, 1, oo, dd, t0, t1, len, &v, &unused, NULL);
+            event[r] = vol_walk(&Vc, 1, oo, dd, t0, t1, len, &v, &flight_cells[r], NULL);
             if (event[r]) t_event[r] = v;
+            else rem_left[r] = v;
         }
+        vol_tally = NULL;
     }
 }
 

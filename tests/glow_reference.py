@@ -20,6 +20,8 @@ class GlowCfg(C.Structure):
 def lib():
     l = cpu_ref.build("glow_ref.c")
     desc, cam, cfg = C.POINTER(rb.SceneDesc), C.POINTER(rb.CameraData), C.POINTER(GlowCfg)
+    l.glow_flights.restype = None
+    l.glow_flights.argtypes = [C.POINTER(rb.MediumParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 9
     l.glow_trace.restype = None
     l.glow_trace.argtypes = [desc, cam, cfg, C.c_int64] + [C.c_void_p] * 8 + [C.c_int32]
     l.glow_frame.restype = None
@@ -30,6 +32,24 @@ def lib():
 def radiance_of(radiance):
     """None → (0, 0, 0); one number or three → three float32."""
     return np.ascontiguousarray(np.broadcast_to(np.asarray(0.0 if radiance is None else radiance, dtype=np.float32), (3,)))
+
+
+def flights(medium, density, o, d, t_end, u, source=0, heat=None):
+    """glow_flight alone on rays (o, d) (m, 3) over [0, t_end] with the draws u (m,): the base is the homogeneous one (density None) or the
+    grid, the cells' h by the source → dict: hit, event, t (0 without an event), E, cells."""
+    import medium_reference as mr
+    m = mr.medium_struct(medium)
+    g, n = vr.grid_of(density) if density is not None else (None, None)
+    h = None if source == 0 else vr.grid_of(density if source == 1 else heat)[0]
+    o, d, t_end = vr._rays(o, d, t_end)
+    k = o.shape[0]
+    u = np.ascontiguousarray(np.broadcast_to(np.asarray(u, dtype=np.float32), (k,)))
+    hit, event, cells = (np.empty(k, np.int32) for _ in range(3))
+    t, E = np.empty(k, np.float32), np.empty(k, np.float32)
+    lib().glow_flights(C.byref(m), g.ctypes.data if g is not None else None, h.ctypes.data if h is not None else None, n.ctypes.data if g is not None else None,
+                       k, o.ctypes.data, d.ctypes.data, t_end.ctypes.data, u.ctypes.data, hit.ctypes.data, event.ctypes.data, t.ctypes.data, E.ctypes.data,
+                       cells.ctypes.data)
+    return dict(hit=hit, event=event, t=t, E=E, cells=cells)
 
 
 def _cfg(medium, density, radiance, source, heat, kw):

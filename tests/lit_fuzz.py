@@ -599,3 +599,183 @@ def gloss_device_keywords(call, env, w, h, spp, depth):
     if call.medium:
         kw.update(medium=fuzz_medium(call.trial))
     return kw
+
+
+# ---- random fog: a box, a density grid, a tint, a glow and a sample mode per trial, for the four fog families that came
+# after §27 — volume, chroma, glow and sampled glow — and the call lists of tests/test_lit_fuzz_fog.py ----------------------------------------
+FOG_DIMS = (1, 2, 3, 5, 7, 13, 16, 32, 64)
+FOG_G = (0.0, 0.7, -0.5, 0.95, -0.95, 0.7, 0.0, -0.5)
+FOG_SAMPLE = ("mis", "light", None, "mis", "light", None, "mis", "light")
+FOG_FAMILIES = ("volume", "chroma", "glow", "glow_sampled")
+
+
+def scene_bounds(host):
+    """The box around every primitive of a scene but its ground and dome (spheres of radius >= 40): (lo, hi)."""
+    d = host.desc
+    lo, hi = np.full(3, np.inf), np.full(3, -np.inf)
+    for k in range(d.num_spheres):
+        s = d.spheres[k]
+        if s.radius < 40.0:
+            c = np.array(s.center.e[:])
+            lo, hi = np.minimum(lo, c - s.radius), np.maximum(hi, c + s.radius)
+    for k in range(d.num_planes):
+        p = d.planes[k]
+        o, u, v = (np.array(x.e[:]) for x in (p.base, p.u, p.v))
+        for a in (-1.0, 0.0, 1.0):          # (whichever way a type spans its plane from base, u and v)
+            for b in (-1.0, 0.0, 1.0):
+                lo, hi = np.minimum(lo, o + a * u + b * v), np.maximum(hi, o + a * u + b * v)
+    return lo, hi
+
+
+def _fog_grid(g, dims, empty):
+    """(nz, ny, nx) densities in [0.1, 2), a share `empty` of the cells exactly 0 (test_volume.random_grid's rule, from the fog's generator)."""
+    shape = (dims[2], dims[1], dims[0])
+    grid = g.uniform(0.1, 2.0, shape).astype(np.float32)
+    grid[g.random(shape) < empty] = 0.0
+    return grid
+
+
+@functools.lru_cache(maxsize=None)
+def fuzz_fog(trial):
+    """The fog of a trial, a pure function of (SEEDS[trial], trial) with a generator of its own: dict(medium: sigma_t, albedo, g and the
+    box; density: an (nz, ny, nx) grid, each dimension drawn from FOG_DIMS; tint; radiance and source (with heat where the source is 2);
+    sample: None, "mis" or "light").  The box comes from the trial's own scene bounds and eye: around the eye (0, 3), around the whole
+    scene (1), a thin slab through it (2), half the scene (4), a face through the first sphere's centre (5), drawn (6, 7).  Arranged,
+    like fuzz_medium's regions: a 1 x 1 x 1 grid of density 0.6 (2), a grid with a 64-long axis and the other two 1 (5), a grid with 60 %
+    of its cells empty (6), equal tints (0) and a tint with a channel of exactly 0 (3), radiance 0 (5: a trial that takes no light samples); source is trial % 3."""
+    c = case(trial)
+    g = np.random.default_rng([SEEDS[trial], trial, 39])
+    f32 = lambda x: tuple(float(np.float32(v)) for v in x)
+    eye = np.array(c.eye)
+    lo, hi = scene_bounds(c.host)
+    dims = [int(g.choice(FOG_DIMS)) for _ in range(3)]
+    half = g.uniform(2.0, 4.0, 3)
+    drawn_lo = g.uniform(-5.0, -1.0, 3)
+    drawn_hi = drawn_lo + g.uniform(3.0, 6.0, 3)
+    margin = g.uniform(0.1, 0.5, 3)
+    sigma_t = float(np.float32(10.0 ** g.uniform(-1.0, 0.2)))
+    albedo = f32(g.uniform(0.7, 0.98, 3))
+    tint = f32(g.uniform(0.3, 1.5, 3))
+    radiance = f32(g.uniform(0.05, 0.4, 3))
+    axis = int(g.integers(0, 3))
+    empty = 1.0 / 3.0
+    if trial in (0, 3):
+        box = np.concatenate([eye - half, eye + half])
+    elif trial == 1:
+        box = np.concatenate([lo - margin, hi + margin])
+    elif trial == 2:
+        box = np.concatenate([lo - margin, hi + margin])
+        mid = 0.5 * (lo[1] + hi[1])
+        box[1], box[4] = mid - 0.1, mid + 0.1
+        dims = [1, 1, 1]
+    elif trial == 4:
+        box = np.concatenate([lo - margin, hi + margin])
+        box[3] = 0.5
+    elif trial == 5:
+        box = np.concatenate([drawn_lo, drawn_hi])
+        s = c.host.desc.spheres[0]
+        box[3] = s.center.e[0]
+        box[0] = min(box[0], box[3] - 3.0)
+        dims = [1, 1, 1]
+        dims[axis] = 64
+    else:
+        box = np.concatenate([drawn_lo, drawn_hi])
+    if trial == 6:
+        empty = 0.6
+    density = np.full((1, 1, 1), 0.6, np.float32) if trial == 2 else _fog_grid(g, dims, empty)
+    heat = _fog_grid(g, dims, 0.25)
+    if trial == 0:
+        tint = (tint[0],) * 3
+    if trial == 3:
+        tint = (1.0, 0.0, 0.5)
+    if trial == 5:
+        radiance = (0.0, 0.0, 0.0)
+    source = trial % 3
+    density.setflags(write=False)
+    heat.setflags(write=False)
+    return dict(medium=dict(sigma_t=sigma_t, albedo=albedo, g=FOG_G[trial], box=f32(box)), density=density, tint=tint, radiance=radiance, source=source,
+                heat=heat if source == 2 else None, sample=FOG_SAMPLE[trial])
+
+
+# A fog call on a twin.  family: one of FOG_FAMILIES; grid: the call passes the fog's grid (else volume = None: the homogeneous box); the
+# rest as in GCall.  The environment is the twin's map where it has one
+FCall = collections.namedtuple("FCall", "test family trial lens planes select mis env shard gn ge grid")
+
+
+def _fog_cells(test, trial):
+    """The fog calls of one twin: per family one call for each (select, sample_planes); the lens and the grid alternate with the pair and
+    the trial, so that over the eight twins every family meets lens off / on x the four pairs x grid / no grid, and per twin every family
+    appears with the grid and without it.  Sampled glow keeps the grid (without one it is the glow call)."""
+    c = gloss_case(trial)
+    out = []
+    for family in FOG_FAMILIES:
+        for p, (planes, select) in enumerate(PLANES_SELECT):
+            lens = (p + trial) % 2 == 1
+            grid = family == "glow_sampled" or ((p >> 1) + (trial >> 1)) % 2 == 0
+            env = (1 if select else 2) if c.env is not None else None
+            out.append(FCall(test, family, trial, lens, planes, select, 1 if lens else 0, env, None, (trial + planes) % 2, (trial + select) % 2 if env else 0, grid))
+    return out
+
+
+def fog_probe_calls(trial):
+    return _fog_cells("fog probes", trial)
+
+
+@functools.lru_cache(maxsize=None)
+def _all_fog_frame_calls():
+    """The frame cells of every twin; each family's calls rotate through SHARDS."""
+    turn, out = collections.Counter(), {}
+    for t in TRIALS:
+        out[t] = []
+        for c in _fog_cells("fog frames", t):
+            out[t].append(c._replace(shard=turn[c.family, c.lens] % 3))
+            turn[c.family, c.lens] += 1
+    return out
+
+
+def fog_frame_calls(trial):
+    return list(_all_fog_frame_calls()[trial])
+
+
+def fog_calls(trial):
+    """Per family, the probe and the frame calls of the trial: {family: (probes, frames)}."""
+    return {f: ([c for c in fog_probe_calls(trial) if c.family == f], [c for c in fog_frame_calls(trial) if c.family == f]) for f in FOG_FAMILIES}
+
+
+def fog_reference_keywords(call, w, h, spp, depth):
+    """The keywords of volume_reference / chroma_reference / glow_reference / glow_sample_reference's trace and frame for a fog call (the
+    camera apart)."""
+    c, f = gloss_case(call.trial), fuzz_fog(call.trial)
+    kw = dict(medium=f["medium"], density=f["density"] if call.grid else None, select=call.select, nee_mis=call.mis, planes=call.planes, glossy=call.gn,
+              glossy_env=call.ge)
+    if call.lens:
+        kw.update(lens=c.lens, cam_close=c.close(w, h, spp, depth))
+    if call.env is not None:
+        kw.update(rgb=c.env, env_params=c.env_params(call.env))
+    if call.family == "chroma":
+        kw.update(tint=f["tint"])
+    if call.family in ("glow", "glow_sampled"):
+        source = f["source"] if call.grid else 0          # (source 1 and 2 follow a grid)
+        kw.update(radiance=f["radiance"], source=source, heat=f["heat"] if source == 2 else None)
+    if call.family == "glow_sampled":
+        kw.update(sample=f["sample"])
+    return kw
+
+
+def fog_device_keywords(call, env, volume, heat, sampler, w, h, spp, depth):
+    """DeviceScene.render_<family>_to_host / trace_samples_<family> keywords of a fog call; env: an rb.Env of the twin's map (or None);
+    volume, heat: the rb.Volumes of the fog's grids (heat None unless the source is 2); sampler: the rb.GlowSampler of them."""
+    c, f = gloss_case(call.trial), fuzz_fog(call.trial)
+    kw = dict(nee={"mis": call.mis, "sample_planes": call.planes, "select": call.select, "glossy": call.gn}, medium=f["medium"], volume=volume if call.grid else None)
+    if call.lens:
+        kw.update(lens=c.lens_dict(), cam_close=c.close(w, h, spp, depth))
+    if call.env is not None:
+        kw.update(env=env, env_params=dict(glossy=call.ge, **c.env_params(call.env)))
+    if call.family == "chroma":
+        kw.update(tint=f["tint"])
+    if call.family in ("glow", "glow_sampled"):
+        source = f["source"] if call.grid else 0
+        kw.update(glow=dict(radiance=f["radiance"], source=source), heat=heat if source == 2 else None)
+    if call.family == "glow_sampled":
+        kw.update(sample=f["sample"], sampler=sampler if f["sample"] is not None else None)
+    return kw

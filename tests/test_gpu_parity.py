@@ -1369,7 +1369,7 @@ def test_developer_build_checks_and_retired_experiments():
     assert b"dev=0" in lib.rt_version_string() and b"parity=1" in lib.rt_version_string()
     assert not hasattr(lib, "rt_debug_check_fast_math") and not hasattr(lib, "rt_debug_check_sphere_roots")
     assert not hasattr(lib, "rt_debug_build_lbvh") and not hasattr(lib, "rt_debug_guard_leaves")
-    assert not hasattr(lib, "rt_debug_math_eval")
+    assert not hasattr(lib, "rt_debug_math_eval") and not hasattr(lib, "rt_debug_fog_rays")
     host = rb.HostScene.rtiow()
     with pytest.raises(RuntimeError, match="retired"):
         rb.DeviceScene(host, device=0, honour_env=False, kernel=rb.KERNEL_WAVEFRONT).render_to_host(rb.rtiow_camera(32, 20, 2, 8))

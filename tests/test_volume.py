@@ -238,23 +238,24 @@ WALK_MEASURED = 3.402e-07
 WALK_TOL = 4 * WALK_MEASURED
 
 
-@functools.lru_cache(maxsize=None)
-def walk_cases(name):
-    """Rays (o, d, t_end) through WALK_GRIDS[name] with a random grid (a third of the cells empty): origins outside aimed into the box,
-    origins inside, rays with one or two d_k == 0 (origins inside and outside), rays aimed exactly at grid vertices and leaving them along
-    exact diagonals, rays along cell planes (the box's faces among them); t_end infinite for half of each kind and finite for the rest."""
-    n, lo, hi = WALK_GRIDS[name]
+# walk_rays' classes in the order it emits them: (name, rays)
+WALK_CLASSES = (("outside, aimed inside", 400), ("inside, any direction", 200), ("one d_k == 0, inside", 60), ("one d_k == 0, outside", 60),
+                ("two d_k == 0, inside", 60), ("two d_k == 0, outside", 60), ("at a grid vertex, from outside", 150), ("at a grid vertex, from inside", 50),
+                ("from a vertex down an exact diagonal", 60), ("along a cell plane or edge, inside", 120), ("along a cell plane, from outside", 60))
+
+
+def walk_rays(n, lo, hi, rng, centre=0.0, scale=1.0):
+    """walk_cases' rays for any box (lo, hi) and dimensions n = (nx, ny, nz), drawn from rng: (o, d, t_end, kind), kind the index of each
+    ray's class in WALK_CLASSES.  The origins "outside" lie on spheres of radius 3.5 … 6 times `scale` about `centre` (0 and 1 for the
+    boxes of WALK_GRIDS, which they were written for)."""
     n, lo, hi = np.array(n), np.array(lo), np.array(hi)
-    rng = np.random.default_rng(sum(map(ord, name)))
-    density = random_grid((n[2], n[1], n[0]), 100 + int(n.sum()))
-    density.flat[0] = 1.5                               # (the 1^3 grid's only cell is not an empty one)
     w = (hi - lo) / n
     inside = lambda k: (lo + rng.random((k, 3)) * (hi - lo)).astype(np.float32)
     vertex = lambda k: (lo + np.stack([rng.integers(0, n[a] + 1, k) for a in range(3)], 1) * w).astype(np.float32)
 
     def sphere(k):
         v = rng.normal(size=(k, 3))
-        return (v / np.linalg.norm(v, axis=1, keepdims=True) * rng.uniform(3.5, 6.0, (k, 1))).astype(np.float32)
+        return (centre + v / np.linalg.norm(v, axis=1, keepdims=True) * rng.uniform(3.5, 6.0, (k, 1)) * scale).astype(np.float32)
     o, d = [], []
     a = sphere(400)                                     # outside, aimed at points inside
     o.append(a)
@@ -262,7 +263,7 @@ def walk_cases(name):
     o.append(inside(200))                               # inside, any direction
     d.append(rng.normal(size=(200, 3)).astype(np.float32))
     for zeros in (1, 2):                                # d_k == 0, origins inside and outside
-        for origin in (inside(60), sphere(60) * np.float32(0.5)):
+        for origin in (inside(60), (centre + (sphere(60) - np.float32(centre)) * np.float32(0.5)).astype(np.float32)):
             dd = rng.normal(size=(60, 3)).astype(np.float32)
             for r in range(60):
                 dd[r, rng.choice(3, zeros, replace=False)] = 0.0
@@ -297,11 +298,44 @@ def walk_cases(name):
         a[r, k] = t[r, k] = v[r, k]
     o.append(a)
     d.append(t - a)
+    assert [len(x) for x in o] == [k for _, k in WALK_CLASSES]
+    kind = np.repeat(np.arange(len(WALK_CLASSES)), [k for _, k in WALK_CLASSES])
     o, d = np.concatenate(o).astype(np.float32), np.concatenate(d).astype(np.float32)
     t_end = np.where(np.arange(o.shape[0]) % 2 == 0, np.float32(np.inf), rng.uniform(0.3, 1.5, o.shape[0]).astype(np.float32)).astype(np.float32)
+    return o, d, t_end, kind
+
+
+@functools.lru_cache(maxsize=None)
+def walk_cases(name):
+    """Rays (o, d, t_end) through WALK_GRIDS[name] with a random grid (a third of the cells empty): origins outside aimed into the box,
+    origins inside, rays with one or two d_k == 0 (origins inside and outside), rays aimed exactly at grid vertices and leaving them along
+    exact diagonals, rays along cell planes (the box's faces among them); t_end infinite for half of each kind and finite for the rest.
+    The rays are walk_rays'; test_walk_cases_are_what_they_were pins the arrays' bytes."""
+    n, lo, hi = WALK_GRIDS[name]
+    n, lo, hi = np.array(n), np.array(lo), np.array(hi)
+    rng = np.random.default_rng(sum(map(ord, name)))
+    density = random_grid((n[2], n[1], n[0]), 100 + int(n.sum()))
+    density.flat[0] = 1.5                               # (the 1^3 grid's only cell is not an empty one)
+    o, d, t_end, _ = walk_rays(n, lo, hi, rng)
     medium = dict(sigma_t=WALK_SIGMA, box=tuple(lo) + tuple(hi))
     tau_max = WALK_SIGMA * float(density.max()) * float(np.linalg.norm(hi - lo))
     return medium, density, o, d, t_end, tau_max, float(np.linalg.norm(hi - lo))
+
+
+# sha256 over the bytes of walk_cases(name)'s density, o, d and t_end, taken before walk_rays was split off it
+WALK_CASES_SHA256 = {"1": "afdfb1e64b566c0157deea5b6ac04d4fe32a4e235e919c5404945e1962649e04",
+                     "2x3x5": "86956aecb424f34aad121055b90b29321776441c5c752e44758d98f66fcf2667",
+                     "16": "b06774428d9b01a6b8f673e55453a0cfd2637d361ba41ce25c816f5d9d2f65d9",
+                     "1x1x64": "ee58d5eaf8854794b1ec8b77e6dc4168dcbdb1c1e98f1ec842cce4c03aa0eb54"}
+
+
+def test_walk_cases_are_what_they_were():
+    """walk_rays generalises walk_cases' generator to any box and dimensions; walk_cases itself returns the arrays it always returned."""
+    import hashlib
+    for name, want in WALK_CASES_SHA256.items():
+        medium, density, o, d, t_end, tau_max, diag = walk_cases(name)
+        assert o.shape == (1280, 3) and o.dtype == d.dtype == t_end.dtype == density.dtype == np.float32
+        assert hashlib.sha256(b"".join(np.ascontiguousarray(a).tobytes() for a in (density, o, d, t_end))).hexdigest() == want, name
 
 
 def _walk_errors(name):

@@ -20,7 +20,7 @@ def lib():
     l = cpu_ref.build("volume_ref.c")
     desc, cam, cfg = C.POINTER(rb.SceneDesc), C.POINTER(rb.CameraData), C.POINTER(VolumeCfg)
     l.volume_walks.restype = None
-    l.volume_walks.argtypes = [C.POINTER(rb.MediumParams), C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 10
+    l.volume_walks.argtypes = [C.POINTER(rb.MediumParams), C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 14
     l.volume_walks_f64.restype = None
     l.volume_walks_f64.argtypes = [C.POINTER(rb.MediumParams), C.c_void_p, C.c_void_p, C.c_int64] + [C.c_void_p] * 6
     l.volume_trace.restype = None
@@ -44,20 +44,31 @@ def _rays(o, d, t_end):
     return o, d, t_end
 
 
-def walks(medium, density, o, d, t_end, rem=None):
+# volume_ref.c's VT_* tallies, in its order: the bit k of walks()' `flags` is TALLIES[k].  The first seven are the walk's (either walk of the
+# ray sets them), the last four the free flight's
+TALLIES = ("two axes tie", "three axes tie", "clamp tb < ta", "entry cell clamped", "left by tb >= t1", "left by the index", "an axis with d_k == 0",
+           "flight: empty cell crossed", "flight: event in the first cell", "flight: event after an empty cell", "flight: no event")
+
+
+def walks(medium, density, o, d, t_end, rem=None, tallies=True):
     """The header's walk on rays (o, d) (m, 3) over [0, t_end] → dict: hit (the interval), acc (float32 optical depth), cells, seg_sum and
-    seg_min (float64, of the float32 segments), length ((t1 - t0) * len in float32); with rem (m,): event and t_event of a free flight."""
+    seg_min (float64, of the float32 segments), length ((t1 - t0) * len in float32), tr (expf(-acc); 0 where the interval is empty), flags
+    (the tallies of the ray's walks, TALLIES' bits); with rem (m,): event, t_event and rem_left (the rem a flight without an event ended
+    with) and flight_cells of a free flight.  tallies=False: the library counts nothing (flags stays 0) — every other column is the same."""
     m = mr.medium_struct(medium)
     g, n = grid_of(density)
     o, d, t_end = _rays(o, d, t_end)
     k = o.shape[0]
     hit, acc, cells, segs = np.empty(k, np.int32), np.empty(k, np.float32), np.empty(k, np.int32), np.empty((k, 3), np.float64)
-    event, t_event = np.zeros(k, np.int32), np.zeros(k, np.float32)
+    event, t_event, rem_left = np.zeros(k, np.int32), np.zeros(k, np.float32), np.zeros(k, np.float32)
+    tr, flight_cells, flags = np.empty(k, np.float32), np.zeros(k, np.int32), np.zeros(k, np.int32)
     if rem is not None:
         rem = np.ascontiguousarray(np.broadcast_to(np.asarray(rem, dtype=np.float32), (k,)))
     lib().volume_walks(C.byref(m), g.ctypes.data, n.ctypes.data, k, o.ctypes.data, d.ctypes.data, t_end.ctypes.data, hit.ctypes.data, acc.ctypes.data,
-                       cells.ctypes.data, segs.ctypes.data, rem.ctypes.data if rem is not None else None, event.ctypes.data, t_event.ctypes.data)
-    return dict(hit=hit, acc=acc, cells=cells, seg_sum=segs[:, 0], seg_min=segs[:, 1], length=segs[:, 2], event=event, t_event=t_event)
+                       cells.ctypes.data, segs.ctypes.data, rem.ctypes.data if rem is not None else None, event.ctypes.data, t_event.ctypes.data,
+                       tr.ctypes.data, rem_left.ctypes.data, flight_cells.ctypes.data, flags.ctypes.data if tallies else None)
+    return dict(hit=hit, acc=acc, cells=cells, seg_sum=segs[:, 0], seg_min=segs[:, 1], length=segs[:, 2], event=event, t_event=t_event, tr=tr,
+                rem_left=rem_left, flight_cells=flight_cells, flags=flags)
 
 
 def walks_f64(medium, density, o, d, t_end):
