@@ -1280,7 +1280,7 @@ rt_status rt_trace_samples_volume(rt_scene *scene, const rt_camera_data *cam_ope
  *   == NULL, the default tint and e == 0, and the probe's cells column is then that call's.  So does a medium with sigma_t == 0 (or no
  *   medium) under any tint.  A 1 x 1 x 1 grid of density 1 = the homogeneous box under the same tint, through the grid's own chroma kernels
  *   (s = R / 1, acc = seg).  volume == NULL = the homogeneous chroma kernels, in any region.
- * Left out: the adaptive, AOV and denoise calls with a tint; choosing the channel by the path's throughput instead of uniformly; a tint per
+ * Left out: ~~the adaptive call with a tint~~ (rt_render_fog_adaptive, "adaptive sampling on every fog rung" below); the AOV and denoise calls with a tint; choosing the channel by the path's throughput instead of uniformly; a tint per
  *   cell; ~~emission in the medium~~ (rt_render_glow, "emission in the medium" below); tiles and rt_context; the guarded walk.
  * Checks, all before anything is enqueued: rt_render_volume's, in its order up to and including the volume's region check; then
  *   RT_ERR_INVALID_ARG for struct_bytes below 8, a tint channel that is negative, NaN or infinite, a product sigma_t * tint[k] that is not
@@ -1331,7 +1331,7 @@ rt_status rt_trace_samples_chroma(rt_scene *scene, const rt_camera_data *cam_ope
  *   checked but not read).  A 1 x 1 x 1 grid of density 1 under source 0 or 1 = the homogeneous box under source 0, through the grid's own
  *   glow kernels (s = rem / sigma_t, E = 0 + 1 * s).  Source 2 with a heat grid equal to the density grid = source 1.
  * Left out: ~~light-sampling the glow (fire lights a room by the paths that happen to cross it)~~ (rt_render_glow_sampled, "light samples of the glow" below); a glow with sigma_t == 0 (the estimator rides
- *   on the free flight); a glow under a tint (rt_render_chroma); the adaptive, AOV and denoise calls with a glow; trilinear heat (h is
+ *   on the free flight); a glow under a tint (rt_render_chroma); ~~the adaptive call with a glow~~ (rt_render_fog_adaptive, "adaptive sampling on every fog rung" below); the AOV and denoise calls with a glow; trilinear heat (h is
  *   piecewise constant like the density); blackbody colour from temperature; tiles and rt_context; the guarded walk.
  * Checks, all before anything is enqueued: rt_render_volume's, in its order up to and including the volume's region check; then
  *   RT_ERR_INVALID_ARG for struct_bytes below 8, source outside {0, 1, 2}, a radiance channel that is negative, NaN or infinite, a non-zero
@@ -1399,7 +1399,7 @@ rt_status rt_trace_samples_glow(rt_scene *scene, const rt_camera_data *cam_open,
  *
  * Identities, bit for bit: params NULL, sample == 0, an empty sampler or radiance 0, 0, 0 hands the call over whole to rt_render_glow
  *   (rt_trace_samples_glow; glow_samples 0).  max_depth = 1 under mis 0 or 1 = rt_render_glow's radiance, through these kernels.
- * Left out: a tint; the adaptive, AOV and denoise calls; a glow without a grid (a homogeneous box can pass a 1 x 1 x 1 grid); a sample that
+ * Left out: a tint; ~~the adaptive call~~ (rt_render_fog_adaptive, "adaptive sampling on every fog rung" below); the AOV and denoise calls; a glow without a grid (a homogeneous box can pass a 1 x 1 x 1 grid); a sample that
  *   picks the cell by its distance to the vertex; tiles and rt_context; the guarded walk.
  * Checks, all before anything is enqueued: rt_render_glow's parameter checks in its order; then RT_ERR_INVALID_ARG for struct_bytes below
  *   8, sample or mis outside {0, 1}, sample = 1 without a volume, sample = 1 without a sampler, a sampler built for another source, other
@@ -1506,6 +1506,54 @@ rt_status rt_render_volume_adaptive(rt_scene *scene, const rt_camera_data *cam_o
 rt_status rt_render_aov_volume(rt_scene *scene, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_medium_params *medium,
                                const rt_volume *volume, const rt_shard *shard, int32_t sample_first, const rt_aov_buffers *buffers,
                                float *d_transmittance_sum /* NULL or 1 float per pixel */, void *hip_stream, int32_t sync, rt_timing *timing);
+
+/* ---- adaptive sampling on every fog rung -------------------------------------------------------------------------------
+ * rt_render_volume_adaptive's rule, statistics, rounds and prior on the estimator of whichever fog call the arguments name: the medium, a
+ * density grid, then either a tint ("chromatic extinction") or a glow ("emission in the medium"), and light samples of the glow ("light
+ * samples of the glow").  No new arithmetic: a sample is the rung's frame call's — rt_render_medium, rt_render_volume, rt_render_chroma,
+ * rt_render_glow or rt_render_glow_sampled, the one that call itself would run after its own hand-overs under the same lit, medium,
+ * volume, chroma, glow, heat, sample and sampler; the moments, the stopping rules and the prior are those of the adaptive sections above.
+ * stop == NULL or rule == 0, and d_prior == NULL, mean what they mean in rt_render_lit_adaptive_prior.
+ *
+ * Per-pixel parity.  Pixel p receives samples sample_first … sample_first + n_p - 1 of the rung's frame call; d_fb_sum[p] is that call's
+ * pixel at samples_per_pixel = n_p and the same sample_first (added in sample order from 0); d_spp[p] = n_p in {min_spp + k * batch_spp <=
+ * max_spp}; d_moments (NULL or 2 floats per pixel) holds (S1, S2) of the luminance of the radiance as that call adds it — the per-channel
+ * weights of a tint, the track-length emission and the glow's light samples with their MIS weights included — float32, in sample order.
+ *
+ * Identities, bit for bit, in all three outputs: threshold = 0 is the rung's frame call at min_spp + R * batch_spp, every count equal to
+ * that.  chroma, glow and sample all NULL is rt_render_volume_adaptive with the same remaining arguments (and from there on its own
+ * identities: volume == NULL, no medium, a 1 x 1 x 1 grid of density 1).  Equal tints e are the grey call at sigma_t * e.  Radiance 0, 0, 0
+ * is the call without a glow.  sample->sample == 0, an empty sampler or a dark glow is the call without a sample.  Each identity runs the
+ * lower rung's kernels, as the frame calls' hand-overs do.
+ *
+ * Checks, all before anything is enqueued, in this order: rt_render_adaptive's parameter checks; the stop parameters'; the prior's; fog ==
+ * NULL or fog->struct_bytes below 8 (every field is optional by size: a shorter struct has the ones behind its end NULL); chroma together with
+ * glow (a call takes a tint or a glow, not both, because no frame call renders both: decided by the pointers alone, whatever they point
+ * to); then the parameter checks of the highest rung the pointers ask for, in that frame call's order (rt_render_lit's, the medium's, the
+ * volume's, the tint's or the glow's, the sample's; heat and sampler are not looked at below their rung, and beside a tint — where there
+ * is no glow to aim at — neither are sample and sampler: the call is the tint's); the sample range
+ * of sample_first + min_spp + R * batch_spp; d_fb_sum or d_spp NULL; the null scene; the volume's, the heat's and the sampler's device
+ * against the scene's; the scene's and the camera's as in rt_render_lit; RT_ERR_UNSUPPORTED for pixels x batch_spp at or above 2^31 - 4096
+ * when R > 0.  Every message names rt_render_fog_adaptive, after a hand-over too.  max_depth <= 0: zero sums and moments, the counts by the
+ * rule.  Rows of a shard only.  Handle state, buffers and timing: as rt_render_volume_adaptive.
+ * Left out: AOVs and the denoisers for a tinted medium (a per-channel transmittance guide is a design of its own); rtp_main's --fog-denoise
+ *   on --fog-adaptive; a tint together with a glow; tiles and rt_context; the guarded walk. */
+typedef struct rt_fog_params {   /* IN, caller-sized; the pointers are read during the call only */
+    uint32_t struct_bytes;
+    const rt_medium_params *medium;         /* NULL: no medium */
+    const rt_volume *volume;                /* NULL: no grid */
+    const rt_chroma_params *chroma;         /* NULL: no tint */
+    const rt_glow_params *glow;             /* NULL: no glow */
+    const rt_volume *heat;                  /* source 2 only */
+    const rt_glow_sample_params *sample;    /* NULL: no light samples of the glow */
+    const rt_glow_sampler *sampler;         /* read under sample = 1 */
+} rt_fog_params;
+/* Defaults into *p: every pointer NULL; struct_bytes = sizeof(rt_fog_params). */
+void rt_fog_params_init(rt_fog_params *p);
+rt_status rt_render_fog_adaptive(rt_scene *scene, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_fog_params *fog,
+                                 const rt_adaptive_params *params, const rt_stop_params *stop, const float *d_prior, const rt_shard *shard,
+                                 int32_t sample_first, float *d_fb_sum, int32_t *d_spp, float *d_moments, void *hip_stream, int32_t sync,
+                                 rt_timing *timing);
 
 /* Milliseconds of the most recent rt_render kernel of this scene (waits for it). */
 rt_status rt_last_kernel_ms(rt_scene *scene, float *ms);

@@ -296,6 +296,7 @@ struct rt_scene {
     int last_passes = 0;
     uint64_t last_samples = 0;
     bool timed = false;
+    bool durations_read = false;    // rt_last_timing has measured the timed render's durations once: it reports those from then on
     int num_cus = 0;
     uint64_t device_bytes = 0;      // total memory of the device (workspace default: a sixteenth of it)
     float build_ms = 0.0f;          // device BVH build time (RTP_BUILD=device), else 0
@@ -1519,6 +1520,7 @@ rt_status close_book(rt_scene *sc, const FrameBook &B, const rt_timing &record, 
     f.samples = samples;
     f.serial = ++sc->frame_serial;
     sc->timed = true;
+    sc->durations_read = false;
     sc->last = record;
     sc->last_passes = passes;
     sc->last_samples = samples;
@@ -3984,6 +3986,42 @@ rt_status rt_trace_samples_glow_sampled(rt_scene *sc, const rt_camera_data *cam_
                      {final_medium_seed, medium_events, cells, glow_length, glow_samples});
 }
 
+// ---- rt_render_fog_adaptive (rtp_amd.h, "adaptive sampling on every fog rung"): rt_render_volume_adaptive's steps
+// (lit_adaptive_run) on the estimator of the rung the arguments name — fog_setup at the highest rung the pointers ask for, then the frame
+// kernel and the list variant of the light with_fog_light makes, which is the lower rung's after a hand-over and with_lit's without a medium.
+void rt_fog_params_init(rt_fog_params *p) {
+    if (!p) return;
+    std::memset(p, 0, sizeof(*p));
+    p->struct_bytes = (uint32_t)sizeof(*p);
+}
+
+rt_status rt_render_fog_adaptive(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_fog_params *fog, const rt_adaptive_params *params,
+                                 const rt_stop_params *stop, const float *d_prior, const rt_shard *shard, int32_t sample_first, float *d_fb_sum, int32_t *d_spp,
+                                 float *d_moments, void *hip_stream, int32_t sync, rt_timing *timing) {
+    const char *what = "rt_render_fog_adaptive";
+    rt_adaptive_params a;
+    int32_t rule;
+    rt_status st = adaptive_check(what, params, a);
+    if (st != RT_OK) return st;
+    if ((st = stop_check(what, stop, rule, "")) != RT_OK) return st;
+    if ((st = prior_check(what, d_prior, cam_open, shard, d_fb_sum, d_spp, d_moments)) != RT_OK) return st;
+    if (!fog || fog->struct_bytes < 8u) return fail(RT_ERR_INVALID_ARG, "rt_render_fog_adaptive: null rt_fog_params (or struct_bytes below 8)");
+    rt_fog_params f{};
+    std::memcpy(&f, fog, fog->struct_bytes < sizeof(f) ? fog->struct_bytes : sizeof(f));
+    if (f.chroma && f.glow) return fail(RT_ERR_INVALID_ARG, "rt_render_fog_adaptive: a call takes a tint or a glow, not both (no frame call renders a tint together with a glow)");
+    // (a sample beside a tint has no glow to aim at: the tint's call, and the sample is above its rung)
+    const FogRung rung = f.chroma ? kFogTint : f.sample ? kFogSample : f.glow ? kFogGlow : kFogVolume;
+    FogSetup X;
+    if ((st = fog_setup(what, rung, cam_open, {lit, f.medium, f.volume, f.chroma, f.glow, f.heat, f.sample, f.sampler}, X)) != RT_OK) return st;
+    if ((st = check_sample_range(what, sample_first, a.min_spp + (a.max_spp - a.min_spp) / a.batch_spp * a.batch_spp)) != RT_OK) return st;
+    if (!d_fb_sum || !d_spp) return fail(RT_ERR_INVALID_ARG, "rt_render_fog_adaptive: null framebuffer or sample counts");
+    if ((st = fog_scene(what, sc, X)) != RT_OK) return st;
+    const LitSetup &S = X.S;
+    return lit_adaptive_run(what, sc, cam_open, S, a, rule, d_prior, shard, sample_first, d_fb_sum, d_spp, d_moments, hip_stream, sync, timing, [&](auto run) {
+        return with_fog_light(sc, X, [&](const auto &T) { return run(lit_kernels_of(S.lens, T).frame, lit_kernels_of(S.lens, T).list, &T); });
+    });
+}
+
 void rt_timing_init(rt_timing *t) {
     if (!t) return;
     std::memset(t, 0, sizeof(*t));
@@ -3994,12 +4032,18 @@ rt_status rt_last_timing(rt_scene *sc, rt_timing *timing) {
     if (!sc) return fail(RT_ERR_INVALID_ARG, "null argument");
     if (const rt_status ts = timing_check(timing)) return ts;
     if (sc->timed) {
-        if (const rt_status ps = sc->clock[kClockRender].elapsed(sc->last.kernel_ms)) return ps;
-        float sum = 0.0f, rework = 0.0f, primary = 0.0f;
+        // (measured once per render: hipEventElapsedTime of one recorded pair can come back a nanosecond apart once later work has
+        // recorded events of its own — an adaptive call, say — and the record of a finished render does not change: DESIGN.md §40)
+        float kernel = 0.0f, sum = 0.0f, rework = 0.0f, primary = 0.0f;
+        if (const rt_status ps = sc->clock[kClockRender].elapsed(kernel)) return ps;
         if (const rt_status ps = frame_parts(sc, sum, rework, primary)) return ps;
-        sc->last.trace_ms = sum;
-        sc->last.rework_ms = rework;
-        sc->last.primary_ms = sc->last.primary_visibility ? primary : 0.0f;
+        if (!sc->durations_read) {
+            sc->last.kernel_ms = kernel;
+            sc->last.trace_ms = sum;
+            sc->last.rework_ms = rework;
+            sc->last.primary_ms = sc->last.primary_visibility ? primary : 0.0f;
+            sc->durations_read = true;
+        }
         // (the frame is done, so what it left for the handle's judgement has landed as well: a scene the guarded walk keeps handing
         // back — dense overlaps, a camera inside a sphere, … — is cheaper on the exact walk alone; later frames of this handle use it)
         if (const rt_status ps = poll_feedback(sc, true)) return ps;

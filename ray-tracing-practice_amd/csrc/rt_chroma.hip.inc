@@ -107,8 +107,12 @@ template <bool kLens, class Base>
 __global__ void __launch_bounds__(kLightBlock, kMediumWaves) chroma_render_kernel(const KParams P, const ChromaLit<Base> T, const LensCam C) {
     lit_render_body<kLens>(P, T, C);
 }
-// (no adaptive call takes a tint: there is no list variant)
+// the list variant: rt_render_fog_adaptive's rounds under a tint (DESIGN.md §40) — the same body on a list whose length lives on the device
+template <bool kLens, class Base>
+__global__ void __launch_bounds__(kLightBlock, kMediumWaves) chroma_list_render_kernel(const KParams P, const ChromaLit<Base> T, const LensCam C) {
+    lit_render_body<kLens, ChromaLit<Base>, true>(P, T, C);
+}
 template <bool kLens, class Base> const void *lit_frame_kernel_of(const ChromaLit<Base> &) { return (const void *)chroma_render_kernel<kLens, Base>; }
-template <bool kLens, class Base> const void *lit_list_kernel_of(const ChromaLit<Base> &) { return nullptr; }
+template <bool kLens, class Base> const void *lit_list_kernel_of(const ChromaLit<Base> &) { return (const void *)chroma_list_render_kernel<kLens, Base>; }
 
 }  // namespace rtk

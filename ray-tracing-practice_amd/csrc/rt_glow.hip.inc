@@ -108,8 +108,12 @@ template <bool kLens, class Base>
 __global__ void __launch_bounds__(kLightBlock, kMediumWaves) glow_render_kernel(const KParams P, const GlowLit<Base> T, const LensCam C) {
     lit_render_body<kLens>(P, T, C);
 }
-// (no adaptive call takes a glow: there is no list variant)
+// the list variant: rt_render_fog_adaptive's rounds under a glow (DESIGN.md §40) — the same body on a list whose length lives on the device
+template <bool kLens, class Base>
+__global__ void __launch_bounds__(kLightBlock, kMediumWaves) glow_list_render_kernel(const KParams P, const GlowLit<Base> T, const LensCam C) {
+    lit_render_body<kLens, GlowLit<Base>, true>(P, T, C);
+}
 template <bool kLens, class Base> const void *lit_frame_kernel_of(const GlowLit<Base> &) { return (const void *)glow_render_kernel<kLens, Base>; }
-template <bool kLens, class Base> const void *lit_list_kernel_of(const GlowLit<Base> &) { return nullptr; }
+template <bool kLens, class Base> const void *lit_list_kernel_of(const GlowLit<Base> &) { return (const void *)glow_list_render_kernel<kLens, Base>; }
 
 }  // namespace rtk

@@ -297,9 +297,18 @@ __global__ void __launch_bounds__(256) glow_sample_probe_kernel(const KParams P,
 // verdict ends the path (no_next_ray).  Across the walks a lane holds, beyond lit_render_body's, the glow sample's direction, f and
 // throughput (seven registers) and pend.
 constexpr int32_t kGlowShadow = 5;
-template <bool kLens, class Table>
+// kList (rt_render_fog_adaptive's rounds; DESIGN.md §40) as in lit_render_body: the work indices are the first *P.work_count entries of
+// P.work_list, a length read once per wave; an empty list leaves before the first atomic, and a fetched index stands for its list entry
+// in map_work and in store_sample alike.
+template <bool kLens, class Table, bool kList = false>
 __device__ __forceinline__ void glow_sample_render_body(const KParams &P, const GlowSampleLit<Table> &T, const LensCam &C) {
     using Lit = GlossLit<Table>;
+    [[maybe_unused]] uint32_t listed = 0u;          // (wave-uniform; kList only)
+    if constexpr (kList) {
+        listed = (uint32_t)__builtin_amdgcn_readfirstlane((int32_t)*P.work_count);
+        if (listed > P.work_cap) listed = P.work_cap;          // (never more entries than the list has room for)
+        if (listed == 0u) return;
+    }
     const int lane = (int)(threadIdx.x & (kWave - 1));
     Lane L;
     L.node = kBlocked;
@@ -324,7 +333,11 @@ __device__ __forceinline__ void glow_sample_render_body(const KParams &P, const 
     uint32_t pool_next = 0, pool_end = 0;  // (wave-uniform)
     bool exhausted = false;
     for (;;) {
-        RTP_LIT_POOL_FETCH(P.total_work, mine)
+        if constexpr (kList) {
+            RTP_LIT_POOL_FETCH(listed, P.work_list[mine])
+        } else {
+            RTP_LIT_POOL_FETCH(P.total_work, mine)
+        }
         const bool busy = phase != kLightIdle;
         if (!__any(busy)) {
             if (exhausted) break;
@@ -392,8 +405,12 @@ template <bool kLens, class Table>
 __global__ void __launch_bounds__(kLightBlock, kMediumWaves) glow_sample_render_kernel(const KParams P, const GlowSampleLit<Table> T, const LensCam C) {
     glow_sample_render_body<kLens>(P, T, C);
 }
-// (no adaptive call takes a glow: there is no list variant)
+// the list variant: rt_render_fog_adaptive's rounds with light samples of the glow (DESIGN.md §40)
+template <bool kLens, class Table>
+__global__ void __launch_bounds__(kLightBlock, kMediumWaves) glow_sample_list_render_kernel(const KParams P, const GlowSampleLit<Table> T, const LensCam C) {
+    glow_sample_render_body<kLens, Table, true>(P, T, C);
+}
 template <bool kLens, class Table> const void *lit_frame_kernel_of(const GlowSampleLit<Table> &) { return (const void *)glow_sample_render_kernel<kLens, Table>; }
-template <bool kLens, class Table> const void *lit_list_kernel_of(const GlowSampleLit<Table> &) { return nullptr; }
+template <bool kLens, class Table> const void *lit_list_kernel_of(const GlowSampleLit<Table> &) { return (const void *)glow_sample_list_render_kernel<kLens, Table>; }
 
 }  // namespace rtk

@@ -173,6 +173,9 @@ struct FrameJob {
     const rt_volume *heat = nullptr;               // the grid of glow's source 2 (--fog-heat)
     const rt_glow_sample_params *glow_sample = nullptr;          // with glow and volume, --fog-glow-sample: through rt_render_glow_sampled …
     const rt_glow_sampler *sampler = nullptr;                    // … with the sampler of these grids
+    // with medium, --fog-adaptive: through rt_render_fog_adaptive with volume, chroma, glow, heat, glow_sample and sampler as they stand
+    // here, and rt_tonemap_spp; without a stop rule or a prior
+    const rt_adaptive_params *fog_adaptive = nullptr;
 };
 // rtp_main --gpu --lens R:F / --motion-blur S / --nee / --env / --lit: the orbit frame after frame on one GPU through the render call the
 // job's members pick (rt_render_lens when none does), saved with rt_tonemap

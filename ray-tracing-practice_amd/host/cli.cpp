@@ -55,7 +55,7 @@ bool threshold_alone(const std::string &value, float &out) {
 struct Pass {
     std::map<std::string, int> at;          // element → its last index; "--denoise*": the last element that begins with --denoise
     std::string denoise_word, env_dash_word;          // that element; the last element that begins with --env-
-    std::string glow_bad, tint_bad, fog_noise_bad, noise_bad, fog_bad, env_bad;
+    std::string glow_bad, tint_bad, fog_noise_bad, fog_adaptive_bad, noise_bad, fog_bad, env_bad;
     bool nee_bad = false, lens_bad = false, adaptive_spp_bad = false;
     bool glow_by_density = false, adaptive_valued = false, shard_valued = false;
     bool env_mode_path = false;          // some --env-mode says path (for --glossy: any of them counts, not the last)
@@ -111,18 +111,20 @@ void read_values(int argc, const char *const *argv, const char *rtp_devices, Cli
             if (!three_not_negative(rgb, cli.fog_glow_radiance)) p.glow_bad = "--fog-glow takes R,G,B[:density]: three finite numbers, none negative";
         }
         if (arg == "--fog-tint" && !three_not_negative(value, cli.fog_tint_rgb)) p.tint_bad = "--fog-tint takes R,G,B: three finite numbers, none negative";
-        if (arg == "--fog-noise-target") {
+        if (arg == "--fog-noise-target" || arg == "--fog-adaptive") {          // one value grammar for both
+            const bool rungs = arg == "--fog-adaptive";
+            float &threshold = rungs ? cli.fog_adaptive_threshold : cli.fog_noise_threshold;
             char *end = nullptr;
-            cli.fog_noise_threshold = strtof(value.c_str(), &end);
-            bool ok = end != value.c_str() && std::isfinite(cli.fog_noise_threshold) && cli.fog_noise_threshold >= 0.0f;
+            threshold = strtof(value.c_str(), &end);
+            bool ok = end != value.c_str() && std::isfinite(threshold) && threshold >= 0.0f;
             if (ok && *end == ':') {
-                CliSpp &s = cli.fog_noise_spp;
+                CliSpp &s = rungs ? cli.fog_adaptive_spp : cli.fog_noise_spp;
                 s.given = true;
                 ok = sscanf(end + 1, "%d:%d:%d%c", &s.min_spp, &s.batch_spp, &s.max_spp, &tail) == 3 && spp_in_range(s);
             } else if (ok) {
                 ok = *end == 0;
             }
-            if (!ok) p.fog_noise_bad = "--fog-noise-target takes T[:min:batch:max] with T finite and not negative, min >= 2, batch >= 1 and min <= max <= 65536";
+            if (!ok) (rungs ? p.fog_adaptive_bad : p.fog_noise_bad) = arg + " takes T[:min:batch:max] with T finite and not negative, min >= 2, batch >= 1 and min <= max <= 65536";
         }
         if (arg == "--noise-target" && !threshold_alone(value, cli.noise_threshold)) p.noise_bad = "--noise-target takes a finite threshold that is not negative";
         if (arg == "--noise-spp") {
@@ -232,6 +234,7 @@ void read_values(int argc, const char *const *argv, const char *rtp_devices, Cli
     cli.fog_glow = p.has("--fog-glow");
     cli.fog_glow_sample = p.has("--fog-glow-sample");
     cli.fog_noise = p.has("--fog-noise-target");
+    cli.fog_adaptive = p.has("--fog-adaptive");
     cli.noise = p.has("--noise-target");
     cli.lens = p.has("--lens");
     cli.motion_blur = p.has("--motion-blur");
@@ -288,6 +291,13 @@ bool parse_cli(int argc, const char *const *argv, const char *rtp_devices, Cli &
     other = p.last_of({"--adaptive", "--denoise*", "--aov", "--stop-rule", "--stop-history", "--noise-target"});
     if (c.fog_noise && !other.empty())
         return refuse(99, "--fog-noise-target cannot be combined with " + other + " (not with --adaptive, --denoise*, --aov, --stop-rule, --stop-history or --noise-target)");
+    // --fog-adaptive (behind --fog-noise-target's block: what that flag refuses, it refuses under its own name)
+    if (!p.fog_adaptive_bad.empty()) return refuse(99, p.fog_adaptive_bad);
+    if (c.fog_adaptive && !(c.fog && c.lit)) return refuse(99, "--fog-adaptive sets the noise target of fogged frames, tinted and glowing ones too: it needs --lit --fog SIGMA");
+    other = p.last_of({"--fog-noise-target", "--fog-denoise", "--adaptive", "--denoise*", "--aov", "--stop-rule", "--stop-history", "--noise-target"});
+    if (c.fog_adaptive && !other.empty())
+        return refuse(99, "--fog-adaptive cannot be combined with " + other +
+                              " (not with --fog-noise-target, --fog-denoise, --adaptive, --denoise*, --aov, --stop-rule, --stop-history or --noise-target)");
     // --denoise-adaptive-temporal, --stop-history, --denoise-adaptive, --stop-rule: exit code 2
     if (c.denoise_adaptive_temporal && (c.denoise || c.denoise_temporal || c.aov || env_devices || many || p.any({"--denoise-adaptive", "--lens", "--motion-blur"})))
         return refuse(2, "--denoise-adaptive-temporal writes <frame>.denoised from pinhole frames and AOVs of its own on one GPU: it cannot "

@@ -19,6 +19,7 @@
 //     --fog-tint R,G,B                          rt_render_chroma
 //     --fog-glow R,G,B[:density] [--fog-heat FILE] [--fog-glow-sample mis|light]               rt_render_glow / rt_render_glow_sampled
 //     --fog-noise-target T[:min:batch:max]      rt_render_volume_adaptive
+//     --fog-adaptive T[:min:batch:max]          rt_render_fog_adaptive: a noise target with --fog-tint, --fog-glow, --fog-glow-sample too
 //     --fog-denoise                             the fogged frame filtered under rt_render_aov_volume's AOVs
 #pragma once
 #include <string>
@@ -28,7 +29,7 @@
 
 namespace rtp {
 
-// min:batch:max of --adaptive-spp, --noise-spp and --fog-noise-target T:min:batch:max; not given: rt_adaptive_params_init's triple stands
+// min:batch:max of --adaptive-spp, --noise-spp and --fog-noise-target / --fog-adaptive T:min:batch:max; not given: rt_adaptive_params_init's triple stands
 struct CliSpp {
     bool given = false;
     int min_spp = 0, batch_spp = 0, max_spp = 0;
@@ -48,7 +49,7 @@ struct Cli {
     // the flags that are on (each: the element is somewhere in argv)
     bool aov = false, denoise = false, denoise_temporal = false, denoise_adaptive = false, denoise_adaptive_temporal = false;
     bool stop_history = false, lit = false, glossy = false, light_tree = false, nee = false, env = false;
-    bool fog = false, fog_denoise = false, fog_tint = false, fog_glow = false, fog_glow_sample = false, fog_noise = false, noise = false;
+    bool fog = false, fog_denoise = false, fog_tint = false, fog_glow = false, fog_glow_sample = false, fog_noise = false, fog_adaptive = false, noise = false;
     bool lens = false, motion_blur = false;
 
     int stop_rule = 0;                                      // --stop-rule: 0 own (default), 1 near
@@ -63,6 +64,8 @@ struct Cli {
     int fog_glow_sample_mis = 1;                            // --fog-glow-sample mis (1) | light (0)
     float fog_noise_threshold = 0.0f, noise_threshold = 0.0f, adaptive_threshold = 0.0f;          // (read when fog_noise / noise / driver adaptive)
     CliSpp fog_noise_spp, noise_spp, adaptive_spp;
+    float fog_adaptive_threshold = 0.0f;                    // --fog-adaptive T[:min:batch:max] (read when fog_adaptive)
+    CliSpp fog_adaptive_spp;
     // --env FILE[:N] --env-mode --env-scale --env-up (read when env)
     std::string env_file;
     int env_n = 1024;

@@ -81,6 +81,8 @@ int render_lens(const rtp::SceneParams &params, const rt_scene_desc &desc, const
     rt_adaptive_params noise;
     if (cli.fog_noise) set_adaptive(noise, cli.fog_noise_threshold, cli.fog_noise_spp);
     else set_adaptive(noise, cli.noise_threshold, cli.noise_spp);
+    rt_adaptive_params fog_adaptive;
+    set_adaptive(fog_adaptive, cli.fog_adaptive_threshold, cli.fog_adaptive_spp);
     rt_stop_params stop;
     rt_stop_params_init(&stop);
     stop.rule = cli.stop_rule;
@@ -120,6 +122,7 @@ int render_lens(const rtp::SceneParams &params, const rt_scene_desc &desc, const
         job.heat = heat;
         job.glow_sample = cli.fog_glow_sample ? &glow_sample : nullptr;
         job.sampler = sampler;
+        job.fog_adaptive = cli.fog_adaptive ? &fog_adaptive : nullptr;
     } else if (cli.env) {
         job.env = env;
         job.env_params = &ep;

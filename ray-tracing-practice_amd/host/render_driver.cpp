@@ -340,7 +340,8 @@ void gpu_render_pipelined(const SceneParams &params, const rt_scene_desc &desc, 
 // rt_render_lit_adaptive and rt_tonemap_spp — every pixel's bytes at its own sample count — and the printed count is the samples taken
 // medium (with lit, without noise; rtp_main --lit --fog): through rt_render_medium; volume (with medium; rtp_main --fog-grid,
 // DESIGN.md §28): through rt_render_volume with this grid in the medium's box.  medium with noise (rtp_main --fog-noise-target, DESIGN.md
-// §29): through rt_render_volume_adaptive (the volume may be null) and rt_tonemap_spp, without a stop rule or a prior.
+// §29): through rt_render_volume_adaptive (the volume may be null) and rt_tonemap_spp, without a stop rule or a prior.  medium with
+// fog_adaptive (rtp_main --fog-adaptive): the same through rt_render_fog_adaptive, under chroma, glow and glow_sample too.
 // fog_denoise (with medium; rtp_main --fog-denoise): denoise — or with noise denoise_adaptive — with the AOVs from
 // rt_render_aov_volume under the frame's own lit, medium and volume.
 // denoise_adaptive (with noise; rtp_main --denoise-adaptive): as in gpu_render_adaptive, the AOVs from rt_render_aov_lens at noise->min_spp
@@ -353,7 +354,8 @@ void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const
     const rt_nee_params *nee = job.nee;
     const rt_env *env = job.env;
     const rt_lit_params *lit = job.lit;
-    const rt_adaptive_params *noise = job.noise;
+    // the adaptive parameters of the job's frames, whichever flag gave them (the counts, rt_tonemap_spp and the denoisers read these)
+    const rt_adaptive_params *noise = job.fog_adaptive ? job.fog_adaptive : job.noise;
     const rt_medium_params *medium = job.medium;
     const rt_volume *volume = job.volume;
     const bool denoise = job.denoise || (fog_denoise && !noise), denoise_adaptive = job.denoise_adaptive || (fog_denoise && noise);
@@ -428,7 +430,18 @@ void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const
                                                    spp_denoiser->d_prior));
         } else if (lit && noise) {
             const rt_lit_params lit_now = frame_lit(cam_close);
-            if (medium)          // (rtp_main --fog-noise-target: no stop rule, no prior; the moments for --fog-denoise)
+            if (medium && job.fog_adaptive) {          // (rtp_main --fog-adaptive: the rung by the job's members; no stop rule, no prior)
+                rt_fog_params fog;
+                rt_fog_params_init(&fog);
+                fog.medium = medium;
+                fog.volume = volume;
+                fog.chroma = job.chroma;
+                fog.glow = job.glow;
+                fog.heat = job.heat;
+                fog.sample = job.glow ? job.glow_sample : nullptr;
+                fog.sampler = job.sampler;
+                RTP_CHECK(rt_render_fog_adaptive(scene, &cam, &lit_now, &fog, noise, nullptr, nullptr, nullptr, 0, d_fb, d_spp, nullptr, nullptr, 1, nullptr));
+            } else if (medium)          // (rtp_main --fog-noise-target: no stop rule, no prior; the moments for --fog-denoise)
                 RTP_CHECK(rt_render_volume_adaptive(scene, &cam, &lit_now, medium, volume, noise, nullptr, nullptr, nullptr, 0, d_fb, d_spp,
                                                     spp_denoiser ? spp_denoiser->d_moments : nullptr, nullptr, 1, nullptr));
             else

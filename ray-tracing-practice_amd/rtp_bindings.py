@@ -549,6 +549,42 @@ def _volume_handle(volume):
     return volume._h
 
 
+class FogParams(_Sized):
+    """rt_fog_params (include/rtp_amd.h, "adaptive sampling on every fog rung"): what a fog call is made of, by pointers — an IN structure
+    of the caller's size.  struct_bytes is set on construction; every pointer is NULL until fog_params() sets it."""
+    _fields_ = [("struct_bytes", C.c_uint32), ("medium", C.POINTER(MediumParams)), ("volume", C.c_void_p), ("chroma", C.POINTER(ChromaParams)),
+                ("glow", C.POINTER(GlowParams)), ("heat", C.c_void_p), ("sample", C.POINTER(GlowSampleParams)), ("sampler", C.c_void_p)]
+
+
+def fog_params(medium=None, volume=None, tint=None, glow=None, heat=None, sample=None, sampler=None):
+    """rt_fog_params with the library's defaults (every pointer NULL), then the given parts: medium, tint, glow and sample as
+    render_medium, render_chroma, render_glow and render_glow_sampled take them; volume and heat a Volume, sampler a GlowSampler.  The
+    structure keeps what it points to alive.  Nothing is checked here: the library refuses what it does not take."""
+    p = _params(FogParams, "rt_fog_params", (), {})
+    keep = []
+
+    def point(field, kind, value):
+        keep.append(value)
+        setattr(p, field, C.cast(C.pointer(value), C.POINTER(kind)))
+    if medium is not None:
+        point("medium", MediumParams, medium if isinstance(medium, MediumParams) else medium_params(**medium))
+    if tint is not None:
+        point("chroma", ChromaParams, tint if isinstance(tint, ChromaParams) else chroma_params(**tint) if isinstance(tint, dict) else chroma_params(tint=tint))
+    if glow is not None:
+        point("glow", GlowParams, glow if isinstance(glow, GlowParams) else glow_params(**glow) if isinstance(glow, dict) else glow_params(radiance=glow))
+    if sample is not None:
+        if isinstance(sample, str):
+            sample = glow_sample_params(sample=1, mis={"mis": 1, "light": 0}[sample])
+        point("sample", GlowSampleParams, sample if isinstance(sample, GlowSampleParams) else glow_sample_params(**sample))
+    for field, handle, value in (("volume", _volume_handle, volume), ("heat", _volume_handle, heat), ("sampler", _sampler_handle, sampler)):
+        h = handle(value)
+        if h is not None:
+            keep.append(value)
+            setattr(p, field, h if isinstance(h, int) else C.cast(h, C.c_void_p).value)
+    p._keep = keep
+    return p
+
+
 TRAVERSAL_AUTO, TRAVERSAL_EXACT, TRAVERSAL_GUARDED = 0, 1, 2
 BUILD_HOST_SAH, BUILD_DEVICE_LBVH = 0, 1
 KERNEL_AUTO, KERNEL_MEGA, KERNEL_WAVEFRONT = 0, 1, 2
@@ -597,6 +633,7 @@ _STATUS = C.c_int
 _DESC, _CFG, _CAM, _SHARD, _TIMING, _AOV = _P(SceneDesc), _P(Config), _P(CameraData), _P(Shard), _P(Timing), _P(AovBuffers)
 _DENOISE, _ADAPTIVE, _STOP, _LENS, _NEE, _ENV = _P(DenoiseParams), _P(AdaptiveParams), _P(StopParams), _P(LensParams), _P(NeeParams), _P(EnvParams)
 _LIT, _MEDIUM, _CHROMA, _GLOW, _GLOW_SAMPLE = _P(LitParams), _P(MediumParams), _P(ChromaParams), _P(GlowParams), _P(GlowSampleParams)
+_FOG = _P(FogParams)
 _OUT = [_VP, _I32, _TIMING]          # how a render call ends: void *hip_stream, int32_t sync, rt_timing *timing
 
 # the calls every build has: a library without one of them fails at load
@@ -699,6 +736,8 @@ _AMD_LATER = {
     "rt_glow_sampler_table": (_STATUS, [_VP, _I32, _I32] + [_VP] * 4 + [_P(_I32)]),
     "rt_render_glow_sampled": (_STATUS, [_VP, _CAM, _LIT, _MEDIUM, _VP, _GLOW, _VP, _GLOW_SAMPLE, _VP, _SHARD, _I32, _VP, *_OUT]),
     "rt_trace_samples_glow_sampled": (_STATUS, [_VP, _CAM, _LIT, _MEDIUM, _VP, _GLOW, _VP, _GLOW_SAMPLE, _VP, _I32] + [_VP] * 11),
+    "rt_fog_params_init": (None, [_FOG]),
+    "rt_render_fog_adaptive": (_STATUS, [_VP, _CAM, _LIT, _FOG, _ADAPTIVE, _STOP, _VP, _SHARD, _I32, _VP, _VP, _VP, *_OUT]),
 }
 # the calls that take a prior: their _rule call (the judgement: the call itself) and, last, the device address of the prior
 for _base, _prior in (("rt_render_adaptive_rule", "rt_render_adaptive_prior"), ("rt_render_lit_adaptive_rule", "rt_render_lit_adaptive_prior"),
@@ -1641,6 +1680,27 @@ class DeviceScene:
                                                        _volume_handle(heat), _glow_sample_struct(sample), _sampler_handle(sampler), n, ijs.ctypes.data,
                                                        *(a.ctypes.data for a in out)), "rt_trace_samples_glow_sampled")
         return out
+
+    def render_fog_adaptive(self, cam, d_fb_ptr, d_spp_ptr, d_moments_ptr=None, *, medium=None, volume=None, tint=None, glow=None, heat=None,
+                            sample=None, sampler=None, cam_close=None, lens=None, emitters=True, nee=None, env=None, env_params=None, shard=None,
+                            stream=None, sync=True, sample_first=0, prior=None, **params):
+        """rt_render_fog_adaptive: render_volume_adaptive's rounds on the estimator of the fog call the keywords name — tint as
+        render_chroma takes it, glow and heat as render_glow, sample and sampler as render_glow_sampled; a tint goes with neither a glow
+        nor a sample.  The other keywords and the device addresses are render_volume_adaptive's.  Returns the rt_timing of this call."""
+        rule = params.pop("rule", None)
+        p = adaptive_params(**params)
+        lit = lit_params(cam_close=cam_close, lens=lens, emitters=emitters, nee=nee, env=env, env_params=env_params)
+        fog = fog_params(medium=medium, volume=volume, tint=tint, glow=glow, heat=heat, sample=sample, sampler=sampler)
+        stop = None if rule is None else C.byref(stop_params(rule=rule))
+        return self._call("rt_render_fog_adaptive", C.byref(cam), C.byref(lit), C.byref(fog), C.byref(p), stop, C.c_void_p(prior or 0), _ref(shard),
+                          sample_first, C.c_void_p(d_fb_ptr), C.c_void_p(d_spp_ptr), C.c_void_p(d_moments_ptr or 0), *_stream_sync(stream, sync))
+
+    def render_fog_adaptive_to_host(self, cam, *, medium=None, volume=None, tint=None, glow=None, heat=None, sample=None, sampler=None, cam_close=None,
+                                    lens=None, emitters=True, nee=None, env=None, env_params=None, shard=None, sample_first=0, prior=None, **params):
+        """rt_render_fog_adaptive through fresh device buffers: render_volume_adaptive_to_host's (fb, spp, moments, rt_timing)."""
+        return _adaptive_to_host(cam, shard, prior, lambda d_fb, d_spp, d_moments, d_prior: self.render_fog_adaptive(
+            cam, d_fb, d_spp, d_moments, medium=medium, volume=volume, tint=tint, glow=glow, heat=heat, sample=sample, sampler=sampler, cam_close=cam_close,
+            lens=lens, emitters=emitters, nee=nee, env=env, env_params=env_params, shard=shard, sample_first=sample_first, prior=d_prior, **params))
 
     def last_kernel_ms(self):
         ms = C.c_float()
