@@ -435,6 +435,16 @@ uint64_t rt_denoise_workspace_bytes(int32_t width, int32_t height);
  * call. */
 rt_status rt_denoise(const float *d_fb_sum, const rt_aov_buffers *aov, int32_t width, int32_t height, int32_t samples_per_pixel,
                      const rt_denoise_params *params, void *d_workspace, uint64_t workspace_bytes, float *d_out, void *hip_stream);
+/* rt_denoise of the two frames rt_render_lit_split writes, filtered separately with the same guides and parameters and added:
+ * d_out = rt_denoise(d_direct_sum) + rt_denoise(d_indirect_sum) per channel, bit for bit (float32, one add).  rt_denoise's launches run
+ * once per component, then one kernel adds.  The workspace holds rt_denoise's and one frame behind it:
+ * rt_denoise_split_workspace_bytes = rt_denoise_workspace_bytes + 12 bytes per pixel (0 when width or height is below 1).
+ * Checks: RT_ERR_INVALID_ARG for a NULL d_direct_sum or d_indirect_sum, then rt_denoise's own in its order — each input, d_out and the
+ * workspace of the larger size stand where rt_denoise's stand.  The two inputs may be the same buffer.  Every check comes before any HIP call. */
+uint64_t rt_denoise_split_workspace_bytes(int32_t width, int32_t height);
+rt_status rt_denoise_split(const float *d_direct_sum, const float *d_indirect_sum, const rt_aov_buffers *aov, int32_t width, int32_t height,
+                           int32_t samples_per_pixel, const rt_denoise_params *params, void *d_workspace, uint64_t workspace_bytes, float *d_out,
+                           void *hip_stream);
 
 /* ---- temporal denoising: SVGF's reprojected history across the frames of an animation ----------------------------------------
  * rt_denoise's filter fed with colour and luminance moments accumulated over earlier frames (Schied et al. 2017, §4.1-4.2): each hit
@@ -1051,6 +1061,36 @@ rt_status rt_render_lit(rt_scene *scene, const rt_camera_data *cam_open, const r
  * shadow ray of either kind), the path's final RNG state and both light streams' final states per (i, j, s). */
 rt_status rt_trace_samples_lit(rt_scene *scene, const rt_camera_data *cam_open, const rt_lit_params *lit, int32_t n, const int32_t *ijs,
                                float *radiance, int32_t *rays, uint32_t *final_seed, uint32_t *final_nee_seed, uint32_t *final_env_seed);
+
+/* ---- direct and indirect light in separate frames --------------------------------------------------------------------
+ * rt_render_lit's sample, its radiance written as two components.  The split draws nothing and changes no branch: rays, the path and the
+ * nee and env streams are rt_render_lit's under the same lit.
+ *   A sample of rt_render_lit is a sum of non-negative contributions, added in a fixed order: a vertex's emission or the miss term, then
+ *   the verdicts of the light samples taken at that vertex (the emitter's, then the environment's).
+ *   A diffuse event is a vertex that scatters diffusely: LAMBERTIAN, and METAL's 20 % branch.  METAL's reflect branch (any fuzz, glossy
+ *   event or not) and DIELECTRIC are not diffuse events.
+ *   A path has a stage.  0: no diffuse event yet; 1: the last vertex was the path's first diffuse event; 2: crossed.  The vertex that the
+ *   ray leaving the first diffuse event finds adds its emission or miss term, MIS weight included, while still in stage 1; immediately
+ *   after that add the path crosses.
+ *   Every contribution added before the crossing is DIRECT: lamps and sky seen directly, in mirrors or through glass; the light samples of
+ *   glossy events before the first diffuse event; both light samples of the first diffuse event; what its BSDF ray finds.  Every
+ *   contribution added after the crossing is INDIRECT.  A path that ends before it crosses is all direct.  Both halves of every MIS pair
+ *   land in the same component, and the definition depends on no switch (mis, sample_planes, select, glossy, the environment's mode).
+ *   Each component is summed in float32 in rt_render_lit's order, from zero: direct is the sample's radiance when the path crosses (or
+ *   ends), indirect what is added from zero after the crossing.  So with max_depth <= 2 direct is rt_render_lit's sample bit for bit and
+ *   indirect is 0; in general direct + indirect differs from it only by the order of summing at most 3 * max_depth + 1 non-negative
+ *   floats.
+ * rt_render_lit_split: d_direct_sum and d_indirect_sum (DEVICE, 3 floats per local pixel each, like d_fb_sum) receive each component's
+ * sum over samples sample_first … sample_first + spp - 1, added strictly in sample order.  Checks: rt_render_lit's, in its order; then
+ * RT_ERR_INVALID_ARG for either output NULL or the two overlapping.  Rows of a shard only.  Handle state and timing: as rt_render_lit.
+ * rt_config.pass_spp and workspace_bytes are honoured; the pass's slab holds both components, so a given budget admits half the samples
+ * per pass.  No samples or no depth: both frames zero.
+ * rt_trace_samples_lit_split: rt_trace_samples_lit's probe (HOST memory) with the radiance in two columns, direct and indirect. */
+rt_status rt_render_lit_split(rt_scene *scene, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_shard *shard,
+                              int32_t sample_first, float *d_direct_sum, float *d_indirect_sum, void *hip_stream, int32_t sync, rt_timing *timing);
+rt_status rt_trace_samples_lit_split(rt_scene *scene, const rt_camera_data *cam_open, const rt_lit_params *lit, int32_t n, const int32_t *ijs,
+                                     float *direct, float *indirect, int32_t *rays, uint32_t *final_seed, uint32_t *final_nee_seed,
+                                     uint32_t *final_env_seed);
 
 /* ---- adaptive sampling on the lit path ----------------------------------------------------------------------------
  * rt_render_adaptive's rounds on rt_render_lit's estimator.  No new arithmetic: the sample is the section above's, the statistics and

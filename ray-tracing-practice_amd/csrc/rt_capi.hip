@@ -20,6 +20,7 @@
 #include "rt_nee.hip.inc"
 #include "rt_env.hip.inc"
 #include "rt_light.hip.inc"
+#include "rt_split.hip.inc"
 #include "rt_medium.hip.inc"
 #include "rt_volume.hip.inc"
 #include "rt_glow.hip.inc"
@@ -830,13 +831,15 @@ rt_status acquire_feedback(rt_scene *sc, rt_scene::Feedback **out) {
 // only padded to the 16 bytes the accumulate kernels' row reads need (a 4K frame at 1 spp: 0.4 GB instead of 3.2 GB)
 uint32_t slab_pitch_of(int pass) { return pass < 32 ? (uint32_t)((pass + 3) & ~3) : (uint32_t)((pass + 31) & ~31); }
 // The passes of a call (rt_accel.h, plan_passes) and a slab that holds one of them: three floats per (local pixel, slot)
-rt_status reserve_slab(rt_scene *sc, uint32_t num_pixels, int32_t spp, hipStream_t stream, rtaccel::PassPlan &plan) {
+// (slabs: how many of them lie side by side — rt_render_lit_split's two: the budget, given or derived, is shared between them)
+rt_status reserve_slab(rt_scene *sc, uint32_t num_pixels, int32_t spp, hipStream_t stream, rtaccel::PassPlan &plan, uint32_t slabs = 1) {
     const rt_config &cfg = sc->cfg;
-    plan = rtaccel::plan_passes(num_pixels, spp, cfg.workspace_bytes, sc->device_bytes, cfg.pass_spp);
+    const uint64_t budget = cfg.workspace_bytes ? (cfg.workspace_bytes / slabs ? cfg.workspace_bytes / slabs : 1) : 0;
+    plan = rtaccel::plan_passes(num_pixels, spp, budget, sc->device_bytes / slabs, cfg.pass_spp);
     if (plan.passes < 1) return fail(RT_ERR_UNSUPPORTED, "image too large for the work index arithmetic");
     if (plan.passes > kMaxPasses) return fail(RT_ERR_UNSUPPORTED, "more than 1024 passes (samples_per_pixel above 65536, or above 64512 at 2^24 pixels)");
     int pass_size = plan.pass_size;
-    size_t need = (size_t)num_pixels * (size_t)slab_pitch_of(pass_size) * 3;
+    size_t need = (size_t)num_pixels * (size_t)slab_pitch_of(pass_size) * 3 * slabs;
     if (sc->slab_floats < need) {
         HIP_TRY(hipStreamSynchronize(stream));
         (void)hipFree(sc->slab);
@@ -849,7 +852,7 @@ rt_status reserve_slab(rt_scene *sc, uint32_t num_pixels, int32_t spp, hipStream
             if (e != hipErrorOutOfMemory || pass_size <= 64) HIP_TRY(e);
             pass_size = pass_size / 2 < 64 ? 64 : pass_size / 2;
             plan = rtaccel::PassPlan::uniform(spp, pass_size);      // (shorter than before: within the bound too)
-            need = (size_t)num_pixels * (size_t)slab_pitch_of(pass_size) * 3;
+            need = (size_t)num_pixels * (size_t)slab_pitch_of(pass_size) * 3 * slabs;
         }
         sc->slab_floats = need;
     }
@@ -1261,13 +1264,14 @@ const void *lens_trace_kernel(const LaunchPlan &L) {
 }
 
 // (second: the second kernel argument — render_lens_kernel's LensCam, a lit trace kernel's light table; null for render_kernel.
-// third: lit_render_kernel's LensCam behind its light; null for every other kernel)
+// third: lit_render_kernel's LensCam behind its light; null for every other kernel.  fourth: lit_split_render_kernel's second slab behind
+// that — the address of the pointer; null for every other kernel)
 hipError_t launch(const void *kernel, uint32_t block, int grid, uint32_t lds, hipStream_t stream, const rtk::KParams &KP, const void *second = nullptr,
-                  const void *third = nullptr) {
+                  const void *third = nullptr, const void *fourth = nullptr) {
     hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     void *args[] = {(void *)&KP};
-    void *more_args[] = {(void *)&KP, (void *)second, (void *)third};
+    void *more_args[] = {(void *)&KP, (void *)second, (void *)third, (void *)fourth};
     e = hipLaunchKernel(kernel, dim3(grid), dim3(block), second ? more_args : args, lds, stream);
     const hipError_t last = hipGetLastError();
     return e != hipSuccess ? e : last;
@@ -3343,6 +3347,112 @@ rt_status rt_trace_samples_lit(rt_scene *sc, const rt_camera_data *cam_open, con
             return RT_OK;
         });
     });
+}
+
+// ---- rt_render_lit_split / rt_trace_samples_lit_split (rtp_amd.h): rt_render_lit's sample in two components.  The frame
+// is render_light_impl's with two slabs side by side in the handle's one (the second is an argument of the split kernels alone: KParams is
+// what it was) and an accumulate per component.
+rt_status rt_render_lit_split(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, const rt_shard *shard, int32_t sample_first,
+                              float *d_direct_sum, float *d_indirect_sum, void *hip_stream, int32_t sync, rt_timing *timing) {
+    const char *what = "rt_render_lit_split";
+    LitSetup S;
+    if (const rt_status st = lit_setup(what, cam_open, lit, S)) return st;
+    if (!sc) return fail(RT_ERR_INVALID_ARG, "rt_render_lit_split: null scene");
+    Frame F;
+    rt_status st = frame_prologue(what, sc, cam_open, shard, nullptr, sample_first, S.env ? &S.env->device : nullptr, nullptr, hip_stream, timing, F, [&]() -> rt_status {
+        if (const rt_status late = refuse_retired(sc->cfg)) return late;
+        if (!d_direct_sum || !d_indirect_sum) return fail(RT_ERR_INVALID_ARG, "rt_render_lit_split: null framebuffer");
+        const uintptr_t a = (uintptr_t)d_direct_sum, b = (uintptr_t)d_indirect_sum, bytes = (uintptr_t)F.num_pixels * 12;
+        if (a == b || (a < b + bytes && b < a + bytes)) return fail(RT_ERR_INVALID_ARG, "rt_render_lit_split: d_direct_sum and d_indirect_sum overlap");
+        return RT_OK;
+    });
+    if (st != RT_OK) return st;
+    if (F.nothing_to_do()) return RT_OK;
+    rtk::KParams &P = F.P;
+    const hipStream_t stream = F.stream;
+    const uint32_t num_pixels = F.num_pixels;
+    if (P.spp <= 0 || P.max_depth <= 0) {
+        HIP_TRY(hipMemsetAsync(d_direct_sum, 0, (size_t)num_pixels * 3 * sizeof(float), stream));
+        return blank_frame(d_indirect_sum, F, sync);
+    }
+    return with_lit(sc, S, [&](const auto &T) -> rt_status {
+        const void *kernel = S.lens ? rtk::lit_split_kernel_of<true>(T) : rtk::lit_split_kernel_of<false>(T);
+        rtaccel::PassPlan passes;
+        if ((st = reserve_slab(sc, num_pixels, P.spp, stream, passes, 2)) != RT_OK) return st;
+        bind_slab(sc, P, num_pixels, passes.pass_size);
+        P.fb = d_direct_sum;
+        float *second = sc->slab + (size_t)num_pixels * (size_t)P.slab_pitch * 3;
+        rtk::KParams Q = P;          // the indirect component's accumulate: the second slab into its own sums
+        const int wgs = sc->num_cus * light_wgs_per_cu(kernel);
+        rt_timing t{};
+        kernel_resources(kernel, t.trace_vgprs, t.trace_scratch_bytes);
+        CallClock &clock = sc->clock[kClockLight];
+        if ((st = clock.make(kMaxPasses)) != RT_OK) return st;
+        HIP_TRY(hipMemsetAsync(clock.words, 0, kMaxPasses * 4, stream));
+        if ((st = clock.start(stream)) != RT_OK) return st;
+        for (int pass = 0; pass < passes.passes; ++pass) {
+            if ((st = set_pass(P, passes, pass, num_pixels, sample_first)) != RT_OK) return st;
+            P.queue = clock.words + pass;
+            const int grid = light_grid(wgs, P.total_work);
+            HIP_TRY(launch(kernel, (uint32_t)rtk::kLightBlock, grid, 0, stream, P, &T, &S.C, &second));
+            Q = P;
+            Q.fb = d_indirect_sum;
+            Q.slab = second;
+            launch_accumulate(stream, P, Acc::every_pixel(pass));
+            launch_accumulate(stream, Q, Acc::every_pixel(pass));
+            HIP_TRY(hipGetLastError());
+            if (pass == 0) t.num_workgroups = (uint32_t)grid;
+        }
+        if ((st = clock.stop(stream)) != RT_OK) return st;
+        t.workgroup_size = (uint32_t)rtk::kLightBlock;
+        t.trace_launches = (uint32_t)passes.passes;
+        t.kernel = RT_KERNEL_MEGA;
+        t.traced_samples = (uint64_t)num_pixels * (uint64_t)P.spp;
+        t.guard_paused = sc->guard_paused ? 1u : 0u;
+        if (sync) {
+            if ((st = clock.elapsed(t.kernel_ms)) != RT_OK) return st;
+            t.trace_ms = t.kernel_ms;
+        }
+        timing_out(t, timing);
+        return RT_OK;
+    });
+}
+
+rt_status rt_trace_samples_lit_split(rt_scene *sc, const rt_camera_data *cam_open, const rt_lit_params *lit, int32_t n, const int32_t *ijs, float *direct,
+                                     float *indirect, int32_t *rays, uint32_t *final_seed, uint32_t *final_nee_seed, uint32_t *final_env_seed) {
+    LitSetup S;
+    if (const rt_status st = lit_setup("rt_trace_samples_lit_split", cam_open, lit, S)) return st;
+    if (n < 0 || (n > 0 && (!ijs || !direct || !indirect || !rays || !final_seed || !final_nee_seed || !final_env_seed)))
+        return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_lit_split: null argument");
+    rtk::KParams P;
+    rt_status st = fill_params(sc, cam_open, nullptr, P);
+    if (st != RT_OK) return st;
+    if ((st = check_device(sc)) != RT_OK) return st;
+    if (S.env && S.env->device != sc->device)
+        return fail(RT_ERR_INVALID_ARG, "rt_trace_samples_lit_split: the environment was created on another device than the scene");
+    float *d_indirect = nullptr;
+    Scratch mem;
+    if (n > 0 && mem.alloc(d_indirect, (size_t)n * 12) != hipSuccess) return fail(RT_ERR_OUT_OF_MEMORY, "rt_trace_samples_lit_split: hipMalloc failed");
+    st = run_probe("rt_trace_samples_lit_split: ", P, cam_open, n, ijs, direct, rays, final_seed, final_nee_seed, final_env_seed,
+                   [&](const rtk::KParams &KP, uint32_t *d_nee, uint32_t *d_env) {
+        return with_lit(sc, S, [&](const auto &T) {
+            using Table = decltype(T.N);
+            const dim3 grid((n + 255) / 256), block(256);
+            if constexpr (rtk::kLitGlossy<std::decay_t<decltype(T)>>) {
+                if (S.lens) hipLaunchKernelGGL((rtk::lit_gloss_split_probe_kernel<true, Table>), grid, block, 0, 0, KP, T, S.C, d_nee, d_env, d_indirect);
+                else hipLaunchKernelGGL((rtk::lit_gloss_split_probe_kernel<false, Table>), grid, block, 0, 0, KP, T, S.C, d_nee, d_env, d_indirect);
+            } else {
+                if (S.lens) hipLaunchKernelGGL((rtk::lit_split_probe_kernel<true, Table>), grid, block, 0, 0, KP, T, S.C, d_nee, d_env, d_indirect);
+                else hipLaunchKernelGGL((rtk::lit_split_probe_kernel<false, Table>), grid, block, 0, 0, KP, T, S.C, d_nee, d_env, d_indirect);
+            }
+            return RT_OK;
+        });
+    });
+    if (st != RT_OK || n == 0) return st;
+    // (run_probe synchronised the device before it copied its own columns back)
+    if (hipMemcpy(indirect, d_indirect, (size_t)n * 12, hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(RT_ERR_HIP, "rt_trace_samples_lit_split: hipMemcpy D2H failed");
+    return RT_OK;
 }
 
 // ---- rt_render_medium / rt_trace_samples_medium and the fog calls above them: one setup (fog_setup), one light

@@ -43,6 +43,7 @@
 #include <cstdint>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "../../include/rtp_amd.h"
 #include "rt_device_math.h"
@@ -609,6 +610,61 @@ rt_status enqueue_steps(const Launch &l, const rt_denoise_params &prm, const flo
     return RT_OK;
 }
 
+// d_out = a + d_out per channel (rt_denoise_split: one float32 add of the two filtered components)
+__global__ __launch_bounds__(256) void denoise_add(const float *a, float *out, uint32_t floats) {
+    const uint32_t k = blockIdx.x * 256u + threadIdx.x;
+    if (k < floats) out[k] = a[k] + out[k];
+}
+
+// rt_denoise's checks, in its order, for a call `who` with nfb beauty inputs and a workspace of `need` bytes → the AOV buffers and parameters
+rt_status denoise_checks(const char *who, const float *const *fbs, int nfb, const rt_aov_buffers *aov, int32_t width, int32_t height, int32_t samples_per_pixel,
+                         const rt_denoise_params *params, const void *d_workspace, uint64_t workspace_bytes, uint64_t need, const float *d_out,
+                         rt_aov_buffers &b, rt_denoise_params &prm) {
+    const std::string w(who);
+    for (int k = 0; k < nfb; ++k)
+        if (!fbs[k]) return fail(RT_ERR_INVALID_ARG, w + ": null argument");
+    if (!aov || !d_workspace || !d_out) return fail(RT_ERR_INVALID_ARG, w + ": null argument");
+    // rt_aov_buffers grows: fields past struct_bytes count as NULL
+    rt_aov_buffers_init(&b);
+    const uint32_t ab = aov->struct_bytes < sizeof(b) ? aov->struct_bytes : (uint32_t)sizeof(b);
+    memcpy(&b, aov, ab);
+    if (ab < offsetof(rt_aov_buffers, hit_count) + sizeof(b.hit_count) || !b.albedo_sum || !b.normal_sum || !b.depth_sum || !b.hit_count)
+        return fail(RT_ERR_INVALID_ARG, w + ": albedo_sum, normal_sum, depth_sum and hit_count are required");
+    if (width < 1 || height < 1) return fail(RT_ERR_INVALID_ARG, w + ": width and height must be at least 1");
+    if (samples_per_pixel < 1 || samples_per_pixel > 65536) return fail(RT_ERR_INVALID_ARG, w + ": samples_per_pixel outside 1 … 65536");
+    const rt_status st = read_params(who, params, prm);
+    if (st != RT_OK) return st;
+    const uint64_t pixels = (uint64_t)width * (uint64_t)height;
+    if (pixels > (1ull << 24)) return fail(RT_ERR_UNSUPPORTED, w + ": more than 2^24 pixels");
+    if (workspace_bytes < need) return fail(RT_ERR_INVALID_ARG, w + ": workspace_bytes below " + w + "_workspace_bytes (" + std::to_string(need) + ")");
+    struct Input { const void *ptr; uint64_t bytes; };
+    std::vector<Input> inputs;          // the beauty inputs first, as rt_denoise always checked them
+    for (int k = 0; k < nfb; ++k) inputs.push_back({fbs[k], 12 * pixels});
+    for (const Input &in : {Input{b.albedo_sum, 12 * pixels}, Input{b.normal_sum, 12 * pixels}, Input{b.depth_sum, 4 * pixels}, Input{b.hit_count, 4 * pixels}})
+        inputs.push_back(in);
+    for (const Input &in : inputs) {
+        if (overlap(d_out, 12 * pixels, in.ptr, in.bytes)) return fail(RT_ERR_INVALID_ARG, w + ": d_out overlaps an input");
+        if (overlap(d_workspace, need, in.ptr, in.bytes)) return fail(RT_ERR_INVALID_ARG, w + ": the workspace overlaps an input");
+    }
+    if (overlap(d_out, 12 * pixels, d_workspace, need)) return fail(RT_ERR_INVALID_ARG, w + ": d_out overlaps the workspace");
+    return RT_OK;
+}
+
+// rt_denoise's launches on one beauty frame
+rt_status denoise_enqueue(const float *d_fb_sum, const rt_aov_buffers &b, int32_t width, int32_t height, int32_t samples_per_pixel, const rt_denoise_params &prm,
+                          void *d_workspace, float *d_out, hipStream_t stream) {
+    const Launch l(width, height, d_workspace);
+    const Inputs in = {d_fb_sum, b.albedo_sum, b.normal_sum, b.depth_sum, b.hit_count};
+    const float inv = (float)(1.0 / (double)samples_per_pixel);
+    const float spp = (float)samples_per_pixel;
+    rt_status st;
+    hipLaunchKernelGGL(denoise_prepass, l.grid, l.block, 0, stream, l.im, in, inv, spp, l.lv[0], l.nz, l.dg, prm.iterations == 0 ? d_out : nullptr);
+    if ((st = launched("denoise_prepass")) != RT_OK || prm.iterations == 0) return st;
+    hipLaunchKernelGGL(denoise_moments, l.grid, l.block, 0, stream, l.im, l.lv[0], l.nz, l.dg, l.lv[1]);
+    if ((st = launched("denoise_moments")) != RT_OK) return st;
+    return enqueue_steps(l, prm, d_fb_sum, spp, d_out, nullptr, stream);
+}
+
 }  // namespace rtdn
 
 extern "C" {
@@ -629,46 +685,39 @@ uint64_t rt_denoise_workspace_bytes(int32_t width, int32_t height) {
 
 rt_status rt_denoise(const float *d_fb_sum, const rt_aov_buffers *aov, int32_t width, int32_t height, int32_t samples_per_pixel,
                      const rt_denoise_params *params, void *d_workspace, uint64_t workspace_bytes, float *d_out, void *hip_stream) {
-    using rtdn::fail;
-    if (!d_fb_sum || !aov || !d_workspace || !d_out) return fail(RT_ERR_INVALID_ARG, "rt_denoise: null argument");
-    // rt_aov_buffers grows: fields past struct_bytes count as NULL
+    const float *fbs[1] = {d_fb_sum};
     rt_aov_buffers b;
-    rt_aov_buffers_init(&b);
-    const uint32_t ab = aov->struct_bytes < sizeof(b) ? aov->struct_bytes : (uint32_t)sizeof(b);
-    memcpy(&b, aov, ab);
-    if (ab < offsetof(rt_aov_buffers, hit_count) + sizeof(b.hit_count) || !b.albedo_sum || !b.normal_sum || !b.depth_sum || !b.hit_count)
-        return fail(RT_ERR_INVALID_ARG, "rt_denoise: albedo_sum, normal_sum, depth_sum and hit_count are required");
-    if (width < 1 || height < 1) return fail(RT_ERR_INVALID_ARG, "rt_denoise: width and height must be at least 1");
-    if (samples_per_pixel < 1 || samples_per_pixel > 65536)
-        return fail(RT_ERR_INVALID_ARG, "rt_denoise: samples_per_pixel outside 1 … 65536");
     rt_denoise_params prm;
-    rt_status st = rtdn::read_params("rt_denoise", params, prm);
+    const rt_status st = rtdn::denoise_checks("rt_denoise", fbs, 1, aov, width, height, samples_per_pixel, params, d_workspace, workspace_bytes,
+                                              rt_denoise_workspace_bytes(width, height), d_out, b, prm);
     if (st != RT_OK) return st;
-    const uint64_t pixels = (uint64_t)width * (uint64_t)height;
-    if (pixels > (1ull << 24)) return fail(RT_ERR_UNSUPPORTED, "rt_denoise: more than 2^24 pixels");
-    const uint64_t need = rt_denoise_workspace_bytes(width, height);
-    if (workspace_bytes < need)
-        return fail(RT_ERR_INVALID_ARG, "rt_denoise: workspace_bytes below rt_denoise_workspace_bytes (" + std::to_string(need) + ")");
-    const struct { const void *ptr; uint64_t bytes; } inputs[] = {
-        {d_fb_sum, 12 * pixels}, {b.albedo_sum, 12 * pixels}, {b.normal_sum, 12 * pixels}, {b.depth_sum, 4 * pixels}, {b.hit_count, 4 * pixels}};
-    for (const auto &in : inputs) {
-        if (rtdn::overlap(d_out, 12 * pixels, in.ptr, in.bytes)) return fail(RT_ERR_INVALID_ARG, "rt_denoise: d_out overlaps an input");
-        if (rtdn::overlap(d_workspace, need, in.ptr, in.bytes)) return fail(RT_ERR_INVALID_ARG, "rt_denoise: the workspace overlaps an input");
-    }
-    if (rtdn::overlap(d_out, 12 * pixels, d_workspace, need)) return fail(RT_ERR_INVALID_ARG, "rt_denoise: d_out overlaps the workspace");
+    return rtdn::denoise_enqueue(d_fb_sum, b, width, height, samples_per_pixel, prm, d_workspace, d_out, (hipStream_t)hip_stream);
+}
 
-    // ---- enqueue -------------------------------------------------------------------------------------------------------------
+uint64_t rt_denoise_split_workspace_bytes(int32_t width, int32_t height) {
+    if (width < 1 || height < 1) return 0;
+    return rt_denoise_workspace_bytes(width, height) + (uint64_t)width * (uint64_t)height * 12;
+}
+
+rt_status rt_denoise_split(const float *d_direct_sum, const float *d_indirect_sum, const rt_aov_buffers *aov, int32_t width, int32_t height,
+                           int32_t samples_per_pixel, const rt_denoise_params *params, void *d_workspace, uint64_t workspace_bytes, float *d_out,
+                           void *hip_stream) {
+    if (!d_direct_sum || !d_indirect_sum) return rtdn::fail(RT_ERR_INVALID_ARG, "rt_denoise_split: null argument");
+    const float *fbs[2] = {d_direct_sum, d_indirect_sum};
+    rt_aov_buffers b;
+    rt_denoise_params prm;
+    rt_status st = rtdn::denoise_checks("rt_denoise_split", fbs, 2, aov, width, height, samples_per_pixel, params, d_workspace, workspace_bytes,
+                                        rt_denoise_split_workspace_bytes(width, height), d_out, b, prm);
+    if (st != RT_OK) return st;
+    // rt_denoise's launches on each component — the direct one into the frame behind rt_denoise's planes, the indirect one into d_out — then the add
     const hipStream_t stream = (hipStream_t)hip_stream;
     const rtdn::Launch l(width, height, d_workspace);
-    const rtdn::Inputs in = {d_fb_sum, b.albedo_sum, b.normal_sum, b.depth_sum, b.hit_count};
-    const float inv = (float)(1.0 / (double)samples_per_pixel);
-    const float spp = (float)samples_per_pixel;
-    using rtdn::launched;
-    hipLaunchKernelGGL(rtdn::denoise_prepass, l.grid, l.block, 0, stream, l.im, in, inv, spp, l.lv[0], l.nz, l.dg, prm.iterations == 0 ? d_out : nullptr);
-    if ((st = launched("denoise_prepass")) != RT_OK || prm.iterations == 0) return st;
-    hipLaunchKernelGGL(rtdn::denoise_moments, l.grid, l.block, 0, stream, l.im, l.lv[0], l.nz, l.dg, l.lv[1]);
-    if ((st = launched("denoise_moments")) != RT_OK) return st;
-    return rtdn::enqueue_steps(l, prm, d_fb_sum, spp, d_out, nullptr, stream);
+    float *first = (float *)(l.dg + (uint64_t)width * (uint64_t)height);
+    if ((st = rtdn::denoise_enqueue(d_direct_sum, b, width, height, samples_per_pixel, prm, d_workspace, first, stream)) != RT_OK) return st;
+    if ((st = rtdn::denoise_enqueue(d_indirect_sum, b, width, height, samples_per_pixel, prm, d_workspace, d_out, stream)) != RT_OK) return st;
+    const uint64_t floats = (uint64_t)width * (uint64_t)height * 3;
+    hipLaunchKernelGGL(rtdn::denoise_add, dim3((uint32_t)((floats + 255) / 256)), dim3(256), 0, stream, (const float *)first, d_out, (uint32_t)floats);
+    return rtdn::launched("denoise_add");
 }
 
 rt_status rt_denoise_spp(const float *d_fb_sum, const int32_t *d_spp, const float *d_moments, const rt_aov_buffers *aov, int32_t aov_samples,

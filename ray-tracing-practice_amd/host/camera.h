@@ -168,6 +168,9 @@ struct FrameJob {
     // with medium, --fog-denoise: each frame also filtered under rt_render_aov_volume's AOVs — by rt_denoise, or with noise by
     // rt_denoise_spp with the frame's counts and moments and AOVs at noise->min_spp — to "<frame file>.denoised"
     bool fog_denoise = false;
+    // with lit alone (no noise, no medium), --split: through rt_render_lit_split — "<frame file>.direct" and "<frame file>.indirect" in the frame's
+    // own format, the frame from their float32 sum, and with denoise "<frame file>.denoised" from rt_denoise_split
+    bool split = false;
     const rt_chroma_params *chroma = nullptr;      // with medium, --fog-tint: the lit frames through rt_render_chroma, with or without the volume
     const rt_glow_params *glow = nullptr;          // with medium, without chroma, --fog-glow: through rt_render_glow, with or without the volume
     const rt_volume *heat = nullptr;               // the grid of glow's source 2 (--fog-heat)

@@ -55,6 +55,7 @@ bool threshold_alone(const std::string &value, float &out) {
 struct Pass {
     std::map<std::string, int> at;          // element → its last index; "--denoise*": the last element that begins with --denoise
     std::string denoise_word, env_dash_word;          // that element; the last element that begins with --env-
+    std::string fog_word;                             // the last element that begins with --fog
     std::string glow_bad, tint_bad, fog_noise_bad, fog_adaptive_bad, noise_bad, fog_bad, env_bad;
     bool nee_bad = false, lens_bad = false, adaptive_spp_bad = false;
     bool glow_by_density = false, adaptive_valued = false, shard_valued = false;
@@ -96,6 +97,7 @@ void read_values(int argc, const char *const *argv, const char *rtp_devices, Cli
             p.denoise_word = arg;
         }
         if (arg.compare(0, 6, "--env-") == 0) p.env_dash_word = arg;
+        if (arg.compare(0, 5, "--fog") == 0) p.fog_word = arg;
         if (arg == "--stop-rule") p.stop_word = value;
         if (arg == "--fog-grid") p.grid_file = value;
         if (arg == "--fog-heat") p.heat_file = value;
@@ -238,6 +240,7 @@ void read_values(int argc, const char *const *argv, const char *rtp_devices, Cli
     cli.noise = p.has("--noise-target");
     cli.lens = p.has("--lens");
     cli.motion_blur = p.has("--motion-blur");
+    cli.split = p.has("--split");
     cli.stop_rule = p.stop_word == "near" ? 1 : 0;
     cli.fog_glow_source = p.has("--fog-heat") ? 2 : (p.glow_by_density ? 1 : 0);
 }
@@ -263,6 +266,14 @@ bool parse_cli(int argc, const char *const *argv, const char *rtp_devices, Cli &
     std::string other;
 
     // ---- the refusals, in order: the first that applies is the answer ----
+    // --split (first, so that every refusal of a command line with it names it)
+    if (c.split && !c.lit) return refuse(99, "--split writes the direct and the indirect light of --lit frames: it needs --lit");
+    if (c.split && !p.fog_word.empty()) return refuse(99, "--split cannot be combined with " + p.fog_word + ": the fog calls have no split");
+    other = p.last_of({"--noise-target", "--noise-spp", "--adaptive", "--adaptive-spp", "--devices", "--shard", "--denoise-temporal", "--denoise-adaptive",
+                       "--denoise-adaptive-temporal", "--stop-rule", "--stop-history"});
+    if (c.split && (!other.empty() || env_devices))
+        return refuse(99, "--split cannot be combined with " + (other.empty() ? std::string("RTP_DEVICES") : other) +
+                              " (not with --noise-target, --adaptive, --devices, --shard, RTP_DEVICES or the temporal and adaptive denoise flags)");
     // --fog-denoise (before the flags it excludes, so that the refusal names it)
     if (c.fog_denoise && !c.fog) return refuse(99, "--fog-denoise filters fogged frames: it needs --lit --fog SIGMA");
     other = p.last_of({"--denoise*", "--aov", "--adaptive", "--devices", "--shard"});

@@ -12,6 +12,8 @@
 //   --glossy                                    with --nee, --env (mis, light) or --lit: METAL's reflect branch takes light samples too
 //   --lit                                       rt_render_lit: --nee, --env, --lens and --motion-blur in any combination, and with it only
 //   --lit --noise-target T [--noise-spp min:batch:max]                          rt_render_lit_adaptive
+//   --lit --split                               rt_render_lit_split: "<frame file>.direct" and "<frame file>.indirect" beside the frame, which is
+//                                               saved from their sum; with --denoise, "<frame file>.denoised" from rt_denoise_split
 //   --denoise-adaptive | --denoise-adaptive-temporal [--stop-history], --stop-rule own|near    with --adaptive or --lit --noise-target:
 //                                               rt_denoise_spp | rt_denoise_temporal_spp [its history as the prior]; the stopping rule
 //   --lit --fog SIGMA[:ALBEDO[:G]] [--fog-ball cx,cy,cz,r | --fog-box x0,y0,z0,x1,y1,z1]       rt_render_medium
@@ -51,6 +53,7 @@ struct Cli {
     bool stop_history = false, lit = false, glossy = false, light_tree = false, nee = false, env = false;
     bool fog = false, fog_denoise = false, fog_tint = false, fog_glow = false, fog_glow_sample = false, fog_noise = false, fog_adaptive = false, noise = false;
     bool lens = false, motion_blur = false;
+    bool split = false;                                     // --split (with --lit only)
 
     int stop_rule = 0;                                      // --stop-rule: 0 own (default), 1 near
     // --fog SIGMA[:ALBEDO[:G]], --fog-ball / --fog-box (read when fog)

@@ -123,6 +123,7 @@ int render_lens(const rtp::SceneParams &params, const rt_scene_desc &desc, const
         job.glow_sample = cli.fog_glow_sample ? &glow_sample : nullptr;
         job.sampler = sampler;
         job.fog_adaptive = cli.fog_adaptive ? &fog_adaptive : nullptr;
+        job.split = cli.split;
     } else if (cli.env) {
         job.env = env;
         job.env_params = &ep;

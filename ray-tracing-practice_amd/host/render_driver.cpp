@@ -365,9 +365,24 @@ void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const
     float *d_fb = nullptr, *d_denoised = nullptr;
     uint8_t *d_rgb = nullptr;
     void *d_workspace = nullptr;
-    const uint64_t workspace_bytes = denoise ? rt_denoise_workspace_bytes(params.width, params.height) : 0;
+    const bool split = job.split && lit && !noise && !medium;
+    const uint64_t workspace_bytes = !denoise ? 0 : split ? rt_denoise_split_workspace_bytes(params.width, params.height) : rt_denoise_workspace_bytes(params.width, params.height);
     RTP_CHECK(rt_device_alloc(num_pixels * 3 * sizeof(float), reinterpret_cast<void **>(&d_fb)));
     RTP_CHECK(rt_device_alloc(num_pixels * 3, reinterpret_cast<void **>(&d_rgb)));
+    // --split: the two components on the device, and on the host for their files and their sum
+    float *d_direct = nullptr, *d_indirect = nullptr;
+    std::vector<float> h_direct, h_indirect;
+    if (split) {
+        RTP_CHECK(rt_device_alloc(num_pixels * 3 * sizeof(float), reinterpret_cast<void **>(&d_direct)));
+        RTP_CHECK(rt_device_alloc(num_pixels * 3 * sizeof(float), reinterpret_cast<void **>(&d_indirect)));
+        h_direct.resize(num_pixels * 3);
+        h_indirect.resize(num_pixels * 3);
+    }
+    auto save_sums = [&](const std::string &path, const float *sums) {          // the frame's own saver code and divisor
+        BinarySaver out(params.sqrt_spp, path);
+        out.set_format(params.width, params.height);
+        for (size_t p = 0; p < num_pixels; ++p) out.write_color(Vec3(sums[3 * p], sums[3 * p + 1], sums[3 * p + 2]));
+    };
     int32_t *d_spp = nullptr;
     std::vector<int32_t> h_spp;
     if (lit && noise) {
@@ -447,6 +462,9 @@ void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const
             else
                 RTP_CHECK(rt_render_lit_adaptive_rule(scene, &cam, &lit_now, noise, job.stop, nullptr, 0, d_fb, d_spp,
                                                       spp_denoiser ? spp_denoiser->d_moments : nullptr, nullptr, 1, nullptr));
+        } else if (split) {
+            const rt_lit_params lit_now = frame_lit(cam_close);
+            RTP_CHECK(rt_render_lit_split(scene, &cam, &lit_now, nullptr, 0, d_direct, d_indirect, nullptr, 1, nullptr));
         } else if (lit) {
             const rt_lit_params lit_now = frame_lit(cam_close);
             if (medium && job.chroma) RTP_CHECK(rt_render_chroma(scene, &cam, &lit_now, medium, volume, job.chroma, nullptr, 0, d_fb, nullptr, 1, nullptr));
@@ -459,7 +477,14 @@ void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const
         } else if (env) RTP_CHECK(rt_render_env(scene, &cam, env, job.env_params, nullptr, 0, d_fb, nullptr, 1, nullptr));
         else if (nee) RTP_CHECK(rt_render_nee(scene, &cam, nee, nullptr, 0, d_fb, nullptr, 1, nullptr));
         else RTP_CHECK(rt_render_lens(scene, &cam, cam_close, &lens, nullptr, 0, d_fb, nullptr, 1, nullptr));
-        if (d_spp) {
+        if (split) {          // the components' files; the frame from their sum, one float32 add per channel
+            RTP_CHECK(rt_copy_to_host(h_direct.data(), d_direct, num_pixels * 3 * sizeof(float)));
+            RTP_CHECK(rt_copy_to_host(h_indirect.data(), d_indirect, num_pixels * 3 * sizeof(float)));
+            save_sums(filename + ".direct", h_direct.data());
+            save_sums(filename + ".indirect", h_indirect.data());
+            for (size_t k = 0; k < num_pixels * 3; ++k) h_direct[k] = h_direct[k] + h_indirect[k];
+            save_sums(filename, h_direct.data());
+        } else if (d_spp) {
             RTP_CHECK(rt_tonemap_spp(d_fb, d_spp, d_rgb, static_cast<int64_t>(num_pixels), nullptr));
             RTP_CHECK(rt_copy_to_host(h_spp.data(), d_spp, num_pixels * sizeof(int32_t)));
             total_rays = 0;
@@ -467,9 +492,11 @@ void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const
         } else {
             RTP_CHECK(rt_tonemap(d_fb, d_rgb, static_cast<int64_t>(num_pixels) * 3, params.sqrt_spp, nullptr));
         }
-        RTP_CHECK(rt_copy_to_host(file.rgb.data(), d_rgb, num_pixels * 3));
-        file.path = filename;
-        write_binary_frame(file);
+        if (!split) {
+            RTP_CHECK(rt_copy_to_host(file.rgb.data(), d_rgb, num_pixels * 3));
+            file.path = filename;
+            write_binary_frame(file);
+        }
         const auto t1 = std::chrono::steady_clock::now();
         const float ms = std::chrono::duration<float, std::milli>(t1 - t0).count();
         std::cout << n << "\t" << ms << "\t" << total_rays << "\n";
@@ -506,8 +533,12 @@ void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const
                 }
             }
             if (denoise) {
-                RTP_CHECK(rt_denoise(d_fb, &aov_bufs, params.width, params.height, cam.samples_per_pixel, nullptr, d_workspace, workspace_bytes,
-                                     d_denoised, nullptr));
+                if (split)
+                    RTP_CHECK(rt_denoise_split(d_direct, d_indirect, &aov_bufs, params.width, params.height, cam.samples_per_pixel, nullptr, d_workspace,
+                                               workspace_bytes, d_denoised, nullptr));
+                else
+                    RTP_CHECK(rt_denoise(d_fb, &aov_bufs, params.width, params.height, cam.samples_per_pixel, nullptr, d_workspace, workspace_bytes,
+                                         d_denoised, nullptr));
                 RTP_CHECK(rt_copy_to_host(h_denoised.data(), d_denoised, num_pixels * 3 * sizeof(float)));
                 BinarySaver out(params.sqrt_spp, filename + ".denoised");
                 out.set_format(params.width, params.height);
@@ -515,6 +546,8 @@ void gpu_render_lens(const SceneParams &params, const rt_scene_desc &desc, const
             }
         }
     }
+    rt_device_free(d_direct);
+    rt_device_free(d_indirect);
     rt_device_free(d_fb);
     rt_device_free(d_rgb);
     rt_device_free(d_spp);

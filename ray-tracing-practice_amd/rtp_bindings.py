@@ -738,6 +738,10 @@ _AMD_LATER = {
     "rt_trace_samples_glow_sampled": (_STATUS, [_VP, _CAM, _LIT, _MEDIUM, _VP, _GLOW, _VP, _GLOW_SAMPLE, _VP, _I32] + [_VP] * 11),
     "rt_fog_params_init": (None, [_FOG]),
     "rt_render_fog_adaptive": (_STATUS, [_VP, _CAM, _LIT, _FOG, _ADAPTIVE, _STOP, _VP, _SHARD, _I32, _VP, _VP, _VP, *_OUT]),
+    "rt_render_lit_split": (_STATUS, [_VP, _CAM, _LIT, _SHARD, _I32, _VP, _VP, *_OUT]),
+    "rt_trace_samples_lit_split": (_STATUS, [_VP, _CAM, _LIT, _I32] + [_VP] * 7),
+    "rt_denoise_split_workspace_bytes": (_U64, [_I32, _I32]),
+    "rt_denoise_split": (_STATUS, [_VP, _VP, _AOV, _I32, _I32, _I32, _DENOISE, _VP, _U64, _VP, _VP]),
 }
 # the calls that take a prior: their _rule call (the judgement: the call itself) and, last, the device address of the prior
 for _base, _prior in (("rt_render_adaptive_rule", "rt_render_adaptive_prior"), ("rt_render_lit_adaptive_rule", "rt_render_lit_adaptive_prior"),
@@ -948,6 +952,25 @@ def denoise(d_fb, aov_ptrs, width, height, spp, d_out, stream=None, workspace=No
                           C.c_void_p(stream or 0)), "rt_denoise")
 
 
+def denoise_split(d_direct, d_indirect, aov_ptrs, width, height, spp, d_out, stream=None, workspace=None, **params):
+    """rt_denoise_split on device addresses: d_direct and d_indirect as DeviceScene.render_lit_split wrote them, the rest as denoise()
+    takes it.  workspace: None (the module's shared one of that size), or (address, bytes) of at least rt_denoise_split_workspace_bytes.
+    Only enqueues on `stream`.  params: rt_denoise_params fields."""
+    lib = amd_lib()
+    b = _aov_struct(aov_ptrs)
+    p = denoise_params(**params)
+    if workspace is None:
+        need = lib.rt_denoise_split_workspace_bytes(width, height)
+        workspace = _denoise_workspaces.get(("split", need))
+        if workspace is None:
+            d = C.c_void_p()
+            _check(lib.rt_device_alloc(need, C.byref(d)), "rt_device_alloc")
+            workspace = _denoise_workspaces[("split", need)] = (d.value, need)
+    ws_ptr, ws_bytes = workspace
+    _check(lib.rt_denoise_split(C.c_void_p(d_direct), C.c_void_p(d_indirect), C.byref(b), width, height, spp, C.byref(p), C.c_void_p(ws_ptr), ws_bytes,
+                                C.c_void_p(d_out), C.c_void_p(stream or 0)), "rt_denoise_split")
+
+
 def _aov_struct(aov_ptrs):
     b = AovBuffers()
     for key, field, _, _ in AOV_CHANNELS:
@@ -1110,6 +1133,20 @@ def denoise_to_host(fb_sum, aov, spp, **params):
         d_out = dev.alloc(fb.nbytes)
         denoise(dev.upload(fb), dev.upload_aov(aov, AOV_CHANNELS[:4]), width, height, spp, d_out, **params)
         return dev.download(d_out, np.empty_like(fb))
+
+
+def denoise_split_to_host(direct_sum, indirect_sum, aov, spp, **params):
+    """rt_denoise_split of host arrays: direct_sum and indirect_sum (H, W, 3) float32 as DeviceScene.render_lit_split_to_host returns them,
+    aov the dict of DeviceScene.render_aov_to_host.  Returns the (H, W, 3) float32 output.  Synchronous (default stream)."""
+    a = np.ascontiguousarray(direct_sum, dtype=np.float32)
+    b = np.ascontiguousarray(indirect_sum, dtype=np.float32)
+    assert a.shape == b.shape, (a.shape, b.shape)
+    height, width = a.shape[:2]
+    with _DeviceBuffers() as dev:
+        d_out = dev.alloc(a.nbytes)
+        need = amd_lib().rt_denoise_split_workspace_bytes(width, height)
+        denoise_split(dev.upload(a), dev.upload(b), dev.upload_aov(aov, AOV_CHANNELS[:4]), width, height, spp, d_out, workspace=(dev.alloc(need), need), **params)
+        return dev.download(d_out, np.empty_like(a))
 
 
 def denoise_spp_to_host(fb_sum, spp, moments, aov, aov_spp, **params):
@@ -1487,6 +1524,33 @@ class DeviceScene:
         """rt_render_lit through a fresh device buffer: (rows, width, 3) float32 sums and the rt_timing."""
         return _frame_to_host(cam, shard, lambda d: self.render_lit(cam, d, cam_close=cam_close, lens=lens, emitters=emitters, nee=nee, env=env, env_params=env_params, shard=shard,
                                                                     sample_first=sample_first))
+
+    def render_lit_split(self, cam, d_direct_ptr, d_indirect_ptr, *, cam_close=None, lens=None, emitters=True, nee=None, env=None, env_params=None,
+                         shard=None, stream=None, sync=True, sample_first=0):
+        """rt_render_lit_split: rt_render_lit's frame as its direct and its indirect light, each 3 floats per pixel at an integer device
+        address (render_lit's keywords).  Returns the rt_timing of this call."""
+        lit = lit_params(cam_close=cam_close, lens=lens, emitters=emitters, nee=nee, env=env, env_params=env_params)
+        return self._call("rt_render_lit_split", C.byref(cam), C.byref(lit), _ref(shard), sample_first, C.c_void_p(d_direct_ptr), C.c_void_p(d_indirect_ptr),
+                          *_stream_sync(stream, sync))
+
+    def render_lit_split_to_host(self, cam, *, cam_close=None, lens=None, emitters=True, nee=None, env=None, env_params=None, shard=None, sample_first=0):
+        """rt_render_lit_split through fresh device buffers: (direct, indirect) (rows, width, 3) float32 sums each, and the rt_timing."""
+        indirect = np.empty((amd_lib().rt_shard_rows(cam.image_height, _ref(shard)), cam.image_width, 3), dtype=np.float32)
+        with _DeviceBuffers() as dev:
+            d2 = dev.alloc(indirect.nbytes)
+            direct, t = _frame_to_host(cam, shard, lambda d: self.render_lit_split(cam, d, d2, cam_close=cam_close, lens=lens, emitters=emitters, nee=nee, env=env,
+                                                                                   env_params=env_params, shard=shard, sample_first=sample_first))
+            dev.download(d2, indirect)
+        return direct, indirect, t
+
+    def trace_samples_lit_split(self, cam, ijs, *, cam_close=None, lens=None, emitters=True, nee=None, env=None, env_params=None):
+        """rt_trace_samples_lit_split: ijs (n, 3) → (direct (n, 3), indirect (n, 3), rays (n,), final seeds (n,), final emitter-stream seeds
+        (n,), final environment-stream seeds (n,))."""
+        ijs, n, out = _probe(ijs, _RGB, _RGB, _COUNT, _SEED, _SEED, _SEED)
+        lit = lit_params(cam_close=cam_close, lens=lens, emitters=emitters, nee=nee, env=env, env_params=env_params)
+        _check(amd_lib().rt_trace_samples_lit_split(self._h, C.byref(cam), C.byref(lit), n, ijs.ctypes.data, *(a.ctypes.data for a in out)),
+               "rt_trace_samples_lit_split")
+        return out
 
     def render_lit_adaptive(self, cam, d_fb_ptr, d_spp_ptr, d_moments_ptr=None, *, cam_close=None, lens=None, emitters=True, nee=None, env=None,
                             env_params=None, shard=None, stream=None, sync=True, sample_first=0, prior=None, **params):
