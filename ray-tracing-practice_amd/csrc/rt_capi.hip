@@ -4474,6 +4474,220 @@ rt_status rt_debug_fog_rays(int32_t routine, const rt_medium_params *medium, con
     return RT_OK;
 }
 
+// Developer hook (not part of the ABI header): the light-sampling routines on the caller's vertices, one vertex per lane, for the
+// vertex-by-vertex check against the CPU restatements (tests/dev_light_vertex_checks.py, tests/light_vertex_cases.py).  The
+// kernel calls the inline functions the render kernels call — light_sample, light_emitted, light_miss, nee_pick, tree_pick, tree_pmf,
+// emit_find / nee_find, gloss_pg, PbPhase — on the light the lit calls would hand their kernels, and writes 16 words per vertex:
+//   0  light_sample on the emitter table, under the call's Pb     ok, dir (3), c (3), code, seed after
+//   1  light_sample on the environment, under the call's Pb       ok, dir (3), c (3), seed after
+//   2  light_emitted of the ray (o = x, d = v) that found         the bool carry's (3), the float carry's with carry = n[0] (3);
+//      primitive code `seed` at closest = s                       emitted going in is beta * a
+//   3  light_miss of the environment, direction v                 depth 0 and 1 with the bool carry (3 + 3), depth 1 and 0 with the float
+//                                                                 carry n[0] (3 + 3)
+//   4  the picks alone                                            nee_pick(u = s); on a tree: tree_pick's entry, its p, seed after,
+//                                                                 tree_pmf(e = (int)n[0], x); emit_find / nee_find of code / sphere `seed`
+//   5  the two densities                                          gloss_pg(w = x, r = v, fuzz = s), PbPhase{ud = n, g = s}(w = x)
+// A refused sample writes ok = 0, zeros and the seed after; the words a routine does not name are 0.  Pb: 0 PbDiffuse, 1 PbGlossy{r = v,
+// fuzz = s}, 2 PbPhase{ud = n, g = s} (with n = ud, as the medium vertex passes it).
+extern "C++" {
+namespace rtk {
+struct LightVertices {
+    int32_t routine, n;
+    const float *x, *nv, *v, *s;
+    const uint32_t *seed;
+    f3 a, beta;
+    uint32_t *out;
+};
+template <int kPb> struct PbOf;
+template <> struct PbOf<0> {
+    __device__ static PbDiffuse make(f3, f3, float) { return PbDiffuse{}; }
+};
+template <> struct PbOf<1> {
+    __device__ static PbGlossy make(f3, f3 v, float s) { return gloss_pb(v, s); }
+};
+template <> struct PbOf<2> {
+    __device__ static PbPhase make(f3 nv, f3, float s) {
+        PbPhase p;
+        p.ud = nv;
+        p.g = s;
+        return p;
+    }
+};
+__device__ __forceinline__ void put3(uint32_t *w, f3 c) {
+    w[0] = __float_as_uint(c.x);
+    w[1] = __float_as_uint(c.y);
+    w[2] = __float_as_uint(c.z);
+}
+template <class Light, int kPb>
+__global__ void __launch_bounds__(256) light_vertices_kernel(const KParams P, const Light T, const LightVertices A) {
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= A.n) return;
+    const f3 x = ld3(A.x + 3 * g), nv = ld3(A.nv + 3 * g), v = ld3(A.v + 3 * g);
+    const float s = A.s[g];
+    const uint32_t seed = A.seed[g];
+    uint32_t w[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) w[k] = 0;
+    if (A.routine == 0 || A.routine == 1) {
+        uint32_t ls = seed;
+        f3 dir = mk(0, 0, 0), c = mk(0, 0, 0);
+        int32_t code = 0;
+        if (light_sample(P, T, ls, x, nv, A.a, A.beta, PbOf<kPb>::make(nv, v, s), dir, c, code)) {
+            w[0] = 1;
+            put3(w + 1, dir);
+            put3(w + 4, c);
+            if (A.routine == 0) w[7] = (uint32_t)code;
+        }
+        w[A.routine == 0 ? 8 : 7] = ls;
+    }
+    if constexpr (kPb == 0) {
+        if (A.routine == 2 || A.routine == 3) {
+            Lane L;
+            L.o = x;
+            L.d = v;
+            L.closest = s;
+            L.hit = A.routine == 2 ? (int32_t)seed : -1;
+            L.beta = A.beta;
+            L.color = mk(0, 0, 0);
+            L.seed = 0;
+            L.depth = 0;
+            const float carry = nv.x;
+            if (A.routine == 2) {
+                const f3 emitted = mul(A.beta, A.a);
+                put3(w + 0, light_emitted(P, T, L, L.hit >> 1, (L.hit & 1) != 0, true, emitted));
+                put3(w + 3, light_emitted(P, T, L, L.hit >> 1, (L.hit & 1) != 0, carry, emitted));
+            } else {
+                put3(w + 0, light_miss(P, T, L, true));
+                put3(w + 9, light_miss(P, T, L, carry));
+                L.depth = 1;
+                put3(w + 3, light_miss(P, T, L, true));
+                put3(w + 6, light_miss(P, T, L, carry));
+            }
+        }
+        if constexpr (kEmitterTable<Light>) {
+            if (A.routine == 4) {
+                const auto &B = emitter_base(T);
+                w[0] = (uint32_t)nee_pick(B, s);
+                if constexpr (std::is_same_v<Light, TreeTable> || std::is_same_v<Light, TreeEmitTable>) {
+                    uint32_t ls = seed;
+                    float p;
+                    w[1] = (uint32_t)tree_pick(T.L, ls, x, p);
+                    w[2] = __float_as_uint(p);
+                    w[3] = ls;
+                    w[4] = __float_as_uint(tree_pmf(T.L, (int32_t)nv.x, x));
+                }
+                if constexpr (std::is_same_v<std::decay_t<decltype(B)>, NeeTable>) w[5] = (uint32_t)nee_find(B, (int32_t)seed);
+                else w[5] = (uint32_t)emit_find(B, (int32_t)seed);
+            }
+        }
+        if (A.routine == 5) {
+            w[0] = __float_as_uint(gloss_pg(x, v, s));
+            PbPhase ph;
+            ph.ud = nv;
+            ph.g = s;
+            w[1] = __float_as_uint(ph(x));
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 16; ++k) A.out[16 * (size_t)g + k] = w[k];
+}
+}  // namespace rtk
+template <class Light>
+void launch_light_vertices(const rtk::KParams &P, const Light &T, const rtk::LightVertices &A, int32_t pb) {
+    const dim3 grid((A.n + 255) / 256), block(256);
+    if (pb == 1) hipLaunchKernelGGL((rtk::light_vertices_kernel<Light, 1>), grid, block, 0, 0, P, T, A);
+    else if (pb == 2) hipLaunchKernelGGL((rtk::light_vertices_kernel<Light, 2>), grid, block, 0, 0, P, T, A);
+    else hipLaunchKernelGGL((rtk::light_vertices_kernel<Light, 0>), grid, block, 0, 0, P, T, A);
+}
+}  // extern "C++"
+// rt_debug_light_vertices: routine 0 … 5 (above) under Pb kind pb over n vertices (x, nv, v: 3 floats each; s and seed: one each; all host
+// arrays) → out, 16 words per vertex (a host array).  ab: the call's albedo a and throughput beta (6 floats).  The scene, the emitter
+// parameters, the environment (routines 1 and 3; else it may be null) and its parameters are the public objects, converted as the render
+// calls convert them: nee_setup and env_setup's checks, with_emitter_table's choice of table, env_dev_of, and the KParams fill_params
+// makes of the scene and the camera (the background and max_depth).  What a routine uses as an index is checked here, before any launch:
+// routine 2's code must name a primitive of the scene, routine 4's entry (int)n[0] an entry of the tree's table.  pb = 1 is refused when
+// the light's glossy switch is off (no call runs PbGlossy then); routines 2 … 5 take pb = 0
+rt_status rt_debug_light_vertices(rt_scene *sc, const rt_camera_data *cam, const rt_nee_params *nee, const rt_env *env, const rt_env_params *env_params,
+                                  int32_t routine, int32_t pb, int32_t n, const float *x, const float *nv, const float *v, const float *s,
+                                  const uint32_t *seed, const float *ab, uint32_t *out) {
+    const std::string w("rt_debug_light_vertices");
+    if (routine < 0 || routine > 5) return fail(RT_ERR_INVALID_ARG, w + ": unknown routine " + std::to_string(routine));
+    if (pb < 0 || pb > 2 || (routine > 1 && pb != 0)) return fail(RT_ERR_INVALID_ARG, w + ": pb must be 0, 1 or 2, and 0 for the routines 2 to 5");
+    if (n <= 0 || !x || !nv || !v || !s || !seed || !ab || !out) return fail(RT_ERR_INVALID_ARG, w + ": null argument or n <= 0");
+    NeeSetup N;
+    if (const rt_status st = nee_setup("rt_debug_light_vertices", nee, N)) return st;
+    rt_env_params np;
+    if (const rt_status st = env_setup("rt_debug_light_vertices", env_params, np)) return st;
+    const bool sky = routine == 1 || routine == 3;
+    if (sky && !env) return fail(RT_ERR_INVALID_ARG, w + ": this routine needs an environment");
+    if (pb == 1 && !(sky ? np.glossy : N.glossy)) return fail(RT_ERR_INVALID_ARG, w + ": pb = 1 needs the light's glossy switch");
+    for (int k = 0; k < 6; ++k)
+        if (!std::isfinite(ab[k])) return fail(RT_ERR_INVALID_ARG, w + ": a or beta is not finite");
+    rtk::KParams P;
+    if (const rt_status st = fill_params(sc, cam, nullptr, P)) return st;
+    if (const rt_status st = check_device(sc)) return st;
+    if (sky && env->device != sc->device) return fail(RT_ERR_INVALID_ARG, w + ": the environment was created on another device than the scene");
+    for (int32_t k = 0; k < n; ++k) {
+        for (int c = 0; c < 3; ++c)
+            if (!(std::isfinite(x[3 * k + c]) && std::isfinite(nv[3 * k + c]) && std::isfinite(v[3 * k + c]) && std::isfinite(s[k])))
+                return fail(RT_ERR_INVALID_ARG, w + ": a vertex is not finite");
+        if (routine == 2) {
+            const int32_t code = (int32_t)seed[k];
+            if (code < 0 || (code >> 1) >= ((code & 1) ? sc->num_planes : sc->num_spheres))
+                return fail(RT_ERR_INVALID_ARG, w + ": a code names no primitive of the scene");
+        }
+    }
+    rtk::LightVertices A{};
+    A.routine = routine;
+    A.n = n;
+    A.a = rtk::mk(ab[0], ab[1], ab[2]);
+    A.beta = rtk::mk(ab[3], ab[4], ab[5]);
+    float *d_x = nullptr, *d_n = nullptr, *d_v = nullptr, *d_s = nullptr;
+    uint32_t *d_seed = nullptr, *d_out = nullptr;
+    Scratch mem;
+    const size_t n3 = (size_t)n * 12, n1 = (size_t)n * 4, n16 = (size_t)n * 64;
+    if (mem.alloc(d_x, n3) != hipSuccess || mem.alloc(d_n, n3) != hipSuccess || mem.alloc(d_v, n3) != hipSuccess || mem.alloc(d_s, n1) != hipSuccess ||
+        mem.alloc(d_seed, n1) != hipSuccess || mem.alloc(d_out, n16) != hipSuccess)
+        return fail(RT_ERR_OUT_OF_MEMORY, "hipMalloc failed");
+    HIP_TRY(hipMemcpy(d_x, x, n3, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_n, nv, n3, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_v, v, n3, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_s, s, n1, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_seed, seed, n1, hipMemcpyHostToDevice));
+    A.x = d_x;
+    A.nv = d_n;
+    A.v = d_v;
+    A.s = d_s;
+    A.seed = d_seed;
+    A.out = d_out;
+    rt_status st = RT_OK;
+    if (sky) {
+        launch_light_vertices(P, env_dev_of(env, np), A, pb);
+    } else {
+        st = with_emitter_table(sc, N, true, [&](const auto &T) {
+            using Table = std::decay_t<decltype(T)>;
+            constexpr bool tree = std::is_same_v<Table, rtk::TreeTable> || std::is_same_v<Table, rtk::TreeEmitTable>;
+            int32_t count;
+            if constexpr (tree) count = T.N.count;
+            else count = T.count;
+            if ((routine == 0 || routine == 2) && count <= 0) return fail(RT_ERR_INVALID_ARG, w + ": the emitter table is empty (light_on is false: no call samples it)");
+            if constexpr (tree) {
+                if (routine == 4)
+                    for (int32_t k = 0; k < n; ++k) {
+                        if (!(nv[3 * k] >= 0.0f && nv[3 * k] < (float)count)) return fail(RT_ERR_INVALID_ARG, w + ": tree_pmf's entry is outside the table");
+                    }
+            }
+            launch_light_vertices(P, T, A, pb);
+            return RT_OK;
+        });
+    }
+    if (st != RT_OK) return st;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, d_out, n16, hipMemcpyDeviceToHost));
+    return RT_OK;
+}
+
 #endif      // RTP_DEV_BUILD
 
 rt_status rt_last_kernel_ms(rt_scene *sc, float *ms) {

@@ -526,6 +526,22 @@ int32_t emit_table(const rt_scene_desc *sc, int32_t sample_planes, int32_t *kind
     return n;
 }
 
+/* per vertex (tests/light_vertex_cases.py): the table's pick at u[k] — the smallest e with u < cdf[e], the table's length when there is
+ * none — and the entry of primitive code[k], -1 when the table does not hold it.  two_kind: code is 2 * index + kind (the two-kind table's
+ * emit_find); else it is a sphere's index (the sphere-only table's nee_find) */
+void emit_vertex_picks(const rt_scene_desc *sc, int32_t sample_planes, int32_t two_kind, int64_t count, const float *u, const int32_t *code, int32_t *entry,
+                       int32_t *found) {
+    emit_tab T;
+    make_tab(sc, 1, 1, sample_planes, &T);
+    for (int64_t k = 0; k < count; ++k) {
+        int32_t e = 0;
+        while (e < T.count && !(u[k] < T.cdf[e])) ++e;
+        entry[k] = e;
+        found[k] = two_kind ? tab_find(&T, code[k] & 1, code[k] >> 1) : tab_find(&T, 0, code[k]);
+    }
+    free_tab(&T);
+}
+
 /* where the pinhole camera ray of count samples first lands: the primitive's kind (0 sphere, 1 plane, -1 nothing), its index and the point */
 void emit_first_hit(const rt_scene_desc *sc, const rt_camera_data *cam, int64_t count, const int32_t *ijs, int32_t *kind, int32_t *index, float *point) {
     for (int64_t k = 0; k < count; ++k) {

@@ -508,6 +508,53 @@ void medium_intervals(const rt_medium_params *m, int64_t count, const float *o, 
     }
 }
 
+/* per vertex (tests/light_vertex_cases.py): gloss_vertices' words for a medium vertex — the light sample under pb = ph about
+ * ud = nv with g = s, without a hemisphere.  routine 0: the emitter table's, 1: the environment's, 5: ph itself in the direction w = x
+ * (word 1: word 0 is gloss_vertices').  flags (may be NULL) takes TL_OK, TL_NO_ENTRY and TL_FELL: the sample functions here keep no note */
+void medium_vertices(const rt_scene_desc *sc, const rt_camera_data *cam, const gloss_cfg *cfg, int32_t routine, int64_t count, const float *x, const float *nv,
+                     const float *s, const uint32_t *seed, const float *ab, uint32_t *out, uint32_t *flags) {
+    emit_tab T;
+    sky_map M;
+    light_tree t;
+    gloss_ctx G;
+    make_gloss_ctx(sc, cam, cfg, &T, &M, &t, 0, &G);
+    const lit_ctx *X = &G.Y.X;
+    const v3 a = V(ab[0], ab[1], ab[2]), beta = V(ab[3], ab[4], ab[5]);
+    memset(out, 0, (size_t)count * 64);
+    for (int64_t k = 0; k < count; ++k) {
+        const v3 xk = V(x[3 * k], x[3 * k + 1], x[3 * k + 2]), ud = V(nv[3 * k], nv[3 * k + 1], nv[3 * k + 2]);
+        uint32_t *w = out + 16 * k;
+        vtx_note note = {0u, 0.0f, 0.0f};
+        vtx_note *N = flags ? &note : NULL;
+        if (routine == 0 || (routine == 1 && X->M)) {
+            uint32_t st = seed[k];
+            v3 dir, c;
+            int ok;
+            int32_t e = 0;
+            if (routine == 0) {
+                float pmf;
+                e = vertex_pick(&G, &st, xk, &pmf, N);
+                ok = e < T.count && med_entry_sample(sc, &T, e, pmf, &st, xk, a, beta, s[k], ud, &dir, &c);
+            } else {
+                ok = med_sky_sample(X->M, X->cfg->ep, &st, a, beta, s[k], ud, &dir, &c, 0);
+            }
+            if (ok) {
+                w[0] = 1;
+                put3(w + 1, dir, N);
+                put3(w + 4, c, N);
+                if (routine == 0) w[7] = (uint32_t)(2 * T.index[e] + T.kind[e]);
+                if (N) N->flags |= TL_OK;
+            }
+            w[routine == 0 ? 8 : 7] = st;
+        } else if (routine == 5) {
+            w[1] = word_of(med_pb(s[k], ud, xk));
+        }
+        if (flags) flags[k] = note.flags;
+    }
+    free_tree(&t);
+    free_ctx(&cfg->base.base, &T, &M);
+}
+
 /* count samples (ijs: i, j, s) → radiance, rays, medium events, how each path ended, and the four final RNG states (seed, nee, env, med);
  * stats (MST_COUNT words, may be NULL): the tallies named above, summed over the samples */
 void medium_trace_stats(const rt_scene_desc *sc, const rt_camera_data *cam, const medium_cfg *cfg, int64_t count, const int32_t *ijs, float *radiance,

@@ -482,6 +482,30 @@ int64_t tree_pick_counts(const rt_scene_desc *sc, int32_t sample_planes, const f
     return bad;
 }
 
+/* per vertex (tests/light_vertex_cases.py): tree_pick from x[k] on the stream that starts at seed[k] → its entry, its p and the stream's
+ * state after it; tree_pmf of entry e_in[k] from the same x; fell[k] (may be NULL): bit 0 the descent, bit 1 the path product took a
+ * node's q for the importances; pl_root[k] (may be NULL): the root's left probability from x, 1 for a tree of one leaf — what the
+ * descent's first draw is compared with */
+void tree_vertex_picks(const rt_scene_desc *sc, int32_t sample_planes, int64_t count, const float *x, const uint32_t *seed, const int32_t *e_in,
+                       int32_t *entry, float *p, uint32_t *seed_after, float *pmf, int32_t *fell, float *pl_root) {
+    emit_tab T;
+    light_tree t;
+    make_tab(sc, 1, 1, sample_planes, &T);
+    make_tree(sc, &T, &t);
+    for (int64_t k = 0; k < count && t.entries > 0; ++k) {
+        const v3 X = V(x[3 * k], x[3 * k + 1], x[3 * k + 2]);
+        uint32_t st = seed[k];
+        int fa = 0, fb = 0;
+        entry[k] = tree_pick(&t, &st, X, &p[k], fell ? &fa : NULL);
+        seed_after[k] = st;
+        pmf[k] = tree_pmf(&t, e_in[k], X, fell ? &fb : NULL);
+        if (fell) fell[k] = fa | (fb << 1);
+        if (pl_root) pl_root[k] = t.entry[0] < 0 ? left_probability(&t, 0, X, NULL) : 1.0f;
+    }
+    free_tree(&t);
+    free_tab(&T);
+}
+
 static void make_tree_ctx(const rt_scene_desc *sc, const rt_camera_data *cam, const tree_cfg *cfg, emit_tab *T, sky_map *M, light_tree *t, int linear, tree_ctx *Y) {
     make_ctx(sc, cam, &cfg->base, T, M, linear, &Y->X);
     make_tree(sc, T, t);

@@ -27,6 +27,8 @@ def lib():
     l.emit_frame.argtypes = [desc, cam, cfg, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     l.emit_table.restype = C.c_int32
     l.emit_table.argtypes = [desc, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    l.emit_vertex_picks.restype = None
+    l.emit_vertex_picks.argtypes = [desc, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     l.emit_first_hit.restype = None
     l.emit_first_hit.argtypes = [desc, cam, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     return l
@@ -51,6 +53,17 @@ def first_hit(host, cam, ijs):
     kind, idx, pt = np.empty(m, np.int32), np.empty(m, np.int32), np.zeros((m, 3), np.float32)
     lib().emit_first_hit(C.byref(host.desc), C.byref(cam), m, ijs.ctypes.data, kind.ctypes.data, idx.ctypes.data, pt.ctypes.data)
     return kind, idx, pt
+
+
+def vertex_picks(host, u, code, planes=1):
+    """Per vertex: the table's pick at u (the table's length: none) and the entry of primitive `code`, -1 when the table does not hold it.
+    On the two-kind table (sample_planes = 1 and a plane in it) code is 2 * index + kind, else a sphere's index → (entry, found)."""
+    u, code = np.ascontiguousarray(u, dtype=np.float32).ravel(), np.ascontiguousarray(code, dtype=np.int32).ravel()
+    assert len(u) == len(code)
+    two_kind = 1 if planes and (table(host, planes)[0] == 1).any() else 0
+    entry, found = np.zeros(len(u), np.int32), np.zeros(len(u), np.int32)
+    lib().emit_vertex_picks(C.byref(host.desc), planes, two_kind, len(u), u.ctypes.data, code.ctypes.data, entry.ctypes.data, found.ctypes.data)
+    return entry, found
 
 
 def _cfg(cam_close, lens, emitters, nee_mis, planes, rgb, env_params):

@@ -29,6 +29,8 @@ def lib():
     l.gloss_lobe_draws.argtypes = [C.c_int64, C.c_void_p, C.c_float, C.c_uint32, C.c_void_p]
     l.gloss_trace.restype = None
     l.gloss_trace.argtypes = [desc, cam, cfg, C.c_int64] + [C.c_void_p] * 6 + [C.c_int32, C.c_void_p]
+    l.gloss_vertices.restype = None
+    l.gloss_vertices.argtypes = [desc, cam, cfg, C.c_int32, C.c_int32, C.c_int64] + [C.c_void_p] * 9
     l.gloss_frame.restype = None
     l.gloss_frame.argtypes = [desc, cam, cfg, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
     return l
@@ -49,6 +51,34 @@ def lobe_draws(r, fuzz, count, seed):
     out = np.empty(count, np.float64)
     lib().gloss_lobe_draws(count, r.ctypes.data, fuzz, seed, out.ctypes.data)
     return out
+
+
+# gloss_ref.c's per-vertex tallies (the TL_ bits, in its order)
+TALLIES = ("cone refused: inside", "om == 0", "hemisphere refused", "pb == 0 refused", "fallback taken", "triangle folded", "no entry", "pl^2 overflows",
+           "plane refused: cos_l < 1e-8", "plane refused: the point is the vertex", "ellipse loop >= 4 rounds", "ok", "found: weighted", "found: pl == 0",
+           "found: not a table entry", "basis: wn.z == +-0", "basis: wn.x == wn.y == 0", "om == 2^-24", "found: carry off", "a NaN in c", "triangle: ua + ub == 1")
+
+
+def vertex_arrays(x, nv, v, s, seed, ab):
+    """The per-vertex inputs as the C side and the developer hook take them: (m, 3) float32 three times, (m,) float32, (m,) uint32, (6,)."""
+    x, nv, v = (np.ascontiguousarray(q, dtype=np.float32).reshape(-1, 3) for q in (x, nv, v))
+    s, seed = np.ascontiguousarray(s, dtype=np.float32).ravel(), np.ascontiguousarray(seed, dtype=np.uint32).ravel()
+    ab = np.ascontiguousarray(ab, dtype=np.float32).ravel()
+    assert len(x) == len(nv) == len(v) == len(s) == len(seed) and ab.shape == (6,)
+    return x, nv, v, s, seed, ab
+
+
+def vertices(host, cam, routine, pb_kind, x, nv, v, s, seed, ab, glossy=1, glossy_env=1, select=0, nee_mis=1, planes=0, rgb=None, env_params=None,
+             tallies=True, densities=False):
+    """gloss_vertices: routine 0, 1, 2, 3 or 5 of rt_debug_light_vertices under Pb kind 0 or 1 on the CPU → (m, 16) uint32, the TL_ bits of
+    each vertex (zeros with tallies=False: the C side is then handed no place to count) and, with densities=True, (pl, pb) of each weight."""
+    c, keep = _cfg(glossy, glossy_env, select, None, None, True, nee_mis, planes, rgb, env_params)
+    x, nv, v, s, seed, ab = vertex_arrays(x, nv, v, s, seed, ab)
+    m = len(x)
+    out, flags, plpb = np.zeros((m, 16), np.uint32), np.zeros(m, np.uint32), np.zeros((m, 2), np.float32)
+    lib().gloss_vertices(C.byref(host.desc), C.byref(cam), C.byref(c), routine, pb_kind, m, x.ctypes.data, nv.ctypes.data, v.ctypes.data, s.ctypes.data,
+                         seed.ctypes.data, ab.ctypes.data, out.ctypes.data, flags.ctypes.data if tallies else None, plpb.ctypes.data if densities else None)
+    return (out, flags, plpb) if densities else (out, flags)
 
 
 def _cfg(glossy, glossy_env, select, cam_close, lens, emitters, nee_mis, planes, rgb, env_params):

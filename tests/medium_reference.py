@@ -32,6 +32,8 @@ def lib():
     l.medium_cos_draws.argtypes = [C.c_int64, C.c_float, C.c_uint32, C.c_void_p]
     l.medium_intervals.restype = None
     l.medium_intervals.argtypes = [C.POINTER(rb.MediumParams), C.c_int64] + [C.c_void_p] * 6
+    l.medium_vertices.restype = None
+    l.medium_vertices.argtypes = [desc, cam, C.POINTER(glr.GlossCfg), C.c_int32, C.c_int64] + [C.c_void_p] * 7
     l.medium_trace.restype = None
     l.medium_trace.argtypes = [desc, cam, cfg, C.c_int64] + [C.c_void_p] * 6 + [C.c_int32]
     l.medium_trace_stats.restype = None
@@ -90,6 +92,18 @@ def intervals(medium, o, d, t_end):
     hit, t0, t1 = np.empty(o.shape[0], np.int32), np.empty(o.shape[0], np.float32), np.empty(o.shape[0], np.float32)
     lib().medium_intervals(C.byref(m), o.shape[0], o.ctypes.data, d.ctypes.data, t_end.ctypes.data, hit.ctypes.data, t0.ctypes.data, t1.ctypes.data)
     return hit, t0, t1
+
+
+def vertices(host, cam, routine, x, nv, s, seed, ab, select=0, nee_mis=1, planes=0, rgb=None, env_params=None, tallies=True):
+    """medium_vertices: routine 0, 1 or 5 of rt_debug_light_vertices under Pb kind 2 — ph about ud = nv with g = s, no hemisphere — on the
+    CPU → (m, 16) uint32 and gloss_reference.TALLIES' bits of each vertex (ok, no entry, fallback taken; zeros with tallies=False)."""
+    c, keep = glr._cfg(0, 0, select, None, None, True, nee_mis, planes, rgb, env_params)
+    x, nv, _, s, seed, ab = glr.vertex_arrays(x, nv, nv, s, seed, ab)
+    m = len(x)
+    out, flags = np.zeros((m, 16), np.uint32), np.zeros(m, np.uint32)
+    lib().medium_vertices(C.byref(host.desc), C.byref(cam), C.byref(c), routine, m, x.ctypes.data, nv.ctypes.data, s.ctypes.data, seed.ctypes.data,
+                          ab.ctypes.data, out.ctypes.data, flags.ctypes.data if tallies else None)
+    return out, flags
 
 
 def _cfg(medium, glossy, glossy_env, select, cam_close, lens, emitters, nee_mis, planes, rgb, env_params):

@@ -30,6 +30,8 @@ def lib():
     l.tree_pmf_points.argtypes = [desc, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]
     l.tree_pick_counts.restype = C.c_int64
     l.tree_pick_counts.argtypes = [desc, C.c_int32, C.c_void_p, C.c_int64, C.c_uint32, C.c_void_p]
+    l.tree_vertex_picks.restype = None
+    l.tree_vertex_picks.argtypes = [desc, C.c_int32, C.c_int64] + [C.c_void_p] * 9
     l.tree_trace.restype = None
     l.tree_trace.argtypes = [desc, cam, cfg, C.c_int64] + [C.c_void_p] * 6 + [C.c_int32, C.c_void_p]
     l.tree_frame.restype = None
@@ -63,6 +65,20 @@ def pick_counts(host, point, draws, seed, planes=0):
     counts = np.zeros(len(emr.table(host, planes)[0]), np.int64)
     bad = lib().tree_pick_counts(C.byref(host.desc), planes, point.ctypes.data, draws, seed, counts.ctypes.data)
     return counts, bad
+
+
+def vertex_picks(host, x, seed, e_in, planes=0, root=False):
+    """Per vertex: tree_pick from x on the stream that starts at seed, and tree_pmf of entry e_in from the same x →
+    (entry, p, seed after, pmf, fell: bit 0 the descent's, bit 1 the product's fallback); root=True adds the root's left probability."""
+    x = np.ascontiguousarray(x, dtype=np.float32).reshape(-1, 3)
+    seed, e_in = np.ascontiguousarray(seed, dtype=np.uint32).ravel(), np.ascontiguousarray(e_in, dtype=np.int32).ravel()
+    m = len(x)
+    assert len(seed) == len(e_in) == m and (e_in >= 0).all() and (e_in < max(1, len(emr.table(host, planes)[0]))).all()
+    entry, p, after = np.zeros(m, np.int32), np.zeros(m, np.float32), np.zeros(m, np.uint32)
+    pmf_, fell, pl = np.zeros(m, np.float32), np.zeros(m, np.int32), np.zeros(m, np.float32)
+    lib().tree_vertex_picks(C.byref(host.desc), planes, m, x.ctypes.data, seed.ctypes.data, e_in.ctypes.data, entry.ctypes.data, p.ctypes.data,
+                            after.ctypes.data, pmf_.ctypes.data, fell.ctypes.data, pl.ctypes.data if root else None)
+    return (entry, p, after, pmf_, fell) + ((pl,) if root else ())
 
 
 def _cfg(select, cam_close, lens, emitters, nee_mis, planes, rgb, env_params):
